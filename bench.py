@@ -10,7 +10,7 @@ a complete forward + backward with its own state) and the forward checks its sta
 (--sync-mode); `config.ms_per_view_one_stream` is the strictly serial figure, `config.ms_per_view_strict_one_stream` the same in the
 library's default status mode (strict), i.e. what a drop-in caller that renders one view at a time sees.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU, rank r renders view r of the same Gaussians (weak scaling) and the
@@ -37,6 +37,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together, .npy headers included, stay under 64 MB
 
 WORKLOADS = {
     # name: (P, W, H, sh_degree)
@@ -149,7 +150,16 @@ def main():
     ap.add_argument("--sync-mode", default="lazy", choices=["lazy", "strict"],
                     help="lazy: forward's status word is checked one step late (no host sync in the step); "
                          "strict: one blocking status read per forward, like the reference")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller -- the rasterizer's outputs "
+                         "(out_<name>.npy) and the leaves' .grad (grad_<name>.npy) -- under DIR, as float32 / float64 (integer "
+                         "outputs as float64), %d bytes at most in all: an array larger than its share is replaced by a seeded "
+                         "sample of its flattened elements (the same indices in every run with the same arguments).  The inputs are "
+                         "seeded, so two builds can be compared output for output; the gradients are sums of float atomics and "
+                         "differ in their last bits from run to run" % DUMP_BUDGET_BYTES)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or os.environ.get("DGR_BENCH_SPAWN") == "1"):
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, RCCL rendezvous on
@@ -251,6 +261,25 @@ def main():
     # the fused all-reduce span is found through the gradients (the batch's per-view means2D gradient is not part of it)
     arena = GradientArena([means3D, shs, opac, scales, rots] if Vb else params) if dist is not None else None
     group_i = [0]
+    # --dump-outputs keeps in last_outs the outputs of the last timed step (record[0] = 1 while it runs) or, with --graph, of
+    # each captured call (record[0] = 2: only a call being captured keeps them, so nothing a warm-up call allocated is released
+    # inside a capture).  Without the option record[0] stays 0 and every tensor lives exactly as long as it did before.
+    record = [0]
+    last_outs = [None]
+    out_names = (("color", "radii", "depth", "uncertainty") if args.variant == "full" else
+                 ("color", "radii", "depth", "depth_median", "depth_var", "opacity_map", "gau_uncertainty", "gau_related_pixels"))
+
+    def keep(outs):
+        if record[0] == 1 or torch.cuda.is_current_stream_capturing():
+            last_outs[0] = outs
+
+    def returned():
+        """What the step issued last handed its caller: the rasterizer's outputs and the leaves' gradients."""
+        r = {"out_" + k: v for k, v in zip(out_names, last_outs[0])}
+        leaves = {"means3D": means3D, "means2D": means2D, "shs": shs, "opacities": opac, "scales": scales, "rotations": rots,
+                  "viewmatrix": views_b if Vb else view}
+        r.update({"grad_" + k: v.grad for k, v in leaves.items() if v.grad is not None})
+        return r
 
     pending = [None]
     G = max(1, args.views_per_allreduce)
@@ -259,8 +288,10 @@ def main():
     def step_batch():
         for p_ in params + [views_b]:
             p_.grad = None
-        color, radii, depth, median, var, alpha, unc, px = rast_b(
-            means3D, means2D, opac, shs=shs, scales=scales, rotations=rots, viewmatrices=views_b, gt_depths=gts_b)
+        outs = rast_b(means3D, means2D, opac, shs=shs, scales=scales, rotations=rots, viewmatrices=views_b, gt_depths=gts_b)
+        if record[0]:
+            keep(outs)
+        color, radii, depth, median, var, alpha, unc, px = outs
         torch.autograd.backward([color, depth, median, var], [gCb, gDb, gMb, gVb])
         if arena is not None:  # one fused RCCL all-reduce of the batch's summed per-Gaussian gradients
             arena.all_reduce(dist)
@@ -278,6 +309,8 @@ def main():
         group_i[0] += 1
         outs = rast(means3D=means3D, means2D=means2D, opacities=opac, shs=shs, scales=scales, rotations=rots,
                     viewmatrix=view, gt_depth=gt)
+        if record[0]:
+            keep(outs)
         if args.variant == "full":
             color, radii, depth, unc = outs
             torch.autograd.backward([color, depth, unc], [gC, gD, gV])
@@ -322,13 +355,15 @@ def main():
 
     captured = []
 
-    def run(n):
+    def run(n, keep_last=0):
         r = None
         if captured:
             for i in range(n):
                 r = captured[i % len(captured)].replay()
             return r[0] if isinstance(r, tuple) else radii
         for i in range(n):
+            if i == n - 1:
+                record[0] = keep_last
             if views is None:
                 r = step()
             else:
@@ -368,7 +403,12 @@ def main():
         # (no dispatch-packet events inside a capture: nothing can be bracketed live in a replayed graph, and events on
         #  EVERY launch of a captured stream -- `profile_every` = 1 below 32 steps -- crash this ROCm's capture)
         _capi.profile_select("")
-        captured.extend(CapturedStep(step, stream=torch.cuda.Stream(device=dev)) for _ in range(K))
+        record[0] = 2 if args.dump_outputs else 0
+        for _ in range(K):
+            captured.append(CapturedStep(step, stream=torch.cuda.Stream(device=dev)))
+            if record[0]:  # this graph's own tensors, rewritten by each of its replays
+                captured[-1].returned, last_outs[0] = returned(), None
+        record[0] = 0
     # one view at a time, for reference (short, untimed by the contract)
     serial_ms = None
     strict_serial_ms = None
@@ -401,18 +441,22 @@ def main():
     barrier()
     _capi.profile_read(dominant)  # discard the events of the untimed passes
     t0 = time.perf_counter()
-    radii = run(args.steps)
+    radii = run(args.steps, keep_last=1 if args.dump_outputs else 0)
     t_issue = time.perf_counter() - t0
     light.check_async_errors()  # status words of every timed step (lazy mode): raises if any forward was invalid
     t_check = time.perf_counter() - t0
     drain()  # the last view's gradient sum completes inside the timed region
     barrier()
     elapsed = time.perf_counter() - t0
+    record[0] = 0
     if os.environ.get("DGR_BENCH_TRACE") == "1" and rank == 0:
         print(f"[trace] host issue of {args.steps} steps done at {t_issue * 1e3:.3f} ms, status checks at {t_check * 1e3:.3f} ms, "
               f"GPU idle at {elapsed * 1e3:.3f} ms", file=sys.stderr)
     dom_tot, dom_n = _capi.profile_read(dominant)
     _capi.profile_select("")
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before anything else runs a step: the last timed step's tensors as it left them)
+        dumped = dump_outputs(args.dump_outputs, captured[(args.steps - 1) % len(captured)].returned if captured else returned())
 
     if dist is not None:
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -569,6 +613,8 @@ def main():
                          "launches_under_overlap": dom_n, "measured_in_timed_region": live},
             "roofline_valu": roofline_valu,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if not args.no_cpu_baseline and world == 1:  # (the CPU baseline: rank 0 at N = 1 only)
             # Beside the headline (eager: every step goes through the autograd surface on the host): the same K steps with
             # one captured view per stream replayed from hipGraphs -- what a fixed-shape SLAM loop can do.  Reported, never
@@ -641,6 +687,32 @@ def allreduce_model(payload_bytes, world, ms_per_collective_interval, alone_ms, 
             "blend_wgs_per_cu": blend_cap,
             "note": "ms_between_collectives is THIS run's measured interval (it already contains whatever the collective cost here); "
                     "an efficiency below ceiling_overlapped.direct means the collective's kernels were starved or serialised"}
+
+
+def dump_outputs(out_dir, tensors):
+    """Writes `tensors` (name -> tensor) as out_dir/<name>.npy: float32 / float64 as they are, anything else as float64 (exact
+    for the integer outputs).  DUMP_BUDGET_BYTES is shared out smallest array first; an array larger than its share is
+    written as a sample of its flattened elements at sorted flat indices drawn with seed 0 -- the same indices whenever the
+    same set of shapes is written.  Returns what was written, for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for k, v in tensors.items():
+        a = v.detach().cpu().numpy()
+        host[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    left, written = DUMP_BUDGET_BYTES, {}
+    for i, k in enumerate(sorted(host, key=lambda k_: (host[k_].nbytes, k_))):
+        a = host[k]
+        n = max(0, (left // (len(host) - i) - 256) // a.itemsize)  # (256 bytes for the .npy header)
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.size > n:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+            entry["sampled_elements"] = int(n)
+        path = os.path.join(out_dir, k + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+        written[k] = entry
+    return {"dir": out_dir, "bytes": DUMP_BUDGET_BYTES - left, "arrays": written}
 
 
 def graph_replay_line(args):

@@ -1,6 +1,7 @@
 import os, sys
 os.environ["DGR_SYNC_MODE"] = sys.argv[1]
-sys.path[:0] = ["/root/repo", "/root/repo/diff-gaussian-rasterization_amd", "/root/repo/tests"]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "diff-gaussian-rasterization_amd"), os.path.join(ROOT, "tests")]
 import torch, numpy as np
 from dgr_amd import light
 from dgr_amd.multiview import make_settings, ViewStreams

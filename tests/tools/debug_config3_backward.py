@@ -1,5 +1,6 @@
 import sys, os
-sys.path[:0] = ["/root/repo", "/root/repo/diff-gaussian-rasterization_amd", "/root/repo/tests"]
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "diff-gaussian-rasterization_amd"), os.path.join(ROOT, "tests")]
 import numpy as np
 from util import make_scene
 import hip_helpers as hh
