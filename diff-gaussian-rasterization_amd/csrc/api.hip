@@ -556,6 +556,97 @@ struct BatchJoinGuard {
     ~BatchJoinGuard() { if (armed) batch_join(main, K); }
 };
 
+// The body of dgr_light_forward_batch / dgr_full_forward_batch: cv[v] = view v's arguments as the one-view presized call takes
+// them (full: the uncertainty image in the out_alpha slot, as dgr_full_forward_presized passes it), bs[v] its state buffers.
+struct BatchViewState {
+    char* geometry_buffer;
+    char* binning_buffer;
+    int binning_capacity;
+    char* image_buffer;
+    int* status;
+};
+int forward_batch(hipStream_t st, int n_views, const FwdCommon* cv, const BatchViewState* bs, bool full) {
+    const int P = cv[0].P, width = cv[0].W, height = cv[0].H;
+    for (int v = 0; v < n_views; v++) {
+        const FwdCommon& w = cv[v];
+        if (!w.viewmatrix || !w.projmatrix || !w.cam_pos || !w.out_color || !w.out_depth || (full && !w.out_alpha)) {
+            g_last_error = "view without camera or outputs";
+            return DGR_ERR_BAD_ARGUMENT;
+        }
+        if (P > 0 && (!bs[v].geometry_buffer || !bs[v].image_buffer || !bs[v].binning_buffer || bs[v].binning_capacity < 0)) {
+            g_last_error = "view without state buffers";
+            return DGR_ERR_BAD_ARGUMENT;
+        }
+    }
+    int rc = check_common(cv[0]);
+    if (rc) return rc;
+    if (P == 0) {
+        for (int v = 0; v < n_views; v++) {
+            if (bs[v].status) HIP_TRY(hipMemsetAsync(bs[v].status, 0, 16, st));
+            if ((rc = zero_outputs(cv[v], st))) return rc;
+        }
+        return DGR_OK;
+    }
+    if ((rc = batch_streams_ready())) return rc;
+    dgr::GeometryView geom[DGR_MAX_BATCH_VIEWS];
+    dgr::ImageView img[DGR_MAX_BATCH_VIEWS];
+    dgr::BinningView bin[DGR_MAX_BATCH_VIEWS];
+    for (int v = 0; v < n_views; v++) {
+        geom[v] = dgr::carve_geometry(bs[v].geometry_buffer, P);
+        img[v] = dgr::carve_image(bs[v].image_buffer, width, height);
+        if (bs[v].status) img[v].status = bs[v].status;
+        bin[v] = dgr::carve_binning(bs[v].binning_buffer, (size_t)bs[v].binning_capacity);
+    }
+    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
+    // One preprocess launch for all views needs the segment binning behind it (its epilogue leaves per-block instance
+    // totals); frames whose segment tables do not fit LDS, or "lds_count" = 0, take the one-view front end per view.
+    const bool shared_front = g_lds_count.load() != 0 && dgr::segment_binning_fits(width, height);
+    if (shared_front) {
+        const FwdCommon& c = cv[0];
+        dgr::PreprocessFwdBatchArgs b{};
+        dgr::PreprocessFwdArgs& a = b.base;
+        a.P = P; a.D = c.D; a.M = c.M; a.W = width; a.H = height; a.grid_x = gx; a.grid_y = gy;
+        a.means3D = c.means3D; a.scales = c.scales; a.scale_modifier = c.scale_modifier; a.rotations = c.rotations;
+        a.opacities = c.opacities; a.shs = c.shs; a.cov3D_precomp = c.cov3D_precomp; a.colors_precomp = c.colors_precomp;
+        a.tan_fovx = c.tan_fovx; a.tan_fovy = c.tan_fovy;
+        a.focal_y = height / (2.0f * c.tan_fovy);  // rasterizer_impl.cu:228-229
+        a.focal_x = width / (2.0f * c.tan_fovx);
+        a.prefiltered = c.prefiltered;
+        a.tight_cull = opt_tight_cull();
+        a.sh_vec_ok = aligned16(c.shs);
+        b.V = n_views;
+        for (int v = 0; v < n_views; v++) {
+            b.v[v].view = cv[v].viewmatrix; b.v[v].proj = cv[v].projmatrix; b.v[v].campos = cv[v].cam_pos;
+            b.v[v].geom = geom[v]; b.v[v].radii_out = cv[v].radii; b.v[v].gau_uncertainty = cv[v].gau_uncertainty;
+            b.v[v].gau_related_pixels = cv[v].gau_related_pixels;
+        }
+        { ScopedStage t(ST_PRE_FWD, st); HIP_TRY(dgr::launch_preprocess_fwd_batch(b, st)); }
+    }
+    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
+    const int K = pipeline ? 2 : batch_stream_count(n_views);
+    if ((rc = batch_fork(st, K))) return rc;
+    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
+    for (int v = 0; v < n_views; v++) {
+        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
+        const int cap = bs[v].binning_capacity;
+        int mode = COUNT_LDS;
+        if (!shared_front) {
+            mode = presized_count_mode(width, height, cap);
+            if ((rc = forward_front(cv[v], geom[v], img[v], sv, &bin[v], cap, bs[v].image_buffer, mode))) return rc;
+        }
+        if ((rc = binning_stages(cv[v], geom[v], img[v], bin[v], cap, sv, mode, bs[v].binning_buffer))) return rc;
+        if (pipeline) {  // the blend of view v on the caller's stream, behind its binning on the helper stream
+            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
+            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
+            sv = st;
+        }
+        if (full) rc = forward_back_full(cv[v], cv[v].out_alpha, geom[v], img[v], bin[v], sv);
+        else rc = forward_back(cv[v], geom[v], img[v], bin[v], sv);
+        if (rc) return rc;
+    }
+    return joined.done();
+}
+
 // ---- state export (tests / profiling) ----
 enum ExportKind { EX_MEANS2D, EX_CONIC_OPACITY, EX_RGB, EX_CLAMPED, EX_TILES_TOUCHED, EX_KEYS };
 
@@ -982,85 +1073,36 @@ int dgr_light_forward_batch(void* stream, int n_views, const dgr_light_view* vie
                             const float* background, int width, int height, const float* means3D, const float* shs,
                             const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
                             const float* rotations, const float* cov3D_precomp, float tan_fovx, float tan_fovy, int prefiltered) {
-    hipStream_t st = (hipStream_t)stream;
     if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
     FwdCommon cv[DGR_MAX_BATCH_VIEWS];
+    BatchViewState bs[DGR_MAX_BATCH_VIEWS];
     for (int v = 0; v < n_views; v++) {
         const dgr_light_view& w = views[v];
         cv[v] = FwdCommon{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
                           cov3D_precomp, scale_modifier, w.viewmatrix, w.projmatrix, w.cam_pos, tan_fovx, tan_fovy, prefiltered,
                           w.out_color, w.out_depth, w.out_median_depth, w.out_alpha, w.gt_depth, w.out_depth_var,
                           w.gau_uncertainty, w.gau_related_pixels, w.radii};
-        if (!w.viewmatrix || !w.projmatrix || !w.cam_pos || !w.out_color || !w.out_depth) { g_last_error = "view without camera or outputs"; return DGR_ERR_BAD_ARGUMENT; }
-        if (P > 0 && (!w.geometry_buffer || !w.image_buffer || !w.binning_buffer || w.binning_capacity < 0)) {
-            g_last_error = "view without state buffers";
-            return DGR_ERR_BAD_ARGUMENT;
-        }
+        bs[v] = BatchViewState{w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer, w.status};
     }
-    int rc = check_common(cv[0]);
-    if (rc) return rc;
-    if (P == 0) {
-        for (int v = 0; v < n_views; v++) {
-            if (views[v].status) HIP_TRY(hipMemsetAsync(views[v].status, 0, 16, st));
-            if ((rc = zero_outputs(cv[v], st))) return rc;
-        }
-        return DGR_OK;
-    }
-    if ((rc = batch_streams_ready())) return rc;
-    dgr::GeometryView geom[DGR_MAX_BATCH_VIEWS];
-    dgr::ImageView img[DGR_MAX_BATCH_VIEWS];
-    dgr::BinningView bin[DGR_MAX_BATCH_VIEWS];
+    return forward_batch((hipStream_t)stream, n_views, cv, bs, false);
+}
+
+int dgr_full_forward_batch(void* stream, int n_views, const dgr_full_view* views, int P, int D, int M,
+                           const float* background, int width, int height, const float* means3D, const float* shs,
+                           const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                           const float* rotations, const float* cov3D_precomp, float tan_fovx, float tan_fovy, int prefiltered) {
+    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    FwdCommon cv[DGR_MAX_BATCH_VIEWS];
+    BatchViewState bs[DGR_MAX_BATCH_VIEWS];
     for (int v = 0; v < n_views; v++) {
-        geom[v] = dgr::carve_geometry(views[v].geometry_buffer, P);
-        img[v] = dgr::carve_image(views[v].image_buffer, width, height);
-        if (views[v].status) img[v].status = views[v].status;
-        bin[v] = dgr::carve_binning(views[v].binning_buffer, (size_t)views[v].binning_capacity);
+        const dgr_full_view& w = views[v];
+        // (as dgr_full_forward_presized: the uncertainty image in the alpha slot, no light-only outputs)
+        cv[v] = FwdCommon{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
+                          cov3D_precomp, scale_modifier, w.viewmatrix, w.projmatrix, w.cam_pos, tan_fovx, tan_fovy, prefiltered,
+                          w.out_color, w.out_depth, nullptr, w.out_uncertainty, w.gt_depth, nullptr, nullptr, nullptr, w.radii};
+        bs[v] = BatchViewState{w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer, w.status};
     }
-    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
-    // One preprocess launch for all views needs the segment binning behind it (its epilogue leaves per-block instance
-    // totals); frames whose segment tables do not fit LDS, or "lds_count" = 0, take the one-view front end per view.
-    const bool shared_front = g_lds_count.load() != 0 && dgr::segment_binning_fits(width, height);
-    if (shared_front) {
-        dgr::PreprocessFwdBatchArgs b{};
-        dgr::PreprocessFwdArgs& a = b.base;
-        a.P = P; a.D = D; a.M = M; a.W = width; a.H = height; a.grid_x = gx; a.grid_y = gy;
-        a.means3D = means3D; a.scales = scales; a.scale_modifier = scale_modifier; a.rotations = rotations;
-        a.opacities = opacities; a.shs = shs; a.cov3D_precomp = cov3D_precomp; a.colors_precomp = colors_precomp;
-        a.tan_fovx = tan_fovx; a.tan_fovy = tan_fovy;
-        a.focal_y = height / (2.0f * tan_fovy);  // rasterizer_impl.cu:228-229
-        a.focal_x = width / (2.0f * tan_fovx);
-        a.prefiltered = prefiltered;
-        a.tight_cull = opt_tight_cull();
-        a.sh_vec_ok = aligned16(shs);
-        b.V = n_views;
-        for (int v = 0; v < n_views; v++) {
-            b.v[v].view = views[v].viewmatrix; b.v[v].proj = views[v].projmatrix; b.v[v].campos = views[v].cam_pos;
-            b.v[v].geom = geom[v]; b.v[v].radii_out = views[v].radii; b.v[v].gau_uncertainty = views[v].gau_uncertainty;
-            b.v[v].gau_related_pixels = views[v].gau_related_pixels;
-        }
-        { ScopedStage t(ST_PRE_FWD, st); HIP_TRY(dgr::launch_preprocess_fwd_batch(b, st)); }
-    }
-    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
-    const int K = pipeline ? 2 : batch_stream_count(n_views);
-    if ((rc = batch_fork(st, K))) return rc;
-    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
-    for (int v = 0; v < n_views; v++) {
-        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
-        const int cap = views[v].binning_capacity;
-        int mode = COUNT_LDS;
-        if (!shared_front) {
-            mode = presized_count_mode(width, height, cap);
-            if ((rc = forward_front(cv[v], geom[v], img[v], sv, &bin[v], cap, views[v].image_buffer, mode))) return rc;
-        }
-        if ((rc = binning_stages(cv[v], geom[v], img[v], bin[v], cap, sv, mode, views[v].binning_buffer))) return rc;
-        if (pipeline) {  // the blend of view v on the caller's stream, behind its binning on the helper stream
-            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
-            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
-            sv = st;
-        }
-        if ((rc = forward_back(cv[v], geom[v], img[v], bin[v], sv))) return rc;
-    }
-    return joined.done();
+    return forward_batch((hipStream_t)stream, n_views, cv, bs, true);
 }
 
 int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
@@ -1143,6 +1185,92 @@ int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_gra
     b.focal_x = width / (2.0f * tan_fovx);
     b.sh_vec_ok = aligned16(shs) && aligned16(dL_dsh);
     b.track_off = track_off; b.map_off = map_off;
+    b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
+    b.dL_dscale = dL_dscale; b.dL_drot = dL_drot;
+    bb.V = n_views;
+    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st)); }
+    return DGR_OK;
+}
+
+int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                            const float* background, int width, int height, const float* means3D, const float* shs,
+                            const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                            const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                            float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot) {
+    (void)colors_precomp;
+    hipStream_t st = (hipStream_t)stream;
+    const bool det = opt_det_grads() != 0;  // (per view the scheme of dgr_full_backward)
+    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
+    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
+    for (int v = 0; v < n_views; v++)
+        if (!views[v].dL_dview) { g_last_error = "view without dL_dview"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P > 0 && !cov3D_precomp && (!scales || !rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P == 0) {  // F/rasterize_points.cu: nothing runs, gradients stay zero
+        for (int v = 0; v < n_views; v++) HIP_TRY(hipMemsetAsync(views[v].dL_dview, 0, 16 * 4, st));
+        return DGR_OK;
+    }
+    for (int v = 0; v < n_views; v++) {
+        const dgr_full_view_grad& w = views[v];
+        if (det && w.num_rendered <= 0) { g_last_error = "deterministic_grads: every view needs num_rendered (it sizes the view's row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
+        const size_t need = dgr_light_backward_scratch_bytes_r(P, width, height, w.num_rendered);
+        if (!w.scratch || w.scratch_bytes < need) { g_last_error = "backward scratch too small"; return DGR_ERR_BAD_ARGUMENT; }
+        // (the blend backward reads gt_depth on every path, the lean one included)
+        if (!w.geometry_buffer || !w.binning_buffer || !w.image_buffer || !w.viewmatrix || !w.projmatrix || !w.cam_pos ||
+            !w.perspec_matrix || !w.gt_depth || !w.dL_dpix || !w.dL_depths) {
+            g_last_error = "view with a missing state buffer, camera or gradient image";
+            return DGR_ERR_BAD_ARGUMENT;
+        }
+    }
+    int rc;
+    if ((rc = batch_streams_ready())) return rc;
+    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
+    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
+    const int K = pipeline ? 2 : batch_stream_count(n_views);
+    dgr::PreprocessBwdBatchArgs bb{};
+    if ((rc = batch_fork(st, K))) return rc;
+    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
+    for (int v = 0; v < n_views; v++) {
+        const dgr_full_view_grad& w = views[v];
+        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
+        dgr::GeometryView geom = dgr::carve_geometry(w.geometry_buffer, P);
+        dgr::ImageView img = dgr::carve_image(w.image_buffer, width, height);
+        dgr::BackwardScratch sc = dgr::carve_backward_scratch(w.scratch, P);
+        { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, sv)); }
+        DetScratch ds{nullptr, nullptr, nullptr, 0};
+        if (det) {
+            ds = carve_det_scratch(w.scratch, P, w.num_rendered);
+            { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(ds.rows, sizeof(float) * DGR_ACC_STRIDE * (size_t)w.num_rendered, sv)); }
+            HIP_TRY(dgr::launch_det_offsets(P, geom.rect, ds.blk, geom.goff, sv));
+        }
+        if (pipeline) {  // the blend backward of view v on the caller's stream, behind its cleared scratch
+            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
+            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
+            sv = st;
+        }
+        dgr::RenderBwdFullArgs r{};
+        r.W = width; r.H = height; r.grid_x = gx; r.grid_y = gy;
+        r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = (const uint32_t*)w.binning_buffer; r.rec = geom.rec; r.bg = background;
+        r.gt_depth = w.gt_depth; r.final_T = img.final_T; r.n_contrib = img.n_contrib; r.first_contrib = img.first_contrib;
+        r.dL_dpix = w.dL_dpix; r.dL_depths = w.dL_depths; r.dL_duncertainties = w.dL_duncertainties; r.acc = sc.acc;
+        if (det) { r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)w.num_rendered; }
+        { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), sv, det)); }
+        if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)w.num_rendered, sc.acc, sv));
+        dgr::BwdViewPart& q = bb.v[v];
+        q.det_pose = det ? ds.pose : nullptr;
+        q.view = w.viewmatrix; q.proj = w.projmatrix; q.campos = w.cam_pos; q.perspec = w.perspec_matrix;
+        q.radii = w.radii ? w.radii : geom.radii; q.geom = geom; q.acc = sc.acc; q.dL_dmean2D = w.dL_dmean2D;
+        q.pose_part = sc.pose_part; q.ticket = sc.ticket; q.dL_dview = w.dL_dview;
+    }
+    if ((rc = joined.done())) return rc;
+    dgr::PreprocessBwdArgs& b = bb.base;
+    b.P = P; b.D = D; b.M = M; b.W = width; b.H = height; b.means3D = means3D; b.shs = shs; b.scales = scales;
+    b.rotations = rotations; b.scale_modifier = scale_modifier; b.cov3D_precomp = cov3D_precomp;
+    b.tan_fovx = tan_fovx; b.tan_fovy = tan_fovy;
+    b.focal_y = height / (2.0f * tan_fovy);
+    b.focal_x = width / (2.0f * tan_fovx);
+    b.sh_vec_ok = aligned16(shs) && aligned16(dL_dsh);
+    b.track_off = 0; b.map_off = 0; b.full_variant = 1;
     b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
     b.dL_dscale = dL_dscale; b.dL_drot = dL_drot;
     bb.V = n_views;

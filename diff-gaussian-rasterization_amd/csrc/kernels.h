@@ -153,7 +153,8 @@ struct BwdViewPart {
     double* det_pose;     // deterministic gradients: this view's [blocks, 12] per-block pose partials (NULL otherwise; all views alike)
 };
 struct PreprocessBwdBatchArgs {
-    PreprocessBwdArgs base;  // the per-view members unused; the dense outputs receive the SUM over the views
+    PreprocessBwdArgs base;  // the per-view members unused; the dense outputs receive the SUM over the views; full_variant
+                             // selects the kernel instance (dL_dconic / dL_ddepth: not written by a batch)
     int V;
     BwdViewPart v[DGR_MAX_BATCH_VIEWS];
 };

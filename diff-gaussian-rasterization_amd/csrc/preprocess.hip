@@ -1154,7 +1154,9 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
 // contraction off, so -- for the same accumulator rows -- dL_dmeans3D / dL_dsh / dL_dopacity / dL_dcov3D are what accumulating
 // the one-view outputs view after view (autograd's `.grad +=`) gives, operation for operation, without the V dense 248-byte
 // rows per Gaussian that costs.
-// Pose gradients and dL_dmean2D (densification statistics) stay per view.  Light variant only.
+// Pose gradients and dL_dmean2D (densification statistics) stay per view.  FULL: the full variant's view terms
+// (bwd_view_terms(a, true, ...): the campos colour term and the depth-to-mean term), summed and written the same way; the
+// batch writes no dL_dconic / dL_ddepth (implementation outputs that no autograd surface returns).
 __device__ __forceinline__ PreprocessBwdArgs batch_view_args(const PreprocessBwdBatchArgs& b, int v) {
     PreprocessBwdArgs a = b.base;
     const BwdViewPart& p = b.v[v];
@@ -1162,6 +1164,7 @@ __device__ __forceinline__ PreprocessBwdArgs batch_view_args(const PreprocessBwd
     a.acc = const_cast<float*>(p.acc); a.dL_dmean2D = p.dL_dmean2D; a.pose_part = p.pose_part; a.ticket = p.ticket; a.dL_dview = p.dL_dview;
     return a;
 }
+template <bool FULL>
 __global__ void __launch_bounds__(256, DGR_BWD_BATCH_WAVES) preprocess_bwd_batch_kernel(PreprocessBwdBatchArgs b) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int P = b.base.P, V = b.V;
@@ -1223,7 +1226,7 @@ __global__ void __launch_bounds__(256, DGR_BWD_BATCH_WAVES) preprocess_bwd_batch
             }
             float3 dmean, dRGB;
             float dcov[6], coef[16];
-            bwd_view_terms(a, false, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
+            bwd_view_terms(a, FULL, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
             any_map |= vis && !a.map_off;
             dop_s += acc[9];
             dcol_s.x += acc[0]; dcol_s.y += acc[1]; dcol_s.z += acc[2];
@@ -1423,7 +1426,8 @@ hipError_t launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream)
 }
 hipError_t launch_preprocess_bwd_batch(const PreprocessBwdBatchArgs& b, hipStream_t stream) {
     if (b.base.P <= 0 || b.V <= 0) return hipSuccess;
-    launch(preprocess_bwd_batch_kernel, dim3((b.base.P + 255) / 256), dim3(256), stream, b);
+    if (b.base.full_variant) launch(preprocess_bwd_batch_kernel<true>, dim3((b.base.P + 255) / 256), dim3(256), stream, b);
+    else launch(preprocess_bwd_batch_kernel<false>, dim3((b.base.P + 255) / 256), dim3(256), stream, b);
     return hipGetLastError();
 }
 hipError_t launch_mark_visible(int P, const float* means, const float* view, uint8_t* present, hipStream_t stream) {

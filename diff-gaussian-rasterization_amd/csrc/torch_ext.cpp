@@ -957,6 +957,112 @@ std::vector<Tensor> light_backward_batch(const Tensor& background, const Tensor&
     return g;
 }
 
+// The full variant's batch (include/dgr_hip.h: dgr_full_forward_batch / _backward_batch; dgr_amd/batch_full.py), same contract.
+// Returns ([V,4] status, color [V,3,H,W], depth [V,1,H,W], uncertainty [V,1,H,W], radii [V,P], geom, binning, img) and the tickets.
+std::tuple<std::vector<Tensor>, std::vector<long>>
+full_forward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
+                   const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
+                   const Tensor& viewmatrices_, const Tensor& gt_depths_, const Tensor& projmatrices_, double tan_fovx,
+                   double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_, bool prefiltered,
+                   long capacity, bool post_status) {
+    if (means3D_.dim() != 2 || means3D_.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
+    const c10::Device dev = means3D_.device();
+    if (!dev.is_cuda()) throw std::runtime_error("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)");
+    const long V = viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0;
+    if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int P = (int)means3D_.size(0);
+    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
+                 opacity = f32c(opacity_, dev), scales = f32c(scales_, dev), rotations = f32c(rotations_, dev),
+                 cov3D = f32c(cov3D_, dev), views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev),
+                 campos = f32c(campos_, dev), gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev);
+    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    const auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
+    const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
+    Tensor color = at::empty({V, 3, H, W}, f32), depth = at::empty({V, 1, H, W}, f32), unc = at::empty({V, 1, H, W}, f32);
+    Tensor radii = P ? at::empty({V, P}, i32) : at::zeros({V, P}, i32);
+    Tensor geom = at::empty({V, (long long)std::max<size_t>(dgr_geometry_bytes(P), 1)}, u8);
+    Tensor img = at::empty({V, (long long)std::max<size_t>(dgr_image_bytes((int)W, (int)H), 1)}, u8);
+    Tensor binning = at::empty({V, (long long)std::max<size_t>(dgr_binning_bytes((int)capacity, (int)W, (int)H), 1)}, u8);
+    Tensor status = at::zeros({V, 4}, i32);
+    dgr_full_view w[DGR_MAX_BATCH_VIEWS];
+    for (long v = 0; v < V; v++) {
+        w[v] = dgr_full_view{row_bytes(geom, v), row_bytes(binning, v), (int)capacity, row_bytes(img, v), row<int>(status, v),
+                             row<float>(views, v), row<float>(projs, v), row<float>(campos, v), row<float>(color, v),
+                             row<float>(depth, v), row<float>(gts, v), row<float>(unc, v), row<int>(radii, v)};
+    }
+    void* st = stream_of(dev);
+    check(dgr_full_forward_batch(st, (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+                                 ptr<float>(sh), ptr<float>(colors), ptr<float>(opacity), ptr<float>(scales), (float)scale_modifier,
+                                 ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0));
+    std::vector<long> tickets;
+    if (post_status && P > 0 && !dgr_stream_is_capturing(st)) {
+        for (long v = 0; v < V; v++) {
+            const long t = dgr_status_post(st, row<int>(status, v));
+            check(t);
+            tickets.push_back(t);
+        }
+    }
+    return {{status, color, depth, unc, radii, geom, binning, img}, tickets};
+}
+
+// Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
+// the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).  An undefined or
+// empty dL_dout_unc: no view's loss used the uncertainty image (the lean blend backward).
+std::vector<Tensor> full_backward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
+                                        const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
+                                        const Tensor& viewmatrices_, const Tensor& projmatrices_, double tan_fovx, double tan_fovy,
+                                        const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_unc,
+                                        const Tensor& gt_depths_, const Tensor& sh_, long degree, const Tensor& campos_,
+                                        const Tensor& geom, const Tensor& binning, const Tensor& img, const Tensor& perspec_,
+                                        bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered) {
+    const c10::Device dev = means3D_.device();
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
+    const int P = (int)means3D_.size(0);
+    const long V = viewmatrices_.size(0), H = dL_dout_color.size(2), W = dL_dout_color.size(3);
+    if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
+    const bool lean = !dL_dout_unc.defined() || dL_dout_unc.numel() == 0;
+    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
+                 scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
+                 views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev), campos = f32c(campos_, dev),
+                 gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev), perspec = f32c_diag4(perspec_, dev),
+                 gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gU = lean ? Tensor() : f32c(dL_dout_unc, dev);
+    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    std::vector<Tensor> g(9);
+    float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Tensor d2;
+    if (need_gaussian_grads) {
+        grad_arena(dev, P, M, g.data());
+        g[0].zero_();  // the arena's one-view means2D slot: a batch returns those gradients per view, beside the arena
+        g[0] = Tensor();
+        for (int i = 1; i < 8; i++) gp[i] = ptr<float>(g[i]);
+        if (need_means2D) { d2 = at::empty({V, P, 3}, f32); g[0] = d2; }
+    }
+    Tensor dview = at::empty({V, 4, 4}, f32);
+    // (deterministic_grads: + 64 bytes per tile instance of the view with the most of them; the views' rows are equally long)
+    long rmax = 0;
+    for (long r : num_rendered) rmax = std::max(rmax, r);
+    const size_t nscr = std::max<size_t>(up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)rmax)), 256);
+    Tensor scratch = at::empty({V, (long long)nscr}, at::TensorOptions().dtype(at::kByte).device(dev));
+    dgr_full_view_grad w[DGR_MAX_BATCH_VIEWS];
+    for (long v = 0; v < V; v++) {
+        w[v] = dgr_full_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
+                                  row<float>(projs, v), row<float>(campos, v), ptr<float>(perspec), row<float>(gts, v),
+                                  row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), lean ? nullptr : row<float>(gU, v),
+                                  d2.defined() ? row<float>(d2, v) : nullptr, row<float>(dview, v), row_bytes(scratch, v), nscr,
+                                  (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0};
+    }
+    // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
+    check(dgr_full_backward_batch(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+                                  ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
+                                  ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, gp[2], gp[1], gp[3],
+                                  gp[4], gp[5], gp[6], gp[7]));
+    g[8] = dview;
+    return g;
+}
+
 Tensor mark_visible(const Tensor& means3D_, const Tensor& viewmatrix_, const Tensor& projmatrix_) {  // L/rasterize_points.cu:238-256
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
@@ -989,6 +1095,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("full_backward", &full_backward);
     m.def("light_forward_batch", &light_forward_batch);
     m.def("light_backward_batch", &light_backward_batch);
+    m.def("full_forward_batch", &full_forward_batch);
+    m.def("full_backward_batch", &full_backward_batch);
     m.def("host_prof_dump", &host_prof_dump);
     m.def("light_apply", &light_apply);
     m.def("full_apply", &full_apply);

@@ -41,6 +41,19 @@ class LightViewGrad(C.Structure):  # dgr_light_view_grad: the per-camera argumen
                 ("scratch_bytes", _sz), ("num_rendered", _i)]
 
 
+class FullView(C.Structure):  # dgr_full_view: the per-camera arguments of a batched forward of the full variant
+    _fields_ = [("geometry_buffer", _vp), ("binning_buffer", _vp), ("binning_capacity", _i), ("image_buffer", _vp),
+                ("status", _vp), ("viewmatrix", _vp), ("projmatrix", _vp), ("cam_pos", _vp), ("out_color", _vp),
+                ("out_depth", _vp), ("gt_depth", _vp), ("out_uncertainty", _vp), ("radii", _vp)]
+
+
+class FullViewGrad(C.Structure):  # dgr_full_view_grad: the per-camera arguments of a batched backward of the full variant
+    _fields_ = [("geometry_buffer", _vp), ("binning_buffer", _vp), ("image_buffer", _vp), ("viewmatrix", _vp),
+                ("projmatrix", _vp), ("cam_pos", _vp), ("perspec_matrix", _vp), ("gt_depth", _vp), ("radii", _vp),
+                ("dL_dpix", _vp), ("dL_depths", _vp), ("dL_duncertainties", _vp), ("dL_dmean2D", _vp), ("dL_dview", _vp),
+                ("scratch", _vp), ("scratch_bytes", _sz), ("num_rendered", _i)]
+
+
 MAX_BATCH_VIEWS = 8  # DGR_MAX_BATCH_VIEWS
 
 # argument lists follow include/dgr_hip.h one to one
@@ -49,6 +62,10 @@ _SIGS = {
                                      _vp, _f, _f, _i]),
     "dgr_light_backward_batch": (_i, [_vp, _i, C.POINTER(LightViewGrad), _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp,
                                       _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i]),
+    "dgr_full_forward_batch": (_i, [_vp, _i, C.POINTER(FullView), _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _vp,
+                                    _vp, _f, _f, _i]),
+    "dgr_full_backward_batch": (_i, [_vp, _i, C.POINTER(FullViewGrad), _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp,
+                                     _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgr_last_error": (C.c_char_p, []),
     "dgr_status_post": (C.c_long, [_vp, _vp]),
     "dgr_status_poll": (_i, [C.c_long, _i, _vp]),

@@ -345,13 +345,19 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     return res
 
 
-def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, track_off=False, map_off=False):
+def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, track_off=False, map_off=False,
+                 variant="light"):
     """`render()` for the V cameras of a keyframe batch in ONE call of the batched entry points (`dgr_amd.batch`, SURVEY.md
-    s8(f) item 2; light variant): the cameras share `fov` and `HW` (one sensor, V poses), every per-view entry of `render()`'s
-    dict comes back with a leading view dimension, and one backward through it yields the Gaussians' gradients already summed
-    over the views, the pose gradient per `viewmatrix` and `viewspace_points.grad` ([V,P,3]) per view.
-    `cameras`: sequence of dicts with `viewmatrix` (W2C^T), `fov`, `HW` and optionally `gt_depth`, `viewpoint_camera`."""
+    s8(f) item 2; `variant="full"`: `dgr_amd.batch_full`): the cameras share `fov` and `HW` (one sensor, V poses), every
+    per-view entry of `render()`'s dict comes back with a leading view dimension, and one backward through it yields the
+    Gaussians' gradients already summed over the views, the pose gradient per `viewmatrix` and `viewspace_points.grad`
+    ([V,P,3]) per view.  `cameras`: sequence of dicts with `viewmatrix` (W2C^T), `fov`, `HW`, `gt_depth` and optionally
+    `viewpoint_camera`.  The full variant has no track_off / map_off."""
     from . import batch as _batch
+    if variant not in ("light", "full"):
+        raise ValueError(f"unknown variant {variant!r}")
+    if variant == "full" and (track_off or map_off):
+        raise ValueError("the full variant has no track_off / map_off")
     cameras = list(cameras)
     if not 1 <= len(cameras) <= _batch.MAX_VIEWS:
         raise ValueError(f"1 .. {_batch.MAX_VIEWS} cameras per call")
@@ -366,7 +372,7 @@ def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_col
     zfar = float(_get(cam0, "zfar", 100.0)) if cam0 is not None else 100.0
     gts = [c.get("gt_depth") for c in cameras]
     if any(g is None for g in gts):
-        raise ValueError("the light variant needs gt_depth for every camera")
+        raise ValueError(f"the {variant} variant's batch needs gt_depth for every camera")
     vms = [c["viewmatrix"] for c in cameras]
     perspec_src = _get(cam0, "projection_matrix") if cam0 is not None else None
     # A mapping loop renders the same keyframes iteration after iteration: the camera tensors derived from the poses (a dozen
@@ -413,6 +419,13 @@ def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_col
         viewmatrices=vm, projmatrices=projmatrices, sh_degree=int(pc.active_sh_degree), campos=campos, prefiltered=False,
         debug=debug, perspec_matrix=perspec, track_off=track_off, map_off=map_off)
     shs, colors = (None, override_color) if override_color is not None else (shs_or_colors, None)
+    if variant == "full":
+        from .batch_full import GaussianRasterizerBatchFull
+        color, radii, depth, uncertainty = GaussianRasterizerBatchFull(settings)(
+            means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors, scales=scaling, rotations=rotation,
+            viewmatrices=viewmatrices, gt_depths=gt_depths)
+        return {"render": color, "depth": depth, "opacity_map": uncertainty, "viewspace_points": screenspace_points,
+                "visibility_filter": radii > 0, "radii": radii}
     color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels = \
         _batch.GaussianRasterizerBatch(settings)(means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors,
                                                  scales=scaling, rotations=rotation, viewmatrices=viewmatrices,
@@ -428,23 +441,25 @@ class _ViewOf(_Mapping):
     which stays the whole [V,P,3] tensor: one backward fills every view's slice."""
     _NAMES = ("render", "depth", "depth_median", "opacity_map", "depth_var", "gau_uncertainty", "num_related_pixels",
               "visibility_filter", "radii", "viewspace_points")
+    _FULL_NAMES = ("render", "depth", "opacity_map", "visibility_filter", "radii", "viewspace_points")  # (variant="full")
 
     def __init__(self, out, k):
         self._out, self._k, self._got = out, k, {}
+        self._names = self._NAMES if "depth_median" in out else self._FULL_NAMES
 
     def __getitem__(self, n):
         v = self._got.get(n)
         if v is None:
-            if n not in self._NAMES:
+            if n not in self._names:
                 raise KeyError(n)
             v = self._got[n] = self._out[n] if n == "viewspace_points" else self._out[n][self._k]
         return v
 
     def __iter__(self):
-        return iter(self._NAMES)
+        return iter(self._names)
 
     def __len__(self):
-        return len(self._NAMES)
+        return len(self._names)
 
 
 def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None, **render_kwargs):
@@ -453,7 +468,8 @@ def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None,
     `render_batch` -- the sum over the keyframes in the Gaussians' `.grad`, one pose gradient per `viewmatrix` -- without V - 1
     accumulation passes over the dense gradient rows and with the camera-independent per-Gaussian work done once.
     `batch_loss_fn(out)`, if given, replaces the V calls of `loss_fn`: it sees the batched dict and returns the SUM of the
-    views' losses as one scalar (then the returned list holds that one value)."""
+    views' losses as one scalar (then the returned list holds that one value).  `variant="full"` (a render_kwargs entry) renders
+    through the full variant's batch."""
     out = render_views(cameras, pc, pipe, bg_color, **render_kwargs)
     if batch_loss_fn is not None:
         # ONE loss over the stacked outputs ([V,3,H,W], [V,1,H,W], ...): no per-view slice in the graph -- each is a node whose

@@ -9,8 +9,11 @@ A synthetic map rendered from K poses gives the keyframes' observed colour and d
   SparseAdam.step        fused Adam over the rows some keyframe saw, one launch per tensor
 all on the GPU, no host synchronisation inside the loop.  --fused renders the keyframe batch through the batched entry points
 instead (slam.render_batch_fused: one forward and one backward call for all keyframes, gradients summed in the kernels).
+--variant full runs the same loop through the -full variant (uncertainty output; it has no track_off, so the pose gradients are
+formed and left unused).
 
-  python examples/mapping.py [--graph] [--fused] [--iters 100] [--keyframes 4] [--width 640 --height 480 --gaussians 100000]
+  python examples/mapping.py [--graph] [--fused] [--variant light|full] [--iters 100] [--keyframes 4]
+                             [--width 640 --height 480 --gaussians 100000]
 """
 import argparse
 import os
@@ -59,7 +62,7 @@ class MapModel:
                 {"params": [self._rotation], "lr": 1e-3}]
 
 
-def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False):
+def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light"):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations."""
     from dgr_amd import light, slam
@@ -71,7 +74,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     bg, gt = torch.from_numpy(s.bg).to(dev), torch.from_numpy(s.gt).to(dev)
     cams = [dict(viewmatrix=torch.from_numpy(sc.view).to(dev), fov=(sc.tanfovx, sc.tanfovy), HW=(H, W), gt_depth=gt)
             for sc in scenes]
-    kw = dict(track_off=True, map_off=False)
+    kw = dict(track_off=True, map_off=False) if variant == "light" else dict(variant="full")
     truth = MapModel(s, dev)
     with torch.no_grad():
         obs = [slam.render(None, truth, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt, **kw)
@@ -170,6 +173,7 @@ def main():
     ap.add_argument("--fused", action="store_true",
                     help="the keyframe batch through one batched forward + backward (slam.render_batch_fused) instead of one "
                          "rasterizer call per keyframe")
+    ap.add_argument("--variant", choices=("light", "full"), default="light", help="which rasterizer variant maps")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -180,9 +184,11 @@ def main():
         os.environ["DGR_SYNC_MODE"] = "lazy"  # a blocking status read cannot be captured
     dev = torch.device("cuda:0")
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
-                                    args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused)
+                                    args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
+                                    variant=args.variant)
     n = float(pc.denom.sum())
-    print(f"loss {l0:.4e} -> {l1:.4e}; {dt * 1e3:.3f} ms per mapping iteration over {args.keyframes} keyframes"
+    print(("full variant: " if args.variant == "full" else "") +
+          f"loss {l0:.4e} -> {l1:.4e}; {dt * 1e3:.3f} ms per mapping iteration over {args.keyframes} keyframes"
           f" ({dt / args.keyframes * 1e3:.3f} ms per keyframe); {int((pc.denom > 0).sum())} Gaussians seen,"
           f" {n:.0f} (Gaussian, view) statistics accumulated")
 

@@ -286,7 +286,8 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
  *     order; the pose gradient's block partials are stored per block and added in block order.  Two runs give the same bits; the
  *     reference's own result, float atomics in arrival order (L/cuda_rasterizer/backward.cu:593-596, 666-680), lies within its
  *     run-to-run spread of it.  Costs about a quarter of the backward at config 3 (profiles/r8/deterministic.txt).  Needs
- *     dgr_light_backward_scratch_bytes_r() of scratch.  The full variant and the batched entry points refuse the option.
+ *     dgr_light_backward_scratch_bytes_r() of scratch.  The full variant and the batched entry points (both variants) use the
+ *     same scheme per view.
  *  "tight_cull": 1 = alpha-aware tile rectangles.  The reference gives a Gaussian every tile its
  *     3-sigma_max circle touches (cuda_rasterizer/forward.cu:229-237, auxiliary.h:46-56); with this option the rectangle
  *     is cut down to the box where alpha can reach 15/255.  Images and gradients are unchanged, but num_rendered, the
@@ -359,7 +360,8 @@ int dgr_cov3d_backward(void* stream, int P, const float* scales, const float* ro
  *    with events (option "batch_streams", 1..8, default 2: one view's binning runs under another view's blend);
  *  - no host synchronisation (hipGraph-capturable after one warm-up call, which creates the internal streams).
  * All views share the image size, tan_fovx / tan_fovy, background and the Gaussians; `views` is a HOST array of n_views
- * (1 .. DGR_MAX_BATCH_VIEWS) structs of DEVICE pointers, read during the call only.  Light variant. */
+ * (1 .. DGR_MAX_BATCH_VIEWS) structs of DEVICE pointers, read during the call only.  Light variant (the full variant's
+ * entry points follow below). */
 #define DGR_MAX_BATCH_VIEWS 8
 typedef struct dgr_light_view {        /* the per-camera arguments of dgr_light_forward_presized, same meaning */
     char* geometry_buffer;
@@ -416,6 +418,58 @@ int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_gra
                              const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                              int track_off, int map_off);
+
+/* ---- the same for the -full variant: dgr_full_forward_presized / dgr_full_backward per view, the contract above ----
+ * Every view's outputs and state buffers are bit-identical to a one-view dgr_full_forward_presized call; the per-Gaussian
+ * backward sums the full variant's per-view terms (computeCov2DCUDA with its depth term, the campos colour term of the pose
+ * gradient) in view order in one launch.  status (device int[4] or NULL): {num_rendered, overflow, prefiltered violation,
+ * num_related_primitives}.  "deterministic_grads" is supported (alpha_mode 0; per view num_rendered sizes the row buffer). */
+typedef struct dgr_full_view {         /* the per-camera arguments of dgr_full_forward_presized, same meaning */
+    char* geometry_buffer;
+    char* binning_buffer;
+    int binning_capacity;
+    char* image_buffer;
+    int* status;                        /* device int[4] or NULL */
+    const float* viewmatrix;
+    const float* projmatrix;
+    const float* cam_pos;
+    float* out_color;
+    float* out_depth;
+    const float* gt_depth;              /* accepted and unused by the forward, as there */
+    float* out_uncertainty;
+    int* radii;                         /* may be NULL */
+} dgr_full_view;
+int dgr_full_forward_batch(void* stream, int n_views, const dgr_full_view* views, int P, int D, int M,
+                           const float* background, int width, int height, const float* means3D, const float* shs,
+                           const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                           const float* rotations, const float* cov3D_precomp, float tan_fovx, float tan_fovy, int prefiltered);
+
+typedef struct dgr_full_view_grad {    /* the per-camera arguments of dgr_full_backward, same meaning */
+    char* geometry_buffer;
+    char* binning_buffer;
+    char* image_buffer;
+    const float* viewmatrix;
+    const float* projmatrix;
+    const float* cam_pos;
+    const float* perspec_matrix;
+    const float* gt_depth;
+    const int* radii;                   /* may be NULL (internal copy is used) */
+    const float* dL_dpix;
+    const float* dL_depths;
+    const float* dL_duncertainties;     /* may be NULL: this view takes the lean blend backward (as dgr_full_backward) */
+    float* dL_dmean2D;                  /* [P,3] of THIS view; may be NULL */
+    float* dL_dview;                    /* [16] of this view */
+    char* scratch;                      /* dgr_light_backward_scratch_bytes_r(P, width, height, num_rendered), one per view */
+    size_t scratch_bytes;
+    int num_rendered;                   /* this view's R as passed to dgr_full_backward; read only with deterministic_grads */
+} dgr_full_view_grad;
+/* dL_dopacity [P], dL_dcolor [P,3], dL_dmean3D [P,3], dL_dcov3D [P,6], dL_dsh [P,M,3] (NULL when M == 0), dL_dscale [P,3],
+ * dL_drot [P,4]: the SUM over the views; each may be NULL. */
+int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                            const float* background, int width, int height, const float* means3D, const float* shs,
+                            const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                            const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                            float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot);
 
 /* Debug: while `device_words` (8 x uint64 per bin_tiles workgroup, caller-owned device memory) is non-NULL, every bin_tiles
  * workgroup stores phase time stamps (100 MHz wall clock) and its segment's sizes there: profiles/r9/bin_tiles_trace.py. */
