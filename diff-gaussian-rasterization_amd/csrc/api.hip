@@ -720,6 +720,14 @@ size_t dgr_binning_bytes(int cap, int width, int height) {
 }
 size_t dgr_light_backward_scratch_bytes(int P, int, int) { return dgr::carve_backward_scratch(nullptr, P).bytes; }
 namespace {
+// absgrad (dgr_*_backward*_absgrad, dgr_hip.h): what is refused, before any device call
+int absgrad_refused(bool wanted, int map_off) {
+    if (!wanted) return DGR_OK;
+    if (map_off) { g_last_error = "absgrad: not with map_off (tracking forms no per-Gaussian gradients)"; return DGR_ERR_BAD_ARGUMENT; }
+    if (opt_det_grads()) { g_last_error = "absgrad: no deterministic form (deterministic_grads is set)"; return DGR_ERR_BAD_ARGUMENT; }
+    if (opt_alpha_mode() == 2) { g_last_error = "absgrad: needs alpha_mode 0 or 1 (not the glibc A/B form)"; return DGR_ERR_BAD_ARGUMENT; }
+    return DGR_OK;
+}
 // deterministic gradients: behind the standard scratch, {per-block instance sums u32[blocks] | per-block pose partials
 // double[blocks][12] | instance-major rows float[R][16]}
 struct DetScratch {
@@ -837,21 +845,23 @@ int dgr_light_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn bi
     return R;
 }
 
-int dgr_light_backward(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
-                       const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
-                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                       float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                       const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
-                       const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                       float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                       float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
-                       const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
-                       const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes) {
+static int light_backward_impl(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+                               const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                               float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                               const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
+                               const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                               float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                               float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
+                               const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
+                               const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes,
+                               float* dL_dmean2D_abs) {
     (void)dgndcs_dviewmatrix; (void)dg_camd_dviewmatrix; (void)colors_precomp;
     hipStream_t st = (hipStream_t)stream;
     const bool scratch_clean = g_scratch_clean_armed;
     g_scratch_clean_armed = false;
+    if (int rc = absgrad_refused(dL_dmean2D_abs != nullptr, map_off)) return rc;
     if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
     if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
         HIP_TRY(hipMemsetAsync(dL_dview, 0, 16 * 4, st));
@@ -873,6 +883,7 @@ int dgr_light_backward(void* stream, int P, int D, int M, int R, const float* ba
     dgr::BackwardScratch sc = dgr::carve_backward_scratch(scratch, P);
     const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
     if (!scratch_clean) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, st)); }
+    if (dL_dmean2D_abs) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_floats(dL_dmean2D_abs, 3 * (size_t)P, st)); }
 
     dgr::RenderBwdLightArgs r{};
     r.W = width; r.H = height; r.grid_x = gx; r.grid_y = gy;
@@ -889,7 +900,8 @@ int dgr_light_backward(void* stream, int P, int D, int M, int R, const float* ba
         HIP_TRY(dgr::launch_det_offsets(P, geom.rect, ds.blk, geom.goff, st));
         r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)R;
     }
-    { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_light(r, opt_alpha_mode(), st)); }
+    if (dL_dmean2D_abs) { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_light_abs(r, dL_dmean2D_abs, opt_alpha_mode(), st)); }
+    else { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_light(r, opt_alpha_mode(), st)); }
     if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)R, sc.acc, st));
 
     dgr::PreprocessBwdArgs b{};
@@ -908,6 +920,42 @@ int dgr_light_backward(void* stream, int P, int D, int M, int R, const float* ba
     { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st)); }
     if (debug && !dgr_stream_is_capturing(stream)) HIP_TRY(hipStreamSynchronize(st));  // (CHECK_CUDA(..., debug); a capturing stream cannot be waited for -- and the attempt would invalidate the capture)
     return DGR_OK;
+}
+int dgr_light_backward(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                       const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+                       const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                       float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                       const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
+                       const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                       float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                       float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
+                       const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
+                       const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes) {
+    return light_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales,
+                               scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                               geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dpix_median_depth,
+                               dL_dpix_depth_var, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D,
+                               dL_dsh, dL_dscale, dL_drot, debug, dgndcs_dviewmatrix, perspec_matrix, dL_dview, dg_camd_dviewmatrix,
+                               gt_depth, track_off, map_off, scratch, scratch_bytes, nullptr);
+}
+int dgr_light_backward_absgrad(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+                               const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                               float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                               const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
+                               const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                               float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                               float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
+                               const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
+                               const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes, float* dL_dmean2D_abs) {
+    return light_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales,
+                               scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                               geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dpix_median_depth,
+                               dL_dpix_depth_var, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D,
+                               dL_dsh, dL_dscale, dL_drot, debug, dgndcs_dviewmatrix, perspec_matrix, dL_dview, dg_camd_dviewmatrix,
+                               gt_depth, track_off, map_off, scratch, scratch_bytes, dL_dmean2D_abs);
 }
 
 // ------------------------------------------------------------------------------------------------ full variant
@@ -998,21 +1046,23 @@ int dgr_full_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn bin
     return R;
 }
 
-int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
-                      const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                      float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                      const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                      char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                      const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                      float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                      float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
-                      const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
-                      float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
-                      float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
-                      size_t scratch_bytes) {
+static int full_backward_impl(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                              char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                              const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                              float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
+                              const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
+                              float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
+                              float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
+                              size_t scratch_bytes,
+                              float* dL_dmean2D_abs) {
     (void)colors_precomp; (void)dpixel_dgc; (void)gau_id_list; (void)pix_id_list; (void)dgc_dCam_position;
     (void)dpixel_dndcs; (void)dgndcs_dviewmatrix; (void)dpixel_dinvcovs; (void)dgc_invcovs_dT; (void)ddepth_dndcs;
     (void)ddepth_dinvcovs;
+    if (int rc = absgrad_refused(dL_dmean2D_abs != nullptr, 0)) return rc;
     const bool det = opt_det_grads() != 0;  // (round 9: the scheme of the light variant, csrc/render_light.hip: DET)
     if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
     if (det && R <= 0) { g_last_error = "deterministic_grads: the backward needs R >= num_rendered (it sizes the instance-major row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
@@ -1037,6 +1087,7 @@ int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* bac
     dgr::BackwardScratch sc = dgr::carve_backward_scratch(scratch, P);
     const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
     if (!scratch_clean) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, st)); }
+    if (dL_dmean2D_abs) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_floats(dL_dmean2D_abs, 3 * (size_t)P, st)); }
     DetScratch ds{nullptr, nullptr, nullptr, 0};
     if (det) {
         ds = carve_det_scratch(scratch, P, R);
@@ -1050,7 +1101,8 @@ int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* bac
     r.gt_depth = gt_depth; r.final_T = img.final_T; r.n_contrib = img.n_contrib; r.first_contrib = img.first_contrib;
     r.dL_dpix = dL_dpix; r.dL_depths = dL_depths; r.dL_duncertainties = dL_duncertainties; r.acc = sc.acc;
     if (det) { r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)R; }
-    { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), st, det)); }
+    if (dL_dmean2D_abs) { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_full_abs(r, dL_dmean2D_abs, opt_alpha_mode(), st)); }
+    else { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), st, det)); }
     if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)R, sc.acc, st));
 
     dgr::PreprocessBwdArgs b{};
@@ -1067,6 +1119,46 @@ int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* bac
     b.dL_dscale = dL_dscale; b.dL_drot = dL_drot; b.pose_part = sc.pose_part; b.ticket = sc.ticket; b.dL_dview = dL_dview;
     { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st)); }
     return DGR_OK;
+}
+int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                      const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                      float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                      const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                      char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                      const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                      float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                      float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
+                      const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
+                      float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
+                      float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
+                      size_t scratch_bytes) {
+    return full_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                              rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
+                              binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                              dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dpixel_dgc, gau_id_list, pix_id_list,
+                              dgc_dCam_position, dpixel_dndcs, perspec_matrix, dgndcs_dviewmatrix, dpixel_dinvcovs, dgc_invcovs_dT,
+                              dL_dview, dL_dgau_depth, ddepth_dndcs, ddepth_dinvcovs, gt_depth, dL_duncertainties, scratch,
+                              scratch_bytes, nullptr);
+}
+int dgr_full_backward_absgrad(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                              char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                              const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                              float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
+                              const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
+                              float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
+                              float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
+                              size_t scratch_bytes, float* dL_dmean2D_abs) {
+    return full_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                              rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
+                              binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                              dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dpixel_dgc, gau_id_list, pix_id_list,
+                              dgc_dCam_position, dpixel_dndcs, perspec_matrix, dgndcs_dviewmatrix, dpixel_dinvcovs, dgc_invcovs_dT,
+                              dL_dview, dL_dgau_depth, ddepth_dndcs, ddepth_dinvcovs, gt_depth, dL_duncertainties, scratch,
+                              scratch_bytes, dL_dmean2D_abs);
 }
 
 int dgr_light_forward_batch(void* stream, int n_views, const dgr_light_view* views, int P, int D, int M,
@@ -1105,17 +1197,21 @@ int dgr_full_forward_batch(void* stream, int n_views, const dgr_full_view* views
     return forward_batch((hipStream_t)stream, n_views, cv, bs, true);
 }
 
-int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
-                             const float* background, int width, int height, const float* means3D, const float* shs,
-                             const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                             const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
-                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                             int track_off, int map_off) {
+static int light_backward_batch_impl(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
+                                     const float* background, int width, int height, const float* means3D, const float* shs,
+                                     const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                     const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                     int track_off, int map_off,
+                                     float* const* dL_dmean2D_abs) {
     (void)colors_precomp;
     hipStream_t st = (hipStream_t)stream;
     const bool det = opt_det_grads() != 0 && !(track_off && map_off);  // (round 9: per view the scheme of the one-view backward)
     if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
     if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    bool any_abs = false;  // (absgrad: a NULL array or NULL entries -- those views as without it)
+    for (int v = 0; dL_dmean2D_abs && v < n_views; v++) any_abs |= dL_dmean2D_abs[v] != nullptr;
+    if (int rc = absgrad_refused(any_abs, map_off)) return rc;
     if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
     for (int v = 0; v < n_views; v++)
         if (!views[v].dL_dview) { g_last_error = "view without dL_dview"; return DGR_ERR_BAD_ARGUMENT; }
@@ -1150,6 +1246,8 @@ int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_gra
         dgr::ImageView img = dgr::carve_image(w.image_buffer, width, height);
         dgr::BackwardScratch sc = dgr::carve_backward_scratch(w.scratch, P);
         { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, sv)); }
+        float* const ab = dL_dmean2D_abs ? dL_dmean2D_abs[v] : nullptr;
+        if (ab) { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_floats(ab, 3 * (size_t)P, sv)); }
         if (pipeline) {  // the blend backward of view v on the caller's stream, behind its cleared scratch
             HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
             HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
@@ -1168,7 +1266,8 @@ int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_gra
             HIP_TRY(dgr::launch_det_offsets(P, geom.rect, ds.blk, geom.goff, sv));
             r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)w.num_rendered;
         }
-        { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_light(r, opt_alpha_mode(), sv)); }
+        if (ab) { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_light_abs(r, ab, opt_alpha_mode(), sv)); }
+        else { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_light(r, opt_alpha_mode(), sv)); }
         if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)w.num_rendered, sc.acc, sv));
         dgr::BwdViewPart& q = bb.v[v];
         q.det_pose = det ? ds.pose : nullptr;
@@ -1191,17 +1290,41 @@ int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_gra
     { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st)); }
     return DGR_OK;
 }
+int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
+                             const float* background, int width, int height, const float* means3D, const float* shs,
+                             const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                             const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                             int track_off, int map_off) {
+    return light_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
+                                     scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
+                                     dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, track_off, map_off, nullptr);
+}
+int dgr_light_backward_batch_absgrad(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
+                                     const float* background, int width, int height, const float* means3D, const float* shs,
+                                     const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                     const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                     int track_off, int map_off, float* const* dL_dmean2D_abs) {
+    return light_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
+                                     scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
+                                     dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, track_off, map_off, dL_dmean2D_abs);
+}
 
-int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
-                            const float* background, int width, int height, const float* means3D, const float* shs,
-                            const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                            const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
-                            float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot) {
+static int full_backward_batch_impl(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                                    const float* background, int width, int height, const float* means3D, const float* shs,
+                                    const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                    const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                    float* const* dL_dmean2D_abs) {
     (void)colors_precomp;
     hipStream_t st = (hipStream_t)stream;
     const bool det = opt_det_grads() != 0;  // (per view the scheme of dgr_full_backward)
     if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
     if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    bool any_abs = false;  // (absgrad: a NULL array or NULL entries -- those views as without it)
+    for (int v = 0; dL_dmean2D_abs && v < n_views; v++) any_abs |= dL_dmean2D_abs[v] != nullptr;
+    if (int rc = absgrad_refused(any_abs, 0)) return rc;
     if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
     for (int v = 0; v < n_views; v++)
         if (!views[v].dL_dview) { g_last_error = "view without dL_dview"; return DGR_ERR_BAD_ARGUMENT; }
@@ -1237,6 +1360,8 @@ int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad*
         dgr::ImageView img = dgr::carve_image(w.image_buffer, width, height);
         dgr::BackwardScratch sc = dgr::carve_backward_scratch(w.scratch, P);
         { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, sv)); }
+        float* const ab = dL_dmean2D_abs ? dL_dmean2D_abs[v] : nullptr;
+        if (ab) { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_floats(ab, 3 * (size_t)P, sv)); }
         DetScratch ds{nullptr, nullptr, nullptr, 0};
         if (det) {
             ds = carve_det_scratch(w.scratch, P, w.num_rendered);
@@ -1254,7 +1379,8 @@ int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad*
         r.gt_depth = w.gt_depth; r.final_T = img.final_T; r.n_contrib = img.n_contrib; r.first_contrib = img.first_contrib;
         r.dL_dpix = w.dL_dpix; r.dL_depths = w.dL_depths; r.dL_duncertainties = w.dL_duncertainties; r.acc = sc.acc;
         if (det) { r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)w.num_rendered; }
-        { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), sv, det)); }
+        if (ab) { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_full_abs(r, ab, opt_alpha_mode(), sv)); }
+        else { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), sv, det)); }
         if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)w.num_rendered, sc.acc, sv));
         dgr::BwdViewPart& q = bb.v[v];
         q.det_pose = det ? ds.pose : nullptr;
@@ -1276,6 +1402,24 @@ int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad*
     bb.V = n_views;
     { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st)); }
     return DGR_OK;
+}
+int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                            const float* background, int width, int height, const float* means3D, const float* shs,
+                            const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                            const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                            float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot) {
+    return full_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
+                                    scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
+                                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr);
+}
+int dgr_full_backward_batch_absgrad(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                                    const float* background, int width, int height, const float* means3D, const float* shs,
+                                    const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                    const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* const* dL_dmean2D_abs) {
+    return full_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
+                                    scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
+                                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dmean2D_abs);
 }
 
 int dgr_cov3d_forward(void* stream, int P, const float* scales, const float* rotations, float scale_modifier, float* cov3D) {

@@ -308,6 +308,13 @@ hipError_t launch_render_fwd_light(const RenderFwdLightArgs& a, int alpha_mode, 
 hipError_t launch_render_bwd_light(const RenderBwdLightArgs& a, int alpha_mode, hipStream_t stream);
 hipError_t launch_render_fwd_full(const RenderFwdFullArgs& a, int alpha_mode, hipStream_t stream);
 hipError_t launch_render_bwd_full(const RenderBwdFullArgs& a, int alpha_mode, hipStream_t stream, bool deterministic = false);
+// absgrad (AbsGS): opt-in instances of the two MAPPING blend backwards that also sum the absolute value of each pixel's dL/dmean2D
+// per Gaussian (render_light.hip: ABS) and add the totals, x and y, into dL_dmean2D_abs [P,3] -- which the caller zero-fills first
+// (launch_zero_floats).  alpha_mode 0 and 1, not deterministic, not with map_off (api.hip checks).
+hipError_t launch_render_bwd_light_abs(const RenderBwdLightArgs& a, float* dL_dmean2D_abs, int alpha_mode, hipStream_t stream);
+hipError_t launch_render_bwd_full_abs(const RenderBwdFullArgs& a, float* dL_dmean2D_abs, int alpha_mode, hipStream_t stream);
+// zero-fill of n floats at any 4-byte aligned address
+hipError_t launch_zero_floats(float* dst, size_t n, hipStream_t stream);
 hipError_t launch_det_offsets(int P, const ushort4* rect, uint32_t* blk, uint32_t* goff, hipStream_t stream);
 hipError_t launch_det_gather(int P, const ushort4* rect, const uint32_t* goff, const float* rows, uint32_t R, float* acc, hipStream_t stream);
 hipError_t launch_half_reduce16_test(const float* in, float* r0, float* r1, int* slot0, int* slot1, hipStream_t stream);

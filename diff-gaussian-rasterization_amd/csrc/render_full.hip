@@ -147,14 +147,16 @@ constexpr int NACC_FULL = 15;
 // variant): one accumulator plane per quadrant wave, plain stores, the planes added in wave order, the finished row of a
 // (tile, Gaussian) pair STORED to its own row of an instance-major buffer that det_gather_kernel adds up per Gaussian in ascending
 // order -- render_light.hip has the scheme; four planes are four times the accumulators, hence 64 positions per batch.
-template <bool DET>
+// ABS (absgrad, render_bwd_full_abs_kernel): two more accumulator rows, components 15 and 16, behind the plane
+template <bool DET, bool ABS = false>
 struct StagedBwdFull {
     static constexpr int NB = DET ? 64 : 128;
     static constexpr int LD = NB + 1;
     static constexpr int PLANE = NACC_FULL * LD;
+    static constexpr int NACC = ABS ? NACC_FULL + 2 : NACC_FULL;  // rows cleared per batch
     typedef StagedT<NB, uint32_t, DET ? 4 : 8> staged_t;  // (paired lists: two list rows per quadrant wave, render_common.h)
     staged_t f;
-    float acc[(DET ? 4 : 1) * PLANE];
+    float acc[(DET ? 4 : 1) * PLANE + (ABS ? 2 * LD : 0)];
     uint32_t inst[DET ? NB : 1];
     int max_last;
     uint64_t exptab[32];  // ALPHA_GLIBC: exact_math.h
@@ -166,12 +168,15 @@ struct StagedBwdFull {
 // (its planes take the LDS).
 // LEAN (round 9, as in the light variant): the caller passed no gradient image for the "uncertainty" output (NULL: the loss did not
 // use it) -- the variance recurrence and its two terms drop out: bit-identical to the kernel fed an all-zero image.
-template <int AM, bool DET = false, bool LEAN = false>
-__global__ void __launch_bounds__(256, 6) render_bwd_full_kernel(RenderBwdFullArgs a) {
-    typedef StagedBwdFull<DET> SB;
+// ABS (absgrad; not DET): as in the light mapping backward (render_light.hip: ABS) -- every lane's own dL/dmean2D (the first of the
+// three "d/d(ndc)" pairs of the finish step, per pixel) in absolute value, reduced per half-wave by half_reduce3 into accumulator
+// rows 15, 16, so the 16-value network keeps its 15 components; the batch's totals go to abs_out [P,3] by global atomics.
+template <int AM, bool DET, bool LEAN, bool ABS>
+__device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a, StagedBwdFull<DET, ABS>& sb, float* __restrict__ abs_out) {
+    static_assert(!ABS || !DET, "absgrad: not the deterministic kernel");
+    typedef StagedBwdFull<DET, ABS> SB;
     constexpr int BWD_NB = SB::NB, BWD_LD = SB::LD;
     constexpr bool PAIRED = !DET;
-    __shared__ SB sb;
     typename SB::staged_t& s = sb.f;
     const uint4 slot = blend_slot(a.sched, a.ranges, a.sched_flag, a.grid_x * a.grid_y);  // {tile, list start, list end}
     const int tile = (int)slot.x;
@@ -236,7 +241,7 @@ __global__ void __launch_bounds__(256, 6) render_bwd_full_kernel(RenderBwdFullAr
         if (tid < cnt) code = stage_tagged<AM, PAIRED ? TAGS_BYTES_HALVES : TAGS_BYTES_QUADRANT>(s, tid, a.point_list[range.x + lo + tid], a.rec, tag8 + (range.x + lo + tid));
         if (!DET) {  // (DET: a plane's column is written by its wave iff the entry's tag names the wave -- nothing to clear)
 #pragma unroll
-            for (int k = 0; k < NACC_FULL; k++)
+            for (int k = 0; k < SB::NACC; k++)
                 if (tid < BWD_NB) sb.acc[k * BWD_LD + tid] = 0.f;
         }
         unsigned long long split[2] = {0ull, 0ull};  // PAIRED: the steps that serve two entries
@@ -314,6 +319,15 @@ __global__ void __launch_bounds__(256, 6) render_bwd_full_kernel(RenderBwdFullAr
                 g[13] = fq * dx;  // front-most depth sums
                 g[14] = fq * dy;
                 g[15] = 0.f;
+                if (ABS) {
+                    // this pixel's dL/dmean2D without the ndc scale, in absolute value
+                    constexpr float UN = AlphaPath<AM>::PUNSCALE;
+                    const float ca = q0[u].z * (-2.f * UN), cb = q1[u].x * (-UN), cc = q0[u].w * (-2.f * UN);
+                    const float h = half_reduce3(fabsf(ca * qdx + cb * qdy), fabsf(cc * qdy + cb * qdx), 0.f);
+                    const int c = half_reduce3_comp(lane);  // 0: |x| in lane 32 h, 1: |y| in lane 32 h + 16
+                    if (c == 0 || c == 1)
+                        atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(sb.acc) + j4 + (NACC_FULL + c) * (BWD_LD * 4)), h);
+                }
                 float tot;
                 if (PAIRED) {
                     float u0, u1;
@@ -375,6 +389,12 @@ __global__ void __launch_bounds__(256, 6) render_bwd_full_kernel(RenderBwdFullAr
             sb.acc[7 * BWD_LD + tid] *= -0.5f;
             sb.acc[8 * BWD_LD + tid] *= -0.5f;
             sb.acc[9 * BWD_LD + tid] *= __builtin_amdgcn_rcpf(r1.y);
+            if (ABS) {
+                const float ax = sb.acc[NACC_FULL * BWD_LD + tid] * ddelx_dx, ay = sb.acc[(NACC_FULL + 1) * BWD_LD + tid] * ddely_dy;
+                const size_t gid = s.id[tid];
+                if (ax != 0.f) atomicAdd(abs_out + 3 * gid, ax);
+                if (ay != 0.f) atomicAdd(abs_out + 3 * gid + 1, ay);
+            }
         }
         __syncthreads();
         if (DET) {  // 16 consecutive lanes store one pair's 64-byte row (component 15 stays zero)
@@ -387,6 +407,18 @@ __global__ void __launch_bounds__(256, 6) render_bwd_full_kernel(RenderBwdFullAr
             flush_acc<NACC_FULL, BWD_LD>(sb.acc, s.id, cnt, a.acc, tid);
         }
     }
+}
+
+template <int AM, bool DET = false, bool LEAN = false>
+__global__ void __launch_bounds__(256, 6) render_bwd_full_kernel(RenderBwdFullArgs a) {
+    __shared__ StagedBwdFull<DET> sb;
+    render_bwd_full_body<AM, DET, LEAN, false>(a, sb, nullptr);
+}
+
+template <int AM, bool LEAN>
+__global__ void __launch_bounds__(256, 6) render_bwd_full_abs_kernel(RenderBwdFullArgs a, float* abs_out) {
+    __shared__ StagedBwdFull<false, true> sb;
+    render_bwd_full_body<AM, false, LEAN, true>(a, sb, abs_out);
 }
 
 }  // namespace
@@ -417,6 +449,16 @@ hipError_t launch_render_bwd_full(const RenderBwdFullArgs& a, int alpha_mode, hi
             if (lean) launch_blend(render_bwd_full_kernel<ALPHA_REF, false, true>, dim3(tiles), dim3(256), stream, a);
             else launch_blend(render_bwd_full_kernel<ALPHA_REF>, dim3(tiles), dim3(256), stream, a);
     }
+    return hipGetLastError();
+}
+hipError_t launch_render_bwd_full_abs(const RenderBwdFullArgs& a, float* dL_dmean2D_abs, int alpha_mode, hipStream_t stream) {
+    const int tiles = a.grid_x * a.grid_y;
+    if (tiles <= 0) return hipSuccess;
+    // (the instances of launch_render_bwd_full's non-deterministic branches)
+    if (alpha_mode == ALPHA_FAST) launch_blend((render_bwd_full_abs_kernel<ALPHA_FAST, false>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+    else if (alpha_mode == ALPHA_REF && a.dL_duncertainties == nullptr) launch_blend((render_bwd_full_abs_kernel<ALPHA_REF, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+    else if (alpha_mode == ALPHA_REF) launch_blend((render_bwd_full_abs_kernel<ALPHA_REF, false>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+    else return hipErrorInvalidValue;  // (alpha_mode 2: refused by the entry points)
     return hipGetLastError();
 }
 

@@ -219,14 +219,16 @@ constexpr int NACC_LIGHT = 14;
 // list positions staged per batch (256: 5 workgroups per CU, 267 us; 128: 247 us).  The deterministic kernel (DET, below) keeps one
 // accumulator plane per quadrant wave -- four times the accumulators -- and stages 64 positions per batch to stay at 8 workgroups
 // per CU.
-template <bool DET, bool HALVES = false>
+// ABS (absgrad, render_bwd_light_abs_kernel): two more accumulator rows, components 14 and 15, behind the plane.
+template <bool DET, bool HALVES = false, bool ABS = false>
 struct StagedBwd {
     static constexpr int NB = DET ? 64 : 128;
     static constexpr int LD = NB + 1;          // accumulator row length
     static constexpr int PLANE = NACC_LIGHT * LD;
+    static constexpr int NACC = ABS ? NACC_LIGHT + 2 : NACC_LIGHT;  // rows cleared per batch
     typedef StagedT<NB, uint32_t, HALVES ? 8 : 4> staged_t;
     staged_t f;
-    float acc[(DET ? 4 : 1) * PLANE];
+    float acc[(DET ? 4 : 1) * PLANE + (ABS ? 2 * LD : 0)];
     uint32_t inst[DET ? NB : 1];               // DET: the staged entries' rows in the instance-major gradient buffer (~0u: none)
     int max_last;
     uint64_t exptab[32];  // ALPHA_GLIBC: exact_math.h
@@ -258,11 +260,19 @@ struct StagedBwd {
 // With DO_MAP, HALVES means PAIRED lists (render_common.h: build_paired_lists): neighbouring entries of a wave's list that live
 // in different halves of the quadrant share a loop step (0.87 steps per entry); such a step reduces its twelve sums per half and
 // each half delivers to its own entry's column -- every entry is still delivered once.
-template <int AM, bool DO_MAP, bool DO_POSE, bool DET, bool LEAN, bool HALVES>
-__device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& a, StagedBwd<DET, HALVES>& sb, const uint4 slot) {
+//
+// ABS (absgrad, AbsGS's "homodirectional" gradient; mapping only, not DET): each lane also forms its pixel's own dL/dmean2D --
+// the formula of the moments -> gradients step below applied to the pixel's q dx, q dy -- and sums the absolute values of its two
+// components.  half_reduce3 reduces the pair over each half-wave, and each half adds its totals to its own entry's column of
+// accumulator rows 14, 15 (a paired step: two entries; otherwise both halves into one), so the default 12-value network and its
+// lane maps stay as they are.  The batch's totals, times W/2 and H/2, go to abs_out [P,3] by global atomics.
+template <int AM, bool DO_MAP, bool DO_POSE, bool DET, bool LEAN, bool HALVES, bool ABS = false>
+__device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& a, StagedBwd<DET, HALVES, ABS>& sb, const uint4 slot,
+                                                      float* __restrict__ abs_out = nullptr) {
     static_assert(!HALVES || !DET, "half-wave / paired lists: not with the deterministic kernel's planes (LDS)");
+    static_assert(!ABS || (DO_MAP && !DET), "absgrad: the mapping backward, not the deterministic kernel");
     constexpr bool PAIRED = HALVES && DO_MAP;
-    typedef StagedBwd<DET, HALVES> SB;
+    typedef StagedBwd<DET, HALVES, ABS> SB;
     constexpr int BWD_NB = SB::NB, BWD_LD = SB::LD;
     typename SB::staged_t& s = sb.f;
     const int tile = (int)slot.x;
@@ -349,7 +359,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         if (tid < cnt) code = stage_tagged<AM, HALVES ? TAGS_BYTES_HALVES : TAGS_BYTES_QUADRANT>(s, tid, a.point_list[range.x + lo + tid], a.rec, tag8 + (range.x + lo + tid));
         if (!DET) {  // (DET: a plane's column is written by its wave iff the entry's tag names the wave -- nothing to clear)
 #pragma unroll
-            for (int k = 0; k < NACC_LIGHT; k++)
+            for (int k = 0; k < SB::NACC; k++)
                 if (BWD_NB == DGR_TILE_PIX || tid < BWD_NB) sb.acc[k * BWD_LD + tid] = 0.f;
         }
         unsigned long long split[2] = {0ull, 0ull};  // PAIRED: the steps that serve two entries
@@ -431,6 +441,15 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
                     g[9] = qq;         // sum q
                     g[10] = DO_POSE ? wd : gmed;   // -> accumulator component 13 / 10
                     g[11] = DO_POSE ? gmed : 0.f;  // -> accumulator component 10
+                    if (ABS) {
+                        // this pixel's dL/dmean2D without the ndc scale (finish step below), in absolute value
+                        constexpr float UN = AlphaPath<AM>::PUNSCALE;
+                        const float ca = q0[u].z * (-2.f * UN), cb = q1[u].x * (-UN), cc = q0[u].w * (-2.f * UN);
+                        const float h = half_reduce3(fabsf(ca * qdx + cb * qdy), fabsf(cc * qdy + cb * qdx), 0.f);
+                        const int c = half_reduce3_comp(lane);  // 0: |x| in lane 32 h, 1: |y| in lane 32 h + 16
+                        if (c == 0 || c == 1)
+                            atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(sb.acc) + j4 + (NACC_LIGHT + c) * (BWD_LD * 4)), h);
+                    }
                     if (PAIRED) {
                         float u0, u1;
                         wave_reduce12d_head(g, u0, u1);
@@ -500,6 +519,12 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
             const float Sx = sb.acc[4 * BWD_LD + tid], Sy = sb.acc[5 * BWD_LD + tid];
             sb.acc[4 * BWD_LD + tid] = -(ca * Sx + cb * Sy) * ddelx_dx;
             sb.acc[5 * BWD_LD + tid] = -(cc * Sy + cb * Sx) * ddely_dy;
+            if (ABS) {  // (a staged entry of this batch is one thread's: its two totals go out from here)
+                const float ax = sb.acc[NACC_LIGHT * BWD_LD + tid] * ddelx_dx, ay = sb.acc[(NACC_LIGHT + 1) * BWD_LD + tid] * ddely_dy;
+                const size_t gid = s.id[tid];
+                if (ax != 0.f) atomicAdd(abs_out + 3 * gid, ax);
+                if (ay != 0.f) atomicAdd(abs_out + 3 * gid + 1, ay);
+            }
             if (DO_MAP) {
                 sb.acc[6 * BWD_LD + tid] *= -0.5f;
                 sb.acc[7 * BWD_LD + tid] *= -0.5f;
@@ -518,6 +543,18 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
             flush_acc<NACC_LIGHT, BWD_LD>(sb.acc, s.id, cnt, a.acc, tid);
         }
     }
+}
+
+// absgrad (ABS above): the mapping instances only, lane lists by the frame's flag as in the default kernel (quadrant lists for the
+// glibc form, which is refused: api.hip).  Two more LDS rows (1 KB) and the pair reduction's registers: the lean instances stay at
+// 8 waves per SIMD; the others would spill at 64 VGPRs and run at 7.
+template <int AM, bool DO_POSE, bool LEAN, bool BY_FRAME>
+__global__ void __launch_bounds__(256, LEAN ? 8 : 7) render_bwd_light_abs_kernel(RenderBwdLightArgs a, float* abs_out) {
+    __shared__ union { StagedBwd<false, BY_FRAME, true> h; StagedBwd<false, false, true> q; } sb;
+    bool quadrant_lists = true;
+    const uint4 slot = blend_slot(a.sched, a.ranges, a.sched_flag, a.grid_x * a.grid_y, nullptr, BY_FRAME ? &quadrant_lists : nullptr);
+    if (BY_FRAME && !quadrant_lists) render_bwd_light_body<AM, true, DO_POSE, false, LEAN, BY_FRAME, true>(a, sb.h, slot, abs_out);
+    else render_bwd_light_body<AM, true, DO_POSE, false, LEAN, false, true>(a, sb.q, slot, abs_out);
 }
 
 // BY_FRAME: half-wave / paired lists or quadrant lists by the frame's flag (render_fwd_light_kernel above: the forward that wrote the
@@ -733,6 +770,37 @@ hipError_t launch_render_bwd_light(const RenderBwdLightArgs& a, int alpha_mode, 
         case ALPHA_GLIBC: launch_bwd_light_mode<ALPHA_GLIBC>(a, tiles, stream); break;
         default: launch_bwd_light_mode<ALPHA_REF>(a, tiles, stream);
     }
+    return hipGetLastError();
+}
+hipError_t launch_render_bwd_light_abs(const RenderBwdLightArgs& a, float* dL_dmean2D_abs, int alpha_mode, hipStream_t stream) {
+    const int tiles = a.grid_x * a.grid_y;
+    if (tiles <= 0 || a.map_off) return hipSuccess;
+    const bool lean = !a.dL_dpix_median && !a.dL_dpix_var;
+    // (the instances of launch_bwd_light_mode's non-deterministic mapping branches)
+    if (alpha_mode == ALPHA_FAST) {
+        if (!a.track_off) launch_blend((render_bwd_light_abs_kernel<ALPHA_FAST, true, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+        else launch_blend((render_bwd_light_abs_kernel<ALPHA_FAST, false, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+    } else if (alpha_mode == ALPHA_REF && lean) {
+        if (!a.track_off) launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, true, true, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+        else launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, false, true, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+    } else if (alpha_mode == ALPHA_REF) {
+        if (!a.track_off) launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, true, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+        else launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, false, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
+    } else {
+        return hipErrorInvalidValue;  // (alpha_mode 2: refused by the entry points)
+    }
+    return hipGetLastError();
+}
+namespace {
+__global__ void __launch_bounds__(256) zero_floats_kernel(float* dst, size_t n) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) dst[i] = 0.f;
+}
+}  // namespace
+hipError_t launch_zero_floats(float* dst, size_t n, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 256 * 16);
+    launch(zero_floats_kernel, dim3(blocks), dim3(256), stream, dst, n);
     return hipGetLastError();
 }
 hipError_t launch_det_offsets(int P, const ushort4* rect, uint32_t* blk, uint32_t* goff, hipStream_t stream) {

@@ -415,14 +415,15 @@ inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g) {
 // L/rasterize_points.cu:131-236.  Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
 // dL_drotations, dL_dview [1,4,4]); the first eight are windows of one flat arena (grad_arena above), or undefined tensors
 // (None) when need_gaussian_grads is false (tracking: the library then skips every dense per-Gaussian row).
-std::vector<Tensor> light_backward(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
+// abs_out (absgrad, dgr_light_backward_absgrad): NULL, or the [P,3] absolute screen-space gradient
+std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
                                    const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
                                    const Tensor& viewmatrix_, const Tensor& projmatrix_, double tan_fovx, double tan_fovy,
                                    const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_median,
                                    const Tensor& dL_dout_var, const Tensor& gt_depth_, const Tensor& sh_, long degree,
                                    const Tensor& campos_, const Tensor& geomBuffer, long R, const Tensor& binningBuffer,
                                    const Tensor& imageBuffer, const Tensor& alphas_, bool debug, const Tensor& perspec_,
-                                   bool track_off, bool map_off, bool need_gaussian_grads) {
+                                   bool track_off, bool map_off, bool need_gaussian_grads, float* abs_out) {
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -456,17 +457,37 @@ std::vector<Tensor> light_backward(const Tensor& background, const Tensor& means
     if (resident) dgr_backward_scratch_clean_arm();
     p_al.stop();
     Probe p_bc(HP_BWD_C);
-    const int rc = (dgr_light_backward(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+    const int rc = (dgr_light_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
                              ptr<float>(sh), ptr<float>(colors), ptr<float>(alphas), ptr<float>(scales), (float)scale_modifier,
                              ptr<float>(rotations), ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos),
                              (float)tan_fovx, (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer),
                              bytes(binningBuffer), bytes(imageBuffer), ptr<float>(gC),
                              ptr<float>(gD), ptr<float>(gM), ptr<float>(gV), gp[0], nullptr, gp[2], gp[1], nullptr, gp[3], gp[4],
                              gp[5], gp[6], gp[7], debug ? 1 : 0, nullptr, ptr<float>(perspec), dview.data_ptr<float>(), nullptr,
-                             ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, (char*)scratch.data_ptr(), nscr));
+                             ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, (char*)scratch.data_ptr(), nscr, abs_out));
     if (rc < 0 && resident) drop_scratch(dev, st);
     check(rc);
     g[8] = std::move(dview);
+    return g;
+}
+#define DGR_LIGHT_BWD_PARAMS                                                                                                         \
+    const Tensor &background, const Tensor &means3D, const Tensor &radii, const Tensor &colors, const Tensor &scales,               \
+        const Tensor &rotations, double scale_modifier, const Tensor &cov3D, const Tensor &viewmatrix, const Tensor &projmatrix,     \
+        double tan_fovx, double tan_fovy, const Tensor &dL_dout_color, const Tensor &dL_dout_depth, const Tensor &dL_dout_median,    \
+        const Tensor &dL_dout_var, const Tensor &gt_depth, const Tensor &sh, long degree, const Tensor &campos,                     \
+        const Tensor &geomBuffer, long R, const Tensor &binningBuffer, const Tensor &imageBuffer, const Tensor &alphas, bool debug, \
+        const Tensor &perspec, bool track_off, bool map_off, bool need_gaussian_grads
+#define DGR_LIGHT_BWD_ARGS                                                                                                         \
+    background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tan_fovx, tan_fovy,     \
+        dL_dout_color, dL_dout_depth, dL_dout_median, dL_dout_var, gt_depth, sh, degree, campos, geomBuffer, R, binningBuffer,    \
+        imageBuffer, alphas, debug, perspec, track_off, map_off, need_gaussian_grads
+std::vector<Tensor> light_backward(DGR_LIGHT_BWD_PARAMS) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, nullptr); }
+// absgrad: light_backward's nine gradients and, tenth, the absolute screen-space gradient [P,3] (every row written)
+std::vector<Tensor> light_backward_absgrad(DGR_LIGHT_BWD_PARAMS) {
+    const long P = means3D.size(0);
+    Tensor abs = at::empty({P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D.device()));
+    std::vector<Tensor> g = light_backward_impl(DGR_LIGHT_BWD_ARGS, P > 0 ? abs.data_ptr<float>() : nullptr);
+    g.push_back(std::move(abs));
     return g;
 }
 
@@ -584,13 +605,14 @@ full_forward(const Tensor& background, const Tensor& means3D, const Tensor& colo
 }
 
 // F/rasterize_points.cu:122-239; returns the nine gradients in the reference's order, dL_dview as [4,4]
-std::vector<Tensor> full_backward(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
+// abs_out: as light_backward_impl's
+std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
                                   const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
                                   const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
                                   double tan_fovy, const Tensor& dL_dout_color, const Tensor& dL_dout_depth,
                                   const Tensor& dL_dout_unc, const Tensor& sh_, long degree, const Tensor& campos_,
                                   const Tensor& geomBuffer, long R, const Tensor& binningBuffer, const Tensor& imageBuffer,
-                                  long NG, const Tensor& perspec_, bool need_gaussian_grads) {
+                                  long NG, const Tensor& perspec_, bool need_gaussian_grads, float* abs_out) {
     (void)NG;
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
@@ -616,17 +638,36 @@ std::vector<Tensor> full_backward(const Tensor& background, const Tensor& means3
     const Tensor scratch = backward_scratch(dev, st, nscr, &resident);
     if (resident) dgr_backward_scratch_clean_arm();
     // gp: [0] means2D [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    const int rc = (dgr_full_backward(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+    const int rc = (dgr_full_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
                             ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier, ptr<float>(rotations),
                             ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
                             (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer), bytes(binningBuffer), bytes(imageBuffer),
                             ptr<float>(gC), ptr<float>(gD), gp[0], nullptr, gp[2], gp[1], gp[3], gp[4], gp[5], gp[6], gp[7], nullptr,
                             nullptr, nullptr, nullptr, nullptr, ptr<float>(perspec), nullptr, nullptr, nullptr,
                             dview.data_ptr<float>(), nullptr, nullptr, nullptr, ptr<float>(gt), ptr<float>(gU),
-                            (char*)scratch.data_ptr(), nscr));
+                            (char*)scratch.data_ptr(), nscr, abs_out));
     if (rc < 0 && resident) drop_scratch(dev, st);
     check(rc);
     g[8] = std::move(dview);
+    return g;
+}
+#define DGR_FULL_BWD_PARAMS                                                                                                          \
+    const Tensor &background, const Tensor &means3D, const Tensor &radii, const Tensor &colors, const Tensor &scales,               \
+        const Tensor &rotations, double scale_modifier, const Tensor &cov3D, const Tensor &viewmatrix, const Tensor &gt_depth,       \
+        const Tensor &projmatrix, double tan_fovx, double tan_fovy, const Tensor &dL_dout_color, const Tensor &dL_dout_depth,      \
+        const Tensor &dL_dout_unc, const Tensor &sh, long degree, const Tensor &campos, const Tensor &geomBuffer, long R,          \
+        const Tensor &binningBuffer, const Tensor &imageBuffer, long NG, const Tensor &perspec, bool need_gaussian_grads
+#define DGR_FULL_BWD_ARGS                                                                                                          \
+    background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrix, gt_depth, projmatrix, tan_fovx,     \
+        tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_unc, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, NG,   \
+        perspec, need_gaussian_grads
+std::vector<Tensor> full_backward(DGR_FULL_BWD_PARAMS) { return full_backward_impl(DGR_FULL_BWD_ARGS, nullptr); }
+// absgrad: full_backward's nine gradients and, tenth, the absolute screen-space gradient [P,3] (every row written)
+std::vector<Tensor> full_backward_absgrad(DGR_FULL_BWD_PARAMS) {
+    const long P = means3D.size(0);
+    Tensor abs = at::empty({P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D.device()));
+    std::vector<Tensor> g = full_backward_impl(DGR_FULL_BWD_ARGS, P > 0 ? abs.data_ptr<float>() : nullptr);
+    g.push_back(std::move(abs));
     return g;
 }
 
@@ -901,14 +942,19 @@ light_forward_batch(const Tensor& background, const Tensor& means3D_, const Tens
 
 // Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
 // the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).
-std::vector<Tensor> light_backward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
-                                         const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                                         const Tensor& viewmatrices_, const Tensor& projmatrices_, double tan_fovx, double tan_fovy,
-                                         const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_median,
-                                         const Tensor& dL_dout_var, const Tensor& gt_depths_, const Tensor& sh_, long degree,
-                                         const Tensor& campos_, const Tensor& geom, const Tensor& binning, const Tensor& img,
-                                         const Tensor& alphas_, const Tensor& perspec_, bool track_off, bool map_off,
-                                         bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered) {
+#define DGR_LIGHT_BWD_BATCH_PARAMS \
+    const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_, const Tensor& scales_, \
+        const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_, const Tensor& viewmatrices_, \
+        const Tensor& projmatrices_, double tan_fovx, double tan_fovy, const Tensor& dL_dout_color, \
+        const Tensor& dL_dout_depth, const Tensor& dL_dout_median, const Tensor& dL_dout_var, const Tensor& gt_depths_, \
+        const Tensor& sh_, long degree, const Tensor& campos_, const Tensor& geom, const Tensor& binning, const Tensor& img, \
+        const Tensor& alphas_, const Tensor& perspec_, bool track_off, bool map_off, bool need_gaussian_grads, \
+        bool need_means2D, const std::vector<long>& num_rendered
+#define DGR_LIGHT_BWD_BATCH_ARGS \
+    background, means3D_, radii, colors_, scales_, rotations_, scale_modifier, cov3D_, viewmatrices_, projmatrices_, tan_fovx, \
+        tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_median, dL_dout_var, gt_depths_, sh_, degree, campos_, geom, binning, \
+        img, alphas_, perspec_, track_off, map_off, need_gaussian_grads, need_means2D, num_rendered
+std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float* const* abs_views) {
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -949,11 +995,24 @@ std::vector<Tensor> light_backward_batch(const Tensor& background, const Tensor&
                                    row_bytes(scratch, v), nscr, (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0};
     }
     // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    check(dgr_light_backward_batch(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+    check(dgr_light_backward_batch_absgrad(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
                                    ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
                                    ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, gp[2], gp[1], gp[3],
-                                   gp[4], gp[5], gp[6], gp[7], track_off ? 1 : 0, map_off ? 1 : 0));
+                                   gp[4], gp[5], gp[6], gp[7], track_off ? 1 : 0, map_off ? 1 : 0, abs_views));
     g[8] = dview;
+    return g;
+}
+std::vector<Tensor> light_backward_batch(DGR_LIGHT_BWD_BATCH_PARAMS) {
+    return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, nullptr);
+}
+// absgrad: the nine results of light_backward_batch and, tenth, every view's absolute screen-space gradient [V,P,3]
+std::vector<Tensor> light_backward_batch_absgrad(DGR_LIGHT_BWD_BATCH_PARAMS) {
+    const long V = viewmatrices_.size(0), P = means3D_.size(0);
+    Tensor abs = at::empty({V, P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D_.device()));
+    float* av[DGR_MAX_BATCH_VIEWS] = {};
+    for (long v = 0; v < V && v < DGR_MAX_BATCH_VIEWS && P > 0; v++) av[v] = row<float>(abs, v);
+    std::vector<Tensor> g = light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, av);
+    g.push_back(std::move(abs));
     return g;
 }
 
@@ -1010,13 +1069,18 @@ full_forward_batch(const Tensor& background, const Tensor& means3D_, const Tenso
 // Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
 // the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).  An undefined or
 // empty dL_dout_unc: no view's loss used the uncertainty image (the lean blend backward).
-std::vector<Tensor> full_backward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
-                                        const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                                        const Tensor& viewmatrices_, const Tensor& projmatrices_, double tan_fovx, double tan_fovy,
-                                        const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_unc,
-                                        const Tensor& gt_depths_, const Tensor& sh_, long degree, const Tensor& campos_,
-                                        const Tensor& geom, const Tensor& binning, const Tensor& img, const Tensor& perspec_,
-                                        bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered) {
+#define DGR_FULL_BWD_BATCH_PARAMS \
+    const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_, const Tensor& scales_, \
+        const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_, const Tensor& viewmatrices_, \
+        const Tensor& projmatrices_, double tan_fovx, double tan_fovy, const Tensor& dL_dout_color, \
+        const Tensor& dL_dout_depth, const Tensor& dL_dout_unc, const Tensor& gt_depths_, const Tensor& sh_, long degree, \
+        const Tensor& campos_, const Tensor& geom, const Tensor& binning, const Tensor& img, const Tensor& perspec_, \
+        bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered
+#define DGR_FULL_BWD_BATCH_ARGS \
+    background, means3D_, radii, colors_, scales_, rotations_, scale_modifier, cov3D_, viewmatrices_, projmatrices_, tan_fovx, \
+        tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_unc, gt_depths_, sh_, degree, campos_, geom, binning, img, perspec_, \
+        need_gaussian_grads, need_means2D, num_rendered
+std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* const* abs_views) {
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -1055,11 +1119,24 @@ std::vector<Tensor> full_backward_batch(const Tensor& background, const Tensor& 
                                   (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0};
     }
     // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    check(dgr_full_backward_batch(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+    check(dgr_full_backward_batch_absgrad(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
                                   ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
                                   ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, gp[2], gp[1], gp[3],
-                                  gp[4], gp[5], gp[6], gp[7]));
+                                  gp[4], gp[5], gp[6], gp[7], abs_views));
     g[8] = dview;
+    return g;
+}
+std::vector<Tensor> full_backward_batch(DGR_FULL_BWD_BATCH_PARAMS) {
+    return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, nullptr);
+}
+// absgrad: the nine results of full_backward_batch and, tenth, every view's absolute screen-space gradient [V,P,3]
+std::vector<Tensor> full_backward_batch_absgrad(DGR_FULL_BWD_BATCH_PARAMS) {
+    const long V = viewmatrices_.size(0), P = means3D_.size(0);
+    Tensor abs = at::empty({V, P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D_.device()));
+    float* av[DGR_MAX_BATCH_VIEWS] = {};
+    for (long v = 0; v < V && v < DGR_MAX_BATCH_VIEWS && P > 0; v++) av[v] = row<float>(abs, v);
+    std::vector<Tensor> g = full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, av);
+    g.push_back(std::move(abs));
     return g;
 }
 
@@ -1097,6 +1174,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("light_backward_batch", &light_backward_batch);
     m.def("full_forward_batch", &full_forward_batch);
     m.def("full_backward_batch", &full_backward_batch);
+    m.def("light_backward_absgrad", &light_backward_absgrad);
+    m.def("full_backward_absgrad", &full_backward_absgrad);
+    m.def("light_backward_batch_absgrad", &light_backward_batch_absgrad);
+    m.def("full_backward_batch_absgrad", &full_backward_batch_absgrad);
     m.def("host_prof_dump", &host_prof_dump);
     m.def("light_apply", &light_apply);
     m.def("full_apply", &full_apply);

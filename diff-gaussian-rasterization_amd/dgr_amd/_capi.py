@@ -128,6 +128,12 @@ _SIGS = {
     "dgr_profile_stage_name": (C.c_char_p, [_i]),
     "dgr_profile_read": (_i, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(_i)]),
 }
+# absgrad (dgr_hip.h): each takes its namesake's arguments plus the absgrad output -- one device pointer, or (batches) a host array
+# of n_views device pointers
+_SIGS["dgr_light_backward_absgrad"] = (_i, _SIGS["dgr_light_backward"][1] + [_vp])
+_SIGS["dgr_full_backward_absgrad"] = (_i, _SIGS["dgr_full_backward"][1] + [_vp])
+_SIGS["dgr_light_backward_batch_absgrad"] = (_i, _SIGS["dgr_light_backward_batch"][1] + [C.POINTER(_vp)])
+_SIGS["dgr_full_backward_batch_absgrad"] = (_i, _SIGS["dgr_full_backward_batch"][1] + [C.POINTER(_vp)])
 
 _lib = None
 

@@ -16,6 +16,7 @@ the C ABI's batched entry points (include/dgr_hip.h: dgr_light_forward_batch / d
 
 torch supplies device memory and the current stream; every compute call goes through the C ABI.  There is no CPU fallback.
 """
+import ctypes as C
 from typing import NamedTuple
 
 import torch
@@ -173,14 +174,16 @@ def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifi
 
 def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
                     tanfovx, tanfovy, gC, gD, gM, gV, gt_depths, sh, degree, campos, geom, binning, img, alphas,
-                    perspec_matrix, track_off, map_off, need_gaussian_grads, need_means2D, num_rendered=None):
+                    perspec_matrix, track_off, map_off, need_gaussian_grads, need_means2D, num_rendered=None, absgrad=False):
     """`num_rendered`: per view, what the one-view backward takes as R (>= the view's instance count); read by the library only
-    under deterministic_grads, where it sizes the views' row buffers."""
+    under deterministic_grads, where it sizes the views' row buffers.  `absgrad=True` (dgr_light_backward_batch_absgrad) appends
+    a tenth result, every view's absolute screen-space gradient [V,P,3]."""
     V_ = viewmatrices.size(0)
     num_rendered = [int(r) for r in (num_rendered if num_rendered is not None else [0] * V_)]
     ext = _ext()
     if ext is not None:
-        g = ext.light_backward_batch(bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
+        fn = ext.light_backward_batch_absgrad if absgrad else ext.light_backward_batch
+        g = fn(bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                      viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD, gM, gV, gt_depths, sh,
                                      int(degree), campos, geom, binning, img, alphas, perspec_matrix, bool(track_off),
                                      bool(map_off), bool(need_gaussian_grads), bool(need_means2D), num_rendered)
@@ -220,11 +223,15 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
         w.num_rendered = num_rendered[v]
     p = _capi.ptr
     q = lambda t: None if t is None else p(t)  # noqa: E731
-    _light._check(lib.dgr_light_backward_batch(
-        _capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
-        float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), q(dop), q(dcol), q(d3), q(dcov),
-        q(dsh), q(dsc), q(drot), int(bool(track_off)), int(bool(map_off))))
-    return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview
+    args = (_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
+            float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), q(dop), q(dcol), q(d3), q(dcov),
+            q(dsh), q(dsc), q(drot), int(bool(track_off)), int(bool(map_off)))
+    if not absgrad:
+        _light._check(lib.dgr_light_backward_batch(*args))
+        return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview
+    dabs = torch.empty((V, P, 3), **f32)
+    _light._check(lib.dgr_light_backward_batch_absgrad(*args, (C.c_void_p * V)(*(_row(dabs, v) for v in range(V)))))
+    return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview, dabs
 
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
@@ -255,19 +262,39 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
          gt_depths) = ctx.saved_tensors
         V, H, W = viewmatrices.size(0), int(rs.image_height), int(rs.image_width)
         zeros = lambda ch: torch.zeros((V, ch, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
+        absgrad = getattr(ctx, "absgrad", False)  # (_RasterizeGaussiansBatchAbs)
         grad_color = zeros(3) if grad_color is None else grad_color
         grad_depth = zeros(1) if grad_depth is None else grad_depth
         grad_depth_median = zeros(1) if grad_depth_median is None else grad_depth_median
         grad_depth_var = zeros(1) if grad_depth_var is None else grad_depth_var
         need = ctx.needs_input_grad
         with _capi.on_device(means3D.device), _capi.under_options(ctx.dgr_options):
-            (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = _backward_batch(
+            g = _backward_batch(
                 rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
                 rs.projmatrices, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_depth_median, grad_depth_var, gt_depths, sh,
                 rs.sh_degree, rs.campos, geom, binning, img, opacity_map, rs.perspec_matrix, rs.track_off, rs.map_off,
-                need_gaussian_grads=any(need[:8]), need_means2D=bool(need[1]), num_rendered=ctx.num_rendered)
+                need_gaussian_grads=any(need[:8]) or absgrad, need_means2D=bool(need[1]), num_rendered=ctx.num_rendered,
+                **({"absgrad": True} if absgrad else {}))
+        (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = g[:9]
         _light._consume_post_backward_wait()
-        return g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None
+        grads = (g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None)
+        return grads + (g[9],) if absgrad else grads
+
+
+class _RasterizeGaussiansBatchAbs(torch.autograd.Function):
+    """_RasterizeGaussiansBatch with one more leaf, means2D_abs [V,P,3], whose gradient is every view's absolute screen-space
+    gradient (absgrad, include/dgr_hip.h: dgr_light_backward_batch_absgrad)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
+                gt_depths, raster_settings, means2D_abs):
+        ctx.absgrad = True
+        return _RasterizeGaussiansBatch.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                cov3Ds_precomp, viewmatrices, gt_depths, raster_settings)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return _RasterizeGaussiansBatch.backward(ctx, *grads)
 
 
 def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
@@ -287,7 +314,9 @@ class GaussianRasterizerBatch(torch.nn.Module):
         self.raster_settings = raster_settings
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, viewmatrices=None, gt_depths=None):
+                cov3D_precomp=None, viewmatrices=None, gt_depths=None, *, means2D_abs=None):
+        # means2D_abs (absgrad): a float32 [V,P,3] leaf whose .grad receives every view's absolute screen-space gradient
+        # (dgr_amd.light.GaussianRasterizer.forward)
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -301,5 +330,10 @@ class GaussianRasterizerBatch(torch.nn.Module):
         cov3D_precomp = e if cov3D_precomp is None else cov3D_precomp
         if viewmatrices is None:
             viewmatrices = self.raster_settings.viewmatrices
+        if means2D_abs is not None:
+            _light.check_means2D_abs(means2D_abs, means3D, self.raster_settings.map_off,
+                                     shape=(viewmatrices.size(0), means3D.size(0), 3))
+            return _RasterizeGaussiansBatchAbs.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                     cov3D_precomp, viewmatrices, gt_depths, self.raster_settings, means2D_abs)
         return rasterize_gaussians_batch(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                          viewmatrices, gt_depths, self.raster_settings)

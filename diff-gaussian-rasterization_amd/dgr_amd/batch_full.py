@@ -12,6 +12,7 @@ The binning capacity and status policy is `dgr_amd.light`'s (`_binning_policy`: 
 runs an unsettled shape strict).  A lazy forward hands its backward the capacity its binning buffers were carved with as R
 (deterministic gradients size their row buffers by it), never the largest count seen.  There is no CPU fallback.
 """
+import ctypes as C
 import weakref
 
 import torch
@@ -129,16 +130,18 @@ def _forward_batch_ctypes(bg, means3D, colors, opacity, scales, rotations, scale
 
 def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
                     tanfovx, tanfovy, gC, gD, gU, gt_depths, sh, degree, campos, geom, binning, img, perspec_matrix,
-                    need_gaussian_grads, need_means2D, num_rendered):
+                    need_gaussian_grads, need_means2D, num_rendered, absgrad=False):
     """gU None: no view's loss used the uncertainty image (the lean blend backward).  `num_rendered`: per view, the R of the
     one-view backward (>= the view's count; sizes the row buffers under deterministic_grads).  Returns (dL_dmeans2D [V,P,3] or
-    None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview [V,4,4])."""
+    None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview [V,4,4]); absgrad=True
+    (dgr_full_backward_batch_absgrad) appends every view's absolute screen-space gradient [V,P,3]."""
     num_rendered = [int(r) for r in num_rendered]
     dev = means3D.device
     ext = _ext()
     if ext is not None:
         e = torch.empty(0, device=dev)
-        return tuple(ext.full_backward_batch(bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
+        fn = ext.full_backward_batch_absgrad if absgrad else ext.full_backward_batch
+        return tuple(fn(bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                                              viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD,
                                              e if gU is None else gU, gt_depths, sh, int(degree), campos, geom, binning, img,
                                              perspec_matrix, bool(need_gaussian_grads), bool(need_means2D), num_rendered))
@@ -176,11 +179,15 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
         w.num_rendered = num_rendered[v]
     p = _capi.ptr
     q = lambda t: None if t is None else p(t)  # noqa: E731
-    _light._check(lib.dgr_full_backward_batch(
-        _capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
-        float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), q(dop), q(dcol), q(d3), q(dcov),
-        q(dsh), q(dsc), q(drot)))
-    return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview
+    args = (_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
+            float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), q(dop), q(dcol), q(d3), q(dcov),
+            q(dsh), q(dsc), q(drot))
+    if not absgrad:
+        _light._check(lib.dgr_full_backward_batch(*args))
+        return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview
+    dabs = torch.empty((V, P, 3), **f32)
+    _light._check(lib.dgr_full_backward_batch_absgrad(*args, (C.c_void_p * V)(*(_row(dabs, v) for v in range(V)))))
+    return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview, dabs
 
 
 class _RasterizeGaussiansBatchFull(torch.autograd.Function):
@@ -215,17 +222,35 @@ class _RasterizeGaussiansBatchFull(torch.autograd.Function):
         grad_depth = zeros(1) if grad_depth is None else grad_depth
         need = ctx.needs_input_grad
         with _capi.on_device(means3D.device), _capi.under_options(ctx.dgr_options):
-            (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = _backward_batch(
+            absgrad = getattr(ctx, "absgrad", False)  # (_RasterizeGaussiansBatchFullAbs)
+            g = _backward_batch(
                 rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
                 rs.projmatrices, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_unc, gt_depths, sh, rs.sh_degree,
-                rs.campos, geom, binning, img, rs.perspec_matrix, need_gaussian_grads=any(need[:8]),
-                need_means2D=bool(need[1]), num_rendered=ctx.num_rendered)
+                rs.campos, geom, binning, img, rs.perspec_matrix, need_gaussian_grads=any(need[:8]) or absgrad,
+                need_means2D=bool(need[1]), num_rendered=ctx.num_rendered, **({"absgrad": True} if absgrad else {}))
+        (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = g[:9]
         _light._consume_post_backward_wait()
-        return g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None
+        grads = (g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None)
+        return grads + (g[9],) if absgrad else grads
+
+
+class _RasterizeGaussiansBatchFullAbs(torch.autograd.Function):
+    """_RasterizeGaussiansBatchFull with one more leaf, means2D_abs [V,P,3] (absgrad: dgr_amd.batch._RasterizeGaussiansBatchAbs)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
+                gt_depths, raster_settings, means2D_abs):
+        ctx.absgrad = True
+        return _RasterizeGaussiansBatchFull.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                    cov3Ds_precomp, viewmatrices, gt_depths, raster_settings)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return _RasterizeGaussiansBatchFull.backward(ctx, *grads)
 
 
 def rasterize_gaussians_batch_full(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                                   viewmatrices, gt_depths, raster_settings):
+                                   viewmatrices, gt_depths, raster_settings, means2D_abs=None):
     """The full variant's `rasterize_gaussians` for V cameras: `means2D` is [V,P,3] (or a tensor that requires no gradient),
     `viewmatrices` [V,4,4], `gt_depths` [V,H,W] (read by the backward); returns color [V,3,H,W], radii [V,P], depth [V,1,H,W]
     and uncertainty [V,1,H,W]."""
@@ -234,6 +259,10 @@ def rasterize_gaussians_batch_full(means3D, means2D, sh, colors_precomp, opaciti
     if gt_depths is None:
         raise ValueError("the full variant's batch needs gt_depths (its backward reads them)")
     _check_inputs(means3D, viewmatrices)
+    if means2D_abs is not None:  # (absgrad: GaussianRasterizerBatchFull.forward)
+        _light.check_means2D_abs(means2D_abs, means3D, False, shape=(viewmatrices.size(0), means3D.size(0), 3))
+        return _RasterizeGaussiansBatchFullAbs.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                                     cov3Ds_precomp, viewmatrices, gt_depths, raster_settings, means2D_abs)
     return _RasterizeGaussiansBatchFull.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                               viewmatrices, gt_depths, raster_settings)
 
@@ -246,7 +275,8 @@ class GaussianRasterizerBatchFull(torch.nn.Module):
         self.raster_settings = raster_settings
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, viewmatrices=None, gt_depths=None):
+                cov3D_precomp=None, viewmatrices=None, gt_depths=None, *, means2D_abs=None):
+        # means2D_abs (absgrad): a float32 [V,P,3] leaf whose .grad receives every view's absolute screen-space gradient
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
@@ -261,4 +291,4 @@ class GaussianRasterizerBatchFull(torch.nn.Module):
         if viewmatrices is None:
             viewmatrices = self.raster_settings.viewmatrices
         return rasterize_gaussians_batch_full(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                              viewmatrices, gt_depths, self.raster_settings)
+                                              viewmatrices, gt_depths, self.raster_settings, means2D_abs=means2D_abs)

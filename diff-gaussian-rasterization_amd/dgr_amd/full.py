@@ -127,9 +127,10 @@ class _C:
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                      cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
                                      dL_dout_color, dL_dout_depth, dL_dout_uncertainty, sh, degree, campos, geomBuffer,
-                                     R, binningBuffer, imageBuffer, NG, perspec_matrix, need_gaussian_grads=True):
+                                     R, binningBuffer, imageBuffer, NG, perspec_matrix, need_gaussian_grads=True, absgrad=False):
         # F/rasterize_points.cu:122-239.  need_gaussian_grads=False (tracking: no Gaussian input requires a gradient) returns
-        # None for the eight per-Gaussian gradients and skips their dense rows; the pose gradient is the same.
+        # None for the eight per-Gaussian gradients and skips their dense rows; the pose gradient is the same.  absgrad=True
+        # (dgr_full_backward_absgrad) appends a tenth result, the absolute screen-space gradient [P,3].
         lib = _capi.load()
         dev = means3D.device
         P = means3D.size(0)
@@ -147,15 +148,20 @@ class _C:
         dL_dview = torch.empty((4, 4), **f32)
         scratch = torch.empty((max(lib.dgr_light_backward_scratch_bytes_r(P, W, H, int(R)), 1),), dtype=torch.uint8, device=dev)
         p = lambda t: None if t is None else _capi.ptr(t)  # noqa: E731
-        _check(lib.dgr_full_backward(
-            _capi.stream_handle(dev.index), P, int(degree), M, int(R), p(background), W, H, p(means3D), p(sh), p(colors),
-            p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos),
-            float(tan_fovx), float(tan_fovy), p(radii), p(geomBuffer), p(binningBuffer), p(imageBuffer), p(gC), p(gD),
-            p(seg["means2D"]), None, p(seg["opacity"]), p(seg["colors"]), p(seg["means3D"]), p(seg["cov3D"]),
-            p(seg["sh"]), p(seg["scales"]), p(seg["rotations"]), None, None, None, None, None, p(perspec_matrix), None,
-            None, None, p(dL_dview), None, None, None, p(gt_depth), p(gU), p(scratch), scratch.numel()))
-        return (seg["means2D"], seg["colors"], seg["opacity"], seg["means3D"], seg["cov3D"], seg["sh"], seg["scales"],
-                seg["rotations"], dL_dview)
+        args = (_capi.stream_handle(dev.index), P, int(degree), M, int(R), p(background), W, H, p(means3D), p(sh), p(colors),
+                p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos),
+                float(tan_fovx), float(tan_fovy), p(radii), p(geomBuffer), p(binningBuffer), p(imageBuffer), p(gC), p(gD),
+                p(seg["means2D"]), None, p(seg["opacity"]), p(seg["colors"]), p(seg["means3D"]), p(seg["cov3D"]),
+                p(seg["sh"]), p(seg["scales"]), p(seg["rotations"]), None, None, None, None, None, p(perspec_matrix), None,
+                None, None, p(dL_dview), None, None, None, p(gt_depth), p(gU), p(scratch), scratch.numel())
+        out = (seg["means2D"], seg["colors"], seg["opacity"], seg["means3D"], seg["cov3D"], seg["sh"], seg["scales"],
+               seg["rotations"], dL_dview)
+        if not absgrad:
+            _check(lib.dgr_full_backward(*args))
+            return out
+        dL_dmeans2D_abs = torch.empty((P, 3), **f32)
+        _check(lib.dgr_full_backward_absgrad(*args, p(dL_dmeans2D_abs)))
+        return out + (dL_dmeans2D_abs,)
 
     @_device_guarded(0)
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -195,8 +201,9 @@ class _CompiledC:
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                      viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                      dL_dout_uncertainty, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, NG,
-                                     perspec_matrix, need_gaussian_grads=True):
-        return tuple(_CompiledC.ext.full_backward(
+                                     perspec_matrix, need_gaussian_grads=True, absgrad=False):
+        fn = _CompiledC.ext.full_backward_absgrad if absgrad else _CompiledC.ext.full_backward
+        return tuple(fn(
             background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix, gt_depth,
             projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_uncertainty, sh, int(degree),
             campos, geomBuffer, int(R), binningBuffer, imageBuffer, int(NG), perspec_matrix, bool(need_gaussian_grads)))
@@ -294,8 +301,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         # outputs that did not take part in the loss arrive as None: zeros, as the reference's autograd would have passed
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
         zeros = lambda c: torch.zeros((c, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
+        absgrad = getattr(ctx, "absgrad", False)  # (_RasterizeGaussiansAbs)
         grad_out_color = zeros(3) if grad_out_color is None else grad_out_color
         grad_out_depth = zeros(1) if grad_out_depth is None else grad_out_depth
+        if absgrad and grad_out_uncertainty is None:  # NULL: the lean blend backward (bit-identical to a zero image)
+            grad_out_uncertainty = _light._EMPTY
         grad_out_uncertainty = zeros(1) if grad_out_uncertainty is None else grad_out_uncertainty
         # argument packing of F/diff_gaussian_rasterization/__init__.py:104-131
         args = (raster_settings.bg,
@@ -324,8 +334,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                 num_related_gaussians,
                 raster_settings.perspec_matrix)
         with _capi.under_options(ctx.dgr_options):  # (the autograd engine may run this on a thread of its own)
-            (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-             grad_rotations, grad_viewmatrix) = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]))
+            if absgrad:
+                out = _C.rasterize_gaussians_backward(*args, absgrad=True)
+            else:
+                out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]))
+        grad_means2D_abs = out[9] if absgrad else None
+        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
+         grad_rotations, grad_viewmatrix) = out[:9]
         _light._consume_post_backward_wait()  # (dgr_amd.multiview.ViewStreams.before_backward)
         grads = (
             grad_means3D,
@@ -340,7 +355,22 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
         )
-        return grads
+        return grads + (grad_means2D_abs,) if absgrad else grads
+
+
+class _RasterizeGaussiansAbs(torch.autograd.Function):
+    """_RasterizeGaussians with one more leaf, means2D_abs [P,3] (absgrad: dgr_amd.light._RasterizeGaussiansAbs)."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
+                gt_depth, raster_settings, means2D_abs):
+        ctx.absgrad = True
+        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                           cov3Ds_precomp, viewmatrix, gt_depth, raster_settings)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return _RasterizeGaussians.backward(ctx, *grads)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -373,8 +403,11 @@ class GaussianRasterizer(nn.Module):
         return visible
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, viewmatrix=None, gt_depth=None):
+                cov3D_precomp=None, viewmatrix=None, gt_depth=None, *, means2D_abs=None):
+        # means2D_abs (absgrad, an extension): as dgr_amd.light.GaussianRasterizer.forward's
         raster_settings = self.raster_settings
+        if means2D_abs is not None:
+            _light.check_means2D_abs(means2D_abs, means3D, False)
 
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -394,5 +427,8 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = _light._EMPTY
 
+        if means2D_abs is not None:
+            return _RasterizeGaussiansAbs.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                cov3D_precomp, viewmatrix, gt_depth, raster_settings, means2D_abs)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    viewmatrix, gt_depth, raster_settings)

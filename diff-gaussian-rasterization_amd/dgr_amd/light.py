@@ -363,10 +363,11 @@ class _C:
                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                      dL_dout_depth, dL_dout_median_depth, dL_dout_depth_var, gt_depth, sh, degree,
                                      campos, geomBuffer, R, binningBuffer, imageBuffer, alphas, debug,
-                                     perspec_matrix, track_off, map_off, need_gaussian_grads=True):
+                                     perspec_matrix, track_off, map_off, need_gaussian_grads=True, absgrad=False):
         # L/rasterize_points.cu:131-236.  `need_gaussian_grads=False` (an extension: the autograd Function passes it when
         # no Gaussian input requires a gradient, i.e. tracking) returns None for the eight per-Gaussian gradients and lets
-        # the library skip their dense rows; the pose gradient is the same.
+        # the library skip their dense rows; the pose gradient is the same.  `absgrad=True` (dgr_light_backward_absgrad)
+        # appends a tenth result, the absolute screen-space gradient [P,3].
         lib = _capi.load()
         dev = means3D.device
         P = means3D.size(0)
@@ -395,16 +396,21 @@ class _C:
         scratch = torch.empty((max(lib.dgr_light_backward_scratch_bytes_r(P, W, H, int(R)), 1),), dtype=torch.uint8, device=dev)
         p = _capi.ptr
         q = lambda t: None if t is None else p(t)  # noqa: E731
-        _check(lib.dgr_light_backward(
-            _capi.stream_handle(dev.index), P, int(degree), M, int(R), p(background), W, H, p(means3D), p(sh), p(colors),
-            p(alphas), p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix),
-            p(projmatrix), p(campos), float(tan_fovx), float(tan_fovy), p(radii), p(geomBuffer), p(binningBuffer),
-            p(imageBuffer), p(gC), p(gD), p(gM), p(gV), q(dL_dmeans2D), None, q(dL_dopacity), q(dL_dcolors), None,
-            q(dL_dmeans3D), q(dL_dcov3D), q(dL_dsh), q(dL_dscales), q(dL_drotations), int(bool(debug)), None,
-            p(perspec_matrix), p(dL_dview), None, p(gt_depth), int(bool(track_off)), int(bool(map_off)),
-            p(scratch), scratch.numel()))
+        args = (_capi.stream_handle(dev.index), P, int(degree), M, int(R), p(background), W, H, p(means3D), p(sh), p(colors),
+                p(alphas), p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix),
+                p(projmatrix), p(campos), float(tan_fovx), float(tan_fovy), p(radii), p(geomBuffer), p(binningBuffer),
+                p(imageBuffer), p(gC), p(gD), p(gM), p(gV), q(dL_dmeans2D), None, q(dL_dopacity), q(dL_dcolors), None,
+                q(dL_dmeans3D), q(dL_dcov3D), q(dL_dsh), q(dL_dscales), q(dL_drotations), int(bool(debug)), None,
+                p(perspec_matrix), p(dL_dview), None, p(gt_depth), int(bool(track_off)), int(bool(map_off)),
+                p(scratch), scratch.numel())
+        if not absgrad:
+            _check(lib.dgr_light_backward(*args))
+            return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
+                    dL_dview)
+        dL_dmeans2D_abs = torch.empty((P, 3), **f32)
+        _check(lib.dgr_light_backward_absgrad(*args, p(dL_dmeans2D_abs)))
         return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-                dL_dview)
+                dL_dview, dL_dmeans2D_abs)
 
     @_device_guarded(0)
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -456,8 +462,9 @@ class _CompiledC:
                                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                      dL_dout_median_depth, dL_dout_depth_var, gt_depth, sh, degree, campos, geomBuffer, R,
                                      binningBuffer, imageBuffer, alphas, debug, perspec_matrix, track_off, map_off,
-                                     need_gaussian_grads=True):
-        g = _CompiledC.ext.light_backward(
+                                     need_gaussian_grads=True, absgrad=False):
+        fn = _CompiledC.ext.light_backward_absgrad if absgrad else _CompiledC.ext.light_backward
+        g = fn(
             background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
             projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_median_depth,
             dL_dout_depth_var, gt_depth, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, alphas,
@@ -614,8 +621,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         # reference's autograd would have passed
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
         zeros = lambda c: torch.zeros((c, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
+        absgrad = getattr(ctx, "absgrad", False)  # (_RasterizeGaussiansAbs)
         grad_color = zeros(3) if grad_color is None else grad_color
         grad_depth = zeros(1) if grad_depth is None else grad_depth
+        if absgrad:  # an unused median / variance output: NULL, the lean blend backward (bit-identical to zero images)
+            grad_depth_median = _EMPTY if grad_depth_median is None else grad_depth_median
+            grad_depth_var = _EMPTY if grad_depth_var is None else grad_depth_var
         grad_depth_median = zeros(1) if grad_depth_median is None else grad_depth_median
         grad_depth_var = zeros(1) if grad_depth_var is None else grad_depth_var
 
@@ -654,14 +665,19 @@ class _RasterizeGaussians(torch.autograd.Function):
             if raster_settings.debug:
                 cpu_args = cpu_deep_copy_tuple(args)
                 try:
-                    out = _C.rasterize_gaussians_backward(*args)
+                    out = _C.rasterize_gaussians_backward(*args, **({"absgrad": True} if absgrad else {}))
                 except Exception as ex:
                     torch.save(cpu_args, "snapshot_bw.dump")
                     print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
                     raise ex
             else:
                 # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp): tracking needs none
-                out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]))
+                if absgrad:
+                    out = _C.rasterize_gaussians_backward(*args, absgrad=True)
+                else:
+                    out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]))
+        grad_means2D_abs = out[9] if absgrad else None
+        out = out[:9]
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, grad_viewmatrix) = out
         # reference: torch.sum(grad_viewmatrix, dim=0) over a [H*W,4,4] buffer (__init__.py:160-161);
@@ -682,7 +698,35 @@ class _RasterizeGaussians(torch.autograd.Function):
             None,
             None,
         )
-        return grads
+        return grads + (grad_means2D_abs,) if absgrad else grads
+
+
+class _RasterizeGaussiansAbs(torch.autograd.Function):
+    """_RasterizeGaussians with one more leaf, means2D_abs [P,3], whose gradient is the absolute screen-space gradient (absgrad,
+    include/dgr_hip.h: dgr_light_backward_absgrad).  Over either binding's forward and backward: the compiled LightNode has no
+    such input."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
+                gt_depth, raster_settings, means2D_abs):
+        ctx.absgrad = True
+        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                           cov3Ds_precomp, viewmatrix, gt_depth, raster_settings)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        return _RasterizeGaussians.backward(ctx, *grads)
+
+
+def check_means2D_abs(means2D_abs, means3D, map_off, shape=None):
+    """The checks of a `means2D_abs` leaf (GaussianRasterizer.forward and the batch classes): float32, on the Gaussians'
+    device, [P,3] (or `shape`), and not with map_off (tracking forms no per-Gaussian gradients)."""
+    if map_off:
+        raise ValueError("means2D_abs: absgrad is a mapping gradient; not with map_off=True")
+    shape = (means3D.size(0), 3) if shape is None else shape
+    if means2D_abs.dtype != torch.float32 or tuple(means2D_abs.shape) != tuple(shape) or means2D_abs.device != means3D.device:
+        raise ValueError(f"means2D_abs: a float32 tensor of shape {tuple(shape)} on {means3D.device} "
+                         f"(got {means2D_abs.dtype} {tuple(means2D_abs.shape)} on {means2D_abs.device})")
 
 
 _EMPTY = torch.Tensor([])  # stands for "None" at the C++ boundary (L/__init__.py:223-232)
@@ -722,8 +766,12 @@ class GaussianRasterizer(nn.Module):
         return visible
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None, viewmatrix=None, gt_depth=None):
+                cov3D_precomp=None, viewmatrix=None, gt_depth=None, *, means2D_abs=None):
+        # means2D_abs (absgrad, an extension): a float32 [P,3] leaf whose .grad receives the absolute screen-space gradient
+        # sum_p |dL/dmean2D contribution of pixel p| per Gaussian (AbsGS; include/dgr_hip.h: dgr_light_backward_absgrad)
         raster_settings = self.raster_settings
+        if means2D_abs is not None:
+            check_means2D_abs(means2D_abs, means3D, raster_settings.map_off)
 
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
@@ -744,6 +792,9 @@ class GaussianRasterizer(nn.Module):
         if cov3D_precomp is None:
             cov3D_precomp = _EMPTY
 
+        if means2D_abs is not None:
+            return _RasterizeGaussiansAbs.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                cov3D_precomp, viewmatrix, gt_depth, raster_settings, means2D_abs)
         return rasterize_gaussians(
             means3D,
             means2D,

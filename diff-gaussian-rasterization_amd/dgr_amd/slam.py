@@ -245,7 +245,7 @@ _ZERO_POINTS = {}  # (device, P) -> a [P, 3] zero tensor for calls whose screen-
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, viewmatrix=None, fov=None,
-           HW=None, gt_depth=None, track_off=False, map_off=False, variant="light", pose_tensors=None):
+           HW=None, gt_depth=None, track_off=False, map_off=False, variant="light", pose_tensors=None, absgrad=False):
     """CG-SLAM's `render()` (reference README.md:33,71).
 
     `pc`: anything with the 3DGS GaussianModel accessors `get_xyz`, `get_opacity`, `get_scaling`, `get_rotation`,
@@ -257,7 +257,9 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     from `viewmatrix` with a dozen small torch kernels (a 640x480 tracking iteration is bound by exactly those).
     Returns the reference's dict (light: render, depth, depth_median, opacity_map, depth_var, gau_uncertainty,
     num_related_pixels; full: render, depth, opacity_map) plus the 3DGS bookkeeping entries viewspace_points,
-    visibility_filter, radii."""
+    visibility_filter, radii.  `absgrad=True` (AbsGS densification, a mapping render) adds `viewspace_points_abs`, a zero leaf
+    shaped like `viewspace_points` whose `.grad` receives the absolute screen-space gradient (GaussianRasterizer.forward's
+    `means2D_abs`): feed it to `optim.add_densification_stats` in place of `viewspace_points.grad`."""
     if viewmatrix is None or fov is None or HW is None:
         raise ValueError("render() needs viewmatrix=W2C^T, fov=(tanfovx, tanfovy) and HW=(H, W)")
     mod = _light if variant == "light" else _full
@@ -331,9 +333,15 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         settings = mod.GaussianRasterizationSettings(**common, perspec_matrix=perspec)
     rasterizer = mod.GaussianRasterizer(raster_settings=settings)
     shs, colors = (None, override_color) if override_color is not None else (shs_or_colors, None)
-    out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
-                     colors_precomp=colors, scales=scaling, rotations=rotation, cov3D_precomp=None,
-                     viewmatrix=viewmatrix, gt_depth=gt_depth)
+    if absgrad:
+        abs_points = torch.zeros_like(means3D, requires_grad=True)
+        out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
+                         colors_precomp=colors, scales=scaling, rotations=rotation, cov3D_precomp=None,
+                         viewmatrix=viewmatrix, gt_depth=gt_depth, means2D_abs=abs_points)
+    else:
+        out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
+                         colors_precomp=colors, scales=scaling, rotations=rotation, cov3D_precomp=None,
+                         viewmatrix=viewmatrix, gt_depth=gt_depth)
     if variant == "light":
         color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels = out
         res = {"render": color, "depth": depth, "depth_median": depth_median, "opacity_map": opacity_map,
@@ -342,17 +350,20 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         color, radii, depth, uncertainty = out
         res = {"render": color, "depth": depth, "opacity_map": uncertainty}
     res.update(viewspace_points=screenspace_points, visibility_filter=radii > 0, radii=radii)
+    if absgrad:
+        res["viewspace_points_abs"] = abs_points
     return res
 
 
 def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, track_off=False, map_off=False,
-                 variant="light"):
+                 variant="light", absgrad=False):
     """`render()` for the V cameras of a keyframe batch in ONE call of the batched entry points (`dgr_amd.batch`, SURVEY.md
     s8(f) item 2; `variant="full"`: `dgr_amd.batch_full`): the cameras share `fov` and `HW` (one sensor, V poses), every
     per-view entry of `render()`'s dict comes back with a leading view dimension, and one backward through it yields the
     Gaussians' gradients already summed over the views, the pose gradient per `viewmatrix` and `viewspace_points.grad`
     ([V,P,3]) per view.  `cameras`: sequence of dicts with `viewmatrix` (W2C^T), `fov`, `HW`, `gt_depth` and optionally
-    `viewpoint_camera`.  The full variant has no track_off / map_off."""
+    `viewpoint_camera`.  The full variant has no track_off / map_off.  `absgrad=True`: as in `render()`, with
+    `viewspace_points_abs` [V,P,3]."""
     from . import batch as _batch
     if variant not in ("light", "full"):
         raise ValueError(f"unknown variant {variant!r}")
@@ -413,6 +424,8 @@ def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_col
     opacity, scaling, rotation = pc.get_opacity, pc.get_scaling, pc.get_rotation
     mapping = not map_off and any(t.requires_grad for t in (means3D, shs_or_colors, opacity, scaling, rotation))
     screenspace_points = torch.zeros((len(cameras),) + tuple(means3D.shape), dtype=means3D.dtype, device=dev, requires_grad=mapping)
+    # (absgrad: a [V,P,3] leaf of its own; None leaves the calls below as they are)
+    abs_points = torch.zeros_like(screenspace_points, requires_grad=True) if absgrad else None
     debug = bool(getattr(pipe, "debug", False)) if pipe is not None else False
     settings = _batch.BatchRasterizationSettings(
         image_height=H, image_width=W, tanfovx=tanfovx, tanfovy=tanfovy, bg=bg_color, scale_modifier=scaling_modifier,
@@ -423,22 +436,28 @@ def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_col
         from .batch_full import GaussianRasterizerBatchFull
         color, radii, depth, uncertainty = GaussianRasterizerBatchFull(settings)(
             means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors, scales=scaling, rotations=rotation,
-            viewmatrices=viewmatrices, gt_depths=gt_depths)
-        return {"render": color, "depth": depth, "opacity_map": uncertainty, "viewspace_points": screenspace_points,
-                "visibility_filter": radii > 0, "radii": radii}
+            viewmatrices=viewmatrices, gt_depths=gt_depths, means2D_abs=abs_points)
+        res = {"render": color, "depth": depth, "opacity_map": uncertainty, "viewspace_points": screenspace_points,
+               "visibility_filter": radii > 0, "radii": radii}
+        if absgrad:
+            res["viewspace_points_abs"] = abs_points
+        return res
     color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels = \
         _batch.GaussianRasterizerBatch(settings)(means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors,
                                                  scales=scaling, rotations=rotation, viewmatrices=viewmatrices,
-                                                 gt_depths=gt_depths)
-    return {"render": color, "depth": depth, "depth_median": depth_median, "opacity_map": opacity_map, "depth_var": depth_var,
-            "gau_uncertainty": gau_uncertainty, "num_related_pixels": gau_related_pixels,
-            "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+                                                 gt_depths=gt_depths, means2D_abs=abs_points)
+    res = {"render": color, "depth": depth, "depth_median": depth_median, "opacity_map": opacity_map, "depth_var": depth_var,
+           "gau_uncertainty": gau_uncertainty, "num_related_pixels": gau_related_pixels,
+           "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
+    if absgrad:
+        res["viewspace_points_abs"] = abs_points
+    return res
 
 
 class _ViewOf(_Mapping):
     """View k of `render_views`' dict: entry n is `out[n][k]`, sliced when it is first asked for (a loss reads two or three
-    of the ten; every slice is an autograd node and a launch-free but not cost-free call) -- except `viewspace_points`,
-    which stays the whole [V,P,3] tensor: one backward fills every view's slice."""
+    of the ten; every slice is an autograd node and a launch-free but not cost-free call) -- except `viewspace_points` (and
+    `viewspace_points_abs`, with absgrad), which stays the whole [V,P,3] tensor: one backward fills every view's slice."""
     _NAMES = ("render", "depth", "depth_median", "opacity_map", "depth_var", "gau_uncertainty", "num_related_pixels",
               "visibility_filter", "radii", "viewspace_points")
     _FULL_NAMES = ("render", "depth", "opacity_map", "visibility_filter", "radii", "viewspace_points")  # (variant="full")
@@ -446,13 +465,16 @@ class _ViewOf(_Mapping):
     def __init__(self, out, k):
         self._out, self._k, self._got = out, k, {}
         self._names = self._NAMES if "depth_median" in out else self._FULL_NAMES
+        if "viewspace_points_abs" in out:
+            self._names = self._names + ("viewspace_points_abs",)
 
     def __getitem__(self, n):
         v = self._got.get(n)
         if v is None:
             if n not in self._names:
                 raise KeyError(n)
-            v = self._got[n] = self._out[n] if n == "viewspace_points" else self._out[n][self._k]
+            whole = n == "viewspace_points" or n == "viewspace_points_abs"
+            v = self._got[n] = self._out[n] if whole else self._out[n][self._k]
         return v
 
     def __iter__(self):
@@ -462,14 +484,16 @@ class _ViewOf(_Mapping):
         return len(self._names)
 
 
-def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None, **render_kwargs):
+def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None, absgrad=False, **render_kwargs):
     """`render_batch` through ONE batched forward and ONE batched backward (`render_views`): `loss_fn(out_k, k)` sees the
     dict of view k (slices of the batched outputs), the losses are summed and back-propagated once.  Same gradients as
     `render_batch` -- the sum over the keyframes in the Gaussians' `.grad`, one pose gradient per `viewmatrix` -- without V - 1
     accumulation passes over the dense gradient rows and with the camera-independent per-Gaussian work done once.
     `batch_loss_fn(out)`, if given, replaces the V calls of `loss_fn`: it sees the batched dict and returns the SUM of the
     views' losses as one scalar (then the returned list holds that one value).  `variant="full"` (a render_kwargs entry) renders
-    through the full variant's batch."""
+    through the full variant's batch.  `absgrad=True`: the returned dict carries `viewspace_points_abs` (render_views)."""
+    if absgrad:
+        render_kwargs["absgrad"] = True
     out = render_views(cameras, pc, pipe, bg_color, **render_kwargs)
     if batch_loss_fn is not None:
         # ONE loss over the stacked outputs ([V,3,H,W], [V,1,H,W], ...): no per-view slice in the graph -- each is a node whose
@@ -482,7 +506,7 @@ def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None,
     return [l_.detach() for l_ in losses], out
 
 
-def render_batch(cameras, pc, pipe, bg_color, loss_fn, views_in_flight=3, **render_kwargs):
+def render_batch(cameras, pc, pipe, bg_color, loss_fn, views_in_flight=3, absgrad=False, **render_kwargs):
     """One mapping step over a batch of keyframes: every camera is rendered, `loss_fn(out, k)`
     is evaluated on its output dict and back-propagated, each view's forward + loss + backward on its own HIP stream
     (`dgr_amd.multiview.ViewStreams`) so that the views overlap on the GPU; gradients accumulate in the `.grad` of the
@@ -490,7 +514,10 @@ def render_batch(cameras, pc, pipe, bg_color, loss_fn, views_in_flight=3, **rend
     (PyTorch gives none): every view's backward waits for the end of the previous view (`views.before_backward()`), its
     forward and loss still overlap the previous view's backward.  `cameras`: sequence of dicts with `viewmatrix`
     (W2C^T), `fov`, `HW` and optionally `gt_depth`, `viewpoint_camera`.  Returns the list of detached loss values
-    (device tensors); the caller's stream is ordered after all views on return."""
+    (device tensors); the caller's stream is ordered after all views on return.  `absgrad=True`: every view's dict carries
+    `viewspace_points_abs` (render()), which `loss_fn` may keep for the densification statistics."""
+    if absgrad:
+        render_kwargs["absgrad"] = True
     from .multiview import ViewStreams
     cameras = list(cameras)
     if not cameras:

@@ -12,7 +12,10 @@ instead (slam.render_batch_fused: one forward and one backward call for all keyf
 --variant full runs the same loop through the -full variant (uncertainty output; it has no track_off, so the pose gradients are
 formed and left unused).
 
-  python examples/mapping.py [--graph] [--fused] [--variant light|full] [--iters 100] [--keyframes 4]
+  python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--iters 100] [--keyframes 4]
+
+--absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
+of 3DGS's `viewspace_points.grad`; a densify step built on it uses a threshold about 4x higher (0.0008 for 0.0002).
                              [--width 640 --height 480 --gaussians 100000]
 """
 import argparse
@@ -62,9 +65,11 @@ class MapModel:
                 {"params": [self._rotation], "lr": 1e-3}]
 
 
-def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light"):
+def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
+                 absgrad=False):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
-    iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations."""
+    iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
+    absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True))."""
     from dgr_amd import light, slam
     from dgr_amd.optim import SparseAdam, add_densification_stats
     from dgr_amd.synth import make_scene
@@ -80,6 +85,9 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         obs = [slam.render(None, truth, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt, **kw)
                for c in cams]
     obs = [(o["render"].detach(), o["depth"].detach()) for o in obs]
+    # the mapping renders: with absgrad their dicts carry `viewspace_points_abs`, which the statistics read instead
+    mkw = dict(kw, absgrad=True) if absgrad else kw
+    points = "viewspace_points_abs" if absgrad else "viewspace_points"
 
     if graph:
         views_in_flight = 1  # (branches of one graph do not overlap on this ROCm, and the leaves' gradient accumulation
@@ -105,8 +113,8 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         # the keyframe batch through ONE batched forward and ONE batched backward (dgr_amd.batch): the Gaussians' gradients
         # arrive summed over the keyframes, the screen-space gradients per view
         opt.zero_grad(set_to_none=True)
-        losses, out = slam.render_batch_fused(cams, pc, None, bg, loss_fn, batch_loss_fn=batch_loss_fn, **kw)
-        pts = out["viewspace_points"].grad
+        losses, out = slam.render_batch_fused(cams, pc, None, bg, loss_fn, batch_loss_fn=batch_loss_fn, **mkw)
+        pts = out[points].grad
         for k in range(keyframes):
             add_densification_stats(pts[k], out["radii"][k], pc.xyz_gradient_accum, pc.denom, pc.max_radii2D)
         torch.amax(out["radii"], dim=0, out=seen)
@@ -120,17 +128,17 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             return iteration_fused()
         opt.zero_grad(set_to_none=True)
         if views_in_flight > 1:
-            losses = slam.render_batch(cams, pc, None, bg, loss_fn, views_in_flight=views_in_flight, **kw)
+            losses = slam.render_batch(cams, pc, None, bg, loss_fn, views_in_flight=views_in_flight, **mkw)
         else:  # one keyframe after the other on the caller's stream
             losses = []
             for k, c in enumerate(cams):
                 loss = loss_fn(slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"],
-                                           gt_depth=gt, **kw), k)
+                                           gt_depth=gt, **mkw), k)
                 loss.backward()
                 losses.append(loss.detach())
         seen.zero_()
         for out in outs:
-            add_densification_stats(out["viewspace_points"].grad, out["radii"], pc.xyz_gradient_accum, pc.denom,
+            add_densification_stats(out[points].grad, out["radii"], pc.xyz_gradient_accum, pc.denom,
                                     pc.max_radii2D)
             torch.maximum(seen, out["radii"], out=seen)
         if not graph:
@@ -174,6 +182,8 @@ def main():
                     help="the keyframe batch through one batched forward + backward (slam.render_batch_fused) instead of one "
                          "rasterizer call per keyframe")
     ap.add_argument("--variant", choices=("light", "full"), default="light", help="which rasterizer variant maps")
+    ap.add_argument("--absgrad", action="store_true",
+                    help="densification statistics from the absolute screen-space gradient (AbsGS) instead of viewspace_points.grad")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -185,9 +195,9 @@ def main():
     dev = torch.device("cuda:0")
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
                                     args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
-                                    variant=args.variant)
+                                    variant=args.variant, absgrad=args.absgrad)
     n = float(pc.denom.sum())
-    print(("full variant: " if args.variant == "full" else "") +
+    print(("full variant: " if args.variant == "full" else "") + ("absgrad: " if args.absgrad else "") +
           f"loss {l0:.4e} -> {l1:.4e}; {dt * 1e3:.3f} ms per mapping iteration over {args.keyframes} keyframes"
           f" ({dt / args.keyframes * 1e3:.3f} ms per keyframe); {int((pc.denom > 0).sum())} Gaussians seen,"
           f" {n:.0f} (Gaussian, view) statistics accumulated")

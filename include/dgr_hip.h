@@ -471,6 +471,54 @@ int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad*
                             const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot);
 
+/* ---- absgrad: the absolute screen-space gradient of AbsGS ("homodirectional" gradient; gsplat's absgrad) ----
+ * Each function takes its namesake's arguments, in the same order, plus the absgrad output, and otherwise does exactly what its
+ * namesake does.  For a Gaussian g, with v_p(g) the contribution of pixel p to g's dL_dmean2D[:2] (every term that reaches it
+ * through alpha at p, the ndc scale W/2, H/2 included -- so sum_p v_p(g) is dL_dmean2D[g, :2]):
+ *     dL_dmean2D_abs[g] = ( sum_p |v_p(g).x|, sum_p |v_p(g).y|, 0 )        float [P,3], written densely: rows the view did not
+ * render and every z are 0.  It is a per-view quantity: the batch forms give one [P,3] per view and never sum them.
+ * A NULL dL_dmean2D_abs (batch: a NULL array, or a NULL entry for that view) is exactly the namesake's behaviour.
+ * DGR_ERR_BAD_ARGUMENT (before any device call) for a non-NULL absgrad output with map_off = 1 (tracking computes no per-Gaussian
+ * gradients), with dgr_set_option("deterministic_grads", 1) (no deterministic form) or with alpha_mode 2 (the glibc A/B form).
+ * Same contract as the namesakes: no host synchronisation, capturable into a hipGraph, P == 0 handled, helper streams rejoined. */
+int dgr_light_backward_absgrad(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+                               const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                               float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                               const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
+                               const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                               float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                               float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
+                               const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
+                               const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes,
+                               float* dL_dmean2D_abs);
+int dgr_full_backward_absgrad(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                              char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                              const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                              float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
+                              const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
+                              float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
+                              float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
+                              size_t scratch_bytes, float* dL_dmean2D_abs);
+/* dL_dmean2D_abs: a HOST array of n_views device pointers (view v's [P,3] absgrad; each may be NULL), or NULL. */
+int dgr_light_backward_batch_absgrad(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
+                                     const float* background, int width, int height, const float* means3D, const float* shs,
+                                     const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                     const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                     int track_off, int map_off, float* const* dL_dmean2D_abs);
+int dgr_full_backward_batch_absgrad(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                                    const float* background, int width, int height, const float* means3D, const float* shs,
+                                    const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                    const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
+                                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                    float* const* dL_dmean2D_abs);
+
 /* Debug: while `device_words` (8 x uint64 per bin_tiles workgroup, caller-owned device memory) is non-NULL, every bin_tiles
  * workgroup stores phase time stamps (100 MHz wall clock) and its segment's sizes there: profiles/r9/bin_tiles_trace.py. */
 int dgr_debug_bin_tiles_trace(unsigned long long* device_words);
