@@ -17,6 +17,7 @@ the C ABI's batched entry points (include/dgr_hip.h: dgr_light_forward_batch / d
 torch supplies device memory and the current stream; every compute call goes through the C ABI.  There is no CPU fallback.
 """
 import ctypes as C
+import weakref
 from typing import NamedTuple
 
 import torch
@@ -62,47 +63,46 @@ def _ext():
     return _light._CompiledC.ext if _light._C is _light._CompiledC else None
 
 
-def _forward_batch_compiled(ext, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
-                            gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, key, V):
-    cap = _light._capacity_cache.get(key, 0)
-    lazy = _light._sync_mode() == "lazy" and cap > 0
-    cap = (int(cap * 1.5) + 4096) if lazy else (int(cap * 1.25) + 4096 if cap else 4 * key[1] + 4096)
+def _policy(key, P, depth=None):
+    """(strict, capacity, cached count) of the next batch of shape `key`: dgr_amd.light's policy (lazy mode follows the shape's
+    growth guard and runs an unsettled shape strict).  A batch has no resize-callback form; where the policy picks that one
+    (DGR_FORWARD_MODE=callback, P == 0) the batch runs strict.  `depth`: status words left unread (light._binning_policy)."""
+    mode, use, cap = _light._binning_policy(key, P, depth)
+    if mode == 0:
+        use = int(cap * 1.25) + 4096 if cap else 4 * P + 4096
+    return mode != 2, use, cap
+
+
+def _settle(status, key, strict, use, cap, V, tickets=None):
+    """After one attempt: (per-view R for the backward, or None when the batch must be run again with a larger capacity).
+    A lazy or captured batch hands its backward the capacity its binning buffers were carved with (the views' counts are read
+    later), a strict one the views' exact counts."""
     capturing = torch.cuda.is_current_stream_capturing()
-    while True:
-        if lazy and not capturing:
-            while len(_light._pending_status) > V:
-                _light._check_oldest()  # status words of earlier calls have long completed: no stall
-        out, tickets = ext.light_forward_batch(bg, means3D, colors, opacity, scales, rotations, float(scale_modifier),
-                                               cov3D_precomp, viewmatrices, gt_depths, projmatrices, float(tanfovx),
-                                               float(tanfovy), int(H), int(W), sh, int(degree), campos, bool(prefiltered), cap,
-                                               bool(lazy))
-        status = out[0]
-        if key[1] == 0:
-            rendered = [0] * V
-            break
-        if lazy or capturing:
-            for t in tickets:
-                _light._pending_status.append((t, key))
-            if capturing:  # recorded into a hipGraph: nothing can be read back now (dgr_amd.light.check_captured_status)
-                import weakref
-                _light._captured_status.append(weakref.ref(status))
-                _light._capture_keepalive.append(status)
-            rendered = [_light._capacity_cache.get(key, 0)] * V
-            break
-        s = status.tolist()  # the one host wait of a strict batch
-        if any(r[2] for r in s):
-            raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-        rendered = [r[0] for r in s]
-        _light._capacity_cache[key] = max(_light._capacity_cache.get(key, 0), max(rendered))
-        if max(rendered) <= cap:
-            break
-        cap = int(max(rendered) * 1.1) + 4096  # overflow: those views' tile lists were left empty; run again
-    return (rendered,) + tuple(out[1:])
+    if not strict or capturing:
+        # no host synchronisation: the status words are looked at one or two calls later (dgr_amd.light.check_async_errors),
+        # or after a replay (check_captured_status)
+        if capturing:
+            _light._captured_status.append(weakref.ref(status))
+            _light._capture_keepalive.append(status)
+        elif tickets is not None:
+            _light._pending_status.extend((t, key) for t in tickets)
+        else:
+            for v in range(V):
+                _light._post_status(status[v], key)
+        return [use] * V  # an upper bound of every view's count
+    s = status.tolist()  # the one host wait of a strict batch
+    if any(r[2] for r in s):
+        raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
+    rendered = [r[0] for r in s]
+    if max(rendered) > use:
+        return None
+    _light._strict_read(key, cap, max(rendered))
+    return rendered
 
 
 def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,
                    projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered):
-    lib = _lib()
+    """Returns (per-view R for the backward, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)."""
     dev = means3D.device
     if dev.type != "cuda":
         raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
@@ -110,11 +110,33 @@ def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifi
     if not 1 <= V <= MAX_VIEWS:
         raise RuntimeError(f"1 .. {MAX_VIEWS} views per batch")
     P = means3D.size(0)
+    key = (dev.index, P, H, W)
+    strict, use, cap = _policy(key, P, V)
     ext = _ext()
-    if ext is not None:
-        return _forward_batch_compiled(ext, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                                       viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos,
-                                       prefiltered, (dev.index, P, H, W), V)
+    while True:
+        if ext is not None:
+            out, tickets = ext.light_forward_batch(bg, means3D, colors, opacity, scales, rotations, float(scale_modifier),
+                                                   cov3D_precomp, viewmatrices, gt_depths, projmatrices, float(tanfovx),
+                                                   float(tanfovy), int(H), int(W), sh, int(degree), campos, bool(prefiltered), use,
+                                                   not strict)
+        else:
+            out, tickets = _forward_batch_ctypes(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                                                 viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree,
+                                                 campos, prefiltered, use, V), None
+        if P == 0:
+            return ([0] * V,) + tuple(out[1:])
+        R = _settle(out[0], key, strict, use, cap, V, tickets)
+        if R is not None:
+            return (R,) + tuple(out[1:])
+        use = int(max(r[0] for r in out[0].tolist()) * 1.1) + 4096  # overflow: those views' tile lists were left empty
+
+
+def _forward_batch_ctypes(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,
+                          projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, cap, V):
+    """One attempt with binning capacity `cap` per view; returns ([V,4] status, color, depth, median, var, alpha, radii, geom,
+    binning, img, unc, px) as the extension's light_forward_batch."""
+    lib = _lib()
+    dev = means3D.device
     f32 = dict(dtype=torch.float32, device=dev)
     i32 = dict(dtype=torch.int32, device=dev)
     u8 = dict(dtype=torch.uint8, device=dev)
@@ -122,6 +144,7 @@ def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifi
     means3D, bg, colors, opacity = c(means3D, dev), c(bg, dev), c(colors, dev), c(opacity, dev)
     scales, rotations, cov3D_precomp, sh = c(scales, dev), c(rotations, dev), c(cov3D_precomp, dev), c(sh, dev)
     viewmatrices, projmatrices, campos, gt_depths = c(viewmatrices, dev), c(projmatrices, dev), c(campos, dev), c(gt_depths, dev)
+    P = means3D.size(0)
     M = sh.size(1) if sh.numel() != 0 else 0
     color = torch.empty((V, 3, H, W), **f32)
     depth, median, var, alpha = (torch.empty((V, 1, H, W), **f32) for _ in range(4))
@@ -131,45 +154,21 @@ def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifi
     px = mk((V, P, 1), **i32)
     geom = torch.empty((V, max(lib.dgr_geometry_bytes(P), 1)), **u8)
     img = torch.empty((V, max(lib.dgr_image_bytes(W, H), 1)), **u8)
+    binning = torch.empty((V, max(lib.dgr_binning_bytes(cap, W, H), 1)), **u8)
     status = torch.zeros((V, 4), **i32)
-    st = _capi.stream_handle(dev.index)
+    views = (_View * V)()
+    for v in range(V):
+        w = views[v]
+        w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer = _row(geom, v), _row(binning, v), cap, _row(img, v)
+        w.status, w.viewmatrix, w.projmatrix, w.cam_pos = _row(status, v), _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v)
+        w.out_color, w.out_depth, w.out_median_depth, w.out_alpha = _row(color, v), _row(depth, v), _row(median, v), _row(alpha, v)
+        w.gt_depth, w.out_depth_var = _row(gt_depths, v), _row(var, v)
+        w.gau_uncertainty, w.gau_related_pixels, w.radii = _row(unc, v), _row(px, v), _row(radii, v)
     p = _capi.ptr
-    key = (dev.index, P, H, W)
-    cap = _light._capacity_cache.get(key, 0)
-    lazy = _light._sync_mode() == "lazy" and cap > 0
-    cap = (int(cap * 1.5) + 4096) if lazy else (int(cap * 1.25) + 4096 if cap else 4 * P + 4096)
-    capturing = torch.cuda.is_current_stream_capturing()
-    while True:
-        binning = torch.empty((V, max(lib.dgr_binning_bytes(cap, W, H), 1)), **u8)
-        views = (_View * V)()
-        for v in range(V):
-            w = views[v]
-            w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer = _row(geom, v), _row(binning, v), cap, _row(img, v)
-            w.status, w.viewmatrix, w.projmatrix, w.cam_pos = _row(status, v), _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v)
-            w.out_color, w.out_depth, w.out_median_depth, w.out_alpha = _row(color, v), _row(depth, v), _row(median, v), _row(alpha, v)
-            w.gt_depth, w.out_depth_var = _row(gt_depths, v), _row(var, v)
-            w.gau_uncertainty, w.gau_related_pixels, w.radii = _row(unc, v), _row(px, v), _row(radii, v)
-        _light._check(lib.dgr_light_forward_batch(st, V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors),
-                                                  p(opacity), p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp),
-                                                  float(tanfovx), float(tanfovy), int(bool(prefiltered))))
-        if P == 0:
-            rendered = [0] * V
-            break
-        if lazy or capturing:
-            # no host synchronisation: the status words are looked at one or two calls later (dgr_amd.light.check_async_errors)
-            for v in range(V):
-                _light._post_status(status[v], key)
-            rendered = [_light._capacity_cache.get(key, 0)] * V
-            break
-        s = status.tolist()  # the one host wait of a strict batch
-        if any(r[2] for r in s):
-            raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-        rendered = [r[0] for r in s]
-        _light._capacity_cache[key] = max(_light._capacity_cache.get(key, 0), max(rendered))
-        if max(rendered) <= cap:
-            break
-        cap = int(max(rendered) * 1.1) + 4096  # overflow: those views' tile lists were left empty; run again
-    return rendered, color, depth, median, var, alpha, radii, geom, binning, img, unc, px
+    _light._check(lib.dgr_light_forward_batch(_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D),
+                                              p(sh), p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations),
+                                              p(cov3D_precomp), float(tanfovx), float(tanfovy), int(bool(prefiltered))))
+    return status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px
 
 
 def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,

@@ -13,13 +13,12 @@ runs an unsettled shape strict).  A lazy forward hands its backward the capacity
 (deterministic gradients size their row buffers by it), never the largest count seen.  There is no CPU fallback.
 """
 import ctypes as C
-import weakref
 
 import torch
 
 from . import _capi
 from . import light as _light
-from .batch import MAX_VIEWS, BatchRasterizationSettings, _ext, _row  # noqa: F401  (the settings are shared)
+from .batch import MAX_VIEWS, BatchRasterizationSettings, _ext, _policy, _row, _settle  # noqa: F401  (the settings are shared)
 
 _View, _ViewGrad = _capi.FullView, _capi.FullViewGrad
 
@@ -31,40 +30,6 @@ def _check_inputs(means3D, viewmatrices):
     if means3D.device.type != "cuda":
         raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
     return V
-
-
-def _policy(key, P):
-    """(strict, capacity, cached count) of the next batch of shape `key`: dgr_amd.light's policy.  A batch has no
-    resize-callback form; where the policy picks that one (DGR_FORWARD_MODE=callback, P == 0) the batch runs strict."""
-    mode, use, cap = _light._binning_policy(key, P)
-    if mode == 0:
-        use = int(cap * 1.25) + 4096 if cap else 4 * P + 4096
-    return mode != 2, use, cap
-
-
-def _settle(status, key, strict, use, cap, V, tickets=None):
-    """After one attempt: (per-view R for the backward, or None when the batch must be run again with a larger capacity)."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    if not strict or capturing:
-        # no host synchronisation: the status words are looked at one or two calls later (dgr_amd.light.check_async_errors),
-        # or after a replay (check_captured_status)
-        if capturing:
-            _light._captured_status.append(weakref.ref(status))
-            _light._capture_keepalive.append(status)
-        elif tickets is not None:
-            _light._pending_status.extend((t, key) for t in tickets)
-        else:
-            for v in range(V):
-                _light._post_status(status[v], key)
-        return [use] * V  # the capacity the binning buffers were carved with: an upper bound of every view's count
-    s = status.tolist()  # the one host wait of a strict batch
-    if any(r[2] for r in s):
-        raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-    rendered = [r[0] for r in s]
-    if max(rendered) > use:
-        return None
-    _light._strict_read(key, cap, max(rendered))
-    return rendered
 
 
 def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,

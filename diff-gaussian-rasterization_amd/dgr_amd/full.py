@@ -6,7 +6,6 @@ Same names, argument order and return arity as the reference module of the -full
 `num_related_gaussians` (the reference's NG, which sizes its pair lists) is still produced and threaded
 through the autograd context, but nothing here is sized by it.
 """
-import os
 from typing import NamedTuple
 
 import torch
@@ -38,11 +37,17 @@ def _device_guarded(arg_index):
 class _C:
     """Functions with the signatures of the full variant's pybind11 module (F/ext.cpp:15-19)."""
 
+    @staticmethod
+    def rasterize_gaussians(*args):
+        # F/rasterize_points.cu:35-120.  The tuple's num_rendered / num_related are the values last read for the shape (a lazy
+        # forward's own are read one call late); the autograd Function takes its backward's R from rasterize_gaussians_r.
+        return _CtypesC.rasterize_gaussians_r(*args)[1]
+
     @_device_guarded(1)
-    def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier,
-                            cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
-                            image_height, image_width, sh, degree, campos, prefiltered):
-        # F/rasterize_points.cu:35-120
+    def rasterize_gaussians_r(background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                              cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
+                              image_height, image_width, sh, degree, campos, prefiltered):
+        """(R for the backward, the `rasterize_gaussians` tuple): see dgr_amd.light._C.rasterize_gaussians_r."""
         if means3D.ndimension() != 2 or means3D.size(1) != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
         lib = _capi.load()
@@ -69,7 +74,9 @@ class _C:
                   float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos),
                   float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), p(out_color), p(out_depth), p(gt_depth),
                   p(out_unc), p(radii))
-        if os.environ.get("DGR_FORWARD_MODE", "presized") == "callback" or P == 0:
+        key = (dev.index, P, H, W)
+        mode, use, cap = _light._binning_policy(key, P)  # (the compiled binding's policy: lazy mode honours _unsettled)
+        if mode == 0:
             import ctypes as C
             bufs = {k: torch.empty((0,), **u8) for k in ("geom", "binning", "img")}
 
@@ -80,48 +87,41 @@ class _C:
                 return _capi.ALLOC_FN(cb)
             cbs = [mk("geom"), mk("binning"), mk("img")]
             ng = C.c_int(0)
-            rendered = _check(lib.dgr_full_forward(st, cbs[0], cbs[1], cbs[2], None, *common, C.byref(ng)))
+            rendered = R = _check(lib.dgr_full_forward(st, cbs[0], cbs[1], cbs[2], None, *common, C.byref(ng)))
             related = ng.value
             geomBuffer, binningBuffer, imgBuffer = bufs["geom"], bufs["binning"], bufs["img"]
         else:
             geomBuffer = torch.empty((lib.dgr_geometry_bytes(P),), **u8)
             imgBuffer = torch.empty((lib.dgr_image_bytes(W, H),), **u8)
             status = torch.empty((4,), **i32)
-            key = (dev.index, P, H, W)
-            cap = _capacity_cache.get(key, 0)
-            if _light._sync_mode() == "lazy" and cap > 0:
+            if mode == 2:
                 # no host synchronisation (dgr_amd/light.py): the status word is checked one call late; the tuple's
-                # num_rendered / num_related members are the latest values read back for this shape
-                while len(_light._pending_status) > _light.lazy_depth() and not torch.cuda.is_current_stream_capturing():
-                    _light._check_oldest()
-                cap = int(cap * 1.5) + 4096
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(cap, W, H),), **u8)
-                _check(lib.dgr_full_forward_presized(st, p(geomBuffer), p(binningBuffer), cap, p(imgBuffer), p(status),
+                # num_rendered / num_related members are the values last read back for this shape, the backward's R is the
+                # capacity the binning buffer was carved with
+                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
+                _check(lib.dgr_full_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer), p(status),
                                                      *common))
                 _light._post_status(status, key)
                 related = _light._last_status.get(key, (0, 0, 0, 0))[3]
-                return (_capacity_cache[key], related, out_color, out_depth, out_unc, radii, geomBuffer, binningBuffer,
-                        imgBuffer)
-            cap = int(cap * 1.25) + 4096 if cap else 4 * P + 4096
+                return use, (_capacity_cache[key], related, out_color, out_depth, out_unc, radii, geomBuffer, binningBuffer,
+                             imgBuffer)
             while True:
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(cap, W, H),), **u8)
+                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
                 lib.dgr_early_status_arm()
-                _check(lib.dgr_full_forward_presized(st, p(geomBuffer), p(binningBuffer), cap, p(imgBuffer), p(status),
+                _check(lib.dgr_full_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer), p(status),
                                                      *common))
                 s = _light._early_status(lib)  # waits until num_rendered is known, not for the whole forward
                 if s[2]:
                     raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-                rendered = s[0]
-                _capacity_cache[key] = max(_capacity_cache.get(key, 0), rendered)
-                if rendered <= cap:
-                    # num_related (the reference's NG) is produced by the forward blend: the second blocking read of
-                    # the reference (F/cuda_rasterizer/rasterizer_impl.cu:498); lazy mode reports it one call late instead
-                    s = status.tolist()
-                    related = s[3]
-                    _light._last_status[key] = s
+                rendered = R = s[0]
+                if rendered <= use:
                     break
-                cap = int(rendered * 1.1) + 4096
-        return rendered, related, out_color, out_depth, out_unc, radii, geomBuffer, binningBuffer, imgBuffer
+                use = int(rendered * 1.1) + 4096
+            # num_related (the reference's NG) is produced by the forward blend: the second blocking read of the reference
+            # (F/cuda_rasterizer/rasterizer_impl.cu:498); lazy mode reports it one call late instead
+            related = status.tolist()[3]
+            _light._strict_read(key, cap, rendered, related)
+        return R, (rendered, related, out_color, out_depth, out_unc, radii, geomBuffer, binningBuffer, imgBuffer)
 
     @_device_guarded(1)
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -176,14 +176,21 @@ class _CompiledC:
     ext = None
 
     @staticmethod
-    def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
-                            gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered):
+    def rasterize_gaussians(*args):
+        return _CompiledC.rasterize_gaussians_r(*args)[1]
+
+    @staticmethod
+    def rasterize_gaussians_r(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                              viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos,
+                              prefiltered):
+        """(R for the backward, the `rasterize_gaussians` tuple): see dgr_amd.light._C.rasterize_gaussians_r."""
         P, H, W = means3D.size(0) if means3D.dim() else 0, int(image_height), int(image_width)
         key = (means3D.device.index, P, H, W)
         mode, use, cap = _light._binning_policy(key, P)
-        (rendered, related, ticket, _, status, color, depth, unc, radii, geom, binning, img) = _CompiledC.ext.full_forward(
+        (rendered, related, ticket, used, status, color, depth, unc, radii, geom, binning, img) = _CompiledC.ext.full_forward(
             background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
             gt_depth, projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered), use, mode)
+        R = rendered
         if mode == 2:
             if ticket >= 0:
                 _light._pending_status.append((ticket, key))
@@ -191,11 +198,10 @@ class _CompiledC:
                 import weakref
                 _light._captured_status.append(weakref.ref(status))
                 _light._capture_keepalive.append(status)
-            rendered, related = _capacity_cache[key], _light._last_status.get(key, (0, 0, 0, 0))[3]
+            rendered, related, R = _capacity_cache[key], _light._last_status.get(key, (0, 0, 0, 0))[3], used
         elif mode == 1:
-            _capacity_cache[key] = max(cap, rendered)
-            _light._last_status[key] = [rendered, 0, 0, related]
-        return rendered, related, color, depth, unc, radii, geom, binning, img
+            _light._strict_read(key, cap, rendered, related)
+        return R, (rendered, related, color, depth, unc, radii, geom, binning, img)
 
     @staticmethod
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -238,9 +244,9 @@ def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales,
             _light._captured_status.append(weakref.ref(status))
             _light._capture_keepalive.append(status)
     elif mode == 1:
-        _capacity_cache[key] = max(cap, rendered)
-        # (the strict node does not wait for num_related -- csrc/torch_ext.cpp: full_forward_core -- and reports -1: keep the last one read)
-        _light._last_status[key] = [rendered, 0, 0, related if related >= 0 else _light._last_status.get(key, (0, 0, 0, 0))[3]]
+        # (the strict node does not wait for num_related -- csrc/torch_ext.cpp: full_forward_core -- and reports -1: _strict_read
+        #  keeps the last one read)
+        _light._strict_read(key, cap, rendered, related)
     return tuple(out)
 
 
@@ -279,10 +285,11 @@ class _RasterizeGaussians(torch.autograd.Function):
             raster_settings.campos,
             raster_settings.prefiltered,
         )
-        (num_rendered, num_related_gaussians, color, depth, uncertainty, radii, geomBuffer, binningBuffer,
-         imgBuffer) = _C.rasterize_gaussians(*args)
+        # (R: the backward's num_rendered -- the capacity of a lazy forward, which never learns its own count)
+        R, (_, num_related_gaussians, color, depth, uncertainty, radii, geomBuffer, binningBuffer,
+            imgBuffer) = _C.rasterize_gaussians_r(*args)
         ctx.raster_settings = raster_settings
-        ctx.num_rendered = num_rendered
+        ctx.num_rendered = R
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
         ctx.num_related_gaussians = num_related_gaussians
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, radii, sh,

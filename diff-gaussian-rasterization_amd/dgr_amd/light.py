@@ -116,12 +116,18 @@ def _note_growth(key, prev, s, capacity_used=None):
             del _unsettled[key]
 
 
-def _strict_read(key, cap, rendered):
-    """A strict forward returned its exact count (and retried an overflow inside the call)."""
-    last = _last_status.get(key)
-    if _sync_mode() == "lazy":
+def _strict_read(key, cap, rendered, related=None):
+    """A strict forward returned its exact count (and retried an overflow inside the call).  `related`: the full variant's
+    num_related (the status word's [3], which its lazy forwards report), kept in every sync mode; < 0 when the forward did not
+    wait for it, and then the last one read stays."""
+    last = _last_status.get(key)  # (the previous count, read before it is overwritten)
+    lazy = _sync_mode() == "lazy"
+    if lazy:
         _note_growth(key, last[0] if last else 0, (rendered, 0, 0, 0))
-        _last_status[key] = [rendered, 0, 0, last[3] if last else 0]
+    if lazy or related is not None:
+        if related is None or related < 0:
+            related = last[3] if last else 0
+        _last_status[key] = [rendered, 0, 0, related]
     _capacity_cache[key] = max(cap, rendered)
 
 
@@ -269,11 +275,19 @@ def _device_guarded(arg_index):
 class _C:
     """Functions with the signatures of the reference's pybind11 module `_C` (L/ext.cpp:15-19)."""
 
+    @staticmethod
+    def rasterize_gaussians(*args):
+        # L/rasterize_points.cu:35-129.  The tuple's num_rendered is the count last read for the shape (a lazy forward's own
+        # count is read one call late); the autograd Function takes its backward's R from rasterize_gaussians_r.
+        return _CtypesC.rasterize_gaussians_r(*args)[1]
+
     @_device_guarded(1)
-    def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier,
-                            cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
-                            image_height, image_width, sh, degree, campos, prefiltered, debug):
-        # L/rasterize_points.cu:35-129
+    def rasterize_gaussians_r(background, means3D, colors, opacity, scales, rotations, scale_modifier,
+                              cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
+                              image_height, image_width, sh, degree, campos, prefiltered, debug):
+        """(R for the backward, the `rasterize_gaussians` tuple).  R is the exact count of a strict forward and the capacity
+        the binning buffer was carved with of a lazy one: at least the frame's count, which the deterministic backward's
+        row buffer needs (csrc/render_light.hip: det_gather_kernel writes NaN past R)."""
         if means3D.ndimension() != 2 or means3D.size(1) != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
         lib = _capi.load()
@@ -309,7 +323,9 @@ class _C:
                   float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), p(out_color), p(out_depth),
                   p(out_median), p(out_alpha), p(gt_depth), p(out_var), p(gau_unc), p(gau_px), p(radii))
 
-        if os.environ.get("DGR_FORWARD_MODE", "presized") == "callback" or P == 0:
+        key = (dev.index, P, H, W)
+        mode, use, cap = _binning_policy(key, P)  # (the compiled binding's policy: lazy mode honours _unsettled)
+        if mode == 0:
             bufs = {k: torch.empty((0,), **u8) for k in ("geom", "binning", "img")}
 
             def mk(name):
@@ -318,45 +334,36 @@ class _C:
                     return bufs[name].data_ptr()
                 return _capi.ALLOC_FN(cb)
             cbs = [mk("geom"), mk("binning"), mk("img")]
-            rendered = _check(lib.dgr_light_forward(st, cbs[0], cbs[1], cbs[2], None, *common, int(bool(debug))))
+            rendered = R = _check(lib.dgr_light_forward(st, cbs[0], cbs[1], cbs[2], None, *common, int(bool(debug))))
             geomBuffer, binningBuffer, imgBuffer = bufs["geom"], bufs["binning"], bufs["img"]
         else:
             geomBuffer = torch.empty((lib.dgr_geometry_bytes(P),), **u8)
             imgBuffer = torch.empty((lib.dgr_image_bytes(W, H),), **u8)
             status = torch.empty((4,), **i32)
-            key = (dev.index, P, H, W)
-            cap = _capacity_cache.get(key, 0)
-            lazy = _sync_mode() == "lazy" and cap > 0
-            if lazy:
-                # status words of earlier calls have long completed: reading them does not stall the pipeline
-                while len(_pending_status) > _LAZY_DEPTH and not torch.cuda.is_current_stream_capturing():
-                    _check_oldest()
-                cap = int(cap * 1.5) + 4096
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(cap, W, H),), **u8)
-                _check(lib.dgr_light_forward_presized(st, p(geomBuffer), p(binningBuffer), cap, p(imgBuffer),
+            if mode == 2:
+                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
+                _check(lib.dgr_light_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer),
                                                       p(status), *common))
                 _post_status(status, key)
-                rendered = _capacity_cache[key]
-                return (rendered, out_color, out_depth, out_median, out_var, out_alpha, radii, geomBuffer,
-                        binningBuffer, imgBuffer, gau_unc, gau_px)
-            cap = int(cap * 1.25) + 4096 if cap else 4 * P + 4096
+                return use, (_capacity_cache[key], out_color, out_depth, out_median, out_var, out_alpha, radii, geomBuffer,
+                             binningBuffer, imgBuffer, gau_unc, gau_px)
             while True:
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(cap, W, H),), **u8)
+                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
                 lib.dgr_early_status_arm()
-                _check(lib.dgr_light_forward_presized(st, p(geomBuffer), p(binningBuffer), cap, p(imgBuffer),
+                _check(lib.dgr_light_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer),
                                                       p(status), *common))
                 s = _early_status(lib)  # the one host wait of this forward: until num_rendered is known, a tenth of the
                 if s[2]:                # way into the forward -- not until the forward has finished
                     raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-                rendered = s[0]
-                _capacity_cache[key] = max(_capacity_cache.get(key, 0), rendered)
-                if rendered <= cap:
+                rendered = R = s[0]
+                if rendered <= use:
                     break
-                cap = int(rendered * 1.1) + 4096  # overflow: every tile list was left empty; run again
+                use = int(rendered * 1.1) + 4096  # overflow: every tile list was left empty; run again
+            _strict_read(key, cap, rendered)
             if debug:
                 torch.cuda.synchronize(dev)
-        return (rendered, out_color, out_depth, out_median, out_var, out_alpha, radii, geomBuffer, binningBuffer,
-                imgBuffer, gau_unc, gau_px)
+        return R, (rendered, out_color, out_depth, out_median, out_var, out_alpha, radii, geomBuffer, binningBuffer,
+                   imgBuffer, gau_unc, gau_px)
 
     @_device_guarded(1)
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -435,27 +442,33 @@ class _CompiledC:
     ext = None
 
     @staticmethod
-    def rasterize_gaussians(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                            viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
-                            campos, prefiltered, debug):
+    def rasterize_gaussians(*args):
+        return _CompiledC.rasterize_gaussians_r(*args)[1]
+
+    @staticmethod
+    def rasterize_gaussians_r(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                              viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
+                              campos, prefiltered, debug):
+        """(R for the backward, the `rasterize_gaussians` tuple): see _C.rasterize_gaussians_r."""
         ext = _CompiledC.ext
         P, H, W = means3D.size(0) if means3D.dim() else 0, int(image_height), int(image_width)
         key = (means3D.device.index, P, H, W)
         mode, use, cap = _binning_policy(key, P)
-        (rendered, ticket, _, status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px) = ext.light_forward(
+        (rendered, ticket, used, status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px) = ext.light_forward(
             background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
             gt_depth, projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered),
             bool(debug), use, mode)
+        R = rendered
         if mode == 2:
             if ticket >= 0:
                 _pending_status.append((ticket, key))
             else:  # recorded into a hipGraph: nothing can be read back now
                 _captured_status.append(weakref.ref(status))
                 _capture_keepalive.append(status)
-            rendered = _capacity_cache[key]
+            rendered, R = _capacity_cache[key], used
         elif mode == 1:
             _strict_read(key, cap, rendered)
-        return (rendered, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)
+        return R, (rendered, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)
 
     @staticmethod
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -489,13 +502,15 @@ if os.environ.get("DGR_BINDING", "compiled") != "ctypes" and not os.environ.get(
         pass
 
 
-def _binning_policy(key, P):
-    """(mode, capacity) of the next forward of shape `key` = (device, P, H, W); see csrc/torch_ext.cpp: light_forward_core."""
+def _binning_policy(key, P, depth=None):
+    """(mode, capacity, cached count) of the next forward of shape `key` = (device, P, H, W); see csrc/torch_ext.cpp:
+    light_forward_core.  Every binding and batch of both variants takes its mode and capacity from here.  `depth`: the status
+    words left unread (default lazy_depth(); a batch of V views posts V per call)."""
     cap = _capacity_cache.get(key, 0)
     if os.environ.get("DGR_FORWARD_MODE", "presized") == "callback" or P == 0:
         return 0, 0, cap
     if _sync_mode() == "lazy" and cap > 0:
-        while len(_pending_status) > _LAZY_DEPTH and not torch.cuda.is_current_stream_capturing():
+        while len(_pending_status) > (_LAZY_DEPTH if depth is None else depth) and not torch.cuda.is_current_stream_capturing():
             _check_oldest()  # status words of earlier calls have long completed: no stall
         if key not in _unsettled or torch.cuda.is_current_stream_capturing():
             return 2, int(cap * 1.5) + 4096, cap
@@ -586,21 +601,22 @@ class _RasterizeGaussians(torch.autograd.Function):
             raster_settings.prefiltered,
             raster_settings.debug,
         )
+        # (R: the backward's num_rendered -- the capacity of a lazy forward, which never learns its own count)
         if raster_settings.debug:
             cpu_args = cpu_deep_copy_tuple(args)
             try:
-                out = _C.rasterize_gaussians(*args)
+                R, out = _C.rasterize_gaussians_r(*args)
             except Exception as ex:
                 torch.save(cpu_args, "snapshot_fw.dump")
                 print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
                 raise ex
         else:
-            out = _C.rasterize_gaussians(*args)
-        (num_rendered, color, depth, depth_median, depth_var, opacity_map, radii, geomBuffer, binningBuffer,
+            R, out = _C.rasterize_gaussians_r(*args)
+        (_, color, depth, depth_median, depth_var, opacity_map, radii, geomBuffer, binningBuffer,
          imgBuffer, gau_uncertainty, gau_related_pixels) = out
 
         ctx.raster_settings = raster_settings
-        ctx.num_rendered = num_rendered
+        ctx.num_rendered = R
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, radii, sh,
                               geomBuffer, binningBuffer, imgBuffer, opacity_map, gt_depth)

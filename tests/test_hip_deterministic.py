@@ -91,7 +91,8 @@ def test_heavy_tailed_scene(deterministic, oracle):
 @pytest.mark.parametrize("sync_mode", ["strict", "lazy"])
 def test_through_the_autograd_surface(deterministic, monkeypatch, sync_mode):
     """GaussianRasterizer -> loss.backward(), twice: the same bits in every leaf's .grad.  In lazy mode the backward is handed the
-    binning CAPACITY as R (the host never learnt num_rendered): the row buffer is sized by it."""
+    binning CAPACITY as R (the host never learnt num_rendered): the row buffer is sized by it.  (Here with a constant count;
+    tests/test_hip_lazy_safety.py grows the count under a lazy forward on every call path.)"""
     from dgr_amd import light
     from dgr_amd.multiview import make_settings
     monkeypatch.setenv("DGR_SYNC_MODE", sync_mode)
