@@ -17,12 +17,11 @@ the C ABI's batched entry points (include/dgr_hip.h: dgr_light_forward_batch / d
 torch supplies device memory and the current stream; every compute call goes through the C ABI.  There is no CPU fallback.
 """
 import ctypes as C
-import weakref
 from typing import NamedTuple
 
 import torch
 
-from . import _capi
+from . import _binning, _capi
 from . import light as _light
 
 MAX_VIEWS = _capi.MAX_BATCH_VIEWS
@@ -63,78 +62,30 @@ def _ext():
     return _light._CompiledC.ext if _light._C is _light._CompiledC else None
 
 
-def _policy(key, P, depth=None):
-    """(strict, capacity, cached count) of the next batch of shape `key`: dgr_amd.light's policy (lazy mode follows the shape's
-    growth guard and runs an unsettled shape strict).  A batch has no resize-callback form; where the policy picks that one
-    (DGR_FORWARD_MODE=callback, P == 0) the batch runs strict.  `depth`: status words left unread (light._binning_policy)."""
-    mode, use, cap = _light._binning_policy(key, P, depth)
-    if mode == 0:
-        use = int(cap * 1.25) + 4096 if cap else 4 * P + 4096
-    return mode != 2, use, cap
-
-
-def _settle(status, key, strict, use, cap, V, tickets=None):
-    """After one attempt: (per-view R for the backward, or None when the batch must be run again with a larger capacity).
-    A lazy or captured batch hands its backward the capacity its binning buffers were carved with (the views' counts are read
-    later), a strict one the views' exact counts."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    if not strict or capturing:
-        # no host synchronisation: the status words are looked at one or two calls later (dgr_amd.light.check_async_errors),
-        # or after a replay (check_captured_status)
-        if capturing:
-            _light._captured_status.append(weakref.ref(status))
-            _light._capture_keepalive.append(status)
-        elif tickets is not None:
-            _light._pending_status.extend((t, key) for t in tickets)
-        else:
-            for v in range(V):
-                _light._post_status(status[v], key)
-        return [use] * V  # an upper bound of every view's count
-    s = status.tolist()  # the one host wait of a strict batch
-    if any(r[2] for r in s):
-        raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-    rendered = [r[0] for r in s]
-    if max(rendered) > use:
-        return None
-    _light._strict_read(key, cap, max(rendered))
-    return rendered
-
-
-def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,
-                   projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered):
-    """Returns (per-view R for the backward, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)."""
-    dev = means3D.device
-    if dev.type != "cuda":
-        raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
-    V = viewmatrices.size(0)
-    if not 1 <= V <= MAX_VIEWS:
-        raise RuntimeError(f"1 .. {MAX_VIEWS} views per batch")
-    P = means3D.size(0)
-    key = (dev.index, P, H, W)
-    strict, use, cap = _policy(key, P, V)
+def _forward_views(variant, View, outputs, V, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                   viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered):
+    """The batch forward of both variants: the extension's <variant>_forward_batch when dgr_amd.light selected it, else
+    dgr_<variant>_forward_batch through ctypes with `View` views; mode, capacity, retries and status words follow
+    dgr_amd._binning.run_batch.  `outputs(V, P, H, W, f32, i32)` -> the variant's output tensors by their `View` field name, in
+    the order of the extension's result, which carries the geometry, binning and image buffers after "radii".  Returns (per-view
+    R for the backward, that result: the [V,4] status words, the outputs and the buffers)."""
     ext = _ext()
-    while True:
+    P = means3D.size(0)
+
+    def attempt(cap, lazy):
         if ext is not None:
-            out, tickets = ext.light_forward_batch(bg, means3D, colors, opacity, scales, rotations, float(scale_modifier),
-                                                   cov3D_precomp, viewmatrices, gt_depths, projmatrices, float(tanfovx),
-                                                   float(tanfovy), int(H), int(W), sh, int(degree), campos, bool(prefiltered), use,
-                                                   not strict)
-        else:
-            out, tickets = _forward_batch_ctypes(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                                                 viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree,
-                                                 campos, prefiltered, use, V), None
-        if P == 0:
-            return ([0] * V,) + tuple(out[1:])
-        R = _settle(out[0], key, strict, use, cap, V, tickets)
-        if R is not None:
-            return (R,) + tuple(out[1:])
-        use = int(max(r[0] for r in out[0].tolist()) * 1.1) + 4096  # overflow: those views' tile lists were left empty
+            return getattr(ext, f"{variant}_forward_batch")(
+                bg, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrices, gt_depths,
+                projmatrices, float(tanfovx), float(tanfovy), int(H), int(W), sh, int(degree), campos, bool(prefiltered), cap, lazy)
+        return _attempt_ctypes(variant, View, outputs, bg, means3D, colors, opacity, scales, rotations, scale_modifier,
+                               cov3D_precomp, viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos,
+                               prefiltered, cap, V), None
+    return _binning.run_batch((means3D.device.index, P, H, W), P, V, attempt)
 
 
-def _forward_batch_ctypes(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,
-                          projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, cap, V):
-    """One attempt with binning capacity `cap` per view; returns ([V,4] status, color, depth, median, var, alpha, radii, geom,
-    binning, img, unc, px) as the extension's light_forward_batch."""
+def _attempt_ctypes(variant, View, outputs, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+                    viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, cap, V):
+    """One ctypes attempt of _forward_views with binning capacity `cap` per view; returns what the extension returns."""
     lib = _lib()
     dev = means3D.device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -146,29 +97,49 @@ def _forward_batch_ctypes(bg, means3D, colors, opacity, scales, rotations, scale
     viewmatrices, projmatrices, campos, gt_depths = c(viewmatrices, dev), c(projmatrices, dev), c(campos, dev), c(gt_depths, dev)
     P = means3D.size(0)
     M = sh.size(1) if sh.numel() != 0 else 0
-    color = torch.empty((V, 3, H, W), **f32)
-    depth, median, var, alpha = (torch.empty((V, 1, H, W), **f32) for _ in range(4))
-    mk = torch.empty if P else torch.zeros
-    radii = mk((V, P), **i32)
-    unc = mk((V, P, 1), **f32)
-    px = mk((V, P, 1), **i32)
+    out = outputs(V, P, H, W, f32, i32)
     geom = torch.empty((V, max(lib.dgr_geometry_bytes(P), 1)), **u8)
     img = torch.empty((V, max(lib.dgr_image_bytes(W, H), 1)), **u8)
     binning = torch.empty((V, max(lib.dgr_binning_bytes(cap, W, H), 1)), **u8)
     status = torch.zeros((V, 4), **i32)
-    views = (_View * V)()
+    views = (View * V)()
     for v in range(V):
         w = views[v]
         w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer = _row(geom, v), _row(binning, v), cap, _row(img, v)
         w.status, w.viewmatrix, w.projmatrix, w.cam_pos = _row(status, v), _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v)
-        w.out_color, w.out_depth, w.out_median_depth, w.out_alpha = _row(color, v), _row(depth, v), _row(median, v), _row(alpha, v)
-        w.gt_depth, w.out_depth_var = _row(gt_depths, v), _row(var, v)
-        w.gau_uncertainty, w.gau_related_pixels, w.radii = _row(unc, v), _row(px, v), _row(radii, v)
+        w.gt_depth = _row(gt_depths, v)
+        for k, t in out.items():
+            setattr(w, k, _row(t, v))
     p = _capi.ptr
-    _light._check(lib.dgr_light_forward_batch(_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D),
-                                              p(sh), p(colors), p(opacity), p(scales), float(scale_modifier), p(rotations),
-                                              p(cov3D_precomp), float(tanfovx), float(tanfovy), int(bool(prefiltered))))
-    return status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px
+    _light._check(getattr(lib, f"dgr_{variant}_forward_batch")(
+        _capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(opacity),
+        p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), int(bool(prefiltered))))
+    i, o = list(out).index("radii") + 1, list(out.values())
+    return (status, *o[:i], geom, binning, img, *o[i:])
+
+
+def _outputs(V, P, H, W, f32, i32):
+    """The light batch's output tensors (_forward_views)."""
+    mk = torch.empty if P else torch.zeros
+    return {"out_color": torch.empty((V, 3, H, W), **f32), "out_depth": torch.empty((V, 1, H, W), **f32),
+            "out_median_depth": torch.empty((V, 1, H, W), **f32), "out_depth_var": torch.empty((V, 1, H, W), **f32),
+            "out_alpha": torch.empty((V, 1, H, W), **f32), "radii": mk((V, P), **i32), "gau_uncertainty": mk((V, P, 1), **f32),
+            "gau_related_pixels": mk((V, P, 1), **i32)}
+
+
+def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,
+                   projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered):
+    """Returns (per-view R for the backward, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)."""
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
+    V = viewmatrices.size(0)
+    if not 1 <= V <= MAX_VIEWS:
+        raise RuntimeError(f"1 .. {MAX_VIEWS} views per batch")
+    R, out = _forward_views("light", _View, _outputs, V, bg, means3D, colors, opacity, scales, rotations, scale_modifier,
+                            cov3D_precomp, viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos,
+                            prefiltered)
+    return (R,) + tuple(out[1:])
 
 
 def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
@@ -187,17 +158,34 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
                                      int(degree), campos, geom, binning, img, alphas, perspec_matrix, bool(track_off),
                                      bool(map_off), bool(need_gaussian_grads), bool(need_means2D), num_rendered)
         return tuple(g)
+    if not need_gaussian_grads:
+        map_off = True  # nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
+    return _backward_views("light", _ViewGrad, {"alphas": alphas, "dL_dpix": gC, "dL_dpix_depth": gD, "dL_dpix_median_depth": gM,
+                                                 "dL_dpix_depth_var": gV},
+                           (int(bool(track_off)), int(bool(map_off))), bg, means3D, radii, colors, scales, rotations,
+                           scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh, degree,
+                           campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad)
+
+
+def _backward_views(variant, ViewGrad, per_view, tail, bg, means3D, radii, colors, scales, rotations, scale_modifier,
+                    cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh, degree, campos, geom, binning,
+                    img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad):
+    """The ctypes batch backward of both variants: dgr_<variant>_backward_batch[_absgrad] with `ViewGrad` views.  `per_view`:
+    the variant's own [V, ...] inputs by the view struct's field name (None: NULL; "dL_dpix" is the colour gradient [V,3,H,W]);
+    `tail`: the entry point's arguments after the common ones.  Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity,
+    dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview [V,4,4]) and, with absgrad, every view's absolute
+    screen-space gradient [V,P,3]."""
     lib = _lib()
     dev = means3D.device
     V, P = viewmatrices.size(0), means3D.size(0)
-    H, W = gC.size(2), gC.size(3)
+    H, W = per_view["dL_dpix"].size(2), per_view["dL_dpix"].size(3)
     f32 = dict(dtype=torch.float32, device=dev)
     c = _light._f32c
     means3D, bg, colors = c(means3D, dev), c(bg, dev), c(colors, dev)
     scales, rotations, cov3D_precomp, sh = c(scales, dev), c(rotations, dev), c(cov3D_precomp, dev), c(sh, dev)
     viewmatrices, projmatrices, campos = c(viewmatrices, dev), c(projmatrices, dev), c(campos, dev)
-    gt_depths, alphas, perspec_matrix = c(gt_depths, dev), c(alphas, dev), c(perspec_matrix, dev)
-    gC, gD, gM, gV = c(gC, dev), c(gD, dev), c(gM, dev), c(gV, dev)
+    gt_depths, perspec_matrix = c(gt_depths, dev), c(perspec_matrix, dev)
+    per_view = {k: None if t is None else c(t, dev) for k, t in per_view.items()}
     M = sh.size(1) if sh.numel() != 0 else 0
     if need_gaussian_grads:
         seg = _light._grad_arena(P, M, f32)
@@ -206,39 +194,41 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
         d2 = torch.empty((V, P, 3), **f32) if need_means2D else None
     else:
         d3 = dsh = dop = dsc = drot = dcov = dcol = d2 = None
-        map_off = True  # nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
     dview = torch.empty((V, 4, 4), **f32)
     nscr = (max(lib.dgr_light_backward_scratch_bytes_r(P, W, H, max(num_rendered + [0])), 1) + 255) // 256 * 256
     scratch = torch.empty((V, nscr), dtype=torch.uint8, device=dev)
-    views = (_ViewGrad * V)()
+    views = (ViewGrad * V)()
     pp = _capi.ptr(perspec_matrix)
     for v in range(V):
         w = views[v]
         w.geometry_buffer, w.binning_buffer, w.image_buffer = _row(geom, v), _row(binning, v), _row(img, v)
         w.viewmatrix, w.projmatrix, w.cam_pos, w.perspec_matrix = _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v), pp
-        w.alphas, w.gt_depth, w.radii = _row(alphas, v), _row(gt_depths, v), _row(radii, v)
-        w.dL_dpix, w.dL_dpix_depth, w.dL_dpix_median_depth, w.dL_dpix_depth_var = _row(gC, v), _row(gD, v), _row(gM, v), _row(gV, v)
+        w.gt_depth, w.radii = _row(gt_depths, v), _row(radii, v)
+        for k, t in per_view.items():
+            setattr(w, k, _row(t, v))
         w.dL_dmean2D, w.dL_dview, w.scratch, w.scratch_bytes = _row(d2, v), _row(dview, v), _row(scratch, v), nscr
         w.num_rendered = num_rendered[v]
     p = _capi.ptr
     q = lambda t: None if t is None else p(t)  # noqa: E731
     args = (_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
             float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), q(dop), q(dcol), q(d3), q(dcov),
-            q(dsh), q(dsc), q(drot), int(bool(track_off)), int(bool(map_off)))
+            q(dsh), q(dsc), q(drot)) + tail
     if not absgrad:
-        _light._check(lib.dgr_light_backward_batch(*args))
+        _light._check(getattr(lib, f"dgr_{variant}_backward_batch")(*args))
         return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview
     dabs = torch.empty((V, P, 3), **f32)
-    _light._check(lib.dgr_light_backward_batch_absgrad(*args, (C.c_void_p * V)(*(_row(dabs, v) for v in range(V)))))
+    _light._check(getattr(lib, f"dgr_{variant}_backward_batch_absgrad")(*args, (C.c_void_p * V)(*(_row(dabs, v) for v in range(V)))))
     return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview, dabs
 
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
-    """`_RasterizeGaussians` (L/diff_gaussian_rasterization/__init__.py:48-176) over V cameras."""
+    """`_RasterizeGaussians` (L/diff_gaussian_rasterization/__init__.py:48-176) over V cameras.  `means2D_abs`: one more leaf
+    [V,P,3] whose gradient is every view's absolute screen-space gradient (absgrad, include/dgr_hip.h:
+    dgr_light_backward_batch_absgrad), or None."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
-                gt_depths, raster_settings):
+                gt_depths, raster_settings, means2D_abs=None):
         rs = raster_settings
         with _capi.on_device(means3D.device):
             out = _forward_batch(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
@@ -247,6 +237,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         (num_rendered, color, depth, depth_median, depth_var, opacity_map, radii, geom, binning, img, unc, px) = out
         ctx.raster_settings = rs
         ctx.num_rendered = num_rendered
+        ctx.absgrad = means2D_abs is not None
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning,
                               img, opacity_map, gt_depths)
@@ -261,7 +252,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
          gt_depths) = ctx.saved_tensors
         V, H, W = viewmatrices.size(0), int(rs.image_height), int(rs.image_width)
         zeros = lambda ch: torch.zeros((V, ch, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
-        absgrad = getattr(ctx, "absgrad", False)  # (_RasterizeGaussiansBatchAbs)
+        absgrad = ctx.absgrad
         grad_color = zeros(3) if grad_color is None else grad_color
         grad_depth = zeros(1) if grad_depth is None else grad_depth
         grad_depth_median = zeros(1) if grad_depth_median is None else grad_depth_median
@@ -273,27 +264,10 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 rs.projmatrices, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_depth_median, grad_depth_var, gt_depths, sh,
                 rs.sh_degree, rs.campos, geom, binning, img, opacity_map, rs.perspec_matrix, rs.track_off, rs.map_off,
                 need_gaussian_grads=any(need[:8]) or absgrad, need_means2D=bool(need[1]), num_rendered=ctx.num_rendered,
-                **({"absgrad": True} if absgrad else {}))
+                absgrad=absgrad)
         (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = g[:9]
         _light._consume_post_backward_wait()
-        grads = (g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None)
-        return grads + (g[9],) if absgrad else grads
-
-
-class _RasterizeGaussiansBatchAbs(torch.autograd.Function):
-    """_RasterizeGaussiansBatch with one more leaf, means2D_abs [V,P,3], whose gradient is every view's absolute screen-space
-    gradient (absgrad, include/dgr_hip.h: dgr_light_backward_batch_absgrad)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
-                gt_depths, raster_settings, means2D_abs):
-        ctx.absgrad = True
-        return _RasterizeGaussiansBatch.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                                cov3Ds_precomp, viewmatrices, gt_depths, raster_settings)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        return _RasterizeGaussiansBatch.backward(ctx, *grads)
+        return g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None, g[9] if absgrad else None
 
 
 def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
@@ -316,23 +290,14 @@ class GaussianRasterizerBatch(torch.nn.Module):
                 cov3D_precomp=None, viewmatrices=None, gt_depths=None, *, means2D_abs=None):
         # means2D_abs (absgrad): a float32 [V,P,3] leaf whose .grad receives every view's absolute screen-space gradient
         # (dgr_amd.light.GaussianRasterizer.forward)
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-        e = torch.Tensor([])
-        shs = e if shs is None else shs
-        colors_precomp = e if colors_precomp is None else colors_precomp
-        scales = e if scales is None else scales
-        rotations = e if rotations is None else rotations
-        cov3D_precomp = e if cov3D_precomp is None else cov3D_precomp
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _light._checked_inputs(shs, colors_precomp, scales, rotations,
+                                                                                       cov3D_precomp)
         if viewmatrices is None:
             viewmatrices = self.raster_settings.viewmatrices
         if means2D_abs is not None:
             _light.check_means2D_abs(means2D_abs, means3D, self.raster_settings.map_off,
                                      shape=(viewmatrices.size(0), means3D.size(0), 3))
-            return _RasterizeGaussiansBatchAbs.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                     cov3D_precomp, viewmatrices, gt_depths, self.raster_settings, means2D_abs)
+            return _RasterizeGaussiansBatch.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                                  cov3D_precomp, viewmatrices, gt_depths, self.raster_settings, means2D_abs)
         return rasterize_gaussians_batch(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                          viewmatrices, gt_depths, self.raster_settings)

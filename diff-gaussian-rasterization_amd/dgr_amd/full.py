@@ -11,27 +11,19 @@ from typing import NamedTuple
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _binning, _capi
 from . import light as _light
-from .light import _capacity_cache, _check, _f32c, _grad_arena
+from .light import _check, _device_guarded, _f32c, _grad_arena, set_tight_culling  # noqa: F401  (set_tight_culling: shared)
 
 
-def set_tight_culling(on=True):
-    """Opt in to alpha-aware tile rectangles (include/dgr_hip.h: dgr_set_option "tight_cull"): same images and gradients,
-    ~40 % fewer tile instances; `num_rendered` and the opaque state buffers are then not the reference's.  Process-wide."""
-    _capi.set_option("tight_cull", 1 if on else 0)
-
-
-def _device_guarded(arg_index):
-    """Runs a `_C` function with its tensors' device current (kernels, events and the stream handle all belong to the
-    device of `means3D`, whichever device the caller had selected)."""
-    def deco(fn):
-        def wrapped(*a, **kw):
-            with _capi.on_device(a[arg_index].device):
-                return fn(*a, **kw)
-        wrapped.__name__, wrapped.__doc__ = fn.__name__, fn.__doc__
-        return staticmethod(wrapped)
-    return deco
+def _full_outputs(P, H, W, gt_depth, f32, i32):
+    """The full forward's output tensors, and their pointers in the order of its entry points' output arguments."""
+    color = torch.empty((3, H, W), **f32)
+    depth = torch.empty((1, H, W), **f32)
+    unc = torch.empty((1, H, W), **f32)
+    radii = torch.zeros((P,), **i32)
+    p = _capi.ptr
+    return (color, depth, unc, radii), (p(color), p(depth), p(gt_depth), p(unc), p(radii))
 
 
 class _C:
@@ -47,81 +39,13 @@ class _C:
     def rasterize_gaussians_r(background, means3D, colors, opacity, scales, rotations, scale_modifier,
                               cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
                               image_height, image_width, sh, degree, campos, prefiltered):
-        """(R for the backward, the `rasterize_gaussians` tuple): see dgr_amd.light._C.rasterize_gaussians_r."""
-        if means3D.ndimension() != 2 or means3D.size(1) != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")
-        lib = _capi.load()
-        dev = means3D.device
-        if dev.type != "cuda":
-            raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
-        P, H, W = means3D.size(0), int(image_height), int(image_width)
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        u8 = dict(dtype=torch.uint8, device=dev)
-        means3D = _f32c(means3D, dev)
-        background, colors, opacity = _f32c(background, dev), _f32c(colors, dev), _f32c(opacity, dev)
-        scales, rotations, cov3D_precomp = _f32c(scales, dev), _f32c(rotations, dev), _f32c(cov3D_precomp, dev)
-        viewmatrix, projmatrix, campos = _f32c(viewmatrix, dev), _f32c(projmatrix, dev), _f32c(campos, dev)
-        gt_depth, sh = _f32c(gt_depth, dev), _f32c(sh, dev)
-        M = sh.size(1) if sh.numel() != 0 else 0
-        out_color = torch.empty((3, H, W), **f32)
-        out_depth = torch.empty((1, H, W), **f32)
-        out_unc = torch.empty((1, H, W), **f32)
-        radii = torch.zeros((P,), **i32)
-        st = _capi.stream_handle(dev.index)
-        p = _capi.ptr
-        common = (P, int(degree), M, p(background), W, H, p(means3D), p(sh), p(colors), p(opacity), p(scales),
-                  float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos),
-                  float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), p(out_color), p(out_depth), p(gt_depth),
-                  p(out_unc), p(radii))
-        key = (dev.index, P, H, W)
-        mode, use, cap = _light._binning_policy(key, P)  # (the compiled binding's policy: lazy mode honours _unsettled)
-        if mode == 0:
-            import ctypes as C
-            bufs = {k: torch.empty((0,), **u8) for k in ("geom", "binning", "img")}
-
-            def mk(name):
-                def cb(nbytes, _user):
-                    bufs[name] = torch.empty((max(int(nbytes), 1),), **u8)
-                    return bufs[name].data_ptr()
-                return _capi.ALLOC_FN(cb)
-            cbs = [mk("geom"), mk("binning"), mk("img")]
-            ng = C.c_int(0)
-            rendered = R = _check(lib.dgr_full_forward(st, cbs[0], cbs[1], cbs[2], None, *common, C.byref(ng)))
-            related = ng.value
-            geomBuffer, binningBuffer, imgBuffer = bufs["geom"], bufs["binning"], bufs["img"]
-        else:
-            geomBuffer = torch.empty((lib.dgr_geometry_bytes(P),), **u8)
-            imgBuffer = torch.empty((lib.dgr_image_bytes(W, H),), **u8)
-            status = torch.empty((4,), **i32)
-            if mode == 2:
-                # no host synchronisation (dgr_amd/light.py): the status word is checked one call late; the tuple's
-                # num_rendered / num_related members are the values last read back for this shape, the backward's R is the
-                # capacity the binning buffer was carved with
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
-                _check(lib.dgr_full_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer), p(status),
-                                                     *common))
-                _light._post_status(status, key)
-                related = _light._last_status.get(key, (0, 0, 0, 0))[3]
-                return use, (_capacity_cache[key], related, out_color, out_depth, out_unc, radii, geomBuffer, binningBuffer,
-                             imgBuffer)
-            while True:
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
-                lib.dgr_early_status_arm()
-                _check(lib.dgr_full_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer), p(status),
-                                                     *common))
-                s = _light._early_status(lib)  # waits until num_rendered is known, not for the whole forward
-                if s[2]:
-                    raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-                rendered = R = s[0]
-                if rendered <= use:
-                    break
-                use = int(rendered * 1.1) + 4096
-            # num_related (the reference's NG) is produced by the forward blend: the second blocking read of the reference
-            # (F/cuda_rasterizer/rasterizer_impl.cu:498); lazy mode reports it one call late instead
-            related = status.tolist()[3]
-            _light._strict_read(key, cap, rendered, related)
-        return R, (rendered, related, out_color, out_depth, out_unc, radii, geomBuffer, binningBuffer, imgBuffer)
+        """(R for the backward, the `rasterize_gaussians` tuple): see dgr_amd.light._C.rasterize_gaussians_r.  num_related is
+        the callback forward's NG, the strict forward's status word [3] and, for a lazy forward, the last one read."""
+        R, rendered, related, out, geom, binning, img = _light._forward_r(
+            True, _full_outputs, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+            viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered)
+        color, depth, unc, radii = out
+        return R, (rendered, related, color, depth, unc, radii, geom, binning, img)
 
     @_device_guarded(1)
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -186,21 +110,11 @@ class _CompiledC:
         """(R for the backward, the `rasterize_gaussians` tuple): see dgr_amd.light._C.rasterize_gaussians_r."""
         P, H, W = means3D.size(0) if means3D.dim() else 0, int(image_height), int(image_width)
         key = (means3D.device.index, P, H, W)
-        mode, use, cap = _light._binning_policy(key, P)
+        mode, use, cap = _binning._binning_policy(key, P)
         (rendered, related, ticket, used, status, color, depth, unc, radii, geom, binning, img) = _CompiledC.ext.full_forward(
             background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
             gt_depth, projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered), use, mode)
-        R = rendered
-        if mode == 2:
-            if ticket >= 0:
-                _light._pending_status.append((ticket, key))
-            else:
-                import weakref
-                _light._captured_status.append(weakref.ref(status))
-                _light._capture_keepalive.append(status)
-            rendered, related, R = _capacity_cache[key], _light._last_status.get(key, (0, 0, 0, 0))[3], used
-        elif mode == 1:
-            _light._strict_read(key, cap, rendered, related)
+        rendered, related, R = _binning.record(key, mode, cap, used, rendered, status, ticket, related)
         return R, (rendered, related, color, depth, unc, radii, geom, binning, img)
 
     @staticmethod
@@ -231,22 +145,14 @@ def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales,
     dgr_amd.light._rasterize_compiled."""
     P, H, W = (means3D.size(0) if means3D.dim() == 2 else 0), rs.image_height, rs.image_width
     key = (means3D.device.index, P, H, W)
-    mode, use, cap = _light._binning_policy(key, P)
-    out, rendered, related, ticket, _, status = _CompiledC.ext.full_apply(
+    mode, use, cap = _binning._binning_policy(key, P)
+    out, rendered, related, ticket, used, status = _CompiledC.ext.full_apply(
         means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, gt_depth, rs.bg,
         rs.projmatrix, rs.campos, rs.perspec_matrix, rs.scale_modifier, rs.tanfovx, rs.tanfovy, H, W, rs.sh_degree,
         rs.prefiltered, use, mode)
-    if mode == 2:
-        if ticket >= 0:
-            _light._pending_status.append((ticket, key))
-        else:
-            import weakref
-            _light._captured_status.append(weakref.ref(status))
-            _light._capture_keepalive.append(status)
-    elif mode == 1:
-        # (the strict node does not wait for num_related -- csrc/torch_ext.cpp: full_forward_core -- and reports -1: _strict_read
-        #  keeps the last one read)
-        _light._strict_read(key, cap, rendered, related)
+    # (the strict node does not wait for num_related -- csrc/torch_ext.cpp: full_forward_core -- and reports -1: the record keeps
+    #  the last one read)
+    _binning.record(key, mode, cap, used, rendered, status, ticket, related)
     return tuple(out)
 
 
@@ -260,9 +166,11 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 
 
 class _RasterizeGaussians(torch.autograd.Function):
+    """`means2D_abs`: one more leaf [P,3] or None (absgrad: dgr_amd.light._RasterizeGaussians)."""
+
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
-                gt_depth, raster_settings):
+                gt_depth, raster_settings, means2D_abs=None):
         # argument packing of F/diff_gaussian_rasterization/__init__.py:62-83
         args = (
             raster_settings.bg,
@@ -290,6 +198,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             imgBuffer) = _C.rasterize_gaussians_r(*args)
         ctx.raster_settings = raster_settings
         ctx.num_rendered = R
+        ctx.absgrad = means2D_abs is not None
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
         ctx.num_related_gaussians = num_related_gaussians
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, radii, sh,
@@ -308,7 +217,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         # outputs that did not take part in the loss arrive as None: zeros, as the reference's autograd would have passed
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
         zeros = lambda c: torch.zeros((c, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
-        absgrad = getattr(ctx, "absgrad", False)  # (_RasterizeGaussiansAbs)
+        absgrad = ctx.absgrad
         grad_out_color = zeros(3) if grad_out_color is None else grad_out_color
         grad_out_depth = zeros(1) if grad_out_depth is None else grad_out_depth
         if absgrad and grad_out_uncertainty is None:  # NULL: the lean blend backward (bit-identical to a zero image)
@@ -361,23 +270,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_viewmatrix,
             None,
             None,
+            grad_means2D_abs,
         )
-        return grads + (grad_means2D_abs,) if absgrad else grads
-
-
-class _RasterizeGaussiansAbs(torch.autograd.Function):
-    """_RasterizeGaussians with one more leaf, means2D_abs [P,3] (absgrad: dgr_amd.light._RasterizeGaussiansAbs)."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
-                gt_depth, raster_settings, means2D_abs):
-        ctx.absgrad = True
-        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                           cov3Ds_precomp, viewmatrix, gt_depth, raster_settings)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        return _RasterizeGaussians.backward(ctx, *grads)
+        return grads
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -415,27 +310,10 @@ class GaussianRasterizer(nn.Module):
         raster_settings = self.raster_settings
         if means2D_abs is not None:
             _light.check_means2D_abs(means2D_abs, means3D, False)
-
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-
-        if shs is None:
-            shs = _light._EMPTY
-        if colors_precomp is None:
-            colors_precomp = _light._EMPTY
-        if scales is None:
-            scales = _light._EMPTY
-        if rotations is None:
-            rotations = _light._EMPTY
-        if cov3D_precomp is None:
-            cov3D_precomp = _light._EMPTY
-
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _light._checked_inputs(shs, colors_precomp, scales, rotations,
+                                                                                       cov3D_precomp)
         if means2D_abs is not None:
-            return _RasterizeGaussiansAbs.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+            return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
                                                 cov3D_precomp, viewmatrix, gt_depth, raster_settings, means2D_abs)
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
                                    viewmatrix, gt_depth, raster_settings)

@@ -13,7 +13,6 @@ to a caller of the autograd surface:
 """
 import ctypes as C
 import os
-import weakref
 from typing import NamedTuple
 
 import threading
@@ -21,7 +20,11 @@ import threading
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _binning, _capi
+# The binning status policy and its state live in dgr_amd._binning; the names outside code reads are the same objects here
+# (mutated in place there, never rebound).  The lazy depth is reached through lazy_depth() / set_lazy_depth() only.
+from ._binning import (_capacity_cache, _capture_keepalive, _check, _check_oldest, _last_status, _pending_status,  # noqa: F401
+                       _unsettled, check_async_errors, check_captured_status, lazy_depth, set_lazy_depth)
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -38,136 +41,6 @@ def _f32c(t, dev):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
-
-
-# binning capacity learned per (device, P, H, W): largest num_rendered seen for that shape
-_capacity_cache = {}
-
-# DGR_SYNC_MODE=lazy: once a shape's num_rendered is known, forward performs NO host synchronisation.  The binning
-# buffer is over-provisioned (1.5x the largest count seen); the device status word {num_rendered, overflow,
-# prefiltered violation, -} is copied asynchronously to pinned host memory behind an event, and inspected when a
-# later call starts (or by check_async_errors()), by which time the event has long fired.  An overflow or a
-# `prefiltered` violation therefore raises one or two calls late.  Default ("strict"): one status read at the end of
-# every forward, like the reference's blocking copy of num_rendered (L/cuda_rasterizer/rasterizer_impl.cu:287).
-_pending_status = []   # [(ticket of dgr_status_post, key)]
-# Status words left unread when a forward is issued.  1: view i is issued once view i-2's forward has reported -- with several
-# views in flight on several streams (dgr_amd.multiview.ViewStreams) that starves a stream whose previous view has finished
-# while the view whose report the host waits for is still in its blend kernels; ViewStreams raises it to its number of streams
-# (three views in flight, config 3: 0.483 -> 0.473 ms per step over 20 steps, 0.434 -> 0.428 over 100: profiles/r6/lazy_depth.txt).
-# The price: an overflow or a `prefiltered` violation is reported up to depth + 1 calls late instead of two.
-_LAZY_DEPTH = max(1, int(os.environ.get("DGR_LAZY_DEPTH", "1")))
-
-
-def lazy_depth():
-    return _LAZY_DEPTH
-
-
-def set_lazy_depth(n):
-    """See _LAZY_DEPTH above; returns the previous value."""
-    global _LAZY_DEPTH
-    prev, _LAZY_DEPTH = _LAZY_DEPTH, max(1, int(n))
-    return prev
-_last_status = {}      # key -> the most recent status word read back for that shape
-
-
-def _sync_mode():
-    return os.environ.get("DGR_SYNC_MODE", "strict")
-
-
-# Status words of forwards recorded into a hipGraph (torch.cuda.graph): nothing can be read back while capturing, so the
-# device tensors are kept and inspected on request after a replay (check_captured_status()).
-_captured_status = []     # weak references: a status word lives as long as the capture that owns it
-_capture_keepalive = []   # strong references collected during ONE capture; CapturedStep takes them over
-
-
-def _post_status(status, key):
-    if torch.cuda.is_current_stream_capturing():
-        _captured_status.append(weakref.ref(status))  # kept alive by the captured step's results (CapturedStep.keep)
-        _capture_keepalive.append(status)
-        return
-    # the library copies the word to pinned host memory behind an event (include/dgr_hip.h: dgr_status_post)
-    ticket = _capi.load().dgr_status_post(_capi.stream_handle(status.device.index), status.data_ptr())
-    _check(ticket)
-    _pending_status.append((ticket, key))
-
-
-# Lazy mode is only as safe as its capacity guess (1.5 x the largest count seen for the shape): a count that GROWS -- the camera
-# closing in, splats being scaled up, a map that densifies without changing P -- reaches it within a few frames, and frames rendered
-# past it have empty tile lists.  Three guards (round 9):
-#   * the blend kernels write NaN images for an overflowed forward (csrc/render_light.hip), never a plausible empty frame, and its
-#     backward (empty lists) yields zero gradients: nothing wrong reaches an optimiser unnoticed;
-#   * a shape whose count grew by more than 25 % between two status reads, came within 20 % of the capacity it was rendered with,
-#     or overflowed, is UNSETTLED: its next forwards run strict (exact count, overflow retried inside the call) until three
-#     reads in a row show less than 10 % growth;
-#   * check_async_errors() before optimizer.step() reads every outstanding word (the forwards' words arrive while their backward
-#     kernels are still queued: the wait costs the GPU nothing) and raises -- dgr_amd.slam's loops and examples/mapping.py do.
-_unsettled = {}        # key -> strict forwards still to run
-_GROWTH_STRICT, _SETTLED_READS = 1.25, 3
-
-
-def _note_growth(key, prev, s, capacity_used=None):
-    grew = prev > 0 and s[0] > _GROWTH_STRICT * prev
-    near = capacity_used is not None and s[0] > 0.8 * capacity_used
-    if s[1] or grew or near:
-        _unsettled[key] = _SETTLED_READS
-    elif key in _unsettled and prev > 0 and s[0] <= 1.1 * prev:
-        _unsettled[key] -= 1
-        if _unsettled[key] <= 0:
-            del _unsettled[key]
-
-
-def _strict_read(key, cap, rendered, related=None):
-    """A strict forward returned its exact count (and retried an overflow inside the call).  `related`: the full variant's
-    num_related (the status word's [3], which its lazy forwards report), kept in every sync mode; < 0 when the forward did not
-    wait for it, and then the last one read stays."""
-    last = _last_status.get(key)  # (the previous count, read before it is overwritten)
-    lazy = _sync_mode() == "lazy"
-    if lazy:
-        _note_growth(key, last[0] if last else 0, (rendered, 0, 0, 0))
-    if lazy or related is not None:
-        if related is None or related < 0:
-            related = last[3] if last else 0
-        _last_status[key] = [rendered, 0, 0, related]
-    _capacity_cache[key] = max(cap, rendered)
-
-
-def _check_oldest():
-    ticket, key = _pending_status.pop(0)
-    buf = (C.c_int * 4)()
-    _check(_capi.load().dgr_status_poll(ticket, 1, buf))  # waits for that forward only
-    s = list(buf)
-    prev = _last_status.get(key, (0, 0, 0, 0))[0]
-    _note_growth(key, prev, s, capacity_used=int(_capacity_cache.get(key, 0) * 1.5) + 4096)
-    _capacity_cache[key] = max(_capacity_cache.get(key, 0), s[0])
-    _last_status[key] = s
-    if s[2]:
-        raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-    if s[1]:
-        raise RuntimeError(f"dgr_hip: binning buffer overflow in an earlier lazily-checked forward (needed {s[0]} "
-                           f"instances); its outputs were invalid -- rerun that step")
-
-
-def check_captured_status():
-    """After replaying a graph that contains forwards: raises if one of them overflowed its binning buffer (the graph
-    was captured with a smaller scene than it is replayed on) or hit the prefiltered trap.  Blocks on the device.
-    Status words whose graph no longer exists (the tensor's storage was freed with the graph's pool) are dropped."""
-    _captured_status[:] = [r for r in _captured_status if r() is not None]
-    for ref in _captured_status:
-        st = ref()
-        if st is None:
-            continue
-        for s in st.reshape(-1, 4).tolist():  # (a batched forward keeps the [V,4] status words of its views in one tensor)
-            if s[2]:
-                raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-            if s[1]:
-                raise RuntimeError(f"dgr_hip: binning buffer overflow in a graph-captured forward (needed {s[0]} instances): "
-                                   f"re-capture after an eager warm-up on the larger scene")
-
-
-def check_async_errors():
-    """Raises if an earlier lazily-checked forward overflowed its binning buffer or hit the prefiltered trap."""
-    while _pending_status:
-        _check_oldest()
 
 
 # dgr_amd.multiview.ViewStreams.before_backward(): an event the rasterizer backward THAT RUNS ON A GIVEN STREAM makes that
@@ -243,17 +116,6 @@ def _early_status(lib):
     return list(buf)
 
 
-def _check(rc):
-    if rc >= 0:
-        return rc
-    msg = _capi.last_error()
-    if rc == _capi.DGR_ERR_PREFILTERED:
-        raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-    if rc == _capi.DGR_ERR_BAD_ARGUMENT:
-        raise RuntimeError(f"dgr_hip: bad argument: {msg}")
-    raise RuntimeError(f"dgr_hip: error {rc}: {msg}")
-
-
 def set_tight_culling(on=True):
     """Opt in to alpha-aware tile rectangles (include/dgr_hip.h: dgr_set_option "tight_cull"): same images and gradients,
     ~40 % fewer tile instances; `num_rendered` and the opaque state buffers are then not the reference's.  Process-wide."""
@@ -272,6 +134,88 @@ def _device_guarded(arg_index):
     return deco
 
 
+def _light_outputs(P, H, W, gt_depth, f32, i32):
+    """The light forward's output tensors, and their pointers in the order of its entry points' output arguments."""
+    color = torch.empty((3, H, W), **f32)
+    depth, median, var, alpha = (torch.empty((1, H, W), **f32) for _ in range(4))
+    # radii is written for every Gaussian and the two median statistics are zeroed by the C ABI (stream memsets)
+    mk = torch.empty if P else torch.zeros
+    radii, unc, px = mk((P,), **i32), mk((P, 1), **f32), mk((P, 1), **i32)
+    p = _capi.ptr
+    return ((color, depth, median, var, alpha, radii, unc, px),
+            (p(color), p(depth), p(median), p(alpha), p(gt_depth), p(var), p(unc), p(px), p(radii)))
+
+
+def _forward_r(full, outputs, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+               gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug=False):
+    """The ctypes binding's one-view forward of both variants (L/rasterize_points.cu:35-129, F/rasterize_points.cu:35-120):
+    `full` picks the entry points, `outputs(P, H, W, gt_depth, f32, i32)` -> (the variant's output tensors, their pointers).
+    Returns (R for the backward, num_rendered and num_related (full; None for light) to report, the output tensors, geometry,
+    binning and image buffers); the mode and capacity come from dgr_amd._binning."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    lib = _capi.load()
+    dev = means3D.device
+    if dev.type != "cuda":
+        raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
+    P, H, W = means3D.size(0), int(image_height), int(image_width)
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    u8 = dict(dtype=torch.uint8, device=dev)
+    means3D = _f32c(means3D, dev)
+    background, colors, opacity = _f32c(background, dev), _f32c(colors, dev), _f32c(opacity, dev)
+    scales, rotations, cov3D_precomp = _f32c(scales, dev), _f32c(rotations, dev), _f32c(cov3D_precomp, dev)
+    viewmatrix, projmatrix, campos = _f32c(viewmatrix, dev), _f32c(projmatrix, dev), _f32c(campos, dev)
+    gt_depth, sh = _f32c(gt_depth, dev), _f32c(sh, dev)
+    M = sh.size(1) if sh.numel() != 0 else 0
+    out, out_ptrs = outputs(P, H, W, gt_depth, f32, i32)
+    st = _capi.stream_handle(dev.index)
+    p = _capi.ptr
+    common = (P, int(degree), M, p(background), W, H, p(means3D), p(sh), p(colors), p(opacity), p(scales),
+              float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos),
+              float(tan_fovx), float(tan_fovy), int(bool(prefiltered))) + out_ptrs
+    forward, presized = ((lib.dgr_full_forward, lib.dgr_full_forward_presized) if full else
+                         (lib.dgr_light_forward, lib.dgr_light_forward_presized))
+
+    key = (dev.index, P, H, W)
+    mode, use, cap = _binning._binning_policy(key, P)
+    if mode == 0:
+        bufs = {k: torch.empty((0,), **u8) for k in ("geom", "binning", "img")}
+
+        def mk(name):
+            def cb(nbytes, _user):
+                bufs[name] = torch.empty((max(int(nbytes), 1),), **u8)
+                return bufs[name].data_ptr()
+            return _capi.ALLOC_FN(cb)
+        cbs = [mk("geom"), mk("binning"), mk("img")]
+        ng = C.c_int(0)  # (the full variant's num_related; the light one takes the debug flag in its place)
+        rendered = _check(forward(st, cbs[0], cbs[1], cbs[2], None, *common, C.byref(ng) if full else int(bool(debug))))
+        return rendered, rendered, ng.value if full else None, out, bufs["geom"], bufs["binning"], bufs["img"]
+    geom = torch.empty((lib.dgr_geometry_bytes(P),), **u8)
+    img = torch.empty((lib.dgr_image_bytes(W, H),), **u8)
+    status = torch.empty((4,), **i32)
+    if mode == 2:
+        binning = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
+        _check(presized(st, p(geom), p(binning), use, p(img), p(status), *common))
+        rendered, related, R = _binning.record(key, 2, cap, use, None, status, related=-1 if full else None)
+        return R, rendered, related, out, geom, binning, img
+
+    def attempt(capacity):
+        binning = torch.empty((lib.dgr_binning_bytes(capacity, W, H),), **u8)
+        lib.dgr_early_status_arm()
+        _check(presized(st, p(geom), p(binning), capacity, p(img), p(status), *common))
+        # the one host wait of this forward: until num_rendered is known, a tenth of the way into the forward -- not until the
+        # forward has finished
+        return [_early_status(lib)], binning
+    # num_related (the reference's NG) is produced by the forward blend: the second blocking read of the reference
+    # (F/cuda_rasterizer/rasterizer_impl.cu:498); lazy mode reports it one call late instead
+    (rendered,), related, binning = _binning.strict_retry(key, cap, use, attempt,
+                                                          (lambda: status.tolist()[3]) if full else None)
+    if debug:
+        torch.cuda.synchronize(dev)
+    return rendered, rendered, related, out, geom, binning, img
+
+
 class _C:
     """Functions with the signatures of the reference's pybind11 module `_C` (L/ext.cpp:15-19)."""
 
@@ -286,84 +230,13 @@ class _C:
                               cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
                               image_height, image_width, sh, degree, campos, prefiltered, debug):
         """(R for the backward, the `rasterize_gaussians` tuple).  R is the exact count of a strict forward and the capacity
-        the binning buffer was carved with of a lazy one: at least the frame's count, which the deterministic backward's
-        row buffer needs (csrc/render_light.hip: det_gather_kernel writes NaN past R)."""
-        if means3D.ndimension() != 2 or means3D.size(1) != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")
-        lib = _capi.load()
-        dev = means3D.device
-        if dev.type != "cuda":
-            raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
-        P, H, W = means3D.size(0), int(image_height), int(image_width)
-        f32 = dict(dtype=torch.float32, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        means3D = _f32c(means3D, dev)
-        background, colors, opacity = _f32c(background, dev), _f32c(colors, dev), _f32c(opacity, dev)
-        scales, rotations, cov3D_precomp = _f32c(scales, dev), _f32c(rotations, dev), _f32c(cov3D_precomp, dev)
-        viewmatrix, projmatrix, campos = _f32c(viewmatrix, dev), _f32c(projmatrix, dev), _f32c(campos, dev)
-        gt_depth, sh = _f32c(gt_depth, dev), _f32c(sh, dev)
-        M = sh.size(1) if sh.numel() != 0 else 0
-
-        out_color = torch.empty((3, H, W), **f32)
-        out_depth = torch.empty((1, H, W), **f32)
-        out_median = torch.empty((1, H, W), **f32)
-        out_var = torch.empty((1, H, W), **f32)
-        out_alpha = torch.empty((1, H, W), **f32)
-        # radii is written for every Gaussian and the two median statistics are zeroed by the C ABI (stream memsets)
-        mk = torch.empty if P else torch.zeros
-        radii = mk((P,), **i32)
-        gau_unc = mk((P, 1), **f32)
-        gau_px = mk((P, 1), **i32)
-        u8 = dict(dtype=torch.uint8, device=dev)
-        st = _capi.stream_handle(dev.index)
-        p = _capi.ptr
-
-        common = (P, int(degree), M, p(background), W, H, p(means3D), p(sh), p(colors), p(opacity), p(scales),
-                  float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos),
-                  float(tan_fovx), float(tan_fovy), int(bool(prefiltered)), p(out_color), p(out_depth),
-                  p(out_median), p(out_alpha), p(gt_depth), p(out_var), p(gau_unc), p(gau_px), p(radii))
-
-        key = (dev.index, P, H, W)
-        mode, use, cap = _binning_policy(key, P)  # (the compiled binding's policy: lazy mode honours _unsettled)
-        if mode == 0:
-            bufs = {k: torch.empty((0,), **u8) for k in ("geom", "binning", "img")}
-
-            def mk(name):
-                def cb(nbytes, _user):
-                    bufs[name] = torch.empty((max(int(nbytes), 1),), **u8)
-                    return bufs[name].data_ptr()
-                return _capi.ALLOC_FN(cb)
-            cbs = [mk("geom"), mk("binning"), mk("img")]
-            rendered = R = _check(lib.dgr_light_forward(st, cbs[0], cbs[1], cbs[2], None, *common, int(bool(debug))))
-            geomBuffer, binningBuffer, imgBuffer = bufs["geom"], bufs["binning"], bufs["img"]
-        else:
-            geomBuffer = torch.empty((lib.dgr_geometry_bytes(P),), **u8)
-            imgBuffer = torch.empty((lib.dgr_image_bytes(W, H),), **u8)
-            status = torch.empty((4,), **i32)
-            if mode == 2:
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
-                _check(lib.dgr_light_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer),
-                                                      p(status), *common))
-                _post_status(status, key)
-                return use, (_capacity_cache[key], out_color, out_depth, out_median, out_var, out_alpha, radii, geomBuffer,
-                             binningBuffer, imgBuffer, gau_unc, gau_px)
-            while True:
-                binningBuffer = torch.empty((lib.dgr_binning_bytes(use, W, H),), **u8)
-                lib.dgr_early_status_arm()
-                _check(lib.dgr_light_forward_presized(st, p(geomBuffer), p(binningBuffer), use, p(imgBuffer),
-                                                      p(status), *common))
-                s = _early_status(lib)  # the one host wait of this forward: until num_rendered is known, a tenth of the
-                if s[2]:                # way into the forward -- not until the forward has finished
-                    raise RuntimeError("Point is filtered although prefiltered is set. This shouldn't happen!")
-                rendered = R = s[0]
-                if rendered <= use:
-                    break
-                use = int(rendered * 1.1) + 4096  # overflow: every tile list was left empty; run again
-            _strict_read(key, cap, rendered)
-            if debug:
-                torch.cuda.synchronize(dev)
-        return R, (rendered, out_color, out_depth, out_median, out_var, out_alpha, radii, geomBuffer, binningBuffer,
-                   imgBuffer, gau_unc, gau_px)
+        the binning buffer was carved with of a lazy one (dgr_amd._binning.record)."""
+        R, rendered, _, out, geom, binning, img = _forward_r(
+            False, _light_outputs, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
+            viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered,
+            debug)
+        color, depth, median, var, alpha, radii, unc, px = out
+        return R, (rendered, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)
 
     @_device_guarded(1)
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
@@ -450,24 +323,14 @@ class _CompiledC:
                               viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
                               campos, prefiltered, debug):
         """(R for the backward, the `rasterize_gaussians` tuple): see _C.rasterize_gaussians_r."""
-        ext = _CompiledC.ext
         P, H, W = means3D.size(0) if means3D.dim() else 0, int(image_height), int(image_width)
         key = (means3D.device.index, P, H, W)
-        mode, use, cap = _binning_policy(key, P)
-        (rendered, ticket, used, status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px) = ext.light_forward(
+        mode, use, cap = _binning._binning_policy(key, P)
+        (rendered, ticket, used, status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px) = _CompiledC.ext.light_forward(
             background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
             gt_depth, projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered),
             bool(debug), use, mode)
-        R = rendered
-        if mode == 2:
-            if ticket >= 0:
-                _pending_status.append((ticket, key))
-            else:  # recorded into a hipGraph: nothing can be read back now
-                _captured_status.append(weakref.ref(status))
-                _capture_keepalive.append(status)
-            rendered, R = _capacity_cache[key], used
-        elif mode == 1:
-            _strict_read(key, cap, rendered)
+        rendered, _, R = _binning.record(key, mode, cap, used, rendered, status, ticket)
         return R, (rendered, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)
 
     @staticmethod
@@ -502,23 +365,6 @@ if os.environ.get("DGR_BINDING", "compiled") != "ctypes" and not os.environ.get(
         pass
 
 
-def _binning_policy(key, P, depth=None):
-    """(mode, capacity, cached count) of the next forward of shape `key` = (device, P, H, W); see csrc/torch_ext.cpp:
-    light_forward_core.  Every binding and batch of both variants takes its mode and capacity from here.  `depth`: the status
-    words left unread (default lazy_depth(); a batch of V views posts V per call)."""
-    cap = _capacity_cache.get(key, 0)
-    if os.environ.get("DGR_FORWARD_MODE", "presized") == "callback" or P == 0:
-        return 0, 0, cap
-    if _sync_mode() == "lazy" and cap > 0:
-        while len(_pending_status) > (_LAZY_DEPTH if depth is None else depth) and not torch.cuda.is_current_stream_capturing():
-            _check_oldest()  # status words of earlier calls have long completed: no stall
-        if key not in _unsettled or torch.cuda.is_current_stream_capturing():
-            return 2, int(cap * 1.5) + 4096, cap
-        # an unsettled shape (above): strict forwards, which also keep the count history going
-        return 1, int(cap * 1.5) + 4096, cap
-    return 1, (int(cap * 1.25) + 4096 if cap else 4 * P + 4096), cap
-
-
 def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
                         gt_depth, rs):
     """`_RasterizeGaussians.apply` through the autograd node compiled into the extension (csrc/torch_ext.cpp: LightNode):
@@ -527,19 +373,12 @@ def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales,
     binding."""
     P, H, W = (means3D.size(0) if means3D.dim() == 2 else 0), rs.image_height, rs.image_width
     key = (means3D.device.index, P, H, W)
-    mode, use, cap = _binning_policy(key, P)
-    out, rendered, ticket, _, status = _CompiledC.ext.light_apply(
+    mode, use, cap = _binning._binning_policy(key, P)
+    out, rendered, ticket, used, status = _CompiledC.ext.light_apply(
         means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, gt_depth, rs.bg,
         rs.projmatrix, rs.campos, rs.perspec_matrix, rs.scale_modifier, rs.tanfovx, rs.tanfovy, H, W, rs.sh_degree,
         rs.prefiltered, rs.track_off, rs.map_off, use, mode)
-    if mode == 2:
-        if ticket >= 0:
-            _pending_status.append((ticket, key))
-        else:  # recorded into a hipGraph: nothing can be read back now
-            _captured_status.append(weakref.ref(status))
-            _capture_keepalive.append(status)
-    elif mode == 1:
-        _strict_read(key, cap, rendered)
+    _binning.record(key, mode, cap, used, rendered, status, ticket)
     return tuple(out)
 
 
@@ -575,9 +414,13 @@ def rasterize_gaussians(
 
 
 class _RasterizeGaussians(torch.autograd.Function):
+    """`means2D_abs` (absgrad, an extension): one more leaf [P,3] whose gradient is the absolute screen-space gradient
+    (include/dgr_hip.h: dgr_light_backward_absgrad); None when absent.  Over either binding's forward and backward: the compiled
+    LightNode has no such input."""
+
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                viewmatrix, gt_depth, raster_settings):
+                viewmatrix, gt_depth, raster_settings, means2D_abs=None):
         # argument packing of L/diff_gaussian_rasterization/__init__.py:66-87
         args = (
             raster_settings.bg,
@@ -617,6 +460,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 
         ctx.raster_settings = raster_settings
         ctx.num_rendered = R
+        ctx.absgrad = means2D_abs is not None
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, radii, sh,
                               geomBuffer, binningBuffer, imgBuffer, opacity_map, gt_depth)
@@ -637,7 +481,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         # reference's autograd would have passed
         H, W = int(raster_settings.image_height), int(raster_settings.image_width)
         zeros = lambda c: torch.zeros((c, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
-        absgrad = getattr(ctx, "absgrad", False)  # (_RasterizeGaussiansAbs)
+        absgrad = ctx.absgrad
         grad_color = zeros(3) if grad_color is None else grad_color
         grad_depth = zeros(1) if grad_depth is None else grad_depth
         if absgrad:  # an unused median / variance output: NULL, the lean blend backward (bit-identical to zero images)
@@ -713,25 +557,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             grad_viewmatrix,
             None,
             None,
+            grad_means2D_abs,
         )
-        return grads + (grad_means2D_abs,) if absgrad else grads
-
-
-class _RasterizeGaussiansAbs(torch.autograd.Function):
-    """_RasterizeGaussians with one more leaf, means2D_abs [P,3], whose gradient is the absolute screen-space gradient (absgrad,
-    include/dgr_hip.h: dgr_light_backward_absgrad).  Over either binding's forward and backward: the compiled LightNode has no
-    such input."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
-                gt_depth, raster_settings, means2D_abs):
-        ctx.absgrad = True
-        return _RasterizeGaussians.forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                           cov3Ds_precomp, viewmatrix, gt_depth, raster_settings)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        return _RasterizeGaussians.backward(ctx, *grads)
+        return grads
 
 
 def check_means2D_abs(means2D_abs, means3D, map_off, shape=None):
@@ -746,6 +574,20 @@ def check_means2D_abs(means2D_abs, means3D, map_off, shape=None):
 
 
 _EMPTY = torch.Tensor([])  # stands for "None" at the C++ boundary (L/__init__.py:223-232)
+
+
+def _checked_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """The checks of the reference's GaussianRasterizer.forward (L/__init__.py:209-232), shared by both variants' one-view and
+    batch rasterizers; a missing input becomes _EMPTY (the reference builds a fresh `torch.Tensor([])` per missing input and
+    call; one shared empty tensor says the same).  Returns (shs, colors_precomp, scales, rotations, cov3D_precomp)."""
+    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    e = _EMPTY
+    return (e if shs is None else shs, e if colors_precomp is None else colors_precomp, e if scales is None else scales,
+            e if rotations is None else rotations, e if cov3D_precomp is None else cov3D_precomp)
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -788,29 +630,11 @@ class GaussianRasterizer(nn.Module):
         raster_settings = self.raster_settings
         if means2D_abs is not None:
             check_means2D_abs(means2D_abs, means3D, raster_settings.map_off)
-
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-
-        # (the reference builds a fresh `torch.Tensor([])` per missing input and call; one shared empty tensor says the same)
-        if shs is None:
-            shs = _EMPTY
-        if colors_precomp is None:
-            colors_precomp = _EMPTY
-        if scales is None:
-            scales = _EMPTY
-        if rotations is None:
-            rotations = _EMPTY
-        if cov3D_precomp is None:
-            cov3D_precomp = _EMPTY
-
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _checked_inputs(shs, colors_precomp, scales, rotations,
+                                                                                cov3D_precomp)
         if means2D_abs is not None:
-            return _RasterizeGaussiansAbs.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                cov3D_precomp, viewmatrix, gt_depth, raster_settings, means2D_abs)
+            return _RasterizeGaussians.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
+                                             cov3D_precomp, viewmatrix, gt_depth, raster_settings, means2D_abs)
         return rasterize_gaussians(
             means3D,
             means2D,

@@ -129,7 +129,7 @@ class ViewStreams:
         self.streams = [torch.cuda.Stream(device=self.device) for _ in range(max(1, int(n)))]
         self._views = [ViewStreams._View(self, st) for st in self.streams]
         # Lazy status mode: while views are in flight the host may run as many forward passes ahead of the status words as
-        # there are streams (light.py: _LAZY_DEPTH) -- raised by the first next(), put back by join(), so that code outside
+        # there are streams (dgr_amd._binning: _LAZY_DEPTH) -- raised by the first next(), put back by join(), so that code outside
         # the in-flight window sees a binning overflow one or two calls late as documented, not n + 1.
         self._saved_depth = None
         self._i = 0
