@@ -257,18 +257,23 @@ std::atomic<int> g_det_grads{[] { const char* e = getenv("DGR_DETERMINISTIC_GRAD
 //   2 (default) = decided per FRAME on the device by the binning kernel, from the frame's own run statistics (segment_binning.hip:
 //       bin_tiles_kernel; big splats -> 0) and recorded in the frame's state, where forward and backward read it.
 // Initial value from DGR_FWD_HALVES = 0 / 1 (the switch's name when it was per process; A/B runs).
+// dgr_set_option("pose_grad", v): 0 (default) = the reference's pose-gradient terms; 1 = the complete pose gradient, the
+// view-matrix counterpart of dL_dmeans3D (csrc/preprocess.hip: bwd_view_terms<true>; include/dgr_hip.h).  A light map_off
+// backward then runs the mapping blend backward (its per-Gaussian outputs are dropped).  Initial value from DGR_POSE_GRAD = 0 / 1.
+std::atomic<int> g_pose_grad{[] { const char* e = getenv("DGR_POSE_GRAD"); return (e && e[0] == '1' && e[1] == 0) ? 1 : 0; }()};
 std::atomic<int> g_lane_lists{[] { const char* e = getenv("DGR_FWD_HALVES"); return (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) ? e[0] - '0' : 2; }()};
 
-// ---- per-THREAD overrides of the three options that change what a call computes (dgr_set_thread_option, round 9).  The options
+// ---- per-THREAD overrides of the four options that change what a call computes (dgr_set_thread_option, round 9).  The options
 // above are process-wide defaults; a tracker thread and a mapper thread of one process -- or a test beside a training loop -- hold
 // their own values here (-1 = inherit).  Every entry point reads its options ONCE, when it is called, and hands them to its
 // launches as template choices / kernel arguments: launches already queued (on any stream) are not affected by a later change.
 // A backward must run with its forward's alpha mode: the autograd bindings snapshot dgr_thread_options_effective() in the
 // forward and swap it in around the backward (which the autograd engine may run on another thread).
-thread_local int t_alpha_mode = -1, t_tight_cull = -1, t_det_grads = -1;
+thread_local int t_alpha_mode = -1, t_tight_cull = -1, t_det_grads = -1, t_pose_grad = -1;
 inline int opt_alpha_mode() { return t_alpha_mode >= 0 ? t_alpha_mode : g_alpha_mode.load(std::memory_order_relaxed); }
 inline int opt_tight_cull() { return t_tight_cull >= 0 ? t_tight_cull : g_tight_cull.load(std::memory_order_relaxed); }
 inline int opt_det_grads() { return t_det_grads >= 0 ? t_det_grads : g_det_grads.load(std::memory_order_relaxed); }
+inline int opt_pose_grad() { return t_pose_grad >= 0 ? t_pose_grad : g_pose_grad.load(std::memory_order_relaxed); }
 // dgr_set_option("lds_count", v): how the forward bins tile instances.
 //   1 (default) = the two-level segment binning (csrc/segment_binning.hip) whenever the frame's segment tables fit LDS;
 //   0 = returning global atomics on per-tile counters (csrc/binning.hip; inside preprocess_fwd when presized), which also
@@ -868,6 +873,7 @@ static int light_backward_impl(void* stream, int P, int D, int M, int R, const f
         return DGR_OK;
     }
     const bool det = opt_det_grads() != 0 && !(track_off && map_off);
+    const bool complete = opt_pose_grad() != 0 && !track_off;  // (track_off: no pose gradient, nothing to complete)
     if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
     if (det && R <= 0) { g_last_error = "deterministic_grads: the backward needs R >= num_rendered (it sizes the instance-major row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
     if (scratch_bytes < dgr_light_backward_scratch_bytes_r(P, width, height, R) || !scratch) {
@@ -890,7 +896,8 @@ static int light_backward_impl(void* stream, int P, int D, int M, int R, const f
     r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = (const uint32_t*)binning_buffer; r.rec = geom.rec; r.bg = background;
     r.gt_depth = gt_depth; r.alphas = alphas; r.n_contrib = img.n_contrib; r.dL_dpix = dL_dpix;
     r.dL_dpix_depth = dL_dpix_depth; r.dL_dpix_median = dL_dpix_median_depth; r.dL_dpix_var = dL_dpix_depth_var;
-    r.means3D = means3D; r.view = viewmatrix; r.acc = sc.acc; r.track_off = track_off; r.map_off = map_off;
+    // (complete pose gradient: the tracking blend's three sums are not enough -- the mapping blend backward forms all of them)
+    r.means3D = means3D; r.view = viewmatrix; r.acc = sc.acc; r.track_off = track_off; r.map_off = complete ? 0 : map_off;
     DetScratch ds{nullptr, nullptr, nullptr, 0};
     if (det) {
         // (the Gaussians' first-instance offsets go into the geometry state's goff array, which only the global-counter binning
@@ -917,7 +924,7 @@ static int light_backward_impl(void* stream, int P, int D, int M, int R, const f
     b.dL_dmean2D = dL_dmean2D; b.dL_dconic = dL_dconic; b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor;
     b.dL_ddepth = dL_ddepth; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
     b.dL_dscale = dL_dscale; b.dL_drot = dL_drot; b.pose_part = sc.pose_part; b.ticket = sc.ticket; b.dL_dview = dL_dview;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st)); }
+    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st, complete)); }
     if (debug && !dgr_stream_is_capturing(stream)) HIP_TRY(hipStreamSynchronize(st));  // (CHECK_CUDA(..., debug); a capturing stream cannot be waited for -- and the attempt would invalidate the capture)
     return DGR_OK;
 }
@@ -1117,7 +1124,7 @@ static int full_backward_impl(void* stream, int P, int D, int M, int R, const fl
     b.dL_dmean2D = dL_dmean2D; b.dL_dconic = dL_dconic; b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor;
     b.dL_ddepth = dL_dgau_depth; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
     b.dL_dscale = dL_dscale; b.dL_drot = dL_drot; b.pose_part = sc.pose_part; b.ticket = sc.ticket; b.dL_dview = dL_dview;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st)); }
+    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st, opt_pose_grad() != 0)); }
     return DGR_OK;
 }
 int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
@@ -1207,6 +1214,7 @@ static int light_backward_batch_impl(void* stream, int n_views, const dgr_light_
     (void)colors_precomp;
     hipStream_t st = (hipStream_t)stream;
     const bool det = opt_det_grads() != 0 && !(track_off && map_off);  // (round 9: per view the scheme of the one-view backward)
+    const bool complete = opt_pose_grad() != 0 && !track_off;           // (as the one-view backward: the mapping blend under map_off)
     if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
     if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
     bool any_abs = false;  // (absgrad: a NULL array or NULL entries -- those views as without it)
@@ -1258,7 +1266,7 @@ static int light_backward_batch_impl(void* stream, int n_views, const dgr_light_
         r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = (const uint32_t*)w.binning_buffer; r.rec = geom.rec; r.bg = background;
         r.gt_depth = w.gt_depth; r.alphas = w.alphas; r.n_contrib = img.n_contrib; r.dL_dpix = w.dL_dpix;
         r.dL_dpix_depth = w.dL_dpix_depth; r.dL_dpix_median = w.dL_dpix_median_depth; r.dL_dpix_var = w.dL_dpix_depth_var;
-        r.means3D = means3D; r.view = w.viewmatrix; r.acc = sc.acc; r.track_off = track_off; r.map_off = map_off;
+        r.means3D = means3D; r.view = w.viewmatrix; r.acc = sc.acc; r.track_off = track_off; r.map_off = complete ? 0 : map_off;
         DetScratch ds{nullptr, nullptr, nullptr, 0};
         if (det) {
             ds = carve_det_scratch(w.scratch, P, w.num_rendered);
@@ -1287,7 +1295,7 @@ static int light_backward_batch_impl(void* stream, int n_views, const dgr_light_
     b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
     b.dL_dscale = dL_dscale; b.dL_drot = dL_drot;
     bb.V = n_views;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st)); }
+    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st, complete)); }
     return DGR_OK;
 }
 int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
@@ -1400,7 +1408,7 @@ static int full_backward_batch_impl(void* stream, int n_views, const dgr_full_vi
     b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
     b.dL_dscale = dL_dscale; b.dL_drot = dL_drot;
     bb.V = n_views;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st)); }
+    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st, opt_pose_grad() != 0)); }
     return DGR_OK;
 }
 int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
@@ -1733,6 +1741,11 @@ int dgr_set_option(const char* name, int value) {
     if (n == "lds_count") { g_lds_count.store(value < 0 ? 0 : value > 2 ? 2 : value); return DGR_OK; }
     if (n == "lane_lists") { g_lane_lists.store(value < 0 ? 0 : value > 2 ? 2 : value); return DGR_OK; }
     if (n == "deterministic_grads") { g_det_grads.store(value ? 1 : 0); return DGR_OK; }
+    if (n == "pose_grad") {
+        if (value < 0 || value > 1) { g_last_error = "pose_grad: 0 (the reference's pose terms) or 1 (complete)"; return DGR_ERR_BAD_ARGUMENT; }
+        g_pose_grad.store(value);
+        return DGR_OK;
+    }
     if (n == "profile_every") { g_profile_every.store(value > 0 ? value : 1); return DGR_OK; }
     if (n == "batch_order") { g_batch_order.store(value ? 1 : 0); return DGR_OK; }
     if (n == "batch_streams") { g_batch_streams.store(value < 1 ? 1 : value > DGR_BATCH_MAX_STREAMS ? DGR_BATCH_MAX_STREAMS : value); return DGR_OK; }
@@ -1749,6 +1762,7 @@ int dgr_get_option(const char* name) {
     if (n == "lds_count") return g_lds_count.load();
     if (n == "lane_lists") return g_lane_lists.load();
     if (n == "deterministic_grads") return g_det_grads.load();
+    if (n == "pose_grad") return g_pose_grad.load();
     if (n == "profile_every") return g_profile_every.load();
     if (n == "batch_streams") return g_batch_streams.load();
     if (n == "batch_order") return g_batch_order.load();
@@ -1765,6 +1779,11 @@ int dgr_set_thread_option(const char* name, int value) {
     if (n == "fast_alpha") { t_alpha_mode = value < 0 ? -1 : (value ? 1 : 0); return DGR_OK; }
     if (n == "tight_cull") { t_tight_cull = value < 0 ? -1 : (value ? 1 : 0); return DGR_OK; }
     if (n == "deterministic_grads") { t_det_grads = value < 0 ? -1 : (value ? 1 : 0); return DGR_OK; }
+    if (n == "pose_grad") {
+        if (value > 1) { g_last_error = "pose_grad: 0, 1 (or < 0: the process-wide option)"; return DGR_ERR_BAD_ARGUMENT; }
+        t_pose_grad = value < 0 ? -1 : value;
+        return DGR_OK;
+    }
     g_last_error = "not a per-thread option: " + n;
     return DGR_ERR_BAD_ARGUMENT;
 }
@@ -1774,17 +1793,21 @@ int dgr_get_thread_option(const char* name) {
     if (n == "fast_alpha") return opt_alpha_mode() == 1 ? 1 : 0;
     if (n == "tight_cull") return opt_tight_cull();
     if (n == "deterministic_grads") return opt_det_grads();
+    if (n == "pose_grad") return opt_pose_grad();
     return DGR_ERR_BAD_ARGUMENT;
 }
-// the three as one word, each field = value + 1 (0 = "inherit", in an override word): bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
-// deterministic_grads
-int dgr_thread_options_effective(void) { return (opt_alpha_mode() + 1) | ((opt_tight_cull() + 1) << 4) | ((opt_det_grads() + 1) << 8); }
+// the four as one word, each field = value + 1 (0 = "inherit", in an override word): bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
+// deterministic_grads, 12-15 pose_grad
+int dgr_thread_options_effective(void) {
+    return (opt_alpha_mode() + 1) | ((opt_tight_cull() + 1) << 4) | ((opt_det_grads() + 1) << 8) | ((opt_pose_grad() + 1) << 12);
+}
 int dgr_thread_options_swap(int word) {
-    const int prev = (t_alpha_mode + 1) | ((t_tight_cull + 1) << 4) | ((t_det_grads + 1) << 8);
+    const int prev = (t_alpha_mode + 1) | ((t_tight_cull + 1) << 4) | ((t_det_grads + 1) << 8) | ((t_pose_grad + 1) << 12);
     if (word >= 0) {
         t_alpha_mode = (word & 15) - 1;
         t_tight_cull = ((word >> 4) & 15) - 1;
         t_det_grads = ((word >> 8) & 15) - 1;
+        t_pose_grad = ((word >> 12) & 15) - 1;
     }
     return prev;
 }

@@ -251,9 +251,10 @@ struct RenderBwdFullArgs {
 
 // ---- launchers (each enqueues on `stream` and returns the hipError_t of the launch) ----
 hipError_t launch_preprocess_fwd(const PreprocessFwdArgs& a, hipStream_t stream);
-hipError_t launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream);
+// complete_pose: dgr_set_option("pose_grad", 1) -- the instance with the complete pose gradient (preprocess.hip: bwd_view_terms)
+hipError_t launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream, bool complete_pose = false);
 hipError_t launch_preprocess_fwd_batch(const PreprocessFwdBatchArgs& b, hipStream_t stream);
-hipError_t launch_preprocess_bwd_batch(const PreprocessBwdBatchArgs& b, hipStream_t stream);
+hipError_t launch_preprocess_bwd_batch(const PreprocessBwdBatchArgs& b, hipStream_t stream, bool complete_pose = false);
 // zero-fill of a 16-byte aligned buffer whose size is a multiple of 16 (a kernel rather than hipMemsetAsync: memset nodes of a
 // captured hipGraph were seen to re-execute with corrupted parameters on this ROCm)
 hipError_t launch_zero_fill(void* dst, size_t bytes, hipStream_t stream);

@@ -611,6 +611,11 @@ __global__ void __launch_bounds__(256) mark_visible_kernel(int P, const float* _
 // Everything that depends on the camera: the median-depth term, computeCov2DCUDA, preprocessCUDA, the SH backward up to
 // the scalars coef[k] and the masked colour gradient (dL_dsh[k] = coef[k] * dRGB), the pose-gradient terms.  `acc` = the
 // blend backward's sums for this Gaussian in this view (zeros when it was not visible).
+// COMPLETE (dgr_set_option("pose_grad", 1)): the pose gradient is the view-matrix counterpart of dL_dmeans3D -- the reference's
+// ndc terms plus the z path (the depth sums dL_dmeans3D uses), the cov2D path (A = Ju Rcam: dL/dRcam = Ju^T dL/dA and t_cam through
+// Ju) and the SH path (campos = -Rcam^T t) -- while every per-Gaussian output keeps its bits.
+// Under map_off the covariance and SH blocks still run (the pose needs dL/da..c and dL/dcampos) but add nothing to the outputs.
+template <bool COMPLETE = false>
 __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const bool full, float3 m, const float (&c3)[6],
                                                const float (&acc)[16], bool vis, uint8_t cl_in, float4 shd0, float4 shd1,
                                                float4 shd2, float3& dmean_out, float (&dcov)[6], float (&coef)[16],
@@ -620,15 +625,23 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
     if (!full) {
         // light: the blend kernel's median-depth term (L/cuda_rasterizer/backward.cu:654-664), whose pixel sum of
         // dL/dmedian arrives in acc[10]; the per-Gaussian factors are applied here
+        // (COMPLETE under map_off: the mapping blend ran and acc[10] holds a sum, but the output stays what the tracking
+        //  blend's zero row gives)
         const float* v = a.view;
         const float mul3 = v[2] * m.x + v[6] * m.y + v[10] * m.z + v[14];
-        dmean = make_float3((v[2] - v[3] * mul3) * acc[10], (v[6] - v[7] * mul3) * acc[10], (v[10] - v[11] * mul3) * acc[10]);
+        const float med = (COMPLETE && a.map_off) ? 0.0f : acc[10];
+        dmean = make_float3((v[2] - v[3] * mul3) * med, (v[6] - v[7] * mul3) * med, (v[10] - v[11] * mul3) * med);
     }
     float3 s_cam = make_float3(0.f, 0.f, 0.f);  // full: sum_ch dL_dcolor[ch] * d(rgb[ch])/d(campos.{x,y,z})
     const bool do_map = vis && !a.map_off;
+    const bool do_terms = COMPLETE ? vis : do_map;  // the blocks below run (COMPLETE: for the pose too)
+    float px[12];  // COMPLETE: the cov2D and SH paths' pose terms, [3 k + j] = dL/dv[4 k + j]
+    float3 g_cam = make_float3(0.f, 0.f, 0.f);  // COMPLETE: dL/dcampos of the masked colour gradient
+#pragma unroll
+    for (int i = 0; i < 12; i++) px[i] = 0.0f;
 #pragma unroll
     for (int i = 0; i < 6; i++) dcov[i] = 0.0f;
-    if (do_map) {
+    if (do_terms) {
         // ---------------- computeCov2DCUDA (L/cuda_rasterizer/backward.cu:144-276)
         const float3 dconic = make_float3(acc[6], acc[7], acc[8]);
         Cov2D c;
@@ -646,12 +659,14 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
             dL_da = denom2inv * (-cc * cc * dconic.x + 2 * cb * cc * dconic.y + (denom - ca * cc) * dconic.z);
             dL_dc = denom2inv * (-ca * ca * dconic.z + 2 * ca * cb * dconic.y + (denom - ca * cc) * dconic.x);
             dL_db = denom2inv * 2 * (cb * cc * dconic.x - (denom + 2 * cb * cb) * dconic.y + ca * cb * dconic.z);
+            if (!COMPLETE || do_map) {  // (COMPLETE under map_off: no dL_dcov3D)
             dcov[0] = (T.m[0][0] * T.m[0][0] * dL_da + T.m[0][0] * T.m[1][0] * dL_db + T.m[1][0] * T.m[1][0] * dL_dc);
             dcov[3] = (T.m[0][1] * T.m[0][1] * dL_da + T.m[0][1] * T.m[1][1] * dL_db + T.m[1][1] * T.m[1][1] * dL_dc);
             dcov[5] = (T.m[0][2] * T.m[0][2] * dL_da + T.m[0][2] * T.m[1][2] * dL_db + T.m[1][2] * T.m[1][2] * dL_dc);
             dcov[1] = 2 * T.m[0][0] * T.m[0][1] * dL_da + (T.m[0][0] * T.m[1][1] + T.m[0][1] * T.m[1][0]) * dL_db + 2 * T.m[1][0] * T.m[1][1] * dL_dc;
             dcov[2] = 2 * T.m[0][0] * T.m[0][2] * dL_da + (T.m[0][0] * T.m[1][2] + T.m[0][2] * T.m[1][0]) * dL_db + 2 * T.m[1][0] * T.m[1][2] * dL_dc;
             dcov[4] = 2 * T.m[0][2] * T.m[0][1] * dL_da + (T.m[0][1] * T.m[1][2] + T.m[0][2] * T.m[1][1]) * dL_db + 2 * T.m[1][1] * T.m[1][2] * dL_dc;
+            }
         }
         const float dL_dT00 = 2 * (T.m[0][0] * Vrk.m[0][0] + T.m[0][1] * Vrk.m[0][1] + T.m[0][2] * Vrk.m[0][2]) * dL_da +
                               (T.m[1][0] * Vrk.m[0][0] + T.m[1][1] * Vrk.m[0][1] + T.m[1][2] * Vrk.m[0][2]) * dL_db;
@@ -676,9 +691,30 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
         const float dL_dty = y_grad_mul * -h_y * tz2 * dL_dJ12;
         const float dL_dtz = -h_x * tz2 * dL_dJ00 - h_y * tz2 * dL_dJ11 + (2 * h_x * t.x) * tz3 * dL_dJ02 + (2 * h_y * t.y) * tz3 * dL_dJ12;
         const float* v = a.view;
-        dmean.x += v[0] * dL_dtx + v[1] * dL_dty + v[2] * dL_dtz;
-        dmean.y += v[4] * dL_dtx + v[5] * dL_dty + v[6] * dL_dtz;
-        dmean.z += v[8] * dL_dtx + v[9] * dL_dty + v[10] * dL_dtz;
+        if (COMPLETE) {
+            // dL/dA = 2 G A Sigma, G = [[dL_da, dL_db/2], [dL_db/2, dL_dc]]: dL_dT{i}{k} above (T.m[i][k] = A[i][k]).
+            // A = Ju Rcam: dL/dRcam[j][k] = sum_i Ju[i][j] dL/dA[i][k]; t_cam = Rcam m + t reaches Ju: mm_k dL/dt_cam,j.
+            const float J00 = h_x * tz, J02 = -(h_x * t.x) * tz2, J11 = h_y * tz, J12 = -(h_y * t.y) * tz2;
+            const float dA0[3] = {dL_dT00, dL_dT01, dL_dT02}, dA1[3] = {dL_dT10, dL_dT11, dL_dT12};
+            const float mm[4] = {m.x, m.y, m.z, 1.0f};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                px[3 * k + 0] += mm[k] * dL_dtx;
+                px[3 * k + 1] += mm[k] * dL_dty;
+                px[3 * k + 2] += mm[k] * dL_dtz;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                px[3 * k + 0] += J00 * dA0[k];
+                px[3 * k + 1] += J11 * dA1[k];
+                px[3 * k + 2] += J02 * dA0[k] + J12 * dA1[k];
+            }
+        }
+        if (!COMPLETE || do_map) {
+            dmean.x += v[0] * dL_dtx + v[1] * dL_dty + v[2] * dL_dtz;
+            dmean.y += v[4] * dL_dtx + v[5] * dL_dty + v[6] * dL_dtz;
+            dmean.z += v[8] * dL_dtx + v[9] * dL_dty + v[10] * dL_dtz;
+        }
         if (full) {  // depth -> mean term inside computeCov2DCUDA (F/cuda_rasterizer/backward.cu:385-386)
             const float mul3f = v[2] * m.x + v[6] * m.y + v[10] * m.z + v[14];
             dmean.x = dmean.x + acc[3] * (v[2] - v[3] * mul3f);
@@ -697,8 +733,8 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
         d1.x = (pj[0] * m_w - pj[3] * mul1) * g2x + (pj[1] * m_w - pj[3] * mul2) * g2y;
         d1.y = (pj[4] * m_w - pj[7] * mul1) * g2x + (pj[5] * m_w - pj[7] * mul2) * g2y;
         d1.z = (pj[8] * m_w - pj[11] * mul1) * g2x + (pj[9] * m_w - pj[11] * mul2) * g2y;
-        dmean.x += d1.x; dmean.y += d1.y; dmean.z += d1.z;
-        if (!full) {  // light: depth -> mean term inside preprocessCUDA (L/cuda_rasterizer/backward.cu:396-407)
+        if (!COMPLETE || do_map) { dmean.x += d1.x; dmean.y += d1.y; dmean.z += d1.z; }
+        if (!full && (!COMPLETE || do_map)) {  // light: depth -> mean term inside preprocessCUDA (L/cuda_rasterizer/backward.cu:396-407)
             const float mul3 = v[2] * m.x + v[6] * m.y + v[10] * m.z + v[14];
             float3 d2;
             d2.x = (v[2] - v[3] * mul3) * acc[3];
@@ -711,7 +747,9 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
 #pragma unroll
     for (int k = 0; k < 16; k++) coef[k] = 0.0f;
     dRGB = make_float3(0.f, 0.f, 0.f);
-    if (a.dL_dsh && a.M > 0 && do_map && a.shs) {
+    // (COMPLETE: also without a dL_dsh output -- a tracking step -- for dL/dcampos; the outputs below only where the default runs)
+    const bool sh_out = a.dL_dsh && do_map;
+    if ((COMPLETE ? true : a.dL_dsh != nullptr) && a.M > 0 && do_terms && a.shs) {
         const float3 cam = make_float3(a.campos[0], a.campos[1], a.campos[2]);
         const float3 dir_orig = m - cam;
         const float len = sqrtf(dot3(dir_orig, dir_orig));
@@ -768,9 +806,31 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
             const float3 vv = dir_orig, dv = dL_ddir;
             const float sum2 = vv.x * vv.x + vv.y * vv.y + vv.z * vv.z;
             const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-            dmean.x += ((+sum2 - vv.x * vv.x) * dv.x - vv.y * vv.x * dv.y - vv.z * vv.x * dv.z) * invsum32;
-            dmean.y += (-vv.x * vv.y * dv.x + (sum2 - vv.y * vv.y) * dv.y - vv.z * vv.y * dv.z) * invsum32;
-            dmean.z += (-vv.x * vv.z * dv.x - vv.y * vv.z * dv.y + (sum2 - vv.z * vv.z) * dv.z) * invsum32;
+            if (!COMPLETE || sh_out) {
+                dmean.x += ((+sum2 - vv.x * vv.x) * dv.x - vv.y * vv.x * dv.y - vv.z * vv.x * dv.z) * invsum32;
+                dmean.y += (-vv.x * vv.y * dv.x + (sum2 - vv.y * vv.y) * dv.y - vv.z * vv.y * dv.z) * invsum32;
+                dmean.z += (-vv.x * vv.z * dv.x - vv.y * vv.z * dv.y + (sum2 - vv.z * vv.z) * dv.z) * invsum32;
+            }
+            if (COMPLETE)  // dir = m - campos: dL/dcampos is minus the term above
+                g_cam = make_float3(-(((+sum2 - vv.x * vv.x) * dv.x - vv.y * vv.x * dv.y - vv.z * vv.x * dv.z) * invsum32),
+                                    -((-vv.x * vv.y * dv.x + (sum2 - vv.y * vv.y) * dv.y - vv.z * vv.y * dv.z) * invsum32),
+                                    -((-vv.x * vv.z * dv.x - vv.y * vv.z * dv.y + (sum2 - vv.z * vv.z) * dv.z) * invsum32));
+        }
+        if (COMPLETE && !sh_out) {  // (no dL_dsh row for this view: as the default leaves it)
+            dRGB = make_float3(0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < 16; k++) coef[k] = 0.0f;
+        }
+    }
+    if (COMPLETE) {
+        // campos = -Rcam^T t: dL/dRcam[j][k] = -t_j g_k, dL/dt_j = -sum_k Rcam[j][k] g_k  (Rcam[j][k] = v[4 k + j], t_j = v[12 + j])
+        const float* v = a.view;
+        const float g[3] = {g_cam.x, g_cam.y, g_cam.z};
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) px[3 * k + j] += -v[12 + j] * g[k];
+            px[9 + j] += -(v[j] * g[0] + v[4 + j] * g[1] + v[8 + j] * g[2]);
         }
     }
     // ---------------- pose gradient: sum over Gaussians of Jacobian x (sum over pixels)
@@ -780,7 +840,18 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
         const float4 m_hom = xform4x4(m, a.proj);
         const float m_w = 1.0f / (m_hom.w + 0.0000001f);
         const float mm[4] = {m.x, m.y, m.z, 1.0f};
-        if (!full) {
+        if (COMPLETE) {
+            // the ndc terms from the mean2D sums dL_dmeans3D uses, the z path from its depth sums (light: depth and variance in
+            // acc[3], median in acc[10]; full: the depth -> mean term's acc[3]), then the cov2D and SH paths
+            const float A = acc[4], B = acc[5], Dz = full ? acc[3] : acc[3] + acc[10];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                pose[3 * k + 0] = (m_w * a.perspec[0] * mm[k]) * A + px[3 * k + 0];
+                pose[3 * k + 1] = (m_w * a.perspec[5] * mm[k]) * B + px[3 * k + 1];
+                pose[3 * k + 2] = (m_hom.x * (-m_w * m_w) * mm[k]) * A + (m_hom.y * (-m_w * m_w) * mm[k]) * B + mm[k] * Dz +
+                                  px[3 * k + 2];
+            }
+        } else if (!full) {
             const float A = acc[4], B = acc[5], Dd = acc[13];
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -986,6 +1057,8 @@ __device__ __forceinline__ void pose_block_reduce_det(const float (&pose)[12], d
 #ifndef DGR_PPB_WAVES
 #define DGR_PPB_WAVES 4
 #endif
+// COMPLETE: the complete pose gradient (bwd_view_terms); the default instance is the reference's terms, unchanged.
+template <bool COMPLETE>
 __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(PreprocessBwdArgs a) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     float pose[12];
@@ -1004,9 +1077,11 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
         // A tracking step (map_off: the pose gradient only) needs the three sums, the mean and the radius: the covariance, the
         // scale / rotation, the clamp bits and the SH direction derivatives -- 77 of the 157 bytes a Gaussian costs this kernel --
         // feed only the per-Gaussian gradients.  The test is kernel-uniform and known at launch: no load waits for another.
+        // (COMPLETE: the pose's cov2D and SH paths need the covariance, the clamp bits and the SH direction derivatives too)
         const bool need_map = !a.map_off;
+        const bool need_terms = COMPLETE || need_map;
         float c3[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (need_map) {
+        if (need_terms) {
             if (a.cov3D_precomp) {
                 const float* c3p = a.cov3D_precomp + 6 * (size_t)idx;
 #pragma unroll
@@ -1023,7 +1098,7 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
         }
         uint8_t cl_in = 0;
         float4 shd0 = make_float4(0.f, 0.f, 0.f, 0.f), shd1 = shd0, shd2 = shd0;
-        if (need_map) {
+        if (need_terms) {
             cl_in = a.geom.clamped[idx];
             shd0 = a.geom.shd[idx]; shd1 = a.geom.shd[(size_t)a.P + idx]; shd2 = a.geom.shd[2 * (size_t)a.P + idx];
         }
@@ -1046,22 +1121,24 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
             a.dL_dmean2D[3 * (size_t)idx + 1] = a.map_off ? 0.0f : acc[5];
             a.dL_dmean2D[3 * (size_t)idx + 2] = 0.0f;
         }
-        if (a.dL_dopacity) a.dL_dopacity[idx] = acc[9];
+        // (COMPLETE under map_off: the mapping blend filled these sums, the tracking blend leaves them zero -- so do the outputs)
+        const bool zero_copies = COMPLETE && a.map_off;
+        if (a.dL_dopacity) a.dL_dopacity[idx] = zero_copies ? 0.0f : acc[9];
         if (a.dL_dcolor) {
-            a.dL_dcolor[3 * (size_t)idx + 0] = acc[0];
-            a.dL_dcolor[3 * (size_t)idx + 1] = acc[1];
-            a.dL_dcolor[3 * (size_t)idx + 2] = acc[2];
+            a.dL_dcolor[3 * (size_t)idx + 0] = zero_copies ? 0.0f : acc[0];
+            a.dL_dcolor[3 * (size_t)idx + 1] = zero_copies ? 0.0f : acc[1];
+            a.dL_dcolor[3 * (size_t)idx + 2] = zero_copies ? 0.0f : acc[2];
         }
-        if (a.dL_ddepth) a.dL_ddepth[idx] = acc[3];
+        if (a.dL_ddepth) a.dL_ddepth[idx] = zero_copies ? 0.0f : acc[3];
         if (a.dL_dconic) {
             float4* o = reinterpret_cast<float4*>(a.dL_dconic) + idx;
-            *o = make_float4(acc[6], acc[7], 0.0f, acc[8]);
+            *o = zero_copies ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(acc[6], acc[7], 0.0f, acc[8]);
         }
 
         float3 dmean;
         float dcov[6], coef[16];
         float3 dRGB;
-        bwd_view_terms(a, a.full_variant != 0, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
+        bwd_view_terms<COMPLETE>(a, a.full_variant != 0, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
         float3 dscale = make_float3(0, 0, 0);
         float4 drot = make_float4(0, 0, 0, 0);
         const bool do_map = vis && !a.map_off;
@@ -1164,8 +1241,9 @@ __device__ __forceinline__ PreprocessBwdArgs batch_view_args(const PreprocessBwd
     a.acc = const_cast<float*>(p.acc); a.dL_dmean2D = p.dL_dmean2D; a.pose_part = p.pose_part; a.ticket = p.ticket; a.dL_dview = p.dL_dview;
     return a;
 }
-template <bool FULL>
-__global__ void __launch_bounds__(256, DGR_BWD_BATCH_WAVES) preprocess_bwd_batch_kernel(PreprocessBwdBatchArgs b) {
+// (COMPLETE: held to the default instances' 3 waves per SIMD -- left to itself the light one takes 178 VGPRs, 2 waves)
+template <bool FULL, bool COMPLETE = false>
+__global__ void __launch_bounds__(256, COMPLETE ? 3 : DGR_BWD_BATCH_WAVES) preprocess_bwd_batch_kernel(PreprocessBwdBatchArgs b) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int P = b.base.P, V = b.V;
     const bool in = idx < P;
@@ -1226,10 +1304,12 @@ __global__ void __launch_bounds__(256, DGR_BWD_BATCH_WAVES) preprocess_bwd_batch
             }
             float3 dmean, dRGB;
             float dcov[6], coef[16];
-            bwd_view_terms(a, FULL, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
+            bwd_view_terms<COMPLETE>(a, FULL, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
             any_map |= vis && !a.map_off;
-            dop_s += acc[9];
-            dcol_s.x += acc[0]; dcol_s.y += acc[1]; dcol_s.z += acc[2];
+            if (!(COMPLETE && a.map_off)) {  // (COMPLETE under map_off: the mapping blend's sums reach no output, as one view)
+                dop_s += acc[9];
+                dcol_s.x += acc[0]; dcol_s.y += acc[1]; dcol_s.z += acc[2];
+            }
             dmean_s.x += dmean.x; dmean_s.y += dmean.y; dmean_s.z += dmean.z;
 #pragma unroll
             for (int i = 0; i < 6; i++) dcov_s[i] += dcov[i];
@@ -1418,16 +1498,23 @@ hipError_t launch_preprocess_fwd_batch(const PreprocessFwdBatchArgs& b, hipStrea
     launch(preprocess_fwd_batch_kernel, dim3((b.base.P + 255) / 256), dim3(256), stream, b);
     return hipGetLastError();
 }
-hipError_t launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream) {
+hipError_t launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream, bool complete_pose) {
     const int blocks = (a.P + 255) / 256;
     if (blocks <= 0) return hipSuccess;
-    launch(preprocess_bwd_kernel, dim3(blocks), dim3(256), stream, a);
+    if (complete_pose) launch(preprocess_bwd_kernel<true>, dim3(blocks), dim3(256), stream, a);
+    else launch(preprocess_bwd_kernel<false>, dim3(blocks), dim3(256), stream, a);
     return hipGetLastError();
 }
-hipError_t launch_preprocess_bwd_batch(const PreprocessBwdBatchArgs& b, hipStream_t stream) {
+hipError_t launch_preprocess_bwd_batch(const PreprocessBwdBatchArgs& b, hipStream_t stream, bool complete_pose) {
     if (b.base.P <= 0 || b.V <= 0) return hipSuccess;
-    if (b.base.full_variant) launch(preprocess_bwd_batch_kernel<true>, dim3((b.base.P + 255) / 256), dim3(256), stream, b);
-    else launch(preprocess_bwd_batch_kernel<false>, dim3((b.base.P + 255) / 256), dim3(256), stream, b);
+    const dim3 grid((b.base.P + 255) / 256);
+    if (b.base.full_variant) {
+        if (complete_pose) launch(preprocess_bwd_batch_kernel<true, true>, grid, dim3(256), stream, b);
+        else launch(preprocess_bwd_batch_kernel<true>, grid, dim3(256), stream, b);
+    } else {
+        if (complete_pose) launch(preprocess_bwd_batch_kernel<false, true>, grid, dim3(256), stream, b);
+        else launch(preprocess_bwd_batch_kernel<false>, grid, dim3(256), stream, b);
+    }
     return hipGetLastError();
 }
 hipError_t launch_mark_visible(int P, const float* means, const float* view, uint8_t* present, hipStream_t stream) {

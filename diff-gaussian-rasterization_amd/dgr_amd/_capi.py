@@ -213,7 +213,7 @@ class thread_options:
     """`with thread_options(alpha_mode=1, tight_cull=1): ...` -- the calling THREAD's rasterizer calls inside the block use these
     values of the per-call options (include/dgr_hip.h: dgr_set_thread_option) whatever the process-wide ones are; other threads
     are not affected, and a backward runs under its forward's options wherever autograd runs it.  Names: alpha_mode (fast_alpha),
-    tight_cull, deterministic_grads."""
+    tight_cull, deterministic_grads, pose_grad (1: the complete pose gradient, include/dgr_hip.h)."""
 
     def __init__(self, **options):
         self.options = options

@@ -116,6 +116,13 @@ def _early_status(lib):
     return list(buf)
 
 
+def set_complete_pose_gradient(on=True):
+    """Opt in to the complete pose gradient (include/dgr_hip.h: dgr_set_option "pose_grad"): dL_dview becomes the view-matrix
+    counterpart of dL_dmeans3D -- 2D covariance, SH colour (through campos = -Rcam^T t) and every depth term included --
+    instead of the reference's mean2D + depth terms.  Process-wide; per thread: `_capi.thread_options(pose_grad=1)`."""
+    _capi.set_option("pose_grad", 1 if on else 0)
+
+
 def set_tight_culling(on=True):
     """Opt in to alpha-aware tile rectangles (include/dgr_hip.h: dgr_set_option "tight_cull"): same images and gradients,
     ~40 % fewer tile instances; `num_rendered` and the opaque state buffers are then not the reference's.  Process-wide."""

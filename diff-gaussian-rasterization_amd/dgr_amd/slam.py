@@ -13,6 +13,7 @@ Matrix convention (cuda_rasterizer/auxiliary.h:58-77 reads 16 floats column-majo
 `campos` are recomputed from the same pose but enter as constants, exactly as in the reference (its backward adds their
 dependence inside the kernels: L/cuda_rasterizer/backward.cu:633-651, 683-751).
 """
+import contextlib as _contextlib
 from collections.abc import Mapping as _Mapping
 
 import torch
@@ -245,7 +246,8 @@ _ZERO_POINTS = {}  # (device, P) -> a [P, 3] zero tensor for calls whose screen-
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, viewmatrix=None, fov=None,
-           HW=None, gt_depth=None, track_off=False, map_off=False, variant="light", pose_tensors=None, absgrad=False):
+           HW=None, gt_depth=None, track_off=False, map_off=False, variant="light", pose_tensors=None, absgrad=False,
+           complete_pose=False):
     """CG-SLAM's `render()` (reference README.md:33,71).
 
     `pc`: anything with the 3DGS GaussianModel accessors `get_xyz`, `get_opacity`, `get_scaling`, `get_rotation`,
@@ -259,7 +261,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     num_related_pixels; full: render, depth, opacity_map) plus the 3DGS bookkeeping entries viewspace_points,
     visibility_filter, radii.  `absgrad=True` (AbsGS densification, a mapping render) adds `viewspace_points_abs`, a zero leaf
     shaped like `viewspace_points` whose `.grad` receives the absolute screen-space gradient (GaussianRasterizer.forward's
-    `means2D_abs`): feed it to `optim.add_densification_stats` in place of `viewspace_points.grad`."""
+    `means2D_abs`): feed it to `optim.add_densification_stats` in place of `viewspace_points.grad`.
+    `complete_pose=True`: the backward returns the complete pose gradient (library option "pose_grad" = 1: the view-matrix
+    counterpart of the Gaussians' dL_dmeans3D, with the 2D-covariance, colour and depth terms the reference leaves out) instead
+    of the reference's; the forward runs under it and its backward follows.  The campos used is the one formed from
+    `viewmatrix` here (or `pose_tensors`), which is what makes the colour term exact."""
     if viewmatrix is None or fov is None or HW is None:
         raise ValueError("render() needs viewmatrix=W2C^T, fov=(tanfovx, tanfovy) and HW=(H, W)")
     mod = _light if variant == "light" else _full
@@ -333,15 +339,16 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         settings = mod.GaussianRasterizationSettings(**common, perspec_matrix=perspec)
     rasterizer = mod.GaussianRasterizer(raster_settings=settings)
     shs, colors = (None, override_color) if override_color is not None else (shs_or_colors, None)
-    if absgrad:
-        abs_points = torch.zeros_like(means3D, requires_grad=True)
-        out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
-                         colors_precomp=colors, scales=scaling, rotations=rotation, cov3D_precomp=None,
-                         viewmatrix=viewmatrix, gt_depth=gt_depth, means2D_abs=abs_points)
-    else:
-        out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
-                         colors_precomp=colors, scales=scaling, rotations=rotation, cov3D_precomp=None,
-                         viewmatrix=viewmatrix, gt_depth=gt_depth)
+    with _pose_mode(complete_pose):
+        if absgrad:
+            abs_points = torch.zeros_like(means3D, requires_grad=True)
+            out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
+                             colors_precomp=colors, scales=scaling, rotations=rotation, cov3D_precomp=None,
+                             viewmatrix=viewmatrix, gt_depth=gt_depth, means2D_abs=abs_points)
+        else:
+            out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
+                             colors_precomp=colors, scales=scaling, rotations=rotation, cov3D_precomp=None,
+                             viewmatrix=viewmatrix, gt_depth=gt_depth)
     if variant == "light":
         color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels = out
         res = {"render": color, "depth": depth, "depth_median": depth_median, "opacity_map": opacity_map,
@@ -355,15 +362,23 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     return res
 
 
+def _pose_mode(complete_pose):
+    """The block's rasterizer calls under pose_grad = 1 (their backwards follow through the forward's options snapshot)."""
+    if not complete_pose:
+        return _contextlib.nullcontext()
+    from . import _capi
+    return _capi.thread_options(pose_grad=1)
+
+
 def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, track_off=False, map_off=False,
-                 variant="light", absgrad=False):
+                 variant="light", absgrad=False, complete_pose=False):
     """`render()` for the V cameras of a keyframe batch in ONE call of the batched entry points (`dgr_amd.batch`, SURVEY.md
     s8(f) item 2; `variant="full"`: `dgr_amd.batch_full`): the cameras share `fov` and `HW` (one sensor, V poses), every
     per-view entry of `render()`'s dict comes back with a leading view dimension, and one backward through it yields the
     Gaussians' gradients already summed over the views, the pose gradient per `viewmatrix` and `viewspace_points.grad`
     ([V,P,3]) per view.  `cameras`: sequence of dicts with `viewmatrix` (W2C^T), `fov`, `HW`, `gt_depth` and optionally
     `viewpoint_camera`.  The full variant has no track_off / map_off.  `absgrad=True`: as in `render()`, with
-    `viewspace_points_abs` [V,P,3]."""
+    `viewspace_points_abs` [V,P,3].  `complete_pose=True`: every view's pose gradient is the complete one, as in `render()`."""
     from . import batch as _batch
     if variant not in ("light", "full"):
         raise ValueError(f"unknown variant {variant!r}")
@@ -434,18 +449,20 @@ def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_col
     shs, colors = (None, override_color) if override_color is not None else (shs_or_colors, None)
     if variant == "full":
         from .batch_full import GaussianRasterizerBatchFull
-        color, radii, depth, uncertainty = GaussianRasterizerBatchFull(settings)(
-            means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors, scales=scaling, rotations=rotation,
-            viewmatrices=viewmatrices, gt_depths=gt_depths, means2D_abs=abs_points)
+        with _pose_mode(complete_pose):
+            color, radii, depth, uncertainty = GaussianRasterizerBatchFull(settings)(
+                means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors, scales=scaling, rotations=rotation,
+                viewmatrices=viewmatrices, gt_depths=gt_depths, means2D_abs=abs_points)
         res = {"render": color, "depth": depth, "opacity_map": uncertainty, "viewspace_points": screenspace_points,
                "visibility_filter": radii > 0, "radii": radii}
         if absgrad:
             res["viewspace_points_abs"] = abs_points
         return res
-    color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels = \
-        _batch.GaussianRasterizerBatch(settings)(means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors,
-                                                 scales=scaling, rotations=rotation, viewmatrices=viewmatrices,
-                                                 gt_depths=gt_depths, means2D_abs=abs_points)
+    with _pose_mode(complete_pose):
+        color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels = \
+            _batch.GaussianRasterizerBatch(settings)(means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors,
+                                                     scales=scaling, rotations=rotation, viewmatrices=viewmatrices,
+                                                     gt_depths=gt_depths, means2D_abs=abs_points)
     res = {"render": color, "depth": depth, "depth_median": depth_median, "opacity_map": opacity_map, "depth_var": depth_var,
            "gau_uncertainty": gau_uncertainty, "num_related_pixels": gau_related_pixels,
            "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii}
@@ -491,7 +508,8 @@ def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None,
     accumulation passes over the dense gradient rows and with the camera-independent per-Gaussian work done once.
     `batch_loss_fn(out)`, if given, replaces the V calls of `loss_fn`: it sees the batched dict and returns the SUM of the
     views' losses as one scalar (then the returned list holds that one value).  `variant="full"` (a render_kwargs entry) renders
-    through the full variant's batch.  `absgrad=True`: the returned dict carries `viewspace_points_abs` (render_views)."""
+    through the full variant's batch.  `absgrad=True`: the returned dict carries `viewspace_points_abs` (render_views).
+    `complete_pose=True` (a render_kwargs entry) passes through to `render_views`: complete pose gradients."""
     if absgrad:
         render_kwargs["absgrad"] = True
     out = render_views(cameras, pc, pipe, bg_color, **render_kwargs)

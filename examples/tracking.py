@@ -7,7 +7,12 @@ map_off=True, no Gaussian gradients).  With --graph the whole iteration -- pose 
 Adam step -- is recorded once into a hipGraph and replayed (dgr_amd.multiview.CapturedStep), which removes the host
 from the loop.
 
-  python examples/tracking.py [--graph] [--fused] [--iters 150] [--width 640 --height 480 --gaussians 100000]
+With --complete-pose the pose gradient is the complete one (slam.render(complete_pose=True): 2D covariance, colour and every
+depth term included) instead of the reference's.  --trace K prints the pose error every K iterations (the timing then includes
+those reads).
+
+  python examples/tracking.py [--graph] [--fused] [--complete-pose] [--trace K] [--iters 150]
+                              [--width 640 --height 480 --gaussians 100000]
 """
 import argparse
 import os
@@ -31,6 +36,8 @@ def main():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
+    ap.add_argument("--complete-pose", action="store_true", help="the complete pose gradient (library option pose_grad = 1)")
+    ap.add_argument("--trace", type=int, default=0, help="print the pose error every K iterations")
     args = ap.parse_args()
     if args.graph or args.fused:
         # a blocking status read cannot be captured, and a tracking loop has no use for num_rendered on the host: no host wait
@@ -46,7 +53,8 @@ def main():
     pc = Model(s, dev)
     tanfovx, tanfovy, Rm, t_true, *_ = camera(W, H, 0.05)
     bg, gt_depth = torch.from_numpy(s.bg).to(dev), torch.from_numpy(s.gt).to(dev)
-    kw = dict(fov=(tanfovx, tanfovy), HW=(H, W), gt_depth=gt_depth, track_off=False, map_off=True)
+    kw = dict(fov=(tanfovx, tanfovy), HW=(H, W), gt_depth=gt_depth, track_off=False, map_off=True,
+              complete_pose=args.complete_pose)
 
     # one device, one Python thread: the autograd engine's worker thread only adds a hand-off per backward (0.47 -> 0.32 ms per
     # iteration here); a switch of PyTorch, not of the rasterizer
@@ -104,13 +112,17 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.iters):
         loss = run()
+        if args.trace and (i + 1) % args.trace == 0:
+            e = err()
+            print(f"  iteration {i + 1}: rotation error {e[0]:.2e}, translation error {e[1]:.2e}")
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if args.graph:
         step.check()
     print(f"finish: rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}, loss {float(loss):.3e}")
     print(f"{args.iters} iterations in {dt * 1e3:.1f} ms = {dt / args.iters * 1e3:.3f} ms per tracking iteration"
-          f" ({'hipGraph replay' if args.graph else 'eager'}{', fused pose and loss' if args.fused else ''})")
+          f" ({'hipGraph replay' if args.graph else 'eager'}{', fused pose and loss' if args.fused else ''}"
+          f"{', complete pose gradient' if args.complete_pose else ''})")
 
 
 if __name__ == "__main__":

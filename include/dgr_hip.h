@@ -288,6 +288,17 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
  *     run-to-run spread of it.  Costs about a quarter of the backward at config 3 (profiles/r8/deterministic.txt).  Needs
  *     dgr_light_backward_scratch_bytes_r() of scratch.  The full variant and the batched entry points (both variants) use the
  *     same scheme per view.
+ *  "pose_grad" (default 0; DGR_POSE_GRAD = 0 / 1 in the environment sets the initial value): 0 = the reference's pose gradient
+ *     (dL_dview from the mean2D path and the depth sum only); 1 = the complete pose gradient: dL_dview is the view-matrix
+ *     counterpart of the dL_dmeans3D the same backward returns -- the ndc terms from its mean2D sums, the z path from its depth
+ *     sums (light: depth, variance and median; full: the depth term of computeCov2DCUDA), the 2D covariance through Rcam in
+ *     A = Ju Rcam and through t_cam in Ju, and the SH colour through campos.  It keeps the variant's quirks (straight-through
+ *     alpha clamp, the clamp of t.x/t.z and t.y/t.z, the light median criterion, the full variant's uncertainty consumed as a
+ *     variance), so for a rigid view dL_dview[12..14] = Rcam sum_g dL_dmeans3D[g] to float rounding.  Entries 3, 7, 11, 15 stay
+ *     0; the per-Gaussian outputs are unchanged; track_off = 1 makes it a no-op.  The library differentiates campos as
+ *     -Rcam^T t of the view matrix while using the campos passed to the forward: the derivative is exact for callers that pass a
+ *     consistent campos.  A light map_off backward then runs the mapping blend backward and drops its per-Gaussian outputs.
+ *     Other values: DGR_ERR_BAD_ARGUMENT.
  *  "tight_cull": 1 = alpha-aware tile rectangles.  The reference gives a Gaussian every tile its
  *     3-sigma_max circle touches (cuda_rasterizer/forward.cu:229-237, auxiliary.h:46-56); with this option the rectangle
  *     is cut down to the box where alpha can reach 15/255.  Images and gradients are unchanged, but num_rendered, the
@@ -321,12 +332,12 @@ int dgr_set_option(const char* name, int value);
 int dgr_get_option(const char* name);
 
 /* Per-THREAD values of the options that change what a call computes -- "alpha_mode" (and its older name "fast_alpha"),
- * "tight_cull", "deterministic_grads" -- overriding the process-wide ones above for the calling thread's next calls (value < 0:
+ * "tight_cull", "deterministic_grads", "pose_grad" -- overriding the process-wide ones above for the calling thread's next calls (value < 0:
  * inherit again).  A tracker and a mapper thread of one process hold different settings this way, and nothing a thread sets
  * reaches launches that are already queued: every entry point reads its options once, when it is called.  (The reference has
  * no options; its one compile-time choice is the variant.)  dgr_get_thread_option = the value the calling thread's next call
- * uses.  dgr_thread_options_effective() packs the three (each field value + 1: bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
- * deterministic_grads) and dgr_thread_options_swap(word) installs such a word as the thread's overrides (field 0 = inherit;
+ * uses.  dgr_thread_options_effective() packs the four (each field value + 1: bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
+ * deterministic_grads, 12-15 pose_grad) and dgr_thread_options_swap(word) installs such a word as the thread's overrides (field 0 = inherit;
  * word < 0: only read) and returns the previous one -- what an autograd binding uses to run a backward, on whatever thread the
  * engine picks, under its forward's options. */
 int dgr_set_thread_option(const char* name, int value);
