@@ -434,35 +434,30 @@ int binning_stages(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView im
     return DGR_OK;
 }
 
-int forward_back(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, dgr::BinningView bin, hipStream_t st,
-                 ArmedReport* armed = nullptr) {
-    const int gx = dgr::tiles_x(c.W), gy = dgr::tiles_y(c.H);
-    dgr::RenderFwdLightArgs r{};
-    r.W = c.W; r.H = c.H; r.grid_x = gx; r.grid_y = gy;
-    r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = bin.point_list; r.rec = geom.rec; r.bg = c.background; r.gt_depth = c.gt_depth;
-    r.out_color = c.out_color; r.out_depth = c.out_depth; r.out_median = c.out_median_depth; r.out_alpha = c.out_alpha;
-    r.out_depth_var = c.out_depth_var; r.n_contrib = img.n_contrib; r.gau_uncertainty = c.gau_uncertainty;
-    r.gau_related_pixels = c.gau_related_pixels;
-    r.rep = armed ? armed->rep : dgr::StatusReport{nullptr, 0u, nullptr};
-    r.status = img.status;
-    { ScopedStage t(ST_RENDER_FWD, st); HIP_TRY(dgr::launch_render_fwd_light(r, opt_alpha_mode(), st)); }
-    if (armed) armed->handed_over = true;  // (workgroup 0 of the blend delivers the word)
-    return DGR_OK;
-}
-
-// ---- full variant: same front end, different blend
-int forward_back_full(const FwdCommon& c, float* out_uncertainty, dgr::GeometryView geom, dgr::ImageView img,
-                      dgr::BinningView bin, hipStream_t st, ArmedReport* armed = nullptr) {
-    const int gx = dgr::tiles_x(c.W), gy = dgr::tiles_y(c.H);
-    dgr::RenderFwdFullArgs r{};
-    r.W = c.W; r.H = c.H; r.grid_x = gx; r.grid_y = gy;
+// The forward blend, light or full (the full variant's uncertainty image in c.out_alpha)
+template <class A>
+void blend_fwd_common(A& r, const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, dgr::BinningView bin, ArmedReport* armed) {
+    r.W = c.W; r.H = c.H; r.grid_x = dgr::tiles_x(c.W); r.grid_y = dgr::tiles_y(c.H);
     r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = bin.point_list; r.rec = geom.rec; r.bg = c.background;
-    r.out_color = c.out_color; r.out_depth = c.out_depth; r.out_uncertainty = out_uncertainty;
-    r.n_contrib = img.n_contrib; r.n_valid = img.n_valid; r.first_contrib = img.first_contrib; r.final_T = img.final_T;
-    r.status = img.status;
+    r.out_color = c.out_color; r.out_depth = c.out_depth; r.n_contrib = img.n_contrib; r.status = img.status;
     r.rep = armed ? armed->rep : dgr::StatusReport{nullptr, 0u, nullptr};
-    { ScopedStage t(ST_RENDER_FWD, st); HIP_TRY(dgr::launch_render_fwd_full(r, opt_alpha_mode(), st)); }
-    if (armed) armed->handed_over = true;
+}
+int forward_blend(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, dgr::BinningView bin, hipStream_t st, bool full,
+                  ArmedReport* armed = nullptr) {
+    ScopedStage t(ST_RENDER_FWD, st);
+    if (full) {
+        dgr::RenderFwdFullArgs r{};
+        blend_fwd_common(r, c, geom, img, bin, armed);
+        r.out_uncertainty = c.out_alpha; r.n_valid = img.n_valid; r.first_contrib = img.first_contrib; r.final_T = img.final_T;
+        HIP_TRY(dgr::launch_render_fwd_full(r, opt_alpha_mode(), st));
+    } else {
+        dgr::RenderFwdLightArgs r{};
+        blend_fwd_common(r, c, geom, img, bin, armed);
+        r.gt_depth = c.gt_depth; r.out_median = c.out_median_depth; r.out_alpha = c.out_alpha; r.out_depth_var = c.out_depth_var;
+        r.gau_uncertainty = c.gau_uncertainty; r.gau_related_pixels = c.gau_related_pixels;
+        HIP_TRY(dgr::launch_render_fwd_light(r, opt_alpha_mode(), st));
+    }
+    if (armed) armed->handed_over = true;  // (workgroup 0 of the blend delivers the word)
     return DGR_OK;
 }
 
@@ -645,9 +640,7 @@ int forward_batch(hipStream_t st, int n_views, const FwdCommon* cv, const BatchV
             HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
             sv = st;
         }
-        if (full) rc = forward_back_full(cv[v], cv[v].out_alpha, geom[v], img[v], bin[v], sv);
-        else rc = forward_back(cv[v], geom[v], img[v], bin[v], sv);
-        if (rc) return rc;
+        if ((rc = forward_blend(cv[v], geom[v], img[v], bin[v], sv, full))) return rc;
     }
     return joined.done();
 }
@@ -709,22 +702,6 @@ __global__ void export_tag_bytes_kernel(const uint8_t* src, uint8_t* dst, int n,
     dst[i] = (uint8_t)t;
 }
 
-}  // namespace
-
-extern "C" {
-
-const char* dgr_last_error(void) { return g_last_error.c_str(); }
-const char* dgr_version(void) { return "dgr_hip 0.1 gfx950"; }
-
-size_t dgr_geometry_bytes(int P) { return dgr::carve_geometry(nullptr, P).bytes; }
-size_t dgr_image_bytes(int width, int height) { return dgr::carve_image(nullptr, width, height).bytes; }
-size_t dgr_binning_bytes(int cap, int width, int height) {
-    // the sorted list, key scratch, ranks / pair columns and pair keys of `cap` instances, then the forward-only tables of
-    // the segment binning
-    return dgr::carve_binning(nullptr, (size_t)(cap > 0 ? cap : 0)).bytes + dgr::carve_segment_tables(nullptr, width, height).bytes;
-}
-size_t dgr_light_backward_scratch_bytes(int P, int, int) { return dgr::carve_backward_scratch(nullptr, P).bytes; }
-namespace {
 // absgrad (dgr_*_backward*_absgrad, dgr_hip.h): what is refused, before any device call
 int absgrad_refused(bool wanted, int map_off) {
     if (!wanted) return DGR_OK;
@@ -751,7 +728,315 @@ DetScratch carve_det_scratch(char* base, int P, int R) {
     d.bytes = o;
     return d;
 }
+
+// The body of dgr_light_forward_presized / dgr_full_forward_presized (full: the uncertainty image in c.out_alpha)
+int forward_presized(hipStream_t st, const FwdCommon& c, char* geometry_buffer, char* binning_buffer, int binning_capacity,
+                     char* image_buffer, int* status, bool full) {
+    ArmedReport armed(c.W, c.H, c.P, st);  // (dgr_status_arm: completed from the host on every path that enqueues no binning kernel)
+    int rc = check_common(c);
+    if (rc) return rc;
+    if (c.P == 0) {
+        if (status) HIP_TRY(hipMemsetAsync(status, 0, 16, st));
+        return zero_outputs(c, st);
+    }
+    // (the binning buffer also holds the segment binning's tables behind its per-instance arrays: dgr_binning_bytes() is
+    //  non-zero for a capacity of 0, and a NULL buffer is never valid for P > 0)
+    if (!geometry_buffer || !image_buffer || !binning_buffer || binning_capacity < 0) {
+        g_last_error = "presized forward: geometry, binning and image buffers are required (sizes: dgr_*_bytes)";
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    dgr::GeometryView geom = dgr::carve_geometry(geometry_buffer, c.P);
+    dgr::ImageView img = dgr::carve_image(image_buffer, c.W, c.H);
+    if (status) img.status = status;  // the kernels write the caller's status word directly
+    dgr::BinningView bin = dgr::carve_binning(binning_buffer, (size_t)binning_capacity);
+    const int mode = presized_count_mode(c.W, c.H, binning_capacity);
+    if ((rc = forward_front(c, geom, img, st, &bin, binning_capacity, image_buffer, mode))) return rc;
+    if ((rc = binning_stages(c, geom, img, bin, binning_capacity, st, mode, binning_buffer, &armed))) return rc;
+    return forward_blend(c, geom, img, bin, st, full, &armed);
+}
+
+// The body of dgr_light_forward / dgr_full_forward.  num_related (full): the reference's second blocking read, or NULL.
+int forward_callback(hipStream_t st, const FwdCommon& c, dgr_alloc_fn geometryBuffer, dgr_alloc_fn binningBuffer,
+                     dgr_alloc_fn imageBuffer, void* alloc_user, bool full, int* num_related, int debug) {
+    if (num_related) *num_related = 0;
+    int rc = check_common(c);
+    if (rc) return rc;
+    // The callback entry points block the host to size the binning buffer, as the reference does (rasterizer_impl.cu:287): on a
+    // capturing stream that synchronisation would fail AND invalidate the capture -- refuse before anything touches the stream.
+    if (dgr_stream_is_capturing(st)) {
+        g_last_error = "the resize-callback forward blocks the host (it sizes the binning buffer): it cannot be captured into a graph -- use the presized entry point";
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    if (c.P == 0) return zero_outputs(c, st);
+    char* gptr = geometryBuffer(dgr_geometry_bytes(c.P), alloc_user);
+    char* iptr = imageBuffer(dgr_image_bytes(c.W, c.H), alloc_user);
+    if (!gptr || !iptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
+    dgr::GeometryView geom = dgr::carve_geometry(gptr, c.P);
+    dgr::ImageView img = dgr::carve_image(iptr, c.W, c.H);
+    if ((rc = forward_front(c, geom, img, st))) return rc;
+    // the one blocking read the reference also has (rasterizer_impl.cu:287, F/...:435): num_rendered sizes the binning buffer
+    int status[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (status[2]) { g_last_error = "Point is filtered although prefiltered is set. This shouldn't happen!"; return DGR_ERR_PREFILTERED; }
+    const int R = status[0];
+    char* bptr = nullptr;
+    if (R > 0) {
+        bptr = binningBuffer(dgr_binning_bytes(R, c.W, c.H), alloc_user);
+        if (!bptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
+    } else {
+        binningBuffer(0, alloc_user);
+    }
+    dgr::BinningView bin = dgr::carve_binning(bptr, (size_t)R);
+    // (also with R == 0: it writes the (empty) range table)
+    const int mode = (R > 0 && presized_count_mode(c.W, c.H, R) == COUNT_LDS) ? COUNT_LDS_CALLBACK : COUNT_CALLBACK;
+    if ((rc = binning_stages(c, geom, img, bin, R, st, mode, bptr))) return rc;
+    if ((rc = forward_blend(c, geom, img, bin, st, full))) return rc;
+    if (num_related) {  // second blocking read of the reference (F/cuda_rasterizer/rasterizer_impl.cu:498)
+        HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *num_related = status[3];
+    }
+    if (debug) HIP_TRY(hipStreamSynchronize(st));  // CHECK_CUDA(..., debug): L/cuda_rasterizer/auxiliary.h:166-173
+    return R;
+}
+
+// ---- backward (one view, or a batch).  The scene's side -- the Gaussians, their gradients, the variant -- is a PreprocessBwdArgs
+// whose per-view members are filled per view; the full variant is the light path with track_off = map_off = 0, full_variant = 1.
+// One view's side, as the one-view entry points and the batches' view structs give it:
+struct BwdView {
+    char *geometry_buffer, *binning_buffer, *image_buffer;
+    const float *viewmatrix, *projmatrix, *cam_pos, *perspec_matrix, *gt_depth;
+    const int* radii;
+    const float *alphas, *dL_dpix, *dL_dpix_depth, *dL_dpix_median_depth, *dL_dpix_depth_var;  // (light; full: dL_dpix only)
+    const float *dL_depths, *dL_duncertainties;                                                 // (full)
+    float *dL_dmean2D, *dL_dview, *dL_dmean2D_abs;
+    char* scratch;
+    size_t scratch_bytes;
+    int R;  // >= the view's num_rendered: sizes the deterministic row buffer
+};
+BwdView bwd_view(const dgr_light_view_grad& w, float* abs) {
+    return BwdView{w.geometry_buffer, w.binning_buffer, w.image_buffer, w.viewmatrix, w.projmatrix, w.cam_pos, w.perspec_matrix,
+                   w.gt_depth, w.radii, w.alphas, w.dL_dpix, w.dL_dpix_depth, w.dL_dpix_median_depth, w.dL_dpix_depth_var, nullptr,
+                   nullptr, w.dL_dmean2D, w.dL_dview, abs, w.scratch, w.scratch_bytes, w.num_rendered};
+}
+BwdView bwd_view(const dgr_full_view_grad& w, float* abs) {
+    return BwdView{w.geometry_buffer, w.binning_buffer, w.image_buffer, w.viewmatrix, w.projmatrix, w.cam_pos, w.perspec_matrix,
+                   w.gt_depth, w.radii, nullptr, w.dL_dpix, nullptr, nullptr, nullptr, w.dL_depths, w.dL_duncertainties,
+                   w.dL_dmean2D, w.dL_dview, abs, w.scratch, w.scratch_bytes, w.num_rendered};
+}
+dgr::PreprocessBwdArgs bwd_scene(int P, int D, int M, int W, int H, const float* means3D, const float* shs, const float* scales,
+                                 float scale_modifier, const float* rotations, const float* cov3D_precomp, float tan_fovx,
+                                 float tan_fovy, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                                 float* dL_dsh, float* dL_dscale, float* dL_drot, int track_off, int map_off, int full) {
+    dgr::PreprocessBwdArgs b{};
+    b.P = P; b.D = D; b.M = M; b.W = W; b.H = H; b.means3D = means3D; b.shs = shs; b.scales = scales;
+    b.rotations = rotations; b.scale_modifier = scale_modifier; b.cov3D_precomp = cov3D_precomp;
+    b.tan_fovx = tan_fovx; b.tan_fovy = tan_fovy;
+    b.focal_y = H / (2.0f * tan_fovy);
+    b.focal_x = W / (2.0f * tan_fovx);
+    b.sh_vec_ok = aligned16(shs) && aligned16(dL_dsh);
+    b.track_off = track_off; b.map_off = map_off; b.full_variant = full;
+    b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
+    b.dL_dscale = dL_dscale; b.dL_drot = dL_drot;
+    return b;
+}
+
+// A view's state and scratch, carved
+struct BwdBufs {
+    dgr::GeometryView geom;
+    dgr::ImageView img;
+    dgr::BackwardScratch sc;
+    DetScratch ds;
+};
+// Carves a view's buffers and clears what its blend backward adds into: the accumulator rows (unless the resident scratch is
+// known to be clean), the absgrad output and, with deterministic_grads, the row buffer; then the Gaussians' first-instance offsets.
+int bwd_view_prepare(const BwdView& w, int P, int W, int H, bool det, bool scratch_clean, BwdBufs& s, hipStream_t st) {
+    s.geom = dgr::carve_geometry(w.geometry_buffer, P);
+    s.img = dgr::carve_image(w.image_buffer, W, H);
+    s.sc = dgr::carve_backward_scratch(w.scratch, P);
+    s.ds = DetScratch{nullptr, nullptr, nullptr, 0};
+    if (!scratch_clean) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(s.sc.acc, s.sc.zero_bytes, st)); }
+    if (w.dL_dmean2D_abs) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_floats(w.dL_dmean2D_abs, 3 * (size_t)P, st)); }
+    if (det) {
+        // (the Gaussians' first-instance offsets go into the geometry state's goff array, which only the global-counter binning
+        //  of the FORWARD uses: free by now)
+        s.ds = carve_det_scratch(w.scratch, P, w.R);
+        { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(s.ds.rows, sizeof(float) * DGR_ACC_STRIDE * (size_t)w.R, st)); }
+        HIP_TRY(dgr::launch_det_offsets(P, s.geom.rect, s.ds.blk, s.geom.goff, st));
+    }
+    return DGR_OK;
+}
+
+// The blend backward of one view: what both variants' arguments share, then one function per variant that fills the rest and
+// launches it (absgrad: the _abs instance)
+template <class A>
+void blend_bwd_common(A& r, const BwdView& w, const float* bg, int W, int H, const BwdBufs& s, bool det) {
+    r.W = W; r.H = H; r.grid_x = dgr::tiles_x(W); r.grid_y = dgr::tiles_y(H);
+    r.sched = s.img.tile_sched; r.ranges = s.img.ranges; r.sched_flag = s.img.cursor + 3; r.point_list = (const uint32_t*)w.binning_buffer;
+    r.rec = s.geom.rec; r.bg = bg; r.gt_depth = w.gt_depth; r.n_contrib = s.img.n_contrib; r.acc = s.sc.acc;
+    if (det) { r.det_rows = s.ds.rows; r.det_rect = s.geom.rect; r.det_goff = s.geom.goff; r.det_R = (uint32_t)w.R; }
+}
+int blend_bwd_light(const BwdView& w, const dgr::PreprocessBwdArgs& b, const float* bg, const BwdBufs& s, bool det, bool complete,
+                    hipStream_t st) {
+    dgr::RenderBwdLightArgs r{};
+    blend_bwd_common(r, w, bg, b.W, b.H, s, det);
+    r.alphas = w.alphas; r.dL_dpix = w.dL_dpix; r.dL_dpix_depth = w.dL_dpix_depth; r.dL_dpix_median = w.dL_dpix_median_depth;
+    r.dL_dpix_var = w.dL_dpix_depth_var;
+    // (complete pose gradient: the tracking blend's three sums are not enough -- the mapping blend backward forms all of them)
+    r.means3D = b.means3D; r.view = w.viewmatrix; r.track_off = b.track_off; r.map_off = complete ? 0 : b.map_off;
+    ScopedStage t(ST_RENDER_BWD, st);
+    if (w.dL_dmean2D_abs) HIP_TRY(dgr::launch_render_bwd_light_abs(r, w.dL_dmean2D_abs, opt_alpha_mode(), st));
+    else HIP_TRY(dgr::launch_render_bwd_light(r, opt_alpha_mode(), st));
+    return DGR_OK;
+}
+int blend_bwd_full(const BwdView& w, const dgr::PreprocessBwdArgs& b, const float* bg, const BwdBufs& s, bool det, hipStream_t st) {
+    dgr::RenderBwdFullArgs r{};
+    blend_bwd_common(r, w, bg, b.W, b.H, s, det);
+    r.final_T = s.img.final_T; r.first_contrib = s.img.first_contrib;
+    r.dL_dpix = w.dL_dpix; r.dL_depths = w.dL_depths; r.dL_duncertainties = w.dL_duncertainties;
+    ScopedStage t(ST_RENDER_BWD, st);
+    if (w.dL_dmean2D_abs) HIP_TRY(dgr::launch_render_bwd_full_abs(r, w.dL_dmean2D_abs, opt_alpha_mode(), st));
+    else HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), st, det));
+    return DGR_OK;
+}
+// ... and the gather of the deterministic rows into the accumulators behind it
+int bwd_view_blend(const BwdView& w, const dgr::PreprocessBwdArgs& b, const float* bg, const BwdBufs& s, bool det, bool complete,
+                   hipStream_t st) {
+    const int rc = b.full_variant ? blend_bwd_full(w, b, bg, s, det, st) : blend_bwd_light(w, b, bg, s, det, complete, st);
+    if (rc) return rc;
+    if (det) HIP_TRY(dgr::launch_det_gather(b.P, s.geom.rect, s.geom.goff, s.ds.rows, (uint32_t)w.R, s.sc.acc, st));
+    return DGR_OK;
+}
+
+// The per-view members of the per-Gaussian backward: PreprocessBwdArgs (one view) or a batch's BwdViewPart
+template <class Q>
+void bwd_view_part(Q& q, const BwdView& w, const BwdBufs& s, bool det) {
+    q.det_pose = det ? s.ds.pose : nullptr;
+    q.view = w.viewmatrix; q.proj = w.projmatrix; q.campos = w.cam_pos; q.perspec = w.perspec_matrix;
+    q.radii = w.radii ? w.radii : s.geom.radii; q.geom = s.geom; q.acc = s.sc.acc; q.dL_dmean2D = w.dL_dmean2D;
+    q.pose_part = s.sc.pose_part; q.ticket = s.sc.ticket; q.dL_dview = w.dL_dview;
+}
+
+// The body of dgr_{light,full}_backward[_absgrad]
+int backward_one(hipStream_t st, dgr::PreprocessBwdArgs b, const float* background, const BwdView& w, int debug) {
+    const bool scratch_clean = g_scratch_clean_armed;  // (consumed by every call, a refused one included)
+    g_scratch_clean_armed = false;
+    const int P = b.P, width = b.W, height = b.H, R = w.R;
+    if (int rc = absgrad_refused(w.dL_dmean2D_abs != nullptr, b.map_off)) return rc;
+    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
+        HIP_TRY(hipMemsetAsync(w.dL_dview, 0, 16 * 4, st));
+        return DGR_OK;
+    }
+    const bool det = opt_det_grads() != 0 && !(b.track_off && b.map_off);
+    const bool complete = opt_pose_grad() != 0 && !b.track_off;  // (track_off: no pose gradient, nothing to complete)
+    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
+    if (det && R <= 0) { g_last_error = "deterministic_grads: the backward needs R >= num_rendered (it sizes the instance-major row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
+    if (w.scratch_bytes < dgr_light_backward_scratch_bytes_r(P, width, height, R) || !w.scratch) {
+        g_last_error = det ? "backward scratch too small (deterministic_grads: dgr_light_backward_scratch_bytes_r)" : "backward scratch too small";
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    // (the 3D covariance is not kept by the forward: the backward re-forms it from scale and rotation -- the SAME tensors the
+    //  forward saw, or the bits differ -- unless the caller precomputed it)
+    if (!b.cov3D_precomp && (!b.scales || !b.rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
+    if (!w.geometry_buffer || !w.binning_buffer || !w.image_buffer) { g_last_error = "backward: the forward's three state buffers are required"; return DGR_ERR_BAD_ARGUMENT; }
+    BwdBufs s;
+    if (int rc = bwd_view_prepare(w, P, width, height, det, scratch_clean, s, st)) return rc;
+    if (int rc = bwd_view_blend(w, b, background, s, det, complete, st)) return rc;
+    bwd_view_part(b, w, s, det);
+    b.clear_scratch = scratch_clean ? 1 : 0;
+    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st, complete)); }
+    if (debug && !dgr_stream_is_capturing(st)) HIP_TRY(hipStreamSynchronize(st));  // (CHECK_CUDA(..., debug); a capturing stream cannot be waited for -- and the attempt would invalidate the capture)
+    return DGR_OK;
+}
+
+// The inputs a view of a batch backward must have (the full blend backward reads gt_depth on every path, the lean one included)
+bool bwd_view_complete(const BwdView& w, bool full) {
+    if (!w.geometry_buffer || !w.binning_buffer || !w.image_buffer || !w.viewmatrix || !w.projmatrix || !w.cam_pos || !w.perspec_matrix)
+        return false;
+    if (full) return w.gt_depth && w.dL_dpix && w.dL_depths;
+    return w.alphas && w.dL_dpix && w.dL_dpix_depth && w.dL_dpix_median_depth && w.dL_dpix_depth_var;
+}
+
+// The body of dgr_{light,full}_backward_batch[_absgrad]: per view the scheme of the one-view backward (without the resident
+// scratch), the per-Gaussian backward once for all views
+int backward_batch(hipStream_t st, dgr::PreprocessBwdArgs b, const float* background, int n_views, const BwdView* views) {
+    const int P = b.P, width = b.W, height = b.H;
+    const bool det = opt_det_grads() != 0 && !(b.track_off && b.map_off);
+    const bool complete = opt_pose_grad() != 0 && !b.track_off;
+    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
+    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    bool any_abs = false;  // (absgrad: a NULL array or NULL entries -- those views as without it)
+    for (int v = 0; v < n_views; v++) any_abs |= views[v].dL_dmean2D_abs != nullptr;
+    if (int rc = absgrad_refused(any_abs, b.map_off)) return rc;
+    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
+    for (int v = 0; v < n_views; v++)
+        if (!views[v].dL_dview) { g_last_error = "view without dL_dview"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P > 0 && !b.cov3D_precomp && (!b.scales || !b.rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
+        for (int v = 0; v < n_views; v++) HIP_TRY(hipMemsetAsync(views[v].dL_dview, 0, 16 * 4, st));
+        return DGR_OK;
+    }
+    for (int v = 0; v < n_views; v++) {
+        const BwdView& w = views[v];
+        if (det && w.R <= 0) { g_last_error = "deterministic_grads: every view needs num_rendered (it sizes the view's row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
+        const size_t need = dgr_light_backward_scratch_bytes_r(P, width, height, w.R);
+        if (!w.scratch || w.scratch_bytes < need) { g_last_error = "backward scratch too small"; return DGR_ERR_BAD_ARGUMENT; }
+        if (!bwd_view_complete(w, b.full_variant != 0)) {
+            g_last_error = "view with a missing state buffer, camera or gradient image";
+            return DGR_ERR_BAD_ARGUMENT;
+        }
+    }
+    int rc;
+    if ((rc = batch_streams_ready())) return rc;
+    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
+    const int K = pipeline ? 2 : batch_stream_count(n_views);
+    dgr::PreprocessBwdBatchArgs bb{};
+    bb.base = b;
+    if ((rc = batch_fork(st, K))) return rc;
+    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
+    for (int v = 0; v < n_views; v++) {
+        const BwdView& w = views[v];
+        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
+        BwdBufs s;
+        if ((rc = bwd_view_prepare(w, P, width, height, det, false, s, sv))) return rc;
+        if (pipeline) {  // the blend backward of view v on the caller's stream, behind its cleared scratch
+            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
+            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
+            sv = st;
+        }
+        if ((rc = bwd_view_blend(w, b, background, s, det, complete, sv))) return rc;
+        bwd_view_part(bb.v[v], w, s, det);
+    }
+    if ((rc = joined.done())) return rc;
+    bb.V = n_views;
+    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st, complete)); }
+    return DGR_OK;
+}
+// the batch's view structs as BwdView (as many as the batch may hold: backward_batch checks n_views)
+template <class G>
+int backward_batch_views(hipStream_t st, const dgr::PreprocessBwdArgs& b, const float* background, int n_views, const G* views,
+                         float* const* dL_dmean2D_abs) {
+    BwdView bv[DGR_MAX_BATCH_VIEWS];
+    for (int v = 0; views && v < n_views && v < DGR_MAX_BATCH_VIEWS; v++) bv[v] = bwd_view(views[v], dL_dmean2D_abs ? dL_dmean2D_abs[v] : nullptr);
+    return backward_batch(st, b, background, n_views, views ? bv : nullptr);
+}
 }  // namespace
+
+extern "C" {
+
+const char* dgr_last_error(void) { return g_last_error.c_str(); }
+const char* dgr_version(void) { return "dgr_hip 0.1 gfx950"; }
+
+size_t dgr_geometry_bytes(int P) { return dgr::carve_geometry(nullptr, P).bytes; }
+size_t dgr_image_bytes(int width, int height) { return dgr::carve_image(nullptr, width, height).bytes; }
+size_t dgr_binning_bytes(int cap, int width, int height) {
+    // the sorted list, key scratch, ranks / pair columns and pair keys of `cap` instances, then the forward-only tables of
+    // the segment binning
+    return dgr::carve_binning(nullptr, (size_t)(cap > 0 ? cap : 0)).bytes + dgr::carve_segment_tables(nullptr, width, height).bytes;
+}
+size_t dgr_light_backward_scratch_bytes(int P, int, int) { return dgr::carve_backward_scratch(nullptr, P).bytes; }
 size_t dgr_light_backward_scratch_bytes_r(int P, int W, int H, int R) {
     if (!opt_det_grads()) return dgr_light_backward_scratch_bytes(P, W, H);
     return carve_det_scratch(nullptr, P, R).bytes;
@@ -762,6 +1047,7 @@ int dgr_mark_visible(void* stream, int P, const float* means3D, const float* vie
     return DGR_OK;
 }
 
+
 int dgr_light_forward_presized(void* stream, char* geometry_buffer, char* binning_buffer, int binning_capacity,
                                char* image_buffer, int* status, int P, int D, int M, const float* background,
                                int width, int height, const float* means3D, const float* shs,
@@ -771,33 +1057,11 @@ int dgr_light_forward_presized(void* stream, char* geometry_buffer, char* binnin
                                float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_depth,
                                float* out_median_depth, float* out_alpha, const float* gt_depth,
                                float* out_depth_var, float* gau_uncertainty, int* gau_related_pixels, int* radii) {
-    hipStream_t st = (hipStream_t)stream;
     FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
                 cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
                 out_color, out_depth, out_median_depth, out_alpha, gt_depth, out_depth_var, gau_uncertainty,
                 gau_related_pixels, radii};
-    ArmedReport armed(width, height, P, st);  // (dgr_status_arm: completed from the host on every path that enqueues no binning kernel)
-    int rc = check_common(c);
-    if (rc) return rc;
-    if (P == 0) {
-        if (status) HIP_TRY(hipMemsetAsync(status, 0, 16, st));
-        return zero_outputs(c, st);
-    }
-    // (the binning buffer also holds the segment binning's tables behind its per-instance arrays: dgr_binning_bytes() is
-    //  non-zero for a capacity of 0, and a NULL buffer is never valid for P > 0)
-    if (!geometry_buffer || !image_buffer || !binning_buffer || binning_capacity < 0) {
-        g_last_error = "presized forward: geometry, binning and image buffers are required (sizes: dgr_*_bytes)";
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    dgr::GeometryView geom = dgr::carve_geometry(geometry_buffer, P);
-    dgr::ImageView img = dgr::carve_image(image_buffer, width, height);
-    if (status) img.status = status;  // the kernels write the caller's status word directly
-    dgr::BinningView bin = dgr::carve_binning(binning_buffer, (size_t)binning_capacity);
-    const int mode = presized_count_mode(width, height, binning_capacity);
-    if ((rc = forward_front(c, geom, img, st, &bin, binning_capacity, image_buffer, mode))) return rc;
-    if ((rc = binning_stages(c, geom, img, bin, binning_capacity, st, mode, binning_buffer, &armed))) return rc;
-    if ((rc = forward_back(c, geom, img, bin, st, &armed))) return rc;
-    return DGR_OK;
+    return forward_presized((hipStream_t)stream, c, geometry_buffer, binning_buffer, binning_capacity, image_buffer, status, false);
 }
 
 int dgr_light_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn binningBuffer, dgr_alloc_fn imageBuffer,
@@ -808,126 +1072,13 @@ int dgr_light_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn bi
                       float tan_fovy, int prefiltered, float* out_color, float* out_depth, float* out_median_depth,
                       float* out_alpha, const float* gt_depth, float* out_depth_var, float* gau_uncertainty,
                       int* gau_related_pixels, int* radii, int debug) {
-    hipStream_t st = (hipStream_t)stream;
     FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
                 cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
                 out_color, out_depth, out_median_depth, out_alpha, gt_depth, out_depth_var, gau_uncertainty,
                 gau_related_pixels, radii};
-    int rc = check_common(c);
-    if (rc) return rc;
-    // The callback entry points block the host to size the binning buffer, as the reference does (rasterizer_impl.cu:287): on a
-    // capturing stream that synchronisation would fail AND invalidate the capture -- refuse before anything touches the stream.
-    if (dgr_stream_is_capturing(stream)) {
-        g_last_error = "the resize-callback forward blocks the host (it sizes the binning buffer): it cannot be captured into a graph -- use the presized entry point";
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    if (P == 0) return zero_outputs(c, st);
-    char* gptr = geometryBuffer(dgr_geometry_bytes(P), alloc_user);
-    char* iptr = imageBuffer(dgr_image_bytes(width, height), alloc_user);
-    if (!gptr || !iptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
-    dgr::GeometryView geom = dgr::carve_geometry(gptr, P);
-    dgr::ImageView img = dgr::carve_image(iptr, width, height);
-    if ((rc = forward_front(c, geom, img, st))) return rc;
-    // the one blocking read the reference also has (rasterizer_impl.cu:287): num_rendered sizes the binning buffer
-    int status[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (status[2]) { g_last_error = "Point is filtered although prefiltered is set. This shouldn't happen!"; return DGR_ERR_PREFILTERED; }
-    const int R = status[0];
-    char* bptr = nullptr;
-    if (R > 0) {
-        bptr = binningBuffer(dgr_binning_bytes(R, width, height), alloc_user);
-        if (!bptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
-    } else {
-        binningBuffer(0, alloc_user);
-    }
-    dgr::BinningView bin = dgr::carve_binning(bptr, (size_t)R);
-    // (also with R == 0: it writes the (empty) range table)
-    const int mode = (R > 0 && presized_count_mode(width, height, R) == COUNT_LDS) ? COUNT_LDS_CALLBACK : COUNT_CALLBACK;
-    if ((rc = binning_stages(c, geom, img, bin, R, st, mode, bptr))) return rc;
-    if ((rc = forward_back(c, geom, img, bin, st))) return rc;
-    if (debug) HIP_TRY(hipStreamSynchronize(st));  // CHECK_CUDA(..., debug): L/cuda_rasterizer/auxiliary.h:166-173
-    return R;
+    return forward_callback((hipStream_t)stream, c, geometryBuffer, binningBuffer, imageBuffer, alloc_user, false, nullptr, debug);
 }
 
-static int light_backward_impl(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
-                               const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
-                               const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
-                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
-                               float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
-                               const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
-                               const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
-                               float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
-                               float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
-                               const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
-                               const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes,
-                               float* dL_dmean2D_abs) {
-    (void)dgndcs_dviewmatrix; (void)dg_camd_dviewmatrix; (void)colors_precomp;
-    hipStream_t st = (hipStream_t)stream;
-    const bool scratch_clean = g_scratch_clean_armed;
-    g_scratch_clean_armed = false;
-    if (int rc = absgrad_refused(dL_dmean2D_abs != nullptr, map_off)) return rc;
-    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
-    if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
-        HIP_TRY(hipMemsetAsync(dL_dview, 0, 16 * 4, st));
-        return DGR_OK;
-    }
-    const bool det = opt_det_grads() != 0 && !(track_off && map_off);
-    const bool complete = opt_pose_grad() != 0 && !track_off;  // (track_off: no pose gradient, nothing to complete)
-    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
-    if (det && R <= 0) { g_last_error = "deterministic_grads: the backward needs R >= num_rendered (it sizes the instance-major row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
-    if (scratch_bytes < dgr_light_backward_scratch_bytes_r(P, width, height, R) || !scratch) {
-        g_last_error = det ? "backward scratch too small (deterministic_grads: dgr_light_backward_scratch_bytes_r)" : "backward scratch too small";
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    // (the 3D covariance is not kept by the forward: the backward re-forms it from scale and rotation -- the SAME tensors the
-    //  forward saw, or the bits differ -- unless the caller precomputed it)
-    if (!cov3D_precomp && (!scales || !rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
-    if (!geom_buffer || !binning_buffer || !image_buffer) { g_last_error = "backward: the forward's three state buffers are required"; return DGR_ERR_BAD_ARGUMENT; }
-    dgr::GeometryView geom = dgr::carve_geometry(geom_buffer, P);
-    dgr::ImageView img = dgr::carve_image(image_buffer, width, height);
-    dgr::BackwardScratch sc = dgr::carve_backward_scratch(scratch, P);
-    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
-    if (!scratch_clean) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, st)); }
-    if (dL_dmean2D_abs) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_floats(dL_dmean2D_abs, 3 * (size_t)P, st)); }
-
-    dgr::RenderBwdLightArgs r{};
-    r.W = width; r.H = height; r.grid_x = gx; r.grid_y = gy;
-    r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = (const uint32_t*)binning_buffer; r.rec = geom.rec; r.bg = background;
-    r.gt_depth = gt_depth; r.alphas = alphas; r.n_contrib = img.n_contrib; r.dL_dpix = dL_dpix;
-    r.dL_dpix_depth = dL_dpix_depth; r.dL_dpix_median = dL_dpix_median_depth; r.dL_dpix_var = dL_dpix_depth_var;
-    // (complete pose gradient: the tracking blend's three sums are not enough -- the mapping blend backward forms all of them)
-    r.means3D = means3D; r.view = viewmatrix; r.acc = sc.acc; r.track_off = track_off; r.map_off = complete ? 0 : map_off;
-    DetScratch ds{nullptr, nullptr, nullptr, 0};
-    if (det) {
-        // (the Gaussians' first-instance offsets go into the geometry state's goff array, which only the global-counter binning
-        //  of the FORWARD uses: free by now)
-        ds = carve_det_scratch(scratch, P, R);
-        { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(ds.rows, sizeof(float) * DGR_ACC_STRIDE * (size_t)R, st)); }
-        HIP_TRY(dgr::launch_det_offsets(P, geom.rect, ds.blk, geom.goff, st));
-        r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)R;
-    }
-    if (dL_dmean2D_abs) { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_light_abs(r, dL_dmean2D_abs, opt_alpha_mode(), st)); }
-    else { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_light(r, opt_alpha_mode(), st)); }
-    if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)R, sc.acc, st));
-
-    dgr::PreprocessBwdArgs b{};
-    b.det_pose = det ? ds.pose : nullptr;
-    b.P = P; b.D = D; b.M = M; b.W = width; b.H = height; b.means3D = means3D; b.radii = radii ? radii : geom.radii; b.shs = shs;
-    b.scales = scales;
-    b.rotations = rotations; b.scale_modifier = scale_modifier; b.cov3D_precomp = cov3D_precomp; b.view = viewmatrix;
-    b.proj = projmatrix; b.campos = campos; b.perspec = perspec_matrix; b.tan_fovx = tan_fovx; b.tan_fovy = tan_fovy;
-    b.focal_y = height / (2.0f * tan_fovy);
-    b.focal_x = width / (2.0f * tan_fovx);
-    b.sh_vec_ok = aligned16(shs) && aligned16(dL_dsh);
-    b.track_off = track_off; b.map_off = map_off; b.geom = geom; b.acc = sc.acc; b.clear_scratch = scratch_clean ? 1 : 0;
-    b.dL_dmean2D = dL_dmean2D; b.dL_dconic = dL_dconic; b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor;
-    b.dL_ddepth = dL_ddepth; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
-    b.dL_dscale = dL_dscale; b.dL_drot = dL_drot; b.pose_part = sc.pose_part; b.ticket = sc.ticket; b.dL_dview = dL_dview;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st, complete)); }
-    if (debug && !dgr_stream_is_capturing(stream)) HIP_TRY(hipStreamSynchronize(st));  // (CHECK_CUDA(..., debug); a capturing stream cannot be waited for -- and the attempt would invalidate the capture)
-    return DGR_OK;
-}
 int dgr_light_backward(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
                        const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
                        const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
@@ -939,12 +1090,13 @@ int dgr_light_backward(void* stream, int P, int D, int M, int R, const float* ba
                        float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
                        const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
                        const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes) {
-    return light_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales,
-                               scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                               geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dpix_median_depth,
-                               dL_dpix_depth_var, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D,
-                               dL_dsh, dL_dscale, dL_drot, debug, dgndcs_dviewmatrix, perspec_matrix, dL_dview, dg_camd_dviewmatrix,
-                               gt_depth, track_off, map_off, scratch, scratch_bytes, nullptr);
+    return dgr_light_backward_absgrad(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales,
+                                      scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                                      radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth,
+                                      dL_dpix_median_depth, dL_dpix_depth_var, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                                      dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, dgndcs_dviewmatrix,
+                                      perspec_matrix, dL_dview, dg_camd_dviewmatrix, gt_depth, track_off, map_off, scratch,
+                                      scratch_bytes, nullptr);
 }
 int dgr_light_backward_absgrad(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
                                const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
@@ -957,12 +1109,15 @@ int dgr_light_backward_absgrad(void* stream, int P, int D, int M, int R, const f
                                float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
                                const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
                                const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes, float* dL_dmean2D_abs) {
-    return light_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales,
-                               scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
-                               geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth, dL_dpix_median_depth,
-                               dL_dpix_depth_var, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepth, dL_dmean3D, dL_dcov3D,
-                               dL_dsh, dL_dscale, dL_drot, debug, dgndcs_dviewmatrix, perspec_matrix, dL_dview, dg_camd_dviewmatrix,
-                               gt_depth, track_off, map_off, scratch, scratch_bytes, dL_dmean2D_abs);
+    (void)dgndcs_dviewmatrix; (void)dg_camd_dviewmatrix; (void)colors_precomp;
+    dgr::PreprocessBwdArgs b = bwd_scene(P, D, M, width, height, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                                         tan_fovx, tan_fovy, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                         dL_drot, track_off, map_off, 0);
+    b.dL_dconic = dL_dconic; b.dL_ddepth = dL_ddepth;
+    const BwdView w{geom_buffer, binning_buffer, image_buffer, viewmatrix, projmatrix, campos, perspec_matrix, gt_depth, radii,
+                    alphas, dL_dpix, dL_dpix_depth, dL_dpix_median_depth, dL_dpix_depth_var, nullptr, nullptr, dL_dmean2D, dL_dview,
+                    dL_dmean2D_abs, scratch, scratch_bytes, R};
+    return backward_one((hipStream_t)stream, b, background, w, debug);
 }
 
 // ------------------------------------------------------------------------------------------------ full variant
@@ -973,32 +1128,10 @@ int dgr_full_forward_presized(void* stream, char* geometry_buffer, char* binning
                               const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                               const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                               float* out_depth, const float* gt_depth, float* out_uncertainty, int* radii) {
-    hipStream_t st = (hipStream_t)stream;
     FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
                 cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
                 out_color, out_depth, nullptr, out_uncertainty, gt_depth, nullptr, nullptr, nullptr, radii};
-    ArmedReport armed(width, height, P, st);  // (dgr_status_arm: completed from the host on every path that enqueues no binning kernel)
-    int rc = check_common(c);
-    if (rc) return rc;
-    if (P == 0) {
-        if (status) HIP_TRY(hipMemsetAsync(status, 0, 16, st));
-        return zero_outputs(c, st);
-    }
-    // (the binning buffer also holds the segment binning's tables behind its per-instance arrays: dgr_binning_bytes() is
-    //  non-zero for a capacity of 0, and a NULL buffer is never valid for P > 0)
-    if (!geometry_buffer || !image_buffer || !binning_buffer || binning_capacity < 0) {
-        g_last_error = "presized forward: geometry, binning and image buffers are required (sizes: dgr_*_bytes)";
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    dgr::GeometryView geom = dgr::carve_geometry(geometry_buffer, P);
-    dgr::ImageView img = dgr::carve_image(image_buffer, width, height);
-    if (status) img.status = status;  // the kernels write the caller's status word directly
-    dgr::BinningView bin = dgr::carve_binning(binning_buffer, (size_t)binning_capacity);
-    const int mode = presized_count_mode(width, height, binning_capacity);
-    if ((rc = forward_front(c, geom, img, st, &bin, binning_capacity, image_buffer, mode))) return rc;
-    if ((rc = binning_stages(c, geom, img, bin, binning_capacity, st, mode, binning_buffer, &armed))) return rc;
-    if ((rc = forward_back_full(c, out_uncertainty, geom, img, bin, st, &armed))) return rc;
-    return DGR_OK;
+    return forward_presized((hipStream_t)stream, c, geometry_buffer, binning_buffer, binning_capacity, image_buffer, status, true);
 }
 
 int dgr_full_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn binningBuffer, dgr_alloc_fn imageBuffer,
@@ -1008,125 +1141,13 @@ int dgr_full_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn bin
                      const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
                      float tan_fovy, int prefiltered, float* out_color, float* out_depth, const float* gt_depth,
                      float* out_uncertainty, int* radii, int* num_related_primitives) {
-    hipStream_t st = (hipStream_t)stream;
     FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
                 cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
                 out_color, out_depth, nullptr, out_uncertainty, gt_depth, nullptr, nullptr, nullptr, radii};
-    if (num_related_primitives) *num_related_primitives = 0;
-    int rc = check_common(c);
-    if (rc) return rc;
-    // The callback entry points block the host to size the binning buffer, as the reference does (rasterizer_impl.cu:287): on a
-    // capturing stream that synchronisation would fail AND invalidate the capture -- refuse before anything touches the stream.
-    if (dgr_stream_is_capturing(stream)) {
-        g_last_error = "the resize-callback forward blocks the host (it sizes the binning buffer): it cannot be captured into a graph -- use the presized entry point";
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    if (P == 0) return zero_outputs(c, st);
-    char* gptr = geometryBuffer(dgr_geometry_bytes(P), alloc_user);
-    char* iptr = imageBuffer(dgr_image_bytes(width, height), alloc_user);
-    if (!gptr || !iptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
-    dgr::GeometryView geom = dgr::carve_geometry(gptr, P);
-    dgr::ImageView img = dgr::carve_image(iptr, width, height);
-    if ((rc = forward_front(c, geom, img, st))) return rc;
-    int status[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));  // first blocking read of the reference (F/cuda_rasterizer/rasterizer_impl.cu:435)
-    if (status[2]) { g_last_error = "Point is filtered although prefiltered is set. This shouldn't happen!"; return DGR_ERR_PREFILTERED; }
-    const int R = status[0];
-    char* bptr = nullptr;
-    if (R > 0) {
-        bptr = binningBuffer(dgr_binning_bytes(R, width, height), alloc_user);
-        if (!bptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
-    } else {
-        binningBuffer(0, alloc_user);
-    }
-    dgr::BinningView bin = dgr::carve_binning(bptr, (size_t)R);
-    // (also with R == 0: it writes the (empty) range table)
-    const int mode = (R > 0 && presized_count_mode(width, height, R) == COUNT_LDS) ? COUNT_LDS_CALLBACK : COUNT_CALLBACK;
-    if ((rc = binning_stages(c, geom, img, bin, R, st, mode, bptr))) return rc;
-    if ((rc = forward_back_full(c, out_uncertainty, geom, img, bin, st))) return rc;
-    if (num_related_primitives) {  // second blocking read of the reference (:498)
-        HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *num_related_primitives = status[3];
-    }
-    return R;
+    return forward_callback((hipStream_t)stream, c, geometryBuffer, binningBuffer, imageBuffer, alloc_user, true,
+                            num_related_primitives, 0);
 }
 
-static int full_backward_impl(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
-                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
-                              float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                              char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                              const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                              float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
-                              const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
-                              float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
-                              float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
-                              size_t scratch_bytes,
-                              float* dL_dmean2D_abs) {
-    (void)colors_precomp; (void)dpixel_dgc; (void)gau_id_list; (void)pix_id_list; (void)dgc_dCam_position;
-    (void)dpixel_dndcs; (void)dgndcs_dviewmatrix; (void)dpixel_dinvcovs; (void)dgc_invcovs_dT; (void)ddepth_dndcs;
-    (void)ddepth_dinvcovs;
-    if (int rc = absgrad_refused(dL_dmean2D_abs != nullptr, 0)) return rc;
-    const bool det = opt_det_grads() != 0;  // (round 9: the scheme of the light variant, csrc/render_light.hip: DET)
-    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
-    if (det && R <= 0) { g_last_error = "deterministic_grads: the backward needs R >= num_rendered (it sizes the instance-major row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
-    hipStream_t st = (hipStream_t)stream;
-    const bool scratch_clean = g_scratch_clean_armed;
-    g_scratch_clean_armed = false;
-    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
-    if (P == 0) {
-        HIP_TRY(hipMemsetAsync(dL_dview, 0, 16 * 4, st));
-        return DGR_OK;
-    }
-    if (scratch_bytes < dgr_light_backward_scratch_bytes_r(P, width, height, R) || !scratch) {
-        g_last_error = det ? "backward scratch too small (deterministic_grads: dgr_light_backward_scratch_bytes_r)" : "backward scratch too small";
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    // (the 3D covariance is not kept by the forward: the backward re-forms it from scale and rotation -- the SAME tensors the
-    //  forward saw, or the bits differ -- unless the caller precomputed it)
-    if (!cov3D_precomp && (!scales || !rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
-    if (!geom_buffer || !binning_buffer || !image_buffer) { g_last_error = "backward: the forward's three state buffers are required"; return DGR_ERR_BAD_ARGUMENT; }
-    dgr::GeometryView geom = dgr::carve_geometry(geom_buffer, P);
-    dgr::ImageView img = dgr::carve_image(image_buffer, width, height);
-    dgr::BackwardScratch sc = dgr::carve_backward_scratch(scratch, P);
-    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
-    if (!scratch_clean) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, st)); }
-    if (dL_dmean2D_abs) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_floats(dL_dmean2D_abs, 3 * (size_t)P, st)); }
-    DetScratch ds{nullptr, nullptr, nullptr, 0};
-    if (det) {
-        ds = carve_det_scratch(scratch, P, R);
-        { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_fill(ds.rows, sizeof(float) * DGR_ACC_STRIDE * (size_t)R, st)); }
-        HIP_TRY(dgr::launch_det_offsets(P, geom.rect, ds.blk, geom.goff, st));
-    }
-
-    dgr::RenderBwdFullArgs r{};
-    r.W = width; r.H = height; r.grid_x = gx; r.grid_y = gy;
-    r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = (const uint32_t*)binning_buffer; r.rec = geom.rec; r.bg = background;
-    r.gt_depth = gt_depth; r.final_T = img.final_T; r.n_contrib = img.n_contrib; r.first_contrib = img.first_contrib;
-    r.dL_dpix = dL_dpix; r.dL_depths = dL_depths; r.dL_duncertainties = dL_duncertainties; r.acc = sc.acc;
-    if (det) { r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)R; }
-    if (dL_dmean2D_abs) { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_full_abs(r, dL_dmean2D_abs, opt_alpha_mode(), st)); }
-    else { ScopedStage t(ST_RENDER_BWD, st); HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), st, det)); }
-    if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)R, sc.acc, st));
-
-    dgr::PreprocessBwdArgs b{};
-    b.det_pose = det ? ds.pose : nullptr;
-    b.P = P; b.D = D; b.M = M; b.means3D = means3D; b.radii = radii ? radii : geom.radii; b.shs = shs; b.scales = scales;
-    b.rotations = rotations; b.scale_modifier = scale_modifier; b.cov3D_precomp = cov3D_precomp; b.view = viewmatrix;
-    b.proj = projmatrix; b.campos = campos; b.perspec = perspec_matrix; b.tan_fovx = tan_fovx; b.tan_fovy = tan_fovy;
-    b.focal_y = height / (2.0f * tan_fovy);
-    b.focal_x = width / (2.0f * tan_fovx);
-    b.sh_vec_ok = aligned16(shs) && aligned16(dL_dsh);
-    b.track_off = 0; b.map_off = 0; b.full_variant = 1; b.geom = geom; b.acc = sc.acc; b.clear_scratch = scratch_clean ? 1 : 0;
-    b.dL_dmean2D = dL_dmean2D; b.dL_dconic = dL_dconic; b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor;
-    b.dL_ddepth = dL_dgau_depth; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
-    b.dL_dscale = dL_dscale; b.dL_drot = dL_drot; b.pose_part = sc.pose_part; b.ticket = sc.ticket; b.dL_dview = dL_dview;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st, opt_pose_grad() != 0)); }
-    return DGR_OK;
-}
 int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
                       const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
                       float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
@@ -1139,13 +1160,13 @@ int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* bac
                       float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
                       float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
                       size_t scratch_bytes) {
-    return full_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
-                              rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
-                              binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
-                              dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dpixel_dgc, gau_id_list, pix_id_list,
-                              dgc_dCam_position, dpixel_dndcs, perspec_matrix, dgndcs_dviewmatrix, dpixel_dinvcovs, dgc_invcovs_dT,
-                              dL_dview, dL_dgau_depth, ddepth_dndcs, ddepth_dinvcovs, gt_depth, dL_duncertainties, scratch,
-                              scratch_bytes, nullptr);
+    return dgr_full_backward_absgrad(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                     scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                                     radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dconic,
+                                     dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dpixel_dgc,
+                                     gau_id_list, pix_id_list, dgc_dCam_position, dpixel_dndcs, perspec_matrix, dgndcs_dviewmatrix,
+                                     dpixel_dinvcovs, dgc_invcovs_dT, dL_dview, dL_dgau_depth, ddepth_dndcs, ddepth_dinvcovs,
+                                     gt_depth, dL_duncertainties, scratch, scratch_bytes, nullptr);
 }
 int dgr_full_backward_absgrad(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
                               const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
@@ -1159,13 +1180,17 @@ int dgr_full_backward_absgrad(void* stream, int P, int D, int M, int R, const fl
                               float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
                               float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
                               size_t scratch_bytes, float* dL_dmean2D_abs) {
-    return full_backward_impl(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
-                              rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
-                              binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
-                              dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dpixel_dgc, gau_id_list, pix_id_list,
-                              dgc_dCam_position, dpixel_dndcs, perspec_matrix, dgndcs_dviewmatrix, dpixel_dinvcovs, dgc_invcovs_dT,
-                              dL_dview, dL_dgau_depth, ddepth_dndcs, ddepth_dinvcovs, gt_depth, dL_duncertainties, scratch,
-                              scratch_bytes, dL_dmean2D_abs);
+    (void)colors_precomp; (void)dpixel_dgc; (void)gau_id_list; (void)pix_id_list; (void)dgc_dCam_position;
+    (void)dpixel_dndcs; (void)dgndcs_dviewmatrix; (void)dpixel_dinvcovs; (void)dgc_invcovs_dT; (void)ddepth_dndcs;
+    (void)ddepth_dinvcovs;
+    dgr::PreprocessBwdArgs b = bwd_scene(P, D, M, width, height, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                                         tan_fovx, tan_fovy, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                         dL_drot, 0, 0, 1);
+    b.dL_dconic = dL_dconic; b.dL_ddepth = dL_dgau_depth;
+    const BwdView w{geom_buffer, binning_buffer, image_buffer, viewmatrix, projmatrix, campos, perspec_matrix, gt_depth, radii,
+                    nullptr, dL_dpix, nullptr, nullptr, nullptr, dL_depths, dL_duncertainties, dL_dmean2D, dL_dview,
+                    dL_dmean2D_abs, scratch, scratch_bytes, R};
+    return backward_one((hipStream_t)stream, b, background, w, 0);
 }
 
 int dgr_light_forward_batch(void* stream, int n_views, const dgr_light_view* views, int P, int D, int M,
@@ -1204,109 +1229,16 @@ int dgr_full_forward_batch(void* stream, int n_views, const dgr_full_view* views
     return forward_batch((hipStream_t)stream, n_views, cv, bs, true);
 }
 
-static int light_backward_batch_impl(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
-                                     const float* background, int width, int height, const float* means3D, const float* shs,
-                                     const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                                     const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
-                                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                                     int track_off, int map_off,
-                                     float* const* dL_dmean2D_abs) {
-    (void)colors_precomp;
-    hipStream_t st = (hipStream_t)stream;
-    const bool det = opt_det_grads() != 0 && !(track_off && map_off);  // (round 9: per view the scheme of the one-view backward)
-    const bool complete = opt_pose_grad() != 0 && !track_off;           // (as the one-view backward: the mapping blend under map_off)
-    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
-    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
-    bool any_abs = false;  // (absgrad: a NULL array or NULL entries -- those views as without it)
-    for (int v = 0; dL_dmean2D_abs && v < n_views; v++) any_abs |= dL_dmean2D_abs[v] != nullptr;
-    if (int rc = absgrad_refused(any_abs, map_off)) return rc;
-    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
-    for (int v = 0; v < n_views; v++)
-        if (!views[v].dL_dview) { g_last_error = "view without dL_dview"; return DGR_ERR_BAD_ARGUMENT; }
-    if (P > 0 && !cov3D_precomp && (!scales || !rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
-    if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
-        for (int v = 0; v < n_views; v++) HIP_TRY(hipMemsetAsync(views[v].dL_dview, 0, 16 * 4, st));
-        return DGR_OK;
-    }
-    for (int v = 0; v < n_views; v++) {
-        const dgr_light_view_grad& w = views[v];
-        if (det && w.num_rendered <= 0) { g_last_error = "deterministic_grads: every view needs num_rendered (it sizes the view's row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
-        const size_t need = dgr_light_backward_scratch_bytes_r(P, width, height, w.num_rendered);
-        if (!w.scratch || w.scratch_bytes < need) { g_last_error = "backward scratch too small"; return DGR_ERR_BAD_ARGUMENT; }
-        if (!w.geometry_buffer || !w.image_buffer || !w.viewmatrix || !w.projmatrix || !w.cam_pos || !w.perspec_matrix || !w.alphas ||
-            !w.dL_dpix || !w.dL_dpix_depth || !w.dL_dpix_median_depth || !w.dL_dpix_depth_var) {
-            g_last_error = "view with a missing state buffer, camera or gradient image";
-            return DGR_ERR_BAD_ARGUMENT;
-        }
-    }
-    int rc;
-    if ((rc = batch_streams_ready())) return rc;
-    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
-    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
-    const int K = pipeline ? 2 : batch_stream_count(n_views);
-    dgr::PreprocessBwdBatchArgs bb{};
-    if ((rc = batch_fork(st, K))) return rc;
-    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
-    for (int v = 0; v < n_views; v++) {
-        const dgr_light_view_grad& w = views[v];
-        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
-        dgr::GeometryView geom = dgr::carve_geometry(w.geometry_buffer, P);
-        dgr::ImageView img = dgr::carve_image(w.image_buffer, width, height);
-        dgr::BackwardScratch sc = dgr::carve_backward_scratch(w.scratch, P);
-        { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, sv)); }
-        float* const ab = dL_dmean2D_abs ? dL_dmean2D_abs[v] : nullptr;
-        if (ab) { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_floats(ab, 3 * (size_t)P, sv)); }
-        if (pipeline) {  // the blend backward of view v on the caller's stream, behind its cleared scratch
-            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
-            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
-            sv = st;
-        }
-        dgr::RenderBwdLightArgs r{};
-        r.W = width; r.H = height; r.grid_x = gx; r.grid_y = gy;
-        r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = (const uint32_t*)w.binning_buffer; r.rec = geom.rec; r.bg = background;
-        r.gt_depth = w.gt_depth; r.alphas = w.alphas; r.n_contrib = img.n_contrib; r.dL_dpix = w.dL_dpix;
-        r.dL_dpix_depth = w.dL_dpix_depth; r.dL_dpix_median = w.dL_dpix_median_depth; r.dL_dpix_var = w.dL_dpix_depth_var;
-        r.means3D = means3D; r.view = w.viewmatrix; r.acc = sc.acc; r.track_off = track_off; r.map_off = complete ? 0 : map_off;
-        DetScratch ds{nullptr, nullptr, nullptr, 0};
-        if (det) {
-            ds = carve_det_scratch(w.scratch, P, w.num_rendered);
-            { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(ds.rows, sizeof(float) * DGR_ACC_STRIDE * (size_t)w.num_rendered, sv)); }
-            HIP_TRY(dgr::launch_det_offsets(P, geom.rect, ds.blk, geom.goff, sv));
-            r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)w.num_rendered;
-        }
-        if (ab) { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_light_abs(r, ab, opt_alpha_mode(), sv)); }
-        else { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_light(r, opt_alpha_mode(), sv)); }
-        if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)w.num_rendered, sc.acc, sv));
-        dgr::BwdViewPart& q = bb.v[v];
-        q.det_pose = det ? ds.pose : nullptr;
-        q.view = w.viewmatrix; q.proj = w.projmatrix; q.campos = w.cam_pos; q.perspec = w.perspec_matrix;
-        q.radii = w.radii ? w.radii : geom.radii; q.geom = geom; q.acc = sc.acc; q.dL_dmean2D = w.dL_dmean2D;
-        q.pose_part = sc.pose_part; q.ticket = sc.ticket; q.dL_dview = w.dL_dview;
-    }
-    if ((rc = joined.done())) return rc;
-    dgr::PreprocessBwdArgs& b = bb.base;
-    b.P = P; b.D = D; b.M = M; b.W = width; b.H = height; b.means3D = means3D; b.shs = shs; b.scales = scales;
-    b.rotations = rotations; b.scale_modifier = scale_modifier; b.cov3D_precomp = cov3D_precomp;
-    b.tan_fovx = tan_fovx; b.tan_fovy = tan_fovy;
-    b.focal_y = height / (2.0f * tan_fovy);
-    b.focal_x = width / (2.0f * tan_fovx);
-    b.sh_vec_ok = aligned16(shs) && aligned16(dL_dsh);
-    b.track_off = track_off; b.map_off = map_off;
-    b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
-    b.dL_dscale = dL_dscale; b.dL_drot = dL_drot;
-    bb.V = n_views;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st, complete)); }
-    return DGR_OK;
-}
 int dgr_light_backward_batch(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
                              const float* background, int width, int height, const float* means3D, const float* shs,
                              const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                              const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                              int track_off, int map_off) {
-    return light_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
-                                     scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
-                                     dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, track_off, map_off, nullptr);
+    return dgr_light_backward_batch_absgrad(stream, n_views, views, P, D, M, background, width, height, means3D, shs,
+                                            colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy,
+                                            dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, track_off,
+                                            map_off, nullptr);
 }
 int dgr_light_backward_batch_absgrad(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
                                      const float* background, int width, int height, const float* means3D, const float* shs,
@@ -1314,120 +1246,32 @@ int dgr_light_backward_batch_absgrad(void* stream, int n_views, const dgr_light_
                                      const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                                      float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                                      int track_off, int map_off, float* const* dL_dmean2D_abs) {
-    return light_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
-                                     scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
-                                     dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, track_off, map_off, dL_dmean2D_abs);
+    (void)colors_precomp;
+    const dgr::PreprocessBwdArgs b = bwd_scene(P, D, M, width, height, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                                               tan_fovx, tan_fovy, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                               dL_drot, track_off, map_off, 0);
+    return backward_batch_views((hipStream_t)stream, b, background, n_views, views, dL_dmean2D_abs);
 }
 
-static int full_backward_batch_impl(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
-                                    const float* background, int width, int height, const float* means3D, const float* shs,
-                                    const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
-                                    const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
-                                    float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
-                                    float* const* dL_dmean2D_abs) {
-    (void)colors_precomp;
-    hipStream_t st = (hipStream_t)stream;
-    const bool det = opt_det_grads() != 0;  // (per view the scheme of dgr_full_backward)
-    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
-    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
-    bool any_abs = false;  // (absgrad: a NULL array or NULL entries -- those views as without it)
-    for (int v = 0; dL_dmean2D_abs && v < n_views; v++) any_abs |= dL_dmean2D_abs[v] != nullptr;
-    if (int rc = absgrad_refused(any_abs, 0)) return rc;
-    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
-    for (int v = 0; v < n_views; v++)
-        if (!views[v].dL_dview) { g_last_error = "view without dL_dview"; return DGR_ERR_BAD_ARGUMENT; }
-    if (P > 0 && !cov3D_precomp && (!scales || !rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
-    if (P == 0) {  // F/rasterize_points.cu: nothing runs, gradients stay zero
-        for (int v = 0; v < n_views; v++) HIP_TRY(hipMemsetAsync(views[v].dL_dview, 0, 16 * 4, st));
-        return DGR_OK;
-    }
-    for (int v = 0; v < n_views; v++) {
-        const dgr_full_view_grad& w = views[v];
-        if (det && w.num_rendered <= 0) { g_last_error = "deterministic_grads: every view needs num_rendered (it sizes the view's row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
-        const size_t need = dgr_light_backward_scratch_bytes_r(P, width, height, w.num_rendered);
-        if (!w.scratch || w.scratch_bytes < need) { g_last_error = "backward scratch too small"; return DGR_ERR_BAD_ARGUMENT; }
-        // (the blend backward reads gt_depth on every path, the lean one included)
-        if (!w.geometry_buffer || !w.binning_buffer || !w.image_buffer || !w.viewmatrix || !w.projmatrix || !w.cam_pos ||
-            !w.perspec_matrix || !w.gt_depth || !w.dL_dpix || !w.dL_depths) {
-            g_last_error = "view with a missing state buffer, camera or gradient image";
-            return DGR_ERR_BAD_ARGUMENT;
-        }
-    }
-    int rc;
-    if ((rc = batch_streams_ready())) return rc;
-    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
-    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
-    const int K = pipeline ? 2 : batch_stream_count(n_views);
-    dgr::PreprocessBwdBatchArgs bb{};
-    if ((rc = batch_fork(st, K))) return rc;
-    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
-    for (int v = 0; v < n_views; v++) {
-        const dgr_full_view_grad& w = views[v];
-        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
-        dgr::GeometryView geom = dgr::carve_geometry(w.geometry_buffer, P);
-        dgr::ImageView img = dgr::carve_image(w.image_buffer, width, height);
-        dgr::BackwardScratch sc = dgr::carve_backward_scratch(w.scratch, P);
-        { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(sc.acc, sc.zero_bytes, sv)); }
-        float* const ab = dL_dmean2D_abs ? dL_dmean2D_abs[v] : nullptr;
-        if (ab) { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_floats(ab, 3 * (size_t)P, sv)); }
-        DetScratch ds{nullptr, nullptr, nullptr, 0};
-        if (det) {
-            ds = carve_det_scratch(w.scratch, P, w.num_rendered);
-            { ScopedStage t(ST_ZERO, sv); HIP_TRY(dgr::launch_zero_fill(ds.rows, sizeof(float) * DGR_ACC_STRIDE * (size_t)w.num_rendered, sv)); }
-            HIP_TRY(dgr::launch_det_offsets(P, geom.rect, ds.blk, geom.goff, sv));
-        }
-        if (pipeline) {  // the blend backward of view v on the caller's stream, behind its cleared scratch
-            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
-            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
-            sv = st;
-        }
-        dgr::RenderBwdFullArgs r{};
-        r.W = width; r.H = height; r.grid_x = gx; r.grid_y = gy;
-        r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = (const uint32_t*)w.binning_buffer; r.rec = geom.rec; r.bg = background;
-        r.gt_depth = w.gt_depth; r.final_T = img.final_T; r.n_contrib = img.n_contrib; r.first_contrib = img.first_contrib;
-        r.dL_dpix = w.dL_dpix; r.dL_depths = w.dL_depths; r.dL_duncertainties = w.dL_duncertainties; r.acc = sc.acc;
-        if (det) { r.det_rows = ds.rows; r.det_rect = geom.rect; r.det_goff = geom.goff; r.det_R = (uint32_t)w.num_rendered; }
-        if (ab) { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_full_abs(r, ab, opt_alpha_mode(), sv)); }
-        else { ScopedStage t(ST_RENDER_BWD, sv); HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), sv, det)); }
-        if (det) HIP_TRY(dgr::launch_det_gather(P, geom.rect, geom.goff, ds.rows, (uint32_t)w.num_rendered, sc.acc, sv));
-        dgr::BwdViewPart& q = bb.v[v];
-        q.det_pose = det ? ds.pose : nullptr;
-        q.view = w.viewmatrix; q.proj = w.projmatrix; q.campos = w.cam_pos; q.perspec = w.perspec_matrix;
-        q.radii = w.radii ? w.radii : geom.radii; q.geom = geom; q.acc = sc.acc; q.dL_dmean2D = w.dL_dmean2D;
-        q.pose_part = sc.pose_part; q.ticket = sc.ticket; q.dL_dview = w.dL_dview;
-    }
-    if ((rc = joined.done())) return rc;
-    dgr::PreprocessBwdArgs& b = bb.base;
-    b.P = P; b.D = D; b.M = M; b.W = width; b.H = height; b.means3D = means3D; b.shs = shs; b.scales = scales;
-    b.rotations = rotations; b.scale_modifier = scale_modifier; b.cov3D_precomp = cov3D_precomp;
-    b.tan_fovx = tan_fovx; b.tan_fovy = tan_fovy;
-    b.focal_y = height / (2.0f * tan_fovy);
-    b.focal_x = width / (2.0f * tan_fovx);
-    b.sh_vec_ok = aligned16(shs) && aligned16(dL_dsh);
-    b.track_off = 0; b.map_off = 0; b.full_variant = 1;
-    b.dL_dopacity = dL_dopacity; b.dL_dcolor = dL_dcolor; b.dL_dmean3D = dL_dmean3D; b.dL_dcov3D = dL_dcov3D; b.dL_dsh = dL_dsh;
-    b.dL_dscale = dL_dscale; b.dL_drot = dL_drot;
-    bb.V = n_views;
-    { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st, opt_pose_grad() != 0)); }
-    return DGR_OK;
-}
 int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
                             const float* background, int width, int height, const float* means3D, const float* shs,
                             const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                             const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                             float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot) {
-    return full_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
-                                    scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
-                                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr);
+    return dgr_full_backward_batch_absgrad(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
+                                           scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity,
+                                           dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr);
 }
 int dgr_full_backward_batch_absgrad(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
                                     const float* background, int width, int height, const float* means3D, const float* shs,
                                     const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                                     const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* const* dL_dmean2D_abs) {
-    return full_backward_batch_impl(stream, n_views, views, P, D, M, background, width, height, means3D, shs, colors_precomp,
-                                    scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy, dL_dopacity, dL_dcolor,
-                                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_dmean2D_abs);
+    (void)colors_precomp;
+    const dgr::PreprocessBwdArgs b = bwd_scene(P, D, M, width, height, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
+                                               tan_fovx, tan_fovy, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
+                                               dL_drot, 0, 0, 1);
+    return backward_batch_views((hipStream_t)stream, b, background, n_views, views, dL_dmean2D_abs);
 }
 
 int dgr_cov3d_forward(void* stream, int P, const float* scales, const float* rotations, float scale_modifier, float* cov3D) {

@@ -185,6 +185,10 @@ inline Tensor view_of(const Tensor& base, size_t byte_off, c10::IntArrayRef size
     }
     return mode ? raw_view(base, byte_off, sizes, dt) : dispatcher_view(base, byte_off, sizes, dt);
 }
+// row v of a [V, ...] tensor (NULL for an empty one)
+inline char* row_bytes(const Tensor& t, long v) { return t.numel() == 0 ? nullptr : reinterpret_cast<char*>(t.data_ptr()) + v * t.stride(0) * t.element_size(); }
+template <typename T>
+inline T* row(const Tensor& t, long v) { return reinterpret_cast<T*>(row_bytes(t, v)); }
 inline Tensor bytes_on(const c10::Device& dev, size_t n) {
     return at::empty({(long long)std::max<size_t>(n, 1)}, at::TensorOptions().dtype(at::kByte).device(dev));
 }
@@ -224,11 +228,71 @@ inline void strict_status(Run& run, long cap, int* s, void* st) {
     check(dgr_status_poll(ticket, 1, s));
 }
 
+// A forward's inputs as contiguous fp32 tensors on the Gaussians' device, under its device guard (one-view forwards: one camera;
+// batches: [V, ...] per camera)
+inline c10::Device forward_device(const Tensor& means3D) {
+    if (means3D.dim() != 2 || means3D.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
+    const c10::Device dev = means3D.device();
+    if (!dev.is_cuda()) throw std::runtime_error("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)");
+    return dev;
+}
+struct FwdInputs {
+    c10::Device dev;
+    c10::hip::HIPGuardMasqueradingAsCUDA guard;
+    int P, M;
+    Tensor means3D, bg, colors, opacity, scales, rotations, cov3D, view, proj, campos, gt, sh;
+    FwdInputs(const c10::Device& d, const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
+              const Tensor& scales_, const Tensor& rotations_, const Tensor& cov3D_, const Tensor& view_, const Tensor& gt_,
+              const Tensor& proj_, const Tensor& sh_, const Tensor& campos_)
+        : dev(d), guard(d), P((int)means3D_.size(0)), means3D(f32c(means3D_, d)), bg(f32c(background, d)), colors(f32c(colors_, d)),
+          opacity(f32c(opacity_, d)), scales(f32c(scales_, d)), rotations(f32c(rotations_, d)), cov3D(f32c(cov3D_, d)),
+          view(f32c(view_, d)), proj(f32c(proj_, d)), campos(f32c(campos_, d)), gt(f32c(gt_, d)), sh(f32c(sh_, d)) {
+        M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    }
+};
+
 // mode: 0 = callback entry point (the strict mirror: allocation callbacks + the reference's blocking read),
 //       1 = presized, strict: one host wait until num_rendered is known; retries a too-small capacity itself,
 //       2 = presized, lazy: no host synchronisation; returns a status ticket (dgr_status_post) or -1 while capturing.
-struct LightFwd {
+struct FwdCounts {
     long rendered = -1, ticket = -1, cap = 0;
+};
+// Modes 1 and 2 around `run(cap)`: the variant's state allocation and presized entry point
+template <typename Run>
+void presized_forward(Run& run, long capacity, long mode, void* st, FwdCounts& o) {
+    if (mode == 2) {
+        // the status word comes back through pinned host memory written by the binning kernel (dgr_status_arm): no copy, no
+        // event; while a hipGraph is being recorded nothing can be read back
+        {
+            Probe p_arm(HP_ARM);
+            if (!dgr_stream_is_capturing(st)) {
+                o.ticket = dgr_status_arm();
+                check(o.ticket);
+            }
+        }
+        try {
+            run(capacity);
+        } catch (...) {
+            int unused[4];
+            if (o.ticket >= 0) (void)dgr_status_poll(o.ticket, 1, unused);  // (completed by the library: releases the slot)
+            throw;
+        }
+        o.cap = capacity;
+        return;
+    }
+    long cap = capacity;
+    for (;;) {
+        int s[4] = {0, 0, 0, 0};
+        strict_status(run, cap, s, st);  // the one host wait of this forward: until num_rendered is known
+        if (s[2]) throw std::runtime_error("Point is filtered although prefiltered is set. This shouldn't happen!");
+        o.rendered = s[0];
+        if (o.rendered <= cap) break;
+        cap = (long)(o.rendered * 1.1) + 4096;  // overflow: every tile list was left empty; run again
+    }
+    o.cap = cap;
+}
+
+struct LightFwd : FwdCounts {
     Tensor status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px;
 };
 LightFwd light_forward_core(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
@@ -236,17 +300,11 @@ LightFwd light_forward_core(const Tensor& background, const Tensor& means3D_, co
                             const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
                             double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_,
                             bool prefiltered, bool debug, long capacity, long mode) {
-    if (means3D_.dim() != 2 || means3D_.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
-    const c10::Device dev = means3D_.device();
-    if (!dev.is_cuda()) throw std::runtime_error("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)");
     Probe p_pre(HP_PRELUDE);
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 opacity = f32c(opacity_, dev), scales = f32c(scales_, dev), rotations = f32c(rotations_, dev),
-                 cov3D = f32c(cov3D_, dev), view = f32c(viewmatrix_, dev), proj = f32c(projmatrix_, dev),
-                 campos = f32c(campos_, dev), gt = f32c(gt_depth_, dev), sh = f32c(sh_, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    const FwdInputs in(forward_device(means3D_), background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrix_,
+                       gt_depth_, projmatrix_, sh_, campos_);
+    const c10::Device dev = in.dev;
+    const int P = in.P, M = in.M;
     keep_until_read(dev, {&means3D_, &background, &colors_, &opacity_, &scales_, &rotations_, &cov3D_, &viewmatrix_, &projmatrix_,
                           &campos_, &gt_depth_, &sh_});
     const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
@@ -273,12 +331,12 @@ LightFwd light_forward_core(const Tensor& background, const Tensor& means3D_, co
     if (mode == 0 || P == 0) {
         o.geom = at::empty({0}, u8); o.binning = at::empty({0}, u8); o.img = at::empty({0}, u8);
         Alloc3 al{{&o.geom, dev}, {&o.binning, dev}, {&o.img, dev}};
-        const int rc = dgr_light_forward(st, cb_geom, cb_binning, cb_img, &al, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
-                                         ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(opacity),
-                                         ptr<float>(scales), (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D),
-                                         ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
+        const int rc = dgr_light_forward(st, cb_geom, cb_binning, cb_img, &al, P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
+                                         ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
+                                         ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
+                                         ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx,
                                          (float)tan_fovy, prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth),
-                                         ptr<float>(o.median), ptr<float>(o.alpha), ptr<float>(gt), ptr<float>(o.var),
+                                         ptr<float>(o.median), ptr<float>(o.alpha), ptr<float>(in.gt), ptr<float>(o.var),
                                          ptr<float>(o.unc), ptr<int>(o.px), ptr<int>(o.radii), debug ? 1 : 0);
         check(rc);
         o.rendered = o.cap = rc;
@@ -291,45 +349,16 @@ LightFwd light_forward_core(const Tensor& background, const Tensor& means3D_, co
         p_st.stop();
         Probe p_c(HP_FWD_C);
         check(dgr_light_forward_presized(st, (char*)o.geom.data_ptr(), (char*)o.binning.data_ptr(), (int)cap, (char*)o.img.data_ptr(),
-                                         o.status.data_ptr<int>(), P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
-                                         ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(opacity),
-                                         ptr<float>(scales), (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D),
-                                         ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
+                                         o.status.data_ptr<int>(), P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
+                                         ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
+                                         ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
+                                         ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx,
                                          (float)tan_fovy, prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth),
-                                         ptr<float>(o.median), ptr<float>(o.alpha), ptr<float>(gt), ptr<float>(o.var),
+                                         ptr<float>(o.median), ptr<float>(o.alpha), ptr<float>(in.gt), ptr<float>(o.var),
                                          ptr<float>(o.unc), ptr<int>(o.px), ptr<int>(o.radii)));
     };
-    if (mode == 2) {
-        // the status word comes back through pinned host memory written by the binning kernel (dgr_status_arm): no copy, no
-        // event; while a hipGraph is being recorded nothing can be read back
-        {
-            Probe p_arm(HP_ARM);
-            if (!dgr_stream_is_capturing(st)) {
-                o.ticket = dgr_status_arm();
-                check(o.ticket);
-            }
-        }
-        try {
-            run(capacity);
-        } catch (...) {
-            int unused[4];
-            if (o.ticket >= 0) (void)dgr_status_poll(o.ticket, 1, unused);  // (completed by the library: releases the slot)
-            throw;
-        }
-        o.cap = capacity;
-        return o;
-    }
-    long cap = capacity;
-    for (;;) {
-        int s[4] = {0, 0, 0, 0};
-        strict_status(run, cap, s, st);  // the one host wait of this forward: until num_rendered is known
-        if (s[2]) throw std::runtime_error("Point is filtered although prefiltered is set. This shouldn't happen!");
-        o.rendered = s[0];
-        if (o.rendered <= cap) break;
-        cap = (long)(o.rendered * 1.1) + 4096;  // overflow: every tile list was left empty; run again
-    }
-    o.cap = cap;
-    if (debug) check(hipStreamSynchronize((hipStream_t)st) == hipSuccess ? 0 : DGR_ERR_HIP);
+    presized_forward(run, capacity, mode, st, o);
+    if (mode != 2 && debug) check(hipStreamSynchronize((hipStream_t)st) == hipSuccess ? 0 : DGR_ERR_HIP);
     return o;
 }
 
@@ -396,12 +425,37 @@ void drop_scratch(const c10::Device& dev, void* stream) {  // after a failed cal
     for (size_t i = 0; i < c.size();)
         if (c[i].device == dev.index() && c[i].stream == stream) c.erase(c.begin() + (long)i); else i++;
 }
+// A one-view backward's C ABI call `call(scratch)` on the scratch above: armed clean when the buffer is resident, dropped when the
+// call fails
+template <typename Call>
+void on_backward_scratch(const c10::Device& dev, void* st, size_t nscr, Call call) {
+    bool resident = false;
+    const Tensor scratch = backward_scratch(dev, st, nscr, &resident);
+    if (resident) dgr_backward_scratch_clean_arm();
+    const int rc = call((char*)scratch.data_ptr());
+    if (rc < 0 && resident) drop_scratch(dev, st);
+    check(rc);
+}
+
+// absgrad: a backward's results and, last, the absolute screen-space gradient [P,3] -- or, for a batch of V views, every view's
+// [V,P,3] (every row written).  `impl` takes the per-view output pointers.
+template <typename Impl>
+std::vector<Tensor> with_absgrad(const Tensor& means3D, long V, Impl impl) {
+    const long P = means3D.size(0);
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(means3D.device());
+    Tensor abs = V ? at::empty({V, P, 3}, f32) : at::empty({P, 3}, f32);
+    float* av[DGR_MAX_BATCH_VIEWS] = {};
+    for (long v = 0; v < std::max(V, 1L) && v < DGR_MAX_BATCH_VIEWS && P > 0; v++) av[v] = row<float>(abs, v);
+    std::vector<Tensor> g = impl(av);
+    g.push_back(std::move(abs));
+    return g;
+}
 
 // The flat arena of the eight per-Gaussian gradients (dgr_amd.light._grad_arena): segments in the order means3D, means2D,
 // sh, opacity, scales, rotations | cov3D, colors, 256-byte aligned; the first six are one contiguous span = the multi-GPU
 // all-reduce payload.  g[] receives them in the return order of the reference binding: means2D, colors, opacity, means3D,
 // cov3D, sh, scales, rotations.  Every row is written by the kernels (zeros for invisible Gaussians): no zero-fill.
-inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g) {
+inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g, float** gp) {
     const long long n[8] = {3LL * P, 3LL * P, 3LL * M * P, P, 3LL * P, 4LL * P, 6LL * P, 3LL * P};
     size_t off[8], o = 0;
     for (int i = 0; i < 8; i++) { off[i] = o; o += up256(4 * (size_t)n[i]); }
@@ -410,6 +464,7 @@ inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g) {
     g[5] = view_of(arena, off[2], {P, M, 3}, at::kFloat); g[2] = view_of(arena, off[3], {P, 1}, at::kFloat);
     g[6] = view_of(arena, off[4], {P, 3}, at::kFloat); g[7] = view_of(arena, off[5], {P, 4}, at::kFloat);
     g[4] = view_of(arena, off[6], {P, 6}, at::kFloat); g[1] = view_of(arena, off[7], {P, 3}, at::kFloat);
+    for (int i = 0; i < 8; i++) gp[i] = ptr<float>(g[i]);
 }
 
 // L/rasterize_points.cu:131-236.  Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
@@ -440,34 +495,27 @@ std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& 
     Probe p_al(HP_BWD_ALLOC);
     std::vector<Tensor> g(9);
     float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (need_gaussian_grads) {
-        grad_arena(dev, P, M, g.data());
-        for (int i = 0; i < 8; i++) gp[i] = ptr<float>(g[i]);
-    } else {
-        map_off = true;  // nobody reads the per-Gaussian sums: the blend kernel forms the three pose sums only
-    }
+    if (need_gaussian_grads) grad_arena(dev, P, M, g.data(), gp);
+    else map_off = true;  // nobody reads the per-Gaussian sums: the blend kernel forms the three pose sums only
     // scratch (accumulator rows, cleared by the backward's first launch) and, behind it, the [1,4,4] pose gradient -- what
     // L/__init__.py:160-161 sums over dim 0
     // (with the option "deterministic_grads" the scratch also holds 64 bytes per tile instance: R = num_rendered, or a lazy forward's capacity)
     const size_t nscr = up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)R));
     void* st = stream_of(dev);
-    bool resident = false;
-    const Tensor scratch = backward_scratch(dev, st, nscr, &resident);
-    Tensor dview = at::empty({1, 4, 4}, at::TensorOptions().dtype(at::kFloat).device(dev));
-    if (resident) dgr_backward_scratch_clean_arm();
-    p_al.stop();
-    Probe p_bc(HP_BWD_C);
-    const int rc = (dgr_light_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                             ptr<float>(sh), ptr<float>(colors), ptr<float>(alphas), ptr<float>(scales), (float)scale_modifier,
-                             ptr<float>(rotations), ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos),
-                             (float)tan_fovx, (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer),
-                             bytes(binningBuffer), bytes(imageBuffer), ptr<float>(gC),
-                             ptr<float>(gD), ptr<float>(gM), ptr<float>(gV), gp[0], nullptr, gp[2], gp[1], nullptr, gp[3], gp[4],
-                             gp[5], gp[6], gp[7], debug ? 1 : 0, nullptr, ptr<float>(perspec), dview.data_ptr<float>(), nullptr,
-                             ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, (char*)scratch.data_ptr(), nscr, abs_out));
-    if (rc < 0 && resident) drop_scratch(dev, st);
-    check(rc);
-    g[8] = std::move(dview);
+    g[8] = at::empty({1, 4, 4}, at::TensorOptions().dtype(at::kFloat).device(dev));
+    on_backward_scratch(dev, st, nscr, [&](char* scratch) {
+        p_al.stop();
+        Probe p_bc(HP_BWD_C);
+        return dgr_light_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+                                          ptr<float>(sh), ptr<float>(colors), ptr<float>(alphas), ptr<float>(scales), (float)scale_modifier,
+                                          ptr<float>(rotations), ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos),
+                                          (float)tan_fovx, (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer),
+                                          bytes(binningBuffer), bytes(imageBuffer), ptr<float>(gC),
+                                          ptr<float>(gD), ptr<float>(gM), ptr<float>(gV), gp[0], nullptr, gp[2], gp[1], nullptr,
+                                          gp[3], gp[4],
+                                          gp[5], gp[6], gp[7], debug ? 1 : 0, nullptr, ptr<float>(perspec), g[8].data_ptr<float>(), nullptr,
+                                          ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, scratch, nscr, abs_out);
+    });
     return g;
 }
 #define DGR_LIGHT_BWD_PARAMS                                                                                                         \
@@ -482,20 +530,15 @@ std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& 
         dL_dout_color, dL_dout_depth, dL_dout_median, dL_dout_var, gt_depth, sh, degree, campos, geomBuffer, R, binningBuffer,    \
         imageBuffer, alphas, debug, perspec, track_off, map_off, need_gaussian_grads
 std::vector<Tensor> light_backward(DGR_LIGHT_BWD_PARAMS) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, nullptr); }
-// absgrad: light_backward's nine gradients and, tenth, the absolute screen-space gradient [P,3] (every row written)
 std::vector<Tensor> light_backward_absgrad(DGR_LIGHT_BWD_PARAMS) {
-    const long P = means3D.size(0);
-    Tensor abs = at::empty({P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D.device()));
-    std::vector<Tensor> g = light_backward_impl(DGR_LIGHT_BWD_ARGS, P > 0 ? abs.data_ptr<float>() : nullptr);
-    g.push_back(std::move(abs));
-    return g;
+    return with_absgrad(means3D, 0, [&](float* const* abs) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, abs[0]); });
 }
 
 
 // ------------------------------------------------------------------------------------------------ full variant
 // F/rasterize_points.cu:35-120.  Modes as light_forward_core.
-struct FullFwd {
-    long rendered = -1, related = -1, ticket = -1, cap = 0;
+struct FullFwd : FwdCounts {
+    long related = -1;
     Tensor status, color, depth, unc, radii, geom, binning, img;
 };
 FullFwd full_forward_core(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
@@ -503,16 +546,10 @@ FullFwd full_forward_core(const Tensor& background, const Tensor& means3D_, cons
                           const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
                           double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_,
                           bool prefiltered, long capacity, long mode, bool want_related = true) {
-    if (means3D_.dim() != 2 || means3D_.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
-    const c10::Device dev = means3D_.device();
-    if (!dev.is_cuda()) throw std::runtime_error("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)");
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 opacity = f32c(opacity_, dev), scales = f32c(scales_, dev), rotations = f32c(rotations_, dev),
-                 cov3D = f32c(cov3D_, dev), view = f32c(viewmatrix_, dev), proj = f32c(projmatrix_, dev),
-                 campos = f32c(campos_, dev), gt = f32c(gt_depth_, dev), sh = f32c(sh_, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    const FwdInputs in(forward_device(means3D_), background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrix_,
+                       gt_depth_, projmatrix_, sh_, campos_);
+    const c10::Device dev = in.dev;
+    const int P = in.P, M = in.M;
     keep_until_read(dev, {&means3D_, &background, &colors_, &opacity_, &scales_, &rotations_, &cov3D_, &viewmatrix_, &projmatrix_,
                           &campos_, &gt_depth_, &sh_});
     const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
@@ -530,11 +567,11 @@ FullFwd full_forward_core(const Tensor& background, const Tensor& means3D_, cons
         o.geom = at::empty({0}, u8); o.binning = at::empty({0}, u8); o.img = at::empty({0}, u8);
         Alloc3 al{{&o.geom, dev}, {&o.binning, dev}, {&o.img, dev}};
         int ng = 0;
-        const int rc = dgr_full_forward(st, cb_geom, cb_binning, cb_img, &al, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
-                                        ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(opacity),
-                                        ptr<float>(scales), (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D),
-                                        ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx, (float)tan_fovy,
-                                        prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(gt), ptr<float>(o.unc),
+        const int rc = dgr_full_forward(st, cb_geom, cb_binning, cb_img, &al, P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
+                                        ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
+                                        ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
+                                        ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx, (float)tan_fovy,
+                                        prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(in.gt), ptr<float>(o.unc),
                                         ptr<int>(o.radii), &ng);
         check(rc);
         o.rendered = o.cap = rc;
@@ -545,43 +582,15 @@ FullFwd full_forward_core(const Tensor& background, const Tensor& means3D_, cons
         const StateArena sa(dev, P, (int)W, (int)H, cap);
         o.geom = sa.geom; o.binning = sa.binning; o.img = sa.img;
         check(dgr_full_forward_presized(st, (char*)o.geom.data_ptr(), (char*)o.binning.data_ptr(), (int)cap, (char*)o.img.data_ptr(),
-                                        o.status.data_ptr<int>(), P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
-                                        ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(opacity),
-                                        ptr<float>(scales), (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D),
-                                        ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx, (float)tan_fovy,
-                                        prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(gt), ptr<float>(o.unc),
+                                        o.status.data_ptr<int>(), P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
+                                        ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
+                                        ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
+                                        ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx, (float)tan_fovy,
+                                        prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(in.gt), ptr<float>(o.unc),
                                         ptr<int>(o.radii)));
     };
-    if (mode == 2) {
-        // the status word comes back through pinned host memory written by the binning kernel (dgr_status_arm): no copy, no
-        // event; while a hipGraph is being recorded nothing can be read back
-        {
-            Probe p_arm(HP_ARM);
-            if (!dgr_stream_is_capturing(st)) {
-                o.ticket = dgr_status_arm();
-                check(o.ticket);
-            }
-        }
-        try {
-            run(capacity);
-        } catch (...) {
-            int unused[4];
-            if (o.ticket >= 0) (void)dgr_status_poll(o.ticket, 1, unused);  // (completed by the library: releases the slot)
-            throw;
-        }
-        o.cap = capacity;
-        return o;
-    }
-    long cap = capacity;
-    for (;;) {
-        int s[4] = {0, 0, 0, 0};
-        strict_status(run, cap, s, st);
-        if (s[2]) throw std::runtime_error("Point is filtered although prefiltered is set. This shouldn't happen!");
-        o.rendered = s[0];
-        if (o.rendered <= cap) break;
-        cap = (long)(o.rendered * 1.1) + 4096;
-    }
-    o.cap = cap;
+    presized_forward(run, capacity, mode, st, o);
+    if (mode == 2) return o;
     // num_related (the reference's NG) is produced by the forward blend: the reference's second blocking read
     // (F/cuda_rasterizer/rasterizer_impl.cu:498) -- a wait for the whole forward.  The `_C.rasterize_gaussians` mirror returns the
     // number, as the reference's does; the autograd node does not wait for it: NG only sizes the reference's pair lists in ITS
@@ -627,28 +636,23 @@ std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& m
     keep_until_read(dev, {&dL_dout_color, &dL_dout_depth, &dL_dout_unc, &perspec_});
     std::vector<Tensor> g(9);
     float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (need_gaussian_grads) {
-        grad_arena(dev, P, M, g.data());
-        for (int i = 0; i < 8; i++) gp[i] = ptr<float>(g[i]);
-    }
-    Tensor dview = at::empty({4, 4}, at::TensorOptions().dtype(at::kFloat).device(dev));
+    if (need_gaussian_grads) grad_arena(dev, P, M, g.data(), gp);
+    g[8] = at::empty({4, 4}, at::TensorOptions().dtype(at::kFloat).device(dev));
     const size_t nscr = up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)R));  // (deterministic_grads: + rows per instance)
     void* st = stream_of(dev);
-    bool resident = false;
-    const Tensor scratch = backward_scratch(dev, st, nscr, &resident);
-    if (resident) dgr_backward_scratch_clean_arm();
     // gp: [0] means2D [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    const int rc = (dgr_full_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                            ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier, ptr<float>(rotations),
-                            ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
-                            (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer), bytes(binningBuffer), bytes(imageBuffer),
-                            ptr<float>(gC), ptr<float>(gD), gp[0], nullptr, gp[2], gp[1], gp[3], gp[4], gp[5], gp[6], gp[7], nullptr,
-                            nullptr, nullptr, nullptr, nullptr, ptr<float>(perspec), nullptr, nullptr, nullptr,
-                            dview.data_ptr<float>(), nullptr, nullptr, nullptr, ptr<float>(gt), ptr<float>(gU),
-                            (char*)scratch.data_ptr(), nscr, abs_out));
-    if (rc < 0 && resident) drop_scratch(dev, st);
-    check(rc);
-    g[8] = std::move(dview);
+    on_backward_scratch(dev, st, nscr, [&](char* scratch) {
+        return dgr_full_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+                                         ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
+                                         ptr<float>(rotations),
+                                         ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
+                                         (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer), bytes(binningBuffer), bytes(imageBuffer),
+                                         ptr<float>(gC), ptr<float>(gD), gp[0], nullptr, gp[2], gp[1], gp[3], gp[4], gp[5], gp[6],
+                                         gp[7], nullptr,
+                                         nullptr, nullptr, nullptr, nullptr, ptr<float>(perspec), nullptr, nullptr, nullptr,
+                                         g[8].data_ptr<float>(), nullptr, nullptr, nullptr, ptr<float>(gt), ptr<float>(gU),
+                                         scratch, nscr, abs_out);
+    });
     return g;
 }
 #define DGR_FULL_BWD_PARAMS                                                                                                          \
@@ -662,13 +666,8 @@ std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& m
         tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_unc, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, NG,   \
         perspec, need_gaussian_grads
 std::vector<Tensor> full_backward(DGR_FULL_BWD_PARAMS) { return full_backward_impl(DGR_FULL_BWD_ARGS, nullptr); }
-// absgrad: full_backward's nine gradients and, tenth, the absolute screen-space gradient [P,3] (every row written)
 std::vector<Tensor> full_backward_absgrad(DGR_FULL_BWD_PARAMS) {
-    const long P = means3D.size(0);
-    Tensor abs = at::empty({P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D.device()));
-    std::vector<Tensor> g = full_backward_impl(DGR_FULL_BWD_ARGS, P > 0 ? abs.data_ptr<float>() : nullptr);
-    g.push_back(std::move(abs));
-    return g;
+    return with_absgrad(means3D, 0, [&](float* const* abs) { return full_backward_impl(DGR_FULL_BWD_ARGS, abs[0]); });
 }
 
 // ------------------------------------------------------------------------------------------------ autograd nodes
@@ -720,8 +719,15 @@ struct FwdReport {
 };
 thread_local FwdReport g_report;
 
-inline Tensor zeros_like_image(long c, long H, long W, const c10::Device& dev) {
-    return at::zeros({c, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev));
+// an output that did not take part in the loss arrives undefined: zeros, as the reference's autograd would have passed
+inline Tensor grad_or_zeros(const Tensor& g, long c, long H, long W, const c10::Device& dev) {
+    return g.defined() ? g : at::zeros({c, H, W}, at::TensorOptions().dtype(at::kFloat).device(dev));
+}
+// (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp): tracking needs none
+inline bool needs_gaussian_grads(AutogradContext* ctx) {
+    bool need = false;
+    for (int i = 0; i < 8; i++) need = need || ctx->needs_input_grad(i);
+    return need;
 }
 
 // a block under a word of dgr_thread_options_effective() (include/dgr_hip.h): a backward under its forward's options
@@ -730,6 +736,16 @@ struct UnderOptions {
     explicit UnderOptions(int word) : prev(dgr_thread_options_swap(word)) {}
     ~UnderOptions() { dgr_thread_options_swap(prev); }
 };
+
+// A backward's gradients (means2D, colors, opacity, means3D, cov3D, sh, scales, rotations, dL_dview [4,4]) in the order of the
+// nodes' inputs (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix); None for the rest
+variable_list node_grads(std::vector<Tensor>& g, size_t n_inputs) {
+    variable_list out(n_inputs);
+    out[0] = std::move(g[3]); out[1] = std::move(g[0]); out[2] = std::move(g[5]); out[3] = std::move(g[1]);
+    out[4] = std::move(g[2]); out[5] = std::move(g[6]); out[6] = std::move(g[7]); out[7] = std::move(g[4]);
+    out[8] = std::move(g[8]);
+    return out;
+}
 
 struct LightNode : public torch::autograd::Function<LightNode> {
     // inputs 0..9 as L/__init__.py:46-60; then the settings' tensors and scalars (L/__init__.py:180-195) and the binning policy
@@ -770,28 +786,20 @@ struct LightNode : public torch::autograd::Function<LightNode> {
         const c10::Device dev = means3D.device();
         const long H = d["H"].toInt(), W = d["W"].toInt();
         p_u.stop();
-        // an output that did not take part in the loss arrives undefined: zeros, as the reference's autograd would have passed
-        const Tensor gC = grad[0].defined() ? grad[0] : zeros_like_image(3, H, W, dev);
-        const Tensor gD = grad[2].defined() ? grad[2] : zeros_like_image(1, H, W, dev);
+        const Tensor gC = grad_or_zeros(grad[0], 3, H, W, dev), gD = grad_or_zeros(grad[2], 1, H, W, dev);
         // (no gradient image for the median depth / the depth variance: NULL at the C ABI, which then runs the lean blend backward
         //  -- no zero images are made, filled and read)
         const Tensor gM = grad[3].defined() ? grad[3] : Tensor();
         const Tensor gV = grad[4].defined() ? grad[4] : Tensor();
-        bool need = false;  // (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp): tracking needs none
-        for (int i = 0; i < 8; i++) need = need || ctx->needs_input_grad(i);
         const UnderOptions under((int)d["options"].toInt());  // (the engine may run this node on a thread of its own)
         std::vector<Tensor> g = light_backward(sv[13], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4],
                                                sv[5], sv[14], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gM, gV, sv[12],
                                                sv[7], d["degree"].toInt(), sv[15], sv[8], d["R"].toInt(), sv[9], sv[10], sv[11], false,
-                                               sv[16], d["track_off"].toBool(), d["map_off"].toBool(), need);
+                                               sv[16], d["track_off"].toBool(), d["map_off"].toBool(), needs_gaussian_grads(ctx));
         consume_post_backward_wait(stream_of(dev));
         // the reference sums a [H*W,4,4] buffer over dim 0 (L/__init__.py:160-161); here it is [1,4,4], already reduced
-        Tensor gview = view_of(g[8], 0, {4, 4}, at::kFloat);
-        variable_list out(25);
-        out[0] = std::move(g[3]); out[1] = std::move(g[0]); out[2] = std::move(g[5]); out[3] = std::move(g[1]);
-        out[4] = std::move(g[2]); out[5] = std::move(g[6]); out[6] = std::move(g[7]); out[7] = std::move(g[4]);
-        out[8] = std::move(gview);
-        return out;
+        g[8] = view_of(g[8], 0, {4, 4}, at::kFloat);
+        return node_grads(g, 25);
     }
 };
 
@@ -844,22 +852,16 @@ struct FullNode : public torch::autograd::Function<FullNode> {
         const Tensor& means3D = sv[1];
         const c10::Device dev = means3D.device();
         const long H = d["H"].toInt(), W = d["W"].toInt();
-        const Tensor gC = grad[0].defined() ? grad[0] : zeros_like_image(3, H, W, dev);
-        const Tensor gD = grad[2].defined() ? grad[2] : zeros_like_image(1, H, W, dev);
+        const Tensor gC = grad_or_zeros(grad[0], 3, H, W, dev), gD = grad_or_zeros(grad[2], 1, H, W, dev);
         // (no gradient image for the uncertainty output: NULL at the C ABI, which then runs the lean blend backward)
         const Tensor gU = grad[3].defined() ? grad[3] : Tensor();
-        bool need = false;
-        for (int i = 0; i < 8; i++) need = need || ctx->needs_input_grad(i);
         const UnderOptions under((int)d["options"].toInt());
         std::vector<Tensor> g = full_backward(sv[12], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4], sv[5],
                                               sv[11], sv[13], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gU, sv[7],
-                                              d["degree"].toInt(), sv[14], sv[8], d["R"].toInt(), sv[9], sv[10], 0, sv[15], need);
+                                              d["degree"].toInt(), sv[14], sv[8], d["R"].toInt(), sv[9], sv[10], 0, sv[15],
+                                              needs_gaussian_grads(ctx));
         consume_post_backward_wait(stream_of(dev));
-        variable_list out(23);
-        out[0] = std::move(g[3]); out[1] = std::move(g[0]); out[2] = std::move(g[5]); out[3] = std::move(g[1]);
-        out[4] = std::move(g[2]); out[5] = std::move(g[6]); out[6] = std::move(g[7]); out[7] = std::move(g[4]);
-        out[8] = std::move(g[8]);
-        return out;
+        return node_grads(g, 23);
     }
 };
 
@@ -884,9 +886,22 @@ full_apply(const Tensor& means3D, const Tensor& means2D, const Tensor& sh, const
 // synchronisation; the capacity policy, the strict mode's status read and its retry stay in Python (dgr_amd/batch.py).
 // post_status: copy every view's status word to pinned memory behind an event (lazy mode) and return the tickets.
 // Returns ([V,4] status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px) and the tickets.
-inline char* row_bytes(const Tensor& t, long v) { return t.numel() == 0 ? nullptr : reinterpret_cast<char*>(t.data_ptr()) + v * t.stride(0) * t.element_size(); }
-template <typename T>
-inline T* row(const Tensor& t, long v) { return reinterpret_cast<T*>(row_bytes(t, v)); }
+inline long batch_size(long V) {
+    if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
+    return V;
+}
+// lazy mode: every view's status word copied to pinned memory behind an event; returns the tickets
+std::vector<long> post_batch_status(bool post_status, int P, void* st, const Tensor& status, long V) {
+    std::vector<long> tickets;
+    if (post_status && P > 0 && !dgr_stream_is_capturing(st)) {
+        for (long v = 0; v < V; v++) {
+            const long t = dgr_status_post(st, row<int>(status, v));
+            check(t);
+            tickets.push_back(t);
+        }
+    }
+    return tickets;
+}
 
 std::tuple<std::vector<Tensor>, std::vector<long>>
 light_forward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
@@ -894,18 +909,11 @@ light_forward_batch(const Tensor& background, const Tensor& means3D_, const Tens
                     const Tensor& viewmatrices_, const Tensor& gt_depths_, const Tensor& projmatrices_, double tan_fovx,
                     double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_, bool prefiltered,
                     long capacity, bool post_status) {
-    if (means3D_.dim() != 2 || means3D_.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
-    const c10::Device dev = means3D_.device();
-    if (!dev.is_cuda()) throw std::runtime_error("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)");
-    const long V = viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0;
-    if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 opacity = f32c(opacity_, dev), scales = f32c(scales_, dev), rotations = f32c(rotations_, dev),
-                 cov3D = f32c(cov3D_, dev), views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev),
-                 campos = f32c(campos_, dev), gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    const c10::Device dev = forward_device(means3D_);
+    const long V = batch_size(viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0);
+    const FwdInputs in(dev, background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrices_, gt_depths_,
+                       projmatrices_, sh_, campos_);
+    const int P = in.P;
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
     const auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
     const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
@@ -921,24 +929,44 @@ light_forward_batch(const Tensor& background, const Tensor& means3D_, const Tens
     dgr_light_view w[DGR_MAX_BATCH_VIEWS];
     for (long v = 0; v < V; v++) {
         w[v] = dgr_light_view{row_bytes(geom, v), row_bytes(binning, v), (int)capacity, row_bytes(img, v), row<int>(status, v),
-                              row<float>(views, v), row<float>(projs, v), row<float>(campos, v), row<float>(color, v),
-                              row<float>(depth, v), row<float>(median, v), row<float>(alpha, v), row<float>(gts, v),
+                              row<float>(in.view, v), row<float>(in.proj, v), row<float>(in.campos, v), row<float>(color, v),
+                              row<float>(depth, v), row<float>(median, v), row<float>(alpha, v), row<float>(in.gt, v),
                               row<float>(var, v), row<float>(unc, v), row<int>(px, v), row<int>(radii, v)};
     }
     void* st = stream_of(dev);
-    check(dgr_light_forward_batch(st, (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                                  ptr<float>(sh), ptr<float>(colors), ptr<float>(opacity), ptr<float>(scales), (float)scale_modifier,
-                                  ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0));
-    std::vector<long> tickets;
-    if (post_status && P > 0 && !dgr_stream_is_capturing(st)) {
-        for (long v = 0; v < V; v++) {
-            const long t = dgr_status_post(st, row<int>(status, v));
-            check(t);
-            tickets.push_back(t);
-        }
-    }
-    return {{status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px}, tickets};
+    check(dgr_light_forward_batch(st, (int)V, w, P, (int)degree, in.M, ptr<float>(in.bg), (int)W, (int)H, ptr<float>(in.means3D),
+                                  ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity), ptr<float>(in.scales),
+                                  (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D), (float)tan_fovx, (float)tan_fovy,
+                                  prefiltered ? 1 : 0));
+    return {{status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px},
+            post_batch_status(post_status, P, st, status, V)};
 }
+
+// A batch backward's results: g[1..7] the arena's seven sums (gp[1..7]: their pointers; none without need_gaussian_grads), g[0]
+// every view's dL_dmeans2D [V,P,3] (need_means2D) or None, g[8] dL_dview [V,4,4]; and V scratch rows of nscr bytes
+struct BatchBwdOut {
+    std::vector<Tensor> g = std::vector<Tensor>(9);
+    float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Tensor scratch;
+    size_t nscr;
+    BatchBwdOut(const c10::Device& dev, int P, int M, long V, long W, long H, bool need_gaussian_grads, bool need_means2D,
+                const std::vector<long>& num_rendered) {
+        const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+        if (need_gaussian_grads) {
+            grad_arena(dev, P, M, g.data(), gp);
+            g[0].zero_();  // the arena's one-view means2D slot: a batch returns those gradients per view, beside the arena
+            g[0] = need_means2D ? at::empty({V, P, 3}, f32) : Tensor();
+        }
+        g[8] = at::empty({V, 4, 4}, f32);
+        // (deterministic_grads: + 64 bytes per tile instance of the view with the most of them; the views' rows are equally long)
+        long rmax = 0;
+        for (long r : num_rendered) rmax = std::max(rmax, r);
+        nscr = std::max<size_t>(up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)rmax)), 256);
+        scratch = at::empty({V, (long long)nscr}, at::TensorOptions().dtype(at::kByte).device(dev));
+    }
+    float* dmean2D(long v) const { return g[0].defined() ? row<float>(g[0], v) : nullptr; }
+};
+inline int rendered_of(const std::vector<long>& num_rendered, long v) { return (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0; }
 
 // Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
 // the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).
@@ -959,7 +987,7 @@ std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float*
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
     const long V = viewmatrices_.size(0), H = dL_dout_color.size(2), W = dL_dout_color.size(3);
-    if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
+    batch_size(V);
     const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
                  scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
                  views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev), campos = f32c(campos_, dev),
@@ -967,53 +995,31 @@ std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float*
                  gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gM = f32c(dL_dout_median, dev),
                  gV = f32c(dL_dout_var, dev);
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
-    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-    std::vector<Tensor> g(9);
-    float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Tensor d2;
-    if (need_gaussian_grads) {
-        grad_arena(dev, P, M, g.data());
-        g[0].zero_();  // the arena's one-view means2D slot: a batch returns those gradients per view, beside the arena
-        g[0] = Tensor();
-        for (int i = 1; i < 8; i++) gp[i] = ptr<float>(g[i]);
-        if (need_means2D) { d2 = at::empty({V, P, 3}, f32); g[0] = d2; }
-    } else {
-        map_off = true;  // nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
-    }
-    Tensor dview = at::empty({V, 4, 4}, f32);
-    // (deterministic_grads: + 64 bytes per tile instance of the view with the most of them; the views' rows are equally long)
-    long rmax = 0;
-    for (long r : num_rendered) rmax = std::max(rmax, r);
-    const size_t nscr = std::max<size_t>(up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)rmax)), 256);
-    Tensor scratch = at::empty({V, (long long)nscr}, at::TensorOptions().dtype(at::kByte).device(dev));
+    BatchBwdOut o(dev, P, M, V, W, H, need_gaussian_grads, need_means2D, num_rendered);
+    if (!need_gaussian_grads) map_off = true;  // nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
     dgr_light_view_grad w[DGR_MAX_BATCH_VIEWS];
     for (long v = 0; v < V; v++) {
         w[v] = dgr_light_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
                                    row<float>(projs, v), row<float>(campos, v), ptr<float>(perspec), row<float>(alphas, v),
                                    row<float>(gts, v), row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), row<float>(gM, v),
-                                   row<float>(gV, v), d2.defined() ? row<float>(d2, v) : nullptr, row<float>(dview, v),
-                                   row_bytes(scratch, v), nscr, (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0};
+                                   row<float>(gV, v), o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr,
+                                   rendered_of(num_rendered, v)};
     }
     // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    check(dgr_light_backward_batch_absgrad(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+    check(dgr_light_backward_batch_absgrad(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
+    ptr<float>(means3D),
                                    ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
-                                   ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, gp[2], gp[1], gp[3],
-                                   gp[4], gp[5], gp[6], gp[7], track_off ? 1 : 0, map_off ? 1 : 0, abs_views));
-    g[8] = dview;
-    return g;
+                                   ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3],
+                                   o.gp[4], o.gp[5], o.gp[6], o.gp[7], track_off ? 1 : 0, map_off ? 1 : 0, abs_views));
+    return o.g;
 }
 std::vector<Tensor> light_backward_batch(DGR_LIGHT_BWD_BATCH_PARAMS) {
     return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, nullptr);
 }
 // absgrad: the nine results of light_backward_batch and, tenth, every view's absolute screen-space gradient [V,P,3]
 std::vector<Tensor> light_backward_batch_absgrad(DGR_LIGHT_BWD_BATCH_PARAMS) {
-    const long V = viewmatrices_.size(0), P = means3D_.size(0);
-    Tensor abs = at::empty({V, P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D_.device()));
-    float* av[DGR_MAX_BATCH_VIEWS] = {};
-    for (long v = 0; v < V && v < DGR_MAX_BATCH_VIEWS && P > 0; v++) av[v] = row<float>(abs, v);
-    std::vector<Tensor> g = light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, av);
-    g.push_back(std::move(abs));
-    return g;
+    return with_absgrad(means3D_, viewmatrices_.size(0),
+                        [&](float* const* abs) { return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, abs); });
 }
 
 // The full variant's batch (include/dgr_hip.h: dgr_full_forward_batch / _backward_batch; dgr_amd/batch_full.py), same contract.
@@ -1024,18 +1030,11 @@ full_forward_batch(const Tensor& background, const Tensor& means3D_, const Tenso
                    const Tensor& viewmatrices_, const Tensor& gt_depths_, const Tensor& projmatrices_, double tan_fovx,
                    double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_, bool prefiltered,
                    long capacity, bool post_status) {
-    if (means3D_.dim() != 2 || means3D_.size(1) != 3) throw std::runtime_error("means3D must have dimensions (num_points, 3)");
-    const c10::Device dev = means3D_.device();
-    if (!dev.is_cuda()) throw std::runtime_error("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)");
-    const long V = viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0;
-    if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 opacity = f32c(opacity_, dev), scales = f32c(scales_, dev), rotations = f32c(rotations_, dev),
-                 cov3D = f32c(cov3D_, dev), views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev),
-                 campos = f32c(campos_, dev), gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
+    const c10::Device dev = forward_device(means3D_);
+    const long V = batch_size(viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0);
+    const FwdInputs in(dev, background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrices_, gt_depths_,
+                       projmatrices_, sh_, campos_);
+    const int P = in.P;
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
     const auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
     const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
@@ -1048,22 +1047,15 @@ full_forward_batch(const Tensor& background, const Tensor& means3D_, const Tenso
     dgr_full_view w[DGR_MAX_BATCH_VIEWS];
     for (long v = 0; v < V; v++) {
         w[v] = dgr_full_view{row_bytes(geom, v), row_bytes(binning, v), (int)capacity, row_bytes(img, v), row<int>(status, v),
-                             row<float>(views, v), row<float>(projs, v), row<float>(campos, v), row<float>(color, v),
-                             row<float>(depth, v), row<float>(gts, v), row<float>(unc, v), row<int>(radii, v)};
+                             row<float>(in.view, v), row<float>(in.proj, v), row<float>(in.campos, v), row<float>(color, v),
+                             row<float>(depth, v), row<float>(in.gt, v), row<float>(unc, v), row<int>(radii, v)};
     }
     void* st = stream_of(dev);
-    check(dgr_full_forward_batch(st, (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                                 ptr<float>(sh), ptr<float>(colors), ptr<float>(opacity), ptr<float>(scales), (float)scale_modifier,
-                                 ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, prefiltered ? 1 : 0));
-    std::vector<long> tickets;
-    if (post_status && P > 0 && !dgr_stream_is_capturing(st)) {
-        for (long v = 0; v < V; v++) {
-            const long t = dgr_status_post(st, row<int>(status, v));
-            check(t);
-            tickets.push_back(t);
-        }
-    }
-    return {{status, color, depth, unc, radii, geom, binning, img}, tickets};
+    check(dgr_full_forward_batch(st, (int)V, w, P, (int)degree, in.M, ptr<float>(in.bg), (int)W, (int)H, ptr<float>(in.means3D),
+                                 ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity), ptr<float>(in.scales),
+                                 (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D), (float)tan_fovx, (float)tan_fovy,
+                                 prefiltered ? 1 : 0));
+    return {{status, color, depth, unc, radii, geom, binning, img}, post_batch_status(post_status, P, st, status, V)};
 }
 
 // Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
@@ -1085,7 +1077,7 @@ std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* c
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
     const long V = viewmatrices_.size(0), H = dL_dout_color.size(2), W = dL_dout_color.size(3);
-    if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
+    batch_size(V);
     const bool lean = !dL_dout_unc.defined() || dL_dout_unc.numel() == 0;
     const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
                  scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
@@ -1093,51 +1085,28 @@ std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* c
                  gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev), perspec = f32c_diag4(perspec_, dev),
                  gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gU = lean ? Tensor() : f32c(dL_dout_unc, dev);
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
-    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-    std::vector<Tensor> g(9);
-    float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Tensor d2;
-    if (need_gaussian_grads) {
-        grad_arena(dev, P, M, g.data());
-        g[0].zero_();  // the arena's one-view means2D slot: a batch returns those gradients per view, beside the arena
-        g[0] = Tensor();
-        for (int i = 1; i < 8; i++) gp[i] = ptr<float>(g[i]);
-        if (need_means2D) { d2 = at::empty({V, P, 3}, f32); g[0] = d2; }
-    }
-    Tensor dview = at::empty({V, 4, 4}, f32);
-    // (deterministic_grads: + 64 bytes per tile instance of the view with the most of them; the views' rows are equally long)
-    long rmax = 0;
-    for (long r : num_rendered) rmax = std::max(rmax, r);
-    const size_t nscr = std::max<size_t>(up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)rmax)), 256);
-    Tensor scratch = at::empty({V, (long long)nscr}, at::TensorOptions().dtype(at::kByte).device(dev));
+    BatchBwdOut o(dev, P, M, V, W, H, need_gaussian_grads, need_means2D, num_rendered);
     dgr_full_view_grad w[DGR_MAX_BATCH_VIEWS];
     for (long v = 0; v < V; v++) {
         w[v] = dgr_full_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
                                   row<float>(projs, v), row<float>(campos, v), ptr<float>(perspec), row<float>(gts, v),
                                   row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), lean ? nullptr : row<float>(gU, v),
-                                  d2.defined() ? row<float>(d2, v) : nullptr, row<float>(dview, v), row_bytes(scratch, v), nscr,
-                                  (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0};
+                                  o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr, rendered_of(num_rendered, v)};
     }
     // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
     check(dgr_full_backward_batch_absgrad(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
                                   ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
-                                  ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, gp[2], gp[1], gp[3],
-                                  gp[4], gp[5], gp[6], gp[7], abs_views));
-    g[8] = dview;
-    return g;
+                                  ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3],
+                                  o.gp[4], o.gp[5], o.gp[6], o.gp[7], abs_views));
+    return o.g;
 }
 std::vector<Tensor> full_backward_batch(DGR_FULL_BWD_BATCH_PARAMS) {
     return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, nullptr);
 }
 // absgrad: the nine results of full_backward_batch and, tenth, every view's absolute screen-space gradient [V,P,3]
 std::vector<Tensor> full_backward_batch_absgrad(DGR_FULL_BWD_BATCH_PARAMS) {
-    const long V = viewmatrices_.size(0), P = means3D_.size(0);
-    Tensor abs = at::empty({V, P, 3}, at::TensorOptions().dtype(at::kFloat).device(means3D_.device()));
-    float* av[DGR_MAX_BATCH_VIEWS] = {};
-    for (long v = 0; v < V && v < DGR_MAX_BATCH_VIEWS && P > 0; v++) av[v] = row<float>(abs, v);
-    std::vector<Tensor> g = full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, av);
-    g.push_back(std::move(abs));
-    return g;
+    return with_absgrad(means3D_, viewmatrices_.size(0),
+                        [&](float* const* abs) { return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, abs); });
 }
 
 Tensor mark_visible(const Tensor& means3D_, const Tensor& viewmatrix_, const Tensor& projmatrix_) {  // L/rasterize_points.cu:238-256

@@ -67,6 +67,24 @@ def test_bad_view_counts_are_refused_before_touching_the_gpu():
     assert b"dL_dview" in lib.dgr_last_error()
 
 
+@pytest.mark.parametrize("variant,cls", [("light", _capi.LightViewGrad), ("full", _capi.FullViewGrad)])
+def test_batch_backward_refuses_a_view_without_its_binning_buffer(variant, cls):
+    """Both variants' batch backward read the view's binning buffer as its sorted list: a view with every other input and a
+    NULL binning buffer is refused before anything touches a device (host pointers stand in for device ones)."""
+    lib = _capi.load()
+    host = torch.zeros(1024, dtype=torch.uint8)
+    fake = host.data_ptr()
+    grads = (cls * 1)()
+    for name, t in cls._fields_:
+        setattr(grads[0], name, fake if t is ctypes.c_void_p else 1 << 40 if name == "scratch_bytes" else 100)
+    grads[0].binning_buffer = None
+    sig = _capi._SIGS["dgr_%s_backward_batch" % variant][1]
+    args = [fake if t is ctypes.c_void_p else 1.0 if t is ctypes.c_float else 0 for t in sig]
+    args[:10] = [None, 1, grads, 10, 3, 16, fake, 64, 48, fake]  # stream, n_views, views, P, D, M, background, W, H, means3D
+    assert getattr(lib, "dgr_%s_backward_batch" % variant)(*args) == _capi.DGR_ERR_BAD_ARGUMENT
+    assert b"missing state buffer" in lib.dgr_last_error()
+
+
 def _settings(V, track_off=False, map_off=False):
     from dgr_amd.batch_full import BatchRasterizationSettings
     eye = torch.eye(4).expand(V, 4, 4).contiguous()

@@ -6,6 +6,7 @@ import torch
 
 from util import assert_grad_close, assert_image_close, make_scene, mask_flipped_pixels
 import hip_helpers as hh
+from dgr_amd import _capi
 from test_hip_light_parity import assert_images_carry_the_references_bits
 
 pytestmark = pytest.mark.gpu
@@ -38,22 +39,84 @@ def test_precomputed_colors_and_covariances(oracle):
             assert g["dL_dsh"].size == 0
 
 
-def test_empty_input_returns_zeros():
-    """P == 0: nothing runs, outputs are the zero fills (L/rasterize_points.cu:88,188) -- not the background."""
+@pytest.mark.parametrize("det", [0, 1], ids=["atomics", "deterministic"])
+@pytest.mark.parametrize("variant", ["light", "full"])
+def test_empty_input_returns_zeros(variant, det):
+    """P == 0: nothing runs, outputs are the zero fills (L/rasterize_points.cu:88,188) -- not the background; under
+    deterministic_grads as well (there is no row buffer to size)."""
+    from dgr_amd import _capi
+    from dgr_amd import full as F
     from dgr_amd import light as L
     dev = hh.dev()
     s = make_scene(10, 48, 32, 0)
     E = lambda *shape: torch.empty(shape, device=dev)  # noqa: E731
-    out = L._C.rasterize_gaussians(hh.T(s.bg), E(0, 3), E(0), E(0, 1), E(0, 3), E(0, 4), 1.0, E(0), hh.T(s.view), hh.T(s.gt),
-                                   hh.T(s.proj), s.tanfovx, s.tanfovy, s.H, s.W, E(0, 16, 3), 3, hh.T(s.campos), False, False)
+    with _capi.thread_options(deterministic_grads=det):
+        if variant == "light":
+            out = L._C.rasterize_gaussians(hh.T(s.bg), E(0, 3), E(0), E(0, 1), E(0, 3), E(0, 4), 1.0, E(0), hh.T(s.view),
+                                           hh.T(s.gt), hh.T(s.proj), s.tanfovx, s.tanfovy, s.H, s.W, E(0, 16, 3), 3,
+                                           hh.T(s.campos), False, False)
+            images = out[1:6]
+            g = L._C.rasterize_gaussians_backward(hh.T(s.bg), E(0, 3), out[6], E(0), E(0, 3), E(0, 4), 1.0, E(0), hh.T(s.view),
+                                                  hh.T(s.proj), s.tanfovx, s.tanfovy, hh.T(s.gC), hh.T(s.gD[None]),
+                                                  hh.T(s.gM[None]), hh.T(s.gV[None]), hh.T(s.gt), E(0, 16, 3), 3, hh.T(s.campos),
+                                                  out[7], 0, out[8], out[9], out[5], False, hh.T(s.persp), False, False)
+        else:
+            out = F._C.rasterize_gaussians(hh.T(s.bg), E(0, 3), E(0), E(0, 1), E(0, 3), E(0, 4), 1.0, E(0), hh.T(s.view),
+                                           hh.T(s.gt), hh.T(s.proj), s.tanfovx, s.tanfovy, s.H, s.W, E(0, 16, 3), 3,
+                                           hh.T(s.campos), False)
+            images = out[2:5]
+            g = F._C.rasterize_gaussians_backward(hh.T(s.bg), E(0, 3), out[5], E(0), E(0, 3), E(0, 4), 1.0, E(0), hh.T(s.view),
+                                                  hh.T(s.gt), hh.T(s.proj), s.tanfovx, s.tanfovy, hh.T(s.gC), hh.T(s.gD[None]),
+                                                  hh.T(s.gV[None]), E(0, 16, 3), 3, hh.T(s.campos), out[6], out[0], out[7],
+                                                  out[8], out[1], hh.T(s.persp))
     assert out[0] == 0
-    for t in out[1:6]:
+    for t in images:
         assert float(t.abs().sum()) == 0.0
-    g = L._C.rasterize_gaussians_backward(hh.T(s.bg), E(0, 3), out[6], E(0), E(0, 3), E(0, 4), 1.0, E(0), hh.T(s.view),
-                                          hh.T(s.proj), s.tanfovx, s.tanfovy, hh.T(s.gC), hh.T(s.gD[None]), hh.T(s.gM[None]),
-                                          hh.T(s.gV[None]), hh.T(s.gt), E(0, 16, 3), 3, hh.T(s.campos), out[7], 0, out[8],
-                                          out[9], out[5], False, hh.T(s.persp), False, False)
-    assert g[8].shape == (1, 4, 4) and float(g[8].abs().sum()) == 0.0 and g[3].shape == (0, 3)
+    assert g[8].numel() == 16 and float(g[8].abs().sum()) == 0.0 and g[3].shape == (0, 3)
+
+
+def _full_backward_into(s, out, scratch, dL_dmeans2D_abs=None):
+    """dgr_full_backward_absgrad over ctypes into the caller's scratch: (return code, gradients)"""
+    lib = _capi.load()
+    R, NG, color, depth, unc, radii, geom, binning, img = out
+    P, M = s.means.shape[0], s.shs.shape[1]
+    f32 = dict(dtype=torch.float32, device=hh.dev())
+    g = {n: torch.zeros(shape, **f32) for n, shape in (("means2D", (P, 3)), ("opacity", (P, 1)), ("means3D", (P, 3)),
+                                                         ("cov3D", (P, 6)), ("sh", (P, M, 3)), ("scales", (P, 3)),
+                                                         ("rotations", (P, 4)), ("view", (4, 4)))}
+    bg, means, shs, scales, rots, view, proj, campos, gC, gD, gU, persp, gt = (
+        hh.T(a) for a in (s.bg, s.means, s.shs, s.scales, s.rots, s.view, s.proj, s.campos, s.gC, s.gD[None], s.gV[None],
+                          s.persp, s.gt))
+    p = _capi.ptr
+    rc = lib.dgr_full_backward_absgrad(
+        _capi.stream_handle(), P, 3, M, int(R), p(bg), s.W, s.H, p(means), p(shs), None, p(scales), 1.0, p(rots), None, p(view),
+        p(proj), p(campos), s.tanfovx, s.tanfovy, p(radii), p(geom), p(binning), p(img), p(gC), p(gD), p(g["means2D"]), None,
+        p(g["opacity"]), None, p(g["means3D"]), p(g["cov3D"]), p(g["sh"]), p(g["scales"]), p(g["rotations"]), None, None, None,
+        None, None, p(persp), None, None, None, p(g["view"]), None, None, None, p(gt), p(gU), p(scratch), scratch.numel(),
+        p(dL_dmeans2D_abs))
+    torch.cuda.synchronize()
+    return rc, {k: v.cpu().numpy() for k, v in g.items()}
+
+
+def test_a_refused_backward_consumes_the_scratch_clean_arm():
+    """dgr_backward_scratch_clean_arm promises the NEXT backward of the thread a clean scratch; a backward refused before any
+    device call (absgrad with alpha_mode 2) is that backward too, so the one after it clears its scratch itself."""
+    lib = _capi.load()
+    s = make_scene(3000, 96, 64, 7)
+    out, _ = hh.hip_full_forward(s, 3)
+    P = s.means.shape[0]
+    n = lib.dgr_light_backward_scratch_bytes_r(P, s.W, s.H, int(out[0]))
+    rc, clean = _full_backward_into(s, out, torch.zeros(n, dtype=torch.uint8, device=hh.dev()))
+    assert rc == 0, _capi.last_error()
+    assert lib.dgr_backward_scratch_clean_arm() == 0
+    with _capi.thread_options(alpha_mode=2):
+        rc, _ = _full_backward_into(s, out, torch.zeros(n, dtype=torch.uint8, device=hh.dev()),
+                                    torch.zeros((P, 3), device=hh.dev()))
+    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and "alpha_mode" in _capi.last_error()
+    rc, dirty = _full_backward_into(s, out, torch.full((n,), 0x3F, dtype=torch.uint8, device=hh.dev()))
+    assert rc == 0, _capi.last_error()
+    for k in clean:
+        assert_grad_close(dirty[k], clean[k], k, rel_to_max=1e-5, elem_rtol=1e-3, elem_frac=1e-3)
 
 
 def test_bad_means_shape_raises_like_the_reference():
