@@ -842,14 +842,21 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
         const float mm[4] = {m.x, m.y, m.z, 1.0f};
         if (COMPLETE) {
             // the ndc terms from the mean2D sums dL_dmeans3D uses, the z path from its depth sums (light: depth and variance in
-            // acc[3], median in acc[10]; full: the depth -> mean term's acc[3]), then the cov2D and SH paths
+            // acc[3], median in acc[10]; full: the depth -> mean term's acc[3]), then the cov2D and SH paths.  The ndc rows get
+            // their full derivative d ndc_r / d t_cam,j = m_w persp[4 j + r] - m_hom.r m_w^2 persp[4 j + 3]: the principal point
+            // (persp[8], persp[9]) and any skew reach the pose as they reach dL_dmeans3D through projmatrix
             const float A = acc[4], B = acc[5], Dz = full ? acc[3] : acc[3] + acc[10];
+            const float* pp = a.perspec;
+            const float hx = m_hom.x * (-m_w * m_w), hy = m_hom.y * (-m_w * m_w);
+            float nd[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                nd[j] = (m_w * pp[4 * j + 0] + hx * pp[4 * j + 3]) * A + (m_w * pp[4 * j + 1] + hy * pp[4 * j + 3]) * B;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                pose[3 * k + 0] = (m_w * a.perspec[0] * mm[k]) * A + px[3 * k + 0];
-                pose[3 * k + 1] = (m_w * a.perspec[5] * mm[k]) * B + px[3 * k + 1];
-                pose[3 * k + 2] = (m_hom.x * (-m_w * m_w) * mm[k]) * A + (m_hom.y * (-m_w * m_w) * mm[k]) * B + mm[k] * Dz +
-                                  px[3 * k + 2];
+                pose[3 * k + 0] = nd[0] * mm[k] + px[3 * k + 0];
+                pose[3 * k + 1] = nd[1] * mm[k] + px[3 * k + 1];
+                pose[3 * k + 2] = nd[2] * mm[k] + mm[k] * Dz + px[3 * k + 2];
             }
         } else if (!full) {
             const float A = acc[4], B = acc[5], Dd = acc[13];

@@ -79,11 +79,13 @@ inline Tensor f32c(const Tensor& t, const c10::Device& dev) {
     if (t.numel() == 0 || (t.scalar_type() == at::kFloat && t.is_contiguous() && t.device() == dev)) return t;
     return t.to(dev, at::kFloat).contiguous();
 }
-// perspec_matrix: the kernels read entries 0 and 5 only (L/cr/backward.cu:725-739) -- the diagonal, which a transposed
-// 4x4 (how callers usually hold Proj^T: `projection.transpose(0, 1)`) keeps in place: no copy kernel per backward for it
+// perspec_matrix: the default pose gradient reads entries 0 and 5 only (L/cr/backward.cu:725-739) -- the diagonal, which a
+// transposed 4x4 (how callers usually hold Proj^T: `projection.transpose(0, 1)`) keeps in place: no copy kernel per backward
+// for it.  The complete one (option "pose_grad" = 1, in effect for the calling thread) reads entries 3, 8, 9 and 11 as well,
+// which the transposed storage does not hold where the kernels look: it gets the contiguous copy.
 inline Tensor f32c_diag4(const Tensor& t, const c10::Device& dev) {
     if (t.scalar_type() == at::kFloat && t.device() == dev && t.dim() == 2 && t.size(0) == 4 && t.size(1) == 4 && t.stride(0) == 1 &&
-        t.stride(1) == 4)
+        t.stride(1) == 4 && ((dgr_thread_options_effective() >> 12) & 15) != 2)
         return t;
     return f32c(t, dev);
 }
@@ -189,6 +191,8 @@ inline Tensor view_of(const Tensor& base, size_t byte_off, c10::IntArrayRef size
 inline char* row_bytes(const Tensor& t, long v) { return t.numel() == 0 ? nullptr : reinterpret_cast<char*>(t.data_ptr()) + v * t.stride(0) * t.element_size(); }
 template <typename T>
 inline T* row(const Tensor& t, long v) { return reinterpret_cast<T*>(row_bytes(t, v)); }
+// a batch's perspec_matrix: one [4,4] for every view, or [V,4,4] (a projection per view)
+inline float* perspec_row(const Tensor& t, long v) { return t.dim() == 3 ? row<float>(t, v) : ptr<float>(t); }
 inline Tensor bytes_on(const c10::Device& dev, size_t n) {
     return at::empty({(long long)std::max<size_t>(n, 1)}, at::TensorOptions().dtype(at::kByte).device(dev));
 }
@@ -1000,7 +1004,7 @@ std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float*
     dgr_light_view_grad w[DGR_MAX_BATCH_VIEWS];
     for (long v = 0; v < V; v++) {
         w[v] = dgr_light_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
-                                   row<float>(projs, v), row<float>(campos, v), ptr<float>(perspec), row<float>(alphas, v),
+                                   row<float>(projs, v), row<float>(campos, v), perspec_row(perspec, v), row<float>(alphas, v),
                                    row<float>(gts, v), row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), row<float>(gM, v),
                                    row<float>(gV, v), o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr,
                                    rendered_of(num_rendered, v)};
@@ -1089,7 +1093,7 @@ std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* c
     dgr_full_view_grad w[DGR_MAX_BATCH_VIEWS];
     for (long v = 0; v < V; v++) {
         w[v] = dgr_full_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
-                                  row<float>(projs, v), row<float>(campos, v), ptr<float>(perspec), row<float>(gts, v),
+                                  row<float>(projs, v), row<float>(campos, v), perspec_row(perspec, v), row<float>(gts, v),
                                   row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), lean ? nullptr : row<float>(gU, v),
                                   o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr, rendered_of(num_rendered, v)};
     }

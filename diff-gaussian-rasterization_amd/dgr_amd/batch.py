@@ -44,7 +44,7 @@ class BatchRasterizationSettings(NamedTuple):
     campos: torch.Tensor         # [V,3]
     prefiltered: bool
     debug: bool
-    perspec_matrix: torch.Tensor  # [4,4] (one projection for the batch)
+    perspec_matrix: torch.Tensor  # [4,4] (one projection for the batch) or [V,4,4] (one per view, e.g. per-view cx, cy)
     track_off: bool
     map_off: bool
 
@@ -202,7 +202,8 @@ def _backward_views(variant, ViewGrad, per_view, tail, bg, means3D, radii, color
     for v in range(V):
         w = views[v]
         w.geometry_buffer, w.binning_buffer, w.image_buffer = _row(geom, v), _row(binning, v), _row(img, v)
-        w.viewmatrix, w.projmatrix, w.cam_pos, w.perspec_matrix = _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v), pp
+        w.viewmatrix, w.projmatrix, w.cam_pos = _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v)
+        w.perspec_matrix = _row(perspec_matrix, v) if perspec_matrix.dim() == 3 else pp
         w.gt_depth, w.radii = _row(gt_depths, v), _row(radii, v)
         for k, t in per_view.items():
             setattr(w, k, _row(t, v))

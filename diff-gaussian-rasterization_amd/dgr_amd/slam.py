@@ -175,7 +175,8 @@ def _perspec_cached(tanfovx, tanfovy, znear, zfar, device):
 def pose_to_camera(q, t, tanfovx, tanfovy, znear=0.01, zfar=100.0):
     """(viewmatrix, projmatrix, perspec_matrix, campos) from a quaternion (r, x, y, z) and a translation, float32 GPU
     tensors: the fused form of `camera_tensors(w2c_from_quat_trans(q, t), tanfovx, tanfovy)` (2 launches for forward +
-    backward instead of ~40 elementwise torch kernels)."""
+    backward instead of ~40 elementwise torch kernels).  The perspec_matrix is a symmetric frustum's (principal point at the
+    image centre); an off-centre camera goes through `render(viewpoint_camera=...)` with its own `projection_matrix`."""
     perspec = _perspec_cached(tanfovx, tanfovy, znear, zfar, q.device)
     view, proj, campos = _PoseToCamera.apply(q, t, perspec)
     return view, proj, perspec, campos

@@ -298,7 +298,10 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
  *     0; the per-Gaussian outputs are unchanged; track_off = 1 makes it a no-op.  The library differentiates campos as
  *     -Rcam^T t of the view matrix while using the campos passed to the forward: the derivative is exact for callers that pass a
  *     consistent campos.  A light map_off backward then runs the mapping blend backward and drops its per-Gaussian outputs.
- *     Other values: DGR_ERR_BAD_ARGUMENT.
+ *     The ndc rows take their full derivative, m_w perspec[4 j + r] - m_hom.r m_w^2 perspec[4 j + 3], so an off-centre
+ *     principal point (perspec[8], perspec[9]) is exact too.  The default mode keeps the reference's symmetric-frustum Jacobian
+ *     (perspec[0] and perspec[5] only, L/cuda_rasterizer/backward.cu:725-739): its pose gradient is not exact for an
+ *     off-centre projection, and pose_grad = 1 is.  Other values: DGR_ERR_BAD_ARGUMENT.
  *  "tight_cull": 1 = alpha-aware tile rectangles.  The reference gives a Gaussian every tile its
  *     3-sigma_max circle touches (cuda_rasterizer/forward.cu:229-237, auxiliary.h:46-56); with this option the rectangle
  *     is cut down to the box where alpha can reach 15/255.  Images and gradients are unchanged, but num_rendered, the

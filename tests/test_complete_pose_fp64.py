@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_oracle_autograd import CASES, sh_to_rgb
+from test_oracle_autograd import (CAMERA_CASES, CASES, assert_placement_edge, camera_case_id, camera_case_scene,
+                                  reference_ndc_pose, sh_to_rgb)
 from util import make_scene
 
 WRITTEN = [0, 1, 2, 4, 5, 6, 8, 9, 10, 12, 13, 14]  # the view entries a pose gradient writes (3, 7, 11, 15 stay 0)
@@ -22,7 +23,10 @@ def complete_forward(s, variant, deg, vis, point_list, ranges, n_contrib, grads,
                      added=True, view=None, frozen=None):
     """Returns (loss, leaves, images, frozen).  `added=False` (light only) detaches the paths the reference's pose gradient
     leaves out -- cov2D, SH campos, the variance and median z -- so that dL/dview is the reference's.  `view`: a float64 [4,4]
-    view matrix instead of the scene's; `frozen`: the dict of detached values / decisions of an earlier call, reused."""
+    view matrix instead of the scene's; `frozen`: the dict of detached values / decisions of an earlier call, reused.  The ndc
+    position is differentiated through the full perspec in the complete formulation and through the reference's symmetric-
+    frustum Jacobian (test_oracle_autograd.reference_ndc_pose) in the reference split: the two part where persp[8] or
+    persp[9] (an off-centre principal point) is not 0."""
     f = lambda a: torch.tensor(np.asarray(a, np.float64))  # noqa: E731
     fr = {} if frozen is None else frozen
 
@@ -46,9 +50,11 @@ def complete_forward(s, variant, deg, vis, point_list, ranges, n_contrib, grads,
     idx = torch.tensor(np.nonzero(vis)[0])
     m = leaves["means3D"][idx]
     mh = torch.cat([m, torch.ones(len(idx), 1, dtype=torch.float64)], 1)
-    p_hom = mh @ (V @ persp)                                   # ndc path
+    p_hom = mh @ ((V if added else V.detach()) @ persp)        # ndc path (complete: the full projection's derivative)
     p_w = 1.0 / (p_hom[:, 3] + 1e-7)
     pix = torch.stack([((p_hom[:, 0] * p_w + 1.0) * W - 1.0) * 0.5, ((p_hom[:, 1] * p_w + 1.0) * H - 1.0) * 0.5], 1)
+    if not added:  # the reference's pose Jacobian of the ndc position (persp[0], persp[5] and m_hom only)
+        pix = pix + reference_ndc_pose(mh, V, persp, p_hom, W, H)
     z_depth = (mh @ V)[:, 2]                                   # the depth image's z (a reference path)
     t = (mh @ Va)[:, :3]                                       # t_cam = Rcam m + t: cov2D, variance, median
     z_cam = t[:, 2]
@@ -186,13 +192,26 @@ def test_complete_formulation_images_and_reference_split(oracle, case, variant):
     """(1) the one-leaf formulation renders the oracle's images; (2) light: with the added paths detached its dL/dview is the
     oracle's reference pose gradient, so the complete gradient differs from it by exactly the added branches."""
     P, W, H, deg, seed = case
-    s = make_scene(P, W, H, seed)
+    check_formulation_and_reference_split(oracle, make_scene(P, W, H, seed), deg, variant)
+
+
+@pytest.mark.parametrize("variant", ["light", "full"])
+@pytest.mark.parametrize("case", CAMERA_CASES, ids=camera_case_id)
+def test_complete_formulation_and_reference_split_at_cameras(oracle, case, variant):
+    """As above at the cameras of tests/cameras.py: off-centre (the reference split then needs the reference's shortened ndc
+    Jacobian), fx != fy, the Jacobian clamp, the near plane."""
+    s, deg, info = camera_case_scene(case)
+    ref = check_formulation_and_reference_split(oracle, s, deg, variant, img_tol=2.0)
+    assert_placement_edge(oracle, case[1], s, info, ref["radii"])
+
+
+def check_formulation_and_reference_split(oracle, s, deg, variant, img_tol=1.0):
     grads = scaled_grads(s, variant)
     st, ref, g = oracle_run(oracle, s, variant, deg, grads)
     gv, _, _, img = complete_grad(s, variant, deg, st, ref, grads)
     for k, v in img.items():
         d = np.abs(v.reshape(-1) - ref[k].astype(np.float64).reshape(-1))
-        assert d.max() <= IMG_TOL[k], f"{k}: float64 forward differs from the oracle by {d.max():.2e}"
+        assert d.max() <= IMG_TOL[k] * img_tol, f"{k}: float64 forward differs from the oracle by {d.max():.2e}"
     assert np.abs(gv).max() > 0
     if variant == "light":
         gr, _, _, _ = complete_grad(s, variant, deg, st, ref, grads, added=False)
@@ -201,6 +220,7 @@ def test_complete_formulation_images_and_reference_split(oracle, case, variant):
         assert err <= 5e-5, f"reference split: {err:.2e} of scale"
         # (and the added branches are not negligible here: the complete gradient is a different vector)
         assert np.abs(gv - gr).max() >= 1e-3 * np.abs(gv).max()
+    return ref
 
 
 @pytest.mark.parametrize("variant", ["light", "full"])
@@ -208,7 +228,18 @@ def test_complete_formulation_images_and_reference_split(oracle, case, variant):
 def test_complete_translation_identity(oracle, case, variant):
     """(3) for a rigid (orthonormal) view dL/dt = Rcam sum_g dL/dmeans3D[g]: the complete gradient is the means' counterpart."""
     P, W, H, deg, seed = case
-    s = make_scene(P, W, H, seed)
+    check_translation_identity(oracle, make_scene(P, W, H, seed), deg, variant)
+
+
+@pytest.mark.parametrize("variant", ["light", "full"])
+@pytest.mark.parametrize("case", CAMERA_CASES, ids=camera_case_id)
+def test_complete_translation_identity_at_cameras(oracle, case, variant):
+    """(3) at the cameras of tests/cameras.py: dL_dmeans3D goes through the full projection, so must the complete pose."""
+    s, deg, _ = camera_case_scene(case)
+    check_translation_identity(oracle, s, deg, variant)
+
+
+def check_translation_identity(oracle, s, deg, variant):
     grads = scaled_grads(s, variant)
     st, ref, _ = oracle_run(oracle, s, variant, deg, grads)
     V = orthonormal_view(s.view)
@@ -224,7 +255,18 @@ def test_complete_gradient_matches_central_differences(oracle, variant):
     """(4) central differences of the loss over the 12 written view entries, every decision and detached value frozen at the
     unperturbed view, agree with autograd's dL/dview."""
     P, W, H, deg, seed = CASES[0]
-    s = make_scene(P, W, H, seed)
+    check_central_differences(oracle, make_scene(P, W, H, seed), deg, variant)
+
+
+@pytest.mark.parametrize("variant", ["light", "full"])
+@pytest.mark.parametrize("case", [CAMERA_CASES[1], CAMERA_CASES[2]], ids=camera_case_id)
+def test_complete_gradient_matches_central_differences_at_cameras(oracle, case, variant):
+    """(4) at an off-centre camera with fx != fy, and with Gaussians beyond the Jacobian clamp."""
+    s, deg, _ = camera_case_scene(case)
+    check_central_differences(oracle, s, deg, variant)
+
+
+def check_central_differences(oracle, s, deg, variant):
     grads = scaled_grads(s, variant)
     st, ref, _ = oracle_run(oracle, s, variant, deg, grads)
     args = (s, variant, deg, ref["radii"] > 0, st.get("point_list"), st.get("ranges"), st.get("n_contrib"), grads)

@@ -11,9 +11,11 @@ shaped so that autograd produces the reference's quantity (each is a documented 
   * depth_var is 0 in the forward yet its gradient is consumed as d/d sum (d - gt)^2 alpha T (:600-608): the loss below
     contains that sum;
   * the median-depth gradient goes to the deepest valid Gaussian with T > 0.5 after the division (:656-663);
-  * the pose gradient covers only mean2D (through proj = view x perspec) and the depth sum (:633-651): the view matrix
-    enters the forward below as three tensors (ndc path, depth path, everything else) and only the first two are
-    differentiated;
+  * the pose gradient covers only mean2D and the depth sum (:633-651): the view matrix enters the forward below as three
+    tensors (ndc path, depth path, everything else) and only the first two are differentiated;
+  * its ndc Jacobian is the symmetric frustum's (:725-739, F/cr/backward.cu:516-534): x column m_w persp[0], y column
+    m_w persp[5], z column -m_hom m_w^2 with m_hom from the full projection -- persp[8] and persp[9] (the principal point)
+    and every other entry are left out (`reference_ndc_pose`); dL_dmeans3D uses the full projection;
   * the clamp of t.x / t.z treats the clamped coordinate as independent of t.z (:175-176,262-264).
 """
 import numpy as np
@@ -47,6 +49,20 @@ def sh_to_rgb(deg, sh, d):
     return torch.clamp(r + 0.5, min=0.0)
 
 
+def reference_ndc_pose(mh, view, persp, p_hom, W, H):
+    """A zero-valued [n, 2] pixel offset whose gradient w.r.t. `view` is the reference's pose Jacobian of the ndc position
+    (L/cuda_rasterizer/backward.cu:725-739, F/cuda_rasterizer/backward.cu:516-534): d ndc_x / d t_cam = (m_w persp[0], 0,
+    -m_hom.x m_w^2), d ndc_y / d t_cam = (0, m_w persp[5], -m_hom.y m_w^2), m_hom = the full projection of the mean (detached,
+    as are `mh` and `persp`).  For a symmetric frustum (persp[8] = persp[9] = 0, persp[11] = 1) it is the exact derivative."""
+    tc = mh.detach() @ view                                   # t_cam (homogeneous), gradient -> view only
+    pf = persp.detach().reshape(-1)
+    ph = p_hom.detach()
+    mw = 1.0 / (ph[:, 3] + 1e-7)
+    nx = mw * pf[0] * tc[:, 0] - ph[:, 0] * mw * mw * tc[:, 2]
+    ny = mw * pf[5] * tc[:, 1] - ph[:, 1] * mw * mw * tc[:, 2]
+    return torch.stack([(nx - nx.detach()) * (0.5 * W), (ny - ny.detach()) * (0.5 * H)], 1)
+
+
 def torch_light(s, deg, vis, point_list, ranges, n_contrib, grads, colors_precomp=None, cov3D_precomp=None):
     """Returns (loss, leaves dict, images dict).  `vis`, `point_list`, `ranges`, `n_contrib` come from the oracle's
     integer path (pinned separately by SURVEY Appendix C); everything float is recomputed here in float64.
@@ -66,10 +82,11 @@ def torch_light(s, deg, vis, point_list, ranges, n_contrib, grads, colors_precom
     idx = torch.tensor(np.nonzero(vis)[0])
     m = leaves["means3D"][idx]
     mh = torch.cat([m, torch.ones(len(idx), 1, dtype=torch.float64)], 1)
-    # A-P 2, 7: p_hom = proj m, p_w = 1 / (w + 1e-7), pixel = ((ndc + 1) S - 1) / 2          (pose path 1)
-    p_hom = mh @ (leaves["view_ndc"] @ persp)
+    # A-P 2, 7: p_hom = proj m, p_w = 1 / (w + 1e-7), pixel = ((ndc + 1) S - 1) / 2          (pose path 1: the reference's Jacobian)
+    p_hom = mh @ (view_o @ persp)
     p_w = 1.0 / (p_hom[:, 3] + 1e-7)
     pix = torch.stack([((p_hom[:, 0] * p_w + 1.0) * W - 1.0) * 0.5, ((p_hom[:, 1] * p_w + 1.0) * H - 1.0) * 0.5], 1)
+    pix = pix + reference_ndc_pose(mh, leaves["view_ndc"], persp, p_hom, W, H)
     pix.retain_grad()   # (dL_dmeans2D in pixels, for tests/tools/arbitrate_fp64.py: returned as `_pix`, rows `_idx`)
     z_depth = (mh @ leaves["view_depth"])[:, 2]                                              # (pose path 2)
     t = (mh @ view_o)[:, :3]                                                                  # (no pose gradient)
@@ -154,12 +171,52 @@ def torch_light(s, deg, vis, point_list, ranges, n_contrib, grads, colors_precom
 
 
 CASES = [(400, 64, 48, 3, 11), (300, 40, 40, 0, 12), (500, 70, 45, 2, 13), (300, 40, 40, 1, 15)]
+# (camera, placement, P, W, SH degree, seed) of tests/cameras.py: off-centre principal points, fx != fy, the Jacobian clamp
+# and the near plane, where the reference's shortened pose Jacobian and the exact one part.  (The placements' bands are sized
+# to these small frames: a hundred Gaussians of sigma 20 .. 150 px stacked on every pixel of a 64 x 48 frame leave the
+# float32 backward's transmittance, re-derived by division, at 5e-4 of scale from float64 -- in dL_dopacity as much as
+# anywhere, a property of the reference's algorithm, not of the camera.)
+CAMERA_CASES = [("tum", "plain", 400, 64, 3, 21), ("skewed_pp", "plain", 400, 64, 2, 22),
+                ("skewed_pp", "clamp", 500, 96, 3, 23, dict(n=70, sigma_px=(12.0, 40.0), opacity=(0.05, 0.25))),
+                ("tum", "near", 300, 48, 1, 24, dict(n=30, sigma_px=(4.0, 16.0), opacity=(0.05, 0.25)))]
+
+
+def camera_case_id(case):
+    return f"{case[0]}-{case[1]}"
+
+
+def camera_case_scene(case):
+    """(scene, SH degree, placement info) of a CAMERA_CASES entry; the placement's edge is asserted by the caller."""
+    from cameras import CAMERAS, placed
+    cid, placement, P, W, deg, seed = case[:6]
+    s, info = placed(CAMERAS[cid].at(W), P, placement, seed, **(case[6] if len(case) > 6 else {}))
+    return s, deg, info
 
 
 @pytest.mark.parametrize("case", CASES)
 def test_oracle_backward_equals_fp64_autograd(oracle, case):
     P, W, H, deg, seed = case
-    s = make_scene(P, W, H, seed)
+    check_light_against_fp64(oracle, make_scene(P, W, H, seed), deg)
+
+
+@pytest.mark.parametrize("case", CAMERA_CASES, ids=camera_case_id)
+def test_oracle_backward_equals_fp64_autograd_at_cameras(oracle, case):
+    s, deg, info = camera_case_scene(case)
+    ref = check_light_against_fp64(oracle, s, deg, img_tol=2.0)
+    assert_placement_edge(oracle, case[1], s, info, ref["radii"])
+
+
+def assert_placement_edge(oracle, placement, s, info, radii):
+    from cameras import assert_clamp_edge, assert_near_edge
+    if placement == "clamp":
+        assert_clamp_edge(s, info, radii)
+    elif placement == "near":
+        assert_near_edge(s, info, oracle.mark_visible(s.means, s.view, s.proj), radii, least=10)
+
+
+def check_light_against_fp64(oracle, s, deg, img_tol=1.0):
+    """`img_tol` scales the image bars (2: the camera cases, whose bands put up to ~70 more float32 terms into a pixel's sums)."""
+    P, W, H = s.P, s.W, s.H
     grads = tuple(np.asarray(g, np.float64) * (W * H) ** 0.5 for g in (s.gC, s.gD, s.gM, s.gV))
     st, ref = oracle.light_forward(s.bg, s.means, None, s.opac, s.scales, s.rots, 1.0, None, s.view, s.gt, s.proj,
                                    s.tanfovx, s.tanfovy, H, W, s.shs, deg, s.campos)
@@ -168,7 +225,7 @@ def test_oracle_backward_equals_fp64_autograd(oracle, case):
     # same decisions: the float64 forward reproduces the oracle's float32 images to rounding
     for k, tol in (("color", 2e-6), ("depth", 1e-5), ("opacity_map", 2e-6)):
         d = np.abs(img[k].reshape(-1) - ref[k].astype(np.float64).reshape(-1))
-        assert d.max() <= tol, f"{k}: float64 forward differs from the oracle by {d.max():.2e}"
+        assert d.max() <= tol * img_tol, f"{k}: float64 forward differs from the oracle by {d.max():.2e}"
     loss.backward()
     g = oracle.light_backward(st, s.bg, s.means, None, s.scales, s.rots, 1.0, None, s.view, s.proj, s.tanfovx, s.tanfovy,
                               *(np.asarray(x, np.float32) for x in grads), s.gt, s.shs, deg, s.campos,
@@ -187,6 +244,7 @@ def test_oracle_backward_equals_fp64_autograd(oracle, case):
         # the oracle works in float32 (and forms T_final = 1 - alpha, a cancellation): measured 1e-6 .. 3e-5 of scale on
         # these scenes; a wrong term or sign in any component shows up at >= 1e-3
         assert err <= 5e-5, f"{k}: oracle vs float64 autograd differ by {err:.2e} of the tensor's scale"
+    return ref
 
 
 def torch_full(s, deg, vis, point_list, ranges, n_contrib, grads):
@@ -222,7 +280,8 @@ def torch_full(s, deg, vis, point_list, ranges, n_contrib, grads):
         return torch.stack([((p_hom[:, 0] * p_w + 1.0) * W - 1.0) * 0.5, ((p_hom[:, 1] * p_w + 1.0) * H - 1.0) * 0.5], 1)
 
     pix = pixels(mh, view_o @ persp)                     # gradient -> means
-    pix_pose = pixels(mh_c, leaves["view_ndc"] @ persp)  # gradient -> view (ndc path), nothing else
+    # gradient -> view (ndc path, the reference's Jacobian), nothing else
+    pix_pose = pix.detach() + reference_ndc_pose(mh_c, leaves["view_ndc"], persp, mh_c @ (view_o @ persp), W, H)
     t = (mh @ view_o)[:, :3]
     z = t[:, 2]                                          # gradient -> means
     z_pose = (mh_c @ leaves["view_depth"])[:, 2]         # gradient -> view (depth path)
@@ -339,14 +398,24 @@ def test_oracle_full_backward_equals_fp64_autograd(oracle, case):
     """a12 / a16: the full variant's per-Gaussian gradients (uncertainty consumed as a variance) and its pose gradient
     (ComputePG part 1 + part 2-1, depth terms of the front-most valid Gaussian only) against the formulation above."""
     P, W, H, deg, seed = case
-    s = make_scene(P, W, H, seed)
+    check_full_against_fp64(oracle, make_scene(P, W, H, seed), deg)
+
+
+@pytest.mark.parametrize("case", CAMERA_CASES, ids=camera_case_id)
+def test_oracle_full_backward_equals_fp64_autograd_at_cameras(oracle, case):
+    s, deg, info = camera_case_scene(case)
+    check_full_against_fp64(oracle, s, deg, img_tol=2.0)
+
+
+def check_full_against_fp64(oracle, s, deg, img_tol=1.0):
+    P, W, H = s.P, s.W, s.H
     grads = tuple(np.asarray(g, np.float64) * (W * H) ** 0.5 for g in (s.gC, s.gD, s.gV))
     st, ref = oracle.full_forward(s.bg, s.means, None, s.opac, s.scales, s.rots, 1.0, None, s.view, s.gt, s.proj,
                                   s.tanfovx, s.tanfovy, H, W, s.shs, deg, s.campos)
     loss, leaves, img = torch_full(s, deg, ref["radii"] > 0, st.get("point_list"), st.get("ranges"), st.get("n_contrib"), grads)
     for k, tol in (("color", 2e-6), ("depth", 1e-5), ("uncertainty", 2e-6)):
         d = np.abs(img[k].reshape(-1) - ref[k].astype(np.float64).reshape(-1))
-        assert d.max() <= tol, f"{k}: float64 forward differs from the oracle by {d.max():.2e}"
+        assert d.max() <= tol * img_tol, f"{k}: float64 forward differs from the oracle by {d.max():.2e}"
     loss.backward()
     g = oracle.full_backward(st, s.bg, s.means, None, s.scales, s.rots, 1.0, None, s.view, s.gt, s.proj, s.tanfovx,
                              s.tanfovy, *(np.asarray(x, np.float32) for x in grads), s.shs, deg, s.campos, s.persp)
