@@ -261,6 +261,11 @@ std::atomic<int> g_det_grads{[] { const char* e = getenv("DGR_DETERMINISTIC_GRAD
 // view-matrix counterpart of dL_dmeans3D (csrc/preprocess.hip: bwd_view_terms<true>; include/dgr_hip.h).  A light map_off
 // backward then runs the mapping blend backward (its per-Gaussian outputs are dropped).  Initial value from DGR_POSE_GRAD = 0 / 1.
 std::atomic<int> g_pose_grad{[] { const char* e = getenv("DGR_POSE_GRAD"); return (e && e[0] == '1' && e[1] == 0) ? 1 : 0; }()};
+// dgr_set_option("silhouette_grad", v): 0 (default) / 1.  No entry point reads it: it is the bindings' switch (include/dgr_hip.h),
+// kept here so that both bindings and every thread share one value and a backward runs under its forward's snapshot.  1: the
+// bindings pass the opacity_map (light) / uncertainty (full) gradient as the dL_dpix_silhouette image of the _silhouette entry
+// points.  Initial value from DGR_SILHOUETTE_GRAD = 0 / 1.
+std::atomic<int> g_silhouette_grad{[] { const char* e = getenv("DGR_SILHOUETTE_GRAD"); return (e && e[0] == '1' && e[1] == 0) ? 1 : 0; }()};
 std::atomic<int> g_lane_lists{[] { const char* e = getenv("DGR_FWD_HALVES"); return (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) ? e[0] - '0' : 2; }()};
 
 // ---- per-THREAD overrides of the four options that change what a call computes (dgr_set_thread_option, round 9).  The options
@@ -269,11 +274,12 @@ std::atomic<int> g_lane_lists{[] { const char* e = getenv("DGR_FWD_HALVES"); ret
 // launches as template choices / kernel arguments: launches already queued (on any stream) are not affected by a later change.
 // A backward must run with its forward's alpha mode: the autograd bindings snapshot dgr_thread_options_effective() in the
 // forward and swap it in around the backward (which the autograd engine may run on another thread).
-thread_local int t_alpha_mode = -1, t_tight_cull = -1, t_det_grads = -1, t_pose_grad = -1;
+thread_local int t_alpha_mode = -1, t_tight_cull = -1, t_det_grads = -1, t_pose_grad = -1, t_silhouette_grad = -1;
 inline int opt_alpha_mode() { return t_alpha_mode >= 0 ? t_alpha_mode : g_alpha_mode.load(std::memory_order_relaxed); }
 inline int opt_tight_cull() { return t_tight_cull >= 0 ? t_tight_cull : g_tight_cull.load(std::memory_order_relaxed); }
 inline int opt_det_grads() { return t_det_grads >= 0 ? t_det_grads : g_det_grads.load(std::memory_order_relaxed); }
 inline int opt_pose_grad() { return t_pose_grad >= 0 ? t_pose_grad : g_pose_grad.load(std::memory_order_relaxed); }
+inline int opt_silhouette_grad() { return t_silhouette_grad >= 0 ? t_silhouette_grad : g_silhouette_grad.load(std::memory_order_relaxed); }
 // dgr_set_option("lds_count", v): how the forward bins tile instances.
 //   1 (default) = the two-level segment binning (csrc/segment_binning.hip) whenever the frame's segment tables fit LDS;
 //   0 = returning global atomics on per-tile counters (csrc/binning.hip; inside preprocess_fwd when presized), which also
@@ -811,19 +817,20 @@ struct BwdView {
     const float *alphas, *dL_dpix, *dL_dpix_depth, *dL_dpix_median_depth, *dL_dpix_depth_var;  // (light; full: dL_dpix only)
     const float *dL_depths, *dL_duncertainties;                                                 // (full)
     float *dL_dmean2D, *dL_dview, *dL_dmean2D_abs;
+    const float* dL_dpix_silhouette;  // dL/d(opacity_map) (light) or the exact dL/d(uncertainty) (full), or NULL
     char* scratch;
     size_t scratch_bytes;
     int R;  // >= the view's num_rendered: sizes the deterministic row buffer
 };
-BwdView bwd_view(const dgr_light_view_grad& w, float* abs) {
+BwdView bwd_view(const dgr_light_view_grad& w, float* abs, const float* sil) {
     return BwdView{w.geometry_buffer, w.binning_buffer, w.image_buffer, w.viewmatrix, w.projmatrix, w.cam_pos, w.perspec_matrix,
                    w.gt_depth, w.radii, w.alphas, w.dL_dpix, w.dL_dpix_depth, w.dL_dpix_median_depth, w.dL_dpix_depth_var, nullptr,
-                   nullptr, w.dL_dmean2D, w.dL_dview, abs, w.scratch, w.scratch_bytes, w.num_rendered};
+                   nullptr, w.dL_dmean2D, w.dL_dview, abs, sil, w.scratch, w.scratch_bytes, w.num_rendered};
 }
-BwdView bwd_view(const dgr_full_view_grad& w, float* abs) {
+BwdView bwd_view(const dgr_full_view_grad& w, float* abs, const float* sil) {
     return BwdView{w.geometry_buffer, w.binning_buffer, w.image_buffer, w.viewmatrix, w.projmatrix, w.cam_pos, w.perspec_matrix,
                    w.gt_depth, w.radii, nullptr, w.dL_dpix, nullptr, nullptr, nullptr, w.dL_depths, w.dL_duncertainties,
-                   w.dL_dmean2D, w.dL_dview, abs, w.scratch, w.scratch_bytes, w.num_rendered};
+                   w.dL_dmean2D, w.dL_dview, abs, sil, w.scratch, w.scratch_bytes, w.num_rendered};
 }
 dgr::PreprocessBwdArgs bwd_scene(int P, int D, int M, int W, int H, const float* means3D, const float* shs, const float* scales,
                                  float scale_modifier, const float* rotations, const float* cov3D_precomp, float tan_fovx,
@@ -882,7 +889,7 @@ int blend_bwd_light(const BwdView& w, const dgr::PreprocessBwdArgs& b, const flo
     dgr::RenderBwdLightArgs r{};
     blend_bwd_common(r, w, bg, b.W, b.H, s, det);
     r.alphas = w.alphas; r.dL_dpix = w.dL_dpix; r.dL_dpix_depth = w.dL_dpix_depth; r.dL_dpix_median = w.dL_dpix_median_depth;
-    r.dL_dpix_var = w.dL_dpix_depth_var;
+    r.dL_dpix_var = w.dL_dpix_depth_var; r.dL_dpix_silhouette = w.dL_dpix_silhouette;
     // (complete pose gradient: the tracking blend's three sums are not enough -- the mapping blend backward forms all of them)
     r.means3D = b.means3D; r.view = w.viewmatrix; r.track_off = b.track_off; r.map_off = complete ? 0 : b.map_off;
     ScopedStage t(ST_RENDER_BWD, st);
@@ -895,6 +902,7 @@ int blend_bwd_full(const BwdView& w, const dgr::PreprocessBwdArgs& b, const floa
     blend_bwd_common(r, w, bg, b.W, b.H, s, det);
     r.final_T = s.img.final_T; r.first_contrib = s.img.first_contrib;
     r.dL_dpix = w.dL_dpix; r.dL_depths = w.dL_depths; r.dL_duncertainties = w.dL_duncertainties;
+    r.dL_dpix_silhouette = w.dL_dpix_silhouette;
     ScopedStage t(ST_RENDER_BWD, st);
     if (w.dL_dmean2D_abs) HIP_TRY(dgr::launch_render_bwd_full_abs(r, w.dL_dmean2D_abs, opt_alpha_mode(), st));
     else HIP_TRY(dgr::launch_render_bwd_full(r, opt_alpha_mode(), st, det));
@@ -918,7 +926,7 @@ void bwd_view_part(Q& q, const BwdView& w, const BwdBufs& s, bool det) {
     q.pose_part = s.sc.pose_part; q.ticket = s.sc.ticket; q.dL_dview = w.dL_dview;
 }
 
-// The body of dgr_{light,full}_backward[_absgrad]
+// The body of dgr_{light,full}_backward[_absgrad|_silhouette]
 int backward_one(hipStream_t st, dgr::PreprocessBwdArgs b, const float* background, const BwdView& w, int debug) {
     const bool scratch_clean = g_scratch_clean_armed;  // (consumed by every call, a refused one included)
     g_scratch_clean_armed = false;
@@ -959,7 +967,7 @@ bool bwd_view_complete(const BwdView& w, bool full) {
     return w.alphas && w.dL_dpix && w.dL_dpix_depth && w.dL_dpix_median_depth && w.dL_dpix_depth_var;
 }
 
-// The body of dgr_{light,full}_backward_batch[_absgrad]: per view the scheme of the one-view backward (without the resident
+// The body of dgr_{light,full}_backward_batch[_absgrad|_silhouette]: per view the scheme of the one-view backward (without the resident
 // scratch), the per-Gaussian backward once for all views
 int backward_batch(hipStream_t st, dgr::PreprocessBwdArgs b, const float* background, int n_views, const BwdView* views) {
     const int P = b.P, width = b.W, height = b.H;
@@ -1017,9 +1025,10 @@ int backward_batch(hipStream_t st, dgr::PreprocessBwdArgs b, const float* backgr
 // the batch's view structs as BwdView (as many as the batch may hold: backward_batch checks n_views)
 template <class G>
 int backward_batch_views(hipStream_t st, const dgr::PreprocessBwdArgs& b, const float* background, int n_views, const G* views,
-                         float* const* dL_dmean2D_abs) {
+                         float* const* dL_dmean2D_abs, const float* const* dL_dpix_silhouette) {
     BwdView bv[DGR_MAX_BATCH_VIEWS];
-    for (int v = 0; views && v < n_views && v < DGR_MAX_BATCH_VIEWS; v++) bv[v] = bwd_view(views[v], dL_dmean2D_abs ? dL_dmean2D_abs[v] : nullptr);
+    for (int v = 0; views && v < n_views && v < DGR_MAX_BATCH_VIEWS; v++)
+        bv[v] = bwd_view(views[v], dL_dmean2D_abs ? dL_dmean2D_abs[v] : nullptr, dL_dpix_silhouette ? dL_dpix_silhouette[v] : nullptr);
     return backward_batch(st, b, background, n_views, views ? bv : nullptr);
 }
 }  // namespace
@@ -1109,6 +1118,26 @@ int dgr_light_backward_absgrad(void* stream, int P, int D, int M, int R, const f
                                float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
                                const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
                                const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes, float* dL_dmean2D_abs) {
+    return dgr_light_backward_silhouette(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, alphas, scales,
+                                         scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                                         radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dpix_depth,
+                                         dL_dpix_median_depth, dL_dpix_depth_var, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                                         dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, debug, dgndcs_dviewmatrix,
+                                         perspec_matrix, dL_dview, dg_camd_dviewmatrix, gt_depth, track_off, map_off, scratch,
+                                         scratch_bytes, dL_dmean2D_abs, nullptr);
+}
+int dgr_light_backward_silhouette(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                               const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+                               const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                               const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                               float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                               const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
+                               const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                               float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                               float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
+                               const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
+                               const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes, float* dL_dmean2D_abs,
+                               const float* dL_dpix_silhouette) {
     (void)dgndcs_dviewmatrix; (void)dg_camd_dviewmatrix; (void)colors_precomp;
     dgr::PreprocessBwdArgs b = bwd_scene(P, D, M, width, height, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                          tan_fovx, tan_fovy, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
@@ -1116,7 +1145,7 @@ int dgr_light_backward_absgrad(void* stream, int P, int D, int M, int R, const f
     b.dL_dconic = dL_dconic; b.dL_ddepth = dL_ddepth;
     const BwdView w{geom_buffer, binning_buffer, image_buffer, viewmatrix, projmatrix, campos, perspec_matrix, gt_depth, radii,
                     alphas, dL_dpix, dL_dpix_depth, dL_dpix_median_depth, dL_dpix_depth_var, nullptr, nullptr, dL_dmean2D, dL_dview,
-                    dL_dmean2D_abs, scratch, scratch_bytes, R};
+                    dL_dmean2D_abs, dL_dpix_silhouette, scratch, scratch_bytes, R};
     return backward_one((hipStream_t)stream, b, background, w, debug);
 }
 
@@ -1180,6 +1209,26 @@ int dgr_full_backward_absgrad(void* stream, int P, int D, int M, int R, const fl
                               float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
                               float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
                               size_t scratch_bytes, float* dL_dmean2D_abs) {
+    return dgr_full_backward_silhouette(stream, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                                        scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy,
+                                        radii, geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_depths, dL_dmean2D, dL_dconic,
+                                        dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dpixel_dgc,
+                                        gau_id_list, pix_id_list, dgc_dCam_position, dpixel_dndcs, perspec_matrix, dgndcs_dviewmatrix,
+                                        dpixel_dinvcovs, dgc_invcovs_dT, dL_dview, dL_dgau_depth, ddepth_dndcs, ddepth_dinvcovs,
+                                        gt_depth, dL_duncertainties, scratch, scratch_bytes, dL_dmean2D_abs, nullptr);
+}
+int dgr_full_backward_silhouette(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                              const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                              float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                              const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                              char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                              const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                              float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                              float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
+                              const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
+                              float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
+                              float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
+                              size_t scratch_bytes, float* dL_dmean2D_abs, const float* dL_dpix_silhouette) {
     (void)colors_precomp; (void)dpixel_dgc; (void)gau_id_list; (void)pix_id_list; (void)dgc_dCam_position;
     (void)dpixel_dndcs; (void)dgndcs_dviewmatrix; (void)dpixel_dinvcovs; (void)dgc_invcovs_dT; (void)ddepth_dndcs;
     (void)ddepth_dinvcovs;
@@ -1189,7 +1238,7 @@ int dgr_full_backward_absgrad(void* stream, int P, int D, int M, int R, const fl
     b.dL_dconic = dL_dconic; b.dL_ddepth = dL_dgau_depth;
     const BwdView w{geom_buffer, binning_buffer, image_buffer, viewmatrix, projmatrix, campos, perspec_matrix, gt_depth, radii,
                     nullptr, dL_dpix, nullptr, nullptr, nullptr, dL_depths, dL_duncertainties, dL_dmean2D, dL_dview,
-                    dL_dmean2D_abs, scratch, scratch_bytes, R};
+                    dL_dmean2D_abs, dL_dpix_silhouette, scratch, scratch_bytes, R};
     return backward_one((hipStream_t)stream, b, background, w, 0);
 }
 
@@ -1246,11 +1295,23 @@ int dgr_light_backward_batch_absgrad(void* stream, int n_views, const dgr_light_
                                      const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                                      float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                                      int track_off, int map_off, float* const* dL_dmean2D_abs) {
+    return dgr_light_backward_batch_silhouette(stream, n_views, views, P, D, M, background, width, height, means3D, shs,
+                                               colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy,
+                                               dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, track_off,
+                                               map_off, dL_dmean2D_abs, nullptr);
+}
+int dgr_light_backward_batch_silhouette(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
+                                        const float* background, int width, int height, const float* means3D, const float* shs,
+                                        const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                        const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity,
+                                        float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                                        float* dL_drot, int track_off, int map_off, float* const* dL_dmean2D_abs,
+                                        const float* const* dL_dpix_silhouette) {
     (void)colors_precomp;
     const dgr::PreprocessBwdArgs b = bwd_scene(P, D, M, width, height, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                                tan_fovx, tan_fovy, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
                                                dL_drot, track_off, map_off, 0);
-    return backward_batch_views((hipStream_t)stream, b, background, n_views, views, dL_dmean2D_abs);
+    return backward_batch_views((hipStream_t)stream, b, background, n_views, views, dL_dmean2D_abs, dL_dpix_silhouette);
 }
 
 int dgr_full_backward_batch(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
@@ -1267,11 +1328,22 @@ int dgr_full_backward_batch_absgrad(void* stream, int n_views, const dgr_full_vi
                                     const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
                                     const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, float* const* dL_dmean2D_abs) {
+    return dgr_full_backward_batch_silhouette(stream, n_views, views, P, D, M, background, width, height, means3D, shs,
+                                              colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, tan_fovx, tan_fovy,
+                                              dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                                              dL_dmean2D_abs, nullptr);
+}
+int dgr_full_backward_batch_silhouette(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                                       const float* background, int width, int height, const float* means3D, const float* shs,
+                                       const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                       const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity,
+                                       float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                                       float* dL_drot, float* const* dL_dmean2D_abs, const float* const* dL_dpix_silhouette) {
     (void)colors_precomp;
     const dgr::PreprocessBwdArgs b = bwd_scene(P, D, M, width, height, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp,
                                                tan_fovx, tan_fovy, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale,
                                                dL_drot, 0, 0, 1);
-    return backward_batch_views((hipStream_t)stream, b, background, n_views, views, dL_dmean2D_abs);
+    return backward_batch_views((hipStream_t)stream, b, background, n_views, views, dL_dmean2D_abs, dL_dpix_silhouette);
 }
 
 int dgr_cov3d_forward(void* stream, int P, const float* scales, const float* rotations, float scale_modifier, float* cov3D) {
@@ -1590,6 +1662,11 @@ int dgr_set_option(const char* name, int value) {
         g_pose_grad.store(value);
         return DGR_OK;
     }
+    if (n == "silhouette_grad") {
+        if (value < 0 || value > 1) { g_last_error = "silhouette_grad: 0 (the reference's gradients) or 1 (exact silhouette gradient)"; return DGR_ERR_BAD_ARGUMENT; }
+        g_silhouette_grad.store(value);
+        return DGR_OK;
+    }
     if (n == "profile_every") { g_profile_every.store(value > 0 ? value : 1); return DGR_OK; }
     if (n == "batch_order") { g_batch_order.store(value ? 1 : 0); return DGR_OK; }
     if (n == "batch_streams") { g_batch_streams.store(value < 1 ? 1 : value > DGR_BATCH_MAX_STREAMS ? DGR_BATCH_MAX_STREAMS : value); return DGR_OK; }
@@ -1607,6 +1684,7 @@ int dgr_get_option(const char* name) {
     if (n == "lane_lists") return g_lane_lists.load();
     if (n == "deterministic_grads") return g_det_grads.load();
     if (n == "pose_grad") return g_pose_grad.load();
+    if (n == "silhouette_grad") return g_silhouette_grad.load();
     if (n == "profile_every") return g_profile_every.load();
     if (n == "batch_streams") return g_batch_streams.load();
     if (n == "batch_order") return g_batch_order.load();
@@ -1628,6 +1706,11 @@ int dgr_set_thread_option(const char* name, int value) {
         t_pose_grad = value < 0 ? -1 : value;
         return DGR_OK;
     }
+    if (n == "silhouette_grad") {
+        if (value > 1) { g_last_error = "silhouette_grad: 0, 1 (or < 0: the process-wide option)"; return DGR_ERR_BAD_ARGUMENT; }
+        t_silhouette_grad = value < 0 ? -1 : value;
+        return DGR_OK;
+    }
     g_last_error = "not a per-thread option: " + n;
     return DGR_ERR_BAD_ARGUMENT;
 }
@@ -1638,20 +1721,24 @@ int dgr_get_thread_option(const char* name) {
     if (n == "tight_cull") return opt_tight_cull();
     if (n == "deterministic_grads") return opt_det_grads();
     if (n == "pose_grad") return opt_pose_grad();
+    if (n == "silhouette_grad") return opt_silhouette_grad();
     return DGR_ERR_BAD_ARGUMENT;
 }
-// the four as one word, each field = value + 1 (0 = "inherit", in an override word): bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
-// deterministic_grads, 12-15 pose_grad
+// the five as one word, each field = value + 1 (0 = "inherit", in an override word): bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
+// deterministic_grads, 12-15 pose_grad, 16-19 silhouette_grad
 int dgr_thread_options_effective(void) {
-    return (opt_alpha_mode() + 1) | ((opt_tight_cull() + 1) << 4) | ((opt_det_grads() + 1) << 8) | ((opt_pose_grad() + 1) << 12);
+    return (opt_alpha_mode() + 1) | ((opt_tight_cull() + 1) << 4) | ((opt_det_grads() + 1) << 8) | ((opt_pose_grad() + 1) << 12) |
+           ((opt_silhouette_grad() + 1) << 16);
 }
 int dgr_thread_options_swap(int word) {
-    const int prev = (t_alpha_mode + 1) | ((t_tight_cull + 1) << 4) | ((t_det_grads + 1) << 8) | ((t_pose_grad + 1) << 12);
+    const int prev = (t_alpha_mode + 1) | ((t_tight_cull + 1) << 4) | ((t_det_grads + 1) << 8) | ((t_pose_grad + 1) << 12) |
+                     ((t_silhouette_grad + 1) << 16);
     if (word >= 0) {
         t_alpha_mode = (word & 15) - 1;
         t_tight_cull = ((word >> 4) & 15) - 1;
         t_det_grads = ((word >> 8) & 15) - 1;
         t_pose_grad = ((word >> 12) & 15) - 1;
+        t_silhouette_grad = ((word >> 16) & 15) - 1;
     }
     return prev;
 }

@@ -195,6 +195,7 @@ struct RenderBwdLightArgs {
     const float* dL_dpix_depth;
     const float* dL_dpix_median;
     const float* dL_dpix_var;
+    const float* dL_dpix_silhouette;  // [H,W] dL/d(opacity_map) or NULL (render_light.hip: SILHOUETTE)
     const float* means3D;
     const float* view;
     float* acc;  // [P,16]
@@ -241,6 +242,7 @@ struct RenderBwdFullArgs {
     const float* dL_dpix;
     const float* dL_depths;
     const float* dL_duncertainties;
+    const float* dL_dpix_silhouette;  // [H,W] the exact gradient of the uncertainty output (sum alpha T) or NULL (render_full.hip)
     float* acc;  // [P,16]
     // deterministic gradients (render_light.hip: DET): the finished row of a (tile, Gaussian) pair is stored to det_rows instead
     float* det_rows;

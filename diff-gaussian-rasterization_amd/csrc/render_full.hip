@@ -168,6 +168,9 @@ struct StagedBwdFull {
 // (its planes take the LDS).
 // LEAN (round 9, as in the light variant): the caller passed no gradient image for the "uncertainty" output (NULL: the loss did not
 // use it) -- the variance recurrence and its two terms drop out: bit-identical to the kernel fed an all-zero image.
+// SILHOUETTE (not a template axis; as in the light variant, render_light.hip): the exact gradient of the opacity_map sum_k alpha_k T_k,
+// a.dL_dpix_silhouette (nullable), enters the per-pixel constant bg_term only.  It is read whatever LEAN says: the lean kernel
+// (no dL_duncertainties) with a silhouette image is the exact silhouette gradient; given both, the two terms add.
 // ABS (absgrad; not DET): as in the light mapping backward (render_light.hip: ABS) -- every lane's own dL/dmean2D (the first of the
 // three "d/d(ndc)" pairs of the finish step, per pixel) in absolute value, reduced per half-wave by half_reduce3 into accumulator
 // rows 15, 16, so the 16-value network keeps its 15 components; the batch's totals go to abs_out [P,3] by global atomics.
@@ -211,16 +214,18 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
 
     const float T_final = inside ? a.final_T[pix_id] : 0.f;  // backward.cu:598
     float T = T_final;
-    float dpix0 = 0.f, dpix1 = 0.f, dpix2 = 0.f, dL_depth = 0.f, dL_dunc = 0.f, gt_px = 0.f;
+    float dpix0 = 0.f, dpix1 = 0.f, dpix2 = 0.f, dL_depth = 0.f, dL_dunc = 0.f, gt_px = 0.f, dpix_sil = 0.f;
     if (inside) {
         dpix0 = a.dL_dpix[pix_id];
         dpix1 = a.dL_dpix[N + pix_id];
         dpix2 = a.dL_dpix[2 * N + pix_id];
         dL_depth = a.dL_depths[pix_id];
         if (!LEAN && a.dL_duncertainties) dL_dunc = a.dL_duncertainties[pix_id];
+        if (a.dL_dpix_silhouette) dpix_sil = __builtin_nontemporal_load(a.dL_dpix_silhouette + pix_id);  // (every form: SILHOUETTE)
         gt_px = a.gt_depth[pix_id];
     }
-    const float bg_term = -T_final * (a.bg[0] * dpix0 + a.bg[1] * dpix1 + a.bg[2] * dpix2);  // times 1/(1 - alpha): background term of dL/dalpha
+    // times 1/(1 - alpha): background and silhouette terms of dL/dalpha (no silhouette image: the subtracted +0 changes no bit)
+    const float bg_term = -T_final * ((a.bg[0] * dpix0 + a.bg[1] * dpix1 + a.bg[2] * dpix2) - dpix_sil);
     const float dunc2 = 2.f * dL_dunc;
     // Linear recurrences instead of the reference's five accum_rec_* (see render_light.hip): the full variant needs
     // the colour part and the depth part of dL/dalpha separately (pose terms), hence three scalars:

@@ -261,6 +261,10 @@ struct StagedBwd {
 // in different halves of the quadrant share a loop step (0.87 steps per entry); such a step reduces its twelve sums per half and
 // each half delivers to its own entry's column -- every entry is still delivered once.
 //
+// SILHOUETTE (every form above; not a template axis): the opacity_map A = sum_k alpha_k T_k has dA/dalpha_k = T_final / (1 - alpha_k),
+// the shape of the background term.  A caller's dL/dA image (a.dL_dpix_silhouette, nullable) therefore only changes the per-pixel
+// constant bg_term, read once before the loop: the pair loop and everything downstream of dL/dalpha stay as they are.
+//
 // ABS (absgrad, AbsGS's "homodirectional" gradient; mapping only, not DET): each lane also forms its pixel's own dL/dmean2D --
 // the formula of the moments -> gradients step below applied to the pixel's q dx, q dy -- and sums the absolute values of its two
 // components.  half_reduce3 reduces the pair over each half-wave, and each half adds its totals to its own entry's column of
@@ -307,7 +311,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
 
     const float T_final = inside ? (1.0f - a.alphas[pix_id]) : 0.f;
     float T = T_final;
-    float dpix0 = 0.f, dpix1 = 0.f, dpix2 = 0.f, dpix_depth = 0.f, dpix_median = 0.f, dpix_var = 0.f, gt_px = 0.f;
+    float dpix0 = 0.f, dpix1 = 0.f, dpix2 = 0.f, dpix_depth = 0.f, dpix_median = 0.f, dpix_var = 0.f, gt_px = 0.f, dpix_sil = 0.f;
     if (inside) {
         // (single-use images, 28 bytes per pixel: nontemporal, so that they do not push the accumulator rows and render records out of
         //  the caches -- preprocess_bwd behind this kernel 45 -> 43.5 us, profiles/r6/ab_nontemporal.txt)
@@ -315,15 +319,16 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         dpix1 = __builtin_nontemporal_load(a.dL_dpix + N + pix_id);
         dpix2 = __builtin_nontemporal_load(a.dL_dpix + 2 * N + pix_id);
         dpix_depth = __builtin_nontemporal_load(a.dL_dpix_depth + pix_id);
+        if (a.dL_dpix_silhouette) dpix_sil = __builtin_nontemporal_load(a.dL_dpix_silhouette + pix_id);  // (every form: SILHOUETTE)
         if (!LEAN) {  // (either image may be missing on its own: it then reads as zero)
             if (a.dL_dpix_median) dpix_median = __builtin_nontemporal_load(a.dL_dpix_median + pix_id);
             if (a.dL_dpix_var) dpix_var = __builtin_nontemporal_load(a.dL_dpix_var + pix_id);
             gt_px = __builtin_nontemporal_load(a.gt_depth + pix_id);
         }
     }
-    // per-pixel constants of the loop: -T_final <bg, dL/dpixel> (the background term of dL/dalpha is this times
-    // 1/(1 - alpha)) and 2 dL/dvar
-    const float bg_term = -T_final * (a.bg[0] * dpix0 + a.bg[1] * dpix1 + a.bg[2] * dpix2);
+    // per-pixel constants of the loop: -T_final (<bg, dL/dpixel> - dL/dsilhouette) (the background and silhouette terms of dL/dalpha
+    // are this times 1/(1 - alpha); without a silhouette image the subtracted +0 leaves the bits as they were) and 2 dL/dvar
+    const float bg_term = -T_final * ((a.bg[0] * dpix0 + a.bg[1] * dpix1 + a.bg[2] * dpix2) - dpix_sil);
     const float ddelx_dx = 0.5f * a.W, ddely_dy = 0.5f * a.H;
     // The reference keeps five "accumulated behind me" recurrences (3 colours, depth, variance: backward.cu:580-608)
     // only to form dL/dalpha = sum_c (c_j - accum_rec_c) dL/dpixel_c.  They are linear, so one scalar suffices:

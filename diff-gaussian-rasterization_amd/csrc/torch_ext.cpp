@@ -475,6 +475,7 @@ inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g, float** 
 // dL_drotations, dL_dview [1,4,4]); the first eight are windows of one flat arena (grad_arena above), or undefined tensors
 // (None) when need_gaussian_grads is false (tracking: the library then skips every dense per-Gaussian row).
 // abs_out (absgrad, dgr_light_backward_absgrad): NULL, or the [P,3] absolute screen-space gradient
+// dL_dout_alpha (option "silhouette_grad", dgr_light_backward_silhouette): the opacity_map gradient [1,H,W], or undefined / empty (NULL)
 std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
                                    const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
                                    const Tensor& viewmatrix_, const Tensor& projmatrix_, double tan_fovx, double tan_fovy,
@@ -482,7 +483,8 @@ std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& 
                                    const Tensor& dL_dout_var, const Tensor& gt_depth_, const Tensor& sh_, long degree,
                                    const Tensor& campos_, const Tensor& geomBuffer, long R, const Tensor& binningBuffer,
                                    const Tensor& imageBuffer, const Tensor& alphas_, bool debug, const Tensor& perspec_,
-                                   bool track_off, bool map_off, bool need_gaussian_grads, float* abs_out) {
+                                   bool track_off, bool map_off, bool need_gaussian_grads, float* abs_out,
+                                   const Tensor& dL_dout_alpha = Tensor()) {
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -492,10 +494,10 @@ std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& 
                  view = f32c(viewmatrix_, dev), proj = f32c(projmatrix_, dev), campos = f32c(campos_, dev),
                  gt = f32c(gt_depth_, dev), sh = f32c(sh_, dev), alphas = f32c(alphas_, dev), perspec = f32c_diag4(perspec_, dev),
                  gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gM = f32c(dL_dout_median, dev),
-                 gV = f32c(dL_dout_var, dev);
+                 gV = f32c(dL_dout_var, dev), gA = f32c(dL_dout_alpha, dev);
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
     // (the forward recorded the saved inputs; the gradient images of a graph root are whatever the caller passed in)
-    keep_until_read(dev, {&dL_dout_color, &dL_dout_depth, &dL_dout_median, &dL_dout_var, &alphas_, &perspec_});
+    keep_until_read(dev, {&dL_dout_color, &dL_dout_depth, &dL_dout_median, &dL_dout_var, &alphas_, &perspec_, &dL_dout_alpha});
     Probe p_al(HP_BWD_ALLOC);
     std::vector<Tensor> g(9);
     float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -510,15 +512,15 @@ std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& 
     on_backward_scratch(dev, st, nscr, [&](char* scratch) {
         p_al.stop();
         Probe p_bc(HP_BWD_C);
-        return dgr_light_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                                          ptr<float>(sh), ptr<float>(colors), ptr<float>(alphas), ptr<float>(scales), (float)scale_modifier,
-                                          ptr<float>(rotations), ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos),
-                                          (float)tan_fovx, (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer),
-                                          bytes(binningBuffer), bytes(imageBuffer), ptr<float>(gC),
-                                          ptr<float>(gD), ptr<float>(gM), ptr<float>(gV), gp[0], nullptr, gp[2], gp[1], nullptr,
-                                          gp[3], gp[4],
-                                          gp[5], gp[6], gp[7], debug ? 1 : 0, nullptr, ptr<float>(perspec), g[8].data_ptr<float>(), nullptr,
-                                          ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, scratch, nscr, abs_out);
+        return dgr_light_backward_silhouette(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+                                             ptr<float>(sh), ptr<float>(colors), ptr<float>(alphas), ptr<float>(scales), (float)scale_modifier,
+                                             ptr<float>(rotations), ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos),
+                                             (float)tan_fovx, (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer),
+                                             bytes(binningBuffer), bytes(imageBuffer), ptr<float>(gC),
+                                             ptr<float>(gD), ptr<float>(gM), ptr<float>(gV), gp[0], nullptr, gp[2], gp[1], nullptr,
+                                             gp[3], gp[4],
+                                             gp[5], gp[6], gp[7], debug ? 1 : 0, nullptr, ptr<float>(perspec), g[8].data_ptr<float>(), nullptr,
+                                             ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, scratch, nscr, abs_out, ptr<float>(gA));
     });
     return g;
 }
@@ -536,6 +538,12 @@ std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& 
 std::vector<Tensor> light_backward(DGR_LIGHT_BWD_PARAMS) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, nullptr); }
 std::vector<Tensor> light_backward_absgrad(DGR_LIGHT_BWD_PARAMS) {
     return with_absgrad(means3D, 0, [&](float* const* abs) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, abs[0]); });
+}
+// silhouette: light_backward (absgrad: light_backward_absgrad) with the opacity_map gradient dL_dout_alpha [1,H,W] as the silhouette
+// image (an empty tensor: NULL, the namesake's results)
+std::vector<Tensor> light_backward_silhouette(DGR_LIGHT_BWD_PARAMS, const Tensor& dL_dout_alpha, bool absgrad) {
+    if (!absgrad) return light_backward_impl(DGR_LIGHT_BWD_ARGS, nullptr, dL_dout_alpha);
+    return with_absgrad(means3D, 0, [&](float* const* abs) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, abs[0], dL_dout_alpha); });
 }
 
 
@@ -618,14 +626,15 @@ full_forward(const Tensor& background, const Tensor& means3D, const Tensor& colo
 }
 
 // F/rasterize_points.cu:122-239; returns the nine gradients in the reference's order, dL_dview as [4,4]
-// abs_out: as light_backward_impl's
+// abs_out: as light_backward_impl's; dL_dout_sil: the exact silhouette gradient image (dgr_full_backward_silhouette) or undefined
 std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
                                   const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
                                   const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
                                   double tan_fovy, const Tensor& dL_dout_color, const Tensor& dL_dout_depth,
                                   const Tensor& dL_dout_unc, const Tensor& sh_, long degree, const Tensor& campos_,
                                   const Tensor& geomBuffer, long R, const Tensor& binningBuffer, const Tensor& imageBuffer,
-                                  long NG, const Tensor& perspec_, bool need_gaussian_grads, float* abs_out) {
+                                  long NG, const Tensor& perspec_, bool need_gaussian_grads, float* abs_out,
+                                  const Tensor& dL_dout_sil = Tensor()) {
     (void)NG;
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
@@ -635,9 +644,9 @@ std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& m
                  scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
                  view = f32c(viewmatrix_, dev), proj = f32c(projmatrix_, dev), campos = f32c(campos_, dev),
                  gt = f32c(gt_depth_, dev), sh = f32c(sh_, dev), perspec = f32c_diag4(perspec_, dev), gC = f32c(dL_dout_color, dev),
-                 gD = f32c(dL_dout_depth, dev), gU = f32c(dL_dout_unc, dev);
+                 gD = f32c(dL_dout_depth, dev), gU = f32c(dL_dout_unc, dev), gS = f32c(dL_dout_sil, dev);
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
-    keep_until_read(dev, {&dL_dout_color, &dL_dout_depth, &dL_dout_unc, &perspec_});
+    keep_until_read(dev, {&dL_dout_color, &dL_dout_depth, &dL_dout_unc, &perspec_, &dL_dout_sil});
     std::vector<Tensor> g(9);
     float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (need_gaussian_grads) grad_arena(dev, P, M, g.data(), gp);
@@ -646,16 +655,16 @@ std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& m
     void* st = stream_of(dev);
     // gp: [0] means2D [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
     on_backward_scratch(dev, st, nscr, [&](char* scratch) {
-        return dgr_full_backward_absgrad(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                                         ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
-                                         ptr<float>(rotations),
-                                         ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
-                                         (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer), bytes(binningBuffer), bytes(imageBuffer),
-                                         ptr<float>(gC), ptr<float>(gD), gp[0], nullptr, gp[2], gp[1], gp[3], gp[4], gp[5], gp[6],
-                                         gp[7], nullptr,
-                                         nullptr, nullptr, nullptr, nullptr, ptr<float>(perspec), nullptr, nullptr, nullptr,
-                                         g[8].data_ptr<float>(), nullptr, nullptr, nullptr, ptr<float>(gt), ptr<float>(gU),
-                                         scratch, nscr, abs_out);
+        return dgr_full_backward_silhouette(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
+                                            ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
+                                            ptr<float>(rotations),
+                                            ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
+                                            (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer), bytes(binningBuffer), bytes(imageBuffer),
+                                            ptr<float>(gC), ptr<float>(gD), gp[0], nullptr, gp[2], gp[1], gp[3], gp[4], gp[5], gp[6],
+                                            gp[7], nullptr,
+                                            nullptr, nullptr, nullptr, nullptr, ptr<float>(perspec), nullptr, nullptr, nullptr,
+                                            g[8].data_ptr<float>(), nullptr, nullptr, nullptr, ptr<float>(gt), ptr<float>(gU),
+                                            scratch, nscr, abs_out, ptr<float>(gS));
     });
     return g;
 }
@@ -672,6 +681,12 @@ std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& m
 std::vector<Tensor> full_backward(DGR_FULL_BWD_PARAMS) { return full_backward_impl(DGR_FULL_BWD_ARGS, nullptr); }
 std::vector<Tensor> full_backward_absgrad(DGR_FULL_BWD_PARAMS) {
     return with_absgrad(means3D, 0, [&](float* const* abs) { return full_backward_impl(DGR_FULL_BWD_ARGS, abs[0]); });
+}
+// silhouette: full_backward (absgrad: full_backward_absgrad) with dL_dout_sil [1,H,W] as the exact silhouette image; dL_dout_unc
+// keeps the reference's variance form (the bindings pass an empty tensor there when the option is on)
+std::vector<Tensor> full_backward_silhouette(DGR_FULL_BWD_PARAMS, const Tensor& dL_dout_sil, bool absgrad) {
+    if (!absgrad) return full_backward_impl(DGR_FULL_BWD_ARGS, nullptr, dL_dout_sil);
+    return with_absgrad(means3D, 0, [&](float* const* abs) { return full_backward_impl(DGR_FULL_BWD_ARGS, abs[0], dL_dout_sil); });
 }
 
 // ------------------------------------------------------------------------------------------------ autograd nodes
@@ -734,6 +749,8 @@ inline bool needs_gaussian_grads(AutogradContext* ctx) {
     return need;
 }
 
+// the "silhouette_grad" field (bits 16-19) of such a word: the exact silhouette gradient was on at the forward
+inline bool silhouette_on(int word) { return ((word >> 16) & 15) == 2; }
 // a block under a word of dgr_thread_options_effective() (include/dgr_hip.h): a backward under its forward's options
 struct UnderOptions {
     int prev;
@@ -775,7 +792,7 @@ struct LightNode : public torch::autograd::Function<LightNode> {
         d["H"] = H; d["W"] = W;
         d["options"] = (int64_t)dgr_thread_options_effective();  // the backward runs under the forward's per-call options
         // four of the eight outputs (radii, opacity_map, gau_uncertainty, gau_related_pixels) have no gradient input in the
-        // backward: no zero-filled gradient tensors for them
+        // backward -- opacity_map has one with the option "silhouette_grad" -- : no zero-filled gradient tensors for them
         ctx->set_materialize_grads(false);
         ctx->mark_non_differentiable({o.radii, o.px});
         return {o.color, o.radii, o.depth, o.median, o.var, o.alpha, o.unc, o.px};
@@ -795,11 +812,15 @@ struct LightNode : public torch::autograd::Function<LightNode> {
         //  -- no zero images are made, filled and read)
         const Tensor gM = grad[3].defined() ? grad[3] : Tensor();
         const Tensor gV = grad[4].defined() ? grad[4] : Tensor();
-        const UnderOptions under((int)d["options"].toInt());  // (the engine may run this node on a thread of its own)
-        std::vector<Tensor> g = light_backward(sv[13], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4],
-                                               sv[5], sv[14], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gM, gV, sv[12],
-                                               sv[7], d["degree"].toInt(), sv[15], sv[8], d["R"].toInt(), sv[9], sv[10], sv[11], false,
-                                               sv[16], d["track_off"].toBool(), d["map_off"].toBool(), needs_gaussian_grads(ctx));
+        // (option "silhouette_grad" at the forward: the opacity_map gradient is the silhouette image; unused, or the option off: NULL)
+        const int options = (int)d["options"].toInt();
+        const Tensor gA = silhouette_on(options) && grad[5].defined() ? grad[5] : Tensor();
+        const UnderOptions under(options);  // (the engine may run this node on a thread of its own)
+        std::vector<Tensor> g = light_backward_impl(sv[13], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4],
+                                                    sv[5], sv[14], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gM, gV, sv[12],
+                                                    sv[7], d["degree"].toInt(), sv[15], sv[8], d["R"].toInt(), sv[9], sv[10], sv[11], false,
+                                                    sv[16], d["track_off"].toBool(), d["map_off"].toBool(), needs_gaussian_grads(ctx),
+                                                    nullptr, gA);
         consume_post_backward_wait(stream_of(dev));
         // the reference sums a [H*W,4,4] buffer over dim 0 (L/__init__.py:160-161); here it is [1,4,4], already reduced
         g[8] = view_of(g[8], 0, {4, 4}, at::kFloat);
@@ -857,13 +878,16 @@ struct FullNode : public torch::autograd::Function<FullNode> {
         const c10::Device dev = means3D.device();
         const long H = d["H"].toInt(), W = d["W"].toInt();
         const Tensor gC = grad_or_zeros(grad[0], 3, H, W, dev), gD = grad_or_zeros(grad[2], 1, H, W, dev);
-        // (no gradient image for the uncertainty output: NULL at the C ABI, which then runs the lean blend backward)
+        // (no gradient image for the uncertainty output: NULL at the C ABI, which then runs the lean blend backward.  Option
+        //  "silhouette_grad" at the forward: that gradient is the exact silhouette image, and dL_duncertainties NULL -- the lean kernel)
+        const int options = (int)d["options"].toInt();
         const Tensor gU = grad[3].defined() ? grad[3] : Tensor();
-        const UnderOptions under((int)d["options"].toInt());
-        std::vector<Tensor> g = full_backward(sv[12], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4], sv[5],
-                                              sv[11], sv[13], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gU, sv[7],
-                                              d["degree"].toInt(), sv[14], sv[8], d["R"].toInt(), sv[9], sv[10], 0, sv[15],
-                                              needs_gaussian_grads(ctx));
+        const bool sil = silhouette_on(options);
+        const UnderOptions under(options);
+        std::vector<Tensor> g = full_backward_impl(sv[12], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4], sv[5],
+                                                   sv[11], sv[13], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD,
+                                                   sil ? Tensor() : gU, sv[7], d["degree"].toInt(), sv[14], sv[8], d["R"].toInt(), sv[9],
+                                                   sv[10], 0, sv[15], needs_gaussian_grads(ctx), nullptr, sil ? gU : Tensor());
         consume_post_backward_wait(stream_of(dev));
         return node_grads(g, 23);
     }
@@ -986,7 +1010,8 @@ inline int rendered_of(const std::vector<long>& num_rendered, long v) { return (
     background, means3D_, radii, colors_, scales_, rotations_, scale_modifier, cov3D_, viewmatrices_, projmatrices_, tan_fovx, \
         tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_median, dL_dout_var, gt_depths_, sh_, degree, campos_, geom, binning, \
         img, alphas_, perspec_, track_off, map_off, need_gaussian_grads, need_means2D, num_rendered
-std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float* const* abs_views) {
+// sil (silhouette): every view's opacity_map gradient [V,1,H,W], or undefined / empty (no silhouette image)
+std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float* const* abs_views, const Tensor& sil = Tensor()) {
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -997,12 +1022,14 @@ std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float*
                  views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev), campos = f32c(campos_, dev),
                  gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev), alphas = f32c(alphas_, dev), perspec = f32c_diag4(perspec_, dev),
                  gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gM = f32c(dL_dout_median, dev),
-                 gV = f32c(dL_dout_var, dev);
+                 gV = f32c(dL_dout_var, dev), gA = f32c(sil, dev);
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
     BatchBwdOut o(dev, P, M, V, W, H, need_gaussian_grads, need_means2D, num_rendered);
     if (!need_gaussian_grads) map_off = true;  // nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
     dgr_light_view_grad w[DGR_MAX_BATCH_VIEWS];
+    const float* sv[DGR_MAX_BATCH_VIEWS] = {};
     for (long v = 0; v < V; v++) {
+        sv[v] = gA.numel() ? row<float>(gA, v) : nullptr;
         w[v] = dgr_light_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
                                    row<float>(projs, v), row<float>(campos, v), perspec_row(perspec, v), row<float>(alphas, v),
                                    row<float>(gts, v), row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), row<float>(gM, v),
@@ -1010,11 +1037,11 @@ std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float*
                                    rendered_of(num_rendered, v)};
     }
     // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    check(dgr_light_backward_batch_absgrad(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
-    ptr<float>(means3D),
-                                   ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
-                                   ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3],
-                                   o.gp[4], o.gp[5], o.gp[6], o.gp[7], track_off ? 1 : 0, map_off ? 1 : 0, abs_views));
+    check(dgr_light_backward_batch_silhouette(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
+                                              ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(scales),
+                                              (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx,
+                                              (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3], o.gp[4], o.gp[5], o.gp[6], o.gp[7],
+                                              track_off ? 1 : 0, map_off ? 1 : 0, abs_views, gA.numel() ? sv : nullptr));
     return o.g;
 }
 std::vector<Tensor> light_backward_batch(DGR_LIGHT_BWD_BATCH_PARAMS) {
@@ -1024,6 +1051,12 @@ std::vector<Tensor> light_backward_batch(DGR_LIGHT_BWD_BATCH_PARAMS) {
 std::vector<Tensor> light_backward_batch_absgrad(DGR_LIGHT_BWD_BATCH_PARAMS) {
     return with_absgrad(means3D_, viewmatrices_.size(0),
                         [&](float* const* abs) { return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, abs); });
+}
+// silhouette: light_backward_batch (absgrad: _absgrad) with every view's opacity_map gradient dL_dout_alpha [V,1,H,W] (empty: none)
+std::vector<Tensor> light_backward_batch_silhouette(DGR_LIGHT_BWD_BATCH_PARAMS, const Tensor& dL_dout_alpha, bool absgrad) {
+    if (!absgrad) return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, nullptr, dL_dout_alpha);
+    return with_absgrad(means3D_, viewmatrices_.size(0),
+                        [&](float* const* abs) { return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, abs, dL_dout_alpha); });
 }
 
 // The full variant's batch (include/dgr_hip.h: dgr_full_forward_batch / _backward_batch; dgr_amd/batch_full.py), same contract.
@@ -1076,7 +1109,8 @@ full_forward_batch(const Tensor& background, const Tensor& means3D_, const Tenso
     background, means3D_, radii, colors_, scales_, rotations_, scale_modifier, cov3D_, viewmatrices_, projmatrices_, tan_fovx, \
         tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_unc, gt_depths_, sh_, degree, campos_, geom, binning, img, perspec_, \
         need_gaussian_grads, need_means2D, num_rendered
-std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* const* abs_views) {
+// sil (silhouette): every view's exact silhouette gradient [V,1,H,W], or undefined / empty
+std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* const* abs_views, const Tensor& sil = Tensor()) {
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -1087,21 +1121,25 @@ std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* c
                  scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
                  views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev), campos = f32c(campos_, dev),
                  gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev), perspec = f32c_diag4(perspec_, dev),
-                 gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gU = lean ? Tensor() : f32c(dL_dout_unc, dev);
+                 gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gU = lean ? Tensor() : f32c(dL_dout_unc, dev),
+                 gS = f32c(sil, dev);
     const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
     BatchBwdOut o(dev, P, M, V, W, H, need_gaussian_grads, need_means2D, num_rendered);
     dgr_full_view_grad w[DGR_MAX_BATCH_VIEWS];
+    const float* sv[DGR_MAX_BATCH_VIEWS] = {};
     for (long v = 0; v < V; v++) {
+        sv[v] = gS.numel() ? row<float>(gS, v) : nullptr;
         w[v] = dgr_full_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
                                   row<float>(projs, v), row<float>(campos, v), perspec_row(perspec, v), row<float>(gts, v),
                                   row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), lean ? nullptr : row<float>(gU, v),
                                   o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr, rendered_of(num_rendered, v)};
     }
     // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    check(dgr_full_backward_batch_absgrad(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                                  ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
-                                  ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx, (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3],
-                                  o.gp[4], o.gp[5], o.gp[6], o.gp[7], abs_views));
+    check(dgr_full_backward_batch_silhouette(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
+                                             ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(scales),
+                                             (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx,
+                                             (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3], o.gp[4], o.gp[5], o.gp[6], o.gp[7], abs_views,
+                                             gS.numel() ? sv : nullptr));
     return o.g;
 }
 std::vector<Tensor> full_backward_batch(DGR_FULL_BWD_BATCH_PARAMS) {
@@ -1111,6 +1149,12 @@ std::vector<Tensor> full_backward_batch(DGR_FULL_BWD_BATCH_PARAMS) {
 std::vector<Tensor> full_backward_batch_absgrad(DGR_FULL_BWD_BATCH_PARAMS) {
     return with_absgrad(means3D_, viewmatrices_.size(0),
                         [&](float* const* abs) { return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, abs); });
+}
+// silhouette: full_backward_batch (absgrad: _absgrad) with every view's exact silhouette gradient dL_dout_sil [V,1,H,W] (empty: none)
+std::vector<Tensor> full_backward_batch_silhouette(DGR_FULL_BWD_BATCH_PARAMS, const Tensor& dL_dout_sil, bool absgrad) {
+    if (!absgrad) return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, nullptr, dL_dout_sil);
+    return with_absgrad(means3D_, viewmatrices_.size(0),
+                        [&](float* const* abs) { return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, abs, dL_dout_sil); });
 }
 
 Tensor mark_visible(const Tensor& means3D_, const Tensor& viewmatrix_, const Tensor& projmatrix_) {  // L/rasterize_points.cu:238-256
@@ -1151,6 +1195,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("full_backward_absgrad", &full_backward_absgrad);
     m.def("light_backward_batch_absgrad", &light_backward_batch_absgrad);
     m.def("full_backward_batch_absgrad", &full_backward_batch_absgrad);
+    m.def("light_backward_silhouette", &light_backward_silhouette);
+    m.def("full_backward_silhouette", &full_backward_silhouette);
+    m.def("light_backward_batch_silhouette", &light_backward_batch_silhouette);
+    m.def("full_backward_batch_silhouette", &full_backward_batch_silhouette);
     m.def("host_prof_dump", &host_prof_dump);
     m.def("light_apply", &light_apply);
     m.def("full_apply", &full_apply);

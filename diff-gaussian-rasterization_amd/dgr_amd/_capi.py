@@ -134,6 +134,12 @@ _SIGS["dgr_light_backward_absgrad"] = (_i, _SIGS["dgr_light_backward"][1] + [_vp
 _SIGS["dgr_full_backward_absgrad"] = (_i, _SIGS["dgr_full_backward"][1] + [_vp])
 _SIGS["dgr_light_backward_batch_absgrad"] = (_i, _SIGS["dgr_light_backward_batch"][1] + [C.POINTER(_vp)])
 _SIGS["dgr_full_backward_batch_absgrad"] = (_i, _SIGS["dgr_full_backward_batch"][1] + [C.POINTER(_vp)])
+# the exact silhouette gradient (dgr_hip.h): each takes its _absgrad namesake's arguments plus dL_dpix_silhouette -- one device
+# pointer, or (batches) a host array of n_views device pointers
+_SIGS["dgr_light_backward_silhouette"] = (_i, _SIGS["dgr_light_backward_absgrad"][1] + [_vp])
+_SIGS["dgr_full_backward_silhouette"] = (_i, _SIGS["dgr_full_backward_absgrad"][1] + [_vp])
+_SIGS["dgr_light_backward_batch_silhouette"] = (_i, _SIGS["dgr_light_backward_batch_absgrad"][1] + [C.POINTER(_vp)])
+_SIGS["dgr_full_backward_batch_silhouette"] = (_i, _SIGS["dgr_full_backward_batch_absgrad"][1] + [C.POINTER(_vp)])
 
 _lib = None
 
@@ -213,7 +219,8 @@ class thread_options:
     """`with thread_options(alpha_mode=1, tight_cull=1): ...` -- the calling THREAD's rasterizer calls inside the block use these
     values of the per-call options (include/dgr_hip.h: dgr_set_thread_option) whatever the process-wide ones are; other threads
     are not affected, and a backward runs under its forward's options wherever autograd runs it.  Names: alpha_mode (fast_alpha),
-    tight_cull, deterministic_grads, pose_grad (1: the complete pose gradient, include/dgr_hip.h)."""
+    tight_cull, deterministic_grads, pose_grad (1: the complete pose gradient, include/dgr_hip.h), silhouette_grad (1: the bindings
+    pass the exact silhouette gradient of opacity_map / uncertainty)."""
 
     def __init__(self, **options):
         self.options = options
@@ -231,6 +238,11 @@ class thread_options:
     def __exit__(self, *exc):
         load().dgr_thread_options_swap(self.prev)
         return False
+
+
+def silhouette_on(word):
+    """Whether a dgr_thread_options_effective() word has the option "silhouette_grad" on (bits 16-19: value + 1)."""
+    return ((int(word) >> 16) & 15) == 2
 
 
 class under_options:

@@ -144,33 +144,39 @@ def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifi
 
 def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
                     tanfovx, tanfovy, gC, gD, gM, gV, gt_depths, sh, degree, campos, geom, binning, img, alphas,
-                    perspec_matrix, track_off, map_off, need_gaussian_grads, need_means2D, num_rendered=None, absgrad=False):
+                    perspec_matrix, track_off, map_off, need_gaussian_grads, need_means2D, num_rendered=None, absgrad=False,
+                    silhouette=None):
     """`num_rendered`: per view, what the one-view backward takes as R (>= the view's instance count); read by the library only
     under deterministic_grads, where it sizes the views' row buffers.  `absgrad=True` (dgr_light_backward_batch_absgrad) appends
-    a tenth result, every view's absolute screen-space gradient [V,P,3]."""
+    a tenth result, every view's absolute screen-space gradient [V,P,3].  `silhouette`: every view's opacity_map gradient
+    [V,1,H,W] (dgr_light_backward_batch_silhouette), or None."""
     V_ = viewmatrices.size(0)
     num_rendered = [int(r) for r in (num_rendered if num_rendered is not None else [0] * V_)]
     ext = _ext()
     if ext is not None:
+        args = (bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
+                viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD, gM, gV, gt_depths, sh,
+                int(degree), campos, geom, binning, img, alphas, perspec_matrix, bool(track_off),
+                bool(map_off), bool(need_gaussian_grads), bool(need_means2D), num_rendered)
+        if silhouette is not None:
+            return tuple(ext.light_backward_batch_silhouette(*args, silhouette, bool(absgrad)))
         fn = ext.light_backward_batch_absgrad if absgrad else ext.light_backward_batch
-        g = fn(bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
-                                     viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD, gM, gV, gt_depths, sh,
-                                     int(degree), campos, geom, binning, img, alphas, perspec_matrix, bool(track_off),
-                                     bool(map_off), bool(need_gaussian_grads), bool(need_means2D), num_rendered)
-        return tuple(g)
+        return tuple(fn(*args))
     if not need_gaussian_grads:
         map_off = True  # nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
     return _backward_views("light", _ViewGrad, {"alphas": alphas, "dL_dpix": gC, "dL_dpix_depth": gD, "dL_dpix_median_depth": gM,
                                                  "dL_dpix_depth_var": gV},
                            (int(bool(track_off)), int(bool(map_off))), bg, means3D, radii, colors, scales, rotations,
                            scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh, degree,
-                           campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad)
+                           campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad,
+                           silhouette)
 
 
 def _backward_views(variant, ViewGrad, per_view, tail, bg, means3D, radii, colors, scales, rotations, scale_modifier,
                     cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh, degree, campos, geom, binning,
-                    img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad):
-    """The ctypes batch backward of both variants: dgr_<variant>_backward_batch[_absgrad] with `ViewGrad` views.  `per_view`:
+                    img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad, silhouette=None):
+    """The ctypes batch backward of both variants: dgr_<variant>_backward_batch[_absgrad|_silhouette] with `ViewGrad` views
+    (`silhouette`: every view's silhouette gradient image [V,1,H,W], or None).  `per_view`:
     the variant's own [V, ...] inputs by the view struct's field name (None: NULL; "dL_dpix" is the colour gradient [V,3,H,W]);
     `tail`: the entry point's arguments after the common ones.  Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity,
     dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview [V,4,4]) and, with absgrad, every view's absolute
@@ -214,18 +220,26 @@ def _backward_views(variant, ViewGrad, per_view, tail, bg, means3D, radii, color
     args = (_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
             float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), q(dop), q(dcol), q(d3), q(dcov),
             q(dsh), q(dsc), q(drot)) + tail
-    if not absgrad:
+    out = (d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview)
+    if not absgrad and silhouette is None:
         _light._check(getattr(lib, f"dgr_{variant}_backward_batch")(*args))
-        return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview
-    dabs = torch.empty((V, P, 3), **f32)
-    _light._check(getattr(lib, f"dgr_{variant}_backward_batch_absgrad")(*args, (C.c_void_p * V)(*(_row(dabs, v) for v in range(V)))))
-    return d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview, dabs
+        return out
+    dabs = torch.empty((V, P, 3), **f32) if absgrad else None
+    abs_views = (C.c_void_p * V)(*(_row(dabs, v) for v in range(V))) if absgrad else None
+    if silhouette is None:
+        _light._check(getattr(lib, f"dgr_{variant}_backward_batch_absgrad")(*args, abs_views))
+    else:
+        sil = c(silhouette, dev)
+        _light._check(getattr(lib, f"dgr_{variant}_backward_batch_silhouette")(
+            *args, abs_views, (C.c_void_p * V)(*(_row(sil, v) for v in range(V)))))
+    return out + (dabs,) if absgrad else out
 
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
     """`_RasterizeGaussians` (L/diff_gaussian_rasterization/__init__.py:48-176) over V cameras.  `means2D_abs`: one more leaf
     [V,P,3] whose gradient is every view's absolute screen-space gradient (absgrad, include/dgr_hip.h:
-    dgr_light_backward_batch_absgrad), or None."""
+    dgr_light_backward_batch_absgrad), or None.  Option "silhouette_grad" at the forward: the opacity_map gradient is every
+    view's silhouette image (dgr_light_backward_batch_silhouette)."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
@@ -240,6 +254,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         ctx.num_rendered = num_rendered
         ctx.absgrad = means2D_abs is not None
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
+        ctx.silhouette = _capi.silhouette_on(ctx.dgr_options)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning,
                               img, opacity_map, gt_depths)
         ctx.set_materialize_grads(False)
@@ -265,7 +280,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
                 rs.projmatrices, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_depth_median, grad_depth_var, gt_depths, sh,
                 rs.sh_degree, rs.campos, geom, binning, img, opacity_map, rs.perspec_matrix, rs.track_off, rs.map_off,
                 need_gaussian_grads=any(need[:8]) or absgrad, need_means2D=bool(need[1]), num_rendered=ctx.num_rendered,
-                absgrad=absgrad)
+                absgrad=absgrad, silhouette=grad_alpha if ctx.silhouette else None)
         (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = g[:9]
         _light._consume_post_backward_wait()
         return g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None, g[9] if absgrad else None

@@ -50,30 +50,35 @@ def _outputs(V, P, H, W, f32, i32):
 
 def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
                     tanfovx, tanfovy, gC, gD, gU, gt_depths, sh, degree, campos, geom, binning, img, perspec_matrix,
-                    need_gaussian_grads, need_means2D, num_rendered, absgrad=False):
+                    need_gaussian_grads, need_means2D, num_rendered, absgrad=False, silhouette=None):
     """gU None: no view's loss used the uncertainty image (the lean blend backward).  `num_rendered`: per view, the R of the
     one-view backward (>= the view's count; sizes the row buffers under deterministic_grads).  Returns (dL_dmeans2D [V,P,3] or
     None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview [V,4,4]); absgrad=True
-    (dgr_full_backward_batch_absgrad) appends every view's absolute screen-space gradient [V,P,3]."""
+    (dgr_full_backward_batch_absgrad) appends every view's absolute screen-space gradient [V,P,3].  `silhouette`: every view's
+    exact silhouette gradient [V,1,H,W] (dgr_full_backward_batch_silhouette), or None."""
     num_rendered = [int(r) for r in num_rendered]
     dev = means3D.device
     ext = _ext()
     if ext is not None:
         e = torch.empty(0, device=dev)
+        args = (bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
+                viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD,
+                e if gU is None else gU, gt_depths, sh, int(degree), campos, geom, binning, img,
+                perspec_matrix, bool(need_gaussian_grads), bool(need_means2D), num_rendered)
+        if silhouette is not None:
+            return tuple(ext.full_backward_batch_silhouette(*args, silhouette, bool(absgrad)))
         fn = ext.full_backward_batch_absgrad if absgrad else ext.full_backward_batch
-        return tuple(fn(bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
-                                             viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD,
-                                             e if gU is None else gU, gt_depths, sh, int(degree), campos, geom, binning, img,
-                                             perspec_matrix, bool(need_gaussian_grads), bool(need_means2D), num_rendered))
+        return tuple(fn(*args))
     return _backward_views("full", _ViewGrad, {"dL_dpix": gC, "dL_depths": gD, "dL_duncertainties": gU}, (), bg, means3D, radii,
                            colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy,
                            gt_depths, sh, degree, campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D,
-                           num_rendered, absgrad)
+                           num_rendered, absgrad, silhouette)
 
 
 class _RasterizeGaussiansBatchFull(torch.autograd.Function):
     """The full variant's `_RasterizeGaussians` (F/diff_gaussian_rasterization/__init__.py) over V cameras.  `means2D_abs`: one
-    more leaf [V,P,3] or None (absgrad: dgr_amd.batch._RasterizeGaussiansBatch)."""
+    more leaf [V,P,3] or None (absgrad: dgr_amd.batch._RasterizeGaussiansBatch).  Option "silhouette_grad" at the forward: the
+    uncertainty gradient is every view's exact silhouette image, and no view has a dL_duncertainties image."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
@@ -88,6 +93,7 @@ class _RasterizeGaussiansBatchFull(torch.autograd.Function):
         ctx.num_rendered = R
         ctx.absgrad = means2D_abs is not None
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
+        ctx.silhouette = _capi.silhouette_on(ctx.dgr_options)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning,
                               img, gt_depths)
         ctx.set_materialize_grads(False)
@@ -104,12 +110,14 @@ class _RasterizeGaussiansBatchFull(torch.autograd.Function):
         grad_color = zeros(3) if grad_color is None else grad_color
         grad_depth = zeros(1) if grad_depth is None else grad_depth
         need, absgrad = ctx.needs_input_grad, ctx.absgrad
+        sil = grad_unc if ctx.silhouette else None
+        grad_unc = None if ctx.silhouette else grad_unc
         with _capi.on_device(means3D.device), _capi.under_options(ctx.dgr_options):
             g = _backward_batch(
                 rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
                 rs.projmatrices, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_unc, gt_depths, sh, rs.sh_degree,
                 rs.campos, geom, binning, img, rs.perspec_matrix, need_gaussian_grads=any(need[:8]) or absgrad,
-                need_means2D=bool(need[1]), num_rendered=ctx.num_rendered, absgrad=absgrad)
+                need_means2D=bool(need[1]), num_rendered=ctx.num_rendered, absgrad=absgrad, silhouette=sil)
         (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = g[:9]
         _light._consume_post_backward_wait()
         return g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None, g[9] if absgrad else None

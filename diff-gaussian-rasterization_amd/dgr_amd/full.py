@@ -51,10 +51,13 @@ class _C:
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier,
                                      cov3D_precomp, viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy,
                                      dL_dout_color, dL_dout_depth, dL_dout_uncertainty, sh, degree, campos, geomBuffer,
-                                     R, binningBuffer, imageBuffer, NG, perspec_matrix, need_gaussian_grads=True, absgrad=False):
+                                     R, binningBuffer, imageBuffer, NG, perspec_matrix, need_gaussian_grads=True, absgrad=False,
+                                     silhouette=None):
         # F/rasterize_points.cu:122-239.  need_gaussian_grads=False (tracking: no Gaussian input requires a gradient) returns
         # None for the eight per-Gaussian gradients and skips their dense rows; the pose gradient is the same.  absgrad=True
-        # (dgr_full_backward_absgrad) appends a tenth result, the absolute screen-space gradient [P,3].
+        # (dgr_full_backward_absgrad) appends a tenth result, the absolute screen-space gradient [P,3].  `silhouette`
+        # (dgr_full_backward_silhouette): the exact silhouette gradient image [1,H,W], or None; dL_dout_uncertainty keeps the
+        # reference's variance form.
         lib = _capi.load()
         dev = means3D.device
         P = means3D.size(0)
@@ -80,12 +83,16 @@ class _C:
                 None, None, p(dL_dview), None, None, None, p(gt_depth), p(gU), p(scratch), scratch.numel())
         out = (seg["means2D"], seg["colors"], seg["opacity"], seg["means3D"], seg["cov3D"], seg["sh"], seg["scales"],
                seg["rotations"], dL_dview)
-        if not absgrad:
+        if not absgrad and silhouette is None:
             _check(lib.dgr_full_backward(*args))
             return out
-        dL_dmeans2D_abs = torch.empty((P, 3), **f32)
-        _check(lib.dgr_full_backward_absgrad(*args, p(dL_dmeans2D_abs)))
-        return out + (dL_dmeans2D_abs,)
+        dL_dmeans2D_abs = torch.empty((P, 3), **f32) if absgrad else None
+        if silhouette is None:
+            _check(lib.dgr_full_backward_absgrad(*args, p(dL_dmeans2D_abs)))
+        else:
+            gS = _f32c(silhouette, dev)
+            _check(lib.dgr_full_backward_silhouette(*args, p(dL_dmeans2D_abs), p(gS)))
+        return out + (dL_dmeans2D_abs,) if absgrad else out
 
     @_device_guarded(0)
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -121,12 +128,14 @@ class _CompiledC:
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                      viewmatrix, gt_depth, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                      dL_dout_uncertainty, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, NG,
-                                     perspec_matrix, need_gaussian_grads=True, absgrad=False):
+                                     perspec_matrix, need_gaussian_grads=True, absgrad=False, silhouette=None):
+        args = (background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix, gt_depth,
+                projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_uncertainty, sh, int(degree),
+                campos, geomBuffer, int(R), binningBuffer, imageBuffer, int(NG), perspec_matrix, bool(need_gaussian_grads))
+        if silhouette is not None:
+            return tuple(_CompiledC.ext.full_backward_silhouette(*args, silhouette, bool(absgrad)))
         fn = _CompiledC.ext.full_backward_absgrad if absgrad else _CompiledC.ext.full_backward
-        return tuple(fn(
-            background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix, gt_depth,
-            projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_uncertainty, sh, int(degree),
-            campos, geomBuffer, int(R), binningBuffer, imageBuffer, int(NG), perspec_matrix, bool(need_gaussian_grads)))
+        return tuple(fn(*args))
 
     @staticmethod
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -166,7 +175,9 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
 
 
 class _RasterizeGaussians(torch.autograd.Function):
-    """`means2D_abs`: one more leaf [P,3] or None (absgrad: dgr_amd.light._RasterizeGaussians)."""
+    """`means2D_abs`: one more leaf [P,3] or None (absgrad: dgr_amd.light._RasterizeGaussians).  With the option
+    "silhouette_grad" on at the forward, the uncertainty gradient goes to the backward as the exact silhouette image and
+    dL_duncertainties is NULL (dgr_full_backward_silhouette); without it, it is the reference's variance form."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
@@ -200,6 +211,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = R
         ctx.absgrad = means2D_abs is not None
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
+        ctx.silhouette = _capi.silhouette_on(ctx.dgr_options)
         ctx.num_related_gaussians = num_related_gaussians
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, radii, sh,
                               geomBuffer, binningBuffer, imgBuffer, gt_depth)
@@ -220,6 +232,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         absgrad = ctx.absgrad
         grad_out_color = zeros(3) if grad_out_color is None else grad_out_color
         grad_out_depth = zeros(1) if grad_out_depth is None else grad_out_depth
+        kw = {}
+        if ctx.silhouette:  # the exact silhouette gradient: the image (or NULL, unused) there, NULL as dL_duncertainties
+            if grad_out_uncertainty is not None:
+                kw["silhouette"] = grad_out_uncertainty
+            grad_out_uncertainty = _light._EMPTY
         if absgrad and grad_out_uncertainty is None:  # NULL: the lean blend backward (bit-identical to a zero image)
             grad_out_uncertainty = _light._EMPTY
         grad_out_uncertainty = zeros(1) if grad_out_uncertainty is None else grad_out_uncertainty
@@ -251,9 +268,9 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raster_settings.perspec_matrix)
         with _capi.under_options(ctx.dgr_options):  # (the autograd engine may run this on a thread of its own)
             if absgrad:
-                out = _C.rasterize_gaussians_backward(*args, absgrad=True)
+                out = _C.rasterize_gaussians_backward(*args, absgrad=True, **kw)
             else:
-                out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]))
+                out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]), **kw)
         grad_means2D_abs = out[9] if absgrad else None
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, grad_viewmatrix) = out[:9]

@@ -123,6 +123,14 @@ def set_complete_pose_gradient(on=True):
     _capi.set_option("pose_grad", 1 if on else 0)
 
 
+def set_silhouette_gradient(on=True):
+    """Opt in to the exact silhouette gradient (include/dgr_hip.h: dgr_set_option "silhouette_grad"): a loss on `opacity_map`
+    (light; the full variant's `uncertainty`, the same sum alpha T) then trains the Gaussians and the pose through
+    dA/dalpha_k = T_final / (1 - alpha_k), instead of being dropped (light) or taken as the depth variance (full).  Takes effect
+    at the next forward; process-wide; per thread: `_capi.thread_options(silhouette_grad=1)`."""
+    _capi.set_option("silhouette_grad", 1 if on else 0)
+
+
 def set_tight_culling(on=True):
     """Opt in to alpha-aware tile rectangles (include/dgr_hip.h: dgr_set_option "tight_cull"): same images and gradients,
     ~40 % fewer tile instances; `num_rendered` and the opaque state buffers are then not the reference's.  Process-wide."""
@@ -250,11 +258,13 @@ class _C:
                                      cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
                                      dL_dout_depth, dL_dout_median_depth, dL_dout_depth_var, gt_depth, sh, degree,
                                      campos, geomBuffer, R, binningBuffer, imageBuffer, alphas, debug,
-                                     perspec_matrix, track_off, map_off, need_gaussian_grads=True, absgrad=False):
+                                     perspec_matrix, track_off, map_off, need_gaussian_grads=True, absgrad=False,
+                                     silhouette=None):
         # L/rasterize_points.cu:131-236.  `need_gaussian_grads=False` (an extension: the autograd Function passes it when
         # no Gaussian input requires a gradient, i.e. tracking) returns None for the eight per-Gaussian gradients and lets
         # the library skip their dense rows; the pose gradient is the same.  `absgrad=True` (dgr_light_backward_absgrad)
-        # appends a tenth result, the absolute screen-space gradient [P,3].
+        # appends a tenth result, the absolute screen-space gradient [P,3].  `silhouette` (dgr_light_backward_silhouette):
+        # the opacity_map gradient [1,H,W], or None (no image).
         lib = _capi.load()
         dev = means3D.device
         P = means3D.size(0)
@@ -290,14 +300,17 @@ class _C:
                 q(dL_dmeans3D), q(dL_dcov3D), q(dL_dsh), q(dL_dscales), q(dL_drotations), int(bool(debug)), None,
                 p(perspec_matrix), p(dL_dview), None, p(gt_depth), int(bool(track_off)), int(bool(map_off)),
                 p(scratch), scratch.numel())
-        if not absgrad:
+        out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview)
+        if not absgrad and silhouette is None:
             _check(lib.dgr_light_backward(*args))
-            return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-                    dL_dview)
-        dL_dmeans2D_abs = torch.empty((P, 3), **f32)
-        _check(lib.dgr_light_backward_absgrad(*args, p(dL_dmeans2D_abs)))
-        return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-                dL_dview, dL_dmeans2D_abs)
+            return out
+        dL_dmeans2D_abs = torch.empty((P, 3), **f32) if absgrad else None
+        if silhouette is None:
+            _check(lib.dgr_light_backward_absgrad(*args, p(dL_dmeans2D_abs)))
+        else:
+            gA = _f32c(silhouette, dev)
+            _check(lib.dgr_light_backward_silhouette(*args, q(dL_dmeans2D_abs), p(gA)))
+        return out + (dL_dmeans2D_abs,) if absgrad else out
 
     @_device_guarded(0)
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -345,14 +358,15 @@ class _CompiledC:
                                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                      dL_dout_median_depth, dL_dout_depth_var, gt_depth, sh, degree, campos, geomBuffer, R,
                                      binningBuffer, imageBuffer, alphas, debug, perspec_matrix, track_off, map_off,
-                                     need_gaussian_grads=True, absgrad=False):
+                                     need_gaussian_grads=True, absgrad=False, silhouette=None):
+        args = (background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
+                projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_median_depth,
+                dL_dout_depth_var, gt_depth, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, alphas,
+                bool(debug), perspec_matrix, bool(track_off), bool(map_off), bool(need_gaussian_grads))
+        if silhouette is not None:
+            return tuple(_CompiledC.ext.light_backward_silhouette(*args, silhouette, bool(absgrad)))
         fn = _CompiledC.ext.light_backward_absgrad if absgrad else _CompiledC.ext.light_backward
-        g = fn(
-            background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
-            projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_median_depth,
-            dL_dout_depth_var, gt_depth, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, alphas,
-            bool(debug), perspec_matrix, bool(track_off), bool(map_off), bool(need_gaussian_grads))
-        return tuple(g)
+        return tuple(fn(*args))
 
     @staticmethod
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -423,7 +437,8 @@ def rasterize_gaussians(
 class _RasterizeGaussians(torch.autograd.Function):
     """`means2D_abs` (absgrad, an extension): one more leaf [P,3] whose gradient is the absolute screen-space gradient
     (include/dgr_hip.h: dgr_light_backward_absgrad); None when absent.  Over either binding's forward and backward: the compiled
-    LightNode has no such input."""
+    LightNode has no such input.  With the option "silhouette_grad" on at the forward, the opacity_map gradient goes to the
+    backward as the silhouette image (dgr_light_backward_silhouette); without it, it is dropped, as the reference does."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -469,10 +484,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.num_rendered = R
         ctx.absgrad = means2D_abs is not None
         ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
+        ctx.silhouette = _capi.silhouette_on(ctx.dgr_options)
         ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, radii, sh,
                               geomBuffer, binningBuffer, imgBuffer, opacity_map, gt_depth)
         # Four of the eight outputs (radii, opacity_map, gau_uncertainty, gau_related_pixels) have no gradient input in
-        # the C++ backward; autograd would still zero-fill a gradient tensor for each of them on every backward.
+        # the C++ backward (opacity_map has one with "silhouette_grad"); autograd would still zero-fill a gradient tensor for
+        # each of them on every backward.
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(radii, gau_related_pixels)
         return color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels
@@ -528,11 +545,13 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raster_settings.track_off,
                 raster_settings.map_off)
 
+        # (option "silhouette_grad" at the forward: the opacity_map gradient is the silhouette image; an unused one is NULL)
+        kw = {"silhouette": grad_alpha} if ctx.silhouette and grad_alpha is not None else {}
         with _capi.under_options(ctx.dgr_options):  # (the autograd engine may run this on a thread of its own)
             if raster_settings.debug:
                 cpu_args = cpu_deep_copy_tuple(args)
                 try:
-                    out = _C.rasterize_gaussians_backward(*args, **({"absgrad": True} if absgrad else {}))
+                    out = _C.rasterize_gaussians_backward(*args, **({"absgrad": True} if absgrad else {}), **kw)
                 except Exception as ex:
                     torch.save(cpu_args, "snapshot_bw.dump")
                     print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
@@ -540,9 +559,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             else:
                 # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp): tracking needs none
                 if absgrad:
-                    out = _C.rasterize_gaussians_backward(*args, absgrad=True)
+                    out = _C.rasterize_gaussians_backward(*args, absgrad=True, **kw)
                 else:
-                    out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]))
+                    out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]), **kw)
         grad_means2D_abs = out[9] if absgrad else None
         out = out[:9]
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,

@@ -248,7 +248,7 @@ _ZERO_POINTS = {}  # (device, P) -> a [P, 3] zero tensor for calls whose screen-
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, viewmatrix=None, fov=None,
            HW=None, gt_depth=None, track_off=False, map_off=False, variant="light", pose_tensors=None, absgrad=False,
-           complete_pose=False):
+           complete_pose=False, silhouette_grad=False):
     """CG-SLAM's `render()` (reference README.md:33,71).
 
     `pc`: anything with the 3DGS GaussianModel accessors `get_xyz`, `get_opacity`, `get_scaling`, `get_rotation`,
@@ -266,7 +266,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     `complete_pose=True`: the backward returns the complete pose gradient (library option "pose_grad" = 1: the view-matrix
     counterpart of the Gaussians' dL_dmeans3D, with the 2D-covariance, colour and depth terms the reference leaves out) instead
     of the reference's; the forward runs under it and its backward follows.  The campos used is the one formed from
-    `viewmatrix` here (or `pose_tensors`), which is what makes the colour term exact."""
+    `viewmatrix` here (or `pose_tensors`), which is what makes the colour term exact.
+    `silhouette_grad=True`: `res["opacity_map"]` carries the exact gradient of the silhouette sum alpha T in both variants
+    (library option "silhouette_grad" = 1): a mask or opacity loss on it trains the Gaussians and the pose, instead of being
+    dropped (light) or taken as the full variant's depth variance.  The full variant's pose gradient receives it only
+    together with `complete_pose=True` (include/dgr_hip.h)."""
     if viewmatrix is None or fov is None or HW is None:
         raise ValueError("render() needs viewmatrix=W2C^T, fov=(tanfovx, tanfovy) and HW=(H, W)")
     mod = _light if variant == "light" else _full
@@ -340,7 +344,7 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
         settings = mod.GaussianRasterizationSettings(**common, perspec_matrix=perspec)
     rasterizer = mod.GaussianRasterizer(raster_settings=settings)
     shs, colors = (None, override_color) if override_color is not None else (shs_or_colors, None)
-    with _pose_mode(complete_pose):
+    with _pose_mode(complete_pose, silhouette_grad):
         if absgrad:
             abs_points = torch.zeros_like(means3D, requires_grad=True)
             out = rasterizer(means3D=means3D, means2D=screenspace_points, opacities=opacity, shs=shs,
@@ -363,23 +367,28 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, override_
     return res
 
 
-def _pose_mode(complete_pose):
-    """The block's rasterizer calls under pose_grad = 1 (their backwards follow through the forward's options snapshot)."""
-    if not complete_pose:
+def _pose_mode(complete_pose, silhouette_grad=False):
+    """The block's rasterizer calls under pose_grad = 1 and / or silhouette_grad = 1 (their backwards follow through the
+    forward's options snapshot)."""
+    modes = dict(pose_grad=1) if complete_pose else {}
+    if silhouette_grad:
+        modes["silhouette_grad"] = 1
+    if not modes:
         return _contextlib.nullcontext()
     from . import _capi
-    return _capi.thread_options(pose_grad=1)
+    return _capi.thread_options(**modes)
 
 
 def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_color=None, track_off=False, map_off=False,
-                 variant="light", absgrad=False, complete_pose=False):
+                 variant="light", absgrad=False, complete_pose=False, silhouette_grad=False):
     """`render()` for the V cameras of a keyframe batch in ONE call of the batched entry points (`dgr_amd.batch`, SURVEY.md
     s8(f) item 2; `variant="full"`: `dgr_amd.batch_full`): the cameras share `fov` and `HW` (one sensor, V poses), every
     per-view entry of `render()`'s dict comes back with a leading view dimension, and one backward through it yields the
     Gaussians' gradients already summed over the views, the pose gradient per `viewmatrix` and `viewspace_points.grad`
     ([V,P,3]) per view.  `cameras`: sequence of dicts with `viewmatrix` (W2C^T), `fov`, `HW`, `gt_depth` and optionally
     `viewpoint_camera`.  The full variant has no track_off / map_off.  `absgrad=True`: as in `render()`, with
-    `viewspace_points_abs` [V,P,3].  `complete_pose=True`: every view's pose gradient is the complete one, as in `render()`."""
+    `viewspace_points_abs` [V,P,3].  `complete_pose=True`: every view's pose gradient is the complete one, as in `render()`.
+    `silhouette_grad=True`: every view's `opacity_map` carries the exact silhouette gradient, as in `render()`."""
     from . import batch as _batch
     if variant not in ("light", "full"):
         raise ValueError(f"unknown variant {variant!r}")
@@ -450,7 +459,7 @@ def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_col
     shs, colors = (None, override_color) if override_color is not None else (shs_or_colors, None)
     if variant == "full":
         from .batch_full import GaussianRasterizerBatchFull
-        with _pose_mode(complete_pose):
+        with _pose_mode(complete_pose, silhouette_grad):
             color, radii, depth, uncertainty = GaussianRasterizerBatchFull(settings)(
                 means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors, scales=scaling, rotations=rotation,
                 viewmatrices=viewmatrices, gt_depths=gt_depths, means2D_abs=abs_points)
@@ -459,7 +468,7 @@ def render_views(cameras, pc, pipe, bg_color, scaling_modifier=1.0, override_col
         if absgrad:
             res["viewspace_points_abs"] = abs_points
         return res
-    with _pose_mode(complete_pose):
+    with _pose_mode(complete_pose, silhouette_grad):
         color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels = \
             _batch.GaussianRasterizerBatch(settings)(means3D, screenspace_points, opacity, shs=shs, colors_precomp=colors,
                                                      scales=scaling, rotations=rotation, viewmatrices=viewmatrices,
@@ -502,7 +511,8 @@ class _ViewOf(_Mapping):
         return len(self._names)
 
 
-def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None, absgrad=False, **render_kwargs):
+def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None, absgrad=False, silhouette_grad=False,
+                       **render_kwargs):
     """`render_batch` through ONE batched forward and ONE batched backward (`render_views`): `loss_fn(out_k, k)` sees the
     dict of view k (slices of the batched outputs), the losses are summed and back-propagated once.  Same gradients as
     `render_batch` -- the sum over the keyframes in the Gaussians' `.grad`, one pose gradient per `viewmatrix` -- without V - 1
@@ -510,7 +520,10 @@ def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None,
     `batch_loss_fn(out)`, if given, replaces the V calls of `loss_fn`: it sees the batched dict and returns the SUM of the
     views' losses as one scalar (then the returned list holds that one value).  `variant="full"` (a render_kwargs entry) renders
     through the full variant's batch.  `absgrad=True`: the returned dict carries `viewspace_points_abs` (render_views).
-    `complete_pose=True` (a render_kwargs entry) passes through to `render_views`: complete pose gradients."""
+    `complete_pose=True` (a render_kwargs entry) passes through to `render_views`: complete pose gradients.
+    `silhouette_grad=True`: the exact silhouette gradient of every view's `opacity_map` (render_views)."""
+    if silhouette_grad:
+        render_kwargs["silhouette_grad"] = True
     if absgrad:
         render_kwargs["absgrad"] = True
     out = render_views(cameras, pc, pipe, bg_color, **render_kwargs)
@@ -525,7 +538,8 @@ def render_batch_fused(cameras, pc, pipe, bg_color, loss_fn, batch_loss_fn=None,
     return [l_.detach() for l_ in losses], out
 
 
-def render_batch(cameras, pc, pipe, bg_color, loss_fn, views_in_flight=3, absgrad=False, **render_kwargs):
+def render_batch(cameras, pc, pipe, bg_color, loss_fn, views_in_flight=3, absgrad=False, silhouette_grad=False,
+                 **render_kwargs):
     """One mapping step over a batch of keyframes: every camera is rendered, `loss_fn(out, k)`
     is evaluated on its output dict and back-propagated, each view's forward + loss + backward on its own HIP stream
     (`dgr_amd.multiview.ViewStreams`) so that the views overlap on the GPU; gradients accumulate in the `.grad` of the
@@ -534,9 +548,12 @@ def render_batch(cameras, pc, pipe, bg_color, loss_fn, views_in_flight=3, absgra
     forward and loss still overlap the previous view's backward.  `cameras`: sequence of dicts with `viewmatrix`
     (W2C^T), `fov`, `HW` and optionally `gt_depth`, `viewpoint_camera`.  Returns the list of detached loss values
     (device tensors); the caller's stream is ordered after all views on return.  `absgrad=True`: every view's dict carries
-    `viewspace_points_abs` (render()), which `loss_fn` may keep for the densification statistics."""
+    `viewspace_points_abs` (render()), which `loss_fn` may keep for the densification statistics.  `silhouette_grad=True`: every
+    view's `opacity_map` carries the exact silhouette gradient (render())."""
     if absgrad:
         render_kwargs["absgrad"] = True
+    if silhouette_grad:
+        render_kwargs["silhouette_grad"] = True
     from .multiview import ViewStreams
     cameras = list(cameras)
     if not cameras:

@@ -302,6 +302,13 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
  *     principal point (perspec[8], perspec[9]) is exact too.  The default mode keeps the reference's symmetric-frustum Jacobian
  *     (perspec[0] and perspec[5] only, L/cuda_rasterizer/backward.cu:725-739): its pose gradient is not exact for an
  *     off-centre projection, and pose_grad = 1 is.  Other values: DGR_ERR_BAD_ARGUMENT.
+ *  "silhouette_grad" (default 0; DGR_SILHOUETTE_GRAD = 0 / 1 sets the initial value): the BINDINGS' switch for the exact gradient
+ *     of the silhouette A = sum_k alpha_k T_k (light: opacity_map; full: the uncertainty output).  No entry point reads it; it
+ *     lives here, per process and per thread and in the options word, so that both bindings and a tracker and a mapper thread
+ *     share one value and a backward runs under its forward's snapshot.  1: the bindings call the dgr_*_backward*_silhouette
+ *     entry points below with that output's gradient as the silhouette image (full: and NULL as dL_duncertainties).  0: they pass
+ *     no image (light: the opacity_map gradient is dropped, as the reference does; full: it goes to dL_duncertainties, the
+ *     reference's variance form).  Other values: DGR_ERR_BAD_ARGUMENT.
  *  "tight_cull": 1 = alpha-aware tile rectangles.  The reference gives a Gaussian every tile its
  *     3-sigma_max circle touches (cuda_rasterizer/forward.cu:229-237, auxiliary.h:46-56); with this option the rectangle
  *     is cut down to the box where alpha can reach 15/255.  Images and gradients are unchanged, but num_rendered, the
@@ -335,12 +342,12 @@ int dgr_set_option(const char* name, int value);
 int dgr_get_option(const char* name);
 
 /* Per-THREAD values of the options that change what a call computes -- "alpha_mode" (and its older name "fast_alpha"),
- * "tight_cull", "deterministic_grads", "pose_grad" -- overriding the process-wide ones above for the calling thread's next calls (value < 0:
+ * "tight_cull", "deterministic_grads", "pose_grad", "silhouette_grad" -- overriding the process-wide ones above for the calling thread's next calls (value < 0:
  * inherit again).  A tracker and a mapper thread of one process hold different settings this way, and nothing a thread sets
  * reaches launches that are already queued: every entry point reads its options once, when it is called.  (The reference has
  * no options; its one compile-time choice is the variant.)  dgr_get_thread_option = the value the calling thread's next call
- * uses.  dgr_thread_options_effective() packs the four (each field value + 1: bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
- * deterministic_grads, 12-15 pose_grad) and dgr_thread_options_swap(word) installs such a word as the thread's overrides (field 0 = inherit;
+ * uses.  dgr_thread_options_effective() packs the five (each field value + 1: bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
+ * deterministic_grads, 12-15 pose_grad, 16-19 silhouette_grad) and dgr_thread_options_swap(word) installs such a word as the thread's overrides (field 0 = inherit;
  * word < 0: only read) and returns the previous one -- what an autograd binding uses to run a backward, on whatever thread the
  * engine picks, under its forward's options. */
 int dgr_set_thread_option(const char* name, int value);
@@ -532,6 +539,59 @@ int dgr_full_backward_batch_absgrad(void* stream, int n_views, const dgr_full_vi
                                     const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity, float* dL_dcolor,
                                     float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                                     float* const* dL_dmean2D_abs);
+
+/* ---- the exact silhouette gradient ----
+ * Each function takes its _absgrad namesake's arguments, in the same order, plus dL_dpix_silhouette, and otherwise does exactly
+ * what the namesake does.  dL_dpix_silhouette is an [H,W] device image dL/dA (one-view forms) or a HOST array of n_views such
+ * device pointers (batch forms); the array may be NULL, and so may any entry.  A = sum_k alpha_k T_k is the pixel's silhouette
+ * (light: the opacity_map output, 1 - T_final; full: the uncertainty output), and dA/dalpha_k = T_final / (1 - alpha_k) -- the
+ * shape of the background term, so the blend backwards take it into that term's per-pixel constant:
+ *     dL/dalpha_k += T_final (dL/dA - <bg, dL/dC>) / (1 - alpha_k)
+ * and every gradient downstream of dL/dalpha carries it (means2D, conics, opacities, means3D, scales, rotations, the pose gradient,
+ * absgrad).  A NULL image gives bit for bit what the namesake gives.  In the full variant dL_duncertainties keeps the reference's
+ * meaning (the depth-variance form): a caller that wants the exact gradient passes NULL there and the image here; given both,
+ * the two terms add.  Full-variant pose caveat: with pose_grad = 0 its dL_dview comes from the reference's colour-only and
+ * front-most-depth sums, which no background share reaches -- so the silhouette term does not reach it either, and dL_dview is
+ * the same with and without the image; with pose_grad = 1 it comes from the mean2D sums and carries the term.
+ * Same contract as the namesakes: no host synchronisation, capturable into a hipGraph, P == 0 handled; absgrad's refusals only
+ * when an absgrad output is given. */
+int dgr_light_backward_silhouette(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                                  const float* means3D, const float* shs, const float* colors_precomp, const float* alphas,
+                                  const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                                  const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                                  float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                                  const float* dL_dpix, const float* dL_dpix_depth, const float* dL_dpix_median_depth,
+                                  const float* dL_dpix_depth_var, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity,
+                                  float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
+                                  float* dL_dscale, float* dL_drot, int debug, float* dgndcs_dviewmatrix,
+                                  const float* perspec_matrix, float* dL_dview, float* dg_camd_dviewmatrix,
+                                  const float* gt_depth, int track_off, int map_off, char* scratch, size_t scratch_bytes,
+                                  float* dL_dmean2D_abs, const float* dL_dpix_silhouette);
+int dgr_full_backward_silhouette(void* stream, int P, int D, int M, int R, const float* background, int width, int height,
+                                 const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                                 float scale_modifier, const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                                 const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                                 char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                                 const float* dL_depths, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                                 float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
+                                 float* dpixel_dgc, int* gau_id_list, int* pix_id_list, float* dgc_dCam_position, float* dpixel_dndcs,
+                                 const float* perspec_matrix, float* dgndcs_dviewmatrix, float* dpixel_dinvcovs,
+                                 float* dgc_invcovs_dT, float* dL_dview, float* dL_dgau_depth, float* ddepth_dndcs,
+                                 float* ddepth_dinvcovs, const float* gt_depth, const float* dL_duncertainties, char* scratch,
+                                 size_t scratch_bytes, float* dL_dmean2D_abs, const float* dL_dpix_silhouette);
+int dgr_light_backward_batch_silhouette(void* stream, int n_views, const dgr_light_view_grad* views, int P, int D, int M,
+                                        const float* background, int width, int height, const float* means3D, const float* shs,
+                                        const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                        const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity,
+                                        float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                                        float* dL_drot, int track_off, int map_off, float* const* dL_dmean2D_abs,
+                                        const float* const* dL_dpix_silhouette);
+int dgr_full_backward_batch_silhouette(void* stream, int n_views, const dgr_full_view_grad* views, int P, int D, int M,
+                                       const float* background, int width, int height, const float* means3D, const float* shs,
+                                       const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                                       const float* cov3D_precomp, float tan_fovx, float tan_fovy, float* dL_dopacity,
+                                       float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
+                                       float* dL_drot, float* const* dL_dmean2D_abs, const float* const* dL_dpix_silhouette);
 
 /* Debug: while `device_words` (8 x uint64 per bin_tiles workgroup, caller-owned device memory) is non-NULL, every bin_tiles
  * workgroup stores phase time stamps (100 MHz wall clock) and its segment's sizes there: profiles/r9/bin_tiles_trace.py. */
