@@ -441,19 +441,20 @@ void on_backward_scratch(const c10::Device& dev, void* st, size_t nscr, Call cal
     check(rc);
 }
 
-// absgrad: a backward's results and, last, the absolute screen-space gradient [P,3] -- or, for a batch of V views, every view's
-// [V,P,3] (every row written).  `impl` takes the per-view output pointers.
-template <typename Impl>
-std::vector<Tensor> with_absgrad(const Tensor& means3D, long V, Impl impl) {
-    const long P = means3D.size(0);
-    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(means3D.device());
-    Tensor abs = V ? at::empty({V, P, 3}, f32) : at::empty({P, 3}, f32);
-    float* av[DGR_MAX_BATCH_VIEWS] = {};
-    for (long v = 0; v < std::max(V, 1L) && v < DGR_MAX_BATCH_VIEWS && P > 0; v++) av[v] = row<float>(abs, v);
-    std::vector<Tensor> g = impl(av);
-    g.push_back(std::move(abs));
-    return g;
-}
+// absgrad: a backward's tenth result, the absolute screen-space gradient [P,3] -- or, for a batch of V views, every view's
+// [V,P,3] (every row written) -- and the per-view output pointers; neither when `on` is false.
+struct AbsGrad {
+    Tensor t;
+    float* view[DGR_MAX_BATCH_VIEWS] = {};
+    AbsGrad(bool on, const Tensor& means3D, long V) {
+        if (!on) return;
+        const long P = means3D.size(0);
+        const auto f32 = at::TensorOptions().dtype(at::kFloat).device(means3D.device());
+        t = V ? at::empty({V, P, 3}, f32) : at::empty({P, 3}, f32);
+        for (long v = 0; v < std::max(V, 1L) && v < DGR_MAX_BATCH_VIEWS && P > 0; v++) view[v] = row<float>(t, v);
+    }
+    float* const* views() const { return t.defined() ? view : nullptr; }
+};
 
 // The flat arena of the eight per-Gaussian gradients (dgr_amd.light._grad_arena): segments in the order means3D, means2D,
 // sh, opacity, scales, rotations | cov3D, colors, 256-byte aligned; the first six are one contiguous span = the multi-GPU
@@ -474,17 +475,19 @@ inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g, float** 
 // L/rasterize_points.cu:131-236.  Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
 // dL_drotations, dL_dview [1,4,4]); the first eight are windows of one flat arena (grad_arena above), or undefined tensors
 // (None) when need_gaussian_grads is false (tracking: the library then skips every dense per-Gaussian row).
-// abs_out (absgrad, dgr_light_backward_absgrad): NULL, or the [P,3] absolute screen-space gradient
-// dL_dout_alpha (option "silhouette_grad", dgr_light_backward_silhouette): the opacity_map gradient [1,H,W], or undefined / empty (NULL)
-std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
+// dL_dout_alpha (option "silhouette_grad", dgr_light_backward_silhouette): the opacity_map gradient [1,H,W] as the silhouette
+// image, or undefined / empty (NULL)
+// absgrad (dgr_light_backward_absgrad): a tenth result, the [P,3] absolute screen-space gradient
+std::vector<Tensor> light_backward(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
                                    const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
                                    const Tensor& viewmatrix_, const Tensor& projmatrix_, double tan_fovx, double tan_fovy,
                                    const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_median,
                                    const Tensor& dL_dout_var, const Tensor& gt_depth_, const Tensor& sh_, long degree,
                                    const Tensor& campos_, const Tensor& geomBuffer, long R, const Tensor& binningBuffer,
                                    const Tensor& imageBuffer, const Tensor& alphas_, bool debug, const Tensor& perspec_,
-                                   bool track_off, bool map_off, bool need_gaussian_grads, float* abs_out,
-                                   const Tensor& dL_dout_alpha = Tensor()) {
+                                   bool track_off, bool map_off, bool need_gaussian_grads, const Tensor& dL_dout_alpha,
+                                   bool absgrad) {
+    AbsGrad abs(absgrad, means3D_, 0);
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -520,32 +523,11 @@ std::vector<Tensor> light_backward_impl(const Tensor& background, const Tensor& 
                                              ptr<float>(gD), ptr<float>(gM), ptr<float>(gV), gp[0], nullptr, gp[2], gp[1], nullptr,
                                              gp[3], gp[4],
                                              gp[5], gp[6], gp[7], debug ? 1 : 0, nullptr, ptr<float>(perspec), g[8].data_ptr<float>(), nullptr,
-                                             ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, scratch, nscr, abs_out, ptr<float>(gA));
+                                             ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, scratch, nscr, abs.view[0], ptr<float>(gA));
     });
+    if (absgrad) g.push_back(std::move(abs.t));
     return g;
 }
-#define DGR_LIGHT_BWD_PARAMS                                                                                                         \
-    const Tensor &background, const Tensor &means3D, const Tensor &radii, const Tensor &colors, const Tensor &scales,               \
-        const Tensor &rotations, double scale_modifier, const Tensor &cov3D, const Tensor &viewmatrix, const Tensor &projmatrix,     \
-        double tan_fovx, double tan_fovy, const Tensor &dL_dout_color, const Tensor &dL_dout_depth, const Tensor &dL_dout_median,    \
-        const Tensor &dL_dout_var, const Tensor &gt_depth, const Tensor &sh, long degree, const Tensor &campos,                     \
-        const Tensor &geomBuffer, long R, const Tensor &binningBuffer, const Tensor &imageBuffer, const Tensor &alphas, bool debug, \
-        const Tensor &perspec, bool track_off, bool map_off, bool need_gaussian_grads
-#define DGR_LIGHT_BWD_ARGS                                                                                                         \
-    background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tan_fovx, tan_fovy,     \
-        dL_dout_color, dL_dout_depth, dL_dout_median, dL_dout_var, gt_depth, sh, degree, campos, geomBuffer, R, binningBuffer,    \
-        imageBuffer, alphas, debug, perspec, track_off, map_off, need_gaussian_grads
-std::vector<Tensor> light_backward(DGR_LIGHT_BWD_PARAMS) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, nullptr); }
-std::vector<Tensor> light_backward_absgrad(DGR_LIGHT_BWD_PARAMS) {
-    return with_absgrad(means3D, 0, [&](float* const* abs) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, abs[0]); });
-}
-// silhouette: light_backward (absgrad: light_backward_absgrad) with the opacity_map gradient dL_dout_alpha [1,H,W] as the silhouette
-// image (an empty tensor: NULL, the namesake's results)
-std::vector<Tensor> light_backward_silhouette(DGR_LIGHT_BWD_PARAMS, const Tensor& dL_dout_alpha, bool absgrad) {
-    if (!absgrad) return light_backward_impl(DGR_LIGHT_BWD_ARGS, nullptr, dL_dout_alpha);
-    return with_absgrad(means3D, 0, [&](float* const* abs) { return light_backward_impl(DGR_LIGHT_BWD_ARGS, abs[0], dL_dout_alpha); });
-}
-
 
 // ------------------------------------------------------------------------------------------------ full variant
 // F/rasterize_points.cu:35-120.  Modes as light_forward_core.
@@ -626,16 +608,18 @@ full_forward(const Tensor& background, const Tensor& means3D, const Tensor& colo
 }
 
 // F/rasterize_points.cu:122-239; returns the nine gradients in the reference's order, dL_dview as [4,4]
-// abs_out: as light_backward_impl's; dL_dout_sil: the exact silhouette gradient image (dgr_full_backward_silhouette) or undefined
-std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
+// dL_dout_sil: the exact silhouette gradient image [1,H,W] (dgr_full_backward_silhouette) or undefined / empty; dL_dout_unc keeps
+// the reference's variance form (the bindings pass an empty tensor there when the option is on); absgrad: as light_backward's
+std::vector<Tensor> full_backward(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
                                   const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
                                   const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
                                   double tan_fovy, const Tensor& dL_dout_color, const Tensor& dL_dout_depth,
                                   const Tensor& dL_dout_unc, const Tensor& sh_, long degree, const Tensor& campos_,
                                   const Tensor& geomBuffer, long R, const Tensor& binningBuffer, const Tensor& imageBuffer,
-                                  long NG, const Tensor& perspec_, bool need_gaussian_grads, float* abs_out,
-                                  const Tensor& dL_dout_sil = Tensor()) {
+                                  long NG, const Tensor& perspec_, bool need_gaussian_grads, const Tensor& dL_dout_sil,
+                                  bool absgrad) {
     (void)NG;
+    AbsGrad abs(absgrad, means3D_, 0);
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -664,29 +648,10 @@ std::vector<Tensor> full_backward_impl(const Tensor& background, const Tensor& m
                                             gp[7], nullptr,
                                             nullptr, nullptr, nullptr, nullptr, ptr<float>(perspec), nullptr, nullptr, nullptr,
                                             g[8].data_ptr<float>(), nullptr, nullptr, nullptr, ptr<float>(gt), ptr<float>(gU),
-                                            scratch, nscr, abs_out, ptr<float>(gS));
+                                            scratch, nscr, abs.view[0], ptr<float>(gS));
     });
+    if (absgrad) g.push_back(std::move(abs.t));
     return g;
-}
-#define DGR_FULL_BWD_PARAMS                                                                                                          \
-    const Tensor &background, const Tensor &means3D, const Tensor &radii, const Tensor &colors, const Tensor &scales,               \
-        const Tensor &rotations, double scale_modifier, const Tensor &cov3D, const Tensor &viewmatrix, const Tensor &gt_depth,       \
-        const Tensor &projmatrix, double tan_fovx, double tan_fovy, const Tensor &dL_dout_color, const Tensor &dL_dout_depth,      \
-        const Tensor &dL_dout_unc, const Tensor &sh, long degree, const Tensor &campos, const Tensor &geomBuffer, long R,          \
-        const Tensor &binningBuffer, const Tensor &imageBuffer, long NG, const Tensor &perspec, bool need_gaussian_grads
-#define DGR_FULL_BWD_ARGS                                                                                                          \
-    background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrix, gt_depth, projmatrix, tan_fovx,     \
-        tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_unc, sh, degree, campos, geomBuffer, R, binningBuffer, imageBuffer, NG,   \
-        perspec, need_gaussian_grads
-std::vector<Tensor> full_backward(DGR_FULL_BWD_PARAMS) { return full_backward_impl(DGR_FULL_BWD_ARGS, nullptr); }
-std::vector<Tensor> full_backward_absgrad(DGR_FULL_BWD_PARAMS) {
-    return with_absgrad(means3D, 0, [&](float* const* abs) { return full_backward_impl(DGR_FULL_BWD_ARGS, abs[0]); });
-}
-// silhouette: full_backward (absgrad: full_backward_absgrad) with dL_dout_sil [1,H,W] as the exact silhouette image; dL_dout_unc
-// keeps the reference's variance form (the bindings pass an empty tensor there when the option is on)
-std::vector<Tensor> full_backward_silhouette(DGR_FULL_BWD_PARAMS, const Tensor& dL_dout_sil, bool absgrad) {
-    if (!absgrad) return full_backward_impl(DGR_FULL_BWD_ARGS, nullptr, dL_dout_sil);
-    return with_absgrad(means3D, 0, [&](float* const* abs) { return full_backward_impl(DGR_FULL_BWD_ARGS, abs[0], dL_dout_sil); });
 }
 
 // ------------------------------------------------------------------------------------------------ autograd nodes
@@ -816,11 +781,11 @@ struct LightNode : public torch::autograd::Function<LightNode> {
         const int options = (int)d["options"].toInt();
         const Tensor gA = silhouette_on(options) && grad[5].defined() ? grad[5] : Tensor();
         const UnderOptions under(options);  // (the engine may run this node on a thread of its own)
-        std::vector<Tensor> g = light_backward_impl(sv[13], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4],
-                                                    sv[5], sv[14], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gM, gV, sv[12],
-                                                    sv[7], d["degree"].toInt(), sv[15], sv[8], d["R"].toInt(), sv[9], sv[10], sv[11], false,
-                                                    sv[16], d["track_off"].toBool(), d["map_off"].toBool(), needs_gaussian_grads(ctx),
-                                                    nullptr, gA);
+        std::vector<Tensor> g = light_backward(sv[13], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4],
+                                               sv[5], sv[14], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gM, gV, sv[12],
+                                               sv[7], d["degree"].toInt(), sv[15], sv[8], d["R"].toInt(), sv[9], sv[10], sv[11], false,
+                                               sv[16], d["track_off"].toBool(), d["map_off"].toBool(), needs_gaussian_grads(ctx), gA,
+                                               /*absgrad=*/false);
         consume_post_backward_wait(stream_of(dev));
         // the reference sums a [H*W,4,4] buffer over dim 0 (L/__init__.py:160-161); here it is [1,4,4], already reduced
         g[8] = view_of(g[8], 0, {4, 4}, at::kFloat);
@@ -884,10 +849,10 @@ struct FullNode : public torch::autograd::Function<FullNode> {
         const Tensor gU = grad[3].defined() ? grad[3] : Tensor();
         const bool sil = silhouette_on(options);
         const UnderOptions under(options);
-        std::vector<Tensor> g = full_backward_impl(sv[12], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4], sv[5],
-                                                   sv[11], sv[13], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD,
-                                                   sil ? Tensor() : gU, sv[7], d["degree"].toInt(), sv[14], sv[8], d["R"].toInt(), sv[9],
-                                                   sv[10], 0, sv[15], needs_gaussian_grads(ctx), nullptr, sil ? gU : Tensor());
+        std::vector<Tensor> g = full_backward(sv[12], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4], sv[5],
+                                              sv[11], sv[13], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD,
+                                              sil ? Tensor() : gU, sv[7], d["degree"].toInt(), sv[14], sv[8], d["R"].toInt(), sv[9],
+                                              sv[10], 0, sv[15], needs_gaussian_grads(ctx), sil ? gU : Tensor(), /*absgrad=*/false);
         consume_post_backward_wait(stream_of(dev));
         return node_grads(g, 23);
     }
@@ -998,20 +963,18 @@ inline int rendered_of(const std::vector<long>& num_rendered, long v) { return (
 
 // Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
 // the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).
-#define DGR_LIGHT_BWD_BATCH_PARAMS \
-    const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_, const Tensor& scales_, \
-        const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_, const Tensor& viewmatrices_, \
-        const Tensor& projmatrices_, double tan_fovx, double tan_fovy, const Tensor& dL_dout_color, \
-        const Tensor& dL_dout_depth, const Tensor& dL_dout_median, const Tensor& dL_dout_var, const Tensor& gt_depths_, \
-        const Tensor& sh_, long degree, const Tensor& campos_, const Tensor& geom, const Tensor& binning, const Tensor& img, \
-        const Tensor& alphas_, const Tensor& perspec_, bool track_off, bool map_off, bool need_gaussian_grads, \
-        bool need_means2D, const std::vector<long>& num_rendered
-#define DGR_LIGHT_BWD_BATCH_ARGS \
-    background, means3D_, radii, colors_, scales_, rotations_, scale_modifier, cov3D_, viewmatrices_, projmatrices_, tan_fovx, \
-        tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_median, dL_dout_var, gt_depths_, sh_, degree, campos_, geom, binning, \
-        img, alphas_, perspec_, track_off, map_off, need_gaussian_grads, need_means2D, num_rendered
-// sil (silhouette): every view's opacity_map gradient [V,1,H,W], or undefined / empty (no silhouette image)
-std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float* const* abs_views, const Tensor& sil = Tensor()) {
+// sil (silhouette, dgr_light_backward_batch_silhouette): every view's opacity_map gradient [V,1,H,W], or undefined / empty (no
+// silhouette image); absgrad (dgr_light_backward_batch_absgrad): a tenth result, every view's absolute screen-space gradient [V,P,3]
+std::vector<Tensor> light_backward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
+                                         const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
+                                         const Tensor& viewmatrices_, const Tensor& projmatrices_, double tan_fovx, double tan_fovy,
+                                         const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_median,
+                                         const Tensor& dL_dout_var, const Tensor& gt_depths_, const Tensor& sh_, long degree,
+                                         const Tensor& campos_, const Tensor& geom, const Tensor& binning, const Tensor& img,
+                                         const Tensor& alphas_, const Tensor& perspec_, bool track_off, bool map_off,
+                                         bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered,
+                                         const Tensor& sil, bool absgrad) {
+    AbsGrad abs(absgrad, means3D_, viewmatrices_.size(0));
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -1041,22 +1004,9 @@ std::vector<Tensor> light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_PARAMS, float*
                                               ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(scales),
                                               (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx,
                                               (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3], o.gp[4], o.gp[5], o.gp[6], o.gp[7],
-                                              track_off ? 1 : 0, map_off ? 1 : 0, abs_views, gA.numel() ? sv : nullptr));
+                                              track_off ? 1 : 0, map_off ? 1 : 0, abs.views(), gA.numel() ? sv : nullptr));
+    if (absgrad) o.g.push_back(std::move(abs.t));
     return o.g;
-}
-std::vector<Tensor> light_backward_batch(DGR_LIGHT_BWD_BATCH_PARAMS) {
-    return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, nullptr);
-}
-// absgrad: the nine results of light_backward_batch and, tenth, every view's absolute screen-space gradient [V,P,3]
-std::vector<Tensor> light_backward_batch_absgrad(DGR_LIGHT_BWD_BATCH_PARAMS) {
-    return with_absgrad(means3D_, viewmatrices_.size(0),
-                        [&](float* const* abs) { return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, abs); });
-}
-// silhouette: light_backward_batch (absgrad: _absgrad) with every view's opacity_map gradient dL_dout_alpha [V,1,H,W] (empty: none)
-std::vector<Tensor> light_backward_batch_silhouette(DGR_LIGHT_BWD_BATCH_PARAMS, const Tensor& dL_dout_alpha, bool absgrad) {
-    if (!absgrad) return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, nullptr, dL_dout_alpha);
-    return with_absgrad(means3D_, viewmatrices_.size(0),
-                        [&](float* const* abs) { return light_backward_batch_impl(DGR_LIGHT_BWD_BATCH_ARGS, abs, dL_dout_alpha); });
 }
 
 // The full variant's batch (include/dgr_hip.h: dgr_full_forward_batch / _backward_batch; dgr_amd/batch_full.py), same contract.
@@ -1098,19 +1048,17 @@ full_forward_batch(const Tensor& background, const Tensor& means3D_, const Tenso
 // Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
 // the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).  An undefined or
 // empty dL_dout_unc: no view's loss used the uncertainty image (the lean blend backward).
-#define DGR_FULL_BWD_BATCH_PARAMS \
-    const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_, const Tensor& scales_, \
-        const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_, const Tensor& viewmatrices_, \
-        const Tensor& projmatrices_, double tan_fovx, double tan_fovy, const Tensor& dL_dout_color, \
-        const Tensor& dL_dout_depth, const Tensor& dL_dout_unc, const Tensor& gt_depths_, const Tensor& sh_, long degree, \
-        const Tensor& campos_, const Tensor& geom, const Tensor& binning, const Tensor& img, const Tensor& perspec_, \
-        bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered
-#define DGR_FULL_BWD_BATCH_ARGS \
-    background, means3D_, radii, colors_, scales_, rotations_, scale_modifier, cov3D_, viewmatrices_, projmatrices_, tan_fovx, \
-        tan_fovy, dL_dout_color, dL_dout_depth, dL_dout_unc, gt_depths_, sh_, degree, campos_, geom, binning, img, perspec_, \
-        need_gaussian_grads, need_means2D, num_rendered
-// sil (silhouette): every view's exact silhouette gradient [V,1,H,W], or undefined / empty
-std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* const* abs_views, const Tensor& sil = Tensor()) {
+// sil (silhouette, dgr_full_backward_batch_silhouette): every view's exact silhouette gradient [V,1,H,W], or undefined / empty;
+// absgrad (dgr_full_backward_batch_absgrad): a tenth result, every view's absolute screen-space gradient [V,P,3]
+std::vector<Tensor> full_backward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
+                                        const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
+                                        const Tensor& viewmatrices_, const Tensor& projmatrices_, double tan_fovx, double tan_fovy,
+                                        const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_unc,
+                                        const Tensor& gt_depths_, const Tensor& sh_, long degree, const Tensor& campos_,
+                                        const Tensor& geom, const Tensor& binning, const Tensor& img, const Tensor& perspec_,
+                                        bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered,
+                                        const Tensor& sil, bool absgrad) {
+    AbsGrad abs(absgrad, means3D_, viewmatrices_.size(0));
     const c10::Device dev = means3D_.device();
     c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
     const int P = (int)means3D_.size(0);
@@ -1138,23 +1086,10 @@ std::vector<Tensor> full_backward_batch_impl(DGR_FULL_BWD_BATCH_PARAMS, float* c
     check(dgr_full_backward_batch_silhouette(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
                                              ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(scales),
                                              (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx,
-                                             (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3], o.gp[4], o.gp[5], o.gp[6], o.gp[7], abs_views,
+                                             (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3], o.gp[4], o.gp[5], o.gp[6], o.gp[7], abs.views(),
                                              gS.numel() ? sv : nullptr));
+    if (absgrad) o.g.push_back(std::move(abs.t));
     return o.g;
-}
-std::vector<Tensor> full_backward_batch(DGR_FULL_BWD_BATCH_PARAMS) {
-    return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, nullptr);
-}
-// absgrad: the nine results of full_backward_batch and, tenth, every view's absolute screen-space gradient [V,P,3]
-std::vector<Tensor> full_backward_batch_absgrad(DGR_FULL_BWD_BATCH_PARAMS) {
-    return with_absgrad(means3D_, viewmatrices_.size(0),
-                        [&](float* const* abs) { return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, abs); });
-}
-// silhouette: full_backward_batch (absgrad: _absgrad) with every view's exact silhouette gradient dL_dout_sil [V,1,H,W] (empty: none)
-std::vector<Tensor> full_backward_batch_silhouette(DGR_FULL_BWD_BATCH_PARAMS, const Tensor& dL_dout_sil, bool absgrad) {
-    if (!absgrad) return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, nullptr, dL_dout_sil);
-    return with_absgrad(means3D_, viewmatrices_.size(0),
-                        [&](float* const* abs) { return full_backward_batch_impl(DGR_FULL_BWD_BATCH_ARGS, abs, dL_dout_sil); });
 }
 
 Tensor mark_visible(const Tensor& means3D_, const Tensor& viewmatrix_, const Tensor& projmatrix_) {  // L/rasterize_points.cu:238-256
@@ -1191,14 +1126,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("light_backward_batch", &light_backward_batch);
     m.def("full_forward_batch", &full_forward_batch);
     m.def("full_backward_batch", &full_backward_batch);
-    m.def("light_backward_absgrad", &light_backward_absgrad);
-    m.def("full_backward_absgrad", &full_backward_absgrad);
-    m.def("light_backward_batch_absgrad", &light_backward_batch_absgrad);
-    m.def("full_backward_batch_absgrad", &full_backward_batch_absgrad);
-    m.def("light_backward_silhouette", &light_backward_silhouette);
-    m.def("full_backward_silhouette", &full_backward_silhouette);
-    m.def("light_backward_batch_silhouette", &light_backward_batch_silhouette);
-    m.def("full_backward_batch_silhouette", &full_backward_batch_silhouette);
     m.def("host_prof_dump", &host_prof_dump);
     m.def("light_apply", &light_apply);
     m.def("full_apply", &full_apply);

@@ -176,6 +176,31 @@ def ptr(t):
     return t.data_ptr()
 
 
+def row_ptr(t, v):
+    """Device pointer of view v's slice of a contiguous [V, ...] tensor (NULL for None / empty)."""
+    if t is None or t.numel() == 0:
+        return None
+    return t.data_ptr() + v * t.stride(0) * t.element_size()
+
+
+def call_backward(variant, n_views, args, abs_out=None, silhouette=None):
+    """The one place that knows the three entry points of a backward (include/dgr_hip.h): dgr_<variant>_backward (n_views = 0)
+    or dgr_<variant>_backward_batch with `args`; the _absgrad namesake, which takes one more argument, when only `abs_out` is
+    given (the tensor that receives the absolute screen-space gradient, [P,3] or [V,P,3]); the _silhouette one, which takes
+    both, when `silhouette` is (the silhouette gradient image [1,H,W] or [V,1,H,W], contiguous fp32 on the device).  Each goes
+    in as one device pointer, or (batches) as a host array of n_views device pointers.  Returns the entry point's result."""
+    def arg(t):
+        if t is None or not n_views:
+            return ptr(t)
+        return (C.c_void_p * n_views)(*(row_ptr(t, v) for v in range(n_views)))
+    name = f"dgr_{variant}_backward" + ("_batch" if n_views else "")
+    if silhouette is not None:
+        name, args = name + "_silhouette", (*args, arg(abs_out), arg(silhouette))
+    elif abs_out is not None:
+        name, args = name + "_absgrad", (*args, arg(abs_out))
+    return getattr(load(), name)(*args)
+
+
 def stream_handle(device_index=None):
     """Raw handle of torch's current HIP stream ON THE GIVEN DEVICE -- pass the index of the device the tensors live on
     (the private torch binding is ~20x cheaper than building a Stream object)."""

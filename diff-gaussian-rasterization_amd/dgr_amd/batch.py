@@ -16,7 +16,6 @@ the C ABI's batched entry points (include/dgr_hip.h: dgr_light_forward_batch / d
 
 torch supplies device memory and the current stream; every compute call goes through the C ABI.  There is no CPU fallback.
 """
-import ctypes as C
 from typing import NamedTuple
 
 import torch
@@ -49,11 +48,7 @@ class BatchRasterizationSettings(NamedTuple):
     map_off: bool
 
 
-def _row(t, v):
-    """device pointer of view v's slice of a contiguous [V, ...] tensor (NULL for None / empty)"""
-    if t is None or t.numel() == 0:
-        return None
-    return t.data_ptr() + v * t.stride(0) * t.element_size()
+_row = _capi.row_ptr
 
 
 def _ext():
@@ -157,11 +152,9 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
         args = (bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                 viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD, gM, gV, gt_depths, sh,
                 int(degree), campos, geom, binning, img, alphas, perspec_matrix, bool(track_off),
-                bool(map_off), bool(need_gaussian_grads), bool(need_means2D), num_rendered)
-        if silhouette is not None:
-            return tuple(ext.light_backward_batch_silhouette(*args, silhouette, bool(absgrad)))
-        fn = ext.light_backward_batch_absgrad if absgrad else ext.light_backward_batch
-        return tuple(fn(*args))
+                bool(map_off), bool(need_gaussian_grads), bool(need_means2D), num_rendered,
+                _light._EMPTY if silhouette is None else silhouette, bool(absgrad))
+        return tuple(ext.light_backward_batch(*args))
     if not need_gaussian_grads:
         map_off = True  # nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
     return _backward_views("light", _ViewGrad, {"alphas": alphas, "dL_dpix": gC, "dL_dpix_depth": gD, "dL_dpix_median_depth": gM,
@@ -216,22 +209,12 @@ def _backward_views(variant, ViewGrad, per_view, tail, bg, means3D, radii, color
         w.dL_dmean2D, w.dL_dview, w.scratch, w.scratch_bytes = _row(d2, v), _row(dview, v), _row(scratch, v), nscr
         w.num_rendered = num_rendered[v]
     p = _capi.ptr
-    q = lambda t: None if t is None else p(t)  # noqa: E731
     args = (_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
-            float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), q(dop), q(dcol), q(d3), q(dcov),
-            q(dsh), q(dsc), q(drot)) + tail
+            float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), p(dop), p(dcol), p(d3), p(dcov),
+            p(dsh), p(dsc), p(drot)) + tail
     out = (d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview)
-    if not absgrad and silhouette is None:
-        _light._check(getattr(lib, f"dgr_{variant}_backward_batch")(*args))
-        return out
     dabs = torch.empty((V, P, 3), **f32) if absgrad else None
-    abs_views = (C.c_void_p * V)(*(_row(dabs, v) for v in range(V))) if absgrad else None
-    if silhouette is None:
-        _light._check(getattr(lib, f"dgr_{variant}_backward_batch_absgrad")(*args, abs_views))
-    else:
-        sil = c(silhouette, dev)
-        _light._check(getattr(lib, f"dgr_{variant}_backward_batch_silhouette")(
-            *args, abs_views, (C.c_void_p * V)(*(_row(sil, v) for v in range(V)))))
+    _light._check(_capi.call_backward(variant, V, args, dabs, None if silhouette is None else c(silhouette, dev)))
     return out + (dabs,) if absgrad else out
 
 

@@ -64,11 +64,9 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
         args = (bg, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp,
                 viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD,
                 e if gU is None else gU, gt_depths, sh, int(degree), campos, geom, binning, img,
-                perspec_matrix, bool(need_gaussian_grads), bool(need_means2D), num_rendered)
-        if silhouette is not None:
-            return tuple(ext.full_backward_batch_silhouette(*args, silhouette, bool(absgrad)))
-        fn = ext.full_backward_batch_absgrad if absgrad else ext.full_backward_batch
-        return tuple(fn(*args))
+                perspec_matrix, bool(need_gaussian_grads), bool(need_means2D), num_rendered,
+                e if silhouette is None else silhouette, bool(absgrad))
+        return tuple(ext.full_backward_batch(*args))
     return _backward_views("full", _ViewGrad, {"dL_dpix": gC, "dL_depths": gD, "dL_duncertainties": gU}, (), bg, means3D, radii,
                            colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy,
                            gt_depths, sh, degree, campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D,

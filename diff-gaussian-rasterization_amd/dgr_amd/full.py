@@ -74,7 +74,7 @@ class _C:
         seg = _grad_arena(P, M, f32) if need_gaussian_grads else dict.fromkeys(names)
         dL_dview = torch.empty((4, 4), **f32)
         scratch = torch.empty((max(lib.dgr_light_backward_scratch_bytes_r(P, W, H, int(R)), 1),), dtype=torch.uint8, device=dev)
-        p = lambda t: None if t is None else _capi.ptr(t)  # noqa: E731
+        p = _capi.ptr
         args = (_capi.stream_handle(dev.index), P, int(degree), M, int(R), p(background), W, H, p(means3D), p(sh), p(colors),
                 p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix), p(projmatrix), p(campos),
                 float(tan_fovx), float(tan_fovy), p(radii), p(geomBuffer), p(binningBuffer), p(imageBuffer), p(gC), p(gD),
@@ -83,15 +83,8 @@ class _C:
                 None, None, p(dL_dview), None, None, None, p(gt_depth), p(gU), p(scratch), scratch.numel())
         out = (seg["means2D"], seg["colors"], seg["opacity"], seg["means3D"], seg["cov3D"], seg["sh"], seg["scales"],
                seg["rotations"], dL_dview)
-        if not absgrad and silhouette is None:
-            _check(lib.dgr_full_backward(*args))
-            return out
         dL_dmeans2D_abs = torch.empty((P, 3), **f32) if absgrad else None
-        if silhouette is None:
-            _check(lib.dgr_full_backward_absgrad(*args, p(dL_dmeans2D_abs)))
-        else:
-            gS = _f32c(silhouette, dev)
-            _check(lib.dgr_full_backward_silhouette(*args, p(dL_dmeans2D_abs), p(gS)))
+        _check(_capi.call_backward("full", 0, args, dL_dmeans2D_abs, None if silhouette is None else _f32c(silhouette, dev)))
         return out + (dL_dmeans2D_abs,) if absgrad else out
 
     @_device_guarded(0)
@@ -131,11 +124,9 @@ class _CompiledC:
                                      perspec_matrix, need_gaussian_grads=True, absgrad=False, silhouette=None):
         args = (background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix, gt_depth,
                 projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_uncertainty, sh, int(degree),
-                campos, geomBuffer, int(R), binningBuffer, imageBuffer, int(NG), perspec_matrix, bool(need_gaussian_grads))
-        if silhouette is not None:
-            return tuple(_CompiledC.ext.full_backward_silhouette(*args, silhouette, bool(absgrad)))
-        fn = _CompiledC.ext.full_backward_absgrad if absgrad else _CompiledC.ext.full_backward
-        return tuple(fn(*args))
+                campos, geomBuffer, int(R), binningBuffer, imageBuffer, int(NG), perspec_matrix, bool(need_gaussian_grads),
+                _light._EMPTY if silhouette is None else silhouette, bool(absgrad))
+        return tuple(_CompiledC.ext.full_backward(*args))
 
     @staticmethod
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -232,11 +223,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         absgrad = ctx.absgrad
         grad_out_color = zeros(3) if grad_out_color is None else grad_out_color
         grad_out_depth = zeros(1) if grad_out_depth is None else grad_out_depth
-        kw = {}
+        silhouette = None
         if ctx.silhouette:  # the exact silhouette gradient: the image (or NULL, unused) there, NULL as dL_duncertainties
-            if grad_out_uncertainty is not None:
-                kw["silhouette"] = grad_out_uncertainty
-            grad_out_uncertainty = _light._EMPTY
+            silhouette, grad_out_uncertainty = grad_out_uncertainty, _light._EMPTY
         if absgrad and grad_out_uncertainty is None:  # NULL: the lean blend backward (bit-identical to a zero image)
             grad_out_uncertainty = _light._EMPTY
         grad_out_uncertainty = zeros(1) if grad_out_uncertainty is None else grad_out_uncertainty
@@ -267,10 +256,8 @@ class _RasterizeGaussians(torch.autograd.Function):
                 num_related_gaussians,
                 raster_settings.perspec_matrix)
         with _capi.under_options(ctx.dgr_options):  # (the autograd engine may run this on a thread of its own)
-            if absgrad:
-                out = _C.rasterize_gaussians_backward(*args, absgrad=True, **kw)
-            else:
-                out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]), **kw)
+            out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=absgrad or any(ctx.needs_input_grad[:8]),
+                                                  absgrad=absgrad, silhouette=silhouette)
         grad_means2D_abs = out[9] if absgrad else None
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
          grad_rotations, grad_viewmatrix) = out[:9]

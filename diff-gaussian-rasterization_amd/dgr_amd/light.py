@@ -292,24 +292,16 @@ class _C:
         # (option "deterministic_grads": + 64 bytes per tile instance; R = num_rendered, or the capacity of a lazy forward)
         scratch = torch.empty((max(lib.dgr_light_backward_scratch_bytes_r(P, W, H, int(R)), 1),), dtype=torch.uint8, device=dev)
         p = _capi.ptr
-        q = lambda t: None if t is None else p(t)  # noqa: E731
         args = (_capi.stream_handle(dev.index), P, int(degree), M, int(R), p(background), W, H, p(means3D), p(sh), p(colors),
                 p(alphas), p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), p(viewmatrix),
                 p(projmatrix), p(campos), float(tan_fovx), float(tan_fovy), p(radii), p(geomBuffer), p(binningBuffer),
-                p(imageBuffer), p(gC), p(gD), p(gM), p(gV), q(dL_dmeans2D), None, q(dL_dopacity), q(dL_dcolors), None,
-                q(dL_dmeans3D), q(dL_dcov3D), q(dL_dsh), q(dL_dscales), q(dL_drotations), int(bool(debug)), None,
+                p(imageBuffer), p(gC), p(gD), p(gM), p(gV), p(dL_dmeans2D), None, p(dL_dopacity), p(dL_dcolors), None,
+                p(dL_dmeans3D), p(dL_dcov3D), p(dL_dsh), p(dL_dscales), p(dL_drotations), int(bool(debug)), None,
                 p(perspec_matrix), p(dL_dview), None, p(gt_depth), int(bool(track_off)), int(bool(map_off)),
                 p(scratch), scratch.numel())
         out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview)
-        if not absgrad and silhouette is None:
-            _check(lib.dgr_light_backward(*args))
-            return out
         dL_dmeans2D_abs = torch.empty((P, 3), **f32) if absgrad else None
-        if silhouette is None:
-            _check(lib.dgr_light_backward_absgrad(*args, p(dL_dmeans2D_abs)))
-        else:
-            gA = _f32c(silhouette, dev)
-            _check(lib.dgr_light_backward_silhouette(*args, q(dL_dmeans2D_abs), p(gA)))
+        _check(_capi.call_backward("light", 0, args, dL_dmeans2D_abs, None if silhouette is None else _f32c(silhouette, dev)))
         return out + (dL_dmeans2D_abs,) if absgrad else out
 
     @_device_guarded(0)
@@ -362,11 +354,9 @@ class _CompiledC:
         args = (background, means3D, radii, colors, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
                 projmatrix, float(tan_fovx), float(tan_fovy), dL_dout_color, dL_dout_depth, dL_dout_median_depth,
                 dL_dout_depth_var, gt_depth, sh, int(degree), campos, geomBuffer, int(R), binningBuffer, imageBuffer, alphas,
-                bool(debug), perspec_matrix, bool(track_off), bool(map_off), bool(need_gaussian_grads))
-        if silhouette is not None:
-            return tuple(_CompiledC.ext.light_backward_silhouette(*args, silhouette, bool(absgrad)))
-        fn = _CompiledC.ext.light_backward_absgrad if absgrad else _CompiledC.ext.light_backward
-        return tuple(fn(*args))
+                bool(debug), perspec_matrix, bool(track_off), bool(map_off), bool(need_gaussian_grads),
+                _EMPTY if silhouette is None else silhouette, bool(absgrad))
+        return tuple(_CompiledC.ext.light_backward(*args))
 
     @staticmethod
     def mark_visible(means3D, viewmatrix, projmatrix):
@@ -546,22 +536,19 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raster_settings.map_off)
 
         # (option "silhouette_grad" at the forward: the opacity_map gradient is the silhouette image; an unused one is NULL)
-        kw = {"silhouette": grad_alpha} if ctx.silhouette and grad_alpha is not None else {}
+        debug = raster_settings.debug
+        cpu_args = cpu_deep_copy_tuple(args) if debug else None
         with _capi.under_options(ctx.dgr_options):  # (the autograd engine may run this on a thread of its own)
-            if raster_settings.debug:
-                cpu_args = cpu_deep_copy_tuple(args)
-                try:
-                    out = _C.rasterize_gaussians_backward(*args, **({"absgrad": True} if absgrad else {}), **kw)
-                except Exception as ex:
+            try:
+                # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp): tracking needs none
+                out = _C.rasterize_gaussians_backward(
+                    *args, need_gaussian_grads=debug or absgrad or any(ctx.needs_input_grad[:8]), absgrad=absgrad,
+                    silhouette=grad_alpha if ctx.silhouette else None)
+            except Exception:
+                if debug:
                     torch.save(cpu_args, "snapshot_bw.dump")
                     print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                    raise ex
-            else:
-                # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp): tracking needs none
-                if absgrad:
-                    out = _C.rasterize_gaussians_backward(*args, absgrad=True, **kw)
-                else:
-                    out = _C.rasterize_gaussians_backward(*args, need_gaussian_grads=any(ctx.needs_input_grad[:8]), **kw)
+                raise
         grad_means2D_abs = out[9] if absgrad else None
         out = out[:9]
         (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
