@@ -6,328 +6,31 @@
 //             per-tile sort -> blend
 //   backward: zero accumulator rows -> blend backward -> fused per-Gaussian backward -> pose reduce
 // Nothing here touches the CPU oracle; a missing GPU or a failed launch is reported, never papered over.
+// The library options are in options.hip, the status read-back in status.hip, the stage profiler in profile.hip and
+// dgr_state_export in state_export.hip.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-#include <climits>
-#include <cstdlib>
-#include <mutex>
-#include <utility>
-#include <vector>
-#include <cstdio>
-#include <cstring>
 #include <algorithm>
-#include <atomic>
-#include <mutex>
 #include <string>
-#include <thread>
 
 #include "../../include/dgr_hip.h"
 #include "dgr_common.h"
+#include "host_util.h"
 #include "kernels.h"
+#include "options.h"
+#include "profile.h"
+#include "status.h"
 
 namespace dgr {
-thread_local LaunchEvents* g_launch_events = nullptr;
+namespace {
+thread_local std::string g_last_error = "";
 }
-namespace { extern std::atomic<int> g_blend_wgs_per_cu; }
-namespace dgr {
-size_t blend_pad_bytes(const void* kernel) {
-    const int n = g_blend_wgs_per_cu.load(std::memory_order_relaxed);
-    if (n < 3 || n > 7) return 0;
-    static std::mutex mu;
-    static std::vector<std::pair<const void*, size_t>> known;  // static LDS bytes of the blend kernels seen so far
-    size_t static_lds = ~(size_t)0;
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        for (const auto& e : known)
-            if (e.first == kernel) static_lds = e.second;
-        if (static_lds == ~(size_t)0) {
-            hipFuncAttributes attr{};
-            if (hipFuncGetAttributes(&attr, kernel) != hipSuccess) return 0;
-            static_lds = attr.sharedSizeBytes;
-            known.emplace_back(kernel, static_lds);
-        }
-    }
-    // the smallest LDS claim that keeps workgroup n + 1 off a CU: n claims then leave the rest of the 160 KB to whatever else
-    // fits beside them (160 / n each, as through round 6, left nothing -- and every front-end kernel stages through LDS)
-    const size_t per = (((size_t)(160 * 1024) / (size_t)(n + 1)) & ~(size_t)255) + 256;
-    return per > static_lds ? per - static_lds : 0;
-}
-}
+void set_last_error(const std::string& text) { g_last_error = text; }
+}  // namespace dgr
+
+using namespace dgr;
 
 namespace {
-
-thread_local std::string g_last_error = "";
-
-int hip_fail(hipError_t e, const char* what) {
-    g_last_error = std::string(what) + ": " + hipGetErrorString(e);
-    return DGR_ERR_HIP;
-}
-#define HIP_TRY(expr)                                   \
-    do {                                                \
-        hipError_t _e = (expr);                         \
-        if (_e != hipSuccess) return hip_fail(_e, #expr); \
-    } while (0)
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// ---- early status (dgr_early_status_arm / _wait): num_rendered and the prefiltered flag are final after scan_blocks,
-// a tenth of the way into the forward; a caller that needs them on the host (the reference's blocking copy of
-// num_rendered) waits for a copy issued at that point instead of for the whole forward.
-struct EarlyStatus {
-    bool armed = false, pending = false;
-    hipEvent_t ev = nullptr;   // an event belongs to the device that was current when it was created:
-    int ev_device = -1;        // re-created when this thread moves to another device
-    int* pinned = nullptr;
-};
-thread_local EarlyStatus g_early;
-
-int early_status_post(const int* device_status, hipStream_t st) {
-    if (!g_early.armed) return DGR_OK;
-    g_early.armed = false;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (!g_early.ev || g_early.ev_device != dev) {
-        if (g_early.ev) HIP_TRY(hipEventDestroy(g_early.ev));
-        g_early.ev = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&g_early.ev, hipEventDisableTiming));
-        g_early.ev_device = dev;
-    }
-    if (!g_early.pinned) HIP_TRY(hipHostMalloc((void**)&g_early.pinned, 4 * sizeof(int), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(g_early.pinned, device_status, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(g_early.ev, st));
-    g_early.pending = true;
-    return DGR_OK;
-}
-
-// Waiting for a status copy that is tens of microseconds away: hipEventSynchronize parks the thread and pays a wake-up
-// of the order of 100 us when the event has not fired yet (measured: a 640x480 tracking iteration went from 0.46 to
-// 0.55 ms when the status moved 20 us later in the forward), so poll for a while first.
-hipError_t wait_event_spinning(hipEvent_t ev) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(400)) return hipEventSynchronize(ev);
-    }
-}
-
-// ---- resident backward scratch (dgr_backward_scratch_clean_arm): the next backward of this thread finds its scratch all zero and
-// leaves it all zero -- no clearing launch in front of the blend backward.
-thread_local bool g_scratch_clean_armed = false;
-
-// ---- asynchronous status read-back (dgr_status_post / _poll): the lazy mode of the bindings copies a forward's status
-// word to pinned host memory behind an event and looks at it one or two calls later.  Slots are pooled per device.
-// Two ways to fill a slot: dgr_status_post copies a device word behind an event (any status word, after the fact);
-// dgr_status_arm hands the slot to the NEXT presized forward, whose forward blend (workgroup 0, first thing) writes the word
-// straight into the slot's pinned memory (mapped into the device's address space) with a tag last -- no copy, no event, nothing
-// to wait for on the stream.  One device word owned by the slot (zero between forwards) gathers the frame's longest tile list.
-struct StatusSlot {
-    hipEvent_t ev = nullptr;
-    int* pinned = nullptr;       // host int[8]: {num_rendered, overflow, prefiltered violation, num_related | tag, longest list, -, -}
-    int* pinned_dev = nullptr;   // the same memory as the device sees it
-    uint32_t* ws = nullptr;      // device uint32[16], zero between forwards
-    int device = -1;
-    bool busy = false;
-    bool mapped = false;         // this use of the slot: armed (written by the kernels) rather than posted (copied)
-    uint32_t tag = 0;
-    int W = 0, H = 0, P = 0;     // the forward that took the arm (key of the schedule hint below)
-    hipStream_t stream = nullptr;  // ... and the stream its kernels were enqueued on (dgr_status_poll watches it while it waits)
-    bool enqueued = false;         // the forward's blend kernel -- which delivers the word -- has been enqueued
-    bool quarantined = false;      // a poll gave this slot up (timeout, stream error) while its forward may still be queued: the
-                                   // blend kernel can still write words 0-5 and its tag here, so the slot is not handed out again
-                                   // before that stream has drained (status_slot_acquire)
-};
-std::mutex g_status_mu;
-std::vector<StatusSlot> g_status_slots;
-uint32_t g_status_tag = 0;
-thread_local long g_armed_slot = -1;
-
-// ---- tile schedule policy (dgr_set_option("tile_schedule", v)): 1 = every forward runs tile_schedule_kernel (the blend kernels
-// take their tiles classes of long lists first), 0 = never (static XCD band map), 2 (default) = by the frame: a forward whose
-// status word came back through an armed slot also reports its longest tile list, and the NEXT forward of that shape
-// (device, P, W, H) skips the schedule when the longest list was within 2x the mean + 32 -- on such a frame the schedule buys
-// nothing (uniform synth-v1 scene: 1 % of the blend time) and costs a launch, a 1024-thread workgroup in front of the blend
-// (11 us at 1080p) and some of the blend's L2 locality; a clustered frame (longest list 5x the mean) gets it back one
-// forward later.  Forwards without a report (callback path, batched entry points, hipGraph capture, direct C-ABI callers that
-// never arm) keep the schedule.  Results do not depend on it: only the order in which tiles are worked on.
-std::atomic<int> g_tile_schedule{[] { const char* e = getenv("DGR_TILE_SCHEDULE"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }()};
-struct SchedHint { int device, W, H, P, on, longest; };
-std::vector<SchedHint> g_sched_hints;  // (under g_status_mu)
-bool want_schedule(int W, int H, int P) {
-    const int mode = g_tile_schedule.load(std::memory_order_relaxed);
-    if (mode != 2) return mode != 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return true;
-    std::lock_guard<std::mutex> lk(g_status_mu);
-    for (const auto& h : g_sched_hints)
-        if (h.device == dev && h.W == W && h.H == H && h.P == P) return h.on != 0;
-    return true;
-}
-// The same report also sizes the binning's row segments (segment_binning.hip: segment_shift): the longest tile list of this shape's
-// last reported frame, or -1 without one.  On a clustered frame the capacity alone says "16 tiles per segment" (the AVERAGE
-// segment fits bin_tiles' LDS) while every segment of the cluster overflows it and takes the dense path.
-int hinted_longest_list(int W, int H, int P) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    std::lock_guard<std::mutex> lk(g_status_mu);
-    for (const auto& h : g_sched_hints)
-        if (h.device == dev && h.W == W && h.H == H && h.P == P) return h.longest;
-    return -1;
-}
-void note_schedule_hint(const StatusSlot& sl, const int* word) {  // (g_status_mu held)
-    const long tiles = (long)dgr::tiles_x(sl.W) * dgr::tiles_y(sl.H);
-    if (tiles <= 0 || word[1] /* overflow: the lists were left empty */) return;
-    const long longest = word[5];
-    const int on = (longest >= 0x7fffffff || longest * tiles > 2L * word[0] + 32L * tiles) ? 1 : 0;
-    const int lg = longest >= 0x7fffffff ? -1 : (int)longest;
-    for (auto& h : g_sched_hints)
-        if (h.device == sl.device && h.W == sl.W && h.H == sl.H && h.P == sl.P) { h.on = on; h.longest = lg; return; }
-    if (g_sched_hints.size() >= 64) g_sched_hints.erase(g_sched_hints.begin());
-    g_sched_hints.push_back(SchedHint{sl.device, sl.W, sl.H, sl.P, on, lg});
-}
-
-// The armed slot of this thread, taken by a presized forward.  If the call leaves before its binning kernel is enqueued
-// (an error, P == 0) the word is completed from the host -- all zero -- so that a poll never waits for a write that will not come.
-struct ArmedReport {
-    long id = -1;
-    dgr::StatusReport rep{nullptr, 0u, nullptr};
-    bool handed_over = false;
-    ArmedReport(int W, int H, int P, hipStream_t st = nullptr) {
-        id = g_armed_slot;
-        g_armed_slot = -1;
-        if (id < 0) return;
-        std::lock_guard<std::mutex> lk(g_status_mu);
-        StatusSlot& sl = g_status_slots[(size_t)id];
-        sl.W = W; sl.H = H; sl.P = P; sl.stream = st; sl.enqueued = false;
-        rep.host = sl.pinned_dev; rep.tag = sl.tag; rep.ws = sl.ws;
-    }
-    ~ArmedReport() {
-        if (id < 0) return;
-        std::lock_guard<std::mutex> lk(g_status_mu);
-        StatusSlot& sl = g_status_slots[(size_t)id];
-        if (handed_over) { sl.enqueued = true; return; }
-        volatile int* w = sl.pinned;
-        w[0] = w[1] = w[2] = w[3] = 0; w[5] = 0x7fffffff;
-        w[4] = (int)sl.tag;
-    }
-};
-
-// ---- optional per-stage timing with HIP events on the launching stream (dgr_profile_* in dgr_hip.h).
-// Disabled by default; when a stage is selected, two events bracket that stage's launch only.
-struct StageProf {
-    const char* name;
-    bool on = false;
-    unsigned seen = 0;  // launches of this stage since it was selected
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-};
-StageProf g_prof[] = {{"zero_counters"}, {"preprocess_fwd"}, {"scan_blocks"}, {"bin_segments"}, {"bin_tiles"}, {"count_rank"},
-                      {"scan_tiles"}, {"emit_instances"}, {"sort_tiles"}, {"tile_schedule"}, {"render_fwd"}, {"zero_scratch"}, {"render_bwd"},
-                      {"preprocess_bwd"}};
-enum { ST_ZERO_FWD, ST_PRE_FWD, ST_SCAN_BLOCKS, ST_BIN_SEGMENTS, ST_BIN_TILES, ST_COUNT_RANK, ST_SCAN, ST_EMIT, ST_SORT, ST_TILE_SCHED, ST_RENDER_FWD,
-       ST_ZERO, ST_RENDER_BWD, ST_PRE_BWD, ST_COUNT };
-std::mutex g_prof_mu;
-std::atomic<int> g_profile_every{1};
-
-// dgr_set_option("tight_cull", 1): alpha-aware tile rectangles (preprocess.hip); process-wide, default off
-std::atomic<int> g_tight_cull{0};
-// dgr_set_option("alpha_mode", v): how the blend kernels evaluate alpha and T / (1 - alpha) (csrc/render_common.h).
-//   0 (default) = the reference's expression with the CPU restatement's bits (exp_p32 / div_ref, csrc/exact_math.h): alpha
-//       image, n_contrib and median depth bit-identical to the restatement, gradients within 1e-5 of it;
-//   1 (= "fast_alpha", 1) = log2(e)-scaled conic, one v_exp_f32, v_rcp_f32: every operation good to an ulp, but the light
-//       backward's T_final = 1 - alpha and its divisions by (1 - alpha) amplify the last-bit differences to 6e-5 abs at config 3;
-//   2 = as 0 with glibc's expf algorithm in the double pipe (exp_glibc; rounds 5-7's default, the oracle's exp mode 1), for A/B.
-// Set it before the forward whose backward should use it (forward and backward of a view must use the same mode).
-// Initial value from DGR_ALPHA_MODE (or DGR_FAST_ALPHA=1), for A/B runs.
-std::atomic<int> g_alpha_mode{[] {
-    const char* m = getenv("DGR_ALPHA_MODE");
-    if (m && m[0] >= '0' && m[0] <= '2' && m[1] == 0) return m[0] - '0';
-    const char* e = getenv("DGR_FAST_ALPHA");
-    return (e && e[0] == '1') ? 1 : 0;
-}()};
-// dgr_set_option("deterministic_grads", 1): the light backward (one-view entry point, alpha_mode 0) forms its gradients without
-// order-dependent float atomics (csrc/render_light.hip: DET): bit-identical run after run, at the price of an instance-major row
-// buffer (64 bytes per tile instance: zero-filled, written and read once) and a smaller batch in the blend backward.  The backward
-// then needs dgr_light_backward_scratch_bytes_r(P, W, H, R) bytes of scratch, R = the value passed as `R` (>= num_rendered).
-std::atomic<int> g_det_grads{[] { const char* e = getenv("DGR_DETERMINISTIC_GRADS"); return (e && e[0] == '1') ? 1 : 0; }()};
-
-// dgr_set_option("lane_lists", v): the lists the LIGHT blend kernels walk (csrc/render_light.hip).
-//   1 = one list per half of a quadrant wave in the forward and the tracking backward, paired lists in the mapping backward (round 8);
-//   0 = one list per quadrant wave everywhere (rounds 1-7);
-//   2 (default) = decided per FRAME on the device by the binning kernel, from the frame's own run statistics (segment_binning.hip:
-//       bin_tiles_kernel; big splats -> 0) and recorded in the frame's state, where forward and backward read it.
-// Initial value from DGR_FWD_HALVES = 0 / 1 (the switch's name when it was per process; A/B runs).
-// dgr_set_option("pose_grad", v): 0 (default) = the reference's pose-gradient terms; 1 = the complete pose gradient, the
-// view-matrix counterpart of dL_dmeans3D (csrc/preprocess.hip: bwd_view_terms<true>; include/dgr_hip.h).  A light map_off
-// backward then runs the mapping blend backward (its per-Gaussian outputs are dropped).  Initial value from DGR_POSE_GRAD = 0 / 1.
-std::atomic<int> g_pose_grad{[] { const char* e = getenv("DGR_POSE_GRAD"); return (e && e[0] == '1' && e[1] == 0) ? 1 : 0; }()};
-// dgr_set_option("silhouette_grad", v): 0 (default) / 1.  No entry point reads it: it is the bindings' switch (include/dgr_hip.h),
-// kept here so that both bindings and every thread share one value and a backward runs under its forward's snapshot.  1: the
-// bindings pass the opacity_map (light) / uncertainty (full) gradient as the dL_dpix_silhouette image of the _silhouette entry
-// points.  Initial value from DGR_SILHOUETTE_GRAD = 0 / 1.
-std::atomic<int> g_silhouette_grad{[] { const char* e = getenv("DGR_SILHOUETTE_GRAD"); return (e && e[0] == '1' && e[1] == 0) ? 1 : 0; }()};
-std::atomic<int> g_lane_lists{[] { const char* e = getenv("DGR_FWD_HALVES"); return (e && (e[0] == '0' || e[0] == '1') && e[1] == 0) ? e[0] - '0' : 2; }()};
-
-// ---- per-THREAD overrides of the four options that change what a call computes (dgr_set_thread_option, round 9).  The options
-// above are process-wide defaults; a tracker thread and a mapper thread of one process -- or a test beside a training loop -- hold
-// their own values here (-1 = inherit).  Every entry point reads its options ONCE, when it is called, and hands them to its
-// launches as template choices / kernel arguments: launches already queued (on any stream) are not affected by a later change.
-// A backward must run with its forward's alpha mode: the autograd bindings snapshot dgr_thread_options_effective() in the
-// forward and swap it in around the backward (which the autograd engine may run on another thread).
-thread_local int t_alpha_mode = -1, t_tight_cull = -1, t_det_grads = -1, t_pose_grad = -1, t_silhouette_grad = -1;
-inline int opt_alpha_mode() { return t_alpha_mode >= 0 ? t_alpha_mode : g_alpha_mode.load(std::memory_order_relaxed); }
-inline int opt_tight_cull() { return t_tight_cull >= 0 ? t_tight_cull : g_tight_cull.load(std::memory_order_relaxed); }
-inline int opt_det_grads() { return t_det_grads >= 0 ? t_det_grads : g_det_grads.load(std::memory_order_relaxed); }
-inline int opt_pose_grad() { return t_pose_grad >= 0 ? t_pose_grad : g_pose_grad.load(std::memory_order_relaxed); }
-inline int opt_silhouette_grad() { return t_silhouette_grad >= 0 ? t_silhouette_grad : g_silhouette_grad.load(std::memory_order_relaxed); }
-// dgr_set_option("lds_count", v): how the forward bins tile instances.
-//   1 (default) = the two-level segment binning (csrc/segment_binning.hip) whenever the frame's segment tables fit LDS;
-//   0 = returning global atomics on per-tile counters (csrc/binning.hip; inside preprocess_fwd when presized), which also
-//       serves frames too large for the segment tables.  (2 is accepted as a synonym of 1.)
-// Measured, round 5 (profiles/r5/): the segment binning is faster one view at a time at every size (config 3: 0.51 against
-// 0.59 ms per view, config 4: 1.71 / 1.85, config 5: 4.54 / 4.86) and equal or faster with three views in flight (0.455 /
-// 0.466, 1.57 / 1.57, 4.27 / 4.53), so nothing switches by job size or by the number of views in flight any more.
-// Initial value from DGR_LDS_COUNT (for A/B runs).
-std::atomic<int> g_lds_count{[] { const char* e = getenv("DGR_LDS_COUNT"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1; }()};
-
-// dgr_set_option("blend_wgs_per_cu", n): cap on the blend kernels' workgroups per CU (kernels.h: launch_blend); 0 = none.
-// Initial value from DGR_BLEND_WGS_PER_CU (for A/B runs).
-std::atomic<int> g_blend_wgs_per_cu{[] { const char* e = getenv("DGR_BLEND_WGS_PER_CU"); return (e && e[0] >= '3' && e[0] <= '7') ? e[0] - '0' : 0; }()};
-
-// A kernel stage hands its two events to the stage's first kernel launch (dgr::launch, kernels.h): they then hold
-// that kernel's start and end.  A stage without a kernel (the scratch memset) is bracketed with hipEventRecord.
-struct ScopedStage {
-    StageProf* p = nullptr;
-    hipStream_t st;
-    dgr::LaunchEvents le{};
-    bool kernel_stage;
-    ScopedStage(int id, hipStream_t s, bool is_kernel = true) : st(s), kernel_stage(is_kernel) {
-        if (!g_prof[id].on) return;
-        // dgr_set_option("profile_every", n): bracket every n-th launch only (the events ride in the dispatch packet
-        // and cost a little overlap between streams; a sample keeps the timed region undisturbed)
-        if (g_prof[id].seen++ % (unsigned)std::max(1, g_profile_every.load()) != 0) return;
-        p = &g_prof[id];
-        if (hipEventCreate(&le.start) != hipSuccess || hipEventCreate(&le.stop) != hipSuccess) { p = nullptr; return; }
-        le.used = false;
-        if (kernel_stage) dgr::g_launch_events = &le;
-        else (void)hipEventRecord(le.start, st);
-    }
-    ~ScopedStage() {
-        if (!p) return;
-        if (kernel_stage) {
-            dgr::g_launch_events = nullptr;
-            if (!le.used) {  // nothing was launched (empty input)
-                (void)hipEventDestroy(le.start);
-                (void)hipEventDestroy(le.stop);
-                return;
-            }
-        } else {
-            (void)hipEventRecord(le.stop, st);
-        }
-        std::lock_guard<std::mutex> lk(g_prof_mu);
-        p->ev.emplace_back(le.start, le.stop);
-    }
-};
 
 struct FwdCommon {
     int P, D, M, W, H;
@@ -341,6 +44,29 @@ struct FwdCommon {
     float *out_depth_var, *gau_uncertainty;
     int *gau_related_pixels, *radii;
 };
+
+// One view's forward arguments as the entry points of a variant take them, in the C ABI's order
+FwdCommon light_common(int P, int D, int M, const float* background, int width, int height, const float* means3D, const float* shs,
+                       const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                       const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_depth,
+                       float* out_median_depth, float* out_alpha, const float* gt_depth, float* out_depth_var, float* gau_uncertainty,
+                       int* gau_related_pixels, int* radii) {
+    return FwdCommon{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
+                     cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
+                     out_color, out_depth, out_median_depth, out_alpha, gt_depth, out_depth_var, gau_uncertainty,
+                     gau_related_pixels, radii};
+}
+// ... the full variant: the uncertainty image in the alpha slot, no light-only outputs
+FwdCommon full_common(int P, int D, int M, const float* background, int width, int height, const float* means3D, const float* shs,
+                      const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                      const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_depth,
+                      const float* gt_depth, float* out_uncertainty, int* radii) {
+    return light_common(P, D, M, background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier, rotations,
+                        cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color, out_depth, nullptr,
+                        out_uncertainty, gt_depth, nullptr, nullptr, nullptr, radii);
+}
 
 // P == 0: the reference launches nothing and returns zero-filled outputs (L/rasterize_points.cu:88).
 int zero_outputs(const FwdCommon& c, hipStream_t st) {
@@ -362,32 +88,32 @@ int zero_outputs(const FwdCommon& c, hipStream_t st) {
 // Callback path (the binning buffer is sized after a host read of num_rendered): COUNT_LDS_CALLBACK = the same segment
 // binning behind scan_blocks, COUNT_CALLBACK = the count_rank kernel on global tile counters (R = 0, or a frame too large).
 enum { COUNT_CALLBACK = 0, COUNT_FUSED = 1, COUNT_LDS = 2, COUNT_LDS_CALLBACK = 3 };
-int presized_count_mode(int W, int H, int capacity) {
-    const int v = g_lds_count.load();
-    (void)capacity;
-    const bool lds = v != 0 && dgr::segment_binning_fits(W, H);
+int presized_count_mode(int W, int H) {
+    const bool lds = option(OPT_LDS_COUNT) != 0 && dgr::segment_binning_fits(W, H);
     return lds ? COUNT_LDS : COUNT_FUSED;
 }
-int forward_front(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, hipStream_t st,
-                  const dgr::BinningView* bin = nullptr, int capacity = 0, char* image_base = nullptr,
-                  int mode = COUNT_CALLBACK) {
-    const int gx = dgr::tiles_x(c.W), gy = dgr::tiles_y(c.H), tiles = gx * gy;
-    // No memsets: preprocess clears the per-Gaussian median statistics (and, on the callback path, the tile counters);
-    // scan_blocks / scan_tiles initialise the status word.
-    dgr::PreprocessFwdArgs a{};
-    a.P = c.P; a.D = c.D; a.M = c.M; a.W = c.W; a.H = c.H; a.grid_x = gx; a.grid_y = gy;
+// The scene half of the preprocess arguments: what the views of a batch share
+void preprocess_scene(dgr::PreprocessFwdArgs& a, const FwdCommon& c) {
+    a.P = c.P; a.D = c.D; a.M = c.M; a.W = c.W; a.H = c.H; a.grid_x = dgr::tiles_x(c.W); a.grid_y = dgr::tiles_y(c.H);
     a.means3D = c.means3D; a.scales = c.scales; a.scale_modifier = c.scale_modifier; a.rotations = c.rotations;
     a.opacities = c.opacities; a.shs = c.shs; a.cov3D_precomp = c.cov3D_precomp; a.colors_precomp = c.colors_precomp;
-    a.view = c.viewmatrix; a.proj = c.projmatrix; a.campos = c.cam_pos;
     a.tan_fovx = c.tan_fovx; a.tan_fovy = c.tan_fovy;
     a.focal_y = c.H / (2.0f * c.tan_fovy);  // rasterizer_impl.cu:228-229
     a.focal_x = c.W / (2.0f * c.tan_fovx);
     a.prefiltered = c.prefiltered;
     a.tight_cull = opt_tight_cull();
     a.sh_vec_ok = aligned16(c.shs);
+}
+int forward_front(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, hipStream_t st,
+                  const dgr::BinningView* bin = nullptr, int capacity = 0, char* image_base = nullptr,
+                  int mode = COUNT_CALLBACK) {
+    // No memsets: preprocess clears the per-Gaussian median statistics (and, on the callback path, the tile counters);
+    // scan_blocks / scan_tiles initialise the status word.
+    dgr::PreprocessFwdArgs a{};
+    preprocess_scene(a, c);
+    a.view = c.viewmatrix; a.proj = c.projmatrix; a.campos = c.cam_pos;
     a.geom = geom; a.radii_out = c.radii;
     a.gau_uncertainty = c.gau_uncertainty; a.gau_related_pixels = c.gau_related_pixels;
-    (void)tiles;
     if (bin && mode == COUNT_LDS) {
         // nothing to clear: the kernel leaves its per-block instance totals (and the `prefiltered` flag) in
         // geom.block_tiles, bin_segments / bin_tiles take it from there
@@ -415,8 +141,8 @@ int binning_stages(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView im
                    hipStream_t st, int mode = COUNT_CALLBACK, char* binning_base = nullptr, ArmedReport* armed = nullptr) {
     const int gx = dgr::tiles_x(c.W), gy = dgr::tiles_y(c.H), tiles = gx * gy;
     // the tile schedule: always, unless this shape's last reported frame had even lists (want_schedule above)
-    const bool sched_on = !(armed && armed->id >= 0) ? (g_tile_schedule.load(std::memory_order_relaxed) != 0) : want_schedule(c.W, c.H, c.P);
-    const int lists = g_lane_lists.load(std::memory_order_relaxed);
+    const bool sched_on = !(armed && armed->id >= 0) ? (option(OPT_TILE_SCHEDULE) != 0) : want_schedule(c.W, c.H, c.P);
+    const int lists = option(OPT_LANE_LISTS);
     const int blend_flags = (sched_on ? dgr::BLEND_SCHEDULE : 0) | (lists == 0 ? dgr::BLEND_LISTS_QUADRANT : lists == 2 ? dgr::BLEND_LISTS_AUTO : 0);
     const dgr::StatusReport rep = armed ? armed->rep : dgr::StatusReport{nullptr, 0u, nullptr};
     if (mode == COUNT_LDS || mode == COUNT_LDS_CALLBACK) {
@@ -468,12 +194,12 @@ int forward_blend(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img
 }
 
 int check_common(const FwdCommon& c) {
-    if (c.P < 0 || c.W <= 0 || c.H <= 0) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
-    if ((unsigned)c.P > DGR_ID_MASK) { g_last_error = "more than 2^28 Gaussians"; return DGR_ERR_BAD_ARGUMENT; }
-    if (c.P > 0 && !c.shs && !c.colors_precomp) { g_last_error = "need SHs or precomputed colours"; return DGR_ERR_BAD_ARGUMENT; }
-    if (c.P > 0 && !c.cov3D_precomp && (!c.scales || !c.rotations)) { g_last_error = "need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
+    if (c.P < 0 || c.W <= 0 || c.H <= 0) { set_last_error("bad sizes"); return DGR_ERR_BAD_ARGUMENT; }
+    if ((unsigned)c.P > DGR_ID_MASK) { set_last_error("more than 2^28 Gaussians"); return DGR_ERR_BAD_ARGUMENT; }
+    if (c.P > 0 && !c.shs && !c.colors_precomp) { set_last_error("need SHs or precomputed colours"); return DGR_ERR_BAD_ARGUMENT; }
+    if (c.P > 0 && !c.cov3D_precomp && (!c.scales || !c.rotations)) { set_last_error("need scale/rotation or cov3D"); return DGR_ERR_BAD_ARGUMENT; }
     // (2^30 pixels: the blend kernels index pixels, and the three colour planes, with 32-bit words)
-    if (dgr::tiles_x(c.W) > 65535 || dgr::tiles_y(c.H) > 65535 || (long long)c.W * c.H > (1ll << 30)) { g_last_error = "image too large"; return DGR_ERR_BAD_ARGUMENT; }
+    if (dgr::tiles_x(c.W) > 65535 || dgr::tiles_y(c.H) > 65535 || (long long)c.W * c.H > (1ll << 30)) { set_last_error("image too large"); return DGR_ERR_BAD_ARGUMENT; }
     return DGR_OK;
 }
 
@@ -488,7 +214,6 @@ int check_common(const FwdCommon& c) {
 // 3 views 0.459 / 0.434 / 0.436 / 0.438 / 0.444, 4 views 0.450 / 0.415 / 0.419 / 0.446 / 0.437, 8 views 0.425 / 0.377 /
 // 0.380 / 0.391 / 0.407 -- one view's binning under another view's blend is the whole gain; more blend kernels at once
 // only take each other's L2 and wave slots.
-std::atomic<int> g_batch_streams{2};
 // dgr_set_option("batch_order", o): how the per-view stages of a batch are spread over the streams.
 //   0 (default) = round robin: view v's whole chain on stream v mod K ("batch_streams");
 //   1 = pipeline: the views' BINNING stages (count, scan, emit, sort -- kernels that leave most of the chip idle) one after the
@@ -500,10 +225,8 @@ std::atomic<int> g_batch_streams{2};
 //       0.156 / 0.116 -- slower even than one stream (0.450 at 4 views): one cross-stream event wait per view each way costs more
 //       than the overlap it arranges (the same finding as round 1's high-priority companion stream).  Kept as the
 //       measured alternative.
-std::atomic<int> g_batch_order{0};
-constexpr int DGR_BATCH_MAX_STREAMS = 8;
 inline int batch_stream_count(int n_views) {
-    const int kmax = std::max(1, std::min(g_batch_streams.load(), DGR_BATCH_MAX_STREAMS));
+    const int kmax = std::max(1, std::min(option(OPT_BATCH_STREAMS), DGR_BATCH_MAX_STREAMS));
     const int rounds = (n_views + kmax - 1) / kmax;
     return (n_views + rounds - 1) / rounds;
 }
@@ -523,7 +246,7 @@ thread_local BatchStreams* g_batch_p = nullptr;
 int batch_streams_ready() {
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= DGR_BATCH_MAX_DEVICES) { g_last_error = "device index above DGR_BATCH_MAX_DEVICES"; return DGR_ERR_BAD_ARGUMENT; }
+    if (dev < 0 || dev >= DGR_BATCH_MAX_DEVICES) { set_last_error("device index above DGR_BATCH_MAX_DEVICES"); return DGR_ERR_BAD_ARGUMENT; }
     g_batch_p = &g_batch_pool[dev];
     if (g_batch_p->device == dev) return DGR_OK;
     for (int i = 0; i < DGR_BATCH_MAX_STREAMS - 1; i++) {
@@ -561,6 +284,26 @@ struct BatchJoinGuard {
     int done() { armed = false; return batch_join(main, K); }
     ~BatchJoinGuard() { if (armed) batch_join(main, K); }
 };
+// Which stream the per-view stages of view v start on, and how they hand over to the caller's stream ("batch_order", above):
+// round robin = view v's whole chain on stream v mod K; pipeline = every view's first stage on one helper stream and the rest on
+// the caller's stream, behind an event.
+struct BatchPlan {
+    hipStream_t main;
+    bool pipeline;
+    int K;
+    BatchPlan(hipStream_t st, int n_views)
+        : main(st), pipeline(option(OPT_BATCH_ORDER) == 1 && n_views > 1 && option(OPT_BATCH_STREAMS) > 1),
+          K(pipeline ? 2 : batch_stream_count(n_views)) {}
+    hipStream_t first_stream(int v) const { return pipeline ? g_batch_p->helper[0] : batch_stream(main, v, K); }
+    // sv = the stream of view v's remaining stages, ordered behind what its first stage enqueued on sv
+    int hand_over(int v, hipStream_t& sv) const {
+        if (!pipeline) return DGR_OK;
+        HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
+        HIP_TRY(hipStreamWaitEvent(main, g_batch_p->stage[v], 0));
+        sv = main;
+        return DGR_OK;
+    }
+};
 
 // The body of dgr_light_forward_batch / dgr_full_forward_batch: cv[v] = view v's arguments as the one-view presized call takes
 // them (full: the uncertainty image in the out_alpha slot, as dgr_full_forward_presized passes it), bs[v] its state buffers.
@@ -576,11 +319,11 @@ int forward_batch(hipStream_t st, int n_views, const FwdCommon* cv, const BatchV
     for (int v = 0; v < n_views; v++) {
         const FwdCommon& w = cv[v];
         if (!w.viewmatrix || !w.projmatrix || !w.cam_pos || !w.out_color || !w.out_depth || (full && !w.out_alpha)) {
-            g_last_error = "view without camera or outputs";
+            set_last_error("view without camera or outputs");
             return DGR_ERR_BAD_ARGUMENT;
         }
         if (P > 0 && (!bs[v].geometry_buffer || !bs[v].image_buffer || !bs[v].binning_buffer || bs[v].binning_capacity < 0)) {
-            g_last_error = "view without state buffers";
+            set_last_error("view without state buffers");
             return DGR_ERR_BAD_ARGUMENT;
         }
     }
@@ -603,23 +346,12 @@ int forward_batch(hipStream_t st, int n_views, const FwdCommon* cv, const BatchV
         if (bs[v].status) img[v].status = bs[v].status;
         bin[v] = dgr::carve_binning(bs[v].binning_buffer, (size_t)bs[v].binning_capacity);
     }
-    const int gx = dgr::tiles_x(width), gy = dgr::tiles_y(height);
     // One preprocess launch for all views needs the segment binning behind it (its epilogue leaves per-block instance
     // totals); frames whose segment tables do not fit LDS, or "lds_count" = 0, take the one-view front end per view.
-    const bool shared_front = g_lds_count.load() != 0 && dgr::segment_binning_fits(width, height);
+    const bool shared_front = option(OPT_LDS_COUNT) != 0 && dgr::segment_binning_fits(width, height);
     if (shared_front) {
-        const FwdCommon& c = cv[0];
         dgr::PreprocessFwdBatchArgs b{};
-        dgr::PreprocessFwdArgs& a = b.base;
-        a.P = P; a.D = c.D; a.M = c.M; a.W = width; a.H = height; a.grid_x = gx; a.grid_y = gy;
-        a.means3D = c.means3D; a.scales = c.scales; a.scale_modifier = c.scale_modifier; a.rotations = c.rotations;
-        a.opacities = c.opacities; a.shs = c.shs; a.cov3D_precomp = c.cov3D_precomp; a.colors_precomp = c.colors_precomp;
-        a.tan_fovx = c.tan_fovx; a.tan_fovy = c.tan_fovy;
-        a.focal_y = height / (2.0f * c.tan_fovy);  // rasterizer_impl.cu:228-229
-        a.focal_x = width / (2.0f * c.tan_fovx);
-        a.prefiltered = c.prefiltered;
-        a.tight_cull = opt_tight_cull();
-        a.sh_vec_ok = aligned16(c.shs);
+        preprocess_scene(b.base, cv[0]);
         b.V = n_views;
         for (int v = 0; v < n_views; v++) {
             b.v[v].view = cv[v].viewmatrix; b.v[v].proj = cv[v].projmatrix; b.v[v].campos = cv[v].cam_pos;
@@ -628,92 +360,30 @@ int forward_batch(hipStream_t st, int n_views, const FwdCommon* cv, const BatchV
         }
         { ScopedStage t(ST_PRE_FWD, st); HIP_TRY(dgr::launch_preprocess_fwd_batch(b, st)); }
     }
-    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
-    const int K = pipeline ? 2 : batch_stream_count(n_views);
-    if ((rc = batch_fork(st, K))) return rc;
-    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
+    const BatchPlan plan(st, n_views);
+    if ((rc = batch_fork(st, plan.K))) return rc;
+    BatchJoinGuard joined(st, plan.K);  // (an early return below still rejoins the helper streams)
     for (int v = 0; v < n_views; v++) {
-        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
+        hipStream_t sv = plan.first_stream(v);
         const int cap = bs[v].binning_capacity;
         int mode = COUNT_LDS;
         if (!shared_front) {
-            mode = presized_count_mode(width, height, cap);
+            mode = presized_count_mode(width, height);
             if ((rc = forward_front(cv[v], geom[v], img[v], sv, &bin[v], cap, bs[v].image_buffer, mode))) return rc;
         }
         if ((rc = binning_stages(cv[v], geom[v], img[v], bin[v], cap, sv, mode, bs[v].binning_buffer))) return rc;
-        if (pipeline) {  // the blend of view v on the caller's stream, behind its binning on the helper stream
-            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
-            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
-            sv = st;
-        }
+        if ((rc = plan.hand_over(v, sv))) return rc;  // (pipeline: the blend on the caller's stream, behind the view's binning)
         if ((rc = forward_blend(cv[v], geom[v], img[v], bin[v], sv, full))) return rc;
     }
     return joined.done();
 }
 
-// ---- state export (tests / profiling) ----
-enum ExportKind { EX_MEANS2D, EX_CONIC_OPACITY, EX_RGB, EX_CLAMPED, EX_TILES_TOUCHED, EX_KEYS };
-
-__global__ void export_geom_kernel(int kind, int P, dgr::GeometryView g, void* dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= P) return;
-    const bool vis = g.radii[i] > 0;
-    switch (kind) {
-        case EX_MEANS2D: {
-            const float4 q = g.rec[DGR_REC_STRIDE * (size_t)i];
-            ((float2*)dst)[i] = vis ? make_float2(q.x, q.y) : make_float2(0, 0);
-        } break;
-        case EX_CONIC_OPACITY: {
-            const float4 q0 = g.rec[DGR_REC_STRIDE * (size_t)i], q1 = g.rec[DGR_REC_STRIDE * (size_t)i + 1];
-            ((float4*)dst)[i] = vis ? make_float4(q1.x, q1.y, q1.z, q0.w) : make_float4(0, 0, 0, 0);
-        } break;
-        case EX_RGB: {
-            const float4 q = g.rec[DGR_REC_STRIDE * (size_t)i + 2];
-            float* d = (float*)dst + 3 * (size_t)i;
-            d[0] = vis ? q.x : 0; d[1] = vis ? q.y : 0; d[2] = vis ? q.z : 0;
-        } break;
-        case EX_CLAMPED: {
-            const uint8_t c = vis ? g.clamped[i] : 0;
-            uint8_t* d = (uint8_t*)dst + 3 * (size_t)i;
-            d[0] = c & 1; d[1] = (c >> 1) & 1; d[2] = (c >> 2) & 1;
-        } break;
-        case EX_TILES_TOUCHED: {
-            const ushort4 r = g.rect[i];
-            ((uint32_t*)dst)[i] = (uint32_t)(r.z - r.x) * (uint32_t)(r.w - r.y);
-        } break;
-    }
-}
-// the reference's sorted 64-bit keys: tile id << 32 | depth bits (rasterizer_impl.cu:97-100)
-__global__ void export_keys_kernel(dgr::ImageView img, dgr::BinningView bin, dgr::GeometryView g, uint64_t* dst) {
-    const int tile = blockIdx.x;
-    const uint2 rg = img.ranges[tile];
-    for (uint32_t i = rg.x + threadIdx.x; i < rg.y; i += blockDim.x)
-        dst[i] = ((uint64_t)tile << 32) | __float_as_uint(g.depths[bin.point_list[i] & DGR_ID_MASK]);
-}
-// the sorted Gaussian ids (the mask: rounds 3-8 kept contribution tags in the top 4 bits; nothing writes them any more)
-__global__ void export_point_list_kernel(const uint32_t* src, uint32_t* dst, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dst[i] = src[i] & DGR_ID_MASK;
-}
-// ... and the contribution tags (tests): the blend forward's tag bytes (bit 2 w + h: half h of quadrant wave w; `half` = 1: as they
-// are), or folded to 4 bits, bit w = quadrant wave w
-__global__ void export_tag_bytes_kernel(const uint8_t* src, uint8_t* dst, int n, int half) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    uint32_t t = src[i];
-    if (!half) {
-        t = (t | (t >> 1)) & 0x55u;
-        t = (t & 1u) | ((t >> 1) & 2u) | ((t >> 2) & 4u) | ((t >> 3) & 8u);
-    }
-    dst[i] = (uint8_t)t;
-}
-
 // absgrad (dgr_*_backward*_absgrad, dgr_hip.h): what is refused, before any device call
 int absgrad_refused(bool wanted, int map_off) {
     if (!wanted) return DGR_OK;
-    if (map_off) { g_last_error = "absgrad: not with map_off (tracking forms no per-Gaussian gradients)"; return DGR_ERR_BAD_ARGUMENT; }
-    if (opt_det_grads()) { g_last_error = "absgrad: no deterministic form (deterministic_grads is set)"; return DGR_ERR_BAD_ARGUMENT; }
-    if (opt_alpha_mode() == 2) { g_last_error = "absgrad: needs alpha_mode 0 or 1 (not the glibc A/B form)"; return DGR_ERR_BAD_ARGUMENT; }
+    if (map_off) { set_last_error("absgrad: not with map_off (tracking forms no per-Gaussian gradients)"); return DGR_ERR_BAD_ARGUMENT; }
+    if (opt_det_grads()) { set_last_error("absgrad: no deterministic form (deterministic_grads is set)"); return DGR_ERR_BAD_ARGUMENT; }
+    if (opt_alpha_mode() == 2) { set_last_error("absgrad: needs alpha_mode 0 or 1 (not the glibc A/B form)"); return DGR_ERR_BAD_ARGUMENT; }
     return DGR_OK;
 }
 // deterministic gradients: behind the standard scratch, {per-block instance sums u32[blocks] | per-block pose partials
@@ -748,14 +418,14 @@ int forward_presized(hipStream_t st, const FwdCommon& c, char* geometry_buffer, 
     // (the binning buffer also holds the segment binning's tables behind its per-instance arrays: dgr_binning_bytes() is
     //  non-zero for a capacity of 0, and a NULL buffer is never valid for P > 0)
     if (!geometry_buffer || !image_buffer || !binning_buffer || binning_capacity < 0) {
-        g_last_error = "presized forward: geometry, binning and image buffers are required (sizes: dgr_*_bytes)";
+        set_last_error("presized forward: geometry, binning and image buffers are required (sizes: dgr_*_bytes)");
         return DGR_ERR_BAD_ARGUMENT;
     }
     dgr::GeometryView geom = dgr::carve_geometry(geometry_buffer, c.P);
     dgr::ImageView img = dgr::carve_image(image_buffer, c.W, c.H);
     if (status) img.status = status;  // the kernels write the caller's status word directly
     dgr::BinningView bin = dgr::carve_binning(binning_buffer, (size_t)binning_capacity);
-    const int mode = presized_count_mode(c.W, c.H, binning_capacity);
+    const int mode = presized_count_mode(c.W, c.H);
     if ((rc = forward_front(c, geom, img, st, &bin, binning_capacity, image_buffer, mode))) return rc;
     if ((rc = binning_stages(c, geom, img, bin, binning_capacity, st, mode, binning_buffer, &armed))) return rc;
     return forward_blend(c, geom, img, bin, st, full, &armed);
@@ -770,13 +440,13 @@ int forward_callback(hipStream_t st, const FwdCommon& c, dgr_alloc_fn geometryBu
     // The callback entry points block the host to size the binning buffer, as the reference does (rasterizer_impl.cu:287): on a
     // capturing stream that synchronisation would fail AND invalidate the capture -- refuse before anything touches the stream.
     if (dgr_stream_is_capturing(st)) {
-        g_last_error = "the resize-callback forward blocks the host (it sizes the binning buffer): it cannot be captured into a graph -- use the presized entry point";
+        set_last_error("the resize-callback forward blocks the host (it sizes the binning buffer): it cannot be captured into a graph -- use the presized entry point");
         return DGR_ERR_BAD_ARGUMENT;
     }
     if (c.P == 0) return zero_outputs(c, st);
     char* gptr = geometryBuffer(dgr_geometry_bytes(c.P), alloc_user);
     char* iptr = imageBuffer(dgr_image_bytes(c.W, c.H), alloc_user);
-    if (!gptr || !iptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
+    if (!gptr || !iptr) { set_last_error("allocation callback returned NULL"); return DGR_ERR_ALLOC; }
     dgr::GeometryView geom = dgr::carve_geometry(gptr, c.P);
     dgr::ImageView img = dgr::carve_image(iptr, c.W, c.H);
     if ((rc = forward_front(c, geom, img, st))) return rc;
@@ -784,18 +454,18 @@ int forward_callback(hipStream_t st, const FwdCommon& c, dgr_alloc_fn geometryBu
     int status[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (status[2]) { g_last_error = "Point is filtered although prefiltered is set. This shouldn't happen!"; return DGR_ERR_PREFILTERED; }
+    if (status[2]) { set_last_error("Point is filtered although prefiltered is set. This shouldn't happen!"); return DGR_ERR_PREFILTERED; }
     const int R = status[0];
     char* bptr = nullptr;
     if (R > 0) {
         bptr = binningBuffer(dgr_binning_bytes(R, c.W, c.H), alloc_user);
-        if (!bptr) { g_last_error = "allocation callback returned NULL"; return DGR_ERR_ALLOC; }
+        if (!bptr) { set_last_error("allocation callback returned NULL"); return DGR_ERR_ALLOC; }
     } else {
         binningBuffer(0, alloc_user);
     }
     dgr::BinningView bin = dgr::carve_binning(bptr, (size_t)R);
     // (also with R == 0: it writes the (empty) range table)
-    const int mode = (R > 0 && presized_count_mode(c.W, c.H, R) == COUNT_LDS) ? COUNT_LDS_CALLBACK : COUNT_CALLBACK;
+    const int mode = (R > 0 && presized_count_mode(c.W, c.H) == COUNT_LDS) ? COUNT_LDS_CALLBACK : COUNT_CALLBACK;
     if ((rc = binning_stages(c, geom, img, bin, R, st, mode, bptr))) return rc;
     if ((rc = forward_blend(c, geom, img, bin, st, full))) return rc;
     if (num_related) {  // second blocking read of the reference (F/cuda_rasterizer/rasterizer_impl.cu:498)
@@ -928,27 +598,26 @@ void bwd_view_part(Q& q, const BwdView& w, const BwdBufs& s, bool det) {
 
 // The body of dgr_{light,full}_backward[_absgrad|_silhouette]
 int backward_one(hipStream_t st, dgr::PreprocessBwdArgs b, const float* background, const BwdView& w, int debug) {
-    const bool scratch_clean = g_scratch_clean_armed;  // (consumed by every call, a refused one included)
-    g_scratch_clean_armed = false;
+    const bool scratch_clean = take_scratch_clean_arm();  // (consumed by every call, a refused one included)
     const int P = b.P, width = b.W, height = b.H, R = w.R;
     if (int rc = absgrad_refused(w.dL_dmean2D_abs != nullptr, b.map_off)) return rc;
-    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { set_last_error("bad sizes"); return DGR_ERR_BAD_ARGUMENT; }
     if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
         HIP_TRY(hipMemsetAsync(w.dL_dview, 0, 16 * 4, st));
         return DGR_OK;
     }
     const bool det = opt_det_grads() != 0 && !(b.track_off && b.map_off);
     const bool complete = opt_pose_grad() != 0 && !b.track_off;  // (track_off: no pose gradient, nothing to complete)
-    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
-    if (det && R <= 0) { g_last_error = "deterministic_grads: the backward needs R >= num_rendered (it sizes the instance-major row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
+    if (det && opt_alpha_mode() != 0) { set_last_error("deterministic_grads needs alpha_mode 0"); return DGR_ERR_BAD_ARGUMENT; }
+    if (det && R <= 0) { set_last_error("deterministic_grads: the backward needs R >= num_rendered (it sizes the instance-major row buffer)"); return DGR_ERR_BAD_ARGUMENT; }
     if (w.scratch_bytes < dgr_light_backward_scratch_bytes_r(P, width, height, R) || !w.scratch) {
-        g_last_error = det ? "backward scratch too small (deterministic_grads: dgr_light_backward_scratch_bytes_r)" : "backward scratch too small";
+        set_last_error(det ? "backward scratch too small (deterministic_grads: dgr_light_backward_scratch_bytes_r)" : "backward scratch too small");
         return DGR_ERR_BAD_ARGUMENT;
     }
     // (the 3D covariance is not kept by the forward: the backward re-forms it from scale and rotation -- the SAME tensors the
     //  forward saw, or the bits differ -- unless the caller precomputed it)
-    if (!b.cov3D_precomp && (!b.scales || !b.rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
-    if (!w.geometry_buffer || !w.binning_buffer || !w.image_buffer) { g_last_error = "backward: the forward's three state buffers are required"; return DGR_ERR_BAD_ARGUMENT; }
+    if (!b.cov3D_precomp && (!b.scales || !b.rotations)) { set_last_error("backward: need scale/rotation or cov3D"); return DGR_ERR_BAD_ARGUMENT; }
+    if (!w.geometry_buffer || !w.binning_buffer || !w.image_buffer) { set_last_error("backward: the forward's three state buffers are required"); return DGR_ERR_BAD_ARGUMENT; }
     BwdBufs s;
     if (int rc = bwd_view_prepare(w, P, width, height, det, scratch_clean, s, st)) return rc;
     if (int rc = bwd_view_blend(w, b, background, s, det, complete, st)) return rc;
@@ -973,47 +642,42 @@ int backward_batch(hipStream_t st, dgr::PreprocessBwdArgs b, const float* backgr
     const int P = b.P, width = b.W, height = b.H;
     const bool det = opt_det_grads() != 0 && !(b.track_off && b.map_off);
     const bool complete = opt_pose_grad() != 0 && !b.track_off;
-    if (det && opt_alpha_mode() != 0) { g_last_error = "deterministic_grads needs alpha_mode 0"; return DGR_ERR_BAD_ARGUMENT; }
-    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    if (det && opt_alpha_mode() != 0) { set_last_error("deterministic_grads needs alpha_mode 0"); return DGR_ERR_BAD_ARGUMENT; }
+    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { set_last_error("1 .. DGR_MAX_BATCH_VIEWS views per batch"); return DGR_ERR_BAD_ARGUMENT; }
     bool any_abs = false;  // (absgrad: a NULL array or NULL entries -- those views as without it)
     for (int v = 0; v < n_views; v++) any_abs |= views[v].dL_dmean2D_abs != nullptr;
     if (int rc = absgrad_refused(any_abs, b.map_off)) return rc;
-    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { g_last_error = "bad sizes"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { set_last_error("bad sizes"); return DGR_ERR_BAD_ARGUMENT; }
     for (int v = 0; v < n_views; v++)
-        if (!views[v].dL_dview) { g_last_error = "view without dL_dview"; return DGR_ERR_BAD_ARGUMENT; }
-    if (P > 0 && !b.cov3D_precomp && (!b.scales || !b.rotations)) { g_last_error = "backward: need scale/rotation or cov3D"; return DGR_ERR_BAD_ARGUMENT; }
+        if (!views[v].dL_dview) { set_last_error("view without dL_dview"); return DGR_ERR_BAD_ARGUMENT; }
+    if (P > 0 && !b.cov3D_precomp && (!b.scales || !b.rotations)) { set_last_error("backward: need scale/rotation or cov3D"); return DGR_ERR_BAD_ARGUMENT; }
     if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
         for (int v = 0; v < n_views; v++) HIP_TRY(hipMemsetAsync(views[v].dL_dview, 0, 16 * 4, st));
         return DGR_OK;
     }
     for (int v = 0; v < n_views; v++) {
         const BwdView& w = views[v];
-        if (det && w.R <= 0) { g_last_error = "deterministic_grads: every view needs num_rendered (it sizes the view's row buffer)"; return DGR_ERR_BAD_ARGUMENT; }
+        if (det && w.R <= 0) { set_last_error("deterministic_grads: every view needs num_rendered (it sizes the view's row buffer)"); return DGR_ERR_BAD_ARGUMENT; }
         const size_t need = dgr_light_backward_scratch_bytes_r(P, width, height, w.R);
-        if (!w.scratch || w.scratch_bytes < need) { g_last_error = "backward scratch too small"; return DGR_ERR_BAD_ARGUMENT; }
+        if (!w.scratch || w.scratch_bytes < need) { set_last_error("backward scratch too small"); return DGR_ERR_BAD_ARGUMENT; }
         if (!bwd_view_complete(w, b.full_variant != 0)) {
-            g_last_error = "view with a missing state buffer, camera or gradient image";
+            set_last_error("view with a missing state buffer, camera or gradient image");
             return DGR_ERR_BAD_ARGUMENT;
         }
     }
     int rc;
     if ((rc = batch_streams_ready())) return rc;
-    const bool pipeline = g_batch_order.load() == 1 && n_views > 1 && g_batch_streams.load() > 1;
-    const int K = pipeline ? 2 : batch_stream_count(n_views);
+    const BatchPlan plan(st, n_views);
     dgr::PreprocessBwdBatchArgs bb{};
     bb.base = b;
-    if ((rc = batch_fork(st, K))) return rc;
-    BatchJoinGuard joined(st, K);  // (an early return below still rejoins the helper streams)
+    if ((rc = batch_fork(st, plan.K))) return rc;
+    BatchJoinGuard joined(st, plan.K);  // (an early return below still rejoins the helper streams)
     for (int v = 0; v < n_views; v++) {
         const BwdView& w = views[v];
-        hipStream_t sv = pipeline ? g_batch_p->helper[0] : batch_stream(st, v, K);
+        hipStream_t sv = plan.first_stream(v);
         BwdBufs s;
         if ((rc = bwd_view_prepare(w, P, width, height, det, false, s, sv))) return rc;
-        if (pipeline) {  // the blend backward of view v on the caller's stream, behind its cleared scratch
-            HIP_TRY(hipEventRecord(g_batch_p->stage[v], sv));
-            HIP_TRY(hipStreamWaitEvent(st, g_batch_p->stage[v], 0));
-            sv = st;
-        }
+        if ((rc = plan.hand_over(v, sv))) return rc;  // (pipeline: the blend backward on the caller's stream, behind the cleared scratch)
         if ((rc = bwd_view_blend(w, b, background, s, det, complete, sv))) return rc;
         bwd_view_part(bb.v[v], w, s, det);
     }
@@ -1066,10 +730,10 @@ int dgr_light_forward_presized(void* stream, char* geometry_buffer, char* binnin
                                float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_depth,
                                float* out_median_depth, float* out_alpha, const float* gt_depth,
                                float* out_depth_var, float* gau_uncertainty, int* gau_related_pixels, int* radii) {
-    FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
-                cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
-                out_color, out_depth, out_median_depth, out_alpha, gt_depth, out_depth_var, gau_uncertainty,
-                gau_related_pixels, radii};
+    const FwdCommon c = light_common(P, D, M, background, width, height, means3D, shs, colors_precomp, opacities, scales,
+                                     scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+                                     prefiltered, out_color, out_depth, out_median_depth, out_alpha, gt_depth, out_depth_var,
+                                     gau_uncertainty, gau_related_pixels, radii);
     return forward_presized((hipStream_t)stream, c, geometry_buffer, binning_buffer, binning_capacity, image_buffer, status, false);
 }
 
@@ -1081,10 +745,10 @@ int dgr_light_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn bi
                       float tan_fovy, int prefiltered, float* out_color, float* out_depth, float* out_median_depth,
                       float* out_alpha, const float* gt_depth, float* out_depth_var, float* gau_uncertainty,
                       int* gau_related_pixels, int* radii, int debug) {
-    FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
-                cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
-                out_color, out_depth, out_median_depth, out_alpha, gt_depth, out_depth_var, gau_uncertainty,
-                gau_related_pixels, radii};
+    const FwdCommon c = light_common(P, D, M, background, width, height, means3D, shs, colors_precomp, opacities, scales,
+                                     scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+                                     prefiltered, out_color, out_depth, out_median_depth, out_alpha, gt_depth, out_depth_var,
+                                     gau_uncertainty, gau_related_pixels, radii);
     return forward_callback((hipStream_t)stream, c, geometryBuffer, binningBuffer, imageBuffer, alloc_user, false, nullptr, debug);
 }
 
@@ -1157,9 +821,9 @@ int dgr_full_forward_presized(void* stream, char* geometry_buffer, char* binning
                               const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
                               const float* cam_pos, float tan_fovx, float tan_fovy, int prefiltered, float* out_color,
                               float* out_depth, const float* gt_depth, float* out_uncertainty, int* radii) {
-    FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
-                cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
-                out_color, out_depth, nullptr, out_uncertainty, gt_depth, nullptr, nullptr, nullptr, radii};
+    const FwdCommon c = full_common(P, D, M, background, width, height, means3D, shs, colors_precomp, opacities, scales,
+                                    scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+                                    prefiltered, out_color, out_depth, gt_depth, out_uncertainty, radii);
     return forward_presized((hipStream_t)stream, c, geometry_buffer, binning_buffer, binning_capacity, image_buffer, status, true);
 }
 
@@ -1170,9 +834,9 @@ int dgr_full_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn bin
                      const float* viewmatrix, const float* projmatrix, const float* cam_pos, float tan_fovx,
                      float tan_fovy, int prefiltered, float* out_color, float* out_depth, const float* gt_depth,
                      float* out_uncertainty, int* radii, int* num_related_primitives) {
-    FwdCommon c{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
-                cov3D_precomp, scale_modifier, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered,
-                out_color, out_depth, nullptr, out_uncertainty, gt_depth, nullptr, nullptr, nullptr, radii};
+    const FwdCommon c = full_common(P, D, M, background, width, height, means3D, shs, colors_precomp, opacities, scales,
+                                    scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+                                    prefiltered, out_color, out_depth, gt_depth, out_uncertainty, radii);
     return forward_callback((hipStream_t)stream, c, geometryBuffer, binningBuffer, imageBuffer, alloc_user, true,
                             num_related_primitives, 0);
 }
@@ -1246,15 +910,15 @@ int dgr_light_forward_batch(void* stream, int n_views, const dgr_light_view* vie
                             const float* background, int width, int height, const float* means3D, const float* shs,
                             const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
                             const float* rotations, const float* cov3D_precomp, float tan_fovx, float tan_fovy, int prefiltered) {
-    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { set_last_error("1 .. DGR_MAX_BATCH_VIEWS views per batch"); return DGR_ERR_BAD_ARGUMENT; }
     FwdCommon cv[DGR_MAX_BATCH_VIEWS];
     BatchViewState bs[DGR_MAX_BATCH_VIEWS];
     for (int v = 0; v < n_views; v++) {
         const dgr_light_view& w = views[v];
-        cv[v] = FwdCommon{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
-                          cov3D_precomp, scale_modifier, w.viewmatrix, w.projmatrix, w.cam_pos, tan_fovx, tan_fovy, prefiltered,
-                          w.out_color, w.out_depth, w.out_median_depth, w.out_alpha, w.gt_depth, w.out_depth_var,
-                          w.gau_uncertainty, w.gau_related_pixels, w.radii};
+        cv[v] = light_common(P, D, M, background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
+                             rotations, cov3D_precomp, w.viewmatrix, w.projmatrix, w.cam_pos, tan_fovx, tan_fovy, prefiltered,
+                             w.out_color, w.out_depth, w.out_median_depth, w.out_alpha, w.gt_depth, w.out_depth_var,
+                             w.gau_uncertainty, w.gau_related_pixels, w.radii);
         bs[v] = BatchViewState{w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer, w.status};
     }
     return forward_batch((hipStream_t)stream, n_views, cv, bs, false);
@@ -1264,15 +928,14 @@ int dgr_full_forward_batch(void* stream, int n_views, const dgr_full_view* views
                            const float* background, int width, int height, const float* means3D, const float* shs,
                            const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
                            const float* rotations, const float* cov3D_precomp, float tan_fovx, float tan_fovy, int prefiltered) {
-    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { g_last_error = "1 .. DGR_MAX_BATCH_VIEWS views per batch"; return DGR_ERR_BAD_ARGUMENT; }
+    if (n_views < 1 || n_views > DGR_MAX_BATCH_VIEWS || !views) { set_last_error("1 .. DGR_MAX_BATCH_VIEWS views per batch"); return DGR_ERR_BAD_ARGUMENT; }
     FwdCommon cv[DGR_MAX_BATCH_VIEWS];
     BatchViewState bs[DGR_MAX_BATCH_VIEWS];
     for (int v = 0; v < n_views; v++) {
         const dgr_full_view& w = views[v];
-        // (as dgr_full_forward_presized: the uncertainty image in the alpha slot, no light-only outputs)
-        cv[v] = FwdCommon{P, D, M, width, height, background, means3D, shs, colors_precomp, opacities, scales, rotations,
-                          cov3D_precomp, scale_modifier, w.viewmatrix, w.projmatrix, w.cam_pos, tan_fovx, tan_fovy, prefiltered,
-                          w.out_color, w.out_depth, nullptr, w.out_uncertainty, w.gt_depth, nullptr, nullptr, nullptr, w.radii};
+        cv[v] = full_common(P, D, M, background, width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
+                            rotations, cov3D_precomp, w.viewmatrix, w.projmatrix, w.cam_pos, tan_fovx, tan_fovy, prefiltered,
+                            w.out_color, w.out_depth, w.gt_depth, w.out_uncertainty, w.radii);
         bs[v] = BatchViewState{w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer, w.status};
     }
     return forward_batch((hipStream_t)stream, n_views, cv, bs, true);
@@ -1347,14 +1010,14 @@ int dgr_full_backward_batch_silhouette(void* stream, int n_views, const dgr_full
 }
 
 int dgr_cov3d_forward(void* stream, int P, const float* scales, const float* rotations, float scale_modifier, float* cov3D) {
-    if (P < 0 || (P > 0 && (!scales || !rotations || !cov3D))) { g_last_error = "dgr_cov3d_forward: bad argument"; return DGR_ERR_BAD_ARGUMENT; }
+    if (P < 0 || (P > 0 && (!scales || !rotations || !cov3D))) { set_last_error("dgr_cov3d_forward: bad argument"); return DGR_ERR_BAD_ARGUMENT; }
     HIP_TRY(dgr::launch_cov3d_forward(P, scales, rotations, scale_modifier, cov3D, (hipStream_t)stream));
     return DGR_OK;
 }
 int dgr_cov3d_backward(void* stream, int P, const float* scales, const float* rotations, float scale_modifier,
                        const float* dL_dcov3D, float* dL_dscales, float* dL_drotations) {
     if (P < 0 || (P > 0 && (!scales || !rotations || !dL_dcov3D || !dL_dscales || !dL_drotations))) {
-        g_last_error = "dgr_cov3d_backward: bad argument";
+        set_last_error("dgr_cov3d_backward: bad argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_cov3d_backward(P, scales, rotations, scale_modifier, dL_dcov3D, dL_dscales, dL_drotations, (hipStream_t)stream));
@@ -1384,7 +1047,7 @@ int dgr_debug_lane_lists(void* stream, const unsigned char* codes, unsigned* pai
 }
 int dgr_debug_exact_math(void* stream, int n, const float* x, const float* a, const float* b, float* out_exp, float* out_div) {
     if (n < 0 || (n > 0 && (!x || !a || !b || !out_exp || !out_div))) {
-        g_last_error = "dgr_debug_exact_math: bad argument";
+        set_last_error("dgr_debug_exact_math: bad argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_exact_math_test(n, x, a, b, out_exp, out_div, opt_alpha_mode(), (hipStream_t)stream));
@@ -1394,7 +1057,7 @@ int dgr_debug_exact_math(void* stream, int n, const float* x, const float* a, co
 int dgr_sparse_adam(void* stream, long rows, int k, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                     const int* visible, float lr, float beta1, float beta2, float eps, int step) {
     if (rows < 0 || k <= 0 || step < 1 || (rows > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) {
-        g_last_error = "dgr_sparse_adam: bad argument";
+        set_last_error("dgr_sparse_adam: bad argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_sparse_adam((size_t)rows, k, param, grad, exp_avg, exp_avg_sq, visible, lr, beta1, beta2, eps, step,
@@ -1405,7 +1068,7 @@ int dgr_sparse_adam_capturable(void* stream, long rows, int k, float* param, con
                                float* exp_avg_sq, const int* visible, float lr, float beta1, float beta2, float eps,
                                const int* step_device) {
     if (rows < 0 || k <= 0 || !step_device || (rows > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) {
-        g_last_error = "dgr_sparse_adam_capturable: bad argument";
+        set_last_error("dgr_sparse_adam_capturable: bad argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_sparse_adam((size_t)rows, k, param, grad, exp_avg, exp_avg_sq, visible, lr, beta1, beta2, eps, 1,
@@ -1416,7 +1079,7 @@ int dgr_sparse_adam_capturable(void* stream, long rows, int k, float* param, con
 int dgr_densification_stats(void* stream, long rows, const float* dmeans2D, const int* radii, float* grad_accum, float* denom,
                             float* max_radii2D) {
     if (rows < 0 || rows > 0x7fffffffL || (rows > 0 && (!radii || (grad_accum && !dmeans2D)))) {
-        g_last_error = "dgr_densification_stats: bad argument";
+        set_last_error("dgr_densification_stats: bad argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_densification_stats((int)rows, dmeans2D, radii, grad_accum, denom, max_radii2D, (hipStream_t)stream));
@@ -1426,7 +1089,7 @@ int dgr_densification_stats(void* stream, long rows, const float* dmeans2D, cons
 int dgr_pose_forward(void* stream, const float* quat, const float* trans, const float* perspec_matrix, float* viewmatrix,
                      float* projmatrix, float* campos) {
     if (!quat || !trans || !perspec_matrix || !viewmatrix || !projmatrix || !campos) {
-        g_last_error = "dgr_pose_forward: NULL argument";
+        set_last_error("dgr_pose_forward: NULL argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_pose_forward(quat, trans, perspec_matrix, viewmatrix, projmatrix, campos, (hipStream_t)stream));
@@ -1434,7 +1097,7 @@ int dgr_pose_forward(void* stream, const float* quat, const float* trans, const 
 }
 int dgr_pose_backward(void* stream, const float* quat, const float* dL_dviewmatrix, float* dL_dquat, float* dL_dtrans) {
     if (!quat || !dL_dviewmatrix || !dL_dquat || !dL_dtrans) {
-        g_last_error = "dgr_pose_backward: NULL argument";
+        set_last_error("dgr_pose_backward: NULL argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_pose_backward(quat, dL_dviewmatrix, dL_dquat, dL_dtrans, (hipStream_t)stream));
@@ -1445,7 +1108,7 @@ int dgr_l1_loss_forward(void* stream, long n_color, const float* color, const fl
                         const float* depth_obs, float w_color, float w_depth, float* scratch, float* loss) {
     if (n_color < 0 || n_depth < 0 || !scratch || !loss || (n_color > 0 && (!color || !color_obs)) ||
         (n_depth > 0 && (!depth || !depth_obs))) {
-        g_last_error = "dgr_l1_loss_forward: bad argument";
+        set_last_error("dgr_l1_loss_forward: bad argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_l1_loss_forward(n_color, color, color_obs, n_depth, depth, depth_obs, w_color, w_depth, scratch, loss,
@@ -1457,378 +1120,12 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
                          float* dL_ddepth) {
     if (n_color < 0 || n_depth < 0 || (n_color > 0 && (!color || !color_obs || !dL_dcolor)) ||
         (n_depth > 0 && (!depth || !depth_obs || !dL_ddepth))) {
-        g_last_error = "dgr_l1_loss_backward: bad argument";
+        set_last_error("dgr_l1_loss_backward: bad argument");
         return DGR_ERR_BAD_ARGUMENT;
     }
     HIP_TRY(dgr::launch_l1_loss_backward(n_color, color, color_obs, n_depth, depth, depth_obs, w_color, w_depth, upstream,
                                          dL_dcolor, dL_ddepth, (hipStream_t)stream));
     return DGR_OK;
-}
-
-// a free slot of the current device (g_status_mu held); creates one when all are busy
-static long status_slot_acquire() {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    for (size_t i = 0; i < g_status_slots.size(); i++) {
-        StatusSlot& c = g_status_slots[i];
-        if (c.busy || c.device != dev) continue;
-        if (c.quarantined) {  // (given up by a poll: reusable once the stream its forward was queued on has drained)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(c.stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) continue;  // a query would invalidate the capture
-            if (hipStreamQuery(c.stream) != hipSuccess) { (void)hipGetLastError(); continue; }
-            c.quarantined = false;
-        }
-        return (long)i;
-    }
-    StatusSlot sl;
-    HIP_TRY(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc((void**)&sl.pinned, 8 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void**)&sl.pinned_dev, sl.pinned, 0));
-    HIP_TRY(hipMalloc((void**)&sl.ws, 16 * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(sl.ws, 0, 16 * sizeof(uint32_t)));  // (once per slot; the kernels keep the words zero between forwards)
-    for (int i = 0; i < 8; i++) sl.pinned[i] = 0;
-    sl.device = dev;
-    g_status_slots.push_back(sl);
-    return (long)g_status_slots.size() - 1;
-}
-
-long dgr_status_post(void* stream, const int* device_status) {
-    if (!device_status) { g_last_error = "dgr_status_post: NULL"; return DGR_ERR_BAD_ARGUMENT; }
-    std::lock_guard<std::mutex> lk(g_status_mu);
-    const long id = status_slot_acquire();
-    if (id < 0) return id;
-    StatusSlot& sl = g_status_slots[(size_t)id];
-    HIP_TRY(hipMemcpyAsync(sl.pinned, device_status, 4 * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_TRY(hipEventRecord(sl.ev, (hipStream_t)stream));
-    sl.busy = true;
-    sl.mapped = false;
-    return id;
-}
-
-long dgr_status_arm(void) {
-    std::lock_guard<std::mutex> lk(g_status_mu);
-    if (g_armed_slot >= 0) {  // armed twice without a forward in between: the first arm is withdrawn
-        g_status_slots[(size_t)g_armed_slot].busy = false;
-        g_armed_slot = -1;
-    }
-    const long id = status_slot_acquire();
-    if (id < 0) return id;
-    StatusSlot& sl = g_status_slots[(size_t)id];
-    if (++g_status_tag == 0u) ++g_status_tag;
-    sl.tag = g_status_tag;
-    sl.busy = true;
-    sl.mapped = true;
-    ((volatile int*)sl.pinned)[4] = 0;
-    g_armed_slot = id;
-    return id;
-}
-
-int dgr_status_poll(long ticket, int wait, int* host_status4) {
-    hipEvent_t ev;
-    int* pinned;
-    bool mapped, enqueued;
-    uint32_t tag;
-    hipStream_t stream;
-    {
-        std::lock_guard<std::mutex> lk(g_status_mu);
-        if (ticket < 0 || (size_t)ticket >= g_status_slots.size() || !g_status_slots[(size_t)ticket].busy || !host_status4) {
-            g_last_error = "dgr_status_poll: bad ticket";
-            return DGR_ERR_BAD_ARGUMENT;
-        }
-        if (ticket == g_armed_slot) { g_last_error = "dgr_status_poll: the slot is armed and no forward has taken it"; return DGR_ERR_BAD_ARGUMENT; }
-        ev = g_status_slots[(size_t)ticket].ev;
-        pinned = g_status_slots[(size_t)ticket].pinned;
-        mapped = g_status_slots[(size_t)ticket].mapped;
-        tag = g_status_slots[(size_t)ticket].tag;
-        stream = g_status_slots[(size_t)ticket].stream;
-        enqueued = g_status_slots[(size_t)ticket].enqueued;
-    }
-    if (mapped) {  // written by the forward blend's first workgroup, the tag last: nothing to wait for on a stream
-        const auto tag_here = [&] { return __atomic_load_n(pinned + 4, __ATOMIC_ACQUIRE) == (int)tag; };
-        if (!tag_here()) {
-            if (!wait) return 0;
-            // Poll for a while, then stop burning the core (as wait_event_spinning).  The tag comes from ONE workgroup of ONE kernel:
-            // if an earlier kernel of that forward faults, the device hangs or the stream was being captured when the forward was
-            // issued, it never arrives -- so every millisecond the stream itself is asked: an error ends the wait with that error, a
-            // stream that has finished all its work without the tag having been written ends it too, and so does a hard limit
-            // (DGR_STATUS_TIMEOUT_MS, default 30 000).
-            // (DGR_STATUS_TIMEOUT_MS = 0: no limit -- profiler replays and collectives' stragglers can legitimately hold a queue
-            //  for longer than any default)
-            static const long limit_ms = [] { const char* e = getenv("DGR_STATUS_TIMEOUT_MS"); return e ? (atol(e) > 0 ? atol(e) : 0L) : 30000L; }();
-            const auto t0 = std::chrono::steady_clock::now();
-            auto next_query = t0 + std::chrono::milliseconds(1);
-            auto release = [&](const char* why, bool quarantine) {
-                std::lock_guard<std::mutex> lk(g_status_mu);
-                g_status_slots[(size_t)ticket].busy = false;
-                g_status_slots[(size_t)ticket].quarantined = quarantine;  // the forward may still be queued and write the slot later
-                g_last_error = why;
-                return DGR_ERR_HIP;
-            };
-            while (!tag_here()) {
-                const auto now = std::chrono::steady_clock::now();
-                if (now - t0 > std::chrono::microseconds(400)) std::this_thread::sleep_for(std::chrono::microseconds(50));
-                if (now < next_query) continue;
-                next_query = now + std::chrono::milliseconds(1);
-                if (enqueued) {
-                    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-                    const bool capturing = hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-                    if (!capturing) {  // (a query on a capturing stream invalidates the capture)
-                        const hipError_t e = hipStreamQuery(stream);
-                        if (e == hipSuccess) {  // everything enqueued on the stream has completed: the tag is there, or it never will be
-                            if (tag_here()) break;
-                            return release("dgr_status_poll: the forward's stream is idle and its status word never arrived (was the forward "
-                                           "issued while the stream was being captured?)", false);
-                        }
-                        if (e != hipErrorNotReady) {
-                            (void)release("", true);
-                            return hip_fail(e, "dgr_status_poll: hipStreamQuery on the forward's stream");
-                        }
-                    }
-                }
-                if (limit_ms > 0 && now - t0 > std::chrono::milliseconds(limit_ms))
-                    return release("dgr_status_poll: timed out waiting for the forward's status word (DGR_STATUS_TIMEOUT_MS; 0 = no limit)", true);
-            }
-        }
-        const volatile int* w = pinned;
-        int word[8];
-        for (int i = 0; i < 8; i++) word[i] = w[i];
-        for (int i = 0; i < 4; i++) host_status4[i] = word[i];
-        std::lock_guard<std::mutex> lk(g_status_mu);
-        note_schedule_hint(g_status_slots[(size_t)ticket], word);
-        g_status_slots[(size_t)ticket].busy = false;
-        return 1;
-    }
-    if (wait) {
-        HIP_TRY(wait_event_spinning(ev));
-    } else {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipErrorNotReady) return 0;
-        if (e != hipSuccess) return hip_fail(e, "hipEventQuery");
-    }
-    for (int i = 0; i < 4; i++) host_status4[i] = pinned[i];
-    std::lock_guard<std::mutex> lk(g_status_mu);
-    g_status_slots[(size_t)ticket].busy = false;
-    return 1;
-}
-
-int dgr_stream_is_capturing(void* stream) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    return st == hipStreamCaptureStatusActive ? 1 : 0;
-}
-
-int dgr_backward_scratch_clean_arm(void) {
-    g_scratch_clean_armed = true;
-    return DGR_OK;
-}
-
-int dgr_early_status_arm(void) {
-    g_early.armed = true;
-    g_early.pending = false;
-    return DGR_OK;
-}
-int dgr_early_status_wait(int* host_status4) {
-    if (!host_status4) { g_last_error = "dgr_early_status_wait: NULL"; return DGR_ERR_BAD_ARGUMENT; }
-    if (!g_early.pending) {  // nothing was posted (P == 0, or no presized forward since arming)
-        g_early.armed = false;
-        host_status4[0] = host_status4[1] = host_status4[2] = host_status4[3] = 0;
-        return 1;
-    }
-    HIP_TRY(wait_event_spinning(g_early.ev));
-    for (int i = 0; i < 4; i++) host_status4[i] = g_early.pinned[i];
-    g_early.pending = false;
-    return DGR_OK;
-}
-
-int dgr_set_option(const char* name, int value) {
-    const std::string n(name ? name : "");
-    if (n == "blend_wgs_per_cu") { g_blend_wgs_per_cu.store((value >= 3 && value <= 7) ? value : 0); return DGR_OK; }
-    if (n == "tight_cull") { g_tight_cull.store(value ? 1 : 0); return DGR_OK; }
-    if (n == "tile_schedule") { g_tile_schedule.store(value < 0 ? 0 : value > 2 ? 2 : value); return DGR_OK; }
-    if (n == "fast_alpha") {  // (the option's name before alpha_mode 2 existed)
-        g_alpha_mode.store(value ? 1 : 0);
-        return DGR_OK;
-    }
-    if (n == "alpha_mode") {
-        if (value < 0 || value > 2) { g_last_error = "alpha_mode: 0 (restatement's bits, fp32 expf), 1 (fast), 2 (glibc's expf form)"; return DGR_ERR_BAD_ARGUMENT; }
-        g_alpha_mode.store(value);
-        return DGR_OK;
-    }
-    if (n == "lds_count") { g_lds_count.store(value < 0 ? 0 : value > 2 ? 2 : value); return DGR_OK; }
-    if (n == "lane_lists") { g_lane_lists.store(value < 0 ? 0 : value > 2 ? 2 : value); return DGR_OK; }
-    if (n == "deterministic_grads") { g_det_grads.store(value ? 1 : 0); return DGR_OK; }
-    if (n == "pose_grad") {
-        if (value < 0 || value > 1) { g_last_error = "pose_grad: 0 (the reference's pose terms) or 1 (complete)"; return DGR_ERR_BAD_ARGUMENT; }
-        g_pose_grad.store(value);
-        return DGR_OK;
-    }
-    if (n == "silhouette_grad") {
-        if (value < 0 || value > 1) { g_last_error = "silhouette_grad: 0 (the reference's gradients) or 1 (exact silhouette gradient)"; return DGR_ERR_BAD_ARGUMENT; }
-        g_silhouette_grad.store(value);
-        return DGR_OK;
-    }
-    if (n == "profile_every") { g_profile_every.store(value > 0 ? value : 1); return DGR_OK; }
-    if (n == "batch_order") { g_batch_order.store(value ? 1 : 0); return DGR_OK; }
-    if (n == "batch_streams") { g_batch_streams.store(value < 1 ? 1 : value > DGR_BATCH_MAX_STREAMS ? DGR_BATCH_MAX_STREAMS : value); return DGR_OK; }
-    g_last_error = "unknown option: " + n;
-    return DGR_ERR_BAD_ARGUMENT;
-}
-int dgr_get_option(const char* name) {
-    const std::string n(name ? name : "");
-    if (n == "blend_wgs_per_cu") return g_blend_wgs_per_cu.load();
-    if (n == "tight_cull") return g_tight_cull.load();
-    if (n == "tile_schedule") return g_tile_schedule.load();
-    if (n == "fast_alpha") return g_alpha_mode.load() == 1 ? 1 : 0;
-    if (n == "alpha_mode") return g_alpha_mode.load();
-    if (n == "lds_count") return g_lds_count.load();
-    if (n == "lane_lists") return g_lane_lists.load();
-    if (n == "deterministic_grads") return g_det_grads.load();
-    if (n == "pose_grad") return g_pose_grad.load();
-    if (n == "silhouette_grad") return g_silhouette_grad.load();
-    if (n == "profile_every") return g_profile_every.load();
-    if (n == "batch_streams") return g_batch_streams.load();
-    if (n == "batch_order") return g_batch_order.load();
-    return DGR_ERR_BAD_ARGUMENT;
-}
-
-int dgr_set_thread_option(const char* name, int value) {
-    const std::string n(name ? name : "");
-    if (n == "alpha_mode") {
-        if (value > 2) { g_last_error = "alpha_mode: 0, 1, 2 (or < 0: the process-wide option)"; return DGR_ERR_BAD_ARGUMENT; }
-        t_alpha_mode = value < 0 ? -1 : value;
-        return DGR_OK;
-    }
-    if (n == "fast_alpha") { t_alpha_mode = value < 0 ? -1 : (value ? 1 : 0); return DGR_OK; }
-    if (n == "tight_cull") { t_tight_cull = value < 0 ? -1 : (value ? 1 : 0); return DGR_OK; }
-    if (n == "deterministic_grads") { t_det_grads = value < 0 ? -1 : (value ? 1 : 0); return DGR_OK; }
-    if (n == "pose_grad") {
-        if (value > 1) { g_last_error = "pose_grad: 0, 1 (or < 0: the process-wide option)"; return DGR_ERR_BAD_ARGUMENT; }
-        t_pose_grad = value < 0 ? -1 : value;
-        return DGR_OK;
-    }
-    if (n == "silhouette_grad") {
-        if (value > 1) { g_last_error = "silhouette_grad: 0, 1 (or < 0: the process-wide option)"; return DGR_ERR_BAD_ARGUMENT; }
-        t_silhouette_grad = value < 0 ? -1 : value;
-        return DGR_OK;
-    }
-    g_last_error = "not a per-thread option: " + n;
-    return DGR_ERR_BAD_ARGUMENT;
-}
-int dgr_get_thread_option(const char* name) {
-    const std::string n(name ? name : "");
-    if (n == "alpha_mode") return opt_alpha_mode();
-    if (n == "fast_alpha") return opt_alpha_mode() == 1 ? 1 : 0;
-    if (n == "tight_cull") return opt_tight_cull();
-    if (n == "deterministic_grads") return opt_det_grads();
-    if (n == "pose_grad") return opt_pose_grad();
-    if (n == "silhouette_grad") return opt_silhouette_grad();
-    return DGR_ERR_BAD_ARGUMENT;
-}
-// the five as one word, each field = value + 1 (0 = "inherit", in an override word): bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
-// deterministic_grads, 12-15 pose_grad, 16-19 silhouette_grad
-int dgr_thread_options_effective(void) {
-    return (opt_alpha_mode() + 1) | ((opt_tight_cull() + 1) << 4) | ((opt_det_grads() + 1) << 8) | ((opt_pose_grad() + 1) << 12) |
-           ((opt_silhouette_grad() + 1) << 16);
-}
-int dgr_thread_options_swap(int word) {
-    const int prev = (t_alpha_mode + 1) | ((t_tight_cull + 1) << 4) | ((t_det_grads + 1) << 8) | ((t_pose_grad + 1) << 12) |
-                     ((t_silhouette_grad + 1) << 16);
-    if (word >= 0) {
-        t_alpha_mode = (word & 15) - 1;
-        t_tight_cull = ((word >> 4) & 15) - 1;
-        t_det_grads = ((word >> 8) & 15) - 1;
-        t_pose_grad = ((word >> 12) & 15) - 1;
-        t_silhouette_grad = ((word >> 16) & 15) - 1;
-    }
-    return prev;
-}
-
-int dgr_profile_select(const char* stage) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    const std::string n(stage ? stage : "");
-    bool found = n.empty() || n == "all";
-    for (auto& p : g_prof) {
-        p.seen = 0;
-        p.on = (n == "all") || (n == p.name);
-        found = found || p.on;
-    }
-    return found ? DGR_OK : DGR_ERR_BAD_ARGUMENT;
-}
-int dgr_profile_stage_count(void) { return ST_COUNT; }
-const char* dgr_profile_stage_name(int i) { return (i >= 0 && i < ST_COUNT) ? g_prof[i].name : ""; }
-int dgr_profile_read(const char* stage, double* total_ms, int* launches) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    for (auto& p : g_prof) {
-        if (std::string(stage) != p.name) continue;
-        double tot = 0;
-        int n = 0;
-        for (auto& e : p.ev) {
-            float ms = 0;
-            if (hipEventSynchronize(e.second) == hipSuccess && hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess) {
-                tot += ms;
-                n++;
-            }
-            (void)hipEventDestroy(e.first);
-            (void)hipEventDestroy(e.second);
-        }
-        p.ev.clear();
-        *total_ms = tot;
-        *launches = n;
-        return DGR_OK;
-    }
-    return DGR_ERR_BAD_ARGUMENT;
-}
-
-long dgr_state_export(void* stream, const char* name, int P, int width, int height, int num_rendered,
-                      int binning_capacity, const char* geom_buffer, const char* binning_buffer, const char* image_buffer,
-                      void* dst) {
-    hipStream_t st = (hipStream_t)stream;
-    if (binning_capacity < num_rendered) { g_last_error = "binning_capacity < num_rendered"; return -1; }
-    dgr::GeometryView g = dgr::carve_geometry(const_cast<char*>(geom_buffer), P);
-    dgr::ImageView img = dgr::carve_image(const_cast<char*>(image_buffer), width, height);
-    dgr::BinningView bin = dgr::carve_binning(const_cast<char*>(binning_buffer), (size_t)binning_capacity);
-    const size_t tiles = (size_t)dgr::tiles_x(width) * dgr::tiles_y(height), N = (size_t)width * height;
-    auto copy = [&](const void* src, size_t bytes) -> int {
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
-        return 0;
-    };
-    auto geomk = [&](int kind) -> int {
-        if (P > 0) hipLaunchKernelGGL(export_geom_kernel, dim3((P + 255) / 256), dim3(256), 0, st, kind, P, g, dst);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    };
-    const std::string n(name);
-    if (n == "depths") return copy(g.depths, 4 * (size_t)P) ? -1 : P;
-    if (n == "radii") return copy(g.radii, 4 * (size_t)P) ? -1 : P;
-    if (n == "means2D") return geomk(EX_MEANS2D) ? -1 : 2L * P;
-    if (n == "conic_opacity") return geomk(EX_CONIC_OPACITY) ? -1 : 4L * P;
-    if (n == "rgb") return geomk(EX_RGB) ? -1 : 3L * P;
-    if (n == "clamped") return geomk(EX_CLAMPED) ? -1 : 3L * P;
-    if (n == "tiles_touched") return geomk(EX_TILES_TOUCHED) ? -1 : P;
-    if (n == "point_list" || n == "contribution_tags" || n == "half_tags") {
-        if (num_rendered > 0) {
-            const dim3 grid((num_rendered + 255) / 256);
-            if (n == "point_list")
-                hipLaunchKernelGGL(export_point_list_kernel, grid, dim3(256), 0, st, bin.point_list, (uint32_t*)dst, num_rendered);
-            else  // (the tag bytes: in the binning's pair_cov bytes, render_common.h)
-                hipLaunchKernelGGL(export_tag_bytes_kernel, grid, dim3(256), 0, st, bin.pair_cov, (uint8_t*)dst, num_rendered, n == "half_tags" ? 1 : 0);
-            if (hipGetLastError() != hipSuccess) return -1;
-        }
-        return num_rendered;
-    }
-    if (n == "keys") {
-        hipLaunchKernelGGL(export_keys_kernel, dim3((unsigned)tiles), dim3(256), 0, st, img, bin, g, (uint64_t*)dst);
-        if (hipGetLastError() != hipSuccess) return -1;
-        return num_rendered;
-    }
-    if (n == "ranges") return copy(img.ranges, 8 * tiles) ? -1 : (long)(2 * tiles);
-    if (n == "tile_sched") return copy(img.tile_sched, 16 * tiles) ? -1 : (long)(4 * tiles);
-    if (n == "sched_flag") return copy(img.cursor + 3, 4) ? -1 : 1L;  // 1: this frame's blend kernels walk tile_sched, 0: the static band map
-    if (n == "n_contrib") return copy(img.n_contrib, 4 * N) ? -1 : (long)N;
-    if (n == "n_valid") return copy(img.n_valid, 4 * N) ? -1 : (long)N;
-    if (n == "final_T") return copy(img.final_T, 4 * N) ? -1 : (long)N;
-    g_last_error = "unknown state array: " + n;
-    return -1;
 }
 
 }  // extern "C"

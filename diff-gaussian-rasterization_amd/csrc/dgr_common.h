@@ -127,7 +127,7 @@ __host__ __device__ inline int xcd_contiguous(int b, int n) {
     return base + local;
 }
 
-// Where a forward reports its status word when a status slot is armed (api.hip: dgr_status_arm): `host` = pinned host memory
+// Where a forward reports its status word when a status slot is armed (status.hip: dgr_status_arm): `host` = pinned host memory
 // mapped into the device's address space.  The word is complete when the binning kernels have finished, so the first workgroup
 // of the forward blend -- the next kernel on the stream -- copies it there: {num_rendered, overflow, prefiltered violation, 0,
 // tag, longest tile list}, `tag` last, and the host reads it without a copy, an event or a wait.  `ws` = a device word owned by

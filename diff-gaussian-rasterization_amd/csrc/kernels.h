@@ -14,7 +14,7 @@ struct LaunchEvents {
     hipEvent_t start, stop;
     bool used;
 };
-extern thread_local LaunchEvents* g_launch_events;  // api.hip
+extern thread_local LaunchEvents* g_launch_events;  // profile.hip
 
 template <typename K, typename... Args>
 inline void launch(K kernel, dim3 grid, dim3 block, hipStream_t stream, Args... args) {
@@ -41,7 +41,7 @@ inline void launch_shmem(K kernel, dim3 grid, dim3 block, size_t shmem, hipStrea
 // whole register file and 144 of the 160 KB of LDS, so another stream's kernels enter a CU only as blend workgroups drain.
 // dgr_set_option("blend_wgs_per_cu", n) (3 <= n <= 7; 0 = no cap) pads each blend workgroup with unused dynamic LDS so
 // that at most n fit a CU, which leaves wave slots, registers and LDS for the other views' bandwidth- and latency-bound
-// kernels.  blend_pad_bytes() (api.hip) caches the kernels' static LDS sizes.
+// kernels.  blend_pad_bytes() (options.hip) caches the kernels' static LDS sizes.
 size_t blend_pad_bytes(const void* kernel);
 template <typename K, typename... Args>
 inline void launch_blend(K kernel, dim3 grid, dim3 block, hipStream_t stream, Args... args) {

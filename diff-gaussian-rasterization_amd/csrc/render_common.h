@@ -11,7 +11,7 @@ namespace dgr {
 // Workgroup b of a blend kernel -> {tile, list start, list end}.  With a schedule (tile_schedule_kernel, binning.hip: classes of
 // long lists first, neighbours on one XCD) that is one 16-byte entry.  A frame whose lists are even needs none -- the schedule
 // then is the static map with extra steps: a launch, 11 us in front of the blend at 1080p, and neighbours spread a little --
-// so the forward skips the kernel (api.hip: the policy) and the workgroups fall back on the band map of rounds 1-5: workgroup
+// so the forward skips the kernel (status.hip: want_schedule, the policy) and the workgroups fall back on the band map of rounds 1-5: workgroup
 // b runs on XCD b % 8, every XCD takes a contiguous band of the image (neighbouring tiles share the records in its L2).
 // Which of the two a frame uses is recorded in its image state by the binning kernel (cursor[3]) for forward and backward alike.
 // The same word's bit 1 says that the frame's binning buffer OVERFLOWED (every tile list is empty): the forward kernels then write NaN

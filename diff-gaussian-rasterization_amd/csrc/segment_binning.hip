@@ -595,7 +595,7 @@ int segment_shift(int W, int H, int capacity, int longest_list) {
     // small frames: bin_tiles is one workgroup per segment and each is a chain of dependent phases -- 90 workgroups on 256
     // CUs (640x480 at 16 tiles per segment) took as long as 544 (1920x1080); prefer at least two workgroups per CU
     while (sh > 2 && (long)gy * ((gx + (1 << sh) - 1) >> sh) < 512) sh--;
-    // The frame's longest tile list, where the last forward of this shape reported it (api.hip: hinted_longest_list): a frame
+    // The frame's longest tile list, where the last forward of this shape reported it (status.hip: hinted_longest_list): a frame
     // whose lists are uneven -- a cluster of 1000-entry lists in a frame that averages 220 -- has segments that overflow the
     // budget although the average one fits, and each of those takes the dense path (every phase several times slower:
     // profiles/r9/bin_tiles_trace_before.txt).  Smaller segments, as long as one made of such lists still fits; if not even

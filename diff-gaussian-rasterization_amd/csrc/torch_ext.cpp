@@ -85,7 +85,7 @@ inline Tensor f32c(const Tensor& t, const c10::Device& dev) {
 // which the transposed storage does not hold where the kernels look: it gets the contiguous copy.
 inline Tensor f32c_diag4(const Tensor& t, const c10::Device& dev) {
     if (t.scalar_type() == at::kFloat && t.device() == dev && t.dim() == 2 && t.size(0) == 4 && t.size(1) == 4 && t.stride(0) == 1 &&
-        t.stride(1) == 4 && ((dgr_thread_options_effective() >> 12) & 15) != 2)
+        t.stride(1) == 4 && ((dgr_thread_options_effective() >> DGR_OPT_SHIFT_POSE_GRAD) & 15) != 2)
         return t;
     return f32c(t, dev);
 }
@@ -714,8 +714,8 @@ inline bool needs_gaussian_grads(AutogradContext* ctx) {
     return need;
 }
 
-// the "silhouette_grad" field (bits 16-19) of such a word: the exact silhouette gradient was on at the forward
-inline bool silhouette_on(int word) { return ((word >> 16) & 15) == 2; }
+// the "silhouette_grad" field (DGR_OPT_SHIFT_SILHOUETTE_GRAD) of such a word: the exact silhouette gradient was on at the forward
+inline bool silhouette_on(int word) { return ((word >> DGR_OPT_SHIFT_SILHOUETTE_GRAD) & 15) == 2; }
 // a block under a word of dgr_thread_options_effective() (include/dgr_hip.h): a backward under its forward's options
 struct UnderOptions {
     int prev;

@@ -267,7 +267,7 @@ class thread_options:
 
 def silhouette_on(word):
     """Whether a dgr_thread_options_effective() word has the option "silhouette_grad" on (bits 16-19: value + 1)."""
-    return ((int(word) >> 16) & 15) == 2
+    return ((int(word) >> 16) & 15) == 2  # 16 = DGR_OPT_SHIFT_SILHOUETTE_GRAD (include/dgr_hip.h)
 
 
 class under_options:

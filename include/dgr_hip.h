@@ -337,7 +337,8 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
  *  "profile_every": n >= 1 = dgr_profile_* brackets every n-th launch of the selected stage only (default 1).
  *  "batch_streams" (default 2): streams the batched entry points spread the per-view stages of a batch over (1..8).
  *  "batch_order" (default 0): 0 = view v's binning + blend chain on stream v mod batch_streams; 1 = all binning stages on a
- *     helper stream and all blend stages on the caller's, joined per view by events (measured slower: csrc/api.hip). */
+ *     helper stream and all blend stages on the caller's, joined per view by events (measured slower: csrc/api.hip).
+ * (csrc/options.h holds the table of these options: a new one is a row there and a line here.) */
 int dgr_set_option(const char* name, int value);
 int dgr_get_option(const char* name);
 
@@ -349,7 +350,12 @@ int dgr_get_option(const char* name);
  * uses.  dgr_thread_options_effective() packs the five (each field value + 1: bits 0-3 alpha_mode, 4-7 tight_cull, 8-11
  * deterministic_grads, 12-15 pose_grad, 16-19 silhouette_grad) and dgr_thread_options_swap(word) installs such a word as the thread's overrides (field 0 = inherit;
  * word < 0: only read) and returns the previous one -- what an autograd binding uses to run a backward, on whatever thread the
- * engine picks, under its forward's options. */
+ * engine picks, under its forward's options.  DGR_OPT_SHIFT_*: the fields' first bits. */
+#define DGR_OPT_SHIFT_ALPHA_MODE 0
+#define DGR_OPT_SHIFT_TIGHT_CULL 4
+#define DGR_OPT_SHIFT_DETERMINISTIC_GRADS 8
+#define DGR_OPT_SHIFT_POSE_GRAD 12
+#define DGR_OPT_SHIFT_SILHOUETTE_GRAD 16
 int dgr_set_thread_option(const char* name, int value);
 int dgr_get_thread_option(const char* name);
 int dgr_thread_options_effective(void);

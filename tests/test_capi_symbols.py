@@ -72,6 +72,125 @@ def test_options_round_trip_and_reject_unknown_names():
     assert lib.dgr_profile_select(b"no_such_stage") == _capi.DGR_ERR_BAD_ARGUMENT
 
 
+X = None  # dgr_set_option refuses the value (DGR_ERR_BAD_ARGUMENT) and the option keeps what it had
+SET_VALUES = tuple(range(-2, 10))
+NORMALISED = (1, 1, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1)
+CLAMPED_0_2 = (0, 0, 0, 1, 2, 2, 2, 2, 2, 2, 2, 2)
+ONLY_0_1 = (X, X, 0, 1, X, X, X, X, X, X, X, X)
+# name: (default, dgr_get_option after dgr_set_option(name, v) for v = -2 .. 9) -- the option table of csrc/options.hip as a caller
+# sees it (include/dgr_hip.h); "fast_alpha" is the alias of "alpha_mode" (set: value ? 1 : 0; get: mode == 1)
+OPTION_TABLE = {
+    "blend_wgs_per_cu": (0, (0, 0, 0, 0, 0, 3, 4, 5, 6, 7, 0, 0)),
+    "tight_cull": (0, NORMALISED),
+    "deterministic_grads": (0, NORMALISED),
+    "batch_order": (0, NORMALISED),
+    "fast_alpha": (0, NORMALISED),
+    "tile_schedule": (2, CLAMPED_0_2),
+    "lane_lists": (2, CLAMPED_0_2),
+    "lds_count": (1, CLAMPED_0_2),
+    "alpha_mode": (0, (X, X, 0, 1, 2, X, X, X, X, X, X, X)),
+    "pose_grad": (0, ONLY_0_1),
+    "silhouette_grad": (0, ONLY_0_1),
+    "profile_every": (1, (1, 1, 1, 1, 2, 3, 4, 5, 6, 7, 8, 9)),
+    "batch_streams": (2, (1, 1, 1, 1, 2, 3, 4, 5, 6, 7, 8, 8)),
+}
+# name: largest value dgr_set_thread_option takes (None: any value >= 0 is normalised to 0 / 1); the field's shift in the options word
+THREAD_OPTIONS = {"alpha_mode": (2, 0), "fast_alpha": (None, 0), "tight_cull": (None, 4), "deterministic_grads": (None, 8),
+                  "pose_grad": (1, 12), "silhouette_grad": (1, 16)}
+OPTION_ENV = ("DGR_TILE_SCHEDULE", "DGR_ALPHA_MODE", "DGR_FAST_ALPHA", "DGR_DETERMINISTIC_GRADS", "DGR_POSE_GRAD",
+              "DGR_SILHOUETTE_GRAD", "DGR_FWD_HALVES", "DGR_LDS_COUNT", "DGR_BLEND_WGS_PER_CU")
+
+
+def test_the_whole_option_table_process_and_thread():
+    """Every option's default, what dgr_set_option makes of -2 .. 9 (clamp, normalise, window or refuse), the per-thread
+    overrides, unknown names, the options word and its swap.  Host-side state only; every value touched is put back."""
+    lib = _capi.load()
+    BAD = _capi.DGR_ERR_BAD_ARGUMENT
+    pristine = not any(v in os.environ for v in OPTION_ENV)  # (the environment sets initial values: defaults only without it)
+    saved = {n: lib.dgr_get_option(n.encode()) for n in OPTION_TABLE if n != "fast_alpha"}
+    saved_word = lib.dgr_thread_options_swap(-1)
+    try:
+        lib.dgr_thread_options_swap(0)  # no overrides while the process-wide values are walked
+        if pristine:
+            for name, (default, _) in OPTION_TABLE.items():
+                assert lib.dgr_get_option(name.encode()) == default, name
+            assert saved_word == 0
+            assert lib.dgr_thread_options_effective() == 69905 == 0x11111
+            assert lib.dgr_thread_options_swap(0) == 0
+        # ---- process-wide
+        for name, (_, after) in OPTION_TABLE.items():
+            n = name.encode()
+            for v, want in zip(SET_VALUES, after):
+                before = lib.dgr_get_option(n)
+                rc = lib.dgr_set_option(n, v)
+                if want is X:
+                    assert rc == BAD, (name, v)
+                    assert lib.dgr_last_error().startswith(n + b": "), (name, v, lib.dgr_last_error())
+                    assert lib.dgr_get_option(n) == before, (name, v)
+                else:
+                    assert rc == 0 and lib.dgr_get_option(n) == want, (name, v, lib.dgr_get_option(n))
+            if name == "fast_alpha":  # the alias writes alpha_mode 0 / 1 and reads "alpha_mode == 1"
+                for mode, fast in ((0, 0), (1, 1), (2, 0)):
+                    assert lib.dgr_set_option(b"alpha_mode", mode) == 0 and lib.dgr_get_option(b"fast_alpha") == fast
+                assert lib.dgr_set_option(b"fast_alpha", 5) == 0 and lib.dgr_get_option(b"alpha_mode") == 1
+            lib.dgr_set_option(b"alpha_mode" if name == "fast_alpha" else n, saved["alpha_mode" if name == "fast_alpha" else name])
+        # ---- unknown names: set says so, the getters return the error code and leave the last error alone
+        assert lib.dgr_set_option(b"no_such_option", 1) == BAD and lib.dgr_last_error() == b"unknown option: no_such_option"
+        assert lib.dgr_set_option(b"alpha_mode", 3) == BAD
+        marker = lib.dgr_last_error()
+        assert marker.startswith(b"alpha_mode: ")
+        assert lib.dgr_get_option(b"no_such_option") == BAD and lib.dgr_get_thread_option(b"no_such_option") == BAD
+        assert lib.dgr_get_thread_option(b"lds_count") == BAD  # (not a per-thread option: nothing to read either)
+        assert lib.dgr_last_error() == marker
+        # ---- per thread
+        for name in list(OPTION_TABLE) + ["no_such_option"]:
+            n = name.encode()
+            if name not in THREAD_OPTIONS:
+                for v in (-1, 0, 1):
+                    assert lib.dgr_set_thread_option(n, v) == BAD, (name, v)
+                    assert lib.dgr_last_error() == b"not a per-thread option: " + n
+                continue
+            top, shift = THREAD_OPTIONS[name]
+            target = b"alpha_mode" if name == "fast_alpha" else n
+            for process_value in (0, 1):
+                assert lib.dgr_set_option(target, process_value) == 0
+                for v in SET_VALUES:
+                    before = lib.dgr_get_thread_option(n)
+                    rc = lib.dgr_set_thread_option(n, v)
+                    if top is not None and v > top:
+                        assert rc == BAD, (name, v)
+                        assert lib.dgr_last_error().startswith(n + b": ") and b"process-wide" in lib.dgr_last_error()
+                        assert lib.dgr_get_thread_option(n) == before, (name, v)
+                        continue
+                    want = process_value if v < 0 else (v if top is not None else int(v != 0))
+                    assert rc == 0 and lib.dgr_get_thread_option(n) == want, (name, v)
+                    assert lib.dgr_get_option(target) == process_value, (name, v)  # the process-wide value is untouched
+                    mode = lib.dgr_get_thread_option(target)
+                    assert (lib.dgr_thread_options_effective() >> shift) & 15 == mode + 1, (name, v)
+                    assert (lib.dgr_thread_options_swap(-1) >> shift) & 15 == (0 if v < 0 else mode + 1), (name, v)
+                assert lib.dgr_set_thread_option(n, -1) == 0
+            lib.dgr_set_option(target, saved[target.decode()])
+        # ---- the options word: every field value + 1, swap installs overrides (field 0 = inherit) and returns the previous word
+        for n in saved:
+            lib.dgr_set_option(n.encode(), 0 if n in ("alpha_mode", "tight_cull", "deterministic_grads", "pose_grad", "silhouette_grad") else saved[n])
+        assert lib.dgr_thread_options_swap(0) == 0 and lib.dgr_thread_options_effective() == 0x11111
+        word = (2 + 1) | (1 + 1) << 4 | (0 + 1) << 8 | (1 + 1) << 12 | (1 + 1) << 16
+        assert lib.dgr_thread_options_swap(word) == 0
+        assert lib.dgr_thread_options_effective() == word and lib.dgr_thread_options_swap(-1) == word
+        got = [lib.dgr_get_thread_option(n) for n in (b"alpha_mode", b"fast_alpha", b"tight_cull", b"deterministic_grads", b"pose_grad", b"silhouette_grad")]
+        assert got == [2, 0, 1, 0, 1, 1]
+        assert all(lib.dgr_get_option(n.encode()) == 0 for n in ("alpha_mode", "tight_cull", "deterministic_grads", "pose_grad", "silhouette_grad"))
+        partial = (1 + 1) << 4  # only tight_cull overridden: the other four inherit
+        assert lib.dgr_thread_options_swap(partial) == word
+        assert lib.dgr_thread_options_effective() == 0x11111 + (1 << 4) and lib.dgr_thread_options_swap(-1) == partial
+        assert lib.dgr_thread_options_swap(0) == partial and lib.dgr_thread_options_effective() == 0x11111
+    finally:
+        for n, v in saved.items():
+            lib.dgr_set_option(n.encode(), v)
+        lib.dgr_thread_options_swap(saved_word)
+    assert {n: lib.dgr_get_option(n.encode()) for n in saved} == saved and lib.dgr_thread_options_swap(-1) == saved_word
+
+
 def test_early_status_without_a_forward_reports_nothing_posted():
     import ctypes
     lib = _capi.load()

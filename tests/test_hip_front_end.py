@@ -414,7 +414,7 @@ def test_inputs_made_on_the_callers_stream_and_dropped_after_the_call_stay_valid
 @pytest.mark.parametrize("cap", [7, 5])
 def test_capped_blend_kernels_give_the_same_view(variant, cap):
     """dgr_set_option("blend_wgs_per_cu", n): the blend kernels claim enough dynamic LDS that only n of their workgroups fit a
-    CU (room for the other streams' kernels and RCCL's; csrc/api.hip: blend_pad_bytes).  A scheduling choice: images and lists
+    CU (room for the other streams' kernels and RCCL's; csrc/options.hip: blend_pad_bytes).  A scheduling choice: images and lists
     bit-identical, gradients equal up to the order of the float atomics."""
     s = make_scene(30000, 320, 240, 6)
     fwd, bwd = (hh.hip_forward, hh.hip_backward) if variant == "light" else (hh.hip_full_forward, hh.hip_full_backward)

@@ -103,11 +103,67 @@ def test_silhouette_field_in_the_options_word(restore_silhouette):
     assert field(lib.dgr_thread_options_effective(), 16) == 2
 
 
-@pytest.mark.parametrize("value,want", [("1", 1), ("0", 0), ("2", 0), ("11", 0)])
-def test_silhouette_env_in_a_fresh_process(value, want):
-    code = "from dgr_amd import _capi; print(_capi.get_option('silhouette_grad'))"
+OPTION_VARS = ("DGR_TILE_SCHEDULE", "DGR_ALPHA_MODE", "DGR_FAST_ALPHA", "DGR_DETERMINISTIC_GRADS", "DGR_POSE_GRAD",
+               "DGR_SILHOUETTE_GRAD", "DGR_FWD_HALVES", "DGR_LDS_COUNT", "DGR_BLEND_WGS_PER_CU")
+
+
+def env_case(variable, option, string, want, also=None, id=None):
+    return pytest.param(variable, option, string, want, also or {}, id=id or f"{variable}-{string}")
+
+
+# (variable, option, string, expected initial value[, other variables set beside it]): the eight variables of the option table
+# (csrc/options.hip) with the strings INTEGRATION.md and include/dgr_hip.h offer, DGR_FAST_ALPHA behind DGR_ALPHA_MODE, and per
+# variable one malformed string: the whole string must be one accepted digit, anything else leaves the default.
+ENV_CASES = [
+    env_case("DGR_SILHOUETTE_GRAD", "silhouette_grad", "1", 1, id="1-1"),
+    env_case("DGR_SILHOUETTE_GRAD", "silhouette_grad", "0", 0, id="0-0"),
+    env_case("DGR_SILHOUETTE_GRAD", "silhouette_grad", "2", 0, id="2-0"),
+    env_case("DGR_SILHOUETTE_GRAD", "silhouette_grad", "11", 0, id="11-0"),
+    env_case("DGR_TILE_SCHEDULE", "tile_schedule", "0", 0),
+    env_case("DGR_TILE_SCHEDULE", "tile_schedule", "1", 1),
+    env_case("DGR_TILE_SCHEDULE", "tile_schedule", "2", 2),
+    env_case("DGR_TILE_SCHEDULE", "tile_schedule", "12", 2),
+    env_case("DGR_ALPHA_MODE", "alpha_mode", "0", 0),
+    env_case("DGR_ALPHA_MODE", "alpha_mode", "1", 1),
+    env_case("DGR_ALPHA_MODE", "alpha_mode", "2", 2),
+    env_case("DGR_ALPHA_MODE", "alpha_mode", "11", 0),
+    env_case("DGR_ALPHA_MODE", "alpha_mode", "0", 0, {"DGR_FAST_ALPHA": "1"}, id="DGR_ALPHA_MODE-0-before-DGR_FAST_ALPHA"),
+    env_case("DGR_ALPHA_MODE", "alpha_mode", "2", 2, {"DGR_FAST_ALPHA": "1"}, id="DGR_ALPHA_MODE-2-before-DGR_FAST_ALPHA"),
+    env_case("DGR_ALPHA_MODE", "alpha_mode", "7", 1, {"DGR_FAST_ALPHA": "1"}, id="DGR_ALPHA_MODE-refused-then-DGR_FAST_ALPHA"),
+    env_case("DGR_FAST_ALPHA", "alpha_mode", "1", 1),
+    env_case("DGR_FAST_ALPHA", "fast_alpha", "1", 1, id="DGR_FAST_ALPHA-1-by-its-own-name"),
+    env_case("DGR_FAST_ALPHA", "alpha_mode", "0", 0),
+    env_case("DGR_FAST_ALPHA", "alpha_mode", "11", 0),
+    env_case("DGR_DETERMINISTIC_GRADS", "deterministic_grads", "1", 1),
+    env_case("DGR_DETERMINISTIC_GRADS", "deterministic_grads", "0", 0),
+    env_case("DGR_DETERMINISTIC_GRADS", "deterministic_grads", "10", 0),
+    env_case("DGR_POSE_GRAD", "pose_grad", "1", 1),
+    env_case("DGR_POSE_GRAD", "pose_grad", "0", 0),
+    env_case("DGR_POSE_GRAD", "pose_grad", "11", 0),
+    env_case("DGR_FWD_HALVES", "lane_lists", "0", 0),
+    env_case("DGR_FWD_HALVES", "lane_lists", "1", 1),
+    env_case("DGR_FWD_HALVES", "lane_lists", "2", 2),
+    env_case("DGR_FWD_HALVES", "lane_lists", "10", 2),
+    env_case("DGR_LDS_COUNT", "lds_count", "0", 0),
+    env_case("DGR_LDS_COUNT", "lds_count", "1", 1),
+    env_case("DGR_LDS_COUNT", "lds_count", "2", 2),
+    env_case("DGR_LDS_COUNT", "lds_count", "05", 1),
+    env_case("DGR_BLEND_WGS_PER_CU", "blend_wgs_per_cu", "3", 3),
+    env_case("DGR_BLEND_WGS_PER_CU", "blend_wgs_per_cu", "7", 7),
+    env_case("DGR_BLEND_WGS_PER_CU", "blend_wgs_per_cu", "2", 0),
+    env_case("DGR_BLEND_WGS_PER_CU", "blend_wgs_per_cu", "8", 0),
+    env_case("DGR_BLEND_WGS_PER_CU", "blend_wgs_per_cu", "35", 0),
+]
+
+
+@pytest.mark.parametrize("variable,option,value,want,also", ENV_CASES)
+def test_silhouette_env_in_a_fresh_process(variable, option, value, want, also):
+    code = f"from dgr_amd import _capi; print(_capi.get_option('{option}'))"
     pkg = os.path.dirname(os.path.dirname(os.path.abspath(_capi.__file__)))  # (the child imports the package from the tree)
-    env = dict(os.environ, DGR_SILHOUETTE_GRAD=value, PYTHONPATH=os.pathsep.join([pkg, os.environ.get("PYTHONPATH", "")]))
+    env = {k: v for k, v in os.environ.items() if k not in OPTION_VARS}         # (only the case's own variables)
+    env.update(also)
+    env[variable] = value
+    env["PYTHONPATH"] = os.pathsep.join([pkg, os.environ.get("PYTHONPATH", "")])
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120,
                          cwd=os.path.dirname(os.path.abspath(__file__)))
     assert out.returncode == 0, out.stderr
