@@ -307,3 +307,32 @@ def placed(cam: Camera, P, placement, seed=0, **kw):
     if placement == "near":
         return near_scene(s, cam, **kw)
     return s, {}
+
+
+# ------------------------------------------------------------------------------------------ cases of the float64 model's tests
+# (camera, placement, P, W, SH degree, seed): off-centre principal points, fx != fy, the Jacobian clamp and the near plane, where
+# the reference's shortened pose Jacobian and the exact one part.  (The placements' bands are sized to these small frames: a
+# hundred Gaussians of sigma 20 .. 150 px stacked on every pixel of a 64 x 48 frame leave the float32 backward's transmittance,
+# re-derived by division, at 5e-4 of scale from float64 -- in dL_dopacity as much as anywhere, a property of the reference's
+# algorithm, not of the camera.)
+CAMERA_CASES = [("tum", "plain", 400, 64, 3, 21), ("skewed_pp", "plain", 400, 64, 2, 22),
+                ("skewed_pp", "clamp", 500, 96, 3, 23, dict(n=70, sigma_px=(12.0, 40.0), opacity=(0.05, 0.25))),
+                ("tum", "near", 300, 48, 1, 24, dict(n=30, sigma_px=(4.0, 16.0), opacity=(0.05, 0.25)))]
+
+
+def camera_case_id(case):
+    return f"{case[0]}-{case[1]}"
+
+
+def camera_case_scene(case):
+    """(scene, SH degree, placement info) of a CAMERA_CASES entry; the placement's edge is asserted by the caller."""
+    cid, placement, P, W, deg, seed = case[:6]
+    s, info = placed(CAMERAS[cid].at(W), P, placement, seed, **(case[6] if len(case) > 6 else {}))
+    return s, deg, info
+
+
+def assert_placement_edge(oracle, placement, s, info, radii):
+    if placement == "clamp":
+        assert_clamp_edge(s, info, radii)
+    elif placement == "near":
+        assert_near_edge(s, info, oracle.mark_visible(s.means, s.view, s.proj), radii, least=10)

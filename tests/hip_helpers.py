@@ -2,9 +2,11 @@
 import ctypes as C
 
 import numpy as np
+import pytest
 import torch
 
 from dgr_amd import _capi
+from dgr_amd import full as F
 from dgr_amd import light as L
 
 
@@ -18,6 +20,18 @@ def T(a):
 
 def E():
     return torch.empty(0, device=dev())
+
+
+@pytest.fixture(params=["compiled", "ctypes"])
+def binding(request, monkeypatch):
+    """over the compiled torch extension (its functions and autograd nodes) and over the ctypes binding of the same C ABI (the
+    `_C` classes and Python Functions; the batch classes follow).  A test module imports it by name."""
+    if request.param == "ctypes":
+        monkeypatch.setattr(L, "_C", L._CtypesC)
+        monkeypatch.setattr(F, "_C", F._CtypesC)
+    elif L._C is not L._CompiledC:
+        pytest.skip("compiled extension not built")
+    return request.param
 
 
 def hip_forward(s, deg, colors_precomp=None, cov3D_precomp=None, prefiltered=False, debug=False, scale_modifier=1.0):
@@ -91,26 +105,44 @@ def hip_cov3D(s, scale_modifier=1.0):
     return shared_cov3D(T(s.scales), T(s.rots), scale_modifier).detach().cpu().numpy()
 
 
-def hip_backward(s, deg, out, colors_precomp=None, cov3D_precomp=None, track_off=False, map_off=False,
-                 scale_modifier=1.0, grads=None, alphas=None):
-    """`alphas` overrides the forward's own opacity map (stage isolation: the light backward derives
-    T_final = 1 - alpha, which amplifies one-ulp forward differences on nearly opaque pixels)."""
+def _image(g, channel=True):
+    """a gradient image for the binding: float32, [1, H, W] (`channel`); None -> the empty tensor (a lean backward's NULL)"""
+    if g is None:
+        return E()
+    g = np.asarray(g, np.float32)
+    return T(g[None] if channel else g)
+
+
+def hip_backward_raw(s, deg, out, grads=None, bg=None, silhouette=None, absgrad=False, track_off=False, map_off=False,
+                     colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0, alphas=None, persp=None):
+    """`L._C.rasterize_gaussians_backward` on a scene and a forward's outputs: the binding's tuple.  `grads` (gC, gD, gM, gV;
+    default the scene's): a None median / variance image is not passed (lean); `silhouette`: dL/d opacity_map [H, W];
+    `alphas` overrides the forward's own opacity map (stage isolation: the light backward derives T_final = 1 - alpha, which
+    amplifies one-ulp forward differences on nearly opaque pixels); `persp`: a device tensor in place of the scene's Proj^T."""
     use_sh = colors_precomp is None
     use_sr = cov3D_precomp is None
     (R, color, depth, median, var, alpha, radii, geom, binning, img, _, _) = out
     gC, gD, gM, gV = grads if grads is not None else (s.gC, s.gD, s.gM, s.gV)
     if alphas is not None:
         alpha = T(alphas)
-    g = L._C.rasterize_gaussians_backward(
-        T(s.bg), T(s.means), radii, E() if use_sh else T(colors_precomp), T(s.scales) if use_sr else E(),
+    return L._C.rasterize_gaussians_backward(
+        T(s.bg if bg is None else bg), T(s.means), radii, E() if use_sh else T(colors_precomp), T(s.scales) if use_sr else E(),
         T(s.rots) if use_sr else E(), scale_modifier, E() if use_sr else T(cov3D_precomp), T(s.view), T(s.proj),
-        s.tanfovx, s.tanfovy, T(gC), T(gD[None]), T(gM[None]), T(gV[None]), T(s.gt), T(s.shs) if use_sh else E(), deg,
-        T(s.campos), geom, R, binning, img, alpha, False, T(s.persp), track_off, map_off)
-    names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
-             "dL_drotations", "dL_dview"]
+        s.tanfovx, s.tanfovy, _image(gC, False), _image(gD), _image(gM), _image(gV), T(s.gt), T(s.shs) if use_sh else E(), deg,
+        T(s.campos), geom, R, binning, img, alpha, False, T(s.persp) if persp is None else persp, track_off, map_off,
+        absgrad=absgrad, silhouette=None if silhouette is None else _image(silhouette))
+
+
+GRAD_NAMES = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales", "dL_drotations",
+              "dL_dview"]
+
+
+def hip_backward(s, deg, out, **kw):
+    """hip_backward_raw's gradients as a dict of numpy arrays"""
+    g = hip_backward_raw(s, deg, out, **kw)
     assert tuple(g[8].shape) == (1, 4, 4)  # what the reference's own __init__.py sums over dim 0
     g = list(g[:8]) + [torch.sum(g[8], dim=0)]
-    return {n: v.cpu().numpy() for n, v in zip(names, g)}
+    return {n: v.cpu().numpy() for n, v in zip(GRAD_NAMES, g)}
 
 
 def oracle_forward(O, s, deg, colors_precomp=None, cov3D_precomp=None, scale_modifier=1.0):
@@ -134,7 +166,6 @@ def oracle_backward(O, st, s, deg, alphas, colors_precomp=None, cov3D_precomp=No
 
 # ------------------------------------------------------------------------------------------ full variant
 def hip_full_forward(s, deg, colors_precomp=None, cov3D_precomp=None):
-    from dgr_amd import full as F
     use_sh = colors_precomp is None
     use_sr = cov3D_precomp is None
     out = F._C.rasterize_gaussians(
@@ -147,20 +178,22 @@ def hip_full_forward(s, deg, colors_precomp=None, cov3D_precomp=None):
     return out, d
 
 
-def hip_full_backward(s, deg, out, colors_precomp=None, cov3D_precomp=None, grads=None):
-    from dgr_amd import full as F
+def hip_full_backward_raw(s, deg, out, grads=None, bg=None, silhouette=None, absgrad=False, colors_precomp=None,
+                          cov3D_precomp=None):
+    """`F._C.rasterize_gaussians_backward`, as hip_backward_raw; `grads` (gC, gD, gU), a None uncertainty image is not passed"""
     use_sh = colors_precomp is None
     use_sr = cov3D_precomp is None
     (R, NG, color, depth, unc, radii, geom, binning, img) = out
     gC, gD, gU = grads if grads is not None else (s.gC, s.gD, s.gV)
-    g = F._C.rasterize_gaussians_backward(
-        T(s.bg), T(s.means), radii, E() if use_sh else T(colors_precomp), T(s.scales) if use_sr else E(),
+    return F._C.rasterize_gaussians_backward(
+        T(s.bg if bg is None else bg), T(s.means), radii, E() if use_sh else T(colors_precomp), T(s.scales) if use_sr else E(),
         T(s.rots) if use_sr else E(), 1.0, E() if use_sr else T(cov3D_precomp), T(s.view), T(s.gt), T(s.proj), s.tanfovx,
-        s.tanfovy, T(gC), T(gD[None]), T(gU[None]), T(s.shs) if use_sh else E(), deg, T(s.campos), geom, R, binning, img,
-        NG, T(s.persp))
-    names = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
-             "dL_drotations", "dL_dview"]
-    return {n: v.cpu().numpy() for n, v in zip(names, g)}
+        s.tanfovy, _image(gC, False), _image(gD), _image(gU), T(s.shs) if use_sh else E(), deg, T(s.campos), geom, R, binning, img,
+        NG, T(s.persp), absgrad=absgrad, silhouette=None if silhouette is None else _image(silhouette))
+
+
+def hip_full_backward(s, deg, out, **kw):
+    return {n: v.cpu().numpy() for n, v in zip(GRAD_NAMES, hip_full_backward_raw(s, deg, out, **kw))}
 
 
 def oracle_full(O, s, deg, colors_precomp=None, cov3D_precomp=None, grads=None, backward=True):

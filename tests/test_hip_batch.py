@@ -17,21 +17,19 @@ import torch
 
 from util import assert_grad_close, assert_image_close, make_scene, mask_flipped_pixels
 import hip_helpers as hh
+from hip_helpers import binding  # noqa: F401  (fixture)
 from dgr_amd import batch as B
 from dgr_amd import light as L
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(autouse=True, params=["compiled", "ctypes"])
-def binding(request, monkeypatch):
+@pytest.fixture(autouse=True)
+def batch_binding(binding):
     """every test runs over the compiled torch extension (csrc/torch_ext.cpp: light_forward_batch / light_backward_batch) and
     over the ctypes binding of the same C ABI"""
-    if request.param == "ctypes":
-        monkeypatch.setattr(L, "_C", L._CtypesC)
-    elif L._C is not L._CompiledC:
-        pytest.skip("compiled extension not built")
-    assert (B._ext() is not None) == (request.param == "compiled")
+    assert (B._ext() is not None) == (binding == "compiled")
+
 
 IMAGES = ("color", "depth", "depth_median", "opacity_map")
 T, E = hh.T, hh.E

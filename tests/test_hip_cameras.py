@@ -10,12 +10,12 @@ import pytest
 import torch
 
 import hip_helpers as hh
-from cameras import CAMERAS, CAMERA_IDS, PLACEMENTS, assert_clamp_edge, assert_near_edge, placed
-from test_complete_pose_fp64 import complete_grad, oracle_run, scaled_grads
+from cameras import (CAMERAS, CAMERA_CASES, CAMERA_IDS, PLACEMENTS, assert_clamp_edge, assert_near_edge, camera_case_id,
+                     camera_case_scene, placed)
+from fp64_model import absgrad_of_pairs, complete_grad, oracle_run, scaled_grads, torch_light
 from test_hip_complete_pose import _identity_distance, hip_view_grad
 from test_hip_light_parity import IMAGES, assert_images_carry_the_references_bits, check_backward
 from test_hip_random_sweep import assert_full_images_carry_the_references_bits
-from test_oracle_autograd import CAMERA_CASES, camera_case_id, camera_case_scene
 from util import assert_grad_close, mask_flipped_pixels
 
 pytestmark = pytest.mark.gpu
@@ -146,17 +146,10 @@ def test_complete_pose_with_a_transposed_perspec_view():
     grads = (s.gC, s.gD, s.gM, s.gV)
     ref_v, _ = hip_view_grad(s, "light", 3, grads, pose_grad=1)
     tp = s._replace(persp=np.ascontiguousarray(s.persp.T))  # storage = Proj; the tensor passed below is its transposed view
-    g32 = tuple(np.asarray(x, np.float32) for x in grads)
     from dgr_amd import _capi
-    from dgr_amd import light as L
     with _capi.thread_options(pose_grad=1):
         out, _ = hh.hip_forward(s, 3)
-        (R, color, depth, median, var, alpha, radii, geom, binning, img, _, _) = out
-        T, E = hh.T, hh.E
-        g = L._C.rasterize_gaussians_backward(
-            T(s.bg), T(s.means), radii, E(), T(s.scales), T(s.rots), 1.0, E(), T(s.view), T(s.proj), s.tanfovx, s.tanfovy,
-            T(g32[0]), T(g32[1][None]), T(g32[2][None]), T(g32[3][None]), T(s.gt), T(s.shs), 3, T(s.campos), geom, R, binning,
-            img, alpha, False, T(tp.persp).t(), False, False)
+        g = hh.hip_backward_raw(s, 3, out, grads=grads, persp=hh.T(tp.persp).t())
     got = torch.sum(g[8], dim=0).cpu().numpy().astype(np.float64).reshape(-1)
     assert np.abs(got - ref_v).max() <= 2e-6 * np.abs(ref_v).max()
 
@@ -164,7 +157,7 @@ def test_complete_pose_with_a_transposed_perspec_view():
 # ------------------------------------------------------------------------------------------ absgrad
 @pytest.mark.parametrize("case", [CAMERA_CASES[1], CAMERA_CASES[2]], ids=camera_case_id)
 def test_absgrad_at_camera(oracle, case):
-    from test_hip_absgrad import absgrad_of_pairs, check_against, light_backward_abs, torch_light
+    from test_hip_absgrad import check_against
     s, deg, _ = camera_case_scene(case)
     W, H, P = s.W, s.H, s.P
     grads = [np.asarray(g, np.float64) * (W * H) ** 0.5 for g in (s.gC, s.gD, s.gM, s.gV)]
@@ -172,12 +165,12 @@ def test_absgrad_at_camera(oracle, case):
                                    s.tanfovx, s.tanfovy, H, W, s.shs, deg, s.campos)
     pairs = []
     loss, leaves, img = torch_light(s, deg, ref["radii"] > 0, st.get("point_list"), st.get("ranges"), st.get("n_contrib"),
-                                    grads, pairs)
+                                    grads, pairs=pairs)
     loss.backward()
     want = absgrad_of_pairs(pairs, img["_idx"], P, W, H)
     out, d = hh.hip_forward(s, deg)
     assert np.array_equal(d["radii"], ref["radii"])
-    g = light_backward_abs(s, deg, out, grads, False)
+    g = hh.hip_backward_raw(s, deg, out, grads=grads, absgrad=True)
     check_against(g[9].cpu().numpy(), want, d["radii"], f"camera {camera_case_id(case)}")
 
 

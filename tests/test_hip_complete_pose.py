@@ -1,5 +1,5 @@
 """The complete pose gradient on the GPU (option "pose_grad" = 1, include/dgr_hip.h): against the float64 formulation of
-tests/test_complete_pose_fp64.py, the translation identity at size, tracking (map_off) against mapping, the default mode
+tests/fp64_model.py (complete_forward), the translation identity at size, tracking (map_off) against mapping, the default mode
 untouched, deterministic sums, the batched entry points and the options snapshot of a forward."""
 import numpy as np
 import pytest
@@ -9,8 +9,8 @@ import hip_helpers as hh
 from dgr_amd import _capi
 from dgr_amd import light as L
 from dgr_amd.synth import heavy_tail_scene
-from test_complete_pose_fp64 import complete_grad, oracle_run, scaled_grads
-from test_oracle_autograd import CASES
+from fp64_model import CASES, complete_grad, oracle_run, scaled_grads
+from hip_helpers import binding  # noqa: F401  (fixture)
 from util import make_scene
 
 pytestmark = pytest.mark.gpu
@@ -153,15 +153,6 @@ def test_deterministic_complete_pose_repeats_bit_for_bit():
         b = _render_views_pose(ss, "light", False, batch=True)
     for x, y in zip(a, b):
         assert np.array_equal(x, y)
-
-
-@pytest.fixture(params=["compiled", "ctypes"])
-def binding(request, monkeypatch):
-    if request.param == "ctypes":
-        monkeypatch.setattr(L, "_C", L._CtypesC)
-    elif L._C is not L._CompiledC:
-        pytest.skip("compiled extension not built")
-    return request.param
 
 
 def test_backward_follows_its_forwards_pose_grad(binding):

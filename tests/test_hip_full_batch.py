@@ -19,25 +19,20 @@ import torch
 
 from util import assert_grad_close, make_scene
 import hip_helpers as hh
+from hip_helpers import binding  # noqa: F401  (fixture)
 from dgr_amd import _capi
 from dgr_amd import batch_full as BF
-from dgr_amd import full as F
 from dgr_amd import light as L
 
 pytestmark = pytest.mark.gpu
 T, E = hh.T, hh.E
 
 
-@pytest.fixture(autouse=True, params=["compiled", "ctypes"])
-def binding(request, monkeypatch):
+@pytest.fixture(autouse=True)
+def batch_binding(binding):
     """every test runs over the compiled torch extension (csrc/torch_ext.cpp: full_forward_batch / full_backward_batch) and
     over the ctypes binding of the same C ABI"""
-    if request.param == "ctypes":
-        monkeypatch.setattr(L, "_C", L._CtypesC)
-        monkeypatch.setattr(F, "_C", F._CtypesC)
-    elif L._C is not L._CompiledC:
-        pytest.skip("compiled extension not built")
-    assert (BF._ext() is not None) == (request.param == "compiled")
+    assert (BF._ext() is not None) == (binding == "compiled")
 
 
 def close(a, b, tol=1e-5):

@@ -1,6 +1,6 @@
 """The exact silhouette gradient on the GPU (option "silhouette_grad", include/dgr_hip.h: dgr_*_backward*_silhouette).
 
-The float64 reference is tests/test_complete_pose_fp64.complete_forward: the silhouette A = sum alpha T = 1 - T_final, and the
+The float64 reference is tests/fp64_model.complete_forward: the silhouette A = sum alpha T = 1 - T_final, and the
 forward's colour carries T_final through its background term, so a loss sum g_A A is (up to a constant) the colour loss
 -sum g_A T_final of a second call with zero colours, background (1, 0, 0) and colour gradient (-g_A, 0, 0) -- same decisions,
 same leaves.  Its gradients are added to those of the first call's loss.  Without the feature the HIP gradients of a silhouette
@@ -17,8 +17,8 @@ import hip_helpers as hh
 from dgr_amd import _capi
 from dgr_amd import full as F
 from dgr_amd import light as L
-from test_complete_pose_fp64 import complete_forward, oracle_run
-from test_hip_absgrad import C0, absgrad_of_pairs, torch_full, torch_light
+from fp64_model import C0, absgrad_of_pairs, complete_forward, oracle_run, torch_full, torch_light
+from hip_helpers import binding  # noqa: F401  (fixture)
 from util import make_scene
 
 pytestmark = pytest.mark.gpu
@@ -26,17 +26,6 @@ pytestmark = pytest.mark.gpu
 T, E = hh.T, hh.E
 CASES = [(400, 64, 48, 3, 11), (300, 40, 40, 0, 12), (500, 70, 45, 2, 13)]
 PER_GAUSSIAN = {"opacities": 2, "means3D": 3, "shs": 5, "scales": 6, "rotations": 7}  # leaf -> index in the backward's tuple
-
-
-@pytest.fixture(params=["compiled", "ctypes"])
-def binding(request, monkeypatch):
-    """the compiled extension's functions and nodes, or the ctypes `_C` classes and Python Functions (the batch classes follow)"""
-    if request.param == "ctypes":
-        monkeypatch.setattr(L, "_C", L._CtypesC)
-        monkeypatch.setattr(F, "_C", F._CtypesC)
-    elif L._C is not L._CompiledC:
-        pytest.skip("compiled extension not built")
-    return request.param
 
 
 def sil_image(s, seed=3):
@@ -68,32 +57,17 @@ def fp64_grads(s, variant, deg, st, ref, grads, gA, added):
     return out
 
 
-def hip_light(s, deg, out, grads, gA=None, bg=None, map_off=False, absgrad=False):
-    (R, color, depth, median, var, alpha, radii, geom, binning, img, _, _) = out
-    gC, gD, gM, gV = (None if g is None else np.asarray(g, np.float32) for g in grads)
-    kw = {} if gA is None else dict(silhouette=T(np.asarray(gA, np.float32)[None]))
-    if absgrad:
-        kw["absgrad"] = True
-    g = L._C.rasterize_gaussians_backward(
-        T(s.bg if bg is None else bg), T(s.means), radii, E(), T(s.scales), T(s.rots), 1.0, E(), T(s.view), T(s.proj),
-        s.tanfovx, s.tanfovy, T(gC), T(gD[None]), E() if gM is None else T(gM[None]), E() if gV is None else T(gV[None]),
-        T(s.gt), T(s.shs), deg, T(s.campos), geom, R, binning, img, alpha, False, T(s.persp), False, map_off, **kw)
+def _host(g):
     torch.cuda.synchronize()
     return [None if x is None else x.detach().cpu().numpy().astype(np.float64) for x in g]
 
 
-def hip_full(s, deg, out, grads, gA=None, bg=None, absgrad=False):
-    (R, NG, color, depth, unc, radii, geom, binning, img) = out
-    gC, gD, gU = (None if g is None else np.asarray(g, np.float32) for g in grads)
-    kw = {} if gA is None else dict(silhouette=T(np.asarray(gA, np.float32)[None]))
-    if absgrad:
-        kw["absgrad"] = True
-    g = F._C.rasterize_gaussians_backward(
-        T(s.bg if bg is None else bg), T(s.means), radii, E(), T(s.scales), T(s.rots), 1.0, E(), T(s.view), T(s.gt), T(s.proj),
-        s.tanfovx, s.tanfovy, T(gC), T(gD[None]), E() if gU is None else T(gU[None]), T(s.shs), deg, T(s.campos), geom, R,
-        binning, img, NG, T(s.persp), **kw)
-    torch.cuda.synchronize()
-    return [None if x is None else x.detach().cpu().numpy().astype(np.float64) for x in g]
+def hip_light(s, deg, out, grads, gA=None, **kw):
+    return _host(hh.hip_backward_raw(s, deg, out, grads=grads, silhouette=gA, **kw))
+
+
+def hip_full(s, deg, out, grads, gA=None, **kw):
+    return _host(hh.hip_full_backward_raw(s, deg, out, grads=grads, silhouette=gA, **kw))
 
 
 def check(got, want, what, tol=5e-5):
@@ -394,20 +368,20 @@ def test_tracking_step_replayed_from_a_graph_equals_eager(monkeypatch):
 
 def fp64_absgrad(s, variant, deg, st, ref, grads, gA):
     """float64 sum_p |v_p(g)| of sum <grads, images> + sum gA * silhouette: the per-(Gaussian, pixel) leaves of the two calls of
-    fp64_grads (test_hip_absgrad's forwards), added per pixel before the absolute value"""
+    fp64_grads (torch_light / torch_full in pairs mode), added per pixel before the absolute value"""
     dec = (ref["radii"] > 0, st.get("point_list"), st.get("ranges"), st.get("n_contrib"))
     zero = np.zeros((s.H, s.W))
     gC = np.stack([-np.asarray(gA, np.float64), zero, zero])
     s2 = s._replace(bg=np.array([1.0, 0.0, 0.0], np.float32))
     p1, p2 = [], []
     if variant == "light":
-        torch_light(s, deg, *dec, grads, p1)[0].backward()
-        torch_light(s2, deg, *dec, (gC, zero, zero, zero), p2, colors_precomp=np.zeros((s.P, 3), np.float32))[0].backward()
+        torch_light(s, deg, *dec, grads, pairs=p1)[0].backward()
+        torch_light(s2, deg, *dec, (gC, zero, zero, zero), pairs=p2, colors_precomp=np.zeros((s.P, 3), np.float32))[0].backward()
     else:  # (no colour input: SH whose colour is 0, C0 sh_0 + 1/2 = 0)
-        torch_full(s, deg, *dec, grads, p1)[0].backward()
+        torch_full(s, deg, *dec, grads, pairs=p1)[0].backward()
         sh0 = np.zeros_like(np.asarray(s.shs, np.float64))
         sh0[:, 0, :] = -0.5 / C0
-        torch_full(s2._replace(shs=sh0), deg, *dec, (gC, zero, zero), p2)[0].backward()
+        torch_full(s2._replace(shs=sh0), deg, *dec, (gC, zero, zero), pairs=p2)[0].backward()
     assert len(p1) == len(p2)
     merged = []
     for (ids, a), (ids2, b) in zip(p1, p2):

@@ -4,7 +4,7 @@
   python tests/tools/arbitrate_fp64.py <seed> <light draw index> [...more indices]
 
 Re-creates light draws of tests/tools/soak_parity.py (same random stream), runs the HIP forward + backward and the oracle, then
-the float64 autograd formulation of tests/test_oracle_autograd.py (written from SURVEY.md's formulas, not from the oracle) on
+the float64 autograd formulation of tests/fp64_model.py (written from SURVEY.md's formulas, not from the oracle) on
 the oracle's integer path, and prints per gradient tensor  max |HIP - f64|, max |oracle - f64|, max |HIP - oracle|  over the
 tensor's scale -- overall and on the row where HIP and oracle differ most.  The scale modifier is folded into the scales
 (exact for 8.0; the reference's dL_dscales is the derivative by the MODIFIED scale, so nothing is scaled back).  Draws with precomputed colours /
@@ -19,7 +19,7 @@ import numpy as np  # noqa: E402
 import hip_helpers as hh  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from soak_draws import Draws  # noqa: E402
-from test_oracle_autograd import torch_light  # noqa: E402
+from fp64_model import torch_light  # noqa: E402
 
 O.build()
 O.use_cmath(False)
