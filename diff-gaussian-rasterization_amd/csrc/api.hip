@@ -187,6 +187,7 @@ int forward_blend(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img
         blend_fwd_common(r, c, geom, img, bin, armed);
         r.gt_depth = c.gt_depth; r.out_median = c.out_median_depth; r.out_alpha = c.out_alpha; r.out_depth_var = c.out_depth_var;
         r.gau_uncertainty = c.gau_uncertainty; r.gau_related_pixels = c.gau_related_pixels;
+        r.live_counts = img.tile_count;  // (dead since the binning: the blend's live counts, render_common.h)
         HIP_TRY(dgr::launch_render_fwd_light(r, opt_alpha_mode(), st));
     }
     if (armed) armed->handed_over = true;  // (workgroup 0 of the blend delivers the word)
@@ -559,7 +560,7 @@ int blend_bwd_light(const BwdView& w, const dgr::PreprocessBwdArgs& b, const flo
     dgr::RenderBwdLightArgs r{};
     blend_bwd_common(r, w, bg, b.W, b.H, s, det);
     r.alphas = w.alphas; r.dL_dpix = w.dL_dpix; r.dL_dpix_depth = w.dL_dpix_depth; r.dL_dpix_median = w.dL_dpix_median_depth;
-    r.dL_dpix_var = w.dL_dpix_depth_var; r.dL_dpix_silhouette = w.dL_dpix_silhouette;
+    r.dL_dpix_var = w.dL_dpix_depth_var; r.dL_dpix_silhouette = w.dL_dpix_silhouette; r.live_counts = s.img.tile_count;
     // (complete pose gradient: the tracking blend's three sums are not enough -- the mapping blend backward forms all of them)
     r.means3D = b.means3D; r.view = w.viewmatrix; r.track_off = b.track_off; r.map_off = complete ? 0 : b.map_off;
     ScopedStage t(ST_RENDER_BWD, st);

@@ -90,7 +90,9 @@ struct ImageView {
                           //     [3] = the frame's blend flags: bit 0: tile_sched holds this frame's schedule (0: the blend kernels use the
                           //           static band map); bit 1: the binning buffer overflowed; bit 2: the light blend kernels walk
                           //           quadrant lists rather than half-wave lists (BLEND_* below: what the host asks the binning for)
-    uint32_t* tile_count; // [tiles * DGR_COUNT_STRIDE] instances per tile (histogram filled by count_rank), one per line
+    uint32_t* tile_count; // [tiles * DGR_COUNT_STRIDE] instances per tile (histogram filled by count_rank), one per line; dead once
+                          //     scan_tiles has run (the segment binning never uses them): the light forward's blend then keeps the
+                          //     tiles' LIVE counts in the first `tiles` words (render_common.h: live_list) -- part of a view's state
     uint2* ranges;        // [tiles] {start, end} into point_list
     uint4* tile_sched;    // [tiles] the blend kernels' schedule: workgroup b works on tile .x, whose list is [.y, .z) --
                           //     classes of long lists first, neighbours on one XCD (tile_schedule_kernel, binning.hip)
@@ -160,7 +162,10 @@ struct BinningView {
     uint64_t* keys;        // [cap] (depth bits << 32 | gaussian id), grouped by tile, unsorted (sort_tiles reads them)
     uint32_t* ranks;       // [cap] Gaussian-major: arrival rank of each instance within its tile (count_rank -> emit)
     // segment binning (segment_binning.hip): one PAIR per (Gaussian, tile row, 16-tile segment) it touches
-    uint64_t* pair_keys;   // [cap] (depth bits << 32 | gaussian id), grouped by producing workgroup, then by segment
+    uint64_t* pair_keys;   // [cap] (depth bits << 32 | gaussian id), grouped by producing workgroup, then by segment (read for the
+                           //       last time by bin_tiles; the global-counter binning never touches them).  CLOBBERED by the light
+                           //       forward's blend, which writes its compacted LIVE LISTS here for the backward, 8 bytes per
+                           //       blended instance (render_common.h: live_list): part of a view's state
     uint8_t* pair_cov;     // [cap] columns covered inside the segment: first | last << 4  (shares the bytes of `ranks`:
                            //       a forward uses either the global-atomic count or the segment binning).  CLOBBERED by the
                            //       light forward's blend, which keeps its contribution tags per half of a quadrant in these

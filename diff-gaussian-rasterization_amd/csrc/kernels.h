@@ -174,6 +174,7 @@ struct RenderFwdLightArgs {
     float* out_alpha;
     float* out_depth_var;
     uint32_t* n_contrib;
+    uint32_t* live_counts;  // [tiles] live entries of each tile (ImageView::tile_count, the binning's dead counters; the entries: render_common.h, live_list)
     float* gau_uncertainty;
     int* gau_related_pixels;
     StatusReport rep;      // armed status slot (dgr_status_arm): workgroup 0 copies the frame's status word to the host
@@ -191,6 +192,7 @@ struct RenderBwdLightArgs {
     const float* gt_depth;
     const float* alphas;
     const uint32_t* n_contrib;
+    const uint32_t* live_counts;  // [tiles] written by the forward blend (render_common.h: live_list)
     const float* dL_dpix;
     const float* dL_dpix_depth;
     const float* dL_dpix_median;

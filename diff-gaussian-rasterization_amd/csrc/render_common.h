@@ -94,11 +94,12 @@ struct StagedT {
     static constexpr int SLOTS = NB;
     static constexpr int SENTINEL = NB;       // record slot that can never contribute (opacity 0)
     static constexpr int LIST_LD = NB + 8;    // list row: NB entries + sentinel padding, 8-byte aligned rows
+    static constexpr int REC_BYTES = 32;      // a list entry = slot * REC_BYTES, the byte offset of the slot's record in `rec`
     float4 rec[2 * (NB + 1)];  // [2*slot] = {x, y, a2, c2}, [2*slot+1] = {b2, opacity, slot (int bits), lthr}
                                //  p2 = dx*(a2*dx + b2*dy) + c2*dy*dy = log2(e) * power (pair_p2)
     float4 rgbd[NB + 1];       // {r, g, b, depth}; [NB] = zeros (the sentinel's entry: the branch-free backward reads it)
     uint32_t id[KEEP_ID ? NB : 1];
-    LIST_T list[NLISTS][LIST_LD];     // per consumer wave (half-wave): byte offsets (slot * 32) into rec, tile-list order
+    LIST_T list[NLISTS][LIST_LD];     // per consumer wave (half-wave): byte offsets (slot * REC_BYTES) into rec, tile-list order
     int cnt4[4][NLISTS];              // [staging wave][consumer] entries contributed
 };
 using Staged = StagedT<DGR_TILE_PIX>;
@@ -202,7 +203,8 @@ __device__ __forceinline__ uint32_t pack4(uint32_t w) { return (w & 1u) | ((w >>
 // `lo` in the spare third word of the staged record: stage_one<AM, true>).
 __device__ __forceinline__ uint32_t tag_byte(uint32_t up, uint32_t lo) { return spread4(pack4(up)) | (spread4(pack4(lo)) << 1); }
 
-// backward staging: returns the entry's tag (TAGS: where it lives and in which form it is wanted); untagged entries are not loaded.
+// backward staging by list position (the full variant; the light backward stages from its live list: stage_live below): returns the
+// entry's tag (TAGS: where it lives and in which form it is wanted); untagged entries are not loaded.
 template <int AM, int TAGS, class S>
 __device__ __forceinline__ unsigned stage_tagged(S& s, int slot, uint32_t entry, const float4* __restrict__ rec,
                                                  const uint8_t* __restrict__ tag8) {
@@ -221,6 +223,66 @@ __device__ __forceinline__ unsigned stage_tagged(S& s, int slot, uint32_t entry,
     s.rgbd[slot] = make_float4(q2.x, q2.y, q2.z, q0.z);
     s.id[slot] = gid;
     return code;
+}
+
+// ---- live lists (the light variant).  The forward blend knows, when it flushes a staged batch, which of its entries some pixel
+// blended (tag byte != 0).  It writes those -- and only those -- out COMPACTED, in tile-list order: one 8-byte entry
+//   {Gaussian id, position in the tile list << 8 | tag byte}
+// per live instance, the k-th live entry of the tile whose list starts at `start` at index start + k (a tile has no more live
+// entries than entries, so it stays inside its own span), and the tile's live count into the tile's word of live_counts.  The light
+// backward stages from that array and nothing else: a batch is NB live entries, not NB list positions, and a tile nobody
+// blended returns at once.  point_list, ranges, n_contrib and the tag bytes stay what they are.
+// The array lies in the binning buffer's `pair_keys` bytes (8 per instance of capacity, found like the tag bytes from the capacity in
+// cursor[2]) and the counts in the image state's tile counters: both are the binning's scratch, read for the last time by
+// bin_tiles / scan_tiles before the forward blend starts, and (re)initialised by the next forward that uses them.
+// (positions take 24 bits: ONE tile's list must stay below 2^24 entries -- a documented, unchecked limit of the light variant,
+//  include/dgr_hip.h; 16.7 M Gaussians would have to reach the same tile)
+__device__ __forceinline__ uint2* live_list(const uint32_t* point_list, const uint32_t* sched_flag) {
+    return reinterpret_cast<uint2*>(carve_binning(reinterpret_cast<char*>(const_cast<uint32_t*>(point_list)), (size_t)sched_flag[-1]).pair_keys);
+}
+
+// The light backward's staged batch: as StagedT with 32-bit list entries, but a slot's {r, g, b, depth} lies BEHIND its record
+// (48 bytes per slot: the pair loop reads it at the list entry's offset + 32, an immediate, independent of the record read) and the
+// record's last word, free of the rgbd offset, carries the entry's POSITION in the tile list -- what the pair loop compares
+// with the pixel's last contributor.
+template <int NB, int NLISTS = 4>
+struct StagedLiveT {
+    typedef uint32_t list_t;
+    static constexpr bool HAS_ID = true;
+    static constexpr int SLOTS = NB;
+    static constexpr int SENTINEL = NB;
+    static constexpr int LIST_LD = NB + 8;
+    static constexpr int REC_BYTES = 48;
+    float4 rec[3 * (NB + 1)];  // [3*slot] = {x, y, a2, c2}, [3*slot+1] = {b2, opacity, 4 * slot, list position (int bits)}, [3*slot+2] = {r, g, b, depth}
+    uint32_t id[NB];
+    uint32_t list[NLISTS][LIST_LD];
+    int cnt4[4][NLISTS];
+};
+
+// backward staging from a live entry; returns its tag (QUADRANT: folded to four bits).  Never zero: only tagged entries are listed.
+template <int AM, bool QUADRANT, class S>
+__device__ __forceinline__ unsigned stage_live(S& s, int slot, uint2 e, const float4* __restrict__ rec) {
+    constexpr float PSCALE = AlphaPath<AM>::PSCALE;
+    unsigned code = e.y & 0xFFu;
+    if (QUADRANT) code = fold8(code);
+    const uint32_t gid = e.x & ID_MASK;
+    const float4 q0 = rec[DGR_REC_STRIDE * (size_t)gid + 0];
+    const float4 q1 = rec[DGR_REC_STRIDE * (size_t)gid + 1];
+    const float4 q2 = rec[DGR_REC_STRIDE * (size_t)gid + 2];
+    s.rec[3 * slot] = make_float4(q0.x, q0.y, -0.5f * PSCALE * q1.x, -0.5f * PSCALE * q1.z);
+    // (.z: 4 * slot = the byte offset of the slot's accumulator column, which the backward addresses LDS with directly)
+    s.rec[3 * slot + 1] = make_float4(-PSCALE * q1.y, q0.w, __int_as_float(slot * 4), __int_as_float((int)(e.y >> 8)));
+    s.rec[3 * slot + 2] = make_float4(q2.x, q2.y, q2.z, q0.z);
+    s.id[slot] = gid;
+    return code;
+}
+// its sentinel: opacity 0 (alpha 0: never valid), accumulator column NB, an all-zero rgbd
+template <class S>
+__device__ __forceinline__ void write_sentinel_live(S& s) {
+    constexpr int NB = S::SLOTS;
+    s.rec[3 * NB] = make_float4(0.f, 0.f, 0.f, 0.f);
+    s.rec[3 * NB + 1] = make_float4(0.f, 0.f, __int_as_float(NB * 4), __int_as_float(0x7fffffff));
+    s.rec[3 * NB + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 __device__ __forceinline__ int lanes_below(unsigned long long m) {
@@ -244,12 +306,12 @@ __device__ __forceinline__ int build_lists(S& s, unsigned code, int tid, int wav
         if ((code >> w) & 1u) {
             int base = 0;
             for (int sw = 0; sw < wave; sw++) base += s.cnt4[sw][w];
-            s.list[w][base + lanes_below(bal[w])] = (LT)(tid * 32);
+            s.list[w][base + lanes_below(bal[w])] = (LT)(tid * S::REC_BYTES);
         }
     }
     const int n = __builtin_amdgcn_readfirstlane(s.cnt4[0][wave] + s.cnt4[1][wave] + s.cnt4[2][wave] + s.cnt4[3][wave]);
     __syncthreads();
-    if (lane < 4) s.list[wave][n + lane] = (LT)(S::SENTINEL * 32);  // own list, own wave: program order suffices
+    if (lane < 4) s.list[wave][n + lane] = (LT)(S::SENTINEL * S::REC_BYTES);  // own list, own wave: program order suffices
     return n;
 }
 
@@ -281,14 +343,14 @@ __device__ __forceinline__ int build_half_lists(S& s, unsigned code, int tid, in
 #pragma unroll
     for (int l = 0; l < 8; l++) {
         const int base = __builtin_amdgcn_readlane(before, l);
-        if ((code >> l) & 1u) s.list[l][base + lanes_below(bal[l])] = (LT)(tid * 32);
+        if ((code >> l) & 1u) s.list[l][base + lanes_below(bal[l])] = (LT)(tid * S::REC_BYTES);
     }
     const int l0 = 2 * wave;
     const int n0 = __builtin_amdgcn_readlane(all, l0), n1 = __builtin_amdgcn_readlane(all, l0 + 1);
     __syncthreads();
     const int n = max(n0, n1);
-    for (int i = n0 + lane; i < n + 4; i += 64) s.list[l0][i] = (LT)(S::SENTINEL * 32);      // own lists, own wave: program order
-    for (int i = n1 + lane; i < n + 4; i += 64) s.list[l0 + 1][i] = (LT)(S::SENTINEL * 32);
+    for (int i = n0 + lane; i < n + 4; i += 64) s.list[l0][i] = (LT)(S::SENTINEL * S::REC_BYTES);      // own lists, own wave: program order
+    for (int i = n1 + lane; i < n + 4; i += 64) s.list[l0 + 1][i] = (LT)(S::SENTINEL * S::REC_BYTES);
     return n;
 }
 
@@ -298,7 +360,8 @@ __device__ __forceinline__ int build_half_lists(S& s, unsigned code, int tid, in
 // pixel still meets its Gaussians in list order -- and the step's reduction stops before the stage that adds the halves
 // (wave_reduce.h).  Every entry is still delivered exactly once with twelve lane-atomics (half-wave lists, where an entry of both
 // halves is delivered twice, drown in them: DESIGN.md Appendix A).
-//   code8 : stage_tagged<AM, TAGS_BYTES_HALVES>'s code (bit 2 w + h: half h of quadrant wave w)
+//   code8 : the staged entries' tag bytes (bit 2 w + h: half h of quadrant wave w) -- stage_live's code in the light backward,
+//           stage_tagged<AM, TAGS_BYTES_HALVES>'s in the full one
 //   phase 1: the four compacted quadrant lists as in build_lists, entry = record offset | type (1 upper, 2 lower, 3 both);
 //   phase 2: every wave pairs its own list (of at most 64 entries: one rank per lane; longer lists stay unpaired): ranks
 //            (2 m, 2 m + 1) first, then (2 m + 1, 2 m + 2) where neither was taken -- a window of five entries, read through
@@ -329,14 +392,14 @@ __device__ __forceinline__ int build_paired_lists(S& s, unsigned code8, int tid,
     for (int w = 0; w < 4; w++) {
         const unsigned t = (code8 >> (2 * w)) & 3u;
         const int base = __builtin_amdgcn_readlane(before, w);
-        if (t != 0u) s.list[2 * w][base + lanes_below(bal[w])] = (LT)(tid * 32) | t;
+        if (t != 0u) s.list[2 * w][base + lanes_below(bal[w])] = (LT)(tid * S::REC_BYTES) | t;
     }
     const int n = __builtin_amdgcn_readlane(all, wave);
     __syncthreads();
     LT* const LU = s.list[2 * wave];
     LT* const LL = s.list[2 * wave + 1];
     if (n <= 64) {
-        // the usual case (a batch of 128 positions leaves ~22 entries per quadrant): one rank per lane, the window of five types
+        // the usual case (a batch of 128 positions leaves ~22 entries per quadrant, a full batch of 128 live entries about twice that): one rank per lane, the window of five types
         // through whole-wave DPP shifts (a lane without a neighbour reads 0 = no entry)
         const bool have = lane < n;
         const unsigned e0 = have ? LU[lane] : 0u;
@@ -363,20 +426,23 @@ __device__ __forceinline__ int build_paired_lists(S& s, unsigned code8, int tid,
             }
         }
         if (lane < 4) {
-            LU[steps + lane] = (LT)(S::SENTINEL * 32);
-            LL[steps + lane] = (LT)(S::SENTINEL * 32);
+            LU[steps + lane] = (LT)(S::SENTINEL * S::REC_BYTES);
+            LL[steps + lane] = (LT)(S::SENTINEL * S::REC_BYTES);
         }
         split[0] = __ballot(lane < steps && LU[lane] != LL[lane]);
         split[1] = 0ull;
         return steps;
     }
-    // more than 64 entries in one quadrant's list of a 128-position batch (big splats, which live in both halves anyway): unpaired
+    // more than 64 entries in one quadrant's list of the batch: unpaired.  In the full variant's batches of 128 POSITIONS that means big
+    // splats, which live in both halves anyway; in the light backward's batches of 128 LIVE entries it is an ordinary dense tile's
+    // full batch -- measured at 500 k Gaussians, 1080p: 42 of synth-v1's 32 740 (quadrant, batch) lists (0.2 % of the entries), 519 of
+    // the clustered scene's 45 756 (2.6 % of the entries; with batches of equal size 183: profiles/live_lists/notes.md)
     const LT ea = lane < n ? LU[lane] : 0u, eb = lane + 64 < n ? LU[lane + 64] : 0u;
     if (lane < n) { LU[lane] = ea & ~3u; LL[lane] = ea & ~3u; }
     if (lane + 64 < n) { LU[lane + 64] = eb & ~3u; LL[lane + 64] = eb & ~3u; }
     if (lane < 4) {
-        LU[n + lane] = (LT)(S::SENTINEL * 32);
-        LL[n + lane] = (LT)(S::SENTINEL * 32);
+        LU[n + lane] = (LT)(S::SENTINEL * S::REC_BYTES);
+        LL[n + lane] = (LT)(S::SENTINEL * S::REC_BYTES);
     }
     split[0] = split[1] = 0ull;
     return n;

@@ -12,7 +12,8 @@
 //    ellipse q(d) <= 2 ln(255 o / 15), boxed with a safety margin) and tests it against the eight
 //    HALVES of the four quadrants (8x4 pixels = lanes 0-31 / 32-63 of the consumer wave).  Wave ballots +
 //    mbcnt turn those tests into eight COMPACTED lists of 16-bit record offsets, one per half-wave, in
-//    tile-list order (the backward: four lists, one per wave, from the forward's contribution tags);
+//    tile-list order (the backward: four lists, one per wave, from the forward's contribution tags, which reach it with the
+//    forward's compacted list of the entries it blended -- render_common.h: live_list -- the only entries the backward stages);
 //  * each wave walks its two lists side by side, two entries per iteration: one 4-byte LDS read per lane
 //    yields two offsets, ds_read_b128 with one address per half-wave fetch the records (the same four
 //    LDS cycles as a broadcast), then pure VALU per pixel.  A splat reaches 16 of a quadrant's 64
@@ -50,29 +51,43 @@ struct StagedFwd {
     float unc[DGR_TILE_PIX];   // per staged instance: sum of (d - gt)^2 alpha T over its median pixels (forward.cu:386)
     uint32_t cnt[DGR_TILE_PIX];
     uint32_t hit[DGR_TILE_PIX];  // byte w of word j != 0 <=> some pixel of quadrant wave w blended staged instance j
+    alignas(16) uint32_t live4[4];  // flush_slot: live entries of the flushed batch per staging wave
     uint64_t exptab[32];         // ALPHA_GLIBC: exact_math.h
 };
 
-// Per-slot results of the batch staged at list position `pos0`: the median statistics go to the Gaussian, the
-// contribution tag into the entry's tag byte (render_common.h).
-
+// Per-slot results of the batch staged at position `pos0` of the tile list that starts at `list0`: the median statistics go to the
+// Gaussian, the contribution tag into the entry's tag byte (render_common.h), and the entries somebody blended -- tag != 0 -- go,
+// compacted in list order, to the tile's live list from `live_base` on (render_common.h: live_list): a ballot and mbcnt per
+// wave, the four waves' counts through LDS.  Every thread of the workgroup calls it (one barrier); returns the new live_base.
 template <class SF>
-__device__ __forceinline__ void flush_slot(const SF& sf, const RenderFwdLightArgs& a, uint8_t* tag8, uint32_t pos0, int tid, bool staged) {
-    if (!staged) return;
-    uint32_t t8;  // bit 2 w <- upper half of wave w, bit 2 w + 1 <- its lower half
-    if constexpr (!SF::staged_t::HAS_ID) {  // (the half-wave body) lower halves: the bytes of the record's third word
-        t8 = tag_byte(sf.hit[tid], __float_as_uint(sf.f.rec[2 * tid + 1].z));
-    } else {                                // (the quadrant body) a quadrant's tag stands for both of its halves
-        t8 = spread4(pack4(sf.hit[tid])) * 3u;
+__device__ __forceinline__ uint32_t flush_slot(SF& sf, const RenderFwdLightArgs& a, uint8_t* tag8, uint2* live, uint32_t list0, uint32_t pos0,
+                                               uint32_t live_base, int tid, bool staged) {
+    uint32_t t8 = 0u;  // bit 2 w <- upper half of wave w, bit 2 w + 1 <- its lower half
+    if (staged) {
+        if constexpr (!SF::staged_t::HAS_ID) {  // (the half-wave body) lower halves: the bytes of the record's third word
+            t8 = tag_byte(sf.hit[tid], __float_as_uint(sf.f.rec[2 * tid + 1].z));
+        } else {                                // (the quadrant body) a quadrant's tag stands for both of its halves
+            t8 = spread4(pack4(sf.hit[tid])) * 3u;
+        }
+        tag8[list0 + pos0 + tid] = (uint8_t)t8;  // every staged entry, blended or not: the byte underneath is the binning's
     }
-    tag8[pos0 + tid] = (uint8_t)t8;         // every staged entry, blended or not: the byte underneath is the binning's
-    if (sf.cnt[tid] != 0u) {                // (which implies a tag)
+    const unsigned long long bal = __ballot(t8 != 0u);
+    if ((tid & 63) == 0) sf.live4[tid >> 6] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    const uint4 c = *reinterpret_cast<const uint4*>(sf.live4);
+    if (t8 != 0u) {
+        const int wave = tid >> 6;
+        const uint32_t before = (wave > 0 ? c.x : 0u) + (wave > 1 ? c.y : 0u) + (wave > 2 ? c.z : 0u);
         uint32_t gid;
         if constexpr (SF::staged_t::HAS_ID) gid = sf.f.id[tid];
-        else gid = a.point_list[pos0 + tid];
-        atomicAdd(&a.gau_uncertainty[gid], sf.unc[tid]);
-        atomicAdd(&a.gau_related_pixels[gid], (int)sf.cnt[tid]);
+        else gid = a.point_list[list0 + pos0 + tid];
+        live[list0 + live_base + before + (uint32_t)lanes_below(bal)] = make_uint2(gid, ((pos0 + (uint32_t)tid) << 8) | t8);
+        if (sf.cnt[tid] != 0u) {                // (a median pixel blended it: it has a tag)
+            atomicAdd(&a.gau_uncertainty[gid], sf.unc[tid]);
+            atomicAdd(&a.gau_related_pixels[gid], (int)sf.cnt[tid]);
+        }
     }
+    return live_base + (uint32_t)__builtin_amdgcn_readfirstlane((int)(c.x + c.y + c.z + c.w));
 }
 
 template <int AM, bool HALVES>
@@ -90,6 +105,8 @@ __device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& 
     const int my_list = HALVES ? 2 * wave + (lane >> 5) : wave;
     // where this lane marks "blended": byte `wave` of hit[j] -- HALVES: lanes 32-63 in byte `wave` of the record's spare word
     uint8_t* const tag8 = half_tags(a.point_list, a.sched_flag);
+    uint2* const live = live_list(a.point_list, a.sched_flag);
+    uint32_t live_base = 0;  // live entries of this tile written so far (workgroup-uniform)
     unsigned char* const mark_base = (HALVES && lane >= 32) ? reinterpret_cast<unsigned char*>(&s.rec[1].z) + wave
                                                              : reinterpret_cast<unsigned char*>(sf.hit) + wave;
     const int mark_stride = (HALVES && lane >= 32) ? 32 : 4;
@@ -113,7 +130,7 @@ __device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& 
         if (__syncthreads_and(ub < 0.f)) break;
         last_base = base;
         // median statistics of the previous batch: slot tid is flushed by the thread that restages it
-        if (have_flush) flush_slot(sf, a, tag8, range.x + base - DGR_TILE_PIX, tid, true);  // (an earlier batch is always full)
+        if (have_flush) live_base = flush_slot(sf, a, tag8, live, range.x, (uint32_t)(base - DGR_TILE_PIX), live_base, tid, true);  // (an earlier batch is always full)
         sf.unc[tid] = 0.f;
         sf.cnt[tid] = 0u;
         sf.hit[tid] = 0u;
@@ -161,7 +178,9 @@ __device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& 
         }
     }
     __syncthreads();
-    if (have_flush) flush_slot(sf, a, tag8, range.x + last_base, tid, tid < total - last_base);
+    if (have_flush) live_base = flush_slot(sf, a, tag8, live, range.x, (uint32_t)last_base, live_base, tid, tid < total - last_base);
+    // (an empty tile, the empty lists of an overflowed frame, a tile that finished early: what was flushed, 0 if nothing was)
+    if (tid == 0) a.live_counts[tile] = live_base;
     // the tail of a list whose tile finished early was never staged: nobody blended it (render_common.h: the tag bytes' invariant)
     for (int p = (have_flush ? last_base + DGR_TILE_PIX : 0) + tid; p < total; p += DGR_TILE_PIX) tag8[range.x + p] = 0;
 
@@ -216,8 +235,10 @@ __global__ void __launch_bounds__(256, 8) render_fwd_light_kernel(RenderFwdLight
 // list that live in different halves into one loop step (build_paired_lists) -- see the HALVES note above the kernel.
 constexpr int NACC_LIGHT = 14;
 
-// list positions staged per batch (256: 5 workgroups per CU, 267 us; 128: 247 us).  The deterministic kernel (DET, below) keeps one
-// accumulator plane per quadrant wave -- four times the accumulators -- and stages 64 positions per batch to stay at 8 workgroups
+// LIVE entries staged per batch -- the entries the forward blended, read from its compacted live list (render_common.h: live_list;
+// until then a batch was 128 list POSITIONS, dead ones included: each cost a tag read, a list read and its share of the batch's
+// barriers, accumulator clears and flush).  (256: 5 workgroups per CU, 267 us; 128: 247 us.)  The deterministic kernel (DET, below) keeps one
+// accumulator plane per quadrant wave -- four times the accumulators -- and stages 64 entries per batch to stay at 8 workgroups
 // per CU.
 // ABS (absgrad, render_bwd_light_abs_kernel): two more accumulator rows, components 14 and 15, behind the plane.
 template <bool DET, bool HALVES = false, bool ABS = false>
@@ -226,11 +247,10 @@ struct StagedBwd {
     static constexpr int LD = NB + 1;          // accumulator row length
     static constexpr int PLANE = NACC_LIGHT * LD;
     static constexpr int NACC = ABS ? NACC_LIGHT + 2 : NACC_LIGHT;  // rows cleared per batch
-    typedef StagedT<NB, uint32_t, HALVES ? 8 : 4> staged_t;
+    typedef StagedLiveT<NB, HALVES ? 8 : 4> staged_t;  // (render_common.h: a batch is NB LIVE entries)
     staged_t f;
     float acc[(DET ? 4 : 1) * PLANE + (ABS ? 2 * LD : 0)];
     uint32_t inst[DET ? NB : 1];               // DET: the staged entries' rows in the instance-major gradient buffer (~0u: none)
-    int max_last;
     uint64_t exptab[32];  // ALPHA_GLIBC: exact_math.h
 };
 
@@ -290,24 +310,15 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
     const float pxf = (float)px, pyf = (float)py;
     const f2 pxy = {pxf, pyf};
 
-    const uint2 range = make_uint2(slot.y, slot.z);
+    // The tile's LIVE entries -- the ones the forward blended for some pixel, compacted in list order (render_common.h: live_list) --
+    // are all this kernel walks: none lies past the tile's last contributor, and a tile nobody blended is done here.
+    const int total = __builtin_amdgcn_readfirstlane((int)a.live_counts[tile]);
+    if (total <= 0) return;
+    const uint2* const live = live_list(a.point_list, a.sched_flag) + slot.y;
     const int last_contributor = inside ? (int)a.n_contrib[pix_id] : 0;
 
-    if (tid == 0) {
-        sb.max_last = 0;
-        write_sentinel<true>(s);
-    }
-    if (AlphaPath<AM>::TABLE) exp_ref_table_fill(sb.exptab, tid);
-    __syncthreads();
-    {
-        int v = last_contributor;  // wave max, then one LDS atomic per wave
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-        if (lane == 0) atomicMax(&sb.max_last, v);
-    }
-    __syncthreads();
-    const int total = min((int)(range.y - range.x), sb.max_last);  // nothing past the last contributor matters
-    if (total <= 0) return;
+    if (tid == 0) write_sentinel_live(s);
+    if (AlphaPath<AM>::TABLE) exp_ref_table_fill(sb.exptab, tid);  // (visible after the first batch's barriers)
 
     const float T_final = inside ? (1.0f - a.alphas[pix_id]) : 0.f;
     float T = T_final;
@@ -350,18 +361,17 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         my_comp = ((lane & 15) == 0 && c < 3) ? (c == 0 ? 4 : c == 1 ? 5 : 13) : -1;
     }
     const int my_list = HALVES ? 2 * wave + (lane >> 5) : wave;
-    const uint8_t* const tag8 = half_tags(a.point_list, a.sched_flag);
 
     // this lane's accumulator row (column = slot); DET: in its wave's own plane
     float* const my_acc = sb.acc + (DET ? wave * SB::PLANE : 0) + (my_comp >= 0 ? my_comp : 0) * BWD_LD;
 
-    // back-to-front: batches cover list positions [lo, hi) with hi walking down from `total`
+    // back-to-front: batches cover the live entries [lo, hi) with hi walking down from `total`
     for (int hi = total; hi > 0; hi -= BWD_NB) {
         const int lo = max(0, hi - BWD_NB);
         const int cnt = hi - lo;
         __syncthreads();  // previous batch fully flushed / consumed
         unsigned code = 0;
-        if (tid < cnt) code = stage_tagged<AM, HALVES ? TAGS_BYTES_HALVES : TAGS_BYTES_QUADRANT>(s, tid, a.point_list[range.x + lo + tid], a.rec, tag8 + (range.x + lo + tid));
+        if (tid < cnt) code = stage_live<AM, !HALVES>(s, tid, live[lo + tid], a.rec);
         if (!DET) {  // (DET: a plane's column is written by its wave iff the entry's tag names the wave -- nothing to clear)
 #pragma unroll
             for (int k = 0; k < SB::NACC; k++)
@@ -371,7 +381,6 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         const int n = PAIRED   ? build_paired_lists(s, code, tid, wave, lane, split)
                       : HALVES ? build_half_lists(s, code, tid, wave, lane)
                                : build_lists(s, code, tid, wave, lane);
-        const int rel_last4 = 4 * (last_contributor - lo);  // slots whose 4 * index is below this are at or before the last contributor
 
         // (the list is padded with sentinels to a multiple of 4, so a multiple of 2 is always readable)
         // PAIRED: one step per iteration -- the second step's records in flight cost eight registers that this kernel does not have
@@ -379,12 +388,18 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         constexpr int U = PAIRED ? 1 : 2;
         for (int k = ((n + U - 1) / U) * U - U; k >= 0; k -= U) {
             float4 q0[2], q1[2];
+            unsigned off[2];
             if (U == 2) {
-                load2(s, my_list, k, q0, q1);
+                const uint2 pk = *reinterpret_cast<const uint2*>(&s.list[my_list][k]);
+                off[0] = pk.x;
+                off[1] = pk.y;
             } else {
-                const unsigned off = s.list[my_list][k];
-                q0[0] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s.rec) + off);
-                q1[0] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s.rec) + off + 16);
+                off[0] = off[1] = s.list[my_list][k];
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                q0[u] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s.rec) + off[u]);
+                q1[u] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s.rec) + off[u] + 16);
             }
 #pragma unroll
             for (int u = U - 1; u >= 0; u--) {
@@ -397,7 +412,8 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
                 // (the reference tests min(0.99, o G) >= 15/255; 0.99 is above the threshold, so o G itself decides)
                 // (written as "not below", so that a NaN o G -- a poisoned opacity -- stays a valid pair with alpha 0.99 as under
                 //  the reference's min(0.99f, NaN))
-                const bool valid = (j4 < rel_last4) & (p2 <= 0.0f) & !(oG < ALPHA_MIN);
+                // (the entry's own position in the tile list against the pixel's last contributor)
+                const bool valid = (__float_as_int(q1[u].w) < last_contributor) & (p2 <= 0.0f) & !(oG < ALPHA_MIN);
                 // No branch: a lane the Gaussian does not reach runs the same instructions with alpha = 0 and o G = 0, which
                 // leave its state untouched -- 1/(1 - 0) is exactly 1, so T, and S = 0 X + 1 S, keep their bits -- and
                 // make every one of its contributions 0.  (The list's sentinel entries have opacity 0 and an all-zero
@@ -405,7 +421,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
                 // the clamp of 0 is 0): a select and a compare issue at 4.2 cycles each, a multiply at 2.4.
                 const float oGm = valid ? oG : 0.f;
                 const float alpha = fminf(0.99f, oGm);
-                const float4 cd = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s.rgbd) + __float_as_int(q1[u].w));
+                const float4 cd = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(s.rec) + off[u] + 32);  // {r, g, b, depth} behind the record
                 const float om = 1.f - alpha;
                 float inv;
                 T = t_div<AM>(T, om, inv);  // backward.cu:570
@@ -519,7 +535,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         //   dL/dmean2D = -(a Sx + b Sy) W/2, -(c Sy + b Sx) H/2;  dL/dconic = -Sxx/2, -Sxy/2, -Syy/2;  dL/dopacity = S0/o
         if (code != 0u) {
             constexpr float UN = AlphaPath<AM>::PUNSCALE;  // (undoes the scale of the staged conic)
-            const float4 r0 = s.rec[2 * tid], r1 = s.rec[2 * tid + 1];
+            const float4 r0 = s.rec[3 * tid], r1 = s.rec[3 * tid + 1];
             const float ca = r0.z * (-2.f * UN), cb = r1.x * (-UN), cc = r0.w * (-2.f * UN);  // unscaled conic
             const float Sx = sb.acc[4 * BWD_LD + tid], Sy = sb.acc[5 * BWD_LD + tid];
             sb.acc[4 * BWD_LD + tid] = -(ca * Sx + cb * Sy) * ddelx_dx;

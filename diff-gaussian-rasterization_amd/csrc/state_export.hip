@@ -110,6 +110,10 @@ long dgr_state_export(void* stream, const char* name, int P, int width, int heig
         if (hipGetLastError() != hipSuccess) return -1;
         return num_rendered;
     }
+    // the light forward's live lists (render_common.h: live_list): per instance slot {Gaussian id, list position << 8 | tag byte}, of
+    // which the first live_counts[tile] from the tile's range start on are written; and the per-tile counts
+    if (n == "live_list") return copy(bin.pair_keys, 8 * (size_t)num_rendered) ? -1 : 2L * num_rendered;
+    if (n == "live_counts") return copy(img.tile_count, 4 * tiles) ? -1 : (long)tiles;
     if (n == "ranges") return copy(img.ranges, 8 * tiles) ? -1 : (long)(2 * tiles);
     if (n == "tile_sched") return copy(img.tile_sched, 16 * tiles) ? -1 : (long)(4 * tiles);
     if (n == "sched_flag") return copy(img.cursor + 3, 4) ? -1 : 1L;  // 1: this frame's blend kernels walk tile_sched, 0: the static band map

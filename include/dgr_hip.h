@@ -183,7 +183,12 @@ int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* bac
 /* Copies one named array of a state buffer to `dst` (device or host pointer).  Names: "depths", "radii",
  * "means2D", "conic_opacity", "rgb", "clamped", "tiles_touched" (geometry); "point_list", "keys" (binning); "contribution_tags"
  * (one byte per list entry, bit w = some pixel of quadrant w of the tile blended it: the forward blend's tag bytes folded),
- * "half_tags" (those bytes as they are: bit 2 w + h = half h of quadrant w);
+ * "half_tags" (those bytes as they are: bit 2 w + h = half h of quadrant w); "live_list" (light variant: two words per instance
+ * slot, {Gaussian id, list position << 8 | tag byte} -- the entries the forward blended, compacted per tile from the tile's range
+ * start on) with "live_counts" (image: one word per tile, how many of them the tile has).  LIMIT (light variant): a live entry
+ * keeps its list position in 24 bits, so ONE tile's list must stay below 2^24 = 16 777 216 entries (16.7 M Gaussians reaching
+ * the same 16x16 tile; config 5's whole frame has 16.4 M instances over 32 400 tiles).  It is not checked: beyond it the
+ * light backward's gradients for that tile are wrong;
  * "ranges", "tile_sched", "sched_flag" (one word, the frame's blend flags: bit 0 = its blend kernels use the schedule, bit 1 = the
  * binning buffer overflowed, bit 2 = quadrant lane lists: option "lane_lists"), "n_contrib", "n_valid",
  * "final_T" (image; the last two: full variant).  Layout conversion to the reference's element types is done on the fly.
