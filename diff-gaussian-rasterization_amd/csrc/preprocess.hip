@@ -1058,6 +1058,26 @@ __device__ __forceinline__ void pose_block_reduce_det(const float (&pose)[12], d
     pose_finish_det(det_pose, ticket, dL_dview, lane_sum, clear);
 }
 
+// The blend kernel's accumulator row of one Gaussian, as the one-view and the batched backward use it: zero when the view culled
+// the Gaussian.  (The four 16-byte loads stay with the caller, which requests every input up front.)
+__device__ __forceinline__ void unpack_acc_row(float4 a0, float4 a1, float4 a2, float4 a3, bool vis, float (&acc)[16]) {
+    if (vis) {
+        acc[0] = a0.x; acc[1] = a0.y; acc[2] = a0.z; acc[3] = a0.w; acc[4] = a1.x; acc[5] = a1.y; acc[6] = a1.z; acc[7] = a1.w;
+        acc[8] = a2.x; acc[9] = a2.y; acc[10] = a2.z; acc[11] = a2.w; acc[12] = a3.x; acc[13] = a3.y; acc[14] = a3.z; acc[15] = a3.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; i++) acc[i] = 0.0f;
+    }
+}
+// dL_dmean2D (nullable, per view): a plain copy of the blend kernel's sums, zero under map_off (preprocess_bwd_kernel has the reason)
+__device__ __forceinline__ void write_dmean2D(const PreprocessBwdArgs& a, int idx, const float (&acc)[16]) {
+    if (a.dL_dmean2D) {
+        a.dL_dmean2D[3 * (size_t)idx + 0] = a.map_off ? 0.0f : acc[4];
+        a.dL_dmean2D[3 * (size_t)idx + 1] = a.map_off ? 0.0f : acc[5];
+        a.dL_dmean2D[3 * (size_t)idx + 2] = 0.0f;
+    }
+}
+
 // Fused per-Gaussian backward.  Order of the dL_dmean3D accumulation follows the reference's kernel
 // order: blend-kernel median term, computeCov2DCUDA, preprocessCUDA (2D mean, depth, SH).
 // (forcing more than 4 waves/SIMD spills: 5 -> 128 us, 6 -> 163 us against 87 us)
@@ -1111,23 +1131,13 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
         }
         const bool vis = rad > 0;
         float acc[16];
-        if (vis) {
-            acc[0] = a0.x; acc[1] = a0.y; acc[2] = a0.z; acc[3] = a0.w; acc[4] = a1.x; acc[5] = a1.y; acc[6] = a1.z; acc[7] = a1.w;
-            acc[8] = a2.x; acc[9] = a2.y; acc[10] = a2.z; acc[11] = a2.w; acc[12] = a3.x; acc[13] = a3.y; acc[14] = a3.z; acc[15] = a3.w;
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; i++) acc[i] = 0.0f;
-        }
+        unpack_acc_row(a0, a1, a2, a3, vis, acc);
 
         // ---- outputs that are plain copies of the blend kernel's sums
         // (with map_off the blend kernel still sums acc[4], acc[5] for the pose gradient, but the
         //  reference leaves every per-Gaussian gradient at zero: L/cuda_rasterizer/backward.cu:666)
         // (every dense output may be NULL: a tracking step needs the pose gradient only, dgr_hip.h)
-        if (a.dL_dmean2D) {
-            a.dL_dmean2D[3 * (size_t)idx + 0] = a.map_off ? 0.0f : acc[4];
-            a.dL_dmean2D[3 * (size_t)idx + 1] = a.map_off ? 0.0f : acc[5];
-            a.dL_dmean2D[3 * (size_t)idx + 2] = 0.0f;
-        }
+        write_dmean2D(a, idx, acc);
         // (COMPLETE under map_off: the mapping blend filled these sums, the tracking blend leaves them zero -- so do the outputs)
         const bool zero_copies = COMPLETE && a.map_off;
         if (a.dL_dopacity) a.dL_dopacity[idx] = zero_copies ? 0.0f : acc[9];
@@ -1297,18 +1307,8 @@ __global__ void __launch_bounds__(256, COMPLETE ? 3 : DGR_BWD_BATCH_WAVES) prepr
             const float4 shd0 = a.geom.shd[idx], shd1 = a.geom.shd[(size_t)P + idx], shd2 = a.geom.shd[2 * (size_t)P + idx];
             const bool vis = rad > 0;
             float acc[16];
-            if (vis) {
-                acc[0] = a0.x; acc[1] = a0.y; acc[2] = a0.z; acc[3] = a0.w; acc[4] = a1.x; acc[5] = a1.y; acc[6] = a1.z; acc[7] = a1.w;
-                acc[8] = a2.x; acc[9] = a2.y; acc[10] = a2.z; acc[11] = a2.w; acc[12] = a3.x; acc[13] = a3.y; acc[14] = a3.z; acc[15] = a3.w;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; i++) acc[i] = 0.0f;
-            }
-            if (a.dL_dmean2D) {
-                a.dL_dmean2D[3 * (size_t)idx + 0] = a.map_off ? 0.0f : acc[4];
-                a.dL_dmean2D[3 * (size_t)idx + 1] = a.map_off ? 0.0f : acc[5];
-                a.dL_dmean2D[3 * (size_t)idx + 2] = 0.0f;
-            }
+            unpack_acc_row(a0, a1, a2, a3, vis, acc);
+            write_dmean2D(a, idx, acc);
             float3 dmean, dRGB;
             float dcov[6], coef[16];
             bwd_view_terms<COMPLETE>(a, FULL, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
@@ -1414,53 +1414,25 @@ __global__ void __launch_bounds__(256) cov3d_fwd_kernel(int P, const float* __re
                                                         float mod, float* __restrict__ cov3D) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= P) return;
-    const float3 sc = make_float3(scales[3 * idx], scales[3 * idx + 1], scales[3 * idx + 2]);
-    const float4 q = make_float4(rotations[4 * idx], rotations[4 * idx + 1], rotations[4 * idx + 2], rotations[4 * idx + 3]);
-    M3 R;
-    quat_to_R(q, R);
-    const M3 S = diag3(mod * sc.x, mod * sc.y, mod * sc.z);
-    const M3 Mm = mul(S, R);
-    const M3 Sigma = mul(transpose(Mm), Mm);
+    float c3[6];
+    compute_cov3d(scales, rotations, mod, idx, c3);
     float* o = cov3D + 6 * (size_t)idx;
-    o[0] = Sigma.m[0][0]; o[1] = Sigma.m[0][1]; o[2] = Sigma.m[0][2];
-    o[3] = Sigma.m[1][1]; o[4] = Sigma.m[1][2]; o[5] = Sigma.m[2][2];
+#pragma unroll
+    for (int i = 0; i < 6; i++) o[i] = c3[i];
 }
 __global__ void __launch_bounds__(256) cov3d_bwd_kernel(int P, const float* __restrict__ scales, const float* __restrict__ rotations,
                                                         float mod, const float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale,
                                                         float* __restrict__ dL_drot) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= P) return;
-    const float* dcov = dL_dcov3D + 6 * (size_t)idx;
+    float dcov[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) dcov[i] = dL_dcov3D[6 * (size_t)idx + i];
     const float3 sc = make_float3(scales[3 * idx], scales[3 * idx + 1], scales[3 * idx + 2]);
     const float4 q = make_float4(rotations[4 * idx], rotations[4 * idx + 1], rotations[4 * idx + 2], rotations[4 * idx + 3]);
-    const float r = q.x, x = q.y, y = q.z, z = q.w;
-    M3 R;
-    quat_to_R(q, R);
-    const float3 s = make_float3(mod * sc.x, mod * sc.y, mod * sc.z);
-    const M3 Mm = mul(diag3(s.x, s.y, s.z), R);
-    M3 dSigma;
-    dSigma.m[0][0] = dcov[0]; dSigma.m[0][1] = 0.5f * dcov[1]; dSigma.m[0][2] = 0.5f * dcov[2];
-    dSigma.m[1][0] = 0.5f * dcov[1]; dSigma.m[1][1] = dcov[3]; dSigma.m[1][2] = 0.5f * dcov[4];
-    dSigma.m[2][0] = 0.5f * dcov[2]; dSigma.m[2][1] = 0.5f * dcov[4]; dSigma.m[2][2] = dcov[5];
-    M3 M2;
-#pragma unroll
-    for (int c = 0; c < 3; c++)
-#pragma unroll
-        for (int rr = 0; rr < 3; rr++) M2.m[c][rr] = Mm.m[c][rr] * 2.0f;
-    const M3 dL_dM = mul(M2, dSigma);
-    const M3 Rt = transpose(R);
-    M3 dMt = transpose(dL_dM);
     float3 dscale;
-    dscale.x = dot3(make_float3(Rt.m[0][0], Rt.m[0][1], Rt.m[0][2]), make_float3(dMt.m[0][0], dMt.m[0][1], dMt.m[0][2]));
-    dscale.y = dot3(make_float3(Rt.m[1][0], Rt.m[1][1], Rt.m[1][2]), make_float3(dMt.m[1][0], dMt.m[1][1], dMt.m[1][2]));
-    dscale.z = dot3(make_float3(Rt.m[2][0], Rt.m[2][1], Rt.m[2][2]), make_float3(dMt.m[2][0], dMt.m[2][1], dMt.m[2][2]));
-#pragma unroll
-    for (int k = 0; k < 3; k++) { dMt.m[0][k] *= s.x; dMt.m[1][k] *= s.y; dMt.m[2][k] *= s.z; }
     float4 drot;
-    drot.x = 2 * z * (dMt.m[0][1] - dMt.m[1][0]) + 2 * y * (dMt.m[2][0] - dMt.m[0][2]) + 2 * x * (dMt.m[1][2] - dMt.m[2][1]);
-    drot.y = 2 * y * (dMt.m[1][0] + dMt.m[0][1]) + 2 * z * (dMt.m[2][0] + dMt.m[0][2]) + 2 * r * (dMt.m[1][2] - dMt.m[2][1]) - 4 * x * (dMt.m[2][2] + dMt.m[1][1]);
-    drot.z = 2 * x * (dMt.m[1][0] + dMt.m[0][1]) + 2 * r * (dMt.m[2][0] - dMt.m[0][2]) + 2 * z * (dMt.m[1][2] + dMt.m[2][1]) - 4 * y * (dMt.m[2][2] + dMt.m[0][0]);
-    drot.w = 2 * r * (dMt.m[0][1] - dMt.m[1][0]) + 2 * x * (dMt.m[2][0] + dMt.m[0][2]) + 2 * y * (dMt.m[1][2] + dMt.m[2][1]) - 4 * z * (dMt.m[1][1] + dMt.m[0][0]);
+    cov3d_backward_terms(sc, q, mod, dcov, dscale, drot);
     // the reference scales dL_dscale by the modifier through `s` only (backward.cu:318-322): so does preprocess_bwd
     dL_dscale[3 * (size_t)idx + 0] = dscale.x;
     dL_dscale[3 * (size_t)idx + 1] = dscale.y;

@@ -104,6 +104,17 @@ struct StagedT {
 };
 using Staged = StagedT<DGR_TILE_PIX>;
 
+// One Gaussian's render record (three 16-byte words at DGR_REC_STRIDE * gid: {x, y, depth, opacity}, {conic a, b, c, -}, {r, g, b, -})
+// and the first word of its staged form, {x, y, a2, c2} (StagedT: p2 = dx*(a2*dx + b2*dy) + c2*dy*dy), which every staging shares.
+template <int AM>
+__device__ __forceinline__ void gather_record(const float4* __restrict__ rec, uint32_t gid, float4& staged0, float4& q0, float4& q1, float4& q2) {
+    constexpr float PSCALE = AlphaPath<AM>::PSCALE;
+    q0 = rec[DGR_REC_STRIDE * (size_t)gid + 0];
+    q1 = rec[DGR_REC_STRIDE * (size_t)gid + 1];
+    q2 = rec[DGR_REC_STRIDE * (size_t)gid + 2];
+    staged0 = make_float4(q0.x, q0.y, -0.5f * PSCALE * q1.x, -0.5f * PSCALE * q1.z);
+}
+
 template <bool HALF_CODES>
 __device__ __forceinline__ unsigned reach_code(const float4& q0, const float4& q1, float l2, float tile_x0, float tile_y0);
 
@@ -117,9 +128,8 @@ __device__ __forceinline__ unsigned reach_code(const float4& q0, const float4& q
 template <int AM, bool HALF_CODES = false, class S>
 __device__ __forceinline__ unsigned stage_one(S& s, int slot, uint32_t gid, const float4* __restrict__ rec,
                                               float tile_x0, float tile_y0) {
-    const float4 q0 = rec[DGR_REC_STRIDE * (size_t)gid + 0];
-    const float4 q1 = rec[DGR_REC_STRIDE * (size_t)gid + 1];
-    const float4 q2 = rec[DGR_REC_STRIDE * (size_t)gid + 2];
+    float4 q0, q1, q2;
+    gather_record<AM>(rec, gid, s.rec[2 * slot], q0, q1, q2);
     const float o = q0.w;
     // log-domain threshold: alpha >= 15/255 <=> p2 >= log2(15/(255 o)); the loop compares against a slightly lower
     // value and re-tests alpha itself on the rare path, so decisions are those of the linear-domain test.
@@ -139,7 +149,6 @@ __device__ __forceinline__ unsigned stage_one(S& s, int slot, uint32_t gid, cons
         lthr = __int_as_float(((__float_as_int(lthr) + 0xFF) & ~0xFF) | slot);
         zword = 0.f;
     }
-    s.rec[2 * slot] = make_float4(q0.x, q0.y, -0.5f * PSCALE * q1.x, -0.5f * PSCALE * q1.z);
     s.rec[2 * slot + 1] = make_float4(-PSCALE * q1.y, o, zword, lthr);
     s.rgbd[slot] = make_float4(q2.x, q2.y, q2.z, q0.z);
     if (S::HAS_ID) s.id[slot] = gid;
@@ -213,10 +222,8 @@ __device__ __forceinline__ unsigned stage_tagged(S& s, int slot, uint32_t entry,
     if (code == 0u) return 0u;
     if (TAGS == TAGS_BYTES_QUADRANT) code = fold8(code);
     const uint32_t gid = entry & ID_MASK;
-    const float4 q0 = rec[DGR_REC_STRIDE * (size_t)gid + 0];
-    const float4 q1 = rec[DGR_REC_STRIDE * (size_t)gid + 1];
-    const float4 q2 = rec[DGR_REC_STRIDE * (size_t)gid + 2];
-    s.rec[2 * slot] = make_float4(q0.x, q0.y, -0.5f * PSCALE * q1.x, -0.5f * PSCALE * q1.z);
+    float4 q0, q1, q2;
+    gather_record<AM>(rec, gid, s.rec[2 * slot], q0, q1, q2);
     // (.z: 4 * slot = the byte offset of the slot's accumulator column; .w: byte offset of its rgbd entry -- the backward
     //  kernels address LDS with both directly, and compare .z with 4 * (slots at or before the pixel's last contributor))
     s.rec[2 * slot + 1] = make_float4(-PSCALE * q1.y, q0.w, __int_as_float(slot * 4), __int_as_float(slot * 16));
@@ -266,10 +273,8 @@ __device__ __forceinline__ unsigned stage_live(S& s, int slot, uint2 e, const fl
     unsigned code = e.y & 0xFFu;
     if (QUADRANT) code = fold8(code);
     const uint32_t gid = e.x & ID_MASK;
-    const float4 q0 = rec[DGR_REC_STRIDE * (size_t)gid + 0];
-    const float4 q1 = rec[DGR_REC_STRIDE * (size_t)gid + 1];
-    const float4 q2 = rec[DGR_REC_STRIDE * (size_t)gid + 2];
-    s.rec[3 * slot] = make_float4(q0.x, q0.y, -0.5f * PSCALE * q1.x, -0.5f * PSCALE * q1.z);
+    float4 q0, q1, q2;
+    gather_record<AM>(rec, gid, s.rec[3 * slot], q0, q1, q2);
     // (.z: 4 * slot = the byte offset of the slot's accumulator column, which the backward addresses LDS with directly)
     s.rec[3 * slot + 1] = make_float4(-PSCALE * q1.y, q0.w, __int_as_float(slot * 4), __int_as_float((int)(e.y >> 8)));
     s.rec[3 * slot + 2] = make_float4(q2.x, q2.y, q2.z, q0.z);
@@ -518,6 +523,125 @@ __device__ __forceinline__ void flush_acc(const float* lds_acc, const uint32_t* 
             const float v = lds_acc[comp * LD + r];
             if (v != 0.f) atomicAdd(global_acc + (size_t)ids[r] * DGR_ACC_STRIDE + comp, v);
         }
+    }
+}
+
+// ================================================================================ shared by the blend bodies
+// What the light and the full bodies have in common apart from compile-time constants; their pair loops stay their own (one
+// recurrence against three, 12 sums against 16, live lists against positions).
+
+// A blend thread's pixel: wave w of the workgroup owns the 8x8-pixel quadrant (w & 1, w >> 1) of tile (tx, ty), lane l its pixel
+// (l & 7, l >> 3).  id = W py + px, a 32-bit word in every blend kernel: W H <= 2^30 (api.hip: check_common), so the offsets of
+// the three colour planes fit as well.
+struct TilePixel {
+    int tx, ty, px, py;
+    bool inside;
+    uint32_t id;
+};
+__device__ __forceinline__ TilePixel tile_pixel(int tile, int grid_x, int W, int H, int wave, int lane) {
+    const int tx = tile % grid_x, ty = tile / grid_x;
+    const int px = tx * DGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
+    const int py = ty * DGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
+    return {tx, ty, px, py, px < W && py < H, (uint32_t)W * (uint32_t)py + (uint32_t)px};
+}
+
+// A backward kernel's batch in LDS: the staged entries (STAGED: StagedLiveT in the light variant, StagedT in the full one) and NACC0
+// accumulator rows, one column per entry.  DET (deterministic_grads): one accumulator plane per quadrant wave -- four times the
+// accumulators, hence 64 entries per batch instead of 128 to stay at the same workgroups per CU -- and the entries' rows in the
+// instance-major gradient buffer.  ABS (absgrad): two more rows, components NACC0 and NACC0 + 1, behind the plane.
+// TAIL: the variant's own words behind them, the exp table (ALPHA_GLIBC: exact_math.h) among them.
+constexpr int bwd_batch_entries(bool det) { return det ? 64 : 128; }
+template <class STAGED, int NACC0, bool DET, bool ABS, class TAIL>
+struct BwdBatch {
+    typedef STAGED staged_t;
+    static constexpr int NB = STAGED::SLOTS;
+    static constexpr int LD = NB + 1;          // accumulator row length
+    static constexpr int PLANE = NACC0 * LD;
+    static constexpr int NACC = ABS ? NACC0 + 2 : NACC0;  // rows cleared per batch
+    staged_t f;
+    float acc[(DET ? 4 : 1) * PLANE + (ABS ? 2 * LD : 0)];
+    uint32_t inst[DET ? NB : 1];               // DET: the staged entries' rows in the instance-major gradient buffer (~0u: none)
+    TAIL t;
+};
+// a batch's accumulator columns back to zero (not DET: a plane's column is written by its wave iff the entry's tag names the wave)
+template <class SB>
+__device__ __forceinline__ void clear_acc(SB& sb, int tid) {
+#pragma unroll
+    for (int k = 0; k < SB::NACC; k++)
+        if (tid < SB::NB) sb.acc[k * SB::LD + tid] = 0.f;
+}
+
+// the conic of a staged record (r0 = {x, y, a2, c2}, r1 = {b2, ...}) without the staging's scale: {a, b, c}
+template <int AM>
+__device__ __forceinline__ float3 unscaled_conic(const float4& r0, const float4& r1) {
+    constexpr float UN = AlphaPath<AM>::PUNSCALE;
+    return make_float3(r0.z * (-2.f * UN), r1.x * (-UN), r0.w * (-2.f * UN));
+}
+// moments -> gradients (backward.cu:627-631): the sums Sx = sum q dx, Sy = sum q dy of one Gaussian become, in place,
+// its "d/d(ndc)" pair -(a Sx + b Sy) W/2, -(c Sy + b Sx) H/2
+__device__ __forceinline__ void mean2d_from_moments(float3 conic, float& Sx, float& Sy, float ddelx_dx, float ddely_dy) {
+    const float sx = Sx, sy = Sy;
+    Sx = -(conic.x * sx + conic.y * sy) * ddelx_dx;
+    Sy = -(conic.z * sy + conic.y * sx) * ddely_dy;
+}
+
+// absgrad, per lane and list entry: this pixel's dL/dmean2D without the ndc scale (mean2d_from_moments applied to the pixel's own
+// q dx, q dy), in absolute value; half_reduce3 sums the pair over each half-wave and each half adds its totals to its own entry's
+// column (j4 = 4 * slot, uniform per half) of accumulator rows NACC0, NACC0 + 1.
+template <int AM, int NACC0, int LD>
+__device__ __forceinline__ void abs_pair_terms(float* acc, const float4& q0, const float4& q1, float qdx, float qdy, int j4, int lane) {
+    const float3 c = unscaled_conic<AM>(q0, q1);
+    const float h = half_reduce3(fabsf(c.x * qdx + c.y * qdy), fabsf(c.z * qdy + c.y * qdx), 0.f);
+    const int comp = half_reduce3_comp(lane);  // 0: |x| in lane 32 h, 1: |y| in lane 32 h + 16
+    if (comp == 0 || comp == 1)
+        atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(acc) + j4 + (NACC0 + comp) * (LD * 4)), h);
+}
+// ... and per batch: a staged entry is one thread's, its two totals, times W/2 and H/2, go to abs_out [P,3] from here
+template <int NACC0, int LD>
+__device__ __forceinline__ void abs_flush(const float* acc, const uint32_t* ids, int tid, float ddelx_dx, float ddely_dy, float* __restrict__ abs_out) {
+    const float ax = acc[NACC0 * LD + tid] * ddelx_dx, ay = acc[(NACC0 + 1) * LD + tid] * ddely_dy;
+    const size_t gid = ids[tid];
+    if (ax != 0.f) atomicAdd(abs_out + 3 * gid, ax);
+    if (ay != 0.f) atomicAdd(abs_out + 3 * gid + 1, ay);
+}
+
+// A paired step's delivery (build_paired_lists): each half's own totals r0, r1 to rows c0, c1 (-1: none) of its own entry's column
+template <int LD>
+__device__ __forceinline__ void deliver_pair(float* acc, int j4, int c0, int c1, float r0, float r1) {
+    char* const col = reinterpret_cast<char*>(acc) + j4;
+    if (c0 >= 0) atomicAdd(reinterpret_cast<float*>(col + c0 * (LD * 4)), r0);
+    if (c1 >= 0) atomicAdd(reinterpret_cast<float*>(col + c1 * (LD * 4)), r1);
+}
+
+// ---- deterministic gradients (render_light.hip has the scheme).  After a batch's pair loop the thread of a staged entry (code: its
+// tag, 0 = nobody's) adds the four waves' planes in wave order into plane 0 (a wave whose bit of `code` is clear never wrote its
+// column; the sentinel entries of a padded list write column NB, which nobody reads).  delivered(k): some lane of this instance
+// delivers component k -- the others are nobody's and read as zero.
+template <int NCOMP, int PLANE, int LD, class DELIVERED>
+__device__ __forceinline__ void det_fold_planes(float* acc, unsigned code, int tid, DELIVERED delivered) {
+#pragma unroll
+    for (int k = 0; k < NCOMP; k++) {
+        float v = 0.f;
+        if (delivered(k)) {
+#pragma unroll
+            for (int w = 0; w < 4; w++)
+                if ((code >> w) & 1u) v += acc[w * PLANE + k * LD + tid];
+        }
+        acc[k * LD + tid] = v;
+    }
+}
+// the (tile, Gaussian) pair's row in the instance-major buffer: the Gaussian's first instance (det_offsets_kernel) + the tile's place in its rectangle
+__device__ __forceinline__ uint32_t det_row_of(const ushort4* __restrict__ det_rect, const uint32_t* __restrict__ det_goff, uint32_t gid, int tx, int ty) {
+    const ushort4 rc = det_rect[gid];
+    return det_goff[gid] + (uint32_t)(ty - (int)rc.y) * (uint32_t)(rc.z - rc.x) + (uint32_t)(tx - (int)rc.x);
+}
+// 16 consecutive lanes store one pair's 64-byte row (the components from NCOMP on stay zero: the buffer is zero-filled first)
+template <int NCOMP, int LD>
+__device__ __forceinline__ void det_store_rows(const float* acc, const uint32_t* inst, int cnt, float* __restrict__ det_rows, uint32_t det_R, int tid) {
+    const int comp = tid & 15;
+    for (int r = tid >> 4; r < cnt; r += 16) {
+        const uint32_t row = inst[r];
+        if (row < det_R && comp < NCOMP) det_rows[(size_t)row * DGR_ACC_STRIDE + comp] = acc[comp * LD + r];
     }
 }
 

@@ -39,11 +39,10 @@ __global__ void __launch_bounds__(256, 8) render_fwd_full_kernel(RenderFwdFullAr
     bool overflowed;
     const uint4 slot = blend_slot(a.sched, a.ranges, a.sched_flag, a.grid_x * a.grid_y, &overflowed);  // {tile, list start, list end}
     const int tile = (int)slot.x;
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * DGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * DGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < a.W && py < a.H;
+    const auto [tx, ty, px, py, inside, pix32] = tile_pixel(tile, a.grid_x, a.W, a.H, wave, lane);
+    // (this variant keeps its 64-bit pixel index: with the 32-bit one of TilePixel the backward measured 0.5 us slower at config 2,
+    //  0.0774 -> 0.0779 ms -- the zero-extended addresses cost it four more v_mov; profiles/blend_shared/notes.md)
     const size_t pix_id = (size_t)a.W * py + px;
     const f2 pxy = {(float)px, (float)py};
     const float tile_x0 = (float)(tx * DGR_BLOCK_X), tile_y0 = (float)(ty * DGR_BLOCK_Y);
@@ -143,24 +142,14 @@ __global__ void __launch_bounds__(256, 8) render_fwd_full_kernel(RenderFwdFullAr
 // ================================================================================ backward
 constexpr int NACC_FULL = 15;
 
-// list positions staged per batch (occupancy: see render_light.hip).  DET (dgr_set_option("deterministic_grads", 1); round 9 for this
-// variant): one accumulator plane per quadrant wave, plain stores, the planes added in wave order, the finished row of a
-// (tile, Gaussian) pair STORED to its own row of an instance-major buffer that det_gather_kernel adds up per Gaussian in ascending
-// order -- render_light.hip has the scheme; four planes are four times the accumulators, hence 64 positions per batch.
-// ABS (absgrad, render_bwd_full_abs_kernel): two more accumulator rows, components 15 and 16, behind the plane
-template <bool DET, bool ABS = false>
-struct StagedBwdFull {
-    static constexpr int NB = DET ? 64 : 128;
-    static constexpr int LD = NB + 1;
-    static constexpr int PLANE = NACC_FULL * LD;
-    static constexpr int NACC = ABS ? NACC_FULL + 2 : NACC_FULL;  // rows cleared per batch
-    typedef StagedT<NB, uint32_t, DET ? 4 : 8> staged_t;  // (paired lists: two list rows per quadrant wave, render_common.h)
-    staged_t f;
-    float acc[(DET ? 4 : 1) * PLANE + (ABS ? 2 * LD : 0)];
-    uint32_t inst[DET ? NB : 1];
-    int max_last;
+// The batch (render_common.h: BwdBatch) stages list POSITIONS, with fifteen accumulator rows.  DET (deterministic_grads; round 9 for
+// this variant): render_light.hip has the scheme.
+struct BwdTailFull {
+    int max_last;         // the tile's last contributor: the list positions this kernel walks
     uint64_t exptab[32];  // ALPHA_GLIBC: exact_math.h
 };
+template <bool DET, bool ABS = false>  // (render_common.h: BwdBatch; paired lists: two list rows per quadrant wave)
+using StagedBwdFull = BwdBatch<StagedT<bwd_batch_entries(DET), uint32_t, DET ? 4 : 8>, NACC_FULL, DET, ABS, BwdTailFull>;
 
 // Paired lists (round 9, as the light mapping backward: render_light.hip, render_common.h: build_paired_lists): from the forward's
 // tags per half, neighbouring entries of a quadrant's list that live in different halves share a loop step, whose sixteen sums are
@@ -183,12 +172,9 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
     typename SB::staged_t& s = sb.f;
     const uint4 slot = blend_slot(a.sched, a.ranges, a.sched_flag, a.grid_x * a.grid_y);  // {tile, list start, list end}
     const int tile = (int)slot.x;
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * DGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * DGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < a.W && py < a.H;
-    const size_t pix_id = (size_t)a.W * py + px;
+    const auto [tx, ty, px, py, inside, pix32] = tile_pixel(tile, a.grid_x, a.W, a.H, wave, lane);
+    const size_t pix_id = (size_t)a.W * py + px;  // (64-bit, as in the forward above)
     const size_t N = (size_t)a.W * a.H;
     const f2 pxy = {(float)px, (float)py};
 
@@ -197,19 +183,19 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
     const int first_contributor = inside ? (int)a.first_contrib[pix_id] : 0;
 
     if (tid == 0) {
-        sb.max_last = 0;
+        sb.t.max_last = 0;
         write_sentinel<true>(s);
     }
-    if (AlphaPath<AM>::TABLE) exp_ref_table_fill(sb.exptab, tid);
+    if (AlphaPath<AM>::TABLE) exp_ref_table_fill(sb.t.exptab, tid);
     __syncthreads();
     {
         int v = last_contributor;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
-        if (lane == 0) atomicMax(&sb.max_last, v);
+        if (lane == 0) atomicMax(&sb.t.max_last, v);
     }
     __syncthreads();
-    const int total = min((int)(range.y - range.x), sb.max_last);
+    const int total = min((int)(range.y - range.x), sb.t.max_last);
     if (total <= 0) return;
 
     const float T_final = inside ? a.final_T[pix_id] : 0.f;  // backward.cu:598
@@ -244,11 +230,7 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
         __syncthreads();
         unsigned code = 0;
         if (tid < cnt) code = stage_tagged<AM, PAIRED ? TAGS_BYTES_HALVES : TAGS_BYTES_QUADRANT>(s, tid, a.point_list[range.x + lo + tid], a.rec, tag8 + (range.x + lo + tid));
-        if (!DET) {  // (DET: a plane's column is written by its wave iff the entry's tag names the wave -- nothing to clear)
-#pragma unroll
-            for (int k = 0; k < SB::NACC; k++)
-                if (tid < BWD_NB) sb.acc[k * BWD_LD + tid] = 0.f;
-        }
+        if (!DET) clear_acc(sb, tid);
         unsigned long long split[2] = {0ull, 0ull};  // PAIRED: the steps that serve two entries
         const int n = PAIRED ? build_paired_lists(s, code, tid, wave, lane, split) : build_lists(s, code, tid, wave, lane);
         // (the staged record carries 4 * slot: render_common.h, stage_tagged)
@@ -273,7 +255,7 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
                 const float p2 = pair_p2<AM>(q0[u], q1[u], pxy, dxy);
                 const int j4 = __float_as_int(q1[u].z);
                 // every listed entry was blended by some pixel of this wave (contribution tags): no wave-level tests
-                const float oG = alpha_raw<AM, true>(q1[u].y, p2, sb.exptab);  // o G: alpha before the 0.99 clamp
+                const float oG = alpha_raw<AM, true>(q1[u].y, p2, sb.t.exptab);  // o G: alpha before the 0.99 clamp
                 // (0.99 is above the threshold, so o G itself decides; "not below" keeps a NaN o G valid as min(0.99f, NaN) does)
                 const bool valid = (j4 < rel_last4) & (p2 <= 0.0f) & !(oG < ALPHA_MIN);
                 // No branch (see render_light.hip): a lane the Gaussian does not reach runs the same instructions with
@@ -324,15 +306,7 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
                 g[13] = fq * dx;  // front-most depth sums
                 g[14] = fq * dy;
                 g[15] = 0.f;
-                if (ABS) {
-                    // this pixel's dL/dmean2D without the ndc scale, in absolute value
-                    constexpr float UN = AlphaPath<AM>::PUNSCALE;
-                    const float ca = q0[u].z * (-2.f * UN), cb = q1[u].x * (-UN), cc = q0[u].w * (-2.f * UN);
-                    const float h = half_reduce3(fabsf(ca * qdx + cb * qdy), fabsf(cc * qdy + cb * qdx), 0.f);
-                    const int c = half_reduce3_comp(lane);  // 0: |x| in lane 32 h, 1: |y| in lane 32 h + 16
-                    if (c == 0 || c == 1)
-                        atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(sb.acc) + j4 + (NACC_FULL + c) * (BWD_LD * 4)), h);
-                }
+                if (ABS) abs_pair_terms<AM, NACC_FULL, BWD_LD>(sb.acc, q0[u], q1[u], qdx, qdy, j4, lane);
                 float tot;
                 if (PAIRED) {
                     float u0, u1;
@@ -343,9 +317,7 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
                         const float r0 = quad_sum(u0), r1 = quad_sum(u1);
                         const int c0 = (lane & 3) == 0 ? wave_reduce16d_half_slot0(lane) : -1;
                         const int c1 = ((lane & 3) == 0 && wave_reduce16d_half_slot1(lane) < NACC_FULL) ? wave_reduce16d_half_slot1(lane) : -1;
-                        char* const col = reinterpret_cast<char*>(sb.acc) + j4;
-                        if (c0 >= 0) atomicAdd(reinterpret_cast<float*>(col + c0 * (BWD_LD * 4)), r0);
-                        if (c1 >= 0) atomicAdd(reinterpret_cast<float*>(col + c1 * (BWD_LD * 4)), r1);
+                        deliver_pair<BWD_LD>(sb.acc, j4, c0, c1, r0, r1);
                         continue;
                     }
                     tot = wave_reduce16d_tail(u0, u1);
@@ -360,54 +332,33 @@ __device__ __forceinline__ void render_bwd_full_body(const RenderBwdFullArgs& a,
         }
         __syncthreads();
         if (DET && tid < BWD_NB) {
-            // the four planes in wave order into plane 0 (a wave whose tag bit is clear never wrote its column), and the pair's row
+            // the four planes in wave order into plane 0 (every component is delivered), and the pair's row
             uint32_t row = ~0u;
             if (code != 0u) {
-#pragma unroll
-                for (int k = 0; k < NACC_FULL; k++) {
-                    float v = 0.f;
-#pragma unroll
-                    for (int w = 0; w < 4; w++)
-                        if ((code >> w) & 1u) v += sb.acc[w * SB::PLANE + k * BWD_LD + tid];
-                    sb.acc[k * BWD_LD + tid] = v;
-                }
-                const uint32_t gid = s.id[tid];
-                const ushort4 rc = a.det_rect[gid];
-                row = a.det_goff[gid] + (uint32_t)(ty - (int)rc.y) * (uint32_t)(rc.z - rc.x) + (uint32_t)(tx - (int)rc.x);
+                det_fold_planes<NACC_FULL, SB::PLANE, BWD_LD>(sb.acc, code, tid, [](int) { return true; });
+                row = det_row_of(a.det_rect, a.det_goff, s.id[tid], tx, ty);
             }
             sb.inst[tid] = row;
         }
         if (DET) __syncthreads();
         // moments -> gradients per staged Gaussian: every "d/d(ndc)" sum is -(a Sx + b Sy) W/2, -(c Sy + b Sx) H/2
         if (code != 0u) {
-            constexpr float UN = AlphaPath<AM>::PUNSCALE;  // (undoes the scale of the staged conic)
             const float4 r0 = s.rec[2 * tid], r1 = s.rec[2 * tid + 1];
-            const float ca = r0.z * (-2.f * UN), cb = r1.x * (-UN), cc = r0.w * (-2.f * UN);
+            const float3 conic = unscaled_conic<AM>(r0, r1);
 #pragma unroll
             for (int p = 0; p < 3; p++) {
-                const int cx = (p == 0) ? 4 : (p == 1) ? 10 : 13, cy = cx + 1;
-                const float Sx = sb.acc[cx * BWD_LD + tid], Sy = sb.acc[cy * BWD_LD + tid];
-                sb.acc[cx * BWD_LD + tid] = -(ca * Sx + cb * Sy) * ddelx_dx;
-                sb.acc[cy * BWD_LD + tid] = -(cc * Sy + cb * Sx) * ddely_dy;
+                const int cx = (p == 0) ? 4 : (p == 1) ? 10 : 13;
+                mean2d_from_moments(conic, sb.acc[cx * BWD_LD + tid], sb.acc[(cx + 1) * BWD_LD + tid], ddelx_dx, ddely_dy);
             }
             sb.acc[6 * BWD_LD + tid] *= -0.5f;
             sb.acc[7 * BWD_LD + tid] *= -0.5f;
             sb.acc[8 * BWD_LD + tid] *= -0.5f;
             sb.acc[9 * BWD_LD + tid] *= __builtin_amdgcn_rcpf(r1.y);
-            if (ABS) {
-                const float ax = sb.acc[NACC_FULL * BWD_LD + tid] * ddelx_dx, ay = sb.acc[(NACC_FULL + 1) * BWD_LD + tid] * ddely_dy;
-                const size_t gid = s.id[tid];
-                if (ax != 0.f) atomicAdd(abs_out + 3 * gid, ax);
-                if (ay != 0.f) atomicAdd(abs_out + 3 * gid + 1, ay);
-            }
+            if (ABS) abs_flush<NACC_FULL, BWD_LD>(sb.acc, s.id, tid, ddelx_dx, ddely_dy, abs_out);
         }
         __syncthreads();
-        if (DET) {  // 16 consecutive lanes store one pair's 64-byte row (component 15 stays zero)
-            const int comp = tid & 15;
-            for (int r = tid >> 4; r < cnt; r += 16) {
-                const uint32_t row = sb.inst[r];
-                if (row < a.det_R && comp < NACC_FULL) a.det_rows[(size_t)row * DGR_ACC_STRIDE + comp] = sb.acc[comp * BWD_LD + r];
-            }
+        if (DET) {
+            det_store_rows<NACC_FULL, BWD_LD>(sb.acc, sb.inst, cnt, a.det_rows, a.det_R, tid);
         } else {
             flush_acc<NACC_FULL, BWD_LD>(sb.acc, s.id, cnt, a.acc, tid);
         }

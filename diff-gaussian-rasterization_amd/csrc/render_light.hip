@@ -94,12 +94,8 @@ template <int AM, bool HALVES>
 __device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& a, StagedFwd<HALVES>& sf, const uint4 slot, const bool overflowed) {
     typename StagedFwd<HALVES>::staged_t& s = sf.f;
     const int tile = (int)slot.x;
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * DGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * DGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < a.W && py < a.H;
-    const uint32_t pix_id = (uint32_t)a.W * (uint32_t)py + (uint32_t)px;  // (W H <= 2^30: api.hip)
+    const auto [tx, ty, px, py, inside, pix_id] = tile_pixel(tile, a.grid_x, a.W, a.H, wave, lane);
     const f2 pxy = {(float)px, (float)py};
     const float tile_x0 = (float)(tx * DGR_BLOCK_X), tile_y0 = (float)(ty * DGR_BLOCK_Y);
     const int my_list = HALVES ? 2 * wave + (lane >> 5) : wave;
@@ -237,22 +233,12 @@ constexpr int NACC_LIGHT = 14;
 
 // LIVE entries staged per batch -- the entries the forward blended, read from its compacted live list (render_common.h: live_list;
 // until then a batch was 128 list POSITIONS, dead ones included: each cost a tag read, a list read and its share of the batch's
-// barriers, accumulator clears and flush).  (256: 5 workgroups per CU, 267 us; 128: 247 us.)  The deterministic kernel (DET, below) keeps one
-// accumulator plane per quadrant wave -- four times the accumulators -- and stages 64 entries per batch to stay at 8 workgroups
-// per CU.
-// ABS (absgrad, render_bwd_light_abs_kernel): two more accumulator rows, components 14 and 15, behind the plane.
-template <bool DET, bool HALVES = false, bool ABS = false>
-struct StagedBwd {
-    static constexpr int NB = DET ? 64 : 128;
-    static constexpr int LD = NB + 1;          // accumulator row length
-    static constexpr int PLANE = NACC_LIGHT * LD;
-    static constexpr int NACC = ABS ? NACC_LIGHT + 2 : NACC_LIGHT;  // rows cleared per batch
-    typedef StagedLiveT<NB, HALVES ? 8 : 4> staged_t;  // (render_common.h: a batch is NB LIVE entries)
-    staged_t f;
-    float acc[(DET ? 4 : 1) * PLANE + (ABS ? 2 * LD : 0)];
-    uint32_t inst[DET ? NB : 1];               // DET: the staged entries' rows in the instance-major gradient buffer (~0u: none)
+// barriers, accumulator clears and flush).  (256: 5 workgroups per CU, 267 us; 128: 247 us; the deterministic kernel's 64: 8 per CU.)
+struct BwdTailLight {
     uint64_t exptab[32];  // ALPHA_GLIBC: exact_math.h
 };
+template <bool DET, bool HALVES = false, bool ABS = false>  // (render_common.h: BwdBatch; a batch is NB LIVE entries)
+using StagedBwd = BwdBatch<StagedLiveT<bwd_batch_entries(DET), HALVES ? 8 : 4>, NACC_LIGHT, DET, ABS, BwdTailLight>;
 
 // 8 waves per SIMD (63 VGPRs, no scratch): measured 258 us at the compiler's own choice of 7, 247 us at 8
 //
@@ -300,12 +286,8 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
     constexpr int BWD_NB = SB::NB, BWD_LD = SB::LD;
     typename SB::staged_t& s = sb.f;
     const int tile = (int)slot.x;
-    const int tx = tile % a.grid_x, ty = tile / a.grid_x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int px = tx * DGR_BLOCK_X + (wave & 1) * 8 + (lane & 7);
-    const int py = ty * DGR_BLOCK_Y + (wave >> 1) * 8 + (lane >> 3);
-    const bool inside = px < a.W && py < a.H;
-    const uint32_t pix_id = (uint32_t)a.W * (uint32_t)py + (uint32_t)px;  // (W H <= 2^30: api.hip)
+    const auto [tx, ty, px, py, inside, pix_id] = tile_pixel(tile, a.grid_x, a.W, a.H, wave, lane);
     const uint32_t N = (uint32_t)a.W * (uint32_t)a.H;
     const float pxf = (float)px, pyf = (float)py;
     const f2 pxy = {pxf, pyf};
@@ -318,7 +300,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
     const int last_contributor = inside ? (int)a.n_contrib[pix_id] : 0;
 
     if (tid == 0) write_sentinel_live(s);
-    if (AlphaPath<AM>::TABLE) exp_ref_table_fill(sb.exptab, tid);  // (visible after the first batch's barriers)
+    if (AlphaPath<AM>::TABLE) exp_ref_table_fill(sb.t.exptab, tid);  // (visible after the first batch's barriers)
 
     const float T_final = inside ? (1.0f - a.alphas[pix_id]) : 0.f;
     float T = T_final;
@@ -372,11 +354,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         __syncthreads();  // previous batch fully flushed / consumed
         unsigned code = 0;
         if (tid < cnt) code = stage_live<AM, !HALVES>(s, tid, live[lo + tid], a.rec);
-        if (!DET) {  // (DET: a plane's column is written by its wave iff the entry's tag names the wave -- nothing to clear)
-#pragma unroll
-            for (int k = 0; k < SB::NACC; k++)
-                if (BWD_NB == DGR_TILE_PIX || tid < BWD_NB) sb.acc[k * BWD_LD + tid] = 0.f;
-        }
+        if (!DET) clear_acc(sb, tid);
         unsigned long long split[2] = {0ull, 0ull};  // PAIRED: the steps that serve two entries
         const int n = PAIRED   ? build_paired_lists(s, code, tid, wave, lane, split)
                       : HALVES ? build_half_lists(s, code, tid, wave, lane)
@@ -408,7 +386,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
                 const float dx = dxy.x, dy = dxy.y;
                 const int j4 = __float_as_int(q1[u].z);  // 4 * slot
                 // every listed entry was blended by some pixel of this wave (contribution tags): no wave-level tests
-                const float oG = alpha_raw<AM, true>(q1[u].y, p2, sb.exptab);  // o G: alpha before the 0.99 clamp, and dalpha/dG * G
+                const float oG = alpha_raw<AM, true>(q1[u].y, p2, sb.t.exptab);  // o G: alpha before the 0.99 clamp, and dalpha/dG * G
                 // (the reference tests min(0.99, o G) >= 15/255; 0.99 is above the threshold, so o G itself decides)
                 // (written as "not below", so that a NaN o G -- a poisoned opacity -- stays a valid pair with alpha 0.99 as under
                 //  the reference's min(0.99f, NaN))
@@ -462,15 +440,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
                     g[9] = qq;         // sum q
                     g[10] = DO_POSE ? wd : gmed;   // -> accumulator component 13 / 10
                     g[11] = DO_POSE ? gmed : 0.f;  // -> accumulator component 10
-                    if (ABS) {
-                        // this pixel's dL/dmean2D without the ndc scale (finish step below), in absolute value
-                        constexpr float UN = AlphaPath<AM>::PUNSCALE;
-                        const float ca = q0[u].z * (-2.f * UN), cb = q1[u].x * (-UN), cc = q0[u].w * (-2.f * UN);
-                        const float h = half_reduce3(fabsf(ca * qdx + cb * qdy), fabsf(cc * qdy + cb * qdx), 0.f);
-                        const int c = half_reduce3_comp(lane);  // 0: |x| in lane 32 h, 1: |y| in lane 32 h + 16
-                        if (c == 0 || c == 1)
-                            atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(sb.acc) + j4 + (NACC_LIGHT + c) * (BWD_LD * 4)), h);
-                    }
+                    if (ABS) abs_pair_terms<AM, NACC_LIGHT, BWD_LD>(sb.acc, q0[u], q1[u], qdx, qdy, j4, lane);
                     if (PAIRED) {
                         float u0, u1;
                         wave_reduce12d_head(g, u0, u1);
@@ -483,9 +453,7 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
                             const int s1 = wave_reduce12d_half_slot1(lane);
                             const int c0 = (lane & 3) == 0 ? comp_of(wave_reduce12d_half_slot0(lane)) : -1;
                             const int c1 = ((lane & 3) == 0 && s1 >= 0) ? comp_of(s1) : -1;
-                            char* const col = reinterpret_cast<char*>(sb.acc) + j4;
-                            if (c0 >= 0) atomicAdd(reinterpret_cast<float*>(col + c0 * (BWD_LD * 4)), r0);
-                            if (c1 >= 0) atomicAdd(reinterpret_cast<float*>(col + c1 * (BWD_LD * 4)), r1);
+                            deliver_pair<BWD_LD>(sb.acc, j4, c0, c1, r0, r1);
                             continue;
                         }
                         tot = wave_reduce12d_tail(u0, u1);
@@ -508,25 +476,14 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
 
         __syncthreads();
         if (DET && tid < BWD_NB) {
-            // the four planes in wave order into plane 0 (a wave whose tag bit is clear never wrote its column; the sentinel
-            // entries of a padded list write column NB, which nobody reads), and the pair's row in the instance-major buffer
+            // the four planes in wave order into plane 0, and the pair's row in the instance-major buffer
             uint32_t row = ~0u;
             if (code != 0u) {
-#pragma unroll
-                for (int k = 0; k < NACC_LIGHT; k++) {
-                    // (components this variant's lanes deliver -- my_comp above; the others are nobody's and read as zero)
-                    const bool delivered = DO_MAP ? (k <= 9 || k == 10 || (DO_POSE && k == 13)) : (k == 4 || k == 5 || k == 13);
-                    float v = 0.f;
-                    if (delivered) {
-#pragma unroll
-                        for (int w = 0; w < 4; w++)
-                            if ((code >> w) & 1u) v += sb.acc[w * SB::PLANE + k * BWD_LD + tid];
-                    }
-                    sb.acc[k * BWD_LD + tid] = v;
-                }
-                const uint32_t gid = s.id[tid];
-                const ushort4 rc = a.det_rect[gid];
-                row = a.det_goff[gid] + (uint32_t)(ty - (int)rc.y) * (uint32_t)(rc.z - rc.x) + (uint32_t)(tx - (int)rc.x);
+                // (the components this instance's lanes deliver: my_comp above)
+                det_fold_planes<NACC_LIGHT, SB::PLANE, BWD_LD>(sb.acc, code, tid, [](int k) {
+                    return DO_MAP ? (k <= 9 || k == 10 || (DO_POSE && k == 13)) : (k == 4 || k == 5 || k == 13);
+                });
+                row = det_row_of(a.det_rect, a.det_goff, s.id[tid], tx, ty);
             }
             sb.inst[tid] = row;
         }
@@ -534,18 +491,9 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
         // moments -> gradients, one thread per staged Gaussian (backward.cu:627-631, 669-678):
         //   dL/dmean2D = -(a Sx + b Sy) W/2, -(c Sy + b Sx) H/2;  dL/dconic = -Sxx/2, -Sxy/2, -Syy/2;  dL/dopacity = S0/o
         if (code != 0u) {
-            constexpr float UN = AlphaPath<AM>::PUNSCALE;  // (undoes the scale of the staged conic)
             const float4 r0 = s.rec[3 * tid], r1 = s.rec[3 * tid + 1];
-            const float ca = r0.z * (-2.f * UN), cb = r1.x * (-UN), cc = r0.w * (-2.f * UN);  // unscaled conic
-            const float Sx = sb.acc[4 * BWD_LD + tid], Sy = sb.acc[5 * BWD_LD + tid];
-            sb.acc[4 * BWD_LD + tid] = -(ca * Sx + cb * Sy) * ddelx_dx;
-            sb.acc[5 * BWD_LD + tid] = -(cc * Sy + cb * Sx) * ddely_dy;
-            if (ABS) {  // (a staged entry of this batch is one thread's: its two totals go out from here)
-                const float ax = sb.acc[NACC_LIGHT * BWD_LD + tid] * ddelx_dx, ay = sb.acc[(NACC_LIGHT + 1) * BWD_LD + tid] * ddely_dy;
-                const size_t gid = s.id[tid];
-                if (ax != 0.f) atomicAdd(abs_out + 3 * gid, ax);
-                if (ay != 0.f) atomicAdd(abs_out + 3 * gid + 1, ay);
-            }
+            mean2d_from_moments(unscaled_conic<AM>(r0, r1), sb.acc[4 * BWD_LD + tid], sb.acc[5 * BWD_LD + tid], ddelx_dx, ddely_dy);
+            if (ABS) abs_flush<NACC_LIGHT, BWD_LD>(sb.acc, s.id, tid, ddelx_dx, ddely_dy, abs_out);
             if (DO_MAP) {
                 sb.acc[6 * BWD_LD + tid] *= -0.5f;
                 sb.acc[7 * BWD_LD + tid] *= -0.5f;
@@ -554,12 +502,8 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
             }
         }
         __syncthreads();
-        if (DET) {  // 16 consecutive lanes store one pair's 64-byte row (components 14, 15 stay zero)
-            const int comp = tid & 15;
-            for (int r = tid >> 4; r < cnt; r += 16) {
-                const uint32_t row = sb.inst[r];
-                if (row < a.det_R && comp < NACC_LIGHT) a.det_rows[(size_t)row * DGR_ACC_STRIDE + comp] = sb.acc[comp * BWD_LD + r];
-            }
+        if (DET) {
+            det_store_rows<NACC_LIGHT, BWD_LD>(sb.acc, sb.inst, cnt, a.det_rows, a.det_R, tid);
         } else {
             flush_acc<NACC_LIGHT, BWD_LD>(sb.acc, s.id, cnt, a.acc, tid);
         }
@@ -649,127 +593,36 @@ __global__ void __launch_bounds__(256) det_gather_kernel(int P, const ushort4* _
     acc[(size_t)g * DGR_ACC_STRIDE + comp] = v;
 }
 
-// self-test of the butterflies: in[c * 64 + lane] -> the three networks' results and value maps per lane (dgr_debug_wave_reduce)
-__global__ void __launch_bounds__(64) wave_reduce_test_kernel(const float* in, float* out16, float* out12, float* out4,
-                                                             int* comp16, int* comp12, int* comp4) {
-    const int lane = threadIdx.x;
-    float g16[16], g12[12], g4[4];
-#pragma unroll
-    for (int k = 0; k < 16; k++) g16[k] = in[k * 64 + lane];
-#pragma unroll
-    for (int k = 0; k < 12; k++) g12[k] = g16[k];
-#pragma unroll
-    for (int k = 0; k < 4; k++) g4[k] = g16[k];
-    out16[lane] = wave_reduce16d(g16);
-    out12[lane] = wave_reduce12d(g12);
-    out4[lane] = wave_reduce4(g4);
-    comp16[lane] = wave_reduce16d_comp(lane);
-    comp12[lane] = wave_reduce12d_comp(lane);
-    comp4[lane] = wave_reduce4_comp(lane);
+// (map_off, track_off) -> the <DO_MAP, DO_POSE> instance: mapping + pose, mapping only, tracking (both off: the callers return first).
+// f(DO_MAP, DO_POSE) takes the two as std::integral_constant types.
+template <class F>
+void with_map_pose(const RenderBwdLightArgs& a, F&& f) {
+    if (!a.map_off && !a.track_off) f(std::true_type(), std::true_type());
+    else if (!a.map_off) f(std::true_type(), std::false_type());
+    else f(std::false_type(), std::true_type());
 }
-
-// self-test of the reductions per HALF of the wave (wave_reduce.h): in[c * 64 + lane], twelve values for the paired step of the
-// mapping backward (r0, r1 and the butterfly slot each lane holds), the first three for the tracking backward's half_reduce3
-__global__ void __launch_bounds__(64) half_reduce_test_kernel(const float* in, float* r0, float* r1, float* h3, int* slot0, int* slot1,
-                                                             int* comp3) {
-    const int lane = threadIdx.x;
-    float g[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) g[k] = in[k * 64 + lane];
-    h3[lane] = half_reduce3(g[0], g[1], g[2]);
-    float u0, u1;
-    wave_reduce12d_head(g, u0, u1);
-    r0[lane] = quad_sum(u0);
-    r1[lane] = quad_sum(u1);
-    slot0[lane] = wave_reduce12d_half_slot0(lane);
-    slot1[lane] = wave_reduce12d_half_slot1(lane);
-    comp3[lane] = half_reduce3_comp(lane);
+template <int AM, bool DET, bool LEAN, bool BY_FRAME>
+void launch_bwd_light_instance(const RenderBwdLightArgs& a, int tiles, hipStream_t stream) {
+    with_map_pose(a, [&](auto do_map, auto do_pose) {
+        launch_blend((render_bwd_light_kernel<AM, decltype(do_map)::value, decltype(do_pose)::value, DET, LEAN, BY_FRAME>), dim3(tiles), dim3(256), stream, a);
+    });
 }
-
-// ... and of the sixteen-value network stopped before its cross-half stage (the paired step of the FULL backward): in[c * 64 + lane]
-__global__ void __launch_bounds__(64) half_reduce16_test_kernel(const float* in, float* r0, float* r1, int* slot0, int* slot1) {
-    const int lane = threadIdx.x;
-    float g[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) g[k] = in[k * 64 + lane];
-    float u0, u1;
-    wave_reduce16d_head(g, u0, u1);
-    r0[lane] = quad_sum(u0);
-    r1[lane] = quad_sum(u1);
-    slot0[lane] = wave_reduce16d_half_slot0(lane);
-    slot1[lane] = wave_reduce16d_half_slot1(lane);
-}
-
-// self-test of the list builders of render_common.h on one batch of 128 staged slots: codes[slot] = the eight bits "half h of
-// quadrant wave w" (bit 2 w + h).  paired[w] / halves[w] (280 words each) = {steps or length, split[0] lo, hi, split[1] lo, hi,
-// list 2 w [0..135], list 2 w + 1 [0..135]} as wave w leaves them (dgr_debug_lane_lists).
-__global__ void __launch_bounds__(256) lane_lists_test_kernel(const unsigned char* codes, uint32_t* paired, uint32_t* halves) {
-    typedef StagedT<128, uint32_t, 8> S;
-    __shared__ S s;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const unsigned code = tid < 128 ? codes[tid] : 0u;
-    for (int pass = 0; pass < 2; pass++) {
-        for (int i = tid; i < 8 * S::LIST_LD; i += 256) (&s.list[0][0])[i] = 0xFFFFFFFFu;
-        __syncthreads();
-        unsigned long long split[2] = {0ull, 0ull};
-        const int n = pass == 0 ? build_paired_lists(s, code, tid, wave, lane, split) : build_half_lists(s, code, tid, wave, lane);
-        uint32_t* const o = (pass == 0 ? paired : halves) + 280 * wave;
-        if (lane == 0) {
-            o[0] = (uint32_t)n;
-            o[1] = (uint32_t)split[0]; o[2] = (uint32_t)(split[0] >> 32);
-            o[3] = (uint32_t)split[1]; o[4] = (uint32_t)(split[1] >> 32);
-        }
-        for (int i = lane; i < S::LIST_LD; i += 64) {
-            o[5 + i] = s.list[2 * wave][i];
-            o[5 + S::LIST_LD + i] = s.list[2 * wave + 1][i];
-        }
-        __syncthreads();
-    }
-}
-
-// self-test of exact_math.h: out_exp[i] = exp_p32(x[i]) (GLIBC: exp_glibc), out_div[i] = div_ref(a[i], b[i]) (dgr_debug_exact_math)
-template <bool GLIBC>
-__global__ void __launch_bounds__(256) exact_math_test_kernel(int n, const float* x, const float* a, const float* b, float* out_exp,
-                                                             float* out_div) {
-    __shared__ uint64_t tab[32];
-    exp_ref_table_fill(tab, threadIdx.x);
-    __syncthreads();
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        // (the clamped forms: equal to the plain ones down to -104, 0 below)
-        out_exp[i] = GLIBC ? exp_glibc<true>(x[i], tab) : exp_p32<true>(x[i]);
-        float inv;
-        out_div[i] = t_div<ALPHA_REF>(a[i], b[i], inv);
-    }
+// (absgrad: the mapping instances only, so DO_MAP is ignored.  The caller returns under map_off; with_map_pose's third branch, which
+//  would be tracking, therefore never runs, and what it instantiates -- DO_POSE = true -- is the first branch's instance: no new kernel)
+template <int AM, bool LEAN>
+void launch_bwd_light_abs_instance(const RenderBwdLightArgs& a, float* abs_out, int tiles, hipStream_t stream) {
+    with_map_pose(a, [&](auto, auto do_pose) {
+        launch_blend((render_bwd_light_abs_kernel<AM, decltype(do_pose)::value, LEAN, true>), dim3(tiles), dim3(256), stream, a, abs_out);
+    });
 }
 
 template <int AM>
 void launch_bwd_light_mode(const RenderBwdLightArgs& a, int tiles, hipStream_t stream) {
     // (the lane lists -- half-wave / paired or per quadrant -- are the frame's own choice: render_bwd_light_kernel)
-    if (AM == ALPHA_REF && !a.det_rows && !a.dL_dpix_median && !a.dL_dpix_var) {
-        if (!a.map_off && !a.track_off)
-            launch_blend((render_bwd_light_kernel<ALPHA_REF, true, true, false, true, true>), dim3(tiles), dim3(256), stream, a);
-        else if (!a.map_off)
-            launch_blend((render_bwd_light_kernel<ALPHA_REF, true, false, false, true, true>), dim3(tiles), dim3(256), stream, a);
-        else
-            launch_blend((render_bwd_light_kernel<ALPHA_REF, false, true, false, true, true>), dim3(tiles), dim3(256), stream, a);
-        return;
-    }
-    if (AM == ALPHA_REF && a.det_rows) {
-        if (!a.map_off && !a.track_off)
-            launch_blend((render_bwd_light_kernel<ALPHA_REF, true, true, true>), dim3(tiles), dim3(256), stream, a);
-        else if (!a.map_off)
-            launch_blend((render_bwd_light_kernel<ALPHA_REF, true, false, true>), dim3(tiles), dim3(256), stream, a);
-        else
-            launch_blend((render_bwd_light_kernel<ALPHA_REF, false, true, true>), dim3(tiles), dim3(256), stream, a);
-        return;
-    }
     constexpr bool BF = AM != ALPHA_GLIBC;  // (the glibc form, an A/B mode, spills a register with the eight lists: quadrant lists)
-    if (!a.map_off && !a.track_off)
-        launch_blend((render_bwd_light_kernel<AM, true, true, false, false, BF>), dim3(tiles), dim3(256), stream, a);
-    else if (!a.map_off)
-        launch_blend((render_bwd_light_kernel<AM, true, false, false, false, BF>), dim3(tiles), dim3(256), stream, a);
-    else
-        launch_blend((render_bwd_light_kernel<AM, false, true, false, false, BF>), dim3(tiles), dim3(256), stream, a);
+    if (AM == ALPHA_REF && a.det_rows) launch_bwd_light_instance<ALPHA_REF, true, false, false>(a, tiles, stream);
+    else if (AM == ALPHA_REF && !a.dL_dpix_median && !a.dL_dpix_var) launch_bwd_light_instance<ALPHA_REF, false, true, true>(a, tiles, stream);
+    else launch_bwd_light_instance<AM, false, false, BF>(a, tiles, stream);
 }
 }  // namespace
 
@@ -798,18 +651,10 @@ hipError_t launch_render_bwd_light_abs(const RenderBwdLightArgs& a, float* dL_dm
     if (tiles <= 0 || a.map_off) return hipSuccess;
     const bool lean = !a.dL_dpix_median && !a.dL_dpix_var;
     // (the instances of launch_bwd_light_mode's non-deterministic mapping branches)
-    if (alpha_mode == ALPHA_FAST) {
-        if (!a.track_off) launch_blend((render_bwd_light_abs_kernel<ALPHA_FAST, true, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
-        else launch_blend((render_bwd_light_abs_kernel<ALPHA_FAST, false, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
-    } else if (alpha_mode == ALPHA_REF && lean) {
-        if (!a.track_off) launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, true, true, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
-        else launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, false, true, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
-    } else if (alpha_mode == ALPHA_REF) {
-        if (!a.track_off) launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, true, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
-        else launch_blend((render_bwd_light_abs_kernel<ALPHA_REF, false, false, true>), dim3(tiles), dim3(256), stream, a, dL_dmean2D_abs);
-    } else {
-        return hipErrorInvalidValue;  // (alpha_mode 2: refused by the entry points)
-    }
+    if (alpha_mode == ALPHA_FAST) launch_bwd_light_abs_instance<ALPHA_FAST, false>(a, dL_dmean2D_abs, tiles, stream);
+    else if (alpha_mode == ALPHA_REF && lean) launch_bwd_light_abs_instance<ALPHA_REF, true>(a, dL_dmean2D_abs, tiles, stream);
+    else if (alpha_mode == ALPHA_REF) launch_bwd_light_abs_instance<ALPHA_REF, false>(a, dL_dmean2D_abs, tiles, stream);
+    else return hipErrorInvalidValue;  // (alpha_mode 2: refused by the entry points)
     return hipGetLastError();
 }
 namespace {
@@ -836,32 +681,4 @@ hipError_t launch_det_gather(int P, const ushort4* rect, const uint32_t* goff, c
     launch(det_gather_kernel, dim3((P + 15) / 16), dim3(256), stream, P, rect, goff, rows, R, acc);
     return hipGetLastError();
 }
-hipError_t launch_exact_math_test(int n, const float* x, const float* a, const float* b, float* out_exp, float* out_div,
-                                  int alpha_mode, hipStream_t stream) {
-    if (n <= 0) return hipSuccess;
-    if (alpha_mode == ALPHA_GLIBC)
-        launch(exact_math_test_kernel<true>, dim3(min((n + 255) / 256, 4096)), dim3(256), stream, n, x, a, b, out_exp, out_div);
-    else
-        launch(exact_math_test_kernel<false>, dim3(min((n + 255) / 256, 4096)), dim3(256), stream, n, x, a, b, out_exp, out_div);
-    return hipGetLastError();
-}
-hipError_t launch_wave_reduce_test(const float* in, float* out16, float* out12, float* out4, int* comp16, int* comp12, int* comp4,
-                                   hipStream_t stream) {
-    launch(wave_reduce_test_kernel, dim3(1), dim3(64), stream, in, out16, out12, out4, comp16, comp12, comp4);
-    return hipGetLastError();
-}
-
-hipError_t launch_half_reduce_test(const float* in, float* r0, float* r1, float* h3, int* slot0, int* slot1, int* comp3, hipStream_t stream) {
-    launch(half_reduce_test_kernel, dim3(1), dim3(64), stream, in, r0, r1, h3, slot0, slot1, comp3);
-    return hipGetLastError();
-}
-hipError_t launch_half_reduce16_test(const float* in, float* r0, float* r1, int* slot0, int* slot1, hipStream_t stream) {
-    launch(half_reduce16_test_kernel, dim3(1), dim3(64), stream, in, r0, r1, slot0, slot1);
-    return hipGetLastError();
-}
-hipError_t launch_lane_lists_test(const unsigned char* codes, uint32_t* paired, uint32_t* halves, hipStream_t stream) {
-    launch(lane_lists_test_kernel, dim3(1), dim3(256), stream, codes, paired, halves);
-    return hipGetLastError();
-}
-
 }  // namespace dgr
