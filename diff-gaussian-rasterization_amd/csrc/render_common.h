@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "wave_reduce.h"
 #include "exact_math.h"
+#include <type_traits>
 
 namespace dgr {
 
@@ -20,16 +21,53 @@ namespace dgr {
 // it per frame (segment_binning.hip) and forward and backward of the frame take the same uniform branch on it.
 // The flags ride in this word because the status word itself is no place to read from here: the full forward's workgroups add their valid-pair counts to
 // status[3] with atomics as they finish, and a load of that line queues behind them -- 34 -> 60 us for render_fwd at config 2.
-__device__ __forceinline__ uint4 blend_slot(const uint4* __restrict__ sched, const uint2* __restrict__ ranges,
-                                            const uint32_t* __restrict__ sched_flag, int tiles, bool* overflowed = nullptr,
-                                            bool* quadrant_lists = nullptr) {
-    const int flag = __builtin_amdgcn_readfirstlane((int)*sched_flag);
-    if (overflowed) *overflowed = (flag & 2) != 0;
-    if (quadrant_lists) *quadrant_lists = (flag & 4) != 0;
-    if (flag & 1) return sched[blockIdx.x];
+enum { BLEND_FLAG_SCHEDULE = 1, BLEND_FLAG_OVERFLOWED = 2, BLEND_FLAG_QUADRANT_LISTS = 4 };
+__device__ __forceinline__ int blend_flags(const uint32_t* __restrict__ sched_flag) { return __builtin_amdgcn_readfirstlane((int)*sched_flag); }
+__device__ __forceinline__ uint4 blend_slot(int flag, const uint4* __restrict__ sched, const uint2* __restrict__ ranges, int tiles) {
+    if (flag & BLEND_FLAG_SCHEDULE) return sched[blockIdx.x];
     const int tile = xcd_contiguous((int)blockIdx.x, tiles);
     const uint2 r = ranges[tile];
     return make_uint4((uint32_t)tile, r.x, r.y, 0u);
+}
+__device__ __forceinline__ uint4 blend_slot(const uint4* __restrict__ sched, const uint2* __restrict__ ranges,
+                                            const uint32_t* __restrict__ sched_flag, int tiles, bool* overflowed = nullptr,
+                                            bool* quadrant_lists = nullptr) {
+    const int flag = blend_flags(sched_flag);
+    if (overflowed) *overflowed = (flag & BLEND_FLAG_OVERFLOWED) != 0;
+    if (quadrant_lists) *quadrant_lists = (flag & BLEND_FLAG_QUADRANT_LISTS) != 0;
+    return blend_slot(flag, sched, ranges, tiles);
+}
+
+// An element at a 32-bit BYTE offset from a pointer.  With a workgroup-uniform `base` the address is a scalar register pair plus one
+// vector register (the global instructions' saddr form); `base[i]` with a 64-bit or scaled index costs 64-bit vector arithmetic
+// (v_lshl_add_u64 and register-pair copies) per access, in kernels whose cost is their vector instruction count.
+template <class T>
+__device__ __forceinline__ T& at_byte(T* base, uint32_t byte_off) {
+    return *reinterpret_cast<T*>(reinterpret_cast<char*>(const_cast<std::remove_const_t<T>*>(base)) + byte_off);
+}
+
+// The same from a workgroup-uniform pointer that is worked out INSIDE a loop (base + list start + batch): the pointer is made opaque
+// first.  Without that the compiler splits `base + uniform + lane` the other way round, hoists `base + lane` out of the loop as a
+// 64-bit vector pair (two registers held through the pair loop, or spilled) and adds the uniform part with v_lshl_add_u64 per
+// access.  What comes out of the asm has lost its address space, so it is named again (global memory): a flat access otherwise.
+// The pointer must be uniform and point to global memory; T a built-in type.
+#define DGR_GLOBAL __attribute__((address_space(1)))
+template <class T>
+__device__ __forceinline__ T DGR_GLOBAL* global_at(T* uniform_ptr, uint32_t byte_off) {
+    asm volatile("" : "+s"(uniform_ptr));
+    return (T DGR_GLOBAL*)((char DGR_GLOBAL*)uniform_ptr + byte_off);
+}
+
+// The calling kernel's argument block (its single by-value argument ARGS), to be read where the values are USED.  Members of the
+// by-value argument itself are loaded wherever the compiler likes -- for a blend kernel at the top, from where they stay in scalar
+// registers (or their spill lanes) through every loop.  The empty asm makes the block's address opaque, so that loads through it
+// stay behind this point; they are still scalar loads from the constant address space.
+template <class ARGS>
+__device__ __forceinline__ const ARGS __attribute__((address_space(4)))* late_kernel_args() {
+    typedef const ARGS __attribute__((address_space(4)))* P;
+    P p = (P)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
 }
 
 // wave-uniform "any lane": one v_cmp into an SGPR pair + s_cmp (HIP's __any() goes through v_cndmask + v_cmp)
@@ -85,8 +123,8 @@ __device__ __forceinline__ float t_div(float T, float om, float& inv) {
 // backward kernels: two entries arrive as one 8-byte read, ready to be used as addresses -- parting two 16-bit halves costs a
 // v_lshrrev_b32 at 4.2 cycles and a mask at 2.4 per two entries, in loops bound by vector issue).
 // NLISTS = 4: one list per quadrant wave; 8: one per HALF of a quadrant (lanes 0-31 = its upper four pixel rows, 32-63 = its
-// lower four: build_half_lists) -- the light forward.  KEEP_ID = false: the Gaussian ids are not kept in LDS (the light forward
-// re-reads them from the tile list when it writes the tags back).
+// lower four: build_half_lists) -- the light forward.  KEEP_ID = false: the Gaussian ids are not kept in LDS (the light forward:
+// a staging thread keeps its instance's id in a register until it flushes the slot).
 template <int NB, typename LIST_T = unsigned short, int NLISTS = 4, bool KEEP_ID = true>
 struct StagedT {
     typedef LIST_T list_t;

@@ -43,10 +43,12 @@ namespace {
 // ================================================================================ forward
 constexpr int FWD_UNROLL = 2;  // list entries per loop iteration (4 was measured: no faster, more registers)
 
-// HALVES: eight lists, one per half of a quadrant (render_common.h: build_half_lists); the ids stay out of LDS to keep 8 workgroups per CU
+// HALVES: eight lists, one per half of a quadrant (render_common.h: build_half_lists); the ids stay out of LDS (8 workgroups per CU):
+// a thread keeps the id of the instance it staged in a register until it flushes the slot
 template <bool HALVES>
 struct StagedFwd {
-    typedef StagedT<DGR_TILE_PIX, unsigned short, HALVES ? 8 : 4, !HALVES> staged_t;
+    typedef StagedT<DGR_TILE_PIX, unsigned short, HALVES ? 8 : 4, false> staged_t;
+    static constexpr bool HALF_LISTS = HALVES;
     staged_t f;
     float unc[DGR_TILE_PIX];   // per staged instance: sum of (d - gt)^2 alpha T over its median pixels (forward.cu:386)
     uint32_t cnt[DGR_TILE_PIX];
@@ -58,40 +60,44 @@ struct StagedFwd {
 // Per-slot results of the batch staged at position `pos0` of the tile list that starts at `list0`: the median statistics go to the
 // Gaussian, the contribution tag into the entry's tag byte (render_common.h), and the entries somebody blended -- tag != 0 -- go,
 // compacted in list order, to the tile's live list from `live_base` on (render_common.h: live_list): a ballot and mbcnt per
-// wave, the four waves' counts through LDS.  Every thread of the workgroup calls it (one barrier); returns the new live_base.
+// wave, the four waves' counts through LDS.  Every thread of the workgroup calls it, once per batch, behind the barrier that ends the
+// batch's pair loop; returns the new live_base.
+// `gid`: the Gaussian the calling thread staged in its slot -- kept in a register since the staging, so that nothing here waits for
+// memory (a re-read of the tile list behind the barrier put its latency at the end of every workgroup).
+// Its one barrier also takes the workgroup's vote "every pixel finished" (`my_done` -> `all_done`: L/cuda_rasterizer/forward.cu:329-332),
+// so a batch costs no barrier of its own for that.
+// Addresses: a workgroup-uniform 64-bit base (scalar arithmetic) and a 32-bit byte offset per lane -- no 64-bit vector adds.
 template <class SF>
 __device__ __forceinline__ uint32_t flush_slot(SF& sf, const RenderFwdLightArgs& a, uint8_t* tag8, uint2* live, uint32_t list0, uint32_t pos0,
-                                               uint32_t live_base, int tid, bool staged) {
+                                               uint32_t live_base, int tid, bool staged, uint32_t gid, bool my_done, bool& all_done) {
     uint32_t t8 = 0u;  // bit 2 w <- upper half of wave w, bit 2 w + 1 <- its lower half
     if (staged) {
-        if constexpr (!SF::staged_t::HAS_ID) {  // (the half-wave body) lower halves: the bytes of the record's third word
+        if constexpr (SF::HALF_LISTS) {  // (the half-wave body) lower halves: the bytes of the record's third word
             t8 = tag_byte(sf.hit[tid], __float_as_uint(sf.f.rec[2 * tid + 1].z));
-        } else {                                // (the quadrant body) a quadrant's tag stands for both of its halves
+        } else {                         // (the quadrant body) a quadrant's tag stands for both of its halves
             t8 = spread4(pack4(sf.hit[tid])) * 3u;
         }
-        tag8[list0 + pos0 + tid] = (uint8_t)t8;  // every staged entry, blended or not: the byte underneath is the binning's
+        *global_at(tag8 + (size_t)(list0 + pos0), (uint32_t)tid) = (uint8_t)t8;  // every staged entry, blended or not: the byte underneath is the binning's
     }
     const unsigned long long bal = __ballot(t8 != 0u);
     if ((tid & 63) == 0) sf.live4[tid >> 6] = (uint32_t)__popcll(bal);
-    __syncthreads();
+    all_done = __syncthreads_and(my_done);
     const uint4 c = *reinterpret_cast<const uint4*>(sf.live4);
     if (t8 != 0u) {
         const int wave = tid >> 6;
         const uint32_t before = (wave > 0 ? c.x : 0u) + (wave > 1 ? c.y : 0u) + (wave > 2 ? c.z : 0u);
-        uint32_t gid;
-        if constexpr (SF::staged_t::HAS_ID) gid = sf.f.id[tid];
-        else gid = a.point_list[list0 + pos0 + tid];
-        live[list0 + live_base + before + (uint32_t)lanes_below(bal)] = make_uint2(gid, ((pos0 + (uint32_t)tid) << 8) | t8);
+        *global_at(reinterpret_cast<unsigned long long*>(live + (size_t)(list0 + live_base)), (before + (uint32_t)lanes_below(bal)) * 8u) =
+            (unsigned long long)gid | ((unsigned long long)(((pos0 + (uint32_t)tid) << 8) | t8) << 32);  // {id, position << 8 | tag}
         if (sf.cnt[tid] != 0u) {                // (a median pixel blended it: it has a tag)
-            atomicAdd(&a.gau_uncertainty[gid], sf.unc[tid]);
-            atomicAdd(&a.gau_related_pixels[gid], (int)sf.cnt[tid]);
+            atomicAdd(&at_byte(a.gau_uncertainty, gid * 4u), sf.unc[tid]);  // (ids stay below 2^28: render_common.h)
+            atomicAdd(&at_byte(a.gau_related_pixels, gid * 4u), (int)sf.cnt[tid]);
         }
     }
     return live_base + (uint32_t)__builtin_amdgcn_readfirstlane((int)(c.x + c.y + c.z + c.w));
 }
 
 template <int AM, bool HALVES>
-__device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& a, StagedFwd<HALVES>& sf, const uint4 slot, const bool overflowed) {
+__device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& a, StagedFwd<HALVES>& sf, const uint4 slot, const int frame_flags) {
     typename StagedFwd<HALVES>::staged_t& s = sf.f;
     const int tile = (int)slot.x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -103,6 +109,7 @@ __device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& 
     uint8_t* const tag8 = half_tags(a.point_list, a.sched_flag);
     uint2* const live = live_list(a.point_list, a.sched_flag);
     uint32_t live_base = 0;  // live entries of this tile written so far (workgroup-uniform)
+    uint32_t my_gid = 0;     // the Gaussian this thread staged in slot tid (flush_slot)
     unsigned char* const mark_base = (HALVES && lane >= 32) ? reinterpret_cast<unsigned char*>(&s.rec[1].z) + wave
                                                              : reinterpret_cast<unsigned char*>(sf.hit) + wave;
     const int mark_stride = (HALVES && lane >= 32) ? 32 : 4;
@@ -115,25 +122,23 @@ __device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& 
     // "done" as a per-lane upper bound on p2: live pixels accept p2 <= 0 (the reference's `power > 0` test),
     // finished pixels compare against -inf and accept nothing
     float ub = inside ? 0.f : -__builtin_inff();
-    const float gt_px = inside ? a.gt_depth[pix_id] : 0.f;
+    const float gt_px = inside ? at_byte(a.gt_depth, pix_id * 4u) : 0.f;  // (4 W H <= 2^32: tile_pixel)
     if (tid == 0) write_sentinel(s);
     if (AlphaPath<AM>::TABLE) exp_ref_table_fill(sf.exptab, tid);  // (visible after the first batch's barriers)
-    bool have_flush = false;
-    int last_base = 0;
 
-    for (int base = 0; base < total; base += DGR_TILE_PIX) {
-        // whole tile finished?  (L/cuda_rasterizer/forward.cu:329-332)
-        if (__syncthreads_and(ub < 0.f)) break;
-        last_base = base;
-        // median statistics of the previous batch: slot tid is flushed by the thread that restages it
-        if (have_flush) live_base = flush_slot(sf, a, tag8, live, range.x, (uint32_t)(base - DGR_TILE_PIX), live_base, tid, true);  // (an earlier batch is always full)
-        sf.unc[tid] = 0.f;
+    // (every tile has a pixel inside the frame, so no tile is finished before its first batch: the vote "whole tile finished",
+    //  L/cuda_rasterizer/forward.cu:329-332, is taken behind each batch -- in flush_slot's barrier -- for the next one)
+    int base = 0;
+    while (base < total) {
+        sf.unc[tid] = 0.f;  // (slot tid: flushed by this thread, below, before it restages it)
         sf.cnt[tid] = 0u;
         sf.hit[tid] = 0u;
-        have_flush = true;
-        const int cnt = min(DGR_TILE_PIX, total - base);
+        const int cnt = total - base;  // (the batch holds min(256, cnt))
         unsigned code = 0;
-        if (tid < cnt) code = stage_one<AM, HALVES>(s, tid, a.point_list[range.x + base + tid], a.rec, tile_x0, tile_y0);
+        if (tid < cnt) {
+            my_gid = *global_at(a.point_list + (size_t)(range.x + (uint32_t)base), (uint32_t)tid * 4u);
+            code = stage_one<AM, HALVES>(s, tid, my_gid, a.rec, tile_x0, tile_y0);
+        }
         const int n = HALVES ? build_half_lists(s, code, tid, wave, lane) : build_lists(s, code, tid, wave, lane);
 
         for (int k = 0; k < n; k += FWD_UNROLL) {
@@ -172,30 +177,46 @@ __device__ __forceinline__ void render_fwd_light_body(const RenderFwdLightArgs& 
             }
             if (!wave_any(ub >= 0.f)) break;
         }
+        __syncthreads();  // the batch's marks and median statistics are complete
+        bool all_done;
+        live_base = flush_slot(sf, a, tag8, live, range.x, (uint32_t)base, live_base, tid, tid < cnt, my_gid, ub < 0.f, all_done);
+        base += DGR_TILE_PIX;
+        if (all_done) break;
     }
-    __syncthreads();
-    if (have_flush) live_base = flush_slot(sf, a, tag8, live, range.x, (uint32_t)last_base, live_base, tid, tid < total - last_base);
     // (an empty tile, the empty lists of an overflowed frame, a tile that finished early: what was flushed, 0 if nothing was)
-    if (tid == 0) a.live_counts[tile] = live_base;
+    // (written by the LAST thread: `tid == 0` is the sentinel's test at the top, and the compiler would carry that lane mask through the loops -- in spill lanes)
+    if (tid == DGR_TILE_PIX - 1) a.live_counts[tile] = live_base;
     // the tail of a list whose tile finished early was never staged: nobody blended it (render_common.h: the tag bytes' invariant)
-    for (int p = (have_flush ? last_base + DGR_TILE_PIX : 0) + tid; p < total; p += DGR_TILE_PIX) tag8[range.x + p] = 0;
+    for (int p = base + tid; p < total; p += DGR_TILE_PIX) at_byte(tag8 + (size_t)range.x, (uint32_t)p) = 0;
 
     // A forward whose binning buffer was too small has rendered EMPTY tile lists (bin_tiles left every range {0, 0}): in lazy mode
     // the host learns of it a call or two later, so the images must not look like a frame -- they are NaN, every value
-    // (strict mode retries inside the call and overwrites them).  The flag came with the schedule word (blend_slot): a uniform branch.
-    if (overflowed) {
+    // (strict mode retries inside the call and overwrites them).  The flag came with the schedule word (blend_slot): a uniform branch,
+    // on the word itself -- one scalar register through the loops, where a bool is a lane mask in two.
+    if (frame_flags & BLEND_FLAG_OVERFLOWED) {
         C0 = C1 = C2 = weight = Dd = D_median = __builtin_nanf("");
     }
     if (inside) {
-        const uint32_t N = (uint32_t)a.W * (uint32_t)a.H;
-        a.n_contrib[pix_id] = last_contributor;
-        a.out_color[pix_id] = C0 + T * a.bg[0];
-        a.out_color[N + pix_id] = C1 + T * a.bg[1];
-        a.out_color[2 * N + pix_id] = C2 + T * a.bg[2];
-        a.out_alpha[pix_id] = weight;  // forward.cu:407
-        a.out_depth[pix_id] = Dd;
-        a.out_median[pix_id] = D_median;
-        a.out_depth_var[pix_id] = 0.0f;  // forward.cu:317,410
+        // The image pointers are needed here and nowhere else: read from the kernel's argument block HERE (late_kernel_args), they
+        // occupy no scalar registers through the batch loop -- loaded at the top, as the compiler does with `a`'s own members,
+        // sixteen of them were spilled to the lanes of a vector register and read back one by one.
+        const auto ka = late_kernel_args<RenderFwdLightArgs>();
+        const size_t N = (size_t)((uint32_t)a.W * (uint32_t)a.H);
+        // the pixel's byte offset, worked out again from the coordinates the pair loop keeps as floats (exact: below 2^24) rather than
+        // carried through the loops in a register of its own -- the kernel has none to spare (opaque, or the compiler carries it)
+        float fx = pxy.x, fy = pxy.y;
+        asm volatile("" : "+v"(fx), "+v"(fy));
+        const uint32_t po = ((uint32_t)fy * (uint32_t)a.W + (uint32_t)fx) * 4u;  // (4 W H <= 2^32: tile_pixel)
+        float* const out_color = ka->out_color;
+        const float* const bg = ka->bg;
+        at_byte(ka->n_contrib, po) = last_contributor;
+        at_byte(out_color, po) = C0 + T * bg[0];
+        at_byte(out_color + N, po) = C1 + T * bg[1];
+        at_byte(out_color + 2 * N, po) = C2 + T * bg[2];
+        at_byte(ka->out_alpha, po) = weight;  // forward.cu:407
+        at_byte(ka->out_depth, po) = Dd;
+        at_byte(ka->out_median, po) = D_median;
+        at_byte(ka->out_depth_var, po) = 0.0f;  // forward.cu:317,410
     }
 }
 
@@ -207,10 +228,10 @@ template <int AM>
 __global__ void __launch_bounds__(256, 8) render_fwd_light_kernel(RenderFwdLightArgs a) {
     __shared__ union { StagedFwd<true> h; StagedFwd<false> q; } sf;
     if (a.rep.host && blockIdx.x == 0 && threadIdx.x == 0) report_status(a.rep, a.status);
-    bool overflowed, quadrant_lists;
-    const uint4 slot = blend_slot(a.sched, a.ranges, a.sched_flag, a.grid_x * a.grid_y, &overflowed, &quadrant_lists);  // {tile, list start, list end}
-    if (quadrant_lists) render_fwd_light_body<AM, false>(a, sf.q, slot, overflowed);
-    else render_fwd_light_body<AM, true>(a, sf.h, slot, overflowed);
+    const int frame_flags = blend_flags(a.sched_flag);
+    const uint4 slot = blend_slot(frame_flags, a.sched, a.ranges, a.grid_x * a.grid_y);  // {tile, list start, list end}
+    if (frame_flags & BLEND_FLAG_QUADRANT_LISTS) render_fwd_light_body<AM, false>(a, sf.q, slot, frame_flags);
+    else render_fwd_light_body<AM, true>(a, sf.h, slot, frame_flags);
 }
 
 // ================================================================================ backward
@@ -348,8 +369,16 @@ __device__ __forceinline__ void render_bwd_light_body(const RenderBwdLightArgs& 
     float* const my_acc = sb.acc + (DET ? wave * SB::PLANE : 0) + (my_comp >= 0 ? my_comp : 0) * BWD_LD;
 
     // back-to-front: batches cover the live entries [lo, hi) with hi walking down from `total`
-    for (int hi = total; hi > 0; hi -= BWD_NB) {
-        const int lo = max(0, hi - BWD_NB);
+    // (batches of equal size: 150 live entries go as 75 + 75, not 128 + 22 -- a full batch of LIVE entries leaves about twice the
+    //  entries per quadrant list that 128 positions did, and the pairing pass takes lists of up to 64: profiles/live_lists/notes.md)
+    // (only where lists are paired; any size with nbatch * per >= total serves: the quotient through the float reciprocal, rounded up)
+    int per = BWD_NB;
+    if (PAIRED && total > BWD_NB) {
+        const int nbatch = (total + BWD_NB - 1) / BWD_NB;
+        per = min(BWD_NB, (int)((float)total * __builtin_amdgcn_rcpf((float)nbatch)) + 1);
+    }
+    for (int hi = total; hi > 0; hi -= per) {
+        const int lo = max(0, hi - per);
         const int cnt = hi - lo;
         __syncthreads();  // previous batch fully flushed / consumed
         unsigned code = 0;
