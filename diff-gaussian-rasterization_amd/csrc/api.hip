@@ -1087,6 +1087,56 @@ int dgr_densification_stats(void* stream, long rows, const float* dmeans2D, cons
     return DGR_OK;
 }
 
+size_t dgr_densify_plan_bytes(long rows) { return rows < 0 ? 0 : dgr::densify_plan_bytes((size_t)rows); }
+
+// P' <= 2 rows must fit the int counts
+static const long DENSIFY_MAX_ROWS = 0x3fffffffL;
+
+int dgr_densify_plan(void* stream, long rows, const float* grad_accum, const float* denom, const float* max_radii2D,
+                     const float* opacity_raw, const float* scaling_raw, float grad_threshold, float opacity_raw_min,
+                     float log_scale_split, float log_scale_prune, float max_screen_size, void* plan, int* counts8_device) {
+    const char* bad = nullptr;
+    if (rows < 0 || rows > DENSIFY_MAX_ROWS) bad = "rows must be 0 .. 2^30 - 1";
+    else if (!plan || !dgr::aligned16(plan)) bad = "plan is NULL or not 16-byte aligned";
+    else if (!counts8_device) bad = "counts8_device is NULL";
+    else if (rows > 0 && (!grad_accum || !denom || !opacity_raw || !scaling_raw)) bad = "a NULL input";
+    if (bad) {
+        set_last_error(std::string("dgr_densify_plan: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_densify_plan((size_t)rows, grad_accum, denom, max_radii2D, opacity_raw, scaling_raw, grad_threshold,
+                                     opacity_raw_min, log_scale_split, log_scale_prune, max_screen_size, plan, counts8_device,
+                                     (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_densify_apply(void* stream, long rows, long rows_out, const void* plan, int n, const dgr_densify_tensor* tensors,
+                      const float* scaling_raw, const float* rotation_raw, const float* noise, unsigned long long seed) {
+    const char* bad = nullptr;
+    int n_xyz = 0;
+    if (rows < 0 || rows > DENSIFY_MAX_ROWS) bad = "rows must be 0 .. 2^30 - 1";
+    else if (rows_out < 0 || rows_out > 2 * rows) bad = "rows_out must be 0 .. 2 rows";
+    else if (!plan || !dgr::aligned16(plan)) bad = "plan is NULL or not 16-byte aligned";
+    else if (n < 1 || n > DGR_DENSIFY_MAX_TENSORS) bad = "n must be 1 .. DGR_DENSIFY_MAX_TENSORS (24) tensors";
+    else if (!tensors) bad = "tensors is NULL";
+    for (int i = 0; !bad && i < n; ++i) {
+        const dgr_densify_tensor& t = tensors[i];
+        if (t.k < 1 || t.k > (1 << 22)) bad = "a tensor with k < 1 or k > 2^22";
+        else if (t.mode < DGR_DENSIFY_COPY || t.mode > DGR_DENSIFY_LOG_SCALE) bad = "unknown mode";
+        else if (t.mode == DGR_DENSIFY_XYZ && t.k != 3) bad = "the XYZ tensor must have k = 3";
+        else if (t.mode == DGR_DENSIFY_XYZ && ++n_xyz > 1) bad = "more than one XYZ tensor";
+        else if (rows_out > 0 && (!t.dst || (t.mode != DGR_DENSIFY_ZERO && !t.src))) bad = "a tensor with a NULL src or dst";
+    }
+    if (!bad && n_xyz && rows_out > 0 && (!scaling_raw || !rotation_raw)) bad = "XYZ needs scaling_raw and rotation_raw";
+    if (bad) {
+        set_last_error(std::string("dgr_densify_apply: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_densify_apply((size_t)rows, (size_t)rows_out, plan, n, tensors, scaling_raw, rotation_raw, noise, seed,
+                                      (hipStream_t)stream));
+    return DGR_OK;
+}
+
 int dgr_pose_forward(void* stream, const float* quat, const float* trans, const float* perspec_matrix, float* viewmatrix,
                      float* projmatrix, float* campos) {
     if (!quat || !trans || !perspec_matrix || !viewmatrix || !projmatrix || !campos) {

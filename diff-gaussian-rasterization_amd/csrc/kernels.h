@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_ext.h>
 #include "dgr_common.h"
+#include "../../include/dgr_hip.h"  // dgr_densify_tensor
 
 namespace dgr {
 
@@ -277,6 +278,15 @@ hipError_t launch_densification_stats(int rows, const float* dmeans2D, const int
 hipError_t launch_sparse_adam(size_t rows, int k, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                               const int* visible, float lr, float beta1, float beta2, float eps, int step,
                               const int* step_dev, hipStream_t stream);
+// fused densify-and-prune (optim.hip): decide + scan into `plan` and counts[8] (device), then one apply launch for n tensors
+size_t densify_plan_bytes(size_t rows);
+hipError_t launch_densify_plan(size_t rows, const float* grad_accum, const float* denom, const float* max_radii2D,
+                               const float* opacity_raw, const float* scaling_raw, float grad_threshold,
+                               float opacity_raw_min, float log_scale_split, float log_scale_prune, float max_screen_size,
+                               void* plan, int* counts, hipStream_t stream);
+hipError_t launch_densify_apply(size_t rows, size_t rows_out, const void* plan, int n, const dgr_densify_tensor* tensors,
+                                const float* scaling_raw, const float* rotation_raw, const float* noise,
+                                unsigned long long seed, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -54,7 +54,15 @@ class FullViewGrad(C.Structure):  # dgr_full_view_grad: the per-camera arguments
                 ("scratch", _vp), ("scratch_bytes", _sz), ("num_rendered", _i)]
 
 
+class DensifyTensor(C.Structure):  # dgr_densify_tensor: one per-Gaussian tensor of a dgr_densify_apply call
+    _fields_ = [("src", _vp), ("dst", _vp), ("k", _i), ("mode", _i)]
+
+
+assert C.sizeof(DensifyTensor) == 24  # two pointers, two ints: the C layout
+
 MAX_BATCH_VIEWS = 8  # DGR_MAX_BATCH_VIEWS
+DENSIFY_MAX_TENSORS = 24  # DGR_DENSIFY_MAX_TENSORS
+DENSIFY_COPY, DENSIFY_ZERO_NEW, DENSIFY_ZERO, DENSIFY_XYZ, DENSIFY_LOG_SCALE = range(5)  # DGR_DENSIFY_*
 
 # argument lists follow include/dgr_hip.h one to one
 _SIGS = {
@@ -80,6 +88,9 @@ _SIGS = {
     "dgr_l1_loss_forward": (_i, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _vp, _vp]),
     "dgr_l1_loss_backward": (_i, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
+    "dgr_densify_plan_bytes": (_sz, [C.c_long]),
+    "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
+    "dgr_densify_apply": (_i, [_vp, C.c_long, C.c_long, _vp, _i, C.POINTER(DensifyTensor), _vp, _vp, _vp, C.c_ulonglong]),
     "dgr_sparse_adam": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i]),
     "dgr_sparse_adam_capturable": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
     "dgr_set_option": (_i, [C.c_char_p, _i]),

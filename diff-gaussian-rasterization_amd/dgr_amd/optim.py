@@ -3,7 +3,14 @@
 `torch.optim.Adam` semantics (no weight decay, no amsgrad) with one HIP launch per tensor through the C ABI
 (`dgr_sparse_adam`, csrc/optim.hip).  `step(visible=radii)` updates only the Gaussians some view saw -- parameter and
 both moments of the other rows are left untouched, as in 3DGS's sparse Adam; `step()` updates every row.
+
+`densify_and_prune` is the step that changes P: 3DGS's densify_and_clone, densify_and_split and prune_points over every
+leaf, Adam moment and accumulator in three launches (`dgr_densify_plan`, `dgr_densify_apply`) and one host read.
 """
+import collections
+import ctypes
+import math
+
 import torch
 
 from . import _capi
@@ -27,6 +34,119 @@ def add_densification_stats(dmeans2D, radii, xyz_gradient_accum=None, denom=None
                                               ptr(max_radii2D))
     if rc:
         raise RuntimeError(_capi.last_error())
+
+
+DensifyCounts = collections.namedtuple("DensifyCounts", "rows survivors clones children split")
+DEFAULT_ROLES = {"xyz": "xyz", "scaling": "scaling", "rotation": "rotation", "opacity": "opacity"}
+
+
+def densify_thresholds(grad_threshold, extent, percent_dense=0.01, min_opacity=0.005, max_screen_size=None):
+    """The five fp32 thresholds of `dgr_densify_plan`, formed in float64 (ctypes rounds each once to fp32): grad_threshold,
+    logit(min_opacity), log(percent_dense * extent), log(0.1 * extent) and max_screen_size -- the last two +inf when
+    max_screen_size is None (neither size rule prunes then)."""
+    inf = float("inf")
+    logit = -inf if min_opacity <= 0 else inf if min_opacity >= 1 else math.log(min_opacity / (1.0 - min_opacity))
+    sized = max_screen_size is not None
+    return (float(grad_threshold), logit, math.log(percent_dense * extent), math.log(0.1 * extent) if sized else inf,
+            float(max_screen_size) if sized else inf)
+
+
+def _rows_tensor(t, P, what):
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() < 1 or t.shape[0] != P:
+        raise RuntimeError(f"densify_and_prune: {what} must be a float32 GPU tensor with {P} rows")
+    return t.detach().contiguous()
+
+
+@torch.no_grad()
+def densify_and_prune(params, optimizer, xyz_gradient_accum, denom, max_radii2D, *, grad_threshold, extent,
+                      percent_dense=0.01, min_opacity=0.005, max_screen_size=None, noise=None, seed=0, roles=None):
+    """3DGS's densify_and_prune (clone, split into two, prune) over the whole model, fused (include/dgr_hip.h:
+    dgr_densify_plan / dgr_densify_apply; the semantics are stated there).
+
+    `params`: dict name -> leaf [P, ...]; `roles` says which names are the xyz [P,3], scaling [P,3] (log of scale), rotation
+    [P,4] (r, x, y, z) and opacity [P] or [P,1] (logit) leaves, default {"xyz": "xyz", ...}; every other entry is copied
+    row-wise.  `optimizer`: a SparseAdam over those leaves (or None): surviving rows keep their moments, new rows start
+    from zero, the step count stays, and the optimiser is pointed at the new leaves (`replace_params`).  The accumulators
+    are float32 tensors of P elements; `max_radii2D` may be None.  `noise`: [P, 2, 3] standard normals for the two children
+    of each ORIGINAL row, or None for the kernel's own generator keyed by `seed`.
+
+    Returns (new params dict, xyz_gradient_accum, denom, max_radii2D, DensifyCounts): leaves with `requires_grad`
+    preserved, the three accumulators as zeros of the new length.  One host synchronisation (the read of the counts), so
+    the call cannot be recorded into a hipGraph."""
+    lib = _capi.load()
+    roles = dict(DEFAULT_ROLES, **(roles or {}))
+    missing = [r for r in DEFAULT_ROLES if roles[r] not in params]
+    if missing:
+        raise KeyError(f"densify_and_prune: params has no entry for {missing} (roles = {roles})")
+    xyz = params[roles["xyz"]]
+    if not xyz.is_cuda:
+        raise RuntimeError("densify_and_prune: the parameters must live on the GPU")
+    P, dev = xyz.shape[0], xyz.device
+    with _capi.on_device(dev):
+        st = _capi.stream_handle(dev.index)
+        if lib.dgr_stream_is_capturing(st):
+            raise RuntimeError("densify_and_prune changes the number of Gaussians and reads the new count on the host: it cannot "
+                               "be recorded into a hipGraph (call it between replays)")
+        src = {name: _rows_tensor(t, P, f"params[{name!r}]") for name, t in params.items()}
+        for role, shape in (("xyz", (P, 3)), ("scaling", (P, 3)), ("rotation", (P, 4))):
+            if tuple(src[roles[role]].shape) != shape:
+                raise RuntimeError(f"densify_and_prune: the {role} leaf must be [P, {shape[1]}]")
+        if src[roles["opacity"]].numel() != P:
+            raise RuntimeError("densify_and_prune: the opacity leaf must be [P] or [P, 1]")
+        acc = {"xyz_gradient_accum": xyz_gradient_accum, "denom": denom, "max_radii2D": max_radii2D}
+        for name, t in acc.items():
+            if t is None and name == "max_radii2D":
+                continue
+            if t is None or t.numel() != P:
+                raise RuntimeError(f"densify_and_prune: {name} must have P elements")
+            acc[name] = _rows_tensor(t, P, name)
+        if noise is not None:
+            if tuple(noise.shape) != (P, 2, 3):
+                raise RuntimeError("densify_and_prune: noise must be [P, 2, 3]")
+            noise = _rows_tensor(noise, P, "noise")
+        thresholds = densify_thresholds(grad_threshold, extent, percent_dense, min_opacity, max_screen_size)
+
+        plan = torch.empty(lib.dgr_densify_plan_bytes(P), dtype=torch.uint8, device=dev)
+        counts_dev = torch.empty(8, dtype=torch.int32, device=dev)
+        scaling, rotation = src[roles["scaling"]], src[roles["rotation"]]
+        rc = lib.dgr_densify_plan(st, P, _capi.ptr(acc["xyz_gradient_accum"]), _capi.ptr(acc["denom"]),
+                                  _capi.ptr(acc["max_radii2D"]), _capi.ptr(src[roles["opacity"]]), _capi.ptr(scaling),
+                                  *thresholds, plan.data_ptr(), counts_dev.data_ptr())
+        if rc:
+            raise RuntimeError(_capi.last_error())
+        counts = DensifyCounts(*counts_dev.tolist()[:5])  # the call's one host synchronisation
+        P_new = counts.rows
+
+        new = lambda t: torch.empty((P_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)  # noqa: E731
+        mode_of = {roles["xyz"]: _capi.DENSIFY_XYZ, roles["scaling"]: _capi.DENSIFY_LOG_SCALE}
+        table, out, moments = [], {}, {}
+        for name, t in src.items():
+            out[name] = new(t)
+            table.append((t, out[name], mode_of.get(name, _capi.DENSIFY_COPY)))
+            state = optimizer.state.get(params[name]) if optimizer is not None else None
+            if state is not None:
+                moments[name] = (new(t), new(t))
+                table += [(m.contiguous(), d, _capi.DENSIFY_ZERO_NEW) for m, d in zip(state, moments[name])]
+        zeroed = []
+        for name, t in acc.items():
+            zeroed.append(torch.empty((P_new,) + tuple(t.shape[1:] if t is not None else ()), dtype=torch.float32, device=dev))
+            table.append((None, zeroed[-1], _capi.DENSIFY_ZERO))
+        for i in range(0, len(table), _capi.DENSIFY_MAX_TENSORS):  # one launch per 24 tensors: one in all for 3DGS's model
+            part = table[i:i + _capi.DENSIFY_MAX_TENSORS]
+            descs = (_capi.DensifyTensor * len(part))()
+            for d, (s, t, mode) in zip(descs, part):
+                d.src, d.dst, d.mode = _capi.ptr(s), _capi.ptr(t), mode
+                d.k = max(math.prod(t.shape[1:]), 1)
+            rc = lib.dgr_densify_apply(st, P, P_new, plan.data_ptr(), len(part), descs, _capi.ptr(scaling), _capi.ptr(rotation),
+                                       _capi.ptr(noise), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)))
+            if rc:
+                raise RuntimeError(_capi.last_error())
+    for name, t in params.items():
+        out[name].requires_grad_(t.requires_grad)
+    if optimizer is not None:
+        optimizer.replace_params({params[name]: out[name] for name in params},
+                                 {params[name]: moments[name] for name in moments})
+    return out, zeroed[0], zeroed[1], zeroed[2], counts
 
 
 class SparseAdam:
@@ -97,3 +217,19 @@ class SparseAdam:
                                              vis, float(g["lr"]), float(b1), float(b2), float(g["eps"]), self.steps)
                 if rc:
                     raise RuntimeError(_capi.last_error())
+
+    def replace_params(self, old_to_new, moments=None):
+        """Points the optimiser at new leaves after the number of rows changed (`densify_and_prune`): `old_to_new` maps each
+        replaced parameter to its successor, `moments` an old parameter to the successor's (exp_avg, exp_avg_sq).  A
+        parameter without moments gets no state (its first step creates it, zeros).  `steps` and the device step count of
+        the capturable form are kept: new rows meet the current bias correction, as 3DGS's do."""
+        moments = moments or {}
+        for g in self.param_groups:
+            g["params"] = [old_to_new.get(p, p) for p in g["params"]]
+        for old, new in old_to_new.items():
+            self.state.pop(old, None)
+            if old in moments:
+                m, v = moments[old]
+                if m.shape != new.shape or v.shape != new.shape:
+                    raise RuntimeError("SparseAdam.replace_params: the moments must have the new parameter's shape")
+                self.state[new] = (m, v)

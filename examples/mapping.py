@@ -7,15 +7,18 @@ A synthetic map rendered from K poses gives the keyframes' observed colour and d
                          no pose gradient), gradients summed into the parameters' .grad
   add_densification_stats 3DGS's per-view bookkeeping (screen-space gradient norm, view count, largest radius), one launch
   SparseAdam.step        fused Adam over the rows some keyframe saw, one launch per tensor
-all on the GPU, no host synchronisation inside the loop.  --fused renders the keyframe batch through the batched entry points
+all on the GPU, no host synchronisation inside the loop.  --densify-every N adds the step that changes the number of
+Gaussians: every N iterations densify_and_prune consumes the statistics (clone, split, prune; three launches and one host read
+for the whole model and its Adam moments) and the loop goes on with the new leaves.  --fused renders the keyframe batch through the batched entry points
 instead (slam.render_batch_fused: one forward and one backward call for all keyframes, gradients summed in the kernels).
 --variant full runs the same loop through the -full variant (uncertainty output; it has no track_off, so the pose gradients are
 formed and left unused).
 
-  python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--iters 100] [--keyframes 4]
+  python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
+                             [--keyframes 4]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
-of 3DGS's `viewspace_points.grad`; a densify step built on it uses a threshold about 4x higher (0.0008 for 0.0002).
+of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
                              [--width 640 --height 480 --gaussians 100000]
 """
 import argparse
@@ -59,6 +62,16 @@ class MapModel:
     get_scaling = property(lambda self: torch.exp(self._scaling))
     get_rotation = property(lambda self: torch.nn.functional.normalize(self._rotation))
 
+    def leaves(self):
+        """name -> raw leaf, under the role names densify_and_prune looks for"""
+        return {"xyz": self._xyz, "features": self._features, "opacity": self._opacity, "scaling": self._scaling,
+                "rotation": self._rotation}
+
+    def replace(self, leaves, xyz_gradient_accum, denom, max_radii2D):
+        self._xyz, self._features, self._opacity = leaves["xyz"], leaves["features"], leaves["opacity"]
+        self._scaling, self._rotation = leaves["scaling"], leaves["rotation"]
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = xyz_gradient_accum, denom, max_radii2D
+
     def groups(self):
         return [{"params": [self._xyz], "lr": 1.6e-4}, {"params": [self._features], "lr": 2.5e-3},
                 {"params": [self._opacity], "lr": 5e-2}, {"params": [self._scaling], "lr": 5e-3},
@@ -66,12 +79,14 @@ class MapModel:
 
 
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
-                 absgrad=False):
+                 absgrad=False, densify_every=0):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
-    absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True))."""
+    absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
+    densify_every=N: every N iterations the statistics are consumed by densify_and_prune (not with graph=True: the step
+    changes the number of Gaussians)."""
     from dgr_amd import light, slam
-    from dgr_amd.optim import SparseAdam, add_densification_stats
+    from dgr_amd.optim import SparseAdam, add_densification_stats, densify_and_prune
     from dgr_amd.synth import make_scene
 
     scenes = [make_scene(P, W, H, 3, view_index=k) for k in range(keyframes)]
@@ -146,6 +161,21 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         opt.step(visible=seen)
         return torch.stack(losses).mean()
 
+    if densify_every:  # the scene's radius stands in for 3DGS's cameras_extent
+        extent = float((truth.get_xyz.detach() - truth.get_xyz.detach().mean(dim=0)).norm(dim=1).max())
+
+    def densify():
+        nonlocal seen
+        before = pc.get_xyz.shape[0]
+        leaves, accum, denom, max_radii2D, counts = densify_and_prune(
+            pc.leaves(), opt, pc.xyz_gradient_accum, pc.denom, pc.max_radii2D,
+            grad_threshold=0.0008 if absgrad else 0.0002, extent=extent, max_screen_size=20.0)
+        pc.replace(leaves, accum, denom, max_radii2D)
+        seen = torch.zeros(counts.rows, dtype=torch.int32, device=dev)
+        if log:
+            log(f"densify: P {before} -> {counts.rows} ({counts.survivors} kept, {counts.clones} cloned, "
+                f"{counts.split} split into {counts.children})")
+
     run = iteration
     if graph:  # (the three eager iterations run inside CapturedStep, on the stream the graph is recorded on)
         from dgr_amd.multiview import CapturedStep
@@ -163,6 +193,8 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     t0 = time.perf_counter()
     for i in range(iters - 3):
         loss = run()
+        if densify_every and (i + 4) % densify_every == 0:
+            densify()
         if log and (i + 3) % 20 == 0:
             log(f"iteration {i + 3:4d}: loss {float(loss):.4e}")
     torch.cuda.synchronize()
@@ -184,10 +216,15 @@ def main():
     ap.add_argument("--variant", choices=("light", "full"), default="light", help="which rasterizer variant maps")
     ap.add_argument("--absgrad", action="store_true",
                     help="densification statistics from the absolute screen-space gradient (AbsGS) instead of viewspace_points.grad")
+    ap.add_argument("--densify-every", type=int, default=0, metavar="N",
+                    help="every N iterations clone / split / prune from the accumulated statistics (densify_and_prune); "
+                         "off by default, not together with --graph")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
     args = ap.parse_args()
+    if args.densify_every < 0 or (args.densify_every and args.graph):
+        ap.error("--densify-every changes the number of Gaussians: it cannot run inside a recorded hipGraph (drop --graph)")
     import torch as _torch
     _torch.autograd.set_multithreading_enabled(False)  # one device, one thread: no engine-thread hand-off per backward
     if args.graph:
@@ -195,12 +232,13 @@ def main():
     dev = torch.device("cuda:0")
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
                                     args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
-                                    variant=args.variant, absgrad=args.absgrad)
+                                    variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every)
     n = float(pc.denom.sum())
     print(("full variant: " if args.variant == "full" else "") + ("absgrad: " if args.absgrad else "") +
           f"loss {l0:.4e} -> {l1:.4e}; {dt * 1e3:.3f} ms per mapping iteration over {args.keyframes} keyframes"
           f" ({dt / args.keyframes * 1e3:.3f} ms per keyframe); {int((pc.denom > 0).sum())} Gaussians seen,"
-          f" {n:.0f} (Gaussian, view) statistics accumulated")
+          f" {n:.0f} (Gaussian, view) statistics accumulated" +
+          (f"; P {args.gaussians} -> {pc.get_xyz.shape[0]}" if args.densify_every else ""))
 
 
 if __name__ == "__main__":

@@ -251,6 +251,51 @@ int dgr_sparse_adam_capturable(void* stream, long rows, int k, float* param, con
 int dgr_densification_stats(void* stream, long rows, const float* dmeans2D, const int* radii, float* grad_accum, float* denom,
                             float* max_radii2D);
 
+/* Fused densify-and-prune: 3DGS's densify_and_clone, densify_and_split and prune_points over every per-Gaussian tensor of
+ * the model, in three launches (csrc/optim.hip).  All decisions are fp32 comparisons on the raw values against thresholds
+ * the caller forms (in float64, rounded once), so that a restatement with plain tensor comparisons takes the same ones:
+ *   hot   = denom > 0 && grad_accum >= grad_threshold * denom      (one rounded fp32 multiply; a NaN is not hot)
+ *   m     = max_k scaling_raw[row, k];   split = hot && m > log_scale_split;   clone = hot && !split
+ * The result is that of: append a copy of every clone row (row order); append the children of every split row (sample 0 of
+ * all split rows, then sample 1), child xyz = xyz + R(q / |q|) (exp(scaling_raw) * n), child scaling_raw = scaling_raw -
+ * logf(1.6f) (one fp32 subtraction of 0x1.e148a2p-2f), everything else the parent's; remove the split originals; then prune
+ * every row, new ones included, with opacity_raw < opacity_raw_min, or max_radii2D > max_screen_size (new rows carry 0), or
+ * its own max_k scaling_raw > log_scale_prune.  Pass +inf for the last two thresholds to switch those rules off.
+ * Output order: surviving originals, clones, children of sample 0, children of sample 1, each in original row order; no
+ * atomic decides a position, so the result is the same bits on every run.
+ *
+ * dgr_densify_plan decides (one action per row) into `plan`, an opaque 16-byte aligned device buffer of
+ * dgr_densify_plan_bytes(rows) bytes, and writes counts8_device[0..7] (device memory) = {rows after the step, surviving
+ * originals, clones kept, children kept, rows split, 0, 0, 0}.  The caller reads counts[0], allocates, and calls
+ * dgr_densify_apply with rows_out = counts[0] and a table of 1 .. DGR_DENSIFY_MAX_TENSORS tensors {src [rows, k], dst
+ * [rows_out, k]}: ONE launch moves them all (call it again with the same plan for more tensors).  Modes: COPY (every emitted
+ * row takes its source row), ZERO_NEW (Adam moments: survivors copied, new rows zero), ZERO (accumulators: dst zeroed, src
+ * unused), XYZ (k = 3, at most one: children displaced as above), LOG_SCALE (children shifted by -logf(1.6f)).
+ * `noise`: [rows, 2, 3] standard normals indexed by the ORIGINAL row (sample, component), or NULL: the kernel then draws
+ * them with Philox4x32-10 keyed by `seed` with the counter (row, sample) and Box-Muller -- the values do not depend on the
+ * grid or on which other rows split.  scaling_raw [rows, 3] / rotation_raw [rows, 4] (r, x, y, z; not unit) are read by XYZ.
+ * rows == 0 succeeds (zero counts).  Argument errors are reported before any HIP call.  Not capturable as a whole: the
+ * caller reads counts between the two calls. */
+#define DGR_DENSIFY_MAX_TENSORS 24
+#define DGR_DENSIFY_COPY 0
+#define DGR_DENSIFY_ZERO_NEW 1
+#define DGR_DENSIFY_ZERO 2
+#define DGR_DENSIFY_XYZ 3
+#define DGR_DENSIFY_LOG_SCALE 4
+typedef struct {
+    const float* src;
+    float* dst;
+    int k;
+    int mode;
+} dgr_densify_tensor;
+size_t dgr_densify_plan_bytes(long rows);
+int dgr_densify_plan(void* stream, long rows, const float* grad_accum, const float* denom, const float* max_radii2D /* or NULL */,
+                     const float* opacity_raw, const float* scaling_raw, float grad_threshold, float opacity_raw_min,
+                     float log_scale_split, float log_scale_prune, float max_screen_size, void* plan, int* counts8_device);
+int dgr_densify_apply(void* stream, long rows, long rows_out, const void* plan, int n, const dgr_densify_tensor* tensors,
+                      const float* scaling_raw, const float* rotation_raw, const float* noise /* or NULL */,
+                      unsigned long long seed);
+
 /* ---- the small pieces of a tracking iteration around the rasterizer, one launch each (the reference's
  * caller, CG-SLAM, does these with a dozen elementwise torch kernels each -- a 640x480 tracking step is launch-bound) ----
  * dgr_pose_forward: (quat = (r, x, y, z), not necessarily unit; trans) -> the three camera tensors the rasterizer takes,
