@@ -256,7 +256,7 @@ struct RenderBwdFullArgs {
 
 // ---- launchers (each enqueues on `stream` and returns the hipError_t of the launch) ----
 hipError_t launch_preprocess_fwd(const PreprocessFwdArgs& a, hipStream_t stream);
-// complete_pose: dgr_set_option("pose_grad", 1) -- the instance with the complete pose gradient (preprocess.hip: bwd_view_terms)
+// complete_pose: dgr_set_option("pose_grad", 1) -- the instance with the complete pose gradient (preprocess_bwd.hip: bwd_view_terms)
 hipError_t launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t stream, bool complete_pose = false);
 hipError_t launch_preprocess_fwd_batch(const PreprocessFwdBatchArgs& b, hipStream_t stream);
 hipError_t launch_preprocess_bwd_batch(const PreprocessBwdBatchArgs& b, hipStream_t stream, bool complete_pose = false);
@@ -287,7 +287,7 @@ hipError_t launch_densify_plan(size_t rows, const float* grad_accum, const float
 hipError_t launch_densify_apply(size_t rows, size_t rows_out, const void* plan, int n, const dgr_densify_tensor* tensors,
                                 const float* scaling_raw, const float* rotation_raw, const float* noise,
                                 unsigned long long seed, hipStream_t stream);
-// view-independent covariance of a batch of views (preprocess.hip)
+// view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,
                                  float* dL_dscale, float* dL_drot, hipStream_t stream);

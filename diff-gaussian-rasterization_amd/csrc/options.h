@@ -21,13 +21,13 @@ namespace dgr {
 //       backward's T_final = 1 - alpha and its divisions by (1 - alpha) amplify the last-bit differences to 6e-5 abs at config 3;
 //   2 = as 0 with glibc's expf algorithm in the double pipe (exp_glibc; rounds 5-7's default, the oracle's exp mode 1), for A/B.
 //   Set it before the forward whose backward should use it (forward and backward of a view must use the same mode).
-// "tight_cull": 1 = alpha-aware tile rectangles (preprocess.hip); default off.
+// "tight_cull": 1 = alpha-aware tile rectangles (preprocess_fwd.hip); default off.
 // "deterministic_grads": 1 = the light backward (one-view entry point, alpha_mode 0) forms its gradients without
 //   order-dependent float atomics (csrc/render_light.hip: DET): bit-identical run after run, at the price of an instance-major row
 //   buffer (64 bytes per tile instance: zero-filled, written and read once) and a smaller batch in the blend backward.  The backward
 //   then needs dgr_light_backward_scratch_bytes_r(P, W, H, R) bytes of scratch, R = the value passed as `R` (>= num_rendered).
 // "pose_grad": 0 (default) = the reference's pose-gradient terms; 1 = the complete pose gradient, the view-matrix counterpart of
-//   dL_dmeans3D (csrc/preprocess.hip: bwd_view_terms<true>; include/dgr_hip.h).  A light map_off backward then runs the mapping
+//   dL_dmeans3D (csrc/preprocess_bwd.hip: bwd_view_terms<true>; include/dgr_hip.h).  A light map_off backward then runs the mapping
 //   blend backward (its per-Gaussian outputs are dropped).
 // "silhouette_grad": 0 (default) / 1.  No entry point reads it: it is the bindings' switch (include/dgr_hip.h), kept here so
 //   that both bindings and every thread share one value and a backward runs under its forward's snapshot.  1: the bindings pass

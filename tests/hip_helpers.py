@@ -99,7 +99,7 @@ def binning_capacity(d, W, H):
 
 
 def hip_cov3D(s, scale_modifier=1.0):
-    """computeCov3D as the forward and the backward evaluate it (the geometry state does not keep it: csrc/preprocess.hip's
+    """computeCov3D as the forward and the backward evaluate it (the geometry state does not keep it: csrc/gaussian_math.h's
     compute_cov3d, through dgr_cov3d_forward -- the same device function)."""
     from dgr_amd.multiview import shared_cov3D
     return shared_cov3D(T(s.scales), T(s.rots), scale_modifier).detach().cpu().numpy()

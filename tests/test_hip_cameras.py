@@ -4,7 +4,7 @@ synth's one symmetric frustum, where a swapped focal / limit pair or a dropped o
 
 Outcome recorded here: the forward, the default backward, absgrad and the batched paths carried the oracle's bits / bars at every
 camera and placement; the complete pose gradient (pose_grad = 1) left out the principal point (persp[8], persp[9]) of the ndc
-rows and missed the float64 formulation at an off-centre camera -- fixed in csrc/preprocess.hip."""
+rows and missed the float64 formulation at an off-centre camera -- fixed in bwd_view_terms (csrc/preprocess_bwd.hip)."""
 import numpy as np
 import pytest
 import torch
