@@ -79,19 +79,16 @@ int zero_outputs(const FwdCommon& c, hipStream_t st) {
     return DGR_OK;
 }
 
-// preprocess.  Callback path (bin == nullptr): afterwards geom.block_tiles holds the instance totals per 256-Gaussian
+// preprocess.  Callback path (path.callback): afterwards geom.block_tiles holds the instance totals per 256-Gaussian
 // block and scan_blocks turns them into offsets and num_rendered.  Presized path (the binning buffer exists already):
 // the kernel also takes the tile-counter atomics and stores the ranks (count_rank.h), behind one small clear of the
 // counters; scan_blocks and count_rank disappear.
-// Presized path, binning mode: COUNT_LDS = the two-level segment binning after preprocess (segment_binning.hip; frames
-// whose segment tables fit LDS), COUNT_FUSED = returning global atomics inside preprocess_fwd (binning.hip).
-// Callback path (the binning buffer is sized after a host read of num_rendered): COUNT_LDS_CALLBACK = the same segment
-// binning behind scan_blocks, COUNT_CALLBACK = the count_rank kernel on global tile counters (R = 0, or a frame too large).
-enum { COUNT_CALLBACK = 0, COUNT_FUSED = 1, COUNT_LDS = 2, COUNT_LDS_CALLBACK = 3 };
-int presized_count_mode(int W, int H) {
-    const bool lds = option(OPT_LDS_COUNT) != 0 && dgr::segment_binning_fits(W, H);
-    return lds ? COUNT_LDS : COUNT_FUSED;
+// Which binning follows (dgr::BinPath, kernels.h): the segment binning wherever "lds_count" allows it and the frame's segment
+// tables fit LDS, the global tile counters otherwise.
+dgr::BinPath bin_path(int W, int H, bool callback) {
+    return {option(OPT_LDS_COUNT) != 0 && dgr::segment_binning_fits(W, H), callback};
 }
+dgr::StatusReport report_of(const ArmedReport* armed) { return armed ? armed->rep : dgr::StatusReport{nullptr, 0u, nullptr}; }
 // The scene half of the preprocess arguments: what the views of a batch share
 void preprocess_scene(dgr::PreprocessFwdArgs& a, const FwdCommon& c) {
     a.P = c.P; a.D = c.D; a.M = c.M; a.W = c.W; a.H = c.H; a.grid_x = dgr::tiles_x(c.W); a.grid_y = dgr::tiles_y(c.H);
@@ -104,9 +101,9 @@ void preprocess_scene(dgr::PreprocessFwdArgs& a, const FwdCommon& c) {
     a.tight_cull = opt_tight_cull();
     a.sh_vec_ok = aligned16(c.shs);
 }
-int forward_front(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, hipStream_t st,
-                  const dgr::BinningView* bin = nullptr, int capacity = 0, char* image_base = nullptr,
-                  int mode = COUNT_CALLBACK) {
+// (presized path: `bin`, `capacity` and `image_base` are the view's binning view, its capacity and its image buffer)
+int forward_front(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, hipStream_t st, dgr::BinPath path,
+                  const dgr::BinningView* bin, int capacity, char* image_base) {
     // No memsets: preprocess clears the per-Gaussian median statistics (and, on the callback path, the tile counters);
     // scan_blocks / scan_tiles initialise the status word.
     dgr::PreprocessFwdArgs a{};
@@ -114,13 +111,13 @@ int forward_front(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img
     a.view = c.viewmatrix; a.proj = c.projmatrix; a.campos = c.cam_pos;
     a.geom = geom; a.radii_out = c.radii;
     a.gau_uncertainty = c.gau_uncertainty; a.gau_related_pixels = c.gau_related_pixels;
-    if (bin && mode == COUNT_LDS) {
+    if (!path.callback && path.segments) {
         // nothing to clear: the kernel leaves its per-block instance totals (and the `prefiltered` flag) in
         // geom.block_tiles, bin_segments / bin_tiles take it from there
         { ScopedStage t(ST_PRE_FWD, st); HIP_TRY(dgr::launch_preprocess_fwd(a, st)); }
         return DGR_OK;
     }
-    if (bin) {
+    if (!path.callback) {
         // cursor + padded tile counters: everything between the start of the image buffer and the range table
         { ScopedStage t(ST_ZERO_FWD, st); HIP_TRY(dgr::launch_zero_fill(image_base, (size_t)((char*)img.ranges - image_base), st)); }
         a.fused_count = 1; a.tile_count = img.tile_count; a.cursor = img.cursor; a.ranks = bin->ranks; a.capacity = capacity;
@@ -135,31 +132,30 @@ int forward_front(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img
 }
 
 // histogram + ranks, range table (status[0] = num_rendered, status[1] = overflow), key scatter, per-tile sort
-// (`fused`: preprocess_fwd counted already; the status word is complete after scan_tiles, which is where a caller that
-// armed the early status gets its copy)
+// (presized path: the status word is complete after bin_tiles / scan_tiles, which is where a caller that armed the early status
+// gets its copy; callback path: the caller has read it already)
 int binning_stages(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, dgr::BinningView bin, int capacity,
-                   hipStream_t st, int mode = COUNT_CALLBACK, char* binning_base = nullptr, ArmedReport* armed = nullptr) {
+                   hipStream_t st, dgr::BinPath path, char* binning_base, ArmedReport* armed) {
     const int gx = dgr::tiles_x(c.W), gy = dgr::tiles_y(c.H), tiles = gx * gy;
     // the tile schedule: always, unless this shape's last reported frame had even lists (want_schedule above)
     const bool sched_on = !(armed && armed->id >= 0) ? (option(OPT_TILE_SCHEDULE) != 0) : want_schedule(c.W, c.H, c.P);
     const int lists = option(OPT_LANE_LISTS);
     const int blend_flags = (sched_on ? dgr::BLEND_SCHEDULE : 0) | (lists == 0 ? dgr::BLEND_LISTS_QUADRANT : lists == 2 ? dgr::BLEND_LISTS_AUTO : 0);
-    const dgr::StatusReport rep = armed ? armed->rep : dgr::StatusReport{nullptr, 0u, nullptr};
-    if (mode == COUNT_LDS || mode == COUNT_LDS_CALLBACK) {
-        const bool cb = mode == COUNT_LDS_CALLBACK;
+    const dgr::StatusReport rep = report_of(armed);
+    if (path.segments) {
         const dgr::SegmentTables tb = dgr::carve_segment_tables(binning_base + bin.bytes, c.W, c.H);
         const int longest = (armed && armed->id >= 0) ? hinted_longest_list(c.W, c.H, c.P) : -1;
         const int ss = dgr::segment_shift(c.W, c.H, capacity, longest);
-        { ScopedStage t(ST_BIN_SEGMENTS, st); HIP_TRY(dgr::launch_bin_segments(c.P, geom, bin, tb, gx, gy, ss, capacity, cb, st)); }
-        { ScopedStage t(ST_BIN_TILES, st); HIP_TRY(dgr::launch_bin_tiles(c.P, geom, img, bin, tb, gx, gy, ss, capacity, cb, blend_flags, rep, st)); }
-        if (!cb) { const int rc = early_status_post(img.status, st); if (rc) return rc; }  // (bin_tiles writes the status word)
+        { ScopedStage t(ST_BIN_SEGMENTS, st); HIP_TRY(dgr::launch_bin_segments(c.P, geom, bin, tb, gx, gy, ss, capacity, path, st)); }
+        { ScopedStage t(ST_BIN_TILES, st); HIP_TRY(dgr::launch_bin_tiles(c.P, geom, img, bin, tb, gx, gy, ss, capacity, path, blend_flags, rep, st)); }
+        if (!path.callback) { const int rc = early_status_post(img.status, st); if (rc) return rc; }  // (bin_tiles writes the status word)
         if (sched_on) { ScopedStage t(ST_TILE_SCHED, st); HIP_TRY(dgr::launch_tile_schedule(img, tiles, st)); }
         return DGR_OK;
     }
-    const bool fused = mode == COUNT_FUSED;
-    if (!fused) { ScopedStage t(ST_COUNT_RANK, st); HIP_TRY(dgr::launch_count_rank(c.P, geom, img, bin, gx, capacity, st)); }
-    { ScopedStage t(ST_SCAN, st); HIP_TRY(dgr::launch_scan_tiles(img, tiles, gx, capacity, fused, blend_flags, rep, st)); }
-    if (fused) { const int rc = early_status_post(img.status, st); if (rc) return rc; }
+    // (presized: preprocess_fwd counted already)
+    if (path.callback) { ScopedStage t(ST_COUNT_RANK, st); HIP_TRY(dgr::launch_count_rank(c.P, geom, img, bin, gx, capacity, st)); }
+    { ScopedStage t(ST_SCAN, st); HIP_TRY(dgr::launch_scan_tiles(img, tiles, gx, capacity, path, blend_flags, rep, st)); }
+    if (!path.callback) { const int rc = early_status_post(img.status, st); if (rc) return rc; }
     { ScopedStage t(ST_EMIT, st); HIP_TRY(dgr::launch_emit_instances(c.P, geom, img, bin, gx, st)); }
     { ScopedStage t(ST_SORT, st); HIP_TRY(dgr::launch_sort_tiles(img, bin, tiles, st)); }
     if (sched_on) { ScopedStage t(ST_TILE_SCHED, st); HIP_TRY(dgr::launch_tile_schedule(img, tiles, st)); }
@@ -172,7 +168,7 @@ void blend_fwd_common(A& r, const FwdCommon& c, dgr::GeometryView geom, dgr::Ima
     r.W = c.W; r.H = c.H; r.grid_x = dgr::tiles_x(c.W); r.grid_y = dgr::tiles_y(c.H);
     r.sched = img.tile_sched; r.ranges = img.ranges; r.sched_flag = img.cursor + 3; r.point_list = bin.point_list; r.rec = geom.rec; r.bg = c.background;
     r.out_color = c.out_color; r.out_depth = c.out_depth; r.n_contrib = img.n_contrib; r.status = img.status;
-    r.rep = armed ? armed->rep : dgr::StatusReport{nullptr, 0u, nullptr};
+    r.rep = report_of(armed);
 }
 int forward_blend(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img, dgr::BinningView bin, hipStream_t st, bool full,
                   ArmedReport* armed = nullptr) {
@@ -349,8 +345,8 @@ int forward_batch(hipStream_t st, int n_views, const FwdCommon* cv, const BatchV
     }
     // One preprocess launch for all views needs the segment binning behind it (its epilogue leaves per-block instance
     // totals); frames whose segment tables do not fit LDS, or "lds_count" = 0, take the one-view front end per view.
-    const bool shared_front = option(OPT_LDS_COUNT) != 0 && dgr::segment_binning_fits(width, height);
-    if (shared_front) {
+    const dgr::BinPath path = bin_path(width, height, /*callback=*/false);
+    if (path.segments) {
         dgr::PreprocessFwdBatchArgs b{};
         preprocess_scene(b.base, cv[0]);
         b.V = n_views;
@@ -367,12 +363,8 @@ int forward_batch(hipStream_t st, int n_views, const FwdCommon* cv, const BatchV
     for (int v = 0; v < n_views; v++) {
         hipStream_t sv = plan.first_stream(v);
         const int cap = bs[v].binning_capacity;
-        int mode = COUNT_LDS;
-        if (!shared_front) {
-            mode = presized_count_mode(width, height);
-            if ((rc = forward_front(cv[v], geom[v], img[v], sv, &bin[v], cap, bs[v].image_buffer, mode))) return rc;
-        }
-        if ((rc = binning_stages(cv[v], geom[v], img[v], bin[v], cap, sv, mode, bs[v].binning_buffer))) return rc;
+        if (!path.segments && (rc = forward_front(cv[v], geom[v], img[v], sv, path, &bin[v], cap, bs[v].image_buffer))) return rc;
+        if ((rc = binning_stages(cv[v], geom[v], img[v], bin[v], cap, sv, path, bs[v].binning_buffer, nullptr))) return rc;
         if ((rc = plan.hand_over(v, sv))) return rc;  // (pipeline: the blend on the caller's stream, behind the view's binning)
         if ((rc = forward_blend(cv[v], geom[v], img[v], bin[v], sv, full))) return rc;
     }
@@ -426,9 +418,9 @@ int forward_presized(hipStream_t st, const FwdCommon& c, char* geometry_buffer, 
     dgr::ImageView img = dgr::carve_image(image_buffer, c.W, c.H);
     if (status) img.status = status;  // the kernels write the caller's status word directly
     dgr::BinningView bin = dgr::carve_binning(binning_buffer, (size_t)binning_capacity);
-    const int mode = presized_count_mode(c.W, c.H);
-    if ((rc = forward_front(c, geom, img, st, &bin, binning_capacity, image_buffer, mode))) return rc;
-    if ((rc = binning_stages(c, geom, img, bin, binning_capacity, st, mode, binning_buffer, &armed))) return rc;
+    const dgr::BinPath path = bin_path(c.W, c.H, /*callback=*/false);
+    if ((rc = forward_front(c, geom, img, st, path, &bin, binning_capacity, image_buffer))) return rc;
+    if ((rc = binning_stages(c, geom, img, bin, binning_capacity, st, path, binning_buffer, &armed))) return rc;
     return forward_blend(c, geom, img, bin, st, full, &armed);
 }
 
@@ -450,7 +442,8 @@ int forward_callback(hipStream_t st, const FwdCommon& c, dgr_alloc_fn geometryBu
     if (!gptr || !iptr) { set_last_error("allocation callback returned NULL"); return DGR_ERR_ALLOC; }
     dgr::GeometryView geom = dgr::carve_geometry(gptr, c.P);
     dgr::ImageView img = dgr::carve_image(iptr, c.W, c.H);
-    if ((rc = forward_front(c, geom, img, st))) return rc;
+    dgr::BinPath path = bin_path(c.W, c.H, /*callback=*/true);
+    if ((rc = forward_front(c, geom, img, st, path, nullptr, 0, nullptr))) return rc;
     // the one blocking read the reference also has (rasterizer_impl.cu:287, F/...:435): num_rendered sizes the binning buffer
     int status[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));
@@ -465,9 +458,9 @@ int forward_callback(hipStream_t st, const FwdCommon& c, dgr_alloc_fn geometryBu
         binningBuffer(0, alloc_user);
     }
     dgr::BinningView bin = dgr::carve_binning(bptr, (size_t)R);
-    // (also with R == 0: it writes the (empty) range table)
-    const int mode = (R > 0 && presized_count_mode(c.W, c.H) == COUNT_LDS) ? COUNT_LDS_CALLBACK : COUNT_CALLBACK;
-    if ((rc = binning_stages(c, geom, img, bin, R, st, mode, bptr))) return rc;
+    // (also with R == 0: nothing to bin, and no buffer for the segment tables -- count_rank and scan_tiles write the empty range table)
+    if (R <= 0) path.segments = false;
+    if ((rc = binning_stages(c, geom, img, bin, R, st, path, bptr, nullptr))) return rc;
     if ((rc = forward_blend(c, geom, img, bin, st, full))) return rc;
     if (num_related) {  // second blocking read of the reference (F/cuda_rasterizer/rasterizer_impl.cu:498)
         HIP_TRY(hipMemcpyAsync(status, img.status, sizeof(status), hipMemcpyDeviceToHost, st));

@@ -19,6 +19,7 @@
 #include "dgr_common.h"
 #include "kernels.h"
 #include "count_rank.h"
+#include "block_scan.h"
 #include "tile_sort.h"
 #include <mutex>
 
@@ -39,7 +40,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_tiles_kernel(ImageView img,
         return img.tile_count[((size_t)ty * pairs_x + (tx >> 1)) * DGR_COUNT_STRIDE + (tx & 1)];
     };
     __shared__ uint32_t wsum[SCAN_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int per = (tiles + SCAN_THREADS - 1) / SCAN_THREADS;
     const int lo = min(t * per, tiles), hi = min(lo + per, tiles);
     // Up to 8 counters per thread stay in registers (every frame up to 8192 tiles, i.e. 1080p); larger grids read
@@ -57,24 +58,9 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_tiles_kernel(ImageView img,
     } else {
         for (int i = lo; i < hi; i++) s += count_of(i);
     }
-    // wave-level inclusive scan, then the 16 wave totals through LDS: one barrier
-    uint32_t incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int ww = 0; ww < SCAN_THREADS / 64; ww++) {
-        const uint32_t v = wsum[ww];
-        if (ww < wave) before += v;
-        total += v;
-    }
+    uint32_t total;
+    uint32_t run = block_exclusive_scan<SCAN_THREADS>(s, wsum, t, &total);  // exclusive prefix of this thread's chunk
     const bool overflow = total > (uint32_t)capacity;
-    uint32_t run = before + incl - s;  // exclusive prefix of this thread's chunk
     if (per <= REG) {
 #pragma unroll
         for (int k = 0; k < REG; k++) {
@@ -92,16 +78,9 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_tiles_kernel(ImageView img,
         }
     }
     if (t == 0) {
-        img.status[0] = (int)total;
-        img.status[1] = overflow ? 1 : 0;
-        img.cursor[2] = (uint32_t)capacity;
-        // bit 0: the blend kernels walk tile_sched; bit 1: this frame overflowed; bit 2: quadrant lists in the light blend kernels
-        // (segment_binning.hip decides that per frame; this path has no run statistics and takes only the forced setting)
-        img.cursor[3] = (uint32_t)(sched_on & 1) | (overflow ? 2u : 0u) | ((sched_on & BLEND_LISTS_QUADRANT) ? 4u : 0u);
-        if (fused) {  // (otherwise scan_blocks initialised them)
-            img.status[2] = (int)img.cursor[1];  // prefiltered violation
-            img.status[3] = 0;                   // full variant: number of valid (pixel, Gaussian) pairs, summed by its forward blend
-        }
+        // (`fused`: no scan_blocks ran, so the violation flag comes from the cursor; this path takes only the forced lane lists)
+        write_frame_words(img, total, capacity, overflow, sched_on, (sched_on & BLEND_LISTS_QUADRANT) != 0,
+                          StatusTail{fused != 0, fused ? (int)img.cursor[1] : 0});
         // (this path does not track the longest list: "unknown" keeps the tile schedule on)
         if (rep.ws) __hip_atomic_store(rep.ws, 0x7fffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -111,7 +90,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_tiles_kernel(ImageView img,
 // (exclusive scan inside this block).  Callback path only: the presized path counts inside preprocess_fwd.
 __global__ void __launch_bounds__(256) count_rank_kernel(int P, GeometryView geom, ImageView img, BinningView bin,
                                                          int grid_x, int capacity) {
-    __shared__ uint32_t wtot[4];
+    __shared__ uint32_t wtot[256 / 64];
     __shared__ uint32_t stage[COUNT_STAGE];
     const int tid = threadIdx.x;
     const int idx = blockIdx.x * 256 + tid;
@@ -119,7 +98,7 @@ __global__ void __launch_bounds__(256) count_rank_kernel(int P, GeometryView geo
     if (idx < P) r = geom.rect[idx];
     const uint32_t n = (uint32_t)(r.z - r.x) * (uint32_t)(r.w - r.y);
     uint32_t block_total;
-    const uint32_t loc = block_exclusive_scan(n, wtot, tid, &block_total);
+    const uint32_t loc = block_exclusive_scan<256>(n, wtot, tid, &block_total);
     const uint32_t block_base = geom.block_tiles[blockIdx.x];
     if (idx < P) geom.goff[idx] = block_base + loc;
     count_and_rank(r, block_base + loc, block_base, block_total, img.tile_count, bin.ranks, grid_x, capacity, stage, tid);
@@ -130,7 +109,7 @@ __global__ void __launch_bounds__(256) count_rank_kernel(int P, GeometryView geo
 __global__ void __launch_bounds__(SCAN_THREADS) scan_blocks_kernel(uint32_t* block_tiles, int nblocks, int* status) {
     __shared__ uint32_t wsum[SCAN_THREADS / 64];
     __shared__ uint32_t any_flag;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x;
     const int per = (nblocks + SCAN_THREADS - 1) / SCAN_THREADS;
     const int lo = min(t * per, nblocks), hi = min(lo + per, nblocks);
     if (t == 0) any_flag = 0u;
@@ -140,12 +119,10 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_blocks_kernel(uint32_t* blo
         s += v & 0x7fffffffu;
         flag |= v >> 31;
     }
-    uint32_t incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
+    // (block_exclusive_scan<SCAN_THREADS>'s steps, left inline with the flag's store between them as before: through the helper
+    //  the stage missed the project's A/B rule in one of its two workloads, profiles/binning_shared/notes.md s5)
+    const int lane = t & 63, wave = t >> 6;
+    const uint32_t incl = wave_inclusive_scan(s, lane);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     if (flag) any_flag = 1u;
@@ -163,12 +140,8 @@ __global__ void __launch_bounds__(SCAN_THREADS) scan_blocks_kernel(uint32_t* blo
         run += c;
     }
     __syncthreads();
-    if (t == 0) {  // the whole status word is (re)initialised here: no memset before the forward
-        status[0] = (int)total;
-        status[1] = 0;               // overflow: scan_tiles
-        status[2] = (int)any_flag;   // prefiltered violation
-        status[3] = 0;               // full variant: number of valid (pixel, Gaussian) pairs, summed by its forward blend
-    }
+    // the whole status word is (re)initialised here: no memset before the forward (overflow: scan_tiles / bin_tiles set it)
+    if (t == 0) write_status_word(status, total, /*overflow=*/false, StatusTail{true, (int)any_flag});
 }
 
 // slot = range start + arrival rank (count_rank's returning atomics on the global tile counters)
@@ -193,27 +166,8 @@ __global__ void __launch_bounds__(SORT_THREADS) sort_tiles_kernel(ImageView img,
     uint64_t* gk = bin.keys + rg.x;
     uint32_t* pl = bin.point_list + rg.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (n > SORT_LDS_MAX) {  // oversize tile: same network, in place in global memory, one barrier per step
-        int np2 = 1;
-        while (np2 < n) np2 <<= 1;
-        const int half = np2 >> 1;
-        for (int size = 2; size <= np2; size <<= 1) {
-            const int hs = size >> 1;
-            for (int t = tid; t < half; t += SORT_THREADS) {
-                const int blk = t / hs, off = t - blk * hs;
-                const int i = blk * size + off, j = blk * size + (size - 1 - off);
-                if (j < n) { const uint64_t x = gk[i], y = gk[j]; if (x > y) { gk[i] = y; gk[j] = x; } }
-            }
-            __syncthreads();
-            for (int d = size >> 2; d > 0; d >>= 1) {
-                for (int t = tid; t < half; t += SORT_THREADS) {
-                    const int blk = t / d, off = t - blk * d;
-                    const int i = blk * 2 * d + off, j = i + d;
-                    if (j < n) { const uint64_t x = gk[i], y = gk[j]; if (x > y) { gk[i] = y; gk[j] = x; } }
-                }
-                __syncthreads();
-            }
-        }
+    if (n > SORT_LDS_MAX) {  // oversize tile: same network, in place in global memory (tile_sort.h)
+        wg_sort_global<SORT_THREADS>(gk, n, tid);
         for (int i = tid; i < n; i += SORT_THREADS) pl[i] = (uint32_t)gk[i];
         return;
     }
@@ -258,134 +212,11 @@ __global__ void __launch_bounds__(SORT_THREADS) sort_tiles_kernel(ImageView img,
     for (int i = tid; i < n; i += SORT_THREADS) pl[i] = (uint32_t)sk[i];
 }
 
-// ---- tile schedule ------------------------------------------------------------------------------------------------
-// The blend kernels run one workgroup per tile and a workgroup's time grows with its list.  On a scene whose Gaussians
-// cluster, a static block -> tile map hands whole clusters to a few XCDs and starts the longest lists last: on a frame with
-// lists of 51 .. 1135 entries (mean 222) the XCD-band map of rounds 1-5 took 236 / 445 us (forward / backward blend) where
-// heaviest-first takes 124 / 220 (profiles/r6/tile_order_clustered.txt).  One workgroup writes, per workgroup slot b of the
-// blend kernels, {tile, list start, list end} (they need no second lookup):
-//   * the tiles go by CLASS of list length, longest first -- two classes per octave (lengths within ~40 % of each other share
-//     one), which is all the balance needs: what matters is that a 1000-entry list does not start behind 200-entry ones;
-//   * inside a class the tiles keep their order in the image, and the class is dealt to the
-//     XCDs in eight CONTIGUOUS parts -- slot b runs on XCD b mod 8 -- so that tiles running together on an XCD are neighbours
-//     and share the Gaussians' records in its L2.  (A fine sort by length scatters neighbours over the XCDs: same kernel
-//     times, but 350 / 359 MB of HBM traffic for the forward / backward blend instead of 188 / 226, profiles/r6_pmc.txt.)
-// On the uniform benchmark scene nine tiles in ten share one class: the schedule is round 5's XCD bands with the few long lists
-// in front.
-constexpr int TS_THREADS = 1024;
-// A class owns the M slots from B on; XCD x = slot mod 8 takes the x-th contiguous part of the class, as many tiles as the class
-// has slots on that XCD.  part_table fills, for one (class, XCD): the class position its part starts at and its first slot.
-__device__ __forceinline__ void part_table(uint32_t B, uint32_t M, uint32_t x, uint32_t& n_x, uint32_t& first) {
-    first = B + ((x + 8u - (B & 7u)) & 7u);  // first slot >= B on XCD x
-    n_x = first < B + M ? (B + M - 1u - first) / 8u + 1u : 0u;
-}
-// Wave w takes the w-th contiguous sixteenth of the tiles, 512 at a time, EIGHT CONSECUTIVE TILES PER LANE: neighbours mostly
-// share a class, so a lane hands in whole runs -- one LDS atomic per run instead of one per tile (same-address LDS atomics retire
-// about one lane per two cycles for the whole CU: 2 x 8160 of them on the uniform scene's one dominant class were 13 of a first
-// version's 16 us).  First every wave counts its tiles per class in its own row of counters; a prefix over the waves turns the
-// rows into each wave's first position inside every class; then every wave places its tiles, drawing positions from its own
-// row: no barrier between the waves, a class's tiles in image order up to the order of the lanes inside one 512-tile block.
-__global__ void __launch_bounds__(TS_THREADS) tile_schedule_kernel(const uint2* __restrict__ ranges, int tiles,
-                                                                    uint4* __restrict__ sched) {
-    constexpr int NW = TS_THREADS / 64, NC = DGR_SCHED_CLASSES, PL = 8;
-    __shared__ uint32_t cntw[NW][NC];  // tiles of wave w in class c; then: position of the wave's next tile inside class c
-    __shared__ uint32_t cnt[NC], base[NC];
-    __shared__ uint32_t part_off[NC][8], part_first[NC][8];  // per (class, XCD): first class position / first slot of the part
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < NW * NC; i += TS_THREADS) (&cntw[0][0])[i] = 0u;
-    __syncthreads();
-    const int per_wave = ((tiles + NW - 1) / NW + 64 * PL - 1) / (64 * PL) * (64 * PL);  // a multiple of 512
-    const int w0 = wave * per_wave, w1 = min(tiles, w0 + per_wave);
-    // the lane's eight tiles of the block starting at b0: ranges, classes, and the runs of equal class among them
-    struct Block { uint2 r[PL]; uint32_t c[PL]; uint32_t len[PL]; bool valid[PL], start[PL]; };
-    auto load_block = [&](int b0, Block& B) {
-        const int t0 = b0 + lane * PL;
-        const uint4* src = reinterpret_cast<const uint4*>(ranges + t0);  // (16-byte aligned: t0 is a multiple of 8; a block's tail may lie
-#pragma unroll                                                          //  behind `tiles` but inside the image buffer: ignored)
-        for (int k = 0; k < PL; k += 2) {
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (t0 + k < w1) v = src[k / 2];
-            B.r[k] = make_uint2(v.x, v.y);
-            B.r[k + 1] = make_uint2(v.z, v.w);
-        }
-#pragma unroll
-        for (int k = 0; k < PL; k++) {
-            B.valid[k] = t0 + k < w1;
-            B.c[k] = sched_class(B.r[k].y - B.r[k].x);
-            B.start[k] = B.valid[k] && (k == 0 || B.c[k] != B.c[k - 1]);
-        }
-        B.len[PL - 1] = 1u;
-#pragma unroll
-        for (int k = PL - 2; k >= 0; k--) B.len[k] = (B.valid[k + 1] && B.c[k + 1] == B.c[k]) ? B.len[k + 1] + 1u : 1u;  // run length from k on
-    };
-    for (int b0 = w0; b0 < w1; b0 += 64 * PL) {
-        Block B;
-        load_block(b0, B);
-#pragma unroll
-        for (int k = 0; k < PL; k++)
-            if (B.start[k]) atomicAdd(&cntw[wave][B.c[k]], B.len[k]);
-    }
-    __syncthreads();
-    {   // every wave's first position inside each class (thread (w, c) sums the rows above its own), the class totals
-        const int w = tid >> 5, c = tid & (NC - 1);
-        uint32_t before = 0u;
-        if (tid < NW * NC)
-            for (int ww = 0; ww < w; ww++) before += cntw[ww][c];
-        if (tid >= (NW - 1) * NC && tid < NW * NC) cnt[c] = before + cntw[NW - 1][c];
-        __syncthreads();
-        if (tid < NW * NC) cntw[w][c] = before;
-    }
-    __syncthreads();
-    if (tid < 64) {  // first slot of every class, the class of the longest lists first (lane l holds class NC - 1 - l)
-        const uint32_t v = lane < NC ? cnt[NC - 1 - lane] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < NC; off <<= 1) {
-            const uint32_t t = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += t;
-        }
-        if (lane < NC) base[NC - 1 - lane] = incl - v;
-    }
-    __syncthreads();
-    if (tid < NC * 8) {  // the XCDs' parts of every class
-        const uint32_t c = (uint32_t)tid >> 3, x = (uint32_t)tid & 7u;
-        uint32_t off = 0u, n_x, first;
-        for (uint32_t xx = 0; xx < x; xx++) { part_table(base[c], cnt[c], xx, n_x, first); off += n_x; }
-        part_table(base[c], cnt[c], x, n_x, first);
-        part_off[c][x] = off;
-        part_first[c][x] = first;
-    }
-    __syncthreads();
-    for (int b0 = w0; b0 < w1; b0 += 64 * PL) {
-        Block B;
-        load_block(b0, B);
-        uint32_t run_base = 0u;
-#pragma unroll
-        for (int k = 0; k < PL; k++) {
-            if (B.start[k]) run_base = atomicAdd(&cntw[wave][B.c[k]], B.len[k]);  // (the wave's own row)
-            else run_base += 1u;                                                     // (next tile of the same run)
-            if (B.valid[k]) {
-                const uint32_t c = B.c[k], p = run_base;  // position inside the class
-                uint32_t x = 0u;  // the part holding it: the last one that starts at or before p (an empty part starts where the next does)
-#pragma unroll
-                for (int j = 1; j < 8; j++) x += p >= part_off[c][j] ? 1u : 0u;
-                sched[part_first[c][x] + 8u * (p - part_off[c][x])] = make_uint4((uint32_t)(b0 + lane * PL + k), B.r[k].x, B.r[k].y, 0u);
-            }
-        }
-    }
-}
-
 }  // namespace
 
-hipError_t launch_tile_schedule(ImageView img, int tiles, hipStream_t stream) {
-    if (tiles <= 0) return hipSuccess;
-    launch(tile_schedule_kernel, dim3(1), dim3(TS_THREADS), stream, (const uint2*)img.ranges, tiles, img.tile_sched);
-    return hipGetLastError();
-}
-
-hipError_t launch_scan_tiles(ImageView img, int tiles, int grid_x, int capacity, bool fused, int blend_flags, StatusReport rep,
+hipError_t launch_scan_tiles(ImageView img, int tiles, int grid_x, int capacity, BinPath path, int blend_flags, StatusReport rep,
                              hipStream_t stream) {
-    launch(scan_tiles_kernel, dim3(1), dim3(SCAN_THREADS), stream, img, tiles, grid_x, capacity, fused ? 1 : 0, blend_flags, rep);
+    launch(scan_tiles_kernel, dim3(1), dim3(SCAN_THREADS), stream, img, tiles, grid_x, capacity, path.callback ? 0 : 1, blend_flags, rep);
     return hipGetLastError();
 }
 hipError_t launch_count_rank(int P, GeometryView geom, ImageView img, BinningView bin, int grid_x, int capacity,

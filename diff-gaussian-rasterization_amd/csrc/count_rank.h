@@ -98,22 +98,4 @@ __device__ __forceinline__ void count_and_rank(ushort4 r, uint32_t off0, uint32_
     }
 }
 
-// In-block exclusive scan of the instance counts: returns this thread's offset inside the block, *total = block total.
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t n, uint32_t* wtot /* 4 words of LDS */, int tid,
-                                                         uint32_t* total) {
-    const int lane = tid & 63, wave = tid >> 6;
-    uint32_t incl = n;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (int ww = 0; ww < wave; ww++) before += wtot[ww];
-    *total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-    return before + incl - n;
-}
-
 }  // namespace dgr

@@ -29,7 +29,7 @@ namespace dgr {
 
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// list length -> class of the blend kernels' tile schedule (binning.hip): 0 for an empty list, then two classes per octave
+// list length -> class of the blend kernels' tile schedule (tile_schedule.hip): 0 for an empty list, then two classes per octave
 // (lengths within ~40 % of each other share a class), saturating at 31 (>= 23 170 entries).  Monotone in n.
 __device__ inline uint32_t sched_class(uint32_t n) {
     if (n == 0u) return 0u;
@@ -81,6 +81,8 @@ __host__ __device__ inline GeometryView carve_geometry(char* base, int P) {
 
 // what the forward asks of the binning kernel that writes ImageView::cursor[3] (launch_bin_tiles / launch_scan_tiles: blend_flags)
 enum { BLEND_SCHEDULE = 1, BLEND_LISTS_QUADRANT = 4, BLEND_LISTS_AUTO = 8 };
+// ... and what that kernel stores there, the frame's blend flags (write_frame_words below; read by render_common.h: blend_flags)
+enum { BLEND_FLAG_SCHEDULE = 1, BLEND_FLAG_OVERFLOWED = 2, BLEND_FLAG_QUADRANT_LISTS = 4 };
 
 struct ImageView {
     int* status;          // [4] {num_rendered, overflow, prefiltered violation, reserved}
@@ -95,7 +97,7 @@ struct ImageView {
                           //     tiles' LIVE counts in the first `tiles` words (render_common.h: live_list) -- part of a view's state
     uint2* ranges;        // [tiles] {start, end} into point_list
     uint4* tile_sched;    // [tiles] the blend kernels' schedule: workgroup b works on tile .x, whose list is [.y, .z) --
-                          //     classes of long lists first, neighbours on one XCD (tile_schedule_kernel, binning.hip)
+                          //     classes of long lists first, neighbours on one XCD (tile_schedule_kernel, tile_schedule.hip)
     uint32_t* n_contrib;  // [N]
     float* final_T;       // [N]   (full variant)
     uint32_t* n_valid;    // [N]   (full variant) valid contributors of the pixel
@@ -119,6 +121,33 @@ __host__ __device__ inline ImageView carve_image(char* base, int W, int H) {
     v.first_contrib = (uint32_t*)(base + o); o = align_up(o + N * 4, 256);
     v.bytes = o;
     return v;
+}
+
+// The frame's words, each written in one place.  The status word {num_rendered, overflow, prefiltered violation, 0}: scan_blocks
+// initialises all of it on the callback path (no memset before the forward), so the kernel that completes it there -- scan_tiles,
+// bin_tiles -- leaves [2..3] alone (StatusTail::write false); on the presized path that kernel writes all four.  One thread calls these.
+struct StatusTail {
+    bool write;     // this kernel stores status[2..3]
+    int violation;  // ... and this is status[2], the prefiltered violation (read only when `write`)
+};
+__device__ __forceinline__ void write_status_word(int* status, uint32_t total, bool overflow, StatusTail tail) {
+    status[0] = (int)total;
+    status[1] = overflow ? 1 : 0;
+    if (tail.write) {
+        status[2] = tail.violation;  // prefiltered violation
+        status[3] = 0;          // full variant: number of valid (pixel, Gaussian) pairs, summed by its forward blend
+    }
+}
+// ... and with it cursor[2] = the capacity the binning buffer was carved with, cursor[3] = the frame's blend flags: bit 0: the
+// blend kernels walk tile_sched (`blend_flags`, what the host asked for: BLEND_SCHEDULE); bit 1: this frame overflowed; bit 2:
+// quadrant lists in the light blend kernels (`quadrant_lists`: bin_tiles decides it per frame; the global-counter path has no
+// run statistics and takes only the forced setting, BLEND_LISTS_QUADRANT).
+__device__ __forceinline__ void write_frame_words(const ImageView& img, uint32_t total, int capacity, bool overflow, int blend_flags,
+                                                  bool quadrant_lists, StatusTail tail) {
+    write_status_word(img.status, total, overflow, tail);
+    img.cursor[2] = (uint32_t)capacity;
+    img.cursor[3] = (uint32_t)((blend_flags & BLEND_SCHEDULE) ? BLEND_FLAG_SCHEDULE : 0) | (overflow ? BLEND_FLAG_OVERFLOWED : 0) |
+                    (quadrant_lists ? BLEND_FLAG_QUADRANT_LISTS : 0);
 }
 
 // bijective XCD-aware remap (workgroup b runs on XCD b % 8): XCD x gets a contiguous run of the n items

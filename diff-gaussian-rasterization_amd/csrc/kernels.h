@@ -294,28 +294,35 @@ hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotati
 hipError_t launch_mark_visible(int P, const float* means, const float* view, uint8_t* present, hipStream_t stream);
 
 // binning: tile_count -> ranges (+ total in status[0], overflow in status[1]); emit keys; sort tiles
-// `fused`: preprocess_fwd counted (no scan_blocks ran): scan_tiles then also fills status[2] (from the cursor's violation
-// word) and status[3]
-hipError_t launch_scan_tiles(ImageView img, int tiles, int grid_x, int capacity, bool fused, int blend_flags, StatusReport rep,
+// Which binning runs behind preprocess and from which entry point: the one description api.hip decides (bin_path) and the
+// launchers below read.
+//   segments: the two-level segment binning (segment_binning.hip; frames whose segment tables fit LDS); otherwise the global
+//             tile counters (binning.hip).
+//   callback: the binning buffer is sized after a host read of num_rendered: scan_blocks has run, so geom.block_tiles is already
+//             the exclusive prefix of the block totals and the status word is initialised.  Otherwise (presized) preprocess_fwd
+//             left raw block totals (segments) or counted itself (counters), and the kernel that completes the status word --
+//             bin_tiles, scan_tiles -- also fills status[2..3].
+struct BinPath {
+    bool segments, callback;
+};
+hipError_t launch_scan_tiles(ImageView img, int tiles, int grid_x, int capacity, BinPath path, int blend_flags, StatusReport rep,
                              hipStream_t stream);
 hipError_t launch_count_rank(int P, GeometryView geom, ImageView img, BinningView bin, int grid_x, int capacity,
                              hipStream_t stream);
 hipError_t launch_scan_blocks(int P, GeometryView geom, ImageView img, hipStream_t stream);
 hipError_t launch_emit_instances(int P, GeometryView geom, ImageView img, BinningView bin, int grid_x, hipStream_t stream);
 // two-level binning (segment_binning.hip): presized and callback paths, frames whose segment tables fit LDS.
-// `prefixed`: geom.block_tiles is already the exclusive prefix of the block totals and the status word is initialised
-// (callback path, after scan_blocks)
 bool segment_binning_fits(int W, int H);
 int segment_binning_workgroups(int P);
 int segment_shift(int W, int H, int capacity, int longest_list = -1);  // log2 of the tiles per segment (4, 3 or 2) for this frame, capacity and (if known) longest list
 hipError_t launch_bin_segments(int P, GeometryView geom, BinningView bin, SegmentTables tb, int grid_x, int grid_y, int seg_shift,
-                               int capacity, bool prefixed, hipStream_t stream);
+                               int capacity, BinPath path, hipStream_t stream);
 extern unsigned long long* g_bin_tiles_trace;  // debug: phase time stamps per bin_tiles workgroup (segment_binning.hip)
 hipError_t launch_bin_tiles(int P, GeometryView geom, ImageView img, BinningView bin, SegmentTables tb, int grid_x, int grid_y,
-                            int seg_shift, int capacity, bool prefixed, int blend_flags, StatusReport rep, hipStream_t stream);
+                            int seg_shift, int capacity, BinPath path, int blend_flags, StatusReport rep, hipStream_t stream);
 hipError_t launch_sort_tiles(ImageView img, BinningView bin, int tiles, hipStream_t stream);
 // ranges -> the blend kernels' schedule (img.tile_sched): tiles by descending list length, so that the longest lists
-// start first and every XCD gets its share of a cluster
+// start first and every XCD gets its share of a cluster (tile_schedule.hip)
 hipError_t launch_tile_schedule(ImageView img, int tiles, hipStream_t stream);
 
 // alpha_mode: render_common.h (0 = ALPHA_REF, the restatement's bits; 1 = ALPHA_FAST; 2 = ALPHA_GLIBC)

@@ -189,6 +189,26 @@ __device__ __forceinline__ uint32_t block_tiles_word(const uint32_t* w) {
     return ((w[0] & 0x7fffffffu) + (w[1] & 0x7fffffffu) + (w[2] & 0x7fffffffu) + (w[3] & 0x7fffffffu)) | flag;
 }
 
+// block_scan.h's block_exclusive_scan<256> in the four-wave form preprocess_fwd_kernel had before that header existed, kept for
+// this kernel alone: with the shared form the kernel is 42 instructions shorter, and its stage then missed the project's A/B rule
+// at config 2 of the full variant (a workload that does not even run the fused count) while passing where the count does run
+// (profiles/binning_shared/notes.md s5).  With this copy the kernel is the earlier one instruction for instruction.
+__device__ __forceinline__ uint32_t block_exclusive_scan4(uint32_t n, uint32_t* wtot /* 4 words of LDS */, int tid, uint32_t* total) {
+    const int lane = tid & 63, wave = tid >> 6;
+    uint32_t incl = n;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t v = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += v;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int ww = 0; ww < wave; ww++) before += wtot[ww];
+    *total = wtot[0] + wtot[1] + wtot[2] + wtot[3];
+    return before + incl - n;
+}
+
 // ------------------------------------------------------------------------------------------------
 #ifndef DGR_PPF_WAVES
 #define DGR_PPF_WAVES 5
@@ -228,7 +248,7 @@ __global__ void __launch_bounds__(256, DGR_PPF_WAVES) preprocess_fwd_kernel(Prep
         const bool any_violation = __syncthreads_or(violation);  // (also orders the SH phase's LDS reads before the stage)
         const uint32_t n = (uint32_t)(rect.z - rect.x) * (uint32_t)(rect.w - rect.y);
         uint32_t block_total;
-        const uint32_t loc = block_exclusive_scan(n, wsum, threadIdx.x, &block_total);
+        const uint32_t loc = block_exclusive_scan4(n, wsum, threadIdx.x, &block_total);
         if (threadIdx.x == 0) {
             s_base = block_total ? atomicAdd(a.cursor, block_total) : 0u;
             if (any_violation) atomicOr(a.cursor + 1, 1u);

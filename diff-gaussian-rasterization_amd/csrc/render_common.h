@@ -9,7 +9,7 @@
 
 namespace dgr {
 
-// Workgroup b of a blend kernel -> {tile, list start, list end}.  With a schedule (tile_schedule_kernel, binning.hip: classes of
+// Workgroup b of a blend kernel -> {tile, list start, list end}.  With a schedule (tile_schedule_kernel, tile_schedule.hip: classes of
 // long lists first, neighbours on one XCD) that is one 16-byte entry.  A frame whose lists are even needs none -- the schedule
 // then is the static map with extra steps: a launch, 11 us in front of the blend at 1080p, and neighbours spread a little --
 // so the forward skips the kernel (status.hip: want_schedule, the policy) and the workgroups fall back on the band map of rounds 1-5: workgroup
@@ -21,7 +21,7 @@ namespace dgr {
 // it per frame (segment_binning.hip) and forward and backward of the frame take the same uniform branch on it.
 // The flags ride in this word because the status word itself is no place to read from here: the full forward's workgroups add their valid-pair counts to
 // status[3] with atomics as they finish, and a load of that line queues behind them -- 34 -> 60 us for render_fwd at config 2.
-enum { BLEND_FLAG_SCHEDULE = 1, BLEND_FLAG_OVERFLOWED = 2, BLEND_FLAG_QUADRANT_LISTS = 4 };
+// (BLEND_FLAG_SCHEDULE / _OVERFLOWED / _QUADRANT_LISTS: dgr_common.h, beside the one function that writes the word)
 __device__ __forceinline__ int blend_flags(const uint32_t* __restrict__ sched_flag) { return __builtin_amdgcn_readfirstlane((int)*sched_flag); }
 __device__ __forceinline__ uint4 blend_slot(int flag, const uint4* __restrict__ sched, const uint2* __restrict__ ranges, int tiles) {
     if (flag & BLEND_FLAG_SCHEDULE) return sched[blockIdx.x];

@@ -25,7 +25,7 @@
 //    A skipped (pixel, Gaussian) pair is one the per-pixel test `power > 0 || alpha < 15/255` would have
 //    rejected, so outputs are unchanged; `contributor` (hence n_contrib) is the position in the tile list,
 //    which skipping does not alter.
-//  * block -> tile through the tile schedule (ImageView::tile_sched, binning.hip): longest list first, consecutive workgroups
+//  * block -> tile through the tile schedule (ImageView::tile_sched, tile_schedule.hip): longest list first, consecutive workgroups
 //    going round the XCDs.  (Rounds 1-5 handed every XCD a contiguous band of tiles for L2 reuse between neighbours: no
 //    measurable gain, and a factor of two lost on a frame whose Gaussians cluster -- DESIGN.md s4.8.)
 //
@@ -36,6 +36,7 @@
 // o * exp2(p2) on a conic pre-scaled by log2(e) -- one v_exp_f32.  Forward and backward of one mode use the identical
 // expression, so they agree on every decision.
 #include "render_common.h"
+#include "block_scan.h"
 
 namespace dgr {
 namespace {
@@ -589,12 +590,7 @@ __global__ void __launch_bounds__(256) det_offsets_kernel(int P, const ushort4* 
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = before;
     const int g = blockIdx.x * 256 + threadIdx.x;
     const uint32_t n = g < P ? rect_tiles(rect[g]) : 0u;
-    uint32_t incl = n;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if ((threadIdx.x & 63) >= off) incl += v;
-    }
+    const uint32_t incl = wave_inclusive_scan(n, (int)(threadIdx.x & 63));
     if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
     __syncthreads();
     uint32_t base = red[0] + red[1] + red[2] + red[3];

@@ -35,6 +35,7 @@
 // 8 + 4 + 8 + 4 B read per instance plus the 8 MB table three times before.
 #include "dgr_common.h"
 #include "kernels.h"
+#include "block_scan.h"
 #include "tile_sort.h"
 #include <mutex>
 
@@ -50,40 +51,6 @@ constexpr int K2_CAP = 6144;        // keys of one segment held in LDS (48 KB: t
 constexpr int REG_SORT_MAX = 1024;  // a wave sorts a tile list in registers up to here (16 chunks of 64)
 constexpr int BIG_PAIRS = 24;       // bin_segments: rectangles of more (row, segment) pairs are walked by a whole wave
 constexpr int BIGQ = 512;           // ... from a queue of this many entries per 4096 Gaussians (8 KB of LDS)
-
-// exclusive (inclusive) scan of a[0..n) in place by the whole workgroup; returns the total.  NT threads, all call it.
-template <int NT>
-__device__ __forceinline__ uint32_t block_scan(uint32_t* a, int n, bool inclusive, uint32_t* wsum, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const int per = (n + NT - 1) / NT;
-    const int lo = min(tid * per, n), hi = min(lo + per, n);
-    uint32_t s = 0;
-    for (int i = lo; i < hi; i++) s += a[i];
-    uint32_t incl = s;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    __syncthreads();  // (wsum may still be read from a previous call)
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int ww = 0; ww < NT / 64; ww++) {
-        const uint32_t v = wsum[ww];
-        if (ww < wave) before += v;
-        total += v;
-    }
-    uint32_t run = before + incl - s;
-    for (int i = lo; i < hi; i++) {
-        const uint32_t c = a[i];
-        a[i] = inclusive ? run + c : run;
-        run += c;
-    }
-    __syncthreads();
-    return total;
-}
 
 // ------------------------------------------------------------------------------------------------ K1
 // Every thread handles its Gaussians four at a time with the four loads issued together (the kernel is a latency
@@ -397,17 +364,8 @@ __global__ void __launch_bounds__(K2_THREADS, 6) bin_tiles_kernel(ImageView img,
             for (int off = 32; off > 0; off >>= 1) vis += __shfl_xor(vis, off, 64);
             quadrant_lists = (unsigned long long)total > 10ull * vis;
         }
-        if (lane == 0) {
-            img.status[0] = (int)total;
-            img.status[1] = overflow ? 1 : 0;
-            if (!prefixed) {
-                img.status[2] = (int)flag;  // prefiltered violation
-                img.status[3] = 0;          // full variant: number of valid (pixel, Gaussian) pairs, summed by its forward blend
-            }
-            img.cursor[2] = (uint32_t)capacity;
-            // bit 0: the blend kernels walk tile_sched; bit 1: this frame overflowed
-            img.cursor[3] = (uint32_t)(sched_on & 1) | (overflow ? 2u : 0u) | (quadrant_lists ? 4u : 0u);
-        }
+        // (callback path: scan_blocks took the violation flag and initialised status[2..3])
+        if (lane == 0) write_frame_words(img, total, capacity, overflow, sched_on, quadrant_lists, StatusTail{!prefixed, (int)flag});
     }
     if (overflow || gcount == 0u) {  // (empty tiles keep {0, 0}: the reference clears the table and writes only tiles that own instances)
         if (part == 0 && tid < ntl) img.ranges[tile0 + tid] = make_uint2(0u, 0u);
@@ -454,12 +412,7 @@ __global__ void __launch_bounds__(K2_THREADS, 6) bin_tiles_kernel(ImageView img,
     stamp(2);
     if (wave == 0) {
         const uint32_t c = (lane < SEG_MAX) ? sh.tcnt[lane] : 0u;
-        uint32_t incl = c;
-#pragma unroll
-        for (int off = 1; off < SEG_MAX; off <<= 1) {
-            const uint32_t v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
+        const uint32_t incl = wave_inclusive_scan<SEG_MAX>(c, lane);
         if (lane < SEG_MAX) sh.tbase[lane] = incl - c;
         if (part == 0 && lane < ntl) img.ranges[tile0 + lane] = c ? make_uint2(before + incl - c, before + incl) : make_uint2(0u, 0u);
     }
@@ -615,7 +568,7 @@ int segment_binning_per_wg(int P) {
 int segment_binning_workgroups(int P) { return max(1, (P + segment_binning_per_wg(P) - 1) / segment_binning_per_wg(P)); }
 
 hipError_t launch_bin_segments(int P, GeometryView geom, BinningView bin, SegmentTables tb, int grid_x, int grid_y, int seg_shift,
-                               int capacity, bool prefixed, hipStream_t stream) {
+                               int capacity, BinPath path, hipStream_t stream) {
     const int nseg = grid_y * ((grid_x + (1 << seg_shift) - 1) >> seg_shift);
     const size_t lds = (size_t)nseg * 16;
     const int per_wg = segment_binning_per_wg(P);
@@ -634,11 +587,11 @@ hipError_t launch_bin_segments(int P, GeometryView geom, BinningView bin, Segmen
         }
     }
     launch_shmem(kernel, dim3(segment_binning_workgroups(P)), dim3(K1_THREADS), lds, stream, P, per_wg, geom, tb, bin.pair_keys,
-                 bin.pair_cov, grid_x, grid_y, seg_shift, capacity, prefixed ? 1 : 0);
+                 bin.pair_cov, grid_x, grid_y, seg_shift, capacity, path.callback ? 1 : 0);
     return hipGetLastError();
 }
 hipError_t launch_bin_tiles(int P, GeometryView geom, ImageView img, BinningView bin, SegmentTables tb, int grid_x, int grid_y,
-                            int seg_shift, int capacity, bool prefixed, int blend_flags, StatusReport rep, hipStream_t stream) {
+                            int seg_shift, int capacity, BinPath path, int blend_flags, StatusReport rep, hipStream_t stream) {
     const int nseg = grid_y * ((grid_x + (1 << seg_shift) - 1) >> seg_shift);
     const int helpers = (1 << seg_shift) / 4 - 1;  // per segment (bin_tiles_kernel)
     // block -> segment map: XCD x takes a contiguous run of segments on a frame known to be even (the last report of this shape
@@ -648,7 +601,7 @@ hipError_t launch_bin_tiles(int P, GeometryView geom, ImageView img, BinningView
     static const int forced_map = [] { const char* e = getenv("DGR_BT_MAP"); return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1; }();
     const int xp_map = forced_map >= 0 ? forced_map : ((blend_flags & 1) ? 0 : 1);
     launch(bin_tiles_kernel, dim3(nseg * (1 + helpers)), dim3(K2_THREADS), stream, img, bin.point_list, bin.keys, tb, bin.pair_keys, bin.pair_cov,
-           geom.block_tiles, (P + 255) / 256, segment_binning_workgroups(P), grid_x, grid_y, seg_shift, capacity, prefixed ? 1 : 0,
+           geom.block_tiles, (P + 255) / 256, segment_binning_workgroups(P), grid_x, grid_y, seg_shift, capacity, path.callback ? 1 : 0,
            blend_flags, rep, xp_map, g_bin_tiles_trace);
     return hipGetLastError();
 }

@@ -792,14 +792,16 @@ def test_callback_entry_points_match_the_presized_path(monkeypatch, oracle, bind
 
 
 @pytest.mark.parametrize("variant", ["light", "full"])
-@pytest.mark.parametrize("P,W,H,sm", [(20000, 320, 240, 1.0), (3000, 97, 61, 4.0), (70000, 640, 480, 1.0), (1500, 16, 16, 6.0)])
+@pytest.mark.parametrize("P,W,H,sm", [(20000, 320, 240, 1.0), (3000, 97, 61, 4.0), (70000, 640, 480, 1.0), (1500, 16, 16, 6.0),
+                                      (9000, 32, 32, 1.0)])
 def test_lds_count_and_global_atomic_count_agree(variant, P, W, H, sm):
     """The forward bins tile instances with the two-level segment binning (csrc/segment_binning.hip: pairs per row segment,
     tile lists built and sorted in LDS); dgr_set_option("lds_count", 0) selects round 2's returning global atomics (inside
     preprocess_fwd on the presized path; csrc/binning.hip), which also serve frames whose segment tables do not fit LDS.
     Both end in a sort of every tile's list on unique keys, so num_rendered, ranges, point_list, keys and every output must be
     identical bit for bit.  Shapes: 20 / 69 bin_segments workgroups, a ragged frame with large splats (one Gaussian covering
-    many rows and segments), a single tile."""
+    many rows and segments), a single tile, and four tiles whose lists (4357 .. 5173 entries) are longer than sort_tiles sorts
+    in LDS (SORT_LDS_MAX = 2048 keys): its in-place global sort, tile_sort.h's wg_sort_global."""
     from dgr_amd import _capi
     s = make_scene(P, W, H, 5)
     res = {}
@@ -813,6 +815,9 @@ def test_lds_count_and_global_atomic_count_agree(variant, P, W, H, sm):
             _capi.set_option("lds_count", 1)
     (d1, st1), (d0, st0) = res[2], res[0]
     assert d1["num_rendered"] == d0["num_rendered"] and d1["num_rendered"] > 0
+    if (P, W, H) == (9000, 32, 32):
+        r = st0["ranges"].reshape(-1, 2).astype(np.int64)
+        assert (r[:, 1] - r[:, 0]).max() > 2048  # (SORT_LDS_MAX: the global-counter path sorted this list in global memory)
     for k in st1:
         assert np.array_equal(st1[k], st0[k]), k
     for k in d1:
@@ -822,6 +827,37 @@ def test_lds_count_and_global_atomic_count_agree(variant, P, W, H, sm):
             assert_grad_close(d1[k], d0[k], k, rel_to_max=1e-6)
         else:
             assert np.array_equal(d1[k], d0[k]), k
+
+
+@pytest.mark.parametrize("P,W,H,sm", [(3000, 97, 61, 4.0), (262144 + 300, 640, 480, 1.0)])
+def test_the_four_front_end_paths_agree(monkeypatch, P, W, H, sm):
+    """Two binnings (segment binning / global tile counters: "lds_count") behind two entry points (presized, the default /
+    DGR_FORWARD_MODE=callback, which sizes the binning buffer from a host read of num_rendered behind scan_blocks): four front ends,
+    the light variant.  All end in a sort of every tile's list on unique keys, so num_rendered, ranges, point_list, keys and the
+    five images must be identical bit for bit to the default path's.  Callback with "lds_count" = 0 is the stand-alone
+    count_rank_kernel, which no other test of the default suite runs.  Shapes: a ragged frame of large splats (rectangles of many
+    rows); 1026 blocks of 256 Gaussians, so that scan_blocks_kernel takes two values per thread and bin_segments reads a prefixed
+    block table with workgroups of more than one round (2048 Gaussians each)."""
+    from dgr_amd import _capi
+    s = make_scene(P, W, H, 5)
+    res = {}
+    for mode, lds in (("presized", 1), ("presized", 0), ("callback", 1), ("callback", 0)):
+        monkeypatch.setenv("DGR_FORWARD_MODE", mode)
+        _capi.set_option("lds_count", lds)
+        try:
+            out, d = hh.hip_forward(s, 3, scale_modifier=sm)
+            res[mode, lds] = (d, {k: hh.hip_state(k, s, d) for k in ("point_list", "ranges", "keys")})
+        finally:
+            _capi.set_option("lds_count", 1)
+    d1, st1 = res["presized", 1]
+    assert d1["num_rendered"] > 0
+    for path, (d0, st0) in res.items():
+        assert d0["num_rendered"] == d1["num_rendered"], path
+        for k in st1:
+            assert np.array_equal(st1[k], st0[k]), (path, k)
+        for k in ("color", "depth", "depth_median", "depth_var", "opacity_map"):
+            assert np.array_equal(d1[k], d0[k]), (path, k)
+        assert_grad_close(d1["gau_uncertainty"], d0["gau_uncertainty"], "gau_uncertainty", rel_to_max=1e-6)  # (float atomics)
 
 
 @pytest.mark.parametrize("P,W,H,sm", [(40000, 320, 240, 1.0), (70000, 320, 240, 1.0), (9000, 97, 61, 2.0)])

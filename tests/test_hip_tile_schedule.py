@@ -1,4 +1,4 @@
-"""The blend kernels' tile schedule (csrc/binning.hip: tile_schedule_kernel) and parity on a NON-UNIFORM scene.
+"""The blend kernels' tile schedule (csrc/tile_schedule.hip: tile_schedule_kernel) and parity on a NON-UNIFORM scene.
 
 synth-v1 spreads the Gaussians evenly (tile lists of 203 +- 20 % at config 3); a mapped room does not.  The schedule hands
 the blend kernels their tiles heaviest first; it changes nothing but the order in which tiles are worked on, so every
@@ -154,7 +154,7 @@ def test_clustered_scene_batch_views_are_the_one_view_calls():
 
 def test_clustered_scene_with_tight_culling_and_through_the_callback_path(oracle, monkeypatch):
     """The two other ways into the binning on a non-uniform frame: alpha-aware tile rectangles (fewer, shorter lists) and the
-    callback entry points (binning buffer sized after a host read: COUNT_LDS_CALLBACK)."""
+    callback entry points (binning buffer sized after a host read: the segment binning behind scan_blocks)."""
     from dgr_amd import _capi
     s = cluster_scene(make_scene(100000, 640, 480, 0))
     st, ref = hh.oracle_forward(oracle, s, 3)
