@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generates tests/golden/*.npz: small regression vectors produced by the CPU oracle (float-math build).
 
-These are NOT outputs of the reference (it cannot be built in this image and ships no vectors of its own); they
+These are NOT outputs of the reference (those are recorded by make_reference_golden.py under reference/); they
 freeze the oracle -- which is pinned to SURVEY.md Appendix C by tests/test_oracle_known_answers.py -- on tiny
 scenes so that (a) a later edit of the oracle cannot drift silently and (b) the GPU path has fixed expected values
 that travel with the repository.  Inputs are regenerated from (P, W, H, seed) by dgr_amd.synth.make_scene.
