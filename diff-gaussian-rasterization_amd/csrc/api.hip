@@ -1172,4 +1172,47 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
     return DGR_OK;
 }
 
+// the shared argument checks of dgr_ssim_loss_forward / _backward: the message, or NULL
+static const char* ssim_bad_argument(int n_images, int channels, int height, int width, const float* img, const float* ref,
+                                     long n_depth, const float* depth, const float* depth_obs, const float* scratch) {
+    if (n_images <= 0 || channels <= 0 || height <= 0 || width <= 0) return "n_images, channels, height and width must be positive";
+    if (!dgr::ssim_shape_ok(n_images, channels, height, width))
+        return "n_images * channels must be at most 65535 (one grid plane each) and height, width at most 2^20";
+    if (!img || !ref) return "img or ref is NULL";
+    if (n_depth < 0) return "n_depth is negative";
+    if (n_depth > 0 && (!depth || !depth_obs)) return "n_depth > 0 with a NULL depth or depth_obs";
+    if (!scratch || !dgr::aligned16(scratch)) return "scratch is NULL or not 16-byte aligned";
+    return nullptr;
+}
+long dgr_ssim_scratch_floats(int n_images, int channels, int height, int width) {
+    return dgr::ssim_scratch_floats(n_images, channels, height, width);
+}
+int dgr_ssim_loss_forward(void* stream, int n_images, int channels, int height, int width, const float* img, const float* ref,
+                          long n_depth, const float* depth, const float* depth_obs, float w_l1, float w_ssim, float w_depth,
+                          float* scratch, int want_maps, float* loss) {
+    const char* bad = ssim_bad_argument(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, scratch);
+    if (!bad && !loss) bad = "loss is NULL";
+    if (bad) {
+        set_last_error(std::string("dgr_ssim_loss_forward: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_ssim_loss_forward(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, w_l1, w_ssim,
+                                          w_depth, scratch, want_maps != 0, loss, (hipStream_t)stream));
+    return DGR_OK;
+}
+int dgr_ssim_loss_backward(void* stream, int n_images, int channels, int height, int width, const float* img, const float* ref,
+                           long n_depth, const float* depth, const float* depth_obs, float w_l1, float w_ssim, float w_depth,
+                           const float* scratch, const float* upstream, float* dL_dimg, float* dL_ddepth) {
+    const char* bad = ssim_bad_argument(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, scratch);
+    if (!bad && !dL_dimg) bad = "dL_dimg is NULL";
+    if (!bad && n_depth > 0 && !dL_ddepth) bad = "n_depth > 0 with a NULL dL_ddepth";
+    if (bad) {
+        set_last_error(std::string("dgr_ssim_loss_backward: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_ssim_loss_backward(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, w_l1, w_ssim,
+                                           w_depth, scratch, upstream, dL_dimg, dL_ddepth, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

@@ -273,6 +273,18 @@ hipError_t launch_l1_loss_forward(long n_c, const float* c, const float* c_obs, 
                                   float w_c, float w_d, float* partial, float* loss, hipStream_t stream);
 hipError_t launch_l1_loss_backward(long n_c, const float* c, const float* c_obs, long n_d, const float* d, const float* d_obs,
                                    float w_c, float w_d, const float* upstream, float* dc, float* dd, hipStream_t stream);
+// ssim.hip: w_l1 mean|img - ref| + w_ssim (1 - SSIM(img, ref)) + w_depth mean|d - d_obs| over a [V, C, H, W] stack (11 x 11 Gaussian
+// window, zero padding); scratch = 4 header floats (mean SSIM, mean|img - ref|, mean|d - d_obs|, maps flag), the partial sums
+// (ssim_partial_floats() with the header) and, with want_maps, the three derivative maps the backward correlates
+bool ssim_shape_ok(int V, int C, int H, int W);
+long ssim_partial_floats(int V, int C, int H, int W);
+long ssim_scratch_floats(int V, int C, int H, int W);
+hipError_t launch_ssim_loss_forward(int V, int C, int H, int W, const float* img, const float* ref, long n_d, const float* d,
+                                    const float* d_obs, float w_l1, float w_ssim, float w_depth, float* scratch, bool want_maps,
+                                    float* loss, hipStream_t stream);
+hipError_t launch_ssim_loss_backward(int V, int C, int H, int W, const float* img, const float* ref, long n_d, const float* d,
+                                     const float* d_obs, float w_l1, float w_ssim, float w_depth, const float* scratch,
+                                     const float* upstream, float* dimg, float* ddepth, hipStream_t stream);
 hipError_t launch_densification_stats(int rows, const float* dmeans2D, const int* radii, float* grad_accum, float* denom,
                                       float* max_radii2D, hipStream_t stream);
 hipError_t launch_sparse_adam(size_t rows, int k, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -87,6 +87,9 @@ _SIGS = {
     "dgr_l1_loss_scratch_floats": (_i, []),
     "dgr_l1_loss_forward": (_i, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _vp, _vp]),
     "dgr_l1_loss_backward": (_i, [_vp, C.c_long, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _vp, _vp, _vp]),
+    "dgr_ssim_scratch_floats": (C.c_long, [_i, _i, _i, _i]),
+    "dgr_ssim_loss_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _f, _vp, _i, _vp]),
+    "dgr_ssim_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

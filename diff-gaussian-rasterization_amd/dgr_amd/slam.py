@@ -217,6 +217,116 @@ def l1_loss(color, depth, color_obs, depth_obs, w_color=1.0, w_depth=0.5):
     return _L1Loss.apply(color, depth, color_obs, depth_obs, w_color, w_depth)
 
 
+def _check_pair(name, a, b, what):
+    """ValueError unless `a`, `b` are float32 tensors of one shape (with _check_gpu: all on the host, before any device call)."""
+    for t, n in ((a, name), (b, name + "_obs")):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: {n} must be a tensor, not {type(t).__name__}")
+    if a.shape != b.shape:
+        raise ValueError(f"{what}: {name} {tuple(a.shape)} and {name}_obs {tuple(b.shape)} differ in shape")
+    for t, n in ((a, name), (b, name + "_obs")):
+        if t.dtype != torch.float32:
+            raise ValueError(f"{what}: {n} must be float32, not {t.dtype}")
+
+
+def _check_gpu(what, *tensors):
+    if any(not t.is_cuda for t in tensors):
+        raise ValueError(f"{what}: the images must be GPU tensors (there is no CPU fallback)")
+    if any(t.device != tensors[0].device for t in tensors):
+        raise ValueError(f"{what}: the images are on different devices")
+
+
+def _image_stack(img, what):
+    """(V, C, H, W) of a [C,H,W] or [V,C,H,W] image tensor the SSIM kernels can read."""
+    if img.dim() not in (3, 4):
+        raise ValueError(f"{what}: images are [C,H,W] or [V,C,H,W], not {tuple(img.shape)}")
+    V, (C, H, W) = (img.shape[0] if img.dim() == 4 else 1), img.shape[-3:]
+    if min(V, C, H, W) < 1 or V * C > 65535:
+        raise ValueError(f"{what}: cannot read a stack of shape {tuple(img.shape)} (empty, or more than 65535 image planes)")
+    return V, C, H, W
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+class _SsimLoss(torch.autograd.Function):
+    """w_l1 mean|img - ref| + w_ssim (1 - SSIM(img, ref)) + w_depth mean|depth - depth_obs| (C ABI: dgr_ssim_loss_forward /
+    _backward; csrc/ssim.hip).  `depth` / `depth_obs` may be None.  `want_ssim`: return the mean SSIM the forward leaves in its
+    scratch header instead of the loss (with weights (0, -1, 0) the loss is SSIM - 1, whose gradient is SSIM's).  `want_maps`:
+    whether a backward will follow (the forward then writes the three derivative maps it needs)."""
+
+    @staticmethod
+    def forward(ctx, img, depth, ref, depth_obs, shape, w_l1, w_ssim, w_depth, want_maps, want_ssim):
+        from . import _capi
+        lib = _capi.load()
+        img, ref = img.contiguous(), ref.contiguous()
+        if depth is not None:
+            depth, depth_obs = depth.contiguous(), depth_obs.contiguous()
+        n_depth = depth.numel() if depth is not None else 0
+        floats = lib.dgr_ssim_scratch_floats(*shape)
+        if not want_maps:  # the inference form: the scratch ends where the derivative maps would begin
+            floats -= 3 * img.numel()
+        buf = torch.empty((floats + 4,), dtype=torch.float32, device=img.device)
+        weights = (float(w_l1), float(w_ssim), float(w_depth))
+        with _capi.on_device(img.device):
+            if lib.dgr_ssim_loss_forward(_capi.stream_handle(img.device.index), *shape, img.data_ptr(), ref.data_ptr(), n_depth,
+                                         _capi.ptr(depth), _capi.ptr(depth_obs), *weights, buf.data_ptr(), int(want_maps),
+                                         buf[floats:].data_ptr()):
+                raise RuntimeError(_capi.last_error())
+        ctx.save_for_backward(img, ref, depth, depth_obs, buf)
+        ctx.call = (shape, n_depth, weights)
+        return buf[0] if want_ssim else buf[floats]
+
+    @staticmethod
+    def backward(ctx, upstream):
+        from . import _capi
+        lib = _capi.load()
+        img, ref, depth, depth_obs, buf = ctx.saved_tensors
+        shape, n_depth, weights = ctx.call
+        dimg = torch.empty_like(img)
+        ddepth = torch.empty_like(depth) if n_depth else None
+        upstream = upstream.contiguous()
+        with _capi.on_device(img.device):
+            if lib.dgr_ssim_loss_backward(_capi.stream_handle(img.device.index), *shape, img.data_ptr(), ref.data_ptr(), n_depth,
+                                          _capi.ptr(depth), _capi.ptr(depth_obs), *weights, buf.data_ptr(), upstream.data_ptr(),
+                                          dimg.data_ptr(), _capi.ptr(ddepth)):
+                raise RuntimeError(_capi.last_error())
+        return dimg, ddepth, None, None, None, None, None, None, None, None
+
+
+def ssim(img, ref):
+    """Mean SSIM of `img` against `ref` as 3DGS's `ssim(img1, img2, window_size=11, size_average=True)` computes it (11 x 11
+    Gaussian window of sigma 1.5 over the zero-padded images, per channel and per image), as a scalar differentiable with respect
+    to `img`: one tiled kernel each way instead of five depthwise convolutions and their elementwise trail.  float32 GPU tensors
+    [C,H,W] or [V,C,H,W] of one shape; `ref` carries no gradient."""
+    _check_pair("img", img, ref, "ssim")
+    shape = _image_stack(img, "ssim")
+    _check_gpu("ssim", img, ref)
+    return _SsimLoss.apply(img, None, ref, None, shape, 0.0, -1.0, 0.0, _wants_grad(img), True)
+
+
+def l1_ssim_loss(color, depth, color_obs, depth_obs, w_color=1.0, w_depth=0.5, lambda_dssim=0.2):
+    """The mapping loss of 3DGS and the SLAM systems built on it,
+        w_color * ((1 - lambda) * mean|color - color_obs| + lambda * (1 - SSIM(color, color_obs))) + w_depth * mean|depth - depth_obs|,
+    in at most three launches, with both gradient images written by at most two in the backward, none of them with atomics: the
+    same bits on every run, and capturable into a hipGraph.  `color` is [C,H,W] or a stack [V,C,H,W] (then the loss is the mean over
+    the stack: multiply the weights by V for a sum over keyframes); `depth` and `depth_obs` may both be None.  float32 GPU tensors;
+    the observations carry no gradient.  When no input requires a gradient the forward skips the derivative maps."""
+    _check_pair("color", color, color_obs, "l1_ssim_loss")
+    shape = _image_stack(color, "l1_ssim_loss")
+    if (depth is None) != (depth_obs is None):
+        raise ValueError("l1_ssim_loss: depth and depth_obs are given together or both None")
+    if depth is not None:
+        _check_pair("depth", depth, depth_obs, "l1_ssim_loss")
+    _check_gpu("l1_ssim_loss", *(t for t in (color, color_obs, depth, depth_obs) if t is not None))
+    if depth is not None and depth.numel() == 0:
+        depth = depth_obs = None
+    lam = float(lambda_dssim)
+    return _SsimLoss.apply(color, depth, color_obs, depth_obs, shape, float(w_color) * (1.0 - lam), float(w_color) * lam,
+                           float(w_depth) if depth is not None else 0.0, _wants_grad(color, depth), False)
+
+
 def _get(obj, name, default=None):
     v = getattr(obj, name, default)
     return v() if callable(v) and not isinstance(v, torch.Tensor) else v

@@ -12,10 +12,11 @@ Gaussians: every N iterations densify_and_prune consumes the statistics (clone, 
 for the whole model and its Adam moments) and the loop goes on with the new leaves.  --fused renders the keyframe batch through the batched entry points
 instead (slam.render_batch_fused: one forward and one backward call for all keyframes, gradients summed in the kernels).
 --variant full runs the same loop through the -full variant (uncertainty output; it has no track_off, so the pose gradients are
-formed and left unused).
+formed and left unused).  --ssim LAMBDA optimises the standard 3DGS mapping loss instead of plain L1: (1 - LAMBDA) L1 + LAMBDA (1 - SSIM)
+on the colour images plus the depth L1 (slam.l1_ssim_loss: at most three launches forward, two backward, capturable).
 
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
-                             [--keyframes 4]
+                             [--keyframes 4] [--ssim LAMBDA]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -79,12 +80,13 @@ class MapModel:
 
 
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
-                 absgrad=False, densify_every=0):
+                 absgrad=False, densify_every=0, ssim_lambda=0.0):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
     densify_every=N: every N iterations the statistics are consumed by densify_and_prune (not with graph=True: the step
-    changes the number of Gaussians)."""
+    changes the number of Gaussians).
+    ssim_lambda > 0: the loss is slam.l1_ssim_loss with that lambda_dssim instead of slam.l1_loss (0.0: the L1 path, unchanged)."""
     from dgr_amd import light, slam
     from dgr_amd.optim import SparseAdam, add_densification_stats, densify_and_prune
     from dgr_amd.synth import make_scene
@@ -112,17 +114,22 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     seen = torch.zeros(P, dtype=torch.int32, device=dev)
     outs = [None] * keyframes
 
+    def photometric(color, depth, color_obs, depth_obs, w_color, w_depth):
+        if ssim_lambda > 0.0:  # (1 - lambda) L1 + lambda (1 - SSIM) on the colour, L1 on the depth
+            return slam.l1_ssim_loss(color, depth, color_obs, depth_obs, w_color, w_depth, ssim_lambda)
+        return slam.l1_loss(color, depth, color_obs, depth_obs, w_color, w_depth)  # one fused reduction
+
     def loss_fn(out, k):
         outs[k] = out
-        return slam.l1_loss(out["render"], out["depth"], obs[k][0], obs[k][1], 1.0, 0.5)  # one fused reduction
+        return photometric(out["render"], out["depth"], obs[k][0], obs[k][1], 1.0, 0.5)
 
     obs_color, obs_depth = torch.stack([o[0] for o in obs]), torch.stack([o[1] for o in obs])
 
     def batch_loss_fn(out):
-        # the keyframes' L1 losses summed, as ONE fused reduction over the stacked images: sum_k (mean_k |c - c_obs| + 0.5
-        # mean_k |d - d_obs|) = V x the means over the whole stack (the keyframes share a size)
+        # the keyframes' losses summed, as ONE fused reduction over the stacked images: sum_k (mean_k |c - c_obs| + 0.5
+        # mean_k |d - d_obs|) = V x the means over the whole stack (the keyframes share a size; SSIM's mean likewise)
         V = float(out["render"].size(0))
-        return slam.l1_loss(out["render"], out["depth"], obs_color, obs_depth, V * 1.0, V * 0.5)
+        return photometric(out["render"], out["depth"], obs_color, obs_depth, V * 1.0, V * 0.5)
 
     def iteration_fused():
         # the keyframe batch through ONE batched forward and ONE batched backward (dgr_amd.batch): the Gaussians' gradients
@@ -180,9 +187,9 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     if graph:  # (the three eager iterations run inside CapturedStep, on the stream the graph is recorded on)
         from dgr_amd.multiview import CapturedStep
         with torch.no_grad():
-            first = float(torch.stack([slam.l1_loss(*(slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"],
-                                                                  HW=c["HW"], gt_depth=gt, **kw)[k_] for k_ in ("render", "depth")),
-                                                    obs[i][0], obs[i][1], 1.0, 0.5) for i, c in enumerate(cams)]).mean())
+            first = float(torch.stack([photometric(*(slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"],
+                                                                 HW=c["HW"], gt_depth=gt, **kw)[k_] for k_ in ("render", "depth")),
+                                                   obs[i][0], obs[i][1], 1.0, 0.5) for i, c in enumerate(cams)]).mean())
         step = CapturedStep(iteration, warmup=3)
         run = step.replay
     else:
@@ -219,10 +226,15 @@ def main():
     ap.add_argument("--densify-every", type=int, default=0, metavar="N",
                     help="every N iterations clone / split / prune from the accumulated statistics (densify_and_prune); "
                          "off by default, not together with --graph")
+    ap.add_argument("--ssim", type=float, default=0.0, metavar="LAMBDA",
+                    help="the 3DGS mapping loss (1 - LAMBDA) L1 + LAMBDA (1 - SSIM) on the colour images (slam.l1_ssim_loss; 3DGS "
+                         "uses 0.2) instead of plain L1; 0 (default) keeps the L1 loss")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
     args = ap.parse_args()
+    if not 0.0 <= args.ssim <= 1.0:
+        ap.error("--ssim LAMBDA lies in [0, 1]")
     if args.densify_every < 0 or (args.densify_every and args.graph):
         ap.error("--densify-every changes the number of Gaussians: it cannot run inside a recorded hipGraph (drop --graph)")
     import torch as _torch
@@ -232,9 +244,10 @@ def main():
     dev = torch.device("cuda:0")
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
                                     args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
-                                    variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every)
+                                    variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every, ssim_lambda=args.ssim)
     n = float(pc.denom.sum())
     print(("full variant: " if args.variant == "full" else "") + ("absgrad: " if args.absgrad else "") +
+          (f"L1 + D-SSIM (lambda {args.ssim:g}): " if args.ssim > 0 else "") +
           f"loss {l0:.4e} -> {l1:.4e}; {dt * 1e3:.3f} ms per mapping iteration over {args.keyframes} keyframes"
           f" ({dt / args.keyframes * 1e3:.3f} ms per keyframe); {int((pc.denom > 0).sum())} Gaussians seen,"
           f" {n:.0f} (Gaussian, view) statistics accumulated" +

@@ -317,6 +317,30 @@ int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const f
                          const float* depth_obs, float w_color, float w_depth, const float* upstream, float* dL_dcolor,
                          float* dL_ddepth);
 
+/* ---- the standard mapping loss: L1 + D-SSIM on the colour images, L1 on the depth (csrc/ssim.hip) ----
+ *   loss = w_l1 * mean|img - ref| + w_ssim * (1 - SSIM(img, ref)) + w_depth * mean|depth - depth_obs|
+ * over a contiguous [n_images, channels, height, width] float stack.  SSIM is 3DGS's ssim(window_size=11, size_average=True):
+ * per channel and image, the 11 x 11 window g g^T with g[i] ~ exp(-(i - 5)^2 / (2 * 1.5^2)) normalised to sum 1, the images
+ * zero-padded by 5, C1 = 0.01^2, C2 = 0.03^2, the mean of the map over every element.  n_depth = 0 drops the depth term.
+ * `scratch`: dgr_ssim_scratch_floats() floats, 16-byte aligned (0 for a shape it refuses: a non-positive dimension,
+ *   n_images * channels above 65535, height or width above 2^20) = 4 header floats, the workgroups' partial sums and the three
+ *   derivative maps (3 * n_images * channels * height * width floats, at the end).  After the forward scratch[0] holds the mean
+ *   SSIM, scratch[1] mean|img - ref| and scratch[2] mean|depth - depth_obs|.
+ * `want_maps` = 0 is the inference form: the maps are neither written nor needed (scratch may end where they would begin) and
+ *   the backward must not be called: one that is fills dL_dimg with NaN.
+ * The forward is at most three launches, the backward at most two; neither synchronises the host or allocates, so both can be
+ * captured into a hipGraph, and neither uses atomics: the loss and both gradient images carry the same bits on every run.
+ * The backward takes the forward's arguments and scratch, writes dL_dimg = d loss / d img * (*upstream) (`upstream` == NULL
+ * meaning 1) once and, with n_depth > 0, dL_ddepth.  `ref` and `depth_obs` receive no gradient.  Every argument error returns
+ * DGR_ERR_BAD_ARGUMENT with a message before any device call. */
+long dgr_ssim_scratch_floats(int n_images, int channels, int height, int width);
+int dgr_ssim_loss_forward(void* stream, int n_images, int channels, int height, int width, const float* img, const float* ref,
+                          long n_depth, const float* depth, const float* depth_obs, float w_l1, float w_ssim, float w_depth,
+                          float* scratch, int want_maps, float* loss);
+int dgr_ssim_loss_backward(void* stream, int n_images, int channels, int height, int width, const float* img, const float* ref,
+                           long n_depth, const float* depth, const float* depth_obs, float w_l1, float w_ssim, float w_depth,
+                           const float* scratch, const float* upstream, float* dL_dimg, float* dL_ddepth /* NULL when n_depth == 0 */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a

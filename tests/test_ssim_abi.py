@@ -1,0 +1,145 @@
+"""The SSIM loss entry points (include/dgr_hip.h: dgr_ssim_*) and their Python surface without a GPU: declared, exported and
+bound; the scratch size; every argument error refused with a message before any device call; and the formula the backward kernel
+implements, pinned against autograd in float64."""
+import ctypes as C
+
+import pytest
+import torch
+
+from dgr_amd import _capi, slam
+
+import ssim_model as M
+from test_capi_symbols import declared_symbols
+
+NAMES = ("dgr_ssim_scratch_floats", "dgr_ssim_loss_forward", "dgr_ssim_loss_backward")
+FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
+
+
+def test_symbols_are_declared_exported_and_bound():
+    lib = C.CDLL(_capi.LIB_PATH)
+    for name in NAMES:
+        assert name in declared_symbols(), name
+        assert name in _capi.exported_symbols(), name
+        assert hasattr(lib, name), name
+    assert len(_capi._SIGS["dgr_ssim_loss_forward"][1]) == 16 and len(_capi._SIGS["dgr_ssim_loss_backward"][1]) == 17
+    assert _capi._SIGS["dgr_ssim_scratch_floats"][0] is C.c_long
+
+
+def test_scratch_size():
+    f = _capi.load().dgr_ssim_scratch_floats
+    for bad in ((0, 3, 8, 8), (1, 0, 8, 8), (1, 3, 0, 8), (1, 3, 8, 0), (-1, 3, 8, 8), (1, 3, -8, 8), (65536, 1, 8, 8),
+                (256, 256, 8, 8)):
+        assert f(*bad) == 0, bad
+    assert f(65535, 1, 1, 1) > 0 and f(255, 257, 1, 1) > 0
+    base = (2, 3, 40, 70)
+    for shape in (base, (1, 1, 1, 1), (4, 3, 480, 640), (1, 3, 1080, 1920), (8, 3, 4000, 6000)):
+        n = shape[0] * shape[1] * shape[2] * shape[3]
+        assert 3 * n < f(*shape) <= 3 * n + n // 16 + 1024, shape   # the maps, and partial sums that stay a small share
+    for dim in range(4):  # monotone in each dimension (also across a tile boundary: 32 -> 33 columns, 16 -> 17 rows)
+        sizes = []
+        for v in (1, 2, 16, 17, 32, 33, 100):
+            shape = list(base)
+            shape[dim] = v
+            sizes.append(f(*shape))
+        assert all(b > a for a, b in zip(sizes, sizes[1:])), (dim, sizes)
+
+
+def _refused(rc, name, text):
+    err = _capi.last_error()
+    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in err and err.startswith(name + ": "), (rc, err)
+
+
+def _forward(shape=(1, 3, 8, 8), img=FAKE, ref=FAKE, n_depth=0, depth=None, depth_obs=None, scratch=FAKE, loss=FAKE):
+    return _capi.load().dgr_ssim_loss_forward(None, *shape, img, ref, n_depth, depth, depth_obs, 0.8, 0.2, 0.5, scratch, 1, loss)
+
+
+def _backward(shape=(1, 3, 8, 8), img=FAKE, ref=FAKE, n_depth=0, depth=None, depth_obs=None, scratch=FAKE, dimg=FAKE, ddepth=None):
+    return _capi.load().dgr_ssim_loss_backward(None, *shape, img, ref, n_depth, depth, depth_obs, 0.8, 0.2, 0.5, scratch, None,
+                                               dimg, ddepth)
+
+
+CASES = [
+    (dict(img=None), "img or ref is NULL"),
+    (dict(ref=None), "img or ref is NULL"),
+    (dict(scratch=None), "scratch is NULL"),
+    (dict(scratch=FAKE + 4), "16-byte aligned"),
+    (dict(shape=(0, 3, 8, 8)), "must be positive"),
+    (dict(shape=(1, 0, 8, 8)), "must be positive"),
+    (dict(shape=(1, 3, -1, 8)), "must be positive"),
+    (dict(shape=(1, 3, 8, 0)), "must be positive"),
+    (dict(n_depth=-1), "n_depth is negative"),
+    (dict(n_depth=64, depth=None, depth_obs=FAKE), "NULL depth or depth_obs"),
+    (dict(n_depth=64, depth=FAKE, depth_obs=None), "NULL depth or depth_obs"),
+    (dict(shape=(65536, 1, 8, 8)), "at most 65535"),
+    (dict(shape=(300, 300, 8, 8)), "at most 65535"),
+]
+IDS = ["img-null", "ref-null", "scratch-null", "scratch-misaligned", "V=0", "C=0", "H<0", "W=0", "n_depth<0", "depth-null",
+       "depth_obs-null", "V-too-large", "VC-too-large"]
+
+
+@pytest.mark.parametrize("case, text", CASES, ids=IDS)
+def test_forward_refuses_bad_arguments_before_touching_the_gpu(case, text):
+    _refused(_forward(**case), "dgr_ssim_loss_forward", text)
+
+
+@pytest.mark.parametrize("case, text", CASES, ids=IDS)
+def test_backward_refuses_bad_arguments_before_touching_the_gpu(case, text):
+    _refused(_backward(**case), "dgr_ssim_loss_backward", text)
+
+
+def test_null_outputs_are_refused():
+    _refused(_forward(loss=None), "dgr_ssim_loss_forward", "loss is NULL")
+    _refused(_backward(dimg=None), "dgr_ssim_loss_backward", "dL_dimg is NULL")
+    _refused(_backward(n_depth=64, depth=FAKE, depth_obs=FAKE, ddepth=None), "dgr_ssim_loss_backward", "NULL dL_ddepth")
+
+
+def test_python_surface_refuses_what_it_cannot_read():
+    """Every check runs on the host, the device check last: CPU tensors reach each of them and never the library."""
+    r = torch.rand
+    x, y = r(3, 8, 8), r(3, 8, 8)
+    for fn in (slam.ssim, lambda a, b: slam.l1_ssim_loss(a, None, b, None)):
+        with pytest.raises(ValueError, match="GPU tensors"):
+            fn(x, y)
+        with pytest.raises(ValueError, match="GPU tensors"):
+            fn(x[None], y[None])
+        with pytest.raises(ValueError, match="float32"):
+            fn(x.double(), y.double())
+        with pytest.raises(ValueError, match="float32"):
+            fn(x, y.half())
+        with pytest.raises(ValueError, match="must be a tensor"):
+            fn(x, None)
+        for a, b, text in ((r(3, 8, 8), r(3, 8, 9), "differ in shape"), (r(3, 8, 8), r(1, 3, 8, 8), "differ in shape"),
+                           (r(8, 8), r(8, 8), r"\[C,H,W\] or \[V,C,H,W\]"), (r(1, 2, 3, 8, 8), r(1, 2, 3, 8, 8), r"\[C,H,W\]"),
+                           (r(0, 3, 8, 8), r(0, 3, 8, 8), "cannot read"), (r(300, 300, 2, 2), r(300, 300, 2, 2), "cannot read")):
+            with pytest.raises(ValueError, match=text):
+                fn(a, b)
+    with pytest.raises(ValueError, match="together or both None"):
+        slam.l1_ssim_loss(x, r(1, 8, 8), y, None)
+    with pytest.raises(ValueError, match="differ in shape"):
+        slam.l1_ssim_loss(x, r(1, 8, 8), y, r(1, 8, 7))
+    with pytest.raises(ValueError, match="float32"):
+        slam.l1_ssim_loss(x, r(1, 8, 8).double(), y, r(1, 8, 8).double())
+    with pytest.raises(ValueError, match="GPU tensors"):
+        slam.l1_ssim_loss(x, r(1, 8, 8), y, r(1, 8, 8))
+
+
+def test_three_map_gradient_is_the_autograd_gradient():
+    """The formula the backward kernel implements, against float64 autograd of the model, on every parity case."""
+    for kind in M.KINDS:
+        for shape in M.SHAPES:
+            x, y = M.inputs(kind, shape)
+            auto = M.model(x, y)["grad"]
+            ana = M.analytic_grad(x, y)
+            scale = float(auto.abs().max())
+            assert scale > 0 and float((ana - auto).abs().max()) <= 1e-10 * scale, (kind, shape)
+
+
+def test_the_model_is_3dgs_ssim():
+    """Spot values that follow from the definition: identical images give 1; the window sums to 1 and is symmetric."""
+    g = M.window_1d().double()
+    assert abs(float(g.sum()) - 1) < 1e-7 and torch.equal(g, g.flip(0)) and float(g[5]) == float(g.max())
+    x, _ = M.inputs("rand", (1, 3, 17, 33))
+    assert abs(float(M.model(x, x)["ssim"]) - 1) < 1e-12
+    x, y = M.inputs("rand", (2, 3, 17, 33))
+    per_view = [float(M.model(x[k], y[k])["ssim"]) for k in range(2)]
+    assert abs(float(M.model(x, y)["ssim"]) - sum(per_view) / 2) < 1e-12
