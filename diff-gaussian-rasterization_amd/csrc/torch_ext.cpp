@@ -1,11 +1,17 @@
-// torch_ext.cpp -- compiled `_C` of the light variant: the counterpart of the reference's pybind11 torch extension
-// (L/ext.cpp:15-19, L/rasterize_points.cu:35-256) over the gfx950 C ABI (include/dgr_hip.h).
+// torch_ext.cpp -- compiled `_C` and compiled autograd nodes of both variants: the counterpart of the reference's pybind11 torch
+// extensions (L/ext.cpp:15-19, L/rasterize_points.cu:35-256; F/ext.cpp:15-19, F/rasterize_points.cu:35-239) over the gfx950 C ABI
+// (include/dgr_hip.h).
 //
 // torch supplies device memory, the current HIP stream and the device guard; every compute call goes through the C
-// ABI in lib/libdgr_hip.so.  The Python side (dgr_amd/light.py) keeps only the policy that is cheap there -- the
-// binning capacity learned per shape and the list of lazily checked status tickets -- and hands it in / gets it back
-// as plain integers, so that a forward costs one pybind call instead of ~40 Python-level tensor operations and a
-// 40-argument ctypes call (profiles/host_breakdown.py: 137 + 162 us per view in the ctypes binding).
+// ABI in lib/libdgr_hip.so.  The Python side (dgr_amd/light.py, full.py, batch.py, batch_full.py) keeps only the policy that is
+// cheap there -- the binning capacity learned per shape and the list of lazily checked status tickets (dgr_amd/_binning.py) -- and
+// hands it in / gets it back as plain integers, so that a forward costs one pybind call instead of ~40 Python-level tensor
+// operations and a 40-argument ctypes call (profiles/host_breakdown.py: 137 + 162 us per view in the ctypes binding).
+//
+// What differs between the variants is in two descriptions, `Light` and `Full`: the output set and its layout, the entry points
+// and their trailing arguments, the gradient images, what a node saves beyond the common set.  Everything else is one template
+// over them: forward_core, backward, Node / apply, forward_batch, backward_batch.  The host profile, the tensor windows and the
+// resident backward scratch are in csrc/torch_support.h.
 #include <torch/extension.h>
 
 // (a ROCm build of torch calls its devices "cuda": the guard and stream accessors that accept them are the
@@ -14,63 +20,16 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPCachingAllocatorMasqueradingAsCUDA.h>
 
-#include <atomic>
-#include <chrono>
-#include <mutex>
-#include <stdexcept>
-#include <string>
+#include <array>
 #include <tuple>
-#include <vector>
 
-#include "dgr_hip.h"
+#include "torch_support.h"
 
 namespace {
 
-using at::Tensor;
-
-// ---- host-side profile of the binding (DGR_HOST_PROF=1; profiles/host_breakdown.py prints it): where a forward's and a
-// backward's microseconds on the issuing thread go.  Off: one predictable branch per probe.
-const bool g_host_prof = [] { const char* e = getenv("DGR_HOST_PROF"); return e && e[0] == '1'; }();
-struct HostProf {
-    const char* name;
-    double us = 0;
-    long n = 0;
-};
-HostProf g_hp[] = {{"fwd: apply() total"}, {"fwd: node forward()"}, {"fwd: core: guard + f32c"}, {"fwd: core: output allocations"},
-                   {"fwd: core: status arm"}, {"fwd: core: state allocation"}, {"fwd: core: C ABI (launches)"},
-                   {"fwd: save_for_backward + saved_data"}, {"bwd: node backward()"}, {"bwd: arena + scratch + dview"},
-                   {"bwd: C ABI (launches)"}, {"bwd: unpack saved"}};
-enum { HP_APPLY, HP_FWD, HP_PRELUDE, HP_OUT_ALLOC, HP_ARM, HP_STATE_ALLOC, HP_FWD_C, HP_SAVE, HP_BWD, HP_BWD_ALLOC, HP_BWD_C, HP_UNPACK };
-struct Probe {
-    int id;
-    std::chrono::steady_clock::time_point t0;
-    explicit Probe(int i) : id(g_host_prof ? i : -1) { if (id >= 0) t0 = std::chrono::steady_clock::now(); }
-    void stop() {
-        if (id < 0) return;
-        g_hp[id].us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-        g_hp[id].n++;
-        id = -1;
-    }
-    ~Probe() { stop(); }
-};
-std::string host_prof_dump(bool reset) {
-    std::string out;
-    for (auto& h : g_hp) {
-        if (h.n) out += std::string(h.name) + ": " + std::to_string(h.us / (double)h.n) + " us x " + std::to_string(h.n) + "\n";
-        if (reset) { h.us = 0; h.n = 0; }
-    }
-    return out;
-}
-
-[[noreturn]] void fail(int rc) {
-    const std::string msg = dgr_last_error();
-    if (rc == DGR_ERR_PREFILTERED) throw std::runtime_error("Point is filtered although prefiltered is set. This shouldn't happen!");
-    if (rc == DGR_ERR_BAD_ARGUMENT) throw std::runtime_error("dgr_hip: bad argument: " + msg);
-    throw std::runtime_error("dgr_hip: error " + std::to_string(rc) + ": " + msg);
-}
-inline void check(long rc) {
-    if (rc < 0) fail((int)rc);
-}
+using namespace dgr_ext;
+using torch::autograd::AutogradContext;
+using torch::autograd::variable_list;
 
 // contiguous fp32 tensor on `dev` (L/rasterize_points.cu:101-125 calls .contiguous() on every input)
 inline Tensor f32c(const Tensor& t, const c10::Device& dev) {
@@ -96,6 +55,12 @@ inline T* ptr(const Tensor& t) {
 }
 inline char* bytes(const Tensor& t) { return t.numel() == 0 ? nullptr : reinterpret_cast<char*>(t.data_ptr()); }
 inline void* stream_of(const c10::Device& dev) { return (void*)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index()).stream(); }
+// row v of a [V, ...] tensor (NULL for an empty one)
+inline char* row_bytes(const Tensor& t, long v) { return t.numel() == 0 ? nullptr : reinterpret_cast<char*>(t.data_ptr()) + v * t.stride(0) * t.element_size(); }
+template <typename T>
+inline T* row(const Tensor& t, long v) { return reinterpret_cast<T*>(row_bytes(t, v)); }
+// a batch's perspec_matrix: one [4,4] for every view, or [V,4,4] (a projection per view)
+inline float* perspec_row(const Tensor& t, long v) { return t.dim() == 3 ? row<float>(t, v) : ptr<float>(t); }
 
 // PyTorch's rule for a tensor read on another stream than the one it was allocated on: tell the caching allocator, or
 // the block is handed out again while that stream's kernels still read it.  A forward issued on a side stream (views in
@@ -105,13 +70,13 @@ inline void* stream_of(const c10::Device& dev) { return (void*)c10::hip::getCurr
 // transposed perspec_matrix is the usual case) the conversion reads it on this stream and its result is a temporary of
 // this stream.  On the default stream: one comparison.
 const bool g_record_inputs = [] { const char* e = getenv("DGR_RECORD_INPUT_STREAMS"); return !(e && e[0] == '0'); }();
-inline void keep_until_read(const c10::Device& dev, std::initializer_list<const Tensor*> inputs) {
+inline void keep_until_read(const c10::Device& dev, const Tensor* const* inputs, size_t n) {
     if (!g_record_inputs) return;  // (DGR_RECORD_INPUT_STREAMS=0: the caller keeps its inputs alive until the streams are joined)
     const auto s = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev.index());
     if (s == c10::hip::getDefaultHIPStreamMasqueradingAsCUDA(dev.index())) return;
-    for (const Tensor* t : inputs)
-        if (t->defined() && t->numel() != 0 && t->is_cuda())
-            c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::recordStreamMasqueradingAsCUDA(t->storage().data_ptr(), s);
+    for (size_t i = 0; i < n; i++)
+        if (inputs[i]->defined() && inputs[i]->numel() != 0 && inputs[i]->is_cuda())
+            c10::hip::HIPCachingAllocatorMasqueradingAsCUDA::recordStreamMasqueradingAsCUDA(inputs[i]->storage().data_ptr(), s);
 }
 
 struct Alloc {
@@ -123,7 +88,7 @@ char* resize_cb(size_t n, void* user) {  // the reference's resizeFunctional (L/
     *a->t = at::empty({(long long)std::max<size_t>(n, 1)}, at::TensorOptions().dtype(at::kByte).device(a->dev));
     return reinterpret_cast<char*>(a->t->data_ptr());
 }
-// dgr_light_forward takes ONE user pointer for its three callbacks: three trampolines route to three tensors
+// the callback entry points take ONE user pointer for their three callbacks: three trampolines route to three tensors
 struct Alloc3 {
     Alloc geom, binning, img;
 };
@@ -131,107 +96,7 @@ char* cb_geom(size_t n, void* u) { return resize_cb(n, &static_cast<Alloc3*>(u)-
 char* cb_binning(size_t n, void* u) { return resize_cb(n, &static_cast<Alloc3*>(u)->binning); }
 char* cb_img(size_t n, void* u) { return resize_cb(n, &static_cast<Alloc3*>(u)->img); }
 
-// ---- several tensors over ONE allocation.  A forward used to make twelve at::empty calls and a backward three plus
-// sixteen narrow / view calls for the gradient arena's segments -- each a trip through the dispatcher and, for the
-// allocations, the caching allocator's lock.  view_of builds the TensorImpl of a contiguous window into `base`'s storage
-// directly (what as_strided does underneath, without the dispatch); byte offsets are multiples of 256.
-inline size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
-// The raw construction below was validated on PyTorch 2.10 (TensorImpl::VIEW constructor, set_sizes_contiguous, set_storage_offset,
-// wrap_tensor_impl; the autograd engine's saved-tensor version check on such outputs: tests/test_hip_binding_guard.py).  Built
-// against another PyTorch it is NOT used unless DGR_RAW_VIEWS=1 asks for it; DGR_RAW_VIEWS=0 switches it off anywhere; and the
-// first view made in a process is checked against the dispatcher's own view of the same window (pointer, sizes, strides, dtype,
-// aliasing, a fresh version counter) -- a mismatch falls back for good, with one warning.  The fall-back is at::from_blob over the
-// window, its deleter holding `base`: a tensor of its own (own storage object, own version counter, not a view in autograd's
-// books), like the raw one.  NOT narrow / view / as_strided: a custom Function that returns several views of one base may not have
-// them edited in place at all, and views of one base share a version counter -- editing `color` would then invalidate the saved
-// `opacity_map`; neither happens with the reference's separately allocated outputs.
-inline Tensor dispatcher_view(const Tensor& base, size_t byte_off, c10::IntArrayRef sizes, at::ScalarType dt) {
-    Tensor keep = base;
-    return at::from_blob(static_cast<char*>(base.data_ptr()) + byte_off, sizes, [keep](void*) mutable { keep = Tensor(); },
-                         at::TensorOptions().dtype(dt).device(base.device()));
-}
-inline Tensor raw_view(const Tensor& base, size_t byte_off, c10::IntArrayRef sizes, at::ScalarType dt) {
-    auto impl = c10::make_intrusive<c10::TensorImpl>(c10::TensorImpl::VIEW, c10::Storage(base.storage()), base.key_set(),
-                                                     c10::scalarTypeToTypeMeta(dt));
-    impl->set_sizes_contiguous(sizes);
-    impl->set_storage_offset((int64_t)(byte_off / c10::elementSize(dt)));
-    return Tensor::wrap_tensor_impl(std::move(impl));
-}
-std::atomic<int> g_raw_views{-1};  // -1: not decided yet, 0: dispatcher views, 1: raw views
-inline bool decide_raw_views(const Tensor& base, size_t byte_off, c10::IntArrayRef sizes, at::ScalarType dt) {
-    const char* e = getenv("DGR_RAW_VIEWS");
-    if (e && e[0] == '0') return false;
-    // validated on PyTorch 2.10; later releases take the self-check below (which the first view of every process runs anyway),
-    // earlier ones the dispatcher's windows unless DGR_RAW_VIEWS=1 asks for the check
-#if !(defined(TORCH_VERSION_MAJOR) && (TORCH_VERSION_MAJOR > 2 || (TORCH_VERSION_MAJOR == 2 && TORCH_VERSION_MINOR >= 10)))
-    if (!(e && e[0] == '1')) return false;
-#endif
-    bool ok = false;
-    try {
-        const Tensor a = raw_view(base, byte_off, sizes, dt), b = dispatcher_view(base, byte_off, sizes, dt);
-        ok = a.data_ptr() == b.data_ptr() && a.sizes() == b.sizes() && a.strides() == b.strides() && a.scalar_type() == b.scalar_type() &&
-             a.device() == b.device() && a.is_alias_of(base) && a._version() == 0 && a.is_contiguous() && !a.requires_grad() &&
-             !a.is_view() && a.numel() == b.numel() && a.key_set() == b.key_set();
-    } catch (...) {
-        ok = false;
-    }
-    if (!ok) TORCH_WARN_ONCE("dgr_hip: the raw tensor views of csrc/torch_ext.cpp do not behave as on the PyTorch they were validated on; "
-                             "using at::from_blob windows instead");
-    return ok;
-}
-inline Tensor view_of(const Tensor& base, size_t byte_off, c10::IntArrayRef sizes, at::ScalarType dt) {
-    int mode = g_raw_views.load(std::memory_order_relaxed);
-    if (mode < 0) {
-        mode = decide_raw_views(base, byte_off, sizes, dt) ? 1 : 0;
-        g_raw_views.store(mode, std::memory_order_relaxed);
-    }
-    return mode ? raw_view(base, byte_off, sizes, dt) : dispatcher_view(base, byte_off, sizes, dt);
-}
-// row v of a [V, ...] tensor (NULL for an empty one)
-inline char* row_bytes(const Tensor& t, long v) { return t.numel() == 0 ? nullptr : reinterpret_cast<char*>(t.data_ptr()) + v * t.stride(0) * t.element_size(); }
-template <typename T>
-inline T* row(const Tensor& t, long v) { return reinterpret_cast<T*>(row_bytes(t, v)); }
-// a batch's perspec_matrix: one [4,4] for every view, or [V,4,4] (a projection per view)
-inline float* perspec_row(const Tensor& t, long v) { return t.dim() == 3 ? row<float>(t, v) : ptr<float>(t); }
-inline Tensor bytes_on(const c10::Device& dev, size_t n) {
-    return at::empty({(long long)std::max<size_t>(n, 1)}, at::TensorOptions().dtype(at::kByte).device(dev));
-}
-
-// The three opaque state buffers of a presized forward as windows of one allocation (they are saved and released together).
-struct StateArena {
-    Tensor geom, binning, img;
-    StateArena(const c10::Device& dev, int P, int W, int H, long cap) {
-        const size_t ng = up256(dgr_geometry_bytes(P)), ni = up256(dgr_image_bytes(W, H)), nb = up256(dgr_binning_bytes((int)cap, W, H));
-        const Tensor a = bytes_on(dev, ng + ni + nb);
-        geom = view_of(a, 0, {(long long)ng}, at::kByte);
-        img = view_of(a, ng, {(long long)ni}, at::kByte);
-        binning = view_of(a, ng + ni, {(long long)nb}, at::kByte);
-    }
-};
-
-// Strict mode's one host wait: the forward reports through an armed status slot (pinned host memory written by the forward
-// blend's first workgroup, include/dgr_hip.h: dgr_status_arm) and the host polls that memory -- the reference's blocking copy
-// of num_rendered (L/cuda_rasterizer/rasterizer_impl.cu:287) without the copy, the event and the wake-up, and with the
-// longest-list report that lets the next forward of the shape skip the tile schedule.  While a hipGraph is recorded nothing
-// can be read back: strict mode cannot be captured (as before).
-template <typename Run>
-inline void strict_status(Run& run, long cap, int* s, void* st) {
-    // (a status word cannot be read back while the stream records a hipGraph: the wait below would never end)
-    if (dgr_stream_is_capturing(st))
-        throw std::runtime_error("strict status mode (one host wait per forward) cannot run while its stream is being captured into a "
-                                 "hipGraph: use the lazy mode (DGR_SYNC_MODE=lazy), after a few eager forwards of the same shape");
-    const long ticket = dgr_status_arm();
-    check(ticket);
-    try {
-        run(cap);
-    } catch (...) {
-        int unused[4];
-        (void)dgr_status_poll(ticket, 1, unused);  // (completed by the library: releases the slot)
-        throw;
-    }
-    check(dgr_status_poll(ticket, 1, s));
-}
-
+// ------------------------------------------------------------------------------------------------ forward
 // A forward's inputs as contiguous fp32 tensors on the Gaussians' device, under its device guard (one-view forwards: one camera;
 // batches: [V, ...] per camera)
 inline c10::Device forward_device(const Tensor& means3D) {
@@ -254,193 +119,75 @@ struct FwdInputs {
         M = sh.numel() != 0 ? (int)sh.size(1) : 0;
     }
 };
+// The scene prefix of the forward entry points' arguments (include/dgr_hip.h), as a tuple that a call is applied to between its own
+// head and tail.  `camera`: the one-view entry points' (viewmatrix, projmatrix, campos); none for the batched ones, whose cameras are
+// in their per-view structs
+template <typename... Camera>
+inline auto scene_args(const FwdInputs& in, long degree, long W, long H, double scale_modifier, double tan_fovx, double tan_fovy,
+                       bool prefiltered, Camera... camera) {
+    return std::make_tuple(in.P, (int)degree, in.M, ptr<float>(in.bg), (int)W, (int)H, ptr<float>(in.means3D), ptr<float>(in.sh),
+                           ptr<float>(in.colors), ptr<float>(in.opacity), ptr<float>(in.scales), (float)scale_modifier,
+                           ptr<float>(in.rotations), ptr<float>(in.cov3D), camera..., (float)tan_fovx, (float)tan_fovy,
+                           prefiltered ? 1 : 0);
+}
+
+// What a forward reports beside its tensors: num_rendered or -1, num_related (full) or -1, status ticket or -1, the capacity used
+// and the device status word.  Python gets it first in every one-view result (dgr_amd/_binning.py: compiled_forward).
+struct FwdReport {
+    long rendered = -1, related = -1, ticket = -1, cap = 0;
+    Tensor status;
+    std::tuple<long, long, long, long, Tensor> py() const { return {rendered, related, ticket, cap, status}; }
+};
+using PyForward = std::tuple<std::tuple<long, long, long, long, Tensor>, std::vector<Tensor>>;
+// ... and its tensors; a variant leaves those it does not have undefined (`unc`: the light variant's gau_uncertainty [P,1], the
+// full one's uncertainty image)
+struct Fwd : FwdReport {
+    Tensor color, depth, median, var, alpha, unc, radii, px, geom, binning, img;
+};
 
 // mode: 0 = callback entry point (the strict mirror: allocation callbacks + the reference's blocking read),
 //       1 = presized, strict: one host wait until num_rendered is known; retries a too-small capacity itself,
 //       2 = presized, lazy: no host synchronisation; returns a status ticket (dgr_status_post) or -1 while capturing.
-struct FwdCounts {
-    long rendered = -1, ticket = -1, cap = 0;
-};
-// Modes 1 and 2 around `run(cap)`: the variant's state allocation and presized entry point
+// Modes 1 and 2 around `run(cap)`: the state allocation and the variant's presized entry point.  The forward reports through an
+// armed status slot (pinned host memory written by the forward blend's first workgroup, include/dgr_hip.h: dgr_status_arm): no
+// copy, no event.  Strict mode's one host wait polls that memory -- the reference's blocking copy of num_rendered
+// (L/cuda_rasterizer/rasterizer_impl.cu:287) without the copy and the wake-up, and with the longest-list report that lets the next
+// forward of the shape skip the tile schedule.  While a hipGraph is recorded nothing can be read back: no slot is armed, and
+// strict mode, whose wait would never end, cannot be captured.
 template <typename Run>
-void presized_forward(Run& run, long capacity, long mode, void* st, FwdCounts& o) {
-    if (mode == 2) {
-        // the status word comes back through pinned host memory written by the binning kernel (dgr_status_arm): no copy, no
-        // event; while a hipGraph is being recorded nothing can be read back
+void presized_forward(Run& run, long capacity, long mode, void* st, FwdReport& o) {
+    const bool capturing = dgr_stream_is_capturing(st);
+    if (capturing && mode != 2)
+        throw std::runtime_error("strict status mode (one host wait per forward) cannot run while its stream is being captured into a "
+                                 "hipGraph: use the lazy mode (DGR_SYNC_MODE=lazy), after a few eager forwards of the same shape");
+    for (long cap = capacity;;) {
+        long ticket = -1;
         {
             Probe p_arm(HP_ARM);
-            if (!dgr_stream_is_capturing(st)) {
-                o.ticket = dgr_status_arm();
-                check(o.ticket);
-            }
+            if (!capturing) check(ticket = dgr_status_arm());
         }
         try {
-            run(capacity);
+            run(cap);
         } catch (...) {
             int unused[4];
-            if (o.ticket >= 0) (void)dgr_status_poll(o.ticket, 1, unused);  // (completed by the library: releases the slot)
+            if (ticket >= 0) (void)dgr_status_poll(ticket, 1, unused);  // (completed by the library: releases the slot)
             throw;
         }
-        o.cap = capacity;
-        return;
-    }
-    long cap = capacity;
-    for (;;) {
+        o.cap = cap;
+        if (mode == 2) {
+            o.ticket = ticket;
+            return;
+        }
         int s[4] = {0, 0, 0, 0};
-        strict_status(run, cap, s, st);  // the one host wait of this forward: until num_rendered is known
+        check(dgr_status_poll(ticket, 1, s));  // the one host wait of this forward: until num_rendered is known
         if (s[2]) throw std::runtime_error("Point is filtered although prefiltered is set. This shouldn't happen!");
         o.rendered = s[0];
-        if (o.rendered <= cap) break;
+        if (o.rendered <= cap) return;
         cap = (long)(o.rendered * 1.1) + 4096;  // overflow: every tile list was left empty; run again
     }
-    o.cap = cap;
 }
 
-struct LightFwd : FwdCounts {
-    Tensor status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px;
-};
-LightFwd light_forward_core(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
-                            const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                            const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
-                            double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_,
-                            bool prefiltered, bool debug, long capacity, long mode) {
-    Probe p_pre(HP_PRELUDE);
-    const FwdInputs in(forward_device(means3D_), background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrix_,
-                       gt_depth_, projmatrix_, sh_, campos_);
-    const c10::Device dev = in.dev;
-    const int P = in.P, M = in.M;
-    keep_until_read(dev, {&means3D_, &background, &colors_, &opacity_, &scales_, &rotations_, &cov3D_, &viewmatrix_, &projmatrix_,
-                          &campos_, &gt_depth_, &sh_});
-    const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
-    p_pre.stop();
-    Probe p_out(HP_OUT_ALLOC);
-    LightFwd o;
-    // allocation 1: the five images (every pixel is written by the blend kernel); allocation 2: radii (written for every
-    // Gaussian), the two median statistics (cleared by the kernels) and the status word
-    const size_t N = (size_t)H * (size_t)W, n1 = up256(4 * N), np = up256(4 * (size_t)P);
-    const Tensor images = bytes_on(dev, up256(12 * N) + 4 * n1);
-    o.color = view_of(images, 0, {3, H, W}, at::kFloat);
-    o.depth = view_of(images, up256(12 * N), {1, H, W}, at::kFloat);
-    o.median = view_of(images, up256(12 * N) + n1, {1, H, W}, at::kFloat);
-    o.var = view_of(images, up256(12 * N) + 2 * n1, {1, H, W}, at::kFloat);
-    o.alpha = view_of(images, up256(12 * N) + 3 * n1, {1, H, W}, at::kFloat);
-    const Tensor per_gaussian = bytes_on(dev, 3 * np + 256);
-    o.radii = view_of(per_gaussian, 0, {P}, at::kInt);
-    o.unc = view_of(per_gaussian, np, {P, 1}, at::kFloat);
-    o.px = view_of(per_gaussian, 2 * np, {P, 1}, at::kInt);
-    o.status = view_of(per_gaussian, 3 * np, {4}, at::kInt);
-    void* st = stream_of(dev);
-    p_out.stop();
-
-    if (mode == 0 || P == 0) {
-        o.geom = at::empty({0}, u8); o.binning = at::empty({0}, u8); o.img = at::empty({0}, u8);
-        Alloc3 al{{&o.geom, dev}, {&o.binning, dev}, {&o.img, dev}};
-        const int rc = dgr_light_forward(st, cb_geom, cb_binning, cb_img, &al, P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
-                                         ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
-                                         ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
-                                         ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx,
-                                         (float)tan_fovy, prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth),
-                                         ptr<float>(o.median), ptr<float>(o.alpha), ptr<float>(in.gt), ptr<float>(o.var),
-                                         ptr<float>(o.unc), ptr<int>(o.px), ptr<int>(o.radii), debug ? 1 : 0);
-        check(rc);
-        o.rendered = o.cap = rc;
-        return o;
-    }
-    auto run = [&](long cap) {
-        Probe p_st(HP_STATE_ALLOC);
-        const StateArena sa(dev, P, (int)W, (int)H, cap);  // allocation 3
-        o.geom = sa.geom; o.binning = sa.binning; o.img = sa.img;
-        p_st.stop();
-        Probe p_c(HP_FWD_C);
-        check(dgr_light_forward_presized(st, (char*)o.geom.data_ptr(), (char*)o.binning.data_ptr(), (int)cap, (char*)o.img.data_ptr(),
-                                         o.status.data_ptr<int>(), P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
-                                         ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
-                                         ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
-                                         ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx,
-                                         (float)tan_fovy, prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth),
-                                         ptr<float>(o.median), ptr<float>(o.alpha), ptr<float>(in.gt), ptr<float>(o.var),
-                                         ptr<float>(o.unc), ptr<int>(o.px), ptr<int>(o.radii)));
-    };
-    presized_forward(run, capacity, mode, st, o);
-    if (mode != 2 && debug) check(hipStreamSynchronize((hipStream_t)st) == hipSuccess ? 0 : DGR_ERR_HIP);
-    return o;
-}
-
-// The `_C.rasterize_gaussians` of the light variant (L/rasterize_points.cu:35-129) plus the policy values the Python side
-// keeps.  Returns (num_rendered or -1, ticket or -1, capacity used, device status word, color, depth, median, var, alpha,
-// radii, geom, binning, img, gau_uncertainty, gau_related_pixels).
-std::tuple<long, long, long, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>
-light_forward(const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity,
-              const Tensor& scales, const Tensor& rotations, double scale_modifier, const Tensor& cov3D,
-              const Tensor& viewmatrix, const Tensor& gt_depth, const Tensor& projmatrix, double tan_fovx,
-              double tan_fovy, long H, long W, const Tensor& sh, long degree, const Tensor& campos, bool prefiltered,
-              bool debug, long capacity, long mode) {
-    const LightFwd o = light_forward_core(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D, viewmatrix,
-                                          gt_depth, projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug,
-                                          capacity, mode);
-    return {o.rendered, o.ticket, o.cap, o.status, o.color, o.depth, o.median, o.var, o.alpha, o.radii, o.geom, o.binning, o.img, o.unc, o.px};
-}
-
-// ---- resident backward scratch.  The backward's accumulator rows (64 bytes per Gaussian) must be zero when the blend
-// backward starts; a fresh allocation per call needs a clearing launch in front of it.  Instead one buffer per (device,
-// stream, size) is kept across calls: zero-filled when created, and every backward leaves it zero again (include/dgr_hip.h:
-// dgr_backward_scratch_clean_arm -- the per-Gaussian kernel clears the rows it reads).  Calls that share a buffer run on one
-// stream, i.e. in order.  Not while a hipGraph is being recorded (a replay may run on any stream, next to anything): a
-// capture gets a fresh buffer and the clearing launch.  DGR_RESIDENT_SCRATCH=0 switches the cache off.
-struct ScratchEntry {
-    int device;
-    void* stream;
-    size_t bytes;
-    Tensor buf;
-    uint64_t stamp;
-};
-std::mutex g_scr_mu;
-std::vector<ScratchEntry>& scratch_cache() {
-    static auto* v = new std::vector<ScratchEntry>();  // never destroyed: tensors must not outlive the allocator at exit
-    return *v;
-}
-uint64_t g_scr_clock = 0;
-const bool g_resident_scratch = [] { const char* e = getenv("DGR_RESIDENT_SCRATCH"); return !(e && e[0] == '0'); }();
-Tensor backward_scratch(const c10::Device& dev, void* stream, size_t nbytes, bool* resident) {
-    *resident = false;
-    if (!g_resident_scratch || dgr_stream_is_capturing(stream)) return bytes_on(dev, nbytes);
-    std::lock_guard<std::mutex> lk(g_scr_mu);
-    auto& c = scratch_cache();
-    for (auto& e : c)
-        if (e.device == dev.index() && e.stream == stream && e.bytes == nbytes) {
-            e.stamp = ++g_scr_clock;
-            *resident = true;
-            return e.buf;
-        }
-    if (c.size() >= 32) {  // drop the entry used longest ago (its memory goes back to the caching allocator)
-        size_t old = 0;
-        for (size_t i = 1; i < c.size(); i++)
-            if (c[i].stamp < c[old].stamp) old = i;
-        c.erase(c.begin() + (long)old);
-    }
-    Tensor buf = at::zeros({(long long)std::max<size_t>(nbytes, 1)}, at::TensorOptions().dtype(at::kByte).device(dev));
-    c.push_back(ScratchEntry{dev.index(), stream, nbytes, buf, ++g_scr_clock});
-    *resident = true;
-    return buf;
-}
-void drop_scratch(const c10::Device& dev, void* stream) {  // after a failed call the buffer's contents are unknown
-    std::lock_guard<std::mutex> lk(g_scr_mu);
-    auto& c = scratch_cache();
-    for (size_t i = 0; i < c.size();)
-        if (c[i].device == dev.index() && c[i].stream == stream) c.erase(c.begin() + (long)i); else i++;
-}
-// A one-view backward's C ABI call `call(scratch)` on the scratch above: armed clean when the buffer is resident, dropped when the
-// call fails
-template <typename Call>
-void on_backward_scratch(const c10::Device& dev, void* st, size_t nscr, Call call) {
-    bool resident = false;
-    const Tensor scratch = backward_scratch(dev, st, nscr, &resident);
-    if (resident) dgr_backward_scratch_clean_arm();
-    const int rc = call((char*)scratch.data_ptr());
-    if (rc < 0 && resident) drop_scratch(dev, st);
-    check(rc);
-}
-
+// ------------------------------------------------------------------------------------------------ backward, what the variants share
 // absgrad: a backward's tenth result, the absolute screen-space gradient [P,3] -- or, for a batch of V views, every view's
 // [V,P,3] (every row written) -- and the per-view output pointers; neither when `on` is false.
 struct AbsGrad {
@@ -461,197 +208,387 @@ struct AbsGrad {
 // all-reduce payload.  g[] receives them in the return order of the reference binding: means2D, colors, opacity, means3D,
 // cov3D, sh, scales, rotations.  Every row is written by the kernels (zeros for invisible Gaussians): no zero-fill.
 inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g, float** gp) {
-    const long long n[8] = {3LL * P, 3LL * P, 3LL * M * P, P, 3LL * P, 4LL * P, 6LL * P, 3LL * P};
-    size_t off[8], o = 0;
-    for (int i = 0; i < 8; i++) { off[i] = o; o += up256(4 * (size_t)n[i]); }
-    const Tensor arena = at::empty({(long long)std::max<size_t>(o / 4, 1)}, at::TensorOptions().dtype(at::kFloat).device(dev));
-    g[3] = view_of(arena, off[0], {P, 3}, at::kFloat); g[0] = view_of(arena, off[1], {P, 3}, at::kFloat);
-    g[5] = view_of(arena, off[2], {P, M, 3}, at::kFloat); g[2] = view_of(arena, off[3], {P, 1}, at::kFloat);
-    g[6] = view_of(arena, off[4], {P, 3}, at::kFloat); g[7] = view_of(arena, off[5], {P, 4}, at::kFloat);
-    g[4] = view_of(arena, off[6], {P, 6}, at::kFloat); g[1] = view_of(arena, off[7], {P, 3}, at::kFloat);
+    carve(dev, {{&g[3], {P, 3}, at::kFloat}, {&g[0], {P, 3}, at::kFloat}, {&g[5], {P, M, 3}, at::kFloat}, {&g[2], {P, 1}, at::kFloat},
+                {&g[6], {P, 3}, at::kFloat}, {&g[7], {P, 4}, at::kFloat}, {&g[4], {P, 6}, at::kFloat}, {&g[1], {P, 3}, at::kFloat}});
     for (int i = 0; i < 8; i++) gp[i] = ptr<float>(g[i]);
 }
 
-// L/rasterize_points.cu:131-236.  Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-// dL_drotations, dL_dview [1,4,4]); the first eight are windows of one flat arena (grad_arena above), or undefined tensors
-// (None) when need_gaussian_grads is false (tracking: the library then skips every dense per-Gaussian row).
-// dL_dout_alpha (option "silhouette_grad", dgr_light_backward_silhouette): the opacity_map gradient [1,H,W] as the silhouette
-// image, or undefined / empty (NULL)
-// absgrad (dgr_light_backward_absgrad): a tenth result, the [P,3] absolute screen-space gradient
-std::vector<Tensor> light_backward(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
-                                   const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                                   const Tensor& viewmatrix_, const Tensor& projmatrix_, double tan_fovx, double tan_fovy,
-                                   const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_median,
-                                   const Tensor& dL_dout_var, const Tensor& gt_depth_, const Tensor& sh_, long degree,
-                                   const Tensor& campos_, const Tensor& geomBuffer, long R, const Tensor& binningBuffer,
-                                   const Tensor& imageBuffer, const Tensor& alphas_, bool debug, const Tensor& perspec_,
-                                   bool track_off, bool map_off, bool need_gaussian_grads, const Tensor& dL_dout_alpha,
-                                   bool absgrad) {
-    AbsGrad abs(absgrad, means3D_, 0);
-    const c10::Device dev = means3D_.device();
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const long H = dL_dout_color.size(1), W = dL_dout_color.size(2);
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
-                 view = f32c(viewmatrix_, dev), proj = f32c(projmatrix_, dev), campos = f32c(campos_, dev),
-                 gt = f32c(gt_depth_, dev), sh = f32c(sh_, dev), alphas = f32c(alphas_, dev), perspec = f32c_diag4(perspec_, dev),
-                 gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gM = f32c(dL_dout_median, dev),
-                 gV = f32c(dL_dout_var, dev), gA = f32c(dL_dout_alpha, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
-    // (the forward recorded the saved inputs; the gradient images of a graph root are whatever the caller passed in)
-    keep_until_read(dev, {&dL_dout_color, &dL_dout_depth, &dL_dout_median, &dL_dout_var, &alphas_, &perspec_, &dL_dout_alpha});
-    Probe p_al(HP_BWD_ALLOC);
-    std::vector<Tensor> g(9);
-    float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (need_gaussian_grads) grad_arena(dev, P, M, g.data(), gp);
-    else map_off = true;  // nobody reads the per-Gaussian sums: the blend kernel forms the three pose sums only
-    // scratch (accumulator rows, cleared by the backward's first launch) and, behind it, the [1,4,4] pose gradient -- what
-    // L/__init__.py:160-161 sums over dim 0
-    // (with the option "deterministic_grads" the scratch also holds 64 bytes per tile instance: R = num_rendered, or a lazy forward's capacity)
-    const size_t nscr = up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)R));
-    void* st = stream_of(dev);
-    g[8] = at::empty({1, 4, 4}, at::TensorOptions().dtype(at::kFloat).device(dev));
-    on_backward_scratch(dev, st, nscr, [&](char* scratch) {
-        p_al.stop();
-        Probe p_bc(HP_BWD_C);
-        return dgr_light_backward_silhouette(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                                             ptr<float>(sh), ptr<float>(colors), ptr<float>(alphas), ptr<float>(scales), (float)scale_modifier,
-                                             ptr<float>(rotations), ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos),
-                                             (float)tan_fovx, (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer),
-                                             bytes(binningBuffer), bytes(imageBuffer), ptr<float>(gC),
-                                             ptr<float>(gD), ptr<float>(gM), ptr<float>(gV), gp[0], nullptr, gp[2], gp[1], nullptr,
-                                             gp[3], gp[4],
-                                             gp[5], gp[6], gp[7], debug ? 1 : 0, nullptr, ptr<float>(perspec), g[8].data_ptr<float>(), nullptr,
-                                             ptr<float>(gt), track_off ? 1 : 0, map_off ? 1 : 0, scratch, nscr, abs.view[0], ptr<float>(gA));
-    });
-    if (absgrad) g.push_back(std::move(abs.t));
-    return g;
-}
-
-// ------------------------------------------------------------------------------------------------ full variant
-// F/rasterize_points.cu:35-120.  Modes as light_forward_core.
-struct FullFwd : FwdCounts {
-    long related = -1;
-    Tensor status, color, depth, unc, radii, geom, binning, img;
-};
-FullFwd full_forward_core(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
-                          const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                          const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
-                          double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_,
-                          bool prefiltered, long capacity, long mode, bool want_related = true) {
-    const FwdInputs in(forward_device(means3D_), background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrix_,
-                       gt_depth_, projmatrix_, sh_, campos_);
-    const c10::Device dev = in.dev;
-    const int P = in.P, M = in.M;
-    keep_until_read(dev, {&means3D_, &background, &colors_, &opacity_, &scales_, &rotations_, &cov3D_, &viewmatrix_, &projmatrix_,
-                          &campos_, &gt_depth_, &sh_});
-    const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
-    FullFwd o;
-    const size_t N = (size_t)H * (size_t)W, n1 = up256(4 * N), np = up256(4 * (size_t)P);
-    const Tensor images = bytes_on(dev, up256(12 * N) + 2 * n1);
-    o.color = view_of(images, 0, {3, H, W}, at::kFloat);
-    o.depth = view_of(images, up256(12 * N), {1, H, W}, at::kFloat);
-    o.unc = view_of(images, up256(12 * N) + n1, {1, H, W}, at::kFloat);
-    const Tensor per_gaussian = bytes_on(dev, np + 256);
-    o.radii = view_of(per_gaussian, 0, {P}, at::kInt);  // (written for every Gaussian by preprocess_fwd)
-    o.status = view_of(per_gaussian, np, {4}, at::kInt);
-    void* st = stream_of(dev);
-    if (mode == 0 || P == 0) {
-        o.geom = at::empty({0}, u8); o.binning = at::empty({0}, u8); o.img = at::empty({0}, u8);
-        Alloc3 al{{&o.geom, dev}, {&o.binning, dev}, {&o.img, dev}};
-        int ng = 0;
-        const int rc = dgr_full_forward(st, cb_geom, cb_binning, cb_img, &al, P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
-                                        ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
-                                        ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
-                                        ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx, (float)tan_fovy,
-                                        prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(in.gt), ptr<float>(o.unc),
-                                        ptr<int>(o.radii), &ng);
-        check(rc);
-        o.rendered = o.cap = rc;
-        o.related = ng;
-        return o;
+// What a backward reads of its forward, FwdInputs' counterpart: the saved inputs as contiguous fp32 tensors on the Gaussians' device,
+// under its device guard, and the forward's own tensors as they are (one view: one camera; batches: [V, ...] per camera)
+struct BwdScene {
+    c10::Device dev;
+    c10::hip::HIPGuardMasqueradingAsCUDA guard;
+    int P, M, degree;
+    float scale_modifier, tan_fovx, tan_fovy;
+    Tensor means3D, bg, colors, scales, rotations, cov3D, view, proj, campos, gt, sh, perspec;
+    const Tensor &radii, &geom, &binning, &img, &perspec_arg;
+    BwdScene(const Tensor& background, const Tensor& means3D_, const Tensor& radii_, const Tensor& colors_, const Tensor& scales_,
+             const Tensor& rotations_, double scale_modifier_, const Tensor& cov3D_, const Tensor& view_, const Tensor& proj_,
+             double tan_fovx_, double tan_fovy_, const Tensor& gt_, const Tensor& sh_, long degree_, const Tensor& campos_,
+             const Tensor& geom_, const Tensor& binning_, const Tensor& img_, const Tensor& perspec_)
+        : dev(means3D_.device()), guard(dev), P((int)means3D_.size(0)), degree((int)degree_), scale_modifier((float)scale_modifier_),
+          tan_fovx((float)tan_fovx_), tan_fovy((float)tan_fovy_), means3D(f32c(means3D_, dev)), bg(f32c(background, dev)),
+          colors(f32c(colors_, dev)), scales(f32c(scales_, dev)), rotations(f32c(rotations_, dev)), cov3D(f32c(cov3D_, dev)),
+          view(f32c(view_, dev)), proj(f32c(proj_, dev)), campos(f32c(campos_, dev)), gt(f32c(gt_, dev)), sh(f32c(sh_, dev)),
+          perspec(f32c_diag4(perspec_, dev)), radii(radii_), geom(geom_), binning(binning_), img(img_), perspec_arg(perspec_) {
+        M = sh.numel() != 0 ? (int)sh.size(1) : 0;
     }
-    auto run = [&](long cap) {
-        const StateArena sa(dev, P, (int)W, (int)H, cap);
-        o.geom = sa.geom; o.binning = sa.binning; o.img = sa.img;
-        check(dgr_full_forward_presized(st, (char*)o.geom.data_ptr(), (char*)o.binning.data_ptr(), (int)cap, (char*)o.img.data_ptr(),
-                                        o.status.data_ptr<int>(), P, (int)degree, M, ptr<float>(in.bg), (int)W, (int)H,
-                                        ptr<float>(in.means3D), ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity),
-                                        ptr<float>(in.scales), (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D),
-                                        ptr<float>(in.view), ptr<float>(in.proj), ptr<float>(in.campos), (float)tan_fovx, (float)tan_fovy,
-                                        prefiltered ? 1 : 0, ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(in.gt), ptr<float>(o.unc),
-                                        ptr<int>(o.radii)));
-    };
-    presized_forward(run, capacity, mode, st, o);
-    if (mode == 2) return o;
+};
+// the light variant's switches of a backward (the full one has none)
+struct BwdFlags {
+    bool debug = false, track_off = false, map_off = false;
+};
+
+// A batch backward's results: g[1..7] the arena's seven sums (gp[1..7]: their pointers; none without need_gaussian_grads), g[0]
+// every view's dL_dmeans2D [V,P,3] (need_means2D) or None, g[8] dL_dview [V,4,4]; and V scratch rows of nscr bytes
+struct BatchBwdOut {
+    std::vector<Tensor> g = std::vector<Tensor>(9);
+    float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Tensor scratch;
+    size_t nscr;
+    BatchBwdOut(const c10::Device& dev, int P, int M, long V, long W, long H, bool need_gaussian_grads, bool need_means2D,
+                const std::vector<long>& num_rendered) {
+        const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+        if (need_gaussian_grads) {
+            grad_arena(dev, P, M, g.data(), gp);
+            g[0].zero_();  // the arena's one-view means2D slot: a batch returns those gradients per view, beside the arena
+            g[0] = need_means2D ? at::empty({V, P, 3}, f32) : Tensor();
+        }
+        g[8] = at::empty({V, 4, 4}, f32);
+        // (deterministic_grads: + 64 bytes per tile instance of the view with the most of them; the views' rows are equally long)
+        long rmax = 0;
+        for (long r : num_rendered) rmax = std::max(rmax, r);
+        nscr = std::max<size_t>(up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)rmax)), 256);
+        scratch = at::empty({V, (long long)nscr}, at::TensorOptions().dtype(at::kByte).device(dev));
+    }
+    float* dmean2D(long v) const { return g[0].defined() ? row<float>(g[0], v) : nullptr; }
+};
+inline int rendered_of(const std::vector<long>& num_rendered, long v) { return (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0; }
+
+// The tensors a node saves, by name: the common set (L/__init__.py:101-102, F/__init__.py:89-90, + the settings' tensors, which the
+// Python Functions read from ctx.raster_settings), then a variant's own from S_COMMON on
+enum Saved { S_COLORS, S_MEANS3D, S_SCALES, S_ROTATIONS, S_COV3D, S_VIEW, S_RADII, S_SH, S_GEOM, S_BINNING, S_IMG, S_GT, S_BG, S_PROJ,
+             S_CAMPOS, S_PERSPEC, S_COMMON };
+
+// ------------------------------------------------------------------------------------------------ the two variants
+// Each description holds what differs and nothing else.  Gradient images go to a backward as an array of N_IMAGES tensors indexed by
+// the variant's enum: GC, GD (colour, depth) and SIL (the exact silhouette gradient image, option "silhouette_grad"; empty: none) in
+// both.  gp[] of a backward: [0] means2D [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations.
+struct Light {
+    enum { GC, GD, GM, GV, SIL, ALPHAS, N_IMAGES };  // + the median depth's and the depth variance's; the forward's alpha image rides along
+    using Images = std::array<Tensor, N_IMAGES>;
+    using View = dgr_light_view;
+    using ViewGrad = dgr_light_view_grad;
+    enum { S_ALPHA = S_COMMON, N_SAVED };
+    static constexpr bool tracking_flags = true;  // the settings carry track_off / map_off
+    // dL_dview is [1,4,4]: the reference binding returns a per-pixel [H*W,4,4] buffer that L/__init__.py:160-161 sums over dim 0;
+    // one already-reduced "pixel" keeps that code working
+    static constexpr bool dview_leading_one = true;
+
+    // allocation 1: the five images (every pixel is written by the blend kernel); allocation 2: radii (written for every
+    // Gaussian), the two median statistics (cleared by the kernels) and the status word
+    static void outputs(Fwd& o, const c10::Device& dev, int P, long H, long W) {
+        carve(dev, {{&o.color, {3, H, W}, at::kFloat}, {&o.depth, {1, H, W}, at::kFloat}, {&o.median, {1, H, W}, at::kFloat},
+                    {&o.var, {1, H, W}, at::kFloat}, {&o.alpha, {1, H, W}, at::kFloat}});
+        carve(dev, {{&o.radii, {P}, at::kInt}, {&o.unc, {P, 1}, at::kFloat}, {&o.px, {P, 1}, at::kInt}, {&o.status, {4}, at::kInt}});
+    }
+    static auto output_args(const Fwd& o, const Tensor& gt) {
+        return std::make_tuple(ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(o.median), ptr<float>(o.alpha), ptr<float>(gt),
+                               ptr<float>(o.var), ptr<float>(o.unc), ptr<int>(o.px), ptr<int>(o.radii));
+    }
+    template <typename Args>
+    static int forward(const Args& args, bool debug, long&) {
+        return std::apply([&](auto... a) { return dgr_light_forward(a..., debug ? 1 : 0); }, args);
+    }
+    template <typename Args>
+    static int forward_presized(const Args& args) {
+        return std::apply([](auto... a) { return dgr_light_forward_presized(a...); }, args);
+    }
+    static void after_strict(Fwd&, void* st, bool debug, bool) {
+        if (debug) check(hipStreamSynchronize((hipStream_t)st) == hipSuccess ? 0 : DGR_ERR_HIP);
+    }
+    // the `_C.rasterize_gaussians` tuple (L/rasterize_points.cu:35-129) behind num_rendered
+    static std::vector<Tensor> forward_tensors(const Fwd& o) {
+        return {o.color, o.depth, o.median, o.var, o.alpha, o.radii, o.geom, o.binning, o.img, o.unc, o.px};
+    }
+
+    // L/rasterize_points.cu:131-236.  Median and variance gradients that are absent stay NULL: the lean blend backward
+    static int backward(void* st, const BwdScene& s, const Images& im, long W, long H, long R, float* const* gp, float* dview,
+                        BwdFlags f, bool need_gaussian_grads, char* scratch, size_t nscr, float* abs) {
+        // (without per-Gaussian gradients nobody reads the per-Gaussian sums: the blend kernel forms the three pose sums only)
+        const bool map_off = f.map_off || !need_gaussian_grads;
+        return dgr_light_backward_silhouette(
+            st, s.P, s.degree, s.M, (int)R, ptr<float>(s.bg), (int)W, (int)H, ptr<float>(s.means3D), ptr<float>(s.sh),
+            ptr<float>(s.colors), ptr<float>(im[ALPHAS]), ptr<float>(s.scales), s.scale_modifier, ptr<float>(s.rotations),
+            ptr<float>(s.cov3D), ptr<float>(s.view), ptr<float>(s.proj), ptr<float>(s.campos), s.tan_fovx, s.tan_fovy, ptr<int>(s.radii),
+            bytes(s.geom), bytes(s.binning), bytes(s.img), ptr<float>(im[GC]), ptr<float>(im[GD]), ptr<float>(im[GM]), ptr<float>(im[GV]),
+            gp[0], nullptr, gp[2], gp[1], nullptr, gp[3], gp[4], gp[5], gp[6], gp[7], f.debug ? 1 : 0, nullptr, ptr<float>(s.perspec),
+            dview, nullptr, ptr<float>(s.gt), f.track_off ? 1 : 0, map_off ? 1 : 0, scratch, nscr, abs, ptr<float>(im[SIL]));
+    }
+
+    // the node (L/__init__.py:46-176): outputs, the extra saved tensor, the gradient images of its backward
+    static variable_list node_outputs(const Fwd& o) { return {o.color, o.radii, o.depth, o.median, o.var, o.alpha, o.unc, o.px}; }
+    // four of the eight outputs (radii, opacity_map, gau_uncertainty, gau_related_pixels) have no gradient input in the
+    // backward -- opacity_map has one with the option "silhouette_grad"
+    static variable_list non_differentiable(const Fwd& o) { return {o.radii, o.px}; }
+    static void save_extra(variable_list& sv, const Fwd& o) { sv[S_ALPHA] = o.alpha; }
+    // (no gradient image for the median depth / the depth variance: undefined, NULL at the C ABI -- no zero images are made, filled
+    //  and read.  The opacity_map gradient is the silhouette image when the option was on at the forward; unused, or the option off: none)
+    static std::array<const Tensor*, N_IMAGES> node_images(const Tensor& gC, const Tensor& gD, const variable_list& grad,
+                                                          const variable_list& sv, bool silhouette, const Tensor& none) {
+        return {&gC, &gD, &grad[3], &grad[4], silhouette ? &grad[5] : &none, &sv[S_ALPHA]};
+    }
+
+    // dgr_amd.batch: [V,...] outputs, one struct of pointers per view
+    static void batch_outputs(Fwd& o, long V, int P, long H, long W, const at::TensorOptions& f32, const at::TensorOptions& i32) {
+        o.color = at::empty({V, 3, H, W}, f32); o.depth = at::empty({V, 1, H, W}, f32); o.median = at::empty({V, 1, H, W}, f32);
+        o.var = at::empty({V, 1, H, W}, f32); o.alpha = at::empty({V, 1, H, W}, f32);
+        o.radii = P ? at::empty({V, P}, i32) : at::zeros({V, P}, i32);
+        o.unc = P ? at::empty({V, P, 1}, f32) : at::zeros({V, P, 1}, f32);
+        o.px = P ? at::empty({V, P, 1}, i32) : at::zeros({V, P, 1}, i32);
+    }
+    static View view(long v, int capacity, const Fwd& o, const FwdInputs& in) {
+        return View{row_bytes(o.geom, v), row_bytes(o.binning, v), capacity, row_bytes(o.img, v), row<int>(o.status, v),
+                    row<float>(in.view, v), row<float>(in.proj, v), row<float>(in.campos, v), row<float>(o.color, v),
+                    row<float>(o.depth, v), row<float>(o.median, v), row<float>(o.alpha, v), row<float>(in.gt, v),
+                    row<float>(o.var, v), row<float>(o.unc, v), row<int>(o.px, v), row<int>(o.radii, v)};
+    }
+    template <typename... A>
+    static int forward_batch(A... a) { return dgr_light_forward_batch(a...); }
+    static std::vector<Tensor> batch_tensors(const Fwd& o) {
+        return {o.status, o.color, o.depth, o.median, o.var, o.alpha, o.radii, o.geom, o.binning, o.img, o.unc, o.px};
+    }
+    static ViewGrad view_grad(long v, const BwdScene& s, const Images& im, const BatchBwdOut& o, int rendered) {
+        return ViewGrad{row_bytes(s.geom, v), row_bytes(s.binning, v), row_bytes(s.img, v), row<float>(s.view, v), row<float>(s.proj, v),
+                        row<float>(s.campos, v), perspec_row(s.perspec, v), row<float>(im[ALPHAS], v), row<float>(s.gt, v),
+                        row<int>(s.radii, v), row<float>(im[GC], v), row<float>(im[GD], v), row<float>(im[GM], v), row<float>(im[GV], v),
+                        o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr, rendered};
+    }
+    static int backward_batch(void* st, int V, const ViewGrad* w, const BwdScene& s, long W, long H, float* const* gp, BwdFlags f,
+                              bool need_gaussian_grads, float* const* abs, const float* const* sil) {
+        const bool map_off = f.map_off || !need_gaussian_grads;  // (as Light::backward)
+        return dgr_light_backward_batch_silhouette(st, V, w, s.P, s.degree, s.M, ptr<float>(s.bg), (int)W, (int)H, ptr<float>(s.means3D),
+                                                   ptr<float>(s.sh), ptr<float>(s.colors), ptr<float>(s.scales), s.scale_modifier,
+                                                   ptr<float>(s.rotations), ptr<float>(s.cov3D), s.tan_fovx, s.tan_fovy, gp[2], gp[1],
+                                                   gp[3], gp[4], gp[5], gp[6], gp[7], f.track_off ? 1 : 0, map_off ? 1 : 0, abs, sil);
+    }
+};
+
+struct Full {
+    enum { GC, GD, GU, SIL, N_IMAGES };  // + the uncertainty image's, in the reference's variance form
+    using Images = std::array<Tensor, N_IMAGES>;
+    using View = dgr_full_view;
+    using ViewGrad = dgr_full_view_grad;
+    enum { N_SAVED = S_COMMON };
+    static constexpr bool tracking_flags = false;
+    static constexpr bool dview_leading_one = false;  // dL_dview is [4,4]
+
+    static void outputs(Fwd& o, const c10::Device& dev, int P, long H, long W) {
+        carve(dev, {{&o.color, {3, H, W}, at::kFloat}, {&o.depth, {1, H, W}, at::kFloat}, {&o.unc, {1, H, W}, at::kFloat}});
+        carve(dev, {{&o.radii, {P}, at::kInt}, {&o.status, {4}, at::kInt}});  // (radii: written for every Gaussian by preprocess_fwd)
+    }
+    static auto output_args(const Fwd& o, const Tensor& gt) {
+        return std::make_tuple(ptr<float>(o.color), ptr<float>(o.depth), ptr<float>(gt), ptr<float>(o.unc), ptr<int>(o.radii));
+    }
+    template <typename Args>
+    static int forward(const Args& args, bool, long& related) {
+        int ng = 0;
+        const int rc = std::apply([&](auto... a) { return dgr_full_forward(a..., &ng); }, args);
+        related = ng;
+        return rc;
+    }
+    template <typename Args>
+    static int forward_presized(const Args& args) {
+        return std::apply([](auto... a) { return dgr_full_forward_presized(a...); }, args);
+    }
     // num_related (the reference's NG) is produced by the forward blend: the reference's second blocking read
     // (F/cuda_rasterizer/rasterizer_impl.cu:498) -- a wait for the whole forward.  The `_C.rasterize_gaussians` mirror returns the
     // number, as the reference's does; the autograd node does not wait for it: NG only sizes the reference's pair lists in ITS
     // backward (F/__init__.py:91,100,130), which this backward does not have (csrc/render_full.hip), and no caller of
     // GaussianRasterizer.forward ever sees it.  The strict forward then returns as soon as num_rendered is known, the blend
     // still running (config 2, one view at a time in the default mode: 0.205 -> 0.17 ms).
-    if (want_related) o.related = o.status.to(at::kCPU).data_ptr<int>()[3];
+    static void after_strict(Fwd& o, void*, bool, bool want_related) {
+        if (want_related) o.related = o.status.to(at::kCPU).data_ptr<int>()[3];
+    }
+    // the `_C.rasterize_gaussians` tuple (F/rasterize_points.cu:35-120) behind num_rendered and num_related
+    static std::vector<Tensor> forward_tensors(const Fwd& o) { return {o.color, o.depth, o.unc, o.radii, o.geom, o.binning, o.img}; }
+
+    // F/rasterize_points.cu:122-239.  im[GU] keeps the reference's variance form (the bindings pass none there when the option
+    // "silhouette_grad" is on)
+    static int backward(void* st, const BwdScene& s, const Images& im, long W, long H, long R, float* const* gp, float* dview, BwdFlags,
+                        bool, char* scratch, size_t nscr, float* abs) {
+        return dgr_full_backward_silhouette(
+            st, s.P, s.degree, s.M, (int)R, ptr<float>(s.bg), (int)W, (int)H, ptr<float>(s.means3D), ptr<float>(s.sh),
+            ptr<float>(s.colors), ptr<float>(s.scales), s.scale_modifier, ptr<float>(s.rotations), ptr<float>(s.cov3D), ptr<float>(s.view),
+            ptr<float>(s.proj), ptr<float>(s.campos), s.tan_fovx, s.tan_fovy, ptr<int>(s.radii), bytes(s.geom), bytes(s.binning),
+            bytes(s.img), ptr<float>(im[GC]), ptr<float>(im[GD]), gp[0], nullptr, gp[2], gp[1], gp[3], gp[4], gp[5], gp[6], gp[7], nullptr,
+            nullptr, nullptr, nullptr, nullptr, ptr<float>(s.perspec), nullptr, nullptr, nullptr, dview, nullptr, nullptr, nullptr,
+            ptr<float>(s.gt), ptr<float>(im[GU]), scratch, nscr, abs, ptr<float>(im[SIL]));
+    }
+
+    // the node (F/__init__.py:46-151)
+    static variable_list node_outputs(const Fwd& o) { return {o.color, o.radii, o.depth, o.unc}; }
+    static variable_list non_differentiable(const Fwd& o) { return {o.radii}; }
+    static void save_extra(variable_list&, const Fwd&) {}
+    // (no gradient image for the uncertainty output: undefined, NULL at the C ABI, which then runs the lean blend backward.  Option
+    //  "silhouette_grad" at the forward: that gradient is the exact silhouette image, and dL_duncertainties NULL -- the lean kernel)
+    static std::array<const Tensor*, N_IMAGES> node_images(const Tensor& gC, const Tensor& gD, const variable_list& grad,
+                                                          const variable_list&, bool silhouette, const Tensor& none) {
+        return {&gC, &gD, silhouette ? &none : &grad[3], silhouette ? &grad[3] : &none};
+    }
+
+    // dgr_amd.batch_full
+    static void batch_outputs(Fwd& o, long V, int P, long H, long W, const at::TensorOptions& f32, const at::TensorOptions& i32) {
+        o.color = at::empty({V, 3, H, W}, f32); o.depth = at::empty({V, 1, H, W}, f32); o.unc = at::empty({V, 1, H, W}, f32);
+        o.radii = P ? at::empty({V, P}, i32) : at::zeros({V, P}, i32);
+    }
+    static View view(long v, int capacity, const Fwd& o, const FwdInputs& in) {
+        return View{row_bytes(o.geom, v), row_bytes(o.binning, v), capacity, row_bytes(o.img, v), row<int>(o.status, v),
+                    row<float>(in.view, v), row<float>(in.proj, v), row<float>(in.campos, v), row<float>(o.color, v),
+                    row<float>(o.depth, v), row<float>(in.gt, v), row<float>(o.unc, v), row<int>(o.radii, v)};
+    }
+    template <typename... A>
+    static int forward_batch(A... a) { return dgr_full_forward_batch(a...); }
+    static std::vector<Tensor> batch_tensors(const Fwd& o) { return {o.status, o.color, o.depth, o.unc, o.radii, o.geom, o.binning, o.img}; }
+    static ViewGrad view_grad(long v, const BwdScene& s, const Images& im, const BatchBwdOut& o, int rendered) {
+        // an undefined or empty dL_dout_unc: no view's loss used the uncertainty image (the lean blend backward)
+        const bool lean = !im[GU].defined() || im[GU].numel() == 0;
+        return ViewGrad{row_bytes(s.geom, v), row_bytes(s.binning, v), row_bytes(s.img, v), row<float>(s.view, v), row<float>(s.proj, v),
+                        row<float>(s.campos, v), perspec_row(s.perspec, v), row<float>(s.gt, v), row<int>(s.radii, v), row<float>(im[GC], v),
+                        row<float>(im[GD], v), lean ? nullptr : row<float>(im[GU], v), o.dmean2D(v), row<float>(o.g[8], v),
+                        row_bytes(o.scratch, v), o.nscr, rendered};
+    }
+    static int backward_batch(void* st, int V, const ViewGrad* w, const BwdScene& s, long W, long H, float* const* gp, BwdFlags, bool,
+                              float* const* abs, const float* const* sil) {
+        return dgr_full_backward_batch_silhouette(st, V, w, s.P, s.degree, s.M, ptr<float>(s.bg), (int)W, (int)H, ptr<float>(s.means3D),
+                                                  ptr<float>(s.sh), ptr<float>(s.colors), ptr<float>(s.scales), s.scale_modifier,
+                                                  ptr<float>(s.rotations), ptr<float>(s.cov3D), s.tan_fovx, s.tan_fovy, gp[2], gp[1], gp[3],
+                                                  gp[4], gp[5], gp[6], gp[7], abs, sil);
+    }
+};
+
+// ------------------------------------------------------------------------------------------------ one view
+// `debug` (light): passed to the callback entry point, and a strict forward ends with a stream synchronise; `want_related` (full):
+// a strict forward reads num_related back (Full::after_strict).
+template <class V>
+Fwd forward_core(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_, const Tensor& scales_,
+                 const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_, const Tensor& viewmatrix_, const Tensor& gt_depth_,
+                 const Tensor& projmatrix_, double tan_fovx, double tan_fovy, long H, long W, const Tensor& sh_, long degree,
+                 const Tensor& campos_, bool prefiltered, bool debug, long capacity, long mode, bool want_related) {
+    Probe p_pre(HP_PRELUDE);
+    const FwdInputs in(forward_device(means3D_), background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrix_,
+                       gt_depth_, projmatrix_, sh_, campos_);
+    const c10::Device dev = in.dev;
+    const int P = in.P;
+    const Tensor* const inputs[] = {&means3D_, &background, &colors_, &opacity_, &scales_, &rotations_, &cov3D_, &viewmatrix_, &projmatrix_,
+                                    &campos_, &gt_depth_, &sh_};
+    keep_until_read(dev, inputs, std::size(inputs));
+    const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
+    p_pre.stop();
+    Probe p_out(HP_OUT_ALLOC);
+    Fwd o;
+    V::outputs(o, dev, P, H, W);  // allocations 1 and 2
+    void* st = stream_of(dev);
+    const auto args = std::tuple_cat(scene_args(in, degree, W, H, scale_modifier, tan_fovx, tan_fovy, prefiltered, ptr<float>(in.view),
+                                                ptr<float>(in.proj), ptr<float>(in.campos)), V::output_args(o, in.gt));
+    p_out.stop();
+
+    if (mode == 0 || P == 0) {
+        o.geom = at::empty({0}, u8); o.binning = at::empty({0}, u8); o.img = at::empty({0}, u8);
+        Alloc3 al{{&o.geom, dev}, {&o.binning, dev}, {&o.img, dev}};
+        const int rc = V::forward(std::tuple_cat(std::make_tuple(st, cb_geom, cb_binning, cb_img, &al), args), debug, o.related);
+        check(rc);
+        o.rendered = o.cap = rc;
+        return o;
+    }
+    auto run = [&](long cap) {
+        Probe p_st(HP_STATE_ALLOC);
+        const StateArena sa(dev, P, (int)W, (int)H, cap);  // allocation 3
+        o.geom = sa.geom; o.binning = sa.binning; o.img = sa.img;
+        p_st.stop();
+        Probe p_c(HP_FWD_C);
+        check(V::forward_presized(std::tuple_cat(std::make_tuple(st, (char*)o.geom.data_ptr(), (char*)o.binning.data_ptr(), (int)cap,
+                                                                 (char*)o.img.data_ptr(), o.status.data_ptr<int>()), args)));
+    };
+    presized_forward(run, capacity, mode, st, o);
+    if (mode != 2) V::after_strict(o, st, debug, want_related);
     return o;
 }
 
-// Returns (num_rendered or -1, num_related or -1, ticket or -1, capacity used, device status word, color, depth,
-// uncertainty, radii, geom, binning, img).
-std::tuple<long, long, long, long, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>
-full_forward(const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity, const Tensor& scales,
-             const Tensor& rotations, double scale_modifier, const Tensor& cov3D, const Tensor& viewmatrix,
-             const Tensor& gt_depth, const Tensor& projmatrix, double tan_fovx, double tan_fovy, long H, long W,
-             const Tensor& sh, long degree, const Tensor& campos, bool prefiltered, long capacity, long mode) {
-    const FullFwd o = full_forward_core(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D, viewmatrix,
-                                        gt_depth, projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, capacity, mode);
-    return {o.rendered, o.related, o.ticket, o.cap, o.status, o.color, o.depth, o.unc, o.radii, o.geom, o.binning, o.img};
+// The `_C.rasterize_gaussians` of a variant plus the policy values the Python side keeps: (the report, V::forward_tensors)
+template <class V>
+PyForward forward(const Tensor& background, const Tensor& means3D, const Tensor& colors, const Tensor& opacity, const Tensor& scales,
+                  const Tensor& rotations, double scale_modifier, const Tensor& cov3D, const Tensor& viewmatrix, const Tensor& gt_depth,
+                  const Tensor& projmatrix, double tan_fovx, double tan_fovy, long H, long W, const Tensor& sh, long degree,
+                  const Tensor& campos, bool prefiltered, bool debug, long capacity, long mode) {
+    const Fwd o = forward_core<V>(background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D, viewmatrix, gt_depth,
+                                  projmatrix, tan_fovx, tan_fovy, H, W, sh, degree, campos, prefiltered, debug, capacity, mode,
+                                  /*want_related=*/true);
+    return {o.py(), V::forward_tensors(o)};
 }
 
-// F/rasterize_points.cu:122-239; returns the nine gradients in the reference's order, dL_dview as [4,4]
-// dL_dout_sil: the exact silhouette gradient image [1,H,W] (dgr_full_backward_silhouette) or undefined / empty; dL_dout_unc keeps
-// the reference's variance form (the bindings pass an empty tensor there when the option is on); absgrad: as light_backward's
-std::vector<Tensor> full_backward(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
-                                  const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                                  const Tensor& viewmatrix_, const Tensor& gt_depth_, const Tensor& projmatrix_, double tan_fovx,
-                                  double tan_fovy, const Tensor& dL_dout_color, const Tensor& dL_dout_depth,
-                                  const Tensor& dL_dout_unc, const Tensor& sh_, long degree, const Tensor& campos_,
-                                  const Tensor& geomBuffer, long R, const Tensor& binningBuffer, const Tensor& imageBuffer,
-                                  long NG, const Tensor& perspec_, bool need_gaussian_grads, const Tensor& dL_dout_sil,
-                                  bool absgrad) {
-    (void)NG;
-    AbsGrad abs(absgrad, means3D_, 0);
-    const c10::Device dev = means3D_.device();
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const long H = dL_dout_color.size(1), W = dL_dout_color.size(2);
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
-                 view = f32c(viewmatrix_, dev), proj = f32c(projmatrix_, dev), campos = f32c(campos_, dev),
-                 gt = f32c(gt_depth_, dev), sh = f32c(sh_, dev), perspec = f32c_diag4(perspec_, dev), gC = f32c(dL_dout_color, dev),
-                 gD = f32c(dL_dout_depth, dev), gU = f32c(dL_dout_unc, dev), gS = f32c(dL_dout_sil, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
-    keep_until_read(dev, {&dL_dout_color, &dL_dout_depth, &dL_dout_unc, &perspec_, &dL_dout_sil});
+// Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview -- light
+// [1,4,4], full [4,4]); the first eight are windows of one flat arena (grad_arena above), or undefined tensors (None) when
+// need_gaussian_grads is false (tracking: the library then skips every dense per-Gaussian row).  `images`: the variant's gradient
+// images as the caller holds them.  absgrad (dgr_*_backward_absgrad): a tenth result, the [P,3] absolute screen-space gradient.
+// R: the forward's num_rendered, or a lazy forward's capacity.
+template <class V>
+std::vector<Tensor> backward(const BwdScene& s, const std::array<const Tensor*, V::N_IMAGES>& images, long R, BwdFlags flags,
+                             bool need_gaussian_grads, bool absgrad) {
+    AbsGrad abs(absgrad, s.means3D, 0);
+    const c10::Device dev = s.dev;
+    const long H = images[V::GC]->size(1), W = images[V::GC]->size(2);
+    typename V::Images im;
+    for (size_t i = 0; i < im.size(); i++) im[i] = f32c(*images[i], dev);
+    // (the forward recorded the saved inputs; the gradient images of a graph root are whatever the caller passed in)
+    const Tensor* recorded[V::N_IMAGES + 1];
+    *std::copy(images.begin(), images.end(), recorded) = &s.perspec_arg;
+    keep_until_read(dev, recorded, std::size(recorded));
+    Probe p_al(HP_BWD_ALLOC);
     std::vector<Tensor> g(9);
     float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (need_gaussian_grads) grad_arena(dev, P, M, g.data(), gp);
-    g[8] = at::empty({4, 4}, at::TensorOptions().dtype(at::kFloat).device(dev));
-    const size_t nscr = up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)R));  // (deterministic_grads: + rows per instance)
+    if (need_gaussian_grads) grad_arena(dev, s.P, s.M, g.data(), gp);
+    // scratch: accumulator rows, cleared by the backward's first launch
+    // (with the option "deterministic_grads" the scratch also holds 64 bytes per tile instance)
+    const size_t nscr = up256(dgr_light_backward_scratch_bytes_r(s.P, (int)W, (int)H, (int)R));
     void* st = stream_of(dev);
-    // gp: [0] means2D [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
+    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    g[8] = V::dview_leading_one ? at::empty({1, 4, 4}, f32) : at::empty({4, 4}, f32);
     on_backward_scratch(dev, st, nscr, [&](char* scratch) {
-        return dgr_full_backward_silhouette(st, P, (int)degree, M, (int)R, ptr<float>(bg), (int)W, (int)H, ptr<float>(means3D),
-                                            ptr<float>(sh), ptr<float>(colors), ptr<float>(scales), (float)scale_modifier,
-                                            ptr<float>(rotations),
-                                            ptr<float>(cov3D), ptr<float>(view), ptr<float>(proj), ptr<float>(campos), (float)tan_fovx,
-                                            (float)tan_fovy, ptr<int>(radii), bytes(geomBuffer), bytes(binningBuffer), bytes(imageBuffer),
-                                            ptr<float>(gC), ptr<float>(gD), gp[0], nullptr, gp[2], gp[1], gp[3], gp[4], gp[5], gp[6],
-                                            gp[7], nullptr,
-                                            nullptr, nullptr, nullptr, nullptr, ptr<float>(perspec), nullptr, nullptr, nullptr,
-                                            g[8].data_ptr<float>(), nullptr, nullptr, nullptr, ptr<float>(gt), ptr<float>(gU),
-                                            scratch, nscr, abs.view[0], ptr<float>(gS));
+        p_al.stop();
+        Probe p_bc(HP_BWD_C);
+        return V::backward(st, s, im, W, H, R, gp, g[8].data_ptr<float>(), flags, need_gaussian_grads, scratch, nscr, abs.view[0]);
     });
     if (absgrad) g.push_back(std::move(abs.t));
     return g;
+}
+
+// The reference's `_C.rasterize_gaussians_backward` signatures.  dL_dout_alpha / dL_dout_sil: the silhouette image [1,H,W], or
+// undefined / empty (NULL)
+std::vector<Tensor> light_backward(const Tensor& background, const Tensor& means3D, const Tensor& radii, const Tensor& colors,
+                                   const Tensor& scales, const Tensor& rotations, double scale_modifier, const Tensor& cov3D,
+                                   const Tensor& viewmatrix, const Tensor& projmatrix, double tan_fovx, double tan_fovy,
+                                   const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_median,
+                                   const Tensor& dL_dout_var, const Tensor& gt_depth, const Tensor& sh, long degree, const Tensor& campos,
+                                   const Tensor& geomBuffer, long R, const Tensor& binningBuffer, const Tensor& imageBuffer,
+                                   const Tensor& alphas, bool debug, const Tensor& perspec, bool track_off, bool map_off,
+                                   bool need_gaussian_grads, const Tensor& dL_dout_alpha, bool absgrad) {
+    const BwdScene s(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tan_fovx,
+                     tan_fovy, gt_depth, sh, degree, campos, geomBuffer, binningBuffer, imageBuffer, perspec);
+    return backward<Light>(s, {&dL_dout_color, &dL_dout_depth, &dL_dout_median, &dL_dout_var, &dL_dout_alpha, &alphas}, R,
+                           {debug, track_off, map_off}, need_gaussian_grads, absgrad);
+}
+std::vector<Tensor> full_backward(const Tensor& background, const Tensor& means3D, const Tensor& radii, const Tensor& colors,
+                                  const Tensor& scales, const Tensor& rotations, double scale_modifier, const Tensor& cov3D,
+                                  const Tensor& viewmatrix, const Tensor& gt_depth, const Tensor& projmatrix, double tan_fovx,
+                                  double tan_fovy, const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_unc,
+                                  const Tensor& sh, long degree, const Tensor& campos, const Tensor& geomBuffer, long R,
+                                  const Tensor& binningBuffer, const Tensor& imageBuffer, long NG, const Tensor& perspec,
+                                  bool need_gaussian_grads, const Tensor& dL_dout_sil, bool absgrad) {
+    (void)NG;  // (sizes the reference's pair lists, which this backward does not have)
+    const BwdScene s(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrix, projmatrix, tan_fovx,
+                     tan_fovy, gt_depth, sh, degree, campos, geomBuffer, binningBuffer, imageBuffer, perspec);
+    return backward<Full>(s, {&dL_dout_color, &dL_dout_depth, &dL_dout_unc, &dL_dout_sil}, R, {}, need_gaussian_grads, absgrad);
 }
 
 // ------------------------------------------------------------------------------------------------ autograd nodes
@@ -659,7 +596,7 @@ std::vector<Tensor> full_backward(const Tensor& background, const Tensor& means3
 // F/__init__.py:46-151).  Kept as that (dgr_amd.light / full._RasterizeGaussians: the debug path, the ctypes binding), it
 // costs a Python frame, a tuple of forty arguments and a context object per forward, and in the backward a hand-off from the
 // autograd engine's thread into the interpreter -- together more than the GPU needs for a 640x480 / 100 k view (BASELINE
-// config 2).  The nodes below are the same Function in C++: ONE Python -> C++ crossing per forward, and a backward that runs
+// config 2).  Node<V> below is the same Function in C++: ONE Python -> C++ crossing per forward, and a backward that runs
 // inside the engine without the interpreter.  Same inputs in the same order, same saved state, same outputs, same None
 // gradients for gt_depth and the settings.
 //
@@ -693,15 +630,27 @@ void consume_post_backward_wait(void* stream) {
     if (ev) check(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)ev, 0) == hipSuccess ? 0 : DGR_ERR_HIP);
 }
 
-using torch::autograd::AutogradContext;
-using torch::autograd::variable_list;
-
-// what a forward reports beside its output tensors (read by light_apply / full_apply right after Function::apply)
-struct FwdReport {
-    long rendered = -1, related = -1, ticket = -1, cap = 0;
-    Tensor status;
-};
+// a forward's report on its way out of Function::apply (read by apply<V> right after it)
 thread_local FwdReport g_report;
+
+// A node's scalars in ctx->saved_data: each() names every key once, for the forward's write and the backward's read
+struct SavedScalars {
+    double scale_modifier, tanfovx, tanfovy;
+    int64_t degree, R, H, W, options;  // R: num_rendered, or a lazy forward's capacity; options: the forward's per-call option word
+    bool track_off = false, map_off = false;
+    template <typename Op>
+    void each(Op op, bool tracking_flags) {
+        op("scale_modifier", scale_modifier); op("tanfovx", tanfovx); op("tanfovy", tanfovy); op("degree", degree); op("R", R);
+        op("H", H); op("W", W); op("options", options);
+        if (tracking_flags) { op("track_off", track_off); op("map_off", map_off); }
+    }
+    template <typename Map>
+    void write(Map& d, bool tracking_flags) { each([&](const char* key, auto& v) { d[key] = v; }, tracking_flags); }
+    template <typename Map>
+    void read(Map& d, bool tracking_flags) {
+        each([&](const char* key, auto& v) { v = d[key].template to<std::decay_t<decltype(v)>>(); }, tracking_flags);
+    }
+};
 
 // an output that did not take part in the loss arrives undefined: zeros, as the reference's autograd would have passed
 inline Tensor grad_or_zeros(const Tensor& g, long c, long H, long W, const c10::Device& dev) {
@@ -725,16 +674,19 @@ struct UnderOptions {
 
 // A backward's gradients (means2D, colors, opacity, means3D, cov3D, sh, scales, rotations, dL_dview [4,4]) in the order of the
 // nodes' inputs (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix); None for the rest
-variable_list node_grads(std::vector<Tensor>& g, size_t n_inputs) {
-    variable_list out(n_inputs);
+constexpr size_t kNodeInputs = 25;
+variable_list node_grads(std::vector<Tensor>& g) {
+    variable_list out(kNodeInputs);
     out[0] = std::move(g[3]); out[1] = std::move(g[0]); out[2] = std::move(g[5]); out[3] = std::move(g[1]);
     out[4] = std::move(g[2]); out[5] = std::move(g[6]); out[6] = std::move(g[7]); out[7] = std::move(g[4]);
     out[8] = std::move(g[8]);
     return out;
 }
 
-struct LightNode : public torch::autograd::Function<LightNode> {
-    // inputs 0..9 as L/__init__.py:46-60; then the settings' tensors and scalars (L/__init__.py:180-195) and the binning policy
+template <class V>
+struct Node : public torch::autograd::Function<Node<V>> {
+    // inputs 0..9 as L/__init__.py:46-60; then the settings' tensors and scalars (L/__init__.py:180-195; track_off and map_off are the
+    // light variant's, false for the full one) and the binning policy
     static variable_list forward(AutogradContext* ctx, const Tensor& means3D, const Tensor& means2D, const Tensor& sh,
                                  const Tensor& colors_precomp, const Tensor& opacities, const Tensor& scales, const Tensor& rotations,
                                  const Tensor& cov3Ds_precomp, const Tensor& viewmatrix, const Tensor& gt_depth, const Tensor& bg,
@@ -743,142 +695,72 @@ struct LightNode : public torch::autograd::Function<LightNode> {
                                  bool track_off, bool map_off, int64_t capacity, int64_t mode) {
         (void)means2D;  // never read (L/__init__.py:66-87): it exists so that autograd hands dL_dmeans2D back
         Probe p_f(HP_FWD);
-        LightFwd o = light_forward_core(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3Ds_precomp,
-                                        viewmatrix, gt_depth, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered,
-                                        false, capacity, mode);
-        g_report.rendered = o.rendered; g_report.ticket = o.ticket; g_report.cap = o.cap; g_report.status = o.status;
+        const Fwd o = forward_core<V>(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3Ds_precomp, viewmatrix,
+                                      gt_depth, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, /*debug=*/false,
+                                      capacity, mode, /*want_related=*/false);
+        g_report = o;
         Probe p_s(HP_SAVE);
-        // L/__init__.py:101-102 (+ the settings' tensors, which the Python Function reads from ctx.raster_settings)
-        ctx->save_for_backward({colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, o.radii, sh, o.geom,
-                                o.binning, o.img, o.alpha, gt_depth, bg, projmatrix, campos, perspec});
-        auto& d = ctx->saved_data;
-        d["scale_modifier"] = scale_modifier; d["tanfovx"] = tanfovx; d["tanfovy"] = tanfovy; d["degree"] = degree;
-        d["R"] = (int64_t)(o.rendered >= 0 ? o.rendered : o.cap); d["track_off"] = track_off; d["map_off"] = map_off;
-        d["H"] = H; d["W"] = W;
-        d["options"] = (int64_t)dgr_thread_options_effective();  // the backward runs under the forward's per-call options
-        // four of the eight outputs (radii, opacity_map, gau_uncertainty, gau_related_pixels) have no gradient input in the
-        // backward -- opacity_map has one with the option "silhouette_grad" -- : no zero-filled gradient tensors for them
+        variable_list sv(V::N_SAVED);
+        sv[S_COLORS] = colors_precomp; sv[S_MEANS3D] = means3D; sv[S_SCALES] = scales; sv[S_ROTATIONS] = rotations;
+        sv[S_COV3D] = cov3Ds_precomp; sv[S_VIEW] = viewmatrix; sv[S_RADII] = o.radii; sv[S_SH] = sh; sv[S_GEOM] = o.geom;
+        sv[S_BINNING] = o.binning; sv[S_IMG] = o.img; sv[S_GT] = gt_depth; sv[S_BG] = bg; sv[S_PROJ] = projmatrix;
+        sv[S_CAMPOS] = campos; sv[S_PERSPEC] = perspec;
+        V::save_extra(sv, o);
+        ctx->save_for_backward(std::move(sv));
+        // (the backward runs under the forward's per-call options)
+        SavedScalars{scale_modifier, tanfovx, tanfovy, degree, (int64_t)(o.rendered >= 0 ? o.rendered : o.cap), H, W,
+                     (int64_t)dgr_thread_options_effective(), track_off, map_off}
+            .write(ctx->saved_data, V::tracking_flags);
+        // no zero-filled gradient tensors for the outputs that have no gradient input in the backward
         ctx->set_materialize_grads(false);
-        ctx->mark_non_differentiable({o.radii, o.px});
-        return {o.color, o.radii, o.depth, o.median, o.var, o.alpha, o.unc, o.px};
+        ctx->mark_non_differentiable(V::non_differentiable(o));
+        return V::node_outputs(o);
     }
 
     static variable_list backward(AutogradContext* ctx, variable_list grad) {
         Probe p_b(HP_BWD);
         Probe p_u(HP_UNPACK);
         const auto sv = ctx->get_saved_variables();
-        auto& d = ctx->saved_data;
-        const Tensor& means3D = sv[1];
+        SavedScalars c;
+        c.read(ctx->saved_data, V::tracking_flags);
+        const Tensor& means3D = sv[S_MEANS3D];
         const c10::Device dev = means3D.device();
-        const long H = d["H"].toInt(), W = d["W"].toInt();
         p_u.stop();
-        const Tensor gC = grad_or_zeros(grad[0], 3, H, W, dev), gD = grad_or_zeros(grad[2], 1, H, W, dev);
-        // (no gradient image for the median depth / the depth variance: NULL at the C ABI, which then runs the lean blend backward
-        //  -- no zero images are made, filled and read)
-        const Tensor gM = grad[3].defined() ? grad[3] : Tensor();
-        const Tensor gV = grad[4].defined() ? grad[4] : Tensor();
-        // (option "silhouette_grad" at the forward: the opacity_map gradient is the silhouette image; unused, or the option off: NULL)
-        const int options = (int)d["options"].toInt();
-        const Tensor gA = silhouette_on(options) && grad[5].defined() ? grad[5] : Tensor();
-        const UnderOptions under(options);  // (the engine may run this node on a thread of its own)
-        std::vector<Tensor> g = light_backward(sv[13], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4],
-                                               sv[5], sv[14], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD, gM, gV, sv[12],
-                                               sv[7], d["degree"].toInt(), sv[15], sv[8], d["R"].toInt(), sv[9], sv[10], sv[11], false,
-                                               sv[16], d["track_off"].toBool(), d["map_off"].toBool(), needs_gaussian_grads(ctx), gA,
-                                               /*absgrad=*/false);
+        const Tensor gC = grad_or_zeros(grad[0], 3, c.H, c.W, dev), gD = grad_or_zeros(grad[2], 1, c.H, c.W, dev), none;
+        const auto images = V::node_images(gC, gD, grad, sv, silhouette_on((int)c.options), none);
+        const UnderOptions under((int)c.options);  // (the engine may run this node on a thread of its own)
+        const BwdScene s(sv[S_BG], means3D, sv[S_RADII], sv[S_COLORS], sv[S_SCALES], sv[S_ROTATIONS], c.scale_modifier, sv[S_COV3D],
+                         sv[S_VIEW], sv[S_PROJ], c.tanfovx, c.tanfovy, sv[S_GT], sv[S_SH], c.degree, sv[S_CAMPOS], sv[S_GEOM],
+                         sv[S_BINNING], sv[S_IMG], sv[S_PERSPEC]);
+        std::vector<Tensor> g = ::backward<V>(s, images, c.R, {false, c.track_off, c.map_off}, needs_gaussian_grads(ctx), /*absgrad=*/false);
         consume_post_backward_wait(stream_of(dev));
-        // the reference sums a [H*W,4,4] buffer over dim 0 (L/__init__.py:160-161); here it is [1,4,4], already reduced
-        g[8] = view_of(g[8], 0, {4, 4}, at::kFloat);
-        return node_grads(g, 25);
+        // (the reference sums light's [H*W,4,4] buffer over dim 0, L/__init__.py:160-161; here it is [1,4,4], already reduced)
+        if (V::dview_leading_one) g[8] = view_of(g[8], 0, {4, 4}, at::kFloat);
+        return node_grads(g);
     }
 };
 
-// (color, radii, depth, depth_median, depth_var, opacity_map, gau_uncertainty, gau_related_pixels), num_rendered or -1,
-// ticket or -1, capacity used, device status word
-std::tuple<std::vector<Tensor>, long, long, long, Tensor>
-light_apply(const Tensor& means3D, const Tensor& means2D, const Tensor& sh, const Tensor& colors_precomp, const Tensor& opacities,
-            const Tensor& scales, const Tensor& rotations, const Tensor& cov3Ds_precomp, const Tensor& viewmatrix,
-            const Tensor& gt_depth, const Tensor& bg, const Tensor& projmatrix, const Tensor& campos, const Tensor& perspec,
-            double scale_modifier, double tanfovx, double tanfovy, long H, long W, long degree, bool prefiltered, bool track_off,
-            bool map_off, long capacity, long mode) {
+// `_RasterizeGaussians.apply` of a variant: (the report, V::node_outputs)
+template <class V>
+PyForward apply(const Tensor& means3D, const Tensor& means2D, const Tensor& sh, const Tensor& colors_precomp, const Tensor& opacities,
+                const Tensor& scales, const Tensor& rotations, const Tensor& cov3Ds_precomp, const Tensor& viewmatrix,
+                const Tensor& gt_depth, const Tensor& bg, const Tensor& projmatrix, const Tensor& campos, const Tensor& perspec,
+                double scale_modifier, double tanfovx, double tanfovy, long H, long W, long degree, bool prefiltered, bool track_off,
+                bool map_off, long capacity, long mode) {
     Probe p_a(HP_APPLY);
-    variable_list out = LightNode::apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
-                                         gt_depth, bg, projmatrix, campos, perspec, scale_modifier, tanfovx, tanfovy, (int64_t)H,
-                                         (int64_t)W, (int64_t)degree, prefiltered, track_off, map_off, (int64_t)capacity, (int64_t)mode);
+    variable_list out = Node<V>::apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
+                                       gt_depth, bg, projmatrix, campos, perspec, scale_modifier, tanfovx, tanfovy, (int64_t)H,
+                                       (int64_t)W, (int64_t)degree, prefiltered, track_off, map_off, (int64_t)capacity, (int64_t)mode);
     p_a.stop();
-    Tensor status = std::move(g_report.status);
+    PyForward result{g_report.py(), std::move(out)};
     g_report.status = Tensor();
-    return {std::move(out), g_report.rendered, g_report.ticket, g_report.cap, std::move(status)};
-}
-
-struct FullNode : public torch::autograd::Function<FullNode> {
-    static variable_list forward(AutogradContext* ctx, const Tensor& means3D, const Tensor& means2D, const Tensor& sh,
-                                 const Tensor& colors_precomp, const Tensor& opacities, const Tensor& scales, const Tensor& rotations,
-                                 const Tensor& cov3Ds_precomp, const Tensor& viewmatrix, const Tensor& gt_depth, const Tensor& bg,
-                                 const Tensor& projmatrix, const Tensor& campos, const Tensor& perspec, double scale_modifier,
-                                 double tanfovx, double tanfovy, int64_t H, int64_t W, int64_t degree, bool prefiltered,
-                                 int64_t capacity, int64_t mode) {
-        (void)means2D;
-        FullFwd o = full_forward_core(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier, cov3Ds_precomp,
-                                      viewmatrix, gt_depth, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered,
-                                      capacity, mode, /*want_related=*/false);
-        g_report.rendered = o.rendered; g_report.related = o.related; g_report.ticket = o.ticket; g_report.cap = o.cap;
-        g_report.status = o.status;
-        // F/__init__.py:89-90
-        ctx->save_for_backward({colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrix, o.radii, sh, o.geom,
-                                o.binning, o.img, gt_depth, bg, projmatrix, campos, perspec});
-        auto& d = ctx->saved_data;
-        d["scale_modifier"] = scale_modifier; d["tanfovx"] = tanfovx; d["tanfovy"] = tanfovy; d["degree"] = degree;
-        d["R"] = (int64_t)(o.rendered >= 0 ? o.rendered : o.cap); d["H"] = H; d["W"] = W;
-        d["options"] = (int64_t)dgr_thread_options_effective();
-        ctx->set_materialize_grads(false);
-        ctx->mark_non_differentiable({o.radii});
-        return {o.color, o.radii, o.depth, o.unc};
-    }
-
-    static variable_list backward(AutogradContext* ctx, variable_list grad) {
-        const auto sv = ctx->get_saved_variables();
-        auto& d = ctx->saved_data;
-        const Tensor& means3D = sv[1];
-        const c10::Device dev = means3D.device();
-        const long H = d["H"].toInt(), W = d["W"].toInt();
-        const Tensor gC = grad_or_zeros(grad[0], 3, H, W, dev), gD = grad_or_zeros(grad[2], 1, H, W, dev);
-        // (no gradient image for the uncertainty output: NULL at the C ABI, which then runs the lean blend backward.  Option
-        //  "silhouette_grad" at the forward: that gradient is the exact silhouette image, and dL_duncertainties NULL -- the lean kernel)
-        const int options = (int)d["options"].toInt();
-        const Tensor gU = grad[3].defined() ? grad[3] : Tensor();
-        const bool sil = silhouette_on(options);
-        const UnderOptions under(options);
-        std::vector<Tensor> g = full_backward(sv[12], means3D, sv[6], sv[0], sv[2], sv[3], d["scale_modifier"].toDouble(), sv[4], sv[5],
-                                              sv[11], sv[13], d["tanfovx"].toDouble(), d["tanfovy"].toDouble(), gC, gD,
-                                              sil ? Tensor() : gU, sv[7], d["degree"].toInt(), sv[14], sv[8], d["R"].toInt(), sv[9],
-                                              sv[10], 0, sv[15], needs_gaussian_grads(ctx), sil ? gU : Tensor(), /*absgrad=*/false);
-        consume_post_backward_wait(stream_of(dev));
-        return node_grads(g, 23);
-    }
-};
-
-// (color, radii, depth, uncertainty), num_rendered or -1, num_related or -1, ticket or -1, capacity used, device status word
-std::tuple<std::vector<Tensor>, long, long, long, long, Tensor>
-full_apply(const Tensor& means3D, const Tensor& means2D, const Tensor& sh, const Tensor& colors_precomp, const Tensor& opacities,
-           const Tensor& scales, const Tensor& rotations, const Tensor& cov3Ds_precomp, const Tensor& viewmatrix,
-           const Tensor& gt_depth, const Tensor& bg, const Tensor& projmatrix, const Tensor& campos, const Tensor& perspec,
-           double scale_modifier, double tanfovx, double tanfovy, long H, long W, long degree, bool prefiltered, long capacity,
-           long mode) {
-    variable_list out = FullNode::apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
-                                        gt_depth, bg, projmatrix, campos, perspec, scale_modifier, tanfovx, tanfovy, (int64_t)H,
-                                        (int64_t)W, (int64_t)degree, prefiltered, (int64_t)capacity, (int64_t)mode);
-    Tensor status = std::move(g_report.status);
-    g_report.status = Tensor();
-    return {std::move(out), g_report.rendered, g_report.related, g_report.ticket, g_report.cap, std::move(status)};
+    return result;
 }
 
 // ------------------------------------------------------------------------------------------------ batched views
-// dgr_amd.batch over the C ABI's batched entry points (include/dgr_hip.h: dgr_light_forward_batch / _backward_batch): V
+// dgr_amd.batch / batch_full over the C ABI's batched entry points (include/dgr_hip.h: dgr_*_forward_batch / _backward_batch): V
 // cameras over one set of Gaussians per call.  ONE attempt with the given binning capacity per view and no host
-// synchronisation; the capacity policy, the strict mode's status read and its retry stay in Python (dgr_amd/batch.py).
-// post_status: copy every view's status word to pinned memory behind an event (lazy mode) and return the tickets.
-// Returns ([V,4] status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px) and the tickets.
+// synchronisation; the capacity policy, the strict mode's status read and its retry stay in Python (dgr_amd/_binning.py).
 inline long batch_size(long V) {
     if (V < 1 || V > DGR_MAX_BATCH_VIEWS) throw std::runtime_error("1 .. " + std::to_string(DGR_MAX_BATCH_VIEWS) + " views per batch");
     return V;
@@ -896,200 +778,87 @@ std::vector<long> post_batch_status(bool post_status, int P, void* st, const Ten
     return tickets;
 }
 
+// post_status: copy every view's status word to pinned memory behind an event (lazy mode) and return the tickets.
+// Returns (V::batch_tensors: the [V,4] status first, then the outputs [V,...] and the state buffers) and the tickets.
+template <class V>
 std::tuple<std::vector<Tensor>, std::vector<long>>
-light_forward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
-                    const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                    const Tensor& viewmatrices_, const Tensor& gt_depths_, const Tensor& projmatrices_, double tan_fovx,
-                    double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_, bool prefiltered,
-                    long capacity, bool post_status) {
+forward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_, const Tensor& scales_,
+              const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_, const Tensor& viewmatrices_, const Tensor& gt_depths_,
+              const Tensor& projmatrices_, double tan_fovx, double tan_fovy, long H, long W, const Tensor& sh_, long degree,
+              const Tensor& campos_, bool prefiltered, long capacity, bool post_status) {
     const c10::Device dev = forward_device(means3D_);
-    const long V = batch_size(viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0);
+    const long nv = batch_size(viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0);
     const FwdInputs in(dev, background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrices_, gt_depths_,
                        projmatrices_, sh_, campos_);
     const int P = in.P;
     const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
     const auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
     const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
-    Tensor color = at::empty({V, 3, H, W}, f32), depth = at::empty({V, 1, H, W}, f32), median = at::empty({V, 1, H, W}, f32),
-           var = at::empty({V, 1, H, W}, f32), alpha = at::empty({V, 1, H, W}, f32);
-    Tensor radii = P ? at::empty({V, P}, i32) : at::zeros({V, P}, i32);
-    Tensor unc = P ? at::empty({V, P, 1}, f32) : at::zeros({V, P, 1}, f32);
-    Tensor px = P ? at::empty({V, P, 1}, i32) : at::zeros({V, P, 1}, i32);
-    Tensor geom = at::empty({V, (long long)std::max<size_t>(dgr_geometry_bytes(P), 1)}, u8);
-    Tensor img = at::empty({V, (long long)std::max<size_t>(dgr_image_bytes((int)W, (int)H), 1)}, u8);
-    Tensor binning = at::empty({V, (long long)std::max<size_t>(dgr_binning_bytes((int)capacity, (int)W, (int)H), 1)}, u8);
-    Tensor status = at::zeros({V, 4}, i32);
-    dgr_light_view w[DGR_MAX_BATCH_VIEWS];
-    for (long v = 0; v < V; v++) {
-        w[v] = dgr_light_view{row_bytes(geom, v), row_bytes(binning, v), (int)capacity, row_bytes(img, v), row<int>(status, v),
-                              row<float>(in.view, v), row<float>(in.proj, v), row<float>(in.campos, v), row<float>(color, v),
-                              row<float>(depth, v), row<float>(median, v), row<float>(alpha, v), row<float>(in.gt, v),
-                              row<float>(var, v), row<float>(unc, v), row<int>(px, v), row<int>(radii, v)};
-    }
+    Fwd o;
+    V::batch_outputs(o, nv, P, H, W, f32, i32);
+    o.geom = at::empty({nv, (long long)std::max<size_t>(dgr_geometry_bytes(P), 1)}, u8);
+    o.img = at::empty({nv, (long long)std::max<size_t>(dgr_image_bytes((int)W, (int)H), 1)}, u8);
+    o.binning = at::empty({nv, (long long)std::max<size_t>(dgr_binning_bytes((int)capacity, (int)W, (int)H), 1)}, u8);
+    o.status = at::zeros({nv, 4}, i32);
+    typename V::View w[DGR_MAX_BATCH_VIEWS];
+    for (long v = 0; v < nv; v++) w[v] = V::view(v, (int)capacity, o, in);
     void* st = stream_of(dev);
-    check(dgr_light_forward_batch(st, (int)V, w, P, (int)degree, in.M, ptr<float>(in.bg), (int)W, (int)H, ptr<float>(in.means3D),
-                                  ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity), ptr<float>(in.scales),
-                                  (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D), (float)tan_fovx, (float)tan_fovy,
-                                  prefiltered ? 1 : 0));
-    return {{status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px},
-            post_batch_status(post_status, P, st, status, V)};
+    check(std::apply([&](auto... scene) { return V::forward_batch(st, (int)nv, w, scene...); },
+                     scene_args(in, degree, W, H, scale_modifier, tan_fovx, tan_fovy, prefiltered)));
+    return {V::batch_tensors(o), post_batch_status(post_status, P, st, o.status, nv)};
 }
 
-// A batch backward's results: g[1..7] the arena's seven sums (gp[1..7]: their pointers; none without need_gaussian_grads), g[0]
-// every view's dL_dmeans2D [V,P,3] (need_means2D) or None, g[8] dL_dview [V,4,4]; and V scratch rows of nscr bytes
-struct BatchBwdOut {
-    std::vector<Tensor> g = std::vector<Tensor>(9);
-    float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    Tensor scratch;
-    size_t nscr;
-    BatchBwdOut(const c10::Device& dev, int P, int M, long V, long W, long H, bool need_gaussian_grads, bool need_means2D,
-                const std::vector<long>& num_rendered) {
-        const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-        if (need_gaussian_grads) {
-            grad_arena(dev, P, M, g.data(), gp);
-            g[0].zero_();  // the arena's one-view means2D slot: a batch returns those gradients per view, beside the arena
-            g[0] = need_means2D ? at::empty({V, P, 3}, f32) : Tensor();
-        }
-        g[8] = at::empty({V, 4, 4}, f32);
-        // (deterministic_grads: + 64 bytes per tile instance of the view with the most of them; the views' rows are equally long)
-        long rmax = 0;
-        for (long r : num_rendered) rmax = std::max(rmax, r);
-        nscr = std::max<size_t>(up256(dgr_light_backward_scratch_bytes_r(P, (int)W, (int)H, (int)rmax)), 256);
-        scratch = at::empty({V, (long long)nscr}, at::TensorOptions().dtype(at::kByte).device(dev));
-    }
-    float* dmean2D(long v) const { return g[0].defined() ? row<float>(g[0], v) : nullptr; }
-};
-inline int rendered_of(const std::vector<long>& num_rendered, long v) { return (size_t)v < num_rendered.size() ? (int)num_rendered[v] : 0; }
-
 // Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
-// the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).
-// sil (silhouette, dgr_light_backward_batch_silhouette): every view's opacity_map gradient [V,1,H,W], or undefined / empty (no
-// silhouette image); absgrad (dgr_light_backward_batch_absgrad): a tenth result, every view's absolute screen-space gradient [V,P,3]
-std::vector<Tensor> light_backward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
-                                         const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                                         const Tensor& viewmatrices_, const Tensor& projmatrices_, double tan_fovx, double tan_fovy,
+// the SUMS over the views, views of one flat arena laid out as a one-view backward's -- and dL_dview [V,4,4]).  `images`: every
+// view's gradient images [V,...]; absgrad (dgr_*_backward_batch_absgrad): a tenth result, every view's absolute screen-space
+// gradient [V,P,3]
+template <class V>
+std::vector<Tensor> backward_batch(const BwdScene& s, const std::array<const Tensor*, V::N_IMAGES>& images, BwdFlags flags,
+                                   bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered, bool absgrad) {
+    const long nv = s.view.size(0), H = images[V::GC]->size(2), W = images[V::GC]->size(3);
+    AbsGrad abs(absgrad, s.means3D, nv);
+    batch_size(nv);
+    typename V::Images im;
+    for (size_t i = 0; i < im.size(); i++) im[i] = f32c(*images[i], s.dev);
+    BatchBwdOut o(s.dev, s.P, s.M, nv, W, H, need_gaussian_grads, need_means2D, num_rendered);
+    typename V::ViewGrad w[DGR_MAX_BATCH_VIEWS];
+    const float* sil[DGR_MAX_BATCH_VIEWS] = {};
+    for (long v = 0; v < nv; v++) {
+        sil[v] = row<float>(im[V::SIL], v);
+        w[v] = V::view_grad(v, s, im, o, rendered_of(num_rendered, v));
+    }
+    check(V::backward_batch(stream_of(s.dev), (int)nv, w, s, W, H, o.gp, flags, need_gaussian_grads, abs.views(),
+                            im[V::SIL].numel() ? sil : nullptr));
+    if (absgrad) o.g.push_back(std::move(abs.t));
+    return o.g;
+}
+
+// sil: every view's opacity_map gradient (light) / exact silhouette gradient (full) [V,1,H,W], or undefined / empty
+std::vector<Tensor> light_backward_batch(const Tensor& background, const Tensor& means3D, const Tensor& radii, const Tensor& colors,
+                                         const Tensor& scales, const Tensor& rotations, double scale_modifier, const Tensor& cov3D,
+                                         const Tensor& viewmatrices, const Tensor& projmatrices, double tan_fovx, double tan_fovy,
                                          const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_median,
-                                         const Tensor& dL_dout_var, const Tensor& gt_depths_, const Tensor& sh_, long degree,
-                                         const Tensor& campos_, const Tensor& geom, const Tensor& binning, const Tensor& img,
-                                         const Tensor& alphas_, const Tensor& perspec_, bool track_off, bool map_off,
+                                         const Tensor& dL_dout_var, const Tensor& gt_depths, const Tensor& sh, long degree,
+                                         const Tensor& campos, const Tensor& geom, const Tensor& binning, const Tensor& img,
+                                         const Tensor& alphas, const Tensor& perspec, bool track_off, bool map_off,
                                          bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered,
                                          const Tensor& sil, bool absgrad) {
-    AbsGrad abs(absgrad, means3D_, viewmatrices_.size(0));
-    const c10::Device dev = means3D_.device();
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const long V = viewmatrices_.size(0), H = dL_dout_color.size(2), W = dL_dout_color.size(3);
-    batch_size(V);
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
-                 views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev), campos = f32c(campos_, dev),
-                 gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev), alphas = f32c(alphas_, dev), perspec = f32c_diag4(perspec_, dev),
-                 gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gM = f32c(dL_dout_median, dev),
-                 gV = f32c(dL_dout_var, dev), gA = f32c(sil, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
-    BatchBwdOut o(dev, P, M, V, W, H, need_gaussian_grads, need_means2D, num_rendered);
-    if (!need_gaussian_grads) map_off = true;  // nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
-    dgr_light_view_grad w[DGR_MAX_BATCH_VIEWS];
-    const float* sv[DGR_MAX_BATCH_VIEWS] = {};
-    for (long v = 0; v < V; v++) {
-        sv[v] = gA.numel() ? row<float>(gA, v) : nullptr;
-        w[v] = dgr_light_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
-                                   row<float>(projs, v), row<float>(campos, v), perspec_row(perspec, v), row<float>(alphas, v),
-                                   row<float>(gts, v), row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), row<float>(gM, v),
-                                   row<float>(gV, v), o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr,
-                                   rendered_of(num_rendered, v)};
-    }
-    // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    check(dgr_light_backward_batch_silhouette(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
-                                              ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(scales),
-                                              (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx,
-                                              (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3], o.gp[4], o.gp[5], o.gp[6], o.gp[7],
-                                              track_off ? 1 : 0, map_off ? 1 : 0, abs.views(), gA.numel() ? sv : nullptr));
-    if (absgrad) o.g.push_back(std::move(abs.t));
-    return o.g;
+    const BwdScene s(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrices, projmatrices, tan_fovx,
+                     tan_fovy, gt_depths, sh, degree, campos, geom, binning, img, perspec);
+    return backward_batch<Light>(s, {&dL_dout_color, &dL_dout_depth, &dL_dout_median, &dL_dout_var, &sil, &alphas},
+                                 {false, track_off, map_off}, need_gaussian_grads, need_means2D, num_rendered, absgrad);
 }
-
-// The full variant's batch (include/dgr_hip.h: dgr_full_forward_batch / _backward_batch; dgr_amd/batch_full.py), same contract.
-// Returns ([V,4] status, color [V,3,H,W], depth [V,1,H,W], uncertainty [V,1,H,W], radii [V,P], geom, binning, img) and the tickets.
-std::tuple<std::vector<Tensor>, std::vector<long>>
-full_forward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& colors_, const Tensor& opacity_,
-                   const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                   const Tensor& viewmatrices_, const Tensor& gt_depths_, const Tensor& projmatrices_, double tan_fovx,
-                   double tan_fovy, long H, long W, const Tensor& sh_, long degree, const Tensor& campos_, bool prefiltered,
-                   long capacity, bool post_status) {
-    const c10::Device dev = forward_device(means3D_);
-    const long V = batch_size(viewmatrices_.dim() == 3 ? viewmatrices_.size(0) : 0);
-    const FwdInputs in(dev, background, means3D_, colors_, opacity_, scales_, rotations_, cov3D_, viewmatrices_, gt_depths_,
-                       projmatrices_, sh_, campos_);
-    const int P = in.P;
-    const auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-    const auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
-    const auto u8 = at::TensorOptions().dtype(at::kByte).device(dev);
-    Tensor color = at::empty({V, 3, H, W}, f32), depth = at::empty({V, 1, H, W}, f32), unc = at::empty({V, 1, H, W}, f32);
-    Tensor radii = P ? at::empty({V, P}, i32) : at::zeros({V, P}, i32);
-    Tensor geom = at::empty({V, (long long)std::max<size_t>(dgr_geometry_bytes(P), 1)}, u8);
-    Tensor img = at::empty({V, (long long)std::max<size_t>(dgr_image_bytes((int)W, (int)H), 1)}, u8);
-    Tensor binning = at::empty({V, (long long)std::max<size_t>(dgr_binning_bytes((int)capacity, (int)W, (int)H), 1)}, u8);
-    Tensor status = at::zeros({V, 4}, i32);
-    dgr_full_view w[DGR_MAX_BATCH_VIEWS];
-    for (long v = 0; v < V; v++) {
-        w[v] = dgr_full_view{row_bytes(geom, v), row_bytes(binning, v), (int)capacity, row_bytes(img, v), row<int>(status, v),
-                             row<float>(in.view, v), row<float>(in.proj, v), row<float>(in.campos, v), row<float>(color, v),
-                             row<float>(depth, v), row<float>(in.gt, v), row<float>(unc, v), row<int>(radii, v)};
-    }
-    void* st = stream_of(dev);
-    check(dgr_full_forward_batch(st, (int)V, w, P, (int)degree, in.M, ptr<float>(in.bg), (int)W, (int)H, ptr<float>(in.means3D),
-                                 ptr<float>(in.sh), ptr<float>(in.colors), ptr<float>(in.opacity), ptr<float>(in.scales),
-                                 (float)scale_modifier, ptr<float>(in.rotations), ptr<float>(in.cov3D), (float)tan_fovx, (float)tan_fovy,
-                                 prefiltered ? 1 : 0));
-    return {{status, color, depth, unc, radii, geom, binning, img}, post_batch_status(post_status, P, st, status, V)};
-}
-
-// Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations --
-// the SUMS over the views, views of one flat arena laid out as light_backward's -- and dL_dview [V,4,4]).  An undefined or
-// empty dL_dout_unc: no view's loss used the uncertainty image (the lean blend backward).
-// sil (silhouette, dgr_full_backward_batch_silhouette): every view's exact silhouette gradient [V,1,H,W], or undefined / empty;
-// absgrad (dgr_full_backward_batch_absgrad): a tenth result, every view's absolute screen-space gradient [V,P,3]
-std::vector<Tensor> full_backward_batch(const Tensor& background, const Tensor& means3D_, const Tensor& radii, const Tensor& colors_,
-                                        const Tensor& scales_, const Tensor& rotations_, double scale_modifier, const Tensor& cov3D_,
-                                        const Tensor& viewmatrices_, const Tensor& projmatrices_, double tan_fovx, double tan_fovy,
+std::vector<Tensor> full_backward_batch(const Tensor& background, const Tensor& means3D, const Tensor& radii, const Tensor& colors,
+                                        const Tensor& scales, const Tensor& rotations, double scale_modifier, const Tensor& cov3D,
+                                        const Tensor& viewmatrices, const Tensor& projmatrices, double tan_fovx, double tan_fovy,
                                         const Tensor& dL_dout_color, const Tensor& dL_dout_depth, const Tensor& dL_dout_unc,
-                                        const Tensor& gt_depths_, const Tensor& sh_, long degree, const Tensor& campos_,
-                                        const Tensor& geom, const Tensor& binning, const Tensor& img, const Tensor& perspec_,
-                                        bool need_gaussian_grads, bool need_means2D, const std::vector<long>& num_rendered,
-                                        const Tensor& sil, bool absgrad) {
-    AbsGrad abs(absgrad, means3D_, viewmatrices_.size(0));
-    const c10::Device dev = means3D_.device();
-    c10::hip::HIPGuardMasqueradingAsCUDA guard(dev);
-    const int P = (int)means3D_.size(0);
-    const long V = viewmatrices_.size(0), H = dL_dout_color.size(2), W = dL_dout_color.size(3);
-    batch_size(V);
-    const bool lean = !dL_dout_unc.defined() || dL_dout_unc.numel() == 0;
-    const Tensor means3D = f32c(means3D_, dev), bg = f32c(background, dev), colors = f32c(colors_, dev),
-                 scales = f32c(scales_, dev), rotations = f32c(rotations_, dev), cov3D = f32c(cov3D_, dev),
-                 views = f32c(viewmatrices_, dev), projs = f32c(projmatrices_, dev), campos = f32c(campos_, dev),
-                 gts = f32c(gt_depths_, dev), sh = f32c(sh_, dev), perspec = f32c_diag4(perspec_, dev),
-                 gC = f32c(dL_dout_color, dev), gD = f32c(dL_dout_depth, dev), gU = lean ? Tensor() : f32c(dL_dout_unc, dev),
-                 gS = f32c(sil, dev);
-    const int M = sh.numel() != 0 ? (int)sh.size(1) : 0;
-    BatchBwdOut o(dev, P, M, V, W, H, need_gaussian_grads, need_means2D, num_rendered);
-    dgr_full_view_grad w[DGR_MAX_BATCH_VIEWS];
-    const float* sv[DGR_MAX_BATCH_VIEWS] = {};
-    for (long v = 0; v < V; v++) {
-        sv[v] = gS.numel() ? row<float>(gS, v) : nullptr;
-        w[v] = dgr_full_view_grad{row_bytes(geom, v), row_bytes(binning, v), row_bytes(img, v), row<float>(views, v),
-                                  row<float>(projs, v), row<float>(campos, v), perspec_row(perspec, v), row<float>(gts, v),
-                                  row<int>(radii, v), row<float>(gC, v), row<float>(gD, v), lean ? nullptr : row<float>(gU, v),
-                                  o.dmean2D(v), row<float>(o.g[8], v), row_bytes(o.scratch, v), o.nscr, rendered_of(num_rendered, v)};
-    }
-    // gp: [1] colors [2] opacity [3] means3D [4] cov3D [5] sh [6] scales [7] rotations
-    check(dgr_full_backward_batch_silhouette(stream_of(dev), (int)V, w, P, (int)degree, M, ptr<float>(bg), (int)W, (int)H,
-                                             ptr<float>(means3D), ptr<float>(sh), ptr<float>(colors), ptr<float>(scales),
-                                             (float)scale_modifier, ptr<float>(rotations), ptr<float>(cov3D), (float)tan_fovx,
-                                             (float)tan_fovy, o.gp[2], o.gp[1], o.gp[3], o.gp[4], o.gp[5], o.gp[6], o.gp[7], abs.views(),
-                                             gS.numel() ? sv : nullptr));
-    if (absgrad) o.g.push_back(std::move(abs.t));
-    return o.g;
+                                        const Tensor& gt_depths, const Tensor& sh, long degree, const Tensor& campos, const Tensor& geom,
+                                        const Tensor& binning, const Tensor& img, const Tensor& perspec, bool need_gaussian_grads,
+                                        bool need_means2D, const std::vector<long>& num_rendered, const Tensor& sil, bool absgrad) {
+    const BwdScene s(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D, viewmatrices, projmatrices, tan_fovx,
+                     tan_fovy, gt_depths, sh, degree, campos, geom, binning, img, perspec);
+    return backward_batch<Full>(s, {&dL_dout_color, &dL_dout_depth, &dL_dout_unc, &sil}, {}, need_gaussian_grads, need_means2D,
+                                num_rendered, absgrad);
 }
 
 Tensor mark_visible(const Tensor& means3D_, const Tensor& viewmatrix_, const Tensor& projmatrix_) {  // L/rasterize_points.cu:238-256
@@ -1118,17 +887,17 @@ py::object status_poll(long ticket, bool wait) {
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.def("light_forward", &light_forward);
+    m.def("light_forward", &forward<Light>);
     m.def("light_backward", &light_backward);
-    m.def("full_forward", &full_forward);
+    m.def("full_forward", &forward<Full>);
     m.def("full_backward", &full_backward);
-    m.def("light_forward_batch", &light_forward_batch);
+    m.def("light_forward_batch", &forward_batch<Light>);
     m.def("light_backward_batch", &light_backward_batch);
-    m.def("full_forward_batch", &full_forward_batch);
+    m.def("full_forward_batch", &forward_batch<Full>);
     m.def("full_backward_batch", &full_backward_batch);
     m.def("host_prof_dump", &host_prof_dump);
-    m.def("light_apply", &light_apply);
-    m.def("full_apply", &full_apply);
+    m.def("light_apply", &apply<Light>);
+    m.def("full_apply", &apply<Full>);
     m.def("set_post_backward_wait", &set_post_backward_wait);
     m.def("drop_post_backward_wait", &drop_post_backward_wait);
     m.def("mark_visible", &mark_visible);

@@ -152,7 +152,7 @@ def check_async_errors():
 
 def _binning_policy(key, P, views=None):
     """(mode, capacity, cached count) of the next forward of shape `key` = (device, P, H, W); see csrc/torch_ext.cpp:
-    light_forward_core.  `views`: a batch of that many views, which leaves one status word per view unread (the depth,
+    forward_core.  `views`: a batch of that many views, which leaves one status word per view unread (the depth,
     lazy_depth() otherwise) and has no resize-callback form: it runs strict where a one-view forward takes mode 0."""
     cap = _capacity_cache.get(key, 0)
     if os.environ.get("DGR_FORWARD_MODE", "presized") == "callback" or P == 0:
@@ -199,6 +199,18 @@ def record(key, mode, cap, use, rendered, status, ticket=None, related=None):
     if mode == 1:
         _strict_read(key, cap, rendered, related)
     return rendered, related, rendered
+
+
+def compiled_forward(fn, args, device_index, P, H, W, full):
+    """A one-view forward of the compiled extension, `fn` = its light_forward / full_forward / light_apply / full_apply: the policy's
+    capacity and mode go in behind `args`, the forward's report (csrc/torch_ext.cpp: FwdReport) comes back in front of its tensors
+    and is recorded.  `full`: the report's num_related is the variant's (the light one records none).  Returns (R for the backward,
+    num_rendered and num_related to report, the tensors)."""
+    key = (device_index, P, H, W)
+    mode, use, cap = _binning_policy(key, P)
+    (rendered, related, ticket, used, status), tensors = fn(*args, use, mode)
+    rendered, related, R = record(key, mode, cap, used, rendered, status, ticket, related if full else None)
+    return R, rendered, related, tensors
 
 
 def strict_retry(key, cap, use, attempt, related=None):

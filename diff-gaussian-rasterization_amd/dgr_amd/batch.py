@@ -52,7 +52,7 @@ _row = _capi.row_ptr
 
 
 def _ext():
-    """the compiled torch extension (csrc/torch_ext.cpp: light_forward_batch / light_backward_batch -- allocation and
+    """the compiled torch extension (csrc/torch_ext.cpp: forward_batch<V> / backward_batch<V> -- allocation and
     marshalling in C++) when dgr_amd.light selected it, else None: the ctypes code below binds the same C ABI"""
     return _light._CompiledC.ext if _light._C is _light._CompiledC else None
 

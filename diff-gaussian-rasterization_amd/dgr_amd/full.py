@@ -109,13 +109,11 @@ class _CompiledC:
                               prefiltered):
         """(R for the backward, the `rasterize_gaussians` tuple): see dgr_amd.light._C.rasterize_gaussians_r."""
         P, H, W = means3D.size(0) if means3D.dim() else 0, int(image_height), int(image_width)
-        key = (means3D.device.index, P, H, W)
-        mode, use, cap = _binning._binning_policy(key, P)
-        (rendered, related, ticket, used, status, color, depth, unc, radii, geom, binning, img) = _CompiledC.ext.full_forward(
-            background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
-            gt_depth, projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered), use, mode)
-        rendered, related, R = _binning.record(key, mode, cap, used, rendered, status, ticket, related)
-        return R, (rendered, related, color, depth, unc, radii, geom, binning, img)
+        args = (background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix, gt_depth,
+                projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered), False)  # (no debug)
+        # tensors: color, depth, uncertainty, radii, geom, binning, img
+        R, rendered, related, tensors = _binning.compiled_forward(_CompiledC.ext.full_forward, args, means3D.device.index, P, H, W, True)
+        return R, (rendered, related, *tensors)
 
     @staticmethod
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -141,19 +139,15 @@ if _light._C is getattr(_light, "_CompiledC", None):  # the light module decided
 
 def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
                         gt_depth, rs):
-    """`_RasterizeGaussians.apply` through the autograd node compiled into the extension (csrc/torch_ext.cpp: FullNode); see
+    """`_RasterizeGaussians.apply` through the autograd node compiled into the extension (csrc/torch_ext.cpp: Node<Full>); see
     dgr_amd.light._rasterize_compiled."""
     P, H, W = (means3D.size(0) if means3D.dim() == 2 else 0), rs.image_height, rs.image_width
-    key = (means3D.device.index, P, H, W)
-    mode, use, cap = _binning._binning_policy(key, P)
-    out, rendered, related, ticket, used, status = _CompiledC.ext.full_apply(
-        means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, gt_depth, rs.bg,
-        rs.projmatrix, rs.campos, rs.perspec_matrix, rs.scale_modifier, rs.tanfovx, rs.tanfovy, H, W, rs.sh_degree,
-        rs.prefiltered, use, mode)
-    # (the strict node does not wait for num_related -- csrc/torch_ext.cpp: full_forward_core -- and reports -1: the record keeps
+    args = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, gt_depth, rs.bg,
+            rs.projmatrix, rs.campos, rs.perspec_matrix, rs.scale_modifier, rs.tanfovx, rs.tanfovy, H, W, rs.sh_degree,
+            rs.prefiltered, False, False)  # (track_off, map_off: the light variant's)
+    # (the strict node does not wait for num_related -- csrc/torch_ext.cpp: Full::after_strict -- and reports -1: the record keeps
     #  the last one read)
-    _binning.record(key, mode, cap, used, rendered, status, ticket, related)
-    return tuple(out)
+    return tuple(_binning.compiled_forward(_CompiledC.ext.full_apply, args, means3D.device.index, P, H, W, True)[3])
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,

@@ -336,14 +336,11 @@ class _CompiledC:
                               campos, prefiltered, debug):
         """(R for the backward, the `rasterize_gaussians` tuple): see _C.rasterize_gaussians_r."""
         P, H, W = means3D.size(0) if means3D.dim() else 0, int(image_height), int(image_width)
-        key = (means3D.device.index, P, H, W)
-        mode, use, cap = _binning._binning_policy(key, P)
-        (rendered, ticket, used, status, color, depth, median, var, alpha, radii, geom, binning, img, unc, px) = _CompiledC.ext.light_forward(
-            background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix,
-            gt_depth, projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered),
-            bool(debug), use, mode)
-        rendered, _, R = _binning.record(key, mode, cap, used, rendered, status, ticket)
-        return R, (rendered, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)
+        args = (background, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrix, gt_depth,
+                projmatrix, float(tan_fovx), float(tan_fovy), H, W, sh, int(degree), campos, bool(prefiltered), bool(debug))
+        # tensors: color, depth, median, var, alpha, radii, geom, binning, img, unc, px
+        R, rendered, _, tensors = _binning.compiled_forward(_CompiledC.ext.light_forward, args, means3D.device.index, P, H, W, False)
+        return R, (rendered, *tensors)
 
     @staticmethod
     def rasterize_gaussians_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
@@ -378,19 +375,15 @@ if os.environ.get("DGR_BINDING", "compiled") != "ctypes" and not os.environ.get(
 
 def _rasterize_compiled(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix,
                         gt_depth, rs):
-    """`_RasterizeGaussians.apply` through the autograd node compiled into the extension (csrc/torch_ext.cpp: LightNode):
+    """`_RasterizeGaussians.apply` through the autograd node compiled into the extension (csrc/torch_ext.cpp: Node<Light>):
     one Python -> C++ crossing per forward, the backward runs inside the autograd engine without the interpreter.  Same
     inputs, outputs, saved state and gradients as the Python Function below, which stays for the debug path and the ctypes
     binding."""
     P, H, W = (means3D.size(0) if means3D.dim() == 2 else 0), rs.image_height, rs.image_width
-    key = (means3D.device.index, P, H, W)
-    mode, use, cap = _binning._binning_policy(key, P)
-    out, rendered, ticket, used, status = _CompiledC.ext.light_apply(
-        means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, gt_depth, rs.bg,
-        rs.projmatrix, rs.campos, rs.perspec_matrix, rs.scale_modifier, rs.tanfovx, rs.tanfovy, H, W, rs.sh_degree,
-        rs.prefiltered, rs.track_off, rs.map_off, use, mode)
-    _binning.record(key, mode, cap, used, rendered, status, ticket)
-    return tuple(out)
+    args = (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrix, gt_depth, rs.bg,
+            rs.projmatrix, rs.campos, rs.perspec_matrix, rs.scale_modifier, rs.tanfovx, rs.tanfovy, H, W, rs.sh_degree,
+            rs.prefiltered, rs.track_off, rs.map_off)
+    return tuple(_binning.compiled_forward(_CompiledC.ext.light_apply, args, means3D.device.index, P, H, W, False)[3])
 
 
 def rasterize_gaussians(
@@ -427,7 +420,7 @@ def rasterize_gaussians(
 class _RasterizeGaussians(torch.autograd.Function):
     """`means2D_abs` (absgrad, an extension): one more leaf [P,3] whose gradient is the absolute screen-space gradient
     (include/dgr_hip.h: dgr_light_backward_absgrad); None when absent.  Over either binding's forward and backward: the compiled
-    LightNode has no such input.  With the option "silhouette_grad" on at the forward, the opacity_map gradient goes to the
+    compiled node has no such input.  With the option "silhouette_grad" on at the forward, the opacity_map gradient goes to the
     backward as the silhouette image (dgr_light_backward_silhouette); without it, it is dropped, as the reference does."""
 
     @staticmethod

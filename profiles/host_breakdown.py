@@ -157,11 +157,11 @@ if light._C is light._CompiledC:
 
     def ext_forward():
         o = ext.light_forward(*a_f)
-        lib.dgr_status_poll(o[1], 1, buf)
+        lib.dgr_status_poll(o[0][2], 1, buf)  # (the report's ticket)
         return o
 
     print(f"ext.light_forward + status poll            {timeit(ext_forward, 500, 1000):6.2f} us  (allocations + launches + status post)")
-    o = ext_forward()
-    a_b = (bg, m3, o[9], E, sc_, ro_, 1.0, E, vw_, proj, s.tanfovx, s.tanfovy, gC, gD, gM, gV, gt, sh_, deg, campos, o[10], cap, o[11],
-           o[12], o[8], False, persp, False, False, True, E, False)
+    _, (_, _, _, _, alpha_, radii_, geom_, binning_, img_, _, _) = ext_forward()
+    a_b = (bg, m3, radii_, E, sc_, ro_, 1.0, E, vw_, proj, s.tanfovx, s.tanfovy, gC, gD, gM, gV, gt, sh_, deg, campos, geom_, cap, binning_,
+           img_, alpha_, False, persp, False, False, True, E, False)
     print(f"ext.light_backward                         {timeit(lambda: ext.light_backward(*a_b)):6.2f} us  (allocations + launches)")

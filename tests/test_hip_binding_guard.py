@@ -1,4 +1,4 @@
-"""The compiled binding's outputs are windows of shared allocations built without the dispatcher (csrc/torch_ext.cpp: view_of).
+"""The compiled binding's outputs are windows of shared allocations built without the dispatcher (csrc/torch_support.h: view_of).
 What must not change for a caller: autograd's saved-tensor check.  An output the backward needs (opacity_map: the light backward
 derives T_final from it, L/diff_gaussian_rasterization/__init__.py:101-102) that is edited in place between forward and backward
 must raise exactly as it does through the Python autograd.Function over `_C`; an output the backward does not need (color) may be

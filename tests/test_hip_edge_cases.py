@@ -713,6 +713,36 @@ def test_compiled_and_ctypes_bindings_agree():
     assert torch.equal(present, L._CtypesC.mark_visible(hh.T(s.means), hh.T(s.view), hh.T(s.proj)))
 
 
+def test_compiled_and_ctypes_bindings_agree_full():
+    """The full variant's `_C` twice, as test_compiled_and_ctypes_bindings_agree: same 9-tuples, bit-identical forward -- the
+    uncertainty image included: csrc/render_full.hip stores it per pixel, no float atomics form it --, gradients equal up to atomic
+    order, dL_dview [4,4]."""
+    from dgr_amd import full as F
+    assert F._C is F._CompiledC, "the compiled extension was not built / not importable"
+    s = make_scene(4000, 112, 80, 12)
+    a = (hh.T(s.bg), hh.T(s.means), hh.E(), hh.T(s.opac), hh.T(s.scales), hh.T(s.rots), 1.0, hh.E(), hh.T(s.view), hh.T(s.gt),
+         hh.T(s.proj), s.tanfovx, s.tanfovy, s.H, s.W, hh.T(s.shs), 3, hh.T(s.campos), False)
+    outs = [C.rasterize_gaussians(*a) for C in (F._CompiledC, F._CtypesC)]
+    assert len(outs[0]) == len(outs[1]) == 9 and outs[0][0] == outs[1][0] > 0 and outs[0][1] == outs[1][1]
+    for i in (2, 3, 4, 5):  # color, depth, uncertainty, radii
+        assert torch.equal(outs[0][i], outs[1][i]), i
+
+    def backward(C, o, **kw):
+        (R, NG, color, depth, unc, radii, geom, binning, img) = o
+        return C.rasterize_gaussians_backward(
+            hh.T(s.bg), hh.T(s.means), radii, hh.E(), hh.T(s.scales), hh.T(s.rots), 1.0, hh.E(), hh.T(s.view), hh.T(s.gt), hh.T(s.proj),
+            s.tanfovx, s.tanfovy, hh.T(s.gC), hh.T(s.gD[None]), hh.T(s.gV[None]), hh.T(s.shs), 3, hh.T(s.campos), geom, R, binning, img,
+            NG, hh.T(s.persp), **kw)
+    grads = [backward(C, o) for C, o in zip((F._CompiledC, F._CtypesC), outs)]
+    assert len(grads[0]) == len(grads[1]) == 9 and tuple(grads[0][8].shape) == (4, 4)
+    for ga, gb in zip(*grads):
+        assert ga.shape == gb.shape
+        assert_grad_close(ga.cpu().numpy(), gb.cpu().numpy(), "binding", rel_to_max=2e-6, elem_rtol=1e-3, elem_frac=1e-3)
+    # tracking form: no per-Gaussian gradients
+    g = backward(F._CompiledC, outs[0], need_gaussian_grads=False)
+    assert all(x is None for x in g[:8]) and g[8].abs().sum() > 0
+
+
 def test_shared_cov3D_across_the_views_of_a_batch():
     """dgr_amd.multiview.shared_cov3D: the covariance of every Gaussian computed once for a batch of views
     and handed to each view as cov3D_precomp; autograd sums the views' dL_dcov3D and ONE conversion gives the scale /
