@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 
 #include "../../include/dgr_hip.h"
@@ -1127,6 +1128,72 @@ int dgr_densify_apply(void* stream, long rows, long rows_out, const void* plan, 
     }
     HIP_TRY(dgr::launch_densify_apply((size_t)rows, (size_t)rows_out, plan, n, tensors, scaling_raw, rotation_raw, noise, seed,
                                       (hipStream_t)stream));
+    return DGR_OK;
+}
+
+// rows + candidates must fit the int counts
+static const long SEED_MAX = 0x3fffffffL;
+static const char* seed_shape_error(int width, int height, int stride) {
+    if (width < 1 || height < 1) return "width and height must be positive";
+    if (stride < 1) return "stride must be positive";
+    if (dgr::seed_candidates(width, height, stride) > (size_t)SEED_MAX) return "2^30 candidates or more";
+    return nullptr;
+}
+size_t dgr_seed_plan_bytes(int width, int height, int stride) {
+    return seed_shape_error(width, height, stride) ? 0 : dgr::seed_plan_bytes(width, height, stride);
+}
+
+int dgr_seed_plan(void* stream, int width, int height, int stride, const float* depth_obs, const float* opacity_map,
+                  const float* depth, float depth_min, float depth_max, float silhouette_threshold, float depth_error_min,
+                  const float* depth_error_min_device, long rows, void* plan, int* counts8_device) {
+    const char* bad = seed_shape_error(width, height, stride);
+    if (!bad && (rows < 0 || rows > SEED_MAX)) bad = "rows must be 0 .. 2^30 - 1";
+    if (!bad && (!plan || !dgr::aligned16(plan))) bad = "plan is NULL or not 16-byte aligned";
+    if (!bad && (!counts8_device)) bad = "counts8_device is NULL";
+    if (!bad && (!depth_obs)) bad = "depth_obs is NULL";
+    if (bad) {
+        set_last_error(std::string("dgr_seed_plan: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_seed_plan(width, height, stride, depth_obs, opacity_map, depth, depth_min, depth_max, silhouette_threshold,
+                                  depth_error_min, depth_error_min_device, (size_t)rows, plan, counts8_device,
+                                  (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_seed_apply(void* stream, int width, int height, int stride, long rows, long rows_out, const void* plan, int n,
+                   const dgr_seed_tensor* tensors, const float* color_obs, const float* depth_obs, const float* viewmatrix,
+                   float fx, float fy, float cx, float cy, float pix) {
+    const char* bad = seed_shape_error(width, height, stride);
+    int n_xyz = 0;
+    if (!bad && (rows < 0 || rows > SEED_MAX)) bad = "rows must be 0 .. 2^30 - 1";
+    if (!bad && (rows_out < rows || rows_out - rows > (long)dgr::seed_candidates(width, height, stride)))
+        bad = "rows_out must be rows + the plan's count of new rows (rows .. rows + candidates)";
+    if (!bad && (!plan || !dgr::aligned16(plan))) bad = "plan is NULL or not 16-byte aligned";
+    if (!bad && (!depth_obs)) bad = "depth_obs is NULL";
+    if (!bad && (!viewmatrix)) bad = "viewmatrix is NULL";
+    if (!bad && (!(fx > 0.0f && fy > 0.0f && std::isfinite(fx) && std::isfinite(fy)))) bad = "fx and fy must be finite and positive";
+    if (!bad && (n < 1 || n > DGR_SEED_MAX_TENSORS)) bad = "n must be 1 .. DGR_SEED_MAX_TENSORS (24) tensors";
+    if (!bad && (!tensors)) bad = "tensors is NULL";
+    for (int i = 0; !bad && i < n; ++i) {
+        const dgr_seed_tensor& t = tensors[i];
+        if (t.k < 1 || t.k > (1 << 22)) bad = "a tensor with k < 1 or k > 2^22";
+        else if (t.mode < DGR_SEED_XYZ || t.mode > DGR_SEED_CONST) bad = "unknown mode";
+        else if (t.mode == DGR_SEED_XYZ && t.k != 3) bad = "the XYZ tensor must have k = 3";
+        else if (t.mode == DGR_SEED_XYZ && ++n_xyz > 1) bad = "more than one XYZ tensor";
+        else if (t.mode == DGR_SEED_LOG_SCALE && t.k != 3 && t.k != 1) bad = "a LOG_SCALE tensor must have k = 3 or k = 1";
+        else if (t.mode == DGR_SEED_RGB_DC && t.k != 3) bad = "an RGB_DC tensor must have k = 3";
+        else if (t.mode == DGR_SEED_RGB_DC && !color_obs) bad = "RGB_DC needs color_obs";
+        else if (t.mode == DGR_SEED_QUAT_IDENTITY && t.k != 4) bad = "a QUAT_IDENTITY tensor must have k = 4";
+        else if (rows_out > 0 && (!t.dst || (rows > 0 && !t.src))) bad = "a tensor with a NULL dst, or a NULL src with rows > 0";
+    }
+    if (bad) {
+        set_last_error(std::string("dgr_seed_apply: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_seed_apply(width, height, stride, (size_t)rows, (size_t)rows_out, plan, n, tensors, color_obs, depth_obs,
+                                   viewmatrix, (float)(1.0 / (double)fx), (float)(1.0 / (double)fy), cx, cy, pix,
+                                   (hipStream_t)stream));
     return DGR_OK;
 }
 

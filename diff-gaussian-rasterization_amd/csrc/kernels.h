@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_ext.h>
 #include "dgr_common.h"
-#include "../../include/dgr_hip.h"  // dgr_densify_tensor
+#include "../../include/dgr_hip.h"  // dgr_densify_tensor, dgr_seed_tensor
 
 namespace dgr {
 
@@ -299,6 +299,17 @@ hipError_t launch_densify_plan(size_t rows, const float* grad_accum, const float
 hipError_t launch_densify_apply(size_t rows, size_t rows_out, const void* plan, int n, const dgr_densify_tensor* tensors,
                                 const float* scaling_raw, const float* rotation_raw, const float* noise,
                                 unsigned long long seed, hipStream_t stream);
+// fused map expansion from an RGB-D keyframe (seed.hip): decide + scan over the candidate pixels into `plan` and counts[8]
+// (device), then one apply launch for n tensors (old rows copied, one new row per selected pixel)
+size_t seed_candidates(int W, int H, int stride);
+size_t seed_plan_bytes(int W, int H, int stride);
+hipError_t launch_seed_plan(int W, int H, int stride, const float* depth_obs, const float* opacity_map, const float* depth,
+                            float depth_min, float depth_max, float silhouette_threshold, float depth_error_min,
+                            const float* depth_error_min_dev, size_t rows, void* plan, int* counts, hipStream_t stream);
+hipError_t launch_seed_apply(int W, int H, int stride, size_t rows, size_t rows_out, const void* plan, int n,
+                             const dgr_seed_tensor* tensors, const float* color_obs, const float* depth_obs,
+                             const float* viewmatrix, float inv_fx, float inv_fy, float cx, float cy, float pix,
+                             hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

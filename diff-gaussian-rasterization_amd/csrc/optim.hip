@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "kernels.h"
+#include "plan_scan.h"
 
 namespace dgr {
 namespace {
@@ -97,9 +98,6 @@ constexpr unsigned ACT_SURVIVE = 1u, ACT_CLONE = 2u, ACT_CHILDREN = 4u, ACT_SPLI
 constexpr int PLAN_HEADER_INTS = 16;
 constexpr float LOG_1P6 = 0x1.e148a2p-2f;  // logf(1.6f)
 
-__device__ inline int lane_rank(unsigned long long m) {  // set bits of m below this lane
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 __host__ __device__ inline size_t plan_blocks(size_t rows) { return (rows + 255) / 256; }
 __device__ inline int4* plan_block_table(void* plan) { return reinterpret_cast<int4*>(static_cast<int*>(plan) + PLAN_HEADER_INTS); }
 __device__ inline const int4* plan_block_table(const void* plan) {
@@ -159,45 +157,11 @@ __global__ void __launch_bounds__(256) densify_decide_kernel(size_t rows, const 
     }
 }
 
-__device__ inline int4 add4(int4 a, int4 b) { return make_int4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-// One workgroup: exclusive scan of the block totals in place, 256 blocks per pass with the running totals carried from
-// pass to pass; then the counts.
+// One workgroup: exclusive scan of the block totals in place (plan_scan.h); then the counts.
 __global__ void __launch_bounds__(256) densify_scan_kernel(size_t blocks, void* plan, int* __restrict__ counts) {
     __shared__ int4 wave_sum[4];
-    int4* table = plan_block_table(plan);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int4 carry = make_int4(0, 0, 0, 0);
-    for (size_t base = 0; base < blocks; base += 256) {
-        const size_t b = base + threadIdx.x;
-        const int4 own = b < blocks ? table[b] : make_int4(0, 0, 0, 0);
-        int4 inc = own;  // inclusive scan within the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            int4 up;
-            up.x = __shfl_up(inc.x, d);
-            up.y = __shfl_up(inc.y, d);
-            up.z = __shfl_up(inc.z, d);
-            up.w = __shfl_up(inc.w, d);
-            if (lane >= d) inc = add4(inc, up);
-        }
-        if (lane == 63) wave_sum[wave] = inc;
-        __syncthreads();
-        int4 before = carry;
-        for (int w = 0; w < wave; ++w) before = add4(before, wave_sum[w]);
-        if (b < blocks) table[b] = make_int4(before.x + inc.x - own.x, before.y + inc.y - own.y, before.z + inc.z - own.z,
-                                             before.w + inc.w - own.w);
-        carry = add4(add4(add4(add4(carry, wave_sum[0]), wave_sum[1]), wave_sum[2]), wave_sum[3]);
-        __syncthreads();  // wave_sum is rewritten by the next pass
-    }
-    if (threadIdx.x < 8) {
-        const int c[8] = {carry.x + carry.y + 2 * carry.z, carry.x, carry.y, 2 * carry.z, carry.w, 0, 0, 0};
-        int v = c[0];
-#pragma unroll
-        for (int s = 1; s < 8; ++s) v = threadIdx.x == s ? c[s] : v;
-        counts[threadIdx.x] = v;
-        static_cast<int*>(plan)[threadIdx.x] = v;
-    }
+    const int4 carry = scan_block_totals(plan_block_table(plan), blocks, wave_sum);
+    write_counts8(carry.x + carry.y + 2 * carry.z, carry.x, carry.y, 2 * carry.z, carry.w, plan, counts);
 }
 
 // Philox4x32-10 (Salmon et al., SC'11) keyed by the seed, counter = (row, sample): the draw of a (row, sample) does not

@@ -60,9 +60,18 @@ class DensifyTensor(C.Structure):  # dgr_densify_tensor: one per-Gaussian tensor
 
 assert C.sizeof(DensifyTensor) == 24  # two pointers, two ints: the C layout
 
+
+class SeedTensor(C.Structure):  # dgr_seed_tensor: one per-Gaussian tensor of a dgr_seed_apply call
+    _fields_ = [("src", _vp), ("dst", _vp), ("k", _i), ("mode", _i), ("value", _f)]
+
+
+assert C.sizeof(SeedTensor) == 32  # two pointers, two ints, a float, padded to the pointers' alignment
+
 MAX_BATCH_VIEWS = 8  # DGR_MAX_BATCH_VIEWS
 DENSIFY_MAX_TENSORS = 24  # DGR_DENSIFY_MAX_TENSORS
 DENSIFY_COPY, DENSIFY_ZERO_NEW, DENSIFY_ZERO, DENSIFY_XYZ, DENSIFY_LOG_SCALE = range(5)  # DGR_DENSIFY_*
+SEED_MAX_TENSORS = 24  # DGR_SEED_MAX_TENSORS
+SEED_XYZ, SEED_LOG_SCALE, SEED_RGB_DC, SEED_QUAT_IDENTITY, SEED_CONST = range(5)  # DGR_SEED_*
 
 # argument lists follow include/dgr_hip.h one to one
 _SIGS = {
@@ -94,6 +103,10 @@ _SIGS = {
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),
     "dgr_densify_apply": (_i, [_vp, C.c_long, C.c_long, _vp, _i, C.POINTER(DensifyTensor), _vp, _vp, _vp, C.c_ulonglong]),
+    "dgr_seed_plan_bytes": (_sz, [_i, _i, _i]),
+    "dgr_seed_plan": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, C.c_long, _vp, _vp]),
+    "dgr_seed_apply": (_i, [_vp, _i, _i, _i, C.c_long, C.c_long, _vp, _i, C.POINTER(SeedTensor), _vp, _vp, _vp, _f, _f, _f, _f,
+                            _f]),
     "dgr_sparse_adam": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i]),
     "dgr_sparse_adam_capturable": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
     "dgr_set_option": (_i, [C.c_char_p, _i]),

@@ -6,6 +6,8 @@ both moments of the other rows are left untouched, as in 3DGS's sparse Adam; `st
 
 `densify_and_prune` is the step that changes P: 3DGS's densify_and_clone, densify_and_split and prune_points over every
 leaf, Adam moment and accumulator in three launches (`dgr_densify_plan`, `dgr_densify_apply`) and one host read.
+`seed_from_frame` is its sibling: it appends one Gaussian per unexplained pixel of an RGB-D keyframe (`dgr_seed_plan`,
+`dgr_seed_apply`).
 """
 import collections
 import ctypes
@@ -51,9 +53,9 @@ def densify_thresholds(grad_threshold, extent, percent_dense=0.01, min_opacity=0
             float(max_screen_size) if sized else inf)
 
 
-def _rows_tensor(t, P, what):
+def _rows_tensor(t, P, what, who="densify_and_prune"):
     if not t.is_cuda or t.dtype != torch.float32 or t.dim() < 1 or t.shape[0] != P:
-        raise RuntimeError(f"densify_and_prune: {what} must be a float32 GPU tensor with {P} rows")
+        raise RuntimeError(f"{who}: {what} must be a float32 GPU tensor with {P} rows")
     return t.detach().contiguous()
 
 
@@ -147,6 +149,159 @@ def densify_and_prune(params, optimizer, xyz_gradient_accum, denom, max_radii2D,
         optimizer.replace_params({params[name]: out[name] for name in params},
                                  {params[name]: moments[name] for name in moments})
     return out, zeroed[0], zeroed[1], zeroed[2], counts
+
+
+SeedCounts = collections.namedtuple("SeedCounts", "rows new valid unseen infront")
+SEED_ROLES = dict(DEFAULT_ROLES, f_dc="f_dc")
+
+
+def seed_constants(fx, fy, *, silhouette_threshold=0.5, depth_error_min=float("inf"), depth_range=(0.0, float("inf")), stride=1,
+                   init_opacity=0.5, scale_factor=1.0):
+    """The host values of `dgr_seed_plan` / `dgr_seed_apply`, formed in float64 (ctypes rounds each once to fp32): (depth_min,
+    depth_max, silhouette_threshold, depth_error_min, pix, opacity_raw) with pix = scale_factor * stride * 0.5 * (1 / fx +
+    1 / fy) and opacity_raw = logit(init_opacity)."""
+    inf = float("inf")
+    logit = -inf if init_opacity <= 0 else inf if init_opacity >= 1 else math.log(init_opacity / (1.0 - init_opacity))
+    return (float(depth_range[0]), float(depth_range[1]), float(silhouette_threshold), float(depth_error_min),
+            float(scale_factor) * stride * 0.5 * (1.0 / fx + 1.0 / fy), logit)
+
+
+def _image(t, shape, what):
+    """a float32 GPU image with `shape`'s elements whose trailing dimensions are `shape`'s (leading ones of size 1 allowed)"""
+    lead = t.dim() - len(shape) if t is not None else 0
+    if (t is None or not t.is_cuda or t.dtype != torch.float32 or lead < 0 or tuple(t.shape[lead:]) != tuple(shape) or
+            t.numel() != math.prod(shape)):
+        raise RuntimeError(f"seed_from_frame: {what} must be a float32 GPU tensor of shape {list(shape)}")
+    return t.detach().contiguous()
+
+
+@torch.no_grad()
+def seed_from_frame(params, optimizer, color_obs, depth_obs, viewmatrix, fx, fy, cx, cy, *, opacity_map=None, depth=None,
+                    silhouette_threshold=0.5, depth_error_min=float("inf"), depth_range=(0.0, float("inf")), stride=1,
+                    init_opacity=0.5, scale_factor=1.0, fill=None, roles=None, xyz_gradient_accum=None, denom=None,
+                    max_radii2D=None):
+    """Map expansion from an RGB-D keyframe, fused (include/dgr_hip.h: dgr_seed_plan / dgr_seed_apply; the semantics are stated
+    there): one new Gaussian per candidate pixel (every `stride`-th of every `stride`-th row) whose `depth_obs` lies inside
+    `depth_range` (exclusive) and which the map does not explain -- `opacity_map` (the forward's silhouette) below
+    `silhouette_threshold`, or the rendered `depth` more than `depth_error_min` behind the observed one; with neither image,
+    every valid candidate (the first frame).  New rows follow the old ones in row-major pixel order.
+
+    `color_obs` [3, H, W], `depth_obs` [H, W], `opacity_map` / `depth` [H, W] or [1, H, W]: float32 on the GPU.  `viewmatrix`:
+    16 floats on the GPU holding W2C^T (what the rasterizer takes, what `slam.pose_to_camera` returns): the pose never visits
+    the host.  `fx, fy, cx, cy`: pixels; a point on the optical axis lands on pixel (cx, cy).  `depth_error_min`: a float, or a
+    one-element float32 GPU tensor (a caller's k * median(error), no host read).
+    `params`: dict name -> leaf [P, ...] (P = 0: empty leaves); `roles` as densify_and_prune's plus "f_dc" (the degree-0 SH
+    coefficients, [P, 3] or [P, 1, 3]; may be absent from `params`).  A new row is: xyz the pixel unprojected to the world;
+    scaling log(depth * scale_factor * stride * (1 / fx + 1 / fy) / 2) in all three components; rotation (1, 0, 0, 0); opacity
+    logit(init_opacity); f_dc (rgb - 0.5) / C0; every other leaf `fill.get(name, 0.0)`.  `optimizer`: a SparseAdam over the leaves
+    (or None): old rows keep their moments, new rows start from zero, the step count stays (`replace_params`).  The accumulators
+    that are given keep their old rows and get zeros for the new ones.
+
+    Returns (params, xyz_gradient_accum, denom, max_radii2D, SeedCounts(rows, new, valid, unseen, infront)), `requires_grad`
+    preserved on every leaf.  When no pixel is selected the inputs are returned as they are and the optimiser is untouched.  One
+    host synchronisation (the read of the counts), so the call cannot be recorded into a hipGraph."""
+    lib = _capi.load()
+    roles = dict(SEED_ROLES, **(roles or {}))
+    missing = [r for r in DEFAULT_ROLES if roles[r] not in params]
+    if missing:
+        raise KeyError(f"seed_from_frame: params has no entry for {missing} (roles = {roles})")
+    fill = dict(fill or {})
+    unknown = [name for name in fill if name not in params or name in roles.values()]
+    if unknown:
+        raise KeyError(f"seed_from_frame: fill names {unknown}, which are not leaves without a role")
+    xyz = params[roles["xyz"]]
+    if not xyz.is_cuda:
+        raise RuntimeError("seed_from_frame: the parameters must live on the GPU")
+    if int(stride) != stride or stride < 1:
+        raise ValueError("seed_from_frame: stride must be an integer >= 1")
+    P, dev, stride = xyz.shape[0], xyz.device, int(stride)
+    with _capi.on_device(dev):
+        st = _capi.stream_handle(dev.index)
+        if lib.dgr_stream_is_capturing(st):
+            raise RuntimeError("seed_from_frame changes the number of Gaussians and reads the new count on the host: it cannot be "
+                               "recorded into a hipGraph (call it between replays)")
+        if depth_obs.dim() < 2:
+            raise RuntimeError("seed_from_frame: depth_obs must be [H, W]")
+        H, W = depth_obs.shape[-2:]
+        depth_obs = _image(depth_obs, (H, W), "depth_obs")
+        opacity_map = None if opacity_map is None else _image(opacity_map, (H, W), "opacity_map")
+        depth = None if depth is None else _image(depth, (H, W), "depth")
+        has_dc = roles["f_dc"] in params
+        if has_dc or color_obs is not None:
+            color_obs = _image(color_obs, (3, H, W), "color_obs")
+        if not viewmatrix.is_cuda or viewmatrix.dtype != torch.float32 or viewmatrix.numel() != 16:
+            raise RuntimeError("seed_from_frame: viewmatrix must hold 16 float32 values on the GPU (W2C^T)")
+        viewmatrix = viewmatrix.detach().contiguous()
+        error_dev = None
+        if isinstance(depth_error_min, torch.Tensor):
+            if not depth_error_min.is_cuda or depth_error_min.dtype != torch.float32 or depth_error_min.numel() != 1:
+                raise RuntimeError("seed_from_frame: a tensor depth_error_min must be one float32 value on the GPU")
+            error_dev, depth_error_min = depth_error_min.detach().contiguous(), float("inf")
+        plan_bytes = lib.dgr_seed_plan_bytes(W, H, stride)
+        if plan_bytes == 0:
+            raise RuntimeError(f"seed_from_frame: a {W} x {H} frame at stride {stride} is refused (dgr_seed_plan_bytes)")
+        src = {name: _rows_tensor(t, P, f"params[{name!r}]", "seed_from_frame") for name, t in params.items()}
+        for role, shape in (("xyz", (P, 3)), ("scaling", (P, 3)), ("rotation", (P, 4))):
+            if tuple(src[roles[role]].shape) != shape:
+                raise RuntimeError(f"seed_from_frame: the {role} leaf must be [P, {shape[1]}]")
+        if math.prod(src[roles["opacity"]].shape[1:]) != 1:
+            raise RuntimeError("seed_from_frame: the opacity leaf must be [P] or [P, 1]")
+        if has_dc and math.prod(src[roles["f_dc"]].shape[1:]) != 3:
+            raise RuntimeError("seed_from_frame: the f_dc leaf must be [P, 3] or [P, 1, 3]")
+        acc = {"xyz_gradient_accum": xyz_gradient_accum, "denom": denom, "max_radii2D": max_radii2D}
+        for name, t in acc.items():
+            if t is not None:
+                if t.numel() != P:
+                    raise RuntimeError(f"seed_from_frame: {name} must have P elements")
+                acc[name] = _rows_tensor(t, P, name, "seed_from_frame")
+        depth_min, depth_max, sil, err_min, pix, opacity_raw = seed_constants(
+            fx, fy, silhouette_threshold=silhouette_threshold, depth_error_min=depth_error_min, depth_range=depth_range,
+            stride=stride, init_opacity=init_opacity, scale_factor=scale_factor)
+
+        plan = torch.empty(plan_bytes, dtype=torch.uint8, device=dev)
+        counts_dev = torch.empty(8, dtype=torch.int32, device=dev)
+        rc = lib.dgr_seed_plan(st, W, H, stride, depth_obs.data_ptr(), _capi.ptr(opacity_map), _capi.ptr(depth), depth_min,
+                               depth_max, sil, err_min, _capi.ptr(error_dev), P, plan.data_ptr(), counts_dev.data_ptr())
+        if rc:
+            raise RuntimeError(_capi.last_error())
+        counts = SeedCounts(*counts_dev.tolist()[:5])  # the call's one host synchronisation
+        if counts.new == 0:
+            return params, xyz_gradient_accum, denom, max_radii2D, counts
+        P_new = counts.rows
+
+        new = lambda t: torch.empty((P_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)  # noqa: E731
+        mode_of = {roles["xyz"]: (_capi.SEED_XYZ, 0.0), roles["scaling"]: (_capi.SEED_LOG_SCALE, 0.0),
+                   roles["rotation"]: (_capi.SEED_QUAT_IDENTITY, 0.0), roles["opacity"]: (_capi.SEED_CONST, opacity_raw),
+                   roles["f_dc"]: (_capi.SEED_RGB_DC, 0.0)}
+        table, out, moments = [], {}, {}
+        for name, t in src.items():
+            out[name] = new(t)
+            table.append((t, out[name]) + mode_of.get(name, (_capi.SEED_CONST, float(fill.get(name, 0.0)))))
+            state = optimizer.state.get(params[name]) if optimizer is not None else None
+            if state is not None:
+                moments[name] = (new(t), new(t))
+                table += [(m.contiguous(), d, _capi.SEED_CONST, 0.0) for m, d in zip(state, moments[name])]
+        grown = {}
+        for name, t in acc.items():
+            if t is not None:
+                grown[name] = new(t)
+                table.append((t, grown[name], _capi.SEED_CONST, 0.0))
+        for i in range(0, len(table), _capi.SEED_MAX_TENSORS):  # one launch per 24 tensors: one in all for 3DGS's model
+            part = table[i:i + _capi.SEED_MAX_TENSORS]
+            descs = (_capi.SeedTensor * len(part))()
+            for d, (s, t, mode, value) in zip(descs, part):
+                d.src, d.dst, d.mode, d.value = _capi.ptr(s), t.data_ptr(), mode, value
+                d.k = max(math.prod(t.shape[1:]), 1)
+            rc = lib.dgr_seed_apply(st, W, H, stride, P, P_new, plan.data_ptr(), len(part), descs, _capi.ptr(color_obs),
+                                    depth_obs.data_ptr(), viewmatrix.data_ptr(), fx, fy, cx, cy, pix)
+            if rc:
+                raise RuntimeError(_capi.last_error())
+    for name, t in params.items():
+        out[name].requires_grad_(t.requires_grad)
+    if optimizer is not None:
+        optimizer.replace_params({params[name]: out[name] for name in params},
+                                 {params[name]: moments[name] for name in moments})
+    return out, grown.get("xyz_gradient_accum"), grown.get("denom"), grown.get("max_radii2D"), counts
 
 
 class SparseAdam:

@@ -14,9 +14,12 @@ instead (slam.render_batch_fused: one forward and one backward call for all keyf
 --variant full runs the same loop through the -full variant (uncertainty output; it has no track_off, so the pose gradients are
 formed and left unused).  --ssim LAMBDA optimises the standard 3DGS mapping loss instead of plain L1: (1 - LAMBDA) L1 + LAMBDA (1 - SSIM)
 on the colour images plus the depth L1 (slam.l1_ssim_loss: at most three launches forward, two backward, capturable).
+--seed starts from an EMPTY map instead of the degraded copy: keyframe 0's observed colour and depth are unprojected into
+Gaussians (optim.seed_from_frame: three launches and one host read for every leaf, moment and accumulator), and each further
+keyframe is rendered before it joins the window and seeded where its silhouette (opacity_map) shows the map does not explain it.
 
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
-                             [--keyframes 4] [--ssim LAMBDA]
+                             [--keyframes 4] [--ssim LAMBDA] [--seed]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -79,16 +82,49 @@ class MapModel:
                 {"params": [self._rotation], "lr": 1e-3}]
 
 
+class SeededMapModel(MapModel):
+    """A MapModel that starts empty and grows by seed_from_frame.  3DGS's own leaves: the SH coefficients are split into the
+    degree-0 ones (f_dc, which a seed takes from the observed colour) and the rest."""
+
+    def __init__(self, dev):
+        empty = lambda *shape: torch.zeros(shape, device=dev).requires_grad_()  # noqa: E731
+        self._xyz, self._f_dc, self._f_rest = empty(0, 3), empty(0, 1, 3), empty(0, 15, 3)
+        self._opacity, self._scaling, self._rotation = empty(0, 1), empty(0, 3), empty(0, 4)
+        self.active_sh_degree = 3
+        self.xyz_gradient_accum = torch.zeros((0, 1), device=dev)
+        self.denom = torch.zeros((0, 1), device=dev)
+        self.max_radii2D = torch.zeros(0, device=dev)
+
+    get_features = property(lambda self: torch.cat([self._f_dc, self._f_rest], dim=1))
+
+    def leaves(self):
+        return {"xyz": self._xyz, "f_dc": self._f_dc, "f_rest": self._f_rest, "opacity": self._opacity, "scaling": self._scaling,
+                "rotation": self._rotation}
+
+    def replace(self, leaves, xyz_gradient_accum, denom, max_radii2D):
+        self._xyz, self._f_dc, self._f_rest = leaves["xyz"], leaves["f_dc"], leaves["f_rest"]
+        self._opacity, self._scaling, self._rotation = leaves["opacity"], leaves["scaling"], leaves["rotation"]
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = xyz_gradient_accum, denom, max_radii2D
+
+    def groups(self):
+        return [{"params": [self._xyz], "lr": 1.6e-4}, {"params": [self._f_dc], "lr": 2.5e-3},
+                {"params": [self._f_rest], "lr": 2.5e-3 / 20}, {"params": [self._opacity], "lr": 5e-2},
+                {"params": [self._scaling], "lr": 5e-3}, {"params": [self._rotation], "lr": 1e-3}]
+
+
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
-                 absgrad=False, densify_every=0, ssim_lambda=0.0):
+                 absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
     densify_every=N: every N iterations the statistics are consumed by densify_and_prune (not with graph=True: the step
     changes the number of Gaussians).
-    ssim_lambda > 0: the loss is slam.l1_ssim_loss with that lambda_dssim instead of slam.l1_loss (0.0: the L1 path, unchanged)."""
+    ssim_lambda > 0: the loss is slam.l1_ssim_loss with that lambda_dssim instead of slam.l1_loss (0.0: the L1 path, unchanged).
+    seed=True: the map starts empty and is seeded from the keyframes (seed_from_frame), which join the window one by one, every
+    iters // keyframes iterations (light variant, not with graph=True or fused=True: the step changes the number of Gaussians
+    and the window grows)."""
     from dgr_amd import light, slam
-    from dgr_amd.optim import SparseAdam, add_densification_stats, densify_and_prune
+    from dgr_amd.optim import SparseAdam, add_densification_stats, densify_and_prune, seed_from_frame
     from dgr_amd.synth import make_scene
 
     scenes = [make_scene(P, W, H, 3, view_index=k) for k in range(keyframes)]
@@ -101,6 +137,9 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     with torch.no_grad():
         obs = [slam.render(None, truth, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt, **kw)
                for c in cams]
+    if seed:  # the synthetic sensor: the truth's expected depth where the truth covers the pixel, a hole (0) elsewhere
+        sensor_depth = [torch.where(o["opacity_map"] > 0.9, o["depth"] / o["opacity_map"], torch.zeros_like(o["depth"])).detach()
+                        for o in obs]
     obs = [(o["render"].detach(), o["depth"].detach()) for o in obs]
     # the mapping renders: with absgrad their dicts carry `viewspace_points_abs`, which the statistics read instead
     mkw = dict(kw, absgrad=True) if absgrad else kw
@@ -109,10 +148,11 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     if graph:
         views_in_flight = 1  # (branches of one graph do not overlap on this ROCm, and the leaves' gradient accumulation
                              #  belongs to the stream they were created on: keep the recorded iteration on one stream)
-    pc = MapModel(s, dev, degrade=7)
+    pc = SeededMapModel(dev) if seed else MapModel(s, dev, degrade=7)
     opt = SparseAdam(pc.groups(), eps=1e-15, capturable=graph)
-    seen = torch.zeros(P, dtype=torch.int32, device=dev)
+    seen = torch.zeros(pc.get_xyz.shape[0], dtype=torch.int32, device=dev)
     outs = [None] * keyframes
+    n_live = 0 if seed else keyframes  # the window: keyframes 0 .. n_live - 1
 
     def photometric(color, depth, color_obs, depth_obs, w_color, w_depth):
         if ssim_lambda > 0.0:  # (1 - lambda) L1 + lambda (1 - SSIM) on the colour, L1 on the depth
@@ -150,16 +190,16 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             return iteration_fused()
         opt.zero_grad(set_to_none=True)
         if views_in_flight > 1:
-            losses = slam.render_batch(cams, pc, None, bg, loss_fn, views_in_flight=views_in_flight, **mkw)
+            losses = slam.render_batch(cams[:n_live], pc, None, bg, loss_fn, views_in_flight=views_in_flight, **mkw)
         else:  # one keyframe after the other on the caller's stream
             losses = []
-            for k, c in enumerate(cams):
+            for k, c in enumerate(cams[:n_live]):
                 loss = loss_fn(slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"],
                                            gt_depth=gt, **mkw), k)
                 loss.backward()
                 losses.append(loss.detach())
         seen.zero_()
-        for out in outs:
+        for out in outs[:n_live]:
             add_densification_stats(out[points].grad, out["radii"], pc.xyz_gradient_accum, pc.denom,
                                     pc.max_radii2D)
             torch.maximum(seen, out["radii"], out=seen)
@@ -183,6 +223,30 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             log(f"densify: P {before} -> {counts.rows} ({counts.survivors} kept, {counts.clones} cloned, "
                 f"{counts.split} split into {counts.children})")
 
+    def seed_keyframe(k):
+        """Keyframe k joins the window: what the map does not explain of it (all of it while the map is empty) becomes Gaussians."""
+        nonlocal seen, n_live
+        c, before = cams[k], pc.get_xyz.shape[0]
+        silhouette = None
+        if before:
+            with torch.no_grad():
+                silhouette = slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt,
+                                         **kw)["opacity_map"]
+        leaves, accum, denom, max_radii2D, counts = seed_from_frame(
+            pc.leaves(), opt, obs[k][0], sensor_depth[k], c["viewmatrix"], W / (2.0 * s.tanfovx), H / (2.0 * s.tanfovy),
+            (W - 1) / 2.0, (H - 1) / 2.0, opacity_map=silhouette, silhouette_threshold=0.5, init_opacity=0.5,
+            xyz_gradient_accum=pc.xyz_gradient_accum, denom=pc.denom, max_radii2D=pc.max_radii2D)
+        pc.replace(leaves, accum, denom, max_radii2D)
+        seen = torch.zeros(counts.rows, dtype=torch.int32, device=dev)
+        n_live = k + 1
+        if log:
+            log(f"seed: keyframe {k}: P {before} -> {counts.rows} ({counts.new} new from {counts.valid} valid pixels"
+                f"{f', {counts.unseen} of them unseen' if before else ''})")
+
+    if seed:
+        seed_keyframe(0)
+    join_every = max(iters // keyframes, 1)
+
     run = iteration
     if graph:  # (the three eager iterations run inside CapturedStep, on the stream the graph is recorded on)
         from dgr_amd.multiview import CapturedStep
@@ -199,6 +263,8 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(iters - 3):
+        if seed and n_live < keyframes and (i + 3) % join_every == 0:
+            seed_keyframe(n_live)
         loss = run()
         if densify_every and (i + 4) % densify_every == 0:
             densify()
@@ -229,6 +295,10 @@ def main():
     ap.add_argument("--ssim", type=float, default=0.0, metavar="LAMBDA",
                     help="the 3DGS mapping loss (1 - LAMBDA) L1 + LAMBDA (1 - SSIM) on the colour images (slam.l1_ssim_loss; 3DGS "
                          "uses 0.2) instead of plain L1; 0 (default) keeps the L1 loss")
+    ap.add_argument("--seed", action="store_true",
+                    help="start from an empty map: seed Gaussians from keyframe 0's colour and depth, then from each further "
+                         "keyframe's unexplained pixels before it joins the window (seed_from_frame); light variant, not together "
+                         "with --graph or --fused")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -237,6 +307,9 @@ def main():
         ap.error("--ssim LAMBDA lies in [0, 1]")
     if args.densify_every < 0 or (args.densify_every and args.graph):
         ap.error("--densify-every changes the number of Gaussians: it cannot run inside a recorded hipGraph (drop --graph)")
+    if args.seed and (args.graph or args.fused or args.variant != "light"):
+        ap.error("--seed changes the number of Gaussians and grows the window: it cannot run inside a recorded hipGraph (drop "
+                 "--graph), and it maps through the per-keyframe light path (drop --fused / --variant full)")
     import torch as _torch
     _torch.autograd.set_multithreading_enabled(False)  # one device, one thread: no engine-thread hand-off per backward
     if args.graph:
@@ -244,14 +317,15 @@ def main():
     dev = torch.device("cuda:0")
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
                                     args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
-                                    variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every, ssim_lambda=args.ssim)
+                                    variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every, ssim_lambda=args.ssim,
+                                    seed=args.seed)
     n = float(pc.denom.sum())
     print(("full variant: " if args.variant == "full" else "") + ("absgrad: " if args.absgrad else "") +
           (f"L1 + D-SSIM (lambda {args.ssim:g}): " if args.ssim > 0 else "") +
           f"loss {l0:.4e} -> {l1:.4e}; {dt * 1e3:.3f} ms per mapping iteration over {args.keyframes} keyframes"
           f" ({dt / args.keyframes * 1e3:.3f} ms per keyframe); {int((pc.denom > 0).sum())} Gaussians seen,"
           f" {n:.0f} (Gaussian, view) statistics accumulated" +
-          (f"; P {args.gaussians} -> {pc.get_xyz.shape[0]}" if args.densify_every else ""))
+          (f"; P {0 if args.seed else args.gaussians} -> {pc.get_xyz.shape[0]}" if args.densify_every or args.seed else ""))
 
 
 if __name__ == "__main__":

@@ -296,6 +296,71 @@ int dgr_densify_apply(void* stream, long rows, long rows_out, const void* plan, 
                       const float* scaling_raw, const float* rotation_raw, const float* noise /* or NULL */,
                       unsigned long long seed);
 
+/* Fused map expansion: new Gaussians from an RGB-D keyframe, appended to every per-Gaussian tensor of the model in three
+ * launches (csrc/seed.hip) -- what an RGB-D SLAM system (CG-SLAM, SplaTAM, MonoGS) does when a keyframe arrives: unproject the
+ * pixels the current map does not explain.  The sibling of densify-and-prune above: decide, scan, one host read, one apply.
+ * Images are float32 on the device: color_obs [3, H, W], depth_obs [H, W], and the optional opacity_map [H, W] (the forward's
+ * silhouette) and depth [H, W] (the rendered depth).  viewmatrix: 16 floats on the device holding W2C^T, what the rasterizer
+ * takes and dgr_pose_forward writes; the pose is taken as rigid.  fx, fy, cx, cy: pixels, in the convention in which a point on
+ * the optical axis lands on pixel (cx, cy) under ndc2Pix: pixel (x, y) at depth d is the camera-space point
+ * p = ((x - cx) / fx * d, (y - cy) / fy * d, d).
+ * Candidates: the pixels with x % stride == 0 && y % stride == 0.  Every decision is an fp32 comparison on the raw values
+ * against thresholds the caller forms (in float64, rounded once); a NaN compares false:
+ *   valid   = depth_obs > depth_min && depth_obs < depth_max
+ *   unseen  = opacity_map given && opacity_map < silhouette_threshold
+ *   infront = depth given && depth > depth_obs && (depth - depth_obs) > depth_error_min     (one rounded fp32 subtraction)
+ *   select  = valid && (unseen || infront);   select = valid when neither image is given (the first frame)
+ * depth_error_min_device (one float on the device, or NULL) overrides depth_error_min when non-NULL, so that a caller's
+ * k * median(error) needs no host read.
+ * The result is the old `rows` rows unchanged, followed by one new row per selected pixel in row-major pixel order (y, then x);
+ * no atomic decides a position, so the result is the same bits on every run.
+ *
+ * dgr_seed_plan decides (one flag byte per candidate) into `plan`, an opaque 16-byte aligned device buffer of
+ * dgr_seed_plan_bytes(width, height, stride) bytes (0 for a shape it refuses: a non-positive dimension or stride, 2^30
+ * candidates or more), and writes counts8_device[0..7] (device memory) = {rows after the step, new rows, valid candidates,
+ * valid candidates that are unseen, valid candidates that are in front, 0, 0, 0}.  The caller reads counts[0], allocates, and
+ * calls dgr_seed_apply with rows_out = counts[0] and a table of 1 .. DGR_SEED_MAX_TENSORS tensors {src [rows, k], dst
+ * [rows_out, k], mode, value}: ONE launch copies the old rows of them all and writes their new rows (call it again with the same
+ * plan for more tensors).  src may be NULL only when rows == 0.  Nothing is written past rows_out.  What `mode` puts into a new
+ * row:
+ *   XYZ (k = 3, at most one per table): p taken to the world, world_i = sum_j view[i][j] (p_j - view[3][j]), view[i][j] =
+ *     viewmatrix[4 i + j], in fp32 (fused multiply-adds allowed);
+ *   LOG_SCALE (k = 3 or 1): every component logf(d * pix), d = depth_obs, one rounded fp32 multiply and the full-precision logf;
+ *     the caller forms pix = scale_factor * stride * 0.5 * (1 / fx + 1 / fy): the Gaussian is as large as the pixel's footprint at
+ *     its depth;
+ *   RGB_DC (k = 3; reads color_obs): the degree-0 SH coefficients of the observed colour, (rgb - 0.5f) * inv_C0 with one rounded
+ *     subtraction, one rounded multiply and inv_C0 = (float)(1 / 0.28209479177387814);
+ *   QUAT_IDENTITY (k = 4): (1, 0, 0, 0);
+ *   CONST (any k): `value` in every component -- logit(init_opacity) for opacity_raw, 0 for the higher SH coefficients, the Adam
+ *     moments and xyz_gradient_accum / denom / max_radii2D.  (Unlike densify-and-prune, which zeroes the accumulators, their old
+ *     rows are copied: a keyframe arriving must not wipe the statistics of the rows that stay.)
+ * Argument errors return DGR_ERR_BAD_ARGUMENT with a message before any device call: a NULL or misaligned plan, NULL depth_obs
+ * or viewmatrix, non-positive width, height or stride, fx or fy not finite and positive, rows_out outside rows .. rows + the
+ * number of candidates (what can be checked of rows_out == rows + the plan's count without reading the device), n outside
+ * 1 .. DGR_SEED_MAX_TENSORS, k < 1, an unknown mode, two XYZ descriptors, a wrong k for a mode, RGB_DC without color_obs.  Not
+ * capturable as a whole: the caller reads counts between the two calls. */
+#define DGR_SEED_MAX_TENSORS 24
+#define DGR_SEED_XYZ 0
+#define DGR_SEED_LOG_SCALE 1
+#define DGR_SEED_RGB_DC 2
+#define DGR_SEED_QUAT_IDENTITY 3
+#define DGR_SEED_CONST 4
+typedef struct {
+    const float* src;
+    float* dst;
+    int k;
+    int mode;
+    float value;
+} dgr_seed_tensor;
+size_t dgr_seed_plan_bytes(int width, int height, int stride);
+int dgr_seed_plan(void* stream, int width, int height, int stride, const float* depth_obs, const float* opacity_map /* or NULL */,
+                  const float* depth /* or NULL */, float depth_min, float depth_max, float silhouette_threshold,
+                  float depth_error_min, const float* depth_error_min_device /* or NULL */, long rows, void* plan,
+                  int* counts8_device);
+int dgr_seed_apply(void* stream, int width, int height, int stride, long rows, long rows_out, const void* plan, int n,
+                   const dgr_seed_tensor* tensors, const float* color_obs /* or NULL */, const float* depth_obs,
+                   const float* viewmatrix, float fx, float fy, float cx, float cy, float pix);
+
 /* ---- the small pieces of a tracking iteration around the rasterizer, one launch each (the reference's
  * caller, CG-SLAM, does these with a dozen elementwise torch kernels each -- a 640x480 tracking step is launch-bound) ----
  * dgr_pose_forward: (quat = (r, x, y, z), not necessarily unit; trans) -> the three camera tensors the rasterizer takes,
