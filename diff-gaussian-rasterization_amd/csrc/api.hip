@@ -1282,4 +1282,65 @@ int dgr_ssim_loss_backward(void* stream, int n_images, int channels, int height,
     return DGR_OK;
 }
 
+// the shared argument checks of dgr_masked_loss_forward / _backward: the message, or NULL
+static const char* masked_loss_bad_argument(int n_views, int channels, int height, int width, const float* color,
+                                            const float* color_obs, const float* depth, const float* depth_obs,
+                                            const dgr_masked_loss_params* p, const void* scratch) {
+    if (n_views <= 0 || channels <= 0 || height <= 0 || width <= 0) return "n_views, channels, height and width must be positive";
+    if (!dgr::masked_loss_shape_ok(n_views, height, width)) return "n_views must be at most 65535 and height * width at most 2^30";
+    if (!color || !color_obs) return "color or color_obs is NULL";
+    if (!depth || !depth_obs) return "depth or depth_obs is NULL";
+    if (!p) return "params is NULL";
+    if (std::isnan(p->depth_lo) || std::isnan(p->depth_hi)) return "depth_lo or depth_hi is NaN";
+    if (std::isnan(p->silhouette_threshold)) return "silhouette_threshold is NaN";
+    if (std::isnan(p->outlier_factor)) return "outlier_factor is NaN";
+    if (p->reject_outliers && p->outlier_factor < 0.f) return "outlier_factor is negative";
+    if (p->reduction != DGR_MASKED_LOSS_SUM && p->reduction != DGR_MASKED_LOSS_MEAN) return "unknown reduction";
+    if (!scratch || !dgr::aligned16(scratch)) return "scratch is NULL or not 16-byte aligned";
+    return nullptr;
+}
+static dgr::MaskedLossArgs masked_loss_args(int n_views, int channels, int height, int width, const float* color,
+                                            const float* color_obs, const float* depth, const float* depth_obs,
+                                            const float* opacity_map, const unsigned char* mask, const dgr_masked_loss_params& p) {
+    dgr::MaskedLossArgs a{};
+    a.V = n_views, a.C = channels, a.H = height, a.W = width;
+    a.color = color, a.color_obs = color_obs, a.depth = depth, a.depth_obs = depth_obs, a.opacity = opacity_map, a.mask = mask;
+    a.lo = p.depth_lo, a.hi = p.depth_hi, a.silhouette = p.silhouette_threshold, a.factor = p.outlier_factor;
+    a.w_color = p.w_color, a.w_depth = p.w_depth;
+    a.reject = p.reject_outliers != 0, a.mask_color = p.mask_color != 0, a.mean = p.reduction == DGR_MASKED_LOSS_MEAN;
+    return a;
+}
+size_t dgr_masked_loss_scratch_bytes(int n_views, int height, int width) {
+    return (size_t)dgr::masked_loss_layout(n_views, height, width).total;
+}
+int dgr_masked_loss_forward(void* stream, int n_views, int channels, int height, int width, const float* color,
+                            const float* color_obs, const float* depth, const float* depth_obs, const float* opacity_map,
+                            const unsigned char* mask, const dgr_masked_loss_params* params, void* scratch, float* loss) {
+    const char* bad = masked_loss_bad_argument(n_views, channels, height, width, color, color_obs, depth, depth_obs, params, scratch);
+    if (!bad && !loss) bad = "loss is NULL";
+    if (bad) {
+        set_last_error(std::string("dgr_masked_loss_forward: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_masked_loss_forward(masked_loss_args(n_views, channels, height, width, color, color_obs, depth, depth_obs,
+                                                             opacity_map, mask, *params),
+                                            scratch, loss, (hipStream_t)stream));
+    return DGR_OK;
+}
+int dgr_masked_loss_backward(void* stream, int n_views, int channels, int height, int width, const float* color,
+                             const float* color_obs, const float* depth, const float* depth_obs, const float* opacity_map,
+                             const unsigned char* mask, const dgr_masked_loss_params* params, const void* scratch,
+                             const float* upstream, float* dL_dcolor, float* dL_ddepth) {
+    const char* bad = masked_loss_bad_argument(n_views, channels, height, width, color, color_obs, depth, depth_obs, params, scratch);
+    if (!bad && !dL_dcolor && !dL_ddepth) bad = "dL_dcolor and dL_ddepth are both NULL";
+    if (bad) {
+        set_last_error(std::string("dgr_masked_loss_backward: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    HIP_TRY(dgr::launch_masked_loss_backward(masked_loss_args(n_views, channels, height, width, color, color_obs, depth, depth_obs,
+                                                              opacity_map, mask, *params),
+                                             scratch, upstream, dL_dcolor, dL_ddepth, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

@@ -285,6 +285,26 @@ hipError_t launch_ssim_loss_forward(int V, int C, int H, int W, const float* img
 hipError_t launch_ssim_loss_backward(int V, int C, int H, int W, const float* img, const float* ref, long n_d, const float* d,
                                      const float* d_obs, float w_l1, float w_ssim, float w_depth, const float* scratch,
                                      const float* upstream, float* dimg, float* ddepth, hipStream_t stream);
+// masked_loss.hip: the masked L1 loss with the per-view median outlier test (include/dgr_hip.h: dgr_masked_loss_*).  The scratch,
+// in bytes from its start: 16 header floats ([0] w_d / N_d, [1] w_c / N_c for the backward), then median / base / kept per view,
+// the views' sums, 3 x V histograms of 2048 bins, the workgroups' slots, the kept mask (a byte per pixel)
+struct MaskedLossArgs {
+    int V, C, H, W;
+    const float *color, *color_obs, *depth, *depth_obs, *opacity;  // opacity: NULL = no silhouette test
+    const unsigned char* mask;                                      // NULL = no user mask
+    float lo, hi, silhouette, factor, w_color, w_depth;
+    bool reject, mask_color, mean;
+};
+struct MaskedLossLayout {
+    long median, base, kept, view_sums, hist, slots, mask, total;  // byte offsets; total = 0 for a refused shape
+    long chunk;                                                    // pixels of a view per workgroup
+    int blocks;                                                    // workgroups per view
+};
+bool masked_loss_shape_ok(int V, int H, int W);
+MaskedLossLayout masked_loss_layout(int V, int H, int W);
+hipError_t launch_masked_loss_forward(const MaskedLossArgs& a, void* scratch, float* loss, hipStream_t stream);
+hipError_t launch_masked_loss_backward(const MaskedLossArgs& a, const void* scratch, const float* upstream, float* dcolor,
+                                       float* ddepth, hipStream_t stream);
 hipError_t launch_densification_stats(int rows, const float* dmeans2D, const int* radii, float* grad_accum, float* denom,
                                       float* max_radii2D, hipStream_t stream);
 hipError_t launch_sparse_adam(size_t rows, int k, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -67,6 +67,15 @@ class SeedTensor(C.Structure):  # dgr_seed_tensor: one per-Gaussian tensor of a 
 
 assert C.sizeof(SeedTensor) == 32  # two pointers, two ints, a float, padded to the pointers' alignment
 
+
+class MaskedLossParams(C.Structure):  # dgr_masked_loss_params
+    _fields_ = [("depth_lo", _f), ("depth_hi", _f), ("silhouette_threshold", _f), ("outlier_factor", _f),
+                ("reject_outliers", _i), ("mask_color", _i), ("reduction", _i), ("w_color", _f), ("w_depth", _f)]
+
+
+assert C.sizeof(MaskedLossParams) == 36  # nine four-byte fields: the C layout
+
+MASKED_LOSS_SUM, MASKED_LOSS_MEAN = 0, 1  # DGR_MASKED_LOSS_*
 MAX_BATCH_VIEWS = 8  # DGR_MAX_BATCH_VIEWS
 DENSIFY_MAX_TENSORS = 24  # DGR_DENSIFY_MAX_TENSORS
 DENSIFY_COPY, DENSIFY_ZERO_NEW, DENSIFY_ZERO, DENSIFY_XYZ, DENSIFY_LOG_SCALE = range(5)  # DGR_DENSIFY_*
@@ -99,6 +108,10 @@ _SIGS = {
     "dgr_ssim_scratch_floats": (C.c_long, [_i, _i, _i, _i]),
     "dgr_ssim_loss_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _f, _vp, _i, _vp]),
     "dgr_ssim_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_long, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "dgr_masked_loss_scratch_bytes": (_sz, [_i, _i, _i]),
+    "dgr_masked_loss_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaskedLossParams), _vp, _vp]),
+    "dgr_masked_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaskedLossParams), _vp, _vp,
+                                      _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

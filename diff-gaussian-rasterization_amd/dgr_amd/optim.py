@@ -189,7 +189,8 @@ def seed_from_frame(params, optimizer, color_obs, depth_obs, viewmatrix, fx, fy,
     `color_obs` [3, H, W], `depth_obs` [H, W], `opacity_map` / `depth` [H, W] or [1, H, W]: float32 on the GPU.  `viewmatrix`:
     16 floats on the GPU holding W2C^T (what the rasterizer takes, what `slam.pose_to_camera` returns): the pose never visits
     the host.  `fx, fy, cx, cy`: pixels; a point on the optical axis lands on pixel (cx, cy).  `depth_error_min`: a float, or a
-    one-element float32 GPU tensor (a caller's k * median(error), no host read).
+    one-element float32 GPU tensor (a caller's k * median(error), no host read: `stats.median * 50` of
+    `slam.masked_l1_loss(..., return_stats=True)` on this frame is one).
     `params`: dict name -> leaf [P, ...] (P = 0: empty leaves); `roles` as densify_and_prune's plus "f_dc" (the degree-0 SH
     coefficients, [P, 3] or [P, 1, 3]; may be absent from `params`).  A new row is: xyz the pixel unprojected to the world;
     scaling log(depth * scale_factor * stride * (1 / fx + 1 / fy) / 2) in all three components; rotation (1, 0, 0, 0); opacity

@@ -15,6 +15,7 @@ dependence inside the kernels: L/cuda_rasterizer/backward.cu:633-651, 683-751).
 """
 import contextlib as _contextlib
 from collections.abc import Mapping as _Mapping
+from typing import NamedTuple as _NamedTuple
 
 import torch
 
@@ -325,6 +326,131 @@ def l1_ssim_loss(color, depth, color_obs, depth_obs, w_color=1.0, w_depth=0.5, l
     lam = float(lambda_dssim)
     return _SsimLoss.apply(color, depth, color_obs, depth_obs, shape, float(w_color) * (1.0 - lam), float(w_color) * lam,
                            float(w_depth) if depth is not None else 0.0, _wants_grad(color, depth), False)
+
+
+class MaskedLossStats(_NamedTuple):
+    """What `masked_l1_loss(..., return_stats=True)` leaves on the device (views into the call's scratch, nothing read on the host):
+    `mask` bool [V,H,W] -- the kept set K; `median` float32 [V] -- the lower median of |depth - depth_obs| over each view's base
+    set (0 for an empty one, NaN when rejection is off); `base`, `kept` int32 [V] -- |B_v| and |K_v|.  `median[v:v + 1] * 50` is a
+    valid device-tensor `depth_error_min` for `optim.seed_from_frame`."""
+    mask: torch.Tensor
+    median: torch.Tensor
+    base: torch.Tensor
+    kept: torch.Tensor
+
+
+def _round16(n):
+    return (n + 15) & ~15
+
+
+class _MaskedL1Loss(torch.autograd.Function):
+    """C ABI: dgr_masked_loss_forward / _backward (csrc/masked_loss.hip).  Returns (loss, scratch): the scratch (uint8, the layout
+    include/dgr_hip.h documents) holds the statistics and the mask bytes the backward reads."""
+
+    @staticmethod
+    def forward(ctx, color, depth, color_obs, depth_obs, opacity_map, mask, shape, params):
+        from . import _capi
+        lib = _capi.load()
+        color, depth, color_obs, depth_obs = (x.contiguous() for x in (color, depth, color_obs, depth_obs))
+        if opacity_map is not None:
+            opacity_map = opacity_map.detach().contiguous()
+        if mask is not None:
+            mask = mask.contiguous()
+        V, C, H, W = shape
+        scratch = torch.empty((lib.dgr_masked_loss_scratch_bytes(V, H, W),), dtype=torch.uint8, device=color.device)
+        loss = scratch[8:12].view(torch.float32)  # (a free word of the stats header)
+        with _capi.on_device(color.device):
+            if lib.dgr_masked_loss_forward(_capi.stream_handle(color.device.index), V, C, H, W, color.data_ptr(),
+                                           color_obs.data_ptr(), depth.data_ptr(), depth_obs.data_ptr(), _capi.ptr(opacity_map),
+                                           _capi.ptr(mask), params, scratch.data_ptr(), loss.data_ptr()):
+                raise RuntimeError(_capi.last_error())
+        ctx.save_for_backward(color, depth, color_obs, depth_obs, opacity_map, mask, scratch)
+        ctx.call = (shape, params)
+        ctx.mark_non_differentiable(scratch)
+        return loss[0], scratch
+
+    @staticmethod
+    def backward(ctx, upstream, _dscratch):
+        from . import _capi
+        lib = _capi.load()
+        color, depth, color_obs, depth_obs, opacity_map, mask, scratch = ctx.saved_tensors
+        (V, C, H, W), params = ctx.call
+        dcolor = torch.empty_like(color) if ctx.needs_input_grad[0] else None
+        ddepth = torch.empty_like(depth) if ctx.needs_input_grad[1] else None
+        if dcolor is None and ddepth is None:
+            return (None,) * 8
+        upstream = upstream.contiguous()
+        with _capi.on_device(color.device):
+            if lib.dgr_masked_loss_backward(_capi.stream_handle(color.device.index), V, C, H, W, color.data_ptr(),
+                                            color_obs.data_ptr(), depth.data_ptr(), depth_obs.data_ptr(), _capi.ptr(opacity_map),
+                                            _capi.ptr(mask), params, scratch.data_ptr(), upstream.data_ptr(),
+                                            _capi.ptr(dcolor), _capi.ptr(ddepth)):
+                raise RuntimeError(_capi.last_error())
+        return dcolor, ddepth, None, None, None, None, None, None
+
+
+def masked_l1_loss(color, depth, color_obs, depth_obs, opacity_map=None, mask=None, *, silhouette_threshold=0.99,
+                   depth_range=(0.0, float("inf")), outlier_factor=10.0, mask_color=True, w_color=1.0, w_depth=0.5,
+                   reduction="sum", return_stats=False):
+    """The masked L1 loss of the RGB-D SLAM systems (SplaTAM's `get_loss`, CG-SLAM's tracking), fused: at most six launches
+    forward, one backward, no host read, the same bits on every run, capturable into a hipGraph.  Per pixel of every view of the
+    stack, in single fp32 operations:
+        e = |depth - depth_obs|
+        B = lo < depth_obs < hi  and  e finite  [and opacity_map > silhouette_threshold]  [and mask != 0]
+        K = B and e <= outlier_factor * median_v         median_v: the exact lower median of e over B of view v (torch.median's,
+                                                          by a radix select on the device; 0 for an empty B)
+        loss = w_depth * sum_K e / N_d + w_color * sum |color - color_obs| / N_c
+    The colour sum runs over the channels and over K, or over every pixel with `mask_color=False` (the mapping form).
+    `reduction="sum"` (SplaTAM's): N_d = N_c = 1; `"mean"`: N_d = |K| over the whole stack, N_c = C |K| (or C H W V unmasked),
+    the counts read on the device; a zero count gives a zero term.  `outlier_factor=None` turns the rejection off (K = B; no
+    median is computed).  The comparison is `<=`: a perfectly fitted frame (median 0) keeps its pixels.  NaN in any image drops
+    the pixel.  Gradients go to `color` and `depth` (sign(.) on their set, zero outside); the mask is piecewise constant, so
+    `opacity_map`, the observations and the median receive none.
+    `color`, `color_obs`: [V,C,H,W] or [C,H,W]; `depth`, `depth_obs`, `opacity_map`: [V,1,H,W], [1,H,W] or [H,W]; `mask`: uint8 or
+    bool of the depth's pixel shape.  float32 GPU tensors.
+    `return_stats=True`: returns (loss, MaskedLossStats(mask, median, base, kept)), device tensors; `stats.median * 50` (one view)
+    is a valid device-tensor `depth_error_min` for `optim.seed_from_frame`."""
+    what = "masked_l1_loss"
+    _check_pair("color", color, color_obs, what)
+    _check_pair("depth", depth, depth_obs, what)
+    V, C, H, W = _image_stack(color, what)
+    pixels = {(V, 1, H, W)} if color.dim() == 4 else {(1, H, W), (H, W)}
+    if tuple(depth.shape) not in pixels:
+        raise ValueError(f"{what}: depth {tuple(depth.shape)} does not match color {tuple(color.shape)} "
+                         "([V,1,H,W] beside [V,C,H,W]; [1,H,W] or [H,W] beside [C,H,W])")
+    if opacity_map is not None:
+        if not isinstance(opacity_map, torch.Tensor) or opacity_map.dtype != torch.float32:
+            raise ValueError(f"{what}: opacity_map must be a float32 tensor")
+        if tuple(opacity_map.shape) not in pixels:
+            raise ValueError(f"{what}: opacity_map {tuple(opacity_map.shape)} does not have the depth's shape {tuple(depth.shape)}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+            raise ValueError(f"{what}: mask must be a uint8 or bool tensor")
+        if tuple(mask.shape) not in pixels and tuple(mask.shape) != (V, H, W):
+            raise ValueError(f"{what}: mask {tuple(mask.shape)} does not have the depth's pixel shape {tuple(depth.shape)}")
+    if reduction not in ("sum", "mean"):
+        raise ValueError(f"{what}: reduction must be 'sum' or 'mean', not {reduction!r}")
+    lo, hi = (float(x) for x in depth_range)
+    factor = 0.0 if outlier_factor is None else float(outlier_factor)
+    if any(x != x for x in (lo, hi, float(silhouette_threshold), factor)) or factor < 0.0:
+        raise ValueError(f"{what}: depth_range, silhouette_threshold and outlier_factor must not be NaN, outlier_factor not negative")
+    _check_gpu(what, *(t for t in (color, color_obs, depth, depth_obs, opacity_map, mask) if t is not None))
+    from . import _capi
+    if _capi.load().dgr_masked_loss_scratch_bytes(V, H, W) == 0:
+        raise ValueError(f"{what}: cannot read a stack of shape {tuple(color.shape)} (more than 2^30 pixels per view)")
+    params = _capi.MaskedLossParams(lo, hi, float(silhouette_threshold), factor, int(outlier_factor is not None), int(bool(mask_color)),
+                                    _capi.MASKED_LOSS_MEAN if reduction == "mean" else _capi.MASKED_LOSS_SUM, float(w_color),
+                                    float(w_depth))
+    if mask is not None and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    loss, scratch = _MaskedL1Loss.apply(color, depth, color_obs, depth_obs, opacity_map, mask, (V, C, H, W), params)
+    if not return_stats:
+        return loss
+    pad, n = _round16(4 * V), V * H * W  # (the scratch layout of include/dgr_hip.h)
+    end = scratch.numel() - _round16(n)
+    return loss, MaskedLossStats(scratch[end:end + n].view(torch.bool).view(V, H, W),
+                                 scratch[64:64 + 4 * V].view(torch.float32), scratch[64 + pad:64 + pad + 4 * V].view(torch.int32),
+                                 scratch[64 + 2 * pad:64 + 2 * pad + 4 * V].view(torch.int32))
 
 
 def _get(obj, name, default=None):

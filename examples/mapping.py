@@ -17,9 +17,13 @@ on the colour images plus the depth L1 (slam.l1_ssim_loss: at most three launche
 --seed starts from an EMPTY map instead of the degraded copy: keyframe 0's observed colour and depth are unprojected into
 Gaussians (optim.seed_from_frame: three launches and one host read for every leaf, moment and accumulator), and each further
 keyframe is rendered before it joins the window and seeded where its silhouette (opacity_map) shows the map does not explain it.
+--masked gives the observed depth the holes of a real sensor (0 where the true map does not cover the pixel) and optimises the
+masked loss in its mapping form (slam.masked_l1_loss(mask_color=False): the depth term over the valid pixels whose error is at most
+10 x the keyframe's median error, the colour term over every pixel); with --seed a joining keyframe is also seeded where the
+rendered depth lies more than 50 x the median depth error behind the sensor's (`stats.median * 50`, a device tensor: no host read).
 
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
-                             [--keyframes 4] [--ssim LAMBDA] [--seed]
+                             [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -113,7 +117,7 @@ class SeededMapModel(MapModel):
 
 
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
-                 absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False):
+                 absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -122,7 +126,9 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     ssim_lambda > 0: the loss is slam.l1_ssim_loss with that lambda_dssim instead of slam.l1_loss (0.0: the L1 path, unchanged).
     seed=True: the map starts empty and is seeded from the keyframes (seed_from_frame), which join the window one by one, every
     iters // keyframes iterations (light variant, not with graph=True or fused=True: the step changes the number of Gaussians
-    and the window grows)."""
+    and the window grows).
+    masked=True: the observed depth has holes and the loss is slam.masked_l1_loss in its mapping form (not with ssim_lambda > 0);
+    with seed=True the seeding also takes `stats.median * 50` as its depth_error_min."""
     from dgr_amd import light, slam
     from dgr_amd.optim import SparseAdam, add_densification_stats, densify_and_prune, seed_from_frame
     from dgr_amd.synth import make_scene
@@ -140,7 +146,11 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     if seed:  # the synthetic sensor: the truth's expected depth where the truth covers the pixel, a hole (0) elsewhere
         sensor_depth = [torch.where(o["opacity_map"] > 0.9, o["depth"] / o["opacity_map"], torch.zeros_like(o["depth"])).detach()
                         for o in obs]
-    obs = [(o["render"].detach(), o["depth"].detach()) for o in obs]
+    if masked:  # the same holes in the depth the loss compares with (the rasterizer's depth is alpha-weighted: obs keeps that form)
+        obs = [(o["render"].detach(), torch.where(o["opacity_map"] > 0.9, o["depth"], torch.zeros_like(o["depth"])).detach())
+               for o in obs]
+    else:
+        obs = [(o["render"].detach(), o["depth"].detach()) for o in obs]
     # the mapping renders: with absgrad their dicts carry `viewspace_points_abs`, which the statistics read instead
     mkw = dict(kw, absgrad=True) if absgrad else kw
     points = "viewspace_points_abs" if absgrad else "viewspace_points"
@@ -155,6 +165,9 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     n_live = 0 if seed else keyframes  # the window: keyframes 0 .. n_live - 1
 
     def photometric(color, depth, color_obs, depth_obs, w_color, w_depth):
+        if masked:  # depth over the valid, non-outlier pixels; colour over every pixel; means over their own counts
+            return slam.masked_l1_loss(color, depth, color_obs, depth_obs, mask_color=False, w_color=w_color, w_depth=w_depth,
+                                       reduction="mean")
         if ssim_lambda > 0.0:  # (1 - lambda) L1 + lambda (1 - SSIM) on the colour, L1 on the depth
             return slam.l1_ssim_loss(color, depth, color_obs, depth_obs, w_color, w_depth, ssim_lambda)
         return slam.l1_loss(color, depth, color_obs, depth_obs, w_color, w_depth)  # one fused reduction
@@ -227,14 +240,19 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         """Keyframe k joins the window: what the map does not explain of it (all of it while the map is empty) becomes Gaussians."""
         nonlocal seen, n_live
         c, before = cams[k], pc.get_xyz.shape[0]
-        silhouette = None
+        silhouette, behind = None, {}
         if before:
             with torch.no_grad():
-                silhouette = slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt,
-                                         **kw)["opacity_map"]
+                r = slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt, **kw)
+                silhouette = r["opacity_map"]
+                if masked:  # also where the map lies far behind the sensor: 50 x the median depth error of the explained pixels
+                    expected = torch.where(silhouette > 0.5, r["depth"] / silhouette, torch.zeros_like(silhouette))
+                    _, stats = slam.masked_l1_loss(r["render"], expected, obs[k][0], sensor_depth[k], silhouette,
+                                                   silhouette_threshold=0.5, mask_color=False, return_stats=True)
+                    behind = dict(depth=expected, depth_error_min=stats.median * 50)
         leaves, accum, denom, max_radii2D, counts = seed_from_frame(
             pc.leaves(), opt, obs[k][0], sensor_depth[k], c["viewmatrix"], W / (2.0 * s.tanfovx), H / (2.0 * s.tanfovy),
-            (W - 1) / 2.0, (H - 1) / 2.0, opacity_map=silhouette, silhouette_threshold=0.5, init_opacity=0.5,
+            (W - 1) / 2.0, (H - 1) / 2.0, opacity_map=silhouette, silhouette_threshold=0.5, init_opacity=0.5, **behind,
             xyz_gradient_accum=pc.xyz_gradient_accum, denom=pc.denom, max_radii2D=pc.max_radii2D)
         pc.replace(leaves, accum, denom, max_radii2D)
         seen = torch.zeros(counts.rows, dtype=torch.int32, device=dev)
@@ -299,12 +317,17 @@ def main():
                     help="start from an empty map: seed Gaussians from keyframe 0's colour and depth, then from each further "
                          "keyframe's unexplained pixels before it joins the window (seed_from_frame); light variant, not together "
                          "with --graph or --fused")
+    ap.add_argument("--masked", action="store_true",
+                    help="observed depth with holes and the masked loss in its mapping form (slam.masked_l1_loss(mask_color=False)); "
+                         "with --seed, stats.median * 50 becomes the seeding's depth_error_min; not together with --ssim")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
     args = ap.parse_args()
     if not 0.0 <= args.ssim <= 1.0:
         ap.error("--ssim LAMBDA lies in [0, 1]")
+    if args.masked and args.ssim > 0:
+        ap.error("--masked replaces the photometric loss: drop --ssim")
     if args.densify_every < 0 or (args.densify_every and args.graph):
         ap.error("--densify-every changes the number of Gaussians: it cannot run inside a recorded hipGraph (drop --graph)")
     if args.seed and (args.graph or args.fused or args.variant != "light"):
@@ -318,10 +341,10 @@ def main():
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
                                     args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
                                     variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every, ssim_lambda=args.ssim,
-                                    seed=args.seed)
+                                    seed=args.seed, masked=args.masked)
     n = float(pc.denom.sum())
     print(("full variant: " if args.variant == "full" else "") + ("absgrad: " if args.absgrad else "") +
-          (f"L1 + D-SSIM (lambda {args.ssim:g}): " if args.ssim > 0 else "") +
+          (f"L1 + D-SSIM (lambda {args.ssim:g}): " if args.ssim > 0 else "") + ("masked L1: " if args.masked else "") +
           f"loss {l0:.4e} -> {l1:.4e}; {dt * 1e3:.3f} ms per mapping iteration over {args.keyframes} keyframes"
           f" ({dt / args.keyframes * 1e3:.3f} ms per keyframe); {int((pc.denom > 0).sum())} Gaussians seen,"
           f" {n:.0f} (Gaussian, view) statistics accumulated" +

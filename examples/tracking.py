@@ -11,7 +11,12 @@ With --complete-pose the pose gradient is the complete one (slam.render(complete
 depth term included) instead of the reference's.  --trace K prints the pose error every K iterations (the timing then includes
 those reads).
 
-  python examples/tracking.py [--graph] [--fused] [--complete-pose] [--trace K] [--iters 150]
+With --masked the observed frame gets what a real depth sensor adds: holes (depth_obs = 0 on a seeded random 20 % of the pixels)
+and gross outliers (2 % of the pixels, metres off).  The pose is then tracked twice from the same start, with the plain L1 loss and
+with the masked loss (slam.masked_l1_loss: valid sensor depth, silhouette above 0.99, depth error at most 10 x the frame's median
+error -- the median found on the device, so the iteration still records into a hipGraph), and both final pose errors are printed.
+
+  python examples/tracking.py [--graph] [--fused] [--masked] [--complete-pose] [--trace K] [--iters 150]
                               [--width 640 --height 480 --gaussians 100000]
 """
 import argparse
@@ -32,6 +37,8 @@ def main():
     ap.add_argument("--fused", action="store_true",
                     help="pose -> camera tensors, the L1 loss and the Adam step as single launches (slam.pose_to_camera, "
                          "slam.l1_loss, optim.SparseAdam)")
+    ap.add_argument("--masked", action="store_true",
+                    help="holes and outliers in the observed depth; track with the plain loss and with slam.masked_l1_loss")
     ap.add_argument("--iters", type=int, default=150)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
@@ -74,55 +81,75 @@ def main():
         obs = render(pose(q_true, t_true))
     obs_c, obs_d = obs["render"].detach(), obs["depth"].detach()
 
-    q = (q_true + torch.tensor([0.0, 0.004, -0.006, 0.003], device=dev)).requires_grad_()
-    t = (t_true + torch.tensor([0.012, -0.009, 0.015], device=dev)).requires_grad_()
-    groups = [{"params": [q], "lr": 5e-4}, {"params": [t], "lr": 1.5e-3}]
-    if args.fused:  # one launch per tensor, step count on the device when the iteration is recorded into a graph
-        from dgr_amd.optim import SparseAdam
-        opt = SparseAdam(groups, capturable=args.graph)
-    else:
-        opt = torch.optim.Adam(groups, capturable=args.graph)
+    if args.masked:
+        g = torch.Generator().manual_seed(11)
+        hole = (torch.rand(obs_d.shape, generator=g) < 0.20).to(dev)
+        gross = (torch.rand(obs_d.shape, generator=g) < 0.02).to(dev)
+        off = (1.0 + 2.0 * torch.rand(obs_d.shape, generator=g)).to(dev)
+        obs_d = torch.where(hole, torch.zeros_like(obs_d), torch.where(gross, obs_d + off, obs_d)).contiguous()
 
-    def iteration():
-        opt.zero_grad(set_to_none=True)
-        out = render(pose(q, t))
-        if args.fused:
-            loss = slam.l1_loss(out["render"], out["depth"], obs_c, obs_d, 1.0, 0.5)
+    def track(masked):
+        q = (q_true + torch.tensor([0.0, 0.004, -0.006, 0.003], device=dev)).requires_grad_()
+        t = (t_true + torch.tensor([0.012, -0.009, 0.015], device=dev)).requires_grad_()
+        groups = [{"params": [q], "lr": 5e-4}, {"params": [t], "lr": 1.5e-3}]
+        if args.fused:  # one launch per tensor, step count on the device when the iteration is recorded into a graph
+            from dgr_amd.optim import SparseAdam
+            opt = SparseAdam(groups, capturable=args.graph)
         else:
-            loss = (out["render"] - obs_c).abs().mean() + 0.5 * (out["depth"] - obs_d).abs().mean()
-        loss.backward()
-        if not args.graph:  # lazy status mode: every outstanding forward reports before the step (an overflowed one raises here)
-            light.check_async_errors()
-        opt.step()
-        return loss.detach()
+            opt = torch.optim.Adam(groups, capturable=args.graph)
 
-    def err():
-        with torch.no_grad():
-            return float((q / q.norm() - q_true).norm()), float((t - t_true).norm())
+        def iteration():
+            opt.zero_grad(set_to_none=True)
+            out = render(pose(q, t))
+            if masked:  # the means over the kept pixels, so that the step sizes compare with the plain loss's
+                loss = slam.masked_l1_loss(out["render"], out["depth"], obs_c, obs_d, out["opacity_map"], w_color=1.0, w_depth=0.5,
+                                           reduction="mean")
+            elif args.fused:
+                loss = slam.l1_loss(out["render"], out["depth"], obs_c, obs_d, 1.0, 0.5)
+            else:
+                loss = (out["render"] - obs_c).abs().mean() + 0.5 * (out["depth"] - obs_d).abs().mean()
+            loss.backward()
+            if not args.graph:  # lazy status mode: every outstanding forward reports before the step (an overflowed one raises here)
+                light.check_async_errors()
+            opt.step()
+            return loss.detach()
 
-    print(f"start : rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}")
-    if args.graph:
-        step = CapturedStep(iteration, warmup=3)  # (three eager iterations first)
-        run = step.replay
-    else:
-        for _ in range(3):  # the same three iterations, so that one-time costs (kernel loading, optimiser set-up) are not timed
-            iteration()
-        run = iteration
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for i in range(args.iters):
-        loss = run()
-        if args.trace and (i + 1) % args.trace == 0:
-            e = err()
-            print(f"  iteration {i + 1}: rotation error {e[0]:.2e}, translation error {e[1]:.2e}")
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    if args.graph:
-        step.check()
-    print(f"finish: rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}, loss {float(loss):.3e}")
-    print(f"{args.iters} iterations in {dt * 1e3:.1f} ms = {dt / args.iters * 1e3:.3f} ms per tracking iteration"
-          f" ({'hipGraph replay' if args.graph else 'eager'}{', fused pose and loss' if args.fused else ''}"
-          f"{', complete pose gradient' if args.complete_pose else ''})")
+        def err():
+            with torch.no_grad():
+                return float((q / q.norm() - q_true).norm()), float((t - t_true).norm())
+
+        if args.masked:
+            print("masked loss (slam.masked_l1_loss):" if masked else "plain L1 loss on the same frame:")
+        print(f"start : rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}")
+        if args.graph:
+            step = CapturedStep(iteration, warmup=3)  # (three eager iterations first)
+            run = step.replay
+        else:
+            for _ in range(3):  # the same three iterations, so that one-time costs (kernel loading, optimiser set-up) are not timed
+                iteration()
+            run = iteration
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(args.iters):
+            loss = run()
+            if args.trace and (i + 1) % args.trace == 0:
+                e = err()
+                print(f"  iteration {i + 1}: rotation error {e[0]:.2e}, translation error {e[1]:.2e}")
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if args.graph:
+            step.check()
+        print(f"finish: rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}, loss {float(loss):.3e}")
+        print(f"{args.iters} iterations in {dt * 1e3:.1f} ms = {dt / args.iters * 1e3:.3f} ms per tracking iteration"
+              f" ({'hipGraph replay' if args.graph else 'eager'}{', fused pose and loss' if args.fused else ''}"
+              f"{', masked loss' if masked else ''}{', complete pose gradient' if args.complete_pose else ''})")
+        return err()
+
+    plain = track(False)
+    if args.masked:
+        kept = track(True)
+        print(f"final pose error, plain L1 -> masked: rotation {plain[0]:.2e} -> {kept[0]:.2e}, "
+              f"translation {plain[1]:.2e} -> {kept[1]:.2e}")
 
 
 if __name__ == "__main__":

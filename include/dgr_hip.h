@@ -406,6 +406,57 @@ int dgr_ssim_loss_backward(void* stream, int n_images, int channels, int height,
                            long n_depth, const float* depth, const float* depth_obs, float w_l1, float w_ssim, float w_depth,
                            const float* scratch, const float* upstream, float* dL_dimg, float* dL_ddepth /* NULL when n_depth == 0 */);
 
+/* ---- the masked L1 loss of RGB-D SLAM with a per-view median outlier test (csrc/masked_loss.hip) ----
+ * Over a stack of n_views views -- color, color_obs: contiguous [n_views, channels, height, width] floats; depth, depth_obs,
+ * opacity_map (NULL: no silhouette test) and mask (bytes, NULL: no user mask): [n_views, height, width] -- per pixel p of view v,
+ * every operation a single fp32 one (a host restatement reproduces masks, medians and counts bit for bit):
+ *   e      = fabsf(depth - depth_obs)
+ *   B      = depth_lo < depth_obs && depth_obs < depth_hi && isfinite(e) [&& opacity_map > silhouette_threshold] [&& mask != 0]
+ *            (a NaN anywhere fails its test: the pixel drops out)
+ *   median = the LOWER median of e over B_v, the element of 0-based rank (|B_v| - 1) / 2 (torch.median's), 0 for an empty B_v;
+ *            exact, by a radix select over the bits of e on the device (no sort, no host read); one per view
+ *   K      = B && e <= outlier_factor * median     (<=: a perfectly fitted frame, median 0, keeps its pixels);
+ *            K = B with reject_outliers = 0, and then no median is computed (the stored one is NaN)
+ *   loss   = w_depth * S_d / N_d + w_color * S_c / N_c,   S_d = sum_K e,   S_c = sum over the channels of |color - color_obs|
+ *            over K (mask_color != 0) or over every pixel (mask_color = 0, the mapping form);
+ *            DGR_MASKED_LOSS_SUM: N_d = N_c = 1;  DGR_MASKED_LOSS_MEAN: N_d = |K| over the whole stack, N_c = channels * |K|, or
+ *            channels * height * width * n_views with mask_color = 0 -- counts read on the device; a zero count gives a zero term
+ *   dL_ddepth = *upstream * w_depth / N_d * sign(depth - depth_obs) on K, 0 elsewhere; dL_dcolor likewise on its set.  The mask
+ *            is piecewise constant: nothing flows to opacity_map, the observations or the median.
+ * `scratch`: dgr_masked_loss_scratch_bytes() bytes, 16-byte aligned (0 for a shape it refuses: a non-positive dimension, n_views
+ *   above 65535, height * width above 2^30).  With R(x) = x rounded up to a multiple of 16, from its start:
+ *     stats header   64 bytes: float[0] = w_depth / N_d, float[1] = w_color / N_c (the backward's scales); bytes 8..63 are not
+ *                    written (a caller may point `loss` there)
+ *     median         float[n_views] at 64;   base = |B_v|: int[n_views] at 64 + R(4 n_views);   kept = |K_v|: int[n_views] at
+ *                    64 + 2 R(4 n_views);    then 16 n_views bytes of per-view sums
+ *     histograms     3 * n_views * 2048 32-bit counts (the select's three digits of 11 / 11 / 10 bits)
+ *     partials       32 bytes per workgroup (sums as hi/lo float pairs, counts)
+ *     mask bytes     the LAST R(n_views * height * width) bytes: 1 for a pixel in K, else 0 -- the backward reads them, so the
+ *                    mask has one definition
+ * The forward is at most six launches (two with reject_outliers = 0), the backward one; none of them blocks the host, both can
+ * be captured into a hipGraph, sums are added in a fixed order and only integers atomically: every output carries the same bits
+ * on every run.  The backward takes the forward's arguments and scratch; dL_dcolor or dL_ddepth may be NULL (not both).
+ * Every argument error returns DGR_ERR_BAD_ARGUMENT with a message before any device call. */
+#define DGR_MASKED_LOSS_SUM 0
+#define DGR_MASKED_LOSS_MEAN 1
+typedef struct dgr_masked_loss_params {
+    float depth_lo, depth_hi;     /* exclusive bounds on depth_obs; (0, INFINITY) = any valid sensor depth */
+    float silhouette_threshold;   /* used when opacity_map != NULL */
+    float outlier_factor;         /* >= 0; used when reject_outliers != 0 */
+    int reject_outliers;
+    int mask_color;
+    int reduction;                /* DGR_MASKED_LOSS_SUM or DGR_MASKED_LOSS_MEAN */
+    float w_color, w_depth;
+} dgr_masked_loss_params;
+size_t dgr_masked_loss_scratch_bytes(int n_views, int height, int width);
+int dgr_masked_loss_forward(void* stream, int n_views, int channels, int height, int width, const float* color,
+                            const float* color_obs, const float* depth, const float* depth_obs, const float* opacity_map,
+                            const unsigned char* mask, const dgr_masked_loss_params* params, void* scratch, float* loss);
+int dgr_masked_loss_backward(void* stream, int n_views, int channels, int height, int width, const float* color,
+                             const float* color_obs, const float* depth, const float* depth_obs, const float* opacity_map,
+                             const unsigned char* mask, const dgr_masked_loss_params* params, const void* scratch,
+                             const float* upstream, float* dL_dcolor, float* dL_ddepth);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
