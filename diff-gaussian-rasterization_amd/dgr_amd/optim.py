@@ -28,8 +28,11 @@ def add_densification_stats(dmeans2D, radii, xyz_gradient_accum=None, denom=None
     for t in (xyz_gradient_accum, denom, max_radii2D):
         if t is not None and (t.numel() != P or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
             raise RuntimeError("add_densification_stats: accumulators must be contiguous float32 GPU tensors with P elements")
-    if radii.dtype != torch.int32 or not radii.is_cuda or dmeans2D.shape != (P, 3) or dmeans2D.dtype != torch.float32:
+    if (radii.dtype != torch.int32 or not radii.is_cuda or not dmeans2D.is_cuda or dmeans2D.shape != (P, 3) or
+            dmeans2D.dtype != torch.float32):
         raise RuntimeError("add_densification_stats: radii must be int32 [P] and dmeans2D float32 [P, 3] on the GPU")
+    if any(t is not None and t.device != radii.device for t in (dmeans2D, xyz_gradient_accum, denom, max_radii2D)):
+        raise RuntimeError("add_densification_stats: every tensor must be on radii's device")
     ptr = lambda t: None if t is None else t.data_ptr()
     rc = _capi.load().dgr_densification_stats(_capi.stream_handle(), P, dmeans2D.contiguous().data_ptr(),
                                               radii.contiguous().data_ptr(), ptr(xyz_gradient_accum), ptr(denom),
@@ -335,17 +338,37 @@ class SparseAdam:
 
     @torch.no_grad()
     def step(self, visible=None):
-        """visible: int32 [P] (e.g. the forward's radii; a row is updated where > 0) or None for every row."""
+        """visible: a bool or integer tensor with one entry per row on the parameters' device (e.g. the forward's radii; a row is
+        updated where > 0; any integer dtype is converted to int32) or None for every row.  Everything is checked on the host
+        before the library is loaded: a refused call leaves `steps`, the device step count and `state` as they were."""
+        if visible is not None and (not isinstance(visible, torch.Tensor) or visible.is_floating_point() or visible.is_complex()):
+            raise RuntimeError("SparseAdam: `visible` must be a bool or integer tensor (e.g. the forward's radii)")
+        live = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if visible is not None and any(visible.numel() != p.shape[0] for p in live if p.dim() >= 1):
+            raise RuntimeError("SparseAdam: `visible` must have one entry per row")
+        for p in live:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.dim() < 1:
+                raise RuntimeError("SparseAdam: parameters must be contiguous float32 tensors on the GPU")
+            if p.grad.dtype != torch.float32 or p.grad.device != p.device or p.grad.shape != p.shape:
+                raise RuntimeError("SparseAdam: a gradient must be a float32 tensor of its parameter's shape and device")
+        if visible is not None and any(visible.device != p.device for p in live):
+            raise RuntimeError(f"SparseAdam: `visible` is on {visible.device}, not on the parameters' device")
+        dev = next(p.device for g in self.param_groups for p in g["params"])
+        fresh = (self.capturable and self._step_dev is None) or any(p not in self.state for p in live)
+        if fresh and dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("SparseAdam: this step() would create the moments or the device step count while a hipGraph is being "
+                               "recorded, and every replay would reset them: take one eager step first, then capture")
         lib = _capi.load()
         self.steps += 1
         if self.capturable:
             if self._step_dev is None:
-                dev = self.param_groups[0]["params"][0].device
                 self._step_dev = torch.full((1,), self.steps - 1, dtype=torch.int32, device=dev)
             self._step_dev.add_(1)
         if visible is not None:
             if visible.dtype == torch.bool:
                 visible = visible.to(torch.int32)
+            elif visible.dtype != torch.int32:  # (the sign test here: a wide value must not wrap into another sign)
+                visible = (visible > 0).to(torch.int32)
             visible = visible.contiguous()
         st = _capi.stream_handle()
         for g in self.param_groups:
@@ -353,16 +376,12 @@ class SparseAdam:
             for p in g["params"]:
                 if p.grad is None:
                     continue
-                if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("SparseAdam: parameters must be contiguous float32 tensors on the GPU")
                 grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 s = self.state.get(p)
                 if s is None:
                     s = self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
                 rows = p.shape[0]
                 k = p.numel() // max(rows, 1)
-                if visible is not None and visible.numel() != rows:
-                    raise RuntimeError("SparseAdam: `visible` must have one entry per row")
                 vis = None if visible is None else visible.data_ptr()
                 if self.capturable:
                     rc = lib.dgr_sparse_adam_capturable(st, rows, k, p.data_ptr(), grad.data_ptr(), s[0].data_ptr(),

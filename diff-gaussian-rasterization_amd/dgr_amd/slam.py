@@ -178,6 +178,11 @@ def pose_to_camera(q, t, tanfovx, tanfovy, znear=0.01, zfar=100.0):
     tensors: the fused form of `camera_tensors(w2c_from_quat_trans(q, t), tanfovx, tanfovy)` (2 launches for forward +
     backward instead of ~40 elementwise torch kernels).  The perspec_matrix is a symmetric frustum's (principal point at the
     image centre); an off-centre camera goes through `render(viewpoint_camera=...)` with its own `projection_matrix`."""
+    for x, n, name in ((q, 4, "q"), (t, 3, "t")):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.numel() != n:
+            raise ValueError(f"pose_to_camera: {name} must be a float32 tensor of {n} elements")
+    if not q.is_cuda or t.device != q.device:
+        raise ValueError("pose_to_camera: q and t must be on one GPU (there is no CPU fallback)")
     perspec = _perspec_cached(tanfovx, tanfovy, znear, zfar, q.device)
     view, proj, campos = _PoseToCamera.apply(q, t, perspec)
     return view, proj, perspec, campos
@@ -214,7 +219,11 @@ class _L1Loss(torch.autograd.Function):
 
 def l1_loss(color, depth, color_obs, depth_obs, w_color=1.0, w_depth=0.5):
     """w_color * mean|color - color_obs| + w_depth * mean|depth - depth_obs| as one fused reduction, with both gradient
-    images written by one launch in the backward (float32 GPU tensors; the observations carry no gradient)."""
+    images written by one launch in the backward (float32 GPU tensors, each image of its observation's shape; the observations
+    carry no gradient)."""
+    _check_pair("color", color, color_obs, "l1_loss")
+    _check_pair("depth", depth, depth_obs, "l1_loss")
+    _check_gpu("l1_loss", color, color_obs, depth, depth_obs)
     return _L1Loss.apply(color, depth, color_obs, depth_obs, w_color, w_depth)
 
 
