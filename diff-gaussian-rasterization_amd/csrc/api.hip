@@ -1343,4 +1343,54 @@ int dgr_masked_loss_backward(void* stream, int n_views, int channels, int height
     return DGR_OK;
 }
 
+// 2^20 keyframes at most: with n_keyframes * candidates below 2^31 the count launch then stays under 2^21 workgroups
+static const int OVERLAP_MAX_KEYFRAMES = 1 << 20;
+static const char* keyframe_overlap_shape_error(int width, int height, int stride, int n_keyframes) {
+    if (width < 1 || height < 1) return "width and height must be positive";
+    if (stride < 1) return "stride must be positive";
+    if (n_keyframes < 1) return "n_keyframes must be positive";
+    if (n_keyframes > OVERLAP_MAX_KEYFRAMES) return "n_keyframes must be at most 2^20";
+    if (dgr::seed_candidates(width, height, stride) * (size_t)n_keyframes >= ((size_t)1 << 31))
+        return "n_keyframes * candidates must be below 2^31";
+    return nullptr;
+}
+size_t dgr_keyframe_overlap_scratch_bytes(int width, int height, int stride, int n_keyframes) {
+    return keyframe_overlap_shape_error(width, height, stride, n_keyframes)
+               ? 0
+               : dgr::keyframe_overlap_scratch_bytes(width, height, stride, n_keyframes);
+}
+int dgr_keyframe_overlap(void* stream, int width, int height, const float* depth_obs, const float* viewmatrix, int n_keyframes,
+                         const float* keyframe_viewmatrices, const float* keyframe_depths,
+                         const dgr_keyframe_overlap_params* params, void* scratch, int* inside, int* visible, int* valid,
+                         float* score, unsigned char* flags) {
+    const dgr_keyframe_overlap_params* p = params;
+    const char* bad = !p ? "params is NULL" : keyframe_overlap_shape_error(width, height, p->stride, n_keyframes);
+    if (!bad && !depth_obs) bad = "depth_obs is NULL";
+    if (!bad && !viewmatrix) bad = "viewmatrix is NULL";
+    if (!bad && !keyframe_viewmatrices) bad = "keyframe_viewmatrices is NULL";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && (!inside || !visible || !valid || !score)) bad = "inside, visible, valid or score is NULL";
+    if (!bad && !(p->fx > 0.0f && p->fy > 0.0f && std::isfinite(p->fx) && std::isfinite(p->fy)))
+        bad = "fx and fy must be finite and positive";
+    if (!bad && (std::isnan(p->cx) || std::isnan(p->cy))) bad = "cx or cy is NaN";
+    if (!bad && (std::isnan(p->depth_min) || std::isnan(p->depth_max))) bad = "depth_min or depth_max is NaN";
+    if (!bad && std::isnan(p->near_z)) bad = "near_z is NaN";
+    if (!bad && !(p->edge >= 0.0f)) bad = "edge is NaN or negative";
+    if (!bad && !(p->depth_tolerance >= 0.0f)) bad = "depth_tolerance is NaN or negative";
+    if (bad) {
+        set_last_error(std::string("dgr_keyframe_overlap: ") + bad);
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    dgr::KeyframeOverlapArgs a{};
+    a.W = width, a.H = height, a.stride = p->stride, a.K = n_keyframes;
+    a.depth_obs = depth_obs, a.viewmatrix = viewmatrix, a.keyframe_viewmatrices = keyframe_viewmatrices;
+    a.keyframe_depths = keyframe_depths;
+    a.fx = p->fx, a.fy = p->fy, a.inv_fx = (float)(1.0 / (double)p->fx), a.inv_fy = (float)(1.0 / (double)p->fy);
+    a.cx = p->cx, a.cy = p->cy, a.depth_min = p->depth_min, a.depth_max = p->depth_max;
+    a.edge = p->edge, a.near_z = p->near_z, a.depth_tolerance = p->depth_tolerance;
+    a.inside = inside, a.visible = visible, a.valid = valid, a.score = score, a.flags = flags;
+    HIP_TRY(dgr::launch_keyframe_overlap(a, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

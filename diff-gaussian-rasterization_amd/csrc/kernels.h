@@ -330,6 +330,20 @@ hipError_t launch_seed_apply(int W, int H, int stride, size_t rows, size_t rows_
                              const dgr_seed_tensor* tensors, const float* color_obs, const float* depth_obs,
                              const float* viewmatrix, float inv_fx, float inv_fy, float cx, float cy, float pix,
                              hipStream_t stream);
+// keyframe overlap scores (keyframe_overlap.hip; include/dgr_hip.h: dgr_keyframe_overlap): the candidates are seed.hip's grid.
+// One launch, or two with more than one block of candidates per keyframe; `scratch`: keyframe_overlap_scratch_bytes() bytes
+struct KeyframeOverlapArgs {
+    int W, H, stride, K;
+    const float *depth_obs, *viewmatrix, *keyframe_viewmatrices, *keyframe_depths;  // keyframe_depths: NULL = visible is inside
+    float fx, fy, inv_fx, inv_fy, cx, cy, depth_min, depth_max, edge, near_z, depth_tolerance;
+    int *inside, *visible, *valid;
+    float* score;
+    unsigned char* flags;  // NULL: not stored
+    size_t candidates;     // filled in by the launcher, as wc (candidates per grid row)
+    int wc;
+};
+size_t keyframe_overlap_scratch_bytes(int W, int H, int stride, int K);
+hipError_t launch_keyframe_overlap(const KeyframeOverlapArgs& args, void* scratch, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -75,6 +75,14 @@ class MaskedLossParams(C.Structure):  # dgr_masked_loss_params
 
 assert C.sizeof(MaskedLossParams) == 36  # nine four-byte fields: the C layout
 
+
+class KeyframeOverlapParams(C.Structure):  # dgr_keyframe_overlap_params
+    _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("depth_min", _f), ("depth_max", _f), ("edge", _f), ("near_z", _f),
+                ("depth_tolerance", _f), ("stride", _i)]
+
+
+assert C.sizeof(KeyframeOverlapParams) == 40  # ten four-byte fields: the C layout
+
 MASKED_LOSS_SUM, MASKED_LOSS_MEAN = 0, 1  # DGR_MASKED_LOSS_*
 MAX_BATCH_VIEWS = 8  # DGR_MAX_BATCH_VIEWS
 DENSIFY_MAX_TENSORS = 24  # DGR_DENSIFY_MAX_TENSORS
@@ -112,6 +120,9 @@ _SIGS = {
     "dgr_masked_loss_forward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaskedLossParams), _vp, _vp]),
     "dgr_masked_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MaskedLossParams), _vp, _vp,
                                       _vp, _vp]),
+    "dgr_keyframe_overlap_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "dgr_keyframe_overlap": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.POINTER(KeyframeOverlapParams), _vp, _vp, _vp, _vp, _vp,
+                                  _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -21,9 +21,12 @@ keyframe is rendered before it joins the window and seeded where its silhouette 
 masked loss in its mapping form (slam.masked_l1_loss(mask_color=False): the depth term over the valid pixels whose error is at most
 10 x the keyframe's median error, the colour term over every pixel); with --seed a joining keyframe is also seeded where the
 rendered depth lies more than 50 x the median depth error behind the sensor's (`stats.median * 50`, a device tensor: no host read).
+--select K treats the --keyframes poses as the session's keyframe POOL (one of which, as in a real session, looks at another part
+of the room) and maps against a window of K of them: the newest keyframe and the K - 1 that overlap it most
+(slam.keyframe_overlap: one launch scores the whole pool on the device; slam.select_keyframes: the top scores, read once).
 
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
-                             [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked]
+                             [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked] [--select K]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -117,7 +120,7 @@ class SeededMapModel(MapModel):
 
 
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
-                 absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False):
+                 absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -128,7 +131,10 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     iters // keyframes iterations (light variant, not with graph=True or fused=True: the step changes the number of Gaussians
     and the window grows).
     masked=True: the observed depth has holes and the loss is slam.masked_l1_loss in its mapping form (not with ssim_lambda > 0);
-    with seed=True the seeding also takes `stats.median * 50` as its depth_error_min."""
+    with seed=True the seeding also takes `stats.median * 50` as its depth_error_min.
+    select=K: the `keyframes` poses are a pool (keyframe 1 of three or more turned to look the opposite way); the window mapped
+    against is the newest keyframe and the K - 1 others that overlap it most (slam.keyframe_overlap / select_keyframes; not with
+    seed=True, whose window grows by itself).  The model's `window` attribute then lists the pool indices chosen."""
     from dgr_amd import light, slam
     from dgr_amd.optim import SparseAdam, add_densification_stats, densify_and_prune, seed_from_frame
     from dgr_amd.synth import make_scene
@@ -138,11 +144,27 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     bg, gt = torch.from_numpy(s.bg).to(dev), torch.from_numpy(s.gt).to(dev)
     cams = [dict(viewmatrix=torch.from_numpy(sc.view).to(dev), fov=(sc.tanfovx, sc.tanfovy), HW=(H, W), gt_depth=gt)
             for sc in scenes]
+    if select and keyframes >= 3:  # a keyframe from elsewhere in the session: same centre, a half turn about the camera's y axis
+        cams[1]["viewmatrix"] = cams[1]["viewmatrix"] * torch.tensor([-1.0, 1.0, -1.0, 1.0], device=dev)
     kw = dict(track_off=True, map_off=False) if variant == "light" else dict(variant="full")
     truth = MapModel(s, dev)
     with torch.no_grad():
         obs = [slam.render(None, truth, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt, **kw)
                for c in cams]
+    window = None
+    if select:  # the window: the newest keyframe and the select - 1 of the others that see most of what it sees
+        newest = keyframes - 1
+        sensor = torch.where(obs[newest]["opacity_map"] > 0.9, obs[newest]["depth"] / obs[newest]["opacity_map"],
+                             torch.zeros_like(obs[newest]["depth"]))
+        pool = torch.stack([c["viewmatrix"] for c in cams[:newest]])
+        overlap = slam.keyframe_overlap(sensor, cams[newest]["viewmatrix"], pool, W / (2.0 * s.tanfovx), H / (2.0 * s.tanfovy),
+                                        (W - 1) / 2.0, (H - 1) / 2.0, stride=max(1, min(16, W // 40)), edge=min(20.0, W / 32.0))
+        chosen, count = slam.select_keyframes(overlap.score, select - 1)
+        window = sorted(chosen[:int(count)].tolist()) + [newest]  # (the step's one host read; logging the scores below is a second)
+        if log:
+            log(f"select: overlap with keyframe {newest}: " + ", ".join(f"{x:.3f}" for x in overlap.score.tolist()) +
+                f" -> window {window}")
+        cams, obs, keyframes = [cams[k] for k in window], [obs[k] for k in window], len(window)
     if seed:  # the synthetic sensor: the truth's expected depth where the truth covers the pixel, a hole (0) elsewhere
         sensor_depth = [torch.where(o["opacity_map"] > 0.9, o["depth"] / o["opacity_map"], torch.zeros_like(o["depth"])).detach()
                         for o in obs]
@@ -292,6 +314,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     dt = (time.perf_counter() - t0) / max(iters - 3, 1)
     if graph:
         step.check()
+    pc.window = window
     return (first, float(loss)), pc, dt
 
 
@@ -320,6 +343,10 @@ def main():
     ap.add_argument("--masked", action="store_true",
                     help="observed depth with holes and the masked loss in its mapping form (slam.masked_l1_loss(mask_color=False)); "
                          "with --seed, stats.median * 50 becomes the seeding's depth_error_min; not together with --ssim")
+    ap.add_argument("--select", type=int, default=0, metavar="K",
+                    help="map against a window of K keyframes chosen from the --keyframes pool by their overlap with the newest one "
+                         "(slam.keyframe_overlap + slam.select_keyframes); 0 (default) maps against every keyframe; not together "
+                         "with --seed")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -333,6 +360,8 @@ def main():
     if args.seed and (args.graph or args.fused or args.variant != "light"):
         ap.error("--seed changes the number of Gaussians and grows the window: it cannot run inside a recorded hipGraph (drop "
                  "--graph), and it maps through the per-keyframe light path (drop --fused / --variant full)")
+    if args.select < 0 or args.select > args.keyframes or (args.select and args.seed):
+        ap.error("--select K chooses 1 .. --keyframes keyframes of the pool; --seed grows its own window (drop one of the two)")
     import torch as _torch
     _torch.autograd.set_multithreading_enabled(False)  # one device, one thread: no engine-thread hand-off per backward
     if args.graph:
@@ -341,7 +370,9 @@ def main():
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
                                     args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
                                     variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every, ssim_lambda=args.ssim,
-                                    seed=args.seed, masked=args.masked)
+                                    seed=args.seed, masked=args.masked, select=args.select)
+    if args.select:
+        args.keyframes = len(pc.window)
     n = float(pc.denom.sum())
     print(("full variant: " if args.variant == "full" else "") + ("absgrad: " if args.absgrad else "") +
           (f"L1 + D-SSIM (lambda {args.ssim:g}): " if args.ssim > 0 else "") + ("masked L1: " if args.masked else "") +

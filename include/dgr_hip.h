@@ -457,6 +457,49 @@ int dgr_masked_loss_backward(void* stream, int n_views, int channels, int height
                              const unsigned char* mask, const dgr_masked_loss_params* params, const void* scratch,
                              const float* upstream, float* dL_dcolor, float* dL_ddepth);
 
+/* ---- keyframe overlap scores: which stored keyframes see what the current frame sees (csrc/keyframe_overlap.hip) ----
+ * What CG-SLAM, SplaTAM and the NICE-SLAM family do before a mapping phase (SplaTAM's keyframe_selection_overlap), and MonoGS
+ * against the last keyframe (n_keyframes = 1) to decide whether a frame becomes a keyframe: pixels of the current frame are
+ * unprojected with the measured depth, taken into every stored keyframe and counted where they land inside its image.  One call
+ * for all keyframes, one launch (two when a keyframe's candidates need more than one workgroup), no host read, no atomics.
+ * Inputs, float32 on the device: depth_obs [height, width]; viewmatrix: the current frame's 16 floats holding W2C^T (what the
+ * rasterizer takes and dgr_pose_forward writes; taken as rigid); keyframe_viewmatrices [n_keyframes, 16], same convention;
+ * keyframe_depths [n_keyframes, height, width] or NULL.  The keyframes share the frame's size and intrinsics (as the batched entry
+ * points assume).
+ * Candidates: the stride grid of dgr_seed_plan -- the pixels with x % stride == 0 && y % stride == 0, numbered row-major, S =
+ *   ceil(width / stride) * ceil(height / stride).  No sampling, no compaction.
+ *   valid   = depth_min < d && d < depth_max, d = depth_obs at the candidate: raw fp32 comparisons, false on a NaN (dgr_seed_plan's)
+ * Geometry, in fp32 (fused multiply-adds allowed): pixel (x, y) at depth d is p = ((x - cx) / fx * d, (y - cy) / fy * d, d) in the
+ *   current camera (dgr_seed_plan's convention); p goes to the world through the rigid inverse of the current pose and on into
+ *   keyframe k, (X, Y, Z) = R_k R^T (p - t) + t_k.  The kernel forms R_k R^T and t_k - R_k R^T t from the two matrices itself, in
+ *   double, rounded once: no inverse is formed on the host.  u = fx * X / Z + cx, v = fy * Y / Z + cy.
+ *   inside  = valid && Z > near_z && edge < u && u < width - edge && edge < v && v < height - edge      (SplaTAM's strict tests)
+ *   visible = inside without keyframe_depths; with them, inside && depth_min < d_k && d_k < depth_max &&
+ *             fabsf(Z - d_k) <= depth_tolerance * d_k, d_k = keyframe k's depth at pixel (floor(u + 0.5), floor(v + 0.5)); a pixel
+ *             outside the image (possible only with edge < 0.5) is not visible
+ * Outputs, on the device: inside[n_keyframes], visible[n_keyframes] (int counts per keyframe), valid[1] (int, the frame's),
+ * score[n_keyframes] = (float)visible[k] / (float)valid as one fp32 division, 0 when valid == 0 (never NaN); flags
+ * [n_keyframes, S] bytes (bit 0 valid, bit 1 inside, bit 2 visible) or NULL.  Nothing else is written.  Counts are integer sums:
+ * the same bits on every run.  Capturable into a hipGraph.
+ * `scratch`: dgr_keyframe_overlap_scratch_bytes() bytes, 16-byte aligned (0 for a shape it refuses).
+ * Argument errors return DGR_ERR_BAD_ARGUMENT with a message before any device call: non-positive width, height, stride or
+ * n_keyframes; n_keyframes above 2^20 or n_keyframes * S at or above 2^31; a NULL params, depth_obs, viewmatrix,
+ * keyframe_viewmatrices, scratch (or a misaligned one) or output other than flags; fx or fy not finite and positive; a NaN cx, cy,
+ * depth_min, depth_max or near_z; an edge or depth_tolerance that is NaN or negative. */
+typedef struct dgr_keyframe_overlap_params {
+    float fx, fy, cx, cy;         /* the shared intrinsics, pixels */
+    float depth_min, depth_max;   /* exclusive bounds on a usable depth; (0, INFINITY) = any valid sensor depth */
+    float edge;                   /* >= 0: the margin inside the keyframe's image, pixels (SplaTAM: 20) */
+    float near_z;                 /* Z > near_z (SplaTAM: 0) */
+    float depth_tolerance;        /* >= 0; used with keyframe_depths */
+    int stride;
+} dgr_keyframe_overlap_params;
+size_t dgr_keyframe_overlap_scratch_bytes(int width, int height, int stride, int n_keyframes);
+int dgr_keyframe_overlap(void* stream, int width, int height, const float* depth_obs, const float* viewmatrix, int n_keyframes,
+                         const float* keyframe_viewmatrices, const float* keyframe_depths /* or NULL */,
+                         const dgr_keyframe_overlap_params* params, void* scratch, int* inside, int* visible, int* valid,
+                         float* score, unsigned char* flags /* or NULL */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
