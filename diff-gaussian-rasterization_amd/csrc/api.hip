@@ -6,8 +6,9 @@
 //             per-tile sort -> blend
 //   backward: zero accumulator rows -> blend backward -> fused per-Gaussian backward -> pose reduce
 // Nothing here touches the CPU oracle; a missing GPU or a failed launch is reported, never papered over.
-// The library options are in options.hip, the status read-back in status.hip, the stage profiler in profile.hip and
-// dgr_state_export in state_export.hip.
+// The library options are in options.hip, the status read-back in status.hip, the stage profiler in profile.hip,
+// dgr_state_export in state_export.hip and the entry points of the steps around the rasteriser (optimiser, map resize, pose,
+// losses, keyframe overlap) in api_steps.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1004,21 +1005,6 @@ int dgr_full_backward_batch_silhouette(void* stream, int n_views, const dgr_full
     return backward_batch_views((hipStream_t)stream, b, background, n_views, views, dL_dmean2D_abs, dL_dpix_silhouette);
 }
 
-int dgr_cov3d_forward(void* stream, int P, const float* scales, const float* rotations, float scale_modifier, float* cov3D) {
-    if (P < 0 || (P > 0 && (!scales || !rotations || !cov3D))) { set_last_error("dgr_cov3d_forward: bad argument"); return DGR_ERR_BAD_ARGUMENT; }
-    HIP_TRY(dgr::launch_cov3d_forward(P, scales, rotations, scale_modifier, cov3D, (hipStream_t)stream));
-    return DGR_OK;
-}
-int dgr_cov3d_backward(void* stream, int P, const float* scales, const float* rotations, float scale_modifier,
-                       const float* dL_dcov3D, float* dL_dscales, float* dL_drotations) {
-    if (P < 0 || (P > 0 && (!scales || !rotations || !dL_dcov3D || !dL_dscales || !dL_drotations))) {
-        set_last_error("dgr_cov3d_backward: bad argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_cov3d_backward(P, scales, rotations, scale_modifier, dL_dcov3D, dL_dscales, dL_drotations, (hipStream_t)stream));
-    return DGR_OK;
-}
-
 int dgr_debug_bin_tiles_trace(unsigned long long* device_words) {
     dgr::g_bin_tiles_trace = device_words;
     return DGR_OK;
@@ -1048,349 +1034,4 @@ int dgr_debug_exact_math(void* stream, int n, const float* x, const float* a, co
     HIP_TRY(dgr::launch_exact_math_test(n, x, a, b, out_exp, out_div, opt_alpha_mode(), (hipStream_t)stream));
     return DGR_OK;
 }
-
-int dgr_sparse_adam(void* stream, long rows, int k, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
-                    const int* visible, float lr, float beta1, float beta2, float eps, int step) {
-    if (rows < 0 || k <= 0 || step < 1 || (rows > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) {
-        set_last_error("dgr_sparse_adam: bad argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_sparse_adam((size_t)rows, k, param, grad, exp_avg, exp_avg_sq, visible, lr, beta1, beta2, eps, step,
-                                    nullptr, (hipStream_t)stream));
-    return DGR_OK;
-}
-int dgr_sparse_adam_capturable(void* stream, long rows, int k, float* param, const float* grad, float* exp_avg,
-                               float* exp_avg_sq, const int* visible, float lr, float beta1, float beta2, float eps,
-                               const int* step_device) {
-    if (rows < 0 || k <= 0 || !step_device || (rows > 0 && (!param || !grad || !exp_avg || !exp_avg_sq))) {
-        set_last_error("dgr_sparse_adam_capturable: bad argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_sparse_adam((size_t)rows, k, param, grad, exp_avg, exp_avg_sq, visible, lr, beta1, beta2, eps, 1,
-                                    step_device, (hipStream_t)stream));
-    return DGR_OK;
-}
-
-int dgr_densification_stats(void* stream, long rows, const float* dmeans2D, const int* radii, float* grad_accum, float* denom,
-                            float* max_radii2D) {
-    if (rows < 0 || rows > 0x7fffffffL || (rows > 0 && (!radii || (grad_accum && !dmeans2D)))) {
-        set_last_error("dgr_densification_stats: bad argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_densification_stats((int)rows, dmeans2D, radii, grad_accum, denom, max_radii2D, (hipStream_t)stream));
-    return DGR_OK;
-}
-
-size_t dgr_densify_plan_bytes(long rows) { return rows < 0 ? 0 : dgr::densify_plan_bytes((size_t)rows); }
-
-// P' <= 2 rows must fit the int counts
-static const long DENSIFY_MAX_ROWS = 0x3fffffffL;
-
-int dgr_densify_plan(void* stream, long rows, const float* grad_accum, const float* denom, const float* max_radii2D,
-                     const float* opacity_raw, const float* scaling_raw, float grad_threshold, float opacity_raw_min,
-                     float log_scale_split, float log_scale_prune, float max_screen_size, void* plan, int* counts8_device) {
-    const char* bad = nullptr;
-    if (rows < 0 || rows > DENSIFY_MAX_ROWS) bad = "rows must be 0 .. 2^30 - 1";
-    else if (!plan || !dgr::aligned16(plan)) bad = "plan is NULL or not 16-byte aligned";
-    else if (!counts8_device) bad = "counts8_device is NULL";
-    else if (rows > 0 && (!grad_accum || !denom || !opacity_raw || !scaling_raw)) bad = "a NULL input";
-    if (bad) {
-        set_last_error(std::string("dgr_densify_plan: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_densify_plan((size_t)rows, grad_accum, denom, max_radii2D, opacity_raw, scaling_raw, grad_threshold,
-                                     opacity_raw_min, log_scale_split, log_scale_prune, max_screen_size, plan, counts8_device,
-                                     (hipStream_t)stream));
-    return DGR_OK;
-}
-
-int dgr_densify_apply(void* stream, long rows, long rows_out, const void* plan, int n, const dgr_densify_tensor* tensors,
-                      const float* scaling_raw, const float* rotation_raw, const float* noise, unsigned long long seed) {
-    const char* bad = nullptr;
-    int n_xyz = 0;
-    if (rows < 0 || rows > DENSIFY_MAX_ROWS) bad = "rows must be 0 .. 2^30 - 1";
-    else if (rows_out < 0 || rows_out > 2 * rows) bad = "rows_out must be 0 .. 2 rows";
-    else if (!plan || !dgr::aligned16(plan)) bad = "plan is NULL or not 16-byte aligned";
-    else if (n < 1 || n > DGR_DENSIFY_MAX_TENSORS) bad = "n must be 1 .. DGR_DENSIFY_MAX_TENSORS (24) tensors";
-    else if (!tensors) bad = "tensors is NULL";
-    for (int i = 0; !bad && i < n; ++i) {
-        const dgr_densify_tensor& t = tensors[i];
-        if (t.k < 1 || t.k > (1 << 22)) bad = "a tensor with k < 1 or k > 2^22";
-        else if (t.mode < DGR_DENSIFY_COPY || t.mode > DGR_DENSIFY_LOG_SCALE) bad = "unknown mode";
-        else if (t.mode == DGR_DENSIFY_XYZ && t.k != 3) bad = "the XYZ tensor must have k = 3";
-        else if (t.mode == DGR_DENSIFY_XYZ && ++n_xyz > 1) bad = "more than one XYZ tensor";
-        else if (rows_out > 0 && (!t.dst || (t.mode != DGR_DENSIFY_ZERO && !t.src))) bad = "a tensor with a NULL src or dst";
-    }
-    if (!bad && n_xyz && rows_out > 0 && (!scaling_raw || !rotation_raw)) bad = "XYZ needs scaling_raw and rotation_raw";
-    if (bad) {
-        set_last_error(std::string("dgr_densify_apply: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_densify_apply((size_t)rows, (size_t)rows_out, plan, n, tensors, scaling_raw, rotation_raw, noise, seed,
-                                      (hipStream_t)stream));
-    return DGR_OK;
-}
-
-// rows + candidates must fit the int counts
-static const long SEED_MAX = 0x3fffffffL;
-static const char* seed_shape_error(int width, int height, int stride) {
-    if (width < 1 || height < 1) return "width and height must be positive";
-    if (stride < 1) return "stride must be positive";
-    if (dgr::seed_candidates(width, height, stride) > (size_t)SEED_MAX) return "2^30 candidates or more";
-    return nullptr;
-}
-size_t dgr_seed_plan_bytes(int width, int height, int stride) {
-    return seed_shape_error(width, height, stride) ? 0 : dgr::seed_plan_bytes(width, height, stride);
-}
-
-int dgr_seed_plan(void* stream, int width, int height, int stride, const float* depth_obs, const float* opacity_map,
-                  const float* depth, float depth_min, float depth_max, float silhouette_threshold, float depth_error_min,
-                  const float* depth_error_min_device, long rows, void* plan, int* counts8_device) {
-    const char* bad = seed_shape_error(width, height, stride);
-    if (!bad && (rows < 0 || rows > SEED_MAX)) bad = "rows must be 0 .. 2^30 - 1";
-    if (!bad && (!plan || !dgr::aligned16(plan))) bad = "plan is NULL or not 16-byte aligned";
-    if (!bad && (!counts8_device)) bad = "counts8_device is NULL";
-    if (!bad && (!depth_obs)) bad = "depth_obs is NULL";
-    if (bad) {
-        set_last_error(std::string("dgr_seed_plan: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_seed_plan(width, height, stride, depth_obs, opacity_map, depth, depth_min, depth_max, silhouette_threshold,
-                                  depth_error_min, depth_error_min_device, (size_t)rows, plan, counts8_device,
-                                  (hipStream_t)stream));
-    return DGR_OK;
-}
-
-int dgr_seed_apply(void* stream, int width, int height, int stride, long rows, long rows_out, const void* plan, int n,
-                   const dgr_seed_tensor* tensors, const float* color_obs, const float* depth_obs, const float* viewmatrix,
-                   float fx, float fy, float cx, float cy, float pix) {
-    const char* bad = seed_shape_error(width, height, stride);
-    int n_xyz = 0;
-    if (!bad && (rows < 0 || rows > SEED_MAX)) bad = "rows must be 0 .. 2^30 - 1";
-    if (!bad && (rows_out < rows || rows_out - rows > (long)dgr::seed_candidates(width, height, stride)))
-        bad = "rows_out must be rows + the plan's count of new rows (rows .. rows + candidates)";
-    if (!bad && (!plan || !dgr::aligned16(plan))) bad = "plan is NULL or not 16-byte aligned";
-    if (!bad && (!depth_obs)) bad = "depth_obs is NULL";
-    if (!bad && (!viewmatrix)) bad = "viewmatrix is NULL";
-    if (!bad && (!(fx > 0.0f && fy > 0.0f && std::isfinite(fx) && std::isfinite(fy)))) bad = "fx and fy must be finite and positive";
-    if (!bad && (n < 1 || n > DGR_SEED_MAX_TENSORS)) bad = "n must be 1 .. DGR_SEED_MAX_TENSORS (24) tensors";
-    if (!bad && (!tensors)) bad = "tensors is NULL";
-    for (int i = 0; !bad && i < n; ++i) {
-        const dgr_seed_tensor& t = tensors[i];
-        if (t.k < 1 || t.k > (1 << 22)) bad = "a tensor with k < 1 or k > 2^22";
-        else if (t.mode < DGR_SEED_XYZ || t.mode > DGR_SEED_CONST) bad = "unknown mode";
-        else if (t.mode == DGR_SEED_XYZ && t.k != 3) bad = "the XYZ tensor must have k = 3";
-        else if (t.mode == DGR_SEED_XYZ && ++n_xyz > 1) bad = "more than one XYZ tensor";
-        else if (t.mode == DGR_SEED_LOG_SCALE && t.k != 3 && t.k != 1) bad = "a LOG_SCALE tensor must have k = 3 or k = 1";
-        else if (t.mode == DGR_SEED_RGB_DC && t.k != 3) bad = "an RGB_DC tensor must have k = 3";
-        else if (t.mode == DGR_SEED_RGB_DC && !color_obs) bad = "RGB_DC needs color_obs";
-        else if (t.mode == DGR_SEED_QUAT_IDENTITY && t.k != 4) bad = "a QUAT_IDENTITY tensor must have k = 4";
-        else if (rows_out > 0 && (!t.dst || (rows > 0 && !t.src))) bad = "a tensor with a NULL dst, or a NULL src with rows > 0";
-    }
-    if (bad) {
-        set_last_error(std::string("dgr_seed_apply: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_seed_apply(width, height, stride, (size_t)rows, (size_t)rows_out, plan, n, tensors, color_obs, depth_obs,
-                                   viewmatrix, (float)(1.0 / (double)fx), (float)(1.0 / (double)fy), cx, cy, pix,
-                                   (hipStream_t)stream));
-    return DGR_OK;
-}
-
-int dgr_pose_forward(void* stream, const float* quat, const float* trans, const float* perspec_matrix, float* viewmatrix,
-                     float* projmatrix, float* campos) {
-    if (!quat || !trans || !perspec_matrix || !viewmatrix || !projmatrix || !campos) {
-        set_last_error("dgr_pose_forward: NULL argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_pose_forward(quat, trans, perspec_matrix, viewmatrix, projmatrix, campos, (hipStream_t)stream));
-    return DGR_OK;
-}
-int dgr_pose_backward(void* stream, const float* quat, const float* dL_dviewmatrix, float* dL_dquat, float* dL_dtrans) {
-    if (!quat || !dL_dviewmatrix || !dL_dquat || !dL_dtrans) {
-        set_last_error("dgr_pose_backward: NULL argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_pose_backward(quat, dL_dviewmatrix, dL_dquat, dL_dtrans, (hipStream_t)stream));
-    return DGR_OK;
-}
-int dgr_l1_loss_scratch_floats(void) { return dgr::l1_loss_partials(); }
-int dgr_l1_loss_forward(void* stream, long n_color, const float* color, const float* color_obs, long n_depth, const float* depth,
-                        const float* depth_obs, float w_color, float w_depth, float* scratch, float* loss) {
-    if (n_color < 0 || n_depth < 0 || !scratch || !loss || (n_color > 0 && (!color || !color_obs)) ||
-        (n_depth > 0 && (!depth || !depth_obs))) {
-        set_last_error("dgr_l1_loss_forward: bad argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_l1_loss_forward(n_color, color, color_obs, n_depth, depth, depth_obs, w_color, w_depth, scratch, loss,
-                                        (hipStream_t)stream));
-    return DGR_OK;
-}
-int dgr_l1_loss_backward(void* stream, long n_color, const float* color, const float* color_obs, long n_depth, const float* depth,
-                         const float* depth_obs, float w_color, float w_depth, const float* upstream, float* dL_dcolor,
-                         float* dL_ddepth) {
-    if (n_color < 0 || n_depth < 0 || (n_color > 0 && (!color || !color_obs || !dL_dcolor)) ||
-        (n_depth > 0 && (!depth || !depth_obs || !dL_ddepth))) {
-        set_last_error("dgr_l1_loss_backward: bad argument");
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_l1_loss_backward(n_color, color, color_obs, n_depth, depth, depth_obs, w_color, w_depth, upstream,
-                                         dL_dcolor, dL_ddepth, (hipStream_t)stream));
-    return DGR_OK;
-}
-
-// the shared argument checks of dgr_ssim_loss_forward / _backward: the message, or NULL
-static const char* ssim_bad_argument(int n_images, int channels, int height, int width, const float* img, const float* ref,
-                                     long n_depth, const float* depth, const float* depth_obs, const float* scratch) {
-    if (n_images <= 0 || channels <= 0 || height <= 0 || width <= 0) return "n_images, channels, height and width must be positive";
-    if (!dgr::ssim_shape_ok(n_images, channels, height, width))
-        return "n_images * channels must be at most 65535 (one grid plane each) and height, width at most 2^20";
-    if (!img || !ref) return "img or ref is NULL";
-    if (n_depth < 0) return "n_depth is negative";
-    if (n_depth > 0 && (!depth || !depth_obs)) return "n_depth > 0 with a NULL depth or depth_obs";
-    if (!scratch || !dgr::aligned16(scratch)) return "scratch is NULL or not 16-byte aligned";
-    return nullptr;
-}
-long dgr_ssim_scratch_floats(int n_images, int channels, int height, int width) {
-    return dgr::ssim_scratch_floats(n_images, channels, height, width);
-}
-int dgr_ssim_loss_forward(void* stream, int n_images, int channels, int height, int width, const float* img, const float* ref,
-                          long n_depth, const float* depth, const float* depth_obs, float w_l1, float w_ssim, float w_depth,
-                          float* scratch, int want_maps, float* loss) {
-    const char* bad = ssim_bad_argument(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, scratch);
-    if (!bad && !loss) bad = "loss is NULL";
-    if (bad) {
-        set_last_error(std::string("dgr_ssim_loss_forward: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_ssim_loss_forward(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, w_l1, w_ssim,
-                                          w_depth, scratch, want_maps != 0, loss, (hipStream_t)stream));
-    return DGR_OK;
-}
-int dgr_ssim_loss_backward(void* stream, int n_images, int channels, int height, int width, const float* img, const float* ref,
-                           long n_depth, const float* depth, const float* depth_obs, float w_l1, float w_ssim, float w_depth,
-                           const float* scratch, const float* upstream, float* dL_dimg, float* dL_ddepth) {
-    const char* bad = ssim_bad_argument(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, scratch);
-    if (!bad && !dL_dimg) bad = "dL_dimg is NULL";
-    if (!bad && n_depth > 0 && !dL_ddepth) bad = "n_depth > 0 with a NULL dL_ddepth";
-    if (bad) {
-        set_last_error(std::string("dgr_ssim_loss_backward: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_ssim_loss_backward(n_images, channels, height, width, img, ref, n_depth, depth, depth_obs, w_l1, w_ssim,
-                                           w_depth, scratch, upstream, dL_dimg, dL_ddepth, (hipStream_t)stream));
-    return DGR_OK;
-}
-
-// the shared argument checks of dgr_masked_loss_forward / _backward: the message, or NULL
-static const char* masked_loss_bad_argument(int n_views, int channels, int height, int width, const float* color,
-                                            const float* color_obs, const float* depth, const float* depth_obs,
-                                            const dgr_masked_loss_params* p, const void* scratch) {
-    if (n_views <= 0 || channels <= 0 || height <= 0 || width <= 0) return "n_views, channels, height and width must be positive";
-    if (!dgr::masked_loss_shape_ok(n_views, height, width)) return "n_views must be at most 65535 and height * width at most 2^30";
-    if (!color || !color_obs) return "color or color_obs is NULL";
-    if (!depth || !depth_obs) return "depth or depth_obs is NULL";
-    if (!p) return "params is NULL";
-    if (std::isnan(p->depth_lo) || std::isnan(p->depth_hi)) return "depth_lo or depth_hi is NaN";
-    if (std::isnan(p->silhouette_threshold)) return "silhouette_threshold is NaN";
-    if (std::isnan(p->outlier_factor)) return "outlier_factor is NaN";
-    if (p->reject_outliers && p->outlier_factor < 0.f) return "outlier_factor is negative";
-    if (p->reduction != DGR_MASKED_LOSS_SUM && p->reduction != DGR_MASKED_LOSS_MEAN) return "unknown reduction";
-    if (!scratch || !dgr::aligned16(scratch)) return "scratch is NULL or not 16-byte aligned";
-    return nullptr;
-}
-static dgr::MaskedLossArgs masked_loss_args(int n_views, int channels, int height, int width, const float* color,
-                                            const float* color_obs, const float* depth, const float* depth_obs,
-                                            const float* opacity_map, const unsigned char* mask, const dgr_masked_loss_params& p) {
-    dgr::MaskedLossArgs a{};
-    a.V = n_views, a.C = channels, a.H = height, a.W = width;
-    a.color = color, a.color_obs = color_obs, a.depth = depth, a.depth_obs = depth_obs, a.opacity = opacity_map, a.mask = mask;
-    a.lo = p.depth_lo, a.hi = p.depth_hi, a.silhouette = p.silhouette_threshold, a.factor = p.outlier_factor;
-    a.w_color = p.w_color, a.w_depth = p.w_depth;
-    a.reject = p.reject_outliers != 0, a.mask_color = p.mask_color != 0, a.mean = p.reduction == DGR_MASKED_LOSS_MEAN;
-    return a;
-}
-size_t dgr_masked_loss_scratch_bytes(int n_views, int height, int width) {
-    return (size_t)dgr::masked_loss_layout(n_views, height, width).total;
-}
-int dgr_masked_loss_forward(void* stream, int n_views, int channels, int height, int width, const float* color,
-                            const float* color_obs, const float* depth, const float* depth_obs, const float* opacity_map,
-                            const unsigned char* mask, const dgr_masked_loss_params* params, void* scratch, float* loss) {
-    const char* bad = masked_loss_bad_argument(n_views, channels, height, width, color, color_obs, depth, depth_obs, params, scratch);
-    if (!bad && !loss) bad = "loss is NULL";
-    if (bad) {
-        set_last_error(std::string("dgr_masked_loss_forward: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_masked_loss_forward(masked_loss_args(n_views, channels, height, width, color, color_obs, depth, depth_obs,
-                                                             opacity_map, mask, *params),
-                                            scratch, loss, (hipStream_t)stream));
-    return DGR_OK;
-}
-int dgr_masked_loss_backward(void* stream, int n_views, int channels, int height, int width, const float* color,
-                             const float* color_obs, const float* depth, const float* depth_obs, const float* opacity_map,
-                             const unsigned char* mask, const dgr_masked_loss_params* params, const void* scratch,
-                             const float* upstream, float* dL_dcolor, float* dL_ddepth) {
-    const char* bad = masked_loss_bad_argument(n_views, channels, height, width, color, color_obs, depth, depth_obs, params, scratch);
-    if (!bad && !dL_dcolor && !dL_ddepth) bad = "dL_dcolor and dL_ddepth are both NULL";
-    if (bad) {
-        set_last_error(std::string("dgr_masked_loss_backward: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    HIP_TRY(dgr::launch_masked_loss_backward(masked_loss_args(n_views, channels, height, width, color, color_obs, depth, depth_obs,
-                                                              opacity_map, mask, *params),
-                                             scratch, upstream, dL_dcolor, dL_ddepth, (hipStream_t)stream));
-    return DGR_OK;
-}
-
-// 2^20 keyframes at most: with n_keyframes * candidates below 2^31 the count launch then stays under 2^21 workgroups
-static const int OVERLAP_MAX_KEYFRAMES = 1 << 20;
-static const char* keyframe_overlap_shape_error(int width, int height, int stride, int n_keyframes) {
-    if (width < 1 || height < 1) return "width and height must be positive";
-    if (stride < 1) return "stride must be positive";
-    if (n_keyframes < 1) return "n_keyframes must be positive";
-    if (n_keyframes > OVERLAP_MAX_KEYFRAMES) return "n_keyframes must be at most 2^20";
-    if (dgr::seed_candidates(width, height, stride) * (size_t)n_keyframes >= ((size_t)1 << 31))
-        return "n_keyframes * candidates must be below 2^31";
-    return nullptr;
-}
-size_t dgr_keyframe_overlap_scratch_bytes(int width, int height, int stride, int n_keyframes) {
-    return keyframe_overlap_shape_error(width, height, stride, n_keyframes)
-               ? 0
-               : dgr::keyframe_overlap_scratch_bytes(width, height, stride, n_keyframes);
-}
-int dgr_keyframe_overlap(void* stream, int width, int height, const float* depth_obs, const float* viewmatrix, int n_keyframes,
-                         const float* keyframe_viewmatrices, const float* keyframe_depths,
-                         const dgr_keyframe_overlap_params* params, void* scratch, int* inside, int* visible, int* valid,
-                         float* score, unsigned char* flags) {
-    const dgr_keyframe_overlap_params* p = params;
-    const char* bad = !p ? "params is NULL" : keyframe_overlap_shape_error(width, height, p->stride, n_keyframes);
-    if (!bad && !depth_obs) bad = "depth_obs is NULL";
-    if (!bad && !viewmatrix) bad = "viewmatrix is NULL";
-    if (!bad && !keyframe_viewmatrices) bad = "keyframe_viewmatrices is NULL";
-    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
-    if (!bad && (!inside || !visible || !valid || !score)) bad = "inside, visible, valid or score is NULL";
-    if (!bad && !(p->fx > 0.0f && p->fy > 0.0f && std::isfinite(p->fx) && std::isfinite(p->fy)))
-        bad = "fx and fy must be finite and positive";
-    if (!bad && (std::isnan(p->cx) || std::isnan(p->cy))) bad = "cx or cy is NaN";
-    if (!bad && (std::isnan(p->depth_min) || std::isnan(p->depth_max))) bad = "depth_min or depth_max is NaN";
-    if (!bad && std::isnan(p->near_z)) bad = "near_z is NaN";
-    if (!bad && !(p->edge >= 0.0f)) bad = "edge is NaN or negative";
-    if (!bad && !(p->depth_tolerance >= 0.0f)) bad = "depth_tolerance is NaN or negative";
-    if (bad) {
-        set_last_error(std::string("dgr_keyframe_overlap: ") + bad);
-        return DGR_ERR_BAD_ARGUMENT;
-    }
-    dgr::KeyframeOverlapArgs a{};
-    a.W = width, a.H = height, a.stride = p->stride, a.K = n_keyframes;
-    a.depth_obs = depth_obs, a.viewmatrix = viewmatrix, a.keyframe_viewmatrices = keyframe_viewmatrices;
-    a.keyframe_depths = keyframe_depths;
-    a.fx = p->fx, a.fy = p->fy, a.inv_fx = (float)(1.0 / (double)p->fx), a.inv_fy = (float)(1.0 / (double)p->fy);
-    a.cx = p->cx, a.cy = p->cy, a.depth_min = p->depth_min, a.depth_max = p->depth_max;
-    a.edge = p->edge, a.near_z = p->near_z, a.depth_tolerance = p->depth_tolerance;
-    a.inside = inside, a.visible = visible, a.valid = valid, a.score = score, a.flags = flags;
-    HIP_TRY(dgr::launch_keyframe_overlap(a, scratch, (hipStream_t)stream));
-    return DGR_OK;
-}
-
 }  // extern "C"

@@ -9,7 +9,7 @@
 
 namespace dgr {
 
-// The text behind dgr_last_error(), one per thread (api.hip).
+// The text behind dgr_last_error(), one per thread (defined in api.hip).
 void set_last_error(const std::string& text);
 
 inline int hip_fail(hipError_t e, const char* what) {

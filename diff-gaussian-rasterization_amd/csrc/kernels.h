@@ -330,7 +330,7 @@ hipError_t launch_seed_apply(int W, int H, int stride, size_t rows, size_t rows_
                              const dgr_seed_tensor* tensors, const float* color_obs, const float* depth_obs,
                              const float* viewmatrix, float inv_fx, float inv_fy, float cx, float cy, float pix,
                              hipStream_t stream);
-// keyframe overlap scores (keyframe_overlap.hip; include/dgr_hip.h: dgr_keyframe_overlap): the candidates are seed.hip's grid.
+// keyframe overlap scores (keyframe_overlap.hip; include/dgr_hip.h: dgr_keyframe_overlap): the candidates are seed.hip's grid (candidate_grid.h).
 // One launch, or two with more than one block of candidates per keyframe; `scratch`: keyframe_overlap_scratch_bytes() bytes
 struct KeyframeOverlapArgs {
     int W, H, stride, K;

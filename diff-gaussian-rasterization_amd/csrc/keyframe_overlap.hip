@@ -1,5 +1,5 @@
 // keyframe_overlap.hip -- keyframe overlap scores for covisibility selection (include/dgr_hip.h: dgr_keyframe_overlap): the
-// candidate pixels of the current frame (seed.hip's stride grid) are unprojected with the measured depth, taken into every stored
+// candidate pixels of the current frame (the stride grid of candidate_grid.h, seed.hip's) are unprojected with the measured depth, taken into every stored
 // keyframe and counted where they land inside its image (and, with the keyframes' depths, where that depth agrees).
 //
 // count : one workgroup per (keyframe, block of 2048 candidates).  Threads 0..11 form the relative transform current camera ->
@@ -11,7 +11,9 @@
 // No atomics, nothing read on the host.
 #include <hip/hip_runtime.h>
 
+#include "candidate_grid.h"
 #include "kernels.h"
+#include "plan.h"
 
 namespace dgr {
 namespace {
@@ -58,8 +60,8 @@ __global__ void __launch_bounds__(THREADS) overlap_count_kernel(KeyframeOverlapA
         const size_t c = c0 + threadIdx.x;
         bool valid = false, inside = false, visible = false;
         if (c < end) {
-            const unsigned cy = (unsigned)(c / (unsigned)a.wc), cx = (unsigned)(c - (size_t)cy * (unsigned)a.wc);
-            const unsigned x = cx * (unsigned)a.stride, y = cy * (unsigned)a.stride;
+            unsigned x, y;
+            candidate_pixel(c, a.wc, a.stride, x, y);
             const float d = a.depth_obs[(size_t)y * (unsigned)a.W + x];
             valid = d > a.depth_min && d < a.depth_max;  // (false on a NaN)
             const float p0 = ((float)x - a.cx) * a.inv_fx * d, p1 = ((float)y - a.cy) * a.inv_fy * d;
@@ -95,7 +97,7 @@ __global__ void __launch_bounds__(THREADS) overlap_count_kernel(KeyframeOverlapA
     if (threadIdx.x == 0) {
         int tot[3];
 #pragma unroll
-        for (int f = 0; f < 3; ++f) tot[f] = wave_tot[0][f] + wave_tot[1][f] + wave_tot[2][f] + wave_tot[3][f];
+        for (int f = 0; f < 3; ++f) tot[f] = wave_total(wave_tot, f);
         if (blocks > 1) {
             slots[blockIdx.x] = make_int4(tot[0], tot[1], tot[2], 0);
         } else {
@@ -141,8 +143,9 @@ size_t keyframe_overlap_scratch_bytes(int W, int H, int stride, int K) {
 
 hipError_t launch_keyframe_overlap(const KeyframeOverlapArgs& args, void* scratch, hipStream_t stream) {
     KeyframeOverlapArgs a = args;
-    a.candidates = seed_candidates(a.W, a.H, a.stride);
-    a.wc = (int)(((long long)a.W + a.stride - 1) / a.stride);
+    const CandidateGrid g = candidate_grid(a.W, a.H, a.stride);
+    a.candidates = g.candidates();
+    a.wc = g.wc;
     const unsigned blocks = overlap_blocks(a.candidates);
     int4* slots = static_cast<int4*>(scratch);
     launch(overlap_count_kernel, dim3((unsigned)a.K * blocks), dim3(THREADS), stream, a, blocks, slots);

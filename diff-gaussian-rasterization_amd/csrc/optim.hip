@@ -12,7 +12,7 @@
 #include <cmath>
 
 #include "kernels.h"
-#include "plan_scan.h"
+#include "plan.h"
 
 namespace dgr {
 namespace {
@@ -91,21 +91,11 @@ hipError_t launch_sparse_adam(size_t rows, int k, float* param, const float* gra
 // Positions come from the scan alone: no atomics, the output order is survivors, clones, children sample 0, children
 // sample 1, each in row order.
 //
-// plan buffer: int[16] header (0..7: the counts), int4 per block (totals, then exclusive offsets), one byte per row.
+// plan buffer (plan.h): one action byte per row.
 namespace {
 
 constexpr unsigned ACT_SURVIVE = 1u, ACT_CLONE = 2u, ACT_CHILDREN = 4u, ACT_SPLIT = 8u;
-constexpr int PLAN_HEADER_INTS = 16;
 constexpr float LOG_1P6 = 0x1.e148a2p-2f;  // logf(1.6f)
-
-__host__ __device__ inline size_t plan_blocks(size_t rows) { return (rows + 255) / 256; }
-__device__ inline int4* plan_block_table(void* plan) { return reinterpret_cast<int4*>(static_cast<int*>(plan) + PLAN_HEADER_INTS); }
-__device__ inline const int4* plan_block_table(const void* plan) {
-    return reinterpret_cast<const int4*>(static_cast<const int*>(plan) + PLAN_HEADER_INTS);
-}
-__device__ inline const unsigned char* plan_actions(const void* plan, size_t rows) {
-    return static_cast<const unsigned char*>(plan) + PLAN_HEADER_INTS * 4 + plan_blocks(rows) * 16;
-}
 
 // The per-row table, derived from the sequence clone -> split -> remove the split originals -> prune everything:
 //   the original survives unless it is split or prunable (its own opacity, its carried max_radii2D, its own scale);
@@ -138,26 +128,13 @@ __global__ void __launch_bounds__(256) densify_decide_kernel(size_t rows, const 
             act |= ACT_SPLIT;
             if (!(new_bad || __fsub_rn(m, LOG_1P6) > log_scale_prune)) act |= ACT_CHILDREN;
         }
-        static_cast<unsigned char*>(plan)[PLAN_HEADER_INTS * 4 + plan_blocks(rows) * 16 + i] = (unsigned char)act;
+        plan_flags(plan, rows)[i] = (unsigned char)act;
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        const int n = __popcll(__ballot((act >> f) & 1u));
-        if (lane == 0) wave_tot[wave][f] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int4 t;
-        t.x = wave_tot[0][0] + wave_tot[1][0] + wave_tot[2][0] + wave_tot[3][0];
-        t.y = wave_tot[0][1] + wave_tot[1][1] + wave_tot[2][1] + wave_tot[3][1];
-        t.z = wave_tot[0][2] + wave_tot[1][2] + wave_tot[2][2] + wave_tot[3][2];
-        t.w = wave_tot[0][3] + wave_tot[1][3] + wave_tot[2][3] + wave_tot[3][3];
-        plan_block_table(plan)[blockIdx.x] = t;
-    }
+    const int4 t = block_flag_totals(act, wave_tot);
+    if (threadIdx.x == 0) plan_block_table(plan)[blockIdx.x] = t;
 }
 
-// One workgroup: exclusive scan of the block totals in place (plan_scan.h); then the counts.
+// One workgroup: exclusive scan of the block totals in place (plan.h); then the counts.
 __global__ void __launch_bounds__(256) densify_scan_kernel(size_t blocks, void* plan, int* __restrict__ counts) {
     __shared__ int4 wave_sum[4];
     const int4 carry = scan_block_totals(plan_block_table(plan), blocks, wave_sum);
@@ -200,14 +177,7 @@ __device__ inline float child_offset(const float* __restrict__ q4, const float* 
     return 2.0f * (x * z - r * y) * v0 + 2.0f * (y * z + r * x) * v1 + (1.0f - 2.0f * (x * x + y * y)) * v2;
 }
 
-// The tensors of one apply launch, and how they are dealt to workgroups: group g (blockIdx.y) moves tensors begin[g] ..
-// begin[g + 1] - 1 of its row block.  A wide tensor is a group of its own; narrow ones (a [P, 1] opacity, the accumulators)
-// share one, so that the ranks are recomputed once for all of them and no workgroup is launched for 256 floats.
-struct DensifyTable {
-    dgr_densify_tensor t[DGR_DENSIFY_MAX_TENSORS];
-    unsigned char begin[DGR_DENSIFY_MAX_TENSORS + 1];
-};
-constexpr int GROUP_STEPS = 12;  // elements per thread and group (a [P, 48] tensor as float4: 12)
+using DensifyTable = TensorTable<dgr_densify_tensor, DGR_DENSIFY_MAX_TENSORS>;  // (plan.h; a tensor's cost: elements per thread)
 
 __device__ inline float shifted(float v) { return __fsub_rn(v, LOG_1P6); }
 __device__ inline float4 shifted(float4 v) { return make_float4(shifted(v.x), shifted(v.y), shifted(v.z), shifted(v.w)); }
@@ -307,7 +277,7 @@ __global__ void __launch_bounds__(256) densify_apply_kernel(size_t rows, size_t 
     __shared__ int wave_tot[4][3];
     const size_t base = (size_t)blockIdx.x * 256;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned act = base + threadIdx.x < rows ? plan_actions(plan, rows)[base + threadIdx.x] : 0u;
+    const unsigned act = base + threadIdx.x < rows ? plan_flags(plan, rows)[base + threadIdx.x] : 0u;
     int rank[3];
 #pragma unroll
     for (int f = 0; f < 3; ++f) {
@@ -348,7 +318,7 @@ __global__ void __launch_bounds__(256) densify_apply_kernel(size_t rows, size_t 
 
 }  // namespace
 
-size_t densify_plan_bytes(size_t rows) { return PLAN_HEADER_INTS * 4 + plan_blocks(rows) * 16 + ((rows + 15) & ~(size_t)15); }
+size_t densify_plan_bytes(size_t rows) { return plan_bytes(rows); }
 
 hipError_t launch_densify_plan(size_t rows, const float* grad_accum, const float* denom, const float* max_radii2D,
                                const float* opacity_raw, const float* scaling_raw, float grad_threshold,
@@ -371,17 +341,7 @@ hipError_t launch_densify_apply(size_t rows, size_t rows_out, const void* plan, 
                                 unsigned long long seed, hipStream_t stream) {
     if (rows == 0 || rows_out == 0) return hipSuccess;
     DensifyTable table = {};
-    int groups = 0, steps = 0;
-    for (int i = 0; i < n; ++i) {
-        table.t[i] = tensors[i];
-        const int cost = tensors[i].k % 4 == 0 ? tensors[i].k / 4 : tensors[i].k;
-        if (i == 0 || steps + cost > GROUP_STEPS) {
-            table.begin[groups++] = (unsigned char)i;
-            steps = 0;
-        }
-        steps += cost;
-    }
-    table.begin[groups] = (unsigned char)n;
+    const int groups = deal_tensors(table, tensors, n, [](const dgr_densify_tensor& t) { return t.k % 4 == 0 ? t.k / 4 : t.k; });
     launch(densify_apply_kernel, dim3((unsigned)plan_blocks(rows), (unsigned)groups), dim3(256), stream, rows, rows_out, plan,
            table, scaling_raw, rotation_raw, noise, seed);
     return hipGetLastError();

@@ -7,40 +7,21 @@
 // the flag bytes (ballot + mbcnt) and write their rows behind the old ones.  Positions come from the scan alone: no atomics,
 // new rows in row-major pixel order.
 //
-// plan buffer: int[16] header (0..7: the counts), int4 per block (totals, then exclusive offsets), one byte per candidate.
+// plan buffer (plan.h): one flag byte per candidate (candidate_grid.h).
 #include <hip/hip_runtime.h>
 
+#include "candidate_grid.h"
 #include "kernels.h"
-#include "plan_scan.h"
+#include "plan.h"
 
 namespace dgr {
 namespace {
 
 constexpr unsigned SEED_SELECT = 1u, SEED_VALID = 2u, SEED_UNSEEN = 4u, SEED_INFRONT = 8u;
-constexpr int PLAN_HEADER_INTS = 16;
 constexpr float INV_C0 = (float)(1.0 / 0.28209479177387814);  // 1 / SH_C0, rounded once
 
-struct SeedGrid {  // the candidates: pixel (cx * stride, cy * stride), cx < wc, cy < hc, numbered cy * wc + cx
-    int W, H, stride, wc, hc;
-    __host__ __device__ size_t candidates() const { return (size_t)wc * (size_t)hc; }
-};
-__host__ __device__ inline SeedGrid seed_grid(int W, int H, int stride) {
-    return SeedGrid{W, H, stride, (int)(((long long)W + stride - 1) / stride), (int)(((long long)H + stride - 1) / stride)};
-}
-__host__ __device__ inline size_t plan_blocks(size_t n) { return (n + 255) / 256; }
-__device__ inline int4* plan_block_table(void* plan) { return reinterpret_cast<int4*>(static_cast<int*>(plan) + PLAN_HEADER_INTS); }
-__device__ inline const int4* plan_block_table(const void* plan) {
-    return reinterpret_cast<const int4*>(static_cast<const int*>(plan) + PLAN_HEADER_INTS);
-}
-__device__ inline unsigned char* plan_flags(void* plan, size_t n) {
-    return static_cast<unsigned char*>(plan) + PLAN_HEADER_INTS * 4 + plan_blocks(n) * 16;
-}
-__device__ inline const unsigned char* plan_flags(const void* plan, size_t n) {
-    return static_cast<const unsigned char*>(plan) + PLAN_HEADER_INTS * 4 + plan_blocks(n) * 16;
-}
-
 // Every comparison is false on a NaN: a NaN depth_obs is not valid, a NaN opacity_map is not unseen, a NaN depth is not in front.
-__global__ void __launch_bounds__(256) seed_decide_kernel(SeedGrid g, const float* __restrict__ depth_obs,
+__global__ void __launch_bounds__(256) seed_decide_kernel(CandidateGrid g, const float* __restrict__ depth_obs,
                                                           const float* __restrict__ opacity_map,
                                                           const float* __restrict__ depth, float depth_min, float depth_max,
                                                           float silhouette_threshold, float depth_error_min,
@@ -51,7 +32,8 @@ __global__ void __launch_bounds__(256) seed_decide_kernel(SeedGrid g, const floa
     if (depth_error_min_dev) depth_error_min = *depth_error_min_dev;
     unsigned flags = 0;
     if (c < n) {
-        const unsigned cy = (unsigned)(c / (unsigned)g.wc), cx = (unsigned)(c - (size_t)cy * (unsigned)g.wc);
+        unsigned cx, cy;
+        candidate_cell(c, g.wc, cx, cy);
         const size_t pix = (size_t)cy * (unsigned)g.stride * (unsigned)g.W + (size_t)cx * (unsigned)g.stride;
         const float d_obs = depth_obs[pix];
         const bool valid = d_obs > depth_min && d_obs < depth_max;
@@ -66,37 +48,18 @@ __global__ void __launch_bounds__(256) seed_decide_kernel(SeedGrid g, const floa
                 (valid && infront ? SEED_INFRONT : 0u);
         plan_flags(plan, n)[c] = (unsigned char)flags;
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        const int cnt = __popcll(__ballot((flags >> f) & 1u));
-        if (lane == 0) wave_tot[wave][f] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int4 t;
-        t.x = wave_tot[0][0] + wave_tot[1][0] + wave_tot[2][0] + wave_tot[3][0];
-        t.y = wave_tot[0][1] + wave_tot[1][1] + wave_tot[2][1] + wave_tot[3][1];
-        t.z = wave_tot[0][2] + wave_tot[1][2] + wave_tot[2][2] + wave_tot[3][2];
-        t.w = wave_tot[0][3] + wave_tot[1][3] + wave_tot[2][3] + wave_tot[3][3];
-        plan_block_table(plan)[blockIdx.x] = t;
-    }
+    const int4 t = block_flag_totals(flags, wave_tot);
+    if (threadIdx.x == 0) plan_block_table(plan)[blockIdx.x] = t;
 }
 
-// One workgroup: exclusive scan of the block totals in place (plan_scan.h); then the counts.
+// One workgroup: exclusive scan of the block totals in place (plan.h); then the counts.
 __global__ void __launch_bounds__(256) seed_scan_kernel(size_t blocks, int rows, void* plan, int* __restrict__ counts) {
     __shared__ int4 wave_sum[4];
     const int4 carry = scan_block_totals(plan_block_table(plan), blocks, wave_sum);
     write_counts8(rows + carry.x, carry.x, carry.y, carry.z, carry.w, plan, counts);
 }
 
-// The tensors of one apply launch and how they are dealt to workgroups (as densify's table): group g (blockIdx.y) moves
-// tensors begin[g] .. begin[g + 1] - 1 of its block.
-struct SeedTable {
-    dgr_seed_tensor t[DGR_SEED_MAX_TENSORS];
-    unsigned char begin[DGR_SEED_MAX_TENSORS + 1];
-};
-constexpr int GROUP_STEPS = 12;  // float4 per thread and group in the copy of the old rows (a [P, 48] tensor: 12)
+using SeedTable = TensorTable<dgr_seed_tensor, DGR_SEED_MAX_TENSORS>;  // (plan.h; a tensor's cost: float4 per thread in the copy)
 
 struct SeedCamera {  // what XYZ, LOG_SCALE and RGB_DC read
     const float* color_obs;
@@ -135,7 +98,7 @@ __device__ inline void copy_block(const float* __restrict__ src, float* __restri
 // element e = row * k + column written by thread e % 256: runs of consecutive addresses.  sel_*: the block's selected
 // candidates in rank order (pixel x, y and the observed depth).
 __device__ inline void fill_block(float* __restrict__ dst, unsigned n_rows, const dgr_seed_tensor& d, const SeedCamera& cam,
-                                  const SeedGrid& g, const int* sel_x, const int* sel_y, const float* sel_d) {
+                                  const CandidateGrid& g, const int* sel_x, const int* sel_y, const float* sel_d) {
     const unsigned k = (unsigned)d.k, n = n_rows * k;
     const int mode = d.mode;
     if (mode == DGR_SEED_CONST) {  // one value over a contiguous run: aligned float4 stores between a scalar head and tail
@@ -186,11 +149,11 @@ __device__ inline void fill_block(float* __restrict__ dst, unsigned n_rows, cons
 
 // grid (copy blocks + candidate blocks, tensor groups).  Nothing is written past rows_out (the caller's allocation), whatever
 // the plan says.
-__global__ void __launch_bounds__(256) seed_apply_kernel(SeedGrid g, size_t rows, size_t rows_out, const void* __restrict__ plan,
+__global__ void __launch_bounds__(256) seed_apply_kernel(CandidateGrid g, size_t rows, size_t rows_out, const void* __restrict__ plan,
                                                          SeedTable table, SeedCamera cam) {
     __shared__ int sel_x[256], sel_y[256];
     __shared__ float sel_d[256];
-    __shared__ int wave_tot[4];
+    __shared__ int wave_tot[4][1];
     const size_t copy_blocks = plan_blocks(rows);
     if (blockIdx.x < copy_blocks) {  // (uniform over the workgroup)
         const size_t base = (size_t)blockIdx.x * 256;
@@ -209,13 +172,14 @@ __global__ void __launch_bounds__(256) seed_apply_kernel(SeedGrid g, size_t rows
     const bool select = cand < n && (plan_flags(plan, n)[cand] & SEED_SELECT) != 0u;
     const unsigned long long m = __ballot(select);
     int rank = lane_rank(m);
-    if (lane == 0) wave_tot[wave] = __popcll(m);
+    if (lane == 0) wave_tot[wave][0] = __popcll(m);
     __syncthreads();
-    for (int w = 0; w < wave; ++w) rank += wave_tot[w];
-    const unsigned n_sel = (unsigned)(wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3]);
+    for (int w = 0; w < wave; ++w) rank += wave_tot[w][0];
+    const unsigned n_sel = (unsigned)wave_total(wave_tot, 0);
     if (select) {
-        const unsigned cy = (unsigned)(cand / (unsigned)g.wc), cx = (unsigned)(cand - (size_t)cy * (unsigned)g.wc);
-        const int x = (int)(cx * (unsigned)g.stride), y = (int)(cy * (unsigned)g.stride);
+        unsigned ux, uy;
+        candidate_pixel(cand, g.wc, g.stride, ux, uy);
+        const int x = (int)ux, y = (int)uy;
         sel_x[rank] = x;
         sel_y[rank] = y;
         sel_d[rank] = cam.depth_obs[(size_t)y * (unsigned)g.W + (unsigned)x];
@@ -233,16 +197,15 @@ __global__ void __launch_bounds__(256) seed_apply_kernel(SeedGrid g, size_t rows
 }  // namespace
 
 size_t seed_plan_bytes(int W, int H, int stride) {
-    const size_t n = seed_grid(W, H, stride).candidates();
-    return PLAN_HEADER_INTS * 4 + plan_blocks(n) * 16 + ((n + 15) & ~(size_t)15);
+    return plan_bytes(candidate_grid(W, H, stride).candidates());
 }
 
-size_t seed_candidates(int W, int H, int stride) { return seed_grid(W, H, stride).candidates(); }
+size_t seed_candidates(int W, int H, int stride) { return candidate_grid(W, H, stride).candidates(); }
 
 hipError_t launch_seed_plan(int W, int H, int stride, const float* depth_obs, const float* opacity_map, const float* depth,
                             float depth_min, float depth_max, float silhouette_threshold, float depth_error_min,
                             const float* depth_error_min_dev, size_t rows, void* plan, int* counts, hipStream_t stream) {
-    const SeedGrid g = seed_grid(W, H, stride);
+    const CandidateGrid g = candidate_grid(W, H, stride);
     const size_t blocks = plan_blocks(g.candidates());
     launch(seed_decide_kernel, dim3((unsigned)blocks), dim3(256), stream, g, depth_obs, opacity_map, depth, depth_min, depth_max,
            silhouette_threshold, depth_error_min, depth_error_min_dev, plan);
@@ -257,19 +220,9 @@ hipError_t launch_seed_apply(int W, int H, int stride, size_t rows, size_t rows_
                              const float* viewmatrix, float inv_fx, float inv_fy, float cx, float cy, float pix,
                              hipStream_t stream) {
     if (rows_out == 0) return hipSuccess;
-    const SeedGrid g = seed_grid(W, H, stride);
+    const CandidateGrid g = candidate_grid(W, H, stride);
     SeedTable table = {};
-    int groups = 0, steps = 0;
-    for (int i = 0; i < n; ++i) {
-        table.t[i] = tensors[i];
-        const int cost = (tensors[i].k + 3) / 4;
-        if (i == 0 || steps + cost > GROUP_STEPS) {
-            table.begin[groups++] = (unsigned char)i;
-            steps = 0;
-        }
-        steps += cost;
-    }
-    table.begin[groups] = (unsigned char)n;
+    const int groups = deal_tensors(table, tensors, n, [](const dgr_seed_tensor& t) { return (t.k + 3) / 4; });
     const size_t blocks = plan_blocks(rows) + (rows_out > rows ? plan_blocks(g.candidates()) : 0);
     const SeedCamera cam = {color_obs, depth_obs, viewmatrix, inv_fx, inv_fy, cx, cy, pix};
     launch(seed_apply_kernel, dim3((unsigned)blocks, (unsigned)groups), dim3(256), stream, g, rows, rows_out, plan, table, cam);

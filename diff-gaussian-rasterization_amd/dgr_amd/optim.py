@@ -56,10 +56,101 @@ def densify_thresholds(grad_threshold, extent, percent_dense=0.01, min_opacity=0
             float(max_screen_size) if sized else inf)
 
 
-def _rows_tensor(t, P, what, who="densify_and_prune"):
+def _rows_tensor(t, P, what, who):
     if not t.is_cuda or t.dtype != torch.float32 or t.dim() < 1 or t.shape[0] != P:
         raise RuntimeError(f"{who}: {what} must be a float32 GPU tensor with {P} rows")
     return t.detach().contiguous()
+
+
+class _ResizeStep:
+    """What the two steps that change P (`densify_and_prune`, `seed_from_frame`; `who` in the messages) share: the checks of the
+    model, the plan's buffers and the one host read, the table of (src, dst, k, mode, value) with every leaf followed by its two
+    Adam moments, the apply launches and the hand-over to the optimiser.  Called in the order the refusals are reported in."""
+    def __init__(self, who, params, optimizer, roles, known_roles):
+        self.who, self.params, self.optimizer = who, params, optimizer
+        self.roles = dict(known_roles, **(roles or {}))
+        missing = [r for r in DEFAULT_ROLES if self.roles[r] not in params]
+        if missing:
+            raise KeyError(f"{who}: params has no entry for {missing} (roles = {self.roles})")
+        self.table, self.out, self.moments = [], {}, {}
+
+    def locate(self):  # P and the device, from the xyz leaf
+        xyz = self.params[self.roles["xyz"]]
+        if not xyz.is_cuda:
+            raise RuntimeError(f"{self.who}: the parameters must live on the GPU")
+        self.P, self.dev = xyz.shape[0], xyz.device
+        return self.P
+
+    def stream(self, lib):
+        st = _capi.stream_handle(self.dev.index)
+        if lib.dgr_stream_is_capturing(st):
+            raise RuntimeError(f"{self.who} changes the number of Gaussians and reads the new count on the host: it cannot be "
+                               "recorded into a hipGraph (call it between replays)")
+        return st
+
+    def check_leaves(self):  # self.src: the leaves, detached and contiguous (the opacity leaf's shape is the caller's to check)
+        P, roles = self.P, self.roles
+        self.src = {name: _rows_tensor(t, P, f"params[{name!r}]", self.who) for name, t in self.params.items()}
+        for role, shape in (("xyz", (P, 3)), ("scaling", (P, 3)), ("rotation", (P, 4))):
+            if tuple(self.src[roles[role]].shape) != shape:
+                raise RuntimeError(f"{self.who}: the {role} leaf must be [P, {shape[1]}]")
+        return self.src
+
+    def check_accumulators(self, xyz_gradient_accum, denom, max_radii2D, required=()):  # self.acc: name -> tensor or None
+        self.acc = {"xyz_gradient_accum": xyz_gradient_accum, "denom": denom, "max_radii2D": max_radii2D}
+        for name, t in self.acc.items():
+            if t is None and name not in required:
+                continue
+            if t is None or t.numel() != self.P:
+                raise RuntimeError(f"{self.who}: {name} must have P elements")
+            self.acc[name] = _rows_tensor(t, self.P, name, self.who)
+        return self.acc
+
+    def plan(self, nbytes, call, counts_type):  # `call(plan pointer, counts pointer)`: the step's dgr_*_plan
+        self.plan_buffer = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        counts_dev = torch.empty(8, dtype=torch.int32, device=self.dev)
+        if call(self.plan_buffer.data_ptr(), counts_dev.data_ptr()):
+            raise RuntimeError(_capi.last_error())
+        return counts_type(*counts_dev.tolist()[:5])  # the call's one host synchronisation
+
+    def add(self, src, tail, k, mode, value=None):
+        # one row of the table: a new [P_new, *tail] tensor (k per row) filled from `src` (or None) as `mode` (and `value`) say
+        dst = torch.empty((self.P_new,) + tail, dtype=torch.float32, device=self.dev)
+        self.table.append((src, dst, k, mode, value))
+        return dst
+
+    def add_leaves(self, P_new, fields_of, moment_fields):
+        # every leaf as `fields_of(name)` = (mode[, value]) says, each followed by its two moments where the optimiser has them
+        self.P_new = P_new
+        add, state_of = self.add, self.optimizer.state if self.optimizer is not None else {}
+        for name, t in self.src.items():
+            tail = tuple(t.shape[1:])
+            k = max(math.prod(tail), 1)
+            self.out[name] = add(t, tail, k, *fields_of(name))
+            state = state_of.get(self.params[name])
+            if state is not None:
+                self.moments[name] = tuple(add(m.contiguous(), tail, k, *moment_fields) for m in state)
+
+    def apply(self, desc_type, max_tensors, call):
+        # `call(n, descriptors)`: the step's dgr_*_apply, once per 24 rows of the table (one launch in all for 3DGS's model)
+        for i in range(0, len(self.table), max_tensors):
+            part = self.table[i:i + max_tensors]
+            descs = (desc_type * len(part))()
+            for d, (s, t, k, mode, value) in zip(descs, part):
+                d.src, d.dst, d.k, d.mode = _capi.ptr(s), t.data_ptr(), k, mode
+                if value is not None:
+                    d.value = value
+            if call(len(part), descs):
+                raise RuntimeError(_capi.last_error())
+
+    def finish(self):  # the new leaves, `requires_grad` as the old ones', and the optimiser pointed at them
+        params, out = self.params, self.out
+        for name, t in params.items():
+            out[name].requires_grad_(t.requires_grad)
+        if self.optimizer is not None:
+            self.optimizer.replace_params({params[name]: out[name] for name in params},
+                                          {params[name]: self.moments[name] for name in self.moments})
+        return out
 
 
 @torch.no_grad()
@@ -79,79 +170,31 @@ def densify_and_prune(params, optimizer, xyz_gradient_accum, denom, max_radii2D,
     preserved, the three accumulators as zeros of the new length.  One host synchronisation (the read of the counts), so
     the call cannot be recorded into a hipGraph."""
     lib = _capi.load()
-    roles = dict(DEFAULT_ROLES, **(roles or {}))
-    missing = [r for r in DEFAULT_ROLES if roles[r] not in params]
-    if missing:
-        raise KeyError(f"densify_and_prune: params has no entry for {missing} (roles = {roles})")
-    xyz = params[roles["xyz"]]
-    if not xyz.is_cuda:
-        raise RuntimeError("densify_and_prune: the parameters must live on the GPU")
-    P, dev = xyz.shape[0], xyz.device
-    with _capi.on_device(dev):
-        st = _capi.stream_handle(dev.index)
-        if lib.dgr_stream_is_capturing(st):
-            raise RuntimeError("densify_and_prune changes the number of Gaussians and reads the new count on the host: it cannot "
-                               "be recorded into a hipGraph (call it between replays)")
-        src = {name: _rows_tensor(t, P, f"params[{name!r}]") for name, t in params.items()}
-        for role, shape in (("xyz", (P, 3)), ("scaling", (P, 3)), ("rotation", (P, 4))):
-            if tuple(src[roles[role]].shape) != shape:
-                raise RuntimeError(f"densify_and_prune: the {role} leaf must be [P, {shape[1]}]")
+    step = _ResizeStep("densify_and_prune", params, optimizer, roles, DEFAULT_ROLES)
+    roles, P = step.roles, step.locate()
+    with _capi.on_device(step.dev):
+        st, src = step.stream(lib), step.check_leaves()
         if src[roles["opacity"]].numel() != P:
             raise RuntimeError("densify_and_prune: the opacity leaf must be [P] or [P, 1]")
-        acc = {"xyz_gradient_accum": xyz_gradient_accum, "denom": denom, "max_radii2D": max_radii2D}
-        for name, t in acc.items():
-            if t is None and name == "max_radii2D":
-                continue
-            if t is None or t.numel() != P:
-                raise RuntimeError(f"densify_and_prune: {name} must have P elements")
-            acc[name] = _rows_tensor(t, P, name)
+        acc = step.check_accumulators(xyz_gradient_accum, denom, max_radii2D, required=("xyz_gradient_accum", "denom"))
         if noise is not None:
             if tuple(noise.shape) != (P, 2, 3):
                 raise RuntimeError("densify_and_prune: noise must be [P, 2, 3]")
-            noise = _rows_tensor(noise, P, "noise")
+            noise = _rows_tensor(noise, P, "noise", "densify_and_prune")
         thresholds = densify_thresholds(grad_threshold, extent, percent_dense, min_opacity, max_screen_size)
 
-        plan = torch.empty(lib.dgr_densify_plan_bytes(P), dtype=torch.uint8, device=dev)
-        counts_dev = torch.empty(8, dtype=torch.int32, device=dev)
         scaling, rotation = src[roles["scaling"]], src[roles["rotation"]]
-        rc = lib.dgr_densify_plan(st, P, _capi.ptr(acc["xyz_gradient_accum"]), _capi.ptr(acc["denom"]),
-                                  _capi.ptr(acc["max_radii2D"]), _capi.ptr(src[roles["opacity"]]), _capi.ptr(scaling),
-                                  *thresholds, plan.data_ptr(), counts_dev.data_ptr())
-        if rc:
-            raise RuntimeError(_capi.last_error())
-        counts = DensifyCounts(*counts_dev.tolist()[:5])  # the call's one host synchronisation
-        P_new = counts.rows
+        counts = step.plan(lib.dgr_densify_plan_bytes(P), lambda plan, counts_dev: lib.dgr_densify_plan(
+            st, P, _capi.ptr(acc["xyz_gradient_accum"]), _capi.ptr(acc["denom"]), _capi.ptr(acc["max_radii2D"]),
+            _capi.ptr(src[roles["opacity"]]), _capi.ptr(scaling), *thresholds, plan, counts_dev), DensifyCounts)
 
-        new = lambda t: torch.empty((P_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)  # noqa: E731
         mode_of = {roles["xyz"]: _capi.DENSIFY_XYZ, roles["scaling"]: _capi.DENSIFY_LOG_SCALE}
-        table, out, moments = [], {}, {}
-        for name, t in src.items():
-            out[name] = new(t)
-            table.append((t, out[name], mode_of.get(name, _capi.DENSIFY_COPY)))
-            state = optimizer.state.get(params[name]) if optimizer is not None else None
-            if state is not None:
-                moments[name] = (new(t), new(t))
-                table += [(m.contiguous(), d, _capi.DENSIFY_ZERO_NEW) for m, d in zip(state, moments[name])]
-        zeroed = []
-        for name, t in acc.items():
-            zeroed.append(torch.empty((P_new,) + tuple(t.shape[1:] if t is not None else ()), dtype=torch.float32, device=dev))
-            table.append((None, zeroed[-1], _capi.DENSIFY_ZERO))
-        for i in range(0, len(table), _capi.DENSIFY_MAX_TENSORS):  # one launch per 24 tensors: one in all for 3DGS's model
-            part = table[i:i + _capi.DENSIFY_MAX_TENSORS]
-            descs = (_capi.DensifyTensor * len(part))()
-            for d, (s, t, mode) in zip(descs, part):
-                d.src, d.dst, d.mode = _capi.ptr(s), _capi.ptr(t), mode
-                d.k = max(math.prod(t.shape[1:]), 1)
-            rc = lib.dgr_densify_apply(st, P, P_new, plan.data_ptr(), len(part), descs, _capi.ptr(scaling), _capi.ptr(rotation),
-                                       _capi.ptr(noise), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)))
-            if rc:
-                raise RuntimeError(_capi.last_error())
-    for name, t in params.items():
-        out[name].requires_grad_(t.requires_grad)
-    if optimizer is not None:
-        optimizer.replace_params({params[name]: out[name] for name in params},
-                                 {params[name]: moments[name] for name in moments})
-    return out, zeroed[0], zeroed[1], zeroed[2], counts
+        step.add_leaves(counts.rows, lambda name: (mode_of.get(name, _capi.DENSIFY_COPY),), (_capi.DENSIFY_ZERO_NEW,))
+        zeroed = [step.add(None, tuple(t.shape[1:]) if t is not None else (), 1, _capi.DENSIFY_ZERO) for t in acc.values()]
+        step.apply(_capi.DensifyTensor, _capi.DENSIFY_MAX_TENSORS, lambda n, descs: lib.dgr_densify_apply(
+            st, P, counts.rows, step.plan_buffer.data_ptr(), n, descs, _capi.ptr(scaling), _capi.ptr(rotation), _capi.ptr(noise),
+            ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1))))
+    return step.finish(), zeroed[0], zeroed[1], zeroed[2], counts
 
 
 SeedCounts = collections.namedtuple("SeedCounts", "rows new valid unseen infront")
@@ -205,25 +248,18 @@ def seed_from_frame(params, optimizer, color_obs, depth_obs, viewmatrix, fx, fy,
     preserved on every leaf.  When no pixel is selected the inputs are returned as they are and the optimiser is untouched.  One
     host synchronisation (the read of the counts), so the call cannot be recorded into a hipGraph."""
     lib = _capi.load()
-    roles = dict(SEED_ROLES, **(roles or {}))
-    missing = [r for r in DEFAULT_ROLES if roles[r] not in params]
-    if missing:
-        raise KeyError(f"seed_from_frame: params has no entry for {missing} (roles = {roles})")
+    step = _ResizeStep("seed_from_frame", params, optimizer, roles, SEED_ROLES)
+    roles = step.roles
     fill = dict(fill or {})
     unknown = [name for name in fill if name not in params or name in roles.values()]
     if unknown:
         raise KeyError(f"seed_from_frame: fill names {unknown}, which are not leaves without a role")
-    xyz = params[roles["xyz"]]
-    if not xyz.is_cuda:
-        raise RuntimeError("seed_from_frame: the parameters must live on the GPU")
+    P = step.locate()
     if int(stride) != stride or stride < 1:
         raise ValueError("seed_from_frame: stride must be an integer >= 1")
-    P, dev, stride = xyz.shape[0], xyz.device, int(stride)
-    with _capi.on_device(dev):
-        st = _capi.stream_handle(dev.index)
-        if lib.dgr_stream_is_capturing(st):
-            raise RuntimeError("seed_from_frame changes the number of Gaussians and reads the new count on the host: it cannot be "
-                               "recorded into a hipGraph (call it between replays)")
+    stride = int(stride)
+    with _capi.on_device(step.dev):
+        st = step.stream(lib)
         if depth_obs.dim() < 2:
             raise RuntimeError("seed_from_frame: depth_obs must be [H, W]")
         H, W = depth_obs.shape[-2:]
@@ -244,68 +280,32 @@ def seed_from_frame(params, optimizer, color_obs, depth_obs, viewmatrix, fx, fy,
         plan_bytes = lib.dgr_seed_plan_bytes(W, H, stride)
         if plan_bytes == 0:
             raise RuntimeError(f"seed_from_frame: a {W} x {H} frame at stride {stride} is refused (dgr_seed_plan_bytes)")
-        src = {name: _rows_tensor(t, P, f"params[{name!r}]", "seed_from_frame") for name, t in params.items()}
-        for role, shape in (("xyz", (P, 3)), ("scaling", (P, 3)), ("rotation", (P, 4))):
-            if tuple(src[roles[role]].shape) != shape:
-                raise RuntimeError(f"seed_from_frame: the {role} leaf must be [P, {shape[1]}]")
+        src = step.check_leaves()
         if math.prod(src[roles["opacity"]].shape[1:]) != 1:
             raise RuntimeError("seed_from_frame: the opacity leaf must be [P] or [P, 1]")
         if has_dc and math.prod(src[roles["f_dc"]].shape[1:]) != 3:
             raise RuntimeError("seed_from_frame: the f_dc leaf must be [P, 3] or [P, 1, 3]")
-        acc = {"xyz_gradient_accum": xyz_gradient_accum, "denom": denom, "max_radii2D": max_radii2D}
-        for name, t in acc.items():
-            if t is not None:
-                if t.numel() != P:
-                    raise RuntimeError(f"seed_from_frame: {name} must have P elements")
-                acc[name] = _rows_tensor(t, P, name, "seed_from_frame")
+        step.check_accumulators(xyz_gradient_accum, denom, max_radii2D)
         depth_min, depth_max, sil, err_min, pix, opacity_raw = seed_constants(
             fx, fy, silhouette_threshold=silhouette_threshold, depth_error_min=depth_error_min, depth_range=depth_range,
             stride=stride, init_opacity=init_opacity, scale_factor=scale_factor)
 
-        plan = torch.empty(plan_bytes, dtype=torch.uint8, device=dev)
-        counts_dev = torch.empty(8, dtype=torch.int32, device=dev)
-        rc = lib.dgr_seed_plan(st, W, H, stride, depth_obs.data_ptr(), _capi.ptr(opacity_map), _capi.ptr(depth), depth_min,
-                               depth_max, sil, err_min, _capi.ptr(error_dev), P, plan.data_ptr(), counts_dev.data_ptr())
-        if rc:
-            raise RuntimeError(_capi.last_error())
-        counts = SeedCounts(*counts_dev.tolist()[:5])  # the call's one host synchronisation
+        counts = step.plan(plan_bytes, lambda plan, counts_dev: lib.dgr_seed_plan(
+            st, W, H, stride, depth_obs.data_ptr(), _capi.ptr(opacity_map), _capi.ptr(depth), depth_min, depth_max, sil, err_min,
+            _capi.ptr(error_dev), P, plan, counts_dev), SeedCounts)
         if counts.new == 0:
             return params, xyz_gradient_accum, denom, max_radii2D, counts
-        P_new = counts.rows
 
-        new = lambda t: torch.empty((P_new,) + tuple(t.shape[1:]), dtype=torch.float32, device=dev)  # noqa: E731
         mode_of = {roles["xyz"]: (_capi.SEED_XYZ, 0.0), roles["scaling"]: (_capi.SEED_LOG_SCALE, 0.0),
                    roles["rotation"]: (_capi.SEED_QUAT_IDENTITY, 0.0), roles["opacity"]: (_capi.SEED_CONST, opacity_raw),
                    roles["f_dc"]: (_capi.SEED_RGB_DC, 0.0)}
-        table, out, moments = [], {}, {}
-        for name, t in src.items():
-            out[name] = new(t)
-            table.append((t, out[name]) + mode_of.get(name, (_capi.SEED_CONST, float(fill.get(name, 0.0)))))
-            state = optimizer.state.get(params[name]) if optimizer is not None else None
-            if state is not None:
-                moments[name] = (new(t), new(t))
-                table += [(m.contiguous(), d, _capi.SEED_CONST, 0.0) for m, d in zip(state, moments[name])]
-        grown = {}
-        for name, t in acc.items():
-            if t is not None:
-                grown[name] = new(t)
-                table.append((t, grown[name], _capi.SEED_CONST, 0.0))
-        for i in range(0, len(table), _capi.SEED_MAX_TENSORS):  # one launch per 24 tensors: one in all for 3DGS's model
-            part = table[i:i + _capi.SEED_MAX_TENSORS]
-            descs = (_capi.SeedTensor * len(part))()
-            for d, (s, t, mode, value) in zip(descs, part):
-                d.src, d.dst, d.mode, d.value = _capi.ptr(s), t.data_ptr(), mode, value
-                d.k = max(math.prod(t.shape[1:]), 1)
-            rc = lib.dgr_seed_apply(st, W, H, stride, P, P_new, plan.data_ptr(), len(part), descs, _capi.ptr(color_obs),
-                                    depth_obs.data_ptr(), viewmatrix.data_ptr(), fx, fy, cx, cy, pix)
-            if rc:
-                raise RuntimeError(_capi.last_error())
-    for name, t in params.items():
-        out[name].requires_grad_(t.requires_grad)
-    if optimizer is not None:
-        optimizer.replace_params({params[name]: out[name] for name in params},
-                                 {params[name]: moments[name] for name in moments})
-    return out, grown.get("xyz_gradient_accum"), grown.get("denom"), grown.get("max_radii2D"), counts
+        step.add_leaves(counts.rows, lambda name: mode_of.get(name) or (_capi.SEED_CONST, float(fill.get(name, 0.0))),
+                        (_capi.SEED_CONST, 0.0))
+        grown = {name: step.add(t, tuple(t.shape[1:]), 1, _capi.SEED_CONST, 0.0) for name, t in step.acc.items() if t is not None}
+        step.apply(_capi.SeedTensor, _capi.SEED_MAX_TENSORS, lambda n, descs: lib.dgr_seed_apply(
+            st, W, H, stride, P, counts.rows, step.plan_buffer.data_ptr(), n, descs, _capi.ptr(color_obs), depth_obs.data_ptr(),
+            viewmatrix.data_ptr(), fx, fy, cx, cy, pix))
+    return step.finish(), grown.get("xyz_gradient_accum"), grown.get("denom"), grown.get("max_radii2D"), counts
 
 
 class SparseAdam:

@@ -7,7 +7,7 @@ import torch
 
 import cameras
 from seed_model import seed_masks, seed_model
-from dgr_amd.optim import SparseAdam, seed_from_frame
+from dgr_amd.optim import SparseAdam, densify_and_prune, seed_from_frame
 from test_hip_densify import EXTRAS, bits_equal, leaves_of
 
 pytestmark = pytest.mark.gpu
@@ -248,6 +248,54 @@ def test_without_accumulators_or_optimizer_and_with_roles():
     assert bits_equal(out["colour"], ref["leaves"]["f_dc"])
     assert ulps(out["scaling"][50:].cpu(), ref["leaves"]["scaling_new"]).max() <= 4.0
     assert not any(p.requires_grad for p in out.values())
+
+
+def test_both_resize_steps_in_sequence_keep_the_optimizer_consistent():
+    """seed_from_frame, densify_and_prune on its output, seed_from_frame again, on one model (P = 300, the nine leaves with moments
+    and the accumulators; 37 x 23 at stride 2): what the two steps share -- the table with the moments interleaved, the hand-over
+    to the optimiser -- seen from both callers.  Nothing numerical beyond the bits of the copied rows."""
+    d, P = dev(), 300
+    L, M, A = state_of(P, 8)
+    f = frame(37, 23, 8)
+    cam = f["cam"]
+    params = {name: t.to(d).requires_grad_(name != "label") for name, t in L.items()}
+    opt = SparseAdam([{"params": [p], "lr": 1e-3} for p in params.values()])
+    for name, (m, v) in M.items():
+        opt.state[params[name]] = (m.to(d), v.to(d))
+    opt.steps = 3
+    accs = [A[name].to(d) for name in ACCS]
+
+    def seed(params, accs):
+        return seed_from_frame(params, opt, f["color_obs"].to(d), f["depth_obs"].to(d), f["view"].to(d), cam.fx, cam.fy, cam.cx,
+                               cam.cy, stride=2, fill=FILL, **dict(zip(ACCS, accs)))
+
+    def consistent(out, rows):
+        assert list(out) == list(L) and all(p.shape[0] == rows for p in out.values())
+        assert all(len(g["params"]) == 1 and g["params"][0] is out[name] for g, name in zip(opt.param_groups, L))
+        assert len(opt.state) == len(L) and opt.steps == 3
+        for name, p in out.items():
+            m, v = opt.state[p]
+            assert m.shape == p.shape and v.shape == p.shape, name
+
+    out, *accs, counts = seed(params, accs)
+    assert counts.rows == P + counts.new and counts.new > 0
+    consistent(out, counts.rows)
+    for name, t in L.items():
+        assert bits_equal(out[name][:P], t), name
+        assert bits_equal(opt.state[out[name]][0][:P], M[name][0]) and bits_equal(opt.state[out[name]][1][:P], M[name][1]), name
+    for got, name in zip(accs, ACCS):
+        assert bits_equal(got[:P], A[name]) and not got[P:].any(), name
+
+    out, *accs, counts = densify_and_prune(out, opt, *accs, grad_threshold=0.3, extent=10.0)
+    assert counts.rows == counts.survivors + counts.clones + counts.children and counts.clones > 0 and counts.children > 0
+    consistent(out, counts.rows)
+    assert all(a.shape[0] == counts.rows and not a.any() for a in accs)
+
+    rows = counts.rows
+    out, *accs, counts = seed(out, accs)
+    assert counts.rows == rows + counts.new and counts.new > 0
+    consistent(out, counts.rows)
+    assert all(a.shape[0] == counts.rows for a in accs)
 
 
 def test_two_runs_give_the_same_bits():
