@@ -264,10 +264,11 @@ hipError_t launch_preprocess_bwd_batch(const PreprocessBwdBatchArgs& b, hipStrea
 // captured hipGraph were seen to re-execute with corrupted parameters on this ROCm)
 hipError_t launch_zero_fill(void* dst, size_t bytes, hipStream_t stream);
 // fused sparse Adam (optim.hip): rows with visible[row] <= 0 are skipped entirely; visible == NULL updates every row
-// slam.hip
+// pose.hip: (quaternion, translation) -> viewmatrix, projmatrix, campos, and dL/dviewmatrix -> (dL/dq, dL/dt); one launch each
 hipError_t launch_pose_forward(const float* q, const float* t, const float* perspec, float* view, float* proj, float* campos,
                                hipStream_t stream);
 hipError_t launch_pose_backward(const float* q, const float* dview, float* dq, float* dt, hipStream_t stream);
+// l1_loss.hip: w_c mean|C - C_obs| + w_d mean|D - D_obs| (`partial`: l1_loss_partials() floats) and its two gradient images
 int l1_loss_partials();
 hipError_t launch_l1_loss_forward(long n_c, const float* c, const float* c_obs, long n_d, const float* d, const float* d_obs,
                                   float w_c, float w_d, float* partial, float* loss, hipStream_t stream);

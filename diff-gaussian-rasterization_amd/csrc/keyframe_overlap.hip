@@ -11,6 +11,7 @@
 // No atomics, nothing read on the host.
 #include <hip/hip_runtime.h>
 
+#include "block_sum.h"
 #include "candidate_grid.h"
 #include "kernels.h"
 #include "plan.h"
@@ -121,11 +122,9 @@ __global__ void __launch_bounds__(THREADS) overlap_finish_kernel(KeyframeOverlap
         n_inside += s.y;
         n_visible += s.z;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        n_valid += __shfl_xor(n_valid, off, 64);
-        n_inside += __shfl_xor(n_inside, off, 64);
-        n_visible += __shfl_xor(n_visible, off, 64);
-    }
+    n_valid = wave_sum(n_valid);
+    n_inside = wave_sum(n_inside);
+    n_visible = wave_sum(n_visible);
     if (lane == 0) {
         a.inside[k] = n_inside;
         a.visible[k] = n_visible;

@@ -20,6 +20,7 @@
 #include <cfloat>
 
 #include "block_scan.h"
+#include "block_sum.h"
 #include "kernels.h"
 
 namespace dgr {
@@ -35,8 +36,6 @@ constexpr long PIXELS_PER_BLOCK = 1024;
 constexpr int STACK_BLOCKS = 2048, MIN_BLOCKS = 256;
 constexpr int HEADER_FLOATS = 16;              // [0] w_d / N_d, [1] w_c / N_c, [2] free for the caller's loss; rest reserved
 constexpr int SLOT_WORDS = 8;                  // a workgroup's partials: S_d hi, lo, S_c hi, lo, |B|, |K|, 2 unused
-
-__device__ __forceinline__ float sign0(float x) { return (x > 0.f) ? 1.f : (x < 0.f) ? -1.f : 0.f; }  // torch.sign
 
 // THE definition of the base set: the bits of e = |depth - depth_obs| for a pixel in B, NO_KEY otherwise (NaN fails every test)
 __device__ __forceinline__ uint32_t base_key(const MaskedLossArgs& a, long o) {
@@ -130,7 +129,8 @@ __global__ void __launch_bounds__(THREADS) select_kernel(MaskedLossArgs a, uint3
     }
 }
 
-// four sums over the workgroup in a fixed order -> the workgroup's slot
+// Four sums over the workgroup in block_sum.h's order -> the workgroup's slot.  Written out: the two types share one barrier,
+// and through block_sums(s, n) the compiler orders lane 0's two LDS stores differently in loss_kernel (profiles/loss_steps/README.md)
 __device__ __forceinline__ void reduce_to_slot(double sd, double sc, uint32_t nb, uint32_t nk, uint32_t* slot) {
     __shared__ double red[THREADS / 64][2];
     __shared__ uint32_t cnt[THREADS / 64][2];
@@ -150,9 +150,7 @@ __device__ __forceinline__ void reduce_to_slot(double sd, double sc, uint32_t nb
     if (threadIdx.x == 0) {
         sd = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
         sc = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        const float dh = (float)sd, ch = (float)sc;
-        reinterpret_cast<uint4*>(slot)[0] = make_uint4(__float_as_uint(dh), __float_as_uint((float)(sd - (double)dh)),
-                                                       __float_as_uint(ch), __float_as_uint((float)(sc - (double)ch)));
+        *reinterpret_cast<float4*>(slot) = doubles_to_pairs(sd, sc);
         reinterpret_cast<uint4*>(slot)[1] = make_uint4(cnt[0][0] + cnt[1][0] + cnt[2][0] + cnt[3][0],
                                                        cnt[0][1] + cnt[1][1] + cnt[2][1] + cnt[3][1], 0, 0);
     }
@@ -204,54 +202,39 @@ __global__ void __launch_bounds__(THREADS) final_kernel(int V, int blocks, const
                                                          int* __restrict__ base, int* __restrict__ kept,
                                                          double* __restrict__ view_sums, float* __restrict__ header,
                                                          float* __restrict__ loss) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int v = wave; v < V; v += THREADS / 64) {
-        double sd = 0.0, sc = 0.0;
-        uint32_t nb = 0, nk = 0;
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int v = tid >> 6; v < V; v += THREADS / 64) {
+        double s[2] = {};
+        uint32_t n[2] = {};
         for (int b = lane; b < blocks; b += 64) {
-            const uint4* s = reinterpret_cast<const uint4*>(slots + SLOT_WORDS * ((long)v * blocks + b));
-            const uint4 f = s[0], n = s[1];
-            sd += (double)__uint_as_float(f.x) + (double)__uint_as_float(f.y);
-            sc += (double)__uint_as_float(f.z) + (double)__uint_as_float(f.w);
-            nb += n.x;
-            nk += n.y;
+            const uint4* slot = reinterpret_cast<const uint4*>(slots + SLOT_WORDS * ((long)v * blocks + b));
+            const uint4 f = slot[0], c = slot[1];
+            s[0] += pair_to_double(__uint_as_float(f.x), __uint_as_float(f.y));
+            s[1] += pair_to_double(__uint_as_float(f.z), __uint_as_float(f.w));
+            n[0] += c.x;
+            n[1] += c.y;
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            sd += __shfl_xor(sd, off, 64);
-            sc += __shfl_xor(sc, off, 64);
-            nb += __shfl_xor(nb, off, 64);
-            nk += __shfl_xor(nk, off, 64);
+        for (int i = 0; i < 2; i++) {
+            s[i] = wave_sum(s[i]);
+            n[i] = wave_sum(n[i]);
         }
         if (lane == 0) {
-            base[v] = (int)nb;
-            kept[v] = (int)nk;
-            view_sums[2 * v] = sd;
-            view_sums[2 * v + 1] = sc;
+            base[v] = (int)n[0];
+            kept[v] = (int)n[1];
+            view_sums[2 * v] = s[0];
+            view_sums[2 * v + 1] = s[1];
         }
     }
     __syncthreads();  // (this workgroup's own global writes, read back below)
-    double sd = 0.0, sc = 0.0, nk = 0.0;  // (a count of up to 2^16 views x 2^30 pixels: exact in a double)
+    double s[3] = {};  // S_d, S_c, |K| (a count of up to 2^16 views x 2^30 pixels: exact in a double)
     for (int v = tid; v < V; v += THREADS) {
-        sd += view_sums[2 * v];
-        sc += view_sums[2 * v + 1];
-        nk += (double)kept[v];
+        s[0] += view_sums[2 * v];
+        s[1] += view_sums[2 * v + 1];
+        s[2] += (double)kept[v];
     }
-    __shared__ double red[THREADS / 64][3];
-    for (int off = 32; off > 0; off >>= 1) {
-        sd += __shfl_xor(sd, off, 64);
-        sc += __shfl_xor(sc, off, 64);
-        nk += __shfl_xor(nk, off, 64);
-    }
-    if (lane == 0) {
-        red[wave][0] = sd;
-        red[wave][1] = sc;
-        red[wave][2] = nk;
-    }
-    __syncthreads();
+    block_sums(s);
     if (tid == 0) {
-        sd = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        sc = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        nk = (red[0][2] + red[1][2]) + (red[2][2] + red[3][2]);
+        const double sd = s[0], sc = s[1], nk = s[2];
         const double n_d = mean ? nk : 1.0, n_c = mean ? (mask_color ? (double)C * nk : n_color_all) : 1.0;
         const double term_d = n_d > 0.0 ? (double)w_depth * sd / n_d : 0.0, term_c = n_c > 0.0 ? (double)w_color * sc / n_c : 0.0;
         header[0] = n_d > 0.0 ? w_depth / (float)n_d : 0.f;

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "block_sum.h"
 #include "kernels.h"
 
 namespace dgr {
@@ -44,8 +45,6 @@ Window make_window() {
     for (int i = 0; i < TAPS; i++) w.g[i] = (float)(e[i] / sum);
     return w;
 }
-
-__device__ __forceinline__ float sign0(float x) { return (x > 0.f) ? 1.f : (x < 0.f) ? -1.f : 0.f; }  // torch.sign
 
 // the halo tiles of K planes (src[q] + offset of the same element) into LDS, 0 outside the image.  Every load of a thread is
 // issued before the first LDS store waits for one: five steps x K loads in flight instead of one round trip to L2 / HBM per step
@@ -74,24 +73,11 @@ __device__ __forceinline__ void load_halos(const float* const (&src)[K], long pl
     }
 }
 
-// two sums in double over the workgroup, in a fixed order, to the workgroup's slot as (hi, lo) float pairs
+// two sums in double over the workgroup (block_sum.h's order) to the workgroup's slot as (hi, lo) float pairs
 __device__ __forceinline__ void reduce_to_slot(double a, double b, float* slot) {
-    __shared__ double red[THREADS / 64][2];
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_xor(a, off, 64);
-        b += __shfl_xor(b, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6][0] = a;
-        red[threadIdx.x >> 6][1] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        a = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        b = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-        const float ah = (float)a, bh = (float)b;
-        *reinterpret_cast<float4*>(slot) = make_float4(ah, (float)(a - (double)ah), bh, (float)(b - (double)bh));
-    }
+    double s[2] = {a, b};
+    block_sums(s);
+    if (threadIdx.x == 0) *reinterpret_cast<float4*>(slot) = doubles_to_pairs(s[0], s[1]);
 }
 
 template <bool MAPS>
@@ -179,32 +165,19 @@ __global__ void __launch_bounds__(THREADS) depth_partial_kernel(long n_d, const 
 __global__ void __launch_bounds__(THREADS) ssim_final_kernel(const float* __restrict__ partials, long n_tiles, int n_depth_slots,
                                                              double inv_n, double inv_n_d, float w_l1, float w_ssim, float w_depth,
                                                              float maps_flag, float* __restrict__ header, float* __restrict__ loss) {
-    double sm = 0.0, sl = 0.0, sd = 0.0;
+    double s[3] = {};  // sums of m, of |img - ref|, of |depth - depth_obs|
     for (long i = threadIdx.x; i < n_tiles; i += THREADS) {
         const float4 p = *reinterpret_cast<const float4*>(partials + 4 * i);
-        sm += (double)p.x + (double)p.y;
-        sl += (double)p.z + (double)p.w;
+        s[0] += pair_to_double(p.x, p.y);
+        s[1] += pair_to_double(p.z, p.w);
     }
     for (long i = threadIdx.x; i < n_depth_slots; i += THREADS) {
         const float4 p = *reinterpret_cast<const float4*>(partials + 4 * (n_tiles + i));
-        sd += (double)p.x + (double)p.y;
+        s[2] += pair_to_double(p.x, p.y);
     }
-    __shared__ double red[THREADS / 64][3];
-    for (int off = 32; off > 0; off >>= 1) {
-        sm += __shfl_xor(sm, off, 64);
-        sl += __shfl_xor(sl, off, 64);
-        sd += __shfl_xor(sd, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6][0] = sm;
-        red[threadIdx.x >> 6][1] = sl;
-        red[threadIdx.x >> 6][2] = sd;
-    }
-    __syncthreads();
+    block_sums(s);
     if (threadIdx.x == 0) {
-        const double ssim = ((red[0][0] + red[1][0]) + (red[2][0] + red[3][0])) * inv_n;
-        const double l1 = ((red[0][1] + red[1][1]) + (red[2][1] + red[3][1])) * inv_n;
-        const double dl1 = ((red[0][2] + red[1][2]) + (red[2][2] + red[3][2])) * inv_n_d;
+        const double ssim = s[0] * inv_n, l1 = s[1] * inv_n, dl1 = s[2] * inv_n_d;
         header[0] = (float)ssim;
         header[1] = (float)l1;
         header[2] = (float)dl1;

@@ -281,6 +281,16 @@ def on_device(dev):
     return torch.cuda.device(dev)
 
 
+def call(name_or_fn, device, *args):
+    """One step call into the C ABI, `dgr_<name>(stream, *args)`, under the device rule: `device` (the tensors') is made current
+    for the call and the stream is ITS current stream, whichever device was current.  RuntimeError with the library's message
+    on a non-zero result."""
+    fn = getattr(load(), name_or_fn) if isinstance(name_or_fn, str) else name_or_fn
+    with on_device(device):
+        if fn(stream_handle(device.index), *args):
+            raise RuntimeError(last_error())
+
+
 def set_option(name, value):
     """Process-wide library option (include/dgr_hip.h: dgr_set_option), e.g. set_option("tight_cull", 1)."""
     if load().dgr_set_option(name.encode(), int(value)):

@@ -1,5 +1,5 @@
 """CPU models of the four small step kernels -- the fused sparse Adam and `add_densification_stats` (csrc/optim.hip), the pose
-kernels and the plain L1 loss (csrc/slam.hip) -- with the inputs and the bars their tests share.
+kernels (csrc/pose.hip) and the plain L1 loss (csrc/l1_loss.hip) -- with the inputs and the bars their tests share.
 
 For every operation: a float64 model, a float32 numpy replica that follows the kernel operation for operation, cached input
 families (made once: treat them as read-only) and a `*_check` function that measures outputs against the model in units of the
@@ -16,7 +16,7 @@ import numpy as np
 U = 2.0 ** -24      # unit roundoff of float32
 TINY = 2.0 ** -149  # the smallest float32 denormal: what an underflowing result may lose
 
-# the launch geometry the shapes below are chosen around (csrc/optim.hip, csrc/slam.hip)
+# the launch geometry the shapes below are chosen around (csrc/optim.hip, csrc/l1_loss.hip)
 ADAM_GRID_PASS = 256 * 32 * 256   # elements one pass of sparse_adam_kernel's grid-stride loop covers
 L1_FORWARD_THREADS = 128 * 256    # threads of l1_partial_kernel: an element past this index is some thread's second term
 L1_BACKWARD_PASS = 2048 * 256     # elements one pass of l1_backward_kernel covers

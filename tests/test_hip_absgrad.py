@@ -413,7 +413,7 @@ class _Map:
 
 @pytest.mark.parametrize("variant", ["light", "full"])
 def test_slam_renders_with_absgrad(variant):
-    from dgr_amd import slam
+    from dgr_amd import pose, slam
     V, H, W = 3, 200, 320
     ss = [make_scene(20000, W, H, 0, view_index=v) for v in range(V)]
     s, dev = ss[0], hh.dev()
@@ -431,9 +431,9 @@ def test_slam_renders_with_absgrad(variant):
     for k, x in enumerate(ss):
         ab = torch.zeros((s.P, 3), device=dev, requires_grad=True)
         vm = hh.T(x.view)
-        perspec = slam._perspec_cached(x.tanfovx, x.tanfovy, 0.01, 100.0, dev)
+        perspec = pose._perspec_cached(x.tanfovx, x.tanfovy, 0.01, 100.0, dev)
         cam = dict(image_height=H, image_width=W, tanfovx=x.tanfovx, tanfovy=x.tanfovy, bg=bg, scale_modifier=1.0, viewmatrix=vm,
-                   projmatrix=slam._matmul_fixed_order(vm, perspec).contiguous(), sh_degree=3, campos=slam._campos(vm),
+                   projmatrix=pose._matmul_fixed_order(vm, perspec).contiguous(), sh_degree=3, campos=pose._campos(vm),
                    prefiltered=False, perspec_matrix=perspec)
         if variant == "light":
             r = L.GaussianRasterizer(L.GaussianRasterizationSettings(**cam, debug=False, track_off=True, map_off=False))

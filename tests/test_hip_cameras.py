@@ -254,7 +254,7 @@ def test_slam_render_with_an_off_centre_projection(complete):
     from types import SimpleNamespace
     from dgr_amd import _capi
     from dgr_amd import light as L
-    from dgr_amd import slam
+    from dgr_amd import pose, slam
     from dgr_amd.multiview import make_settings
     from test_hip_full_batch import Model
     s, _ = small("tum", "plain", 46)
@@ -270,8 +270,8 @@ def test_slam_render_with_an_off_centre_projection(complete):
     pc2 = Model(s, dev)
     with torch.no_grad():
         v0 = hh.T(s.view)
-        settings = make_settings(s, 3, dev)._replace(projmatrix=slam._matmul_fixed_order(v0, hh.T(s.persp)).contiguous(),
-                                                     campos=slam._campos(v0))
+        settings = make_settings(s, 3, dev)._replace(projmatrix=pose._matmul_fixed_order(v0, hh.T(s.persp)).contiguous(),
+                                                     campos=pose._campos(v0))
     with _capi.thread_options(pose_grad=int(complete)):
         r = L.GaussianRasterizer(settings)(
             means3D=pc2.get_xyz, means2D=torch.zeros_like(pc2.get_xyz), opacities=pc2.get_opacity, shs=pc2.get_features,

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from dgr_amd import slam
+from dgr_amd import keyframes, slam
 
 import cameras
 import overlap_model as M
@@ -275,7 +275,7 @@ def test_replayed_from_a_hipgraph(W, H, stride):
 def test_nothing_is_written_outside_the_outputs(monkeypatch, W, H, stride, K):
     """Every buffer the call allocates (the counts and scores, the flags, the scratch) lies between two guard regions."""
     guarded = GuardedTorch()
-    monkeypatch.setattr(slam, "torch", guarded)
+    monkeypatch.setattr(keyframes, "torch", guarded)
     case = random_case(W, H, stride, K, 41, 0.5)
     kd = np.random.default_rng(42).uniform(1.0, 4.0, (K, H, W)).astype(np.float32)
     out, _ = run(case, keyframe_depths=kd, depth_tolerance=0.5)

@@ -1,4 +1,4 @@
-"""The fused sparse Adam, add_densification_stats (csrc/optim.hip), the pose kernels and the plain L1 loss (csrc/slam.hip) against
+"""The fused sparse Adam, add_densification_stats (csrc/optim.hip), the pose kernels (csrc/pose.hip) and the plain L1 loss (csrc/l1_loss.hip) against
 their float64 models, at the shapes that reach every grid-stride pass and on inputs that tell a subtly wrong kernel from a right
 one.  Models, inputs and bars: tests/step_model.py; that they can do so: tests/test_step_model.py (no GPU needed).  Every test
 prints what it measured, in units of its bars, before it asserts."""

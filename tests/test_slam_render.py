@@ -237,28 +237,29 @@ def test_render_views_keeps_the_camera_tensors_of_unchanged_keyframes():
             one = lambda c: slam.render(None, m, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"],  # noqa: E731
                                         gt_depth=c["gt_depth"])
             kept_one = [one(c) for c in cams]      # render() keeps a fixed pose's tensors by the same rule: whatever it holds now
-            slam._VIEW_CACHE.clear()
+            slam._VIEW_CACHE.entries.clear()
             fresh = [one(c) for c in cams]         # ... and these calls derive them afresh (and fill the cache for the next check)
             for k, (o, ko) in enumerate(zip(fresh, kept_one)):
                 assert torch.equal(o["render"], out["render"][k]) and torch.equal(o["depth"], out["depth"][k]), (what, k)
                 assert torch.equal(o["render"], ko["render"]) and torch.equal(o["depth"], ko["depth"]), (what, k)
         return out
 
-    slam._VIEWS_CACHE.clear()
+    kept_batches = slam._VIEWS_CACHE.entries  # key -> (the kept tensors, their stamp)
+    kept_batches.clear()
     check("first call")
-    assert len(slam._VIEWS_CACHE) == 1
-    kept = next(iter(slam._VIEWS_CACHE.values()))
+    assert len(kept_batches) == 1
+    kept = next(iter(kept_batches.values()))[0]
     check("second call")
-    assert len(slam._VIEWS_CACHE) == 1 and next(iter(slam._VIEWS_CACHE.values())) is kept   # served from the kept tensors
+    assert len(kept_batches) == 1 and next(iter(kept_batches.values()))[0] is kept   # served from the kept tensors
     with torch.no_grad():                                   # an optimiser step on pose 1: same tensor, next version
         cams[1]["viewmatrix"][3, 0] += 0.05
     check("pose updated in place")
-    assert next(reversed(slam._VIEWS_CACHE.values())) is not kept
+    assert next(reversed(kept_batches.values()))[0] is not kept
     cams[2]["viewmatrix"] = torch.from_numpy(scenes[0].view).to(dev)      # another tensor
     check("pose replaced")
     cams[0]["gt_depth"] = gt * 1.5                                          # another depth image
     out = check("depth replaced")
-    assert len(slam._VIEWS_CACHE) <= 4
+    assert len(kept_batches) <= 4
     # the per-view mapping of render_batch_fused slices on demand
     v = slam._ViewOf(out, 1)
     assert set(v) == set(out) and torch.equal(v["render"], out["render"][1]) and v["viewspace_points"] is out["viewspace_points"]
