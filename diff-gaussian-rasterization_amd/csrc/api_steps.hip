@@ -122,6 +122,64 @@ int dgr_densify_apply(void* stream, long rows, long rows_out, const void* plan, 
     return DGR_OK;
 }
 
+size_t dgr_relocate_scratch_bytes(long P) { return P < 0 || P > PLAN_MAX_ROWS ? 0 : dgr::relocate_scratch_bytes((size_t)P); }
+
+int dgr_relocate_plan(void* stream, long P, const float* opacity_raw, float opacity_raw_min, const long long* draws,
+                      unsigned long long seed, int step, const int* step_device, void* scratch, int* counts8_device, int* source) {
+    const char* bad = P < 0 || P > PLAN_MAX_ROWS ? "P must be 0 .. 2^30 - 1" : nullptr;
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && !counts8_device) bad = "counts8_device is NULL";
+    if (!bad && P > 0 && !opacity_raw) bad = "opacity_raw is NULL";
+    if (!bad && P > 0 && !source) bad = "source is NULL";
+    if (!bad && std::isnan(opacity_raw_min)) bad = "opacity_raw_min is NaN";
+    if (!bad && !step_device && step < 0) bad = "step is negative";
+    if (bad) return refuse("dgr_relocate_plan", bad);
+    HIP_TRY(dgr::launch_relocate_plan((size_t)P, opacity_raw, opacity_raw_min, draws, seed, step, step_device, scratch,
+                                      counts8_device, source, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_relocate_apply(void* stream, long P, const void* scratch, int n, const dgr_relocate_tensor* tensors, float* scaling_raw,
+                       float* opacity_raw, double min_opacity) {
+    const char* bad = P < 0 || P > PLAN_MAX_ROWS ? "P must be 0 .. 2^30 - 1" : nullptr;
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && !(min_opacity >= 0.0 && min_opacity < 1.0)) bad = "min_opacity must lie in [0, 1)";
+    int n_opacity = 0, n_scale = 0, unused = 0;
+    if (!bad)
+        bad = tensor_table_error(n, tensors, DGR_RELOCATE_MAX_TENSORS, "n must be 1 .. DGR_RELOCATE_MAX_TENSORS (24) tensors",
+                                 DGR_RELOCATE_COPY, DGR_RELOCATE_ZERO_RELOCATED, -1, unused,
+                                 [&](const dgr_relocate_tensor& t) -> const char* {
+                                     if (P > 0 && !t.data) return "a tensor with NULL data";
+                                     if (t.mode == DGR_RELOCATE_OPACITY) {
+                                         if (t.k != 1) return "the OPACITY tensor must have k = 1";
+                                         if (++n_opacity > 1) return "more than one OPACITY tensor";
+                                         if (t.data != opacity_raw) return "the OPACITY tensor must be opacity_raw, which the plan was made from";
+                                     }
+                                     if (t.mode == DGR_RELOCATE_LOG_SCALE) {
+                                         if (++n_scale > 1) return "more than one LOG_SCALE tensor";
+                                         if (t.data != scaling_raw) return "the LOG_SCALE tensor must be scaling_raw";
+                                     }
+                                     return nullptr;
+                                 });
+    if (bad) return refuse("dgr_relocate_apply", bad);
+    HIP_TRY(dgr::launch_relocate_apply((size_t)P, scratch, n, tensors, min_opacity, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_position_noise(void* stream, long P, float* xyz, const float* scaling_raw, const float* rotation, const float* opacity_raw,
+                       const float* noise, unsigned long long seed, int step, const int* step_device, float lr,
+                       const float* lr_device, float scale, float k, float x0) {
+    const char* bad = P < 0 || P > PLAN_MAX_ROWS ? "P must be 0 .. 2^30 - 1" : nullptr;
+    if (!bad && P > 0 && (!xyz || !scaling_raw || !rotation || !opacity_raw)) bad = "xyz, scaling_raw, rotation or opacity_raw is NULL";
+    if (!bad && !step_device && step < 0) bad = "step is negative";
+    if (!bad && !lr_device && !std::isfinite(lr)) bad = "lr is not finite";
+    if (!bad && !(std::isfinite(scale) && std::isfinite(k) && std::isfinite(x0))) bad = "scale, k or x0 is not finite";
+    if (bad) return refuse("dgr_position_noise", bad);
+    HIP_TRY(dgr::launch_position_noise((size_t)P, xyz, scaling_raw, rotation, opacity_raw, noise, seed, step, step_device, lr,
+                                       lr_device, scale, k, x0, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 static const char* seed_shape_error(int width, int height, int stride) {
     if (width < 1 || height < 1) return "width and height must be positive";
     if (stride < 1) return "stride must be positive";

@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_ext.h>
 #include "dgr_common.h"
-#include "../../include/dgr_hip.h"  // dgr_densify_tensor, dgr_seed_tensor
+#include "../../include/dgr_hip.h"  // dgr_densify_tensor, dgr_seed_tensor, dgr_relocate_tensor
 
 namespace dgr {
 
@@ -320,6 +320,17 @@ hipError_t launch_densify_plan(size_t rows, const float* grad_accum, const float
 hipError_t launch_densify_apply(size_t rows, size_t rows_out, const void* plan, int n, const dgr_densify_tensor* tensors,
                                 const float* scaling_raw, const float* rotation_raw, const float* noise,
                                 unsigned long long seed, hipStream_t stream);
+// fixed-size map upkeep (relocate.hip): relocation's plan (weights, scan, draws, the hit sources' new values) into `scratch`,
+// counts[8] and source[P] (device), its in-place apply over n tensors (two launches), and the gated position noise
+size_t relocate_scratch_bytes(size_t P);
+hipError_t launch_relocate_plan(size_t P, const float* opacity_raw, float opacity_raw_min, const long long* draws,
+                                unsigned long long seed, int step, const int* step_dev, void* scratch, int* counts, int* source,
+                                hipStream_t stream);
+hipError_t launch_relocate_apply(size_t P, const void* scratch, int n, const dgr_relocate_tensor* tensors, double min_opacity,
+                                 hipStream_t stream);
+hipError_t launch_position_noise(size_t P, float* xyz, const float* scaling_raw, const float* rotation, const float* opacity_raw,
+                                 const float* noise, unsigned long long seed, int step, const int* step_dev, float lr,
+                                 const float* lr_dev, float scale, float k, float x0, hipStream_t stream);
 // fused map expansion from an RGB-D keyframe (seed.hip): decide + scan over the candidate pixels into `plan` and counts[8]
 // (device), then one apply launch for n tensors (old rows copied, one new row per selected pixel)
 size_t seed_candidates(int W, int H, int stride);

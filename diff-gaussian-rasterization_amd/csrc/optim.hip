@@ -12,6 +12,7 @@
 #include <cmath>
 
 #include "kernels.h"
+#include "philox.h"
 #include "plan.h"
 
 namespace dgr {
@@ -141,29 +142,8 @@ __global__ void __launch_bounds__(256) densify_scan_kernel(size_t blocks, void* 
     write_counts8(carry.x + carry.y + 2 * carry.z, carry.x, carry.y, 2 * carry.z, carry.w, plan, counts);
 }
 
-// Philox4x32-10 (Salmon et al., SC'11) keyed by the seed, counter = (row, sample): the draw of a (row, sample) does not
-// depend on the grid, the launch order or on which rows are split.  Box-Muller turns the four words into four standard
-// normals; components 0..2 are the child's noise.
-__device__ inline float philox_normal(unsigned long long seed, unsigned long long row, unsigned sample, int component) {
-    unsigned c0 = (unsigned)row, c1 = (unsigned)(row >> 32), c2 = sample, c3 = 0u;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    const unsigned a = component < 2 ? c0 : c2, b = component < 2 ? c1 : c3;
-    const float u1 = (float)((a >> 8) + 1u) * 0x1p-24f;  // (0, 1]
-    const float u2 = (float)(b >> 8) * 0x1p-24f;         // [0, 1)
-    const float radius = sqrtf(-2.0f * logf(u1)), angle = 6.283185307179586f * u2;
-    return radius * ((component & 1) ? sinf(angle) : cosf(angle));
-}
+// The children's noise: philox_normal (philox.h), counter = (row, sample), components 0..2: the draw of a (row, sample) does not
+// depend on the grid, the launch order or on which rows are split.
 
 // component c of R(q / |q|) (exp(s) * n): 3DGS's build_rotation, q = (r, x, y, z)
 __device__ inline float child_offset(const float* __restrict__ q4, const float* __restrict__ s3, float n0, float n1, float n2,

@@ -68,6 +68,13 @@ class SeedTensor(C.Structure):  # dgr_seed_tensor: one per-Gaussian tensor of a 
 assert C.sizeof(SeedTensor) == 32  # two pointers, two ints, a float, padded to the pointers' alignment
 
 
+class RelocateTensor(C.Structure):  # dgr_relocate_tensor: one per-Gaussian tensor of a dgr_relocate_apply call (rewritten in place)
+    _fields_ = [("data", _vp), ("k", _i), ("mode", _i)]
+
+
+assert C.sizeof(RelocateTensor) == 16  # a pointer, two ints: the C layout
+
+
 class MaskedLossParams(C.Structure):  # dgr_masked_loss_params
     _fields_ = [("depth_lo", _f), ("depth_hi", _f), ("silhouette_threshold", _f), ("outlier_factor", _f),
                 ("reject_outliers", _i), ("mask_color", _i), ("reduction", _i), ("w_color", _f), ("w_depth", _f)]
@@ -83,6 +90,8 @@ class KeyframeOverlapParams(C.Structure):  # dgr_keyframe_overlap_params
 
 assert C.sizeof(KeyframeOverlapParams) == 40  # ten four-byte fields: the C layout
 
+RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
+RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 MASKED_LOSS_SUM, MASKED_LOSS_MEAN = 0, 1  # DGR_MASKED_LOSS_*
 MAX_BATCH_VIEWS = 8  # DGR_MAX_BATCH_VIEWS
 DENSIFY_MAX_TENSORS = 24  # DGR_DENSIFY_MAX_TENSORS
@@ -131,6 +140,10 @@ _SIGS = {
     "dgr_seed_plan": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _f, _f, _f, _vp, C.c_long, _vp, _vp]),
     "dgr_seed_apply": (_i, [_vp, _i, _i, _i, C.c_long, C.c_long, _vp, _i, C.POINTER(SeedTensor), _vp, _vp, _vp, _f, _f, _f, _f,
                             _f]),
+    "dgr_relocate_scratch_bytes": (_sz, [C.c_long]),
+    "dgr_relocate_plan": (_i, [_vp, C.c_long, _vp, _f, _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp]),
+    "dgr_relocate_apply": (_i, [_vp, C.c_long, _vp, _i, C.POINTER(RelocateTensor), _vp, _vp, C.c_double]),
+    "dgr_position_noise": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _vp, _f, _vp, _f, _f, _f]),
     "dgr_sparse_adam": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i]),
     "dgr_sparse_adam_capturable": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
     "dgr_set_option": (_i, [C.c_char_p, _i]),

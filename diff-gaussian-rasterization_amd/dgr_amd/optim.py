@@ -8,6 +8,8 @@ both moments of the other rows are left untouched, as in 3DGS's sparse Adam; `st
 leaf, Adam moment and accumulator in three launches (`dgr_densify_plan`, `dgr_densify_apply`) and one host read.
 `seed_from_frame` is its sibling: it appends one Gaussian per unexplained pixel of an RGB-D keyframe (`dgr_seed_plan`,
 `dgr_seed_apply`).
+`relocate_dead` and `inject_position_noise` keep a map of FIXED size healthy (3DGS-MCMC's two steps; `dgr_relocate_plan`,
+`dgr_relocate_apply`, `dgr_position_noise`): in place, no host read, capturable.
 """
 import collections
 import ctypes
@@ -306,6 +308,123 @@ def seed_from_frame(params, optimizer, color_obs, depth_obs, viewmatrix, fx, fy,
             st, W, H, stride, P, counts.rows, step.plan_buffer.data_ptr(), n, descs, _capi.ptr(color_obs), depth_obs.data_ptr(),
             viewmatrix.data_ptr(), fx, fy, cx, cy, pix))
     return step.finish(), grown.get("xyz_gradient_accum"), grown.get("denom"), grown.get("max_radii2D"), counts
+
+
+RelocateResult = collections.namedtuple("RelocateResult", "counts source")
+
+
+def _device_scalar(value, dtype, what, who):
+    """(host value, device pointer or None) of an argument that is a Python number or a 1-element `dtype` GPU tensor the kernels read"""
+    if isinstance(value, torch.Tensor):
+        if not value.is_cuda or value.dtype != dtype or value.numel() != 1:
+            raise RuntimeError(f"{who}: a tensor {what} must be one {str(dtype).replace('torch.', '')} value on the GPU")
+        return 0, value.data_ptr()
+    return value, None
+
+
+def _in_place(t, what, who):
+    if not t.is_contiguous():
+        raise RuntimeError(f"{who}: {what} is rewritten in place and must be contiguous")
+    return t
+
+
+@torch.no_grad()
+def relocate_dead(params, optimizer, *, min_opacity=0.005, draws=None, seed=0, step=0, xyz_gradient_accum=None, denom=None,
+                  max_radii2D=None, roles=None):
+    """3DGS-MCMC's relocation for a map of fixed size, fused and in place (include/dgr_hip.h: dgr_relocate_plan /
+    dgr_relocate_apply; the semantics are stated there): every dead Gaussian (opacity below `min_opacity`) is moved onto a live one
+    drawn with probability proportional to its opacity, and the opacity and scale of all N copies of a drawn Gaussian are
+    recomputed, in float64, so that the rendered result is unchanged.
+
+    `params`, `roles`, the accumulators: as densify_and_prune's (opacity [P] or [P, 1]); every leaf, moment and accumulator must
+    be contiguous, because all are rewritten in place: they stay the same tensor objects, P does not change and the optimiser is
+    not re-pointed.  `optimizer`: a SparseAdam over the leaves (or None).  Both Adam moments of every leaf are set to 0 at the
+    relocated rows AND at the sources they hit -- the project's choice: a stale moment belongs neither to the old place nor to the
+    new shape; the accumulators that are given are set to 0 at the relocated rows only.  Every other row keeps its bits.
+    `draws`: int64 [P] with one value in [0, 2^32) per row (read at the dead rows), or None for the kernel's Philox generator
+    keyed by `seed` with the counter (row, step).  `step`: an int, or a 1-element int32 GPU tensor that the kernels read, so that
+    every replay of a recorded graph draws fresh numbers.
+
+    Returns RelocateResult(counts, source), both device tensors: counts int32 [8] = {dead, live, relocated, sources hit, largest
+    hits, 0, 0, 0}, source int32 [P] the source row of a relocated row and -1 elsewhere.  No host read and no allocation that
+    outlives the call: it can be recorded into a hipGraph, or run between the replays of one without re-recording."""
+    who = "relocate_dead"
+    lib = _capi.load()
+    work = _ResizeStep(who, params, optimizer, roles, DEFAULT_ROLES)
+    roles, P = work.roles, work.locate()
+    with _capi.on_device(work.dev):
+        st = _capi.stream_handle(work.dev.index)
+        work.check_leaves()
+        leaves = {name: _in_place(t.detach(), f"params[{name!r}]", who) for name, t in params.items()}
+        opacity, scaling = leaves[roles["opacity"]], leaves[roles["scaling"]]
+        if opacity.numel() != P:
+            raise RuntimeError(f"{who}: the opacity leaf must be [P] or [P, 1]")
+        work.check_accumulators(xyz_gradient_accum, denom, max_radii2D)
+        if not 0.0 <= min_opacity < 1.0:
+            raise ValueError(f"{who}: min_opacity must lie in [0, 1)")
+        if draws is not None and (not draws.is_cuda or draws.dtype != torch.int64 or tuple(draws.shape) != (P,) or
+                                  not draws.is_contiguous()):
+            raise RuntimeError(f"{who}: draws must be a contiguous int64 GPU tensor [P] of values in [0, 2^32)")
+        step, step_dev = _device_scalar(step, torch.int32, "step", who)
+        table = []  # (tensor, k, mode): every leaf followed by its two moments, then the accumulators
+        mode_of = {roles["opacity"]: _capi.RELOCATE_OPACITY, roles["scaling"]: _capi.RELOCATE_LOG_SCALE}
+        state_of = optimizer.state if optimizer is not None else {}
+        for name, t in leaves.items():
+            k = max(math.prod(t.shape[1:]), 1)
+            table.append((t, k, mode_of.get(name, _capi.RELOCATE_COPY)))
+            for m in state_of.get(params[name], ()):
+                if m.shape != t.shape or m.dtype != torch.float32 or m.device != t.device:
+                    raise RuntimeError(f"{who}: the moments of params[{name!r}] must have its shape, dtype and device")
+                table.append((_in_place(m, f"a moment of params[{name!r}]", who), k, _capi.RELOCATE_ZERO_TOUCHED))
+        for name, t in (("xyz_gradient_accum", xyz_gradient_accum), ("denom", denom), ("max_radii2D", max_radii2D)):
+            if t is not None:
+                table.append((_in_place(t.detach(), name, who), 1, _capi.RELOCATE_ZERO_RELOCATED))
+
+        scratch = torch.empty(lib.dgr_relocate_scratch_bytes(P), dtype=torch.uint8, device=work.dev)
+        counts = torch.empty(8, dtype=torch.int32, device=work.dev)
+        source = torch.empty(P, dtype=torch.int32, device=work.dev)
+        if lib.dgr_relocate_plan(st, P, _capi.ptr(opacity), densify_thresholds(0.0, 1.0, min_opacity=min_opacity)[1], _capi.ptr(draws),
+                                 ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), int(step), step_dev, scratch.data_ptr(),
+                                 counts.data_ptr(), _capi.ptr(source)):
+            raise RuntimeError(_capi.last_error())
+        for i in range(0, len(table) if P else 0, _capi.RELOCATE_MAX_TENSORS):
+            part = table[i:i + _capi.RELOCATE_MAX_TENSORS]
+            descs = (_capi.RelocateTensor * len(part))()
+            for d, (t, k, mode) in zip(descs, part):
+                d.data, d.k, d.mode = t.data_ptr(), k, mode
+            if lib.dgr_relocate_apply(st, P, scratch.data_ptr(), len(part), descs, scaling.data_ptr(), opacity.data_ptr(),
+                                      float(min_opacity)):
+                raise RuntimeError(_capi.last_error())
+    return RelocateResult(counts, source)
+
+
+@torch.no_grad()
+def inject_position_noise(params, lr, *, noise_scale=5e5, gate_k=100.0, gate_x0=0.995, noise=None, seed=0, step=0, roles=None):
+    """3DGS-MCMC's SGLD position noise in one launch, fp32, in place (include/dgr_hip.h: dgr_position_noise): xyz += g Sigma n
+    with Sigma = R S^2 R^T of each Gaussian and g = noise_scale * lr / (1 + exp(-gate_k (1 - opacity - gate_x0))): only the
+    near-transparent Gaussians move.  `lr`: the position learning rate, a float or a 1-element float32 GPU tensor.  `noise`: [P, 3]
+    standard normals, or None for Philox normals keyed by `seed` with the counter (row, step); `step` as relocate_dead's.  The xyz
+    leaf must be contiguous; it stays the same tensor.  No host read: capturable."""
+    who = "inject_position_noise"
+    lib = _capi.load()
+    work = _ResizeStep(who, params, None, roles, DEFAULT_ROLES)
+    roles, P = work.roles, work.locate()
+    with _capi.on_device(work.dev):
+        st = _capi.stream_handle(work.dev.index)
+        src = work.check_leaves()
+        if src[roles["opacity"]].numel() != P:
+            raise RuntimeError(f"{who}: the opacity leaf must be [P] or [P, 1]")
+        xyz = _in_place(params[roles["xyz"]].detach(), f"params[{roles['xyz']!r}]", who)
+        if noise is not None:
+            if tuple(noise.shape) != (P, 3):
+                raise RuntimeError(f"{who}: noise must be [P, 3]")
+            noise = _rows_tensor(noise, P, "noise", who)
+        step, step_dev = _device_scalar(step, torch.int32, "step", who)
+        lr, lr_dev = _device_scalar(lr, torch.float32, "lr", who)
+        if lib.dgr_position_noise(st, P, _capi.ptr(xyz), _capi.ptr(src[roles["scaling"]]), _capi.ptr(src[roles["rotation"]]),
+                                  _capi.ptr(src[roles["opacity"]]), _capi.ptr(noise), ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)),
+                                  int(step), step_dev, float(lr), lr_dev, float(noise_scale), float(gate_k), float(gate_x0)):
+            raise RuntimeError(_capi.last_error())
 
 
 class SparseAdam:

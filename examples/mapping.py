@@ -25,8 +25,15 @@ rendered depth lies more than 50 x the median depth error behind the sensor's (`
 of the room) and maps against a window of K of them: the newest keyframe and the K - 1 that overlap it most
 (slam.keyframe_overlap: one launch scores the whole pool on the device; slam.select_keyframes: the top scores, read once).
 
+--relocate-every N keeps a map of FIXED size healthy instead (3DGS-MCMC): every N iterations optim.relocate_dead moves each dead
+Gaussian (opacity below --relocate-min-opacity) onto a live one drawn in proportion to its opacity and recomputes the copies'
+opacity and scale (--relocate-start K: not before iteration K, the method's warm-up); --position-noise adds the gated SGLD noise after it (optim.inject_position_noise).  Neither changes P, reallocates
+a tensor or reads anything on the host, so both go together with --graph and --fused: the step runs between replays, with no
+re-recording.  The logged counts are the step's one host read.
+
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
                              [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked] [--select K]
+                             [--relocate-every N [--relocate-start K] [--position-noise] [--relocate-min-opacity 0.005]]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -120,7 +127,8 @@ class SeededMapModel(MapModel):
 
 
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
-                 absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0):
+                 absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0, relocate_every=0,
+                 position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -134,9 +142,15 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     with seed=True the seeding also takes `stats.median * 50` as its depth_error_min.
     select=K: the `keyframes` poses are a pool (keyframe 1 of three or more turned to look the opposite way); the window mapped
     against is the newest keyframe and the K - 1 others that overlap it most (slam.keyframe_overlap / select_keyframes; not with
-    seed=True, whose window grows by itself).  The model's `window` attribute then lists the pool indices chosen."""
+    seed=True, whose window grows by itself).  The model's `window` attribute then lists the pool indices chosen.
+    relocate_every=N: every N iterations relocate_dead moves the Gaussians whose opacity lies below `relocate_min_opacity` onto live
+    ones (generator keyed by `relocate_seed`) and, with position_noise=True, inject_position_noise follows; in place, also with
+    graph=True (between replays) and fused=True.  relocate_start=K: not before iteration K (3DGS-MCMC's warm-up: a split Gaussian
+    moves twice as fast, which costs loss while the optimiser is still in its first descent).  The model's `relocations` attribute then lists each step's counts
+    [dead, live, relocated, sources hit, largest hits]."""
     from dgr_amd import light, slam
-    from dgr_amd.optim import SparseAdam, add_densification_stats, densify_and_prune, seed_from_frame
+    from dgr_amd.optim import (SparseAdam, add_densification_stats, densify_and_prune, inject_position_noise, relocate_dead,
+                               seed_from_frame)
     from dgr_amd.synth import make_scene
 
     scenes = [make_scene(P, W, H, 3, view_index=k) for k in range(keyframes)]
@@ -283,6 +297,19 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             log(f"seed: keyframe {k}: P {before} -> {counts.rows} ({counts.new} new from {counts.valid} valid pixels"
                 f"{f', {counts.unseen} of them unseen' if before else ''})")
 
+    relocations = []
+
+    def relocate(step):
+        # in place: the leaves, the moments and the accumulators stay the tensors the recorded iteration reads and writes
+        result = relocate_dead(pc.leaves(), opt, min_opacity=relocate_min_opacity, seed=relocate_seed, step=step,
+                               xyz_gradient_accum=pc.xyz_gradient_accum, denom=pc.denom, max_radii2D=pc.max_radii2D)
+        if position_noise:
+            inject_position_noise(pc.leaves(), opt.param_groups[0]["lr"], seed=relocate_seed + 1, step=step)
+        relocations.append(result.counts)
+        if log:
+            dead, live, moved, sources, most = result.counts.tolist()[:5]  # (the step's one host read)
+            log(f"relocate: {dead} dead of {dead + live}, {moved} moved onto {sources} live Gaussians (at most {most} onto one)")
+
     if seed:
         seed_keyframe(0)
     join_every = max(iters // keyframes, 1)
@@ -308,6 +335,8 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         loss = run()
         if densify_every and (i + 4) % densify_every == 0:
             densify()
+        if relocate_every and (i + 4) % relocate_every == 0 and i + 3 >= relocate_start:
+            relocate(i + 3)
         if log and (i + 3) % 20 == 0:
             log(f"iteration {i + 3:4d}: loss {float(loss):.4e}")
     torch.cuda.synchronize()
@@ -315,6 +344,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     if graph:
         step.check()
     pc.window = window
+    pc.relocations = [c.tolist()[:5] for c in relocations]
     return (first, float(loss)), pc, dt
 
 
@@ -347,6 +377,15 @@ def main():
                     help="map against a window of K keyframes chosen from the --keyframes pool by their overlap with the newest one "
                          "(slam.keyframe_overlap + slam.select_keyframes); 0 (default) maps against every keyframe; not together "
                          "with --seed")
+    ap.add_argument("--relocate-every", type=int, default=0, metavar="N",
+                    help="every N iterations move the dead Gaussians onto live ones, in place (relocate_dead: 3DGS-MCMC's relocation "
+                         "for a map of fixed size); off by default; goes together with --graph and --fused")
+    ap.add_argument("--relocate-start", type=int, default=0, metavar="K",
+                    help="with --relocate-every: no relocation before iteration K (3DGS-MCMC starts after a warm-up)")
+    ap.add_argument("--position-noise", action="store_true",
+                    help="with --relocate-every: add the gated SGLD position noise after each relocation (inject_position_noise)")
+    ap.add_argument("--relocate-min-opacity", type=float, default=0.005, metavar="O",
+                    help="a Gaussian whose opacity lies below O is dead (default 0.005)")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -362,6 +401,12 @@ def main():
                  "--graph), and it maps through the per-keyframe light path (drop --fused / --variant full)")
     if args.select < 0 or args.select > args.keyframes or (args.select and args.seed):
         ap.error("--select K chooses 1 .. --keyframes keyframes of the pool; --seed grows its own window (drop one of the two)")
+    if args.relocate_every < 0 or (args.position_noise and not args.relocate_every):
+        ap.error("--relocate-every N takes N >= 0, and --position-noise goes with it")
+    if args.relocate_every and args.seed:
+        ap.error("--relocate-every keeps a map of fixed size; --seed grows one (drop one of the two)")
+    if not 0.0 <= args.relocate_min_opacity < 1.0:
+        ap.error("--relocate-min-opacity lies in [0, 1)")
     import torch as _torch
     _torch.autograd.set_multithreading_enabled(False)  # one device, one thread: no engine-thread hand-off per backward
     if args.graph:
@@ -370,7 +415,11 @@ def main():
     (l0, l1), pc, dt = mapping_loop(dev, args.gaussians, args.width, args.height, args.keyframes, args.iters,
                                     args.views_in_flight, log=None if args.graph else print, graph=args.graph, fused=args.fused,
                                     variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every, ssim_lambda=args.ssim,
-                                    seed=args.seed, masked=args.masked, select=args.select)
+                                    seed=args.seed, masked=args.masked, select=args.select, relocate_every=args.relocate_every,
+                                    position_noise=args.position_noise, relocate_min_opacity=args.relocate_min_opacity,
+                                    relocate_start=args.relocate_start)
+    for step, (dead, live, moved, sources, most) in enumerate(pc.relocations if args.graph else ()):
+        print(f"relocation {step}: {dead} dead of {dead + live}, {moved} moved onto {sources} live Gaussians (at most {most} onto one)")
     if args.select:
         args.keyframes = len(pc.window)
     n = float(pc.denom.sum())

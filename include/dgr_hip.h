@@ -296,6 +296,64 @@ int dgr_densify_apply(void* stream, long rows, long rows_out, const void* plan, 
                       const float* scaling_raw, const float* rotation_raw, const float* noise /* or NULL */,
                       unsigned long long seed);
 
+/* Fixed-size map upkeep: 3DGS-MCMC's relocation of dead Gaussians and its position noise (Kheradmand et al., NeurIPS 2024), in
+ * place (csrc/relocate.hip).  Neither changes the number of rows P: no tensor is reallocated and nothing is read on the host, so
+ * both can be recorded into a hipGraph.  Raw leaves as above: opacity_raw a logit, scaling_raw the log of the scale.
+ *
+ * Relocation.  thr = opacity_raw_min (the caller's logit(min_opacity), formed in float64 and rounded once).
+ *   dead   = opacity_raw < thr (an fp32 comparison, false on a NaN), and opacity_raw finite;
+ *   live   = opacity_raw finite and not dead, with the integer weight w = rint(2^20 o), o = 1 / (1 + exp(-opacity_raw)) in
+ *            float64; a row whose opacity_raw is not finite is neither: weight 0, never read, never written;
+ *   S      = sum of w (exact, 64-bit; below 2^48 for P <= 2^28), C_i = the exclusive prefix of w in row order;
+ *   draw   = every dead row r owns one 32-bit draw d_r: draws[r] (int64 [P], values 0 .. 2^32 - 1) or, with draws == NULL, word 0
+ *            of Philox4x32-10 under key `seed` with the counter (r, step, 1); its target is t_r = (d_r S) >> 32 (exact) and its
+ *            source the live row i with C_i <= t_r < C_i + w_i.  Integer arithmetic only: the result does not depend on the grid
+ *            or the launch order.  With S == 0 nothing is relocated;
+ *   hits_i = how many dead rows drew i (an integer atomic), N_i = min(hits_i + 1, 51).
+ * For a source with hits_i > 0, in float64: o' = 1 - (1 - o)^(1 / N); D = sum_{m=1..N} sum_{k=0..m-1} C(m-1, k) (-1)^k
+ * (k + 1)^(-1/2) o'^(k+1); coeff = o / D; o' is then clamped to [min_opacity, 1 - 2^-23].  The new raw opacity is log(o' / (1 -
+ * o')) and the new raw scale scaling_raw + log(coeff) per component, each rounded once to fp32: the N copies together render what
+ * the one did.  (fp32 loses up to 1.9e-4 relative here, to the cancellation in 1 - (1 - o)^(1/N).)
+ * Writes, all in place: a relocated row takes every tensor of its source bit for bit (COPY), the source's NEW opacity (OPACITY) and
+ * scale (LOG_SCALE); the source takes the same new opacity and scale; ZERO_TOUCHED tensors (the Adam moments: a stale moment belongs
+ * to neither the old place nor the new shape) become 0 at relocated rows and hit sources, ZERO_RELOCATED ones (the densification
+ * accumulators) at relocated rows only.  Every other row keeps its bits in every tensor.
+ *
+ * dgr_relocate_plan (four launches: weights and block totals, a one-workgroup scan, the draws, the hit sources' new values) fills
+ * `scratch`, an opaque 16-byte aligned device buffer of dgr_relocate_scratch_bytes(P) bytes (0 for a P it refuses), and writes
+ * counts8_device[0..7] = {dead, live, relocated, sources hit, largest hits, 0, 0, 0} and source[P] (the source row of a relocated
+ * row, -1 elsewhere), both device memory.  `step` is read from *step_device when that is not NULL (a recorded graph then draws
+ * fresh numbers on every replay).  dgr_relocate_apply then rewrites a table of 1 .. DGR_RELOCATE_MAX_TENSORS tensors {data [P, k]}
+ * in two launches -- the relocated rows, which only read live rows and only write dead ones, then the sources -- from the values
+ * the plan saved, so that no row is read while it is rewritten; call it again with the same scratch for more tensors.  The plan
+ * belongs to the opacity it was made from: an OPACITY tensor must be `opacity_raw` (k = 1, at most one), a LOG_SCALE tensor
+ * `scaling_raw` (at most one).  Argument errors are reported before any HIP call. */
+#define DGR_RELOCATE_MAX_TENSORS 24
+#define DGR_RELOCATE_COPY 0
+#define DGR_RELOCATE_OPACITY 1
+#define DGR_RELOCATE_LOG_SCALE 2
+#define DGR_RELOCATE_ZERO_TOUCHED 3
+#define DGR_RELOCATE_ZERO_RELOCATED 4
+typedef struct {
+    float* data;
+    int k;
+    int mode;
+} dgr_relocate_tensor;
+size_t dgr_relocate_scratch_bytes(long P);
+int dgr_relocate_plan(void* stream, long P, const float* opacity_raw, float opacity_raw_min, const long long* draws /* or NULL */,
+                      unsigned long long seed, int step, const int* step_device /* or NULL */, void* scratch, int* counts8_device,
+                      int* source);
+int dgr_relocate_apply(void* stream, long P, const void* scratch, int n, const dgr_relocate_tensor* tensors, float* scaling_raw,
+                       float* opacity_raw, double min_opacity);
+/* Position noise (SGLD), one launch, fp32, in place: xyz_c += g sum_j Sigma_cj n_j with Sigma = R S^2 R^T from the normalised
+ * quaternion rotation [P, 4] (r, x, y, z) and S = diag(exp(scaling_raw)); g = scale lr / (1 + exp(-k (1 - o - x0))), o =
+ * sigmoid(opacity_raw): the gate opens for the near-transparent rows only (3DGS-MCMC: scale 5e5, k 100, x0 0.995).  `noise`: [P,
+ * 3] standard normals, or NULL: Philox normals (Box-Muller) under key `seed` with the counter (row, step, 0), components 0 .. 2.
+ * `step` / `lr` are read from *step_device / *lr_device when those are not NULL. */
+int dgr_position_noise(void* stream, long P, float* xyz, const float* scaling_raw, const float* rotation, const float* opacity_raw,
+                       const float* noise /* or NULL */, unsigned long long seed, int step, const int* step_device /* or NULL */,
+                       float lr, const float* lr_device /* or NULL */, float scale, float k, float x0);
+
 /* Fused map expansion: new Gaussians from an RGB-D keyframe, appended to every per-Gaussian tensor of the model in three
  * launches (csrc/seed.hip) -- what an RGB-D SLAM system (CG-SLAM, SplaTAM, MonoGS) does when a keyframe arrives: unproject the
  * pixels the current map does not explain.  The sibling of densify-and-prune above: decide, scan, one host read, one apply.
