@@ -15,15 +15,21 @@ int refuse(const char* who, const char* bad) {  // a refusal: "<entry point>: <w
     return DGR_ERR_BAD_ARGUMENT;
 }
 
-// What the plan and apply entry points of the map-resize steps (densify-and-prune, map expansion) check alike:
+// What the plan and apply entry points of the map steps (densify-and-prune, map expansion, relocation, position noise) check alike:
 const long PLAN_MAX_ROWS = 0x3fffffffL;  // densify's P' <= 2 rows and seed's rows + candidates must fit the int counts
 
-// the row range, then `between` (the caller's own refusal reported at this place, or NULL), the plan pointer and, for a plan
-// call, counts8_device: the message, or NULL
-const char* plan_args_error(long rows, const char* between, const void* plan, bool plans, const int* counts8_device) {
-    if (rows < 0 || rows > PLAN_MAX_ROWS) return "rows must be 0 .. 2^30 - 1";
+thread_local std::string named_error;  // a message that names the caller's argument, kept until the thread's next one
+// the row range, under the name the entry point gives its row count: the message, or NULL
+const char* rows_error(long rows, const char* name) {
+    return rows >= 0 && rows <= PLAN_MAX_ROWS ? nullptr : (named_error = std::string(name) + " must be 0 .. 2^30 - 1").c_str();
+}
+// the row range, then `between` (the caller's own refusal reported at this place, or NULL), the plan (or scratch) pointer and, for
+// a plan call, counts8_device: the message, or NULL
+const char* plan_args_error(long rows, const char* between, const void* plan, bool plans, const int* counts8_device,
+                            const char* rows_name = "rows", const char* plan_name = "plan") {
+    if (const char* bad = rows_error(rows, rows_name)) return bad;
     if (between) return between;
-    if (!plan || !dgr::aligned16(plan)) return "plan is NULL or not 16-byte aligned";
+    if (!plan || !dgr::aligned16(plan)) return (named_error = std::string(plan_name) + " is NULL or not 16-byte aligned").c_str();
     if (plans && !counts8_device) return "counts8_device is NULL";
     return nullptr;
 }
@@ -126,9 +132,7 @@ size_t dgr_relocate_scratch_bytes(long P) { return P < 0 || P > PLAN_MAX_ROWS ? 
 
 int dgr_relocate_plan(void* stream, long P, const float* opacity_raw, float opacity_raw_min, const long long* draws,
                       unsigned long long seed, int step, const int* step_device, void* scratch, int* counts8_device, int* source) {
-    const char* bad = P < 0 || P > PLAN_MAX_ROWS ? "P must be 0 .. 2^30 - 1" : nullptr;
-    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
-    if (!bad && !counts8_device) bad = "counts8_device is NULL";
+    const char* bad = plan_args_error(P, nullptr, scratch, true, counts8_device, "P", "scratch");
     if (!bad && P > 0 && !opacity_raw) bad = "opacity_raw is NULL";
     if (!bad && P > 0 && !source) bad = "source is NULL";
     if (!bad && std::isnan(opacity_raw_min)) bad = "opacity_raw_min is NaN";
@@ -141,8 +145,7 @@ int dgr_relocate_plan(void* stream, long P, const float* opacity_raw, float opac
 
 int dgr_relocate_apply(void* stream, long P, const void* scratch, int n, const dgr_relocate_tensor* tensors, float* scaling_raw,
                        float* opacity_raw, double min_opacity) {
-    const char* bad = P < 0 || P > PLAN_MAX_ROWS ? "P must be 0 .. 2^30 - 1" : nullptr;
-    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    const char* bad = plan_args_error(P, nullptr, scratch, false, nullptr, "P", "scratch");
     if (!bad && !(min_opacity >= 0.0 && min_opacity < 1.0)) bad = "min_opacity must lie in [0, 1)";
     int n_opacity = 0, n_scale = 0, unused = 0;
     if (!bad)
@@ -169,7 +172,7 @@ int dgr_relocate_apply(void* stream, long P, const void* scratch, int n, const d
 int dgr_position_noise(void* stream, long P, float* xyz, const float* scaling_raw, const float* rotation, const float* opacity_raw,
                        const float* noise, unsigned long long seed, int step, const int* step_device, float lr,
                        const float* lr_device, float scale, float k, float x0) {
-    const char* bad = P < 0 || P > PLAN_MAX_ROWS ? "P must be 0 .. 2^30 - 1" : nullptr;
+    const char* bad = rows_error(P, "P");
     if (!bad && P > 0 && (!xyz || !scaling_raw || !rotation || !opacity_raw)) bad = "xyz, scaling_raw, rotation or opacity_raw is NULL";
     if (!bad && !step_device && step < 0) bad = "step is negative";
     if (!bad && !lr_device && !std::isfinite(lr)) bad = "lr is not finite";

@@ -1,6 +1,7 @@
-// plan.h -- what the plan-then-apply steps (densify-and-prune in optim.hip, map expansion in seed.hip) share (gfx950, wave64):
-// the plan buffer's layout, the decide kernels' block totals, a lane's rank in a ballot, the one-workgroup exclusive scan of the
-// block totals, and the table that deals an apply launch's tensors to workgroups.
+// plan.h -- what the plan-then-apply steps share (gfx950, wave64): densify-and-prune in optim.hip, map expansion in seed.hip,
+// relocation in relocate.hip.  For all three: 256-row blocks, a lane's rank in a ballot, the one-workgroup exclusive scan of the
+// block totals (over the step's own record) and the table that deals an apply launch's tensors to workgroups.  For the two that
+// change P: the plan buffer's layout and the decide kernels' block totals.
 // plan buffer: int[16] header (0..7: the counts), int4 per 256-element block (totals, then exclusive offsets), a flag byte per element.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,7 +25,6 @@ inline size_t plan_bytes(size_t n) { return PLAN_HEADER_INTS * 4 + plan_blocks(n
 __device__ inline int lane_rank(unsigned long long m) {  // set bits of m below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
-__device__ inline int4 add4(int4 a, int4 b) { return make_int4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 // the four waves' entries of column f of `wave_tot` (int[4][F] of LDS, one row per wave), added
 template <int F>
 __device__ inline int wave_total(const int (*wave_tot)[F], int f) {
@@ -52,31 +52,36 @@ __device__ inline int4 block_flag_totals(const unsigned& flags, int (*wave_tot)[
     return t;
 }
 
+// what scan_block_totals needs of a block record: totals_zero (of a table of them), totals_add, totals_sub, totals_shfl_up (the
+// value d lanes below)
+__device__ inline int4 totals_zero(const int4*) { return make_int4(0, 0, 0, 0); }
+__device__ inline int4 totals_add(int4 a, int4 b) { return make_int4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+__device__ inline int4 totals_sub(int4 a, int4 b) { return make_int4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+__device__ inline int4 totals_shfl_up(int4 v, int d) {
+    return make_int4(__shfl_up(v.x, d), __shfl_up(v.y, d), __shfl_up(v.z, d), __shfl_up(v.w, d));
+}
+
 // One workgroup of 256 threads: exclusive scan of table[0 .. blocks) in place, 256 records per pass with the running totals
-// carried from pass to pass; returns the totals (in every thread).  `wave_sum`: int4[4] of LDS.
-__device__ inline int4 scan_block_totals(int4* table, size_t blocks, int4* wave_sum) {
+// carried from pass to pass; returns the totals (in every thread).  `wave_sum`: R[4] of LDS.
+template <typename R>
+__device__ inline R scan_block_totals(R* table, size_t blocks, R* wave_sum) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int4 carry = make_int4(0, 0, 0, 0);
+    R carry = totals_zero(table);
     for (size_t base = 0; base < blocks; base += 256) {
         const size_t b = base + threadIdx.x;
-        const int4 own = b < blocks ? table[b] : make_int4(0, 0, 0, 0);
-        int4 inc = own;  // inclusive scan within the wave
+        const R own = b < blocks ? table[b] : totals_zero(table);
+        R inc = own;  // inclusive scan within the wave
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
-            int4 up;
-            up.x = __shfl_up(inc.x, d);
-            up.y = __shfl_up(inc.y, d);
-            up.z = __shfl_up(inc.z, d);
-            up.w = __shfl_up(inc.w, d);
-            if (lane >= d) inc = add4(inc, up);
+            const R up = totals_shfl_up(inc, d);
+            if (lane >= d) inc = totals_add(inc, up);
         }
         if (lane == 63) wave_sum[wave] = inc;
         __syncthreads();
-        int4 before = carry;
-        for (int w = 0; w < wave; ++w) before = add4(before, wave_sum[w]);
-        if (b < blocks) table[b] = make_int4(before.x + inc.x - own.x, before.y + inc.y - own.y, before.z + inc.z - own.z,
-                                             before.w + inc.w - own.w);
-        carry = add4(add4(add4(add4(carry, wave_sum[0]), wave_sum[1]), wave_sum[2]), wave_sum[3]);
+        R before = carry;
+        for (int w = 0; w < wave; ++w) before = totals_add(before, wave_sum[w]);
+        if (b < blocks) table[b] = totals_sub(totals_add(before, inc), own);
+        carry = totals_add(totals_add(totals_add(totals_add(carry, wave_sum[0]), wave_sum[1]), wave_sum[2]), wave_sum[3]);
         __syncthreads();  // wave_sum is rewritten by the next pass
     }
     return carry;

@@ -3,8 +3,9 @@
 // tensor is reallocated and nothing is read on the host, so the steps can be recorded into a hipGraph.
 //
 // Relocation, six launches.  weights: one thread per row -> dead / live, the integer weight w = rint(2^20 o) (o in float64), the
-// row's exclusive prefix of w inside its 256-row block and the block's totals (64-bit weight, dead, live); it also clears `hits`
-// and `source`.  scan: one workgroup turns the block totals into exclusive offsets, S and counts[0..2].  sample: one thread per dead
+// row's exclusive prefix of w inside its 256-row block (block_scan.h) and the block's totals (64-bit weight, dead, live); it also
+// clears `hits` and `source`.  scan: one workgroup turns the block totals into exclusive offsets (plan.h's scan_block_totals over
+// this file's record), S and counts[0..2].  sample: one thread per dead
 // row -> its draw's target t = (d S) >> 32, a binary search over the block offsets, then over the block's 256 prefixes, one integer
 // atomic on the source's hit count.  values: one thread per hit source -> its new opacity o' and log(coeff), in float64.  apply,
 // twice over the tensor table: the relocated rows (they read live rows and the saved values, they write dead rows), then the hit
@@ -19,6 +20,7 @@
 
 #include <cstdint>
 
+#include "block_scan.h"
 #include "kernels.h"
 #include "philox.h"
 #include "plan.h"
@@ -31,6 +33,14 @@ struct RelocateBlock {  // a block's totals, after the scan its exclusive offset
     int dead, live;
 };
 static_assert(sizeof(RelocateBlock) == 16, "one 16-byte record per block");
+// the record of plan.h's scan_block_totals (the 64-bit weight shuffled as two words)
+__device__ inline RelocateBlock totals_zero(const RelocateBlock*) { return {0ull, 0, 0}; }
+__device__ inline RelocateBlock totals_add(RelocateBlock a, RelocateBlock b) { return {a.w + b.w, a.dead + b.dead, a.live + b.live}; }
+__device__ inline RelocateBlock totals_sub(RelocateBlock a, RelocateBlock b) { return {a.w - b.w, a.dead - b.dead, a.live - b.live}; }
+__device__ inline RelocateBlock totals_shfl_up(RelocateBlock v, int d) {
+    const unsigned lo = __shfl_up((unsigned)v.w, d), hi = __shfl_up((unsigned)(v.w >> 32), d);
+    return {(unsigned long long)hi << 32 | lo, __shfl_up(v.dead, d), __shfl_up(v.live, d)};
+}
 
 constexpr size_t RELOCATE_HEADER_BYTES = 64;
 constexpr int RELOCATE_MAX_COPIES = 51;  // N = min(hits + 1, 51): 3DGS-MCMC's binomial table ends there
@@ -60,12 +70,12 @@ __device__ inline double sigmoid64(float raw) { return 1.0 / (1.0 + exp(-(double
 
 __global__ void __launch_bounds__(256) relocate_weight_kernel(size_t P, const float* __restrict__ opacity_raw, float thr,
                                                               void* scratch, int* __restrict__ source) {
-    __shared__ unsigned wave_w[4];
+    __shared__ uint32_t wave_w[4];
     __shared__ int wave_dead[4], wave_live[4];
     const RelocateLayout l = relocate_layout(P);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    unsigned w = 0u;
+    uint32_t w = 0u;
     bool dead = false, live = false;
     if (i < P) {
         const float raw = opacity_raw[i];
@@ -78,70 +88,29 @@ __global__ void __launch_bounds__(256) relocate_weight_kernel(size_t P, const fl
         at<int>(scratch, l.source)[i] = -1;
         source[i] = -1;
     }
-    unsigned inc = w;  // inclusive scan within the wave (a block's total is at most 256 * 2^20)
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-    }
     const int n_dead = __popcll(__ballot(dead)), n_live = __popcll(__ballot(live));
-    if (lane == 63) wave_w[wave] = inc;
     if (lane == 0) wave_dead[wave] = n_dead, wave_live[wave] = n_live;
-    __syncthreads();
-    unsigned before = 0u;
-    for (int v = 0; v < wave; ++v) before += wave_w[v];
-    if (i < P) at<unsigned>(scratch, l.prefix)[i] = before + inc - w;
+    uint32_t total;  // (a block's total is at most 256 * 2^20)
+    const uint32_t before = block_exclusive_scan<256>(w, wave_w, (int)threadIdx.x, &total);  // (its barrier covers the counts too)
+    if (i < P) at<unsigned>(scratch, l.prefix)[i] = before;
     if (threadIdx.x == 0) {
         RelocateBlock t;
-        t.w = (unsigned long long)wave_w[0] + wave_w[1] + wave_w[2] + wave_w[3];
+        t.w = total;
         t.dead = wave_dead[0] + wave_dead[1] + wave_dead[2] + wave_dead[3];
         t.live = wave_live[0] + wave_live[1] + wave_live[2] + wave_live[3];
         at<RelocateBlock>(scratch, l.table)[blockIdx.x] = t;
     }
 }
 
-// One workgroup: exclusive scan of the block totals in place, 256 records per pass with the running totals carried (plan.h's
-// scan_block_totals with a 64-bit weight); then S and counts[0..7] = {dead, live, relocated, 0, 0, 0, 0, 0} (the sample kernel
-// counts the hit sources and the largest hit count into [3] and [4]).
+// One workgroup: exclusive scan of the block totals in place (plan.h); then S and counts[0..7] = {dead, live, relocated, 0, 0, 0,
+// 0, 0} (the sample kernel counts the hit sources and the largest hit count into [3] and [4]).
 __global__ void __launch_bounds__(256) relocate_scan_kernel(size_t P, void* scratch, int* __restrict__ counts) {
-    __shared__ unsigned long long wave_w[4];
-    __shared__ int wave_dead[4], wave_live[4];
-    const RelocateLayout l = relocate_layout(P);
-    RelocateBlock* table = at<RelocateBlock>(scratch, l.table);
-    const size_t blocks = plan_blocks(P);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    unsigned long long carry_w = 0ull;
-    int carry_dead = 0, carry_live = 0;
-    for (size_t base = 0; base < blocks; base += 256) {
-        const size_t b = base + threadIdx.x;
-        RelocateBlock own;
-        own.w = 0ull, own.dead = 0, own.live = 0;
-        if (b < blocks) own = table[b];
-        unsigned long long w = own.w;
-        int dead = own.dead, live = own.live;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned lo = __shfl_up((unsigned)w, d), hi = __shfl_up((unsigned)(w >> 32), d);
-            const int up_dead = __shfl_up(dead, d), up_live = __shfl_up(live, d);
-            if (lane >= d) w += (unsigned long long)hi << 32 | lo, dead += up_dead, live += up_live;
-        }
-        if (lane == 63) wave_w[wave] = w, wave_dead[wave] = dead, wave_live[wave] = live;
-        __syncthreads();
-        unsigned long long before_w = carry_w;
-        int before_dead = carry_dead, before_live = carry_live;
-        for (int v = 0; v < wave; ++v) before_w += wave_w[v], before_dead += wave_dead[v], before_live += wave_live[v];
-        if (b < blocks) {
-            RelocateBlock out;
-            out.w = before_w + w - own.w, out.dead = before_dead + dead - own.dead, out.live = before_live + live - own.live;
-            table[b] = out;
-        }
-        for (int v = 0; v < 4; ++v) carry_w += wave_w[v], carry_dead += wave_dead[v], carry_live += wave_live[v];
-        __syncthreads();  // the wave totals are rewritten by the next pass
-    }
-    if (threadIdx.x == 0) *at<unsigned long long>(scratch, 0) = carry_w;
+    __shared__ RelocateBlock wave_sum[4];
+    const RelocateBlock carry = scan_block_totals(at<RelocateBlock>(scratch, relocate_layout(P).table), plan_blocks(P), wave_sum);
+    if (threadIdx.x == 0) *at<unsigned long long>(scratch, 0) = carry.w;
     if (threadIdx.x < 8) {
         const int t = (int)threadIdx.x;
-        counts[t] = t == 0 ? carry_dead : t == 1 ? carry_live : t == 2 ? (carry_w > 0ull ? carry_dead : 0) : 0;
+        counts[t] = t == 0 ? carry.dead : t == 1 ? carry.live : t == 2 ? (carry.w > 0ull ? carry.dead : 0) : 0;
     }
 }
 

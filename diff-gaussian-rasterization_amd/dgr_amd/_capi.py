@@ -294,14 +294,40 @@ def on_device(dev):
     return torch.cuda.device(dev)
 
 
-def call(name_or_fn, device, *args):
-    """One step call into the C ABI, `dgr_<name>(stream, *args)`, under the device rule: `device` (the tensors') is made current
-    for the call and the stream is ITS current stream, whichever device was current.  RuntimeError with the library's message
-    on a non-zero result."""
-    fn = getattr(load(), name_or_fn) if isinstance(name_or_fn, str) else name_or_fn
-    with on_device(device):
-        if fn(stream_handle(device.index), *args):
+class StepCalls:
+    """The one way a step enters the C ABI, for the calls of one invocation (an Adam step's call per tensor, a plan call and its
+    apply calls): `with StepCalls(device) as abi: abi.call("dgr_<name>", *args)`.  The device rule: `device` (the tensors') is
+    made current for the block and `stream` is ITS current stream, whichever device was current; both are looked up once."""
+    __slots__ = ("device", "lib", "stream", "_guard")
+
+    def __init__(self, device):
+        self.device = device
+
+    def __enter__(self):
+        self.lib = load()
+        self._guard = on_device(self.device)
+        self._guard.__enter__()
+        self.stream = stream_handle(self.device.index)
+        return self
+
+    def __exit__(self, *exc):
+        return self._guard.__exit__(*exc)
+
+    def call(self, name_or_fn, *args):
+        """`dgr_<name>(stream, *args)`; RuntimeError with the library's message on a non-zero result"""
+        fn = getattr(self.lib, name_or_fn) if isinstance(name_or_fn, str) else name_or_fn
+        if fn(self.stream, *args):
             raise RuntimeError(last_error())
+
+    def capturing(self):
+        """whether the stream is being recorded into a hipGraph"""
+        return bool(self.lib.dgr_stream_is_capturing(self.stream))
+
+
+def call(name_or_fn, device, *args):
+    """One step call into the C ABI: `StepCalls(device)` used once."""
+    with StepCalls(device) as abi:
+        abi.call(name_or_fn, *args)
 
 
 def set_option(name, value):

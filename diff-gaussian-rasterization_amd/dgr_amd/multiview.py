@@ -27,29 +27,21 @@ def make_settings(s, sh_degree, device, track_off=False, map_off=False, debug=Fa
 class _SharedCov3D(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scales, rotations, scale_modifier):
-        from . import _capi
         scales, rotations = scales.contiguous().float(), rotations.contiguous().float()
         cov = torch.empty((scales.shape[0], 6), dtype=torch.float32, device=scales.device)
-        with _capi.on_device(scales.device):
-            rc = _capi.load().dgr_cov3d_forward(_capi.stream_handle(scales.device.index), scales.shape[0], _capi.ptr(scales),
-                                                _capi.ptr(rotations), float(scale_modifier), _capi.ptr(cov))
-        if rc:
-            raise RuntimeError(_capi.last_error())
+        _capi.call("dgr_cov3d_forward", scales.device, scales.shape[0], _capi.ptr(scales), _capi.ptr(rotations), float(scale_modifier),
+                   _capi.ptr(cov))
         ctx.save_for_backward(scales, rotations)
         ctx.mod = float(scale_modifier)
         return cov
 
     @staticmethod
     def backward(ctx, dL_dcov):
-        from . import _capi
         scales, rotations = ctx.saved_tensors
         dL_dcov = dL_dcov.contiguous().float()
         ds, dr = torch.empty_like(scales), torch.empty_like(rotations)
-        with _capi.on_device(scales.device):
-            rc = _capi.load().dgr_cov3d_backward(_capi.stream_handle(scales.device.index), scales.shape[0], _capi.ptr(scales),
-                                                 _capi.ptr(rotations), ctx.mod, _capi.ptr(dL_dcov), _capi.ptr(ds), _capi.ptr(dr))
-        if rc:
-            raise RuntimeError(_capi.last_error())
+        _capi.call("dgr_cov3d_backward", scales.device, scales.shape[0], _capi.ptr(scales), _capi.ptr(rotations), ctx.mod,
+                   _capi.ptr(dL_dcov), _capi.ptr(ds), _capi.ptr(dr))
         return ds, dr, None
 
 
