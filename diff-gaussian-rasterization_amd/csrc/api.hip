@@ -192,8 +192,11 @@ int forward_blend(const FwdCommon& c, dgr::GeometryView geom, dgr::ImageView img
     return DGR_OK;
 }
 
+// (the SH basis is written out for degrees 0 .. 3: a larger one would be read as 3 by some kernels and as itself by others)
+const char* const BAD_DEGREE = "the SH degree must be 0 .. 3";
 int check_common(const FwdCommon& c) {
     if (c.P < 0 || c.W <= 0 || c.H <= 0) { set_last_error("bad sizes"); return DGR_ERR_BAD_ARGUMENT; }
+    if (c.D < 0 || c.D > 3) { set_last_error(BAD_DEGREE); return DGR_ERR_BAD_ARGUMENT; }
     if ((unsigned)c.P > DGR_ID_MASK) { set_last_error("more than 2^28 Gaussians"); return DGR_ERR_BAD_ARGUMENT; }
     if (c.P > 0 && !c.shs && !c.colors_precomp) { set_last_error("need SHs or precomputed colours"); return DGR_ERR_BAD_ARGUMENT; }
     if (c.P > 0 && !c.cov3D_precomp && (!c.scales || !c.rotations)) { set_last_error("need scale/rotation or cov3D"); return DGR_ERR_BAD_ARGUMENT; }
@@ -515,6 +518,13 @@ dgr::PreprocessBwdArgs bwd_scene(int P, int D, int M, int W, int H, const float*
     return b;
 }
 
+// M > 16: the per-Gaussian backward writes the 16 coefficients the SH basis has; the rest of every dL_dsh row is zero, as in the
+// reference (which zero-fills the tensor), cleared here ahead of the kernel.  M <= 16 rows are written whole by the kernel.
+int zero_wide_sh_rows(const dgr::PreprocessBwdArgs& b, hipStream_t st) {
+    if (b.M > 16 && b.dL_dsh) { ScopedStage t(ST_ZERO, st); HIP_TRY(dgr::launch_zero_floats(b.dL_dsh, 3 * (size_t)b.P * (size_t)b.M, st)); }
+    return DGR_OK;
+}
+
 // A view's state and scratch, carved
 struct BwdBufs {
     dgr::GeometryView geom;
@@ -598,6 +608,7 @@ int backward_one(hipStream_t st, dgr::PreprocessBwdArgs b, const float* backgrou
     const int P = b.P, width = b.W, height = b.H, R = w.R;
     if (int rc = absgrad_refused(w.dL_dmean2D_abs != nullptr, b.map_off)) return rc;
     if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { set_last_error("bad sizes"); return DGR_ERR_BAD_ARGUMENT; }
+    if (b.D < 0 || b.D > 3) { set_last_error(BAD_DEGREE); return DGR_ERR_BAD_ARGUMENT; }
     if (P == 0) {  // L/rasterize_points.cu:188: nothing runs, gradients stay zero
         HIP_TRY(hipMemsetAsync(w.dL_dview, 0, 16 * 4, st));
         return DGR_OK;
@@ -617,6 +628,7 @@ int backward_one(hipStream_t st, dgr::PreprocessBwdArgs b, const float* backgrou
     BwdBufs s;
     if (int rc = bwd_view_prepare(w, P, width, height, det, scratch_clean, s, st)) return rc;
     if (int rc = bwd_view_blend(w, b, background, s, det, complete, st)) return rc;
+    if (int rc = zero_wide_sh_rows(b, st)) return rc;
     bwd_view_part(b, w, s, det);
     b.clear_scratch = scratch_clean ? 1 : 0;
     { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd(b, st, complete)); }
@@ -644,6 +656,7 @@ int backward_batch(hipStream_t st, dgr::PreprocessBwdArgs b, const float* backgr
     for (int v = 0; v < n_views; v++) any_abs |= views[v].dL_dmean2D_abs != nullptr;
     if (int rc = absgrad_refused(any_abs, b.map_off)) return rc;
     if (P < 0 || width <= 0 || height <= 0 || (long long)width * height > (1ll << 30)) { set_last_error("bad sizes"); return DGR_ERR_BAD_ARGUMENT; }
+    if (b.D < 0 || b.D > 3) { set_last_error(BAD_DEGREE); return DGR_ERR_BAD_ARGUMENT; }
     for (int v = 0; v < n_views; v++)
         if (!views[v].dL_dview) { set_last_error("view without dL_dview"); return DGR_ERR_BAD_ARGUMENT; }
     if (P > 0 && !b.cov3D_precomp && (!b.scales || !b.rotations)) { set_last_error("backward: need scale/rotation or cov3D"); return DGR_ERR_BAD_ARGUMENT; }
@@ -679,6 +692,7 @@ int backward_batch(hipStream_t st, dgr::PreprocessBwdArgs b, const float* backgr
     }
     if ((rc = joined.done())) return rc;
     bb.V = n_views;
+    if ((rc = zero_wide_sh_rows(b, st))) return rc;
     { ScopedStage t(ST_PRE_BWD, st); HIP_TRY(dgr::launch_preprocess_bwd_batch(bb, st, complete)); }
     return DGR_OK;
 }

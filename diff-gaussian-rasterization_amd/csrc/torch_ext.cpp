@@ -206,7 +206,8 @@ struct AbsGrad {
 // The flat arena of the eight per-Gaussian gradients (dgr_amd.light._grad_arena): segments in the order means3D, means2D,
 // sh, opacity, scales, rotations | cov3D, colors, 256-byte aligned; the first six are one contiguous span = the multi-GPU
 // all-reduce payload.  g[] receives them in the return order of the reference binding: means2D, colors, opacity, means3D,
-// cov3D, sh, scales, rotations.  Every row is written by the kernels (zeros for invisible Gaussians): no zero-fill.
+// cov3D, sh, scales, rotations.  Every row is written by the kernels (zeros for invisible Gaussians; M > 16: api.hip clears dL_dsh
+// first): no zero-fill.
 inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g, float** gp) {
     carve(dev, {{&g[3], {P, 3}, at::kFloat}, {&g[0], {P, 3}, at::kFloat}, {&g[5], {P, M, 3}, at::kFloat}, {&g[2], {P, 1}, at::kFloat},
                 {&g[6], {P, 3}, at::kFloat}, {&g[7], {P, 4}, at::kFloat}, {&g[4], {P, 6}, at::kFloat}, {&g[1], {P, 3}, at::kFloat}});

@@ -94,7 +94,7 @@ def _grad_arena(P, M, f32):
     """One flat arena holds every per-Gaussian gradient (returned as views), ordered so that the tensors a
     mapping step all-reduces across GPUs -- means3D, means2D, sh, opacity, scales, rotations -- are one
     contiguous span (dgr_amd.multiview.GradientArena).  Every row is written by the kernels (zeros for
-    invisible Gaussians), so the arena is not zero-filled."""
+    invisible Gaussians; the library clears dL_dsh itself when M > 16), so the arena is not zero-filled."""
     shapes = [("means3D", (P, 3)), ("means2D", (P, 3)), ("sh", (P, M, 3)), ("opacity", (P, 1)),
               ("scales", (P, 3)), ("rotations", (P, 4)), ("cov3D", (P, 6)), ("colors", (P, 3))]
     offs, o = {}, 0

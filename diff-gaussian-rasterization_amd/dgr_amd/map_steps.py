@@ -118,14 +118,25 @@ class _ModelTable:
             _in_place(m, f"a moment of params[{name!r}]", self.who)
         return state
 
+    def carry_empty(self, t, tail):  # a leaf or moment without a value per row (a degree-0 model's [P, 0, 3] f_rest): no kernel sees it
+        return t
+
     def add_leaves(self, fields_of, moment_fields):
-        # every leaf as `fields_of(name)` = (mode[, value]) says, each followed by its two moments where the optimiser has them
+        # every leaf as `fields_of(name)` = (mode[, value]) says, each followed by its two moments where the optimiser has them;
+        # a leaf of zero width has no row of the table (the C ABI refuses k < 1 and a NULL tensor): it is carried as it is
         add, state_of = self.add, self.optimizer.state if self.optimizer is not None else {}
         for name, t in self.src.items():
             tail = tuple(t.shape[1:])
-            k = max(math.prod(tail), 1)
-            self.out[name] = add(t, tail, k, *fields_of(name))
+            k = math.prod(tail)
             state = state_of.get(self.params[name])
+            if k == 0:
+                self.out[name] = self.carry_empty(t, tail)
+                if state is not None:
+                    if any(m.shape != t.shape or m.dtype != torch.float32 or m.device != t.device for m in state):
+                        raise RuntimeError(f"{self.who}: the moments of params[{name!r}] must have its shape, dtype and device")
+                    self.moments[name] = tuple(self.carry_empty(m, tail) for m in state)
+                continue
+            self.out[name] = add(t, tail, k, *fields_of(name))
             if state is not None:
                 self.moments[name] = tuple(add(m, tail, k, *moment_fields) for m in self.check_moments(name, t, state))
 
@@ -170,6 +181,9 @@ class _ResizeStep(_ModelTable):
         dst = torch.empty((self.P_new,) + tail, dtype=torch.float32, device=self.dev)
         self.table.append((src, dst, k, mode, value))
         return dst
+
+    def carry_empty(self, t, tail):  # ... of the new length
+        return torch.empty((self.P_new,) + tail, dtype=torch.float32, device=self.dev)
 
     def check_moments(self, name, t, state):
         return state[0].contiguous(), state[1].contiguous()

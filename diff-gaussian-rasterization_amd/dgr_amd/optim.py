@@ -90,6 +90,8 @@ class SparseAdam:
                     s = self.state.get(p)
                     if s is None:
                         s = self.state[p] = (torch.zeros_like(p), torch.zeros_like(p))
+                    if p.numel() == 0:  # no value to update (a degree-0 model's [P, 0, 3] f_rest): the library refuses k < 1
+                        continue
                     rows = p.shape[0]
                     call(entry, rows, p.numel() // max(rows, 1), p.data_ptr(), grad.data_ptr(), s[0].data_ptr(), s[1].data_ptr(),
                          vis, float(g["lr"]), float(b1), float(b2), float(g["eps"]), step)

@@ -68,7 +68,10 @@ int dgr_mark_visible(void* stream, int P, const float* means3D, const float* vie
  * Like the reference it blocks the host once (to size the binning buffer) and returns num_rendered.
  * Outputs need NOT be zero-initialised (the reference's binding zero-fills them first,
  * L/rasterize_points.cu:69-76; here every element is written).  `out_depth_var` is written as 0
- * (L/cr/forward.cu:317,410).  `radii` may be NULL (L/cr/rasterizer_impl.cu:235-238). */
+ * (L/cr/forward.cu:317,410).  `radii` may be NULL (L/cr/rasterizer_impl.cu:235-238).
+ * SH layout, here and in every entry point that takes (D, M, shs): `shs` is [P, M, 3] with any M >= 1 and any alignment; D = 0 .. 3
+ * (else DGR_ERR_BAD_ARGUMENT); coefficients beyond M count as zero; dL_dsh is [P, M, 3] and coefficients beyond 16 get zero gradient.
+ * (The map steps below refuse a tensor with k < 1 values per row: dgr_amd.map_steps hands them no leaf of zero width, which is legal there.) */
 int dgr_light_forward(void* stream, dgr_alloc_fn geometryBuffer, dgr_alloc_fn binningBuffer, dgr_alloc_fn imageBuffer,
                       void* alloc_user, int P, int D, int M, const float* background, int width, int height,
                       const float* means3D, const float* shs, const float* colors_precomp, const float* opacities,

@@ -15,6 +15,10 @@ def dev():
 
 
 def T(a):
+    """a host array as a fresh (256-byte aligned, contiguous) device tensor; a device tensor as it is -- the way a scene carries
+    an input whose placement is the point (tests/test_hip_sh_layouts.py: SH rows that are 4-byte aligned only)"""
+    if isinstance(a, torch.Tensor):
+        return a
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
 
 

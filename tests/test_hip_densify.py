@@ -359,3 +359,26 @@ def test_a_capturing_stream_is_refused_and_the_capture_goes_on():
     # and outside the capture the same call works
     out, _, _, _, counts = densify_and_prune(params, None, accum, denom, None, **kw)
     assert tuple(counts) == (64, 64, 0, 0, 0) and bits_equal(out["xyz"], L["xyz"])
+
+
+@pytest.mark.parametrize("capturable", [False, True], ids=["eager", "capturable"])
+def test_a_degree_zero_model_with_an_empty_f_rest(capturable):
+    """3DGS's degree-0 model has f_rest [P, 0, 3]: the step runs, f_rest and its moments come back [rows, 0, 3], and everything
+    else carries the bits of the same call without that leaf (tests/degree_zero.py) -- before and after a further step()."""
+    import degree_zero
+    d, P = dev(), 549
+    L, _, accum, denom, maxr, noise, kw = mixed_case(P, 11 + P)
+    seen = {}
+    for with_rest in (False, True):
+        params = degree_zero.model(L, d, with_rest)
+        opt = degree_zero.stepped_adam(params, capturable)
+        out, a, dn, mr, counts = densify_and_prune(params, opt, accum.to(d), denom.to(d), maxr.to(d), noise=noise.to(d), **kw)
+        assert counts.rows not in (0, P) and counts.clones > 0 and counts.children > 0 and counts.survivors < P
+        after = degree_zero.snapshot(out, opt, xyz_gradient_accum=a, denom=dn, max_radii2D=mr, counts=tuple(counts))
+        if with_rest:
+            degree_zero.check_rest(out, opt, counts.rows)
+        degree_zero.step_again(opt, out, capturable)
+        assert opt.steps == 2 + (1 if capturable else 0)  # (the replays advance the device's count only)
+        seen[with_rest] = (after, degree_zero.snapshot(out, opt))
+    for with_leaf, without in zip(seen[True], seen[False]):
+        degree_zero.assert_same_bits(with_leaf, without)

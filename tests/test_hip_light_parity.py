@@ -133,16 +133,18 @@ IMAGES = ("color", "depth", "depth_median", "opacity_map")
 
 
 def check_backward(oracle, s, deg, track_off=False, map_off=False, end_to_end=True, scale_modifier=1.0, view_rel_to_max=1e-5,
-                   rel_to_max=1e-5, what=None):
+                   rel_to_max=1e-5, what=None, hip_scene=None):
+    """`hip_scene`: the scene as the HIP side gets it, where some input is a device tensor placed by the test (hh.T)"""
     P, W, H = s.P, s.W, s.H
     grads = tuple(g * (W * H) ** 0.5 for g in (s.gC, s.gD, s.gM, s.gV))  # pixel sums of O(1)
+    ref_scene, s = s, (s if hip_scene is None else hip_scene)
     out, d = hh.hip_forward(s, deg, scale_modifier=scale_modifier)
-    st, ref = hh.oracle_forward(oracle, s, deg, scale_modifier=scale_modifier)
+    st, ref = hh.oracle_forward(oracle, ref_scene, deg, scale_modifier=scale_modifier)
     # pixels where the two forward passes decided a hard threshold differently get zero incoming gradient on both
     # sides (tests/util.py): no skipped comparison, no outlier rows for them
     grads, _ = mask_flipped_pixels(grads, hh.hip_state("n_contrib", s, d), st.get("n_contrib"), W, H, what or f"light P={P}",
                                    images=[(d[k], ref[k]) for k in IMAGES], median_margin=oracle.light_median_margin(st, ref["opacity_map"]))
-    gr = hh.oracle_backward(oracle, st, s, deg, ref["opacity_map"], track_off=track_off, map_off=map_off, grads=grads,
+    gr = hh.oracle_backward(oracle, st, ref_scene, deg, ref["opacity_map"], track_off=track_off, map_off=map_off, grads=grads,
                             scale_modifier=scale_modifier)
     for label, alphas in (("isolated", ref["opacity_map"]), ("end-to-end", None))[:2 if end_to_end else 1]:
         g = hh.hip_backward(s, deg, out, track_off=track_off, map_off=map_off, grads=grads, alphas=alphas, scale_modifier=scale_modifier)

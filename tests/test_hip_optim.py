@@ -114,3 +114,46 @@ def test_capturable_steps_match_and_replay_from_a_graph():
     torch.cuda.synchronize()
     for p, q in zip(a, b):
         np.testing.assert_allclose(p.detach().cpu().numpy(), q.detach().cpu().numpy(), rtol=5e-6, atol=2e-7)
+
+
+@pytest.mark.parametrize("capturable", [False, True], ids=["eager", "capturable"])
+def test_a_parameter_of_zero_width_gets_its_empty_state_and_is_skipped(capturable):
+    """A degree-0 model's f_rest is [P, 0, 3], and autograd hands it a [P, 0, 3] gradient: the step creates its (empty) moments and
+    launches nothing for it -- the library refuses k < 1 -- and the other parameters and moments carry the bits of the steps taken
+    without it: dense, with a visibility mask, and (capturable) replayed from a graph."""
+    dev = torch.device("cuda:0")
+    P = 700
+    radii = (torch.arange(P, device=dev) % 3 != 0).to(torch.int32) * 7
+
+    def run(with_empty):
+        params = [t.clone().requires_grad_() for t in make(P, dev, 7)]
+        grads = make(P, dev, 8)
+        empty = torch.zeros((P, 0, 3), device=dev, requires_grad=True)
+        if with_empty:
+            params.insert(2, empty)
+            grads.insert(2, torch.zeros((P, 0, 3), device=dev))
+        for p, g in zip(params, grads):
+            p.grad = g
+        opt = SparseAdam(params, lr=2e-3, capturable=capturable)
+        opt.step()
+        opt.step(visible=radii)
+        if capturable:
+            graph = torch.cuda.CUDAGraph()
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(graph, stream=side):
+                    opt.step()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            for _ in range(3):
+                graph.replay()
+        torch.cuda.synchronize()
+        if with_empty:
+            assert [tuple(m.shape) for m in opt.state[empty]] == [(P, 0, 3)] * 2 and len(opt.state) == 5
+        kept = [p for p in params if p is not empty]
+        return opt.steps, [t.detach().cpu() for p in kept for t in (p,) + tuple(opt.state[p])]
+
+    (steps_a, a), (steps_b, b) = run(True), run(False)
+    assert steps_a == steps_b == (3 if capturable else 2) and len(a) == len(b) == 12
+    for x, y in zip(a, b):
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32))

@@ -343,3 +343,30 @@ def test_recorded_into_a_graph_the_step_draws_fresh_numbers_on_every_replay():
             for ma, mb in zip(oa.state[pa[name]], ob.state[pb[name]]):
                 assert np.array_equal(bits(ma), bits(mb)), (value, name)
     assert relocated[0] > 50 and relocated[1] > 0, relocated
+
+
+@pytest.mark.parametrize("capturable", [False, True], ids=["eager", "capturable"])
+def test_a_degree_zero_model_with_an_empty_f_rest(capturable):
+    """3DGS's degree-0 model has f_rest [P, 0, 3]: the step runs in place, f_rest and its moments stay the (empty) tensors they
+    were, and everything else carries the bits of the same call without that leaf (tests/degree_zero.py) -- before and after a
+    further step()."""
+    import degree_zero
+    d, P = dev(), 549
+    L, _, A, draws = make_case(P, 100 + P, 0.3)
+    seen = {}
+    for with_rest in (False, True):
+        params = degree_zero.model(L, d, with_rest)
+        opt = degree_zero.stepped_adam(params, capturable)
+        rest = params.get("f_rest")
+        rest_moments = opt.state.get(rest) if with_rest else None
+        acc = {name: t.to(d) for name, t in A.items()}
+        res = relocate_dead(params, opt, draws=draws.to(d), **acc)
+        after = degree_zero.snapshot(params, opt, counts=res.counts, source=res.source, **acc)
+        assert int(after["counts"][2]) > 0.2 * P  # (rows were relocated)
+        if with_rest:
+            degree_zero.check_rest(params, opt, P)
+            assert params["f_rest"] is rest and all(x is y for x, y in zip(opt.state[rest], rest_moments))
+        degree_zero.step_again(opt, params, capturable)
+        seen[with_rest] = (after, degree_zero.snapshot(params, opt))
+    for with_leaf, without in zip(seen[True], seen[False]):
+        degree_zero.assert_same_bits(with_leaf, without)

@@ -440,3 +440,30 @@ def test_a_seeded_map_explains_its_own_frame():
                                               cam.fx, cam.fy, cam.cx, cam.cy, opacity_map=torch.from_numpy(opacity_map).to(d),
                                               silhouette_threshold=0.5)
     assert tuple(counts2) == (counts.rows, 0, cam.W * cam.H, 0, 0) and again is out
+
+
+@pytest.mark.parametrize("capturable", [False, True], ids=["eager", "capturable"])
+def test_a_degree_zero_model_with_an_empty_f_rest(capturable):
+    """3DGS's degree-0 model has f_rest [P, 0, 3]: the step runs, f_rest and its moments come back [rows, 0, 3], and everything
+    else carries the bits of the same call without that leaf (tests/degree_zero.py) -- before and after a further step()."""
+    import degree_zero
+    d, P = dev(), 300
+    L, _, A = state_of(P, 8)
+    f = frame(37, 23, 8)
+    cam = f["cam"]
+    images, kw = selection(f, MASKS["both"])
+    seen = {}
+    for with_rest in (False, True):
+        params = degree_zero.model(L, d, with_rest)
+        opt = degree_zero.stepped_adam(params, capturable)
+        out, a, dn, mr, counts = seed_from_frame(params, opt, f["color_obs"].to(d), f["depth_obs"].to(d), f["view"].to(d), cam.fx, cam.fy,
+                                                 cam.cx, cam.cy, **{n: t.to(d) for n, t in images.items()},
+                                                 **{n: t.to(d) for n, t in A.items()}, **kw)
+        assert counts.new > 0 and counts.rows == P + counts.new
+        after = degree_zero.snapshot(out, opt, xyz_gradient_accum=a, denom=dn, max_radii2D=mr, counts=tuple(counts))
+        if with_rest:
+            degree_zero.check_rest(out, opt, counts.rows)
+        degree_zero.step_again(opt, out, capturable)
+        seen[with_rest] = (after, degree_zero.snapshot(out, opt))
+    for with_leaf, without in zip(seen[True], seen[False]):
+        degree_zero.assert_same_bits(with_leaf, without)

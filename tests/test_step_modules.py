@@ -264,6 +264,93 @@ def test_relocate_dead_refuses_a_strided_leaf_before_it_copies_any(stub, monkeyp
     assert copies == [] and stub.calls == []
 
 
+def _descriptors(stub, entry):
+    """every descriptor that reached `entry` (a dgr_*_apply), as tuples of its fields, with the count handed over beside the array"""
+    rows = []
+    for name, args in stub.calls:
+        if name != entry:
+            continue
+        (i, descs), = [(i, a) for i, a in enumerate(args) if isinstance(a, ctypes.Array)]
+        assert args[i - 1] == len(descs)
+        rows += [tuple(getattr(d, f) for f, _ in d._fields_) for d in descs]
+    return rows
+
+
+def test_a_zero_width_leaf_reaches_no_kernel(stub, monkeypatch):
+    """A degree-0 model as 3DGS builds it: f_dc [P, 1, 3] and f_rest [P, 0, 3].  The C ABI refuses a descriptor with k < 1 or a NULL
+    tensor, so none may leave Python: the descriptors of densify_and_prune, seed_from_frame and relocate_dead, and the calls of
+    SparseAdam.step (eager and capturable), are those of the same call on the model without f_rest; f_rest and its moments come
+    back empty, with the new number of rows, `requires_grad` kept, and the optimiser pointed at them."""
+    real_empty, real_full = torch.empty, torch.full
+    monkeypatch.setattr(torch, "empty", lambda *a, device=None, **kw: real_empty(*a, **kw))
+    monkeypatch.setattr(torch, "full", lambda *a, device=None, **kw: real_full(*a, **kw))
+    P = 5
+    base = {"xyz": _fake(P, 3), "f_dc": _fake(P, 1, 3, seed=2), "opacity": _fake(P, 1), "scaling": _fake(P, 3, seed=1),
+            "rotation": _fake(P, 4)}
+    for t in base.values():
+        t.requires_grad_()
+    f_rest = _fake(P, 0, 3).requires_grad_()
+    assert f_rest.shape == (P, 0, 3) and f_rest.is_cuda
+    with_rest = dict(list(base.items())[:2] + [("f_rest", f_rest)] + list(base.items())[2:])
+    moments = {name: (_fake(*t.shape, seed=4), _fake(*t.shape, seed=5)) for name, t in with_rest.items()}
+    acc = (_fake(P, 1), _fake(P, 1), _fake(P))
+
+    def adam_over(params):
+        adam = optim.SparseAdam(list(params.values()))
+        adam.state = {t: moments[name] for name, t in params.items()}
+        return adam
+
+    steps = {
+        "dgr_densify_apply": lambda params, adam: map_steps.densify_and_prune(params, adam, *acc, grad_threshold=0.1, extent=2.0)[0],
+        "dgr_seed_apply": lambda params, adam: map_steps.seed_from_frame(params, adam, _fake(3, 4, 6), _fake(4, 6), _fake(16), 5.0, 5.0,
+                                                                         3.0, 2.0, stride=2, xyz_gradient_accum=acc[0])[0],
+        "dgr_relocate_apply": lambda params, adam: (map_steps.relocate_dead(params, adam, xyz_gradient_accum=acc[0], denom=acc[1]), params)[1],
+    }
+    for entry, run in steps.items():
+        seen = {}
+        for label, params in (("without", base), ("with", with_rest)):
+            del stub.calls[:]
+            adam = adam_over(params)
+            out = run(dict(params), adam)
+            seen[label] = rows = _descriptors(stub, entry)
+            n_leaves = len(base)
+            assert len(rows) >= 3 * n_leaves, entry  # every leaf with its two moments, then the accumulators
+            for row in rows:
+                fields = dict(zip([f for f, _ in {"dgr_densify_apply": _capi.DensifyTensor, "dgr_seed_apply": _capi.SeedTensor,
+                                                 "dgr_relocate_apply": _capi.RelocateTensor}[entry]._fields_], row))
+                assert fields["k"] >= 1, (entry, label, fields)
+                assert fields.get("dst", 1) and fields.get("data", 1), (entry, label, fields)  # (a NULL src is a mode's: zeros, constants)
+            if label == "with":
+                rows_new = P if entry == "dgr_relocate_apply" else 7  # (the stub's plan: 7 rows after either resize)
+                got = out["f_rest"]
+                assert got.shape == (rows_new, 0, 3) and got.requires_grad and got.dtype == torch.float32
+                assert got in adam.state and [tuple(m.shape) for m in adam.state[got]] == [(rows_new, 0, 3)] * 2
+                assert any(p is got for g in adam.param_groups for p in g["params"])
+                assert all(out[name].shape[0] == rows_new for name in base)
+        # the same descriptors, in the same order (a resize writes into tensors of its own: `dst` differs from call to call)
+        strip = (lambda row: row[:1] + row[2:]) if entry != "dgr_relocate_apply" else (lambda row: row)
+        assert [strip(r) for r in seen["with"]] == [strip(r) for r in seen["without"]], entry
+
+    for t in with_rest.values():
+        t.grad = _fake(*t.shape, seed=3)
+    for capturable in (False, True):
+        entry = "dgr_sparse_adam_capturable" if capturable else "dgr_sparse_adam"
+        seen = {}
+        for label, params in (("without", base), ("with", with_rest)):
+            del stub.calls[:]
+            adam = optim.SparseAdam(list(params.values()), lr=0.01, capturable=capturable)
+            adam.step()
+            adam.step(visible=_fake(P, dtype=torch.int32))
+            calls = [a for name, a in stub.calls if name == entry]
+            assert len(calls) == len(stub.calls) == 2 * len(base)
+            for a in calls:  # (stream, rows, k, parameter, gradient, exp_avg, exp_avg_sq, ...)
+                assert a[1] == P and a[2] >= 1 and all(a[3:7]), (entry, label, a[:7])
+            seen[label] = [a[1:5] for a in calls]
+            if label == "with":
+                assert [tuple(m.shape) for m in adam.state[f_rest]] == [(P, 0, 3)] * 2 and adam.steps == 2
+        assert seen["with"] == seen["without"], entry
+
+
 @pytest.mark.gpu
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason=f"needs two GPUs, this machine has {torch.cuda.device_count()}")
 def test_steps_follow_their_tensors_device_not_the_current_one():
