@@ -15,7 +15,8 @@ int refuse(const char* who, const char* bad) {  // a refusal: "<entry point>: <w
     return DGR_ERR_BAD_ARGUMENT;
 }
 
-// What the plan and apply entry points of the map steps (densify-and-prune, map expansion, relocation, position noise) check alike:
+// What the plan and apply entry points of the map steps (densify-and-prune, map expansion, relocation, position noise, map
+// correction) check alike:
 const long PLAN_MAX_ROWS = 0x3fffffffL;  // densify's P' <= 2 rows and seed's rows + candidates must fit the int counts
 
 thread_local std::string named_error;  // a message that names the caller's argument, kept until the thread's next one
@@ -180,6 +181,50 @@ int dgr_position_noise(void* stream, long P, float* xyz, const float* scaling_ra
     if (bad) return refuse("dgr_position_noise", bad);
     HIP_TRY(dgr::launch_position_noise((size_t)P, xyz, scaling_raw, rotation, opacity_raw, noise, seed, step, step_device, lr,
                                        lr_device, scale, k, x0, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+static const long TRANSFORM_MAX_K = 1L << 20;
+size_t dgr_transform_scratch_bytes(long K) { return K < 1 || K > TRANSFORM_MAX_K ? 0 : dgr::transform_scratch_bytes((size_t)K); }
+
+int dgr_transform_plan(void* stream, long K, const float* transforms, void* scratch, int* counts4_device) {
+    const char* bad = K < 1 || K > TRANSFORM_MAX_K ? "K must be 1 .. 2^20" : nullptr;
+    if (!bad && !transforms) bad = "transforms is NULL";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && !counts4_device) bad = "counts4_device is NULL";
+    if (bad) return refuse("dgr_transform_plan", bad);
+    HIP_TRY(dgr::launch_transform_plan((int)K, transforms, scratch, counts4_device, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_transform_apply(void* stream, long P, long K, const void* scratch, const float* anchor, int n,
+                        const dgr_transform_tensor* tensors, int* counts4_device) {
+    const char* bad = plan_args_error(P, K < 1 || K > TRANSFORM_MAX_K ? "K must be 1 .. 2^20" : nullptr, scratch, false, nullptr, "P",
+                                      "scratch");
+    if (!bad && !counts4_device) bad = "counts4_device is NULL";
+    int n_xyz = 0, n_quat = 0, n_scale = 0;
+    if (!bad)
+        bad = tensor_table_error(
+            n, tensors, DGR_TRANSFORM_MAX_TENSORS, "n must be 1 .. DGR_TRANSFORM_MAX_TENSORS (24) tensors", DGR_TRANSFORM_XYZ,
+            DGR_TRANSFORM_SH + DGR_TRANSFORM_MOMENT2, DGR_TRANSFORM_XYZ, n_xyz, [&](const dgr_transform_tensor& t) -> const char* {
+                const int kind = t.mode & ~3, order = t.mode & 3;
+                if (order > DGR_TRANSFORM_MOMENT2 || (kind == DGR_TRANSFORM_LOG_SCALE && order != DGR_TRANSFORM_VALUE)) return "unknown mode";
+                if (P > 0 && !t.data) return "a tensor with NULL data";
+                if (kind == DGR_TRANSFORM_XYZ && t.k != 3) return "an XYZ tensor must have k = 3";
+                if (kind == DGR_TRANSFORM_QUAT && t.k != 4) return "a QUAT tensor must have k = 4";
+                if (kind == DGR_TRANSFORM_LOG_SCALE && t.k != 3) return "a LOG_SCALE tensor must have k = 3";
+                if (kind != DGR_TRANSFORM_SH && t.skip != 0) return "skip must be 0 for a tensor that is not SH";
+                if (kind == DGR_TRANSFORM_SH) {
+                    if (t.skip != 0 && t.skip != 3) return "an SH tensor's skip must be 0 or 3";
+                    const int width = t.k - t.skip;
+                    if (width != 9 && width != 24 && width != 45) return "an SH tensor must hold the complete bands of degree 1, 2 or 3 (k - skip = 9, 24 or 45)";
+                }
+                if (t.mode == DGR_TRANSFORM_QUAT && ++n_quat > 1) return "more than one QUAT tensor";
+                if (t.mode == DGR_TRANSFORM_LOG_SCALE && ++n_scale > 1) return "more than one LOG_SCALE tensor";
+                return nullptr;
+            });
+    if (bad) return refuse("dgr_transform_apply", bad);
+    HIP_TRY(dgr::launch_transform_apply((size_t)P, (int)K, scratch, anchor, n, tensors, counts4_device, (hipStream_t)stream));
     return DGR_OK;
 }
 

@@ -2,7 +2,7 @@
 #pragma once
 #include <hip/hip_ext.h>
 #include "dgr_common.h"
-#include "../../include/dgr_hip.h"  // dgr_densify_tensor, dgr_seed_tensor, dgr_relocate_tensor
+#include "../../include/dgr_hip.h"  // dgr_densify_tensor, dgr_seed_tensor, dgr_relocate_tensor, dgr_transform_tensor
 
 namespace dgr {
 
@@ -331,6 +331,12 @@ hipError_t launch_relocate_apply(size_t P, const void* scratch, int n, const dgr
 hipError_t launch_position_noise(size_t P, float* xyz, const float* scaling_raw, const float* rotation, const float* opacity_raw,
                                  const float* noise, unsigned long long seed, int step, const int* step_dev, float lr,
                                  const float* lr_dev, float scale, float k, float x0, hipStream_t stream);
+// map correction (transform.hip): the transforms' fp32 records into `scratch` and counts[4] = {0, 0, invalid, 0} (two launches),
+// and the in-place apply over n tensors (the counts' reset and one launch)
+size_t transform_scratch_bytes(size_t K);
+hipError_t launch_transform_plan(int K, const float* transforms, void* scratch, int* counts, hipStream_t stream);
+hipError_t launch_transform_apply(size_t P, int K, const void* scratch, const float* anchor, int n,
+                                  const dgr_transform_tensor* tensors, int* counts, hipStream_t stream);
 // fused map expansion from an RGB-D keyframe (seed.hip): decide + scan over the candidate pixels into `plan` and counts[8]
 // (device), then one apply launch for n tensors (old rows copied, one new row per selected pixel)
 size_t seed_candidates(int W, int H, int stride);

@@ -1,5 +1,6 @@
 // plan.h -- what the plan-then-apply steps share (gfx950, wave64): densify-and-prune in optim.hip, map expansion in seed.hip,
-// relocation in relocate.hip.  For all three: 256-row blocks, a lane's rank in a ballot, the one-workgroup exclusive scan of the
+// relocation in relocate.hip (and, for its tensor table, the map correction in transform.hip).  For all three: 256-row blocks, a
+// lane's rank in a ballot, the one-workgroup exclusive scan of the
 // block totals (over the step's own record) and the table that deals an apply launch's tensors to workgroups.  For the two that
 // change P: the plan buffer's layout and the decide kernels' block totals.
 // plan buffer: int[16] header (0..7: the counts), int4 per 256-element block (totals, then exclusive offsets), a flag byte per element.

@@ -75,6 +75,13 @@ class RelocateTensor(C.Structure):  # dgr_relocate_tensor: one per-Gaussian tens
 assert C.sizeof(RelocateTensor) == 16  # a pointer, two ints: the C layout
 
 
+class TransformTensor(C.Structure):  # dgr_transform_tensor: one per-Gaussian tensor of a dgr_transform_apply call (rewritten in place)
+    _fields_ = [("data", _vp), ("k", _i), ("mode", _i), ("skip", _i)]
+
+
+assert C.sizeof(TransformTensor) == 24  # a pointer, three ints, padded to the pointer's alignment
+
+
 class MaskedLossParams(C.Structure):  # dgr_masked_loss_params
     _fields_ = [("depth_lo", _f), ("depth_hi", _f), ("silhouette_threshold", _f), ("outlier_factor", _f),
                 ("reject_outliers", _i), ("mask_color", _i), ("reduction", _i), ("w_color", _f), ("w_depth", _f)]
@@ -92,6 +99,9 @@ assert C.sizeof(KeyframeOverlapParams) == 40  # ten four-byte fields: the C layo
 
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
+TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
+TRANSFORM_VALUE, TRANSFORM_MOMENT1, TRANSFORM_MOMENT2 = range(3)  # DGR_TRANSFORM_<order>; a mode is kind + order
+TRANSFORM_XYZ, TRANSFORM_QUAT, TRANSFORM_LOG_SCALE, TRANSFORM_SH = 0, 4, 8, 12  # DGR_TRANSFORM_<kind>
 MASKED_LOSS_SUM, MASKED_LOSS_MEAN = 0, 1  # DGR_MASKED_LOSS_*
 MAX_BATCH_VIEWS = 8  # DGR_MAX_BATCH_VIEWS
 DENSIFY_MAX_TENSORS = 24  # DGR_DENSIFY_MAX_TENSORS
@@ -144,6 +154,9 @@ _SIGS = {
     "dgr_relocate_plan": (_i, [_vp, C.c_long, _vp, _f, _vp, C.c_ulonglong, _i, _vp, _vp, _vp, _vp]),
     "dgr_relocate_apply": (_i, [_vp, C.c_long, _vp, _i, C.POINTER(RelocateTensor), _vp, _vp, C.c_double]),
     "dgr_position_noise": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _vp, _f, _vp, _f, _f, _f]),
+    "dgr_transform_scratch_bytes": (_sz, [C.c_long]),
+    "dgr_transform_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp]),
+    "dgr_transform_apply": (_i, [_vp, C.c_long, C.c_long, _vp, _vp, _i, C.POINTER(TransformTensor), _vp]),
     "dgr_sparse_adam": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i]),
     "dgr_sparse_adam_capturable": (_i, [_vp, C.c_long, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp]),
     "dgr_set_option": (_i, [C.c_char_p, _i]),

@@ -7,6 +7,8 @@ leaf, Adam moment and accumulator in three launches (`dgr_densify_plan`, `dgr_de
 `dgr_seed_apply`).
 `relocate_dead` and `inject_position_noise` keep a map of FIXED size healthy (3DGS-MCMC's two steps; `dgr_relocate_plan`,
 `dgr_relocate_apply`, `dgr_position_noise`): in place, no host read, capturable.
+`transform_map` moves the map after a pose-graph update, every Gaussian by the Sim(3) transform of the keyframe it is anchored to
+(`dgr_transform_plan`, `dgr_transform_apply`), and `pose_corrections` forms those transforms from the old and new poses: likewise.
 All see the model through `_ModelTable`, enter the library through `_capi.StepCalls` and keep their names in `dgr_amd.optim`.
 """
 import collections
@@ -450,3 +452,111 @@ def inject_position_noise(params, lr, *, noise_scale=5e5, gate_k=100.0, gate_x0=
         abi.call("dgr_position_noise", P, _capi.ptr(xyz), _capi.ptr(scaling), _capi.ptr(rotation), _capi.ptr(opacity), _capi.ptr(noise),
                  ctypes.c_ulonglong(int(seed) & (2 ** 64 - 1)), int(step), step_dev, float(lr), lr_dev, float(noise_scale),
                  float(gate_k), float(gate_x0))
+
+
+TRANSFORM_ROLES = dict(DEFAULT_ROLES, f_rest="f_rest", shs="shs")
+TransformCounts = collections.namedtuple("TransformCounts", "transformed unanchored invalid_transforms anchored_invalid")
+
+
+class _TransformTable(_ModelTable):
+    """The table of `transform_map`: a row is (tensor, k, mode, skip), and only the leaves the transform changes have one."""
+
+    def add(self, t, tail, k, mode, skip=0):
+        self.table.append((t, k, mode, skip))
+        return t
+
+    @staticmethod
+    def fill(descs, rows):
+        for d, (t, k, mode, skip) in zip(descs, rows):
+            d.data, d.k, d.mode, d.skip = t.data_ptr(), k, mode, skip
+
+
+@torch.no_grad()
+def pose_corrections(old_viewmatrices, new_viewmatrices):
+    """The transforms `transform_map` takes, from the keyframes' poses before and after a pose-graph update: both arguments are
+    stacks [K, 4, 4] (or [K, 16]) of the rasterizer's viewmatrix W2C^T on the GPU; the result is T_k = C2W_new,k W2C_old,k as
+    float32 [K, 4, 4], row-major, old world -> new world: a Gaussian fixed in keyframe k's camera frame stays fixed in it.  Formed in
+    float64 torch ops on the device (W2C = [s R | t] is inverted in closed form, so a Sim(3) pose is taken as well as a rigid one);
+    no host read."""
+    old, new = (m.detach().reshape(-1, 4, 4).transpose(-1, -2).to(torch.float64) for m in (old_viewmatrices, new_viewmatrices))
+    if old.shape != new.shape or not old.is_cuda or not new.is_cuda:
+        raise RuntimeError("pose_corrections: two stacks of the same number of 4 x 4 viewmatrices on the GPU")
+    A, t = new[:, :3, :3], new[:, :3, 3:]
+    A_inv = A.transpose(-1, -2) / ((A * A).sum(dim=(1, 2), keepdim=True) / 3.0)  # (s R)^-1 = R^T / s
+    c2w = torch.zeros_like(new)
+    c2w[:, :3, :3], c2w[:, :3, 3:], c2w[:, 3, 3] = A_inv, -(A_inv @ t), 1.0
+    return (c2w @ old).to(torch.float32).contiguous()
+
+
+@torch.no_grad()
+def transform_map(params, optimizer, transforms, *, anchor="anchor", moments="rotate", roles=None):
+    """The map correction after a pose-graph update (loop closure, global bundle adjustment), fused and in place (include/dgr_hip.h:
+    dgr_transform_plan / dgr_transform_apply; the semantics are stated there): row i of every leaf is moved by transforms[anchor[i]].
+
+    `transforms`: float32 [K, 4, 4] on the GPU, row-major Sim(3) matrices old world -> new world (`pose_corrections` makes them);
+    they are read by the kernels, so a recorded call follows a rewritten tensor.  `anchor`: the name of a leaf of `params` ([P] or
+    [P, 1], what `seed_from_frame(fill={"anchor": k})` wrote and densify_and_prune / relocate_dead copied), a float32 [P] tensor, or
+    None for one global transform (transforms[0]).  A row whose anchor is not an integer in 0 .. K - 1, or whose transform is not a
+    similarity (not finite, det <= 0, A^T A / s^2 off the identity by more than 1e-3), keeps its bits.
+    `roles` as relocate_dead's, plus "f_rest" ([P, M, 3], M = 0, 3, 8 or 15) and "shs" ([P, M + 1, 3], the DC row stays); either may
+    be absent.  xyz -> A x + t, rotation -> q_R (x) q, scaling -> + log s, the SH bands by their rotation matrices; opacity, f_dc
+    and every other leaf are invariant.  `moments`: "rotate" takes the Adam moments of those leaves along (exp_avg as a covector,
+    exp_avg_sq by the squared matrices: the diagonal of the rotated second moment, the project's choice), "keep" leaves the
+    optimiser's state alone.  Everything is rewritten in place: leaves and moments must be contiguous and stay the same tensor
+    objects, P does not change, the optimiser is not re-pointed.
+
+    Returns the counts as an int32 [4] device tensor (`TransformCounts` names the fields): rows transformed, rows whose anchor names
+    no transform, invalid transforms, rows anchored to an invalid transform.  No host read: it can be recorded into a hipGraph."""
+    who = "transform_map"
+    if moments not in ("rotate", "keep"):
+        raise ValueError(f"{who}: moments must be 'rotate' or 'keep'")
+    work = _TransformTable(who, params, optimizer if moments == "rotate" else None, roles, TRANSFORM_ROLES)
+    roles, P = work.roles, work.locate()
+    with _capi.StepCalls(work.dev) as abi:
+        leaves = work.check_leaves()
+        if (not isinstance(transforms, torch.Tensor) or not transforms.is_cuda or transforms.dtype != torch.float32 or
+                transforms.dim() != 3 or tuple(transforms.shape[1:]) != (4, 4) or not transforms.is_contiguous() or
+                transforms.device != work.dev):
+            raise RuntimeError(f"{who}: transforms must be a contiguous float32 GPU tensor [K, 4, 4] on the leaves' device")
+        K = transforms.shape[0]
+        if isinstance(anchor, str):
+            if anchor not in params:
+                raise KeyError(f"{who}: params has no anchor leaf {anchor!r} (pass a tensor, or None for one global transform)")
+            if anchor in (roles[r] for r in roles):
+                raise KeyError(f"{who}: the anchor leaf {anchor!r} has a role")
+            anchor_t = leaves[anchor]
+        else:
+            anchor_t = None if anchor is None else _rows_tensor(anchor, P, "anchor", who)
+        if anchor_t is not None and (anchor_t.numel() != P or not anchor_t.is_contiguous() or anchor_t.device != work.dev):
+            raise RuntimeError(f"{who}: the anchor must be a contiguous float32 [P] or [P, 1] tensor on the leaves' device")
+        kind_of = {roles["xyz"]: _capi.TRANSFORM_XYZ, roles["rotation"]: _capi.TRANSFORM_QUAT,
+                   roles["scaling"]: _capi.TRANSFORM_LOG_SCALE}
+        state_of = work.optimizer.state if work.optimizer is not None else {}
+        for name, t in leaves.items():
+            kind, skip = kind_of.get(name), 0
+            if name in (roles["f_rest"], roles["shs"]):
+                skip = 3 if name == roles["shs"] else 0
+                if t.dim() != 3 or t.shape[2] != 3 or t.shape[1] - skip // 3 not in (0, 3, 8, 15):
+                    raise RuntimeError(f"{who}: params[{name!r}] must be [P, M{' + 1' if skip else ''}, 3] with M = 0, 3, 8 or 15 "
+                                       "(the complete bands of degree 1 .. 3)")
+                kind = _capi.TRANSFORM_SH if t.shape[1] - skip // 3 else None  # nothing above the DC row: nothing rotates
+            if kind is None:
+                continue
+            tail = tuple(t.shape[1:])
+            k = math.prod(tail)
+            work.add(_in_place(t, f"params[{name!r}]", who), tail, k, kind + _capi.TRANSFORM_VALUE, skip)
+            state = state_of.get(params[name])
+            if state is not None and kind != _capi.TRANSFORM_LOG_SCALE:
+                m1, m2 = work.check_moments(name, t, state)
+                work.add(m1, tail, k, kind + _capi.TRANSFORM_MOMENT1, skip)
+                work.add(m2, tail, k, kind + _capi.TRANSFORM_MOMENT2, skip)
+
+        nbytes = abi.lib.dgr_transform_scratch_bytes(K)
+        if nbytes == 0:
+            raise RuntimeError(f"{who}: {K} transforms are refused (1 .. 2^20)")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=work.dev)
+        counts = torch.empty(4, dtype=torch.int32, device=work.dev)
+        abi.call("dgr_transform_plan", K, transforms.data_ptr(), scratch.data_ptr(), counts.data_ptr())
+        work.apply(_capi.TransformTensor, _capi.TRANSFORM_MAX_TENSORS, lambda n, descs: abi.call(
+            "dgr_transform_apply", P, K, scratch.data_ptr(), _capi.ptr(anchor_t), n, descs, counts.data_ptr()))
+    return counts

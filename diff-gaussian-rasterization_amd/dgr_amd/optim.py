@@ -9,9 +9,9 @@ The steps that work on the whole map live in `dgr_amd.map_steps`; their public n
 import torch
 
 from . import _capi
-from .map_steps import (DEFAULT_ROLES, SEED_ROLES, DensifyCounts, RelocateResult, SeedCounts,  # noqa: F401
-                        add_densification_stats, densify_and_prune, densify_thresholds, inject_position_noise, relocate_dead,
-                        seed_constants, seed_from_frame)
+from .map_steps import (DEFAULT_ROLES, SEED_ROLES, TRANSFORM_ROLES, DensifyCounts, RelocateResult, SeedCounts,  # noqa: F401
+                        TransformCounts, add_densification_stats, densify_and_prune, densify_thresholds, inject_position_noise,
+                        pose_corrections, relocate_dead, seed_constants, seed_from_frame, transform_map)
 
 
 class SparseAdam:

@@ -31,9 +31,16 @@ opacity and scale (--relocate-start K: not before iteration K, the method's warm
 a tensor or reads anything on the host, so both go together with --graph and --fused: the step runs between replays, with no
 re-recording.  The logged counts are the step's one host read.
 
+--loop-close-at N (with --seed) is the pose-graph update of a SLAM back end: every keyframe is seeded before the first iteration,
+each Gaussian remembering its keyframe in the role-less leaf "anchor" (seed_from_frame's `fill`); after iteration N the keyframes'
+poses get seeded rigid corrections and optim.transform_map moves every Gaussian, with its Adam moments, by the correction of its
+keyframe (optim.pose_corrections forms them from the old and new poses on the device).  In place and without a host read: it goes
+together with --graph and --fused, between replays.  The losses before and after are logged.
+
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
                              [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked] [--select K]
                              [--relocate-every N [--relocate-start K] [--position-noise] [--relocate-min-opacity 0.005]]
+                             [--loop-close-at N [--loop-close-seed S]]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -100,8 +107,9 @@ class SeededMapModel(MapModel):
     """A MapModel that starts empty and grows by seed_from_frame.  3DGS's own leaves: the SH coefficients are split into the
     degree-0 ones (f_dc, which a seed takes from the observed colour) and the rest."""
 
-    def __init__(self, dev):
+    def __init__(self, dev, anchored=False):
         empty = lambda *shape: torch.zeros(shape, device=dev).requires_grad_()  # noqa: E731
+        self._anchor = torch.zeros(0, device=dev) if anchored else None  # the keyframe each Gaussian was seeded from (no gradient)
         self._xyz, self._f_dc, self._f_rest = empty(0, 3), empty(0, 1, 3), empty(0, 15, 3)
         self._opacity, self._scaling, self._rotation = empty(0, 1), empty(0, 3), empty(0, 4)
         self.active_sh_degree = 3
@@ -112,12 +120,14 @@ class SeededMapModel(MapModel):
     get_features = property(lambda self: torch.cat([self._f_dc, self._f_rest], dim=1))
 
     def leaves(self):
-        return {"xyz": self._xyz, "f_dc": self._f_dc, "f_rest": self._f_rest, "opacity": self._opacity, "scaling": self._scaling,
-                "rotation": self._rotation}
+        leaves = {"xyz": self._xyz, "f_dc": self._f_dc, "f_rest": self._f_rest, "opacity": self._opacity, "scaling": self._scaling,
+                  "rotation": self._rotation}
+        return leaves if self._anchor is None else dict(leaves, anchor=self._anchor)
 
     def replace(self, leaves, xyz_gradient_accum, denom, max_radii2D):
         self._xyz, self._f_dc, self._f_rest = leaves["xyz"], leaves["f_dc"], leaves["f_rest"]
         self._opacity, self._scaling, self._rotation = leaves["opacity"], leaves["scaling"], leaves["rotation"]
+        self._anchor = leaves.get("anchor")
         self.xyz_gradient_accum, self.denom, self.max_radii2D = xyz_gradient_accum, denom, max_radii2D
 
     def groups(self):
@@ -128,7 +138,8 @@ class SeededMapModel(MapModel):
 
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
                  absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0, relocate_every=0,
-                 position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0):
+                 position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0, loop_close_at=0,
+                 loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -147,10 +158,17 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     ones (generator keyed by `relocate_seed`) and, with position_noise=True, inject_position_noise follows; in place, also with
     graph=True (between replays) and fused=True.  relocate_start=K: not before iteration K (3DGS-MCMC's warm-up: a split Gaussian
     moves twice as fast, which costs loss while the optimiser is still in its first descent).  The model's `relocations` attribute then lists each step's counts
-    [dead, live, relocated, sources hit, largest hits]."""
+    [dead, live, relocated, sources hit, largest hits].
+    loop_close_at=N (with seed=True): a pose-graph update after iteration N.  Every keyframe is seeded before the first iteration
+    (so the map and the window are fixed from then on, and graph=True and fused=True are allowed), with its index in the role-less
+    leaf "anchor".  After iteration N the keyframes' poses change -- one rigid motion of size `loop_close_scale` (radians and scene
+    units; 0: none) shared by all of them, as a loop closure moves a stretch of trajectory, followed by each keyframe's own of a
+    hundredth of that, drawn from `loop_close_seed` -- and transform_map moves every Gaussian with its keyframe (between replays
+    with graph=True; loop_close_moves_map=False leaves the map where it was).  The model's `loop_closure` attribute then holds the
+    losses of iteration N and N + 1 (before, after) and the step's counts."""
     from dgr_amd import light, slam
-    from dgr_amd.optim import (SparseAdam, add_densification_stats, densify_and_prune, inject_position_noise, relocate_dead,
-                               seed_from_frame)
+    from dgr_amd.optim import (SparseAdam, add_densification_stats, densify_and_prune, inject_position_noise, pose_corrections,
+                               relocate_dead, seed_from_frame, transform_map)
     from dgr_amd.synth import make_scene
 
     scenes = [make_scene(P, W, H, 3, view_index=k) for k in range(keyframes)]
@@ -194,7 +212,9 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     if graph:
         views_in_flight = 1  # (branches of one graph do not overlap on this ROCm, and the leaves' gradient accumulation
                              #  belongs to the stream they were created on: keep the recorded iteration on one stream)
-    pc = SeededMapModel(dev) if seed else MapModel(s, dev, degrade=7)
+    if loop_close_at and not (seed and 3 <= loop_close_at < iters - 1):
+        raise ValueError("loop_close_at=N needs seed=True and 3 <= N < iters - 1")
+    pc = SeededMapModel(dev, anchored=bool(loop_close_at)) if seed else MapModel(s, dev, degrade=7)
     opt = SparseAdam(pc.groups(), eps=1e-15, capturable=graph)
     seen = torch.zeros(pc.get_xyz.shape[0], dtype=torch.int32, device=dev)
     outs = [None] * keyframes
@@ -289,6 +309,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         leaves, accum, denom, max_radii2D, counts = seed_from_frame(
             pc.leaves(), opt, obs[k][0], sensor_depth[k], c["viewmatrix"], W / (2.0 * s.tanfovx), H / (2.0 * s.tanfovy),
             (W - 1) / 2.0, (H - 1) / 2.0, opacity_map=silhouette, silhouette_threshold=0.5, init_opacity=0.5, **behind,
+            **(dict(fill={"anchor": float(k)}) if loop_close_at else {}),
             xyz_gradient_accum=pc.xyz_gradient_accum, denom=pc.denom, max_radii2D=pc.max_radii2D)
         pc.replace(leaves, accum, denom, max_radii2D)
         seen = torch.zeros(counts.rows, dtype=torch.int32, device=dev)
@@ -310,9 +331,34 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             dead, live, moved, sources, most = result.counts.tolist()[:5]  # (the step's one host read)
             log(f"relocate: {dead} dead of {dead + live}, {moved} moved onto {sources} live Gaussians (at most {most} onto one)")
 
+    def rigid(rng, size):  # a rigid motion of about `size`: a rotation by that angle about a random axis, a translation of that length
+        axis, shift = rng.standard_normal(3), rng.standard_normal(3)
+        x, y, z = axis / np.linalg.norm(axis)
+        K = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+        D = np.eye(4)
+        D[:3, :3], D[:3, 3] = np.eye(3) + np.sin(size) * K + (1.0 - np.cos(size)) * K @ K, size * shift / np.linalg.norm(shift)
+        return D
+
+    def close_loop():
+        # C2W_new = D_k C2W_old: the viewmatrix W2C^T becomes (D_k^-1)^T W2C^T.  The poses are rewritten in place (the recorded
+        # iteration derives its cameras from these tensors on every replay), and the map follows them, in place as well
+        rng = np.random.RandomState(loop_close_seed)
+        shared = rigid(rng, loop_close_scale)
+        deltas = np.stack([rigid(rng, loop_close_scale / 100.0) @ shared for _ in cams])
+        old = torch.stack([c["viewmatrix"] for c in cams])
+        new = (torch.from_numpy(np.linalg.inv(deltas).transpose(0, 2, 1)).to(dev) @ old.double()).float()
+        corrections = pose_corrections(old, new)
+        for c, v in zip(cams, new):
+            c["viewmatrix"].copy_(v)
+        return transform_map(pc.leaves(), opt, corrections) if loop_close_moves_map else None
+
     if seed:
         seed_keyframe(0)
+    if loop_close_at:  # the whole window before the first iteration
+        while n_live < keyframes:
+            seed_keyframe(n_live)
     join_every = max(iters // keyframes, 1)
+    closure = {}
 
     run = iteration
     if graph:  # (the three eager iterations run inside CapturedStep, on the stream the graph is recorded on)
@@ -337,6 +383,10 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             densify()
         if relocate_every and (i + 4) % relocate_every == 0 and i + 3 >= relocate_start:
             relocate(i + 3)
+        if loop_close_at and i + 3 == loop_close_at:
+            closure["before"], closure["counts"] = loss.detach().clone(), close_loop()
+        elif loop_close_at and i + 3 == loop_close_at + 1:
+            closure["after"] = loss.detach().clone()
         if log and (i + 3) % 20 == 0:
             log(f"iteration {i + 3:4d}: loss {float(loss):.4e}")
     torch.cuda.synchronize()
@@ -345,6 +395,12 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         step.check()
     pc.window = window
     pc.relocations = [c.tolist()[:5] for c in relocations]
+    if loop_close_at:
+        pc.loop_closure = dict(before=float(closure["before"]), after=float(closure["after"]),
+                               counts=None if closure["counts"] is None else closure["counts"].tolist())
+        if log:
+            log(f"loop closure after iteration {loop_close_at}: loss {pc.loop_closure['before']:.4e} before, "
+                f"{pc.loop_closure['after']:.4e} after; counts {pc.loop_closure['counts']}")
     return (first, float(loss)), pc, dt
 
 
@@ -386,6 +442,11 @@ def main():
                     help="with --relocate-every: add the gated SGLD position noise after each relocation (inject_position_noise)")
     ap.add_argument("--relocate-min-opacity", type=float, default=0.005, metavar="O",
                     help="a Gaussian whose opacity lies below O is dead (default 0.005)")
+    ap.add_argument("--loop-close-at", type=int, default=0, metavar="N",
+                    help="with --seed: after iteration N the keyframes' poses get seeded rigid corrections, as after a loop closure, and "
+                         "every Gaussian follows the keyframe it was seeded from (pose_corrections + transform_map); all keyframes are "
+                         "then seeded before the first iteration, so --graph and --fused are allowed")
+    ap.add_argument("--loop-close-seed", type=int, default=0, help="the seed of --loop-close-at's corrections")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -396,7 +457,9 @@ def main():
         ap.error("--masked replaces the photometric loss: drop --ssim")
     if args.densify_every < 0 or (args.densify_every and args.graph):
         ap.error("--densify-every changes the number of Gaussians: it cannot run inside a recorded hipGraph (drop --graph)")
-    if args.seed and (args.graph or args.fused or args.variant != "light"):
+    if args.loop_close_at and not args.seed:
+        ap.error("--loop-close-at moves every Gaussian with the keyframe it was seeded from: it needs --seed")
+    if args.seed and (((args.graph or args.fused) and not args.loop_close_at) or args.variant != "light"):
         ap.error("--seed changes the number of Gaussians and grows the window: it cannot run inside a recorded hipGraph (drop "
                  "--graph), and it maps through the per-keyframe light path (drop --fused / --variant full)")
     if args.select < 0 or args.select > args.keyframes or (args.select and args.seed):
@@ -417,7 +480,11 @@ def main():
                                     variant=args.variant, absgrad=args.absgrad, densify_every=args.densify_every, ssim_lambda=args.ssim,
                                     seed=args.seed, masked=args.masked, select=args.select, relocate_every=args.relocate_every,
                                     position_noise=args.position_noise, relocate_min_opacity=args.relocate_min_opacity,
-                                    relocate_start=args.relocate_start)
+                                    relocate_start=args.relocate_start, loop_close_at=args.loop_close_at,
+                                    loop_close_seed=args.loop_close_seed)
+    if args.loop_close_at and args.graph:
+        print(f"loop closure after iteration {args.loop_close_at}: loss {pc.loop_closure['before']:.4e} before, "
+              f"{pc.loop_closure['after']:.4e} after; counts {pc.loop_closure['counts']}")
     for step, (dead, live, moved, sources, most) in enumerate(pc.relocations if args.graph else ()):
         print(f"relocation {step}: {dead} dead of {dead + live}, {moved} moved onto {sources} live Gaussians (at most {most} onto one)")
     if args.select:

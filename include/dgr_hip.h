@@ -357,6 +357,61 @@ int dgr_position_noise(void* stream, long P, float* xyz, const float* scaling_ra
                        const float* noise /* or NULL */, unsigned long long seed, int step, const int* step_device /* or NULL */,
                        float lr, const float* lr_device /* or NULL */, float scale, float k, float x0);
 
+/* Map correction after a pose-graph update (loop closure, global bundle adjustment): every Gaussian moves with the keyframe it was
+ * created from, by that keyframe's Sim(3) transform (csrc/transform.hip).  In place on P rows, no host read and no allocation: the
+ * step can be recorded into a hipGraph, and `transforms` is read when the graph is replayed.
+ * transforms [K, 4, 4]: float32 on the device, row-major, old world coordinates -> new ones; of transform k, A is the upper-left
+ * 3 x 3 block and t the translation column (the bottom row is only tested for being finite).  anchor [P]: float32 on the device,
+ * the transform of each row (what seed_from_frame's `fill` wrote and the other steps copied), or NULL: every row takes transform 0.
+ *
+ * Plan, per transform, in float64, each result rounded once to fp32: s = cbrt(det A); q_R = (r, x, y, z), the unit quaternion of
+ * A / s (Shepperd: the largest of the trace and the diagonal entries picks the branch; then normalised; the sign is the branch's);
+ * R, the rotation matrix of q_R; 1 / s, 1 / s^2, log s; and M_1 (3 x 3), M_2 (5 x 5), M_3 (7 x 7) with B_l(R d) = M_l B_l(d) for
+ * every unit d, B_l being the band-l spherical-harmonic basis as csrc/gaussian_math.h evaluates it (SH_C1, SH_C2[], SH_C3[] as
+ * fp32 constants, its signs, its order): coefficients rotate as c'_l = M_l c_l per colour channel.  M_l is formed as
+ * Y_l(R d) Y_l^-1 over 2 l + 1 fixed directions (csrc/sh_rotation_table.h).  A transform is INVALID, and its rows are left
+ * untouched, when one of its 16 values is not finite, det A <= 0, or max |A^T A / s^2 - I| > 1e-3.
+ *
+ * Apply.  Row i is transformed when its anchor a is an integer value with 0 <= a < K and transform a is valid; every other row (a
+ * NaN, negative, fractional or too large anchor, an invalid transform) keeps its bits in every tensor, and nothing is read out of
+ * range.  Each tensor {data [P, k], mode, skip} has mode = kind + order, fp32 arithmetic on the records:
+ *   XYZ (k = 3)        VALUE x' = A x + t;  MOMENT1 m' = (R m) / s (a gradient is a covector: the inverse transpose of the value's
+ *                      linear part);  MOMENT2 v'_i = (sum_j R_ij^2 v_j) / s^2 (the diagonal of the rotated second moment without
+ *                      the cross terms Adam never tracked; it stays >= 0)
+ *   QUAT (k = 4)       VALUE q' = q_R (x) q (Hamilton product; the row's norm is kept, its sign not canonicalised);  MOMENT1 L(q_R) m
+ *                      with L the (orthogonal) 4 x 4 matrix of the left multiplication;  MOMENT2 (L o L) v, o the element-wise product
+ *   LOG_SCALE (k = 3)  VALUE only: + log s per component (a shift leaves the gradients alone: the moments are not in the table)
+ *   SH                 skip = 0: an f_rest leaf [P, M, 3] (k = 3 M), skip = 3: a combined shs leaf [P, M + 1, 3] (k = 3 M + 3) whose
+ *                      DC row is left alone; M = 3, 8 or 15, coefficient-major, channel-minor.  VALUE and MOMENT1: c'_l = M_l c_l per
+ *                      complete band and channel;  MOMENT2: (M_l o M_l)
+ * Opacity, the DC colour, leaves without a role and the densification accumulators are invariant: they are not in the table.
+ * counts4_device [4] int32 = {rows transformed, rows whose anchor names no transform, invalid transforms, rows anchored to an
+ * invalid transform}: dgr_transform_plan writes {0, 0, invalid, 0}; every dgr_transform_apply rewrites all four (so a second apply
+ * call with the same scratch for more tensors leaves the same counts).
+ *
+ * dgr_transform_plan (the transforms' launch and a one-workgroup count) fills `scratch`, an opaque 16-byte aligned device buffer of
+ * dgr_transform_scratch_bytes(K) bytes (0 for a refused K: K must be 1 .. 2^20).  dgr_transform_apply: the count's reset and one
+ * launch over 1 .. DGR_TRANSFORM_MAX_TENSORS tensors.  At most one XYZ, one QUAT and one LOG_SCALE VALUE tensor per call.  Argument
+ * errors are reported before any HIP call. */
+#define DGR_TRANSFORM_MAX_TENSORS 24
+#define DGR_TRANSFORM_VALUE 0
+#define DGR_TRANSFORM_MOMENT1 1
+#define DGR_TRANSFORM_MOMENT2 2
+#define DGR_TRANSFORM_XYZ 0
+#define DGR_TRANSFORM_QUAT 4
+#define DGR_TRANSFORM_LOG_SCALE 8
+#define DGR_TRANSFORM_SH 12
+typedef struct {
+    float* data;
+    int k;
+    int mode; /* DGR_TRANSFORM_<kind> + DGR_TRANSFORM_<order> */
+    int skip; /* SH: 0 or 3 leading values of each row that stay; 0 for the other kinds */
+} dgr_transform_tensor;
+size_t dgr_transform_scratch_bytes(long K);
+int dgr_transform_plan(void* stream, long K, const float* transforms, void* scratch, int* counts4_device);
+int dgr_transform_apply(void* stream, long P, long K, const void* scratch, const float* anchor /* or NULL */, int n,
+                        const dgr_transform_tensor* tensors, int* counts4_device);
+
 /* Fused map expansion: new Gaussians from an RGB-D keyframe, appended to every per-Gaussian tensor of the model in three
  * launches (csrc/seed.hip) -- what an RGB-D SLAM system (CG-SLAM, SplaTAM, MonoGS) does when a keyframe arrives: unproject the
  * pixels the current map does not explain.  The sibling of densify-and-prune above: decide, scan, one host read, one apply.
