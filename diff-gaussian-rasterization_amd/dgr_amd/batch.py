@@ -11,7 +11,7 @@ the C ABI's batched entry points (include/dgr_hip.h: dgr_light_forward_batch / d
     passes yields (same operations in the same order in the per-Gaussian stage; two runs differ only by the order of the
     blend backward's float atomics, as two one-view runs do) -- formed in registers and written once; `means2D` (the
     screen-space points 3DGS reads its densification statistics from) and `viewmatrices` keep their per-view gradients;
-  * they are views of one flat arena (`dgr_amd.light._grad_arena`), so `dgr_amd.multiview.GradientArena` finds the fused
+  * they are views of one flat arena (`dgr_amd._frontend._grad_arena`), so `dgr_amd.multiview.GradientArena` finds the fused
     all-reduce span of a multi-GPU mapping step in them as it does for a one-view backward.
 
 torch supplies device memory and the current stream; every compute call goes through the C ABI.  There is no CPU fallback.
@@ -20,12 +20,8 @@ from typing import NamedTuple
 
 import torch
 
-from . import _binning, _capi
-from . import light as _light
-
-MAX_VIEWS = _capi.MAX_BATCH_VIEWS
-_View, _ViewGrad = _capi.LightView, _capi.LightViewGrad
-_lib = _capi.load
+from . import _capi, _frontend
+from ._frontend import LIGHT, MAX_VIEWS, _EMPTY, _backward_views, _ext, _forward_views, _row  # noqa: F401  (read from here too)
 
 
 class BatchRasterizationSettings(NamedTuple):
@@ -48,92 +44,12 @@ class BatchRasterizationSettings(NamedTuple):
     map_off: bool
 
 
-_row = _capi.row_ptr
-
-
-def _ext():
-    """the compiled torch extension (csrc/torch_ext.cpp: forward_batch<V> / backward_batch<V> -- allocation and
-    marshalling in C++) when dgr_amd.light selected it, else None: the ctypes code below binds the same C ABI"""
-    return _light._CompiledC.ext if _light._C is _light._CompiledC else None
-
-
-def _forward_views(variant, View, outputs, V, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                   viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered):
-    """The batch forward of both variants: the extension's <variant>_forward_batch when dgr_amd.light selected it, else
-    dgr_<variant>_forward_batch through ctypes with `View` views; mode, capacity, retries and status words follow
-    dgr_amd._binning.run_batch.  `outputs(V, P, H, W, f32, i32)` -> the variant's output tensors by their `View` field name, in
-    the order of the extension's result, which carries the geometry, binning and image buffers after "radii".  Returns (per-view
-    R for the backward, that result: the [V,4] status words, the outputs and the buffers)."""
-    ext = _ext()
-    P = means3D.size(0)
-
-    def attempt(cap, lazy):
-        if ext is not None:
-            return getattr(ext, f"{variant}_forward_batch")(
-                bg, means3D, colors, opacity, scales, rotations, float(scale_modifier), cov3D_precomp, viewmatrices, gt_depths,
-                projmatrices, float(tanfovx), float(tanfovy), int(H), int(W), sh, int(degree), campos, bool(prefiltered), cap, lazy)
-        return _attempt_ctypes(variant, View, outputs, bg, means3D, colors, opacity, scales, rotations, scale_modifier,
-                               cov3D_precomp, viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos,
-                               prefiltered, cap, V), None
-    return _binning.run_batch((means3D.device.index, P, H, W), P, V, attempt)
-
-
-def _attempt_ctypes(variant, View, outputs, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp,
-                    viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered, cap, V):
-    """One ctypes attempt of _forward_views with binning capacity `cap` per view; returns what the extension returns."""
-    lib = _lib()
-    dev = means3D.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    u8 = dict(dtype=torch.uint8, device=dev)
-    c = _light._f32c
-    means3D, bg, colors, opacity = c(means3D, dev), c(bg, dev), c(colors, dev), c(opacity, dev)
-    scales, rotations, cov3D_precomp, sh = c(scales, dev), c(rotations, dev), c(cov3D_precomp, dev), c(sh, dev)
-    viewmatrices, projmatrices, campos, gt_depths = c(viewmatrices, dev), c(projmatrices, dev), c(campos, dev), c(gt_depths, dev)
-    P = means3D.size(0)
-    M = sh.size(1) if sh.numel() != 0 else 0
-    out = outputs(V, P, H, W, f32, i32)
-    geom = torch.empty((V, max(lib.dgr_geometry_bytes(P), 1)), **u8)
-    img = torch.empty((V, max(lib.dgr_image_bytes(W, H), 1)), **u8)
-    binning = torch.empty((V, max(lib.dgr_binning_bytes(cap, W, H), 1)), **u8)
-    status = torch.zeros((V, 4), **i32)
-    views = (View * V)()
-    for v in range(V):
-        w = views[v]
-        w.geometry_buffer, w.binning_buffer, w.binning_capacity, w.image_buffer = _row(geom, v), _row(binning, v), cap, _row(img, v)
-        w.status, w.viewmatrix, w.projmatrix, w.cam_pos = _row(status, v), _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v)
-        w.gt_depth = _row(gt_depths, v)
-        for k, t in out.items():
-            setattr(w, k, _row(t, v))
-    p = _capi.ptr
-    _light._check(getattr(lib, f"dgr_{variant}_forward_batch")(
-        _capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(opacity),
-        p(scales), float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), int(bool(prefiltered))))
-    i, o = list(out).index("radii") + 1, list(out.values())
-    return (status, *o[:i], geom, binning, img, *o[i:])
-
-
-def _outputs(V, P, H, W, f32, i32):
-    """The light batch's output tensors (_forward_views)."""
-    mk = torch.empty if P else torch.zeros
-    return {"out_color": torch.empty((V, 3, H, W), **f32), "out_depth": torch.empty((V, 1, H, W), **f32),
-            "out_median_depth": torch.empty((V, 1, H, W), **f32), "out_depth_var": torch.empty((V, 1, H, W), **f32),
-            "out_alpha": torch.empty((V, 1, H, W), **f32), "radii": mk((V, P), **i32), "gau_uncertainty": mk((V, P, 1), **f32),
-            "gau_related_pixels": mk((V, P, 1), **i32)}
-
-
 def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,
                    projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered):
     """Returns (per-view R for the backward, color, depth, median, var, alpha, radii, geom, binning, img, unc, px)."""
-    dev = means3D.device
-    if dev.type != "cuda":
-        raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
-    V = viewmatrices.size(0)
-    if not 1 <= V <= MAX_VIEWS:
-        raise RuntimeError(f"1 .. {MAX_VIEWS} views per batch")
-    R, out = _forward_views("light", _View, _outputs, V, bg, means3D, colors, opacity, scales, rotations, scale_modifier,
-                            cov3D_precomp, viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos,
-                            prefiltered)
+    V = _frontend._check_batch(means3D, viewmatrices)
+    R, out = _forward_views(LIGHT, V, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                            gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered)
     return (R,) + tuple(out[1:])
 
 
@@ -153,69 +69,14 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
                 viewmatrices, projmatrices, float(tanfovx), float(tanfovy), gC, gD, gM, gV, gt_depths, sh,
                 int(degree), campos, geom, binning, img, alphas, perspec_matrix, bool(track_off),
                 bool(map_off), bool(need_gaussian_grads), bool(need_means2D), num_rendered,
-                _light._EMPTY if silhouette is None else silhouette, bool(absgrad))
+                _EMPTY if silhouette is None else silhouette, bool(absgrad))
         return tuple(ext.light_backward_batch(*args))
-    if not need_gaussian_grads:
-        map_off = True  # nobody reads the per-Gaussian sums: the blend kernels form the three pose sums only
-    return _backward_views("light", _ViewGrad, {"alphas": alphas, "dL_dpix": gC, "dL_dpix_depth": gD, "dL_dpix_median_depth": gM,
-                                                 "dL_dpix_depth_var": gV},
-                           (int(bool(track_off)), int(bool(map_off))), bg, means3D, radii, colors, scales, rotations,
-                           scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh, degree,
-                           campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad,
-                           silhouette)
-
-
-def _backward_views(variant, ViewGrad, per_view, tail, bg, means3D, radii, colors, scales, rotations, scale_modifier,
-                    cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh, degree, campos, geom, binning,
-                    img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered, absgrad, silhouette=None):
-    """The ctypes batch backward of both variants: dgr_<variant>_backward_batch[_absgrad|_silhouette] with `ViewGrad` views
-    (`silhouette`: every view's silhouette gradient image [V,1,H,W], or None).  `per_view`:
-    the variant's own [V, ...] inputs by the view struct's field name (None: NULL; "dL_dpix" is the colour gradient [V,3,H,W]);
-    `tail`: the entry point's arguments after the common ones.  Returns (dL_dmeans2D [V,P,3] or None, dL_dcolors, dL_dopacity,
-    dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations, dL_dview [V,4,4]) and, with absgrad, every view's absolute
-    screen-space gradient [V,P,3]."""
-    lib = _lib()
-    dev = means3D.device
-    V, P = viewmatrices.size(0), means3D.size(0)
-    H, W = per_view["dL_dpix"].size(2), per_view["dL_dpix"].size(3)
-    f32 = dict(dtype=torch.float32, device=dev)
-    c = _light._f32c
-    means3D, bg, colors = c(means3D, dev), c(bg, dev), c(colors, dev)
-    scales, rotations, cov3D_precomp, sh = c(scales, dev), c(rotations, dev), c(cov3D_precomp, dev), c(sh, dev)
-    viewmatrices, projmatrices, campos = c(viewmatrices, dev), c(projmatrices, dev), c(campos, dev)
-    gt_depths, perspec_matrix = c(gt_depths, dev), c(perspec_matrix, dev)
-    per_view = {k: None if t is None else c(t, dev) for k, t in per_view.items()}
-    M = sh.size(1) if sh.numel() != 0 else 0
-    if need_gaussian_grads:
-        seg = _light._grad_arena(P, M, f32)
-        seg["means2D"].zero_()  # the arena's one-view slot: the batch returns means2D gradients per view, beside the arena
-        d3, dsh, dop, dsc, drot, dcov, dcol = (seg[k] for k in ("means3D", "sh", "opacity", "scales", "rotations", "cov3D", "colors"))
-        d2 = torch.empty((V, P, 3), **f32) if need_means2D else None
-    else:
-        d3 = dsh = dop = dsc = drot = dcov = dcol = d2 = None
-    dview = torch.empty((V, 4, 4), **f32)
-    nscr = (max(lib.dgr_light_backward_scratch_bytes_r(P, W, H, max(num_rendered + [0])), 1) + 255) // 256 * 256
-    scratch = torch.empty((V, nscr), dtype=torch.uint8, device=dev)
-    views = (ViewGrad * V)()
-    pp = _capi.ptr(perspec_matrix)
-    for v in range(V):
-        w = views[v]
-        w.geometry_buffer, w.binning_buffer, w.image_buffer = _row(geom, v), _row(binning, v), _row(img, v)
-        w.viewmatrix, w.projmatrix, w.cam_pos = _row(viewmatrices, v), _row(projmatrices, v), _row(campos, v)
-        w.perspec_matrix = _row(perspec_matrix, v) if perspec_matrix.dim() == 3 else pp
-        w.gt_depth, w.radii = _row(gt_depths, v), _row(radii, v)
-        for k, t in per_view.items():
-            setattr(w, k, _row(t, v))
-        w.dL_dmean2D, w.dL_dview, w.scratch, w.scratch_bytes = _row(d2, v), _row(dview, v), _row(scratch, v), nscr
-        w.num_rendered = num_rendered[v]
-    p = _capi.ptr
-    args = (_capi.stream_handle(dev.index), V, views, P, int(degree), M, p(bg), W, H, p(means3D), p(sh), p(colors), p(scales),
-            float(scale_modifier), p(rotations), p(cov3D_precomp), float(tanfovx), float(tanfovy), p(dop), p(dcol), p(d3), p(dcov),
-            p(dsh), p(dsc), p(drot)) + tail
-    out = (d2, dcol, dop, d3, dcov, dsh, dsc, drot, dview)
-    dabs = torch.empty((V, P, 3), **f32) if absgrad else None
-    _light._check(_capi.call_backward(variant, V, args, dabs, None if silhouette is None else c(silhouette, dev)))
-    return out + (dabs,) if absgrad else out
+    return _backward_views(LIGHT, {"alphas": alphas, "dL_dpix": gC, "dL_dpix_depth": gD, "dL_dpix_median_depth": gM,
+                                   "dL_dpix_depth_var": gV},
+                           _frontend._tracking_tail(track_off, map_off, need_gaussian_grads), bg, means3D, radii, colors, scales,
+                           rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh,
+                           degree, campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered,
+                           absgrad, silhouette)
 
 
 class _RasterizeGaussiansBatch(torch.autograd.Function):
@@ -232,41 +93,24 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             out = _forward_batch(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                                  viewmatrices, gt_depths, rs.projmatrices, rs.tanfovx, rs.tanfovy, int(rs.image_height),
                                  int(rs.image_width), sh, rs.sh_degree, rs.campos, rs.prefiltered)
-        (num_rendered, color, depth, depth_median, depth_var, opacity_map, radii, geom, binning, img, unc, px) = out
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.absgrad = means2D_abs is not None
-        ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
-        ctx.silhouette = _capi.silhouette_on(ctx.dgr_options)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning,
-                              img, opacity_map, gt_depths)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(radii, px)
-        return color, radii, depth, depth_median, depth_var, opacity_map, unc, px
+        # (color, radii, depth, depth_median, depth_var, opacity_map, unc, px)
+        return _frontend._record_forward(ctx, LIGHT, rs, out[0], means2D_abs, colors_precomp, means3D, scales, rotations,
+                                         cov3Ds_precomp, viewmatrices, sh, gt_depths, out[1:])
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_depth_median, grad_depth_var, grad_alpha, grad_unc, grad_px):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning, img, opacity_map,
-         gt_depths) = ctx.saved_tensors
-        V, H, W = viewmatrices.size(0), int(rs.image_height), int(rs.image_width)
-        zeros = lambda ch: torch.zeros((V, ch, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
-        absgrad = ctx.absgrad
-        grad_color = zeros(3) if grad_color is None else grad_color
-        grad_depth = zeros(1) if grad_depth is None else grad_depth
-        grad_depth_median = zeros(1) if grad_depth_median is None else grad_depth_median
-        grad_depth_var = zeros(1) if grad_depth_var is None else grad_depth_var
-        need = ctx.needs_input_grad
-        with _capi.on_device(means3D.device), _capi.under_options(ctx.dgr_options):
-            g = _backward_batch(
-                rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
-                rs.projmatrices, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_depth_median, grad_depth_var, gt_depths, sh,
-                rs.sh_degree, rs.campos, geom, binning, img, opacity_map, rs.perspec_matrix, rs.track_off, rs.map_off,
-                need_gaussian_grads=any(need[:8]) or absgrad, need_means2D=bool(need[1]), num_rendered=ctx.num_rendered,
-                absgrad=absgrad, silhouette=grad_alpha if ctx.silhouette else None)
-        (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = g[:9]
-        _light._consume_post_backward_wait()
-        return g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None, g[9] if absgrad else None
+    def backward(ctx, *grad_outputs):
+        def call(saved, images, need_gaussian_grads, silhouette):
+            rs = ctx.raster_settings
+            (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning, img, opacity_map,
+             gt_depths) = saved
+            with _capi.on_device(means3D.device):
+                return _backward_batch(
+                    rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
+                    rs.projmatrices, rs.tanfovx, rs.tanfovy, *images, gt_depths, sh, rs.sh_degree, rs.campos, geom, binning, img,
+                    opacity_map, rs.perspec_matrix, rs.track_off, rs.map_off, need_gaussian_grads=need_gaussian_grads,
+                    need_means2D=bool(ctx.needs_input_grad[1]), num_rendered=ctx.num_rendered, absgrad=ctx.absgrad,
+                    silhouette=silhouette)
+        return _frontend._run_backward(ctx, LIGHT, True, grad_outputs, call)
 
 
 def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, viewmatrices,
@@ -287,16 +131,14 @@ class GaussianRasterizerBatch(torch.nn.Module):
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, viewmatrices=None, gt_depths=None, *, means2D_abs=None):
-        # means2D_abs (absgrad): a float32 [V,P,3] leaf whose .grad receives every view's absolute screen-space gradient
-        # (dgr_amd.light.GaussianRasterizer.forward)
-        shs, colors_precomp, scales, rotations, cov3D_precomp = _light._checked_inputs(shs, colors_precomp, scales, rotations,
-                                                                                       cov3D_precomp)
+        rs = self.raster_settings
         if viewmatrices is None:
-            viewmatrices = self.raster_settings.viewmatrices
+            viewmatrices = rs.viewmatrices
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _frontend._rasterizer_inputs(
+            means3D, means2D_abs, rs.map_off, shs, colors_precomp, scales, rotations, cov3D_precomp,
+            None if means2D_abs is None else (viewmatrices.size(0), means3D.size(0), 3))
         if means2D_abs is not None:
-            _light.check_means2D_abs(means2D_abs, means3D, self.raster_settings.map_off,
-                                     shape=(viewmatrices.size(0), means3D.size(0), 3))
             return _RasterizeGaussiansBatch.apply(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                                  cov3D_precomp, viewmatrices, gt_depths, self.raster_settings, means2D_abs)
+                                                  cov3D_precomp, viewmatrices, gt_depths, rs, means2D_abs)
         return rasterize_gaussians_batch(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,
-                                         viewmatrices, gt_depths, self.raster_settings)
+                                         viewmatrices, gt_depths, rs)

@@ -4,48 +4,30 @@ dgr_full_forward_batch / dgr_full_backward_batch (include/dgr_hip.h).
 The counterpart of `dgr_amd.batch` for the full variant's `_RasterizeGaussians` (F/diff_gaussian_rasterization/__init__.py):
 per view the outputs (colour, radii, depth, uncertainty) are bit-identical to the one-view surface (`dgr_amd.full`); the
 Gaussians' gradients come back SUMMED over the views, formed in registers by one per-Gaussian launch and written once, as views
-of one flat arena (`dgr_amd.light._grad_arena`, so `dgr_amd.multiview.GradientArena` finds the all-reduce span); `means2D`
+of one flat arena (`dgr_amd._frontend._grad_arena`, so `dgr_amd.multiview.GradientArena` finds the all-reduce span); `means2D`
 ([V,P,3]) and `viewmatrices` ([V,4,4]) keep their per-view gradients.  Settings are `dgr_amd.batch.BatchRasterizationSettings`;
 the full variant has no tracking / mapping switches, so `track_off` and `map_off` must be False.
 
-The forward and the ctypes backward are `dgr_amd.batch`'s (`_forward_views`, `_backward_views`), with the binning capacity and
+The forward and the ctypes backward are the light batch's too (`dgr_amd._frontend._forward_views`, `_backward_views`), with the binning capacity and
 status policy of `dgr_amd._binning` (`run_batch`: lazy mode follows the shape's growth guard and runs an unsettled shape strict;
 a batch of V views leaves V status words unread).  A lazy forward hands its backward the capacity its binning buffers were carved
 with as R (deterministic gradients size their row buffers by it), never the largest count seen.  There is no CPU fallback.
 """
 import torch
 
-from . import _capi
-from . import light as _light
-from .batch import MAX_VIEWS, BatchRasterizationSettings, _backward_views, _ext, _forward_views  # noqa: F401  (the settings are shared)
-
-_View, _ViewGrad = _capi.FullView, _capi.FullViewGrad
-
-
-def _check_inputs(means3D, viewmatrices):
-    V = viewmatrices.size(0) if viewmatrices.dim() == 3 else 0
-    if not 1 <= V <= MAX_VIEWS:
-        raise RuntimeError(f"1 .. {MAX_VIEWS} views per batch")
-    if means3D.device.type != "cuda":
-        raise RuntimeError("dgr_hip runs on the GPU only (no CPU path exists, as in the reference)")
-    return V
+from . import _capi, _frontend
+from ._frontend import FULL, MAX_VIEWS, _backward_views, _ext, _forward_views  # noqa: F401  (read from here too)
+from .batch import BatchRasterizationSettings  # noqa: F401  (the settings are shared)
 
 
 def _forward_batch(bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, gt_depths,
                    projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered):
     """Returns (per-view R for the backward, color, depth, uncertainty, radii, geom, binning, img, [V,4] device status words
     {num_rendered, overflow, prefiltered violation, num_related})."""
-    V = _check_inputs(means3D, viewmatrices)
-    R, out = _forward_views("full", _View, _outputs, V, bg, means3D, colors, opacity, scales, rotations, scale_modifier,
-                            cov3D_precomp, viewmatrices, gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos,
-                            prefiltered)
+    V = _frontend._check_batch(means3D, viewmatrices)
+    R, out = _forward_views(FULL, V, bg, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices,
+                            gt_depths, projmatrices, tanfovx, tanfovy, H, W, sh, degree, campos, prefiltered)
     return (R,) + tuple(out[1:]) + (out[0],)
-
-
-def _outputs(V, P, H, W, f32, i32):
-    """The full batch's output tensors (dgr_amd.batch._forward_views)."""
-    return {"out_color": torch.empty((V, 3, H, W), **f32), "out_depth": torch.empty((V, 1, H, W), **f32),
-            "out_uncertainty": torch.empty((V, 1, H, W), **f32), "radii": (torch.empty if P else torch.zeros)((V, P), **i32)}
 
 
 def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices,
@@ -67,10 +49,10 @@ def _backward_batch(bg, means3D, radii, colors, scales, rotations, scale_modifie
                 perspec_matrix, bool(need_gaussian_grads), bool(need_means2D), num_rendered,
                 e if silhouette is None else silhouette, bool(absgrad))
         return tuple(ext.full_backward_batch(*args))
-    return _backward_views("full", _ViewGrad, {"dL_dpix": gC, "dL_depths": gD, "dL_duncertainties": gU}, (), bg, means3D, radii,
-                           colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy,
-                           gt_depths, sh, degree, campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D,
-                           num_rendered, absgrad, silhouette)
+    return _backward_views(FULL, {"dL_dpix": gC, "dL_depths": gD, "dL_duncertainties": gU}, (), bg, means3D, radii, colors, scales,
+                           rotations, scale_modifier, cov3D_precomp, viewmatrices, projmatrices, tanfovx, tanfovy, gt_depths, sh,
+                           degree, campos, geom, binning, img, perspec_matrix, need_gaussian_grads, need_means2D, num_rendered,
+                           absgrad, silhouette)
 
 
 class _RasterizeGaussiansBatchFull(torch.autograd.Function):
@@ -83,42 +65,26 @@ class _RasterizeGaussiansBatchFull(torch.autograd.Function):
                 gt_depths, raster_settings, means2D_abs=None):
         rs = raster_settings
         with _capi.on_device(means3D.device):
-            (R, color, depth, unc, radii, geom, binning, img, _) = _forward_batch(
-                rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
-                gt_depths, rs.projmatrices, rs.tanfovx, rs.tanfovy, int(rs.image_height), int(rs.image_width), sh,
-                rs.sh_degree, rs.campos, rs.prefiltered)
-        ctx.raster_settings = rs
-        ctx.num_rendered = R
-        ctx.absgrad = means2D_abs is not None
-        ctx.dgr_options = _capi.load().dgr_thread_options_effective()  # the backward runs under the forward's options
-        ctx.silhouette = _capi.silhouette_on(ctx.dgr_options)
-        ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning,
-                              img, gt_depths)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, unc
+            out = _forward_batch(rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
+                                 viewmatrices, gt_depths, rs.projmatrices, rs.tanfovx, rs.tanfovy, int(rs.image_height),
+                                 int(rs.image_width), sh, rs.sh_degree, rs.campos, rs.prefiltered)
+        # (color, radii, depth, unc)
+        return _frontend._record_forward(ctx, FULL, rs, out[0], means2D_abs, colors_precomp, means3D, scales, rotations,
+                                         cov3Ds_precomp, viewmatrices, sh, gt_depths, out[1:-1])
 
     @staticmethod
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_unc):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning, img,
-         gt_depths) = ctx.saved_tensors
-        V, H, W = viewmatrices.size(0), int(rs.image_height), int(rs.image_width)
-        zeros = lambda ch: torch.zeros((V, ch, H, W), dtype=torch.float32, device=means3D.device)  # noqa: E731
-        grad_color = zeros(3) if grad_color is None else grad_color
-        grad_depth = zeros(1) if grad_depth is None else grad_depth
-        need, absgrad = ctx.needs_input_grad, ctx.absgrad
-        sil = grad_unc if ctx.silhouette else None
-        grad_unc = None if ctx.silhouette else grad_unc
-        with _capi.on_device(means3D.device), _capi.under_options(ctx.dgr_options):
-            g = _backward_batch(
-                rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
-                rs.projmatrices, rs.tanfovx, rs.tanfovy, grad_color, grad_depth, grad_unc, gt_depths, sh, rs.sh_degree,
-                rs.campos, geom, binning, img, rs.perspec_matrix, need_gaussian_grads=any(need[:8]) or absgrad,
-                need_means2D=bool(need[1]), num_rendered=ctx.num_rendered, absgrad=absgrad, silhouette=sil)
-        (g2, gcol, gop, g3, gcov, gsh, gsc, grot, gview) = g[:9]
-        _light._consume_post_backward_wait()
-        return g3, g2, gsh, gcol, gop, gsc, grot, gcov, gview, None, None, g[9] if absgrad else None
+    def backward(ctx, *grad_outputs):
+        def call(saved, images, need_gaussian_grads, silhouette):
+            rs = ctx.raster_settings
+            (colors_precomp, means3D, scales, rotations, cov3Ds_precomp, viewmatrices, radii, sh, geom, binning, img,
+             gt_depths) = saved
+            with _capi.on_device(means3D.device):
+                return _backward_batch(
+                    rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp, viewmatrices,
+                    rs.projmatrices, rs.tanfovx, rs.tanfovy, *images, gt_depths, sh, rs.sh_degree, rs.campos, geom, binning, img,
+                    rs.perspec_matrix, need_gaussian_grads=need_gaussian_grads, need_means2D=bool(ctx.needs_input_grad[1]),
+                    num_rendered=ctx.num_rendered, absgrad=ctx.absgrad, silhouette=silhouette)
+        return _frontend._run_backward(ctx, FULL, True, grad_outputs, call)
 
 
 def rasterize_gaussians_batch_full(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
@@ -130,9 +96,9 @@ def rasterize_gaussians_batch_full(means3D, means2D, sh, colors_precomp, opaciti
         raise ValueError("the full variant has no track_off / map_off")
     if gt_depths is None:
         raise ValueError("the full variant's batch needs gt_depths (its backward reads them)")
-    _check_inputs(means3D, viewmatrices)
+    _frontend._check_batch(means3D, viewmatrices)
     if means2D_abs is not None:  # (absgrad: GaussianRasterizerBatchFull.forward)
-        _light.check_means2D_abs(means2D_abs, means3D, False, shape=(viewmatrices.size(0), means3D.size(0), 3))
+        _frontend.check_means2D_abs(means2D_abs, means3D, False, shape=(viewmatrices.size(0), means3D.size(0), 3))
     return _RasterizeGaussiansBatchFull.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                                               viewmatrices, gt_depths, raster_settings, means2D_abs)
 
@@ -147,8 +113,8 @@ class GaussianRasterizerBatchFull(torch.nn.Module):
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                 cov3D_precomp=None, viewmatrices=None, gt_depths=None, *, means2D_abs=None):
         # means2D_abs (absgrad): a float32 [V,P,3] leaf whose .grad receives every view's absolute screen-space gradient
-        shs, colors_precomp, scales, rotations, cov3D_precomp = _light._checked_inputs(shs, colors_precomp, scales, rotations,
-                                                                                       cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = _frontend._checked_inputs(shs, colors_precomp, scales, rotations,
+                                                                                          cov3D_precomp)
         if viewmatrices is None:
             viewmatrices = self.raster_settings.viewmatrices
         return rasterize_gaussians_batch_full(means3D, means2D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp,

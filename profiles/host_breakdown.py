@@ -1,6 +1,7 @@
 """Pure host cost of the autograd surface: a tiny scene (GPU work negligible), wall-clock around forward and backward.
-Usage (GPU box): python profiles/host_breakdown.py [light|full]   (DGR_AUTOGRAD=python: the Python autograd.Function
-over the compiled `_C` instead of the compiled node; DGR_BINDING=ctypes: the ctypes binding)"""
+Usage (GPU box): python profiles/host_breakdown.py [light|full] [absgrad]   (DGR_AUTOGRAD=python: the Python autograd.Function
+over the compiled `_C` instead of the compiled node; DGR_BINDING=ctypes: the ctypes binding; absgrad: every step carries a
+`means2D_abs` leaf, which always goes through the Python Function, and only the two end-to-end figures are printed)"""
 import ctypes as C
 import os
 import sys
@@ -16,6 +17,7 @@ from dgr_amd.multiview import make_settings
 from dgr_amd.synth import make_scene
 
 variant = sys.argv[1] if len(sys.argv) > 1 else "light"
+absgrad = sys.argv[2:3] == ["absgrad"]
 P, W, H, deg = 2000, 64, 64, 3
 dev = torch.device("cuda:0")
 s = make_scene(P, W, H, seed=0)
@@ -34,11 +36,16 @@ if variant == "full":
 else:
     rast = light.GaussianRasterizer(make_settings(s, deg, dev))
 params = [means3D, means2D, shs, opac, scales, rots, view]
+extra = {}
+if absgrad:
+    extra["means2D_abs"] = torch.zeros((P, 3), device=dev, requires_grad=True)
+    params.append(extra["means2D_abs"])
 n = 1000
 
 
 def one():
-    outs = rast(means3D=means3D, means2D=means2D, opacities=opac, shs=shs, scales=scales, rotations=rots, viewmatrix=view, gt_depth=gt)
+    outs = rast(means3D=means3D, means2D=means2D, opacities=opac, shs=shs, scales=scales, rotations=rots, viewmatrix=view, gt_depth=gt,
+                **extra)
     return outs
 
 
@@ -64,6 +71,8 @@ def measure(label):
             tb += t2 - t1
         if i % 20 == 19:
             torch.cuda.synchronize()
+    if absgrad:
+        label += ", absgrad"
     print(f"[{label}] forward {1e6 * tf / n:6.1f} us  backward {1e6 * tb / n:6.1f} us  (host, per view; binding={light._C.__name__}, "
           f"autograd={'compiled node' if light._USE_NODE and light._C is light._CompiledC else 'python Function'})", flush=True)
 
@@ -76,6 +85,8 @@ measure(variant + ", autograd multithreading off")
 if light._C is light._CompiledC and os.environ.get("DGR_HOST_PROF") == "1":
     print(light._CompiledC.ext.host_prof_dump(True))
 torch.autograd.set_multithreading_enabled(True)
+if absgrad:
+    sys.exit(0)
 
 # ---- the pieces
 lib = _capi.load()

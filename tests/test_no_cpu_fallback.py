@@ -40,6 +40,18 @@ def test_batched_surface_refuses_cpu_tensors_and_bad_view_counts():
         B.GaussianRasterizerBatch(rs)(x["means3D"], None, x["opac"], shs=x["sh"], scales=x["scales"])
 
 
+def test_both_batches_refuse_views_that_are_not_v_by_4_by_4_before_the_device_check():
+    """A [4,4] `viewmatrices` is not four views: the ctypes binding would form row pointers four floats apart, past its end."""
+    from dgr_amd import batch_full as BF
+    x = _inputs()
+    rs = B.BatchRasterizationSettings(16, 16, 0.6, 0.6, x["bg"], 1.0, x["views"], x["projs"], 3, x["campos"], False, False,
+                                      x["persp"], False, False)
+    for rasterizer in (B.GaussianRasterizerBatch, BF.GaussianRasterizerBatchFull):
+        with pytest.raises(RuntimeError, match="views per batch"):
+            rasterizer(rs)(x["means3D"], torch.zeros(2, 8, 3), x["opac"], shs=x["sh"], scales=x["scales"], rotations=x["rots"],
+                           viewmatrices=x["views"][0], gt_depths=x["gts"])
+
+
 def test_the_product_modules_do_not_import_the_oracle():
     assert not any(m == "oracle" or m.startswith("oracle.") for m in sys.modules if "dgr_amd" in getattr(sys.modules[m], "__name__", "") )
     import dgr_amd.batch, dgr_amd.light, dgr_amd.full, dgr_amd.slam, dgr_amd.multiview, dgr_amd.optim  # noqa: E401,F401
