@@ -119,6 +119,7 @@ long dgr_state_export(void* stream, const char* name, int P, int width, int heig
     if (n == "sched_flag") return copy(img.cursor + 3, 4) ? -1 : 1L;  // 1: this frame's blend kernels walk tile_sched, 0: the static band map
     if (n == "n_contrib") return copy(img.n_contrib, 4 * N) ? -1 : (long)N;
     if (n == "n_valid") return copy(img.n_valid, 4 * N) ? -1 : (long)N;
+    if (n == "first_contrib") return copy(img.first_contrib, 4 * N) ? -1 : (long)N;  // (full variant: 1-based list position, 0 = none)
     if (n == "final_T") return copy(img.final_T, 4 * N) ? -1 : (long)N;
     dgr::set_last_error("unknown state array: " + n);
     return -1;

@@ -194,7 +194,8 @@ int dgr_full_backward(void* stream, int P, int D, int M, int R, const float* bac
  * light backward's gradients for that tile are wrong;
  * "ranges", "tile_sched", "sched_flag" (one word, the frame's blend flags: bit 0 = its blend kernels use the schedule, bit 1 = the
  * binning buffer overflowed, bit 2 = quadrant lane lists: option "lane_lists"), "n_contrib", "n_valid",
- * "final_T" (image; the last two: full variant).  Layout conversion to the reference's element types is done on the fly.
+ * "first_contrib" (uint32 per pixel: the 1-based list position of the pixel's front-most valid Gaussian, 0 = none),
+ * "final_T" (image; the last three: full variant).  Layout conversion to the reference's element types is done on the fly.
  * `num_rendered` instances are exported; `binning_capacity` is the capacity the binning buffer was carved with
  * (= num_rendered after dgr_*_forward, the caller's capacity after *_presized).  Returns the element count, or < 0. */
 long dgr_state_export(void* stream, const char* name, int P, int width, int height, int num_rendered,

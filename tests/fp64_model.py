@@ -311,11 +311,14 @@ def torch_full(s, deg, vis, point_list, ranges, n_contrib, grads, pairs=None):
 
     color = torch.zeros(3, H, W, dtype=torch.float64)
     depth, unc, var = (torch.zeros(H, W, dtype=torch.float64) for _ in range(3))
+    first_contrib, n_valid = (torch.zeros(H, W, dtype=torch.int64) for _ in range(2))
     for tl in tiles(s, vis, point_list, ranges, n_contrib):
         power, alpha = alpha_of(tl, tile_xy(pix, tl, pairs), con, opac)
         _, alpha_p = alpha_of(tl, tile_xy(pix_pose, tl), con_d, opac_d)
         valid = valid_pairs(tl, power, alpha)
         first = valid & (torch.cumsum(valid.long(), 0) == 1)   # the pixel's front-most valid Gaussian
+        put(first_contrib, tl, (first * (tl.pos + 1)).sum(0))   # (1-based list position, 0: no valid Gaussian)
+        put(n_valid, tl, valid.sum(0))
         zeros = torch.zeros_like(alpha)
         pose_term = alpha_p - alpha_p.detach()                  # value 0, gradient -> view (ndc path)
         w_col = blend_weights(torch.where(valid, alpha + pose_term, zeros))[0]
@@ -331,7 +334,7 @@ def torch_full(s, deg, vis, point_list, ranges, n_contrib, grads, pairs=None):
         put(var, tl, (w_unc * e * e).sum(0))
     loss = weighted(grads, (color, depth, var))
     return loss, leaves, dict(color=color.detach().numpy(), depth=depth.detach().numpy(), uncertainty=unc.detach().numpy(),
-                              _pix=pix, _idx=idx.numpy())
+                              first_contrib=first_contrib.numpy(), n_valid=n_valid.numpy(), _pix=pix, _idx=idx.numpy())
 
 
 def complete_forward(s, variant, deg, vis, point_list, ranges, n_contrib, grads, colors_precomp=None, cov3D_precomp=None,

@@ -62,7 +62,7 @@ _EXPORT = {  # name -> (numpy dtype, elements per unit, unit)
     "conic_opacity": (np.float32, "4P"), "rgb": (np.float32, "3P"), "clamped": (np.uint8, "3P"),
     "tiles_touched": (np.uint32, "P"), "point_list": (np.uint32, "R"), "keys": (np.uint64, "R"),
     "contribution_tags": (np.uint8, "R1"),
-    "ranges": (np.uint32, "2T"), "tile_sched": (np.uint32, "4T"), "sched_flag": (np.uint32, "1"), "n_contrib": (np.uint32, "N"), "n_valid": (np.uint32, "N"), "final_T": (np.float32, "N"),
+    "ranges": (np.uint32, "2T"), "tile_sched": (np.uint32, "4T"), "sched_flag": (np.uint32, "1"), "n_contrib": (np.uint32, "N"), "n_valid": (np.uint32, "N"), "first_contrib": (np.uint32, "N"), "final_T": (np.float32, "N"),
 }
 
 

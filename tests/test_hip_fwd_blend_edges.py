@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 
 from dgr_amd import _capi
-from util import make_scene
+from util import make_scene, one_tile_scene
 import hip_helpers as hh
 from test_hip_light_parity import assert_images_carry_the_references_bits, check_backward
 from test_hip_live_lists import assert_live_list_is_the_tagged_entries, opaque_scene
@@ -41,27 +41,6 @@ def lane_lists(request):
     _capi.set_option("lane_lists", request.param)
     yield request.param
     _capi.set_option("lane_lists", 2)
-
-
-def one_tile_scene(K, seed=5):
-    """K small Gaussians whose 3-sigma rectangles lie inside tile (0, 0) of a 32x32 frame: centres on pixels 5 .. 10 of either
-    axis, sigma 0.3 .. 0.6 px before the low-pass filter (radius 3 px at most), moderate opacities so that no pixel saturates
-    early and the tile's list is walked to its end."""
-    W = H = 32
-    s = make_scene(K, W, H, seed)
-    rng = np.random.default_rng(1000 + seed)
-    # (the inverse of make_scene's placement: camera-space point from pixel and depth, then to the world)
-    from dgr_amd.synth import camera
-    tanfovx, tanfovy, Rm, t, *_ = camera(W, H, 0.05)
-    z = rng.uniform(1.0, 6.0, K)
-    px, py = rng.uniform(5.0, 10.0, K), rng.uniform(5.0, 10.0, K)
-    xc = ((2 * px + 1) / W - 1) * tanfovx * z
-    yc = ((2 * py + 1) / H - 1) * tanfovy * z
-    means = ((np.stack([xc, yc, z], 1) - t) @ Rm).astype(np.float32)
-    sig_px = rng.uniform(0.3, 0.6, (K, 3))
-    scales = (sig_px * (2 * tanfovx / W) * z[:, None]).astype(np.float32)
-    opac = rng.uniform(0.1, 0.6, (K, 1)).astype(np.float32)
-    return s._replace(means=means, scales=scales, opac=opac)
 
 
 def fold8(t):

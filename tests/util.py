@@ -4,6 +4,38 @@ import numpy as np
 from dgr_amd.synth import make_scene  # noqa: F401
 
 
+def one_tile_scene(K, seed=5, groups=None):
+    """K small Gaussians whose 3-sigma rectangles lie inside tile (0, 0) of a 32x32 frame: centres on pixels 5 .. 10 of either
+    axis, sigma 0.3 .. 0.6 px before the low-pass filter (radius 3 px at most), moderate opacities so that no pixel saturates
+    early and the tile's list is walked to its end.
+    `groups`: [(count, x range, y range, depth range), ...] with counts that sum to K -- the pixel ranges of the centres and the
+    camera-space depth range of each group of consecutive Gaussians; a range of None is the default (5 .. 10 px, depth 1 .. 6).
+    The radius stays 3 px, so centres within [3, 13) keep a rectangle inside the tile."""
+    W = H = 32
+    s = make_scene(K, W, H, seed)
+    rng = np.random.default_rng(1000 + seed)
+    # (the inverse of make_scene's placement: camera-space point from pixel and depth, then to the world)
+    from dgr_amd.synth import camera
+    tanfovx, tanfovy, Rm, t, *_ = camera(W, H, 0.05)
+    zr, xr, yr = (1.0, 6.0), (5.0, 10.0), (5.0, 10.0)
+    if groups is not None:
+        assert sum(g[0] for g in groups) == K
+
+        def bounds(i, default):  # per-Gaussian (low, high) of the groups' i-th range
+            r = [default if g[i] is None else g[i] for g in groups]
+            return tuple(np.concatenate([np.full(g[0], float(b[e])) for g, b in zip(groups, r)]) for e in (0, 1))
+        xr, yr, zr = bounds(1, xr), bounds(2, yr), bounds(3, zr)
+    z = rng.uniform(zr[0], zr[1], K)
+    px, py = rng.uniform(xr[0], xr[1], K), rng.uniform(yr[0], yr[1], K)
+    xc = ((2 * px + 1) / W - 1) * tanfovx * z
+    yc = ((2 * py + 1) / H - 1) * tanfovy * z
+    means = ((np.stack([xc, yc, z], 1) - t) @ Rm).astype(np.float32)
+    sig_px = rng.uniform(0.3, 0.6, (K, 3))
+    scales = (sig_px * (2 * tanfovx / W) * z[:, None]).astype(np.float32)
+    opac = rng.uniform(0.1, 0.6, (K, 1)).astype(np.float32)
+    return s._replace(means=means, scales=scales, opac=opac)
+
+
 def frac_outside(a, ref, atol, rtol):
     """Fraction of elements with |a-ref| > atol*max(1,|ref|)... generalised: atol + rtol*|ref|."""
     a = np.asarray(a, np.float64)
