@@ -38,6 +38,40 @@ def binding(request, monkeypatch):
     return request.param
 
 
+@pytest.fixture
+def set_lane_lists():
+    """a setter of the "lane_lists" option; 2 (the frame decides) comes back after the test.  Imported `as lane_lists`."""
+    _capi.load()
+    yield lambda v: _capi.set_option("lane_lists", v)
+    _capi.set_option("lane_lists", 2)
+
+
+@pytest.fixture(params=[0, 1], ids=["half-wave lists", "quadrant lists"])
+def forced_lane_lists(request):
+    """the test once under each forced value of the "lane_lists" option (its value); 2 comes back.  Imported `as lane_lists`."""
+    _capi.load()
+    _capi.set_option("lane_lists", request.param)
+    yield request.param
+    _capi.set_option("lane_lists", 2)
+
+
+@pytest.fixture
+def deterministic():
+    _capi.load()
+    _capi.set_option("deterministic_grads", 1)
+    yield
+    _capi.set_option("deterministic_grads", 0)
+
+
+@pytest.fixture
+def lazy(monkeypatch):
+    """dgr_amd.light under DGR_SYNC_MODE=lazy; nothing of the test's stays pending"""
+    monkeypatch.setenv("DGR_SYNC_MODE", "lazy")
+    yield L
+    L._pending_status.clear()
+    L._unsettled.clear()
+
+
 def hip_forward(s, deg, colors_precomp=None, cov3D_precomp=None, prefiltered=False, debug=False, scale_modifier=1.0):
     """Calls the `_C.rasterize_gaussians` mirror; returns (torch outputs tuple, dict of numpy arrays)."""
     use_sh = colors_precomp is None

@@ -1,19 +1,12 @@
 """The C-ABI library loads (no GPU needed) and exports every symbol include/dgr_hip.h declares."""
 import ctypes
 import os
-import re
 
 import pytest
 
 from dgr_amd import _capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "dgr_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(dgr_[a-z0-9_]+)\s*\(", text)))
+from abi_checks import declared_symbols
 
 
 def test_library_exports_every_declared_symbol():

@@ -1,40 +1,27 @@
 """The densify-and-prune entry points (include/dgr_hip.h: dgr_densify_*) without a GPU: declared, exported and bound; the
 descriptor's layout; every argument error refused with a message before any device call."""
 import ctypes as C
-import inspect
 import math
-import os
 
 import pytest
 
 from dgr_amd import _capi
 
-from test_capi_symbols import declared_symbols
+from abi_checks import FAKE, assert_descriptor, assert_entry_points, keyword_only, refused
 
 NAMES = ("dgr_densify_plan_bytes", "dgr_densify_plan", "dgr_densify_apply")
-FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
 INF = float("inf")
 
 
 def test_symbols_are_declared_exported_and_bound():
-    lib = C.CDLL(_capi.LIB_PATH)
-    for name in NAMES:
-        assert name in declared_symbols(), name
-        assert name in _capi.exported_symbols(), name
-        assert hasattr(lib, name), name
-    assert len(_capi._SIGS["dgr_densify_plan"][1]) == 14 and len(_capi._SIGS["dgr_densify_apply"][1]) == 10
+    assert_entry_points(NAMES, {"dgr_densify_plan": 14, "dgr_densify_apply": 10})
 
 
 def test_descriptor_matches_the_c_layout():
     # typedef struct { const float* src; float* dst; int k; int mode; } dgr_densify_tensor;
-    T = _capi.DensifyTensor
-    assert C.sizeof(T) == 2 * C.sizeof(C.c_void_p) + 2 * C.sizeof(C.c_int) == 24
-    assert (T.src.offset, T.dst.offset, T.k.offset, T.mode.offset) == (0, 8, 16, 20)
-    assert _capi.DENSIFY_MAX_TENSORS == 24
-    assert (_capi.DENSIFY_COPY, _capi.DENSIFY_ZERO_NEW, _capi.DENSIFY_ZERO, _capi.DENSIFY_XYZ, _capi.DENSIFY_LOG_SCALE) == (0, 1, 2, 3, 4)
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dgr_hip.h")).read()
-    for name, value in (("MAX_TENSORS", 24), ("COPY", 0), ("ZERO_NEW", 1), ("ZERO", 2), ("XYZ", 3), ("LOG_SCALE", 4)):
-        assert f"#define DGR_DENSIFY_{name} {value}\n" in header, name
+    assert 2 * C.sizeof(C.c_void_p) + 2 * C.sizeof(C.c_int) == 24
+    assert_descriptor(_capi.DensifyTensor, 24, dict(src=0, dst=8, k=16, mode=20), "DENSIFY",
+                      dict(MAX_TENSORS=24, COPY=0, ZERO_NEW=1, ZERO=2, XYZ=3, LOG_SCALE=4))
 
 
 def test_plan_bytes_hold_a_byte_per_row_and_a_record_per_block():
@@ -44,11 +31,6 @@ def test_plan_bytes_hold_a_byte_per_row_and_a_record_per_block():
     assert sizes[0] > 0 and all(b > a for a, b in zip(sizes, sizes[1:]))
     assert all(s % 16 == 0 for s in sizes)
     assert 2_000_000 + 16 * 7813 <= sizes[-1] <= 2_000_000 + 16 * 7813 + 256
-
-
-def _refused(rc, text):
-    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in _capi.last_error(), (rc, _capi.last_error())
-    assert _capi.last_error().startswith("dgr_densify_")
 
 
 def _plan(rows=10, plan=FAKE, counts=FAKE, accum=FAKE):
@@ -63,12 +45,9 @@ def _apply(tensors, rows=10, rows_out=12, plan=FAKE, n=None):
 
 
 def test_plan_refuses_bad_arguments_before_touching_the_gpu():
-    _refused(_plan(rows=-1), "rows")
-    _refused(_plan(rows=1 << 30), "rows")
-    _refused(_plan(plan=None), "plan")
-    _refused(_plan(plan=FAKE + 4), "aligned")
-    _refused(_plan(counts=None), "counts")
-    _refused(_plan(accum=None), "NULL input")
+    for case, text in ((dict(rows=-1), "rows"), (dict(rows=1 << 30), "rows"), (dict(plan=None), "plan"), (dict(plan=FAKE + 4), "aligned"),
+                       (dict(counts=None), "counts"), (dict(accum=None), "NULL input")):
+        refused(_plan(**case), "dgr_densify_plan", text)
 
 
 COPY, ZERO_NEW, ZERO, XYZ, LOG_SCALE = range(5)
@@ -91,19 +70,19 @@ COPY, ZERO_NEW, ZERO, XYZ, LOG_SCALE = range(5)
 ], ids=["rows<0", "rows_out<0", "rows_out>2rows", "plan-null", "n=0", "n<0", "n=25", "k=0", "k<0", "mode=5", "mode<0", "two-xyz",
         "xyz-k4"])
 def test_apply_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_apply(**case), text)
+    refused(_apply(**case), "dgr_densify_apply", text)
 
 
 def test_apply_refuses_null_tensors_and_missing_xyz_inputs():
-    lib = _capi.load()
     descs = (_capi.DensifyTensor * 1)()
+    apply = lambda table, scaling: _capi.load().dgr_densify_apply(None, 10, 12, FAKE, 1, table, scaling, FAKE, None, 0)  # noqa: E731
     descs[0].src, descs[0].dst, descs[0].k, descs[0].mode = None, FAKE, 3, COPY
-    _refused(lib.dgr_densify_apply(None, 10, 12, FAKE, 1, descs, FAKE, FAKE, None, 0), "NULL src or dst")
+    refused(apply(descs, FAKE), "dgr_densify_apply", "NULL src or dst")
     descs[0].src, descs[0].dst, descs[0].mode = None, None, ZERO
-    _refused(lib.dgr_densify_apply(None, 10, 12, FAKE, 1, descs, FAKE, FAKE, None, 0), "NULL src or dst")
+    refused(apply(descs, FAKE), "dgr_densify_apply", "NULL src or dst")
     descs[0].src, descs[0].dst, descs[0].mode = FAKE, FAKE, XYZ
-    _refused(lib.dgr_densify_apply(None, 10, 12, FAKE, 1, descs, None, FAKE, None, 0), "scaling_raw")
-    _refused(lib.dgr_densify_apply(None, 10, 12, FAKE, 1, None, FAKE, FAKE, None, 0), "tensors is NULL")
+    refused(apply(descs, None), "dgr_densify_apply", "scaling_raw")
+    refused(apply(None, FAKE), "dgr_densify_apply", "tensors is NULL")
 
 
 def test_thresholds_are_formed_in_float64():
@@ -115,13 +94,9 @@ def test_thresholds_are_formed_in_float64():
 
 def test_python_surface():
     from dgr_amd import optim
-    p = inspect.signature(optim.densify_and_prune).parameters
-    assert list(p)[:5] == ["params", "optimizer", "xyz_gradient_accum", "denom", "max_radii2D"]
-    for name, default in (("percent_dense", 0.01), ("min_opacity", 0.005), ("max_screen_size", None), ("noise", None),
-                          ("seed", 0), ("roles", None)):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
-    for name in ("grad_threshold", "extent"):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default is inspect.Parameter.empty, name
+    keyword_only(optim.densify_and_prune, ["params", "optimizer", "xyz_gradient_accum", "denom", "max_radii2D"],
+                 dict(percent_dense=0.01, min_opacity=0.005, max_screen_size=None, noise=None, seed=0, roles=None),
+                 required=("grad_threshold", "extent"))
     assert optim.DensifyCounts._fields == ("rows", "survivors", "clones", "children", "split")
 
 

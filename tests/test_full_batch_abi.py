@@ -12,21 +12,17 @@ import torch
 
 from dgr_amd import _capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "dgr_hip.h")
+from abi_checks import HEADER, assert_entry_points, header_text, neutral_args
 
 
 def test_the_full_batch_entry_points_are_exported_and_bound():
-    lib = ctypes.CDLL(_capi.LIB_PATH)
-    for name in ("dgr_full_forward_batch", "dgr_full_backward_batch"):
-        assert hasattr(lib, name), name
-        assert name in _capi.exported_symbols(), name
+    assert_entry_points(("dgr_full_forward_batch", "dgr_full_backward_batch"))
     _capi.load()
 
 
 def header_fields(struct):
     """field names of `typedef struct <struct> { ... }` in declaration order"""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = re.sub(r"/\*.*?\*/", "", header_text(), flags=re.S)
     body = re.search(r"typedef struct %s \{(.*?)\}" % struct, text, flags=re.S).group(1)
     return [re.search(r"(\w+)\s*$", d.strip()).group(1) for d in body.split(";") if d.strip()]
 
@@ -78,8 +74,7 @@ def test_batch_backward_refuses_a_view_without_its_binning_buffer(variant, cls):
     for name, t in cls._fields_:
         setattr(grads[0], name, fake if t is ctypes.c_void_p else 1 << 40 if name == "scratch_bytes" else 100)
     grads[0].binning_buffer = None
-    sig = _capi._SIGS["dgr_%s_backward_batch" % variant][1]
-    args = [fake if t is ctypes.c_void_p else 1.0 if t is ctypes.c_float else 0 for t in sig]
+    args = neutral_args("dgr_%s_backward_batch" % variant, pointer=fake)
     args[:10] = [None, 1, grads, 10, 3, 16, fake, 64, 48, fake]  # stream, n_views, views, P, D, M, background, W, H, means3D
     assert getattr(lib, "dgr_%s_backward_batch" % variant)(*args) == _capi.DGR_ERR_BAD_ARGUMENT
     assert b"missing state buffer" in lib.dgr_last_error()

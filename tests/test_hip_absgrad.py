@@ -15,16 +15,10 @@ from dgr_amd import _capi
 from dgr_amd import full as F
 from dgr_amd import light as L
 from fp64_model import CASES, absgrad_of_pairs, torch_full, torch_light
-from hip_helpers import binding  # noqa: F401  (fixture)
+from hip_helpers import binding, set_lane_lists as lane_lists  # noqa: F401  (fixtures)
 from util import make_scene
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture
-def lane_lists():
-    yield lambda v: _capi.set_option("lane_lists", v)
-    _capi.set_option("lane_lists", 2)
 
 
 def _thread_option(name, value):

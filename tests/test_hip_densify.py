@@ -9,22 +9,12 @@ import torch
 
 from densify_model import densify_model
 from dgr_amd.optim import SparseAdam, densify_and_prune
+from hip_helpers import dev
+from map_step_cases import EXTRAS, assert_rebuilt, bits_equal, leaves_of, moments_of, on_device
 
 pytestmark = pytest.mark.gpu
 
 ROLES = ("xyz", "scaling", "rotation", "opacity")
-# further per-row tensors with k = 3, 45, 48, 1, 4 elements per row
-EXTRAS = {"f_dc": (1, 3), "f_rest": (15, 3), "sh48": (16, 3), "label": (), "aux4": (2, 2)}
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bits_equal(a, b):
-    """same shape and the same fp32 bits (NaNs and signed zeros included)"""
-    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
-    return a.shape == b.shape and a.dtype == b.dtype == torch.float32 and torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 def between(values, q):
@@ -36,19 +26,11 @@ def between(values, q):
     return float((v[i] + v[i + 1]) / 2)
 
 
-def leaves_of(P, g, extras=EXTRAS):
-    L = {"xyz": 3.0 * torch.randn((P, 3), generator=g), "scaling": 0.7 * torch.randn((P, 3), generator=g) - 2.0,
-         "rotation": torch.randn((P, 4), generator=g), "opacity": 2.0 * torch.randn((P, 1), generator=g)}
-    for name, shape in extras.items():
-        L[name] = torch.randn((P,) + shape, generator=g)
-    return L
-
-
 def mixed_case(P, seed):
     """inputs on the CPU + the public arguments, every threshold strictly between two data values"""
     g = torch.Generator(device="cpu").manual_seed(seed)
     L = leaves_of(P, g)
-    M = {name: (torch.randn(t.shape, generator=g), torch.rand(t.shape, generator=g)) for name, t in L.items()}
+    M = moments_of(L, g)
     denom = torch.randint(0, 5, (P, 1), generator=g).float()
     accum = torch.rand((P, 1), generator=g) * denom * 4e-4
     maxr = torch.floor(torch.rand(P, generator=g) * 60.0)
@@ -71,22 +53,12 @@ def mixed_case(P, seed):
 
 def run_hip(L, M, accum, denom, maxr, noise, kw, seed=0):
     """the HIP step on copies of the CPU inputs; returns (leaves, moments by name, accumulators, counts, optimiser)"""
-    d = dev()
-    params = {name: t.to(d).requires_grad_(name != "label") for name, t in L.items()}
-    opt = SparseAdam([{"params": [p], "lr": 1e-3} for p in params.values()])
-    for name, (m, v) in M.items():
-        opt.state[params[name]] = (m.to(d), v.to(d))
-    opt.steps = 3
-    up = lambda t: None if t is None else t.to(d)  # noqa: E731
+    params, opt, _, before = on_device(L, M)
+    up = lambda t: None if t is None else t.to(dev())  # noqa: E731
     out, a, dn, mr, counts = densify_and_prune(params, opt, up(accum), up(denom), up(maxr), noise=up(noise), seed=seed, **kw)
     torch.cuda.synchronize()
-    for name, p in out.items():
-        assert p.requires_grad == (name != "label") and p.is_leaf, name
-    assert opt.steps == 3
-    assert all(g["params"][0] is out[name] for g, name in zip(opt.param_groups, L))
-    moments = {name: opt.state[out[name]] for name in M}
-    assert len(opt.state) == len(M)
-    return out, moments, (a, dn, mr), counts, opt
+    assert_rebuilt(before, out, opt)
+    return out, {name: opt.state[out[name]] for name in M}, (a, dn, mr), counts, opt
 
 
 def check_against_model(L, M, accum, denom, maxr, noise, kw):
@@ -139,7 +111,7 @@ def test_mixed_case_matches_the_sequence(P):
 def quiet_case(P, seed, extras=None):
     g = torch.Generator(device="cpu").manual_seed(seed)
     L = leaves_of(P, g, EXTRAS if extras is None else extras)
-    M = {name: (torch.randn(t.shape, generator=g), torch.rand(t.shape, generator=g)) for name, t in L.items() if name in ROLES}
+    M = moments_of(L, g, ROLES)
     L["opacity"] = L["opacity"].clamp(-3.0, 3.0)
     L["scaling"] = L["scaling"].clamp(-4.0, -1.0)
     denom = torch.ones((P, 1))

@@ -13,22 +13,14 @@ import numpy as np
 import pytest
 import torch
 
-from dgr_amd import _capi
 from util import make_scene
 import hip_helpers as hh
+from hip_helpers import deterministic  # noqa: F401  (fixtures)
 from test_hip_light_parity import GRAD_NAMES, check_backward
 
 pytestmark = pytest.mark.gpu
 
 CONFIGS = [(10000, 256, 256, 0, 0), (100000, 640, 480, 3, 0), (500000, 1920, 1080, 3, 0)]  # BASELINE configs 1-3 (sizes)
-
-
-@pytest.fixture
-def deterministic():
-    _capi.load()
-    _capi.set_option("deterministic_grads", 1)
-    yield
-    _capi.set_option("deterministic_grads", 0)
 
 
 def backward_twice(s, deg, **kw):

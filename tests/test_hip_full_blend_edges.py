@@ -26,6 +26,7 @@ import torch
 import fp64_model as M
 import full_blend_scenes as S
 import hip_helpers as hh
+from hip_helpers import forced_lane_lists as lane_lists  # noqa: F401  (fixtures)
 from dgr_amd import _capi
 from full_blend_scenes import FWD_BATCH
 from ref_parity import BAR_GRAD, BAR_IMAGE, GRADS, SANITY, scale_distance
@@ -41,14 +42,6 @@ FRONT = ["exact129", "exact257", "shadowed", "shadowed272"]          # where the
 DETERMINISTIC = ["exact129", "exact257", "shadowed", "shadowed272", "opaque"]
 EXTRAS = ["exact257", "shadowed"]                                     # absgrad and silhouette
 LISTS = {0: " (h)", 1: " (q)"}                                        # the lane mapping in the printed table: half-wave / quadrant lists
-
-
-@pytest.fixture(params=[0, 1], ids=["half-wave lists", "quadrant lists"])
-def lane_lists(request):
-    _capi.load()
-    _capi.set_option("lane_lists", request.param)
-    yield request.param
-    _capi.set_option("lane_lists", 2)
 
 
 def bits(a):

@@ -24,23 +24,15 @@ K = 256 .. 512, 2616 of 8610 / 768 of 2870 on the ragged frame, 1596 of 6912 / 4
 import numpy as np
 import pytest
 
-from dgr_amd import _capi
 from util import make_scene, one_tile_scene
 import hip_helpers as hh
+from hip_helpers import forced_lane_lists as lane_lists  # noqa: F401  (fixtures)
 from test_hip_light_parity import assert_images_carry_the_references_bits, check_backward
 from test_hip_live_lists import assert_live_list_is_the_tagged_entries, opaque_scene
 
 pytestmark = pytest.mark.gpu
 
 BATCH = 256  # entries the forward stages at a time (DGR_TILE_PIX)
-
-
-@pytest.fixture(params=[0, 1], ids=["half-wave lists", "quadrant lists"])
-def lane_lists(request):
-    _capi.load()
-    _capi.set_option("lane_lists", request.param)
-    yield request.param
-    _capi.set_option("lane_lists", 2)
 
 
 def fold8(t):

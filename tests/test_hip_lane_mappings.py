@@ -18,6 +18,7 @@ import pytest
 
 from util import make_scene
 import hip_helpers as hh
+from hip_helpers import set_lane_lists as lane_lists  # noqa: F401  (fixtures)
 from test_hip_light_parity import assert_images_carry_the_references_bits, check_backward
 
 pytestmark = pytest.mark.gpu
@@ -51,14 +52,6 @@ def test_heavy_tailed_scene_in_every_backward_mode(oracle, mode):
     from dgr_amd.synth import heavy_tail_scene
     s = heavy_tail_scene(make_scene(30000, 640, 480, 4), frac=0.05, sigma_px=(10, 200), seed=9)
     check_backward(oracle, s, 2, what="heavy tail, lane mappings", **mode)
-
-
-@pytest.fixture
-def lane_lists():
-    from dgr_amd import _capi
-    _capi.load()
-    yield lambda v: _capi.set_option("lane_lists", v)
-    _capi.set_option("lane_lists", 2)
 
 
 def quadrant_flag(s, d):

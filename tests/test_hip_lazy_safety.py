@@ -18,6 +18,7 @@ import torch
 
 from util import make_scene
 import hip_helpers as hh
+from hip_helpers import lazy  # noqa: F401  (fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,15 +35,6 @@ def _step(rast, leaves, s, backward=True):
     if backward:
         torch.autograd.backward([o[0], o[2]], [hh.T(s.gC), hh.T(s.gD[None])])
     return o
-
-
-@pytest.fixture
-def lazy(monkeypatch):
-    from dgr_amd import light as L
-    monkeypatch.setenv("DGR_SYNC_MODE", "lazy")
-    yield L
-    L._pending_status.clear()
-    L._unsettled.clear()
 
 
 def test_an_overflowed_lazy_forward_is_nan_not_an_empty_frame_and_raises_before_the_step(lazy):

@@ -19,6 +19,7 @@ from dgr_amd import _capi
 from dgr_amd.synth import cluster_scene, heavy_tail_scene
 from util import assert_grad_close, make_scene, mask_flipped_pixels
 import hip_helpers as hh
+from hip_helpers import deterministic, lazy, set_lane_lists as lane_lists  # noqa: F401  (fixtures)
 from test_hip_light_parity import GRAD_NAMES, IMAGES, check_backward
 
 pytestmark = pytest.mark.gpu
@@ -110,13 +111,6 @@ def test_empty_tiles():
     assert empty.any() and not counts[empty].any()
     g = hh.hip_backward(s, 0, hh.hip_forward(s, 0)[0])  # (tiles without a live entry return at once)
     assert all(np.isfinite(v).all() for v in g.values())
-
-
-@pytest.fixture
-def lane_lists():
-    _capi.load()
-    yield lambda v: _capi.set_option("lane_lists", v)
-    _capi.set_option("lane_lists", 2)
 
 
 def test_both_lane_mappings_by_the_frame(lane_lists):
@@ -270,14 +264,6 @@ def test_batched_backward(oracle):
 
 
 # ------------------------------------------------------------------------------------------ determinism, lazy mode
-@pytest.fixture
-def deterministic():
-    _capi.load()
-    _capi.set_option("deterministic_grads", 1)
-    yield
-    _capi.set_option("deterministic_grads", 0)
-
-
 @pytest.mark.parametrize("case", [DENSE, USUAL])
 @pytest.mark.parametrize("mode", [dict(), dict(map_off=True), dict(track_off=True)], ids=["mapping+pose", "tracking", "mapping"])
 def test_deterministic_grads_two_runs_the_same_bits(deterministic, oracle, case, mode):
@@ -290,15 +276,6 @@ def test_deterministic_grads_two_runs_the_same_bits(deterministic, oracle, case,
         assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
     assert any(v.any() for v in a.values())
     check_backward(oracle, s, deg, what="live lists, deterministic", **mode)  # (the 64-entry batches of the deterministic kernel)
-
-
-@pytest.fixture
-def lazy(monkeypatch):
-    from dgr_amd import light as L
-    monkeypatch.setenv("DGR_SYNC_MODE", "lazy")
-    yield L
-    L._pending_status.clear()
-    L._unsettled.clear()
 
 
 def forget(L, key):

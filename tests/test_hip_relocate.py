@@ -9,27 +9,18 @@ import pytest
 import torch
 
 from dgr_amd.optim import SparseAdam, inject_position_noise, relocate_dead
+from hip_helpers import dev
+from map_step_cases import EXTRAS, assert_in_place, bits_equal, moments_of, on_device
 from relocate_model import position_noise_model, relocate_model, weight
 
 pytestmark = pytest.mark.gpu
 
-# further per-row tensors with k = 3, 45, 48, 1, 4 elements per row (the densify tests' extras); "label" does not require grad
-EXTRAS = {"f_dc": (1, 3), "f_rest": (15, 3), "sh48": (16, 3), "label": (), "aux4": (2, 2)}
 NAN, INF = float("nan"), float("inf")
 NOISE_BAR = 4 * 4.789e-6  # position noise against its float64 model: 4x the worst ratio measured (profiles/relocate/README.md)
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
 def bits(t):
     return t.detach().cpu().contiguous().numpy().view(np.int32)
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
 
 
 def make_case(P, seed, dead=0.1, extras=EXTRAS, opacity=None):
@@ -44,7 +35,7 @@ def make_case(P, seed, dead=0.1, extras=EXTRAS, opacity=None):
         L["opacity"] = torch.tensor(opacity, dtype=torch.float32).reshape(P, 1)
     for name, shape in extras.items():
         L[name] = torch.randn((P,) + shape, generator=g)
-    M = {name: (torch.randn(t.shape, generator=g), torch.rand(t.shape, generator=g) + 0.5) for name, t in L.items()}
+    M = moments_of(L, g, floor=0.5)
     A = {"xyz_gradient_accum": torch.rand((P, 1), generator=g) + 0.5, "denom": torch.rand((P, 1), generator=g) + 0.5,
          "max_radii2D": torch.rand(P, generator=g) + 0.5}
     draws = torch.randint(0, 2 ** 32, (P,), generator=g, dtype=torch.int64)
@@ -55,23 +46,11 @@ def run_hip(L, M, A, draws, optimizer=True, **kw):
     """the HIP step on copies of the CPU inputs; returns (leaves, moments by name, accumulators, result); checks that every tensor
     is still the object it was"""
     d = dev()
-    params = {name: t.to(d).requires_grad_(name != "label") for name, t in L.items()}
-    opt, moments = None, {}
-    if optimizer:
-        opt = SparseAdam([{"params": [p], "lr": 1e-3} for p in params.values()])
-        for name, (m, v) in M.items():
-            moments[name] = opt.state[params[name]] = (m.to(d), v.to(d))
-        opt.steps = 3
+    params, opt, moments, before = on_device(L, M, optimizer)
     acc = {name: None if t is None else t.to(d) for name, t in A.items()}
-    before = {name: (p, p.data_ptr()) for name, p in params.items()}
     res = relocate_dead(params, opt, draws=None if draws is None else draws.to(d), **acc, **kw)
     torch.cuda.synchronize()
-    for name, (p, address) in before.items():
-        assert params[name] is p and p.data_ptr() == address and p.is_leaf and p.requires_grad == (name != "label"), name
-    if optimizer:
-        assert opt.steps == 3 and len(opt.state) == len(M)
-        assert all(g["params"][0] is params[name] for g, name in zip(opt.param_groups, L))
-        assert all(opt.state[params[name]][i] is moments[name][i] for name in M for i in (0, 1))
+    assert_in_place(before, params, opt)
     return params, moments, acc, res
 
 
@@ -339,9 +318,9 @@ def test_recorded_into_a_graph_the_step_draws_fresh_numbers_on_every_replay():
         assert torch.equal(res.counts, eager.counts) and torch.equal(res.source, eager.source)
         relocated.append(int(res.counts[2]))
         for name in L:
-            assert np.array_equal(bits(pa[name]), bits(pb[name])), (value, name)
+            assert bits_equal(pa[name], pb[name]), (value, name)
             for ma, mb in zip(oa.state[pa[name]], ob.state[pb[name]]):
-                assert np.array_equal(bits(ma), bits(mb)), (value, name)
+                assert bits_equal(ma, mb), (value, name)
     assert relocated[0] > 50 and relocated[1] > 0, relocated
 
 

@@ -7,18 +7,15 @@ import torch
 
 import cameras
 from seed_model import seed_masks, seed_model
-from dgr_amd.optim import SparseAdam, densify_and_prune, seed_from_frame
-from test_hip_densify import EXTRAS, bits_equal, leaves_of
+from dgr_amd.optim import densify_and_prune, seed_from_frame
+from hip_helpers import dev
+from map_step_cases import assert_rebuilt, bits_equal, leaves_of, moments_of, on_device
 
 pytestmark = pytest.mark.gpu
 
 NAN, INF = float("nan"), float("inf")
 ACCS = ("xyz_gradient_accum", "denom", "max_radii2D")
 FILL = {"label": 7.0, "aux4": -0.25}  # (f_rest and sh48 take the default 0)
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 def camera(W, H, pose=0.3):
@@ -73,10 +70,10 @@ def assert_off_threshold(f, images, kw):
 
 
 def state_of(P, seed):
-    """leaves with the extra tensors of test_hip_densify.py (k = 1, 3, 4, 45, 48), moments for every leaf, the accumulators"""
+    """leaves with the extra tensors of map_step_cases.py (k = 1, 3, 4, 45, 48), moments for every leaf, the accumulators"""
     g = torch.Generator(device="cpu").manual_seed(seed)
     L = leaves_of(P, g)
-    M = {name: (torch.randn(t.shape, generator=g), torch.rand(t.shape, generator=g)) for name, t in L.items()}
+    M = moments_of(L, g)
     A = {"xyz_gradient_accum": torch.rand((P, 1), generator=g), "denom": torch.randint(0, 5, (P, 1), generator=g).float(),
          "max_radii2D": torch.floor(torch.rand(P, generator=g) * 60.0)}
     return L, M, A
@@ -85,11 +82,7 @@ def state_of(P, seed):
 def run_hip(f, L, M, A, images, kw, error_on_device=False):
     """the HIP step on copies of the CPU inputs; returns (leaves, moments by name, accumulators by name, counts, optimiser)"""
     d, cam = dev(), f["cam"]
-    params = {name: t.to(d).requires_grad_(name != "label") for name, t in L.items()}
-    opt = SparseAdam([{"params": [p], "lr": 1e-3} for p in params.values()])
-    for name, (m, v) in M.items():
-        opt.state[params[name]] = (m.to(d), v.to(d))
-    opt.steps = 3
+    params, opt, _, before = on_device(L, M)
     kw = dict(kw)
     if error_on_device:
         kw["depth_error_min"] = torch.tensor([kw["depth_error_min"]], dtype=torch.float64).float().to(d)
@@ -97,11 +90,7 @@ def run_hip(f, L, M, A, images, kw, error_on_device=False):
     out, a, dn, mr, counts = seed_from_frame(params, opt, f["color_obs"].to(d), f["depth_obs"].to(d), f["view"].to(d), cam.fx, cam.fy,
                                              cam.cx, cam.cy, fill=FILL, **{n: t.to(d) for n, t in images.items()}, **accs, **kw)
     torch.cuda.synchronize()
-    for name, p in out.items():
-        assert p.requires_grad == (name != "label") and p.is_leaf, name
-    assert opt.steps == 3
-    assert all(g["params"][0] is out[name] for g, name in zip(opt.param_groups, L))
-    assert len(opt.state) == len(M)
+    assert_rebuilt(before, out, opt)
     return out, {name: opt.state[out[name]] for name in M}, dict(zip(ACCS, (a, dn, mr))), counts, opt, params
 
 
@@ -258,11 +247,7 @@ def test_both_resize_steps_in_sequence_keep_the_optimizer_consistent():
     L, M, A = state_of(P, 8)
     f = frame(37, 23, 8)
     cam = f["cam"]
-    params = {name: t.to(d).requires_grad_(name != "label") for name, t in L.items()}
-    opt = SparseAdam([{"params": [p], "lr": 1e-3} for p in params.values()])
-    for name, (m, v) in M.items():
-        opt.state[params[name]] = (m.to(d), v.to(d))
-    opt.steps = 3
+    params, opt, _, _ = on_device(L, M)
     accs = [A[name].to(d) for name in ACCS]
 
     def seed(params, accs):

@@ -19,7 +19,7 @@ from dgr_amd import full as F
 from dgr_amd import light as L
 from fp64_model import C0, absgrad_of_pairs, complete_forward, oracle_run, torch_full, torch_light
 from hip_helpers import binding  # noqa: F401  (fixture)
-from util import make_scene
+from util import bits_equal, make_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -83,8 +83,7 @@ def close(a, b, what, tol=1e-6):
     assert np.abs(a - b).max() <= tol * scale, f"{what}: {np.abs(a - b).max() / scale:.2e} of scale"
 
 
-def bits_equal(a, b, what):
-    assert np.array_equal(np.asarray(a, np.float32).view(np.uint32), np.asarray(b, np.float32).view(np.uint32)), what
+f32 = np.float32  # (_host brings the gradients over as float64, each the exact image of an fp32 value: back to the computed bits)
 
 
 def model_leaves(pc):
@@ -166,7 +165,7 @@ def test_full_reference_pose_gradient_does_not_see_the_silhouette():
         out, _ = hh.hip_full_forward(s, 3)
         a = hip_full(s, 3, out, [s.gC, s.gD, None], gA)
         b = hip_full(s, 3, out, [s.gC, s.gD, None])
-    bits_equal(a[8], b[8], "dL_dview")
+    assert bits_equal(f32(a[8]), f32(b[8])), "dL_dview"
     assert np.abs(a[3] - b[3]).max() > 0  # (while the per-Gaussian gradients do change)
 
 
@@ -251,7 +250,7 @@ def test_deterministic_silhouette_repeats_bit_for_bit(variant):
                 a, b = (hip_full(s, 3, out, [s.gC, s.gD, None if lean else s.gV], gA) for _ in range(2))
             for i, (x, y) in enumerate(zip(a, b)):
                 if x is not None:
-                    bits_equal(x, y, f"{variant} lean={lean} {i}")
+                    assert bits_equal(f32(x), f32(y)), f"{variant} lean={lean} {i}"
             # ... and the identity holds there too
             if lean:
                 p, q = bg_identity(s, variant)
@@ -452,7 +451,7 @@ def test_default_off_is_bit_identical(variant):
         b = [g[3], g[5], g[2], g[6], g[7], view16(g[8]).reshape(4, 4), g[0]]
         a[5] = view16(a[5]).reshape(4, 4)
     for i, (x, y) in enumerate(zip(a, b)):
-        bits_equal(x, y, f"{variant} {i}")
+        assert bits_equal(f32(x), f32(y)), f"{variant} {i}"
     on = _node_grads(s, variant, ("color", "depth", "sil"), dict(det, silhouette_grad=1))
     assert np.abs(on[0] - a[0]).max() > 0  # (and the option does change them)
 
@@ -520,7 +519,7 @@ def test_null_image_is_bit_identical_to_the_namesakes(monkeypatch, entries):
             if b is None:
                 assert a is None, i
             else:
-                bits_equal(a, b, f"lean={lean} result {i}")
+                assert bits_equal(f32(a), f32(b)), f"lean={lean} result {i}"
 
 
 # ---- 6. SLAM surface ----------------------------------------------------------------------------------------------------------

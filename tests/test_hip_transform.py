@@ -10,20 +10,13 @@ import hip_helpers as hh
 import transform_model as tm
 from dgr_amd.optim import (SparseAdam, densify_and_prune, pose_corrections, relocate_dead, seed_from_frame, transform_map)
 from dgr_amd.synth import make_scene
+from hip_helpers import dev
+from map_step_cases import assert_in_place, bits_equal, on_device
 
 pytestmark = pytest.mark.gpu
 
 NAN = float("nan")
 KIND = {"xyz": "xyz", "rotation": "quat", "scaling": "log_scale", "f_rest": "sh", "shs": "sh"}
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def bits_equal(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
 
 
 def make_case(P, K, seed, sh="f_rest15", runs=True, weird=True, bad_transforms=True):
@@ -56,21 +49,10 @@ def make_case(P, K, seed, sh="f_rest15", runs=True, weird=True, bad_transforms=T
 
 
 def run_hip(L, M, transforms, optimizer=True, anchor="anchor", **kw):
-    d = dev()
-    params = {n: torch.from_numpy(t).to(d).requires_grad_(n not in ("label", "anchor")) for n, t in L.items()}
-    opt, moments = None, {}
-    if optimizer:
-        opt = SparseAdam([{"params": [p], "lr": 1e-3} for n, p in params.items() if n in M])
-        for n, (m, v) in M.items():
-            moments[n] = opt.state[params[n]] = (torch.from_numpy(m).to(d), torch.from_numpy(v).to(d))
-        opt.steps = 3
-    before = {n: (p, p.data_ptr()) for n, p in params.items()}
-    counts = transform_map(params, opt, torch.from_numpy(transforms).to(d), anchor=anchor, **kw)
+    params, opt, moments, before = on_device(L, M, optimizer, frozen=("label", "anchor"), grouped=M)
+    counts = transform_map(params, opt, torch.from_numpy(transforms).to(dev()), anchor=anchor, **kw)
     torch.cuda.synchronize()
-    for n, (p, address) in before.items():
-        assert params[n] is p and p.data_ptr() == address and p.is_leaf, n
-    if optimizer:
-        assert opt.steps == 3 and all(opt.state[params[n]][i] is moments[n][i] for n in M for i in (0, 1))
+    assert_in_place(before, params, opt)
     out = {n: p.detach().cpu().numpy() for n, p in params.items()}
     mom = {n: tuple(t.cpu().numpy() for t in pair) for n, pair in moments.items()}
     return out, mom, counts.cpu().numpy()

@@ -2,8 +2,6 @@
 exported and bound; the params struct's layout against the header text; the scratch size; every argument error refused with a
 message before any device call; select_keyframes and the float64 model (tests/overlap_model.py) on spot values."""
 import ctypes as C
-import inspect
-import os
 import re
 
 import numpy as np
@@ -13,27 +11,19 @@ import torch
 from dgr_amd import _capi, slam
 
 import overlap_model as M
-from test_capi_symbols import declared_symbols
+from abi_checks import FAKE, assert_entry_points, header_text, keyword_only, refused
 
 NAMES = ("dgr_keyframe_overlap_scratch_bytes", "dgr_keyframe_overlap")
-FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
 NAN, INF = float("nan"), float("inf")
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dgr_hip.h")
 
 
 def test_symbols_are_declared_exported_and_bound():
-    lib = C.CDLL(_capi.LIB_PATH)
-    for name in NAMES:
-        assert name in declared_symbols(), name
-        assert name in _capi.exported_symbols(), name
-        assert hasattr(lib, name), name
-    assert len(_capi._SIGS["dgr_keyframe_overlap"][1]) == 15 and len(_capi._SIGS["dgr_keyframe_overlap_scratch_bytes"][1]) == 4
+    assert_entry_points(NAMES, {"dgr_keyframe_overlap": 15, "dgr_keyframe_overlap_scratch_bytes": 4})
     assert _capi._SIGS["dgr_keyframe_overlap_scratch_bytes"][0] is C.c_size_t
 
 
 def test_params_struct_matches_the_header_text():
-    text = open(HEADER).read()
-    body = text.split("} dgr_keyframe_overlap_params;")[0].rsplit("typedef struct dgr_keyframe_overlap_params {", 1)[1]
+    body = header_text().split("} dgr_keyframe_overlap_params;")[0].rsplit("typedef struct dgr_keyframe_overlap_params {", 1)[1]
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     fields = []
     for decl in body.split(";"):
@@ -58,11 +48,6 @@ def test_scratch_size():
         W, H, s, K = shape
         S = -(-W // s) * -(-H // s)
         assert f(*shape) % 16 == 0 and 0 < f(*shape) <= 16 + 16 * K * (S // 1024 + 1), shape  # far less than a word per pair
-
-
-def _refused(rc, text):
-    err = _capi.last_error()
-    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in err and err.startswith("dgr_keyframe_overlap: "), (rc, err)
 
 
 def _call(width=64, height=48, depth_obs=FAKE, viewmatrix=FAKE, K=3, kf_views=FAKE, kf_depths=None, params=True, scratch=FAKE,
@@ -112,20 +97,15 @@ def _call(width=64, height=48, depth_obs=FAKE, viewmatrix=FAKE, K=3, kf_views=FA
         "score-null", "fx-nan", "fx=0", "fy<0", "fy-inf", "cx-nan", "cy-nan", "lo-nan", "hi-nan", "near-nan", "edge-nan", "edge<0",
         "tol-nan", "tol<0", "tol<0-with-depths"])
 def test_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_call(**case), text)
+    refused(_call(**case), "dgr_keyframe_overlap", text)
 
 
 def test_python_surface():
-    p = inspect.signature(slam.keyframe_overlap).parameters
-    assert list(p)[:7] == ["depth_obs", "viewmatrix", "keyframe_viewmatrices", "fx", "fy", "cx", "cy"]
-    for name, default in (("stride", 16), ("edge", 20.0), ("near", 0.0), ("depth_range", (0.0, INF)), ("keyframe_depths", None),
-                          ("depth_tolerance", 0.05), ("return_flags", False)):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
+    keyword_only(slam.keyframe_overlap, ["depth_obs", "viewmatrix", "keyframe_viewmatrices", "fx", "fy", "cx", "cy"],
+                 dict(stride=16, edge=20.0, near=0.0, depth_range=(0.0, INF), keyframe_depths=None, depth_tolerance=0.05,
+                      return_flags=False))
     assert slam.KeyframeOverlap._fields == ("score", "inside", "visible", "valid", "flags")
-    p = inspect.signature(slam.select_keyframes).parameters
-    assert list(p)[:2] == ["score", "k"]
-    for name, default in (("min_overlap", 0.0), ("mode", "top"), ("generator", None)):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
+    keyword_only(slam.select_keyframes, ["score", "k"], dict(min_overlap=0.0, mode="top", generator=None))
     assert "only host" in " ".join(slam.select_keyframes.__doc__.split())
 
 

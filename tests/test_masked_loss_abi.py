@@ -9,20 +9,14 @@ import torch
 from dgr_amd import _capi, slam
 
 import masked_loss_model as M
-from test_capi_symbols import declared_symbols
+from abi_checks import FAKE, assert_entry_points, refused
 
 NAMES = ("dgr_masked_loss_scratch_bytes", "dgr_masked_loss_forward", "dgr_masked_loss_backward")
-FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
 NAN, INF = float("nan"), float("inf")
 
 
 def test_symbols_are_declared_exported_and_bound():
-    lib = C.CDLL(_capi.LIB_PATH)
-    for name in NAMES:
-        assert name in declared_symbols(), name
-        assert name in _capi.exported_symbols(), name
-        assert hasattr(lib, name), name
-    assert len(_capi._SIGS["dgr_masked_loss_forward"][1]) == 14 and len(_capi._SIGS["dgr_masked_loss_backward"][1]) == 16
+    assert_entry_points(NAMES, {"dgr_masked_loss_forward": 14, "dgr_masked_loss_backward": 16})
     assert _capi._SIGS["dgr_masked_loss_scratch_bytes"][0] is C.c_size_t
     assert C.sizeof(_capi.MaskedLossParams) == 36
     assert hasattr(slam, "masked_l1_loss") and slam.MaskedLossStats._fields == ("mask", "median", "base", "kept")
@@ -47,11 +41,6 @@ def test_scratch_size():
             sizes.append(f(*shape))
         assert all(b > a for a, b in zip(sizes, sizes[1:])), (dim, sizes)
     assert f(1, 1, 1) <= f(1, 1, 2) <= f(1, 1, 17) and f(1, 1, 1) < f(1, 1, 17)
-
-
-def _refused(rc, name, text):
-    err = _capi.last_error()
-    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in err and err.startswith(name + ": "), (rc, err)
 
 
 def _params(lo=0.0, hi=INF, sil=0.99, factor=10.0, reject=1, mask_color=1, reduction=0, w_color=1.0, w_depth=0.5):
@@ -99,17 +88,17 @@ IDS = ["color-null", "color_obs-null", "depth-null", "depth_obs-null", "params-n
 
 @pytest.mark.parametrize("case, text", CASES, ids=IDS)
 def test_forward_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_forward(**case), "dgr_masked_loss_forward", text)
+    refused(_forward(**case), "dgr_masked_loss_forward", text)
 
 
 @pytest.mark.parametrize("case, text", CASES, ids=IDS)
 def test_backward_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_backward(**case), "dgr_masked_loss_backward", text)
+    refused(_backward(**case), "dgr_masked_loss_backward", text)
 
 
 def test_null_outputs_are_refused():
-    _refused(_forward(loss=None), "dgr_masked_loss_forward", "loss is NULL")
-    _refused(_backward(dcolor=None, ddepth=None), "dgr_masked_loss_backward", "both NULL")
+    refused(_forward(loss=None), "dgr_masked_loss_forward", "loss is NULL")
+    refused(_backward(dcolor=None, ddepth=None), "dgr_masked_loss_backward", "both NULL")
 
 
 def test_python_surface_refuses_what_it_cannot_read():

@@ -1,41 +1,26 @@
 """The fixed-size map upkeep entry points (include/dgr_hip.h: dgr_relocate_*, dgr_position_noise) without a GPU: declared, exported
 and bound; the descriptor's layout; every argument error refused with a message before any device call."""
 import ctypes as C
-import inspect
-import os
 
 import pytest
 
 from dgr_amd import _capi
 
-from test_capi_symbols import declared_symbols
+from abi_checks import FAKE, OTHER, assert_descriptor, assert_entry_points, keyword_only, refused
 
 NAMES = ("dgr_relocate_scratch_bytes", "dgr_relocate_plan", "dgr_relocate_apply", "dgr_position_noise")
-FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
-OTHER = 1 << 21
 COPY, OPACITY, LOG_SCALE, ZERO_TOUCHED, ZERO_RELOCATED = range(5)
 
 
 def test_symbols_are_declared_exported_and_bound():
-    lib = C.CDLL(_capi.LIB_PATH)
-    for name in NAMES:
-        assert name in declared_symbols(), name
-        assert name in _capi.exported_symbols(), name
-        assert hasattr(lib, name), name
-    assert [len(_capi._SIGS[name][1]) for name in NAMES] == [1, 11, 8, 15]
+    assert_entry_points(NAMES, dict(zip(NAMES, (1, 11, 8, 15))))
 
 
 def test_descriptor_matches_the_c_layout():
     # typedef struct { float* data; int k; int mode; } dgr_relocate_tensor;
-    T = _capi.RelocateTensor
-    assert C.sizeof(T) == C.sizeof(C.c_void_p) + 2 * C.sizeof(C.c_int) == 16
-    assert (T.data.offset, T.k.offset, T.mode.offset) == (0, 8, 12)
-    assert _capi.RELOCATE_MAX_TENSORS == 24
-    assert (_capi.RELOCATE_COPY, _capi.RELOCATE_OPACITY, _capi.RELOCATE_LOG_SCALE, _capi.RELOCATE_ZERO_TOUCHED,
-            _capi.RELOCATE_ZERO_RELOCATED) == (0, 1, 2, 3, 4)
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dgr_hip.h")).read()
-    for name, value in (("MAX_TENSORS", 24), ("COPY", 0), ("OPACITY", 1), ("LOG_SCALE", 2), ("ZERO_TOUCHED", 3), ("ZERO_RELOCATED", 4)):
-        assert f"#define DGR_RELOCATE_{name} {value}\n" in header, name
+    assert C.sizeof(C.c_void_p) + 2 * C.sizeof(C.c_int) == 16
+    assert_descriptor(_capi.RelocateTensor, 16, dict(data=0, k=8, mode=12), "RELOCATE",
+                      dict(MAX_TENSORS=24, COPY=0, OPACITY=1, LOG_SCALE=2, ZERO_TOUCHED=3, ZERO_RELOCATED=4))
 
 
 def test_scratch_bytes_grow_with_the_rows():
@@ -48,11 +33,6 @@ def test_scratch_bytes_grow_with_the_rows():
     assert 28 * 2_000_000 + 16 * 7813 <= sizes[-1] <= 28 * 2_000_000 + 16 * 7813 + 256
 
 
-def _refused(rc, who, text):
-    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in _capi.last_error(), (rc, _capi.last_error())
-    assert _capi.last_error().startswith(who + ": ")
-
-
 def _plan(P=10, opacity=FAKE, thr=-5.0, step=0, step_dev=None, scratch=FAKE, counts=FAKE, source=FAKE):
     return _capi.load().dgr_relocate_plan(None, P, opacity, thr, None, 0, step, step_dev, scratch, counts, source)
 
@@ -63,7 +43,7 @@ def _plan(P=10, opacity=FAKE, thr=-5.0, step=0, step_dev=None, scratch=FAKE, cou
     (dict(thr=float("nan")), "NaN"), (dict(step=-1), "step is negative"),
 ], ids=["P<0", "P=2^30", "scratch-null", "scratch-unaligned", "counts-null", "opacity-null", "source-null", "thr-nan", "step<0"])
 def test_plan_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_plan(**case), "dgr_relocate_plan", text)
+    refused(_plan(**case), "dgr_relocate_plan", text)
 
 
 def _apply(tensors, P=10, scratch=FAKE, n=None, min_opacity=0.005, data=FAKE, scaling=OTHER, opacity=FAKE, descs=True):
@@ -99,7 +79,7 @@ def _apply(tensors, P=10, scratch=FAKE, n=None, min_opacity=0.005, data=FAKE, sc
 ], ids=["P<0", "P=2^30", "scratch-null", "scratch-unaligned", "min<0", "min=1", "min-nan", "n=0", "n<0", "n=25", "tensors-null", "k=0",
         "k<0", "mode=5", "mode<0", "data-null", "opacity-k3", "two-opacity", "opacity-elsewhere", "two-scale", "scale-elsewhere"])
 def test_apply_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_apply(**case), "dgr_relocate_apply", text)
+    refused(_apply(**case), "dgr_relocate_apply", text)
 
 
 def _noise(P=10, xyz=FAKE, scaling=FAKE, rotation=FAKE, opacity=FAKE, step=0, lr=1e-4, lr_dev=None, scale=5e5, k=100.0, x0=0.995):
@@ -113,20 +93,13 @@ def _noise(P=10, xyz=FAKE, scaling=FAKE, rotation=FAKE, opacity=FAKE, step=0, lr
     (dict(x0=float("nan")), "not finite"),
 ], ids=["P<0", "P=2^30", "xyz-null", "scaling-null", "rotation-null", "opacity-null", "step<0", "lr-inf", "scale-nan", "k-inf", "x0-nan"])
 def test_position_noise_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_noise(**case), "dgr_position_noise", text)
+    refused(_noise(**case), "dgr_position_noise", text)
 
 
 def test_python_surface():
     from dgr_amd import optim
-    p = inspect.signature(optim.relocate_dead).parameters
-    assert list(p)[:2] == ["params", "optimizer"]
-    for name, default in (("min_opacity", 0.005), ("draws", None), ("seed", 0), ("step", 0), ("xyz_gradient_accum", None),
-                          ("denom", None), ("max_radii2D", None), ("roles", None)):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
+    keyword_only(optim.relocate_dead, ["params", "optimizer"],
+                 dict(min_opacity=0.005, draws=None, seed=0, step=0, xyz_gradient_accum=None, denom=None, max_radii2D=None, roles=None))
     assert optim.RelocateResult._fields == ("counts", "source")
-    p = inspect.signature(optim.inject_position_noise).parameters
-    assert list(p)[:2] == ["params", "lr"]
-    for name, default in (("noise_scale", 5e5), ("gate_k", 100.0), ("gate_x0", 0.995), ("noise", None), ("seed", 0), ("step", 0),
-                          ("roles", None)):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
-
+    keyword_only(optim.inject_position_noise, ["params", "lr"],
+                 dict(noise_scale=5e5, gate_k=100.0, gate_x0=0.995, noise=None, seed=0, step=0, roles=None))

@@ -1,44 +1,29 @@
 """The map-expansion entry points (include/dgr_hip.h: dgr_seed_*) without a GPU: declared, exported and bound; the descriptor's
 layout; every argument error refused with a message before any device call."""
-import ctypes as C
-import inspect
 import math
-import os
 
 import pytest
 
 from dgr_amd import _capi
 
-from test_capi_symbols import declared_symbols
+from abi_checks import FAKE, assert_descriptor, assert_entry_points, header_text, keyword_only, refused
 
 NAMES = ("dgr_seed_plan_bytes", "dgr_seed_plan", "dgr_seed_apply")
-FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
 INF = float("inf")
 XYZ, LOG_SCALE, RGB_DC, QUAT_IDENTITY, CONST = range(5)
 
 
 def test_symbols_are_declared_exported_and_bound():
-    lib = C.CDLL(_capi.LIB_PATH)
-    for name in NAMES:
-        assert name in declared_symbols(), name
-        assert name in _capi.exported_symbols(), name
-        assert hasattr(lib, name), name
-    assert len(_capi._SIGS["dgr_seed_plan_bytes"][1]) == 3
-    assert len(_capi._SIGS["dgr_seed_plan"][1]) == 15 and len(_capi._SIGS["dgr_seed_apply"][1]) == 17
+    assert_entry_points(NAMES, dict(zip(NAMES, (3, 15, 17))))
 
 
 def test_descriptor_matches_the_c_layout():
     # typedef struct { const float* src; float* dst; int k; int mode; float value; } dgr_seed_tensor;
-    T = _capi.SeedTensor
-    assert C.sizeof(T) == 32  # 28 bytes of fields, padded to the pointers' alignment
-    assert (T.src.offset, T.dst.offset, T.k.offset, T.mode.offset, T.value.offset) == (0, 8, 16, 20, 24)
-    assert _capi.SEED_MAX_TENSORS == 24
-    assert (_capi.SEED_XYZ, _capi.SEED_LOG_SCALE, _capi.SEED_RGB_DC, _capi.SEED_QUAT_IDENTITY, _capi.SEED_CONST) == (0, 1, 2, 3, 4)
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dgr_hip.h")).read()
-    for name, value in (("MAX_TENSORS", 24), ("XYZ", 0), ("LOG_SCALE", 1), ("RGB_DC", 2), ("QUAT_IDENTITY", 3), ("CONST", 4)):
-        assert f"#define DGR_SEED_{name} {value}\n" in header, name
+    # (32 bytes: 28 of fields, padded to the pointers' alignment)
+    assert_descriptor(_capi.SeedTensor, 32, dict(src=0, dst=8, k=16, mode=20, value=24), "SEED",
+                      dict(MAX_TENSORS=24, XYZ=0, LOG_SCALE=1, RGB_DC=2, QUAT_IDENTITY=3, CONST=4))
     for field in ("const float* src;", "float* dst;", "int k;", "int mode;", "float value;"):
-        assert field in header.split("} dgr_seed_tensor;")[0].rsplit("typedef struct {", 1)[1], field
+        assert field in header_text().split("} dgr_seed_tensor;")[0].rsplit("typedef struct {", 1)[1], field
 
 
 def test_plan_bytes_hold_a_byte_per_candidate_and_a_record_per_block():
@@ -56,11 +41,6 @@ def test_plan_bytes_hold_a_byte_per_candidate_and_a_record_per_block():
     assert n + 16 * 8100 <= sizes[-1] <= n + 16 * 8100 + 256
     # the stride divides rounding up: 37 x 23 at stride 3 has 13 x 8 candidates, as many bytes as a 13 x 8 frame
     assert lib.dgr_seed_plan_bytes(37, 23, 3) == lib.dgr_seed_plan_bytes(13, 8, 1)
-
-
-def _refused(rc, text):
-    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in _capi.last_error(), (rc, _capi.last_error())
-    assert _capi.last_error().startswith("dgr_seed_")
 
 
 def _plan(width=64, height=48, stride=1, depth_obs=FAKE, rows=10, plan=FAKE, counts=FAKE):
@@ -90,8 +70,7 @@ def _apply(tensors, width=64, height=48, stride=1, rows=10, rows_out=12, plan=FA
     (dict(counts=None), "counts"),
 ], ids=["plan-null", "plan-misaligned", "depth_obs-null", "W=0", "H<0", "stride=0", "stride<0", "rows<0", "rows=2^30", "counts-null"])
 def test_plan_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_plan(**case), text)
-    assert _capi.last_error().startswith("dgr_seed_plan: ")
+    refused(_plan(**case), "dgr_seed_plan", text)
 
 
 NAN = float("nan")
@@ -134,8 +113,7 @@ NAN = float("nan")
         "tensors-null", "k=0", "k<0", "mode=5", "mode<0", "two-xyz", "xyz-k4", "log-scale-k2", "rgb-k4", "quat-k3",
         "rgb-without-colour", "dst-null", "src-null-with-rows"])
 def test_apply_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_apply(**case), text)
-    assert _capi.last_error().startswith("dgr_seed_apply: ")
+    refused(_apply(**case), "dgr_seed_apply", text)
 
 
 def test_constants_are_formed_in_float64():
@@ -148,11 +126,8 @@ def test_constants_are_formed_in_float64():
 
 def test_python_surface():
     from dgr_amd import optim
-    p = inspect.signature(optim.seed_from_frame).parameters
-    assert list(p)[:9] == ["params", "optimizer", "color_obs", "depth_obs", "viewmatrix", "fx", "fy", "cx", "cy"]
-    for name, default in (("opacity_map", None), ("depth", None), ("silhouette_threshold", 0.5), ("depth_error_min", INF),
-                          ("depth_range", (0.0, INF)), ("stride", 1), ("init_opacity", 0.5), ("scale_factor", 1.0), ("fill", None),
-                          ("roles", None), ("xyz_gradient_accum", None), ("denom", None), ("max_radii2D", None)):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
+    keyword_only(optim.seed_from_frame, ["params", "optimizer", "color_obs", "depth_obs", "viewmatrix", "fx", "fy", "cx", "cy"],
+                 dict(opacity_map=None, depth=None, silhouette_threshold=0.5, depth_error_min=INF, depth_range=(0.0, INF), stride=1,
+                      init_opacity=0.5, scale_factor=1.0, fill=None, roles=None, xyz_gradient_accum=None, denom=None, max_radii2D=None))
     assert optim.SeedCounts._fields == ("rows", "new", "valid", "unseen", "infront")
     assert optim.SEED_ROLES == dict(optim.DEFAULT_ROLES, f_dc="f_dc")

@@ -9,19 +9,13 @@ import torch
 from dgr_amd import _capi, slam
 
 import ssim_model as M
-from test_capi_symbols import declared_symbols
+from abi_checks import FAKE, assert_entry_points, refused
 
 NAMES = ("dgr_ssim_scratch_floats", "dgr_ssim_loss_forward", "dgr_ssim_loss_backward")
-FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
 
 
 def test_symbols_are_declared_exported_and_bound():
-    lib = C.CDLL(_capi.LIB_PATH)
-    for name in NAMES:
-        assert name in declared_symbols(), name
-        assert name in _capi.exported_symbols(), name
-        assert hasattr(lib, name), name
-    assert len(_capi._SIGS["dgr_ssim_loss_forward"][1]) == 16 and len(_capi._SIGS["dgr_ssim_loss_backward"][1]) == 17
+    assert_entry_points(NAMES, {"dgr_ssim_loss_forward": 16, "dgr_ssim_loss_backward": 17})
     assert _capi._SIGS["dgr_ssim_scratch_floats"][0] is C.c_long
 
 
@@ -42,11 +36,6 @@ def test_scratch_size():
             shape[dim] = v
             sizes.append(f(*shape))
         assert all(b > a for a, b in zip(sizes, sizes[1:])), (dim, sizes)
-
-
-def _refused(rc, name, text):
-    err = _capi.last_error()
-    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in err and err.startswith(name + ": "), (rc, err)
 
 
 def _forward(shape=(1, 3, 8, 8), img=FAKE, ref=FAKE, n_depth=0, depth=None, depth_obs=None, scratch=FAKE, loss=FAKE):
@@ -79,18 +68,18 @@ IDS = ["img-null", "ref-null", "scratch-null", "scratch-misaligned", "V=0", "C=0
 
 @pytest.mark.parametrize("case, text", CASES, ids=IDS)
 def test_forward_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_forward(**case), "dgr_ssim_loss_forward", text)
+    refused(_forward(**case), "dgr_ssim_loss_forward", text)
 
 
 @pytest.mark.parametrize("case, text", CASES, ids=IDS)
 def test_backward_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_backward(**case), "dgr_ssim_loss_backward", text)
+    refused(_backward(**case), "dgr_ssim_loss_backward", text)
 
 
 def test_null_outputs_are_refused():
-    _refused(_forward(loss=None), "dgr_ssim_loss_forward", "loss is NULL")
-    _refused(_backward(dimg=None), "dgr_ssim_loss_backward", "dL_dimg is NULL")
-    _refused(_backward(n_depth=64, depth=FAKE, depth_obs=FAKE, ddepth=None), "dgr_ssim_loss_backward", "NULL dL_ddepth")
+    refused(_forward(loss=None), "dgr_ssim_loss_forward", "loss is NULL")
+    refused(_backward(dimg=None), "dgr_ssim_loss_backward", "dL_dimg is NULL")
+    refused(_backward(n_depth=64, depth=FAKE, depth_obs=FAKE, ddepth=None), "dgr_ssim_loss_backward", "NULL dL_ddepth")
 
 
 def test_python_surface_refuses_what_it_cannot_read():

@@ -1,43 +1,28 @@
 """The map-correction entry points (include/dgr_hip.h: dgr_transform_*) without a GPU: declared, exported and bound; the descriptor's
 layout and the mode constants; the scratch size; every argument error refused with a message before any device call; the Python
 surface."""
-import ctypes as C
 import inspect
-import os
 
 import pytest
 
 from dgr_amd import _capi
 
-from test_capi_symbols import declared_symbols
+from abi_checks import FAKE, assert_descriptor, assert_entry_points, header_text, keyword_only, refused
 
 NAMES = ("dgr_transform_scratch_bytes", "dgr_transform_plan", "dgr_transform_apply")
-FAKE = 1 << 20  # a non-NULL, 16-byte aligned "device" pointer: every call below is refused before anything dereferences it
 VALUE, MOMENT1, MOMENT2 = range(3)
 XYZ, QUAT, LOG_SCALE, SH = 0, 4, 8, 12
 
 
 def test_symbols_are_declared_exported_and_bound():
-    lib = C.CDLL(_capi.LIB_PATH)
-    for name in NAMES:
-        assert name in declared_symbols(), name
-        assert name in _capi.exported_symbols(), name
-        assert hasattr(lib, name), name
-    assert [len(_capi._SIGS[name][1]) for name in NAMES] == [1, 5, 8]
+    assert_entry_points(NAMES, dict(zip(NAMES, (1, 5, 8))))
 
 
 def test_descriptor_and_constants_match_the_header():
     # typedef struct { float* data; int k; int mode; int skip; } dgr_transform_tensor;
-    T = _capi.TransformTensor
-    assert C.sizeof(T) == 24 and (T.data.offset, T.k.offset, T.mode.offset, T.skip.offset) == (0, 8, 12, 16)
-    assert _capi.TRANSFORM_MAX_TENSORS == 24
-    assert (_capi.TRANSFORM_VALUE, _capi.TRANSFORM_MOMENT1, _capi.TRANSFORM_MOMENT2) == (0, 1, 2)
-    assert (_capi.TRANSFORM_XYZ, _capi.TRANSFORM_QUAT, _capi.TRANSFORM_LOG_SCALE, _capi.TRANSFORM_SH) == (0, 4, 8, 12)
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "dgr_hip.h")).read()
-    for name, value in (("MAX_TENSORS", 24), ("VALUE", 0), ("MOMENT1", 1), ("MOMENT2", 2), ("XYZ", 0), ("QUAT", 4), ("LOG_SCALE", 8),
-                        ("SH", 12)):
-        assert f"#define DGR_TRANSFORM_{name} {value}\n" in header, name
-    assert "int skip;" in header and "} dgr_transform_tensor;" in header
+    assert_descriptor(_capi.TransformTensor, 24, dict(data=0, k=8, mode=12, skip=16), "TRANSFORM",
+                      dict(MAX_TENSORS=24, VALUE=0, MOMENT1=1, MOMENT2=2, XYZ=0, QUAT=4, LOG_SCALE=8, SH=12))
+    assert "int skip;" in header_text() and "} dgr_transform_tensor;" in header_text()
 
 
 def test_scratch_bytes():
@@ -50,11 +35,6 @@ def test_scratch_bytes():
     assert 111 * 4 <= sizes[1] - sizes[0] <= 128 * 4 and sizes[0] <= 128 * 4 + 64
 
 
-def _refused(rc, who, text):
-    assert rc == _capi.DGR_ERR_BAD_ARGUMENT and text in _capi.last_error(), (rc, _capi.last_error())
-    assert _capi.last_error().startswith(who + ": ")
-
-
 def _plan(K=3, transforms=FAKE, scratch=FAKE, counts=FAKE):
     return _capi.load().dgr_transform_plan(None, K, transforms, scratch, counts)
 
@@ -64,7 +44,7 @@ def _plan(K=3, transforms=FAKE, scratch=FAKE, counts=FAKE):
     (dict(scratch=None), "scratch"), (dict(scratch=FAKE + 8), "aligned"), (dict(counts=None), "counts4_device"),
 ], ids=["K=0", "K<0", "K>2^20", "transforms-null", "scratch-null", "scratch-unaligned", "counts-null"])
 def test_plan_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_plan(**case), "dgr_transform_plan", text)
+    refused(_plan(**case), "dgr_transform_plan", text)
 
 
 def _apply(tensors, P=10, K=3, scratch=FAKE, anchor=None, n=None, data=FAKE, counts=FAKE, descs=True):
@@ -115,16 +95,13 @@ ONE = [(3, XYZ, 0)]
         "scale-k4", "xyz-skip", "sh-skip1", "sh-k10", "sh-k48-skip0", "sh-k45-skip3", "sh-dc-only", "two-xyz", "two-quat",
         "two-scale"])
 def test_apply_refuses_bad_arguments_before_touching_the_gpu(case, text):
-    _refused(_apply(**case), "dgr_transform_apply", text)
+    refused(_apply(**case), "dgr_transform_apply", text)
 
 
 def test_python_surface():
     from dgr_amd import map_steps, optim
     assert optim.transform_map is map_steps.transform_map and optim.pose_corrections is map_steps.pose_corrections
-    p = inspect.signature(optim.transform_map).parameters
-    assert list(p)[:3] == ["params", "optimizer", "transforms"]
-    for name, default in (("anchor", "anchor"), ("moments", "rotate"), ("roles", None)):
-        assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
+    keyword_only(optim.transform_map, ["params", "optimizer", "transforms"], dict(anchor="anchor", moments="rotate", roles=None))
     assert list(inspect.signature(optim.pose_corrections).parameters) == ["old_viewmatrices", "new_viewmatrices"]
     assert optim.TransformCounts._fields == ("transformed", "unanchored", "invalid_transforms", "anchored_invalid")
     assert optim.TRANSFORM_ROLES["f_rest"] == "f_rest" and optim.TRANSFORM_ROLES["shs"] == "shs"

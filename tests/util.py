@@ -36,6 +36,13 @@ def one_tile_scene(K, seed=5, groups=None):
     return s._replace(means=means, scales=scales, opac=opac)
 
 
+def bits_equal(a, b):
+    """two tensors or arrays (torch or numpy, either side) have the same shape, are both float32 and carry the same bits -- NaNs
+    and signed zeros included.  Nothing is cast: a float64 or integer array is not equal to anything."""
+    a, b = (np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t) for t in (a, b))
+    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
 def frac_outside(a, ref, atol, rtol):
     """Fraction of elements with |a-ref| > atol*max(1,|ref|)... generalised: atol + rtol*|ref|."""
     a = np.asarray(a, np.float64)
