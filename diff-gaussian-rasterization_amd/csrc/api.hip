@@ -1048,4 +1048,34 @@ int dgr_debug_exact_math(void* stream, int n, const float* x, const float* a, co
     HIP_TRY(dgr::launch_exact_math_test(n, x, a, b, out_exp, out_div, opt_alpha_mode(), (hipStream_t)stream));
     return DGR_OK;
 }
+int dgr_debug_tile_sort(void* stream, int mode, int n_lists, const unsigned long long* keys, const int* offsets, unsigned* out_ids,
+                        unsigned long long* out_keys) {
+    const bool ids = mode == DGR_TILE_SORT_WAVE || mode == DGR_TILE_SORT_MERGE;
+    if (mode < DGR_TILE_SORT_WAVE || mode > DGR_TILE_SORT_GLOBAL_256 || n_lists < 0 ||
+        (n_lists > 0 && (!keys || !offsets || (ids ? !out_ids : !out_keys)))) {
+        set_last_error("dgr_debug_tile_sort: bad argument");
+        return DGR_ERR_BAD_ARGUMENT;
+    }
+    if (n_lists == 0) return DGR_OK;
+    // the lengths each routine is called with in the binning kernels (and what its LDS array holds)
+    const int lo = mode == DGR_TILE_SORT_MERGE ? 1025 : 1;
+    const int hi = mode == DGR_TILE_SORT_WAVE ? 1024 : mode == DGR_TILE_SORT_PART ? 512 : mode == DGR_TILE_SORT_MERGE ? 6144 : 0x7fffffff;
+    for (int b = 0; b < n_lists; b++) {
+        const long long n = (long long)offsets[b + 1] - offsets[b];
+        if (offsets[b] < 0 || n < lo || n > hi) {
+            set_last_error("dgr_debug_tile_sort: list " + std::to_string(b) + " has " + std::to_string(n) + " keys, mode " +
+                           std::to_string(mode) + " takes " + std::to_string(lo) + " .. " + std::to_string(hi));
+            return DGR_ERR_BAD_ARGUMENT;
+        }
+    }
+    int* d_off = nullptr;  // (a debug entry: its own allocation, and the call returns when the sort has finished)
+    const size_t bytes = ((size_t)n_lists + 1) * sizeof(int);
+    HIP_TRY(hipMalloc((void**)&d_off, bytes));
+    hipError_t rc = hipMemcpy(d_off, offsets, bytes, hipMemcpyHostToDevice);
+    if (rc == hipSuccess) rc = dgr::launch_tile_sort_test(mode, n_lists, (const uint64_t*)keys, d_off, out_ids, (uint64_t*)out_keys, (hipStream_t)stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize((hipStream_t)stream);
+    (void)hipFree(d_off);
+    HIP_TRY(rc);
+    return DGR_OK;
+}
 }  // extern "C"

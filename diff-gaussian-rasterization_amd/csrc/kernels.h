@@ -421,5 +421,8 @@ hipError_t launch_wave_reduce_test(const float* in, float* out16, float* out12, 
                                    hipStream_t stream);
 hipError_t launch_exact_math_test(int n, const float* x, const float* a, const float* b, float* out_exp, float* out_div, int alpha_mode,
                                   hipStream_t stream);
+// offsets: n_lists + 1 DEVICE ints (api.hip copies the caller's host array)
+hipError_t launch_tile_sort_test(int mode, int n_lists, const uint64_t* keys, const int* offsets, uint32_t* out_ids, uint64_t* out_keys,
+                                 hipStream_t stream);
 
 }  // namespace dgr

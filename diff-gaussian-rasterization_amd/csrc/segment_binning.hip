@@ -279,19 +279,6 @@ __device__ __forceinline__ void for_each_pair(const K2Shared& sh, int nwg, uint3
     }
 }
 
-// One wave, one tile list of up to REG_SORT_MAX entries (tile_sort.h).  (Round 8 gave frames of long lists -- LONG_LISTS, chosen per
-// launch from the expected list length -- a network on the full 64-bit keys, because the 32-bit one needed a four-part rank merge
-// above 512 entries; round 9's takes 1024 in one pass and is the faster of the two there as well: bin_tiles 131 -> 82 us at config 4,
-// 103 -> 67 on the heavy-tailed scene, profiles/r9/bin_tiles_ab.txt.)  Inlined at its three call sites (236 registers spilled around
-// them in all): as a real call -- 45 spilled -- the kernel was a third slower everywhere (synth-v1 25.5 -> 34.3 us, config 4 82 -> 104).
-__device__ __forceinline__ void sort_tile_in_wave(uint64_t* src, int n, uint32_t* dst, int lane) {
-    if (n <= 64) sort_wave_trunc<1>(src, n, dst, lane);
-    else if (n <= 128) sort_wave_trunc<2>(src, n, dst, lane);
-    else if (n <= 256) sort_wave_trunc<4>(src, n, dst, lane);
-    else if (n <= 512) sort_wave_trunc<8>(src, n, dst, lane);
-    else sort_wave_trunc<16>(src, n, dst, lane);
-}
-
 // (xcd_contiguous, dgr_common.h: XCD x gets a contiguous run of segments)
 __global__ void __launch_bounds__(K2_THREADS, 6) bin_tiles_kernel(ImageView img, uint32_t* __restrict__ point_list,
                                                                   uint64_t* __restrict__ key_scratch, SegmentTables tb,

@@ -1,6 +1,7 @@
-// selftest.hip -- device self-tests of the shared headers (wave_reduce.h, render_common.h, exact_math.h) behind the dgr_debug_*
-// entry points (api.hip); no variant's code.
+// selftest.hip -- device self-tests of the shared headers (wave_reduce.h, render_common.h, exact_math.h, tile_sort.h) behind the
+// dgr_debug_* entry points (api.hip); no variant's code.
 #include "render_common.h"
+#include "tile_sort.h"
 
 namespace dgr {
 namespace {
@@ -97,8 +98,58 @@ __global__ void __launch_bounds__(256) exact_math_test_kernel(int n, const float
         out_div[i] = t_div<ALPHA_REF>(a[i], b[i], inv);
     }
 }
+
+// self-test of tile_sort.h (dgr_debug_tile_sort): workgroup b sorts list b = keys[offsets[b] .. offsets[b + 1]), each routine as
+// the binning kernels call it -- bin_tiles' 512 threads and its keys in LDS (segment_binning.hip: K2_THREADS, K2_CAP) for modes
+// 0 .. 2, in place in global memory for the others.  The waves take turns (list b: wave b % 8) and every second list starts
+// at an odd key index, so that the 16-byte rows of the id transposition meet both alignments of a list.
+constexpr int TS_THREADS = 512, TS_WAVES = TS_THREADS / 64, TS_CAP = 6144;
+template <int NT>
+__global__ void __launch_bounds__(NT) tile_sort_test_kernel(int mode, const uint64_t* __restrict__ keys, const int* __restrict__ offsets,
+                                                            uint32_t* __restrict__ out_ids, uint64_t* out_keys) {
+    const int tid = threadIdx.x;
+    const int off = offsets[blockIdx.x], n = offsets[blockIdx.x + 1] - off;
+    if (n <= 0) return;
+    if (mode >= DGR_TILE_SORT_GLOBAL) {
+        for (int i = tid; i < n; i += NT) out_keys[off + i] = keys[off + i];
+        __syncthreads();
+        wg_sort_global<NT>(out_keys + off, n, tid);
+        return;
+    }
+    if constexpr (NT == TS_THREADS) {
+        __shared__ uint64_t sk[TS_CAP + 1];
+        const int lane = tid & 63, wave = tid >> 6;
+        // (the API checked the lengths; a list the mode cannot take is left alone rather than written past the array)
+        if (n > (mode == DGR_TILE_SORT_WAVE ? 1024 : mode == DGR_TILE_SORT_PART ? PART_Q : TS_CAP)) return;
+        uint64_t* const list = sk + (blockIdx.x & 1);
+        for (int i = tid; i < n; i += NT) list[i] = keys[off + i];
+        __syncthreads();
+        const int turn = (int)(blockIdx.x % TS_WAVES);
+        if (mode == DGR_TILE_SORT_WAVE) {
+            if (wave == turn) sort_tile_in_wave(list, n, out_ids + off, lane);
+        } else if (mode == DGR_TILE_SORT_PART) {
+            if (wave == turn) sort_list_part(list, n, 0, lane);
+            __syncthreads();
+            for (int i = tid; i < n; i += NT) out_keys[off + i] = list[i];
+        } else {  // sort_lists' sequence for one long list (segment_binning.hip)
+            for (int p = 0; p < list_parts(n); p++)
+                if ((turn + p) % TS_WAVES == wave) sort_list_part(list, n, p, lane);
+            __syncthreads();
+            merge_list_parts<NT>(list, n, out_ids + off, tid);
+        }
+    }
+}
 }  // namespace
 
+hipError_t launch_tile_sort_test(int mode, int n_lists, const uint64_t* keys, const int* offsets, uint32_t* out_ids, uint64_t* out_keys,
+                                 hipStream_t stream) {
+    if (n_lists <= 0) return hipSuccess;
+    if (mode == DGR_TILE_SORT_GLOBAL_256)  // (sort_tiles_kernel's SORT_THREADS, binning.hip)
+        launch(tile_sort_test_kernel<256>, dim3(n_lists), dim3(256), stream, mode, keys, offsets, out_ids, out_keys);
+    else
+        launch(tile_sort_test_kernel<TS_THREADS>, dim3(n_lists), dim3(TS_THREADS), stream, mode, keys, offsets, out_ids, out_keys);
+    return hipGetLastError();
+}
 hipError_t launch_exact_math_test(int n, const float* x, const float* a, const float* b, float* out_exp, float* out_div,
                                   int alpha_mode, hipStream_t stream) {
     if (n <= 0) return hipSuccess;

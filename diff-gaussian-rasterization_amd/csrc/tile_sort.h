@@ -253,6 +253,20 @@ __device__ __forceinline__ void sort_wave_trunc(uint64_t* list, int n, uint32_t*
     }
 }
 
+// One wave, one tile list of up to 1024 entries (segment_binning.hip: REG_SORT_MAX).  (Round 8 gave frames of long lists -- LONG_LISTS, chosen per
+// launch from the expected list length -- a network on the full 64-bit keys, because the 32-bit one needed a four-part rank merge
+// above 512 entries; round 9's takes 1024 in one pass and is the faster of the two there as well: bin_tiles 131 -> 82 us at config 4,
+// 103 -> 67 on the heavy-tailed scene, profiles/r9/bin_tiles_ab.txt.)  Inlined at bin_tiles' three call sites (236 registers spilled around
+// them in all): as a real call -- 45 spilled -- the kernel was a third slower everywhere (synth-v1 25.5 -> 34.3 us, config 4 82 -> 104).
+// Every network wider than one word per lane gets n > 32 NCH here, which the ids form of sort_wave_trunc needs for its transposition.
+__device__ __forceinline__ void sort_tile_in_wave(uint64_t* src, int n, uint32_t* dst, int lane) {
+    if (n <= 64) sort_wave_trunc<1>(src, n, dst, lane);
+    else if (n <= 128) sort_wave_trunc<2>(src, n, dst, lane);
+    else if (n <= 256) sort_wave_trunc<4>(src, n, dst, lane);
+    else if (n <= 512) sort_wave_trunc<8>(src, n, dst, lane);
+    else sort_wave_trunc<16>(src, n, dst, lane);
+}
+
 // Lists above the one-wave limit, whole workgroup of NT threads, keys in LDS (no padding needed): parts of PART_Q entries are
 // sorted in place by one wave each (sort_list_part; the caller deals the parts of ALL its long lists to its waves at once),
 // then, behind a barrier, every list is merged by rank with every thread searching (merge_list_parts).  1135 entries: ~7 us

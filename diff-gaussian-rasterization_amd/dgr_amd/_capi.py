@@ -200,6 +200,7 @@ _SIGS = {
     "dgr_debug_half_reduce16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "dgr_debug_lane_lists": (_i, [_vp, _vp, _vp, _vp]),
     "dgr_debug_bin_tiles_trace": (_i, [_vp]),
+    "dgr_debug_tile_sort": (_i, [_vp, _i, _i, _vp, C.POINTER(_i), _vp, _vp]),
     "dgr_profile_select": (_i, [C.c_char_p]),
     "dgr_profile_stage_count": (_i, []),
     "dgr_profile_stage_name": (C.c_char_p, [_i]),

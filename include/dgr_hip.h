@@ -978,6 +978,29 @@ int dgr_debug_lane_lists(void* stream, const unsigned char* codes, unsigned* pai
  * a / b for normal operands.  n device floats each.  tests/test_hip_exact_math.py compares both with the CPU restatement's
  * functions bit for bit. */
 int dgr_debug_exact_math(void* stream, int n, const float* x, const float* a, const float* b, float* out_exp, float* out_div);
+/* Self-test of csrc/tile_sort.h, the sorting routines of the binning kernels.  A batch of n_lists lists in ONE launch, a workgroup per
+ * list: list b is keys[offsets[b] .. offsets[b + 1]) -- `keys` device memory, 64-bit (depth bits << 32 | id), unique; `offsets` a
+ * HOST array of n_lists + 1 ascending ints.  Every routine runs as the binning kernels call it (bin_tiles' 512 threads with the keys
+ * in LDS; the global sorts in place in device memory):
+ *   DGR_TILE_SORT_WAVE        sort_tile_in_wave: one wave's register network, 1 .. 1024 keys; out_ids[offsets[b] + i] = the id (low
+ *                             word) of the list's i-th smallest key.  (It picks sort_wave_trunc<NCH, true> with n > 32 NCH for every
+ *                             NCH > 1, which that form's transposition of the ids through the list's own LDS bytes REQUIRES: never call
+ *                             the ids form of a wider network on a shorter list.)
+ *   DGR_TILE_SORT_PART        sort_list_part = sort_wave_trunc<8, false>: 1 .. 512 keys sorted in place; out_keys receives the list;
+ *   DGR_TILE_SORT_MERGE       the long-list sequence: 512-key parts dealt to the waves, barrier, merge_list_parts<512>; 1025 .. 6144
+ *                             keys; out_ids as above;
+ *   DGR_TILE_SORT_GLOBAL      wg_sort_global<512> (bin_tiles' lists above its LDS budget), any length >= 1: out_keys receives a
+ *                             copy of the list and is sorted in place;
+ *   DGR_TILE_SORT_GLOBAL_256  the same with sort_tiles' 256 threads.
+ * The output a mode does not write may be NULL.  A length outside a mode's range is refused (DGR_ERR_BAD_ARGUMENT).  The call
+ * returns after the sort has finished.  tests/test_hip_tile_sort.py compares with a sort of the keys on the host. */
+#define DGR_TILE_SORT_WAVE 0
+#define DGR_TILE_SORT_PART 1
+#define DGR_TILE_SORT_MERGE 2
+#define DGR_TILE_SORT_GLOBAL 3
+#define DGR_TILE_SORT_GLOBAL_256 4
+int dgr_debug_tile_sort(void* stream, int mode, int n_lists, const unsigned long long* keys, const int* offsets, unsigned* out_ids,
+                        unsigned long long* out_keys);
 
 /* ---- per-stage timing (bench.py's roofline object) ----
  * dgr_profile_select("") disables timing (default), "all" brackets every stage, a stage name brackets that

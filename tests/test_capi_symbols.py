@@ -250,3 +250,22 @@ def test_thread_options_override_the_process_wide_ones_per_thread():
         with _capi.thread_options(alpha_mode=7):
             pass
     assert lib.dgr_get_thread_option(b"alpha_mode") == 0
+
+
+def test_tile_sort_self_test_refuses_lengths_its_routines_are_not_called_with():
+    """dgr_debug_tile_sort checks mode, pointers and every list's length on the host before anything touches the GPU: the ids form
+    of the wave sort is only valid in the ranges sort_tile_in_wave gives it, and the LDS array holds 6144 keys."""
+    import ctypes as C
+    from abi_checks import FAKE, refused
+    lib = _capi.load()
+    off = lambda *v: (C.c_int * len(v))(*v)   # noqa: E731
+    who = "dgr_debug_tile_sort"
+    assert lib.dgr_debug_tile_sort(None, 0, 0, None, None, None, None) == 0
+    refused(lib.dgr_debug_tile_sort(None, 5, 1, FAKE, off(0, 1), FAKE, FAKE), who, "bad argument")
+    refused(lib.dgr_debug_tile_sort(None, -1, 1, FAKE, off(0, 1), FAKE, FAKE), who, "bad argument")
+    refused(lib.dgr_debug_tile_sort(None, 0, 1, FAKE, off(0, 1), None, FAKE), who, "bad argument")    # WAVE writes ids
+    refused(lib.dgr_debug_tile_sort(None, 1, 1, FAKE, off(0, 1), FAKE, None), who, "bad argument")    # PART writes keys
+    refused(lib.dgr_debug_tile_sort(None, 0, 1, None, off(0, 1), FAKE, FAKE), who, "bad argument")
+    for mode, n in ((0, 1025), (0, 0), (1, 513), (2, 1024), (2, 6145), (3, 0), (4, -1)):
+        refused(lib.dgr_debug_tile_sort(None, mode, 2, FAKE, off(0, 1 if mode != 2 else 1025, (1 if mode != 2 else 1025) + n), FAKE, FAKE),
+                who, "list 1 has")

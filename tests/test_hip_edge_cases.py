@@ -151,7 +151,9 @@ def test_mark_visible(oracle):
 
 @pytest.mark.parametrize("P", [9000, 24000])
 def test_oversize_tiles_and_many_batches(oracle, P):
-    """~2300 / ~6000 instances per tile: the per-tile sort leaves LDS (n > 2048) and the blend kernels stage many batches."""
+    """~2300 / ~6000 instances per tile, two tiles per segment: lists above the one-wave limit (1024 entries) are sorted in parts
+    of 512 and merged by rank; at ~6000 the segment exceeds bin_tiles' LDS budget (6144 keys) and takes the dense path, a list at
+    a time.  The blend kernels stage many batches.  (The exact edges: tests/test_hip_binning_edges.py.)"""
     s = make_scene(P, 32, 32, 9)
     out, d = hh.hip_forward(s, 1)
     st, ref = hh.oracle_forward(oracle, s, 1)
@@ -895,8 +897,9 @@ def test_tile_lists_with_equal_and_nearly_equal_depths(oracle, P, W, H, sm):
     """The per-tile sort orders a list by ONE 32-bit word per entry -- the depth's upper 22 bits and the entry's slot -- and
     settles entries that agree in those bits with a fix-up on the full (depth, id) keys (csrc/tile_sort.h).  Here a third of
     the Gaussians lie on one plane of constant camera depth (identical depth bits: the id decides), a third within 2^-17
-    relative of another (equal upper bits, different full keys), the rest anywhere.  Lists of ~450 entries (one register pass),
-    ~800 (four parts merged by rank) and ~2000-2800 (the workgroup's LDS sort), runs of equal upper bits hundreds long.
+    relative of another (equal upper bits, different full keys), the rest anywhere.  Lists of ~450 and ~800 entries (one wave's
+    register network, which takes up to 1024) and ~2000-2800 (parts of 512 merged by rank; a segment above 6144 keys takes the
+    dense path), runs of equal upper bits hundreds long.
     point_list and ranges must be the oracle's bit for bit."""
     from dgr_amd.synth import camera
     s = make_scene(P, W, H, 9)
