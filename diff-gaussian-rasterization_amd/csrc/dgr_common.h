@@ -4,8 +4,9 @@
 // (L/cuda_rasterizer/rasterizer_impl.h:29-72, rasterizer_impl.cu:155-193).  The buffers stay
 // opaque at the boundary, so the layout here is chosen for the MI355X kernels instead:
 //   geometry : one 48-byte render record per Gaussian in a 64-byte slot (3 x float4, gathered as whole 16-B
-//              pieces by the blend kernels, from ONE L2 line), depth, radius, tile rect (4 x u16), clamp bits (the 3D covariance is
-//              NOT kept: the backward re-forms it from scale and rotation, same expression, same bits)
+//              pieces by the blend kernels, from ONE L2 line), depth, radius, tile rect (4 x u16), clamp bits, the nine SH direction
+//              derivatives packed to 36 bytes (the 3D covariance is NOT kept: the backward re-forms it from scale and rotation,
+//              same expression, same bits)
 //   image    : per-tile {count, fill, range} + per-pixel n_contrib (+ full: final T, n_valid)
 //   binning  : per-instance 64-bit sort keys (depth bits << 32 | gaussian id), the sorted id list, arrival ranks
 #pragma once
@@ -59,9 +60,11 @@ struct GeometryView {
                         //     point_offsets, exclusive form); written by count_rank
     uint32_t* block_tiles;  // [ceil(P/256)] instances produced by each 256-Gaussian block of preprocess; turned into its
                             //     exclusive prefix in place by scan_blocks
-    float4* shd;        // [3][P] (three planes) d(colour)/d(view direction x, y, z) of the SH evaluation ({r, g, b, -} each), written by
+    float4* shd_a;      // [P] d(colour)/d(view direction x, y, z) of the SH evaluation, nine floats per Gaussian packed into two
+    float4* shd_b;      // [P] float4 planes and one float plane: shd_a = {dx.r, dx.g, dx.b, dy.r}, shd_b = {dy.g, dy.b, dz.r, dz.g},
+    float* shd_c;       // [P] shd_c = dz.b (consecutive lanes touch consecutive, naturally aligned pieces of each plane).  Written by
                         //     preprocess_fwd for the Gaussians whose colour it evaluates: the backward needs the 45 higher SH
-                        //     coefficients only through these nine numbers, so it reads 48 bytes instead of the 192-byte row
+                        //     coefficients only through these nine numbers, so it reads 36 bytes instead of the 192-byte row
     size_t bytes;
 };
 __host__ __device__ inline GeometryView carve_geometry(char* base, int P) {
@@ -74,7 +77,13 @@ __host__ __device__ inline GeometryView carve_geometry(char* base, int P) {
     g.clamped = (uint8_t*)(base + o); o = align_up(o + (size_t)P, 256);
     g.goff = (uint32_t*)(base + o);   o = align_up(o + sizeof(uint32_t) * (size_t)P, 256);
     g.block_tiles = (uint32_t*)(base + o); o = align_up(o + sizeof(uint32_t) * (((size_t)P + 255) / 256), 256);
-    g.shd = (float4*)(base + o);      o = align_up(o + sizeof(float4) * 3 * (size_t)P, 256);
+    // (dgr_geometry_bytes is a documented figure, 133 bytes per Gaussian, that tests/test_capi_symbols.py pins: the packed planes
+    //  lie at the front of the 48 P bytes the three float4 planes had, and the 12 P behind them are never touched)
+    const size_t shd_region_end = align_up(o + sizeof(float4) * 3 * (size_t)P, 256);
+    g.shd_a = (float4*)(base + o);    o = align_up(o + sizeof(float4) * (size_t)P, 256);
+    g.shd_b = (float4*)(base + o);    o = align_up(o + sizeof(float4) * (size_t)P, 256);
+    g.shd_c = (float*)(base + o);     o = align_up(o + sizeof(float) * (size_t)P, 256);
+    if (o < shd_region_end) o = shd_region_end;
     g.bytes = o;
     return g;
 }

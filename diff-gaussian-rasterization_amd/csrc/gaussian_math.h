@@ -214,21 +214,33 @@ __device__ __forceinline__ float4 load_streaming(const float4* src) {
     const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(src));
     return make_float4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ void sh_rows_to_lanes(const float* __restrict__ src, size_t g_block, float* lds, float (&f)[48]) {
+// `need`: the wave's ballot of the lanes that will use their row.  Only those rows are fetched: piece e of slab r belongs to
+// Gaussian 32 r + e / 12 of the wave, and a piece of a row nobody needs is not requested (its LDS cells get zeros, and its lane
+// does not read them: f[] is then left as it was).  A view that culls a Gaussian so never moves its 192-byte row.
+__device__ __forceinline__ void sh_rows_to_lanes(const float* __restrict__ src, size_t g_block, float* lds, uint64_t need, float (&f)[48]) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* my = lds + wave * (SHT_ROWS * SHT_LD);
     const float4* base = reinterpret_cast<const float4*>(src) + (g_block + (size_t)wave * 64) * 12;
 #pragma unroll
     for (int r = 0; r < 2; r++) {
+        const uint32_t slab_need = (uint32_t)(need >> (32 * r));
+        if (slab_need == 0u) continue;  // (wave-uniform)
         const float4* p = base + (size_t)r * SHT_ROWS * 12;
+        float4 v[6];  // all six requests go out before the first is stored
 #pragma unroll
         for (int i = 0; i < 6; i++) {
             const int e = i * 64 + lane;  // float4 index inside the 32-row slab
+            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((slab_need >> (e / 12)) & 1u) v[i] = load_streaming(p + e);
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const int e = i * 64 + lane;
             const int g = e / 12, c = e - 12 * g;
-            *reinterpret_cast<float4*>(my + g * SHT_LD + 4 * c) = load_streaming(p + e);
+            *reinterpret_cast<float4*>(my + g * SHT_LD + 4 * c) = v[i];
         }
         wave_sync();
-        if ((lane >> 5) == r) {
+        if ((lane >> 5) == r && ((slab_need >> (lane & 31)) & 1u)) {
             const float* row = my + (lane & 31) * SHT_LD;
 #pragma unroll
             for (int c = 0; c < 12; c++) {

@@ -17,7 +17,10 @@
 
 #pragma clang fp contract(off)
 #ifndef DGR_BWD_BATCH_WAVES
-#define DGR_BWD_BATCH_WAVES 2  // waves per SIMD the batched backward is compiled for (48 dL_dsh sums live across its view loop)
+// waves per SIMD the batched backward is compiled for (48 dL_dsh sums live across its view loop).  3 is what its 44 KB of LDS allow
+// and what every instance ran at when compiled for 2; stated, since with the packed SH direction derivatives the full instance
+// compiled for 2 takes 184 registers (2 waves) and for 3 the 166 it had, without scratch.
+#define DGR_BWD_BATCH_WAVES 3
 #endif
 
 namespace dgr {
@@ -33,8 +36,8 @@ namespace dgr {
 // Under map_off the covariance and SH blocks still run (the pose needs dL/da..c and dL/dcampos) but add nothing to the outputs.
 template <bool COMPLETE = false>
 __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const bool full, float3 m, const float (&c3)[6],
-                                               const float (&acc)[16], bool vis, uint8_t cl_in, float4 shd0, float4 shd1,
-                                               float4 shd2, float3& dmean_out, float (&dcov)[6], float (&coef)[16],
+                                               const float (&acc)[16], bool vis, uint8_t cl_in, float4 shd_a, float4 shd_b,
+                                               float shd_c, float3& dmean_out, float (&dcov)[6], float (&coef)[16],
                                                float3& dRGB, float (&pose)[12]) {
     // light: the blend kernel's median-depth term; full: computeCov2DCUDA ASSIGNS (F/cuda_rasterizer/backward.cu:383)
     float3 dmean = make_float3(0.f, 0.f, 0.f);
@@ -175,11 +178,11 @@ __device__ __forceinline__ void bwd_view_terms(const PreprocessBwdArgs& a, const
         dRGB.x *= (cl & 1) ? 0 : 1;
         dRGB.y *= (cl & 2) ? 0 : 1;
         dRGB.z *= (cl & 4) ? 0 : 1;
-        // d(colour)/d(direction): the forward evaluated it from the SH row it had in registers (geom.shd, requested
+        // d(colour)/d(direction): the forward evaluated it from the SH row it had in registers (geom.shd_a/b/c, requested
         // with the other inputs above) -- the basis values below need the direction only, so the 192-byte rows are
         // not read again
-        const float3 dRGBdx = make_float3(shd0.x, shd0.y, shd0.z), dRGBdy = make_float3(shd1.x, shd1.y, shd1.z),
-                     dRGBdz = make_float3(shd2.x, shd2.y, shd2.z);
+        const float3 dRGBdx = make_float3(shd_a.x, shd_a.y, shd_a.z), dRGBdy = make_float3(shd_a.w, shd_b.x, shd_b.y),
+                     dRGBdz = make_float3(shd_b.z, shd_b.w, shd_c);
         const float x = dir.x, y = dir.y, z = dir.z;
         coef[0] = SH_C0;
         if (a.D > 0) {
@@ -354,7 +357,7 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
 
         const float3 m = load_row3(a.means3D, idx);
         // A tracking step (map_off: the pose gradient only) needs the three sums, the mean and the radius: the covariance, the
-        // scale / rotation, the clamp bits and the SH direction derivatives -- 77 of the 157 bytes a Gaussian costs this kernel --
+        // scale / rotation, the clamp bits and the SH direction derivatives -- 65 of the 145 bytes a Gaussian costs this kernel --
         // feed only the per-Gaussian gradients.  The test is kernel-uniform and known at launch: no load waits for another.
         // (COMPLETE: the pose's cov2D and SH paths need the covariance, the clamp bits and the SH direction derivatives too)
         const bool need_map = !a.map_off;
@@ -378,10 +381,11 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
             q_in = load_row4(a.rotations, idx);
         }
         uint8_t cl_in = 0;
-        float4 shd0 = make_float4(0.f, 0.f, 0.f, 0.f), shd1 = shd0, shd2 = shd0;
+        float4 shd_a = make_float4(0.f, 0.f, 0.f, 0.f), shd_b = shd_a;
+        float shd_c = 0.f;
         if (need_terms) {
             cl_in = a.geom.clamped[idx];
-            shd0 = a.geom.shd[idx]; shd1 = a.geom.shd[(size_t)a.P + idx]; shd2 = a.geom.shd[2 * (size_t)a.P + idx];
+            shd_a = a.geom.shd_a[idx]; shd_b = a.geom.shd_b[idx]; shd_c = a.geom.shd_c[idx];
         }
         const bool vis = rad > 0;
         float acc[16];
@@ -409,7 +413,7 @@ __global__ void __launch_bounds__(256, DGR_PPB_WAVES) preprocess_bwd_kernel(Prep
         float3 dmean;
         float dcov[6], coef[16];
         float3 dRGB;
-        bwd_view_terms<COMPLETE>(a, a.full_variant != 0, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
+        bwd_view_terms<COMPLETE>(a, a.full_variant != 0, m, c3, acc, vis, cl_in, shd_a, shd_b, shd_c, dmean, dcov, coef, dRGB, pose);
         float3 dscale = make_float3(0, 0, 0);
         float4 drot = make_float4(0, 0, 0, 0);
         const bool do_map = vis && !a.map_off;
@@ -538,14 +542,15 @@ __global__ void __launch_bounds__(256, COMPLETE ? 3 : DGR_BWD_BATCH_WAVES) prepr
             const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3];
             const int rad = a.radii[idx];
             const uint8_t cl_in = a.geom.clamped[idx];
-            const float4 shd0 = a.geom.shd[idx], shd1 = a.geom.shd[(size_t)P + idx], shd2 = a.geom.shd[2 * (size_t)P + idx];
+            const float4 shd_a = a.geom.shd_a[idx], shd_b = a.geom.shd_b[idx];
+            const float shd_c = a.geom.shd_c[idx];
             const bool vis = rad > 0;
             float acc[16];
             unpack_acc_row(a0, a1, a2, a3, vis, acc);
             write_dmean2D(a, idx, acc);
             float3 dmean, dRGB;
             float dcov[6], coef[16];
-            bwd_view_terms<COMPLETE>(a, FULL, m, c3, acc, vis, cl_in, shd0, shd1, shd2, dmean, dcov, coef, dRGB, pose);
+            bwd_view_terms<COMPLETE>(a, FULL, m, c3, acc, vis, cl_in, shd_a, shd_b, shd_c, dmean, dcov, coef, dRGB, pose);
             any_map |= vis && !a.map_off;
             if (!(COMPLETE && a.map_off)) {  // (COMPLETE under map_off: the mapping blend's sums reach no output, as one view)
                 dop_s += acc[9];

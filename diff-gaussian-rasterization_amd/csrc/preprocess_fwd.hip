@@ -146,10 +146,10 @@ __device__ __forceinline__ void fwd_view_colour(const PreprocessFwdArgs& a, int 
         // backward needs of the SH coefficients beyond the basis values, which depend on the direction alone
         float3 dRGBdx = make_float3(0, 0, 0), dRGBdy = make_float3(0, 0, 0), dRGBdz = make_float3(0, 0, 0);
         sh_direction_derivatives(s, a.D, dir, dRGBdx, dRGBdy, dRGBdz);
-        float4* shd = a.geom.shd + (size_t)idx;  // three planes of P float4: consecutive lanes store consecutive 16-byte pieces
-        shd[0] = make_float4(dRGBdx.x, dRGBdx.y, dRGBdx.z, 0.0f);
-        shd[(size_t)a.P] = make_float4(dRGBdy.x, dRGBdy.y, dRGBdy.z, 0.0f);
-        shd[2 * (size_t)a.P] = make_float4(dRGBdz.x, dRGBdz.y, dRGBdz.z, 0.0f);
+        // nine floats in 36 bytes (dgr_common.h: shd_a / shd_b / shd_c): consecutive lanes store consecutive pieces of each plane
+        a.geom.shd_a[idx] = make_float4(dRGBdx.x, dRGBdx.y, dRGBdx.z, dRGBdy.x);
+        a.geom.shd_b[idx] = make_float4(dRGBdy.y, dRGBdy.z, dRGBdz.x, dRGBdz.y);
+        a.geom.shd_c[idx] = dRGBdz.z;
     }
     a.geom.clamped[idx] = (uint8_t)((res.x < 0 ? 1 : 0) | (res.y < 0 ? 2 : 0) | (res.z < 0 ? 4 : 0));
     rgb = make_float3(fmaxf(res.x, 0.0f), fmaxf(res.y, 0.0f), fmaxf(res.z, 0.0f));
@@ -159,10 +159,12 @@ __device__ __forceinline__ void fwd_view_colour(const PreprocessFwdArgs& a, int 
 // The SH row of Gaussian idx for the lanes that `need` it -- whatever the caller's "someone needs SH" predicate is -- as SHCoeffs.
 // Whole block in range, 16 coefficients, 16-byte aligned rows and some lane in need: the block's rows move through LDS
 // (`lds`: 4 * SHT_ROWS * SHT_LD floats; block-uniform, every lane of the block must get here); else a lane loads its own.
+// Either way only the rows of lanes in need are requested (the wave's ballot goes with the transposition): the row of a
+// Gaussian this view culled costs no traffic.
 __device__ __forceinline__ void fetch_sh(const PreprocessFwdArgs& a, int idx, bool need, float* lds, SHCoeffs& s) {
     const bool blk_fast = a.sh_vec_ok && a.M == 16 && (size_t)blockIdx.x * 256 + 256 <= (size_t)a.P && __syncthreads_or(need);
     float shf[48];
-    if (blk_fast) sh_rows_to_lanes(a.shs, (size_t)blockIdx.x * 256, lds, shf);
+    if (blk_fast) sh_rows_to_lanes(a.shs, (size_t)blockIdx.x * 256, lds, __builtin_amdgcn_ballot_w64(need), shf);
     if (need) {
         if (blk_fast) {
 #pragma unroll

@@ -207,11 +207,18 @@ struct AbsGrad {
 // sh, opacity, scales, rotations | cov3D, colors, 256-byte aligned; the first six are one contiguous span = the multi-GPU
 // all-reduce payload.  g[] receives them in the return order of the reference binding: means2D, colors, opacity, means3D,
 // cov3D, sh, scales, rotations.  Every row is written by the kernels (zeros for invisible Gaussians; M > 16: api.hip clears dL_dsh
-// first): no zero-fill.
-inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g, float** gp) {
-    carve(dev, {{&g[3], {P, 3}, at::kFloat}, {&g[0], {P, 3}, at::kFloat}, {&g[5], {P, M, 3}, at::kFloat}, {&g[2], {P, 1}, at::kFloat},
-                {&g[6], {P, 3}, at::kFloat}, {&g[7], {P, 4}, at::kFloat}, {&g[4], {P, 6}, at::kFloat}, {&g[1], {P, 3}, at::kFloat}});
-    for (int i = 0; i < 8; i++) gp[i] = ptr<float>(g[i]);
+// first): no zero-fill.  The two trailing segments are carved only on demand (want_cov3D, want_colors): a caller without a
+// cov3D_precomp / colors_precomp leaf has no use for them, g[4] / g[1] then stay undefined and gp[4] / gp[1] NULL, and the
+// per-Gaussian backward -- every dense output of which may be NULL -- does not write the 24 + 12 bytes per Gaussian.
+inline void grad_arena(const c10::Device& dev, int P, int M, Tensor* g, float** gp, bool want_colors = true, bool want_cov3D = true) {
+    const int64_t s3[] = {P, 3}, ssh[] = {P, M, 3}, s1[] = {P, 1}, s4[] = {P, 4}, s6[] = {P, 6};  // (a Window refers to its sizes)
+    const Window w[8] = {{&g[3], s3, at::kFloat}, {&g[0], s3, at::kFloat}, {&g[5], ssh, at::kFloat}, {&g[2], s1, at::kFloat},
+                         {&g[6], s3, at::kFloat}, {&g[7], s4, at::kFloat}, {&g[4], s6, at::kFloat}, {&g[1], s3, at::kFloat}};
+    if (want_colors && want_cov3D) carve(dev, {w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]});
+    else if (want_cov3D) carve(dev, {w[0], w[1], w[2], w[3], w[4], w[5], w[6]});
+    else if (want_colors) carve(dev, {w[0], w[1], w[2], w[3], w[4], w[5], w[7]});
+    else carve(dev, {w[0], w[1], w[2], w[3], w[4], w[5]});
+    for (int i = 0; i < 8; i++) gp[i] = g[i].defined() ? ptr<float>(g[i]) : nullptr;
 }
 
 // What a backward reads of its forward, FwdInputs' counterpart: the saved inputs as contiguous fp32 tensors on the Gaussians' device,
@@ -532,10 +539,12 @@ PyForward forward(const Tensor& background, const Tensor& means3D, const Tensor&
 // [1,4,4], full [4,4]); the first eight are windows of one flat arena (grad_arena above), or undefined tensors (None) when
 // need_gaussian_grads is false (tracking: the library then skips every dense per-Gaussian row).  `images`: the variant's gradient
 // images as the caller holds them.  absgrad (dgr_*_backward_absgrad): a tenth result, the [P,3] absolute screen-space gradient.
-// R: the forward's num_rendered, or a lazy forward's capacity.
+// R: the forward's num_rendered, or a lazy forward's capacity.  want_colors / want_cov3D: false leaves dL_dcolors / dL_dcov3D out
+// (undefined, NULL to the library: grad_arena) -- the autograd nodes' rule for a caller without that leaf; the mirrors of the
+// reference binding below always return all eight.
 template <class V>
 std::vector<Tensor> backward(const BwdScene& s, const std::array<const Tensor*, V::N_IMAGES>& images, long R, BwdFlags flags,
-                             bool need_gaussian_grads, bool absgrad) {
+                             bool need_gaussian_grads, bool absgrad, bool want_colors = true, bool want_cov3D = true) {
     AbsGrad abs(absgrad, s.means3D, 0);
     const c10::Device dev = s.dev;
     const long H = images[V::GC]->size(1), W = images[V::GC]->size(2);
@@ -548,7 +557,7 @@ std::vector<Tensor> backward(const BwdScene& s, const std::array<const Tensor*, 
     Probe p_al(HP_BWD_ALLOC);
     std::vector<Tensor> g(9);
     float* gp[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (need_gaussian_grads) grad_arena(dev, s.P, s.M, g.data(), gp);
+    if (need_gaussian_grads) grad_arena(dev, s.P, s.M, g.data(), gp, want_colors, want_cov3D);
     // scratch: accumulator rows, cleared by the backward's first launch
     // (with the option "deterministic_grads" the scratch also holds 64 bytes per tile instance)
     const size_t nscr = up256(dgr_light_backward_scratch_bytes_r(s.P, (int)W, (int)H, (int)R));
@@ -733,7 +742,12 @@ struct Node : public torch::autograd::Function<Node<V>> {
         const BwdScene s(sv[S_BG], means3D, sv[S_RADII], sv[S_COLORS], sv[S_SCALES], sv[S_ROTATIONS], c.scale_modifier, sv[S_COV3D],
                          sv[S_VIEW], sv[S_PROJ], c.tanfovx, c.tanfovy, sv[S_GT], sv[S_SH], c.degree, sv[S_CAMPOS], sv[S_GEOM],
                          sv[S_BINNING], sv[S_IMG], sv[S_PERSPEC]);
-        std::vector<Tensor> g = ::backward<V>(s, images, c.R, {false, c.track_off, c.map_off}, needs_gaussian_grads(ctx), /*absgrad=*/false);
+        // (dL_dcolors / dL_dcov3D only for a colors_precomp / cov3Ds_precomp leaf: inputs 3 and 7.  Without one autograd would
+        //  drop the tensor, and the per-Gaussian backward would have written its 36 bytes per Gaussian for nobody.)
+        const bool want_colors = ctx->needs_input_grad(3) && sv[S_COLORS].numel() != 0;
+        const bool want_cov3D = ctx->needs_input_grad(7) && sv[S_COV3D].numel() != 0;
+        std::vector<Tensor> g = ::backward<V>(s, images, c.R, {false, c.track_off, c.map_off}, needs_gaussian_grads(ctx), /*absgrad=*/false,
+                                              want_colors, want_cov3D);
         consume_post_backward_wait(stream_of(dev));
         // (the reference sums light's [H*W,4,4] buffer over dim 0, L/__init__.py:160-161; here it is [1,4,4], already reduced)
         if (V::dview_leading_one) g[8] = view_of(g[8], 0, {4, 4}, at::kFloat);

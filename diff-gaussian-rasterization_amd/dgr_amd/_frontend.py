@@ -581,6 +581,14 @@ def _run_backward(ctx, variant, batch, grad_outputs, call):
     with _capi.under_options(ctx.dgr_options):  # (the autograd engine may run this on a thread of its own)
         # (means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp): tracking needs none
         out = call(saved, images, absgrad or any(ctx.needs_input_grad[:8]), silhouette)
+    if not batch:
+        # One view: dL_dcolors / dL_dcov3D are handed on only for a colors_precomp / cov3Ds_precomp leaf that needs a gradient
+        # (inputs 3 and 7), the compiled node's rule (csrc/torch_ext.cpp: Node::backward, which does not even have the library
+        # write them).  The `_C` mirrors of the reference binding keep returning all eight, and what this binding hands the C ABI
+        # is on record (tests/golden/frontend_calls.json): here the two are only not passed on to autograd, which dropped them anyway.
+        keep = {1: ctx.needs_input_grad[3] and saved[0] is not None and saved[0].numel() != 0,
+                4: ctx.needs_input_grad[7] and saved[4] is not None and saved[4].numel() != 0}
+        out = tuple(x if keep.get(i, True) else None for i, x in enumerate(out))
     (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations,
      grad_viewmatrix) = out[:9]
     _consume_post_backward_wait()  # (dgr_amd.multiview.ViewStreams.before_backward)
