@@ -1,5 +1,5 @@
 // api_steps.hip -- C-ABI entry points (include/dgr_hip.h) of the steps around the rasteriser (optimiser, map resize, pose, losses,
-// keyframe overlap).  Host code: each checks its arguments, leaves a refusal's text for dgr_last_error() and calls its launcher.
+// keyframe overlap, ICP).  Host code: each checks its arguments, leaves a refusal's text for dgr_last_error() and calls its launcher.
 #include <cmath>
 #include <string>
 
@@ -448,6 +448,66 @@ int dgr_keyframe_overlap(void* stream, int width, int height, const float* depth
     a.edge = p->edge, a.near_z = p->near_z, a.depth_tolerance = p->depth_tolerance;
     a.inside = inside, a.visible = visible, a.valid = valid, a.score = score, a.flags = flags;
     HIP_TRY(dgr::launch_keyframe_overlap(a, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_depth_normals(void* stream, int width, int height, const float* depth, const float* mask_image, float mask_threshold,
+                      float fx, float fy, float cx, float cy, float depth_min, float depth_max, float max_jump, float* vnmap) {
+    const char* bad = width < 1 || height < 1 ? "width and height must be positive" : nullptr;
+    if (!bad && (size_t)width * (size_t)height > (size_t)PLAN_MAX_ROWS) bad = "2^30 pixels or more";
+    if (!bad && !depth) bad = "depth is NULL";
+    if (!bad && (!vnmap || !dgr::aligned16(vnmap))) bad = "vnmap is NULL or not 16-byte aligned";
+    if (!bad && !(fx > 0.0f && fy > 0.0f && std::isfinite(fx) && std::isfinite(fy))) bad = "fx and fy must be finite and positive";
+    if (!bad && (std::isnan(cx) || std::isnan(cy))) bad = "cx or cy is NaN";
+    if (!bad && (std::isnan(depth_min) || std::isnan(depth_max))) bad = "depth_min or depth_max is NaN";
+    if (!bad && !(max_jump >= 0.0f)) bad = "max_jump is NaN or negative";
+    if (!bad && mask_image && std::isnan(mask_threshold)) bad = "mask_threshold is NaN";
+    if (bad) return refuse("dgr_depth_normals", bad);
+    dgr::DepthNormalsArgs a{};
+    a.W = width, a.H = height, a.depth = depth, a.mask = mask_image, a.mask_threshold = mask_threshold;
+    a.inv_fx = (float)(1.0 / (double)fx), a.inv_fy = (float)(1.0 / (double)fy), a.cx = cx, a.cy = cy;
+    a.depth_min = depth_min, a.depth_max = depth_max, a.max_jump = max_jump, a.vnmap = reinterpret_cast<float4*>(vnmap);
+    HIP_TRY(dgr::launch_depth_normals(a, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+size_t dgr_icp_scratch_bytes(int width, int height, int stride) {
+    return seed_shape_error(width, height, stride) ? 0 : dgr::icp_scratch_bytes(width, height, stride);
+}
+int dgr_icp_step(void* stream, int width, int height, const float* depth_obs, const float* vn_obs, const float* vn_model,
+                 const float* model_viewmatrix, const float* viewmatrix_in, const dgr_icp_params* params, void* scratch,
+                 float* viewmatrix_out, float* quat_out, float* trans_out, double* stats, unsigned char* flags) {
+    const dgr_icp_params* p = params;
+    const char* bad = !p ? "params is NULL" : seed_shape_error(width, height, p->stride);
+    if (!bad && !depth_obs) bad = "depth_obs is NULL";
+    if (!bad && vn_obs && !dgr::aligned16(vn_obs)) bad = "vn_obs is not 16-byte aligned";
+    if (!bad && (!vn_model || !dgr::aligned16(vn_model))) bad = "vn_model is NULL or not 16-byte aligned";
+    if (!bad && !model_viewmatrix) bad = "model_viewmatrix is NULL";
+    if (!bad && !viewmatrix_in) bad = "viewmatrix_in is NULL";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && !viewmatrix_out) bad = "viewmatrix_out is NULL";
+    if (!bad && (!stats || (reinterpret_cast<uintptr_t>(stats) & 7u))) bad = "stats is NULL or not 8-byte aligned";
+    if (!bad && !(p->fx > 0.0f && p->fy > 0.0f && std::isfinite(p->fx) && std::isfinite(p->fy)))
+        bad = "fx and fy must be finite and positive";
+    if (!bad && (std::isnan(p->cx) || std::isnan(p->cy))) bad = "cx or cy is NaN";
+    if (!bad && (std::isnan(p->depth_min) || std::isnan(p->depth_max))) bad = "depth_min or depth_max is NaN";
+    if (!bad && !(p->dist_max >= 0.0f)) bad = "dist_max is NaN or negative";
+    if (!bad && !(p->normal_cos_min >= -1.0f && p->normal_cos_min <= 1.0f)) bad = "normal_cos_min must lie in [-1, 1]";
+    if (!bad && !(p->huber_delta >= 0.0f)) bad = "huber_delta is NaN or negative";
+    if (!bad && !(p->damping >= 0.0f)) bad = "damping is NaN or negative";
+    if (!bad && !(p->rcond >= 0.0f)) bad = "rcond is NaN or negative";
+    if (!bad && p->min_points < 1) bad = "min_points must be at least 1";
+    if (bad) return refuse("dgr_icp_step", bad);
+    dgr::IcpStepArgs a{};
+    a.W = width, a.H = height, a.stride = p->stride, a.depth_obs = depth_obs;
+    a.vn_obs = reinterpret_cast<const float4*>(vn_obs), a.vn_model = reinterpret_cast<const float4*>(vn_model);
+    a.model_viewmatrix = model_viewmatrix, a.viewmatrix_in = viewmatrix_in;
+    a.fx = p->fx, a.fy = p->fy, a.inv_fx = (float)(1.0 / (double)p->fx), a.inv_fy = (float)(1.0 / (double)p->fy);
+    a.cx = p->cx, a.cy = p->cy, a.depth_min = p->depth_min, a.depth_max = p->depth_max, a.dist_max = p->dist_max;
+    a.normal_cos_min = p->normal_cos_min, a.huber_delta = p->huber_delta, a.damping = (double)p->damping, a.rcond = (double)p->rcond;
+    a.min_points = p->min_points;
+    a.viewmatrix_out = viewmatrix_out, a.quat_out = quat_out, a.trans_out = trans_out, a.stats = stats, a.flags = flags;
+    HIP_TRY(dgr::launch_icp_step(a, scratch, (hipStream_t)stream));
     return DGR_OK;
 }
 

@@ -1,0 +1,403 @@
+// icp.hip -- frame-to-model ICP pose alignment (include/dgr_hip.h: dgr_depth_normals, dgr_icp_step): the geometric pose
+// initialisation in front of the photometric tracker.  KinectFusion's projective point-to-plane ICP of the sensor depth against the
+// model's rendered depth.
+//
+// normals: one thread per pixel: the packed vertex-normal map (nx, ny, nz, d) from a depth image by central differences of the
+//          unprojected neighbours.  One 16-byte store per pixel, so that the step's gather is one 16-byte load from one line.
+// step   : one Gauss-Newton iteration in ONE launch.  One workgroup per block of 2048 candidates (the stride grid of
+//          candidate_grid.h), as overlap_count_kernel: threads 0..11 form rel = T_model T_in^-1 in double and round it once, every
+//          thread takes a candidate per trip and adds its 29 terms (A's upper triangle, b, sum w r^2, count) to its own double
+//          accumulators; block_sums; the block's partial goes to its own row of the scratch and the block takes a ticket
+//          (pose_reduce.h's deterministic form).  The block that draws the last ticket adds the rows in block order, solves the
+//          6 x 6 system by LDL^T in double, forms the new pose and leaves the ticket at zero: a recorded graph replays it.
+// No host read, no float atomics, the same bits on every run.
+#include <hip/hip_runtime.h>
+
+#include "block_sum.h"
+#include "candidate_grid.h"
+#include "kernels.h"
+
+namespace dgr {
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int BLOCK_CANDIDATES = 2048;  // eight trips of a workgroup
+constexpr int SUMS = 29;                // A (21), b (6), sum w r^2, count
+constexpr int ROW = 32;                 // doubles per block in the scratch: a 256-byte row
+constexpr int CHUNK = 64;               // rows the finisher stages in LDS per trip
+constexpr size_t HEADER_BYTES = 256;    // the ticket (a uint32 at byte 0; zero between calls)
+constexpr unsigned ICP_VALID = 1u, ICP_INSIDE = 2u, ICP_ASSOCIATED = 4u;
+// A diagonal entry below this share of the largest is damped as if it were that large: a direction the data does not constrain
+// at all (an exactly zero row of A: the fronto-parallel plane) then has a positive pivot under damping > 0 and does not move.
+constexpr double DAMPING_FLOOR = 1e-3;
+
+__host__ __device__ inline unsigned icp_blocks(size_t candidates) {
+    return (unsigned)((candidates + BLOCK_CANDIDATES - 1) / BLOCK_CANDIDATES);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- normals
+__global__ void __launch_bounds__(THREADS) depth_normals_kernel(DepthNormalsArgs a) {
+    const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t n = (size_t)a.W * (size_t)a.H;
+    if (i >= n) return;
+    const unsigned y = (unsigned)(i / (unsigned)a.W), x = (unsigned)(i - (size_t)y * (unsigned)a.W);
+    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (x >= 1 && y >= 1 && x + 1 < (unsigned)a.W && y + 1 < (unsigned)a.H) {
+        const float d = a.depth[i], dl = a.depth[i - 1], dr = a.depth[i + 1], du = a.depth[i - a.W], dd = a.depth[i + a.W];
+        const float lo = a.depth_min, hi = a.depth_max;
+        bool ok = d > lo && d < hi && dl > lo && dl < hi && dr > lo && dr < hi && du > lo && du < hi && dd > lo && dd < hi;
+        if (a.mask) ok = ok && a.mask[i] > a.mask_threshold;
+        if (ok) {  // (false on a NaN, as every test here)
+            const float jump = a.max_jump * d;
+            ok = fabsf(dl - d) <= jump && fabsf(dr - d) <= jump && fabsf(du - d) <= jump && fabsf(dd - d) <= jump;
+        }
+        if (ok) {
+            const float fx_ = (float)x, fy_ = (float)y;
+            const float X = (fx_ - a.cx) * a.inv_fx, Y = (fy_ - a.cy) * a.inv_fy;  // the centre's ray
+            const float Xl = ((fx_ - 1.f) - a.cx) * a.inv_fx, Xr = ((fx_ + 1.f) - a.cx) * a.inv_fx;
+            const float Yu = ((fy_ - 1.f) - a.cy) * a.inv_fy, Yd = ((fy_ + 1.f) - a.cy) * a.inv_fy;
+            // a = V(x + 1, y) - V(x - 1, y), b = V(x, y + 1) - V(x, y - 1)
+            const float a0 = Xr * dr - Xl * dl, a1 = Y * dr - Y * dl, a2 = dr - dl;
+            const float b0 = X * dd - X * du, b1 = Yd * dd - Yu * du, b2 = dd - du;
+            float c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
+            const float len2 = c0 * c0 + c1 * c1 + c2 * c2;
+            if (len2 > 0.f && len2 < INFINITY) {
+                const float len = sqrtf(len2);
+                c0 /= len, c1 /= len, c2 /= len;
+                if (c0 * (X * d) + c1 * (Y * d) + c2 * d > 0.f) c0 = -c0, c1 = -c1, c2 = -c2;  // facing the camera
+                out = make_float4(c0, c1, c2, d);
+            }
+        }
+    }
+    a.vnmap[i] = out;
+}
+
+// -------------------------------------------------------------------------------------------------------------------- step
+// (r, x, y, z) of a rotation matrix, unit, r >= 0 (Shepperd's branches); R = (r^2 - |v|^2) I + 2 v v^T + 2 r [v]x, pose.hip's
+__device__ void rotation_to_quat(const double (&R)[3][3], double (&q)[4]) {
+    const double tr = R[0][0] + R[1][1] + R[2][2];
+    if (tr > 0.0) {
+        const double s = 2.0 * sqrt(tr + 1.0);
+        q[0] = 0.25 * s, q[1] = (R[2][1] - R[1][2]) / s, q[2] = (R[0][2] - R[2][0]) / s, q[3] = (R[1][0] - R[0][1]) / s;
+    } else if (R[0][0] > R[1][1] && R[0][0] > R[2][2]) {
+        const double s = 2.0 * sqrt(1.0 + R[0][0] - R[1][1] - R[2][2]);
+        q[0] = (R[2][1] - R[1][2]) / s, q[1] = 0.25 * s, q[2] = (R[0][1] + R[1][0]) / s, q[3] = (R[0][2] + R[2][0]) / s;
+    } else if (R[1][1] > R[2][2]) {
+        const double s = 2.0 * sqrt(1.0 + R[1][1] - R[0][0] - R[2][2]);
+        q[0] = (R[0][2] - R[2][0]) / s, q[1] = (R[0][1] + R[1][0]) / s, q[2] = 0.25 * s, q[3] = (R[1][2] + R[2][1]) / s;
+    } else {
+        const double s = 2.0 * sqrt(1.0 + R[2][2] - R[0][0] - R[1][1]);
+        q[0] = (R[1][0] - R[0][1]) / s, q[1] = (R[0][2] + R[2][0]) / s, q[2] = (R[1][2] + R[2][1]) / s, q[3] = 0.25 * s;
+    }
+    const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double sgn = q[0] < 0.0 ? -inv : inv;
+#pragma unroll
+    for (int i = 0; i < 4; i++) q[i] *= sgn;
+}
+__device__ void quat_to_rotation(const double (&q)[4], double (&R)[3][3]) {
+    const double r = q[0], x = q[1], y = q[2], z = q[3];
+    const double d = r * r - (x * x + y * y + z * z);
+    R[0][0] = d + 2.0 * x * x, R[0][1] = 2.0 * x * y - 2.0 * r * z, R[0][2] = 2.0 * x * z + 2.0 * r * y;
+    R[1][0] = 2.0 * x * y + 2.0 * r * z, R[1][1] = d + 2.0 * y * y, R[1][2] = 2.0 * y * z - 2.0 * r * x;
+    R[2][0] = 2.0 * x * z - 2.0 * r * y, R[2][1] = 2.0 * y * z + 2.0 * r * x, R[2][2] = d + 2.0 * z * z;
+}
+// (R, t) of 16 floats holding W2C^T: R[j][i] at [4 i + j], t[j] at [12 + j]
+__device__ void pose_of(const float* v, double (&R)[3][3], double (&t)[3]) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) R[j][i] = (double)v[4 * i + j];
+        t[j] = (double)v[12 + j];
+    }
+}
+// (Ra, ta) (Rb, tb) = (Ra Rb, Ra tb + ta)
+__device__ void compose(const double (&Ra)[3][3], const double (&ta)[3], const double (&Rb)[3][3], const double (&tb)[3],
+                        double (&R)[3][3], double (&t)[3]) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) R[i][j] = Ra[i][0] * Rb[0][j] + Ra[i][1] * Rb[1][j] + Ra[i][2] * Rb[2][j];
+        t[i] = Ra[i][0] * tb[0] + Ra[i][1] * tb[1] + Ra[i][2] * tb[2] + ta[i];
+    }
+}
+// exp of the twist (w, v): R = I + A [w]x + B [w]x^2, t = (I + B [w]x + C [w]x^2) v, A = sin th / th, B = (1 - cos th) / th^2,
+// C = (th - sin th) / th^3, their series below th^2 = 1e-6
+__device__ void se3_exp(const double (&w)[3], const double (&v)[3], double (&R)[3][3], double (&t)[3]) {
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    double A, B, C;
+    if (th2 < 1e-6) {
+        A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0);
+        B = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0);
+        C = 1.0 / 6.0 - th2 / 120.0 * (1.0 - th2 / 42.0);
+    } else {
+        const double th = sqrt(th2), s = sin(th), h = sin(0.5 * th);
+        A = s / th, B = 2.0 * h * h / th2, C = (th - s) / (th2 * th);
+    }
+    const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        double ti = 0.0;
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const double K2 = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
+            const double I = i == j ? 1.0 : 0.0;
+            R[i][j] = I + A * K[i][j] + B * K2;
+            ti += (I + B * K[i][j] + C * K2) * v[j];
+        }
+        t[i] = ti;
+    }
+}
+
+// One thread: the totals -> stats, the solve, the update, the pose outputs.
+__device__ void icp_finish(const IcpStepArgs& a, const double* tot) {
+    double M[6][6], b[6];
+    {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = i; j < 6; j++) M[i][j] = M[j][i] = tot[k++];
+#pragma unroll
+        for (int i = 0; i < 6; i++) b[i] = tot[21 + i];
+    }
+    bool ok = tot[28] >= (double)a.min_points;
+#pragma unroll
+    for (int i = 0; i < 28; i++) ok = ok && isfinite(tot[i]);
+    double max_diag = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) max_diag = fmax(max_diag, M[i][i]);
+#pragma unroll
+    for (int i = 0; i < 6; i++) M[i][i] += a.damping * fmax(M[i][i], DAMPING_FLOOR * max_diag);
+    // M = L D L^T, L unit lower triangular (kept in M's lower triangle), no pivoting: M is symmetric positive semi-definite
+    const double pivot_min = a.rcond * max_diag;
+    double D[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double dj = M[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) dj -= M[j][k] * M[j][k] * D[k];
+        ok = ok && dj > pivot_min && dj > 0.0;  // (false on a NaN)
+        D[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double l = M[i][j];
+#pragma unroll
+            for (int k = 0; k < j; k++) l -= M[i][k] * M[j][k] * D[k];
+            M[i][j] = l / dj;
+        }
+    }
+    double xi[6];
+#pragma unroll
+    for (int i = 0; i < 6; i++) {  // L z = -b
+        double z = -b[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) z -= M[i][k] * xi[k];
+        xi[i] = z;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) xi[i] /= D[i];
+#pragma unroll
+    for (int i = 5; i >= 0; i--) {  // L^T xi = y
+        double z = xi[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; k++) z -= M[k][i] * xi[k];
+        xi[i] = z;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) ok = ok && isfinite(xi[i]);
+
+    double Ri[3][3], ti[3];
+    pose_of(a.viewmatrix_in, Ri, ti);  // (read before anything is written: viewmatrix_out may be viewmatrix_in)
+    uint32_t in_bits[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) in_bits[i] = reinterpret_cast<const uint32_t*>(a.viewmatrix_in)[i];
+    double q[4], Ro[3][3], to[3];
+    if (ok) {
+        // T_out = T_in T_model^-1 exp(-xi) T_model
+        double Rm[3][3], tm[3], Re[3][3], te[3], R1[3][3], t1[3], R2[3][3], t2[3];
+        pose_of(a.model_viewmatrix, Rm, tm);
+        const double w[3] = {-xi[0], -xi[1], -xi[2]}, v[3] = {-xi[3], -xi[4], -xi[5]};
+        se3_exp(w, v, Re, te);
+        compose(Re, te, Rm, tm, R1, t1);
+        double Rmt[3][3], tmi[3];
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) Rmt[i][j] = Rm[j][i];
+            tmi[i] = -(Rm[0][i] * tm[0] + Rm[1][i] * tm[1] + Rm[2][i] * tm[2]);
+        }
+        compose(Rmt, tmi, R1, t1, R2, t2);
+        compose(Ri, ti, R2, t2, Ro, to);
+        rotation_to_quat(Ro, q);  // the rotation re-orthonormalised: through its unit quaternion
+        quat_to_rotation(q, Ro);
+#pragma unroll
+        for (int i = 0; i < 4; i++) ok = ok && isfinite(q[i]);
+#pragma unroll
+        for (int i = 0; i < 3; i++) ok = ok && isfinite(to[i]);
+    }
+    if (!ok) rotation_to_quat(Ri, q);
+    float* out = a.viewmatrix_out;
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) out[4 * i + j] = (float)Ro[j][i];
+            out[4 * i + 3] = 0.f;
+            out[12 + i] = (float)to[i];
+        }
+        out[15] = 1.f;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 16; i++) reinterpret_cast<uint32_t*>(out)[i] = in_bits[i];
+    }
+    if (a.quat_out)
+#pragma unroll
+        for (int i = 0; i < 4; i++) a.quat_out[i] = (float)q[i];
+    if (a.trans_out)
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            if (ok) a.trans_out[i] = (float)to[i];
+            else reinterpret_cast<uint32_t*>(a.trans_out)[i] = in_bits[12 + i];
+        }
+#pragma unroll
+    for (int i = 0; i < SUMS; i++) a.stats[i] = tot[i];
+    a.stats[29] = ok ? 1.0 : 0.0;
+    a.stats[30] = ok ? sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) : 0.0;
+    a.stats[31] = ok ? sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]) : 0.0;
+}
+
+// grid: one workgroup per block of candidates.  `ticket`: zero on entry, left at zero; `part`: a row of ROW doubles per workgroup
+__global__ void __launch_bounds__(THREADS) icp_step_kernel(IcpStepArgs a, uint32_t* __restrict__ ticket, double* __restrict__ part) {
+    __shared__ float rel[12];  // current camera point p -> model camera point: q_j = rel[3 j] p_0 + rel[3 j + 1] p_1 + rel[3 j + 2] p_2 + rel[9 + j]
+    __shared__ int last;
+    __shared__ double rows[CHUNK * ROW];
+    __shared__ double totals[ROW];
+    if (threadIdx.x < 12) {
+        // both matrices hold W2C^T: W2C's rotation entry R[j][i] at [4 i + j], its translation t[j] at [12 + j].
+        // q = R_m R_in^T (p - t_in) + t_m
+        const float* __restrict__ vc = a.viewmatrix_in;
+        const float* __restrict__ vk = a.model_viewmatrix;
+        const int j = threadIdx.x < 9 ? threadIdx.x / 3 : threadIdx.x - 9;
+        double r[3];
+#pragma unroll
+        for (int m = 0; m < 3; ++m)
+            r[m] = (double)vk[j] * (double)vc[m] + (double)vk[4 + j] * (double)vc[4 + m] + (double)vk[8 + j] * (double)vc[8 + m];
+        const int m = threadIdx.x - 3 * j;
+        if (threadIdx.x < 9) rel[threadIdx.x] = (float)(m == 0 ? r[0] : m == 1 ? r[1] : r[2]);
+        else rel[threadIdx.x] = (float)((double)vk[12 + j] - (r[0] * (double)vc[12] + r[1] * (double)vc[13] + r[2] * (double)vc[14]));
+    }
+    __syncthreads();
+    const float r00 = rel[0], r01 = rel[1], r02 = rel[2], r10 = rel[3], r11 = rel[4], r12 = rel[5], r20 = rel[6], r21 = rel[7],
+                r22 = rel[8], t0 = rel[9], t1 = rel[10], t2 = rel[11];
+    const float Wf = (float)a.W, Hf = (float)a.H;
+    const size_t begin = (size_t)blockIdx.x * BLOCK_CANDIDATES;
+    const size_t end = begin + BLOCK_CANDIDATES < a.candidates ? begin + BLOCK_CANDIDATES : a.candidates;
+    double acc[SUMS];
+#pragma unroll
+    for (int i = 0; i < SUMS; i++) acc[i] = 0.0;
+    for (size_t c = begin + threadIdx.x; c < end; c += THREADS) {  // this thread's candidates, ascending
+        unsigned x, y;
+        candidate_pixel(c, a.wc, a.stride, x, y);
+        const size_t pix = (size_t)y * (unsigned)a.W + x;
+        const float d = a.depth_obs[pix];
+        bool valid = d > a.depth_min && d < a.depth_max;  // (false on a NaN)
+        float4 no = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.vn_obs) {
+            no = a.vn_obs[pix];
+            valid = valid && no.w > 0.f;
+        }
+        bool inside = false, associated = false;
+        if (valid) {
+            const float p0 = ((float)x - a.cx) * a.inv_fx * d, p1 = ((float)y - a.cy) * a.inv_fy * d;
+            const float q0 = r00 * p0 + r01 * p1 + r02 * d + t0;
+            const float q1 = r10 * p0 + r11 * p1 + r12 * d + t1;
+            const float q2 = r20 * p0 + r21 * p1 + r22 * d + t2;
+            const float uf = floorf(a.fx * q0 / q2 + a.cx + 0.5f), vf = floorf(a.fy * q1 / q2 + a.cy + 0.5f);
+            if (q2 > 0.f && uf >= 0.f && uf < Wf && vf >= 0.f && vf < Hf) {  // (false on a NaN: the casts below are in range)
+                const float4 m = a.vn_model[(size_t)(unsigned)(int)vf * (unsigned)a.W + (unsigned)(int)uf];
+                if (m.w > 0.f) {
+                    inside = true;
+                    const float e0 = q0 - (uf - a.cx) * a.inv_fx * m.w, e1 = q1 - (vf - a.cy) * a.inv_fy * m.w, e2 = q2 - m.w;
+                    associated = sqrtf(e0 * e0 + e1 * e1 + e2 * e2) <= a.dist_max;
+                    if (a.vn_obs) {
+                        const float n0 = r00 * no.x + r01 * no.y + r02 * no.z, n1 = r10 * no.x + r11 * no.y + r12 * no.z,
+                                    n2 = r20 * no.x + r21 * no.y + r22 * no.z;
+                        associated = associated && n0 * m.x + n1 * m.y + n2 * m.z >= a.normal_cos_min;
+                    }
+                    if (associated) {
+                        const float r = m.x * e0 + m.y * e1 + m.z * e2;
+                        const float J[6] = {q1 * m.z - q2 * m.y, q2 * m.x - q0 * m.z, q0 * m.y - q1 * m.x, m.x, m.y, m.z};
+                        const float ar = fabsf(r);
+                        const float w = ar <= a.huber_delta ? 1.f : a.huber_delta / ar;
+                        int k = 0;
+#pragma unroll
+                        for (int i = 0; i < 6; i++) {
+                            const float wj = w * J[i];
+#pragma unroll
+                            for (int j = i; j < 6; j++) acc[k++] += (double)(wj * J[j]);
+                            acc[21 + i] += (double)(wj * r);
+                        }
+                        acc[27] += (double)((w * r) * r);
+                        acc[28] += 1.0;
+                    }
+                }
+            }
+        }
+        if (a.flags)
+            a.flags[c] = (unsigned char)((valid ? ICP_VALID : 0u) | (inside ? ICP_INSIDE : 0u) | (associated ? ICP_ASSOCIATED : 0u));
+    }
+    block_sums(acc);
+    if (threadIdx.x == 0) {
+        double* row = part + (size_t)blockIdx.x * ROW;
+#pragma unroll
+        for (int i = 0; i < SUMS; i++) __hip_atomic_store(row + i, acc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores are acknowledged before the ticket is taken
+        const uint32_t t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = t == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    // the last block: every row is delivered.  Rows staged in LDS CHUNK at a time (all loads of a chunk in flight together), then
+    // thread s < 29 adds sum s over the rows in block order.
+    double tot = 0.0;
+    for (unsigned base = 0; base < gridDim.x; base += CHUNK) {
+        const unsigned n = gridDim.x - base < CHUNK ? gridDim.x - base : CHUNK;
+        for (unsigned i = threadIdx.x; i < n * ROW; i += THREADS)
+            if ((i & (ROW - 1)) < SUMS)
+                rows[i] = __hip_atomic_load(part + (size_t)base * ROW + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (threadIdx.x < SUMS)
+            for (unsigned r = 0; r < n; r++) tot += rows[r * ROW + threadIdx.x];
+        __syncthreads();
+    }
+    if (threadIdx.x < SUMS) totals[threadIdx.x] = tot;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        icp_finish(a, totals);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_depth_normals(const DepthNormalsArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.W * (size_t)a.H;
+    launch(depth_normals_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), stream, a);
+    return hipGetLastError();
+}
+
+size_t icp_scratch_bytes(int W, int H, int stride) {
+    return HEADER_BYTES + (size_t)icp_blocks(seed_candidates(W, H, stride)) * ROW * sizeof(double);
+}
+
+hipError_t launch_icp_step(const IcpStepArgs& args, void* scratch, hipStream_t stream) {
+    IcpStepArgs a = args;
+    const CandidateGrid g = candidate_grid(a.W, a.H, a.stride);
+    a.candidates = g.candidates();
+    a.wc = g.wc;
+    launch(icp_step_kernel, dim3(icp_blocks(a.candidates)), dim3(THREADS), stream, a, static_cast<uint32_t*>(scratch),
+           reinterpret_cast<double*>(static_cast<char*>(scratch) + HEADER_BYTES));
+    return hipGetLastError();
+}
+
+}  // namespace dgr

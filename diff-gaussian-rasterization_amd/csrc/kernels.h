@@ -362,6 +362,32 @@ struct KeyframeOverlapArgs {
 };
 size_t keyframe_overlap_scratch_bytes(int W, int H, int stride, int K);
 hipError_t launch_keyframe_overlap(const KeyframeOverlapArgs& args, void* scratch, hipStream_t stream);
+// frame-to-model ICP (icp.hip; include/dgr_hip.h: dgr_depth_normals, dgr_icp_step): the packed vertex-normal map of a depth image
+// (one launch) and one Gauss-Newton iteration of projective point-to-plane ICP over the candidate grid (one launch; `scratch`:
+// icp_scratch_bytes() bytes whose first word is zero between calls)
+struct DepthNormalsArgs {
+    int W, H;
+    const float *depth, *mask;  // mask: NULL = no mask image
+    float mask_threshold, inv_fx, inv_fy, cx, cy, depth_min, depth_max, max_jump;
+    float4* vnmap;
+};
+hipError_t launch_depth_normals(const DepthNormalsArgs& a, hipStream_t stream);
+struct IcpStepArgs {
+    int W, H, stride;
+    const float* depth_obs;
+    const float4 *vn_obs, *vn_model;  // vn_obs: NULL = no normal-compatibility test
+    const float *model_viewmatrix, *viewmatrix_in;
+    float fx, fy, inv_fx, inv_fy, cx, cy, depth_min, depth_max, dist_max, normal_cos_min, huber_delta;
+    double damping, rcond;
+    int min_points;
+    float *viewmatrix_out, *quat_out, *trans_out;  // quat_out, trans_out: NULL = not stored
+    double* stats;
+    unsigned char* flags;  // NULL: not stored
+    size_t candidates;     // filled in by the launcher, as wc (candidates per grid row)
+    int wc;
+};
+size_t icp_scratch_bytes(int W, int H, int stride);
+hipError_t launch_icp_step(const IcpStepArgs& args, void* scratch, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -97,6 +97,14 @@ class KeyframeOverlapParams(C.Structure):  # dgr_keyframe_overlap_params
 
 assert C.sizeof(KeyframeOverlapParams) == 40  # ten four-byte fields: the C layout
 
+
+class IcpParams(C.Structure):  # dgr_icp_params
+    _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("depth_min", _f), ("depth_max", _f), ("dist_max", _f),
+                ("normal_cos_min", _f), ("huber_delta", _f), ("damping", _f), ("rcond", _f), ("min_points", _i), ("stride", _i)]
+
+
+assert C.sizeof(IcpParams) == 52  # thirteen four-byte fields: the C layout
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -142,6 +150,9 @@ _SIGS = {
     "dgr_keyframe_overlap_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "dgr_keyframe_overlap": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.POINTER(KeyframeOverlapParams), _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "dgr_depth_normals": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
+    "dgr_icp_scratch_bytes": (_sz, [_i, _i, _i]),
+    "dgr_icp_step": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(IcpParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

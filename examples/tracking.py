@@ -16,7 +16,14 @@ and gross outliers (2 % of the pixels, metres off).  The pose is then tracked tw
 with the masked loss (slam.masked_l1_loss: valid sensor depth, silhouette above 0.99, depth error at most 10 x the frame's median
 error -- the median found on the device, so the iteration still records into a hipGraph), and both final pose errors are printed.
 
-  python examples/tracking.py [--graph] [--fused] [--masked] [--complete-pose] [--trace K] [--iters 150]
+With --icp N the pose is first aligned geometrically (slam.icp_align: frame-to-model point-to-plane ICP): the model's depth is
+rendered at the perturbed start pose, N Gauss-Newton iterations align the observed depth to it on the device, and the resulting
+(quaternion, translation) replace the start pose of the Adam loop, device to device.  The pose error is printed at the start,
+after ICP and at the end, with the time per ICP iteration.  --reach ROT TRANS additionally prints the first Adam iteration at which the
+rotation error is at most ROT and the translation error at most TRANS (read once per iteration: the timing then includes those reads).
+
+  python examples/tracking.py [--graph] [--fused] [--masked] [--complete-pose] [--icp N] [--reach ROT TRANS] [--trace K]
+                              [--iters 150]
                               [--width 640 --height 480 --gaussians 100000]
 """
 import argparse
@@ -45,6 +52,10 @@ def main():
     ap.add_argument("--gaussians", type=int, default=100000)
     ap.add_argument("--complete-pose", action="store_true", help="the complete pose gradient (library option pose_grad = 1)")
     ap.add_argument("--trace", type=int, default=0, help="print the pose error every K iterations")
+    ap.add_argument("--icp", type=int, default=0,
+                    help="N iterations of frame-to-model ICP (slam.icp_align) on the depth images before the Adam loop")
+    ap.add_argument("--reach", type=float, nargs=2, default=None, metavar=("ROT", "TRANS"),
+                    help="print the first Adam iteration at which the pose errors are at most ROT and TRANS")
     args = ap.parse_args()
     if args.graph or args.fused:
         # a blocking status read cannot be captured, and a tracking loop has no use for num_rendered on the host: no host wait
@@ -121,6 +132,29 @@ def main():
         if args.masked:
             print("masked loss (slam.masked_l1_loss):" if masked else "plain L1 loss on the same frame:")
         print(f"start : rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}")
+        if args.icp > 0:
+            # the model's depth at the start pose, then N ICP iterations of the observed depth against it; the pose the Adam
+            # loop starts from is copied into the leaves on the device
+            fx, fy, cx, cy = W / (2.0 * tanfovx), H / (2.0 * tanfovy), (W - 1) / 2.0, (H - 1) / 2.0
+            with torch.no_grad():
+                cam = pose(q, t)
+                model = render(cam)
+                view0 = cam[0].detach().clone()
+
+                def align():
+                    return slam.icp_align(obs_d, model["depth"], None, view0, fx, fy, cx, cy, iterations=args.icp,
+                                          opacity_map=model["opacity_map"], depth_range=(1e-3, float("inf")))
+                align()  # (kernel loading is not timed)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                aligned = align()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                q.copy_(aligned.quat)
+                t.copy_(aligned.trans)
+            ok = int(aligned.stats[:, 29].sum())
+            print(f"icp   : rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}, {ok} of {args.icp} steps accepted, "
+                  f"{int(aligned.stats[-1, 28])} pairs, {dt / args.icp * 1e6:.1f} us per ICP iteration (eager, normals included)")
         if args.graph:
             step = CapturedStep(iteration, warmup=3)  # (three eager iterations first)
             run = step.replay
@@ -130,8 +164,11 @@ def main():
             run = iteration
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        reached = None
         for i in range(args.iters):
             loss = run()
+            if args.reach and reached is None and err()[0] <= args.reach[0] and err()[1] <= args.reach[1]:
+                reached = i + 1
             if args.trace and (i + 1) % args.trace == 0:
                 e = err()
                 print(f"  iteration {i + 1}: rotation error {e[0]:.2e}, translation error {e[1]:.2e}")
@@ -140,6 +177,9 @@ def main():
         if args.graph:
             step.check()
         print(f"finish: rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}, loss {float(loss):.3e}")
+        if args.reach:
+            print(f"reach : rotation error {args.reach[0]:.2e} and translation error {args.reach[1]:.2e} "
+                  f"{'after ' + str(reached) + ' iterations' if reached else 'not within ' + str(args.iters) + ' iterations'}")
         print(f"{args.iters} iterations in {dt * 1e3:.1f} ms = {dt / args.iters * 1e3:.3f} ms per tracking iteration"
               f" ({'hipGraph replay' if args.graph else 'eager'}{', fused pose and loss' if args.fused else ''}"
               f"{', masked loss' if masked else ''}{', complete pose gradient' if args.complete_pose else ''})")

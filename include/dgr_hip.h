@@ -617,6 +617,73 @@ int dgr_keyframe_overlap(void* stream, int width, int height, const float* depth
                          const dgr_keyframe_overlap_params* params, void* scratch, int* inside, int* visible, int* valid,
                          float* score, unsigned char* flags /* or NULL */);
 
+/* ---- frame-to-model ICP pose alignment: the geometric pose initialisation in front of the photometric tracker (csrc/icp.hip) ----
+ * KinectFusion's projective point-to-plane ICP of the sensor depth against the model's rendered depth, as RTG-SLAM and GS-ICP SLAM
+ * run it on a Gaussian map.  Conventions are dgr_keyframe_overlap's and dgr_seed_plan's: float32 images on the device, pixel
+ * (x, y) at depth d is the camera point V = ((x - cx) / fx * d, (y - cy) / fy * d, d), poses are 16 floats holding W2C^T taken as
+ * rigid, raw fp32 comparisons that are false on a NaN, the stride grid as candidates.  No host read, no float atomics, the same
+ * bits on every run, capturable into a hipGraph.
+ *
+ * dgr_depth_normals: depth [height, width] (and mask_image [height, width] or NULL) -> vnmap [height, width, 4] = (nx, ny, nz, d),
+ * packed so that the step's gather is one 16-byte load; one launch.  A pixel is usable when it and its four neighbours x +- 1,
+ * y +- 1 lie inside the image with depth_min < d && d < depth_max; with a mask, its own mask_image > mask_threshold; each
+ * neighbour's depth satisfies fabsf(d_n - d) <= max_jump * d; and the cross product below is non-zero (and finite).  Its normal is
+ * n = normalize((V(x+1, y) - V(x-1, y)) x (V(x, y+1) - V(x, y-1))), flipped so that n . V <= 0 (facing the camera), and d its own
+ * depth's bits.  Every other pixel (the border among them) gets four zeros.
+ * Argument errors: non-positive width or height, 2^30 pixels or more; a NULL depth; a NULL or misaligned vnmap (16 bytes); fx or
+ * fy not finite and positive; a NaN cx, cy, depth_min, depth_max (or mask_threshold with a mask); max_jump NaN or negative.
+ *
+ * dgr_icp_step: one Gauss-Newton iteration, ONE launch.  Inputs: depth_obs [height, width]; vn_obs, the observation's map, or
+ * NULL (used only by the normal-compatibility test); vn_model, the map of the model depth rendered at model_viewmatrix;
+ * viewmatrix_in, the current estimate.  Per candidate pixel (x, y) of depth_obs, in fp32 (fused multiply-adds allowed):
+ *   valid      = depth_min < d && d < depth_max, and with vn_obs its d > 0
+ *   q          = R_rel p + t_rel, p the candidate's camera point, rel = T_model T_in^-1 formed by the kernel from the two matrices
+ *                in double and rounded once (no inverse is formed on the host)
+ *   pixel      = (floor(u + 0.5), floor(v + 0.5)), u = fx * q.x / q.z + cx, v = fy * q.y / q.z + cy
+ *   inside     = valid && q.z > 0 && the pixel lies in the image && the model's d_m > 0 there
+ *   e          = q - v_m, v_m the camera point of that pixel at d_m; n_m the model's normal there
+ *   associated = inside && |e| <= dist_max && (no vn_obs || (R_rel n_obs) . n_m >= normal_cos_min)
+ *   r = n_m . e;  J = (q x n_m, n_m), the rotation part first;  w = 1 for |r| <= huber_delta, else huber_delta / |r|
+ *                (huber_delta = INFINITY: no robust weight)
+ * Sums over the associated candidates, accumulated in double from the first addition in a fixed order (a thread's candidates
+ * ascending, the workgroup's threads by the block sum, the workgroups of 2048 candidates in block order): the 21 upper-triangle
+ * entries of A = sum w J J^T (row-major), the 6 of b = sum w J r, sum w r^2, the count.
+ * Solve, one thread in double: M xi = -b by LDL^T, M = A + damping * diag(max(A_ii, 1e-3 max_i A_ii)) -- Marquardt's scaling with
+ * a floor, so that a direction with an exactly zero row (a fronto-parallel plane's) has a pivot under damping > 0 and stays put.
+ * Refused (ok = 0) when count < min_points, a pivot <= rcond * max_i A_ii, or anything is not finite.  E = exp(xi) on SE(3)
+ * (Rodrigues, series near 0), T_out = T_in T_model^-1 E^-1 T_model, its rotation re-orthonormalised through its unit quaternion.
+ * Outputs: viewmatrix_out[16] (W2C^T; may be viewmatrix_in: the finishing workgroup reads before it writes); quat_out[4]
+ * (r, x, y, z; unit, r >= 0) and trans_out[3] or NULL, dgr_pose_forward's convention; stats, 32 doubles: A (21), b (6),
+ * sum w r^2 [27], count [28], ok [29], |omega| [30], |v| [31] (both 0 when refused); flags [S] bytes or NULL (bit 0 valid, bit 1
+ * inside, bit 2 associated).  When refused every pose output carries the input's bits (quat_out derived from the input matrix).
+ * `scratch`: dgr_icp_scratch_bytes() bytes, 16-byte aligned (0 for a shape it refuses).  Its first 16 bytes hold the workgroups'
+ * ticket and MUST BE ZERO before the first call that uses it; every call leaves them zero, so one zero-filled allocation serves
+ * any number of calls in stream order (and a recorded graph replays).  The rest needs no initialisation.
+ * Argument errors return DGR_ERR_BAD_ARGUMENT with a message before any device call: non-positive width, height or stride, 2^30
+ * candidates or more; a NULL params, depth_obs, vn_model, model_viewmatrix, viewmatrix_in, scratch, viewmatrix_out or stats; a
+ * vn_obs, vn_model or scratch that is not 16-byte aligned, stats not 8-byte aligned; fx or fy not finite and positive; a NaN
+ * cx, cy, depth_min or depth_max; dist_max, huber_delta, damping or rcond NaN or negative; normal_cos_min outside [-1, 1] (or
+ * NaN); min_points < 1. */
+typedef struct dgr_icp_params {
+    float fx, fy, cx, cy;         /* the shared intrinsics, pixels */
+    float depth_min, depth_max;   /* exclusive bounds on a usable depth_obs; (0, INFINITY) = any valid sensor depth */
+    float dist_max;               /* >= 0: largest |q - v_m| of an associated pair (KinectFusion: 0.1 m) */
+    float normal_cos_min;         /* [-1, 1]; used with vn_obs (KinectFusion: cos 20 deg ~ 0.94; 0.8 here) */
+    float huber_delta;            /* >= 0; INFINITY = least squares */
+    float damping;                /* >= 0; 0 = Gauss-Newton */
+    float rcond;                  /* >= 0: smallest pivot accepted, relative to the largest diagonal entry of A */
+    int min_points;               /* >= 1 */
+    int stride;
+} dgr_icp_params;
+int dgr_depth_normals(void* stream, int width, int height, const float* depth, const float* mask_image /* or NULL */,
+                      float mask_threshold, float fx, float fy, float cx, float cy, float depth_min, float depth_max, float max_jump,
+                      float* vnmap);
+size_t dgr_icp_scratch_bytes(int width, int height, int stride);
+int dgr_icp_step(void* stream, int width, int height, const float* depth_obs, const float* vn_obs /* or NULL */,
+                 const float* vn_model, const float* model_viewmatrix, const float* viewmatrix_in, const dgr_icp_params* params,
+                 void* scratch, float* viewmatrix_out, float* quat_out /* or NULL */, float* trans_out /* or NULL */, double* stats,
+                 unsigned char* flags /* or NULL */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
