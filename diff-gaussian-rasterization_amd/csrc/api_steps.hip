@@ -474,10 +474,10 @@ int dgr_depth_normals(void* stream, int width, int height, const float* depth, c
 size_t dgr_icp_scratch_bytes(int width, int height, int stride) {
     return seed_shape_error(width, height, stride) ? 0 : dgr::icp_scratch_bytes(width, height, stride);
 }
-int dgr_icp_step(void* stream, int width, int height, const float* depth_obs, const float* vn_obs, const float* vn_model,
-                 const float* model_viewmatrix, const float* viewmatrix_in, const dgr_icp_params* params, void* scratch,
-                 float* viewmatrix_out, float* quat_out, float* trans_out, double* stats, unsigned char* flags) {
-    const dgr_icp_params* p = params;
+// what dgr_icp_step and dgr_rgbd_step check alike (the message, or NULL) and fill in alike
+static const char* icp_step_bad_argument(int width, int height, const float* depth_obs, const float* vn_obs, const float* vn_model,
+                                         const float* model_viewmatrix, const float* viewmatrix_in, const dgr_icp_params* p,
+                                         void* scratch, float* viewmatrix_out, double* stats) {
     const char* bad = !p ? "params is NULL" : seed_shape_error(width, height, p->stride);
     if (!bad && !depth_obs) bad = "depth_obs is NULL";
     if (!bad && vn_obs && !dgr::aligned16(vn_obs)) bad = "vn_obs is not 16-byte aligned";
@@ -497,8 +497,11 @@ int dgr_icp_step(void* stream, int width, int height, const float* depth_obs, co
     if (!bad && !(p->damping >= 0.0f)) bad = "damping is NaN or negative";
     if (!bad && !(p->rcond >= 0.0f)) bad = "rcond is NaN or negative";
     if (!bad && p->min_points < 1) bad = "min_points must be at least 1";
-    if (bad) return refuse("dgr_icp_step", bad);
-    dgr::IcpStepArgs a{};
+    return bad;
+}
+static void icp_step_fill(dgr::IcpStepArgs& a, int width, int height, const float* depth_obs, const float* vn_obs,
+                          const float* vn_model, const float* model_viewmatrix, const float* viewmatrix_in, const dgr_icp_params* p,
+                          float* viewmatrix_out, float* quat_out, float* trans_out, double* stats, unsigned char* flags) {
     a.W = width, a.H = height, a.stride = p->stride, a.depth_obs = depth_obs;
     a.vn_obs = reinterpret_cast<const float4*>(vn_obs), a.vn_model = reinterpret_cast<const float4*>(vn_model);
     a.model_viewmatrix = model_viewmatrix, a.viewmatrix_in = viewmatrix_in;
@@ -507,7 +510,80 @@ int dgr_icp_step(void* stream, int width, int height, const float* depth_obs, co
     a.normal_cos_min = p->normal_cos_min, a.huber_delta = p->huber_delta, a.damping = (double)p->damping, a.rcond = (double)p->rcond;
     a.min_points = p->min_points;
     a.viewmatrix_out = viewmatrix_out, a.quat_out = quat_out, a.trans_out = trans_out, a.stats = stats, a.flags = flags;
+}
+int dgr_icp_step(void* stream, int width, int height, const float* depth_obs, const float* vn_obs, const float* vn_model,
+                 const float* model_viewmatrix, const float* viewmatrix_in, const dgr_icp_params* params, void* scratch,
+                 float* viewmatrix_out, float* quat_out, float* trans_out, double* stats, unsigned char* flags) {
+    const char* bad = icp_step_bad_argument(width, height, depth_obs, vn_obs, vn_model, model_viewmatrix, viewmatrix_in, params, scratch,
+                                            viewmatrix_out, stats);
+    if (bad) return refuse("dgr_icp_step", bad);
+    dgr::IcpStepArgs a{};
+    icp_step_fill(a, width, height, depth_obs, vn_obs, vn_model, model_viewmatrix, viewmatrix_in, params, viewmatrix_out, quat_out,
+                  trans_out, stats, flags);
     HIP_TRY(dgr::launch_icp_step(a, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_intensity_map(void* stream, int width, int height, int channels, const float* image, const float* mask_image,
+                      float mask_threshold, float* imap, float* intensity) {
+    const char* bad = width < 1 || height < 1 ? "width and height must be positive" : nullptr;
+    if (!bad && (size_t)width * (size_t)height > (size_t)PLAN_MAX_ROWS) bad = "2^30 pixels or more";
+    if (!bad && channels != 1 && channels != 3) bad = "channels must be 1 or 3";
+    if (!bad && !image) bad = "image is NULL";
+    if (!bad && !imap && !intensity) bad = "imap and intensity are both NULL";
+    if (!bad && imap && !dgr::aligned16(imap)) bad = "imap is not 16-byte aligned";
+    if (!bad && mask_image && std::isnan(mask_threshold)) bad = "mask_threshold is NaN";
+    if (bad) return refuse("dgr_intensity_map", bad);
+    dgr::IntensityMapArgs a{};
+    a.W = width, a.H = height, a.C = channels, a.image = image, a.mask = mask_image, a.mask_threshold = mask_threshold;
+    a.imap = reinterpret_cast<float4*>(imap), a.intensity = intensity;
+    HIP_TRY(dgr::launch_intensity_map(a, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+int dgr_frame_halve(void* stream, int width, int height, int n_planes, const float* planes, const float* depth, float depth_min,
+                    float depth_max, float max_jump, float* planes_out, float* depth_out) {
+    const char* bad = width < 2 || height < 2 ? "width and height must be at least 2" : nullptr;
+    if (!bad && (size_t)width * (size_t)height > (size_t)PLAN_MAX_ROWS) bad = "2^30 pixels or more";
+    if (!bad && (n_planes < 0 || n_planes > 64)) bad = "n_planes must be 0 .. 64";
+    if (!bad && n_planes == 0 && !depth) bad = "nothing to halve: n_planes is 0 and depth is NULL";
+    if (!bad && n_planes > 0 && (!planes || !planes_out)) bad = "planes or planes_out is NULL";
+    if (!bad && depth && !depth_out) bad = "depth_out is NULL";
+    if (!bad && depth && (std::isnan(depth_min) || std::isnan(depth_max))) bad = "depth_min or depth_max is NaN";
+    if (!bad && depth && !(max_jump >= 0.0f)) bad = "max_jump is NaN or negative";
+    if (bad) return refuse("dgr_frame_halve", bad);
+    dgr::FrameHalveArgs a{};
+    a.W = width, a.H = height, a.planes = n_planes, a.planes_in = planes, a.depth_in = depth;
+    a.depth_min = depth_min, a.depth_max = depth_max, a.max_jump = max_jump, a.planes_out = planes_out, a.depth_out = depth_out;
+    HIP_TRY(dgr::launch_frame_halve(a, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+size_t dgr_rgbd_scratch_bytes(int width, int height, int stride) { return dgr_icp_scratch_bytes(width, height, stride); }
+int dgr_rgbd_step(void* stream, int width, int height, const float* depth_obs, const float* vn_obs, const float* vn_model,
+                  const float* intensity_obs, const float* imap_model, const float* model_viewmatrix, const float* viewmatrix_in,
+                  const dgr_rgbd_params* params, void* scratch, float* viewmatrix_out, float* quat_out, float* trans_out,
+                  double* stats, unsigned char* flags) {
+    const dgr_rgbd_params* p = params;
+    dgr_icp_params icp{};
+    if (p)
+        icp = dgr_icp_params{p->fx, p->fy, p->cx, p->cy, p->depth_min, p->depth_max, p->dist_max, p->normal_cos_min, p->huber_delta,
+                             p->damping, p->rcond, p->min_points, p->stride};
+    const char* bad = icp_step_bad_argument(width, height, depth_obs, vn_obs, vn_model, model_viewmatrix, viewmatrix_in, p ? &icp : nullptr,
+                                            scratch, viewmatrix_out, stats);
+    if (!bad && !intensity_obs) bad = "intensity_obs is NULL";
+    if (!bad && (!imap_model || !dgr::aligned16(imap_model))) bad = "imap_model is NULL or not 16-byte aligned";
+    if (!bad && !(p->geo_weight >= 0.0f)) bad = "geo_weight is NaN or negative";
+    if (!bad && !(p->photo_weight >= 0.0f)) bad = "photo_weight is NaN or negative";
+    if (!bad && !(p->photo_max >= 0.0f)) bad = "photo_max is NaN or negative";
+    if (!bad && !(p->photo_huber >= 0.0f)) bad = "photo_huber is NaN or negative";
+    if (bad) return refuse("dgr_rgbd_step", bad);
+    dgr::RgbdStepArgs a{};
+    icp_step_fill(a, width, height, depth_obs, vn_obs, vn_model, model_viewmatrix, viewmatrix_in, &icp, viewmatrix_out, quat_out,
+                  trans_out, stats, flags);
+    a.intensity_obs = intensity_obs, a.imap_model = reinterpret_cast<const float4*>(imap_model);
+    a.geo_weight = p->geo_weight, a.photo_weight = p->photo_weight, a.photo_max = p->photo_max, a.photo_huber = p->photo_huber;
+    HIP_TRY(dgr::launch_rgbd_step(a, scratch, (hipStream_t)stream));
     return DGR_OK;
 }
 

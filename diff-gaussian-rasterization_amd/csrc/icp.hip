@@ -10,6 +10,11 @@
 //          accumulators; block_sums; the block's partial goes to its own row of the scratch and the block takes a ticket
 //          (pose_reduce.h's deterministic form).  The block that draws the last ticket adds the rows in block order, solves the
 //          6 x 6 system by LDL^T in double, forms the new pose and leaves the ticket at zero: a recorded graph replays it.
+// Hybrid RGB-D alignment (dgr_intensity_map, dgr_frame_halve, dgr_rgbd_step): the photometric term beside the geometric one.
+// intensity: one thread per pixel: the packed intensity-gradient map (I, I_x, I_y, usable), Sobel / 8, and the plain intensity plane.
+// halve    : one thread per output pixel: one pyramid level of any number of mean planes and one depth plane.
+// rgbd step: the step's body instantiated on RgbdStepArgs: a second 16-byte gather, the photometric pair through the same
+//          accumulation, two more sums (31); everything behind the sums is the ICP step's.
 // No host read, no float atomics, the same bits on every run.
 #include <hip/hip_runtime.h>
 
@@ -23,10 +28,12 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int BLOCK_CANDIDATES = 2048;  // eight trips of a workgroup
 constexpr int SUMS = 29;                // A (21), b (6), sum w r^2, count
+constexpr int RGBD_SUMS = 31;           // A (21), b (6), sum w r^2, count_g, sum w_p r_p^2, count_p (the hybrid step's)
+constexpr int RGBD_STATS = 40;          // doubles of the hybrid step's stats
 constexpr int ROW = 32;                 // doubles per block in the scratch: a 256-byte row
 constexpr int CHUNK = 64;               // rows the finisher stages in LDS per trip
 constexpr size_t HEADER_BYTES = 256;    // the ticket (a uint32 at byte 0; zero between calls)
-constexpr unsigned ICP_VALID = 1u, ICP_INSIDE = 2u, ICP_ASSOCIATED = 4u;
+constexpr unsigned ICP_VALID = 1u, ICP_INSIDE = 2u, ICP_ASSOCIATED = 4u, ICP_PHOTOMETRIC = 8u;
 // A diagonal entry below this share of the largest is damped as if it were that large: a direction the data does not constrain
 // at all (an exactly zero row of A: the fronto-parallel plane) then has a positive pivot under damping > 0 and does not move.
 constexpr double DAMPING_FLOOR = 1e-3;
@@ -70,6 +77,70 @@ __global__ void __launch_bounds__(THREADS) depth_normals_kernel(DepthNormalsArgs
         }
     }
     a.vnmap[i] = out;
+}
+
+// ---------------------------------------------------------------------------------------------------------- intensity map
+// the intensity of pixel i: the single channel's bits, or (0.299 R + 0.587 G) + 0.114 B
+__device__ __forceinline__ float intensity_at(const IntensityMapArgs& a, size_t i, size_t n) {
+    if (a.C == 1) return a.image[i];
+    return (0.299f * a.image[i] + 0.587f * a.image[n + i]) + 0.114f * a.image[2 * n + i];
+}
+__global__ void __launch_bounds__(THREADS) intensity_map_kernel(IntensityMapArgs a) {
+    const size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t n = (size_t)a.W * (size_t)a.H;
+    if (i >= n) return;
+    const unsigned y = (unsigned)(i / (unsigned)a.W), x = (unsigned)(i - (size_t)y * (unsigned)a.W);
+    const float I = intensity_at(a, i, n);
+    if (a.intensity) a.intensity[i] = I;
+    if (!a.imap) return;
+    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (x >= 1 && y >= 1 && x + 1 < (unsigned)a.W && y + 1 < (unsigned)a.H) {
+        const size_t up = i - (size_t)a.W, dn = i + (size_t)a.W;
+        const float ul = intensity_at(a, up - 1, n), uc = intensity_at(a, up, n), ur = intensity_at(a, up + 1, n);
+        const float cl = intensity_at(a, i - 1, n), cr = intensity_at(a, i + 1, n);
+        const float dl = intensity_at(a, dn - 1, n), dc = intensity_at(a, dn, n), dr = intensity_at(a, dn + 1, n);
+        // finite: |v| < inf is false on a NaN
+        bool ok = fabsf(ul) < INFINITY && fabsf(uc) < INFINITY && fabsf(ur) < INFINITY && fabsf(cl) < INFINITY &&
+                  fabsf(I) < INFINITY && fabsf(cr) < INFINITY && fabsf(dl) < INFINITY && fabsf(dc) < INFINITY && fabsf(dr) < INFINITY;
+        if (ok && a.mask) {
+            const float t = a.mask_threshold;
+            ok = a.mask[up - 1] > t && a.mask[up] > t && a.mask[up + 1] > t && a.mask[i - 1] > t && a.mask[i] > t &&
+                 a.mask[i + 1] > t && a.mask[dn - 1] > t && a.mask[dn] > t && a.mask[dn + 1] > t;
+        }
+        if (ok) {
+            const float gx = (((ur - ul) + (dr - dl)) + 2.f * (cr - cl)) * 0.125f;
+            const float gy = (((dl - ul) + (dr - ur)) + 2.f * (dc - uc)) * 0.125f;
+            out = make_float4(I, gx, gy, 1.f);
+        }
+    }
+    a.imap[i] = out;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ halve
+__global__ void __launch_bounds__(THREADS) frame_halve_kernel(FrameHalveArgs a) {
+    const unsigned Wo = (unsigned)a.W >> 1, Ho = (unsigned)a.H >> 1;
+    const size_t o = (size_t)blockIdx.x * THREADS + threadIdx.x;
+    const size_t no = (size_t)Wo * Ho, n = (size_t)a.W * (size_t)a.H;
+    if (o >= no) return;
+    const unsigned y = (unsigned)(o / Wo), x = (unsigned)(o - (size_t)y * Wo);
+    const size_t i = (size_t)(2u * y) * (unsigned)a.W + 2u * x;  // the block's first pixel; an odd last row or column is dropped
+    for (int p = 0; p < a.planes; p++) {
+        const float* in = a.planes_in + (size_t)p * n;
+        a.planes_out[(size_t)p * no + o] = ((in[i] + in[i + 1]) + (in[i + a.W] + in[i + a.W + 1])) * 0.25f;
+    }
+    if (a.depth_in) {
+        const float d[4] = {a.depth_in[i], a.depth_in[i + 1], a.depth_in[i + a.W], a.depth_in[i + a.W + 1]};
+        float v[4], lo = INFINITY, hi = -INFINITY, count = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool ok = d[k] > a.depth_min && d[k] < a.depth_max;  // (false on a NaN)
+            v[k] = ok ? d[k] : 0.f;
+            if (ok) lo = fminf(lo, d[k]), hi = fmaxf(hi, d[k]), count += 1.f;
+        }
+        float out = 0.f;
+        if (count > 0.f && hi - lo <= a.max_jump * lo) out = ((v[0] + v[1]) + (v[2] + v[3])) / count;
+        a.depth_out[o] = out;
+    }
 }
 
 // -------------------------------------------------------------------------------------------------------------------- step
@@ -148,8 +219,10 @@ __device__ void se3_exp(const double (&w)[3], const double (&v)[3], double (&R)[
     }
 }
 
-// One thread: the totals -> stats, the solve, the update, the pose outputs.
+// One thread: the totals -> stats, the solve, the update, the pose outputs.  RGBD: the hybrid step's 31 totals and 40 stats.
+template <bool RGBD>
 __device__ void icp_finish(const IcpStepArgs& a, const double* tot) {
+    constexpr int N = RGBD ? RGBD_SUMS : SUMS;
     double M[6][6], b[6];
     {
         int k = 0;
@@ -160,9 +233,10 @@ __device__ void icp_finish(const IcpStepArgs& a, const double* tot) {
 #pragma unroll
         for (int i = 0; i < 6; i++) b[i] = tot[21 + i];
     }
-    bool ok = tot[28] >= (double)a.min_points;
+    bool ok = (RGBD ? tot[28] + tot[30] : tot[28]) >= (double)a.min_points;
 #pragma unroll
     for (int i = 0; i < 28; i++) ok = ok && isfinite(tot[i]);
+    if constexpr (RGBD) ok = ok && isfinite(tot[29]);
     double max_diag = 0.0;
 #pragma unroll
     for (int i = 0; i < 6; i++) max_diag = fmax(max_diag, M[i][i]);
@@ -260,14 +334,34 @@ __device__ void icp_finish(const IcpStepArgs& a, const double* tot) {
             else reinterpret_cast<uint32_t*>(a.trans_out)[i] = in_bits[12 + i];
         }
 #pragma unroll
-    for (int i = 0; i < SUMS; i++) a.stats[i] = tot[i];
-    a.stats[29] = ok ? 1.0 : 0.0;
-    a.stats[30] = ok ? sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) : 0.0;
-    a.stats[31] = ok ? sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]) : 0.0;
+    for (int i = 0; i < N; i++) a.stats[i] = tot[i];
+    a.stats[N] = ok ? 1.0 : 0.0;
+    a.stats[N + 1] = ok ? sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) : 0.0;
+    a.stats[N + 2] = ok ? sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]) : 0.0;
+    if constexpr (RGBD)
+#pragma unroll
+        for (int i = N + 3; i < RGBD_STATS; i++) a.stats[i] = 0.0;
 }
 
-// grid: one workgroup per block of candidates.  `ticket`: zero on entry, left at zero; `part`: a row of ROW doubles per workgroup
-__global__ void __launch_bounds__(THREADS) icp_step_kernel(IcpStepArgs a, uint32_t* __restrict__ ticket, double* __restrict__ part) {
+// one pair's terms onto a thread's sums: A += (s J_i) J_j, b += (s J_i) r, each product rounded to fp32 before it is widened
+__device__ __forceinline__ void add_pair(double* acc, const float (&J)[6], float r, float s) {
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+        const float sj = s * J[i];
+#pragma unroll
+        for (int j = i; j < 6; j++) acc[k++] += (double)(sj * J[j]);
+        acc[21 + i] += (double)(sj * r);
+    }
+}
+
+// grid: one workgroup per block of candidates.  `ticket`: zero on entry, left at zero; `part`: a row of ROW doubles per workgroup.
+// Args: IcpStepArgs, or RgbdStepArgs for the hybrid step (dgr_rgbd_step): the photometric pair beside the geometric one, each
+// scaled by its class weight, two more sums.
+template <class Args>
+__global__ void __launch_bounds__(THREADS) icp_step_kernel(Args a, uint32_t* __restrict__ ticket, double* __restrict__ part) {
+    constexpr bool RGBD = Args::rgbd;
+    constexpr int SUMS = RGBD ? RGBD_SUMS : dgr::SUMS;
     __shared__ float rel[12];  // current camera point p -> model camera point: q_j = rel[3 j] p_0 + rel[3 j + 1] p_1 + rel[3 j + 2] p_2 + rel[9 + j]
     __shared__ int last;
     __shared__ double rows[CHUNK * ROW];
@@ -307,44 +401,62 @@ __global__ void __launch_bounds__(THREADS) icp_step_kernel(IcpStepArgs a, uint32
             valid = valid && no.w > 0.f;
         }
         bool inside = false, associated = false;
+        [[maybe_unused]] bool photometric = false;
         if (valid) {
             const float p0 = ((float)x - a.cx) * a.inv_fx * d, p1 = ((float)y - a.cy) * a.inv_fy * d;
             const float q0 = r00 * p0 + r01 * p1 + r02 * d + t0;
             const float q1 = r10 * p0 + r11 * p1 + r12 * d + t1;
             const float q2 = r20 * p0 + r21 * p1 + r22 * d + t2;
-            const float uf = floorf(a.fx * q0 / q2 + a.cx + 0.5f), vf = floorf(a.fy * q1 / q2 + a.cy + 0.5f);
+            const float u = a.fx * q0 / q2 + a.cx, v = a.fy * q1 / q2 + a.cy;
+            const float uf = floorf(u + 0.5f), vf = floorf(v + 0.5f);
             if (q2 > 0.f && uf >= 0.f && uf < Wf && vf >= 0.f && vf < Hf) {  // (false on a NaN: the casts below are in range)
-                const float4 m = a.vn_model[(size_t)(unsigned)(int)vf * (unsigned)a.W + (unsigned)(int)uf];
+                const size_t mpix = (size_t)(unsigned)(int)vf * (unsigned)a.W + (unsigned)(int)uf;
+                const float4 m = a.vn_model[mpix];
+                [[maybe_unused]] float4 im;
+                [[maybe_unused]] float io;
+                if constexpr (RGBD) im = a.imap_model[mpix], io = a.intensity_obs[pix];  // (in flight beside m)
                 if (m.w > 0.f) {
                     inside = true;
                     const float e0 = q0 - (uf - a.cx) * a.inv_fx * m.w, e1 = q1 - (vf - a.cy) * a.inv_fy * m.w, e2 = q2 - m.w;
                     associated = sqrtf(e0 * e0 + e1 * e1 + e2 * e2) <= a.dist_max;
+                    [[maybe_unused]] const bool near = associated;  // |e| <= dist_max: the photometric pair's occlusion test
                     if (a.vn_obs) {
                         const float n0 = r00 * no.x + r01 * no.y + r02 * no.z, n1 = r10 * no.x + r11 * no.y + r12 * no.z,
                                     n2 = r20 * no.x + r21 * no.y + r22 * no.z;
                         associated = associated && n0 * m.x + n1 * m.y + n2 * m.z >= a.normal_cos_min;
                     }
-                    if (associated) {
+                    bool geometric = associated;
+                    if constexpr (RGBD) geometric = geometric && a.geo_weight > 0.f;
+                    if (geometric) {
                         const float r = m.x * e0 + m.y * e1 + m.z * e2;
                         const float J[6] = {q1 * m.z - q2 * m.y, q2 * m.x - q0 * m.z, q0 * m.y - q1 * m.x, m.x, m.y, m.z};
                         const float ar = fabsf(r);
                         const float w = ar <= a.huber_delta ? 1.f : a.huber_delta / ar;
-                        int k = 0;
-#pragma unroll
-                        for (int i = 0; i < 6; i++) {
-                            const float wj = w * J[i];
-#pragma unroll
-                            for (int j = i; j < 6; j++) acc[k++] += (double)(wj * J[j]);
-                            acc[21 + i] += (double)(wj * r);
-                        }
+                        if constexpr (RGBD) add_pair(acc, J, r, a.geo_weight * w);
+                        else add_pair(acc, J, r, w);
                         acc[27] += (double)((w * r) * r);
                         acc[28] += 1.0;
+                    }
+                    if constexpr (RGBD) {
+                        // the nearest model pixel's intensity with its first-order sub-pixel correction against the candidate's own
+                        const float rp = ((im.x + im.y * (u - uf)) + im.z * (v - vf)) - io;
+                        const float ap = fabsf(rp);
+                        photometric = near && im.w == 1.f && ap <= a.photo_max && fabsf(io) < INFINITY;  // (false on a NaN)
+                        if (photometric && a.photo_weight > 0.f) {
+                            const float g0 = im.y * a.fx / q2, g1 = im.z * a.fy / q2, g2 = -((g0 * q0 + g1 * q1) / q2);
+                            const float J[6] = {q1 * g2 - q2 * g1, q2 * g0 - q0 * g2, q0 * g1 - q1 * g0, g0, g1, g2};
+                            const float w = ap <= a.photo_huber ? 1.f : a.photo_huber / ap;
+                            add_pair(acc, J, rp, a.photo_weight * w);
+                            acc[29] += (double)((w * rp) * rp);
+                            acc[30] += 1.0;
+                        }
                     }
                 }
             }
         }
         if (a.flags)
-            a.flags[c] = (unsigned char)((valid ? ICP_VALID : 0u) | (inside ? ICP_INSIDE : 0u) | (associated ? ICP_ASSOCIATED : 0u));
+            a.flags[c] = (unsigned char)((valid ? ICP_VALID : 0u) | (inside ? ICP_INSIDE : 0u) | (associated ? ICP_ASSOCIATED : 0u) |
+                                         (RGBD && photometric ? ICP_PHOTOMETRIC : 0u));
     }
     block_sums(acc);
     if (threadIdx.x == 0) {
@@ -374,7 +486,7 @@ __global__ void __launch_bounds__(THREADS) icp_step_kernel(IcpStepArgs a, uint32
     __syncthreads();
     if (threadIdx.x == 0) {
         __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        icp_finish(a, totals);
+        icp_finish<RGBD>(a, totals);
     }
 }
 
@@ -383,6 +495,18 @@ __global__ void __launch_bounds__(THREADS) icp_step_kernel(IcpStepArgs a, uint32
 hipError_t launch_depth_normals(const DepthNormalsArgs& a, hipStream_t stream) {
     const size_t n = (size_t)a.W * (size_t)a.H;
     launch(depth_normals_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_intensity_map(const IntensityMapArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)a.W * (size_t)a.H;
+    launch(intensity_map_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_frame_halve(const FrameHalveArgs& a, hipStream_t stream) {
+    const size_t n = (size_t)(a.W / 2) * (size_t)(a.H / 2);
+    launch(frame_halve_kernel, dim3((unsigned)((n + THREADS - 1) / THREADS)), dim3(THREADS), stream, a);
     return hipGetLastError();
 }
 
@@ -395,7 +519,17 @@ hipError_t launch_icp_step(const IcpStepArgs& args, void* scratch, hipStream_t s
     const CandidateGrid g = candidate_grid(a.W, a.H, a.stride);
     a.candidates = g.candidates();
     a.wc = g.wc;
-    launch(icp_step_kernel, dim3(icp_blocks(a.candidates)), dim3(THREADS), stream, a, static_cast<uint32_t*>(scratch),
+    launch(icp_step_kernel<IcpStepArgs>, dim3(icp_blocks(a.candidates)), dim3(THREADS), stream, a, static_cast<uint32_t*>(scratch),
+           reinterpret_cast<double*>(static_cast<char*>(scratch) + HEADER_BYTES));
+    return hipGetLastError();
+}
+
+hipError_t launch_rgbd_step(const RgbdStepArgs& args, void* scratch, hipStream_t stream) {
+    RgbdStepArgs a = args;
+    const CandidateGrid g = candidate_grid(a.W, a.H, a.stride);
+    a.candidates = g.candidates();
+    a.wc = g.wc;
+    launch(icp_step_kernel<RgbdStepArgs>, dim3(icp_blocks(a.candidates)), dim3(THREADS), stream, a, static_cast<uint32_t*>(scratch),
            reinterpret_cast<double*>(static_cast<char*>(scratch) + HEADER_BYTES));
     return hipGetLastError();
 }

@@ -385,9 +385,35 @@ struct IcpStepArgs {
     unsigned char* flags;  // NULL: not stored
     size_t candidates;     // filled in by the launcher, as wc (candidates per grid row)
     int wc;
+    static constexpr bool rgbd = false;
 };
 size_t icp_scratch_bytes(int W, int H, int stride);
 hipError_t launch_icp_step(const IcpStepArgs& args, void* scratch, hipStream_t stream);
+// hybrid RGB-D alignment (icp.hip; include/dgr_hip.h: dgr_intensity_map, dgr_frame_halve, dgr_rgbd_step): the packed
+// intensity-gradient map of an image (one launch), one pyramid level of a frame (one launch), and the ICP step with the
+// photometric pair beside the geometric one: the same kernel body, instantiated on this argument struct (scratch: icp_scratch_bytes())
+struct IntensityMapArgs {
+    int W, H, C;                // C: 1 or 3 channel planes of W * H floats
+    const float *image, *mask;  // mask: NULL = no mask image
+    float mask_threshold;
+    float4* imap;      // NULL: not stored
+    float* intensity;  // NULL: not stored
+};
+hipError_t launch_intensity_map(const IntensityMapArgs& a, hipStream_t stream);
+struct FrameHalveArgs {
+    int W, H, planes;  // the input's size; the output is (W / 2) x (H / 2)
+    const float *planes_in, *depth_in;  // planes_in [planes, H, W] or NULL with planes = 0; depth_in: NULL = no depth plane
+    float depth_min, depth_max, max_jump;
+    float *planes_out, *depth_out;
+};
+hipError_t launch_frame_halve(const FrameHalveArgs& a, hipStream_t stream);
+struct RgbdStepArgs : IcpStepArgs {
+    const float* intensity_obs;
+    const float4* imap_model;
+    float geo_weight, photo_weight, photo_max, photo_huber;
+    static constexpr bool rgbd = true;
+};
+hipError_t launch_rgbd_step(const RgbdStepArgs& args, void* scratch, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -105,6 +105,13 @@ class IcpParams(C.Structure):  # dgr_icp_params
 
 assert C.sizeof(IcpParams) == 52  # thirteen four-byte fields: the C layout
 
+
+class RgbdParams(C.Structure):  # dgr_rgbd_params: dgr_icp_params' fields, then the two class weights and the photometric bounds
+    _fields_ = IcpParams._fields_ + [("geo_weight", _f), ("photo_weight", _f), ("photo_max", _f), ("photo_huber", _f)]
+
+
+assert C.sizeof(RgbdParams) == 68  # seventeen four-byte fields: the C layout
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -153,6 +160,10 @@ _SIGS = {
     "dgr_depth_normals": (_i, [_vp, _i, _i, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "dgr_icp_scratch_bytes": (_sz, [_i, _i, _i]),
     "dgr_icp_step": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(IcpParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgr_intensity_map": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
+    "dgr_frame_halve": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp]),
+    "dgr_rgbd_scratch_bytes": (_sz, [_i, _i, _i]),
+    "dgr_rgbd_step": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RgbdParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -23,6 +23,7 @@ from . import light as _light
 from .icp import IcpResult, depth_normals, icp_align  # noqa: F401
 from .keyframes import KeyframeOverlap, keyframe_overlap, select_keyframes  # noqa: F401  (slam.X stays the public name)
 from .losses import MaskedLossStats, l1_loss, l1_ssim_loss, masked_l1_loss, ssim  # noqa: F401
+from .rgbd import RgbdResult, halve_frame, intensity_map, level_intrinsics, rgbd_align  # noqa: F401
 from .pose import (_Kept, _cameras_of, camera_tensors, pose_to_camera, projection_matrix, quat_to_rotmat,  # noqa: F401
                    w2c_from_quat_trans)
 

@@ -22,7 +22,12 @@ rendered at the perturbed start pose, N Gauss-Newton iterations align the observ
 after ICP and at the end, with the time per ICP iteration.  --reach ROT TRANS additionally prints the first Adam iteration at which the
 rotation error is at most ROT and the translation error at most TRANS (read once per iteration: the timing then includes those reads).
 
-  python examples/tracking.py [--graph] [--fused] [--masked] [--complete-pose] [--icp N] [--reach ROT TRANS] [--trace K]
+With --rgbd N [--rgbd-levels L] the pose is first aligned by the hybrid step instead (slam.rgbd_align: the point-to-plane term and
+a photometric term on the rendered against the observed colour, N iterations on each of L pyramid levels, coarsest first); the
+rest is --icp's, with which it cannot be combined.
+
+  python examples/tracking.py [--graph] [--fused] [--masked] [--complete-pose] [--icp N | --rgbd N [--rgbd-levels L]]
+                              [--reach ROT TRANS] [--trace K]
                               [--iters 150]
                               [--width 640 --height 480 --gaussians 100000]
 """
@@ -54,9 +59,15 @@ def main():
     ap.add_argument("--trace", type=int, default=0, help="print the pose error every K iterations")
     ap.add_argument("--icp", type=int, default=0,
                     help="N iterations of frame-to-model ICP (slam.icp_align) on the depth images before the Adam loop")
+    ap.add_argument("--rgbd", type=int, default=0,
+                    help="N iterations per level of hybrid RGB-D alignment (slam.rgbd_align) on the colour and depth images before "
+                         "the Adam loop; not together with --icp")
+    ap.add_argument("--rgbd-levels", type=int, default=1, help="pyramid levels of --rgbd, coarsest first")
     ap.add_argument("--reach", type=float, nargs=2, default=None, metavar=("ROT", "TRANS"),
                     help="print the first Adam iteration at which the pose errors are at most ROT and TRANS")
     args = ap.parse_args()
+    if args.icp > 0 and args.rgbd > 0:
+        ap.error("--rgbd cannot be combined with --icp")
     if args.graph or args.fused:
         # a blocking status read cannot be captured, and a tracking loop has no use for num_rendered on the host: no host wait
         os.environ.setdefault("DGR_SYNC_MODE", "lazy") if not args.graph else os.environ.__setitem__("DGR_SYNC_MODE", "lazy")
@@ -155,6 +166,30 @@ def main():
             ok = int(aligned.stats[:, 29].sum())
             print(f"icp   : rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}, {ok} of {args.icp} steps accepted, "
                   f"{int(aligned.stats[-1, 28])} pairs, {dt / args.icp * 1e6:.1f} us per ICP iteration (eager, normals included)")
+        if args.rgbd > 0:
+            # as above with the hybrid step: the model's colour and depth at the start pose against the observed ones
+            fx, fy, cx, cy = W / (2.0 * tanfovx), H / (2.0 * tanfovy), (W - 1) / 2.0, (H - 1) / 2.0
+            with torch.no_grad():
+                cam = pose(q, t)
+                model = render(cam)
+                view0 = cam[0].detach().clone()
+
+                def align():
+                    return slam.rgbd_align(obs_c, obs_d, model["render"], model["depth"], None, view0, fx, fy, cx, cy,
+                                           levels=args.rgbd_levels, iterations=args.rgbd, opacity_map=model["opacity_map"],
+                                           depth_range=(1e-3, float("inf")))
+                align()  # (kernel loading is not timed)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                aligned = align()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                q.copy_(aligned.quat)
+                t.copy_(aligned.trans)
+            n = aligned.stats.shape[0]
+            print(f"rgbd  : rotation error {err()[0]:.2e}, translation error {err()[1]:.2e}, {int(aligned.stats[:, 31].sum())} of {n} "
+                  f"steps accepted, {int(aligned.stats[-1, 28])} geometric and {int(aligned.stats[-1, 30])} photometric pairs, "
+                  f"{dt / n * 1e6:.1f} us per iteration (eager, {args.rgbd_levels} level{'s' if args.rgbd_levels > 1 else ''}, maps included)")
         if args.graph:
             step = CapturedStep(iteration, warmup=3)  # (three eager iterations first)
             run = step.replay

@@ -684,6 +684,86 @@ int dgr_icp_step(void* stream, int width, int height, const float* depth_obs, co
                  void* scratch, float* viewmatrix_out, float* quat_out /* or NULL */, float* trans_out /* or NULL */, double* stats,
                  unsigned char* flags /* or NULL */);
 
+/* ---- hybrid RGB-D pose alignment: a photometric term beside the ICP step (csrc/icp.hip) ----
+ * What every classical RGB-D front end adds to point-to-plane ICP (Kerl's DVO, Open3D's hybrid odometry, the initialisers of
+ * Gaussian-SLAM and LoopSplat): the model's rendered colour against the sensor's colour.  It constrains the directions a planar
+ * scene leaves free.  Conventions are the ICP block's throughout; fused multiply-adds are allowed wherever a sum of products is
+ * written, the operation order is the one written.
+ *
+ * dgr_intensity_map: image [channels, height, width], channels = 1 or 3 (the rasterizer's layout), and mask_image [height, width]
+ * or NULL -> imap [height, width, 4] = (I, I_x, I_y, u), one 16-byte store per pixel, so that the step's gather is one 16-byte
+ * load; one launch, a thread per pixel.
+ *   I   = the single channel's bits, or (0.299f * R + 0.587f * G) + 0.114f * B
+ *   I_x = (((I(x+1,y-1) - I(x-1,y-1)) + (I(x+1,y+1) - I(x-1,y+1))) + 2 * (I(x+1,y) - I(x-1,y))) * 0.125f   (Sobel / 8)
+ *   I_y = (((I(x-1,y+1) - I(x-1,y-1)) + (I(x+1,y+1) - I(x+1,y-1))) + 2 * (I(x,y+1) - I(x,y-1))) * 0.125f
+ *   usable (u = 1.0f): the pixel is interior (x +- 1 and y +- 1 lie inside the image), all nine intensities of its 3 x 3
+ *   neighbourhood are finite, and with a mask all nine mask values > mask_threshold (a rendered image means something only where
+ *   the silhouette is).  Every other pixel gets four zeros.
+ * `intensity` [height, width] or NULL also receives I of every pixel as a plain plane (the observation's side of the step, and
+ * what the next pyramid level is halved from); imap may then be NULL.
+ * Argument errors: non-positive width or height, 2^30 pixels or more; channels other than 1 or 3; a NULL image; imap and
+ * intensity both NULL; a misaligned imap (16 bytes); a NaN mask_threshold with a mask.
+ *
+ * dgr_frame_halve: one pyramid level, one launch: width x height -> floor(width / 2) x floor(height / 2); output pixel (x, y)
+ * is made of the block a = (2x, 2y), b = (2x+1, 2y), c = (2x, 2y+1), d = (2x+1, 2y+1); an odd last row or column is dropped.
+ *   mean planes: planes [n_planes, height, width] -> planes_out [n_planes, height/2, width/2], ((a + b) + (c + d)) * 0.25f
+ *   depth plane (depth [height, width] or NULL -> depth_out): with usable = depth_min < d && d < depth_max per pixel of the
+ *   block, n their number, lo and hi the smallest and largest usable depth: ((a' + b') + (c' + d')) / (float)n where
+ *   n >= 1 && hi - lo <= max_jump * lo (v' = v when usable, else 0.0f; one fp32 division), else 0.0f.
+ * Pixel centres sit at integers, so the level's intrinsics are fx / 2, fy / 2, (cx - 0.5) / 2, (cy - 0.5) / 2.
+ * Argument errors: width or height below 2, 2^30 pixels or more; n_planes outside 0 .. 64; n_planes = 0 without a depth; a NULL
+ * planes or planes_out with n_planes > 0; a depth without depth_out; with a depth, a NaN depth_min or depth_max, max_jump NaN or
+ * negative.
+ *
+ * dgr_rgbd_step: one hybrid Gauss-Newton iteration, ONE launch: dgr_icp_step with a photometric pair per candidate beside the
+ * geometric one.  Extra inputs: intensity_obs [height, width], the observation's intensity as a plain plane (only the candidate's
+ * own value is read); imap_model [height, width, 4], dgr_intensity_map of the model's colour rendered at model_viewmatrix.
+ * Per candidate: valid, q, u, v, the pixel (px, py) = (floor(u + 0.5), floor(v + 0.5)), inside, e, associated, r, J and w are
+ * exactly dgr_icp_step's.  The geometric pair (an associated candidate) enters the sums only when geo_weight > 0.
+ *   photometric = inside && |e| <= dist_max (the occlusion test; no normal test) && u_m == 1 at (px, py) && I_obs finite &&
+ *                 |r_p| <= photo_max; it enters the sums only when photo_weight > 0
+ *   r_p = ((I_m + I_x * (u - px)) + I_y * (v - py)) - I_obs(x, y): the nearest model pixel with its first-order sub-pixel
+ *         correction: one gather, exact on a linear ramp
+ *   g   = (g_x, g_y, g_z), g_x = (I_x * fx) / q.z, g_y = (I_y * fy) / q.z, g_z = -((g_x * q.x + g_y * q.y) / q.z)
+ *   J_p = (q x g, g);  w_p = 1 for |r_p| <= photo_huber, else photo_huber / |r_p|
+ * Sums, in dgr_icp_step's order and double accumulation, a candidate's geometric pair before its photometric one: per pair
+ * s = class weight * w as one fp32 product (geo_weight * w, photo_weight * w_p), A += (s J_i) J_j, b += (s J_i) r, each product
+ * rounded to fp32; kept apart and unscaled by the class weight: sum w r^2 = sum (w r) r and count_g, sum w_p r_p^2 and count_p.
+ * Refused when count_g + count_p < min_points, or by dgr_icp_step's pivot and finiteness rules (sum w_p r_p^2 among the sums
+ * that must be finite).  Solve, update, outputs, the aliasing guarantee and the scratch contract are dgr_icp_step's;
+ * dgr_rgbd_scratch_bytes = dgr_icp_scratch_bytes, and one scratch serves both steps.
+ * stats, 40 doubles: A (21), b (6), sum w r^2 [27], count_g [28], sum w_p r_p^2 [29], count_p [30], ok [31], |omega| [32],
+ * |v| [33], zeros [34..39].  flags: dgr_icp_step's bits and bit 3 = photometric (whatever the class weights are).
+ * With geo_weight = 1 and photo_weight = 0 every pose output, A, b, sum w r^2 and the count carry dgr_icp_step's bits (1 * w is
+ * exact).
+ * Argument errors: dgr_icp_step's, and a NULL intensity_obs, a NULL or misaligned imap_model (16 bytes), geo_weight,
+ * photo_weight, photo_max or photo_huber NaN or negative. */
+typedef struct dgr_rgbd_params {
+    float fx, fy, cx, cy;         /* dgr_icp_params' fields, in its order */
+    float depth_min, depth_max;
+    float dist_max;
+    float normal_cos_min;
+    float huber_delta;
+    float damping;
+    float rcond;
+    int min_points;
+    int stride;
+    float geo_weight;             /* >= 0: the geometric pairs' class weight; 0 = photometric only */
+    float photo_weight;           /* >= 0: the photometric pairs' class weight (intensity^-2 against metres^-2); 0 = dgr_icp_step */
+    float photo_max;              /* >= 0: largest |r_p| of a photometric pair; INFINITY = none */
+    float photo_huber;            /* >= 0; INFINITY = least squares */
+} dgr_rgbd_params;
+int dgr_intensity_map(void* stream, int width, int height, int channels, const float* image, const float* mask_image /* or NULL */,
+                      float mask_threshold, float* imap /* or NULL */, float* intensity /* or NULL */);
+int dgr_frame_halve(void* stream, int width, int height, int n_planes, const float* planes /* or NULL */,
+                    const float* depth /* or NULL */, float depth_min, float depth_max, float max_jump, float* planes_out,
+                    float* depth_out);
+size_t dgr_rgbd_scratch_bytes(int width, int height, int stride);
+int dgr_rgbd_step(void* stream, int width, int height, const float* depth_obs, const float* vn_obs /* or NULL */,
+                  const float* vn_model, const float* intensity_obs, const float* imap_model, const float* model_viewmatrix,
+                  const float* viewmatrix_in, const dgr_rgbd_params* params, void* scratch, float* viewmatrix_out,
+                  float* quat_out /* or NULL */, float* trans_out /* or NULL */, double* stats, unsigned char* flags /* or NULL */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
