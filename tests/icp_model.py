@@ -53,11 +53,12 @@ def skew(w):
     return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
 
 
-def se3_exp(xi):
-    """(R, t) of the twist (omega | v): Rodrigues, the series below theta^2 = 1e-6"""
+def se3_exp(xi, mutate=None):
+    """(R, t) of the twist (omega | v): Rodrigues, the series below theta^2 = 1e-6.  `mutate`: "series_only" (the series at
+    every theta: a deliberately wrong model)"""
     w, v = np.asarray(xi[:3], np.float64), np.asarray(xi[3:], np.float64)
     th2 = float(w @ w)
-    if th2 < 1e-6:
+    if th2 < 1e-6 or mutate == "series_only":
         A = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0)
         B = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0)
         C = 1.0 / 6.0 - th2 / 120.0 * (1.0 - th2 / 42.0)
@@ -81,23 +82,38 @@ def w2ct(R, t):
     return np.ascontiguousarray(m.T.astype(np.float32))
 
 
-def rotation_to_quat(R):
-    """(r, x, y, z), unit, r >= 0: Shepperd's branches"""
-    tr = R[0, 0] + R[1, 1] + R[2, 2]
-    if tr > 0.0:
-        s = 2.0 * np.sqrt(tr + 1.0)
+QUAT_BRANCHES = ("trace", "x", "y", "z")
+POSE_MUTANTS = ("quat_branch_x", "quat_branch_y", "quat_branch_z", "no_sign_fix", "series_only")
+
+
+def quat_branch(R):
+    """which of Shepperd's branches rotation_to_quat takes on R: one of QUAT_BRANCHES"""
+    if R[0, 0] + R[1, 1] + R[2, 2] > 0.0:
+        return "trace"
+    if R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        return "x"
+    return "y" if R[1, 1] > R[2, 2] else "z"
+
+
+def rotation_to_quat(R, mutate=None):
+    """(r, x, y, z), unit, r >= 0: Shepperd's branches.  `mutate`: "quat_branch_x", "quat_branch_y", "quat_branch_z" (one
+    off-diagonal sum of that branch with a wrong sign), "no_sign_fix" (r < 0 is kept) -- deliberately wrong models"""
+    branch = quat_branch(R)
+    wrong = -1.0 if mutate == "quat_branch_" + branch else 1.0
+    if branch == "trace":
+        s = 2.0 * np.sqrt(R[0, 0] + R[1, 1] + R[2, 2] + 1.0)
         q = [0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
-    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+    elif branch == "x":
         s = 2.0 * np.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2])
-        q = [(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]
-    elif R[1, 1] > R[2, 2]:
+        q = [(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + wrong * R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]
+    elif branch == "y":
         s = 2.0 * np.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2])
-        q = [(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s]
+        q = [(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + wrong * R[2, 1]) / s]
     else:
         s = 2.0 * np.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1])
-        q = [(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s]
+        q = [(R[1, 0] - R[0, 1]) / s, (R[0, 2] + wrong * R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s]
     q = np.array(q) / np.linalg.norm(q)
-    return -q if q[0] < 0.0 else q
+    return -q if q[0] < 0.0 and mutate != "no_sign_fix" else q
 
 
 def quat_to_rotation(q):
@@ -157,6 +173,67 @@ def corner_scene(W, H, twist=TWIST):
     model_view, true_view = w2ct(Rm, tm), w2ct(Re @ Rm, Re @ tm + te)
     return dict(W=W, H=H, fx=fx, fy=fy, cx=cx, cy=cy, model_view=model_view, true_view=true_view,
                 model_depth=plane_depth(W, H, fx, fy, cx, cy, model_view), depth_obs=plane_depth(W, H, fx, fy, cx, cy, true_view))
+
+
+# ------------------------------------------------------------------------------------------------------------ world frames
+def move_world(view, Rt, c, model_view=None):
+    """The same camera seen from another world frame, X' = G X + c with G^T = Rm^T Rt, Rm the rotation of the scene's
+    `model_view` (None: `view` is the model's): the pose (R, t) becomes (R G^T, t - R G^T c), rounded once to fp32.  The model's
+    own rotation becomes Rt (to the orthonormality of an fp32 pose).  Applied to every pose of a scene alike; what lives in the
+    camera frame -- depth images, normal maps, intensity maps -- does not change."""
+    R, t = pose_of(view)
+    Rm, _ = pose_of(view if model_view is None else model_view)
+    RG = R @ (Rm.T @ np.asarray(Rt, np.float64))
+    return w2ct(RG, t - RG @ np.asarray(c, np.float64))
+
+
+def move_scene(s, name):
+    """a copy of the scene (or frame) `s` with model_view, view_in (where it has one) and true_view moved to WORLD_FRAMES[name]"""
+    Rt, c = WORLD_FRAMES[name]
+    out = dict(s)
+    for k in ("model_view", "view_in", "true_view"):
+        if k in s:
+            out[k] = move_world(s[k], Rt, c, s["model_view"])
+    return out
+
+
+def _axis_rotation(axis, angle):
+    i, j = (axis + 1) % 3, (axis + 2) % 3
+    R = np.eye(3)
+    R[i, i] = R[j, j] = np.cos(angle)
+    R[i, j], R[j, i] = -np.sin(angle), np.sin(angle)
+    return R
+
+
+def _world_frames():
+    """name -> (Rt, c): the model camera's rotation in the moved world and the moved world's origin shift.
+    identity: the control.  half_x, half_y, half_z: the half turns, where the model's, the input's and the output's rotations all
+    take Shepperd's diagonal branch x, y, z at a trace of -1 + O(twist^2).  near_x, near_y, near_z: rot_a(2.9) rot_b(0.2), a generic
+    rotation inside each diagonal branch.  perm120: the cyclic permutation, trace 0.  far: near_y at |c| = 100 m, where the
+    translations are large and cancel in rel.  random0 .. random31: seeded random rotations.  |c| <= 5 m but for far."""
+    rng = np.random.default_rng(2024)
+
+    def shift(length):
+        d = rng.standard_normal(3)
+        return d / np.linalg.norm(d) * length
+
+    near = [_axis_rotation(a, 2.9) @ _axis_rotation((a + 1) % 3, 0.2) for a in range(3)]
+    frames = {"identity": (np.eye(3), np.zeros(3))}
+    for a, n in enumerate("xyz"):
+        frames["half_" + n] = (np.diag([1.0 if k == a else -1.0 for k in range(3)]), shift(rng.uniform(1.0, 5.0)))
+    for a, n in enumerate("xyz"):
+        frames["near_" + n] = (near[a], shift(rng.uniform(1.0, 5.0)))
+    frames["perm120"] = (np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), shift(rng.uniform(1.0, 5.0)))
+    frames["far"] = (near[1], shift(100.0))
+    for k in range(32):
+        q = rng.standard_normal(4)
+        frames[f"random{k}"] = (quat_to_rotation(q / np.linalg.norm(q)), shift(rng.uniform(0.0, 5.0)))
+    return frames
+
+
+WORLD_FRAMES = _world_frames()
+NAMED_FRAMES = tuple(n for n in WORLD_FRAMES if not n.startswith("random"))
+RANDOM_FRAMES = tuple(n for n in WORLD_FRAMES if n.startswith("random"))
 
 
 def fronto_parallel_scene(W, H, depth=2.0):
@@ -375,9 +452,11 @@ def unpack(sums29):
     return A, np.asarray(sums29[21:27], np.float64), float(sums29[27]), float(sums29[28])
 
 
-def solve_update(sums29, model_view, view_in, *, damping=0.0, rcond=1e-8, min_points=6):
+def solve_update(sums29, model_view, view_in, *, damping=0.0, rcond=1e-8, min_points=6, mutate=None):
     """The finisher in float64: the solve by LDL^T, the refusals, the update.  Returns a dict: ok, xi [6], cond (of A; inf when
-    singular), cond_solved (of the damped matrix the solve factorises), viewmatrix float32 [4,4], quat float32 [4], trans float32 [3], omega, v (the norms; 0 when refused)."""
+    singular), cond_solved (of the damped matrix the solve factorises), viewmatrix float32 [4,4], quat float32 [4], trans float32 [3], omega, v (the norms; 0 when refused),
+    branch (Shepperd's, of the rotation whose quaternion is returned).  `mutate`: one of POSE_MUTANTS, the deliberately wrong
+    finishers (rotation_to_quat's and se3_exp's)."""
     A, b, _, count = unpack(np.asarray(sums29, np.float64))
     damping, rcond = f32(damping), f32(rcond)
     ok = count >= min_points and bool(np.all(np.isfinite(sums29[:28])))
@@ -404,17 +483,45 @@ def solve_update(sums29, model_view, view_in, *, damping=0.0, rcond=1e-8, min_po
     view_in = np.asarray(view_in, np.float32).reshape(4, 4)
     if ok:
         Rm, tm = pose_of(model_view)
-        Re, te = se3_exp(-xi)
+        Re, te = se3_exp(-xi, mutate)
         R1, t1 = Re @ Rm, Re @ tm + te
         R2, t2 = Rm.T @ R1, Rm.T @ (t1 - tm)
         Ro, to = Ri @ R2, Ri @ t2 + ti
-        quat = rotation_to_quat(Ro)
+        quat, branch = rotation_to_quat(Ro, mutate), quat_branch(Ro)
         view, trans = w2ct(quat_to_rotation(quat), to), to.astype(np.float32)
     else:
         xi = np.zeros(6)
-        quat, view, trans = rotation_to_quat(Ri), view_in.copy(), view_in[3, :3].copy()
+        quat, branch, view, trans = rotation_to_quat(Ri, mutate), quat_branch(Ri), view_in.copy(), view_in[3, :3].copy()
     return dict(ok=ok, xi=xi, cond=cond, cond_solved=cond_solved, viewmatrix=view, quat=quat.astype(np.float32), trans=trans,
-                omega=float(np.linalg.norm(xi[:3])), v=float(np.linalg.norm(xi[3:])))
+                omega=float(np.linalg.norm(xi[:3])), v=float(np.linalg.norm(xi[3:])), branch=branch)
+
+
+ULP = 2.0 ** -23  # of 1.0
+
+
+def pose_figures(view, quat, trans, want):
+    """A finisher's pose (float32 viewmatrix [4,4], quat [4], trans [3]) against solve_update's `want` of the same sums, as
+    figures: ulps [4,4] of the viewmatrix in the ulp of want's entries and the `allowed` number of them, rot (the largest
+    |R(quat) - R| against the viewmatrix's own rotation), norm (|quat|), r (quat[0]), trans_bits (trans carries the viewmatrix's
+    translation row bit for bit), last_column (0, 0, 0, 1 where the step was accepted).
+    Both sides are float64: they differ by the solve's rounding, the factorised matrix's condition number (A's without damping)
+    times 2^-53 times a small constant (16 here) relative to xi, which is at most of order 1 against matrix entries of order 1 --
+    in fp32 ulps of an entry 16 cond(A) 2^-29, nothing at cond(A) <= 1e3 and 0.03 ulp at 1e6 -- on top of the 2 ulp that the two
+    roundings to fp32 may differ by.  A refused step carries the input's bits: no tolerance."""
+    view, quat, trans = (np.asarray(a, np.float32) for a in (view, quat, trans))
+    ulps = np.abs(view.astype(np.float64) - want["viewmatrix"]) / np.spacing(np.abs(want["viewmatrix"]) + np.float32(1e-30))
+    allowed = 2.0 + 16.0 * want["cond_solved"] * 2.0 ** -29 if want["ok"] else 0.0
+    R = quat_to_rotation(quat.astype(np.float64))
+    return dict(ulps=ulps, allowed=allowed, rot=float(np.abs(R - view.astype(np.float64)[:3, :3].T).max()),
+                norm=float(np.linalg.norm(quat.astype(np.float64))), r=float(quat[0]),
+                trans_bits=bool(np.array_equal(trans.view(np.uint32), view[3, :3].view(np.uint32))),
+                last_column=view[:, 3].tolist() == [0.0, 0.0, 0.0, 1.0] or not want["ok"])
+
+
+def pose_holds(fig):
+    """the standard the figures are held to: check_pose's (tests/test_hip_icp.py)"""
+    return bool((fig["ulps"] <= fig["allowed"]).all() and fig["last_column"] and fig["rot"] <= 4 * ULP and
+                abs(fig["norm"] - 1.0) <= 2 * ULP and fig["r"] >= 0 and fig["trans_bits"])
 
 
 def icp_align_model(depth_obs, model_depth, viewmatrix, model_viewmatrix, fx, fy, cx, cy, *, iterations=10, strides=None,

@@ -135,12 +135,10 @@ STEP_CASES = ([(W, H, st, o, h) for W, H, st in ((3, 3, 1), (67, 5, 1), (67, 5, 
                for o in (True, False) for h in (INF, 0.01)] + [(640, 480, 1, True, INF)])
 
 
-@pytest.mark.parametrize("W,H,stride,with_obs,huber", STEP_CASES,
-                         ids=[f"{w}x{h}-stride{st}{'-vn_obs' if o else ''}-huber{hu}" for w, h, st, o, hu in STEP_CASES])
-def test_step_flags_sums_solve_and_update(W, H, stride, with_obs, huber):
-    s = frame(W, H)
-    m = step_model(W, H, stride, with_obs, huber)
-    out = run_step(s, stride, with_obs, huber)
+def check_step(out, m, s, label, conditioned=True, **solve):
+    """A step's result `out` on the frame `s` against the model's step `m` of the same arguments: the flags bit for bit at
+    unmarked candidates, the 28 sums within the model's bound over the kernel's own associated set, the solve and the update
+    against the model's (with `solve`'s arguments) fed with the kernel's own sums.  Prints the figures first; returns (stats, want)."""
     flags, stats = out.flags.cpu().numpy(), out.stats.cpu().numpy()[0]
     amb = m["ambiguous"]
     differ = flags != m["flags"]
@@ -149,7 +147,7 @@ def test_step_flags_sums_solve_and_update(W, H, stride, with_obs, huber):
     allowed = B + 2.0 ** -50 * mag
     with np.errstate(divide="ignore", invalid="ignore"):
         ratio = np.where(allowed > 0, np.abs(stats[:28] - S29[:28]) / allowed, np.where(stats[:28] == S29[:28], 0.0, INF))
-    print(f"{W}x{H}/{stride} vn_obs {with_obs} huber {huber}: S {m['S']} valid {m['valid']} associated {int(associated.sum())} "
+    print(f"{label}: S {m['S']} valid {m['valid']} associated {int(associated.sum())} "
           f"(model {int(m['associated'].sum())}) marked {int(amb.sum())} flags differ outside the marks {int((differ & ~amb).sum())} "
           f"inside {int((differ & amb).sum())}; largest |sum - model| / bound {ratio.max():.3g}; bound / sum |term| at most "
           f"{(B / (mag + 1e-300)).max():.3g}")
@@ -160,32 +158,39 @@ def test_step_flags_sums_solve_and_update(W, H, stride, with_obs, huber):
     assert stats[28] == associated.sum() > 0
     assert (ratio <= 1.0).all()
     # the solve and the update: the model's, fed with the kernel's own sums
-    want = M.solve_update(stats[:29], s["model_view"], s["view_in"])
-    assert want["cond"] <= 1e3 or (W, H) in ((3, 3), (67, 5))  # (the two tiny frames are there for the sums, not for the solve)
-    check_pose(out, want, stats, f"{W}x{H}/{stride}")
+    want = M.solve_update(stats[:29], s["model_view"], s["view_in"], **solve)
+    assert want["cond"] <= 1e3 or not conditioned
+    check_pose(out, want, stats, label)
+    return stats, want
+
+
+@pytest.mark.parametrize("W,H,stride,with_obs,huber", STEP_CASES,
+                         ids=[f"{w}x{h}-stride{st}{'-vn_obs' if o else ''}-huber{hu}" for w, h, st, o, hu in STEP_CASES])
+def test_step_flags_sums_solve_and_update(W, H, stride, with_obs, huber):
+    s = frame(W, H)
+    out = run_step(s, stride, with_obs, huber)
+    # (the two tiny frames are there for the sums, not for the solve)
+    check_step(out, step_model(W, H, stride, with_obs, huber), s, f"{W}x{H}/{stride} vn_obs {with_obs} huber {huber}",
+               conditioned=(W, H) not in ((3, 3), (67, 5)))
 
 
 def check_pose(out, want, stats, label):
-    """The kernel's pose against the model's solve and update of the kernel's own sums.  Both are float64: they differ by the
-    solve's rounding, the factorised matrix's condition number (A's without damping) times 2^-53 times a small constant (16 here) relative to xi, which is at most of order 1 against matrix
-    entries of order 1 -- in fp32 ulps of an entry 16 cond(A) 2^-29, nothing at cond(A) <= 1e3 and 0.03 ulp at 1e6 -- on top of
-    the 2 ulp that the two roundings to fp32 may differ by.  A refused step carries the input's bits: no tolerance."""
-    view, quat, trans = out.viewmatrix.cpu().numpy(), out.quat.cpu().numpy(), out.trans.cpu().numpy()
-    ulps = np.abs(view.astype(np.float64) - want["viewmatrix"]) / np.spacing(np.abs(want["viewmatrix"]) + np.float32(1e-30))
-    allowed = 2.0 + 16.0 * want["cond_solved"] * 2.0 ** -29 if want["ok"] else 0.0
+    """The kernel's pose against the model's solve and update of the kernel's own sums, by icp_model.pose_figures' standard
+    (shared with the model's own tests): the viewmatrix within 2 ulp (and the solve's rounding) of the model's, R(quat) within
+    4 ulp of 1 of the viewmatrix's rotation, |quat| within 2 ulp of 1, quat[0] >= 0, trans the viewmatrix's bits.  A refused step
+    carries the input's bits: no tolerance."""
+    fig = M.pose_figures(out.viewmatrix.cpu().numpy(), out.quat.cpu().numpy(), out.trans.cpu().numpy(), want)
     relative = max(1e-9, 16.0 * want["cond_solved"] * 2.0 ** -53) if want["ok"] else 0.0
-    R = M.quat_to_rotation(quat.astype(np.float64))
-    dq = np.abs(R - view.astype(np.float64)[:3, :3].T).max()
-    norm = np.linalg.norm(quat.astype(np.float64))
     print(f"{label}: ok {stats[29]} (model {want['ok']}) cond {want['cond']:.3g} |omega| {stats[30]:.3g} |v| {stats[31]:.3g}; "
-          f"viewmatrix_out differs by at most {ulps.max():.3g} ulp (allowed {allowed:.3g}); R(quat) - R {dq / ULP:.3g} ulp of 1; "
-          f"|quat| - 1 {(norm - 1) / ULP:.3g} ulp")
+          f"viewmatrix_out differs by at most {fig['ulps'].max():.3g} ulp (allowed {fig['allowed']:.3g}); R(quat) - R "
+          f"{fig['rot'] / ULP:.3g} ulp of 1; |quat| - 1 {(fig['norm'] - 1) / ULP:.3g} ulp; branch {want['branch']}")
     assert stats[29] == (1.0 if want["ok"] else 0.0)
-    assert (ulps <= allowed).all()
+    assert (fig["ulps"] <= fig["allowed"]).all()
     assert abs(stats[30] - want["omega"]) <= relative * max(want["omega"], 1e-3) and abs(stats[31] - want["v"]) <= relative * max(want["v"], 1e-3)
-    assert view[:, 3].tolist() == [0.0, 0.0, 0.0, 1.0] or not want["ok"]
-    assert dq <= 4 * ULP and abs(norm - 1.0) <= 2 * ULP and quat[0] >= 0
-    assert np.array_equal(trans.view(np.uint32), view[3, :3].view(np.uint32))
+    assert fig["last_column"]
+    assert fig["rot"] <= 4 * ULP and abs(fig["norm"] - 1.0) <= 2 * ULP and fig["r"] >= 0
+    assert fig["trans_bits"]
+    assert M.pose_holds(fig)
 
 
 def test_aliased_in_and_out_give_the_bits_of_separate_buffers():

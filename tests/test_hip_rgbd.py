@@ -108,12 +108,10 @@ STEP_CASES = [(W, H, st, w, h) for W, H, st in ((3, 3, 1), (67, 5, 1), (67, 5, 3
               for h in HUBERS]
 
 
-@pytest.mark.parametrize("W,H,stride,weights,hubers", STEP_CASES,
-                         ids=[f"{w}x{h}-stride{st}-geo{g[0]}-huber{hu[0]}" for w, h, st, g, hu in STEP_CASES])
-def test_step_flags_sums_solve_and_update(W, H, stride, weights, hubers):
-    s = corner_frame(W, H)
-    m = right_step(W, H, stride, weights, hubers)
-    out = run_step(s, stride, True, weights, hubers)
+def check_step(out, m, s, label, weights=(1.0, 1.0), **solve):
+    """A hybrid step's result `out` on the frame `s` against the model's step `m` of the same arguments: the flags bit for bit at
+    unmarked candidates, the 31 sums within the model's bound over the kernel's own pairs, the solve and the update to
+    test_hip_icp's standard (with `solve`'s arguments).  Prints the figures first; returns (stats, want)."""
     flags, stats = out.flags.cpu().numpy(), out.stats.cpu().numpy()[0]
     amb = m["ambiguous"]
     differ = flags != m["flags"]
@@ -123,7 +121,7 @@ def test_step_flags_sums_solve_and_update(W, H, stride, weights, hubers):
     sums = [k for k in range(31) if k not in (28, 30)]
     with np.errstate(divide="ignore", invalid="ignore"):
         ratio = np.where(allowed > 0, np.abs(stats[:31] - S31) / allowed, np.where(stats[:31] == S31, 0.0, INF))[sums]
-    print(f"{W}x{H}/{stride} weights {weights} hubers {hubers}: S {m['S']} valid {m['valid']} geometric {int(geometric.sum())} "
+    print(f"{label}: S {m['S']} valid {m['valid']} geometric {int(geometric.sum())} "
           f"photometric {int(photometric.sum())} (model {int(m['geometric'].sum())}, {int(m['photometric'].sum())}) marked "
           f"{int(amb.sum())} flags differ outside the marks {int((differ & ~amb).sum())} inside {int((differ & amb).sum())}; largest "
           f"|sum - model| / bound {ratio.max():.3g}; bound / sum |term| at most {(B / (mag + 1e-300)).max():.3g}")
@@ -133,9 +131,18 @@ def test_step_flags_sums_solve_and_update(W, H, stride, weights, hubers):
     assert not ((flags & 2) > (flags & 1) * 2).any() and not ((flags & 4) > (flags & 2) * 2).any() and not ((flags & 8) > (flags & 2) * 4).any()
     assert stats[28] == (geometric.sum() if weights[0] > 0 else 0) and stats[30] == photometric.sum() > 0
     assert (ratio <= 1.0).all() and not stats[34:].any()
-    want = R.solve_update(stats[:31], s["model_view"], s["view_in"])
+    want = R.solve_update(stats[:31], s["model_view"], s["view_in"], **solve)
     icp_like = np.concatenate([R.as_icp_sums(stats[:31]), stats[31:34]])  # check_pose reads ok, |omega|, |v| at [29..31]
-    check_pose(out, want, icp_like, f"{W}x{H}/{stride}")
+    check_pose(out, want, icp_like, label)
+    return stats, want
+
+
+@pytest.mark.parametrize("W,H,stride,weights,hubers", STEP_CASES,
+                         ids=[f"{w}x{h}-stride{st}-geo{g[0]}-huber{hu[0]}" for w, h, st, g, hu in STEP_CASES])
+def test_step_flags_sums_solve_and_update(W, H, stride, weights, hubers):
+    s = corner_frame(W, H)
+    out = run_step(s, stride, True, weights, hubers)
+    check_step(out, right_step(W, H, stride, weights, hubers), s, f"{W}x{H}/{stride} weights {weights} hubers {hubers}", weights)
 
 
 def test_photo_weight_zero_carries_the_bits_of_the_icp_step():
