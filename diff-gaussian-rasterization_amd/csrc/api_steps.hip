@@ -587,4 +587,62 @@ int dgr_rgbd_step(void* stream, int width, int height, const float* depth_obs, c
     return DGR_OK;
 }
 
+static const int PGO_MAX_POSES = 1 << 16, PGO_MAX_EDGES = 1 << 18, PGO_MAX_ITERATIONS = 1000;
+// 12 * 65 536 (the Python default at the largest graph) fits; one launch runs at most iterations * cg_iterations CG iterations
+static const int PGO_MAX_CG_ITERATIONS = 1 << 20;
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+static const char* pgo_shape_error(int n_poses, int n_edges) {
+    if (n_poses < 1 || n_poses > PGO_MAX_POSES) return "n_poses must be 1 .. 65536";
+    if (n_edges < 0 || n_edges > PGO_MAX_EDGES) return "n_edges must be 0 .. 2^18";
+    return nullptr;
+}
+size_t dgr_pgo_scratch_bytes(int n_poses, int n_edges) {
+    return pgo_shape_error(n_poses, n_edges) ? 0 : dgr::pgo_scratch_bytes(n_poses, n_edges);
+}
+int dgr_pgo_plan(void* stream, int n_poses, int n_edges, const int* edges, void* scratch) {
+    const char* bad = pgo_shape_error(n_poses, n_edges);
+    if (!bad && n_edges > 0 && !edges) bad = "edges is NULL";
+    if (!bad && !aligned4(edges)) bad = "edges is not 4-byte aligned";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (bad) return refuse("dgr_pgo_plan", bad);
+    HIP_TRY(dgr::launch_pgo_plan(n_poses, n_edges, edges, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+int dgr_pgo_solve(void* stream, int n_poses, int n_edges, const float* poses_in, const int* edges, const float* measurements,
+                  const float* information, int information_kind, const unsigned char* fixed, const dgr_pgo_params* params,
+                  void* scratch, float* poses_out, float* chi2, double* stats, int* flags) {
+    const dgr_pgo_params* p = params;
+    const char* bad = !p ? "params is NULL" : pgo_shape_error(n_poses, n_edges);
+    if (!bad && !poses_in) bad = "poses_in is NULL";
+    if (!bad && n_edges > 0 && !edges) bad = "edges is NULL";
+    if (!bad && n_edges > 0 && !measurements) bad = "measurements is NULL";
+    if (!bad && information_kind != 0 && information_kind != 2 && information_kind != 36) bad = "information_kind must be 0, 2 or 36";
+    if (!bad && information_kind != 0 && n_edges > 0 && !information) bad = "information is NULL";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && !poses_out) bad = "poses_out is NULL";
+    if (!bad && (!stats || (reinterpret_cast<uintptr_t>(stats) & 7u))) bad = "stats is NULL or not 8-byte aligned";
+    if (!bad && !flags) bad = "flags is NULL";
+    if (!bad && !(aligned4(poses_in) && aligned4(edges) && aligned4(measurements) && aligned4(information) && aligned4(poses_out) &&
+                  aligned4(chi2) && aligned4(flags)))
+        bad = "poses_in, edges, measurements, information, poses_out, chi2 or flags is not 4-byte aligned";
+    if (!bad && (p->iterations < 0 || p->iterations > PGO_MAX_ITERATIONS)) bad = "iterations must be 0 .. 1000";
+    if (!bad && (p->cg_iterations < 1 || p->cg_iterations > PGO_MAX_CG_ITERATIONS)) bad = "cg_iterations must be 1 .. 2^20";
+    if (!bad && !(p->cg_tolerance >= 0.0f)) bad = "cg_tolerance is NaN or negative";
+    if (!bad && !(p->huber_delta >= 0.0f)) bad = "huber_delta is NaN or negative";
+    if (!bad && !(p->damping >= 0.0f)) bad = "damping is NaN or negative";
+    if (!bad && !(p->rcond >= 0.0f)) bad = "rcond is NaN or negative";
+    if (!bad && !(p->step_tolerance >= 0.0f)) bad = "step_tolerance is NaN or negative";
+    if (!bad && !(p->cost_tolerance >= 0.0f)) bad = "cost_tolerance is NaN or negative";
+    if (bad) return refuse("dgr_pgo_solve", bad);
+    dgr::PgoArgs a{};
+    a.K = n_poses, a.E = n_edges, a.poses_in = poses_in, a.edges = edges, a.measurements = measurements;
+    a.information = information, a.information_kind = information_kind, a.fixed = fixed;
+    a.iterations = p->iterations, a.cg_iterations = p->cg_iterations;
+    a.cg_tolerance = (double)p->cg_tolerance, a.huber_delta = (double)p->huber_delta, a.damping = (double)p->damping;
+    a.rcond = (double)p->rcond, a.step_tolerance = (double)p->step_tolerance, a.cost_tolerance = (double)p->cost_tolerance;
+    a.poses_out = poses_out, a.chi2 = chi2, a.stats = stats, a.flags = flags;
+    HIP_TRY(dgr::launch_pgo_solve(a, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

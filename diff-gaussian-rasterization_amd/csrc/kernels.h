@@ -414,6 +414,27 @@ struct RgbdStepArgs : IcpStepArgs {
     static constexpr bool rgbd = true;
 };
 hipError_t launch_rgbd_step(const RgbdStepArgs& args, void* scratch, hipStream_t stream);
+// pose-graph optimisation (pgo.hip; include/dgr_hip.h: dgr_pgo_plan, dgr_pgo_solve): the nodes' incidence lists into `scratch`
+// (one launch of one workgroup), and the whole Levenberg-Marquardt solve over them (one launch of one workgroup; `scratch`:
+// pgo_scratch_bytes() bytes that a plan call for the same K, E and edges filled)
+struct PgoArgs {
+    int K, E;
+    const float* poses_in;      // [K,16], W2C^T
+    const int* edges;           // [E,2]
+    const float* measurements;  // [E,16], Z^T
+    const float* information;   // NULL with kind 0, [E,2] with kind 2, [E,36] with kind 36
+    int information_kind;
+    const unsigned char* fixed;  // [K] or NULL: only pose 0 is fixed
+    int iterations, cg_iterations;
+    double cg_tolerance, huber_delta, damping, rcond, step_tolerance, cost_tolerance;
+    float* poses_out;  // [K,16]; may be poses_in
+    float* chi2;       // [E] or NULL
+    double* stats;     // [16]
+    int* flags;        // [1]
+};
+size_t pgo_scratch_bytes(int K, int E);
+hipError_t launch_pgo_plan(int K, int E, const int* edges, void* scratch, hipStream_t stream);
+hipError_t launch_pgo_solve(const PgoArgs& args, void* scratch, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -112,6 +112,14 @@ class RgbdParams(C.Structure):  # dgr_rgbd_params: dgr_icp_params' fields, then 
 
 assert C.sizeof(RgbdParams) == 68  # seventeen four-byte fields: the C layout
 
+
+class PgoParams(C.Structure):  # dgr_pgo_params
+    _fields_ = [("iterations", _i), ("cg_iterations", _i), ("cg_tolerance", _f), ("huber_delta", _f), ("damping", _f),
+                ("rcond", _f), ("step_tolerance", _f), ("cost_tolerance", _f)]
+
+
+assert C.sizeof(PgoParams) == 32  # eight four-byte fields: the C layout
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -164,6 +172,9 @@ _SIGS = {
     "dgr_frame_halve": (_i, [_vp, _i, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp]),
     "dgr_rgbd_scratch_bytes": (_sz, [_i, _i, _i]),
     "dgr_rgbd_step": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RgbdParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dgr_pgo_scratch_bytes": (_sz, [_i, _i]),
+    "dgr_pgo_plan": (_i, [_vp, _i, _i, _vp, _vp]),
+    "dgr_pgo_solve": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(PgoParams), _vp, _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

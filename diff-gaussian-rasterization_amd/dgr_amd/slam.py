@@ -22,6 +22,7 @@ from . import full as _full
 from . import light as _light
 from .icp import IcpResult, depth_normals, icp_align  # noqa: F401
 from .keyframes import KeyframeOverlap, keyframe_overlap, select_keyframes  # noqa: F401  (slam.X stays the public name)
+from .posegraph import PgoPlan, PgoResult, pose_graph_optimize, pose_graph_plan, relative_pose  # noqa: F401
 from .losses import MaskedLossStats, l1_loss, l1_ssim_loss, masked_l1_loss, ssim  # noqa: F401
 from .rgbd import RgbdResult, halve_frame, intensity_map, level_intrinsics, rgbd_align  # noqa: F401
 from .pose import (_Kept, _cameras_of, camera_tensors, pose_to_camera, projection_matrix, quat_to_rotmat,  # noqa: F401

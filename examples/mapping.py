@@ -139,7 +139,7 @@ class SeededMapModel(MapModel):
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
                  absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0, relocate_every=0,
                  position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0, loop_close_at=0,
-                 loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True):
+                 loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True, loop_close_pgo=False):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -165,7 +165,11 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     units; 0: none) shared by all of them, as a loop closure moves a stretch of trajectory, followed by each keyframe's own of a
     hundredth of that, drawn from `loop_close_seed` -- and transform_map moves every Gaussian with its keyframe (between replays
     with graph=True; loop_close_moves_map=False leaves the map where it was).  The model's `loop_closure` attribute then holds the
-    losses of iteration N and N + 1 (before, after) and the step's counts."""
+    losses of iteration N and N + 1 (before, after) and the step's counts.
+    loop_close_pgo=True: the drawn poses are the truth, and the poses the map follows are SOLVED for: slam.pose_graph_optimize gets
+    the old poses with keyframe 0 set to its true pose and fixed, K - 1 chain edges and one loop edge K - 1 -> 0, each measured on
+    the truth with slam.relative_pose; its result goes to pose_corrections and transform_map in place of the drawn poses (on the
+    device, between replays with graph=True).  `loop_closure` then also holds "solved" and "truth" ([K,4,4] each) and "pgo_stats"."""
     from dgr_amd import light, slam
     from dgr_amd.optim import (SparseAdam, add_densification_stats, densify_and_prune, inject_position_noise, pose_corrections,
                                relocate_dead, seed_from_frame, transform_map)
@@ -347,6 +351,15 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         deltas = np.stack([rigid(rng, loop_close_scale / 100.0) @ shared for _ in cams])
         old = torch.stack([c["viewmatrix"] for c in cams])
         new = (torch.from_numpy(np.linalg.inv(deltas).transpose(0, 2, 1)).to(dev) @ old.double()).float()
+        if loop_close_pgo:
+            K = len(cams)
+            edges = torch.tensor([(k + 1, k) for k in range(K - 1)] + [(K - 1, 0)], dtype=torch.int32, device=dev)
+            measured = slam.relative_pose(new[edges[:, 0].long()], new[edges[:, 1].long()])
+            start = old.clone()
+            start[0] = new[0]
+            solved = slam.pose_graph_optimize(start, edges, measured, iterations=20)
+            closure.update(truth=new, solved=solved.viewmatrices, pgo_stats=solved.stats)
+            new = solved.viewmatrices
         corrections = pose_corrections(old, new)
         for c, v in zip(cams, new):
             c["viewmatrix"].copy_(v)
@@ -398,6 +411,8 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     if loop_close_at:
         pc.loop_closure = dict(before=float(closure["before"]), after=float(closure["after"]),
                                counts=None if closure["counts"] is None else closure["counts"].tolist())
+        if loop_close_pgo:
+            pc.loop_closure.update(solved=closure["solved"], truth=closure["truth"], pgo_stats=closure["pgo_stats"].tolist())
         if log:
             log(f"loop closure after iteration {loop_close_at}: loss {pc.loop_closure['before']:.4e} before, "
                 f"{pc.loop_closure['after']:.4e} after; counts {pc.loop_closure['counts']}")
@@ -447,6 +462,9 @@ def main():
                          "every Gaussian follows the keyframe it was seeded from (pose_corrections + transform_map); all keyframes are "
                          "then seeded before the first iteration, so --graph and --fused are allowed")
     ap.add_argument("--loop-close-seed", type=int, default=0, help="the seed of --loop-close-at's corrections")
+    ap.add_argument("--pgo", action="store_true",
+                    help="with --loop-close-at: the corrected poses are solved for on the device (slam.pose_graph_optimize over chain "
+                         "edges and one loop edge measured on the drawn poses) instead of being taken as drawn")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -459,6 +477,8 @@ def main():
         ap.error("--densify-every changes the number of Gaussians: it cannot run inside a recorded hipGraph (drop --graph)")
     if args.loop_close_at and not args.seed:
         ap.error("--loop-close-at moves every Gaussian with the keyframe it was seeded from: it needs --seed")
+    if args.pgo and not args.loop_close_at:
+        ap.error("--pgo solves the pose graph of --loop-close-at: give that too")
     if args.seed and (((args.graph or args.fused) and not args.loop_close_at) or args.variant != "light"):
         ap.error("--seed changes the number of Gaussians and grows the window: it cannot run inside a recorded hipGraph (drop "
                  "--graph), and it maps through the per-keyframe light path (drop --fused / --variant full)")
@@ -481,7 +501,12 @@ def main():
                                     seed=args.seed, masked=args.masked, select=args.select, relocate_every=args.relocate_every,
                                     position_noise=args.position_noise, relocate_min_opacity=args.relocate_min_opacity,
                                     relocate_start=args.relocate_start, loop_close_at=args.loop_close_at,
-                                    loop_close_seed=args.loop_close_seed)
+                                    loop_close_seed=args.loop_close_seed, loop_close_pgo=args.pgo)
+    if args.pgo:
+        c = pc.loop_closure
+        s = c["pgo_stats"]
+        print(f"pose graph: {len(c['solved'])} poses solved in {s[3]:.0f} trials ({s[4]:.0f} accepted, {s[6]:.0f} CG iterations), cost "
+              f"{s[0]:.4e} -> {s[1]:.4e}, ok {s[2]:.0f}, |solved - drawn| {float((c['solved'] - c['truth']).abs().max()):.3e}")
     if args.loop_close_at and args.graph:
         print(f"loop closure after iteration {args.loop_close_at}: loss {pc.loop_closure['before']:.4e} before, "
               f"{pc.loop_closure['after']:.4e} after; counts {pc.loop_closure['counts']}")

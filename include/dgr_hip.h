@@ -764,6 +764,78 @@ int dgr_rgbd_step(void* stream, int width, int height, const float* depth_obs, c
                   const float* viewmatrix_in, const dgr_rgbd_params* params, void* scratch, float* viewmatrix_out,
                   float* quat_out /* or NULL */, float* trans_out /* or NULL */, double* stats, unsigned char* flags /* or NULL */);
 
+/* ---- pose-graph optimisation: the solver in front of the map correction (csrc/pgo.hip) ----
+ * What a SLAM back end runs after a loop closure (g2o, GTSAM, Open3D's pose graph), here on the device: n_poses keyframe poses
+ * T_k (16 floats holding W2C^T each, as everywhere above) and n_edges relative-pose constraints give the poses that
+ * dgr_transform_plan's corrections are formed from.  No host read, no float atomics, the same bits on every run, capturable
+ * into a hipGraph.
+ * Problem: edge e = (i, j, Z_e, Omega_e), edges [n_edges, 2] int32 = (i, j), measures Z_e ~ T_i T_j^-1 (camera j's coordinates to
+ *   camera i's); measurements [n_edges, 16] holds Z_e^T, the viewmatrix layout.  r_e = Log(Z_e^-1 T_i T_j^-1) in R^6, ordered
+ *   (omega, v) as dgr_icp_step's twist; s_e = sqrt(r_e^T Omega_e r_e); minimised is sum_e rho(s_e), rho(s) = s^2 for
+ *   s <= huber_delta and 2 huber_delta s - huber_delta^2 beyond (INFINITY: least squares), over the free poses with the update
+ *   T_k <- Exp(d_k) T_k.  `fixed` [n_poses] bytes (non-zero = fixed) holds the gauge; NULL fixes pose 0 only.
+ *   information_kind 0: Omega = I (information ignored); 2: information [n_edges, 2] = (rotation weight, translation weight),
+ *   Omega = diag(a, a, a, b, b, b); 36: information [n_edges, 6, 6] row-major, its symmetric part used.
+ * dgr_pgo_plan: ONE launch of one workgroup: every pose's incidence list (edge, side) into `scratch`, in ascending edge order, side
+ *   i before side j.  This order is the summation order of every per-node sum below.  An edge with an index outside
+ *   0 .. n_poses - 1 or with i == j is left out (and counted as skipped by the solve).  A plan serves every solve with the same
+ *   n_poses, n_edges and edges, in stream order (and a recorded graph replays).
+ * dgr_pgo_solve: ONE launch of one workgroup runs the whole solve, all in double: Levenberg-Marquardt with iteratively
+ *   reweighted Huber, at most `iterations` trials.  Poses are read into unit quaternions and translations; the solve is REFUSED
+ *   (stats ok = 0, every pose output the input's bits, chi2 NaN) when a pose is not rigid: not finite, det <= 0, or R^T R off the
+ *   identity by more than 1e-3 (dgr_transform_plan's rule), or when `scratch` holds no plan for this n_poses and n_edges.
+ *   Linearise: per usable edge r_e, the exact first-order Jacobians J_j = -J_r^-1(r_e), J_i = J_r^-1(r_e) Ad(T_j T_i^-1) in closed
+ *   form, w_e = min(1, huber_delta / s_e), the blocks of H = sum J^T (w Omega) J and g = sum J^T (w Omega) r.  The Log goes through
+ *   the sign-normalised unit quaternion (stable up to an angle of pi; a series below theta^2 = 1e-6).  An edge is skipped and
+ *   counted when the plan left it out, Z_e is not rigid (the rule above) or Omega_e has a non-finite entry.
+ *   Per node, in list order: its diagonal block and gradient; the damped block's 6 x 6 LDL^T.  A free node with a pivot
+ *   <= rcond * (its largest diagonal entry) -- a node with no usable edge among them -- is loose: treated as fixed for the rest
+ *   of the solve and counted.
+ *   (H + lambda diag H) d = -g by preconditioned conjugate gradients, block-Jacobi preconditioner (those LDL^T), x0 = 0, at most
+ *   cg_iterations, stopped at r^T M^-1 r <= cg_tolerance^2 r0^T M^-1 r0.  H p is a per-node gather: the damped diagonal block
+ *   first, then the off-diagonal blocks in list order.  Dot products and the cost: a thread's items ascending (thread t of 256
+ *   takes t, t + 256, ..), then the workgroup's fixed-order block sum.
+ *   The candidate T_k <- Exp(d_k) T_k is accepted when its cost fell, then lambda <- max(lambda / 10, 1e-12); otherwise the poses
+ *   are restored and lambda <- min(10 lambda, 1e12).  Stops early on an accepted step with max(|omega_k|, |v_k|) <
+ *   step_tolerance or a relative cost decrease below cost_tolerance (both: converged), on a zero gradient or no free node left
+ *   (converged, the trial not counted), or with lambda at its maximum.
+ * Outputs: poses_out [n_poses, 16] (may be poses_in), rotations re-orthonormalised through the quaternion; fixed and loose poses
+ *   -- and every pose when no step was accepted -- keep the input's bits.  chi2 [n_edges] or NULL: s_e^2 at the poses as
+ *   written, NaN for a skipped edge.  stats, 16 doubles: initial cost [0], final cost (at the poses as written) [1], ok [2],
+ *   trials run [3], accepted [4], rejected [5], CG iterations in total [6], final lambda [7], max_k |omega_k| [8] and max_k |v_k|
+ *   [9] of the last accepted step, max |g| over the free poses at the poses as written [10] (g = sum J^T w Omega r, half the
+ *   cost's gradient), edges used [11], edges skipped [12], loose poses [13], converged [14], 0 [15].  flags [1] int: bit 0
+ *   refused, bit 1 an edge was skipped, bit 2 a pose is loose, bit 3 stopped with lambda at its maximum, bit 4 a CG solve ran
+ *   into cg_iterations, bit 5 no plan.
+ * `scratch`: dgr_pgo_scratch_bytes() bytes, 16-byte aligned (0 for a shape it refuses: n_poses outside 1 .. 65536, n_edges
+ *   outside 0 .. 2^18); no initialisation needed before dgr_pgo_plan.
+ * Argument errors return DGR_ERR_BAD_ARGUMENT with a message before any device call: those shapes; a NULL params, poses_in,
+ *   poses_out, flags, scratch (or a misaligned one), stats (or one not 8-byte aligned); with n_edges > 0 a NULL edges,
+ *   measurements, or information with a kind other than 0; an information_kind other than 0, 2, 36; iterations outside
+ *   0 .. 1000; cg_iterations outside 1 .. 2^20; a poses_in, edges, measurements, information, poses_out, chi2 or flags that is not
+ *   4-byte aligned; a cg_tolerance, huber_delta, damping, rcond, step_tolerance or cost_tolerance that is NaN or negative.
+ * How long one launch can run: the solve is one workgroup that nothing interrupts, and it runs at most iterations * cg_iterations
+ *   CG iterations, each a pass over the nodes and their lists (measured on an MI355X: 12 us at 200 poses, 64 us at 1000, growing
+ *   with n_poses / 256 and with the degrees).  The caps keep that finite, not short: at the largest shapes and the Python default of
+ *   12 n_poses the bound is hours on one compute unit.  Size iterations and cg_iterations to the time the device can be held;
+ *   flags bit 4 says when a CG solve was cut off. */
+typedef struct dgr_pgo_params {
+    int iterations;               /* 0 .. 1000 trials; 0 evaluates chi2 and the costs only */
+    int cg_iterations;            /* 1 .. 2^20; block-Jacobi CG needs about 2 n_poses on a chain */
+    float cg_tolerance;           /* >= 0: relative, on sqrt(r^T M^-1 r) */
+    float huber_delta;            /* >= 0; INFINITY = least squares */
+    float damping;                /* >= 0: the initial lambda (kept inside 1e-12 .. 1e12) */
+    float rcond;                  /* >= 0: smallest pivot of a node's block, relative to its largest diagonal entry */
+    float step_tolerance;         /* >= 0 */
+    float cost_tolerance;         /* >= 0 */
+} dgr_pgo_params;
+size_t dgr_pgo_scratch_bytes(int n_poses, int n_edges);
+int dgr_pgo_plan(void* stream, int n_poses, int n_edges, const int* edges, void* scratch);
+int dgr_pgo_solve(void* stream, int n_poses, int n_edges, const float* poses_in, const int* edges, const float* measurements,
+                  const float* information /* or NULL */, int information_kind, const unsigned char* fixed /* or NULL */,
+                  const dgr_pgo_params* params, void* scratch, float* poses_out, float* chi2 /* or NULL */, double* stats,
+                  int* flags);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
