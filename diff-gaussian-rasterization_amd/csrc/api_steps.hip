@@ -5,6 +5,7 @@
 
 #include "host_util.h"
 #include "kernels.h"
+#include "options.h"
 
 using namespace dgr;
 
@@ -642,6 +643,66 @@ int dgr_pgo_solve(void* stream, int n_poses, int n_edges, const float* poses_in,
     a.rcond = (double)p->rcond, a.step_tolerance = (double)p->step_tolerance, a.cost_tolerance = (double)p->cost_tolerance;
     a.poses_out = poses_out, a.chi2 = chi2, a.stats = stats, a.flags = flags;
     HIP_TRY(dgr::launch_pgo_solve(a, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+// ---- contribution statistics (contrib.hip)
+static bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+static size_t contribution_plane(long P, size_t elem) { return dgr::align_up(elem * (size_t)P, 256); }
+size_t dgr_contribution_scratch_bytes(long P) {
+    if (P < 0 || P > (long)DGR_ID_MASK) return 0;
+    return contribution_plane(P, 4) + contribution_plane(P, 4) + contribution_plane(P, 8) + 256;  // (never 0 for a valid P)
+}
+int dgr_contribution_stats(void* stream, long P, int width, int height, int R, const char* geometry_buffer,
+                           const char* binning_buffer, const char* image_buffer, const dgr_contribution_params* params,
+                           void* scratch, int* n_touched, float* max_weight, long long* sum_weight, long long* touched_total,
+                           float* max_weight_total, long long* sum_weight_total, int* views, int* last_seen,
+                           int* counts4_device) {
+    const dgr_contribution_params* p = params;
+    const bool all_views = n_touched && max_weight && sum_weight;
+    const char* bad = !p ? "params is NULL" : nullptr;
+    if (!bad && (P < 0 || P > (long)DGR_ID_MASK)) bad = "P must be 0 .. 2^28 - 1";
+    if (!bad && (width <= 0 || height <= 0 || (long long)width * height > (1ll << 30))) bad = "width and height must be positive (and width * height at most 2^30)";
+    if (!bad && R < 0) bad = "R is negative";
+    if (!bad && P > 0 && (!geometry_buffer || !binning_buffer || !image_buffer)) bad = "the forward's three state buffers are required";
+    if (!bad && p->min_pixels < 0) bad = "min_pixels is negative";
+    if (!bad && !(p->weight_min >= 0.0f)) bad = "weight_min is NaN or negative";
+    if (!bad && P > 0 && !all_views && !scratch) bad = "scratch is NULL (a per-view output is NULL: it lives there)";
+    if (!bad && !dgr::aligned16(scratch)) bad = "scratch is not 16-byte aligned";
+    if (!bad && !(aligned_to(n_touched, 4) && aligned_to(max_weight, 4) && aligned_to(views, 4) && aligned_to(last_seen, 4) &&
+                  aligned_to(max_weight_total, 4) && aligned_to(counts4_device, 4)))
+        bad = "n_touched, max_weight, max_weight_total, views, last_seen or counts4_device is not 4-byte aligned";
+    if (!bad && !(aligned_to(sum_weight, 8) && aligned_to(touched_total, 8) && aligned_to(sum_weight_total, 8)))
+        bad = "sum_weight, touched_total or sum_weight_total is not 8-byte aligned";
+    if (!bad && !n_touched && !max_weight && !sum_weight && !touched_total && !max_weight_total && !sum_weight_total && !views &&
+        !last_seen && !counts4_device)
+        bad = "nothing to write (every output is NULL)";
+    if (bad) return refuse("dgr_contribution_stats", bad);
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 0) {  // no Gaussians, no frame: only the counts
+        if (counts4_device) HIP_TRY(dgr::launch_contrib_clear(0, nullptr, nullptr, nullptr, counts4_device, st));
+        return DGR_OK;
+    }
+    char* sc = static_cast<char*>(scratch);
+    if (!n_touched) n_touched = reinterpret_cast<int*>(sc);
+    if (!max_weight) max_weight = reinterpret_cast<float*>(sc + contribution_plane(P, 4));
+    if (!sum_weight) sum_weight = reinterpret_cast<long long*>(sc + 2 * contribution_plane(P, 4));
+    const dgr::GeometryView geom = dgr::carve_geometry(const_cast<char*>(geometry_buffer), (int)P);
+    const dgr::ImageView img = dgr::carve_image(const_cast<char*>(image_buffer), width, height);
+    HIP_TRY(dgr::launch_contrib_clear(P, n_touched, max_weight, sum_weight, counts4_device, st));
+    dgr::ContribTilesArgs t{};
+    t.W = width, t.H = height, t.grid_x = dgr::tiles_x(width), t.grid_y = dgr::tiles_y(height);
+    t.sched = img.tile_sched, t.ranges = img.ranges, t.sched_flag = img.cursor + 3;
+    t.point_list = reinterpret_cast<const uint32_t*>(binning_buffer), t.rec = geom.rec, t.n_contrib = img.n_contrib;
+    t.n_touched = n_touched, t.max_weight_bits = reinterpret_cast<uint32_t*>(max_weight);
+    t.sum_weight = reinterpret_cast<unsigned long long*>(sum_weight);
+    HIP_TRY(dgr::launch_contrib_tiles(t, dgr::opt_alpha_mode(), st));
+    dgr::ContribFoldArgs f{};
+    f.P = P, f.sched_flag = img.cursor + 3, f.n_touched = n_touched, f.max_weight = max_weight, f.sum_weight = sum_weight;
+    f.min_pixels = p->min_pixels, f.weight_min = p->weight_min, f.frame_id = p->frame_id;
+    f.touched_total = touched_total, f.max_weight_total = max_weight_total, f.sum_weight_total = sum_weight_total;
+    f.views = views, f.last_seen = last_seen, f.counts = counts4_device;
+    if (touched_total || max_weight_total || sum_weight_total || views || last_seen || counts4_device) HIP_TRY(dgr::launch_contrib_fold(f, st));
     return DGR_OK;
 }
 

@@ -435,6 +435,39 @@ struct PgoArgs {
 size_t pgo_scratch_bytes(int K, int E);
 hipError_t launch_pgo_plan(int K, int E, const int* edges, void* scratch, hipStream_t stream);
 hipError_t launch_pgo_solve(const PgoArgs& args, void* scratch, hipStream_t stream);
+// per-Gaussian contribution statistics of a rendered view (contrib.hip; include/dgr_hip.h: dgr_contribution_stats): the clear of the
+// per-view arrays and counts[4], the replay of the forward's blend over the tiles, and the fold into counts and the running accumulators
+struct ContribTilesArgs {
+    int W, H, grid_x, grid_y;
+    const uint4* sched;    // as the blend kernels' (render_common.h: blend_slot)
+    const uint2* ranges;
+    const uint32_t* sched_flag;
+    const uint32_t* point_list;
+    const float4* rec;
+    const uint32_t* n_contrib;
+    int* n_touched;                  // [P], zero on entry
+    uint32_t* max_weight_bits;       // [P] float32 bits, zero on entry
+    unsigned long long* sum_weight;  // [P] Q32, zero on entry
+};
+struct ContribFoldArgs {
+    long P;
+    const uint32_t* sched_flag;  // the frame's blend flags (NULL: P == 0, no frame)
+    const int* n_touched;
+    const float* max_weight;
+    const long long* sum_weight;
+    int min_pixels;
+    float weight_min;
+    int frame_id;
+    long long* touched_total;   // the accumulators, [P] each, any of them NULL
+    float* max_weight_total;
+    long long* sum_weight_total;
+    int* views;
+    int* last_seen;
+    int* counts;  // [4] or NULL; cleared by launch_contrib_clear
+};
+hipError_t launch_contrib_clear(long P, int* n_touched, float* max_weight, long long* sum_weight, int* counts, hipStream_t stream);
+hipError_t launch_contrib_tiles(const ContribTilesArgs& a, int alpha_mode, hipStream_t stream);
+hipError_t launch_contrib_fold(const ContribFoldArgs& a, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -120,6 +120,13 @@ class PgoParams(C.Structure):  # dgr_pgo_params
 
 assert C.sizeof(PgoParams) == 32  # eight four-byte fields: the C layout
 
+
+class ContributionParams(C.Structure):  # dgr_contribution_params
+    _fields_ = [("min_pixels", _i), ("weight_min", _f), ("frame_id", _i)]
+
+
+assert C.sizeof(ContributionParams) == 12  # three four-byte fields: the C layout
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -175,6 +182,9 @@ _SIGS = {
     "dgr_pgo_scratch_bytes": (_sz, [_i, _i]),
     "dgr_pgo_plan": (_i, [_vp, _i, _i, _vp, _vp]),
     "dgr_pgo_solve": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, C.POINTER(PgoParams), _vp, _vp, _vp, _vp, _vp]),
+    "dgr_contribution_scratch_bytes": (_sz, [C.c_long]),
+    "dgr_contribution_stats": (_i, [_vp, C.c_long, _i, _i, _i, _vp, _vp, _vp, C.POINTER(ContributionParams), _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

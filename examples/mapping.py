@@ -37,10 +37,16 @@ poses get seeded rigid corrections and optim.transform_map moves every Gaussian,
 keyframe (optim.pose_corrections forms them from the old and new poses on the device).  In place and without a host read: it goes
 together with --graph and --fused, between replays.  The losses before and after are logged.
 
+--prune-unseen N (with --densify-every or --relocate-every) prunes by what the keyframes actually BLEND: every N iterations each
+keyframe of the window goes through slam.render_contributions into one ContributionAccumulator, and the Gaussians that fewer than
+--prune-min-views M keyframes observed (blended by at least one pixel: occluded and never-seen Gaussians, which get no gradient
+and so never lose their opacity) have their opacity logit set far below the pruning threshold; that iteration's densify_and_prune
+removes them, or its relocate_dead recycles them.  The count is logged.  Not together with --graph.
+
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
                              [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked] [--select K]
                              [--relocate-every N [--relocate-start K] [--position-noise] [--relocate-min-opacity 0.005]]
-                             [--loop-close-at N [--loop-close-seed S]]
+                             [--loop-close-at N [--loop-close-seed S]] [--prune-unseen N [--prune-min-views M]]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -139,7 +145,8 @@ class SeededMapModel(MapModel):
 def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, graph=False, fused=False, variant="light",
                  absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0, relocate_every=0,
                  position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0, loop_close_at=0,
-                 loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True, loop_close_pgo=False):
+                 loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True, loop_close_pgo=False, prune_unseen=0,
+                 prune_min_views=1):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -169,7 +176,13 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     loop_close_pgo=True: the drawn poses are the truth, and the poses the map follows are SOLVED for: slam.pose_graph_optimize gets
     the old poses with keyframe 0 set to its true pose and fixed, K - 1 chain edges and one loop edge K - 1 -> 0, each measured on
     the truth with slam.relative_pose; its result goes to pose_corrections and transform_map in place of the drawn poses (on the
-    device, between replays with graph=True).  `loop_closure` then also holds "solved" and "truth" ([K,4,4] each) and "pgo_stats"."""
+    device, between replays with graph=True).  `loop_closure` then also holds "solved" and "truth" ([K,4,4] each) and "pgo_stats".
+    prune_unseen=N (with densify_every or relocate_every; not with graph=True): every N iterations the window's keyframes are
+    rendered through slam.render_contributions into one accumulator and the Gaussians observed by fewer than `prune_min_views` of
+    them get an opacity logit far below the pruning threshold, ahead of that iteration's densify_and_prune / relocate_dead.  The
+    model's `unseen` attribute then lists each step's [Gaussians, unseen ones]."""
+    if prune_unseen and (graph or not (densify_every or relocate_every)):
+        raise ValueError("prune_unseen=N marks Gaussians for densify_and_prune or relocate_dead (give one of them), not with graph=True")
     from dgr_amd import light, slam
     from dgr_amd.optim import (SparseAdam, add_densification_stats, densify_and_prune, inject_position_noise, pose_corrections,
                                relocate_dead, seed_from_frame, transform_map)
@@ -335,6 +348,21 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             dead, live, moved, sources, most = result.counts.tolist()[:5]  # (the step's one host read)
             log(f"relocate: {dead} dead of {dead + live}, {moved} moved onto {sources} live Gaussians (at most {most} onto one)")
 
+    unseen_steps = []
+
+    def mark_unseen(step):
+        """What no keyframe of the window blends gets an opacity no pruning rule keeps (sigmoid(-15) = 3e-7; the thresholds are 0.005)."""
+        acc = slam.ContributionAccumulator(pc.get_xyz.shape[0], dev)
+        with torch.no_grad():
+            for c in cams[:n_live]:  # a window is a loop over its keyframes into one accumulator
+                slam.render_contributions(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt,
+                                          variant=variant, into=acc, frame_id=step)
+            unseen = ~acc.observed(min(prune_min_views, n_live))  # (a window that is still growing cannot ask for more views than it has)
+            pc._opacity.masked_fill_(unseen[:, None], -15.0)
+        unseen_steps.append([acc.P, int(unseen.sum())])  # (the step's one host read)
+        if log:
+            log(f"prune-unseen: {unseen_steps[-1][1]} of {acc.P} Gaussians blended by fewer than {min(prune_min_views, n_live)} of {n_live} keyframes")
+
     def rigid(rng, size):  # a rigid motion of about `size`: a rotation by that angle about a random axis, a translation of that length
         axis, shift = rng.standard_normal(3), rng.standard_normal(3)
         x, y, z = axis / np.linalg.norm(axis)
@@ -392,6 +420,8 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         if seed and n_live < keyframes and (i + 3) % join_every == 0:
             seed_keyframe(n_live)
         loss = run()
+        if prune_unseen and (i + 4) % prune_unseen == 0:
+            mark_unseen(i + 3)
         if densify_every and (i + 4) % densify_every == 0:
             densify()
         if relocate_every and (i + 4) % relocate_every == 0 and i + 3 >= relocate_start:
@@ -408,6 +438,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
         step.check()
     pc.window = window
     pc.relocations = [c.tolist()[:5] for c in relocations]
+    pc.unseen = unseen_steps
     if loop_close_at:
         pc.loop_closure = dict(before=float(closure["before"]), after=float(closure["after"]),
                                counts=None if closure["counts"] is None else closure["counts"].tolist())
@@ -465,6 +496,11 @@ def main():
     ap.add_argument("--pgo", action="store_true",
                     help="with --loop-close-at: the corrected poses are solved for on the device (slam.pose_graph_optimize over chain "
                          "edges and one loop edge measured on the drawn poses) instead of being taken as drawn")
+    ap.add_argument("--prune-unseen", type=int, default=0, metavar="N",
+                    help="every N iterations give the Gaussians that fewer than --prune-min-views keyframes of the window blend "
+                         "(slam.render_contributions) an opacity below the pruning threshold; needs --densify-every or "
+                         "--relocate-every, which then removes or recycles them; not together with --graph")
+    ap.add_argument("--prune-min-views", type=int, default=1, metavar="M", help="with --prune-unseen: the views a Gaussian needs (default 1)")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -488,6 +524,10 @@ def main():
         ap.error("--relocate-every N takes N >= 0, and --position-noise goes with it")
     if args.relocate_every and args.seed:
         ap.error("--relocate-every keeps a map of fixed size; --seed grows one (drop one of the two)")
+    if args.prune_unseen < 0 or args.prune_min_views < 1 or (args.prune_unseen and not (args.densify_every or args.relocate_every)):
+        ap.error("--prune-unseen N marks Gaussians for removal: give --densify-every or --relocate-every too (N >= 0, --prune-min-views >= 1)")
+    if args.prune_unseen and args.graph:
+        ap.error("--prune-unseen renders the window outside the recorded iteration and reads a count: drop --graph")
     if not 0.0 <= args.relocate_min_opacity < 1.0:
         ap.error("--relocate-min-opacity lies in [0, 1)")
     import torch as _torch
@@ -501,7 +541,11 @@ def main():
                                     seed=args.seed, masked=args.masked, select=args.select, relocate_every=args.relocate_every,
                                     position_noise=args.position_noise, relocate_min_opacity=args.relocate_min_opacity,
                                     relocate_start=args.relocate_start, loop_close_at=args.loop_close_at,
-                                    loop_close_seed=args.loop_close_seed, loop_close_pgo=args.pgo)
+                                    loop_close_seed=args.loop_close_seed, loop_close_pgo=args.pgo, prune_unseen=args.prune_unseen,
+                                    prune_min_views=args.prune_min_views)
+    if args.prune_unseen:
+        print(f"prune-unseen: {sum(u for _, u in pc.unseen)} Gaussians marked unseen in {len(pc.unseen)} steps "
+              f"(fewer than {args.prune_min_views} keyframes blended them)")
     if args.pgo:
         c = pc.loop_closure
         s = c["pgo_stats"]

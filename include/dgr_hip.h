@@ -836,6 +836,41 @@ int dgr_pgo_solve(void* stream, int n_poses, int n_edges, const float* poses_in,
                   const dgr_pgo_params* params, void* scratch, float* poses_out, float* chi2 /* or NULL */, double* stats,
                   int* flags);
 
+/* ---- per-Gaussian contribution statistics of a rendered view (csrc/contrib.hip) ----
+ * Which Gaussians did the pixels of a finished forward actually BLEND, and how much -- what radii > 0 (a frustum and rectangle
+ * test an occluded Gaussian passes) cannot say: MonoGS's n_touched, the largest / accumulated blend weight alpha T that RTG-SLAM,
+ * LightGaussian and Mini-Splatting rank by.  The call replays the blend of the view whose state the three buffers hold (light or
+ * full forward, one view; the buffers as the backward entry points take them, `R` as theirs: >= 0, the binning buffer is found
+ * from the capacity the forward recorded) under the calling thread's alpha_mode (0, 1 and 2 all supported), as for a backward.
+ *   A pair (pixel p, 1-based position k in the list of p's tile) is BLENDED iff k <= n_contrib[p], power <= 0 and
+ *   alpha = min(0.99, o G) >= 15/255 (the blend kernels' ALPHA_MIN, evaluated by their own functions).  Its weight is w = alpha T,
+ *   T the running product of (1 - alpha) over the pixel's earlier blended pairs in list order: the forward's bits.
+ *   Per Gaussian g of this view:  n_touched[g] int32 = number of blended pairs;  max_weight[g] float32 = largest w (0 if none);
+ *   sum_weight[g] int64 = sum of floor(w 2^32) (Q32 fixed point: * 2^-32 is the accumulated weight; an integer sum does not
+ *   depend on the order the atomics arrive in).  Each of the three may be NULL; it then lives in `scratch`.
+ *   The running accumulators [P], each of which may be NULL, receive this view in a last pass:  touched_total (int64) +=
+ *   n_touched;  max_weight_total (float32) = max;  sum_weight_total (int64) += sum_weight;  views (int32) += 1 and last_seen
+ *   (int32) = frame_id where the view OBSERVED g: n_touched >= min_pixels && max_weight >= weight_min.
+ *   counts4_device (device int[4], may be NULL) = {Gaussians with n_touched > 0, Gaussians observed, 1 if the frame's binning had
+ *   overflowed else 0, 0}.  An overflowed frame has empty lists: its per-view outputs are zero and it is NOT folded into the
+ *   accumulators (nor counted as observing anything).
+ * At most three launches (clear, tiles, fold), integer atomics only -- the same bits on every run --, nothing read on the host,
+ * capturable into a hipGraph.  scratch: dgr_contribution_scratch_bytes(P) bytes, 16-byte aligned; needed (non-NULL) when a
+ * per-view output is NULL.  P == 0 succeeds (the state buffers may then be NULL; counts4_device is cleared).  Refused before any
+ * device call: params NULL, P < 0 or above 2^28 - 1, width or height <= 0, R < 0, a NULL state buffer, negative min_pixels, NaN
+ * or negative weight_min, a scratch that is missing or misaligned, a misaligned output, nothing to write. */
+typedef struct dgr_contribution_params {
+    int min_pixels;   /* >= 0: blended pairs a view needs to have observed a Gaussian */
+    float weight_min; /* >= 0: ... and the largest weight it needs */
+    int frame_id;     /* what last_seen receives */
+} dgr_contribution_params;
+size_t dgr_contribution_scratch_bytes(long P);
+int dgr_contribution_stats(void* stream, long P, int width, int height, int R, const char* geometry_buffer,
+                           const char* binning_buffer, const char* image_buffer, const dgr_contribution_params* params,
+                           void* scratch, int* n_touched, float* max_weight, long long* sum_weight, long long* touched_total,
+                           float* max_weight_total, long long* sum_weight_total, int* views, int* last_seen,
+                           int* counts4_device);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
