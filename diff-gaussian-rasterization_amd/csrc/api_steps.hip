@@ -706,4 +706,85 @@ int dgr_contribution_stats(void* stream, long P, int width, int height, int R, c
     return DGR_OK;
 }
 
+// ---- TSDF fusion and mesh extraction (tsdf.hip)
+static const char* tsdf_grid_error(const dgr_tsdf_grid* g) {
+    if (!g) return "grid is NULL";
+    if (g->nx < 1 || g->ny < 1 || g->nz < 1) return "the grid's nx, ny and nz must be positive";
+    if ((unsigned long long)g->nx * (unsigned long long)g->ny >= (1ull << 31) ||
+        (unsigned long long)g->nx * (unsigned long long)g->ny * (unsigned long long)g->nz >= (1ull << 31))
+        return "the grid must hold fewer than 2^31 samples";
+    if (!(g->voxel_size > 0.0f) || !std::isfinite(g->voxel_size)) return "voxel_size must be finite and positive";
+    return nullptr;
+}
+int dgr_tsdf_integrate(void* stream, const dgr_tsdf_grid* grid, float* volume, float* color, int n_views, int width, int height,
+                       const float* depth, const float* image, const float* mask, const float* viewmatrices,
+                       const dgr_tsdf_params* params) {
+    const dgr_tsdf_params* p = params;
+    const char* bad = tsdf_grid_error(grid);
+    if (!bad && !p) bad = "params is NULL";
+    if (!bad && n_views < 1) bad = "n_views must be at least 1";
+    if (!bad && (width < 1 || height < 1 || (long long)width * height > (1ll << 30))) bad = "width and height must be positive (and width * height at most 2^30)";
+    if (!bad && !volume) bad = "volume is NULL";
+    if (!bad && !depth) bad = "depth is NULL";
+    if (!bad && !viewmatrices) bad = "viewmatrices is NULL";
+    if (!bad && ((color != nullptr) != (image != nullptr))) bad = "the colour volume and the colour images go together: one of them is NULL";
+    if (!bad && (!aligned_to(volume, 8) || !dgr::aligned16(color))) bad = "volume is not 8-byte aligned or color is not 16-byte aligned";
+    if (!bad && !(aligned_to(depth, 4) && aligned_to(image, 4) && aligned_to(mask, 4) && aligned_to(viewmatrices, 4)))
+        bad = "depth, image, mask or viewmatrices is not 4-byte aligned";
+    if (!bad && !(p->fx > 0.0f && p->fy > 0.0f && std::isfinite(p->fx) && std::isfinite(p->fy))) bad = "fx and fy must be finite and positive";
+    if (!bad && (!(p->truncation > 0.0f) || !std::isfinite(p->truncation))) bad = "truncation must be finite and positive";
+    if (bad) return refuse("dgr_tsdf_integrate", bad);
+    dgr::TsdfIntegrateArgs a{};
+    a.nx = grid->nx, a.ny = grid->ny, a.nz = grid->nz;
+    a.ox = grid->origin[0], a.oy = grid->origin[1], a.oz = grid->origin[2], a.voxel = grid->voxel_size;
+    a.volume = reinterpret_cast<float2*>(volume), a.color = reinterpret_cast<float4*>(color);
+    a.V = n_views, a.W = width, a.H = height, a.depth = depth, a.image = image, a.mask = mask, a.view = viewmatrices;
+    a.fx = p->fx, a.fy = p->fy, a.cx = p->cx, a.cy = p->cy, a.truncation = p->truncation, a.weight = p->weight;
+    a.max_weight = p->max_weight, a.depth_min = p->depth_min, a.depth_max = p->depth_max, a.near_z = p->near_z;
+    a.mask_threshold = p->mask_threshold;
+    HIP_TRY(dgr::launch_tsdf_integrate(a, (hipStream_t)stream));
+    return DGR_OK;
+}
+
+size_t dgr_mesh_scratch_bytes(const dgr_tsdf_grid* grid) {
+    return tsdf_grid_error(grid) ? 0 : dgr::mesh_scratch_bytes(grid->nx, grid->ny, grid->nz);
+}
+static dgr::MeshArgs mesh_args(const dgr_tsdf_grid* grid, const float* volume, const float* color, float min_weight) {
+    dgr::MeshArgs a{};
+    a.nx = grid->nx, a.ny = grid->ny, a.nz = grid->nz;
+    a.ox = grid->origin[0], a.oy = grid->origin[1], a.oz = grid->origin[2], a.voxel = grid->voxel_size;
+    a.volume = reinterpret_cast<const float2*>(volume), a.color = reinterpret_cast<const float4*>(color), a.min_weight = min_weight;
+    return a;
+}
+int dgr_mesh_plan(void* stream, const dgr_tsdf_grid* grid, const float* volume, float min_weight, int max_triangles, void* scratch,
+                  int* count, int* flags) {
+    const char* bad = tsdf_grid_error(grid);
+    if (!bad && !volume) bad = "volume is NULL";
+    if (!bad && !aligned_to(volume, 8)) bad = "volume is not 8-byte aligned";
+    if (!bad && std::isnan(min_weight)) bad = "min_weight is NaN";
+    if (!bad && max_triangles < 0) bad = "max_triangles is negative";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && (!count || !flags)) bad = "count or flags is NULL";
+    if (!bad && !(aligned_to(count, 4) && aligned_to(flags, 4))) bad = "count or flags is not 4-byte aligned";
+    if (bad) return refuse("dgr_mesh_plan", bad);
+    HIP_TRY(dgr::launch_mesh_plan(mesh_args(grid, volume, nullptr, min_weight), max_triangles, scratch, count, flags, (hipStream_t)stream));
+    return DGR_OK;
+}
+int dgr_mesh_emit(void* stream, const dgr_tsdf_grid* grid, const float* volume, const float* color, float min_weight,
+                  int max_triangles, const void* scratch, float* vertices, float* colors) {
+    const char* bad = tsdf_grid_error(grid);
+    if (!bad && !volume) bad = "volume is NULL";
+    if (!bad && (!aligned_to(volume, 8) || !dgr::aligned16(color))) bad = "volume is not 8-byte aligned or color is not 16-byte aligned";
+    if (!bad && std::isnan(min_weight)) bad = "min_weight is NaN";
+    if (!bad && max_triangles < 0) bad = "max_triangles is negative";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && max_triangles > 0 && !vertices) bad = "vertices is NULL";
+    if (!bad && colors && !color) bad = "colors asked for of a volume without colour";
+    if (!bad && !(aligned_to(vertices, 4) && aligned_to(colors, 4))) bad = "vertices or colors is not 4-byte aligned";
+    if (bad) return refuse("dgr_mesh_emit", bad);
+    HIP_TRY(dgr::launch_mesh_emit(mesh_args(grid, volume, colors ? color : nullptr, min_weight), max_triangles, scratch, vertices, colors,
+                                  (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

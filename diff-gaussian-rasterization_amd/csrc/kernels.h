@@ -468,6 +468,34 @@ struct ContribFoldArgs {
 hipError_t launch_contrib_clear(long P, int* n_touched, float* max_weight, long long* sum_weight, int* counts, hipStream_t stream);
 hipError_t launch_contrib_tiles(const ContribTilesArgs& a, int alpha_mode, hipStream_t stream);
 hipError_t launch_contrib_fold(const ContribFoldArgs& a, hipStream_t stream);
+// TSDF fusion of rendered views and marching-tetrahedra extraction (tsdf.hip; include/dgr_hip.h: dgr_tsdf_integrate, dgr_mesh_plan,
+// dgr_mesh_emit): one integrate launch for any number of views; count, scan and emit of the mesh
+struct TsdfIntegrateArgs {
+    int nx, ny, nz;
+    float ox, oy, oz, voxel;
+    float2* volume;  // [nz, ny, nx] (tsdf, weight)
+    float4* color;   // [nz, ny, nx] (r, g, b, 0) or NULL
+    int V, W, H;
+    const float* depth;  // [V, H, W]
+    const float* image;  // [V, 3, H, W] or NULL (with color)
+    const float* mask;   // [V, H, W] or NULL
+    const float* view;   // [V, 16] W2C^T
+    float fx, fy, cx, cy, truncation, weight, max_weight, depth_min, depth_max, near_z, mask_threshold;
+    unsigned bricks_x, bricks_y;  // filled by the launcher
+};
+hipError_t launch_tsdf_integrate(const TsdfIntegrateArgs& args, hipStream_t stream);
+struct MeshArgs {
+    int nx, ny, nz;
+    float ox, oy, oz, voxel;
+    const float2* volume;
+    const float4* color;  // or NULL
+    float min_weight;
+    size_t cells;  // filled by the launchers
+};
+size_t mesh_scratch_bytes(int nx, int ny, int nz);
+hipError_t launch_mesh_plan(const MeshArgs& args, int max_triangles, void* scratch, int* count, int* flags, hipStream_t stream);
+hipError_t launch_mesh_emit(const MeshArgs& args, int max_triangles, const void* scratch, float* vertices, float* colors,
+                            hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

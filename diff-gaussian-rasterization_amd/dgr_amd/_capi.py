@@ -127,6 +127,21 @@ class ContributionParams(C.Structure):  # dgr_contribution_params
 
 assert C.sizeof(ContributionParams) == 12  # three four-byte fields: the C layout
 
+
+class TsdfGrid(C.Structure):  # dgr_tsdf_grid
+    _fields_ = [("nx", _i), ("ny", _i), ("nz", _i), ("origin", _f * 3), ("voxel_size", _f)]
+
+
+assert C.sizeof(TsdfGrid) == 28  # seven four-byte fields: the C layout
+
+
+class TsdfParams(C.Structure):  # dgr_tsdf_params
+    _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("truncation", _f), ("weight", _f), ("max_weight", _f),
+                ("depth_min", _f), ("depth_max", _f), ("near_z", _f), ("mask_threshold", _f)]
+
+
+assert C.sizeof(TsdfParams) == 44  # eleven four-byte fields: the C layout
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -185,6 +200,10 @@ _SIGS = {
     "dgr_contribution_scratch_bytes": (_sz, [C.c_long]),
     "dgr_contribution_stats": (_i, [_vp, C.c_long, _i, _i, _i, _vp, _vp, _vp, C.POINTER(ContributionParams), _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp]),
+    "dgr_tsdf_integrate": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.POINTER(TsdfParams)]),
+    "dgr_mesh_scratch_bytes": (_sz, [C.POINTER(TsdfGrid)]),
+    "dgr_mesh_plan": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _f, _i, _vp, _vp, _vp]),
+    "dgr_mesh_emit": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, _f, _i, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -43,10 +43,17 @@ keyframe of the window goes through slam.render_contributions into one Contribut
 and so never lose their opacity) have their opacity logit set far below the pruning threshold; that iteration's densify_and_prune
 removes them, or its relocate_dead recycles them.  The count is logged.  Not together with --graph.
 
+--tsdf VOXEL hands the run's result over as a surface: after the last iteration the window's keyframes are rendered once more,
+their depth and colour are fused into a truncated signed distance volume of that voxel size around the map
+(slam.tsdf_integrate: every keyframe in ONE pass over the volume, mask_image = the render's opacity_map) and the zero level is
+extracted by marching tetrahedra (slam.extract_mesh); one line reports the volume, the triangles and their area.
+--mesh-out PATH writes that mesh as an ASCII PLY (from the host, with numpy).
+
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
                              [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked] [--select K]
                              [--relocate-every N [--relocate-start K] [--position-noise] [--relocate-min-opacity 0.005]]
                              [--loop-close-at N [--loop-close-seed S]] [--prune-unseen N [--prune-min-views M]]
+                             [--tsdf VOXEL [--mesh-out PATH]]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -146,7 +153,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
                  absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0, relocate_every=0,
                  position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0, loop_close_at=0,
                  loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True, loop_close_pgo=False, prune_unseen=0,
-                 prune_min_views=1):
+                 prune_min_views=1, tsdf=0.0, mesh_out=None):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -180,7 +187,15 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     prune_unseen=N (with densify_every or relocate_every; not with graph=True): every N iterations the window's keyframes are
     rendered through slam.render_contributions into one accumulator and the Gaussians observed by fewer than `prune_min_views` of
     them get an opacity logit far below the pruning threshold, ahead of that iteration's densify_and_prune / relocate_dead.  The
-    model's `unseen` attribute then lists each step's [Gaussians, unseen ones]."""
+    model's `unseen` attribute then lists each step's [Gaussians, unseen ones].
+    tsdf=VOXEL: after the last iteration the window's keyframes are rendered once more and fused into a TSDF volume of that voxel
+    size around the map (slam.tsdf_integrate, one call for all of them, mask_image=opacity_map), and slam.extract_mesh gives its
+    zero level; the model's `tsdf` attribute then holds dims, triangles, area and the mesh.  mesh_out=PATH (with tsdf) writes the
+    mesh as an ASCII PLY."""
+    if mesh_out and not tsdf:
+        raise ValueError("mesh_out=PATH writes the mesh that tsdf=VOXEL extracts: give that too")
+    if tsdf < 0 or tsdf != tsdf:
+        raise ValueError("tsdf=VOXEL takes a voxel size > 0 (0: no fusion)")
     if prune_unseen and (graph or not (densify_every or relocate_every)):
         raise ValueError("prune_unseen=N marks Gaussians for densify_and_prune or relocate_dead (give one of them), not with graph=True")
     from dgr_amd import light, slam
@@ -436,6 +451,10 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     dt = (time.perf_counter() - t0) / max(iters - 3, 1)
     if graph:
         step.check()
+    if tsdf:
+        pc.tsdf = fuse_window(slam, pc, cams[:max(n_live, 1)], bg, gt, kw, W, H, s.tanfovx, s.tanfovy, float(tsdf), mesh_out)
+        if log:
+            log(tsdf_line(pc.tsdf))
     pc.window = window
     pc.relocations = [c.tolist()[:5] for c in relocations]
     pc.unseen = unseen_steps
@@ -448,6 +467,48 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             log(f"loop closure after iteration {loop_close_at}: loss {pc.loop_closure['before']:.4e} before, "
                 f"{pc.loop_closure['after']:.4e} after; counts {pc.loop_closure['counts']}")
     return (first, float(loss)), pc, dt
+
+
+def fuse_window(slam, pc, cams, bg, gt, kw, W, H, tanfovx, tanfovy, voxel, mesh_out=None):
+    """The map's surface: the keyframes `cams` rendered once more, fused into a TSDF volume of voxel size `voxel` around the map in
+    one call and extracted.  Returns dict(dims, triangles, area, mesh)."""
+    with torch.no_grad():
+        outs = [slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt, **kw) for c in cams]
+        alpha = torch.stack([o["opacity_map"].reshape(H, W) for o in outs])
+        # the rasterizer's depth is alpha-weighted: the sensor's form is depth / alpha (where the map covers the pixel; 0 = a hole)
+        depth = torch.stack([o["depth"].reshape(H, W) for o in outs])
+        depth = torch.where(alpha > 0.5, depth / alpha.clamp_min(1e-6), torch.zeros_like(depth))
+        color = torch.stack([o["render"] for o in outs]).clamp(0.0, 1.0)
+        views = torch.stack([c["viewmatrix"] for c in cams])
+        # around the scene: the map's positions without their outermost hundredth, a truncation's width more (one host read)
+        xyz = pc.get_xyz.detach()
+        q = torch.quantile(xyz[::max(1, xyz.shape[0] // 100000)], torch.tensor([0.01, 0.99], device=xyz.device), dim=0).tolist()
+        pad = 4.0 * voxel
+        vol = slam.TsdfVolume.from_bounds([v - pad for v in q[0]], [v + pad for v in q[1]], voxel, device=xyz.device)
+        slam.tsdf_integrate(vol, depth, views, W / (2.0 * tanfovx), H / (2.0 * tanfovy), (W - 1) / 2.0, (H - 1) / 2.0, color=color,
+                            mask_image=alpha)
+        mesh = slam.extract_mesh(vol)
+        tri = mesh.vertices.reshape(-1, 3, 3).double()
+        area = float(0.5 * torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]).norm(dim=1).sum())
+    if mesh_out:
+        write_ply(mesh_out, mesh.vertices.cpu().numpy(), mesh.colors.cpu().numpy())
+    return dict(dims=vol.dims, triangles=mesh.vertices.shape[0] // 3, area=area, mesh=mesh)
+
+
+def tsdf_line(t):
+    return f"tsdf: {t['dims'][0]}x{t['dims'][1]}x{t['dims'][2]} voxels, {t['triangles']} triangles, area {t['area']:.4f}"
+
+
+def write_ply(path, vertices, colors):
+    """an unindexed triangle list [3 T, 3] with colours in [0, 1] as an ASCII PLY"""
+    n = len(vertices)
+    rgb = np.clip(np.rint(colors * 255.0), 0, 255).astype(np.int64)
+    with open(path, "w") as f:
+        f.write(f"ply\nformat ascii 1.0\nelement vertex {n}\nproperty float x\nproperty float y\nproperty float z\n"
+                f"property uchar red\nproperty uchar green\nproperty uchar blue\nelement face {n // 3}\n"
+                "property list uchar int vertex_indices\nend_header\n")
+        np.savetxt(f, np.concatenate([vertices.astype(np.float64), rgb], axis=1), fmt="%.7g %.7g %.7g %d %d %d")
+        np.savetxt(f, np.concatenate([np.full((n // 3, 1), 3), np.arange(n).reshape(-1, 3)], axis=1), fmt="%d")
 
 
 def main():
@@ -501,6 +562,10 @@ def main():
                          "(slam.render_contributions) an opacity below the pruning threshold; needs --densify-every or "
                          "--relocate-every, which then removes or recycles them; not together with --graph")
     ap.add_argument("--prune-min-views", type=int, default=1, metavar="M", help="with --prune-unseen: the views a Gaussian needs (default 1)")
+    ap.add_argument("--tsdf", type=float, default=0.0, metavar="VOXEL",
+                    help="after the last iteration fuse the window's rendered keyframes into a TSDF volume of this voxel size around "
+                         "the map (slam.tsdf_integrate) and extract its surface (slam.extract_mesh); 0 (default): off")
+    ap.add_argument("--mesh-out", default=None, metavar="PATH", help="with --tsdf: write the mesh as an ASCII PLY")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -528,6 +593,8 @@ def main():
         ap.error("--prune-unseen N marks Gaussians for removal: give --densify-every or --relocate-every too (N >= 0, --prune-min-views >= 1)")
     if args.prune_unseen and args.graph:
         ap.error("--prune-unseen renders the window outside the recorded iteration and reads a count: drop --graph")
+    if args.tsdf < 0 or (args.mesh_out and not args.tsdf):
+        ap.error("--tsdf VOXEL takes a voxel size > 0, and --mesh-out PATH writes its mesh: give --tsdf too")
     if not 0.0 <= args.relocate_min_opacity < 1.0:
         ap.error("--relocate-min-opacity lies in [0, 1)")
     import torch as _torch
@@ -542,7 +609,9 @@ def main():
                                     position_noise=args.position_noise, relocate_min_opacity=args.relocate_min_opacity,
                                     relocate_start=args.relocate_start, loop_close_at=args.loop_close_at,
                                     loop_close_seed=args.loop_close_seed, loop_close_pgo=args.pgo, prune_unseen=args.prune_unseen,
-                                    prune_min_views=args.prune_min_views)
+                                    prune_min_views=args.prune_min_views, tsdf=args.tsdf, mesh_out=args.mesh_out)
+    if args.tsdf and args.graph:  # (otherwise the loop has logged it)
+        print(tsdf_line(pc.tsdf))
     if args.prune_unseen:
         print(f"prune-unseen: {sum(u for _, u in pc.unseen)} Gaussians marked unseen in {len(pc.unseen)} steps "
               f"(fewer than {args.prune_min_views} keyframes blended them)")

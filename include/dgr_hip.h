@@ -871,6 +871,66 @@ int dgr_contribution_stats(void* stream, long P, int width, int height, int R, c
                            float* max_weight_total, long long* sum_weight_total, int* views, int* last_seen,
                            int* counts4_device);
 
+/* ---- TSDF fusion of rendered views and mesh extraction (csrc/tsdf.hip) ----
+ * The surface a dense RGB-D SLAM run hands over: depth and colour rendered (or measured) at the keyframe poses, fused into a
+ * truncated signed distance volume, and the zero level of that volume as a triangle mesh.
+ * The volume: a dense lattice of nx x ny x nz samples, sample (ix, iy, iz) at origin + voxel_size (ix, iy, iz), x the fastest index.
+ *   volume float32 [nz, ny, nx, 2] = (tsdf in [-1, 1], weight >= 0), 8-byte aligned; color float32 [nz, ny, nx, 4] = (r, g, b, 0),
+ *   16-byte aligned, or NULL.  Plain memory the caller owns; all zero = empty.  nx ny nz < 2^31.
+ * dgr_tsdf_integrate: n_views >= 1 views in ONE launch; every sample is read once and written at most once per call -- not at
+ *   all when no view updated it -- whatever n_views is.  depth [n_views, height, width]; image [n_views, 3, height, width] or NULL
+ *   (with color: both or neither); mask [n_views, height, width] or NULL; viewmatrices [n_views, 16] = W2C^T; pixel (x, y) at depth
+ *   d is the camera point ((x - cx) / fx d, (y - cy) / fy d, d) (dgr_keyframe_overlap's convention).
+ *   Per sample p_w and per view, in the order given:  p_c = W2C p_w, z = p_c.z, skip unless z > near_z;  u = fx x / z + cx,
+ *   v = fy y / z + cy, the nearest pixel (floor(u + 0.5), floor(v + 0.5)), skip unless inside the image;  d = depth there, skip
+ *   unless depth_min < d < depth_max (a NaN fails) and skip if mask there <= mask_threshold;  sdf = d - z (projective), skip if
+ *   sdf < -truncation;  t = min(1, sdf / truncation);  tsdf = (tsdf w + t weight) / (w + weight), the colour likewise, then
+ *   w = min(w + weight, max_weight).
+ *   One thread owns a sample and applies the views in index order: no atomics, the same bits on every run, V views in one call
+ *   equal the same views in V calls bit for bit.  Nothing is read on the host and nothing allocated: capturable into a hipGraph.
+ *   The values of depth, image, mask and the poses are not validated: a NaN ends in a skipped update or a garbage value, never
+ *   in an out-of-range read.
+ * dgr_mesh_plan / dgr_mesh_emit: marching tetrahedra on Kuhn's split of every cell (the cube of 8 neighbouring samples, corners
+ *   numbered by bits x = 1, y = 2, z = 4) into the six tetrahedra {0, a, a|b, 7}, (a, b) = (1,2), (1,4), (2,1), (2,4), (4,1), (4,2)
+ *   in this order.  A cell is valid when all 8 weights are >= min_weight; a sample is inside when tsdf < 0 (an exact 0 is
+ *   outside).  A vertex on the edge (A, B), A the corner with the smaller number, is p_A + t (p_B - p_A), t = v_A / (v_A - v_B),
+ *   so every cell that shares the edge writes the same bits; colours are interpolated with the same t.  A tetrahedron with one
+ *   corner apart gives a triangle, two and two a quadrilateral: its crossings in cyclic order, normal from the inside (negative)
+ *   corners to the outside ones, started at the edge with the smallest (A, B), fanned from there: (e0, e1, e2), (e0, e2, e3).
+ *   Degenerate triangles are kept.  Output: an unindexed list, vertices float32 [3 T, 3] and colors float32 [3 T, 3], ordered
+ *   by linear cell index (x fastest, over the (nx-1)(ny-1)(nz-1) cells), then tetrahedron, then triangle.
+ *   plan: two launches (count per 256-cell block, a one-workgroup scan).  count [1] int32 = the triangles needed (saturated at
+ *   2^31 - 1), flags [1] int32: bit 0 = more than max_triangles.  emit: one launch; writes the first min(count, max_triangles)
+ *   triangles and nothing behind them; the same volume, min_weight and scratch as the plan.  With a caller-given capacity nothing
+ *   is read on the host: capturable.  scratch: dgr_mesh_scratch_bytes(grid) bytes (0 for a grid it refuses), 16-byte aligned.
+ * Refused with DGR_ERR_BAD_ARGUMENT and a message before any device call: a NULL grid or params; non-positive nx, ny, nz; 2^31
+ *   samples or more; a voxel_size, fx, fy or truncation that is not finite and positive; n_views < 1; width or height < 1; a NULL
+ *   volume, depth or viewmatrices; color without image or image without color; a misaligned pointer; (mesh) a NaN min_weight, a
+ *   negative max_triangles, a NULL or misaligned scratch, a NULL count or flags, a NULL vertices with max_triangles > 0, colors of
+ *   a volume without color. */
+typedef struct dgr_tsdf_grid {
+    int nx, ny, nz;
+    float origin[3];
+    float voxel_size;
+} dgr_tsdf_grid;
+typedef struct dgr_tsdf_params {
+    float fx, fy, cx, cy;
+    float truncation;     /* > 0 */
+    float weight;         /* what a view adds to a sample's weight */
+    float max_weight;     /* the weight's cap; INFINITY = none */
+    float depth_min, depth_max;
+    float near_z;
+    float mask_threshold; /* a pixel with mask <= this is not fused */
+} dgr_tsdf_params;
+int dgr_tsdf_integrate(void* stream, const dgr_tsdf_grid* grid, float* volume, float* color /* or NULL */, int n_views, int width,
+                       int height, const float* depth, const float* image /* or NULL */, const float* mask /* or NULL */,
+                       const float* viewmatrices, const dgr_tsdf_params* params);
+size_t dgr_mesh_scratch_bytes(const dgr_tsdf_grid* grid);
+int dgr_mesh_plan(void* stream, const dgr_tsdf_grid* grid, const float* volume, float min_weight, int max_triangles, void* scratch,
+                  int* count, int* flags);
+int dgr_mesh_emit(void* stream, const dgr_tsdf_grid* grid, const float* volume, const float* color /* or NULL */, float min_weight,
+                  int max_triangles, const void* scratch, float* vertices, float* colors /* or NULL */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
