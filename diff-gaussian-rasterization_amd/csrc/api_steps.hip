@@ -787,4 +787,53 @@ int dgr_mesh_emit(void* stream, const dgr_tsdf_grid* grid, const float* volume, 
     return DGR_OK;
 }
 
+// ---- ray-casting the TSDF volume (raycast.hip)
+size_t dgr_tsdf_brick_bytes(const dgr_tsdf_grid* grid) {
+    return tsdf_grid_error(grid) ? 0 : dgr::tsdf_brick_count(grid->nx, grid->ny, grid->nz);
+}
+int dgr_tsdf_bricks(void* stream, const dgr_tsdf_grid* grid, const float* volume, float min_weight, unsigned char* bricks) {
+    const char* bad = tsdf_grid_error(grid);
+    if (!bad && !volume) bad = "volume is NULL";
+    if (!bad && !aligned_to(volume, 8)) bad = "volume is not 8-byte aligned";
+    if (!bad && std::isnan(min_weight)) bad = "min_weight is NaN";
+    if (!bad && !bricks && dgr::tsdf_brick_count(grid->nx, grid->ny, grid->nz) > 0) bad = "bricks is NULL";
+    if (bad) return refuse("dgr_tsdf_bricks", bad);
+    dgr::BricksArgs a{};
+    a.nx = grid->nx, a.ny = grid->ny, a.nz = grid->nz;
+    a.volume = reinterpret_cast<const float2*>(volume), a.min_weight = min_weight, a.bricks = bricks;
+    HIP_TRY(dgr::launch_tsdf_bricks(a, (hipStream_t)stream));
+    return DGR_OK;
+}
+int dgr_tsdf_raycast(void* stream, const dgr_tsdf_grid* grid, const float* volume, const float* color, const unsigned char* bricks,
+                     int n_views, int width, int height, const float* viewmatrices, const dgr_raycast_params* params, float* depth,
+                     float* vnmap, float* color_out, unsigned char* flags) {
+    const dgr_raycast_params* p = params;
+    const char* bad = tsdf_grid_error(grid);
+    if (!bad && !p) bad = "params is NULL";
+    if (!bad && (n_views < 1 || n_views > 65535)) bad = "n_views must be at least 1 (and at most 65535)";
+    if (!bad && (width < 1 || height < 1 || (long long)width * height > (1ll << 30))) bad = "width and height must be positive (and width * height at most 2^30)";
+    if (!bad && !volume) bad = "volume is NULL";
+    if (!bad && !viewmatrices) bad = "viewmatrices is NULL";
+    if (!bad && !depth && !vnmap && !color_out && !flags) bad = "no output given: depth, vnmap, color_out and flags are all NULL";
+    if (!bad && color_out && !color) bad = "color_out asked for of a volume without colour";
+    if (!bad && (!aligned_to(volume, 8) || !dgr::aligned16(color))) bad = "volume is not 8-byte aligned or color is not 16-byte aligned";
+    if (!bad && !dgr::aligned16(vnmap)) bad = "vnmap is not 16-byte aligned";
+    if (!bad && !(aligned_to(viewmatrices, 4) && aligned_to(depth, 4) && aligned_to(color_out, 4))) bad = "viewmatrices, depth or color_out is not 4-byte aligned";
+    if (!bad && !(p->fx > 0.0f && p->fy > 0.0f && std::isfinite(p->fx) && std::isfinite(p->fy))) bad = "fx and fy must be finite and positive";
+    if (!bad && (!(p->step > 0.0f) || !std::isfinite(p->step))) bad = "step must be finite and positive";
+    if (!bad && std::isnan(p->min_weight)) bad = "min_weight is NaN";
+    if (!bad && (!std::isfinite(p->depth_min) || std::isnan(p->depth_max))) bad = "depth_min must be finite and depth_max not NaN";
+    if (bad) return refuse("dgr_tsdf_raycast", bad);
+    dgr::RaycastArgs a{};
+    a.nx = grid->nx, a.ny = grid->ny, a.nz = grid->nz;
+    a.ox = grid->origin[0], a.oy = grid->origin[1], a.oz = grid->origin[2], a.voxel = grid->voxel_size;
+    a.volume = reinterpret_cast<const float2*>(volume), a.color = reinterpret_cast<const float4*>(color), a.bricks = bricks;
+    a.V = n_views, a.W = width, a.H = height, a.view = viewmatrices;
+    a.fx = p->fx, a.fy = p->fy, a.cx = p->cx, a.cy = p->cy, a.depth_min = p->depth_min, a.depth_max = p->depth_max;
+    a.step = p->step, a.min_weight = p->min_weight;
+    a.depth = depth, a.vnmap = reinterpret_cast<float4*>(vnmap), a.color_out = color_out, a.flags = flags;
+    HIP_TRY(dgr::launch_tsdf_raycast(a, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

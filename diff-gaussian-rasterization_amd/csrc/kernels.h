@@ -496,6 +496,32 @@ size_t mesh_scratch_bytes(int nx, int ny, int nz);
 hipError_t launch_mesh_plan(const MeshArgs& args, int max_triangles, void* scratch, int* count, int* flags, hipStream_t stream);
 hipError_t launch_mesh_emit(const MeshArgs& args, int max_triangles, const void* scratch, float* vertices, float* colors,
                             hipStream_t stream);
+// ray-casting the TSDF volume (raycast.hip; include/dgr_hip.h: dgr_tsdf_bricks, dgr_tsdf_raycast): the map of live bricks in one
+// launch, the march of V views in one launch
+struct BricksArgs {
+    int nx, ny, nz;
+    const float2* volume;
+    float min_weight;
+    unsigned char* bricks;  // [ceil((nz-1)/8), ceil((ny-1)/8), ceil((nx-1)/8)]
+    unsigned bnx, bny;      // filled by the launcher
+};
+size_t tsdf_brick_count(int nx, int ny, int nz);
+hipError_t launch_tsdf_bricks(const BricksArgs& args, hipStream_t stream);
+struct RaycastArgs {
+    int nx, ny, nz;
+    float ox, oy, oz, voxel;
+    const float2* volume;
+    const float4* color;           // or NULL
+    const unsigned char* bricks;   // or NULL
+    int V, W, H;
+    const float* view;             // [V, 16] W2C^T
+    float fx, fy, cx, cy, depth_min, depth_max, step, min_weight;
+    float* depth;                  // [V, H, W] or NULL
+    float4* vnmap;                 // [V, H, W] (n_c, z) or NULL
+    float* color_out;              // [V, 3, H, W] or NULL
+    unsigned char* flags;          // [V, H, W] or NULL
+};
+hipError_t launch_tsdf_raycast(const RaycastArgs& args, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -142,6 +142,13 @@ class TsdfParams(C.Structure):  # dgr_tsdf_params
 
 assert C.sizeof(TsdfParams) == 44  # eleven four-byte fields: the C layout
 
+
+class RaycastParams(C.Structure):  # dgr_raycast_params
+    _fields_ = [("fx", _f), ("fy", _f), ("cx", _f), ("cy", _f), ("depth_min", _f), ("depth_max", _f), ("step", _f), ("min_weight", _f)]
+
+
+assert C.sizeof(RaycastParams) == 32  # eight four-byte fields: the C layout
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -204,6 +211,9 @@ _SIGS = {
     "dgr_mesh_scratch_bytes": (_sz, [C.POINTER(TsdfGrid)]),
     "dgr_mesh_plan": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _f, _i, _vp, _vp, _vp]),
     "dgr_mesh_emit": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, _f, _i, _vp, _vp, _vp]),
+    "dgr_tsdf_brick_bytes": (_sz, [C.POINTER(TsdfGrid)]),
+    "dgr_tsdf_bricks": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _f, _vp]),
+    "dgr_tsdf_raycast": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, _vp, _i, _i, _i, _vp, C.POINTER(RaycastParams), _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -1,7 +1,8 @@
-"""TSDF fusion of rendered views and mesh extraction on the device (C ABI: dgr_tsdf_integrate, dgr_mesh_plan, dgr_mesh_emit): the
-surface a dense RGB-D SLAM run hands over at the end -- what CG-SLAM, SplaTAM, MonoGS and the Point-SLAM family get from Open3D
-on the host: depth and colour rendered at the keyframe poses, fused into a truncated signed distance volume, and its zero level
-as a triangle mesh (marching tetrahedra)."""
+"""TSDF fusion of rendered views, mesh extraction and ray-casting on the device (C ABI: dgr_tsdf_integrate, dgr_mesh_plan,
+dgr_mesh_emit, dgr_tsdf_bricks, dgr_tsdf_raycast): the surface a dense RGB-D SLAM run hands over at the end -- what CG-SLAM,
+SplaTAM, MonoGS and the Point-SLAM family get from Open3D on the host: depth and colour rendered at the keyframe poses, fused
+into a truncated signed distance volume, its zero level as a triangle mesh (marching tetrahedra), and the volume seen from any
+pose (depth, normals, colour: KinectFusion's model frame)."""
 import math as _math
 from typing import NamedTuple as _NamedTuple
 
@@ -160,3 +161,108 @@ def extract_mesh(vol, *, min_weight=1.0, max_triangles=None):
         colors = torch.empty((3 * cap, 3), dtype=torch.float32, device=dev) if vol.color is not None else None
         abi.call("dgr_mesh_emit", grid, p(vol.volume), p(vol.color), min_weight, cap, p(scratch), p(vertices), p(colors))
     return TsdfMesh(vertices, colors, count, flags)
+
+
+class TsdfRaycast(_NamedTuple):
+    """A ray-cast of the volume: `depth` float32 [V, H, W] (0 without a hit), `vnmap` float32 [V, H, W, 4] = (normal in the camera
+    frame, depth), what depth_normals writes and icp_step reads, or None; `color` float32 [V, 3, H, W] or None; `flags` uint8
+    [V, H, W] or None: bit 0 a hit, bit 1 the ray ended unseen (inside the surface or behind unmeasured space), bit 2 a hit
+    without a normal.  With a [4, 4] pose the leading V is dropped."""
+    depth: torch.Tensor
+    vnmap: torch.Tensor
+    color: torch.Tensor
+    flags: torch.Tensor
+
+
+def _min_weight(what, min_weight):
+    min_weight = float(min_weight)
+    if min_weight != min_weight:
+        raise ValueError(f"{what}: min_weight must not be NaN")
+    return min_weight
+
+
+def _brick_shape(dims):
+    return tuple(-(-(n - 1) // 8) for n in reversed(dims))
+
+
+def tsdf_bricks(vol, *, min_weight=1.0):
+    """The map of live bricks that lets tsdf_raycast jump over empty space: uint8 [ceil((Nz-1)/8), ceil((Ny-1)/8), ceil((Nx-1)/8)],
+    1 iff the brick of 8 x 8 x 8 cells holds a cell whose 8 weights are >= `min_weight` and that has a corner with tsdf <= 0
+    (only such a cell can end a ray).  One launch, exact, no atomics, capturable.  Build it again after the volume changed."""
+    what = "tsdf_bricks"
+    if not isinstance(vol, TsdfVolume):
+        raise ValueError(f"{what}: vol must be a TsdfVolume, not {type(vol).__name__}")
+    min_weight = _min_weight(what, min_weight)
+    dev = vol.device
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: the volume must live on the GPU (there is no CPU fallback)")
+    bricks = torch.empty(_brick_shape(vol.dims), dtype=torch.uint8, device=dev)
+    if _capi.load().dgr_tsdf_brick_bytes(vol.grid()) != bricks.numel():
+        raise ValueError(f"{what}: the library refuses a grid of {vol.dims} samples")
+    _capi.call("dgr_tsdf_bricks", dev, vol.grid(), _capi.ptr(vol.volume), min_weight, _capi.ptr(bricks))
+    return bricks
+
+
+def tsdf_raycast(vol, viewmatrices, fx, fy, cx, cy, H, W, *, depth_range=(0.05, _INF), step=None, min_weight=1.0, bricks="build",
+                 normals=True, color=None, return_flags=False):
+    """The volume seen from V poses in one launch, one lane per ray: `viewmatrices` [V, 4, 4] = W2C^T (or [4, 4]: the results then
+    lose their leading V), pixel (x, y) at depth z = the camera point ((x - cx) / fx z, (y - cy) / fy z, z), as in tsdf_integrate.
+    The ray is sampled at z_k = depth_range[0] + k step < depth_range[1] (`step` in metres of depth, None = half a voxel); a
+    sample counts when its cell's 8 weights are >= `min_weight`, and its value is the trilinear interpolant.  The first sample
+    with a value <= 0 ends the ray: a hit when the sample before it counts and is > 0 (depth by linear interpolation between the
+    two, normal from central differences of the interpolant a voxel either side, turned to the camera, colour by trilinear
+    interpolation), otherwise no depth (flags bit 1).  include/dgr_hip.h: dgr_tsdf_raycast.
+    `bricks`: "build" makes the map of live bricks first (tsdf_bricks: two launches in all), a tensor from tsdf_bricks reuses one
+    (same volume, same min_weight), None marches every sample; the results are the same bits either way.  `normals=False` leaves
+    vnmap out, `color` (None: as the volume has one) the colour, `return_flags` adds the flags.  Nothing is read on the host:
+    capturable.  Returns TsdfRaycast(depth, vnmap, color, flags)."""
+    what = "tsdf_raycast"
+    if not isinstance(vol, TsdfVolume):
+        raise ValueError(f"{what}: vol must be a TsdfVolume, not {type(vol).__name__}")
+    if not isinstance(viewmatrices, torch.Tensor):
+        raise ValueError(f"{what}: viewmatrices must be a tensor, not {type(viewmatrices).__name__}")
+    single = viewmatrices.dim() == 2
+    if single:
+        viewmatrices = viewmatrices[None]
+    if viewmatrices.dim() != 3 or viewmatrices.size(0) < 1:
+        raise ValueError(f"{what}: viewmatrices must be [V, 4, 4] with V >= 1 or [4, 4], not {list(viewmatrices.shape)}")
+    V, H, W = int(viewmatrices.size(0)), int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: H and W must be positive, not {(H, W)}")
+    dev = vol.device
+    viewmatrices = _image(what, "viewmatrices", viewmatrices, (V, 4, 4), dev)
+    fx, fy, cx, cy = float(fx), float(fy), float(cx), float(cy)
+    if not (_math.isfinite(fx) and _math.isfinite(fy) and fx > 0.0 and fy > 0.0):
+        raise ValueError(f"{what}: fx and fy must be finite and positive, not {(fx, fy)}")
+    lo, hi = (float(v) for v in depth_range)
+    if not _math.isfinite(lo) or hi != hi:
+        raise ValueError(f"{what}: depth_range must start at a finite depth and not end at NaN, not {(lo, hi)}")
+    step = 0.5 * vol.voxel_size if step is None else float(step)
+    if not (_math.isfinite(step) and step > 0.0):
+        raise ValueError(f"{what}: step must be finite and positive, not {step}")
+    min_weight = _min_weight(what, min_weight)
+    color = vol.color is not None if color is None else bool(color)
+    if color and vol.color is None:
+        raise ValueError(f"{what}: color asked for, but the volume was made with color=False")
+    if isinstance(bricks, torch.Tensor):
+        if bricks.dtype != torch.uint8 or tuple(bricks.shape) != _brick_shape(vol.dims) or bricks.device != dev:
+            raise ValueError(f"{what}: bricks must be the uint8 {list(_brick_shape(vol.dims))} tensor tsdf_bricks returns for this "
+                             f"volume, not {bricks.dtype} {list(bricks.shape)} on {bricks.device}")
+        bricks = bricks.contiguous()
+    elif bricks is not None and bricks != "build":
+        raise ValueError(f"{what}: bricks must be \"build\", None or a tensor from tsdf_bricks, not {bricks!r}")
+    if dev.type != "cuda":
+        raise ValueError(f"{what}: the volume must live on the GPU (there is no CPU fallback)")
+    if isinstance(bricks, str):
+        bricks = tsdf_bricks(vol, min_weight=min_weight)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    vnmap = torch.empty((V, H, W, 4), dtype=torch.float32, device=dev) if normals else None
+    color_out = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev) if color else None
+    flags = torch.empty((V, H, W), dtype=torch.uint8, device=dev) if return_flags else None
+    params = _capi.RaycastParams(fx, fy, cx, cy, lo, hi, step, min_weight)
+    p = _capi.ptr
+    _capi.call("dgr_tsdf_raycast", dev, vol.grid(), p(vol.volume), p(vol.color) if color else None,
+               p(bricks), V, W, H, p(viewmatrices), params, p(depth), p(vnmap), p(color_out), p(flags))
+    if single:
+        depth, vnmap, color_out, flags = (None if t is None else t[0] for t in (depth, vnmap, color_out, flags))
+    return TsdfRaycast(depth, vnmap, color_out, flags)

@@ -21,7 +21,7 @@ import torch
 from . import full as _full
 from . import light as _light
 from .contrib import ContributionAccumulator, ContributionStats, contribution_stats, render_contributions  # noqa: F401
-from .fusion import TsdfMesh, TsdfVolume, extract_mesh, tsdf_integrate  # noqa: F401
+from .fusion import TsdfMesh, TsdfRaycast, TsdfVolume, extract_mesh, tsdf_bricks, tsdf_integrate, tsdf_raycast  # noqa: F401
 from .icp import IcpResult, depth_normals, icp_align  # noqa: F401
 from .keyframes import KeyframeOverlap, keyframe_overlap, select_keyframes  # noqa: F401  (slam.X stays the public name)
 from .posegraph import PgoPlan, PgoResult, pose_graph_optimize, pose_graph_plan, relative_pose  # noqa: F401

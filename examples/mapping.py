@@ -48,12 +48,15 @@ their depth and colour are fused into a truncated signed distance volume of that
 (slam.tsdf_integrate: every keyframe in ONE pass over the volume, mask_image = the render's opacity_map) and the zero level is
 extracted by marching tetrahedra (slam.extract_mesh); one line reports the volume, the triangles and their area.
 --mesh-out PATH writes that mesh as an ASCII PLY (from the host, with numpy).
+--raycast (with --tsdf) then looks at the fused volume from the fused keyframes' poses (slam.tsdf_raycast, all of them in one
+launch) and reports the share of pixels that hit the surface and the mean |rendered depth - ray-cast depth| where both are valid:
+how far the Gaussians' depth lies from the surface fused from it.
 
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
                              [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked] [--select K]
                              [--relocate-every N [--relocate-start K] [--position-noise] [--relocate-min-opacity 0.005]]
                              [--loop-close-at N [--loop-close-seed S]] [--prune-unseen N [--prune-min-views M]]
-                             [--tsdf VOXEL [--mesh-out PATH]]
+                             [--tsdf VOXEL [--mesh-out PATH] [--raycast]]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -153,7 +156,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
                  absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0, relocate_every=0,
                  position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0, loop_close_at=0,
                  loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True, loop_close_pgo=False, prune_unseen=0,
-                 prune_min_views=1, tsdf=0.0, mesh_out=None):
+                 prune_min_views=1, tsdf=0.0, mesh_out=None, raycast=False):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -191,7 +194,10 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     tsdf=VOXEL: after the last iteration the window's keyframes are rendered once more and fused into a TSDF volume of that voxel
     size around the map (slam.tsdf_integrate, one call for all of them, mask_image=opacity_map), and slam.extract_mesh gives its
     zero level; the model's `tsdf` attribute then holds dims, triangles, area and the mesh.  mesh_out=PATH (with tsdf) writes the
-    mesh as an ASCII PLY."""
+    mesh as an ASCII PLY.  raycast=True (with tsdf): the volume is ray-cast at the fused keyframes' poses (slam.tsdf_raycast) and
+    `tsdf` also holds hit_share and depth_diff, the mean |rendered depth - ray-cast depth| over the pixels where both are valid."""
+    if raycast and not tsdf:
+        raise ValueError("raycast=True looks at the volume that tsdf=VOXEL fuses: give that too")
     if mesh_out and not tsdf:
         raise ValueError("mesh_out=PATH writes the mesh that tsdf=VOXEL extracts: give that too")
     if tsdf < 0 or tsdf != tsdf:
@@ -452,9 +458,11 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     if graph:
         step.check()
     if tsdf:
-        pc.tsdf = fuse_window(slam, pc, cams[:max(n_live, 1)], bg, gt, kw, W, H, s.tanfovx, s.tanfovy, float(tsdf), mesh_out)
+        pc.tsdf = fuse_window(slam, pc, cams[:max(n_live, 1)], bg, gt, kw, W, H, s.tanfovx, s.tanfovy, float(tsdf), mesh_out, raycast)
         if log:
             log(tsdf_line(pc.tsdf))
+            if raycast:
+                log(raycast_line(pc.tsdf))
     pc.window = window
     pc.relocations = [c.tolist()[:5] for c in relocations]
     pc.unseen = unseen_steps
@@ -469,9 +477,10 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     return (first, float(loss)), pc, dt
 
 
-def fuse_window(slam, pc, cams, bg, gt, kw, W, H, tanfovx, tanfovy, voxel, mesh_out=None):
+def fuse_window(slam, pc, cams, bg, gt, kw, W, H, tanfovx, tanfovy, voxel, mesh_out=None, raycast=False):
     """The map's surface: the keyframes `cams` rendered once more, fused into a TSDF volume of voxel size `voxel` around the map in
-    one call and extracted.  Returns dict(dims, triangles, area, mesh)."""
+    one call and extracted.  Returns dict(dims, triangles, area, mesh); with `raycast` the volume is also ray-cast at the same
+    poses, and hit_share and depth_diff (mean |rendered - ray-cast depth| where both are valid) join them."""
     with torch.no_grad():
         outs = [slam.render(None, pc, None, bg, viewmatrix=c["viewmatrix"], fov=c["fov"], HW=c["HW"], gt_depth=gt, **kw) for c in cams]
         alpha = torch.stack([o["opacity_map"].reshape(H, W) for o in outs])
@@ -490,13 +499,24 @@ def fuse_window(slam, pc, cams, bg, gt, kw, W, H, tanfovx, tanfovy, voxel, mesh_
         mesh = slam.extract_mesh(vol)
         tri = mesh.vertices.reshape(-1, 3, 3).double()
         area = float(0.5 * torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]).norm(dim=1).sum())
+        out = dict(dims=vol.dims, triangles=mesh.vertices.shape[0] // 3, area=area, mesh=mesh)
+        if raycast:
+            cast = slam.tsdf_raycast(vol, views, W / (2.0 * tanfovx), H / (2.0 * tanfovy), (W - 1) / 2.0, (H - 1) / 2.0, H, W,
+                                     normals=False, color=False)
+            both = (cast.depth > 0) & (depth > 0)
+            diff = (cast.depth - depth).abs()[both]
+            out.update(hit_share=float((cast.depth > 0).float().mean()), depth_diff=float(diff.mean()) if diff.numel() else float("nan"))
     if mesh_out:
         write_ply(mesh_out, mesh.vertices.cpu().numpy(), mesh.colors.cpu().numpy())
-    return dict(dims=vol.dims, triangles=mesh.vertices.shape[0] // 3, area=area, mesh=mesh)
+    return out
 
 
 def tsdf_line(t):
     return f"tsdf: {t['dims'][0]}x{t['dims'][1]}x{t['dims'][2]} voxels, {t['triangles']} triangles, area {t['area']:.4f}"
+
+
+def raycast_line(t):
+    return f"raycast: hit share {t['hit_share']:.4f}, mean |rendered - ray-cast depth| {t['depth_diff']:.5f}"
 
 
 def write_ply(path, vertices, colors):
@@ -566,6 +586,9 @@ def main():
                     help="after the last iteration fuse the window's rendered keyframes into a TSDF volume of this voxel size around "
                          "the map (slam.tsdf_integrate) and extract its surface (slam.extract_mesh); 0 (default): off")
     ap.add_argument("--mesh-out", default=None, metavar="PATH", help="with --tsdf: write the mesh as an ASCII PLY")
+    ap.add_argument("--raycast", action="store_true",
+                    help="with --tsdf: ray-cast the fused volume at the fused keyframes' poses (slam.tsdf_raycast) and report the hit "
+                         "share and the mean |rendered depth - ray-cast depth|")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -595,6 +618,8 @@ def main():
         ap.error("--prune-unseen renders the window outside the recorded iteration and reads a count: drop --graph")
     if args.tsdf < 0 or (args.mesh_out and not args.tsdf):
         ap.error("--tsdf VOXEL takes a voxel size > 0, and --mesh-out PATH writes its mesh: give --tsdf too")
+    if args.raycast and not args.tsdf:
+        ap.error("--raycast looks at the volume that --tsdf VOXEL fuses: give --tsdf too")
     if not 0.0 <= args.relocate_min_opacity < 1.0:
         ap.error("--relocate-min-opacity lies in [0, 1)")
     import torch as _torch
@@ -609,9 +634,11 @@ def main():
                                     position_noise=args.position_noise, relocate_min_opacity=args.relocate_min_opacity,
                                     relocate_start=args.relocate_start, loop_close_at=args.loop_close_at,
                                     loop_close_seed=args.loop_close_seed, loop_close_pgo=args.pgo, prune_unseen=args.prune_unseen,
-                                    prune_min_views=args.prune_min_views, tsdf=args.tsdf, mesh_out=args.mesh_out)
+                                    prune_min_views=args.prune_min_views, tsdf=args.tsdf, mesh_out=args.mesh_out, raycast=args.raycast)
     if args.tsdf and args.graph:  # (otherwise the loop has logged it)
         print(tsdf_line(pc.tsdf))
+        if args.raycast:
+            print(raycast_line(pc.tsdf))
     if args.prune_unseen:
         print(f"prune-unseen: {sum(u for _, u in pc.unseen)} Gaussians marked unseen in {len(pc.unseen)} steps "
               f"(fewer than {args.prune_min_views} keyframes blended them)")

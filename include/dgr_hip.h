@@ -931,6 +931,56 @@ int dgr_mesh_plan(void* stream, const dgr_tsdf_grid* grid, const float* volume, 
 int dgr_mesh_emit(void* stream, const dgr_tsdf_grid* grid, const float* volume, const float* color /* or NULL */, float min_weight,
                   int max_triangles, const void* scratch, float* vertices, float* colors /* or NULL */);
 
+/* ---- Ray-casting the TSDF volume: depth, normals and colour at any pose (csrc/raycast.hip) ----
+ * The other half of a volumetric pipeline: the fused surface seen from a pose -- a multi-view-averaged depth with normals from the
+ * field's gradient, as dgr_icp_step's vn_model and dgr_depth_normals' input; the depth the "Depth L1" tables are measured on.
+ * The volume, grid and conventions are dgr_tsdf_integrate's: viewmatrices [n_views, 16] = W2C^T with W2C = [R | t]; pixel (x, y) at
+ *   z-depth z is the camera point z d_c, d_c = ((x - cx) / fx, (y - cy) / fy, 1), the world point p_w = R^T (z d_c - t).
+ * Samples: z_k = depth_min + k step for k = 0, 1, ... while z_k < depth_max (and k < 2^24); each z_k is ONE fused multiply-add from
+ *   k, never accumulated along the ray.  step is in metres of z-depth.  Lattice coordinates q = (p_w - origin) / voxel_size, the
+ *   cell i = floor(q), the fraction f = q - i.  A sample is valid iff 0 <= i <= n - 2 on every axis and all 8 corner weights are
+ *   >= min_weight (dgr_mesh_plan's cell validity).  Its value F is the trilinear interpolant of the 8 tsdf values.
+ * Decision: k* = the smallest k whose sample is valid with F <= 0.  None: a miss, flags = 0.  If k* >= 1 and sample k* - 1 is
+ *   valid with F > 0: a hit, flags bit 0.  Otherwise the ray ends there unseen, flags bit 1, no depth: it started inside the
+ *   surface or came out of unmeasured space behind it.  Nothing else ends a ray.  (Samples outside the lattice are invalid: the
+ *   march starts at the box and stops behind it, which is no part of the rule.  depth_max may be INFINITY.)
+ * A hit's outputs: depth z* = z_(k*-1) + step F_(k*-1) / (F_(k*-1) - F_k*), p* the world point there.  Normal: the central
+ *   differences of the same validity-checked interpolant F at p* +- voxel_size along each world axis, normalised, rotated by R
+ *   into the camera frame and turned to face the camera (n . p_c <= 0) as dgr_depth_normals does; if one of the six evaluations
+ *   is invalid or the gradient is zero, infinite or NaN: flags bit 2, the normal stays zero, depth and colour are still written.
+ *   Colour: plain trilinear interpolation of the colour volume in p*'s cell (which exists: both ends of the segment lie in the
+ *   lattice's convex cell range); the weights are NOT consulted for the colour.
+ * Outputs, each may be NULL but not all: depth [n_views, height, width], 0 without a hit (the sensor's "invalid"); vnmap
+ *   [n_views, height, width, 4] = (n_c, z*), what dgr_depth_normals writes and dgr_icp_step reads, four zeros without a hit or
+ *   without a normal, 16-byte aligned; color_out [n_views, 3, height, width], 0 without a hit; flags uint8 [n_views, height, width].
+ * NaN poses and NaN volume entries end in misses or garbage values, never in an out-of-range read: comparisons are made in float
+ *   (false on a NaN) and the integer indices are tested again before every gather.
+ * Empty-space skipping: a brick is 8 x 8 x 8 cells; bricks uint8 [ceil((nz-1)/8), ceil((ny-1)/8), ceil((nx-1)/8)], 1 iff the brick
+ *   contains a valid cell (for the min_weight given) with at least one corner tsdf <= 0 -- only such a cell can hold a valid sample
+ *   with F <= 0, a trilinear value never lying below its corners' minimum.  dgr_tsdf_bricks builds it in one launch (comparisons
+ *   and integer logic, no atomics); dgr_tsdf_brick_bytes(grid) is its size (0 for a grid the library refuses, and for one without
+ *   a cell).  dgr_tsdf_raycast takes the map or NULL; with it, runs of samples whose cells lie in dead bricks are jumped over, and
+ *   the outputs are the SAME BITS as without: every surviving sample is computed from its own k, a jump is checked against the
+ *   sample it would skip last and the sample landed on has its brick tested again, and sample k* - 1 is evaluated for real
+ *   wherever it lies.  The map must have been built from this volume with this min_weight.
+ * One lane per ray, every view in one launch; nothing allocated, nothing read on the host: capturable into a hipGraph.
+ * Refused with DGR_ERR_BAD_ARGUMENT and a message before any device call: a NULL grid, params, volume or viewmatrices; a grid
+ *   dgr_tsdf_integrate refuses; fx, fy or step not finite and positive; a NaN min_weight, a NaN depth_max, a depth_min that is not
+ *   finite; n_views < 1 (or > 65535), width or height < 1; no output at all; color_out without a colour volume; a misaligned
+ *   pointer (vnmap and color 16 bytes, volume 8); (bricks) a NULL bricks for a grid with cells. */
+typedef struct dgr_raycast_params {
+    float fx, fy, cx, cy;
+    float depth_min, depth_max; /* the samples' z-depths: depth_min + k step < depth_max */
+    float step;                 /* > 0, metres of z-depth */
+    float min_weight;           /* a cell counts when its 8 weights are >= this */
+} dgr_raycast_params;
+size_t dgr_tsdf_brick_bytes(const dgr_tsdf_grid* grid);
+int dgr_tsdf_bricks(void* stream, const dgr_tsdf_grid* grid, const float* volume, float min_weight, unsigned char* bricks);
+int dgr_tsdf_raycast(void* stream, const dgr_tsdf_grid* grid, const float* volume, const float* color /* or NULL */,
+                     const unsigned char* bricks /* or NULL */, int n_views, int width, int height, const float* viewmatrices,
+                     const dgr_raycast_params* params, float* depth /* or NULL */, float* vnmap /* or NULL */,
+                     float* color_out /* or NULL */, unsigned char* flags /* or NULL */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
