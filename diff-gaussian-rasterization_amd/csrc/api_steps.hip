@@ -836,4 +836,45 @@ int dgr_tsdf_raycast(void* stream, const dgr_tsdf_grid* grid, const float* volum
     return DGR_OK;
 }
 
+// ---- exact k-nearest-neighbour search (knn.hip)
+size_t dgr_knn_index_bytes(int n_points) { return dgr::knn_index_bytes(n_points); }
+size_t dgr_knn_scratch_bytes(int n_points, int n_queries) { return dgr::knn_scratch_bytes(n_points, n_queries); }
+int dgr_knn_build(void* stream, int n_points, const float* points, void* index, void* scratch) {
+    const char* bad = nullptr;
+    if (dgr::knn_index_bytes(n_points) == 0) bad = "n_points must be 1 .. 2^24";
+    if (!bad && !points) bad = "points is NULL";
+    if (!bad && !aligned_to(points, 4)) bad = "points is not 4-byte aligned";
+    if (!bad && (!index || !dgr::aligned16(index))) bad = "index is NULL or not 16-byte aligned";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (bad) return refuse("dgr_knn_build", bad);
+    HIP_TRY(dgr::launch_knn_build(n_points, points, index, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+int dgr_knn_search(void* stream, const void* index, int n_points, const float* points, int n_queries, const float* queries,
+                   const dgr_knn_params* params, void* scratch, float* dist2, int* idx, int* count, float* mean_dist2) {
+    const dgr_knn_params* p = params;
+    const char* bad = nullptr;
+    if (dgr::knn_index_bytes(n_points) == 0) bad = "n_points must be 1 .. 2^24";
+    if (!bad && (n_queries < 1 || n_queries > (1 << 24))) bad = "n_queries must be 1 .. 2^24";
+    if (!bad && !p) bad = "params is NULL";
+    if (!bad && (p->k < 1 || p->k > DGR_KNN_MAX_K)) bad = "k must be 1 .. 16";
+    if (!bad && (std::isnan(p->max_dist2) || p->max_dist2 < 0.0f)) bad = "max_dist2 is NaN or negative";
+    if (!bad && queries && p->exclude_self) bad = "exclude_self with queries given: it is defined in self mode only";
+    if (!bad && !queries && n_queries != n_points) bad = "n_queries must equal n_points in self mode (queries is NULL)";
+    if (!bad && (!index || !dgr::aligned16(index))) bad = "index is NULL or not 16-byte aligned";
+    if (!bad && !points) bad = "points is NULL";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && !dist2 && !idx && !count && !mean_dist2) bad = "no output given: dist2, idx, count and mean_dist2 are all NULL";
+    if (!bad && !(aligned_to(points, 4) && aligned_to(queries, 4) && aligned_to(dist2, 4) && aligned_to(idx, 4) && aligned_to(count, 4) &&
+                  aligned_to(mean_dist2, 4)))
+        bad = "points, queries or an output is not 4-byte aligned";
+    if (bad) return refuse("dgr_knn_search", bad);
+    dgr::KnnSearchCall c{};
+    c.index = index, c.n_points = n_points, c.n_queries = n_queries, c.queries = queries;
+    c.k = p->k, c.exclude_self = p->exclude_self ? 1 : 0, c.max_dist2 = p->max_dist2, c.scratch = scratch;
+    c.dist2 = dist2, c.idx = idx, c.count = count, c.mean_dist2 = mean_dist2;
+    HIP_TRY(dgr::launch_knn_search(c, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

@@ -522,6 +522,23 @@ struct RaycastArgs {
     unsigned char* flags;          // [V, H, W] or NULL
 };
 hipError_t launch_tsdf_raycast(const RaycastArgs& args, hipStream_t stream);
+// exact k-nearest-neighbour search (knn.hip): the index (sorted records and 256-record leaves) and the pruned scan over it
+size_t knn_index_bytes(int n_points);                  // 0: refused (n_points outside 1 .. 2^24)
+size_t knn_scratch_bytes(int n_points, int n_queries);  // 0: refused
+hipError_t launch_knn_build(int n_points, const float* points, void* index, void* scratch, hipStream_t stream);
+struct KnnSearchCall {
+    const void* index;
+    int n_points, n_queries;
+    const float* queries;  // [Q, 3] or NULL: the indexed points, query i is point i
+    int k, exclude_self;
+    float max_dist2;
+    void* scratch;
+    float* dist2;       // [Q, k] or NULL
+    int* idx;           // [Q, k] or NULL
+    int* count;         // [Q] or NULL
+    float* mean_dist2;  // [Q] or NULL
+};
+hipError_t launch_knn_search(const KnnSearchCall& call, hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -149,6 +149,14 @@ class RaycastParams(C.Structure):  # dgr_raycast_params
 
 assert C.sizeof(RaycastParams) == 32  # eight four-byte fields: the C layout
 
+
+class KnnParams(C.Structure):  # dgr_knn_params
+    _fields_ = [("k", _i), ("exclude_self", _i), ("max_dist2", _f)]
+
+
+assert C.sizeof(KnnParams) == 12  # three four-byte fields: the C layout
+KNN_MAX_K = 16  # DGR_KNN_MAX_K
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -214,6 +222,10 @@ _SIGS = {
     "dgr_tsdf_brick_bytes": (_sz, [C.POINTER(TsdfGrid)]),
     "dgr_tsdf_bricks": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _f, _vp]),
     "dgr_tsdf_raycast": (_i, [_vp, C.POINTER(TsdfGrid), _vp, _vp, _vp, _i, _i, _i, _vp, C.POINTER(RaycastParams), _vp, _vp, _vp, _vp]),
+    "dgr_knn_index_bytes": (_sz, [_i]),
+    "dgr_knn_scratch_bytes": (_sz, [_i, _i]),
+    "dgr_knn_build": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "dgr_knn_search": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.POINTER(KnnParams), _vp, _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -23,6 +23,7 @@ from . import light as _light
 from .contrib import ContributionAccumulator, ContributionStats, contribution_stats, render_contributions  # noqa: F401
 from .fusion import TsdfMesh, TsdfRaycast, TsdfVolume, extract_mesh, tsdf_bricks, tsdf_integrate, tsdf_raycast  # noqa: F401
 from .icp import IcpResult, depth_normals, icp_align  # noqa: F401
+from .knn import KnnIndex, KnnResult, dist2, knn_build, knn_search  # noqa: F401
 from .keyframes import KeyframeOverlap, keyframe_overlap, select_keyframes  # noqa: F401  (slam.X stays the public name)
 from .posegraph import PgoPlan, PgoResult, pose_graph_optimize, pose_graph_plan, relative_pose  # noqa: F401
 from .losses import MaskedLossStats, l1_loss, l1_ssim_loss, masked_l1_loss, ssim  # noqa: F401

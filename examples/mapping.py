@@ -51,12 +51,15 @@ extracted by marching tetrahedra (slam.extract_mesh); one line reports the volum
 --raycast (with --tsdf) then looks at the fused volume from the fused keyframes' poses (slam.tsdf_raycast, all of them in one
 launch) and reports the share of pixels that hit the surface and the mean |rendered depth - ray-cast depth| where both are valid:
 how far the Gaussians' depth lies from the surface fused from it.
+--knn-scale (with --seed) gives the Gaussians a seeding adds 3DGS's initial scale: log-scale = 0.5 log(max(dist2, 1e-7)), dist2 the
+mean squared distance to the three nearest Gaussians of the whole map (slam.dist2, the distCUDA2 of simple-knn), written into the
+new rows in place (their Adam moments are zero already).
 
   python examples/mapping.py [--graph] [--fused] [--variant light|full] [--absgrad] [--densify-every N] [--iters 100]
                              [--keyframes 4] [--ssim LAMBDA] [--seed] [--masked] [--select K]
                              [--relocate-every N [--relocate-start K] [--position-noise] [--relocate-min-opacity 0.005]]
                              [--loop-close-at N [--loop-close-seed S]] [--prune-unseen N [--prune-min-views M]]
-                             [--tsdf VOXEL [--mesh-out PATH] [--raycast]]
+                             [--tsdf VOXEL [--mesh-out PATH] [--raycast]] [--knn-scale]
 
 --absgrad feeds the densification statistics with AbsGS's absolute screen-space gradient (`viewspace_points_abs.grad`) instead
 of 3DGS's `viewspace_points.grad`; the densify step then uses a threshold 4x higher (0.0008 for 0.0002).
@@ -156,7 +159,7 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
                  absgrad=False, densify_every=0, ssim_lambda=0.0, seed=False, masked=False, select=0, relocate_every=0,
                  position_noise=False, relocate_min_opacity=0.005, relocate_seed=0, relocate_start=0, loop_close_at=0,
                  loop_close_seed=0, loop_close_scale=0.1, loop_close_moves_map=True, loop_close_pgo=False, prune_unseen=0,
-                 prune_min_views=1, tsdf=0.0, mesh_out=None, raycast=False):
+                 prune_min_views=1, tsdf=0.0, mesh_out=None, raycast=False, knn_scale=False, on_knn_scale=None):
     """Returns (losses of the first and last iteration, model, seconds per iteration).  graph=True records the whole
     iteration (renders, losses, backward passes, statistics, Adam) into one hipGraph after three eager iterations.
     absgrad=True: the statistics take the absolute screen-space gradient (slam.render*(absgrad=True)).
@@ -195,9 +198,14 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
     size around the map (slam.tsdf_integrate, one call for all of them, mask_image=opacity_map), and slam.extract_mesh gives its
     zero level; the model's `tsdf` attribute then holds dims, triangles, area and the mesh.  mesh_out=PATH (with tsdf) writes the
     mesh as an ASCII PLY.  raycast=True (with tsdf): the volume is ray-cast at the fused keyframes' poses (slam.tsdf_raycast) and
-    `tsdf` also holds hit_share and depth_diff, the mean |rendered depth - ray-cast depth| over the pixels where both are valid."""
+    `tsdf` also holds hit_share and depth_diff, the mean |rendered depth - ray-cast depth| over the pixels where both are valid.
+    knn_scale=True (with seed): after each seeding the new rows' log-scales become 0.5 log(max(slam.dist2(xyz), 1e-7)) over the whole
+    map (3DGS's initialisation); `on_knn_scale(rows_before, xyz, new_log_scales)`, if given, is called after each such write with
+    views of the map's tensors."""
     if raycast and not tsdf:
         raise ValueError("raycast=True looks at the volume that tsdf=VOXEL fuses: give that too")
+    if knn_scale and not seed:
+        raise ValueError("knn_scale=True sets the scale of the Gaussians that seed=True adds: give that too")
     if mesh_out and not tsdf:
         raise ValueError("mesh_out=PATH writes the mesh that tsdf=VOXEL extracts: give that too")
     if tsdf < 0 or tsdf != tsdf:
@@ -350,6 +358,14 @@ def mapping_loop(dev, P, W, H, keyframes, iters, views_in_flight=3, log=None, gr
             **(dict(fill={"anchor": float(k)}) if loop_close_at else {}),
             xyz_gradient_accum=pc.xyz_gradient_accum, denom=pc.denom, max_radii2D=pc.max_radii2D)
         pc.replace(leaves, accum, denom, max_radii2D)
+        if knn_scale and counts.rows > before:  # 3DGS's initial scale, over the whole map; the new rows' Adam moments are zero
+            with torch.no_grad():
+                d2 = slam.dist2(pc._xyz.detach())
+                pc._scaling[before:] = (0.5 * torch.log(torch.clamp(d2[before:], min=1e-7)))[:, None].expand(-1, 3)
+            if on_knn_scale:
+                on_knn_scale(before, pc._xyz.detach(), pc._scaling.detach()[before:])
+            if log:
+                log(f"knn-scale: keyframe {k}: {counts.rows - before} new rows, mean scale {float(pc._scaling.detach()[before:].exp().mean()):.5f}")
         seen = torch.zeros(counts.rows, dtype=torch.int32, device=dev)
         n_live = k + 1
         if log:
@@ -589,6 +605,10 @@ def main():
     ap.add_argument("--raycast", action="store_true",
                     help="with --tsdf: ray-cast the fused volume at the fused keyframes' poses (slam.tsdf_raycast) and report the hit "
                          "share and the mean |rendered depth - ray-cast depth|")
+    ap.add_argument("--knn-scale", action="store_true",
+                    help="with --seed: the log-scale of the new Gaussians becomes 0.5 log(max(dist2, 1e-7)), dist2 the mean squared "
+                         "distance to the three nearest Gaussians of the whole map (slam.dist2, simple-knn's distCUDA2): 3DGS's "
+                         "initialisation")
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--gaussians", type=int, default=100000)
@@ -618,6 +638,8 @@ def main():
         ap.error("--prune-unseen renders the window outside the recorded iteration and reads a count: drop --graph")
     if args.tsdf < 0 or (args.mesh_out and not args.tsdf):
         ap.error("--tsdf VOXEL takes a voxel size > 0, and --mesh-out PATH writes its mesh: give --tsdf too")
+    if args.knn_scale and not args.seed:
+        ap.error("--knn-scale sets the scale of the Gaussians that --seed adds: give --seed too")
     if args.raycast and not args.tsdf:
         ap.error("--raycast looks at the volume that --tsdf VOXEL fuses: give --tsdf too")
     if not 0.0 <= args.relocate_min_opacity < 1.0:
@@ -634,7 +656,8 @@ def main():
                                     position_noise=args.position_noise, relocate_min_opacity=args.relocate_min_opacity,
                                     relocate_start=args.relocate_start, loop_close_at=args.loop_close_at,
                                     loop_close_seed=args.loop_close_seed, loop_close_pgo=args.pgo, prune_unseen=args.prune_unseen,
-                                    prune_min_views=args.prune_min_views, tsdf=args.tsdf, mesh_out=args.mesh_out, raycast=args.raycast)
+                                    prune_min_views=args.prune_min_views, tsdf=args.tsdf, mesh_out=args.mesh_out, raycast=args.raycast,
+                                    knn_scale=args.knn_scale)
     if args.tsdf and args.graph:  # (otherwise the loop has logged it)
         print(tsdf_line(pc.tsdf))
         if args.raycast:

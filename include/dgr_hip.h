@@ -981,6 +981,61 @@ int dgr_tsdf_raycast(void* stream, const dgr_tsdf_grid* grid, const float* volum
                      const dgr_raycast_params* params, float* depth /* or NULL */, float* vnmap /* or NULL */,
                      float* color_out /* or NULL */, unsigned char* flags /* or NULL */);
 
+/* Exact k-nearest-neighbour search: which points lie next to this one (simple-knn's distCUDA2 is self mode with k = 3,
+ * exclude_self and the mean_dist2 output; per-point neighbourhoods for G-ICP covariances, outlier removal and duplicate
+ * suppression use the indices, the radius and queries of their own).
+ * THE RULE (normative: the index below only finds this answer faster, it cannot change a bit of it).
+ *   points [P,3] float32, contiguous.  A point with a non-finite coordinate is INVALID: it is never indexed and never returned.
+ *   queries [Q,3] float32, or NULL = SELF MODE: the queries are the indexed points, query i is point i (n_queries = n_points).
+ *   distance, in fp32, every operation rounded once (to nearest even) and nothing contracted:
+ *       dx = px - qx, dy = py - qy, dz = pz - qz;   d2 = ((dx dx) + (dy dy)) + (dz dz)
+ *     (__fsub_rn, __fmul_rn, __fadd_rn), so that a float32 numpy twin reproduces d2 bit for bit.  d2 may be +inf for huge
+ *     coordinates; it is never NaN for finite inputs.
+ *   candidates are totally ordered by (d2, index): d2 as a float compare, then the index ascending.
+ *   a candidate is admitted iff d2 <= max_dist2 (default +inf, which admits d2 = +inf) and, in self mode with exclude_self,
+ *     its index differs from the query's (other coincident points stay, with d2 = 0).
+ *   the result of a query is the first k admitted candidates in that order, ascending; 1 <= k <= DGR_KNN_MAX_K.
+ *   outputs, each optional (NULL): dist2 [Q,k] float32; idx [Q,k] int32, indices into the caller's points; count [Q] int32, the
+ *     number of neighbours found; mean_dist2 [Q] float32 = the k distances added left to right in ascending order (__fadd_rn),
+ *     then one division (__fdiv_rn) by (float)k.  Slots beyond count hold idx = -1 and dist2 = +inf, and mean_dist2 is then
+ *     +inf.  A query with a non-finite coordinate gets count = 0 (in self mode an invalid point is such a query).  Nothing else
+ *     is written.
+ *   distCUDA2(points) = self mode, k = 3, exclude_self, mean_dist2.  With fewer than four valid points it is +inf here
+ *     (simple-knn returns a FLT_MAX-derived value there); the yardstick is the brute-force model of the rule (tests/knn_model.py),
+ *     no bit parity with simple-knn is claimed.
+ * dgr_knn_build writes the opaque `index` (dgr_knn_index_bytes(n_points) bytes, 16-byte aligned) from `points`: the box of the
+ *   valid points, a 30-bit Morton key per point on it (an axis of zero or non-finite extent quantises to 0), a stable radix sort of
+ *   (key, index), the sorted (x, y, z, index) records and, per leaf of 256 consecutive records, its exact fp32 box.  The index
+ *   holds a copy of the coordinates: a search answers for the points as they were when the index was built.  dgr_knn_search's
+ *   `points` is therefore not read by the launch: it is reserved (the tensor the indices refer to), and only checked for NULL.
+ * dgr_knn_search: one lane per query, 64 queries that are consecutive in Morton order per wave (cross mode: the queries are keyed
+ *   on the index's box and sorted by the same sort, and the results go back to the caller's rows).  A wave starts at its own leaf
+ *   and sweeps the leaves outwards; a leaf is skipped only when bound > limit, where bound is the SAME rounded formula at the
+ *   box's nearest point (per-axis gap max(0, lo - q, q - hi) by one rounded subtraction; rounding is monotone, so the bound never
+ *   exceeds the fp32 d2 of a point inside) and limit is the smaller of max_dist2 and the lane's current k-th d2.
+ * `scratch`: dgr_knn_scratch_bytes(n_points, n_queries) bytes, 16-byte aligned; nothing in it is kept between calls (a build
+ *   needs no more than dgr_knn_scratch_bytes(n_points, 1)).  Both size functions return 0 for a shape they refuse.
+ * Launch properties: nothing read on the host, every size known from n_points, n_queries and k, integer atomics only, no
+ *   spin-wait and no grid barrier (the phases are separate launches), every loop bounded by the number of leaves or a leaf's
+ *   count, the same bits on every run, capturable into a hipGraph (`points` and `queries` are read at replay).
+ * Limits: n_points, n_queries <= 2^24.  The worst case per query is O(n_points) -- an outlier that stretches the box, all points
+ *   coincident, or d2 = +inf neighbours, which no bound can prune: slow, and still the exact answer.
+ * Refused with DGR_ERR_BAD_ARGUMENT and a message before any device call: n_points or n_queries outside 1 .. 2^24 (self mode:
+ *   n_queries != n_points); k outside 1 .. 16; a NULL index, points, params or scratch; an index or scratch that is not 16-byte
+ *   aligned; all four outputs NULL; a NaN or negative max_dist2; exclude_self with queries given. */
+#define DGR_KNN_MAX_K 16
+typedef struct dgr_knn_params {
+    int k;            /* 1 .. DGR_KNN_MAX_K */
+    int exclude_self; /* self mode only: the query's own index is not a candidate */
+    float max_dist2;  /* admitted: d2 <= max_dist2; +inf admits everything */
+} dgr_knn_params;
+size_t dgr_knn_index_bytes(int n_points);
+size_t dgr_knn_scratch_bytes(int n_points, int n_queries);
+int dgr_knn_build(void* stream, int n_points, const float* points, void* index, void* scratch);
+int dgr_knn_search(void* stream, const void* index, int n_points, const float* points, int n_queries,
+                   const float* queries /* NULL: self mode */, const dgr_knn_params* params, void* scratch,
+                   float* dist2 /* or NULL */, int* idx /* or NULL */, int* count /* or NULL */, float* mean_dist2 /* or NULL */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
