@@ -877,4 +877,74 @@ int dgr_knn_search(void* stream, const void* index, int n_points, const float* p
     return DGR_OK;
 }
 
+// ---- generalized ICP over the kNN index (gicp.hip)
+int dgr_point_covariances(void* stream, int n_points, const float* points, int k, const int* idx,
+                          const dgr_covariance_params* params, float* cov, float* normals, float* log_scales, float* quats,
+                          unsigned char* flags) {
+    const dgr_covariance_params* p = params;
+    const char* bad = nullptr;
+    if (n_points < 1 || n_points > (1 << 24)) bad = "n_points must be 1 .. 2^24";
+    if (!bad && (k < 1 || k > DGR_KNN_MAX_K)) bad = "k must be 1 .. 16";
+    if (!bad && !points) bad = "points is NULL";
+    if (!bad && !idx) bad = "idx is NULL";
+    if (!bad && !p) bad = "params is NULL";
+    if (!bad && !cov && !normals && !log_scales && !quats && !flags)
+        bad = "no output given: cov, normals, log_scales, quats and flags are all NULL";
+    if (!bad && !dgr::aligned16(cov)) bad = "cov is not 16-byte aligned";
+    if (!bad && !(aligned_to(points, 4) && aligned_to(idx, 4) && aligned_to(normals, 4) && aligned_to(log_scales, 4) && aligned_to(quats, 4)))
+        bad = "points, idx or an output is not 4-byte aligned";
+    if (!bad && p->mode != DGR_COV_RAW && p->mode != DGR_COV_PLANE) bad = "unknown mode";
+    if (!bad && !(p->epsilon > 0.0f && p->epsilon <= 1.0f)) bad = "epsilon must lie in (0, 1]";
+    if (!bad && (p->min_neighbours < 3 || p->min_neighbours > k)) bad = "min_neighbours must be 3 .. k";
+    if (!bad && std::isnan(p->scale_floor)) bad = "scale_floor is NaN";
+    if (!bad && p->has_viewpoint && (std::isnan(p->viewpoint[0]) || std::isnan(p->viewpoint[1]) || std::isnan(p->viewpoint[2])))
+        bad = "viewpoint holds a NaN";
+    if (bad) return refuse("dgr_point_covariances", bad);
+    dgr::PointCovArgs a{};
+    a.P = n_points, a.k = k, a.points = points, a.idx = idx;
+    a.mode = p->mode, a.min_neighbours = p->min_neighbours, a.has_viewpoint = p->has_viewpoint ? 1 : 0;
+    a.epsilon = p->epsilon, a.scale_floor = p->scale_floor;
+    for (int i = 0; i < 3; ++i) a.viewpoint[i] = p->has_viewpoint ? p->viewpoint[i] : 0.0f;
+    a.cov = reinterpret_cast<float4*>(cov), a.normals = normals, a.log_scales = log_scales, a.quats = quats, a.flags = flags;
+    HIP_TRY(dgr::launch_point_covariances(a, (hipStream_t)stream));
+    return DGR_OK;
+}
+size_t dgr_gicp_scratch_bytes(int n_target, int n_source) { return dgr::gicp_scratch_bytes(n_target, n_source); }
+int dgr_gicp_step(void* stream, const void* target_index, int n_target, const float* target, const float* target_cov, int n_source,
+                  const float* source, const float* source_cov, const float* transform_in, const dgr_gicp_params* params,
+                  void* scratch, float* transform_out, float* quat_out, float* trans_out, double* stats, int* idx_out,
+                  unsigned char* flags) {
+    const dgr_gicp_params* p = params;
+    const char* bad = nullptr;
+    if (n_target < 1 || n_target > (1 << 24)) bad = "n_target must be 1 .. 2^24";
+    if (!bad && (n_source < 1 || n_source > (1 << 24))) bad = "n_source must be 1 .. 2^24";
+    if (!bad && !p) bad = "params is NULL";
+    if (!bad && (!target_index || !dgr::aligned16(target_index))) bad = "target_index is NULL or not 16-byte aligned";
+    if (!bad && !target) bad = "target is NULL";
+    if (!bad && !source) bad = "source is NULL";
+    if (!bad && !dgr::aligned16(target_cov)) bad = "target_cov is not 16-byte aligned";
+    if (!bad && !dgr::aligned16(source_cov)) bad = "source_cov is not 16-byte aligned";
+    if (!bad && !transform_in) bad = "transform_in is NULL";
+    if (!bad && (!scratch || !dgr::aligned16(scratch))) bad = "scratch is NULL or not 16-byte aligned";
+    if (!bad && !transform_out) bad = "transform_out is NULL";
+    if (!bad && (!stats || (reinterpret_cast<uintptr_t>(stats) & 7u))) bad = "stats is NULL or not 8-byte aligned";
+    if (!bad && !(aligned_to(target, 4) && aligned_to(source, 4) && aligned_to(transform_in, 4) && aligned_to(transform_out, 4) &&
+                  aligned_to(quat_out, 4) && aligned_to(trans_out, 4) && aligned_to(idx_out, 4)))
+        bad = "target, source, a transform or an output is not 4-byte aligned";
+    if (!bad && !(p->dist_max >= 0.0f)) bad = "dist_max is NaN or negative";
+    if (!bad && !(p->huber_delta >= 0.0f)) bad = "huber_delta is NaN or negative";
+    if (!bad && !(p->damping >= 0.0f)) bad = "damping is NaN or negative";
+    if (!bad && !(p->rcond >= 0.0f)) bad = "rcond is NaN or negative";
+    if (!bad && p->min_points < 1) bad = "min_points must be at least 1";
+    if (bad) return refuse("dgr_gicp_step", bad);
+    dgr::GicpStepArgs a{};
+    a.N = n_target, a.S = n_source, a.target = target, a.source = source;
+    a.target_cov = reinterpret_cast<const float4*>(target_cov), a.source_cov = reinterpret_cast<const float4*>(source_cov);
+    a.transform_in = transform_in, a.huber_delta = p->huber_delta, a.damping = (double)p->damping, a.rcond = (double)p->rcond;
+    a.min_points = p->min_points;
+    a.transform_out = transform_out, a.quat_out = quat_out, a.trans_out = trans_out, a.stats = stats, a.flags = flags;
+    HIP_TRY(dgr::launch_gicp_step(a, target_index, p->dist_max, idx_out, scratch, (hipStream_t)stream));
+    return DGR_OK;
+}
+
 }  // extern "C"

@@ -539,6 +539,37 @@ struct KnnSearchCall {
     float* mean_dist2;  // [Q] or NULL
 };
 hipError_t launch_knn_search(const KnnSearchCall& call, hipStream_t stream);
+// generalized ICP over the kNN index (gicp.hip; include/dgr_hip.h: dgr_point_covariances, dgr_gicp_step): the neighbourhood
+// covariances of a cloud (one launch), and one Gauss-Newton iteration: the source moved by the estimate, the cross-mode search with
+// k = 1, the fused step (`scratch`: gicp_scratch_bytes() bytes whose first word is zero between calls)
+struct PointCovArgs {
+    int P, k;
+    const float* points;  // [P,3]
+    const int* idx;       // [P,k]
+    int mode, min_neighbours, has_viewpoint;
+    float epsilon, scale_floor, viewpoint[3];
+    float4* cov;  // [P,2] or NULL, as every output
+    float *normals, *log_scales, *quats;
+    unsigned char* flags;
+};
+hipError_t launch_point_covariances(const PointCovArgs& a, hipStream_t stream);
+struct GicpStepArgs {
+    int N, S;
+    const float *target, *source;           // [N,3], [S,3]
+    const float4 *target_cov, *source_cov;  // [N,2], [S,2] or NULL
+    const float* transform_in;
+    float huber_delta;
+    double damping, rcond;
+    int min_points;
+    float *transform_out, *quat_out, *trans_out;  // quat_out, trans_out: NULL = not stored
+    double* stats;
+    unsigned char* flags;  // NULL: not stored
+    const float* q;        // filled in by the launcher: the moved source and its association, in the scratch
+    const int* idx;
+};
+size_t gicp_scratch_bytes(int n_target, int n_source);  // 0: refused (a size outside 1 .. 2^24)
+hipError_t launch_gicp_step(const GicpStepArgs& args, const void* index, float dist_max, int* idx_out, void* scratch,
+                            hipStream_t stream);
 // view-independent covariance of a batch of views (preprocess_fwd.hip, preprocess_bwd.hip)
 hipError_t launch_cov3d_forward(int P, const float* scales, const float* rotations, float mod, float* cov3D, hipStream_t stream);
 hipError_t launch_cov3d_backward(int P, const float* scales, const float* rotations, float mod, const float* dL_dcov3D,

@@ -157,6 +157,21 @@ class KnnParams(C.Structure):  # dgr_knn_params
 assert C.sizeof(KnnParams) == 12  # three four-byte fields: the C layout
 KNN_MAX_K = 16  # DGR_KNN_MAX_K
 
+
+class CovarianceParams(C.Structure):  # dgr_covariance_params
+    _fields_ = [("mode", _i), ("epsilon", _f), ("min_neighbours", _i), ("scale_floor", _f), ("viewpoint", _f * 3), ("has_viewpoint", _i)]
+
+
+assert C.sizeof(CovarianceParams) == 32  # eight four-byte fields: the C layout
+COV_RAW, COV_PLANE = 0, 1  # DGR_COV_*
+
+
+class GicpParams(C.Structure):  # dgr_gicp_params
+    _fields_ = [("dist_max", _f), ("huber_delta", _f), ("damping", _f), ("rcond", _f), ("min_points", _i)]
+
+
+assert C.sizeof(GicpParams) == 20  # five four-byte fields: the C layout
+
 RELOCATE_MAX_TENSORS = 24  # DGR_RELOCATE_MAX_TENSORS
 RELOCATE_COPY, RELOCATE_OPACITY, RELOCATE_LOG_SCALE, RELOCATE_ZERO_TOUCHED, RELOCATE_ZERO_RELOCATED = range(5)  # DGR_RELOCATE_*
 TRANSFORM_MAX_TENSORS = 24  # DGR_TRANSFORM_MAX_TENSORS
@@ -226,6 +241,9 @@ _SIGS = {
     "dgr_knn_scratch_bytes": (_sz, [_i, _i]),
     "dgr_knn_build": (_i, [_vp, _i, _vp, _vp, _vp]),
     "dgr_knn_search": (_i, [_vp, _vp, _i, _vp, _i, _vp, C.POINTER(KnnParams), _vp, _vp, _vp, _vp, _vp]),
+    "dgr_point_covariances": (_i, [_vp, _i, _vp, _i, _vp, C.POINTER(CovarianceParams), _vp, _vp, _vp, _vp, _vp]),
+    "dgr_gicp_scratch_bytes": (_sz, [_i, _i]),
+    "dgr_gicp_step": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(GicpParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densification_stats": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
     "dgr_densify_plan_bytes": (_sz, [C.c_long]),
     "dgr_densify_plan": (_i, [_vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _vp, _vp]),

@@ -24,6 +24,8 @@ from .contrib import ContributionAccumulator, ContributionStats, contribution_st
 from .fusion import TsdfMesh, TsdfRaycast, TsdfVolume, extract_mesh, tsdf_bricks, tsdf_integrate, tsdf_raycast  # noqa: F401
 from .icp import IcpResult, depth_normals, icp_align  # noqa: F401
 from .knn import KnnIndex, KnnResult, dist2, knn_build, knn_search  # noqa: F401
+from .gicp import (GicpResult, PointCovariances, gaussian_covariances, gicp_align, gicp_step, point_covariances,  # noqa: F401
+                   unproject_depth)
 from .keyframes import KeyframeOverlap, keyframe_overlap, select_keyframes  # noqa: F401  (slam.X stays the public name)
 from .posegraph import PgoPlan, PgoResult, pose_graph_optimize, pose_graph_plan, relative_pose  # noqa: F401
 from .losses import MaskedLossStats, l1_loss, l1_ssim_loss, masked_l1_loss, ssim  # noqa: F401

@@ -1036,6 +1036,103 @@ int dgr_knn_search(void* stream, const void* index, int n_points, const float* p
                    const float* queries /* NULL: self mode */, const dgr_knn_params* params, void* scratch,
                    float* dist2 /* or NULL */, int* idx /* or NULL */, int* count /* or NULL */, float* mean_dist2 /* or NULL */);
 
+/* ---- generalized ICP over the kNN index: neighbourhood covariances and a fused Gauss-Newton step (csrc/gicp.hip) ----
+ * Segal's Generalized ICP: nearest-neighbour association in 3-D, a covariance per point, and the 6 x 6 step over
+ * sum e^T (C_B + R C_A R^T)^-1 e.  It aligns two clouds that need not overlap pixel for pixel: the loop edges that
+ * dgr_pgo_solve is fed, and GS-ICP SLAM's scan-to-map tracker (a map's own Sigma = R S S^T R^T as the target side).  No host
+ * read, no float atomics, no spin-wait, the same bits on every run, capturable into a hipGraph.
+ *
+ * dgr_point_covariances: ONE launch, one thread per point.  points [n_points,3] float32; idx [n_points,k] int32 as
+ * dgr_knn_search writes it, 1 <= k <= DGR_KNN_MAX_K.  A row's NEIGHBOURHOOD is its leading entries in [0, n_points): the first
+ * entry outside that range (-1 among them) ends the list, and nothing is read out of bounds.  Whether the point itself is among
+ * them is the caller's choice (self mode with or without exclude_self).  With n the neighbourhood's size, in double from the
+ * first operation (the fp32 coordinates widened), nothing contracted:
+ *   mu = (1/n) sum p_j, j in the row's order;   C = (1/n) sum (p_j - mu)(p_j - mu)^T in the same order
+ *   eigenpairs of C by cyclic Jacobi: V = I, then sweeps over the pairs (0,1), (0,2), (1,2) in that order.  A pair with
+ *     a_pq == 0 is skipped; otherwise theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) with
+ *     sgn(0) = +1, c = 1 / sqrt(t^2 + 1), s = t c;  a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0;  with r the third index
+ *     a_rp' = c a_rp - s a_rq, a_rq' = s a_rp + c a_rq;  V's columns p, q likewise.  The sweeps end when the three off-diagonal
+ *     entries are exactly zero, or after 16 sweeps (quadratic convergence reaches exact zeros in 6 to 10 on a covariance whose
+ *     entries are not denormal; 16 is the fixed bound).
+ *   the eigenvalues (A's diagonal) are clamped at 0 and sorted ascending with their columns, ties keeping column order:
+ *     lambda_0 <= lambda_1 <= lambda_2, v_0 the normal's axis.
+ * A row is INVALID when its own point or a point of its neighbourhood has a non-finite coordinate, n < min_neighbours, or
+ * lambda_2 is 0 (or not finite): all its outputs are +0 and its flag 0.  Outputs, each optional (NULL):
+ *   cov [n_points,8] float32, 16-byte aligned rows (c00, c01, c02, c11, c12, c22, sigma, n): sigma = lambda_0 / (lambda_0 +
+ *     lambda_1 + lambda_2) (the surface variation), n the neighbourhood's size as a float, 0 = invalid.  mode DGR_COV_RAW: C
+ *     rounded once; DGR_COV_PLANE (GICP's (epsilon, 1, 1) replacement): I - (1 - epsilon) v_0 v_0^T, rounded once.
+ *   normals [n_points,4] = (v_0, sigma): v_0 turned so that v_0 . (viewpoint - p) >= 0 with has_viewpoint (with the viewpoint
+ *     at the origin of a camera-frame cloud: dgr_depth_normals' facing convention), otherwise so that its largest-magnitude
+ *     component (the first such) is positive.
+ *   log_scales [n_points,3] = 0.5 log(max(lambda, scale_floor^2)), largest first, and quats [n_points,4] (r, x, y, z; unit,
+ *     r >= 0) of the frame (v_2, +-v_1, the oriented v_0), v_1's sign chosen for det +1: the anisotropic Gaussian the
+ *     neighbourhood spans (GS-ICP SLAM's seeds; dgr_knn_search's mean_dist2 gives only an isotropic scale).
+ *   flags [n_points] bytes: bit 0 valid.
+ * Refused with DGR_ERR_BAD_ARGUMENT and a message before any device call: n_points outside 1 .. 2^24; k outside 1 .. 16; a NULL
+ * points, idx or params; all five outputs NULL; cov not 16-byte aligned; an unknown mode; epsilon not in (0, 1];
+ * min_neighbours < 3 or > k; a NaN scale_floor; with has_viewpoint a NaN in viewpoint. */
+#define DGR_COV_RAW 0
+#define DGR_COV_PLANE 1
+typedef struct dgr_covariance_params {
+    int mode;            /* DGR_COV_RAW or DGR_COV_PLANE */
+    float epsilon;       /* (0, 1]: the variance along the normal in PLANE mode (GICP: 1e-3) */
+    int min_neighbours;  /* 3 .. k */
+    float scale_floor;   /* the smallest standard deviation log_scales reports (its square is the floor on lambda) */
+    float viewpoint[3];
+    int has_viewpoint;   /* 0: viewpoint is not read */
+} dgr_covariance_params;
+int dgr_point_covariances(void* stream, int n_points, const float* points, int k, const int* idx,
+                          const dgr_covariance_params* params, float* cov /* or NULL */, float* normals /* or NULL */,
+                          float* log_scales /* or NULL */, float* quats /* or NULL */, unsigned char* flags /* or NULL */);
+
+/* dgr_gicp_step: one Gauss-Newton iteration in one C call.  Inputs: target_index, what dgr_knn_build made of target
+ * [n_target,3]; target_cov [n_target,8] or NULL and source_cov [n_source,8] or NULL, rows as dgr_point_covariances packs them
+ * (any symmetric positive C with n > 0 will do: a Gaussian map's own covariances); source [n_source,3]; transform_in[16], which
+ * maps source to target coordinates, stored transposed with the translation at [12..14] (R[j][c] at [4 c + j]): dgr_pgo_solve's
+ * measurement layout, so that with the source a cloud in camera j's frame and the target one in camera i's the result is Z_ij.
+ * Launches, no host read between them:
+ *   1. gicp_transform_kernel: q_i = R a_i + t into the scratch, in fp32 with every operation rounded once (__fmul_rn,
+ *      __fadd_rn): q_i0 = ((R00 a0 + R01 a1) + R02 a2) + t0 and likewise; R and t are transform_in's bits.  A non-finite
+ *      source row stays non-finite.
+ *   2. dgr_knn_search's launches in cross mode with queries q, k = 1 and max_dist2 = the fp32 product dist_max * dist_max,
+ *      writing idx to the scratch (or idx_out [n_source] when given): the association is the kNN rule's answer bit for bit.
+ *   3. gicp_step_kernel, of dgr_icp_step's shape: a workgroup of 256 threads per block of 2048 sources, a thread's sources
+ *      ascending, the workgroup's threads by the block sum, one 256-byte row per block, the blocks in block order.
+ * A source i is VALID when q_i is finite and, with source_cov, its own row has n > 0; ASSOCIATED when valid, j = idx[i] >= 0
+ * and, with target_cov, the target's row j has n > 0.  Per associated pair, in double from the widened fp32 inputs:
+ *   e = q - b_j;  C = C_B + R C_A R^T (a NULL side contributes nothing; both NULL: C = I, point-to-point ICP)
+ *   M = adj(C) / det(C); det <= 0 or not finite: the pair is SINGULAR and dropped
+ *   s^2 = max(e^T M e, 0), s = sqrt(s^2);  w = 1 for s <= huber_delta, else huber_delta / s
+ *   J = [-[q]x | I]: the left perturbation T <- exp(xi) T, the rotation part first
+ * Sums in dgr_icp_step's layout and double accumulation: the 21 upper-triangle entries of A = sum w J^T M J (row-major), the
+ * 6 of b = sum w J^T M e, sum w s^2, the count.  Solve, one thread in double: dgr_icp_step's -- M xi = -b by LDL^T on A + damping
+ * diag(max(A_ii, 1e-3 max A_ii)); refused when count < min_points, a pivot <= rcond max A_ii, or anything is not finite.
+ * T_out = exp(xi) T_in, its rotation re-orthonormalised through its unit quaternion.
+ * Outputs: transform_out[16] (may be transform_in: the finishing workgroup reads before it writes); quat_out[4] (r, x, y, z;
+ * unit, r >= 0) and trans_out[3] or NULL; stats, 32 doubles in dgr_icp_step's order: A (21), b (6), sum w s^2 [27], count [28],
+ * ok [29], |omega| [30], |v| [31]; flags [n_source] bytes or NULL: bit 0 valid, bit 1 associated, bit 2 singular.  A refused
+ * step writes the input's bits to every pose output (quat_out derived from the input matrix).
+ * `scratch`: dgr_gicp_scratch_bytes(n_target, n_source) bytes (0 for a shape it refuses), 16-byte aligned.  Its first 16 bytes
+ * hold the ticket and MUST BE ZERO before the first call that uses it; every call leaves them zero, so one zero-filled
+ * allocation of the largest shape serves any number of calls in stream order, and a recorded graph replays.  The scratch belongs
+ * to the call while it is in flight, as dgr_knn_search's does: the search sorts the queries' rows through it and reads them back
+ * as indices, so nothing else may write it (a zero-fill still pending on another stream included) until the call has finished.
+ * Refused with a message before any device call: n_target or n_source outside 1 .. 2^24; a NULL target_index, target, source,
+ * transform_in, params, scratch, transform_out or stats; target_index, target_cov, source_cov or scratch not 16-byte aligned,
+ * stats not 8-byte aligned; dist_max, huber_delta, damping or rcond NaN or negative; min_points < 1. */
+typedef struct dgr_gicp_params {
+    float dist_max;     /* >= 0: largest |q - b| of an association (INFINITY: the nearest target point whatever its distance) */
+    float huber_delta;  /* >= 0 on s, the Mahalanobis length; INFINITY = least squares */
+    float damping;      /* >= 0; 0 = Gauss-Newton */
+    float rcond;        /* >= 0: smallest pivot accepted, relative to the largest diagonal entry of A */
+    int min_points;     /* >= 1 */
+} dgr_gicp_params;
+size_t dgr_gicp_scratch_bytes(int n_target, int n_source);
+int dgr_gicp_step(void* stream, const void* target_index, int n_target, const float* target, const float* target_cov /* or NULL */,
+                  int n_source, const float* source, const float* source_cov /* or NULL */, const float* transform_in,
+                  const dgr_gicp_params* params, void* scratch, float* transform_out, float* quat_out /* or NULL */,
+                  float* trans_out /* or NULL */, double* stats, int* idx_out /* or NULL */, unsigned char* flags /* or NULL */);
+
 /* Process-wide options (default 0 unless stated).
  *  "alpha_mode": how the blend kernels evaluate alpha = min(0.99, o exp(power)) and T / (1 - alpha).  0 (default) = the
  *     reference's expression in the reference's association (forward.cu:354-364, backward.cu:561-570) with an expf and a
