@@ -8,6 +8,11 @@ factor 2 covers another equally valid order or fused multiply-adds), floor = 8 f
 epsilons per view, and the averaging lets at most a few views' worth survive: 8 eps = 9.5e-7 for the colours in [0, 1], twice
 that for the tsdf, whose range [-1, 1] has size 2.
 Figures measured on the MI355X: profiles/tsdf/measured.txt.
+The view loop and the brick culling (tests/tsdf_model.py: MANY_CASES, CULLING) go through the same comparison: scenes of up to 513
+views of which a few see the lattice, at every line of the loop (a ballot's high half, waves 1-3, a later chunk, a partial one), and
+poses at which the culling decides (cameras inside the lattice, rolled, a near plane across it, a principal point outside the image,
+fx != fy); a view fused under a wrong number would fuse a constant image or miss a rendered one.  Where every view is live the
+model's ambiguous share has no bound: there the bits of one call are held against those of calls of at most five views.
 
 Extraction.  From volumes written directly as analytic distance fields over the truncation, with irrational centres and radii
 (no value is exactly 0): the triangle count per cell equals the model's (the sign decisions are taken on the same float32
@@ -56,15 +61,7 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def pattern(s, seed=5):
-    """a volume that is recognisably not empty: tsdf in (-1, 1) without zeros, weights in [0.5, 3] (quarters: their sums with a
-    view's weight are exact in float32 as in float64, so the weights can be compared for equality), colours in (0, 1)"""
-    rng = np.random.default_rng(seed)
-    nx, ny, nz = s["dims"]
-    tsdf = rng.uniform(0.05, 0.95, (nz, ny, nx)) * rng.choice([-1.0, 1.0], (nz, ny, nx))
-    vol = np.stack([tsdf, rng.integers(2, 13, (nz, ny, nx)) / 4.0], axis=-1).astype(np.float32)
-    col = np.concatenate([rng.uniform(0.01, 0.99, (nz, ny, nx, 3)), np.zeros((nz, ny, nx, 1))], axis=-1).astype(np.float32)
-    return vol, col
+pattern = M.pattern
 
 
 def check_against_model(name, s, volume=None, color_volume=None, with_color=True, mask=None, **opts):
@@ -223,6 +220,113 @@ def test_integrate_captured_into_a_graph_equals_eager():
         graph.replay()
         got = host(vol)
         assert np.array_equal(bits(got[0]), bits(eager[name][0])) and np.array_equal(bits(got[1]), bits(eager[name][1])), name
+
+
+# ---- the view loop (chunks of 256 views, a ballot per wave of 64) and the brick culling; the scenes and the conditions under which
+# they say something: tests/tsdf_model.py, tests/test_tsdf_model.py
+
+def same_bits(a, b):
+    return np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
+
+
+def fused(s, start, calls, **opts):
+    """the (volume, colour) after one fuse() per entry of `calls` (index lists or slices), from `start`"""
+    vol = make_volume(s, *start)
+    for part in calls:
+        fuse(vol, s, part, **opts)
+    return host(vol)
+
+
+MANY_GPU = ["64-high-half", "65-wave-1", "256-waves-1-3", "257-second-chunk", "257-first-chunk-blind", "513-three-chunks"]
+
+
+@pytest.mark.parametrize("name", MANY_GPU)
+def test_many_views_equal_the_model(name):
+    s = M.many_case(name)
+    check_against_model("many " + name, s, *M.pattern(s), **M.MANY_OPTS)
+
+
+@pytest.mark.parametrize("name", ["257-second-chunk", "257-first-chunk-blind", "513-three-chunks"])
+def test_many_views_in_one_call_equal_the_live_views_alone_bit_for_bit(name):
+    s = M.many_case(name)
+    start = M.pattern(s)
+    whole = fused(s, start, [slice(None)], **M.MANY_OPTS)
+    assert same_bits(fused(s, start, [s["live"]], **M.MANY_OPTS), whole)
+    assert same_bits(fused(s, start, [[v] for v in s["live"]], **M.MANY_OPTS), whole)
+    assert not np.array_equal(bits(whole[0]), bits(start[0])) and not np.array_equal(bits(whole[1]), bits(start[1]))
+    changed = (bits(whole[0]) != bits(start[0])).any(axis=-1)
+    print(f"tsdf-measured many {name} bits: views {len(s['views'])} live {len(s['live'])} samples {changed.size} changed {changed.mean():.4f}; "
+          f"one call = the live views in one call = a call per live view")
+
+
+def test_three_hundred_live_views_equal_sixty_calls_of_five():
+    s = M.many_view_scene(live=range(M.ALL_LIVE["V"]), **M.ALL_LIVE)
+    start = M.pattern(s)
+    whole = fused(s, start, [slice(None)], max_weight=4.0)
+    assert same_bits(fused(s, start, [slice(v, v + 5) for v in range(0, 300, 5)], max_weight=4.0), whole)
+    assert same_bits(fused(s, start, [slice(0, 256), slice(256, 300)], max_weight=4.0), whole)
+    first = fused(s, start, [slice(0, 256)], max_weight=4.0)
+    assert not same_bits(whole, start) and not np.array_equal(bits(whole[0]), bits(first[0])) and not np.array_equal(bits(whole[1]), bits(first[1]))
+    changed = (bits(whole[0]) != bits(start[0])).any(axis=-1)
+    print(f"tsdf-measured all-live 300: samples {changed.size} changed {changed.mean():.4f} changed by views 256.. "
+          f"{(bits(whole[0]) != bits(first[0])).any(axis=-1).mean():.4f}")
+
+
+@pytest.mark.parametrize("name", sorted(M.CULLING))
+def test_culling_scenes_equal_the_model(name):
+    s, opts = M.culling_case(name)
+    start = M.pattern(s)
+    _, _, touched, amb = check_against_model("culling " + name, s, *start, **opts)
+    share = M.brick_shares(touched)
+    assert (share == 0).sum() >= 5 and ((share > 0) & (share < 1)).sum() >= 5
+    _, gcol, _, _ = check_against_model("culling " + name + " no-colour", s, *start, with_color=False, **opts)
+    assert np.array_equal(bits(gcol), bits(start[1]))
+
+
+def test_a_graph_replay_with_many_views():
+    s, other = M.many_case("257-second-chunk"), M.many_case("257-moved")
+    assert other["live"] == [1, 65, 256] and other["dims"] == s["dims"]
+    start = M.pattern(s)
+    eager = {name: fused(sc, start, [slice(None)], **M.MANY_OPTS) for name, sc in (("first", s), ("moved", other))}
+    assert not same_bits(eager["first"], eager["moved"])
+    vol = make_volume(s, *start)
+    depth, color, views = T(s["depth"]), T(s["color"]), T(s["views"])
+    step = lambda: slam.tsdf_integrate(vol, depth, views, s["fx"], s["fy"], s["cx"], s["cy"], color=color, **M.MANY_OPTS)  # noqa: E731
+    graph, side = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        step()
+        side.synchronize()
+        with torch.cuda.graph(graph, stream=side):
+            step()
+    for name, sc in (("moved", other), ("first", s)):
+        vol.volume.copy_(T(start[0]))
+        vol.color.copy_(T(start[1]))
+        depth.copy_(T(sc["depth"]))
+        color.copy_(T(sc["color"]))
+        views.copy_(T(sc["views"]))
+        graph.replay()
+        got = host(vol)
+        print(f"tsdf-measured graph replay 257 views, live {sc['live']}: changed {(bits(got[0]) != bits(start[0])).any(axis=-1).mean():.4f}")
+        assert same_bits(got, eager[name]), name
+
+
+def test_the_wrapper_takes_strided_inputs_of_many_views():
+    """every other view of a 514-view batch, as strided tensors: 257 views, the same bits as from contiguous copies"""
+    s = M.many_case("257-second-chunk")
+    start = M.pattern(s)
+    want = fused(s, start, [slice(None)], **M.MANY_OPTS)
+
+    def strided(a):
+        wide = torch.full((2 * a.shape[0],) + a.shape[1:], float("nan"), dtype=torch.float32, device=DEV)
+        wide[::2] = T(a)
+        return wide[::2]
+    depth, color, views = strided(s["depth"]), strided(s["color"]), strided(s["views"])
+    assert not depth.is_contiguous() and not color.is_contiguous() and not views.is_contiguous()
+    vol = make_volume(s, *start)
+    slam.tsdf_integrate(vol, depth, views, s["fx"], s["fy"], s["cx"], s["cy"], color=color, **M.MANY_OPTS)
+    got = host(vol)
+    print(f"tsdf-measured strided 257 of 514 views: changed {(bits(got[0]) != bits(start[0])).any(axis=-1).mean():.4f}")
+    assert same_bits(got, want)
 
 
 # ---- extraction

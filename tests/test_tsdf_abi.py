@@ -1,6 +1,7 @@
 """The TSDF entry points (include/dgr_hip.h: dgr_tsdf_integrate, dgr_mesh_scratch_bytes, dgr_mesh_plan, dgr_mesh_emit) and their
 Python surface without a GPU: declared, exported and bound; the two descriptors' layouts against the header text; every argument
-error refused with its message before any device call (FAKE pointers: nothing is dereferenced); the scratch size."""
+error refused with its message before any device call (FAKE pointers: nothing is dereferenced); the scratch size.  One test is
+marked gpu: the entry point with 65 536 views."""
 import ctypes as C
 import re
 
@@ -195,3 +196,60 @@ def test_python_surface_refuses_what_it_cannot_read():
         slam.extract_mesh(v, min_weight=NAN)
     with pytest.raises(ValueError, match="max_triangles must be"):
         slam.extract_mesh(v, max_triangles=-1)
+
+
+def test_python_surface_takes_more_views_than_a_chunk():
+    """V > 256 passes every shape check (the device check, the last one, is what refuses CPU tensors); a wrong V anywhere is named"""
+    v = slam.TsdfVolume((0, 0, 0), 0.1, (4, 4, 4), device="cpu")
+    ok = dict(fx=10.0, fy=10.0, cx=4.0, cy=3.0)
+    for V in (257, 600):
+        d, m, c, k = torch.ones(V, 6, 8), torch.eye(4).repeat(V, 1, 1), torch.ones(V, 3, 6, 8), torch.ones(V, 6, 8)
+        with pytest.raises(ValueError, match="must live on the GPU"):
+            slam.tsdf_integrate(v, d, m, **ok, color=c, mask_image=k)
+        with pytest.raises(ValueError, match="must live on the GPU"):  # strided: every other view of a batch twice as long
+            slam.tsdf_integrate(v, d.repeat(2, 1, 1)[::2], m.repeat(2, 1, 1)[::2], **ok, color=c.repeat(2, 1, 1, 1)[::2])
+        with pytest.raises(ValueError, match=rf"viewmatrices must be float32 \[{V}, 4, 4\]"):
+            slam.tsdf_integrate(v, d, m[:256], **ok)
+        with pytest.raises(ValueError, match=rf"color must be float32 \[{V}, 3, 6, 8\]"):
+            slam.tsdf_integrate(v, d, m, **ok, color=c[:V - 1])
+        with pytest.raises(ValueError, match=rf"mask_image must be float32 \[{V}, 6, 8\]"):
+            slam.tsdf_integrate(v, d, m, **ok, mask_image=k[:256])
+
+
+@pytest.mark.gpu
+def test_sixty_five_thousand_blind_views_in_one_call_leave_the_sample_alone():
+    """n_views = 65 536 through the C ABI (256 chunks of the view loop), a 1 x 1 x 1 lattice, a 1 x 1 image: DGR_OK, the bits kept"""
+    import numpy as np
+    import tsdf_model as M
+    V, dev = 1 << 16, torch.device("cuda:0")
+    origin, voxel = (0.011, -0.017, 1.47), 0.05
+    kinds = np.stack([M.pose(rx, ry, 0.0, t) for rx, ry, t in M.BLIND_KINDS])
+    one = np.full((len(kinds), 1, 1), M.BLIND_DEPTH, dtype=np.float32)
+    start = np.array([[[[0.375, 1.25]]]], dtype=np.float32), np.array([[[[0.25, 0.5, 0.75, 0.0]]]], dtype=np.float32)
+    model = M.integrate(start[0], start[1], origin, voxel, 0.2, one, kinds, 0.9, 0.9, 0.1, -0.1, color=np.repeat(one[:, None], 3, axis=1))
+    assert not model[3].any() and not model[2].any()  # blind in the model, and not next to a decision
+    views = torch.from_numpy(np.ascontiguousarray(np.tile(kinds, (V // len(kinds) + 1, 1, 1))[:V])).to(dev)
+    depth = torch.full((V, 1, 1), M.BLIND_DEPTH, dtype=torch.float32, device=dev)
+    image = torch.full((V, 3, 1, 1), M.BLIND_COLOR, dtype=torch.float32, device=dev)
+    volume, color = torch.from_numpy(start[0]).to(dev), torch.from_numpy(start[1]).to(dev)
+    grid = _capi.TsdfGrid(1, 1, 1, (C.c_float * 3)(*origin), voxel)
+    params = _capi.TsdfParams(0.9, 0.9, 0.1, -0.1, 0.2, 1.0, INF, 0.0, INF, 0.05, 0.99)
+    rc = _capi.load().dgr_tsdf_integrate(_capi.stream_handle(0), grid, volume.data_ptr(), color.data_ptr(), V, 1, 1, depth.data_ptr(),
+                                         image.data_ptr(), None, views.data_ptr(), params)
+    assert rc == _capi.DGR_OK, _capi.last_error()
+    torch.cuda.synchronize()
+    assert np.array_equal(volume.cpu().numpy().view(np.uint32), start[0].view(np.uint32))
+    assert np.array_equal(color.cpu().numpy().view(np.uint32), start[1].view(np.uint32))
+    # and with the last view the one that sees it, the sample is that view's: the loop reached view 65 535
+    views[V - 1] = torch.from_numpy(M.pose(0.0, 0.0, 0.0, [0.0, 0.0, 0.0])).to(dev)
+    rc = _capi.load().dgr_tsdf_integrate(_capi.stream_handle(0), grid, volume.data_ptr(), color.data_ptr(), V, 1, 1, depth.data_ptr(),
+                                         image.data_ptr(), None, views.data_ptr(), params)
+    assert rc == _capi.DGR_OK, _capi.last_error()
+    torch.cuda.synchronize()
+    # depth 2 is more than a truncation in front of z = 1.47: t = 1, (x w + t) / (w + 1) with w = 1.25; two products, a sum and a
+    # quotient of values <= 1, half an epsilon each: 2 eps
+    got, gcol, eps = volume.cpu().numpy().astype(np.float64), color.cpu().numpy().astype(np.float64), float(np.finfo(np.float32).eps)
+    print(f"tsdf-measured 65536 views, the last one live: weight {got[0, 0, 0, 1]} tsdf error {abs(got[0, 0, 0, 0] - (0.375 * 1.25 + 1.0) / 2.25):.3e} "
+          f"(bound {2 * eps:.3e})")
+    assert got[0, 0, 0, 1] == 2.25 and abs(got[0, 0, 0, 0] - (0.375 * 1.25 + 1.0) / 2.25) <= 2 * eps
+    assert np.abs(gcol[0, 0, 0, :3] - (start[1][0, 0, 0, :3].astype(np.float64) * 1.25 + M.BLIND_COLOR) / 2.25).max() <= 2 * eps and gcol[0, 0, 0, 3] == 0.0

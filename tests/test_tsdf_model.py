@@ -1,6 +1,8 @@
 """The numpy model of the TSDF steps (tests/tsdf_model.py) on its own, without a GPU: the fused values of a plane and a sphere
 against their analytic distance fields; the share of samples next to a decision in every scene the GPU tests use; float32 against
-float64 outside that mask; marching tetrahedra against analytic surfaces (closed, Euler characteristic, volume, orientation)."""
+float64 outside that mask; marching tetrahedra against analytic surfaces (closed, Euler characteristic, volume, orientation); and
+what keeps the GPU tests of the view loop and the brick culling from passing vacuously: blind views that touch nothing, live views
+that each touch something and whose order shows, bricks left out and bricks cut in every culling scene."""
 import numpy as np
 import pytest
 
@@ -94,3 +96,75 @@ def test_min_weight_and_empty_volumes():
     assert not cells[:, 2:4, :].any() and np.array_equal(cells[:, :2], counts.reshape(4, 6, 8)[:, :2])
     assert M.triangles(np.ones((3, 3, 3, 2), np.float32), origin, h)[0].sum() == 0
     assert M.triangles(np.ones((1, 3, 3, 2), np.float32), origin, h)[1].shape == (0, 3, 3)
+
+
+# ---- the scenes for the integrate kernel's view loop and brick culling: the conditions under which the GPU tests say something
+
+EPS = float(np.finfo(np.float32).eps)
+
+
+def _fused(s, fn=M.integrate, **opts):
+    start = M.pattern(s)
+    return M.run(s, fn, start[0].copy(), start[1].copy(), **opts)
+
+
+def _gpu_tolerance(v64, v32, amb):
+    """what tests/test_hip_tsdf.py's check_against_model allows the tsdf: max(2 e32, 2 FLOOR), FLOOR = 8 eps"""
+    return max(2 * float(np.abs(v32[..., 0] - v64[..., 0])[~amb].max(initial=0.0)), 2 * 8 * EPS)
+
+
+@pytest.mark.parametrize("name", sorted(M.MANY_CASES))
+def test_many_view_scenes_show_a_wrong_view_number(name):
+    s = M.many_case(name)
+    V, live = M.MANY_CASES[name]
+    assert len(s["views"]) == V and s["live"] == sorted(live) and 1 <= len(live) <= 8
+    assert len({v.tobytes() for v in s["views"]}) == V  # no two poses are equal
+    blind = M.blind_views(s)
+    assert (s["depth"][blind] == np.float32(M.BLIND_DEPTH)).all() and (s["color"][blind] == np.float32(M.BLIND_COLOR)).all()
+    if blind:
+        _, _, amb, touched = _fused(M.sub_scene(s, blind), **M.MANY_OPTS)
+        assert not touched.any() and not amb.any()
+        kinds = {k % len(M.BLIND_KINDS) for k in blind}
+        assert len(kinds) >= min(len(M.BLIND_KINDS), 4)
+    v64, c64, amb, touched = _fused(s, **M.MANY_OPTS)
+    assert amb.mean() <= 0.03, amb.mean()
+    v32, c32, _, _ = _fused(s, M.integrate32, **M.MANY_OPTS)
+    assert np.array_equal(v32[..., 1][~amb], v64[..., 1][~amb])
+    for v in s["live"]:
+        assert M.run(M.sub_scene(s, [v]), **M.MANY_OPTS)[3].any(), v
+    print(name, "ambiguous", amb.mean(), "touched", touched.mean())
+    if len(live) >= 2:  # (a single live view has no order)
+        back, _, amb_back, _ = _fused(M.sub_scene(s, s["live"][::-1]), **M.MANY_OPTS)
+        alone, _, amb_alone, _ = _fused(M.sub_scene(s, s["live"]), **M.MANY_OPTS)
+        assert np.array_equal(alone, v64) and np.array_equal(amb_alone, amb) and np.array_equal(amb_back, amb)  # (the blind views: nothing)
+        assert np.abs(back[..., 0] - v64[..., 0])[~amb].max() > 100 * _gpu_tolerance(v64, v32, amb)
+
+
+def test_every_view_of_the_all_live_scene_touches_a_sample():
+    s = M.many_view_scene(live=range(M.ALL_LIVE["V"]), **M.ALL_LIVE)
+    assert len({v.tobytes() for v in s["views"]}) == 300
+    for v in range(300):
+        assert M.run(M.sub_scene(s, [v]))[3].any(), v
+
+
+@pytest.mark.parametrize("name", sorted(M.CULLING))
+def test_culling_scenes_leave_bricks_out_and_cut_bricks(name):
+    s, opts = M.culling_case(name)
+    assert s["dims"] == (130, 10, 12) and len(s["views"]) == 2
+    v64, c64, amb, touched = _fused(s, **opts)
+    assert amb.mean() <= 0.03, amb.mean()
+    v32, c32, _, _ = _fused(s, M.integrate32, **opts)
+    assert np.array_equal(v32[..., 1][~amb], v64[..., 1][~amb])
+    share = M.brick_shares(touched)
+    assert share.shape == (12, 3, 3)
+    untouched, partly = int((share == 0).sum()), int(((share > 0) & (share < 1)).sum())
+    print(name, "ambiguous", amb.mean(), "touched", touched.mean(), "bricks untouched", untouched, "partly", partly, "of", share.size)
+    assert untouched >= 5 and partly >= 5
+    for v in range(2):
+        assert M.run(M.sub_scene(s, [v]), **opts)[3].any(), v
+    if name in ("inside", "minus-x"):
+        near = opts.get("near", 0.05)
+        for view in s["views"]:
+            z = M.brick_corner_depths(s, view)
+            assert ((z.min(axis=-1) < near) & (z.max(axis=-1) > near)).any()
+            assert ((z.min(axis=-1) < 0.0) & (z.max(axis=-1) > near)).any()  # (and of 0: where the side planes' signs turn)

@@ -4,6 +4,7 @@ to a decision; `integrate32` the same arithmetic in float32 (it only sizes the t
 without a case table: per tetrahedron the sign-changing edges are intersected, the polygon is ordered geometrically around the
 gradient of the four values, started at the edge with the smallest corner pair and fanned from there.  Also the scenes the
 tests fuse and the analytic distance fields they extract from."""
+import functools
 import itertools
 
 import numpy as np
@@ -258,3 +259,166 @@ def run(s, fn=integrate, volume=None, color_volume=None, with_color=True, **opts
         color_volume = np.zeros((nz, ny, nx, 4), dtype=np.float32)
     return fn(volume, color_volume if with_color else None, s["origin"], s["voxel"], np.float32(4.0 * s["voxel"]), s["depth"], s["views"],
               s["fx"], s["fy"], s["cx"], s["cy"], color=s["color"] if with_color else None, **opts)
+
+
+def pattern(s, seed=5):
+    """a volume that is recognisably not empty: tsdf in (-1, 1) without zeros, weights in [0.5, 3] (quarters: their sums with a
+    view's weight are exact in float32 as in float64, so the weights can be compared for equality), colours in (0, 1)"""
+    rng = np.random.default_rng(seed)
+    nx, ny, nz = s["dims"]
+    tsdf = rng.uniform(0.05, 0.95, (nz, ny, nx)) * rng.choice([-1.0, 1.0], (nz, ny, nx))
+    vol = np.stack([tsdf, rng.integers(2, 13, (nz, ny, nx)) / 4.0], axis=-1).astype(np.float32)
+    col = np.concatenate([rng.uniform(0.01, 0.99, (nz, ny, nx, 3)), np.zeros((nz, ny, nx, 1))], axis=-1).astype(np.float32)
+    return vol, col
+
+
+# ---- scenes for the view loop and the brick culling of the integrate kernel: a workgroup owns a brick of 64 x 4 x 1 samples, tests
+# the views in chunks of 256 (four ballots of 64) and walks the views its brick can see
+
+BRICK_X, BRICK_Y = 64, 4
+
+
+def pose_at(c, rx, ry, rz):
+    """`pose` given by the camera centre c: t = -R c"""
+    R = pose(rx, ry, rz, [0.0, 0.0, 0.0]).astype(np.float64).T[:3, :3]
+    return pose(rx, ry, rz, -R @ np.asarray(c, dtype=np.float64))
+
+
+def with_frames(s, poses, holes=True):
+    """the scene dict `s` with `poses` and what they see of the sphere and the wall"""
+    frames = [render_scene(p, s["H"], s["W"], s["fx"], s["fy"], s["cx"], s["cy"], holes) for p in poses]
+    s.update(depth=np.stack([f[0] for f in frames]), color=np.stack([f[1] for f in frames]), views=np.stack(poses))
+    return s
+
+
+def sub_scene(s, index):
+    """the scene with the views `index` (a list or a slice) only, in that order"""
+    return dict(s, depth=s["depth"][index], color=s["color"][index], views=s["views"][index])
+
+
+def live_pose(rng):
+    """a pose that sees the lattices in front of the identity: up to +-0.25 rad and +-0.3 m around it"""
+    return pose(*rng.uniform(-0.25, 0.25, 3), rng.uniform(-0.3, 0.3, 3))
+
+
+# poses that see nothing of a lattice in front of the identity, one kind per test of the culling (rx, ry, t): facing away and far
+# behind the camera (`behind`), and the lattice past each of the image's four sides
+BLIND_KINDS = [(0.0, np.pi, (0.0, 0.0, 0.0)), (0.0, 1.4, (0.0, 0.0, 0.0)), (-1.3, 0.0, (0.0, 0.0, 0.0)), (0.0, 0.0, (0.0, 0.0, -10.0)),
+               (0.0, -1.4, (0.0, 0.0, 0.0)), (1.3, 0.0, (0.0, 0.0, 0.0))]
+BLIND_DEPTH, BLIND_COLOR = 2.0, 0.5
+
+
+def blind_pose(k, rng):
+    """the k-th kind (in rotation), jittered so that no two blind poses are equal"""
+    rx, ry, t = BLIND_KINDS[k % len(BLIND_KINDS)]
+    j = rng.uniform(-1.0, 1.0, 5)
+    return pose(rx + 0.03 * j[0], ry + 0.03 * j[1], 0.0, np.array(t) + 0.05 * j[2:])
+
+
+def many_view_scene(V, live, dims, origin, voxel, seed):
+    """V views of which only the indices `live` see the lattice: distinct seeded poses with their rendered depth and colour; the
+    others are blind poses with a constant valid depth and a constant colour, so that a blind image under a live pose, or a live
+    image under a blind pose, would change the result.  `live` is kept in the dict (sorted)."""
+    rng = np.random.default_rng(seed)
+    s = dict(MAIN, dims=tuple(dims), origin=tuple(origin), voxel=voxel, live=sorted(int(v) for v in live))
+    assert len(set(s["live"])) == len(s["live"]) and all(0 <= v < V for v in s["live"])
+    H, W = s["H"], s["W"]
+    depth = np.full((V, H, W), BLIND_DEPTH, dtype=np.float32)
+    color = np.full((V, 3, H, W), BLIND_COLOR, dtype=np.float32)
+    views = np.stack([blind_pose(k, rng) for k in range(V)])
+    for v in s["live"]:
+        views[v] = live_pose(rng)
+        depth[v], color[v] = render_scene(views[v], H, W, s["fx"], s["fy"], s["cx"], s["cy"])
+    s.update(depth=depth, color=color, views=views)
+    return s
+
+
+def blind_views(s):
+    return [v for v in range(len(s["views"])) if v not in s["live"]]
+
+
+# the lattice of the many-view cases: two bricks along x and two along y, both hanging over the lattice's edge
+MANY = dict(dims=(70, 6, 3), origin=(-1.7, -0.13, 1.6), voxel=0.05)
+MANY_OPTS = dict(max_weight=3.0)
+# name -> (V, live): a case per line of the view loop
+MANY_CASES = {
+    "64-high-half": (64, (31, 32, 63)),
+    "65-wave-1": (65, (0, 63, 64)),
+    "256-waves-1-3": (256, (64, 127, 128, 191, 192, 255)),
+    "257-second-chunk": (257, (0, 63, 64, 255, 256)),
+    "257-first-chunk-blind": (257, (256,)),
+    "513-three-chunks": (513, (5, 64, 255, 256, 300, 511, 512)),
+    "257-moved": (257, (1, 65, 256)),  # (the scene a captured 257-view call is replayed on)
+}
+# seeds at which no sample of a blind view sits within NEAR_EPS of the near plane (a pose that looks past the lattice has samples on
+# both sides of it) and the ambiguous share stays well under the cap (tests/test_tsdf_model.py holds them to both)
+MANY_SEEDS = {"64-high-half": 101, "65-wave-1": 101, "256-waves-1-3": 102, "257-second-chunk": 102, "257-first-chunk-blind": 102,
+              "513-three-chunks": 102, "257-moved": 102}
+ALL_LIVE = dict(V=300, dims=(7, 5, 3), origin=(-0.2, -0.1, 1.45), voxel=0.04, seed=7)  # every view live: no model, bits only
+
+
+@functools.lru_cache(maxsize=None)
+def many_case(name):
+    """the scene of MANY_CASES[name] on the MANY lattice (shared: leave it unchanged)"""
+    V, live = MANY_CASES[name]
+    s = many_view_scene(V, live, seed=MANY_SEEDS[name], **MANY)
+    for k in ("depth", "color", "views"):
+        s[k].setflags(write=False)
+    return s
+
+
+# the lattice of the culling scenes: 3 x 3 x 12 bricks, the last along x two samples wide, the last along y two rows high
+CULLING_LATTICE = dict(dims=(130, 10, 12), origin=(-1.6, -0.12, 1.4), voxel=0.025)
+# name -> (scene entries replaced, [(camera centre, rx, ry, rz)] of its two views, options of the call)
+CULLING = {
+    "inside": ({}, [((-0.6, 0.0, 1.5), 0.0, 1.0, 0.0), ((0.7, -0.03, 1.6), 0.05, -1.0, 0.0)], {}),
+    "roll": ({}, [((0.1, 0.0, 0.2), 0.0, 0.1, 0.785), ((-0.2, 0.05, 0.3), 0.05, -0.15, -2.2)], {}),
+    "near-oblique": ({}, [((0.3, 0.0, 0.2), 0.0, 0.6, 0.0), ((1.2, 0.02, 0.25), 0.03, -0.6, 0.0)], dict(near=1.3)),
+    "pp-outside": (dict(cx=-20.0, cy=60.0), [((-0.8, 0.5, 0.3), 0.0, 0.0, 0.0), ((-1.5, 0.4, 0.5), 0.05, 0.1, -0.05)], {}),
+    "aniso": (dict(fx=25.0, fy=140.0), [((0.0, 0.25, 0.0), 0.0, 0.0, 0.0), ((0.4, 0.3, 0.1), -0.05, 0.3, 0.1)], {}),
+    "minus-x": ({}, [((0.9, 0.0, 1.5), 0.0, np.pi / 2 - 0.1, 0.0), ((-0.8, -0.02, 1.6), 0.0, -np.pi / 2 + 0.1, 0.0)], {}),
+    # The side planes' margins where they are widest in pixels: the culling keeps one pixel more than the image, which at depth Z is
+    # a margin of Z in the units of its comparisons (fx X + c Z against 0), so a margin wrong by some delta costs delta / Z pixels,
+    # and shows only on a brick that lies whole within that many pixels of an image border.  The last brick along x (two samples)
+    # seen end-on from 0.25 m, along -x, by a principal point near the image's corner: the layer 8.3 mm beside the camera's axis
+    # lands in pixel column W - 2 of the first view and, rolled a quarter turn, in pixel row H - 2 of the second.
+    "edge-pixels": (dict(cx=60.0, cy=44.0), [((1.85, 0.0, 1.55 - 0.25 / 30.0), 0.0, np.pi / 2, 0.0),
+                                              ((1.85, 0.0, 1.55 - 0.25 / 30.0), 0.0, np.pi / 2, np.pi / 2)], {}),
+    "sideways": ({}, [((-2.2, 0.0, 1.5), 0.0, -np.pi / 2 + 0.15, 0.0), ((2.3, 0.02, 1.45), 0.0, np.pi / 2 - 0.2, 0.0)], {}),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def culling_case(name):
+    """-> (scene, options) of CULLING[name] (shared: leave them unchanged)"""
+    over, poses, opts = CULLING[name]
+    s = with_frames(dict(MAIN, **CULLING_LATTICE, **over), [pose_at(*p) for p in poses])
+    for k in ("depth", "color", "views"):
+        s[k].setflags(write=False)
+    return s, dict(opts)
+
+
+def brick_shares(touched):
+    """the share of touched samples of every brick, [Nz, ceil(Ny / 4), ceil(Nx / 64)]"""
+    nz, ny, nx = touched.shape
+    by, bx = -(-ny // BRICK_Y), -(-nx // BRICK_X)
+    out = np.zeros((nz, by, bx))
+    for j in range(by):
+        for i in range(bx):
+            out[:, j, i] = touched[:, j * BRICK_Y:(j + 1) * BRICK_Y, i * BRICK_X:(i + 1) * BRICK_X].mean(axis=(1, 2))
+    return out
+
+
+def brick_corner_depths(s, view):
+    """the camera depth of every brick's four corners (those of the lattice where the brick hangs over), [Nz, by, bx, 4]"""
+    nx, ny, nz = s["dims"]
+    m = view.astype(np.float64)
+    o, h = [np.float64(np.float32(v)) for v in s["origin"]], np.float64(np.float32(s["voxel"]))
+    x0 = np.arange(0, nx, BRICK_X)
+    y0 = np.arange(0, ny, BRICK_Y)
+    xs = np.stack([x0, np.minimum(x0 + BRICK_X - 1, nx - 1)])  # [2, bx]
+    ys = np.stack([y0, np.minimum(y0 + BRICK_Y - 1, ny - 1)])
+    z = o[2] + h * np.arange(nz)
+    out = [m[0, 2] * (o[0] + h * xs[a])[None, None, :] + m[1, 2] * (o[1] + h * ys[b])[None, :, None] + m[2, 2] * z[:, None, None] + m[3, 2]
+           for a in (0, 1) for b in (0, 1)]
+    return np.stack(out, axis=-1)
