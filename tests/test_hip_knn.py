@@ -2,7 +2,9 @@
 mean_dist2 BIT FOR BIT, every element -- the arithmetic and the tie order are fully specified, so the twin alone decides.  The
 shapes are the smallest at which the kernels can go wrong: fewer points than k, the 256-record leaf edge, 16 385 points (a second
 block of 64 leaves, more than one sort block of 4096 keys, a partial last leaf), equal keys, zero extents, massive ties, an
-outlier that puts everything else into one Morton cell, infinite distances, invalid rows."""
+outlier that puts everything else into one Morton cell, infinite distances, invalid rows.  Beyond those: every k from 1 to 16, four
+blocks of 64 leaves (50 000 and 65 001 points, sampled rows against brute force, every row by what needs none), cross mode with
+more than one sort block of queries, and the index itself against the twin of the build (knn_model.morton_order32, index_view)."""
 import functools
 import importlib
 import os
@@ -59,6 +61,8 @@ def dataset(name):
         for j, r in enumerate(rows):
             p[r, j % 3] = (np.nan, np.inf, -np.inf)[j % 3 if j % 2 else (j // 2) % 3]
         return p
+    if name in M.SMALL:  # no valid row, one, exactly a leaf of them, an infinite extent, subnormal distances
+        return M.small_dataset(name)
     raise KeyError(name)
 
 
@@ -98,7 +102,7 @@ def search(index, queries=None, k=3, **kw):
 
 
 SELF = ("cloud1", "cloud2", "cloud3", "cloud4", "cloud255", "cloud256", "cloud257", "cloud16385", "coincident600", "line", "plane",
-        "lattice8", "duplicates", "outlier", "huge", "invalid")
+        "lattice8", "duplicates", "outlier", "huge", "invalid") + M.SMALL
 
 
 @pytest.mark.parametrize("exclude_self", [True, False], ids=["exclude_self", "with_self"])
@@ -127,6 +131,24 @@ def test_the_data_sets_are_what_they_claim():
     assert (d[:, :3] == 1).all()
     d, i, c, m = reference("duplicates", True)
     assert (d[:, 0] == 0).all() and (d[:, 1] > 0).all()
+    # (tests/test_knn_model.py holds the generators of the next five to more)
+    for exclude_self in (True, False):
+        d, i, c, m = reference("none_valid", exclude_self)
+        assert len(c) == 70 and (i == -1).all() and np.isposinf(d).all() and (c == 0).all() and np.isposinf(m).all()
+        d, i, c, m = reference("one_valid", exclude_self)
+        assert c.sum() == (0 if exclude_self else 1) and c[37] == (0 if exclude_self else 1) and np.isposinf(m).all()
+        assert (i[37, 0] == 37 and d[37, 0] == 0) or exclude_self
+    p = dataset("leaf_edge_valid")
+    d, i, c, m = reference("leaf_edge_valid", True)
+    assert len(p) == 600 and M.valid_rows(p).sum() == 256 and (c[M.valid_rows(p)] == 16).all() and (c[~M.valid_rows(p)] == 0).all()
+    p = dataset("overflow_extent")
+    d, i, c, m = reference("overflow_extent", True)
+    with np.errstate(over="ignore"):
+        assert M.valid_rows(p).all() and np.isposinf(p[:, 0].max() - p[:, 0].min()) and (M.quanta32(p)[:, 0] == 0).all()
+    assert np.isposinf(d).any() and not np.isnan(d).any() and (c == 16).all()
+    d, i, c, m = reference("subnormal", True)
+    tiny = np.finfo(np.float32).tiny
+    assert (c == 16).all() and ((d > 0) & (d < tiny)).mean() >= 0.9 and (d < tiny).all() and (np.diff(d, axis=1) == 0).any()
 
 
 @functools.lru_cache(maxsize=None)
@@ -180,6 +202,116 @@ def test_max_distance_in_cross_mode():
     want = M.knn32(p, q, 8, max_dist2=M.max_distance_squared(0.12))
     assert 0 < (want[2] < 8).sum() < 1000 and (want[2] == 8).any()
     assert_same_bits(search(knn.knn_build(T(p)), T(q), 8, max_distance=0.12), want, "cross radius")
+
+
+EVERY_K = [(name, flag) for name in ("lattice8", "duplicates", "cloud257", "invalid") for flag in (True, False)] + [("cross", False)]
+
+
+@pytest.mark.parametrize("name, exclude_self", EVERY_K, ids=[f"{n}-{'exclude_self' if f else 'with_self'}" for n, f in EVERY_K[:-1]] + ["cross"])
+def test_every_k_gives_the_twins_bits(name, exclude_self):
+    """k = 1 .. 16: every k below the K of its kernel (slot k - 1 as what a candidate has to beat, the j < k output loops, the
+    division by k) on data with ties, and K = 4, which KS does not reach"""
+    if name == "cross":
+        p, q, ref = cross_case()
+        queries, kw = T(q), {}
+    else:
+        p, queries, ref, kw = dataset(name), None, reference(name, exclude_self), {"exclude_self": exclude_self}
+    index = knn.knn_build(T(p))
+    for k in range(1, 17):
+        assert_same_bits(search(index, queries, k, **kw), M.first_k(ref, k), f"{name} k={k}")
+    if name == "cross":
+        r2 = M.max_distance_squared(0.12)
+        for k in (4, 6):
+            want = M.knn32(p, q, k, max_dist2=r2)
+            assert ((want[2] > 0) & (want[2] < k)).any() and (want[2] == k).any()
+            assert_same_bits(search(index, queries, k, max_distance=0.12), want, f"cross radius k={k}")
+
+
+# ---- the index itself: the answers do not depend on it, so only reading it shows a build that is not the stated one
+INDEXED = tuple(f"cloud{n}" for n in (1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 16385)) + (
+    "invalid", "coincident600", "line", "outlier", "huge") + M.SMALL
+
+
+@pytest.mark.parametrize("name", INDEXED)
+def test_the_index_is_the_stated_build(name):
+    """the box of the valid points, the 30-bit Morton key on it, the stable sort of (key, index) and the leaves' exact boxes, first
+    keys and counts, all bit for bit against the twin of the build (knn_model.morton_order32); P on the sort's edges (64 keys per
+    round, 1024 per wave, 4096 per workgroup) and the leaf's (256)"""
+    p = dataset(name)
+    P, ok = len(p), M.valid_rows(p)
+    n = int(ok.sum())
+    v = M.index_view(knn.knn_build(T(p)).index.cpu().numpy(), P)
+    assert v.n_valid == n
+    lo, hi = M.box_bits(p)
+    assert np.array_equal(v.lo, lo) and np.array_equal(v.hi, hi), (v.lo, lo, v.hi, hi)
+    assert np.array_equal(np.sort(v.row), np.arange(P)), "the records' rows are no permutation"
+    assert np.array_equal(bits(v.xyz), bits(p[v.row])), "a record does not hold its point's bits"
+    order, key = M.morton_order32(p), M.morton_keys32(p)
+    assert ok[order[:n]].all() and not ok[order[n:]].any()
+    bad = np.flatnonzero(v.row[:n] != order[:n])
+    assert not len(bad), f"{len(bad)} of {n} valid records out of the stated order, first at {bad[0]}: row {v.row[bad[0]]}, want {order[bad[0]]}"
+    assert np.array_equal(v.row[n:], np.flatnonzero(~ok)), "the invalid rows do not follow in index order"
+    for leaf in range(len(v.leaf_count)):
+        first = leaf * M.LEAF
+        count = min(M.LEAF, n - first)
+        if count <= 0:
+            assert v.leaf_count[leaf] == 0 and v.leaf_key[leaf] == 0xFFFFFFFF, leaf
+            continue
+        mine = v.xyz[first:first + count]
+        assert v.leaf_count[leaf] == count and v.leaf_key[leaf] == key[v.row[first]], leaf
+        assert np.array_equal(v.leaf_lo[leaf], mine.min(axis=0)) and np.array_equal(v.leaf_hi[leaf], mine.max(axis=0)), leaf
+
+
+# ---- more than two blocks of 64 leaves, more than one sort block of queries
+def check_every_row(p, got, k, exclude_self):
+    """what holds for a right answer and needs no brute force"""
+    d, i, c, m = got
+    assert (c == k).all() and (i >= 0).all() and (i < len(p)).all()
+    assert (d[:, 1:] >= d[:, :-1]).all()
+    assert np.array_equal(bits(d), bits(M.dist2_of_pairs32(p, p, i))), "a dist2 is not the distance to its idx"
+    assert (np.diff(np.sort(i, axis=1), axis=1) > 0).all(), "an index twice in a row"
+    own = i == np.arange(len(p), dtype=np.int32)[:, None]
+    assert not own.any() if exclude_self else own[:, 0].all()
+    assert np.array_equal(bits(m), bits(M.mean32(d)))
+
+
+@pytest.mark.parametrize("exclude_self", [True, False], ids=["exclude_self", "with_self"])
+@pytest.mark.parametrize("k", [1, 4, 16])
+@pytest.mark.parametrize("case", ["cloud50000", "collapsed"])
+def test_self_mode_across_four_blocks_of_leaves(case, k, exclude_self):
+    """the sweep own_block, -1, +1, -2, +2, -3, +3.  cloud50000: 196 leaves, the compared rows at the plane where the true
+    neighbours are two blocks away; collapsed: 254 leaves in the rows' own order, the true neighbours in every block (the
+    conditions: tests/test_knn_model.py).  The compared rows bit for bit, all rows by what needs no brute force."""
+    c = M.cloud50000_case() if case == "cloud50000" else M.collapsed_case()
+    got = search(knn.knn_build(T(c.p)), None, k, exclude_self=exclude_self)
+    want = M.first_k(c.exclude_self if exclude_self else c.with_self, k)
+    assert_same_bits(tuple(a[c.rows] for a in got), want, f"{case} k={k}")
+    check_every_row(c.p, got, k, exclude_self)
+
+
+def test_cross_mode_with_two_sort_blocks_of_queries():
+    """4200 queries against the 196 leaves of cloud50000: a query sort of two sort blocks, the binary search for the own leaf over
+    more than 64 leaves, own leaves in every block, queries outside the box on every side, a last wave of invalid queries alone
+    and a mixed one before it (the conditions: tests/test_knn_model.py)"""
+    p, q, ref = M.cloud50000_case().p, M.two_sort_block_queries(), M.two_sort_block_reference()
+    index = knn.knn_build(T(p))
+    for k in (1, 4, 16):
+        assert_same_bits(search(index, T(q), k), M.first_k(ref, k), f"k={k}")
+    want = M.within(ref, 4, M.max_distance_squared(0.02))
+    assert ((want[2] > 0) & (want[2] < 4)).any() and (want[2] == 4).any()
+    assert_same_bits(search(index, T(q), 4, max_distance=0.02), want, "radius 0.02")
+
+
+def test_no_valid_point_in_cross_mode():
+    q = cloud(90, 35)
+    q[11] = np.nan
+    for name in ("none_valid", "one_valid"):
+        p = dataset(name)
+        index = knn.knn_build(T(p))
+        for k in (1, 5, 16):
+            want = M.knn32(p, q, k)
+            assert (want[2] == (name == "one_valid") * M.valid_rows(q)).all()
+            assert_same_bits(search(index, T(q), k), want, f"{name} k={k}")
 
 
 def test_distcuda2_through_the_drop_in_import(monkeypatch):
@@ -239,6 +371,11 @@ def test_nothing_is_written_outside_the_buffers(monkeypatch):
     got = search(index, T(q), 3)  # more queries than points: a scratch of its own
     assert guarded.check() >= 7
     assert_same_bits(got, M.knn32(p[:300], q, 3), "cross")
+    big = M.two_sort_block_queries()  # the scratch sized by 4200 queries: two sort blocks and the query records behind them
+    assert _capi.load().dgr_knn_scratch_bytes(300, len(big)) > index.scratch.numel()  # (a scratch of its own again)
+    got = search(index, T(big), 3)
+    assert guarded.check() >= 5  # scratch, four outputs
+    assert_same_bits(got, M.knn32(p[:300], big, 3), "cross, two sort blocks")
     assert knn.dist2(T(dataset("cloud257"))).shape == (257,) and guarded.check() >= 3
 
 
