@@ -8,34 +8,30 @@
 // step   : one Gauss-Newton iteration in THREE stages with no host read between them: the source moved by the current estimate
 //          (fp32, every operation rounded once: a numpy twin gives the same bits), the cross-mode kNN search with k = 1 (the
 //          association IS the kNN rule's answer), and the step kernel: icp.hip's shape -- a workgroup per block of 2048 sources,
-//          a thread's sources ascending, 29 double accumulators, block_sums, one 256-byte row per block and a ticket
-//          (pose_reduce.h's deterministic form); the block that draws the last ticket adds the rows in block order, solves the
-//          6 x 6 system by LDL^T in double and writes T_out = exp(xi) T_in.  The row / ticket / block-order tail repeats
-//          icp.hip's on purpose (that file stays as it is).
+//          a thread's sources ascending, 29 double accumulators.  Everything behind the sums is gn_step.h's, shared with
+//          icp.hip: the row / ticket / block-order reduction, the damped LDL^T solve, the pose and stats writer.  This file's
+//          own is the update between the last two: T_out = exp(xi) T_in.
 // No host read, no float atomics, no spin-wait, the same bits on every run.  Compiled with contraction off: the transform's fp32
-// rule and the double rules of the header mean one thing.
+// rule and the double rules of the header mean one thing.  se3.h above the pragma is contracted here as everywhere; gn_step.h
+// below it sets no mode of its own and is not.
 #include <hip/hip_runtime.h>
 
-#include "block_sum.h"
 #include "kernels.h"
 #include "se3.h"
 
 #pragma clang fp contract(off)
 
+#include "gn_step.h"
+
 namespace dgr {
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int BLOCK_SOURCES = 2048;   // eight trips of a workgroup
+constexpr int THREADS = GN_THREADS;
+constexpr int BLOCK_SOURCES = GN_BLOCK_ITEMS;
 constexpr int SUMS = 29;              // A (21), b (6), sum w s^2, count
-constexpr int ROW = 32;               // doubles per block in the scratch: a 256-byte row
-constexpr int CHUNK = 64;             // rows the finisher stages in LDS per trip
-constexpr size_t HEADER_BYTES = 256;  // the ticket (a uint32 at byte 0; zero between calls)
 constexpr int JACOBI_SWEEPS = 16;     // (dgr_hip.h: the fixed number of sweeps)
 constexpr unsigned GICP_VALID = 1u, GICP_ASSOCIATED = 2u, GICP_SINGULAR = 4u;
-constexpr double DAMPING_FLOOR = 1e-3;  // (dgr_icp_step's)
 
-__host__ __device__ inline unsigned gicp_blocks(size_t sources) { return (unsigned)((sources + BLOCK_SOURCES - 1) / BLOCK_SOURCES); }
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
@@ -194,83 +190,20 @@ __global__ void __launch_bounds__(THREADS) gicp_transform_kernel(int S, const fl
 }
 
 // -------------------------------------------------------------------------------------------------------------------- step
-// One thread: the totals -> stats, the solve, the update T_out = exp(xi) T_in, the pose outputs (icp.hip's finisher with the left
-// perturbation in place of the model-frame one).
+// One thread: the totals through gn_step.h's solve, the left update T_out = exp(xi) T_in, its writer.
 __device__ void gicp_finish(const GicpStepArgs& a, const double* tot) {
-    double M[6][6], b[6];
-    {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = i; j < 6; j++) M[i][j] = M[j][i] = tot[k++];
-#pragma unroll
-        for (int i = 0; i < 6; i++) b[i] = tot[21 + i];
-    }
-    bool ok = tot[28] >= (double)a.min_points;
-#pragma unroll
-    for (int i = 0; i < 28; i++) ok = ok && isfinite(tot[i]);
-    double max_diag = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) max_diag = fmax(max_diag, M[i][i]);
-#pragma unroll
-    for (int i = 0; i < 6; i++) M[i][i] += a.damping * fmax(M[i][i], DAMPING_FLOOR * max_diag);
-    const double pivot_min = a.rcond * max_diag;
-    double D[6];
-    ok = ldlt6_factor(M, D, pivot_min) && ok;
     double xi[6];
-    const double nb[6] = {-b[0], -b[1], -b[2], -b[3], -b[4], -b[5]};
-    ldlt6_solve(M, D, nb, xi);  // M xi = -b
-#pragma unroll
-    for (int i = 0; i < 6; i++) ok = ok && isfinite(xi[i]);
-
-    double Ri[3][3], ti[3];
-    pose_of(a.transform_in, Ri, ti);  // (read before anything is written: transform_out may be transform_in)
-    uint32_t in_bits[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) in_bits[i] = reinterpret_cast<const uint32_t*>(a.transform_in)[i];
-    double q[4], Ro[3][3], to[3];
+    const bool ok = gn_solve(tot, tot[28], true, a.min_points, a.damping, a.rcond, xi);
+    GnPoseIn in;
+    gn_read_pose(a.transform_in, in);
+    double Ro[3][3], to[3];
     if (ok) {
         double Re[3][3], te[3];
         const double w[3] = {xi[0], xi[1], xi[2]}, v[3] = {xi[3], xi[4], xi[5]};
         se3_exp(w, v, Re, te);
-        compose(Re, te, Ri, ti, Ro, to);
-        rotation_to_quat(Ro, q);  // the rotation re-orthonormalised: through its unit quaternion
-        quat_to_rotation(q, Ro);
-#pragma unroll
-        for (int i = 0; i < 4; i++) ok = ok && isfinite(q[i]);
-#pragma unroll
-        for (int i = 0; i < 3; i++) ok = ok && isfinite(to[i]);
+        compose(Re, te, in.R, in.t, Ro, to);
     }
-    if (!ok) rotation_to_quat(Ri, q);
-    float* out = a.transform_out;
-    if (ok) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) out[4 * i + j] = (float)Ro[j][i];
-            out[4 * i + 3] = 0.f;
-            out[12 + i] = (float)to[i];
-        }
-        out[15] = 1.f;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; i++) reinterpret_cast<uint32_t*>(out)[i] = in_bits[i];
-    }
-    if (a.quat_out)
-#pragma unroll
-        for (int i = 0; i < 4; i++) a.quat_out[i] = (float)q[i];
-    if (a.trans_out)
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            if (ok) a.trans_out[i] = (float)to[i];
-            else reinterpret_cast<uint32_t*>(a.trans_out)[i] = in_bits[12 + i];
-        }
-#pragma unroll
-    for (int i = 0; i < SUMS; i++) a.stats[i] = tot[i];
-    a.stats[SUMS] = ok ? 1.0 : 0.0;
-    a.stats[SUMS + 1] = ok ? sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) : 0.0;
-    a.stats[SUMS + 2] = ok ? sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]) : 0.0;
+    gn_write<SUMS, SUMS + 3>(ok, Ro, to, in, xi, tot, a.transform_out, a.quat_out, a.trans_out, a.stats);
 }
 
 // the six entries (00, 01, 02, 11, 12, 22) and the validity of a packed covariance row: two 16-byte loads from one line
@@ -280,11 +213,8 @@ __device__ __forceinline__ bool load_cov(const float4* __restrict__ rows, size_t
     return hi.w > 0.f;  // n, the neighbour count: 0 = invalid (false on a NaN)
 }
 
-// grid: one workgroup per block of sources.  `ticket`: zero on entry, left at zero; `part`: a row of ROW doubles per workgroup.
+// grid: one workgroup per block of sources.  `ticket`, `part`: gn_reduce's.
 __global__ void __launch_bounds__(THREADS) gicp_step_kernel(GicpStepArgs a, uint32_t* __restrict__ ticket, double* __restrict__ part) {
-    __shared__ int last;
-    __shared__ double rows[CHUNK * ROW];
-    __shared__ double totals[ROW];
     // R of the current estimate, widened: R[j][c] at [4 c + j]
     const float* T = a.transform_in;  // (not __restrict__: transform_out may be the same address)
     const double R00 = (double)T[0], R01 = (double)T[4], R02 = (double)T[8], R10 = (double)T[1], R11 = (double)T[5], R12 = (double)T[9],
@@ -358,47 +288,18 @@ __global__ void __launch_bounds__(THREADS) gicp_step_kernel(GicpStepArgs a, uint
         if (a.flags)
             a.flags[i] = (unsigned char)((valid ? GICP_VALID : 0u) | (associated ? GICP_ASSOCIATED : 0u) | (singular ? GICP_SINGULAR : 0u));
     }
-    block_sums(acc);
-    if (threadIdx.x == 0) {
-        double* row = part + (size_t)blockIdx.x * ROW;
-#pragma unroll
-        for (int i = 0; i < SUMS; i++) __hip_atomic_store(row + i, acc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores are acknowledged before the ticket is taken
-        const uint32_t t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = t == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    // the last block: every row is delivered.  Rows staged in LDS CHUNK at a time, then thread s < 29 adds sum s in block order.
-    double tot = 0.0;
-    for (unsigned base = 0; base < gridDim.x; base += CHUNK) {
-        const unsigned n = gridDim.x - base < CHUNK ? gridDim.x - base : CHUNK;
-        for (unsigned i = threadIdx.x; i < n * ROW; i += THREADS)
-            if ((i & (ROW - 1)) < SUMS)
-                rows[i] = __hip_atomic_load(part + (size_t)base * ROW + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (threadIdx.x < SUMS)
-            for (unsigned r = 0; r < n; r++) tot += rows[r * ROW + threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x < SUMS) totals[threadIdx.x] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        gicp_finish(a, totals);
-    }
+    gn_reduce(acc, ticket, part, [&](const double* totals) { gicp_finish(a, totals); });
 }
 
 // the scratch: the header (ticket), a row per block, q [S,3], idx [S], then the search's own scratch; every part 256-byte aligned
 struct GicpScratch {
-    size_t rows, q, idx, knn, total;
+    size_t q, idx, knn, total;
 };
 GicpScratch gicp_layout(int N, int S) {
     GicpScratch l{};
     const size_t knn = knn_scratch_bytes(N, S);
     if (!knn) return l;
-    l.rows = HEADER_BYTES;
-    l.q = l.rows + (size_t)gicp_blocks((size_t)S) * ROW * sizeof(double);
+    l.q = gn_scratch_bytes((size_t)S);
     l.idx = l.q + align256(12 * (size_t)S);
     l.knn = l.idx + align256(4 * (size_t)S);
     l.total = l.knn + align256(knn);
@@ -430,8 +331,7 @@ hipError_t launch_gicp_step(const GicpStepArgs& args, const void* index, float d
     c.scratch = base + l.knn, c.idx = idx;
     if (hipError_t e = launch_knn_search(c, stream); e != hipSuccess) return e;
     a.q = q, a.idx = idx;
-    launch(gicp_step_kernel, dim3(gicp_blocks((size_t)a.S)), dim3(THREADS), stream, a, reinterpret_cast<uint32_t*>(base),
-           reinterpret_cast<double*>(base + l.rows));
+    launch(gicp_step_kernel, dim3(gn_blocks((size_t)a.S)), dim3(THREADS), stream, a, gn_ticket(scratch), gn_rows(scratch));
     return hipGetLastError();
 }
 

@@ -7,9 +7,9 @@
 // step   : one Gauss-Newton iteration in ONE launch.  One workgroup per block of 2048 candidates (the stride grid of
 //          candidate_grid.h), as overlap_count_kernel: threads 0..11 form rel = T_model T_in^-1 in double and round it once, every
 //          thread takes a candidate per trip and adds its 29 terms (A's upper triangle, b, sum w r^2, count) to its own double
-//          accumulators; block_sums; the block's partial goes to its own row of the scratch and the block takes a ticket
-//          (pose_reduce.h's deterministic form).  The block that draws the last ticket adds the rows in block order, solves the
-//          6 x 6 system by LDL^T in double, forms the new pose and leaves the ticket at zero: a recorded graph replays it.
+//          accumulators.  Everything behind the sums is gn_step.h's, shared with gicp.hip: the row / ticket / block-order
+//          reduction, the damped LDL^T solve, the pose and stats writer.  This file's own is the update between the last two:
+//          T_out = T_in T_model^-1 exp(-xi) T_model.
 // Hybrid RGB-D alignment (dgr_intensity_map, dgr_frame_halve, dgr_rgbd_step): the photometric term beside the geometric one.
 // intensity: one thread per pixel: the packed intensity-gradient map (I, I_x, I_y, usable), Sobel / 8, and the plain intensity plane.
 // halve    : one thread per output pixel: one pyramid level of any number of mean planes and one depth plane.
@@ -18,30 +18,19 @@
 // No host read, no float atomics, the same bits on every run.
 #include <hip/hip_runtime.h>
 
-#include "block_sum.h"
 #include "candidate_grid.h"
+#include "gn_step.h"
 #include "kernels.h"
-#include "se3.h"
 
 namespace dgr {
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int BLOCK_CANDIDATES = 2048;  // eight trips of a workgroup
+constexpr int THREADS = GN_THREADS;
+constexpr int BLOCK_CANDIDATES = GN_BLOCK_ITEMS;
 constexpr int SUMS = 29;                // A (21), b (6), sum w r^2, count
 constexpr int RGBD_SUMS = 31;           // A (21), b (6), sum w r^2, count_g, sum w_p r_p^2, count_p (the hybrid step's)
 constexpr int RGBD_STATS = 40;          // doubles of the hybrid step's stats
-constexpr int ROW = 32;                 // doubles per block in the scratch: a 256-byte row
-constexpr int CHUNK = 64;               // rows the finisher stages in LDS per trip
-constexpr size_t HEADER_BYTES = 256;    // the ticket (a uint32 at byte 0; zero between calls)
 constexpr unsigned ICP_VALID = 1u, ICP_INSIDE = 2u, ICP_ASSOCIATED = 4u, ICP_PHOTOMETRIC = 8u;
-// A diagonal entry below this share of the largest is damped as if it were that large: a direction the data does not constrain
-// at all (an exactly zero row of A: the fronto-parallel plane) then has a positive pivot under damping > 0 and does not move.
-constexpr double DAMPING_FLOOR = 1e-3;
-
-__host__ __device__ inline unsigned icp_blocks(size_t candidates) {
-    return (unsigned)((candidates + BLOCK_CANDIDATES - 1) / BLOCK_CANDIDATES);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- normals
 __global__ void __launch_bounds__(THREADS) depth_normals_kernel(DepthNormalsArgs a) {
@@ -145,44 +134,15 @@ __global__ void __launch_bounds__(THREADS) frame_halve_kernel(FrameHalveArgs a) 
 }
 
 // -------------------------------------------------------------------------------------------------------------------- step
-// One thread: the totals -> stats, the solve, the update, the pose outputs.  RGBD: the hybrid step's 31 totals and 40 stats.
+// One thread: the totals through gn_step.h's solve, the model-frame update, its writer.  RGBD: the hybrid step's 31 totals (the
+// count is both classes', the photometric sum w r^2 must be finite too) and 40 stats.
 template <bool RGBD>
 __device__ void icp_finish(const IcpStepArgs& a, const double* tot) {
-    constexpr int N = RGBD ? RGBD_SUMS : SUMS;
-    double M[6][6], b[6];
-    {
-        int k = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-            for (int j = i; j < 6; j++) M[i][j] = M[j][i] = tot[k++];
-#pragma unroll
-        for (int i = 0; i < 6; i++) b[i] = tot[21 + i];
-    }
-    bool ok = (RGBD ? tot[28] + tot[30] : tot[28]) >= (double)a.min_points;
-#pragma unroll
-    for (int i = 0; i < 28; i++) ok = ok && isfinite(tot[i]);
-    if constexpr (RGBD) ok = ok && isfinite(tot[29]);
-    double max_diag = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) max_diag = fmax(max_diag, M[i][i]);
-#pragma unroll
-    for (int i = 0; i < 6; i++) M[i][i] += a.damping * fmax(M[i][i], DAMPING_FLOOR * max_diag);
-    const double pivot_min = a.rcond * max_diag;
-    double D[6];
-    ok = ldlt6_factor(M, D, pivot_min) && ok;  // (se3.h: M = L D L^T, no pivoting)
     double xi[6];
-    const double nb[6] = {-b[0], -b[1], -b[2], -b[3], -b[4], -b[5]};
-    ldlt6_solve(M, D, nb, xi);  // M xi = -b
-#pragma unroll
-    for (int i = 0; i < 6; i++) ok = ok && isfinite(xi[i]);
-
-    double Ri[3][3], ti[3];
-    pose_of(a.viewmatrix_in, Ri, ti);  // (read before anything is written: viewmatrix_out may be viewmatrix_in)
-    uint32_t in_bits[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) in_bits[i] = reinterpret_cast<const uint32_t*>(a.viewmatrix_in)[i];
-    double q[4], Ro[3][3], to[3];
+    const bool ok = gn_solve(tot, RGBD ? tot[28] + tot[30] : tot[28], !RGBD || isfinite(tot[29]), a.min_points, a.damping, a.rcond, xi);
+    GnPoseIn in;
+    gn_read_pose(a.viewmatrix_in, in);
+    double Ro[3][3], to[3];
     if (ok) {
         // T_out = T_in T_model^-1 exp(-xi) T_model
         double Rm[3][3], tm[3], Re[3][3], te[3], R1[3][3], t1[3], R2[3][3], t2[3];
@@ -198,46 +158,9 @@ __device__ void icp_finish(const IcpStepArgs& a, const double* tot) {
             tmi[i] = -(Rm[0][i] * tm[0] + Rm[1][i] * tm[1] + Rm[2][i] * tm[2]);
         }
         compose(Rmt, tmi, R1, t1, R2, t2);
-        compose(Ri, ti, R2, t2, Ro, to);
-        rotation_to_quat(Ro, q);  // the rotation re-orthonormalised: through its unit quaternion
-        quat_to_rotation(q, Ro);
-#pragma unroll
-        for (int i = 0; i < 4; i++) ok = ok && isfinite(q[i]);
-#pragma unroll
-        for (int i = 0; i < 3; i++) ok = ok && isfinite(to[i]);
+        compose(in.R, in.t, R2, t2, Ro, to);
     }
-    if (!ok) rotation_to_quat(Ri, q);
-    float* out = a.viewmatrix_out;
-    if (ok) {
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-#pragma unroll
-            for (int j = 0; j < 3; j++) out[4 * i + j] = (float)Ro[j][i];
-            out[4 * i + 3] = 0.f;
-            out[12 + i] = (float)to[i];
-        }
-        out[15] = 1.f;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; i++) reinterpret_cast<uint32_t*>(out)[i] = in_bits[i];
-    }
-    if (a.quat_out)
-#pragma unroll
-        for (int i = 0; i < 4; i++) a.quat_out[i] = (float)q[i];
-    if (a.trans_out)
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            if (ok) a.trans_out[i] = (float)to[i];
-            else reinterpret_cast<uint32_t*>(a.trans_out)[i] = in_bits[12 + i];
-        }
-#pragma unroll
-    for (int i = 0; i < N; i++) a.stats[i] = tot[i];
-    a.stats[N] = ok ? 1.0 : 0.0;
-    a.stats[N + 1] = ok ? sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]) : 0.0;
-    a.stats[N + 2] = ok ? sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]) : 0.0;
-    if constexpr (RGBD)
-#pragma unroll
-        for (int i = N + 3; i < RGBD_STATS; i++) a.stats[i] = 0.0;
+    gn_write<RGBD ? RGBD_SUMS : SUMS, RGBD ? RGBD_STATS : SUMS + 3>(ok, Ro, to, in, xi, tot, a.viewmatrix_out, a.quat_out, a.trans_out, a.stats);
 }
 
 // one pair's terms onto a thread's sums: A += (s J_i) J_j, b += (s J_i) r, each product rounded to fp32 before it is widened
@@ -252,7 +175,7 @@ __device__ __forceinline__ void add_pair(double* acc, const float (&J)[6], float
     }
 }
 
-// grid: one workgroup per block of candidates.  `ticket`: zero on entry, left at zero; `part`: a row of ROW doubles per workgroup.
+// grid: one workgroup per block of candidates.  `ticket`, `part`: gn_reduce's.
 // Args: IcpStepArgs, or RgbdStepArgs for the hybrid step (dgr_rgbd_step): the photometric pair beside the geometric one, each
 // scaled by its class weight, two more sums.
 template <class Args>
@@ -260,9 +183,6 @@ __global__ void __launch_bounds__(THREADS) icp_step_kernel(Args a, uint32_t* __r
     constexpr bool RGBD = Args::rgbd;
     constexpr int SUMS = RGBD ? RGBD_SUMS : dgr::SUMS;
     __shared__ float rel[12];  // current camera point p -> model camera point: q_j = rel[3 j] p_0 + rel[3 j + 1] p_1 + rel[3 j + 2] p_2 + rel[9 + j]
-    __shared__ int last;
-    __shared__ double rows[CHUNK * ROW];
-    __shared__ double totals[ROW];
     if (threadIdx.x < 12) {
         // both matrices hold W2C^T: W2C's rotation entry R[j][i] at [4 i + j], its translation t[j] at [12 + j].
         // q = R_m R_in^T (p - t_in) + t_m
@@ -355,36 +275,7 @@ __global__ void __launch_bounds__(THREADS) icp_step_kernel(Args a, uint32_t* __r
             a.flags[c] = (unsigned char)((valid ? ICP_VALID : 0u) | (inside ? ICP_INSIDE : 0u) | (associated ? ICP_ASSOCIATED : 0u) |
                                          (RGBD && photometric ? ICP_PHOTOMETRIC : 0u));
     }
-    block_sums(acc);
-    if (threadIdx.x == 0) {
-        double* row = part + (size_t)blockIdx.x * ROW;
-#pragma unroll
-        for (int i = 0; i < SUMS; i++) __hip_atomic_store(row + i, acc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores are acknowledged before the ticket is taken
-        const uint32_t t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = t == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!last) return;
-    // the last block: every row is delivered.  Rows staged in LDS CHUNK at a time (all loads of a chunk in flight together), then
-    // thread s < 29 adds sum s over the rows in block order.
-    double tot = 0.0;
-    for (unsigned base = 0; base < gridDim.x; base += CHUNK) {
-        const unsigned n = gridDim.x - base < CHUNK ? gridDim.x - base : CHUNK;
-        for (unsigned i = threadIdx.x; i < n * ROW; i += THREADS)
-            if ((i & (ROW - 1)) < SUMS)
-                rows[i] = __hip_atomic_load(part + (size_t)base * ROW + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        if (threadIdx.x < SUMS)
-            for (unsigned r = 0; r < n; r++) tot += rows[r * ROW + threadIdx.x];
-        __syncthreads();
-    }
-    if (threadIdx.x < SUMS) totals[threadIdx.x] = tot;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        icp_finish<RGBD>(a, totals);
-    }
+    gn_reduce(acc, ticket, part, [&](const double* totals) { icp_finish<RGBD>(a, totals); });
 }
 
 }  // namespace
@@ -407,28 +298,21 @@ hipError_t launch_frame_halve(const FrameHalveArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-size_t icp_scratch_bytes(int W, int H, int stride) {
-    return HEADER_BYTES + (size_t)icp_blocks(seed_candidates(W, H, stride)) * ROW * sizeof(double);
-}
+size_t icp_scratch_bytes(int W, int H, int stride) { return gn_scratch_bytes(seed_candidates(W, H, stride)); }
 
-hipError_t launch_icp_step(const IcpStepArgs& args, void* scratch, hipStream_t stream) {
-    IcpStepArgs a = args;
+namespace {
+template <class Args>
+hipError_t launch_step(const Args& args, void* scratch, hipStream_t stream) {
+    Args a = args;
     const CandidateGrid g = candidate_grid(a.W, a.H, a.stride);
     a.candidates = g.candidates();
     a.wc = g.wc;
-    launch(icp_step_kernel<IcpStepArgs>, dim3(icp_blocks(a.candidates)), dim3(THREADS), stream, a, static_cast<uint32_t*>(scratch),
-           reinterpret_cast<double*>(static_cast<char*>(scratch) + HEADER_BYTES));
+    launch(icp_step_kernel<Args>, dim3(gn_blocks(a.candidates)), dim3(THREADS), stream, a, gn_ticket(scratch), gn_rows(scratch));
     return hipGetLastError();
 }
+}  // namespace
 
-hipError_t launch_rgbd_step(const RgbdStepArgs& args, void* scratch, hipStream_t stream) {
-    RgbdStepArgs a = args;
-    const CandidateGrid g = candidate_grid(a.W, a.H, a.stride);
-    a.candidates = g.candidates();
-    a.wc = g.wc;
-    launch(icp_step_kernel<RgbdStepArgs>, dim3(icp_blocks(a.candidates)), dim3(THREADS), stream, a, static_cast<uint32_t*>(scratch),
-           reinterpret_cast<double*>(static_cast<char*>(scratch) + HEADER_BYTES));
-    return hipGetLastError();
-}
+hipError_t launch_icp_step(const IcpStepArgs& args, void* scratch, hipStream_t stream) { return launch_step(args, scratch, stream); }
+hipError_t launch_rgbd_step(const RgbdStepArgs& args, void* scratch, hipStream_t stream) { return launch_step(args, scratch, stream); }
 
 }  // namespace dgr

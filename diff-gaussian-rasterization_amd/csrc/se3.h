@@ -1,5 +1,7 @@
-// se3.h -- the rigid-motion helpers the pose steps share (icp.hip's finisher, pgo.hip), all in double on the device: a pose as
-// (R, t) of W2C, its unit quaternion (r, x, y, z; r >= 0), the exponential of a twist (w, v) and the 6 x 6 LDL^T the steps solve with.
+// se3.h -- the rigid-motion helpers the pose steps share (gn_step.h's solve and writer, the update rules of icp.hip and gicp.hip
+// between them, pgo.hip), all in double on the device: a pose as (R, t) of W2C, its unit quaternion (r, x, y, z; r >= 0), the
+// exponential of a twist (w, v) and the 6 x 6 LDL^T the steps solve with.  No contraction mode of its own either: every file
+// includes it above any pragma of its own, so it is contracted everywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -7,9 +7,9 @@ from typing import NamedTuple as _NamedTuple
 import torch
 
 from . import _capi
+from ._align import INF, _Chain, _number, _pose
 from .knn import KnnIndex, _check_gpu, _points, knn_build, knn_search
 
-INF = float("inf")
 _MODES = {"raw": _capi.COV_RAW, "plane": _capi.COV_PLANE}
 
 
@@ -37,15 +37,6 @@ class GicpResult(_NamedTuple):
     stats: torch.Tensor
     idx: torch.Tensor
     flags: torch.Tensor
-
-
-def _number(what, name, v, lowest=None):
-    v = float(v)
-    if v != v:
-        raise ValueError(f"{what}: {name} must not be NaN")
-    if lowest is not None and v < lowest:
-        raise ValueError(f"{what}: {name} must not be {'negative' if lowest == 0.0 else f'below {lowest}'}, not {v}")
-    return v
 
 
 def point_covariances(points, index=None, *, k=10, include_self=True, mode="plane", epsilon=1e-3, min_neighbours=4, viewpoint=None,
@@ -163,13 +154,7 @@ def _cov_rows(what, name, t, n):
 
 
 def _transform(what, name, t):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{what}: {name} must be a tensor, not {type(t).__name__}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{what}: {name} must be float32, not {t.dtype}")
-    if tuple(t.shape) != (4, 4):
-        raise ValueError(f"{what}: {name} is [4,4] (the motion transposed, relative_pose's layout), not {tuple(t.shape)}")
-    return t
+    return _pose(what, name, t, "the motion transposed, relative_pose's layout")
 
 
 def _step_numbers(what, max_distance, huber_delta, damping, rcond, min_points):
@@ -213,19 +198,13 @@ def gicp_step(source, target_index, transform_in, *, transform_out=None, source_
     _check_gpu(what, source, target, transform_in, *(t for t in (source_cov, target_cov) if t is not None))
     dev = source.device
     source, transform_in = source.detach().contiguous(), transform_in.contiguous()
-    out = torch.empty((4, 4), dtype=torch.float32, device=dev) if transform_out is None else transform_out
-    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (4, 4) and out.is_contiguous()):
-        raise ValueError(f"{what}: transform_out must be a contiguous float32 GPU tensor [4,4]")
-    qt = torch.empty((8,), dtype=torch.float32, device=dev)
-    stats = torch.empty((1, 32), dtype=torch.float64, device=dev)
-    idx = torch.empty((S,), dtype=torch.int32, device=dev) if return_idx else None
-    flags = torch.empty((S,), dtype=torch.uint8, device=dev) if return_flags else None
+    chain = _Chain(torch, what, dev, 1, 32, out=transform_out, out_name="transform_out", flags=S if return_flags else None,
+                   idx=S if return_idx else None)
     if scratch is None:
         scratch = _scratch(what, N, S, dev)
     _capi.call("dgr_gicp_step", dev, target_index.index.data_ptr(), N, target.data_ptr(), _capi.ptr(target_cov), S, source.data_ptr(),
-               _capi.ptr(source_cov), transform_in.data_ptr(), params, scratch.data_ptr(), out.data_ptr(), qt.data_ptr(),
-               qt[4:].data_ptr(), stats.data_ptr(), _capi.ptr(idx), _capi.ptr(flags))
-    return GicpResult(out, qt[:4], qt[4:7], stats, idx, flags)
+               _capi.ptr(source_cov), transform_in.data_ptr(), params, scratch.data_ptr(), *chain.tail(0))
+    return chain.result(GicpResult)
 
 
 def gicp_align(source, target, *, transform=None, source_cov=None, target_cov=None, target_index=None, iterations=15,
@@ -263,18 +242,11 @@ def gicp_align(source, target, *, transform=None, source_cov=None, target_cov=No
     if target_index is None:
         target_index = knn_build(target)
     target = target_index.points
-    pose = torch.empty((4, 4), dtype=torch.float32, device=dev)
-    pose.copy_(torch.eye(4, dtype=torch.float32, device=dev) if transform is None else transform.detach())
-    qt = torch.empty((8,), dtype=torch.float32, device=dev)
-    stats = torch.empty((iterations, 32), dtype=torch.float64, device=dev)
-    idx = torch.empty((S,), dtype=torch.int32, device=dev) if return_idx else None
-    flags = torch.empty((S,), dtype=torch.uint8, device=dev) if return_flags else None
+    chain = _Chain(torch, what, dev, iterations, 32, first=torch.eye(4, dtype=torch.float32, device=dev) if transform is None else transform,
+                   flags=S if return_flags else None, idx=S if return_idx else None)
     scratch = _scratch(what, N, S, dev)
     with _capi.StepCalls(dev) as abi:
         for k in range(iterations):
-            last = k == iterations - 1
             abi.call("dgr_gicp_step", target_index.index.data_ptr(), N, target.data_ptr(), _capi.ptr(target_cov), S, source.data_ptr(),
-                     _capi.ptr(source_cov), pose.data_ptr(), params, scratch.data_ptr(), pose.data_ptr(),
-                     qt.data_ptr() if last else None, qt[4:].data_ptr() if last else None, stats[k].data_ptr(),
-                     _capi.ptr(idx) if last else None, _capi.ptr(flags) if last else None)
-    return GicpResult(pose, qt[:4], qt[4:7], stats, idx, flags)
+                     _capi.ptr(source_cov), chain.pose.data_ptr(), params, scratch.data_ptr(), *chain.tail(k))
+    return chain.result(GicpResult)

@@ -6,9 +6,8 @@ from typing import NamedTuple as _NamedTuple
 import torch
 
 from . import _capi
+from ._align import INF, _Chain, _pose, _scalars, _step_scratch
 from .losses import _check_gpu
-
-INF = float("inf")
 
 
 class IcpResult(_NamedTuple):
@@ -36,32 +35,6 @@ def _image(what, name, t, shape=None):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"{what}: {name} {tuple(t.shape)} is not [H,W] = {tuple(shape)}")
     return t
-
-
-def _pose(what, name, t):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{what}: {name} must be a tensor, not {type(t).__name__}")
-    if t.dtype != torch.float32:
-        raise ValueError(f"{what}: {name} must be float32, not {t.dtype}")
-    if tuple(t.shape) != (4, 4):
-        raise ValueError(f"{what}: {name} is [4,4] (W2C^T), not {tuple(t.shape)}")
-    return t
-
-
-def _scalars(what, fx, fy, **named):
-    """floats, none of them NaN, fx and fy finite and positive, every name of `named` given as (value, lowest allowed or None)"""
-    out = dict(fx=float(fx), fy=float(fy))
-    out.update({n: float(v[0]) for n, v in named.items()})
-    for n, v in out.items():
-        if v != v:
-            raise ValueError(f"{what}: {n} must not be NaN")
-    for n in ("fx", "fy"):
-        if not 0.0 < out[n] < INF:
-            raise ValueError(f"{what}: {n} must be finite and positive, not {out[n]}")
-    for n, (_, lowest) in named.items():
-        if lowest is not None and out[n] < lowest:
-            raise ValueError(f"{what}: {n} must not be {'negative' if lowest == 0.0 else f'below {lowest}'}, not {out[n]}")
-    return out
 
 
 def _depth_range(what, depth_range):
@@ -103,14 +76,6 @@ def depth_normals(depth, fx, fy, cx, cy, *, depth_range=(0.0, INF), max_jump=0.1
     return vnmap
 
 
-def _step_scratch(what, W, H, strides, dev):
-    """one zero-filled scratch that serves every stride of `strides` (the ticket at its start is left at zero by every step)"""
-    sizes = [_capi.load().dgr_icp_scratch_bytes(W, H, s) for s in sorted(set(strides))]
-    if not all(sizes):
-        raise ValueError(f"{what}: cannot take a {W} x {H} frame at strides {sorted(set(strides))} (below 2^30 candidates)")
-    return torch.zeros((max(sizes),), dtype=torch.uint8, device=dev)
-
-
 def icp_step(depth_obs, vn_obs, vn_model, model_viewmatrix, viewmatrix_in, fx, fy, cx, cy, *, viewmatrix_out=None, stride=1,
              depth_range=(0.0, INF), dist_max=0.1, normal_cos_min=0.8, huber_delta=INF, damping=0.0, rcond=1e-8, min_points=6,
              return_flags=False, scratch=None):
@@ -131,20 +96,14 @@ def icp_step(depth_obs, vn_obs, vn_model, model_viewmatrix, viewmatrix_in, fx, f
     _check_gpu(what, depth_obs, model_viewmatrix, viewmatrix_in, *(t for _, t in maps))
     dev = depth_obs.device
     depth_obs, model_viewmatrix, viewmatrix_in = depth_obs.detach().contiguous(), model_viewmatrix.contiguous(), viewmatrix_in.contiguous()
-    out = torch.empty((4, 4), dtype=torch.float32, device=dev) if viewmatrix_out is None else viewmatrix_out
-    if not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (4, 4) and out.is_contiguous()):
-        raise ValueError(f"{what}: viewmatrix_out must be a contiguous float32 GPU tensor [4,4]")
-    qt = torch.empty((8,), dtype=torch.float32, device=dev)
-    stats = torch.empty((1, 32), dtype=torch.float64, device=dev)
     S = -(-W // stride[0]) * -(-H // stride[0])
-    flags = torch.empty((S,), dtype=torch.uint8, device=dev) if return_flags else None
+    chain = _Chain(torch, what, dev, 1, 32, out=viewmatrix_out, out_name="viewmatrix_out", flags=S if return_flags else None)
     if scratch is None:
-        scratch = _step_scratch(what, W, H, stride, dev)
+        scratch = _step_scratch(torch, what, "dgr_icp_scratch_bytes", W, H, stride, dev)
     params = _params(s, lo, hi, min_points, stride[0])
     _capi.call("dgr_icp_step", dev, W, H, depth_obs.data_ptr(), _capi.ptr(vn_obs), vn_model.data_ptr(), model_viewmatrix.data_ptr(),
-               viewmatrix_in.data_ptr(), params, scratch.data_ptr(), out.data_ptr(), qt.data_ptr(), qt[4:].data_ptr(),
-               stats.data_ptr(), _capi.ptr(flags))
-    return IcpResult(out, qt[:4], qt[4:7], stats, flags)
+               viewmatrix_in.data_ptr(), params, scratch.data_ptr(), *chain.tail(0))
+    return chain.result(IcpResult)
 
 
 def _step_arguments(what, fx, fy, cx, cy, depth_range, dist_max, normal_cos_min, huber_delta, damping, rcond, min_points, strides):
@@ -213,21 +172,15 @@ def icp_align(depth_obs, model_depth, viewmatrix, model_viewmatrix, fx, fy, cx, 
         opacity_map = opacity_map.detach().contiguous()
     model_viewmatrix = model_viewmatrix.detach().contiguous()
     maps = torch.empty((2 if use_obs_normals else 1, H, W, 4), dtype=torch.float32, device=dev)
-    pose = torch.empty((4, 4), dtype=torch.float32, device=dev)
-    pose.copy_(viewmatrix.detach())
-    qt = torch.empty((8,), dtype=torch.float32, device=dev)
-    stats = torch.empty((iterations, 32), dtype=torch.float64, device=dev)
     S = -(-W // strides[-1]) * -(-H // strides[-1])
-    flags = torch.empty((S,), dtype=torch.uint8, device=dev) if return_flags else None
-    scratch = _step_scratch(what, W, H, strides, dev)
+    chain = _Chain(torch, what, dev, iterations, 32, first=viewmatrix, flags=S if return_flags else None)
+    scratch = _step_scratch(torch, what, "dgr_icp_scratch_bytes", W, H, strides, dev)
     with _capi.StepCalls(dev) as abi:
         _normals_into(abi, maps[0], model_depth, opacity_map, s, lo, hi)
         if use_obs_normals:
             _normals_into(abi, maps[1], depth_obs, None, s, lo, hi)
         for k, stride in enumerate(strides):
-            last = k == iterations - 1
             abi.call("dgr_icp_step", W, H, depth_obs.data_ptr(), maps[1].data_ptr() if use_obs_normals else None,
-                     maps[0].data_ptr(), model_viewmatrix.data_ptr(), pose.data_ptr(), _params(s, lo, hi, min_points, stride),
-                     scratch.data_ptr(), pose.data_ptr(), qt.data_ptr() if last else None, qt[4:].data_ptr() if last else None,
-                     stats[k].data_ptr(), _capi.ptr(flags) if last else None)
-    return IcpResult(pose, qt[:4], qt[4:7], stats, flags)
+                     maps[0].data_ptr(), model_viewmatrix.data_ptr(), chain.pose.data_ptr(), _params(s, lo, hi, min_points, stride),
+                     scratch.data_ptr(), *chain.tail(k))
+    return chain.result(IcpResult)

@@ -7,7 +7,8 @@ from typing import NamedTuple as _NamedTuple
 import torch
 
 from . import _capi
-from .icp import INF, _depth_range, _image, _normals_into, _pose, _scalars, _step_arguments
+from ._align import INF, _Chain, _pose, _scalars, _step_scratch
+from .icp import _depth_range, _image, _normals_into, _step_arguments
 from .losses import _check_gpu
 
 
@@ -144,14 +145,6 @@ def _params(s, lo, hi, min_points, stride, ph, intr=None):
                             min_points, stride, ph["geo_weight"], ph["photo_weight"], ph["photo_max"], ph["photo_huber"])
 
 
-def _step_scratch(what, W, H, strides, dev):
-    """one zero-filled scratch that serves every stride of `strides` (the ticket at its start is left at zero by every step)"""
-    sizes = [_capi.load().dgr_rgbd_scratch_bytes(W, H, s) for s in sorted(set(strides))]
-    if not all(sizes):
-        raise ValueError(f"{what}: cannot take a {W} x {H} frame at strides {sorted(set(strides))} (below 2^30 candidates)")
-    return torch.zeros((max(sizes),), dtype=torch.uint8, device=dev)
-
-
 def rgbd_step(depth_obs, vn_obs, vn_model, intensity_obs, imap_model, model_viewmatrix, viewmatrix_in, fx, fy, cx, cy, *,
               viewmatrix_out=None, stride=1, depth_range=(0.0, INF), dist_max=0.1, normal_cos_min=0.8, huber_delta=INF,
               geo_weight=1.0, photo_weight=1.0, photo_max=INF, photo_huber=INF, damping=0.0, rcond=1e-8, min_points=6,
@@ -176,19 +169,14 @@ def rgbd_step(depth_obs, vn_obs, vn_model, intensity_obs, imap_model, model_view
     dev = depth_obs.device
     depth_obs, intensity_obs = depth_obs.detach().contiguous(), intensity_obs.detach().contiguous()
     model_viewmatrix, viewmatrix_in = model_viewmatrix.contiguous(), viewmatrix_in.contiguous()
-    out = torch.empty((4, 4), dtype=torch.float32, device=dev) if viewmatrix_out is None else viewmatrix_out
-    if not (out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (4, 4) and out.is_contiguous()):
-        raise ValueError(f"{what}: viewmatrix_out must be a contiguous float32 GPU tensor [4,4]")
-    qt = torch.empty((8,), dtype=torch.float32, device=dev)
-    stats = torch.empty((1, 40), dtype=torch.float64, device=dev)
     S = -(-W // stride[0]) * -(-H // stride[0])
-    flags = torch.empty((S,), dtype=torch.uint8, device=dev) if return_flags else None
+    chain = _Chain(torch, what, dev, 1, 40, out=viewmatrix_out, out_name="viewmatrix_out", flags=S if return_flags else None)
     if scratch is None:
-        scratch = _step_scratch(what, W, H, stride, dev)
+        scratch = _step_scratch(torch, what, "dgr_rgbd_scratch_bytes", W, H, stride, dev)
     _capi.call("dgr_rgbd_step", dev, W, H, depth_obs.data_ptr(), _capi.ptr(vn_obs), vn_model.data_ptr(), intensity_obs.data_ptr(),
                imap_model.data_ptr(), model_viewmatrix.data_ptr(), viewmatrix_in.data_ptr(), _params(s, lo, hi, min_points, stride[0], ph),
-               scratch.data_ptr(), out.data_ptr(), qt.data_ptr(), qt[4:].data_ptr(), stats.data_ptr(), _capi.ptr(flags))
-    return RgbdResult(out, qt[:4], qt[4:7], stats, flags)
+               scratch.data_ptr(), *chain.tail(0))
+    return chain.result(RgbdResult)
 
 
 def _level_plan(what, W, H, levels, iterations, strides):
@@ -257,13 +245,9 @@ def rgbd_align(color_obs, depth_obs, model_color, model_depth, viewmatrix, model
     # one arena for every level's images: per level 3 mean planes (I_obs, I_model, the silhouette), 2 depths, 3 packed maps
     sizes = [(H >> level, W >> level) for level in range(levels)]
     arena = torch.empty((sum(-(-17 * h * w // 4) * 4 for h, w in sizes),), dtype=torch.float32, device=dev)
-    pose = torch.empty((4, 4), dtype=torch.float32, device=dev)
-    pose.copy_(viewmatrix.detach())
-    qt = torch.empty((8,), dtype=torch.float32, device=dev)
-    stats = torch.empty((len(order), 40), dtype=torch.float64, device=dev)
     S = -(-W // strides[-1]) * -(-H // strides[-1])
-    flags = torch.empty((S,), dtype=torch.uint8, device=dev) if return_flags else None
-    scratch = _step_scratch(what, W, H, [1], dev)  # (the finest level at stride 1: the largest grid any iteration has)
+    chain = _Chain(torch, what, dev, len(order), 40, first=viewmatrix, flags=S if return_flags else None)
+    scratch = _step_scratch(torch, what, "dgr_rgbd_scratch_bytes", W, H, [1], dev)  # (the finest level at stride 1: the largest grid any iteration has)
     frames, at = [], 0
     for h, w in sizes:
         n = h * w
@@ -299,11 +283,9 @@ def rgbd_align(color_obs, depth_obs, model_color, model_depth, viewmatrix, model
             if use_obs_normals:
                 _normals_into(abi, f["maps"][1], f["depth_obs"], None, sl, lo, hi)
             while k < len(order) and order[k] == level:
-                last = k == len(order) - 1
                 abi.call("dgr_rgbd_step", w, h, f["depth_obs"].data_ptr(), f["maps"][1].data_ptr() if use_obs_normals else None,
                          f["maps"][0].data_ptr(), f["obs"].data_ptr(), f["maps"][2].data_ptr(), model_viewmatrix.data_ptr(),
-                         pose.data_ptr(), _params(s, lo, hi, min_points, strides[k], ph, intr), scratch.data_ptr(), pose.data_ptr(),
-                         qt.data_ptr() if last else None, qt[4:].data_ptr() if last else None, stats[k].data_ptr(),
-                         _capi.ptr(flags) if last else None)
+                         chain.pose.data_ptr(), _params(s, lo, hi, min_points, strides[k], ph, intr), scratch.data_ptr(),
+                         *chain.tail(k))
                 k += 1
-    return RgbdResult(pose, qt[:4], qt[4:7], stats, flags)
+    return chain.result(RgbdResult)

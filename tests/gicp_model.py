@@ -301,31 +301,11 @@ def gicp_step_model(target, target_cov, source, source_cov, T, *, dist_max=INF, 
     return dict(q=q32, idx=idx.astype(np.int32), flags=flags, terms=terms, mags=mags, used=used, cond_max=cond_max, sums=sums, S=S)
 
 
-def solve_update(sums29, T_in, *, damping=0.0, rcond=1e-8, min_points=6, mutate=None):
-    """The finisher in float64: dgr_icp_step's solve and refusals, the update T_out = exp(xi) T_in.  Returns icp_model.solve_update's
+def solve_update(sums29, T_in, *, mutate=None, **kw):
+    """The finisher in float64: icp_model.solve (its keywords), the update T_out = exp(xi) T_in.  Returns icp_model.solve_update's
     dict (`viewmatrix` is the motion, float32 [4,4]), so that icp_model.pose_figures and pose_holds apply.
     `mutate`: "right_update" (T_in exp(xi): a deliberately wrong model)."""
-    sums29 = np.asarray(sums29, np.float64)
-    A, b, _, count = im.unpack(sums29)
-    damping, rcond = f32(damping), f32(rcond)
-    ok = count >= min_points and bool(np.all(np.isfinite(sums29[:28])))
-    diag = np.diag(A).copy()
-    max_diag = max(0.0, float(diag.max())) if ok else 0.0
-    M = A + damping * np.diag(np.maximum(diag, im.DAMPING_FLOOR * max_diag))
-    L, D, xi = np.eye(6), np.zeros(6), np.zeros(6)
-    with np.errstate(all="ignore"):
-        for j in range(6):
-            D[j] = M[j, j] - np.sum(L[j, :j] ** 2 * D[:j])
-            ok = ok and bool(D[j] > rcond * max_diag and D[j] > 0.0)
-            for i in range(j + 1, 6):
-                L[i, j] = (M[i, j] - np.sum(L[i, :j] * L[j, :j] * D[:j])) / D[j]
-        if ok:
-            xi = np.linalg.solve(L.T, np.linalg.solve(L, -b) / D)
-            ok = bool(np.all(np.isfinite(xi)))
-        eig = np.linalg.eigvalsh(A) if np.all(np.isfinite(A)) else np.array([0.0, 1.0])
-        cond = float(eig[-1] / eig[0]) if eig[0] > 0 else INF
-        eig = np.linalg.eigvalsh(M) if np.all(np.isfinite(M)) else np.array([0.0, 1.0])
-        cond_solved = float(eig[-1] / eig[0]) if eig[0] > 0 else INF
+    ok, xi, cond, cond_solved = im.solve(sums29, **kw)
     Ri, ti = motion_of(T_in)
     T_in = np.asarray(T_in, np.float32).reshape(4, 4)
     if ok:
@@ -334,7 +314,6 @@ def solve_update(sums29, T_in, *, damping=0.0, rcond=1e-8, min_points=6, mutate=
         quat, branch = im.rotation_to_quat(Ro), im.quat_branch(Ro)
         out, trans = as_transform(im.quat_to_rotation(quat), to), to.astype(np.float32)
     else:
-        xi = np.zeros(6)
         quat, branch, out, trans = im.rotation_to_quat(Ri), im.quat_branch(Ri), T_in.copy(), T_in[3, :3].copy()
     return dict(ok=ok, xi=xi, cond=cond, cond_solved=cond_solved, viewmatrix=out, quat=quat.astype(np.float32), trans=trans,
                 omega=float(np.linalg.norm(xi[:3])), v=float(np.linalg.norm(xi[3:])), branch=branch)

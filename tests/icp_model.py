@@ -452,12 +452,12 @@ def unpack(sums29):
     return A, np.asarray(sums29[21:27], np.float64), float(sums29[27]), float(sums29[28])
 
 
-def solve_update(sums29, model_view, view_in, *, damping=0.0, rcond=1e-8, min_points=6, mutate=None):
-    """The finisher in float64: the solve by LDL^T, the refusals, the update.  Returns a dict: ok, xi [6], cond (of A; inf when
-    singular), cond_solved (of the damped matrix the solve factorises), viewmatrix float32 [4,4], quat float32 [4], trans float32 [3], omega, v (the norms; 0 when refused),
-    branch (Shepperd's, of the rotation whose quaternion is returned).  `mutate`: one of POSE_MUTANTS, the deliberately wrong
-    finishers (rotation_to_quat's and se3_exp's)."""
-    A, b, _, count = unpack(np.asarray(sums29, np.float64))
+def solve(sums29, *, damping=0.0, rcond=1e-8, min_points=6):
+    """The finisher's solve in float64, the one every pose step's model uses: M xi = -b by LDL^T, M = A damped, and the refusals.
+    Returns ok, xi [6] (zeros when refused), cond (of A; inf when singular), cond_solved (of the damped matrix the solve
+    factorises)."""
+    sums29 = np.asarray(sums29, np.float64)
+    A, b, _, count = unpack(sums29)
     damping, rcond = f32(damping), f32(rcond)
     ok = count >= min_points and bool(np.all(np.isfinite(sums29[:28])))
     diag = np.diag(A).copy()
@@ -479,6 +479,15 @@ def solve_update(sums29, model_view, view_in, *, damping=0.0, rcond=1e-8, min_po
         cond = float(eig[-1] / eig[0]) if eig[0] > 0 else INF
         eig = np.linalg.eigvalsh(M) if np.all(np.isfinite(M)) else np.array([0.0, 1.0])
         cond_solved = float(eig[-1] / eig[0]) if eig[0] > 0 else INF
+    return ok, xi if ok else np.zeros(6), cond, cond_solved
+
+
+def solve_update(sums29, model_view, view_in, *, mutate=None, **kw):
+    """The finisher in float64: `solve` (its keywords), the update.  Returns a dict: ok, xi [6], cond, cond_solved (solve's),
+    viewmatrix float32 [4,4], quat float32 [4], trans float32 [3], omega, v (the norms; 0 when refused),
+    branch (Shepperd's, of the rotation whose quaternion is returned).  `mutate`: one of POSE_MUTANTS, the deliberately wrong
+    finishers (rotation_to_quat's and se3_exp's)."""
+    ok, xi, cond, cond_solved = solve(sums29, **kw)
     Ri, ti = pose_of(view_in)
     view_in = np.asarray(view_in, np.float32).reshape(4, 4)
     if ok:
@@ -490,7 +499,6 @@ def solve_update(sums29, model_view, view_in, *, damping=0.0, rcond=1e-8, min_po
         quat, branch = rotation_to_quat(Ro, mutate), quat_branch(Ro)
         view, trans = w2ct(quat_to_rotation(quat), to), to.astype(np.float32)
     else:
-        xi = np.zeros(6)
         quat, branch, view, trans = rotation_to_quat(Ri, mutate), quat_branch(Ri), view_in.copy(), view_in[3, :3].copy()
     return dict(ok=ok, xi=xi, cond=cond, cond_solved=cond_solved, viewmatrix=view, quat=quat.astype(np.float32), trans=trans,
                 omega=float(np.linalg.norm(xi[:3])), v=float(np.linalg.norm(xi[3:])), branch=branch)

@@ -105,7 +105,7 @@ def run_step(s, stride, with_obs=True, weights=(1.0, 1.0), hubers=(INF, INF), **
 
 
 STEP_CASES = [(W, H, st, w, h) for W, H, st in ((3, 3, 1), (67, 5, 1), (67, 5, 3), (96, 80, 1), (640, 480, 4)) for w in WEIGHTS
-              for h in HUBERS]
+              for h in HUBERS] + [(256, 520, 1, WEIGHTS[0], HUBERS[0])]  # (65 blocks: the finisher's second trip through its LDS)
 
 
 def check_step(out, m, s, label, weights=(1.0, 1.0), **solve):
