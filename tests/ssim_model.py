@@ -8,7 +8,8 @@
 
 `model(..., dtype=torch.float64)` is the model the tests measure distances from; the same lines in float32 (the 121-tap window
 applied directly by `F.conv2d`) are the YARDSTICK: how far a float32 evaluation of this loss lies from the model.
-`analytic_grad` is the three-map form of dSSIM/dx the backward kernel evaluates."""
+`maps` are the three derivative maps the forward kernel leaves in its scratch and `analytic_grad` the form of dSSIM/dx the
+backward kernel evaluates from them.  The edge cases of tests/test_hip_ssim_edges.py are defined at the end."""
 import math
 
 import torch
@@ -66,23 +67,107 @@ def model(x, y, depth=None, depth_obs=None, w_l1=0.0, w_ssim=-1.0, w_depth=0.0, 
     return dict(loss=loss.detach(), ssim=ssim.detach(), grad=x.grad, grad_depth=None if d is None else d.grad, m=m.detach())
 
 
-def analytic_grad(x, y, dtype=torch.float64):
-    """dSSIM/dx in the three-map form: with A, B the numerator and Cc, D the denominator factors of m,
-        dm/ds1 = -m / D,  dm/ds12 = 2A / (Cc D),  dm/dmu1 = 2 mu2 B / (Cc D) - 2 mu1 m / Cc - 2 mu1 dm/ds1 - mu2 dm/ds12
-        dSSIM/dx = [w*(dm/dmu1) + 2x w*(dm/ds1) + y w*(dm/ds12)] / N
-    (the window is symmetric: the same zero-padded correlation serves forward and backward)."""
+def maps(x, y, dtype=torch.float64):
+    """The three derivative maps the forward kernel leaves for the backward, (dm/dmu1, dm/ds1, dm/ds12), each [V, C, H, W] in
+    `dtype`: with A, B the numerator and Cc, D the denominator factors of m,
+        dm/ds1 = -m / D,  dm/ds12 = 2A / (Cc D),  dm/dmu1 = 2 mu2 B / (Cc D) - 2 mu1 m / Cc - 2 mu1 dm/ds1 - mu2 dm/ds12"""
     x, y = _as_stack(x, dtype), _as_stack(y, dtype)
-    w, mu1, mu2, s1, s2, s12 = _moments(x, y)
+    _, mu1, mu2, s1, s2, s12 = _moments(x, y)
     A, B, Cc, D = 2 * mu1 * mu2 + C1, 2 * s12 + C2, mu1 * mu1 + mu2 * mu2 + C1, s1 + s2 + C2
     m = A * B / (Cc * D)
     dm_ds1 = -m / D
     dm_ds12 = 2 * A / (Cc * D)
     dm_dmu1 = 2 * mu2 * B / (Cc * D) - 2 * mu1 * m / Cc - 2 * mu1 * dm_ds1 - mu2 * dm_ds12
+    return dm_dmu1, dm_ds1, dm_ds12
+
+
+def grad_from_maps(x, y, three, dtype=torch.float64):
+    """dSSIM/dx = [w*(dm/dmu1) + 2x w*(dm/ds1) + y w*(dm/ds12)] / N from the three maps (the window is symmetric: the same
+    zero-padded correlation serves forward and backward)."""
+    x, y = _as_stack(x, dtype), _as_stack(y, dtype)
+    w = _window_2d(x.shape[1], dtype)
+    dm_dmu1, dm_ds1, dm_ds12 = (t.to(dtype) for t in three)
     return (_conv(dm_dmu1, w) + 2 * x * _conv(dm_ds1, w) + y * _conv(dm_ds12, w)) / x.numel()
+
+
+def analytic_grad(x, y, dtype=torch.float64):
+    """dSSIM/dx in the three-map form the backward kernel evaluates: `maps` recombined by `grad_from_maps`."""
+    return grad_from_maps(x, y, maps(x, y, dtype), dtype)
+
+
+def placed(canvas_hw, patch, oy, ox, background=(0.5, 0.4)):
+    """(img, ref) float32 [1, 1, H, W]: constant canvases of `background` with the patch pair `patch` = (px, py), two [h, w]
+    tensors, written at rows oy .. oy + h, columns ox .. ox + w."""
+    out = []
+    for p, level in zip(patch, background):
+        canvas = torch.full((1, 1) + tuple(canvas_hw), level, dtype=torch.float32)
+        canvas[0, 0, oy:oy + p.shape[0], ox:ox + p.shape[1]] = p
+        out.append(canvas)
+    return tuple(out)
+
+
+def tiles_of(shape):
+    """workgroups of the tile kernels for a (V, C, H, W) stack: one per 32 x 16 tile of every plane"""
+    V, C, H, W = shape
+    return V * C * ((H + 15) // 16) * ((W + 31) // 32)
 
 
 SHAPES = ((1, 3, 7, 9), (1, 1, 16, 16), (2, 3, 17, 33), (1, 3, 37, 53), (4, 3, 48, 64), (1, 3, 144, 192))
 KINDS = ("rand", "smooth", "flatbright")
+
+# ---- the edge cases of tests/test_hip_ssim_edges.py (their defining conditions are asserted in tests/test_ssim_abi.py) ----
+# one tile exactly, one over in each direction, a single pixel / row / column, images smaller than the window, an odd height
+EDGE_SHAPES = ((1, 1, 16, 32), (1, 1, 17, 32), (1, 1, 16, 33), (1, 1, 1, 1), (1, 2, 1, 45), (2, 1, 45, 1), (1, 3, 5, 11),
+               (1, 3, 11, 5), (2, 2, 37, 53))
+# "same": ref == img (gradient 0 analytically); "const": constant planes (sigma = 0, D = C2 away from the border)
+EDGE_KINDS = KINDS + ("same", "const")
+# the one-workgroup sum adds the tiles' slots 256 at a time: tile counts below, at and past one trip
+TILE_SHAPES = ((255, 1, 3, 3), (256, 1, 3, 3), (257, 1, 3, 3), (65, 4, 1, 1), (3, 3, 97, 161))
+FINAL_THREADS = 256
+# the depth term's sum is a grid-stride loop over 128 x 256 threads
+DEPTH_COUNTS = (32767, 32768, 32769, 65537)
+DEPTH_THREADS = 128 * 256
+# the largest shapes dgr_ssim_scratch_floats accepts
+LIMIT_SHAPES = ((65535, 1, 1, 1), (1, 1, 1 << 20, 1), (1, 1, 1, 1 << 20))
+# the tile-phase scene: a 13 x 19 patch pair on a constant canvas, its corner at (20 + dy, 20 + dx)
+CANVAS_HW, PATCH_HW, PATCH_ORIGIN, MARGIN = (68, 90), (13, 19), (20, 20), 10
+PHASES = ([(0, dx) for dx in range(32)] + [(dy, 0) for dy in range(1, 16)]
+          + [(1, 1), (15, 31), (7, 13), (8, 16), (15, 1), (1, 31), (11, 29), (5, 22)])
+
+
+def edge_inputs(kind, shape, seed=0):
+    """(x, y) for EDGE_KINDS: `inputs` for the model's three kinds; "same": y is x; "const": one level per plane and image."""
+    if kind in KINDS:
+        return inputs(kind, shape, seed)
+    g = torch.Generator().manual_seed(5000 + 7 * sum(shape) + seed)
+    if kind == "same":
+        x = torch.rand(shape, generator=g, dtype=torch.float32)
+        return x, x.clone()
+    if kind == "const":
+        a = 0.2 + 0.7 * torch.rand(shape[:2] + (1, 1), generator=g, dtype=torch.float32)
+        b = 0.2 + 0.7 * torch.rand(shape[:2] + (1, 1), generator=g, dtype=torch.float32)
+        return a.expand(shape).contiguous(), b.expand(shape).contiguous()
+    raise ValueError(kind)
+
+
+def patch_pair(seed=0):
+    g = torch.Generator().manual_seed(7000 + seed)
+    return torch.rand(PATCH_HW, generator=g, dtype=torch.float32), torch.rand(PATCH_HW, generator=g, dtype=torch.float32)
+
+
+def depth_pair(n_depth, variant, seed=0):
+    """(d, d_obs, special) float32 [n_depth]: |d - d_obs| below 0.5 everywhere but at `special` = the indices DEPTH_THREADS - 1,
+    DEPTH_THREADS (where they exist) and n_depth - 1, the last element of the loop's first trip, the first of its second and the
+    last of all.  variant "ties": d == d_obs there; "peaks": d - d_obs = +-8 there, so that one dropped or doubled element
+    moves the mean by 8 / n_depth."""
+    g = torch.Generator().manual_seed(9000 + n_depth + seed)
+    d_obs = 1.0 + torch.rand(n_depth, generator=g, dtype=torch.float32)
+    d = d_obs + (torch.rand(n_depth, generator=g, dtype=torch.float32) - 0.5)
+    special = sorted({i for i in (DEPTH_THREADS - 1, DEPTH_THREADS, n_depth - 1) if i < n_depth})
+    for k, i in enumerate(special):
+        d_obs[i] = 1.5  # (so that d - d_obs is 8 exactly)
+        d[i] = d_obs[i] if variant == "ties" else d_obs[i] + (8.0 if k % 2 == 0 else -8.0)
+    return d, d_obs, special
 
 
 def inputs(kind, shape, seed=0):
